@@ -16,6 +16,7 @@ Objects in the line besides the contract's fields:
                 box's host cores on BASELINE config 1 (B=4, 16-step Euler), rank 0 at N=1 only
   secondary     the other BASELINE numbers on the same box: Euler with CFG, "100-step" RK4 with CFG at config 3's per-GPU share,
                 SD-VAE decode (its own roofline entry) / encode, decoded images/s  (N=1: all; N>1: the RK4 share only)
+  dump_outputs  with --dump-outputs DIR: the arrays written there (see dump_outputs below)
 """
 from __future__ import annotations
 
@@ -38,7 +39,7 @@ if not os.environ.get("FLOCODER_AMD_KEEP_ENV"):
 
 import torch  # noqa: E402
 
-PEAK_FP32_MFMA_TFLOPS = 157.3     # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)"
+PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X (gfx950) peak FP32 matrix rate
 N_EULER, BATCH, LATENT, DIM, NCLS = 64, 64, (4, 32, 32), 32, 102
 RK4_STEPS, RK4_SHARE, CFG = 100, 32, 3.0          # BASELINE configs[2]: 100-"step" RK4, B=256 over 8 GPUs = 32 per GPU, cfg_strength 3.0
 DECODE_CHUNK = 16
@@ -265,6 +266,25 @@ def headline_parity(model, out, noise, ids):
     return {"rel_l2": float(f"{rel:.3e}"), "gate": PARITY_GATE, "ok": bool(rel < PARITY_GATE), "rows": PARITY_ROWS,
             "against": f"oracle.flow_oracle.euler_sampler, {N_EULER} steps, rows 0..{PARITY_ROWS - 1} of the last timed step",
             "max_abs_diff": float((got.double() - want.double()).abs().max())}
+
+
+def dump_outputs(out_dir, out, world):
+    """--dump-outputs DIR: what the timed path returned in its LAST timed step, as DIR/<name>.npy, so that two builds can be compared
+    output for output.  The inputs are seeded (synthetic_inputs, build_model), so the same arguments give the same inputs in every run.
+    `latents`: the final latents of the 64-step Euler sampler, float32 [64 x n_gpus, 4, 32, 32] (1 MiB per GPU), all ranks' shards
+    gathered in global sample order.  Collective: every rank calls it; rank 0 writes.  Returns {name: shape} on rank 0, else None."""
+    import numpy as np
+    from flocoder_amd.dist import gather_samples
+    arrays = {"latents": gather_samples(out.contiguous(), BATCH * world)}
+    if torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        a = a.detach().to("cpu", torch.float32).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 # --------------------------------------------------------------------------------------------------- secondary numbers
@@ -608,9 +628,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output arrays to DIR/<name>.npy (float32)")
     ap.add_argument("--secondary-only", action="store_true", help="(internal) run the one-GPU secondary legs and print their JSON: the main run "
                     "starts this in a child process, so that nothing in them can cost the headline line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.secondary_only:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -685,6 +708,7 @@ def main():
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
     model.check_errors()                             # (every euler_sampler call above checked already: Unet.integrate(check=True))
+    dumped = dump_outputs(args.dump_outputs, out, world) if args.dump_outputs else None
     last_noise, last_ids = variants[(calls["n"] - 1) % len(variants)]
     parity = headline_parity(model, out, last_noise, last_ids) if rank == 0 else None     # the timed configuration's own output against the CPU oracle
     assert model.fused_tail_errors() == 0, "a fused Block tail timed out waiting for its sample group: results invalid"
@@ -707,6 +731,8 @@ def main():
                    "plan": "exclusive device (cross-workgroup Block tails)" if model.meeting_launches else "shared device (no cross-workgroup waits)",
                    "runtime_env": {k: os.environ.get(k) for k in ("AMD_DIRECT_DISPATCH", "FLOCODER_AMD_KEEP_ENV") if os.environ.get(k) is not None}},
     }
+    if dumped:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "dtype": "float32"}
     if parity:
         line["parity_rel_l2"] = parity["rel_l2"]
         line["parity"] = parity

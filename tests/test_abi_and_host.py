@@ -107,3 +107,13 @@ def test_bench_starts_its_own_ranks_and_refuses_without_gpus():
     assert r.returncode == 2 and "--gpus 2 but this node shows" in r.stderr, (r.returncode, r.stderr[-500:])
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "torch.distributed.run" in src and "launch_ranks" in src
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` is divided by it: zero steps (or a negative warm-up) is a usage error, before
+    anything touches a GPU."""
+    import subprocess
+    import sys
+    for args in (["--steps", "0"], ["--steps", "2", "--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, (args, r.returncode, r.stderr[-500:])

@@ -5,13 +5,17 @@
   (b) the SD-VAE alone at 256x256 <-> 4x32x32 -- the shapes whose plan picks the M256N64 tile and gn_fold;
   (c) the DEFAULT plan at B=64 (no debug switch): rows 0-7 against the oracle, and the launch list is the one bench.py times;
   (d) "100-step" RK4 (99 intervals, 396 evaluations) with CFG 3.0 on the dim-32 model: error growth over BASELINE config 3's length;
-  (e) decode_latents with chunk_size < batch (sampling.py:169-183).
+  (e) decode_latents with chunk_size < batch (sampling.py:169-183);
+  (f) bench.py --dump-outputs: the arrays it writes are the last timed step's latents, and the line counts the steps it was given.
 
 Tolerances: single forward rel-L2 <= 2e-5; trajectories <= 2e-4 (64 evaluations) / 1e-3 (396 evaluations with CFG); decoded images
 <= 1e-3 (north_star).  The SD-VAE oracle is PARITY UNPINNED (diffusers + weights absent): those cases are GPU <-> own restatement."""
+import json
 import os
+import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -145,3 +149,29 @@ def test_e_decode_latents_in_chunks(sdvae):
     assert rel_l2(parts.cpu(), vo.decode(vsd, z)) < 2e-4
     one = S.decode_latents(codec, z.to(DEV), chunk_size=1)
     assert rel_l2(one.cpu(), whole.cpu()) < 1e-6
+
+
+@pytest.mark.skipif(os.environ.get("FLOCODER_AMD_IN_CHILD_SUITE") == "1", reason="already inside the child suite")
+def test_f_bench_dumps_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` (a child process, as it is run): DIR holds latents.npy, float32 [64, 4, 32, 32], the output of the LAST
+    timed step -- its row 0 is the oracle's 64-step trajectory of that step's input (bench.py takes four seeded variants of its batch in
+    turn) -- and the result line reports the number of timed steps it was given and the milliseconds one of them took."""
+    sys.path.insert(0, ROOT)
+    import bench
+    steps, warmup = 3, 1
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--no-secondary", "--no-roofline", "--cpu-baseline", "none", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-1500:])
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert line["dump_outputs"]["arrays"] == {"latents": [bench.BATCH, *bench.LATENT]}
+    assert sorted(os.listdir(out_dir)) == ["latents.npy"]
+    lat = np.load(out_dir / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (bench.BATCH, *bench.LATENT) and np.isfinite(lat).all()
+    noise, ids = bench.synthetic_inputs(0, 1, "cpu")
+    k = (warmup + steps - 1) % 4                                           # the variant the last timed step integrated
+    sd = {n: v.detach() for n, v in bench.build_model("cpu").state_dict().items()}
+    ref, _ = fo.euler_sampler(sd, noise.roll(k, 0)[:1], bench.N_EULER, ids.roll(k, 0)[:1])
+    assert rel_l2(torch.from_numpy(lat[:1]), ref) < 2e-4
