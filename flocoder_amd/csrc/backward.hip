@@ -278,15 +278,14 @@ int gn_bwd_chunks(int HW) { return (HW + kGnChunk - 1) / kGnChunk; }
 int gn_bwd_launch(const GnBwdArgs& a, hipStream_t s) {
     if (a.C & 3) return fail(FC_E_SHAPE, "gn_bwd: C must be a multiple of 4");
     if (!a.xf.mode || !a.xf.stats || !a.s12 || !a.s12p || !a.dh) return fail(FC_E_ARG, "gn_bwd: needs statistics and workspaces");
-    static const bool no_small = std::getenv("FLOCODER_AMD_GN_BWD_SPLIT") != nullptr;
-    if (!no_small && a.HW * a.C <= 8192 && (a.C & (a.C - 1)) == 0 && a.C <= 1024 && a.C % a.xf.G == 0) {
+    if (a.HW * a.C <= 8192 && (a.C & (a.C - 1)) == 0 && a.C <= 1024 && a.C % a.xf.G == 0) {
         const size_t lds = (size_t)(4 * a.xf.G + 5 * a.C + 2048) * sizeof(float);
         hipLaunchKernelGGL(gn_bwd_small_kernel<256>, dim3(a.B), dim3(256), lds, s, a);
         FC_HIP(hipGetLastError());
         return FC_OK;
     }
     // up to 32768 elements per sample (32 channels at 32x32): the same one-pass form with 1024 threads instead of reduce + apply
-    if (!no_small && a.HW * a.C <= 32768 && (a.C & (a.C - 1)) == 0 && a.C <= 1024 && a.C % a.xf.G == 0) {
+    if (a.HW * a.C <= 32768 && (a.C & (a.C - 1)) == 0 && a.C <= 1024 && a.C % a.xf.G == 0) {
         const size_t lds = (size_t)(4 * a.xf.G + 5 * a.C + 8192) * sizeof(float);
         hipLaunchKernelGGL(gn_bwd_small_kernel<1024>, dim3(a.B), dim3(1024), lds, s, a);
         FC_HIP(hipGetLastError());

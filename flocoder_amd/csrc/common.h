@@ -77,8 +77,6 @@ struct ConvFin {
     unsigned* sync = nullptr;       // one arrival counter per sample group, never reset: arrival number / group size + 1 = this launch's epoch
     unsigned long long* gran = nullptr;   // [B][G][T][2] tagged granules {epoch << 32 | float bits}: the partials AS the hand-off (no flag, no fence)
     int* err = nullptr;             // set to 1 if a wait ever times out
-    float* raw = nullptr;           // training plans: the convolution output BEFORE the tail (NHWC, the backward's h2) is stored too, and
-                                    // the partial statistics also land in stats_out in the ordinary [B][G][T][2] form
 };
 
 struct ConvArgs {
@@ -240,8 +238,6 @@ struct LaArgs {
     unsigned long long* gran = nullptr;   // [B][T][2] {epoch << 32 | float bits}, zero when allocated
     unsigned* sync = nullptr;             // [B] arrival counters (epoch = arrival / T + 1), zero when allocated
     int* err = nullptr;                   // the handle's error word: set when a wait gives up (the sample's output is NaN then)
-    unsigned* tickets = nullptr;   // [B] arrival counters, zero when allocated: with them the module is ONE launch -- the workgroup of a sample that
-                                   // arrives last (ticket % heads == heads - 1) adds the shares, normalises and writes `out`; nobody waits
 };
 int linattn_fused_init();
 bool linattn_fused_supported(int n, int C, int heads);
@@ -252,7 +248,6 @@ bool linattn_fused_meeting_ok(int B, int n, int C);   // may LaArgs::gran be set
 // The whole Residual(PreNorm(LinearAttention)) module in two launches, a workgroup per (sample, head) then per sample (n <= 64 positions)
 int linattn_sample_init();
 bool linattn_sample_supported(int n, int C, int heads);
-bool linattn_sample_one_launch(int n, int C);      // may LaArgs::tickets be set for this shape
 int linattn_sample_launch(const LaArgs& a, hipStream_t s);
 // Residual(PreNorm(Attention)) on the same kernels (g2 / b2 unused: to_out has no norm)
 bool attn_sample_supported(int n, int C, int heads);
@@ -263,14 +258,14 @@ int rope_attn_launch(const float* x, const float* wq, const float* bq, const flo
 // Softmax attention core (unet.py:114-121), n <= 64
 int attn_small_launch(const float* qkv, float* out, int B, int n, int heads, hipStream_t s);
 
+// 2-D neighbourhood attention on a fused NHWC qkv tensor (natten.hip)
+int na2d_launch(const float* qkv, float* out, const float* gamma, int B, int H, int W, int C, int heads, int ksize, int mode, hipStream_t s);
+
 // ---- ODE state updates on the NCHW boundary tensors (ode.hip) -----------------------------------
 // Device-resident integrator state: `step` (interval counter), `ts` (time grid), `sc` = {t, dt} of the
 // interval in flight.  All arithmetic is fp32 in the reference's operation order (sampling.py:43-48,74),
 // with FMA contraction disabled, so a step is reproducible against the CPU oracle to rounding.
 // First kernel of a step: reads ts[*step], publishes sc/tvec, then advances the counter.
-int delay_launch(long long cycles, hipStream_t s);
-// 2-D neighbourhood attention on a fused NHWC qkv tensor (natten.hip)
-int na2d_launch(const float* qkv, float* out, const float* gamma, int B, int H, int W, int C, int heads, int ksize, int mode, hipStream_t s);
 int ode_all_times_launch(const float* ts, int n_steps, int rk4, float t_scale, float* tv_out, hipStream_t s);
 int ode_time_launch(int* step, const float* ts, float t_scale, int rk4, float* sc, float* tvec, int rows, hipStream_t s);
 // v = cfg_on ? v_nc + cfg*(v_c - v_nc) : v   with v2 = [v_c ; v_nc] (n elements each)

@@ -252,11 +252,6 @@ static const int kPipeLoaderThreads[TILE_COUNT] = {256, 256, 512, 512, 256, 256}
 
 static int align4(int v) { return (v + 3) & ~3; }
 
-static bool pipe_disabled() {
-    static const bool off = [] { const char* e = std::getenv("FLOCODER_AMD_CONV"); return e && std::string(e) == "simple"; }();
-    return off;
-}
-
 static int g_cu_count = 0;
 static int conv_cu_count() { return g_cu_count > 0 ? g_cu_count : 256; }
 
@@ -343,14 +338,12 @@ static int conv_geometry(const ConvArgs& a, int tile, bool pipe, ConvDev* d, Con
         if (a.fin.gamma) epi += 2 * TB * t.BN;
         p.o_gran = o + epi;
         if (a.fin.gamma) epi += align4(TB * (p.cpg >= t.BN ? 1 : t.BN / p.cpg) * g->T * 2);   // partials of every workgroup of the sample group, gathered
-        static const bool wide = [] { const char* e = std::getenv("FLOCODER_AMD_WIDE_STORE"); return !(e && std::string(e) == "0"); }();
         p.o_out = -1;
-        if (wide && (size_t)(o + epi + t.BM * (t.BN + 4)) * sizeof(float) <= 160 * 1024) { p.o_out = o + epi; epi += t.BM * (t.BN + 4); }
+        if ((size_t)(o + epi + t.BM * (t.BN + 4)) * sizeof(float) <= 160 * 1024) { p.o_out = o + epi; epi += t.BM * (t.BN + 4); }
         o += main_sz > epi ? main_sz : epi;
         p.zeros16 = conv_zeros16();
         p.stamps = conv_stamp_buffer();
-        static const int lprio = [] { const char* e = std::getenv("FLOCODER_AMD_LOADER_PRIO"); return e ? std::atoi(e) : 1; }();   // measured: 1 = +1.5 %, 2 / 3 a little less (profiles/r02_*)
-        p.loader_prio = lprio;
+        p.loader_prio = 1;   // measured: 1 = +1.5 %, 2 / 3 a little less (profiles/r02_*)
         g->tile = tile; g->grid = p.nblocks; g->lds = (size_t)o * sizeof(float);
         if (g->lds > 160 * 1024) return fail(FC_E_SHAPE, "conv: tile does not fit in LDS");
         p.gsz = 1; p.fin_local = 0;
@@ -409,7 +402,6 @@ bool conv_fin_possible(const ConvArgs& a, int tile) {
     ConvArgs b = a;
     if (!b.fin.gamma) b.fin.gamma = reinterpret_cast<const float*>(16);   // geometry only
     if (!b.stats_out) b.stats_out = reinterpret_cast<float*>(16);
-    if (pipe_disabled()) return false;
     return conv_geometry(b, tile, true, &d, &g) == FC_OK;   // a refusal leaves its reason in fc_last_error, harmlessly
 }
 
@@ -420,7 +412,7 @@ static int auto_tile(const ConvArgs& a) {
     auto ok = [&](int t) { return !(a.w_batch_stride && hw < kTiles[t].BM) && M >= kTiles[t].BM; };
     // measured on the SD-VAE shapes (tools/conv_microbench.py --vae, B=16): M256N64 113 / 109 / 101 TFLOP/s at 512@64^2 / 256@128^2 /
     // 128@256^2 against 101 / 97 / 90 for M128N64 and 98 / 105 / 98 for M128N32; the 64-wide column tile only pays for 1x1 layers
-    if (a.Cout >= 64 && ok(TILE_M256N64) && blocks(TILE_M256N64) >= 512 && !pipe_disabled()) {
+    if (a.Cout >= 64 && ok(TILE_M256N64) && blocks(TILE_M256N64) >= 512) {
         ConvDev d;
         ConvGeom g;
         if (conv_geometry(a, TILE_M256N64, true, &d, &g) == FC_OK) return TILE_M256N64;   // else: patch / LDS limits, fall through
@@ -444,7 +436,7 @@ void conv_set_stamp_buffer(unsigned long long* p) { g_stamps = p; }
 
 // pipelined kernel when its constraints hold, else the synchronous one
 static int geometry_best(const ConvArgs& a, int tile, ConvDev* d, ConvGeom* g) {
-    if (!pipe_disabled() && conv_geometry(a, tile, true, d, g) == FC_OK) return FC_OK;
+    if (conv_geometry(a, tile, true, d, g) == FC_OK) return FC_OK;
     return conv_geometry(a, tile, false, d, g);
 }
 

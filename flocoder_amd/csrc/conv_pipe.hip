@@ -860,14 +860,13 @@ static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, 
         const bool small_tile = tile == TILE_M32N32K4;
         const int need = (d.a.fin.gamma ? FL_FIN : 0) | (d.a.res_out ? FL_RES : 0) | (d.a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |
                          (d.a.s1.C ? FL_CAT : 0) | (d.stamps ? FL_STAMP : 0) | (d.a.stats_out ? FL_STATS : 0) | (d.a.fin.gn1_out ? FL_GN1 : 0) |
-                         ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | ((d.o_out < 0 || d.a.fin.raw) ? FL_NARROW : 0) |   // (a training tail that keeps its raw output also goes to the all-in-one kernel)
+                         ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | (d.o_out < 0 ? FL_NARROW : 0) |
                          ((d.TB > 1 && !small_tile) ? FL_MULTI : 0) |
                          ((d.a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
         int r = -1;
         if (d.a.KS == 3) {
             // register-fed weights in the k-step-quad layout: whole 32-channel chunks, whole 32-column tiles, the centre tap at (1, 1)
-            static const bool no_w4 = std::getenv("FLOCODER_AMD_NO_W4") != nullptr;
-            const bool w4 = !no_w4 && small_tile && d.a.w4 && d.a.Cin % 32 == 0 && d.a.Cout % 32 == 0 && d.a.pad == 1 && !d.a.w_batch_stride &&
+            const bool w4 = small_tile && d.a.w4 && d.a.Cin % 32 == 0 && d.a.Cout % 32 == 0 && d.a.pad == 1 && !d.a.w_batch_stride &&
                             (!d.a.res_out || d.a.res_w4);
             if (w4) {
 #define X(F) if (r == -1 && need == (F)) r = lean_launch_db4<(F)>(d, tile, grid, lds, s, occ);
@@ -904,7 +903,7 @@ int conv_pipe_blocks_per_cu(const ConvDev& d, int tile, size_t lds) {
     static std::mutex mu;
     const int mask = (d.a.fin.gamma ? FL_FIN : 0) | (d.a.res_out ? FL_RES : 0) | (d.a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |
                      (d.a.s1.C ? FL_CAT : 0) | (d.stamps ? FL_STAMP : 0) | (d.a.stats_out ? FL_STATS : 0) | (d.a.fin.gn1_out ? FL_GN1 : 0) |
-                     ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | ((d.o_out < 0 || d.a.fin.raw) ? FL_NARROW : 0) | (d.TB > 1 ? FL_MULTI : 0) |
+                     ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | (d.o_out < 0 ? FL_NARROW : 0) | (d.TB > 1 ? FL_MULTI : 0) |
                      ((d.a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
     const auto key = std::make_tuple(tile, d.a.KS, mask, lds);
     std::lock_guard<std::mutex> lk(mu);

@@ -325,8 +325,7 @@ static int wgrad_geometry(const WgradArgs& a, WgradDev* d) {
     }
     p.nsplit = ns < 1 ? 1 : ns;
     const int xs_floats = p.P * CS > 3 * 1024 ? p.P * CS : 3 * 1024;
-    static const bool no_direct = std::getenv("FLOCODER_AMD_WGRAD_1X1_STAGED") != nullptr;
-    p.direct1 = (!no_direct && a.KS == 1 && a.stride == 1 && !a.ups && a.pad == 0 && a.Hs == a.H && a.Ws == a.W) ? 1 : 0;
+    p.direct1 = (a.KS == 1 && a.stride == 1 && !a.ups && a.pad == 0 && a.Hs == a.H && a.Ws == a.W) ? 1 : 0;
     p.o_ys = (xs_floats + 3) & ~3;
     p.o_pix = (p.o_ys + p.BM * CS + 3) & ~3;
     return FC_OK;

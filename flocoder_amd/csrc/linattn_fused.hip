@@ -642,11 +642,7 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
 }
 
 static size_t la_ctx_fast_lds(int C, int NW) { return (size_t)(2 * C + C * 64 + NW * 32 * (C + 1) + 2 * NW * 32 * PS + 32 * NW + 64 * NW) * sizeof(float); }
-static int la_ctx_waves(int n) {      // eight waves once every one of them has a 32-position block of its own (FLOCODER_AMD_LA_CTX_WAVES=4: never)
-    static const int forced = [] { const char* e = std::getenv("FLOCODER_AMD_LA_CTX_WAVES"); return e ? std::atoi(e) : 0; }();
-    if (forced == 4 || forced == 8) return (forced == 8 && n >= 256) ? 8 : 4;
-    return n >= 256 ? 8 : 4;
-}
+static int la_ctx_waves(int n) { return n >= 256 ? 8 : 4; }      // eight waves once every one of them has a 32-position block of its own
 static size_t la_apply_fast_lds(int C, int CT) {
     const int XS = C + 1 > PS ? C + 1 : PS;
     return (size_t)(2 * C + C * LHID + LHID * CT * 32 + LHEADS * LDH * PS + 4 * 32 * XS) * sizeof(float);
@@ -658,15 +654,11 @@ static int launch_fast(const LaArgs& a, hipStream_t s) {
     FC_HIP(hipGetLastError());
     const int T = linattn_fused_tiles(a.n);
     const float n_t = linattn_fused_nt(a.n, a.C);
-    const int tiles = cdiv(a.n, 128);
-    int gx = tiles;                                   // two tiles per workgroup once that still leaves >= 256 workgroups
-    // Round 4: one 128-position tile per workgroup again.  Two tiles per workgroup (round 2: half the weight staging) leave 256 workgroups of
+    // Round 4: one 128-position tile per workgroup.  Two tiles per workgroup (round 2: half the weight staging) leave 256 workgroups of
     // four waves -- one wave per SIMD, nothing to cover the LDS round trips between the five dependent phases of a head; with one tile each,
     // two workgroups share a CU (67 KB of LDS each).  Measured per module at n = 1024: 55.0 -> 51.0 and 50.9 -> 47.0 us; sampler 793 -> 805
-    // samples/s on one box (791 / 788 with four-wave la_ctx and two tiles).  FLOCODER_AMD_LA_APPLY_GX=half: the old form.
-    static const bool gx_half = [] { const char* e = std::getenv("FLOCODER_AMD_LA_APPLY_GX"); return e && std::string(e) == "half"; }();
-    if (!a.gran && gx_half && tiles >= 2 && (tiles / 2) * a.B >= 256) gx = tiles / 2;      // (the fused close: one tile per workgroup, always)
-    const dim3 grid(gx, a.B);
+    // samples/s on one box (791 / 788 with four-wave la_ctx and two tiles).
+    const dim3 grid(cdiv(a.n, 128), a.B);
     if (a.C <= 32) hipLaunchKernelGGL((la_apply_fast_kernel<NQ, 1>), grid, dim3(256), la_apply_fast_lds(a.C, 1), s, a, T, n_t);
     else hipLaunchKernelGGL((la_apply_fast_kernel<NQ, 2>), grid, dim3(256), la_apply_fast_lds(a.C, 2), s, a, T, n_t);
     FC_HIP(hipGetLastError());
@@ -720,9 +712,7 @@ static int apply_blocks_per_cu(int C) {
     return e == hipSuccess ? nb : 0;
 }
 bool linattn_fused_meeting_ok(int B, int n, int C) {
-    static const bool off = [] { const char* e = std::getenv("FLOCODER_AMD_LA_CLOSE"); return e && std::string(e) == "0"; }();
-    static const bool no_fast = std::getenv("FLOCODER_AMD_LINATTN_GENERAL") != nullptr;
-    if (off || no_fast || n < 256 || (n & 127) || !(C == 8 || C == 16 || C == 32 || C == 64)) return false;
+    if (n < 256 || (n & 127) || !(C == 8 || C == 16 || C == 32 || C == 64)) return false;
     const int T = linattn_fused_tiles(n);
     if (T != n / 128 || T > kPartPre) return false;
     if (linattn_fused_init() != FC_OK) return false;
@@ -735,10 +725,9 @@ bool linattn_fused_meeting_ok(int B, int n, int C) {
 int linattn_fused_launch(const LaArgs& a, hipStream_t s) {
     if (!linattn_fused_supported(a.n, a.C, a.heads)) return fail(FC_E_SHAPE, "linattn_fused: unsupported shape");
     if (a.xf.mode != 1 || a.xf.G != 1 || !a.xf.stats) return fail(FC_E_ARG, "linattn_fused: needs GroupNorm(1) statistics of x");
-    if (a.gran && (!a.sync || !a.out || !a.g2 || !a.b2 || !(a.C == 8 || a.C == 16 || a.C == 32 || a.C == 64) || std::getenv("FLOCODER_AMD_LINATTN_GENERAL")))
+    if (a.gran && (!a.sync || !a.out || !a.g2 || !a.b2 || !(a.C == 8 || a.C == 16 || a.C == 32 || a.C == 64)))
         return fail(FC_E_ARG, "linattn_fused: the fused close needs the fast path, the arrival counters, to_out.1's parameters and the output");
-    static const bool no_fast = std::getenv("FLOCODER_AMD_LINATTN_GENERAL") != nullptr;
-    if (!no_fast && a.C <= 64 && (a.C & 7) == 0 && (a.C == 8 || a.C == 16 || a.C == 32 || a.C == 64)) {
+    if (a.C <= 64 && (a.C & 7) == 0 && (a.C == 8 || a.C == 16 || a.C == 32 || a.C == 64)) {
         switch (a.C) {
             case 8: return launch_fast<1>(a, s);
             case 16: return launch_fast<2>(a, s);

@@ -52,7 +52,6 @@ struct TapeItem { int kind, idx; };   // 0 ResRec, 1 LinRec, 2 MidRec, 3 ConvRec
 struct Plan {                 // one launch plan + activation arena for up to maxB rows
     int maxB = 0, H = 0, W = 0;
     std::vector<Op> ops;
-    int side_ops = 0, join_at = 0;   // ops [0, side_ops) depend on nothing the ops [side_ops, join_at) produce or read: they may run beside them
     std::vector<std::string> op_kernel, op_what;  // parallel to ops: kernel family, reference module it serves
     std::vector<double> op_flops;                  // algorithmic FLOPs per sample of that launch
     std::vector<double> op_bytes_ps, op_bytes_fixed;   // algorithmic HBM bytes of that launch: per sample (activations in + out, each once) and per launch (weights); 0 = not stated
@@ -278,7 +277,6 @@ struct PlanBuilder {
         if (a.res_out) e += (double)a.H * a.W * a.Cout;
         if (a.add) e += (double)a.H * a.W * a.Cout;
         if (a.fin.res) e += (double)a.H * a.W * a.Cout;
-        if (a.fin.raw) e += (double)a.H * a.W * a.Cout;
         if (a.w_batch_stride) e += (double)a.KS * a.KS * a.Cin * a.Cout;
         return 4.0 * e;
     }
@@ -361,21 +359,20 @@ struct PlanBuilder {
     // the workgroups of a sample through a counter (ConvFin).  Returns false, emitting nothing, when the launch cannot keep its whole
     // grid resident or the shape is outside the fused tail's conditions -- the caller then emits conv + finalize.
     bool conv_fin(ConvArgs a, const Act& out, int G, const float* gamma, const float* beta, const float* res, bool want_gn1, Stat* gn1,
-                  bool only_local = false, const Act* raw = nullptr, Stat* st_out = nullptr) {
+                  bool only_local = false) {
         if (err) return false;
         a.B = B; a.H = out.H; a.W = out.W; a.Cout = out.C; a.out = out.p;
         a.Cin = a.s0.C + a.s1.C;
         if ((out.H * out.W) % 16) return false;
         a.Gout = G; a.stats_out = reinterpret_cast<float*>(16);
         a.fin.gamma = gamma; a.fin.beta = beta; a.fin.res = res;
-        if (want_gn1) a.fin.gn1_out = reinterpret_cast<float*>(16);   // placeholders: the geometry (and the occupancy query behind the
-        if (raw) a.fin.raw = reinterpret_cast<float*>(16);            // residency check) must see the flavour the launch will use
+        if (want_gn1) a.fin.gn1_out = reinterpret_cast<float*>(16);   // placeholder: the geometry (and the occupancy query behind the
+                                                                      // residency check) must see the flavour the launch will use
         ConvGeom g;
         if (conv_plan(a, TILE_AUTO, &g) != FC_OK || !g.pipe) return false;
         if (only_local && !g.fin_local) return false;    // the cross-workgroup meeting costs what the finalize launch costs; the local form is free
         Stat st = stat(G, g.T, g.n_t);
         a.stats_out = st.p;
-        if (raw) { a.fin.raw = raw->p; if (st_out) *st_out = st; }
         if (want_gn1) { *gn1 = stat(1, g.T1, g.n_t1); a.fin.gn1_out = gn1->p; }
         unsigned* sync = reinterpret_cast<unsigned*>(dmalloc((size_t)g.groups + 1));
         if (err) return false;

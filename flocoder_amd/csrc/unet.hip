@@ -123,19 +123,16 @@ static int declare_all(fc_unet* u) {
 }
 
 // Fused Block tails across workgroups (ConvFin): on by default since the meeting became one tagged-granule round trip (+2.5 % on the
-// sampler, profiles/r02_*); FLOCODER_AMD_FUSED_TAIL=local keeps only the meeting-free form, =0 turns both off.
+// sampler, profiles/r02_*).  fc_debug_set_fused_tail: -1 default (on), 0 no meeting launches (the tile-local form stays), 1 on.
 static int g_fused_tail = -1;
-static bool fused_tail_enabled() {
-    if (g_fused_tail < 0) { const char* e = std::getenv("FLOCODER_AMD_FUSED_TAIL"); g_fused_tail = (e && (std::string(e) == "0" || std::string(e) == "local")) ? 0 : 1; }
-    return g_fused_tail == 1;
-}
+static bool fused_tail_enabled() { return g_fused_tail != 0; }
 
 // ------------------------------------------------------------------------------------------- plan builder
 struct Builder : PlanBuilder {
     fc_unet* u = nullptr;
     Builder(fc_unet* u_, Plan* pl_, int B_) : u(u_) { pl = pl_; B = B_; fin_err_word = u_->dev_err; }
-    // launches that wait for other workgroups: only on a device this handle has to itself, and never with two chains on two streams
-    bool meeting_ok() const { return fused_tail_enabled() && !u->shared && u->nchains < 2; }
+    // launches that wait for other workgroups: only on a device this handle has to itself
+    bool meeting_ok() const { return fused_tail_enabled() && !u->shared; }
 
     // ResnetBlock (unet.py:76-96): conv1 [+res_conv] | conv2 with GN+FiLM+SiLU folded into its loader | finalize.
     Act resblock(const std::string& p, const Act& x, const Act* skip, int cout, bool want_gn1, Stat* gn1) {
@@ -156,29 +153,19 @@ struct Builder : PlanBuilder {
             if (!a.res_w4) a.w4 = nullptr;      // both operands or neither
         }
         conv(a, h1, G, &st1);
-        if (pl->join_at == 0) pl->join_at = (int)pl->ops.size();   // first reader of the scale / shift table
         ConvArgs b;
         b.s0.p = h1.p; b.s0.C = cout;
         b.s0.xf = xf_of(st1, 2, u->R(p + ".block1.norm.weight"), u->R(p + ".block1.norm.bias"), pl->ss + u->ss_off.at(p), u->S);
         b.Hs = x.H; b.Ws = x.W; b.KS = 3; b.pad = 1;
         b.w = u->P(p + ".block2.proj.weight"); b.bias = u->R(p + ".block2.proj.bias");
         b.w4 = u->P8(p + ".block2.proj.weight");
-        // inference plans close the Block inside conv2 (ConvFin) when the launch keeps its whole grid resident; training plans keep
-        // the raw h2 and its statistics for the backward
-        // Measured on one box, B=64 (profiles/README.md r01_g): 494 samples/s with the fused tails against 503 without -- the
-        // in-kernel meeting (four dependent memory round trips) costs what a launch boundary plus the finalize pass cost.  Off
-        // unless FLOCODER_AMD_FUSED_TAIL=1 / fc_debug_set_fused_tail(1).
+        // Inference plans close the Block inside conv2 (ConvFin) when the launch keeps its whole grid resident: across workgroups where
+        // meeting launches are allowed (meeting_ok), and always where a tile holds whole GroupNorm groups (dim 32: the 128-channel blocks
+        // at 4x4 and 8x8, 32 channels per group) and there is nothing to meet for.  Training plans keep the raw h2 and its statistics for
+        // the backward: conv + finalize (a fused training tail measured no faster, r02: stl_sd step 3.515 against 3.446 ms).
         const float* resp = (cin != cout) ? rb.p : x.p;
-        // Where a tile holds whole GroupNorm groups (dim 32: the 128-channel blocks at 4x4 and 8x8, 32 channels per group) there is nothing to meet
-        // for and the tail is always fused (FLOCODER_AMD_FUSED_TAIL=0 turns that off too).
-        static const bool no_local = [] { const char* e = std::getenv("FLOCODER_AMD_FUSED_TAIL"); return e && std::string(e) == "0"; }();
-        // training plans can fuse the tail too, keeping what the backward reads (raw h2, its statistics in the ordinary form):
-        // FLOCODER_AMD_TRAIN_FUSED_TAIL=1.  Off by default -- measured on one box (r02): stl_sd step 3.515 ms fused against 3.446 ms
-        // with conv + finalize, flowers-sized step 7.91 against 7.92: at these small grids the meeting costs what the launch it saves does.
-        static const bool train_fused = [] { const char* e = std::getenv("FLOCODER_AMD_TRAIN_FUSED_TAIL"); return e && std::string(e) == "1"; }();
-        const bool fused = (!u->keep_all || train_fused) && (meeting_ok() || !no_local) &&
-                           conv_fin(b, out, G, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias"), resp, want_gn1, gn1,
-                                    !meeting_ok(), u->keep_all ? &h2 : nullptr, u->keep_all ? &st2 : nullptr);
+        const bool fused = !u->keep_all &&
+                           conv_fin(b, out, G, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias"), resp, want_gn1, gn1, !meeting_ok());
         if (!fused) {
             conv(b, h2, G, &st2);
             FinalizeArgs f;
@@ -204,13 +191,11 @@ struct Builder : PlanBuilder {
     Act linattn(const std::string& p, const Act& x, const Stat& gn1) {
         scope = p;
         const int hid = u->heads * 32, n = x.H * x.W, heads = u->heads;
-        static const bool no_fuse = [] { const char* e = std::getenv("FLOCODER_AMD_LINATTN"); return e && std::string(e) == "unfused"; }();
         // measured (tools/op_table.py, B=64): fused 110 vs 201 us at n=1024, 43 vs 65 us at n=256; at n <= 64 the per-workgroup weight
         // loads dominate and the unfused chain wins (37 vs 67 us at n=16, C=256)
-        if (!u->keep_all && !no_fuse && n >= 256 && linattn_fused_supported(n, x.C, heads)) return linattn_fused(p, x, gn1);
+        if (!u->keep_all && n >= 256 && linattn_fused_supported(n, x.C, heads)) return linattn_fused(p, x, gn1);
         // n <= 64: a workgroup per (sample, head), then one per sample (linattn_sample.hip): 2 launches instead of 5
-        static const bool no_sample = std::getenv("FLOCODER_AMD_LINATTN_NO_SAMPLE") != nullptr;
-        if (!u->keep_all && !no_fuse && !no_sample && linattn_sample_supported(n, x.C, heads)) return linattn_sample(p, x, gn1);
+        if (!u->keep_all && linattn_sample_supported(n, x.C, heads)) return linattn_sample(p, x, gn1);
         Act qkv = act(3 * hid, x.H, x.W), lao = act(hid, x.H, x.W), yb = act(x.C, x.H, x.W), out = act(x.C, x.H, x.W);
         float* ctx = dmalloc((size_t)B * heads * 32 * 32);
         ConvArgs a;
@@ -277,19 +262,7 @@ struct Builder : PlanBuilder {
         return out;
     }
 
-    // arrival counters of the one-launch form of linattn_sample.hip (zeroed here, once: every launch adds `heads` per sample), or null.
-    // Default: null -- the closing step stays a launch of its own (la_join).  FLOCODER_AMD_LA_JOIN=one selects the one-launch form: built and
-    // tested in round 3, but it measures the same or slightly below the two-launch form (789 against 793 samples/s, three alternating pairs;
-    // 1286 against 1279 us of kernel time per forward), so it is not the default.
-    unsigned* la_tickets(int n, int C) {
-        static const bool one = [] { const char* e = std::getenv("FLOCODER_AMD_LA_JOIN"); return e && std::string(e) == "one"; }();
-        if (!one || !linattn_sample_one_launch(n, C) || err) return nullptr;
-        unsigned* t = reinterpret_cast<unsigned*>(dmalloc((size_t)B));
-        if (t && hipMemset(t, 0, (size_t)B * sizeof(unsigned)) != hipSuccess) { err = fail(FC_E_HIP, "hipMemset failed on the attention tickets"); return nullptr; }
-        return t;
-    }
-
-    // the whole module in one launch, or two (linattn_sample.hip)
+    // the whole module in two launches (linattn_sample.hip)
     Act linattn_sample(const std::string& p, const Act& x, const Stat& gn1) {
         const int n = x.H * x.W, heads = u->heads, hid = heads * 32;
         Act out = act(x.C, x.H, x.W);
@@ -300,7 +273,6 @@ struct Builder : PlanBuilder {
         a.g2 = u->R(p + ".fn.fn.to_out.1.weight"); a.b2 = u->R(p + ".fn.fn.to_out.1.bias"); a.out = out.p;
         a.n = n; a.C = x.C; a.heads = heads;
         a.part = dmalloc((size_t)B * heads * n * x.C);
-        a.tickets = la_tickets(n, x.C);
         const double fl = 2.0 * n * (double)x.C * 3 * hid + 2.0 * 2 * n * 32 * 32 * heads + 2.0 * n * (double)hid * x.C;
         if (!err) push([a](const FwdCtx& c, hipStream_t s) { LaArgs b = a; b.B = c.B; return linattn_sample_launch(b, s); }, "linattn_sample", fl);
         pl->named[p] = out;
@@ -311,8 +283,7 @@ struct Builder : PlanBuilder {
     Act midattn(const Act& x, const Stat& gn1) {
         scope = "mid_attn";
         const int hid = u->heads * 32, n = x.H * x.W, heads = u->heads;
-        static const bool no_sample = std::getenv("FLOCODER_AMD_LINATTN_NO_SAMPLE") != nullptr;
-        if (!u->keep_all && !no_sample && attn_sample_supported(n, x.C, heads)) {    // two launches instead of three (linattn_sample.hip)
+        if (!u->keep_all && attn_sample_supported(n, x.C, heads)) {    // two launches instead of three (linattn_sample.hip)
             Act out = act(x.C, x.H, x.W);
             LaArgs a;
             a.x = x.p; a.xf = xf_of(gn1, 1, u->R("mid_attn.fn.norm.weight"), u->R("mid_attn.fn.norm.bias"));
@@ -320,7 +291,6 @@ struct Builder : PlanBuilder {
             a.wqkv4 = u->P8("mid_attn.fn.fn.to_qkv.weight");
             a.out = out.p; a.n = n; a.C = x.C; a.heads = heads;
             a.part = dmalloc((size_t)B * heads * n * x.C);
-            a.tickets = la_tickets(n, x.C);
             const double fl = 2.0 * n * (double)x.C * 3 * hid + 2.0 * 2.0 * n * n * 32 * heads + 2.0 * n * (double)hid * x.C;
             if (!err) push([a](const FwdCtx& c, hipStream_t s) { LaArgs b = a; b.B = c.B; return attn_sample_launch(b, s); }, "attn_sample", fl);
             pl->named["mid_attn"] = out;
@@ -386,7 +356,7 @@ struct Builder : PlanBuilder {
 static void free_plan(fc_unet* u) {
     for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
     u->graphs.clear();
-    for (Plan& pln : u->plan) pln.release();
+    u->plan.release();
     u->bwd.release();                       // the backward plan points into the forward arena
     u->dgrad_packs.clear();
     u->dgrad_table.release();
@@ -412,7 +382,7 @@ static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, 
     if (maxB > cus) return 1;
     const fc_unet_config& c = u->cfg;
     const int L = c.n_levels, dim = c.dim, ch = c.channels, G = c.groups, heads = u->heads;
-    if (off || u->keep_all || G > 8 || heads != 4 || u->nchains > 1) return 1;
+    if (off || u->keep_all || G > 8 || heads != 4) return 1;
     const std::vector<int>& cs = u->chans;
     struct T { int off = -1, C = 0, H = 0, W = 0; };
     std::vector<SStep> prog;
@@ -605,7 +575,6 @@ static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, 
     const int zero_off = alloc(128);
     const int wbuf_off = alloc(2 * 4096), prog_off = alloc((int)(prog.size() * sizeof(SStep) / 4) + 4);
     const size_t lds = (size_t)peak * sizeof(float);
-    if (std::getenv("FLOCODER_AMD_SAMPLE_KERNEL_DEBUG")) fprintf(stderr, "[unet_sample] %zu steps, %zu bytes of LDS per sample\n", prog.size(), lds);
     if (lds > 158 * 1024) return 1;                       // the sample does not fit a CU: ordinary plan
     FC_TRY(unet_sample_init());
     SStep* dev = reinterpret_cast<SStep*>(b.dmalloc((prog.size() * sizeof(SStep) + 3) / 4 + 4));
@@ -666,14 +635,12 @@ static int build_plan(fc_unet* u, Plan* pl, int maxB, int H, int W) {
         float* ss = pl->ss;
         b.scope = "resblock.mlp";
         b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.fetch.all ? (int)FC_OK : ss_launch(te, wt, sb, ss, cx.B, td, S, s); }, "ss", 2.0 * (double)td * S);
-        pl->side_ops = (int)pl->ops.size();   // the conditioning chain reads only time / class ids: it runs beside init_conv and the first conv1
     }
 
     {   // small models: the whole forward of a sample in one workgroup (unet_sample.hip); 1 = does not qualify
         const int r = build_sample_plan(u, pl, b, maxB, H, W);
         if (r != 1) {
             if (r != FC_OK) return r;
-            pl->join_at = (int)pl->ops.size();
             pl->maxB = maxB; pl->H = H; pl->W = W;
             return FC_OK;
         }
@@ -846,29 +813,6 @@ static int alloc_integrator(fc_unet* u, int rows, int H, int W) {
     return FC_OK;
 }
 
-// Rows [r0, r0 + n) of the caller's batch as a context of their own (row r reads sample r % x_mod, class id r % ids_mod,
-// no class at all from row null_from on -- the CFG layout of fc_unet_integrate).
-static FwdCtx slice_ctx(const FwdCtx& c, int r0, int n, size_t sample_floats) {
-    FwdCtx k = c;
-    k.B = n;
-    k.time = c.time + r0;
-    k.out = c.out + (size_t)r0 * sample_floats;
-    const int xs = r0 % c.x_mod;                 // first sample this slice reads
-    k.x = c.x + (size_t)xs * sample_floats;
-    if (c.mask) k.mask = c.mask + (size_t)xs * sample_floats;
-    k.x_mod = c.x_mod - xs;
-    if (c.ids) {
-        if (c.null_from > 0 && r0 >= c.null_from) { k.ids = nullptr; k.null_from = 0; }
-        else {
-            const int is = r0 % c.ids_mod;
-            k.ids = c.ids + is;
-            k.ids_mod = c.ids_mod - is;
-            k.null_from = c.null_from > 0 ? c.null_from - r0 : 0;
-        }
-    }
-    return k;
-}
-
 // ---- process-wide guard of the meeting launches ------------------------------------------------------------------------------
 // A launch whose workgroups wait for each other is only safe while no OTHER such launch can hold part of the CUs: two of them, each
 // half resident, would wait for workgroups that cannot start (bounded by the spin limit, then NaN + error -- never a hang, never silent).
@@ -879,7 +823,7 @@ struct MeetGuard { std::mutex mu; hipEvent_t ev = nullptr; hipStream_t s = nullp
 static MeetGuard g_meet[16];
 static MeetGuard& meet_guard(int device) { return g_meet[device & 15]; }
 
-static int plan_meets(const fc_unet* u) { return u->plan[0].n_meet + u->plan[1].n_meet; }
+static int plan_meets(const fc_unet* u) { return u->plan.n_meet; }
 
 static int meet_enter(fc_unet* u, hipStream_t s) {
     if (!plan_meets(u)) return FC_OK;
@@ -913,41 +857,6 @@ static int check_poison(fc_unet* u) {
     return FC_OK;
 }
 
-// one chain: the conditioning MLPs (time / class embedding -> every block's scale and shift) on the second stream, joined before
-// the first conv2; inside a captured step this becomes a parallel branch of the graph
-static int run_single(fc_unet* u, const Plan& pl, const FwdCtx& c, hipStream_t s) {
-    // Opt-in (FLOCODER_AMD_SIDE=1): worth +0.9 % while the conditioning chain took 46 us; since it takes 8 + 12 + 11 us the two forms
-    // measure the same (631.4 / 629.4 vs 630.6 / 631.5 samples/s), so the plain single-stream order is the default.
-    static const bool no_side = std::getenv("FLOCODER_AMD_SIDE") == nullptr;
-    const int ns = pl.side_ops, nj = pl.join_at;
-    if (no_side || ns <= 0 || nj <= ns || !u->stream2) return run_plan(pl, c, s);
-    FC_HIP(hipEventRecord(u->ev_fork, s));
-    FC_HIP(hipStreamWaitEvent(u->stream2, u->ev_fork, 0));
-    for (int i = 0; i < ns; ++i) FC_TRY(pl.ops[i](c, u->stream2));
-    FC_HIP(hipEventRecord(u->ev_join, u->stream2));
-    for (int i = ns; i < nj; ++i) FC_TRY(pl.ops[i](c, s));
-    FC_HIP(hipStreamWaitEvent(s, u->ev_join, 0));
-    for (size_t i = nj; i < pl.ops.size(); ++i) FC_TRY(pl.ops[i](c, s));
-    return FC_OK;
-}
-
-static int run_forward(fc_unet* u, const FwdCtx& c, hipStream_t s) {
-    if (u->nchains < 2 || c.B < 2) return run_single(u, u->plan[0], c, s);
-    // two chains: with CFG the conditional and the unconditional rows, otherwise the two halves of the batch
-    const int r0 = (c.null_from > 0 && c.null_from < c.B) ? c.null_from : (c.B + 1) / 2;
-    if (r0 > u->plan[0].maxB || c.B - r0 > u->plan[1].maxB) return fail(FC_E_STATE, "unet: chain plans too small for this batch");
-    const size_t sf = (size_t)u->cfg.channels * u->H * u->W;
-    FC_HIP(hipEventRecord(u->ev_fork, s));
-    FC_HIP(hipStreamWaitEvent(u->stream2, u->ev_fork, 0));
-    static const long long delay = [] { const char* e = std::getenv("FLOCODER_AMD_CHAIN_DELAY_US"); return e ? (long long)(std::atof(e) * 2100.0) : 0ll; }();
-    if (delay > 0) FC_TRY(delay_launch(delay, u->stream2));   // the second chain runs half a kernel behind the first
-    FC_TRY(run_plan(u->plan[1], slice_ctx(c, r0, c.B - r0, sf), u->stream2));
-    FC_HIP(hipEventRecord(u->ev_join, u->stream2));
-    FC_TRY(run_plan(u->plan[0], slice_ctx(c, 0, r0, sf), s));
-    FC_HIP(hipStreamWaitEvent(s, u->ev_join, 0));
-    return FC_OK;
-}
-
 }  // namespace fc
 
 // =============================================================================================== C ABI
@@ -974,7 +883,7 @@ int fc_unet_create(const fc_unet_config* cfg, int device, fc_unet** out) {
     std::unique_ptr<fc_unet> u(new fc_unet);
     u->cfg = *cfg;
     u->device = device;
-    u->want_k8 = std::getenv("FLOCODER_AMD_NO_K8") == nullptr;
+    u->want_k8 = true;
     FC_TRY(declare_all(u.get()));
     if (device < 0) {  // description only: parameter table without touching a GPU
         *out = u.release();
@@ -996,9 +905,6 @@ int fc_unet_create(const fc_unet_config* cfg, int device, fc_unet** out) {
     FC_HIP(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
     FC_HIP(hipEventCreateWithFlags(&u->ev_in, hipEventDisableTiming));
     FC_HIP(hipEventCreateWithFlags(&u->ev_out, hipEventDisableTiming));
-    FC_HIP(hipStreamCreateWithFlags(&u->stream2, hipStreamNonBlocking));
-    FC_HIP(hipEventCreateWithFlags(&u->ev_fork, hipEventDisableTiming));
-    FC_HIP(hipEventCreateWithFlags(&u->ev_join, hipEventDisableTiming));
     FC_HIP(hipEventCreateWithFlags(&u->ev_meet, hipEventDisableTiming));
     FC_HIP(hipMalloc(reinterpret_cast<void**>(&u->dev_err), sizeof(int)));
     FC_HIP(hipMemset(u->dev_err, 0, sizeof(int)));
@@ -1020,9 +926,6 @@ void fc_unet_destroy(fc_unet* u) {
     if (u->stream) (void)hipStreamDestroy(u->stream);
     if (u->ev_in) (void)hipEventDestroy(u->ev_in);
     if (u->ev_out) (void)hipEventDestroy(u->ev_out);
-    if (u->stream2) (void)hipStreamDestroy(u->stream2);
-    if (u->ev_fork) (void)hipEventDestroy(u->ev_fork);
-    if (u->ev_join) (void)hipEventDestroy(u->ev_join);
     meet_forget(u);
     if (u->ev_meet) (void)hipEventDestroy(u->ev_meet);
     if (u->dev_err) (void)hipFree(u->dev_err);
@@ -1069,11 +972,7 @@ int fc_unet_reserve(fc_unet* u, int max_batch, int height, int width) {
     FC_HIP(hipDeviceSynchronize());
     free_plan(u);
     u->arena_touched(0);
-    static const int want_chains = [] { const char* e = std::getenv("FLOCODER_AMD_CHAINS"); return e ? std::atoi(e) : 1; }();   // measured: 2 half-batch chains 404 vs 1 chain 446 samples/s (profiles/r01_c_*)
-    u->nchains = (want_chains >= 2 && max_batch >= 2) ? 2 : 1;
-    const int rows0 = u->nchains == 2 ? (max_batch + 1) / 2 : max_batch;
-    int r = build_plan(u, &u->plan[0], rows0, height, width);
-    if (r == FC_OK && u->nchains == 2) r = build_plan(u, &u->plan[1], rows0, height, width);
+    int r = build_plan(u, &u->plan, max_batch, height, width);
     if (r == FC_OK) r = alloc_integrator(u, max_batch, height, width);
     if (r != FC_OK) { free_plan(u); return r; }
     u->maxB = max_batch; u->H = height; u->W = width;
@@ -1101,7 +1000,7 @@ int fc_unet_forward(fc_unet* u, const float* x, const float* time, const int64_t
     FC_TRY(check_poison(u));
     u->arena_touched(u->keep_all ? B : 0);
     FC_TRY(meet_enter(u, static_cast<hipStream_t>(stream)));
-    FC_TRY(run_forward(u, c, static_cast<hipStream_t>(stream)));
+    FC_TRY(run_plan(u->plan, c, static_cast<hipStream_t>(stream)));
     return meet_leave(u, static_cast<hipStream_t>(stream));
 }
 
@@ -1145,8 +1044,7 @@ int fc_debug_set_stamp_op(int op_index, void* buf_dev) { g_stamp_op = buf_dev ? 
 int fc_unet_profile_ops(fc_unet* u, int batch, int repeats, float* ms_out, int n_out, void* stream) {
     if (!u || !ms_out || repeats < 1) return fail(FC_E_ARG, "fc_unet_profile_ops: bad argument");
     FC_TRY(check_ready(u, batch, u->H, u->W));
-    const Plan& pl0 = u->plan[0];
-    if (batch > pl0.maxB) batch = pl0.maxB;   // ops are timed on chain 0's plan, at the rows one chain carries
+    const Plan& pl0 = u->plan;
     u->arena_touched(0);
     const int n = (int)pl0.ops.size();
     if (n_out < n) return fail(FC_E_ARG, "fc_unet_profile_ops: output array too small");
@@ -1180,24 +1078,24 @@ int fc_unet_profile_ops(fc_unet* u, int batch, int repeats, float* ms_out, int n
 }
 
 int fc_unet_op_info(const fc_unet* u, int i, const char** kernel, const char** module, double* flops_per_sample) {
-    if (!u || i < 0 || i >= (int)u->plan[0].ops.size()) return fail(FC_E_ARG, "fc_unet_op_info: index out of range");
-    if (kernel) *kernel = u->plan[0].op_kernel[i].c_str();
-    if (module) *module = u->plan[0].op_what[i].c_str();
-    if (flops_per_sample) *flops_per_sample = u->plan[0].op_flops[i];
+    if (!u || i < 0 || i >= (int)u->plan.ops.size()) return fail(FC_E_ARG, "fc_unet_op_info: index out of range");
+    if (kernel) *kernel = u->plan.op_kernel[i].c_str();
+    if (module) *module = u->plan.op_what[i].c_str();
+    if (flops_per_sample) *flops_per_sample = u->plan.op_flops[i];
     return FC_OK;
 }
 
 int fc_unet_op_bytes(const fc_unet* u, int i, double* bytes_per_sample, double* bytes_per_launch) {
-    if (!u || i < 0 || i >= (int)u->plan[0].ops.size()) return fail(FC_E_ARG, "fc_unet_op_bytes: index out of range");
-    if (bytes_per_sample) *bytes_per_sample = u->plan[0].op_bytes_ps[i];
-    if (bytes_per_launch) *bytes_per_launch = u->plan[0].op_bytes_fixed[i];
+    if (!u || i < 0 || i >= (int)u->plan.ops.size()) return fail(FC_E_ARG, "fc_unet_op_bytes: index out of range");
+    if (bytes_per_sample) *bytes_per_sample = u->plan.op_bytes_ps[i];
+    if (bytes_per_launch) *bytes_per_launch = u->plan.op_bytes_fixed[i];
     return FC_OK;
 }
 
 int fc_unet_chains(const fc_unet* u, int* rows_per_chain) {
     if (!u) return 0;
-    if (rows_per_chain) *rows_per_chain = u->plan[0].maxB;
-    return u->nchains;
+    if (rows_per_chain) *rows_per_chain = u->maxB;
+    return 1;
 }
 
 int fc_unet_fused_tail_errors(const fc_unet* u, int* count) {
@@ -1210,51 +1108,48 @@ int fc_unet_fused_tail_errors(const fc_unet* u, int* count) {
     return FC_OK;
 }
 
-int fc_unet_plan_launches(const fc_unet* u) { return u ? (int)u->plan[0].ops.size() : 0; }
-double fc_unet_flops_per_sample(const fc_unet* u) { return u ? u->plan[0].flops : 0.0; }
+int fc_unet_plan_launches(const fc_unet* u) { return u ? (int)u->plan.ops.size() : 0; }
+double fc_unet_flops_per_sample(const fc_unet* u) { return u ? u->plan.flops : 0.0; }
 
 // -------------------------------------------------------------------------------- integrator
 static uint32_t fbits(float f) { uint32_t v; std::memcpy(&v, &f, 4); return v; }
 
 // enqueue one integration step on `s` (captured into a graph by the caller)
-// Legacy Euler without CFG on one chain: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
-static bool euler_tail_ok(const fc_unet* u, int method, bool cfg_on) {
-    static const bool off = std::getenv("FLOCODER_AMD_NO_EULER_TAIL") != nullptr;
-    return !off && method == FC_METHOD_EULER && !cfg_on && u->nchains < 2;
-}
+// Legacy Euler without CFG: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
+static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_EULER && !cfg_on; }
 
 static int enqueue_step(fc_unet* u, int method, int B, bool cfg_on, float cfg, float dt_euler, float t_scale, bool has_ids, int mask_mode,
                         bool pre_on, hipStream_t s) {
     const int rows = cfg_on ? 2 * B : B, n = B * u->cfg.channels * u->H * u->W;
     FwdCtx c;
     if (pre_on) {   // conditioning rows of every evaluation are in u->pre: init_conv fetches slice *evalc, final_conv advances the counter
-        c.fetch.all = u->pre_ss; c.fetch.evalc = u->step + 1; c.fetch.dst = u->plan[0].ss; c.fetch.n4 = rows * u->S / 4;
+        c.fetch.all = u->pre_ss; c.fetch.evalc = u->step + 1; c.fetch.dst = u->plan.ss; c.fetch.n4 = rows * u->S / 4;
         c.euler.evalc = u->step + 1;
     }
     c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
     c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
     c.out = u->v2; c.B = rows;
-    if (euler_tail_ok(u, method, cfg_on)) {   // the update and the next interval's time ride in final_conv: no launches around the plan
+    if (euler_tail_ok(method, cfg_on)) {   // the update and the next interval's time ride in final_conv: no launches around the plan
         c.x = u->y;
         c.euler.y = u->y; c.euler.dt = dt_euler; c.euler.step = u->step; c.euler.ts = u->ts_dev; c.euler.t_scale = t_scale;
         c.euler.sc = u->sc; c.euler.tvec = u->tvec; c.euler.rows = rows;
-        return run_forward(u, c, s);
+        return run_plan(u->plan, c, s);
     }
     FC_TRY(ode_time_launch(u->step, u->ts_dev, t_scale, method == FC_METHOD_RK4, u->sc, u->tvec, rows, s));
     if (method == FC_METHOD_EULER) {
         c.x = u->y;
-        FC_TRY(run_forward(u, c, s));
+        FC_TRY(run_plan(u->plan, c, s));
         return ode_euler_update_launch(u->y, u->v2, n, cfg_on, cfg, dt_euler, s);
     }
     c.x = u->y;
-    FC_TRY(run_forward(u, c, s));                                                                                        // k1 = f(y, t)
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k1 = f(y, t)
     FC_TRY(ode_rk4_stage_launch(u->sc, u->y, u->xs, u->k1, u->v2, n, cfg_on, cfg, 0, 1, t_scale, u->tvec, rows, s));      // y + dt*k1/2, t+dt/2
     c.x = u->xs;
-    FC_TRY(run_forward(u, c, s));                                                                                        // k2
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k2
     FC_TRY(ode_rk4_stage_launch(u->sc, u->y, u->xs, u->k2, u->v2, n, cfg_on, cfg, 0, 1, t_scale, u->tvec, rows, s));      // y + dt*k2/2, t+dt/2
-    FC_TRY(run_forward(u, c, s));                                                                                        // k3
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k3
     FC_TRY(ode_rk4_stage_launch(u->sc, u->y, u->xs, u->k3, u->v2, n, cfg_on, cfg, 1, 2, t_scale, u->tvec, rows, s));      // y + dt*k3, t+dt
-    FC_TRY(run_forward(u, c, s));                                                                                        // k4
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k4
     return ode_rk4_final_launch(u->sc, u->y, u->k1, u->k2, u->k3, u->v2, n, cfg_on, cfg, s);
 }
 
@@ -1294,11 +1189,10 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
     // Conditioning of every evaluation, once: the grid is known, so time MLP / class MLP / FiLM projections of all (evaluation, row)
     // pairs are three launches here instead of three at the head of each forward (44 us of every 1.6 ms step inside the replayed graph:
     // cold weights, latency-bound).  Rows are bit-identical to the per-forward ones (same kernels, same time arithmetic).
-    static const bool no_pre = std::getenv("FLOCODER_AMD_NO_PRECOND") != nullptr;
     const int n_evals = method == FC_METHOD_RK4 ? 4 * n_steps : n_steps;
     const size_t R = (size_t)n_evals * rows, tvn = ((size_t)n_evals + 3) & ~(size_t)3;
     const size_t need = tvn + R * u->td * 3 + R * u->S;
-    const bool pre_on = !no_pre && u->nchains < 2 && n_steps >= 2 && need * sizeof(float) <= (2ull << 30) && R < (1u << 30) / (unsigned)u->S;
+    const bool pre_on = n_steps >= 2 && need * sizeof(float) <= (2ull << 30) && R < (1u << 30) / (unsigned)u->S;
     if (pre_on) {
         if (need > u->pre_cap) {
             FC_HIP(hipStreamSynchronize(s));
@@ -1329,7 +1223,7 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
         ca.w = u->P("__ss_wt"); ca.bias = u->P("__ss_bias"); ca.out = u->pre_ss;
         FC_TRY(conv_launch(ca, TILE_AUTO, s));
     }
-    if (euler_tail_ok(u, method, cfg_on))   // time of the first interval; every step publishes its successor's
+    if (euler_tail_ok(method, cfg_on))   // time of the first interval; every step publishes its successor's
         FC_TRY(ode_time_launch(u->step, u->ts_dev, t_scale, 0, u->sc, u->tvec, rows, s));
     FC_TRY(meet_enter(u, s));
     static const bool no_graph = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
@@ -1339,10 +1233,9 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
         // One graph holds SEVERAL consecutive intervals (round 3): the step counter, the time grid and the conditioning slice index all
         // live on the device, so a captured interval is position-independent and k of them in a row are one hipGraphLaunch instead
         // of k (the per-interval form left ~4 % of the trajectory between replays: 64 launches of a 70-node graph).  Capped by node
-        // count; FLOCODER_AMD_GRAPH_STEPS=1 restores one interval per graph.
-        static const int steps_env = [] { const char* e = std::getenv("FLOCODER_AMD_GRAPH_STEPS"); return e ? std::atoi(e) : 0; }();
-        const int nodes_per_step = (int)u->plan[0].ops.size() * (method == FC_METHOD_RK4 ? 4 : 1) * (u->nchains == 2 ? 2 : 1) + 16;
-        int per = steps_env > 0 ? steps_env : (6144 / nodes_per_step > 0 ? 6144 / nodes_per_step : 1);
+        // count.
+        const int nodes_per_step = (int)u->plan.ops.size() * (method == FC_METHOD_RK4 ? 4 : 1) + 16;
+        int per = 6144 / nodes_per_step > 0 ? 6144 / nodes_per_step : 1;
         if (per > 255) per = 255;
         for (int left = n_steps; left > 0;) {
             const int k = left < per ? left : per;
@@ -1371,9 +1264,8 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
             // five); FLOCODER_AMD_NO_GRAPH=1, AMD_DIRECT_DISPATCH=1 and this wait each give 1e-7 in all of them, an event wait on the
             // same stream does not.  bench.py never saw it: every timed step integrates the same samples, so a stale table is the right
             // one.  Replays that follow a replay are ordered (RK4: five graphs per call); work issued behind a replay is ordered as well.
-            // Cost: the host idles for the prologue (~0.1 ms per call of 80 ms).  FLOCODER_AMD_GRAPH_FENCE=0 removes the wait (measurements only).
-            static const bool fence = [] { const char* e = std::getenv("FLOCODER_AMD_GRAPH_FENCE"); return !(e && std::atoi(e) == 0); }();
-            if (fence && left == n_steps) FC_HIP(hipStreamSynchronize(s));
+            // Cost: the host idles for the prologue (~0.1 ms per call of 80 ms).
+            if (left == n_steps) FC_HIP(hipStreamSynchronize(s));
             FC_HIP(hipGraphLaunch(it->second, s));
             left -= k;
         }
@@ -1388,8 +1280,8 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
 // ---- debug / test hooks --------------------------------------------------------------------------
 int fc_unet_debug_tensor(const fc_unet* u, const char* name, const float** ptr, int* C, int* H, int* W) {
     if (!u || !name) return fail(FC_E_ARG, "fc_unet_debug_tensor: null argument");
-    auto it = u->plan[0].named.find(name);   // chain 0 = the first rows of the batch
-    if (it == u->plan[0].named.end()) {
+    auto it = u->plan.named.find(name);
+    if (it == u->plan.named.end()) {
         it = u->bwd.named.find(name);        // "grad:<tap>": gradient of that tap after fc_unet_backward
         if (it == u->bwd.named.end()) return fail(FC_E_ARG, std::string("fc_unet_debug_tensor: no tap named ") + name);
     }
@@ -1400,18 +1292,18 @@ int fc_unet_debug_tensor(const fc_unet* u, const char* name, const float** ptr, 
 // Test hook: put the arrival counter of one meeting launch out of step, so that its workgroups draw different epochs and every wait of
 // that launch times out (bounded spins) -- the failure a shared device can cause, on demand.
 int fc_debug_unet_break_meeting(fc_unet* u) {
-    if (!u || u->plan[0].fin_sync.empty()) return fail(FC_E_STATE, "fc_debug_unet_break_meeting: the plan has no meeting launch");
+    if (!u || u->plan.fin_sync.empty()) return fail(FC_E_STATE, "fc_debug_unet_break_meeting: the plan has no meeting launch");
     FC_HIP(hipDeviceSynchronize());
     unsigned v = 0;
-    FC_HIP(hipMemcpy(&v, u->plan[0].fin_sync[0], sizeof(unsigned), hipMemcpyDeviceToHost));
+    FC_HIP(hipMemcpy(&v, u->plan.fin_sync[0], sizeof(unsigned), hipMemcpyDeviceToHost));
     ++v;
-    FC_HIP(hipMemcpy(u->plan[0].fin_sync[0], &v, sizeof(unsigned), hipMemcpyHostToDevice));
+    FC_HIP(hipMemcpy(u->plan.fin_sync[0], &v, sizeof(unsigned), hipMemcpyHostToDevice));
     return FC_OK;
 }
 
 int fc_debug_unet_break_meeting_kind(fc_unet* u, int kind) {      // the same for the first meeting launch of a kind (0 Block tail, 1 linear attention close)
     if (!u) return fail(FC_E_ARG, "fc_debug_unet_break_meeting_kind: null handle");
-    const Plan& pl = u->plan[0];
+    const Plan& pl = u->plan;
     for (size_t i = 0; i < pl.fin_sync.size(); ++i)
         if (pl.fin_kind[i] == kind) {
             FC_HIP(hipDeviceSynchronize());
@@ -1424,7 +1316,7 @@ int fc_debug_unet_break_meeting_kind(fc_unet* u, int kind) {      // the same fo
     return fail(FC_E_STATE, "fc_debug_unet_break_meeting_kind: the plan has no meeting launch of that kind");
 }
 
-int fc_debug_set_fused_tail(int on) {   // plans built from now on use (1) / do not use (0) the fused Block tails; < 0: back to the default (environment)
+int fc_debug_set_fused_tail(int on) {   // plans built from now on use (1) / do not use (0) the meeting launches; < 0: back to the default (on)
     fc::g_fused_tail = on < 0 ? -1 : (on ? 1 : 0);
     return FC_OK;
 }
@@ -1461,7 +1353,7 @@ int fc_debug_conv(const float* src0, int c0, const float* src1, int c1, const fl
     int r = pack_conv_launch(w_oihw, wp, cout, a.Cin, ksize, ksize, s);
     a.w = wp;
     float* wp8 = nullptr;       // the k-step-quad copy where the shapes allow it, as a U-Net plan would carry it (conv_pipe.hip FL_W4)
-    if (r == FC_OK && ksize == 3 && a.Cin % 32 == 0 && cout % 32 == 0 && std::getenv("FLOCODER_AMD_NO_K8") == nullptr) {
+    if (r == FC_OK && ksize == 3 && a.Cin % 32 == 0 && cout % 32 == 0) {
         FC_HIP(hipMalloc(reinterpret_cast<void**>(&wp8), (size_t)cout * a.Cin * 9 * sizeof(float)));
         r = pack_conv_k8_launch(w_oihw, wp8, cout, a.Cin, 9, s);
         a.w4 = wp8;

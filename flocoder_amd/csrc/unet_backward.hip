@@ -54,7 +54,7 @@ struct BwdBuilder : PlanBuilder {
     // Weight gradients themselves are deferred too (full-batch steps): every layer's launch is recorded as a table entry and all
     // entries of one kernel size run as ONE launch after the data-gradient chain.  Their operands (the layer input, possibly a
     // recomputed activation, and the output gradient) therefore stay alive to the end: release() leaves pinned buffers alone.
-    bool batch_wgrad = std::getenv("FLOCODER_AMD_WGRAD_EACH") == nullptr && std::getenv("FLOCODER_AMD_WGRAD_REDUCE_EACH") == nullptr;
+    bool batch_wgrad = std::getenv("FLOCODER_AMD_WGRAD_EACH") == nullptr;
     std::set<const float*> pinned;
     struct WgradClass { std::vector<WgradDev> jobs; std::vector<int2> blocks; size_t lds = 0; };
     std::map<int, WgradClass> wclasses;     // by kernel size
@@ -70,13 +70,12 @@ struct BwdBuilder : PlanBuilder {
         const int64_t wo = off(wname), bo = bname.empty() ? -1 : off(bname);
         // at the plan's full batch the launch keeps its partials in a workspace of its own and leaves the summation to the table launch
         int ns = 1; size_t stride_f = 0;
-        static const bool no_defer = std::getenv("FLOCODER_AMD_WGRAD_REDUCE_EACH") != nullptr;
         float* own = nullptr;
         // a table launch runs ~70 layers side by side: a quarter of the stand-alone split fills the chip, with a quarter of the partials
         static const int table_target = [] { const char* e = std::getenv("FLOCODER_AMD_WGRAD_TABLE_SPLIT"); return e ? std::atoi(e) : 256; }();
-        const bool to_table = batch_wgrad && !no_defer && guard == 0;
+        const bool to_table = batch_wgrad && guard == 0;
         if (to_table) a.split_target = table_target;
-        if (!no_defer && guard == 0 && conv_wgrad_split(a, &ns, &stride_f) == FC_OK && ns > 1) {   // guarded (mask-branch) launches may not run: they reduce on the spot
+        if (guard == 0 && conv_wgrad_split(a, &ns, &stride_f) == FC_OK && ns > 1) {   // guarded (mask-branch) launches may not run: they reduce on the spot
             own = dmalloc((size_t)ns * stride_f);
             if (err) return;
             wred_jobs.push_back({own, ns, a.Cout, stride_f, (size_t)a.Cout * a.Cin * KS * KS, wo, bo, a.Cin, KS * KS});
@@ -382,12 +381,11 @@ static size_t max_wgrad_ws(const fc_unet* u, const Plan& fw, int B) {
 
 int build_backward(fc_unet* u) {
     const fc_unet_config& c = u->cfg;
-    const Plan& fw = u->plan[0];
+    const Plan& fw = u->plan;
     u->bwd.release();
     u->dgrad_packs.clear();
     u->dgrad_table.release();
     u->dgrad_version = ~0ull;
-    if (u->nchains != 1) return fail(FC_E_STATE, "unet: training needs a single-chain plan (unset FLOCODER_AMD_CHAINS)");
     FC_TRY(conv_wgrad_init());
     const int B = fw.maxB, H = fw.H, W = fw.W, HW = H * W, dim = c.dim, ch = c.channels, td = u->td, S = u->S, ncls = c.n_classes;
     BwdBuilder b(u, &fw, &u->bwd, B);
@@ -531,7 +529,7 @@ int build_backward(fc_unet* u) {
     u->bwd_split_op = -1; u->grad_split = 0;
     // two buckets only for a trainer that asked for them (fc_unet_set_grad_buckets): a single process gains nothing from the second set of
     // table launches (stl_sd step 2.73 ms with them, 2.65 without)
-    const bool no_buckets = !u->want_buckets || std::getenv("FLOCODER_AMD_NO_GRAD_BUCKETS") != nullptr;
+    const bool no_buckets = !u->want_buckets;
     for (int i = (int)fw.tape.size() - 1; i >= 0 && !b.err; --i) {
         const TapeItem& t = fw.tape[i];
         if (t.kind == 0) {
@@ -668,7 +666,7 @@ int fc_unet_train_reserve(fc_unet* u, int max_batch, int height, int width) {
         }
     }
     FC_TRY(fc_unet_reserve(u, max_batch, height, width));
-    if (u->bwd.maxB == u->plan[0].maxB && u->bwd.H == height && u->bwd.W == width && u->bwd.maxB > 0) return FC_OK;
+    if (u->bwd.maxB == u->plan.maxB && u->bwd.H == height && u->bwd.W == width && u->bwd.maxB > 0) return FC_OK;
     FC_HIP(hipSetDevice(u->device));
     FC_HIP(hipDeviceSynchronize());
     const int r = build_backward(u);
@@ -705,7 +703,7 @@ int fc_unet_backward_parts(fc_unet* u, const float* x, const float* time, const 
                            const float* d_out, float* grads, int64_t numel, float* dx_out, float* dmask_out, int B, int H, int W,
                            int first_part, int last_part, void* stream) {
     if (!u || !x || !time || !d_out || !grads || B < 1) return fail(FC_E_ARG, "fc_unet_backward: null argument");
-    if (u->bwd.maxB < B || u->bwd.H != H || u->bwd.W != W || u->plan[0].maxB < B) return fail(FC_E_STATE, "unet: no backward plan for this shape; call fc_unet_train_reserve");
+    if (u->bwd.maxB < B || u->bwd.H != H || u->bwd.W != W || u->plan.maxB < B) return fail(FC_E_STATE, "unet: no backward plan for this shape; call fc_unet_train_reserve");
     if (numel != u->raw_numel) return fail(FC_E_ARG, "fc_unet_backward: gradient vector must have " + std::to_string(u->raw_numel) + " floats (padded table layout)");
     if (!u->loaded) return fail(FC_E_STATE, "unet: weights not loaded");
     if (u->arena_train_rows != B)

@@ -15,13 +15,9 @@ struct fc_unet : fc::ParamStore {
     std::unordered_map<std::string, int> ss_off;  // resblock prefix -> column offset
     float* freqs = nullptr;
 
-    // plans: the batch can run as `nchains` independent row ranges on concurrent streams (no cross-sample op exists in the
-    // network; FLOCODER_AMD_CHAINS=2).  Off by default: half-batch launches lose more than the overlap wins on one GPU.
-    int maxB = 0, H = 0, W = 0, nchains = 1;
-    fc::Plan plan[2];
+    int maxB = 0, H = 0, W = 0;
+    fc::Plan plan;                           // the forward launch plan for up to maxB rows
     std::vector<void*> int_allocs;           // integrator state
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
     // integrator state (library-owned so captured graphs never see caller pointers)
     hipStream_t stream = nullptr;

@@ -95,19 +95,15 @@ struct VBuilder : PlanBuilder {
     SrcXform gn(const Stat& st, const std::string& norm, int mode) { return xf_of(st, mode, v->R(norm + ".weight"), v->R(norm + ".bias"), nullptr, 0, kEps); }
 
     // Pre-norm input of a resnet convolution.  Round 3: one elementwise launch writes act(GN(x)) and the convolution reads that.  Rounds 1-2
-    // normalised in the convolution's staging waves and never materialised the tensor (FLOCODER_AMD_VAE_PRENORM=fused: still available), which
-    // saves one round trip through HBM but transforms every window element once per output-channel tile and halo copy -- ~10x at 512
-    // channels -- and VALU work of the staging waves does not overlap the MFMAs of the waves they share a SIMD with:
-    // measured per resnet, fp32: 1.40 -> 1.29 + 0.03 ms at 512 channels, 6.32 -> 5.79 + 0.43 ms at 128; split-bf16: 0.55 -> 0.45 + 0.03, 2.89 -> 2.38 + 0.43.
-    bool materialize_prenorm() const {
-        static const bool fused = [] { const char* e = std::getenv("FLOCODER_AMD_VAE_PRENORM"); return e && std::string(e) == "fused"; }();
-        return !fused;
-    }
-    // fills `src` for a convolution that reads x through `xf`; *tmp is the tensor to release after the convolution (or empty)
+    // normalised in the convolution's staging waves and never materialised the tensor, which saves one round trip through HBM but
+    // transforms every window element once per output-channel tile and halo copy -- ~10x at 512 channels -- and VALU work of the staging
+    // waves does not overlap the MFMAs of the waves they share a SIMD with: measured per resnet, fp32: 1.40 -> 1.29 + 0.03 ms
+    // at 512 channels, 6.32 -> 5.79 + 0.43 ms at 128; split-bf16: 0.55 -> 0.45 + 0.03, 2.89 -> 2.38 + 0.43.
+    // Fills `src` for a convolution that reads x through `xf`; *tmp is the tensor to release after the convolution (or empty).
     void prenorm_src(ConvSrc& src, const Act& x, const SrcXform& xf, Act* tmp) {
         src.p = x.p; src.C = x.C; src.xf = xf;
         *tmp = Act();
-        if (!materialize_prenorm() || err) return;
+        if (err) return;
         Act y = act(x.C, x.H, x.W);
         FinalizeArgs f;
         f.h = x.p; f.xf = xf; f.y = y.p; f.HW = x.H * x.W; f.C = x.C;

@@ -177,9 +177,8 @@ struct QBuilder : PlanBuilder {
             mid_in = a2; mid_raw = true;
         }
         // (round 3) without an attention in between, the activated tensor is materialised as well instead of being normalised in conv2's staging
-        // waves once per output-channel tile and halo copy (vae.hip prenorm_src has the measurements); FLOCODER_AMD_VAE_PRENORM=fused: as before
-        static const bool fused_prenorm = [] { const char* e = std::getenv("FLOCODER_AMD_VAE_PRENORM"); return e && std::string(e) == "fused"; }();
-        if (!mid_raw && !fused_prenorm && !err) {
+        // waves once per output-channel tile and halo copy (vae.hip prenorm_src has the measurements)
+        if (!mid_raw && !err) {
             Act a1 = act(co, Ho, Wo);
             FinalizeArgs f;
             f.h = h1.p; f.xf = mid_xf; f.y = a1.p; f.HW = Ho * Wo; f.C = co;

@@ -212,7 +212,7 @@ class Unet(nn.Module):
 
     @property
     def chains(self):
-        """(number of concurrent row-range chains, rows per chain) of the current plan."""
+        """(1, reserved rows): the plan runs the batch as one chain of rows (fc_unet_chains, kept for compatibility)."""
         rows = C.c_int(0)
         n = B.lib().fc_unet_chains(self._handle, C.byref(rows)) if self._handle else 0
         return n, rows.value
@@ -447,7 +447,7 @@ class Unet(nn.Module):
         lib, h = B.lib(), self._handle
         rows = C.c_int(0)
         lib.fc_unet_chains(h, C.byref(rows))
-        batch = min(batch, rows.value)                 # launches are timed at the rows one chain carries
+        batch = min(batch, rows.value)                 # launches are timed at no more than the reserved rows
         n = lib.fc_unet_plan_launches(h)
         ms = (C.c_float * n)()
         dev = self._handle_device

@@ -106,11 +106,10 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int batch, int heigh
                       const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev, int mask_is_ones,
                       void* stream);
 
-/* Number of kernel launches in one U-Net forward of the current plan, and its algorithmic FLOPs per
- * sample (2 x MACs over every conv / linear / attention contraction). */
-/* The reserved batch runs as this many independent row ranges ("chains") on concurrent streams; *rows_per_chain = the rows
- * each chain's plan holds (= the batch every kernel launch of that chain sees). */
+/* Kept for compatibility: the reserved batch always runs as ONE chain of rows on one stream, so this returns 1 and sets
+ * *rows_per_chain to the reserved batch (0 before fc_unet_reserve). */
 int fc_unet_chains(const fc_unet* u, int* rows_per_chain);
+/* Number of kernel launches in one U-Net forward of the current plan. */
 int fc_unet_plan_launches(const fc_unet* u);
 /* Fused Block tails meet the workgroups of a sample at a device-side counter (bounded wait).  *count = launches whose wait ever
  * timed out since the plan was built -- must be 0; anything else means the residency assumption broke and results are invalid.
@@ -133,8 +132,8 @@ int fc_unet_check(fc_unet* u, void* stream, int synchronize);
 /* Test hook: makes the next run of the plan's first meeting launch time out. */
 int fc_debug_unet_break_meeting(fc_unet* u);
 int fc_debug_unet_break_meeting_kind(fc_unet* u, int kind);   /* kind: 0 a convolution's Block tail, 1 the linear attention's fused close */
-/* Experiment switch: plans built after the call use (1) / do not use (0) the cross-workgroup Block tails; < 0 restores the default
- * (on, unless FLOCODER_AMD_FUSED_TAIL says otherwise). */
+/* Experiment switch: plans built after the call use (1) / do not use (0) the launches whose workgroups meet (cross-workgroup Block
+ * tails, the linear attention's fused close; tile-local Block tails stay); < 0 restores the default (on). */
 int fc_debug_set_fused_tail(int on);
 /* FLOPs per sample and evaluation as the REFERENCE computes the network (2 x MACs of every module, unet.py:289-372; SURVEY 8(d): 1.0008e9 at
  * dim 32) -- the unit of every end-to-end TFLOP/s figure.  Inference plans execute less where nn.Upsample + conv3x3 is folded into four 2x2
@@ -146,8 +145,7 @@ int fc_unet_op_info(const fc_unet* u, int i, const char** kernel, const char** m
  * once, per launch = the weights once -- the figure bench.py's roofline.traffic is read against. */
 int fc_unet_op_bytes(const fc_unet* u, int i, double* bytes_per_sample, double* bytes_per_launch);
 /* Measurement hook for bench.py: average device milliseconds of every launch of the plan at `batch` rows, each
- * timed alone with HIP events on `stream` over `repeats` back-to-back launches (`batch` is clamped to the rows of one
- * chain, see fc_unet_chains).  Synchronises. */
+ * timed alone with HIP events on `stream` over `repeats` back-to-back launches.  Synchronises. */
 int fc_unet_profile_ops(fc_unet* u, int batch, int repeats, float* ms_out, int n_out, void* stream);
 
 /* The sinusoidal frequency table exp(-k ln(1e4)/(dim/2-1)) (unet.py:26-27).  The library builds it in double

@@ -47,7 +47,7 @@ torch.cuda.synchronize()
 t = (time.perf_counter() - t0) / 3
 evals = (N - 1) * 4
 print(json.dumps({"ms": round(1e3 * t, 1), "samples_per_s": round(B / t, 1), "us_per_evaluation": round(1e6 * t / evals, 1), "finite": bool(torch.isfinite(lat).all()),
-                  "checksum": float(lat.double().abs().sum()), "chains": os.environ.get("FLOCODER_AMD_CHAINS"), "launches": unet.launches_per_forward}))
+                  "checksum": float(lat.double().abs().sum()), "launches": unet.launches_per_forward}))
 
 # the same 64 samples as K independent trajectories in flight (sampling.sample_many: K replicas, K streams)
 from flocoder_amd.sampling import sample_many  # noqa: E402

@@ -4,7 +4,7 @@
     python tools/conv_microbench.py [--batch 64] [--only NAME] [--tiles M128N32,M64N32K2,...]
 
 Prints, per layer shape and tile, microseconds per launch (back-to-back launches, warm caches) and TFLOP/s against
-the 157.3 TFLOP/s fp32-MFMA peak.  FLOCODER_AMD_CONV=simple selects the synchronous kernel for an A/B.
+the 157.3 TFLOP/s fp32-MFMA peak.
 """
 import argparse
 import os

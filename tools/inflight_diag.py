@@ -66,7 +66,7 @@ def main():
     noise, ids = bench.synthetic_inputs(0, 1, dev, per_rank=args.batch)
     shape = (args.batch,) + bench.LATENT
     env = {k: os.environ.get(k) for k in ("AMD_DIRECT_DISPATCH", "FLOCODER_AMD_POISON", "FLOCODER_AMD_NO_GRAPH", "FLOCODER_AMD_UPS_FOLD",
-                                           "FLOCODER_AMD_NO_PRECOND", "FLOCODER_AMD_NO_W4", "FLOCODER_AMD_LEAN_KERNELS")}
+                                           "FLOCODER_AMD_LEAN_KERNELS")}
     failed = False
 
     def poison():

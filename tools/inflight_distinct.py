@@ -51,7 +51,7 @@ def main():
     shared = [one(c, s) for c, s in zip(cls, srcs)]
     model.set_shared_device(None)
     torch.cuda.synchronize()
-    head = {"what": "one at a time", "method": args.method, "env": {k: os.environ.get(k) for k in ("AMD_DIRECT_DISPATCH", "FLOCODER_AMD_NO_GRAPH", "FLOCODER_AMD_NO_PRECOND")},
+    head = {"what": "one at a time", "method": args.method, "env": {k: os.environ.get(k) for k in ("AMD_DIRECT_DISPATCH", "FLOCODER_AMD_NO_GRAPH")},
             "shared_vs_exclusive": [rel(a, b) for a, b in zip(shared, excl)]}
     if args.oracle:
         from oracle import flow_oracle as fo
