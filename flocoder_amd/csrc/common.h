@@ -277,6 +277,35 @@ int ode_rk4_stage_launch(const float* sc, const float* y, float* xs, float* k_ou
 int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v2, int n,
                          int cfg_on, float cfg, hipStream_t s);
 
+// ---- adaptive RK45 (ode.hip): scipy's solve_ivp(method="RK45") with the controller on the device ----------------------------
+// Controller state and status record of one solve (fp64 as scipy; `failed`: 1 step size below spacing, 2 attempt cap).
+struct Rk45State {
+    double t, t_new, t_bound, dir, h, h_abs, rtol, atol, h0, d1, err;
+    int nfev, accepted, rejected, attempts, done, failed, step_rejected, accepted_last, max_attempts, pad;
+};
+struct Rk45K { float* k[7]; };             // stage derivatives K0..K6 (fp32, CFG-blended)
+int rk45_parts(int n);                     // partial sums the reduction kernels write (pairs of doubles)
+// y = double(x), xs = x, state for (t0 -> t1), time row of f(t0)
+int rk45_setup_launch(const float* x, double* y, float* xs, int n, Rk45State* st, double t0, double t1, double rtol, double atol,
+                      int max_attempts, float t_scale, float* tvec, int rows, hipStream_t s);
+// select_initial_step: K0 = f0 and d0/d1 partials | h0 and the time row of f1 | xs = y0 + h0 f0 | d2 partials | h1, first attempt
+int rk45_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int n, int cfg_on, float cfg, double* part, hipStream_t s);
+int rk45_h0_launch(Rk45State* st, const double* part, int n, float t_scale, float* tvec, int rows, hipStream_t s);
+int rk45_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int n, hipStream_t s);
+int rk45_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int n, int cfg_on, float cfg, double* part,
+                   hipStream_t s);
+int rk45_h1_launch(Rk45State* st, const double* part, int n, hipStream_t s);
+// one attempt: stages 1..5 (K[s-1] = blend(v2), xs = y + h sum A K), finish (K5, y_new), error partials (K6), controller, commit
+int rk45_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
+                      float* xs, float t_scale, float* tvec, int rows, hipStream_t s);
+int rk45_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
+                       float* xs, float t_scale, float* tvec, int rows, hipStream_t s);
+int rk45_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int n, int cfg_on,
+                      float cfg, double* part, hipStream_t s);
+int rk45_control_launch(Rk45State* st, const double* part, int n, hipStream_t s);
+int rk45_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int n, hipStream_t s);
+int rk45_out_launch(const double* y, float* x, int n, hipStream_t s);
+
 // ---- weight packing (pack.hip) ----------------------------------------------------------------
 struct PackJob { const float* src; float* dst; int kind, a, b, c, d, e; size_t total; };
 constexpr int kPackPerBlock = 4096;          // elements a workgroup of the table kernel moves

@@ -143,4 +143,374 @@ int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float
     return FC_OK;
 }
 
+
+// ================================================================================================ adaptive RK45
+// scipy.integrate.solve_ivp(method="RK45") as the legacy sampler calls it (legacy/train_sd_flowers.py:78-107): scipy 1.15's
+// _ivp/rk.py (rk_step, RungeKutta._step_impl, RK45 tableau) and _ivp/common.py (select_initial_step, norm).  One step size and one error
+// norm for the whole batch, as there.  y, y_new, the stage sums, the scale and the error are fp64; every forward gets float32(y_stage) and
+// time float32(t + c h) * t_scale (fp32); the stage derivatives K_i are the fp32 forwards (scipy's fp64 copies of them are exact).
+// Controller decisions happen on the device (Rk45State); the host only reads the status record behind each attempt.
+
+__constant__ double c_rk45_C[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
+__constant__ double c_rk45_A[6][5] = {
+    {0, 0, 0, 0, 0},
+    {1.0 / 5, 0, 0, 0, 0},
+    {3.0 / 40, 9.0 / 40, 0, 0, 0},
+    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
+    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
+    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
+__constant__ double c_rk45_B[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
+__constant__ double c_rk45_E[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+
+// Python's min(a, b) / max(a, b) (first argument unless the second compares smaller / larger: NaN handling as scipy sees it)
+__device__ __forceinline__ double py_min(double a, double b) { return b < a ? b : a; }
+__device__ __forceinline__ double py_max(double a, double b) { return b > a ? b : a; }
+// np.maximum: NaN propagates
+__device__ __forceinline__ double np_maximum(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
+
+// sum of a block's 256 per-thread values, fixed tree order; valid in thread 0
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// one workgroup: total of `nblk` partial sums (stride `stride`, offset `off`) in a fixed order
+__device__ __forceinline__ double reduce_parts(const double* part, int nblk, int stride, int off, double* red) {
+    double v = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) v += part[(size_t)b * stride + off];
+    const double r = block_sum(v, red);
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ float stage_time(double t, float t_scale) { return mul_((float)t, t_scale); }   // ones(B) * t * 999
+
+__device__ __forceinline__ void write_tvec(float* tvec, int rows, float tv) {
+    for (int r = threadIdx.x; r < rows; r += 256) tvec[r] = tv;
+}
+
+// RungeKutta._step_impl up to rk_step: the h and t_new of the next attempt.  `start`: a new step (after select_initial_step or an
+// acceptance) -- h_abs is raised to min_step there; after a rejection it is not, and h_abs < min_step fails.
+__device__ void rk45_next_attempt(Rk45State* st, bool start) {
+    const double t = st->t, dir = st->dir;
+    const double min_step = 10.0 * fabs(nextafter(t, dir * (double)INFINITY) - t);
+    double h_abs = st->h_abs;
+    if (start && h_abs < min_step) h_abs = min_step;     // (max_step is inf)
+    if (h_abs < min_step) { st->failed = 1; return; }
+    if (st->attempts >= st->max_attempts) { st->failed = 2; return; }
+    double h = h_abs * dir;
+    double t_new = t + h;
+    if (dir * (t_new - st->t_bound) > 0) t_new = st->t_bound;
+    h = t_new - t;
+    st->h = h; st->t_new = t_new; st->h_abs = fabs(h);
+}
+
+// y = double(x), xs = x (the first forward's input), controller state, time row of f(t0, y0)
+__global__ void __launch_bounds__(256) rk45_setup_kernel(const float* x, double* y, float* xs, int n, Rk45State* st, double t0, double t1,
+                                                         double rtol, double atol, int max_attempts, float t_scale, float* tvec, int rows) {
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) {
+            Rk45State s{};
+            s.t = t0; s.t_bound = t1; s.dir = t1 > t0 ? 1.0 : -1.0; s.rtol = rtol; s.atol = atol; s.max_attempts = max_attempts;
+            s.nfev = 1;
+            *st = s;
+        }
+        write_tvec(tvec, rows, stage_time(t0, t_scale));
+    }
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const float4 v = *reinterpret_cast<const float4*>(x + i);
+        *reinterpret_cast<float4*>(xs + i) = v;
+        *reinterpret_cast<double2*>(y + i) = make_double2(v.x, v.y);
+        *reinterpret_cast<double2*>(y + i + 2) = make_double2(v.z, v.w);
+    }
+}
+
+__device__ __forceinline__ void load_y4(const double* y, int i, double o[4]) {
+    const double2 a = *reinterpret_cast<const double2*>(y + i), b = *reinterpret_cast<const double2*>(y + i + 2);
+    o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
+}
+__device__ __forceinline__ void f4_to(const float4 v, double o[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+
+// select_initial_step, part 1: f0 = blend(v2) -> K0; partial sums of (y0/scale)^2 and (f0/scale)^2, scale = atol + |y0| rtol
+__global__ void __launch_bounds__(256) rk45_d01_kernel(const Rk45State* st, const double* y, float* k0, const float* v2, int n, int cfg_on,
+                                                       float cfg, double* part) {
+    __shared__ double red[256];
+    const double rtol = st->rtol, atol = st->atol;
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const float4 f = load_v(v2, i, n, cfg_on, cfg);
+        *reinterpret_cast<float4*>(k0 + i) = f;
+        double yv[4], fv[4];
+        load_y4(y, i, yv); f4_to(f, fv);
+        for (int j = 0; j < 4; ++j) {
+            const double sc = atol + fabs(yv[j]) * rtol;
+            const double a = yv[j] / sc, b = fv[j] / sc;
+            s0 += a * a; s1 += b * b;
+        }
+    }
+    const double r0 = block_sum(s0, red);
+    __syncthreads();
+    const double r1 = block_sum(s1, red);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = r0; part[2 * blockIdx.x + 1] = r1; }
+}
+
+// select_initial_step, part 2 (one workgroup): d0, d1 -> h0; time row of f(t0 + h0 dir, y1)
+__global__ void __launch_bounds__(256) rk45_h0_kernel(Rk45State* st, const double* part, int nblk, int n, float t_scale, float* tvec,
+                                                      int rows) {
+    __shared__ double red[256];
+    __shared__ double sh_h0;
+    const double s0 = reduce_parts(part, nblk, 2, 0, red), s1 = reduce_parts(part, nblk, 2, 1, red);
+    if (threadIdx.x == 0) {
+        const double rn = sqrt((double)n);
+        const double d0 = sqrt(s0) / rn, d1 = sqrt(s1) / rn;
+        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+        h0 = py_min(h0, fabs(st->t_bound - st->t));
+        st->h0 = h0; st->d1 = d1;
+        sh_h0 = h0;
+    }
+    __syncthreads();
+    write_tvec(tvec, rows, stage_time(st->t + sh_h0 * st->dir, t_scale));
+}
+
+// xs = float32(y0 + h0 dir f0)
+__global__ void __launch_bounds__(256) rk45_y1_kernel(const Rk45State* st, const double* y, const float* k0, float* xs, int n) {
+    const double hd = st->h0 * st->dir;
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        double yv[4], fv[4];
+        load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), fv);
+        float4 o;
+        o.x = (float)(yv[0] + hd * fv[0]); o.y = (float)(yv[1] + hd * fv[1]);
+        o.z = (float)(yv[2] + hd * fv[2]); o.w = (float)(yv[3] + hd * fv[3]);
+        *reinterpret_cast<float4*>(xs + i) = o;
+    }
+}
+
+// select_initial_step, part 3: partial sums of ((f1 - f0)/scale)^2
+__global__ void __launch_bounds__(256) rk45_d2_kernel(const Rk45State* st, const double* y, const float* k0, const float* v2, int n,
+                                                      int cfg_on, float cfg, double* part) {
+    __shared__ double red[256];
+    const double rtol = st->rtol, atol = st->atol;
+    double s = 0.0;
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        double yv[4], f0[4], f1[4];
+        load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), f0); f4_to(load_v(v2, i, n, cfg_on, cfg), f1);
+        for (int j = 0; j < 4; ++j) {
+            const double a = (f1[j] - f0[j]) / (atol + fabs(yv[j]) * rtol);
+            s += a * a;
+        }
+    }
+    const double r = block_sum(s, red);
+    if (threadIdx.x == 0) part[2 * blockIdx.x] = r;
+}
+
+// select_initial_step, part 4 (one workgroup): d2 -> h1 -> first step; the first attempt's h and t_new
+__global__ void __launch_bounds__(256) rk45_h1_kernel(Rk45State* st, const double* part, int nblk, int n) {
+    __shared__ double red[256];
+    const double s2 = reduce_parts(part, nblk, 2, 0, red);
+    if (threadIdx.x == 0) {
+        const double h0 = st->h0, d1 = st->d1;
+        const double d2 = sqrt(s2) / sqrt((double)n) / h0;
+        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? py_max(1e-6, h0 * 1e-3) : pow(0.01 / py_max(d1, d2), 1.0 / (4 + 1));
+        st->h_abs = py_min(py_min(100 * h0, h1), fabs(st->t_bound - st->t));
+        st->nfev = 2;
+        rk45_next_attempt(st, true);
+    }
+}
+
+// Stage s = 1..5 of rk_step: K[s-1] = blend(v2) (s >= 2; K0 is the committed f); xs = float32(y + (sum_{j<s} A[s][j] K_j) h);
+// time row of stage s.
+template <int s>
+__global__ void __launch_bounds__(256) rk45_stage_kernel(const Rk45State* st, const double* y, Rk45K kk, const float* v2, int n,
+                                                         int cfg_on, float cfg, float* xs, float t_scale, float* tvec, int rows) {
+    const double h = st->h;
+    if (blockIdx.x == 0) write_tvec(tvec, rows, stage_time(st->t + c_rk45_C[s] * h, t_scale));
+    float* kprev = kk.k[s - 1];
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0}, kv[4];
+#pragma unroll
+        for (int j = 0; j < s; ++j) {
+            float4 k;
+            if (j == s - 1 && s >= 2) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kprev + i) = k; }
+            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
+            f4_to(k, kv);
+            const double a = c_rk45_A[s][j];
+            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * a : acc[q] + kv[q] * a;
+        }
+        double yv[4];
+        load_y4(y, i, yv);
+        float4 o;
+        o.x = (float)(yv[0] + acc[0] * h); o.y = (float)(yv[1] + acc[1] * h);
+        o.z = (float)(yv[2] + acc[2] * h); o.w = (float)(yv[3] + acc[3] * h);
+        *reinterpret_cast<float4*>(xs + i) = o;
+    }
+}
+
+// K5 = blend(v2); y_new = y + h (sum_j B_j K_j); xs = float32(y_new); time row of f(t + h, y_new)
+__global__ void __launch_bounds__(256) rk45_finish_kernel(const Rk45State* st, const double* y, double* y_new, Rk45K kk,
+                                                          const float* v2, int n, int cfg_on, float cfg, float* xs, float t_scale,
+                                                          float* tvec, int rows) {
+    const double h = st->h;
+    if (blockIdx.x == 0) write_tvec(tvec, rows, stage_time(st->t + h, t_scale));
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        double acc[4], kv[4];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            float4 k;
+            if (j == 5) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[5] + i) = k; }
+            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
+            f4_to(k, kv);
+            const double b = c_rk45_B[j];
+            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * b : acc[q] + kv[q] * b;
+        }
+        double yv[4], o[4];
+        load_y4(y, i, yv);
+        for (int q = 0; q < 4; ++q) o[q] = yv[q] + h * acc[q];
+        *reinterpret_cast<double2*>(y_new + i) = make_double2(o[0], o[1]);
+        *reinterpret_cast<double2*>(y_new + i + 2) = make_double2(o[2], o[3]);
+        *reinterpret_cast<float4*>(xs + i) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+    }
+}
+
+// K6 = blend(v2) = f(t + h, y_new); partial sums of ((sum_j E_j K_j) h / scale)^2, scale = atol + max(|y|, |y_new|) rtol
+__global__ void __launch_bounds__(256) rk45_error_kernel(const Rk45State* st, const double* y, const double* y_new, Rk45K kk,
+                                                         const float* v2, int n, int cfg_on, float cfg, double* part) {
+    __shared__ double red[256];
+    const double h = st->h, rtol = st->rtol, atol = st->atol;
+    double s = 0.0;
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        double acc[4], kv[4];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            float4 k;
+            if (j == 6) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[6] + i) = k; }
+            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
+            f4_to(k, kv);
+            const double e = c_rk45_E[j];
+            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * e : acc[q] + kv[q] * e;
+        }
+        double yv[4], yn[4];
+        load_y4(y, i, yv); load_y4(y_new, i, yn);
+        for (int q = 0; q < 4; ++q) {
+            const double sc = atol + np_maximum(fabs(yv[q]), fabs(yn[q])) * rtol;
+            const double a = acc[q] * h / sc;
+            s += a * a;
+        }
+    }
+    const double r = block_sum(s, red);
+    if (threadIdx.x == 0) part[2 * blockIdx.x] = r;
+}
+
+// One workgroup: error norm, accept / reject (RungeKutta._step_impl), the next attempt, the status record
+__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int nblk, int n) {
+    __shared__ double red[256];
+    const double s = reduce_parts(part, nblk, 2, 0, red);
+    if (threadIdx.x != 0) return;
+    const double en = sqrt(s) / sqrt((double)n);
+    const double expo = -1.0 / (4 + 1);
+    st->err = en;
+    st->nfev += 6;
+    st->attempts += 1;
+    double h_abs = st->h_abs;
+    if (en < 1) {
+        double factor = en == 0 ? 10.0 : py_min(10.0, 0.9 * pow(en, expo));
+        if (st->step_rejected) factor = py_min(1.0, factor);
+        st->h_abs = h_abs * factor;
+        st->t = st->t_new;
+        st->accepted += 1;
+        st->accepted_last = 1;
+        st->step_rejected = 0;
+        if (st->dir * (st->t - st->t_bound) >= 0) { st->done = 1; return; }
+        rk45_next_attempt(st, true);
+    } else {
+        st->h_abs = h_abs * py_max(0.2, 0.9 * pow(en, expo));
+        st->rejected += 1;
+        st->accepted_last = 0;
+        st->step_rejected = 1;
+        rk45_next_attempt(st, false);
+    }
+}
+
+// on acceptance: y <- y_new, K0 <- K6 (FSAL)
+__global__ void __launch_bounds__(256) rk45_commit_kernel(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int n) {
+    if (!st->accepted_last) return;
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        *reinterpret_cast<double2*>(y + i) = *reinterpret_cast<const double2*>(y_new + i);
+        *reinterpret_cast<double2*>(y + i + 2) = *reinterpret_cast<const double2*>(y_new + i + 2);
+        *reinterpret_cast<float4*>(k0 + i) = *reinterpret_cast<const float4*>(k6 + i);
+    }
+}
+
+__global__ void __launch_bounds__(256) rk45_out_kernel(const double* y, float* x, int n) {
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        double yv[4];
+        load_y4(y, i, yv);
+        *reinterpret_cast<float4*>(x + i) = make_float4((float)yv[0], (float)yv[1], (float)yv[2], (float)yv[3]);
+    }
+}
+
+int rk45_parts(int n) { return egrid(n); }
+
+#define RK45_LAUNCH(kern, grid, ...)                                                    \
+    do {                                                                                \
+        if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4"); \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, __VA_ARGS__);             \
+        FC_HIP(hipGetLastError());                                                      \
+        return FC_OK;                                                                   \
+    } while (0)
+
+int rk45_setup_launch(const float* x, double* y, float* xs, int n, Rk45State* st, double t0, double t1, double rtol, double atol,
+                      int max_attempts, float t_scale, float* tvec, int rows, hipStream_t s) {
+    RK45_LAUNCH(rk45_setup_kernel, egrid(n), x, y, xs, n, st, t0, t1, rtol, atol, max_attempts, t_scale, tvec, rows);
+}
+int rk45_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int n, int cfg_on, float cfg, double* part, hipStream_t s) {
+    RK45_LAUNCH(rk45_d01_kernel, egrid(n), st, y, k0, v2, n, cfg_on, cfg, part);
+}
+int rk45_h0_launch(Rk45State* st, const double* part, int n, float t_scale, float* tvec, int rows, hipStream_t s) {
+    RK45_LAUNCH(rk45_h0_kernel, 1, st, part, egrid(n), n, t_scale, tvec, rows);
+}
+int rk45_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int n, hipStream_t s) {
+    RK45_LAUNCH(rk45_y1_kernel, egrid(n), st, y, k0, xs, n);
+}
+int rk45_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int n, int cfg_on, float cfg, double* part,
+                   hipStream_t s) {
+    RK45_LAUNCH(rk45_d2_kernel, egrid(n), st, y, k0, v2, n, cfg_on, cfg, part);
+}
+int rk45_h1_launch(Rk45State* st, const double* part, int n, hipStream_t s) {
+    RK45_LAUNCH(rk45_h1_kernel, 1, st, part, egrid(n), n);
+}
+int rk45_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
+                      float* xs, float t_scale, float* tvec, int rows, hipStream_t s) {
+    switch (stage) {
+        case 1: RK45_LAUNCH(rk45_stage_kernel<1>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+        case 2: RK45_LAUNCH(rk45_stage_kernel<2>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+        case 3: RK45_LAUNCH(rk45_stage_kernel<3>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+        case 4: RK45_LAUNCH(rk45_stage_kernel<4>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+        case 5: RK45_LAUNCH(rk45_stage_kernel<5>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+        default: return fail(FC_E_ARG, "rk45: stage must lie in [1, 5]");
+    }
+}
+int rk45_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
+                       float* xs, float t_scale, float* tvec, int rows, hipStream_t s) {
+    RK45_LAUNCH(rk45_finish_kernel, egrid(n), st, y, y_new, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+}
+int rk45_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int n, int cfg_on,
+                      float cfg, double* part, hipStream_t s) {
+    RK45_LAUNCH(rk45_error_kernel, egrid(n), st, y, y_new, kk, v2, n, cfg_on, cfg, part);
+}
+int rk45_control_launch(Rk45State* st, const double* part, int n, hipStream_t s) {
+    RK45_LAUNCH(rk45_control_kernel, 1, st, part, egrid(n), n);
+}
+int rk45_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int n, hipStream_t s) {
+    RK45_LAUNCH(rk45_commit_kernel, egrid(n), st, y, y_new, k0, k6, n);
+}
+int rk45_out_launch(const double* y, float* x, int n, hipStream_t s) {
+    RK45_LAUNCH(rk45_out_kernel, egrid(n), y, x, n);
+}
+#undef RK45_LAUNCH
+
 }  // namespace fc

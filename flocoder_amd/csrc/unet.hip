@@ -362,6 +362,7 @@ static void free_plan(fc_unet* u) {
     u->dgrad_table.release();
     for (void* p : u->int_allocs) dev_free(p);
     u->int_allocs.clear();
+    u->rk_y = u->rk_ynew = u->rk_part = nullptr; u->rk_k = Rk45K{}; u->rk_st = nullptr;   // (were in int_allocs)
     u->maxB = 0;
     // a rebuilt plan starts clean (callers of free_plan have synchronised the device)
     if (u->dev_err) (void)hipMemset(u->dev_err, 0, sizeof(int));
@@ -930,6 +931,8 @@ void fc_unet_destroy(fc_unet* u) {
     if (u->ev_meet) (void)hipEventDestroy(u->ev_meet);
     if (u->dev_err) (void)hipFree(u->dev_err);
     if (u->host_err) (void)hipHostFree(const_cast<int*>(u->host_err));
+    if (u->rk_host) (void)hipHostFree(u->rk_host);
+    if (u->ev_rk) (void)hipEventDestroy(u->ev_rk);
     delete u;
 }
 
@@ -1274,6 +1277,135 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
     FC_TRY(meet_leave(u, s));
     FC_HIP(hipEventRecord(u->ev_out, s));
     FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
+    return FC_OK;
+}
+
+// ---- adaptive RK45 ----------------------------------------------------------------------------------------------------------------
+static constexpr int kRk45MaxAttempts = 10000;     // a field that never settles raises instead of spinning (scipy has no such cap)
+static constexpr int kRk45Method = 2;              // graph-cache key of an attempt (beside FC_METHOD_EULER / FC_METHOD_RK4)
+
+static int alloc_rk45(fc_unet* u) {
+    const size_t nstate = (size_t)u->maxB * u->cfg.channels * u->H * u->W;
+    auto get = [&](size_t bytes, void** out) -> int {
+        FC_TRY(dev_alloc(out, bytes, "integrator.rk45"));
+        u->int_allocs.push_back(*out);
+        return FC_OK;
+    };
+    void* p = nullptr;
+    FC_TRY(get(nstate * sizeof(double), &p)); u->rk_y = static_cast<double*>(p);
+    FC_TRY(get(nstate * sizeof(double), &p)); u->rk_ynew = static_cast<double*>(p);
+    for (int j = 0; j < 7; ++j) { FC_TRY(get(nstate * sizeof(float), &p)); u->rk_k.k[j] = static_cast<float*>(p); }
+    FC_TRY(get(2 * (size_t)rk45_parts((int)nstate) * sizeof(double), &p)); u->rk_part = static_cast<double*>(p);
+    FC_TRY(get(sizeof(Rk45State), &p)); u->rk_st = static_cast<Rk45State*>(p);
+    return FC_OK;
+}
+
+// one attempt of RungeKutta._step_impl: five stages, y_new and f(t + h, y_new), the error norm, the controller, the commit
+static int enqueue_rk45_attempt(fc_unet* u, int B, bool cfg_on, float cfg, float t_scale, bool has_ids, int mask_mode, hipStream_t s) {
+    const int rows = cfg_on ? 2 * B : B, n = B * u->cfg.channels * u->H * u->W;
+    FwdCtx c;   // no conditioning table: each forward takes its time from u->tvec
+    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
+    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
+    c.out = u->v2; c.B = rows;
+    for (int st = 1; st <= 5; ++st) {
+        FC_TRY(rk45_stage_launch(u->rk_st, st, u->rk_y, u->rk_k, u->v2, n, cfg_on, cfg, u->xs, t_scale, u->tvec, rows, s));
+        FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
+    }
+    FC_TRY(rk45_finish_launch(u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, n, cfg_on, cfg, u->xs, t_scale, u->tvec, rows, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
+    FC_TRY(rk45_error_launch(u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, n, cfg_on, cfg, u->rk_part, s));
+    FC_TRY(rk45_control_launch(u->rk_st, u->rk_part, n, s));
+    return rk45_commit_launch(u->rk_st, u->rk_y, u->rk_ynew, u->rk_k.k[0], u->rk_k.k[6], n, s);
+}
+
+int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
+                                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
+                                      int* counters, void* stream) {
+    if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, "fc_unet_integrate_rk45: bad argument");
+    if (!(atol >= 0)) return fail(FC_E_ARG, "fc_unet_integrate_rk45: `atol` must be positive.");      // validate_tol
+    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, "fc_unet_integrate_rk45: t0 and t1 must be finite");
+    const double eps100 = 100 * 2.220446049250313e-16;
+    if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
+    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
+    const bool cfg_on = has_ids && cfg_strength != 0.0f;
+    const int rows = cfg_on ? 2 * B : B;
+    FC_TRY(check_ready(u, rows, H, W));
+    FC_TRY(check_poison(u));
+    counters[0] = 1; counters[1] = counters[2] = 0;
+    if (t0 == t1) return FC_OK;                  // scipy: one evaluation, no step, y0 returned
+    u->arena_touched(0);
+    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
+    const int n = B * u->cfg.channels * H * W;
+    const size_t nbytes = (size_t)n * sizeof(float);
+    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
+    FC_HIP(hipSetDevice(u->device));
+    if (!u->rk_st) FC_TRY(alloc_rk45(u));
+    if (!u->rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45State), hipHostMallocDefault)); u->rk_host = static_cast<Rk45State*>(hp); }
+    if (!u->ev_rk) FC_HIP(hipEventCreateWithFlags(&u->ev_rk, hipEventDisableTiming));
+
+    FC_HIP(hipEventRecord(u->ev_in, caller));
+    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
+    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
+    FC_TRY(meet_enter(u, s));
+
+    // f(t0, y0) and select_initial_step (two forwards, no graph)
+    FwdCtx c;
+    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
+    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
+    c.out = u->v2; c.B = rows;
+    const int cf = cfg_on ? 1 : 0;
+    FC_TRY(rk45_setup_launch(x_dev, u->rk_y, u->xs, n, u->rk_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, u->tvec, rows, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
+    FC_TRY(rk45_d01_launch(u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, n, cf, cfg_strength, u->rk_part, s));
+    FC_TRY(rk45_h0_launch(u->rk_st, u->rk_part, n, t_scale, u->tvec, rows, s));
+    FC_TRY(rk45_y1_launch(u->rk_st, u->rk_y, u->rk_k.k[0], u->xs, n, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
+    FC_TRY(rk45_d2_launch(u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, n, cf, cfg_strength, u->rk_part, s));
+    FC_TRY(rk45_h1_launch(u->rk_st, u->rk_part, n, s));
+    FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_st, sizeof(Rk45State), hipMemcpyDeviceToHost, s));
+    // This wait is also the one fc_unet_integrate makes before its first replay: under AMD_DIRECT_DISPATCH=0 a graph submitted from this
+    // thread can overtake the plain launches and copies queued just before it (see there).
+    FC_HIP(hipStreamSynchronize(s));
+
+    static const bool no_graph = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
+    const auto key = std::make_tuple(kRk45Method, B, (int)cfg_on, mask_mode, fbits(cfg_strength), 0u, fbits(t_scale), (int)has_ids);
+    int r = FC_OK;
+    while (r == FC_OK && !u->rk_host->done && !u->rk_host->failed) {
+        if (no_graph) {
+            r = enqueue_rk45_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
+            if (r != FC_OK) break;
+        } else {
+            auto it = u->graphs.find(key);
+            if (it == u->graphs.end()) {    // one attempt = one graph: 6 plan runs and 8 small launches, a single chain (no parallel branches)
+                hipGraph_t graph = nullptr;
+                FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+                r = enqueue_rk45_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
+                const hipError_t e = hipStreamEndCapture(s, &graph);
+                if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
+                if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+                hipGraphExec_t exec = nullptr;
+                FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+                FC_HIP(hipGraphDestroy(graph));
+                it = u->graphs.emplace(key, exec).first;
+            }
+            FC_HIP(hipGraphLaunch(it->second, s));
+        }
+        // the status record behind every attempt: one small host wait per six forwards
+        FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_st, sizeof(Rk45State), hipMemcpyDeviceToHost, s));
+        FC_HIP(hipEventRecord(u->ev_rk, s));
+        FC_HIP(hipEventSynchronize(u->ev_rk));
+    }
+    if (r != FC_OK) return r;
+    const Rk45State st = *u->rk_host;
+    counters[0] = st.nfev; counters[1] = st.accepted; counters[2] = st.rejected;
+    if (st.done) FC_TRY(rk45_out_launch(u->rk_y, x_dev, n, s));
+    FC_TRY(meet_leave(u, s));
+    FC_HIP(hipEventRecord(u->ev_out, s));
+    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
+    if (st.failed == 1) return fail(FC_E_STATE, "rk45: Required step size is less than spacing between numbers.");
+    if (st.failed) return fail(FC_E_STATE, "rk45: no convergence after " + std::to_string(st.attempts) + " attempts (t = " +
+                                               std::to_string(st.t) + ", h = " + std::to_string(st.h_abs) + ")");
     return FC_OK;
 }
 

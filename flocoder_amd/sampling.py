@@ -130,12 +130,73 @@ def euler_sampler(model, shape, sample_N, device=None, cond=None, source=None, e
     return x, sample_N
 
 
+def _validate_tol(rtol, atol):
+    """scipy/integrate/_ivp/common.py validate_tol for scalar tolerances."""
+    eps100 = 100 * float(torch.finfo(torch.float64).eps)
+    if rtol < eps100:
+        import warnings
+        warnings.warn(f"At least one element of `rtol` is too small. Setting `rtol = np.maximum(rtol, {eps100})`.", stacklevel=3)
+        rtol = eps100
+    if atol < 0:
+        raise ValueError("`atol` must be positive.")
+    return rtol, atol
+
+
+@torch.no_grad()
+def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rtol=1e-5, atol=1e-5, cfg_strength=0.0):
+    """Legacy adaptive sampler, train_sd_flowers.py:78-107: ``scipy.integrate.solve_ivp(method="RK45")`` over ``(eps, 1)`` on
+    ``model(float32(x), float32(t) * 999, cond)``; returns ``(latents, nfe)`` with nfe = scipy's ``solution.nfev``.  ``cond`` is a class-id
+    tensor as upstream or a cond dict; ``source`` replaces the randn start; ``cfg_strength`` is an extension (0 keeps upstream behaviour;
+    a guided pair counts as one evaluation).  The batch is ONE system of B*C*H*W unknowns with one step size and one error norm, as
+    upstream, so a sample's trajectory depends on the rest of its batch.  A ``flocoder_amd.Unet`` runs the whole solve in the library
+    (Unet.integrate_rk45: stages, error norm and step controller on the device); any other model takes the legacy host path through
+    numpy.  Where scipy would return ``success=False`` (step size below the spacing of t) this raises RuntimeError -- the legacy code
+    silently used the last state."""
+    rtol, atol = _validate_tol(rtol, atol)
+    p0 = next(model.parameters())
+    device = p0.device if device is None else torch.device(device)
+    if cond is not None and not isinstance(cond, dict):
+        cond = {'class_cond': cond}
+    x = (source if source is not None else torch.randn(shape, device=device)).to(device=device, dtype=torch.float32).contiguous().clone()
+    if isinstance(model, Unet):
+        cls = cond.get('class_cond') if cond else None
+        mask, ones = _mask_flags(cond)
+        nfev, _, _ = model.integrate_rk45(x, eps, 1.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
+                                          mask_is_ones=ones)
+        return x, nfev
+
+    import numpy as np
+    from scipy import integrate
+    shape = tuple(x.shape)
+    t_vec_template = torch.zeros(shape[0], device=device)
+
+    def ode_func(t, y):
+        xt = torch.from_numpy(np.asarray(y).reshape(shape)).to(device).type(torch.float32)
+        drift = v_func_cfg(model, cond, cfg_strength, t_vec_template, xt, t)
+        return drift.detach().cpu().numpy().reshape((-1,))
+
+    solution = integrate.solve_ivp(ode_func, (eps, 1), x.detach().cpu().numpy().reshape((-1,)), rtol=rtol, atol=atol, method="RK45")
+    if not solution.success:
+        raise RuntimeError(f"rk45_sampler: {solution.message}")
+    return torch.tensor(solution.y[:, -1]).reshape(shape).type(torch.float32).to(device), solution.nfev
+
+
+@torch.no_grad()
+def generate_latents_rk45(model, shape, device=None, cond=None, cfg_strength=3.0, source=None, rtol=1e-5, atol=1e-5):
+    """The function sampling.py:142-143 dispatches to (undefined upstream): the legacy RK45 sampler over (1e-3, 1), no time warp, with
+    classifier-free guidance as generate_latents_rk4 applies it.  Returns (latents, nfe)."""
+    return rk45_sampler(model, shape, device=device, cond=cond, source=source, eps=1e-3, rtol=rtol, atol=atol, cfg_strength=cfg_strength)
+
+
 @torch.no_grad()
 def generate_latents(model, shape, method='rk4', n_steps=50, cond=None, cfg_strength=3.0, device=None, source=None,
                      init_latents=None, init_strength=0.0, debug=False):
-    """sampling.py:128-146.  'rk45' is undefined upstream; 'euler' selects the legacy sampler."""
+    """sampling.py:128-146.  'rk45' selects generate_latents_rk45 (undefined upstream; built here from the legacy RK45
+    sampler); 'euler' selects the legacy sampler."""
     if method == "rk45":
-        raise NameError("generate_latents_rk45 is not defined in the reference either (sampling.py:142-143)")
+        if init_latents is not None:
+            raise ValueError("init_latents is not defined for method='rk45' (upstream has no such integration)")
+        return generate_latents_rk45(model, shape, device, cond, cfg_strength, source=source)
     if method == "euler":
         # (the legacy sampler has no guidance upstream: generate_latents keeps that; sample_many forwards its cfg_strength itself)
         return euler_sampler(model, shape, n_steps, device=device, cond=cond, source=source)

@@ -441,6 +441,51 @@ class Unet(nn.Module):
             B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
         return x
 
+    def integrate_rk45(self, x: torch.Tensor, t0: float, t1: float, *, rtol: float, atol: float, t_scale: float = 999.0,
+                       class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,
+                       mask_is_ones: bool = False, check: bool = True) -> Tuple[int, int, int]:
+        """Integrate ``x`` in place from ``t0`` to ``t1`` with scipy's adaptive RK45 (``fc_unet_integrate_rk45``: solve_ivp semantics,
+        one step size and one error norm for the whole batch, so a sample's trajectory depends on the rest of its batch as upstream).
+        Synchronous: the host waits for a small status record behind every attempt of six evaluations.  Returns ``(nfev, accepted,
+        rejected)``; ``nfev`` is scipy's ``solution.nfev`` (a CFG pair counts once).  Raises RuntimeError when the step size falls below
+        the spacing of t (scipy's ``success=False``) and ValueError for ``atol < 0``."""
+        if not x.is_cuda:
+            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+        if atol < 0:
+            raise ValueError("`atol` must be positive.")
+        eps100 = 100 * float(torch.finfo(torch.float64).eps)
+        if rtol < eps100:
+            import warnings
+            warnings.warn(f"At least one element of `rtol` is too small. Setting `rtol = np.maximum(rtol, {eps100})`.", stacklevel=2)
+            rtol = eps100
+        dev = x.device
+        bsz, ch, h, w = x.shape
+        if not x.is_contiguous() or x.dtype != torch.float32:
+            raise ValueError("x must be a contiguous fp32 tensor (it is updated in place)")
+        if class_ids is not None and not self.class_condition:
+            class_ids = None
+        if class_ids is not None:
+            class_ids = class_ids.to(device=dev, dtype=torch.int64).contiguous()
+            if class_ids.shape != (bsz,):
+                raise ValueError("class ids must have shape [batch]")
+            self.check_class_ids(class_ids)
+        if mask is not None and not self._cfg.mask_cond:
+            mask = None
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+            if mask.shape != x.shape:
+                raise ValueError("mask_cond must have the shape of x")
+        rows = bsz * (2 if (class_ids is not None and cfg_strength) else 1)
+        hnd = self._native(dev)
+        B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
+        counters = (C.c_int * 3)()
+        B.check(B.lib().fc_unet_integrate_rk45(hnd, B.ptr(x), bsz, h, w, float(t0), float(t1), float(rtol), float(atol), float(t_scale),
+                                               B.ptr(class_ids), float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), counters,
+                                               B.current_stream(dev)))
+        if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
+            B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
+        return int(counters[0]), int(counters[1]), int(counters[2])
+
     def profile_ops(self, batch: int, repeats: int = 20):
         """Per-launch device time of the current plan (bench.py's live roofline measurement).  Run a forward or an
         integration first so the internal state holds finite data.  Returns a list of dicts."""

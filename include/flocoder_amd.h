@@ -106,6 +106,22 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int batch, int heigh
                       const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev, int mask_is_ones,
                       void* stream);
 
+/* Adaptive RK45: scipy.integrate.solve_ivp(f, (t0, t1), y0, method="RK45", rtol, atol) as the legacy evaluation sampler calls it
+ * (legacy/train_sd_flowers.py:78-107), with f(t, y) = U-Net(float32(y), float32(t) * t_scale) [CFG-blended as fc_unet_integrate].
+ * scipy 1.15 semantics (_ivp/rk.py, _ivp/common.py): Dormand-Prince 5(4) with FSAL, select_initial_step, RMS error norm over ALL
+ * batch*C*H*W unknowns -- ONE step size for the whole batch, so a sample's trajectory depends on the rest of its batch, as upstream.
+ * y, y_new, stage sums and the error are fp64; the forwards take and return fp32.  x_dev [B,C,H,W] is replaced by float32(y(t1)).
+ * counters[3] (host) = { nfev (scipy's solution.nfev; a CFG pair counts once), accepted steps, rejected attempts }.
+ * atol < 0 -> FC_E_ARG; rtol below 100 eps is raised to 100 eps.  A step below the spacing of t ("Required step size is less than
+ * spacing between numbers.") or an internal cap on attempts -> FC_E_STATE, x_dev untouched.
+ * One attempt (6 forwards + 8 small launches) is a captured hipGraph per (B, cfg, mask, class ids) variant; the controller runs on the
+ * device and the host reads a status record behind each replay.  Unlike fc_unet_integrate this call is SYNCHRONOUS with respect to
+ * the library stream (it must see when the solve ends): on return the result is queued on `stream` behind the solve.  The extra
+ * state (fp64 y / y_new, K0..K6) is allocated by the first call, not by fc_unet_reserve. */
+int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int batch, int height, int width, double t0, double t1, double rtol, double atol,
+                           float t_scale, const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev, int mask_is_ones,
+                           int* counters, void* stream);
+
 /* Kept for compatibility: the reserved batch always runs as ONE chain of rows on one stream, so this returns 1 and sets
  * *rows_per_chain to the reserved batch (0 before fc_unet_reserve). */
 int fc_unet_chains(const fc_unet* u, int* rows_per_chain);
