@@ -306,6 +306,30 @@ int rk45_control_launch(Rk45State* st, const double* part, int n, hipStream_t s)
 int rk45_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int n, hipStream_t s);
 int rk45_out_launch(const double* y, float* x, int n, hipStream_t s);
 
+// ---- per-sample adaptive RK45 (ode.hip): every sample of B its own solve_ivp problem over its m = C*H*W unknowns --------------
+// st[B] holds one controller per sample; partial sums are [B][rk45ps_chunks(m)][2] (the partition depends on m only); the rows of
+// sample b are b and, with CFG, B + b.  The launches mirror the batch-coupled ones above.
+struct Rk45Status { int unfinished, failed, pad0, pad1; };   // samples still stepping / failed: what the host reads behind an attempt
+int rk45ps_chunks(int m);                  // workgroups per sample of the elementwise and partial-sum kernels
+int rk45ps_setup_launch(const float* x, double* y, float* xs, int B, int m, Rk45State* st, double t0, double t1, double rtol, double atol,
+                        int max_attempts, float t_scale, float* tvec, int cfg_on, hipStream_t s);
+int rk45ps_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
+                      hipStream_t s);
+int rk45ps_h0_launch(Rk45State* st, const double* part, int B, int m, float t_scale, float* tvec, int cfg_on, hipStream_t s);
+int rk45ps_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int B, int m, hipStream_t s);
+int rk45ps_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
+                     hipStream_t s);
+int rk45ps_h1_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s);
+int rk45ps_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
+                        float* xs, float t_scale, float* tvec, hipStream_t s);
+int rk45ps_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
+                         float* xs, float t_scale, float* tvec, hipStream_t s);
+int rk45ps_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on,
+                        float cfg, double* part, hipStream_t s);
+int rk45ps_control_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s);
+int rk45ps_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int B, int m, hipStream_t s);
+int rk45ps_status_launch(const Rk45State* st, int B, Rk45Status* out, hipStream_t s);
+
 // ---- weight packing (pack.hip) ----------------------------------------------------------------
 struct PackJob { const float* src; float* dst; int kind, a, b, c, d, e; size_t total; };
 constexpr int kPackPerBlock = 4096;          // elements a workgroup of the table kernel moves

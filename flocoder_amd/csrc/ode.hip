@@ -259,20 +259,23 @@ __global__ void __launch_bounds__(256) rk45_d01_kernel(const Rk45State* st, cons
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = r0; part[2 * blockIdx.x + 1] = r1; }
 }
 
+// select_initial_step up to h0, from the sums of (y0/scale)^2 and (f0/scale)^2 over n unknowns; returns h0
+__device__ __forceinline__ double rk45_select_h0(Rk45State* st, double s0, double s1, int n) {
+    const double rn = sqrt((double)n);
+    const double d0 = sqrt(s0) / rn, d1 = sqrt(s1) / rn;
+    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    h0 = py_min(h0, fabs(st->t_bound - st->t));
+    st->h0 = h0; st->d1 = d1;
+    return h0;
+}
+
 // select_initial_step, part 2 (one workgroup): d0, d1 -> h0; time row of f(t0 + h0 dir, y1)
 __global__ void __launch_bounds__(256) rk45_h0_kernel(Rk45State* st, const double* part, int nblk, int n, float t_scale, float* tvec,
                                                       int rows) {
     __shared__ double red[256];
     __shared__ double sh_h0;
     const double s0 = reduce_parts(part, nblk, 2, 0, red), s1 = reduce_parts(part, nblk, 2, 1, red);
-    if (threadIdx.x == 0) {
-        const double rn = sqrt((double)n);
-        const double d0 = sqrt(s0) / rn, d1 = sqrt(s1) / rn;
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = py_min(h0, fabs(st->t_bound - st->t));
-        st->h0 = h0; st->d1 = d1;
-        sh_h0 = h0;
-    }
+    if (threadIdx.x == 0) sh_h0 = rk45_select_h0(st, s0, s1, n);
     __syncthreads();
     write_tvec(tvec, rows, stage_time(st->t + sh_h0 * st->dir, t_scale));
 }
@@ -308,18 +311,21 @@ __global__ void __launch_bounds__(256) rk45_d2_kernel(const Rk45State* st, const
     if (threadIdx.x == 0) part[2 * blockIdx.x] = r;
 }
 
+// select_initial_step from the sum of ((f1 - f0)/scale)^2 over n unknowns: h1, the first step, the first attempt
+__device__ __forceinline__ void rk45_select_h1(Rk45State* st, double s2, int n) {
+    const double h0 = st->h0, d1 = st->d1;
+    const double d2 = sqrt(s2) / sqrt((double)n) / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? py_max(1e-6, h0 * 1e-3) : pow(0.01 / py_max(d1, d2), 1.0 / (4 + 1));
+    st->h_abs = py_min(py_min(100 * h0, h1), fabs(st->t_bound - st->t));
+    st->nfev = 2;
+    rk45_next_attempt(st, true);
+}
+
 // select_initial_step, part 4 (one workgroup): d2 -> h1 -> first step; the first attempt's h and t_new
 __global__ void __launch_bounds__(256) rk45_h1_kernel(Rk45State* st, const double* part, int nblk, int n) {
     __shared__ double red[256];
     const double s2 = reduce_parts(part, nblk, 2, 0, red);
-    if (threadIdx.x == 0) {
-        const double h0 = st->h0, d1 = st->d1;
-        const double d2 = sqrt(s2) / sqrt((double)n) / h0;
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? py_max(1e-6, h0 * 1e-3) : pow(0.01 / py_max(d1, d2), 1.0 / (4 + 1));
-        st->h_abs = py_min(py_min(100 * h0, h1), fabs(st->t_bound - st->t));
-        st->nfev = 2;
-        rk45_next_attempt(st, true);
-    }
+    if (threadIdx.x == 0) rk45_select_h1(st, s2, n);
 }
 
 // Stage s = 1..5 of rk_step: K[s-1] = blend(v2) (s >= 2; K0 is the committed f); xs = float32(y + (sum_{j<s} A[s][j] K_j) h);
@@ -405,12 +411,8 @@ __global__ void __launch_bounds__(256) rk45_error_kernel(const Rk45State* st, co
     if (threadIdx.x == 0) part[2 * blockIdx.x] = r;
 }
 
-// One workgroup: error norm, accept / reject (RungeKutta._step_impl), the next attempt, the status record
-__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int nblk, int n) {
-    __shared__ double red[256];
-    const double s = reduce_parts(part, nblk, 2, 0, red);
-    if (threadIdx.x != 0) return;
-    const double en = sqrt(s) / sqrt((double)n);
+// Accept / reject on the error norm `en` (RungeKutta._step_impl), the next attempt, the status record
+__device__ __forceinline__ void rk45_decide(Rk45State* st, double en) {
     const double expo = -1.0 / (4 + 1);
     st->err = en;
     st->nfev += 6;
@@ -433,6 +435,14 @@ __global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const 
         st->step_rejected = 1;
         rk45_next_attempt(st, false);
     }
+}
+
+// One workgroup: error norm, then rk45_decide
+__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int nblk, int n) {
+    __shared__ double red[256];
+    const double s = reduce_parts(part, nblk, 2, 0, red);
+    if (threadIdx.x != 0) return;
+    rk45_decide(st, sqrt(s) / sqrt((double)n));
 }
 
 // on acceptance: y <- y_new, K0 <- K6 (FSAL)
@@ -512,5 +522,334 @@ int rk45_out_launch(const double* y, float* x, int n, hipStream_t s) {
     RK45_LAUNCH(rk45_out_kernel, egrid(n), y, x, n);
 }
 #undef RK45_LAUNCH
+
+// ================================================================================================ per-sample adaptive RK45
+// Every sample b is its own solve_ivp problem over its m = C*H*W unknowns: its own select_initial_step, error norm, step size,
+// accept / reject decisions and counters (st[b]), with the arithmetic of the batch-coupled kernels above.  The elementwise and
+// reduction kernels run on a (chunks, B) grid: blockIdx.y is the sample, and its `chunks` workgroups stride over its m unknowns.
+// `chunks` depends on m alone, so the fp64 partial sums of a sample's norms ([B][chunks][2]) -- reduced in a fixed order by one
+// workgroup per sample -- and with them its step sequence do not depend on the batch size or on the other samples.  A sample that
+// has finished or failed keeps h = 0: its rows are still evaluated (at float32(y), t), its state, counters and K stay as they are.
+
+int rk45ps_chunks(int m) { int g = (m / 4 + 255) / 256; return g < 1 ? 1 : (g > 64 ? 64 : g); }
+
+__device__ __forceinline__ bool rk45_live(const Rk45State& s) { return !s.done && !s.failed; }
+
+// after a decision: a finished or failed sample keeps h = 0
+__device__ __forceinline__ void rk45ps_freeze(Rk45State* st) {
+    if (!rk45_live(*st)) { st->h = 0.0; st->t_new = st->t; }
+}
+
+// the time rows of sample b: row b, and with CFG its unguided twin B + b
+__device__ __forceinline__ void write_trow(float* tvec, int b, int B, int cfg_on, float tv) {
+    tvec[b] = tv;
+    if (cfg_on) tvec[B + b] = tv;
+}
+
+// xs = float32(y) over this workgroup's part of sample b (the rows of a sample that no longer steps)
+__device__ __forceinline__ void rk45ps_hold(const double* y, float* xs, int base, int m) {
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        double yv[4];
+        load_y4(y, base + j, yv);
+        *reinterpret_cast<float4*>(xs + base + j) = make_float4((float)yv[0], (float)yv[1], (float)yv[2], (float)yv[3]);
+    }
+}
+
+__device__ __forceinline__ double* ps_part(double* part, int b) { return part + 2 * ((size_t)b * gridDim.x + blockIdx.x); }
+
+__global__ void __launch_bounds__(256) rk45ps_setup_kernel(const float* x, double* y, float* xs, int m, Rk45State* st, double t0, double t1,
+                                                           double rtol, double atol, int max_attempts, float t_scale, float* tvec,
+                                                           int cfg_on) {
+    const int b = blockIdx.y, base = b * m;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        Rk45State s{};
+        s.t = t0; s.t_bound = t1; s.dir = t1 > t0 ? 1.0 : -1.0; s.rtol = rtol; s.atol = atol; s.max_attempts = max_attempts;
+        s.nfev = 1;
+        st[b] = s;
+        write_trow(tvec, b, gridDim.y, cfg_on, stage_time(t0, t_scale));
+    }
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const float4 v = *reinterpret_cast<const float4*>(x + base + j);
+        *reinterpret_cast<float4*>(xs + base + j) = v;
+        *reinterpret_cast<double2*>(y + base + j) = make_double2(v.x, v.y);
+        *reinterpret_cast<double2*>(y + base + j + 2) = make_double2(v.z, v.w);
+    }
+}
+
+__global__ void __launch_bounds__(256) rk45ps_d01_kernel(const Rk45State* st, const double* y, float* k0, const float* v2, int m,
+                                                         int cfg_on, float cfg, double* part) {
+    __shared__ double red[256];
+    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
+    const double rtol = st[b].rtol, atol = st[b].atol;
+    double s0 = 0.0, s1 = 0.0;
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const int i = base + j;
+        const float4 f = load_v(v2, i, n, cfg_on, cfg);
+        *reinterpret_cast<float4*>(k0 + i) = f;
+        double yv[4], fv[4];
+        load_y4(y, i, yv); f4_to(f, fv);
+        for (int q = 0; q < 4; ++q) {
+            const double sc = atol + fabs(yv[q]) * rtol;
+            const double a = yv[q] / sc, c = fv[q] / sc;
+            s0 += a * a; s1 += c * c;
+        }
+    }
+    const double r0 = block_sum(s0, red);
+    __syncthreads();
+    const double r1 = block_sum(s1, red);
+    if (threadIdx.x == 0) { double* p = ps_part(part, b); p[0] = r0; p[1] = r1; }
+}
+
+// one workgroup per sample
+__global__ void __launch_bounds__(256) rk45ps_h0_kernel(Rk45State* st, const double* part, int chunks, int m, float t_scale, float* tvec,
+                                                        int cfg_on) {
+    __shared__ double red[256];
+    const int b = blockIdx.x;
+    const double* p = part + 2 * (size_t)b * chunks;
+    const double s0 = reduce_parts(p, chunks, 2, 0, red), s1 = reduce_parts(p, chunks, 2, 1, red);
+    if (threadIdx.x == 0) {
+        Rk45State* sb = st + b;
+        const double h0 = rk45_select_h0(sb, s0, s1, m);
+        write_trow(tvec, b, gridDim.x, cfg_on, stage_time(sb->t + h0 * sb->dir, t_scale));
+    }
+}
+
+__global__ void __launch_bounds__(256) rk45ps_y1_kernel(const Rk45State* st, const double* y, const float* k0, float* xs, int m) {
+    const int b = blockIdx.y, base = b * m;
+    const double hd = st[b].h0 * st[b].dir;
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const int i = base + j;
+        double yv[4], fv[4];
+        load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), fv);
+        float4 o;
+        o.x = (float)(yv[0] + hd * fv[0]); o.y = (float)(yv[1] + hd * fv[1]);
+        o.z = (float)(yv[2] + hd * fv[2]); o.w = (float)(yv[3] + hd * fv[3]);
+        *reinterpret_cast<float4*>(xs + i) = o;
+    }
+}
+
+__global__ void __launch_bounds__(256) rk45ps_d2_kernel(const Rk45State* st, const double* y, const float* k0, const float* v2, int m,
+                                                        int cfg_on, float cfg, double* part) {
+    __shared__ double red[256];
+    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
+    const double rtol = st[b].rtol, atol = st[b].atol;
+    double s = 0.0;
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const int i = base + j;
+        double yv[4], f0[4], f1[4];
+        load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), f0); f4_to(load_v(v2, i, n, cfg_on, cfg), f1);
+        for (int q = 0; q < 4; ++q) {
+            const double a = (f1[q] - f0[q]) / (atol + fabs(yv[q]) * rtol);
+            s += a * a;
+        }
+    }
+    const double r = block_sum(s, red);
+    if (threadIdx.x == 0) ps_part(part, b)[0] = r;
+}
+
+// one workgroup per sample
+__global__ void __launch_bounds__(256) rk45ps_h1_kernel(Rk45State* st, const double* part, int chunks, int m) {
+    __shared__ double red[256];
+    const int b = blockIdx.x;
+    const double s2 = reduce_parts(part + 2 * (size_t)b * chunks, chunks, 2, 0, red);
+    if (threadIdx.x == 0) {
+        rk45_select_h1(st + b, s2, m);
+        rk45ps_freeze(st + b);
+    }
+}
+
+template <int s>
+__global__ void __launch_bounds__(256) rk45ps_stage_kernel(const Rk45State* st, const double* y, Rk45K kk, const float* v2, int m,
+                                                           int cfg_on, float cfg, float* xs, float t_scale, float* tvec) {
+    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
+    const double h = st[b].h;
+    if (blockIdx.x == 0 && threadIdx.x == 0) write_trow(tvec, b, gridDim.y, cfg_on, stage_time(st[b].t + c_rk45_C[s] * h, t_scale));
+    if (!rk45_live(st[b])) { rk45ps_hold(y, xs, base, m); return; }
+    float* kprev = kk.k[s - 1];
+    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+        const int i = base + jj;
+        double acc[4] = {0.0, 0.0, 0.0, 0.0}, kv[4];
+#pragma unroll
+        for (int j = 0; j < s; ++j) {
+            float4 k;
+            if (j == s - 1 && s >= 2) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kprev + i) = k; }
+            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
+            f4_to(k, kv);
+            const double a = c_rk45_A[s][j];
+            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * a : acc[q] + kv[q] * a;
+        }
+        double yv[4];
+        load_y4(y, i, yv);
+        float4 o;
+        o.x = (float)(yv[0] + acc[0] * h); o.y = (float)(yv[1] + acc[1] * h);
+        o.z = (float)(yv[2] + acc[2] * h); o.w = (float)(yv[3] + acc[3] * h);
+        *reinterpret_cast<float4*>(xs + i) = o;
+    }
+}
+
+__global__ void __launch_bounds__(256) rk45ps_finish_kernel(const Rk45State* st, const double* y, double* y_new, Rk45K kk,
+                                                            const float* v2, int m, int cfg_on, float cfg, float* xs, float t_scale,
+                                                            float* tvec) {
+    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
+    const double h = st[b].h;
+    if (blockIdx.x == 0 && threadIdx.x == 0) write_trow(tvec, b, gridDim.y, cfg_on, stage_time(st[b].t + h, t_scale));
+    if (!rk45_live(st[b])) { rk45ps_hold(y, xs, base, m); return; }
+    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+        const int i = base + jj;
+        double acc[4], kv[4];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            float4 k;
+            if (j == 5) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[5] + i) = k; }
+            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
+            f4_to(k, kv);
+            const double c = c_rk45_B[j];
+            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * c : acc[q] + kv[q] * c;
+        }
+        double yv[4], o[4];
+        load_y4(y, i, yv);
+        for (int q = 0; q < 4; ++q) o[q] = yv[q] + h * acc[q];
+        *reinterpret_cast<double2*>(y_new + i) = make_double2(o[0], o[1]);
+        *reinterpret_cast<double2*>(y_new + i + 2) = make_double2(o[2], o[3]);
+        *reinterpret_cast<float4*>(xs + i) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+    }
+}
+
+__global__ void __launch_bounds__(256) rk45ps_error_kernel(const Rk45State* st, const double* y, const double* y_new, Rk45K kk,
+                                                           const float* v2, int m, int cfg_on, float cfg, double* part) {
+    __shared__ double red[256];
+    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
+    const double h = st[b].h, rtol = st[b].rtol, atol = st[b].atol;
+    double s = 0.0;
+    if (rk45_live(st[b])) {
+        for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+            const int i = base + jj;
+            double acc[4], kv[4];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                float4 k;
+                if (j == 6) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[6] + i) = k; }
+                else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
+                f4_to(k, kv);
+                const double e = c_rk45_E[j];
+                for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * e : acc[q] + kv[q] * e;
+            }
+            double yv[4], yn[4];
+            load_y4(y, i, yv); load_y4(y_new, i, yn);
+            for (int q = 0; q < 4; ++q) {
+                const double sc = atol + np_maximum(fabs(yv[q]), fabs(yn[q])) * rtol;
+                const double a = acc[q] * h / sc;
+                s += a * a;
+            }
+        }
+    }
+    const double r = block_sum(s, red);
+    if (threadIdx.x == 0) ps_part(part, b)[0] = r;
+}
+
+// one workgroup per sample: its error norm and decision; a sample that no longer steps only clears accepted_last
+__global__ void __launch_bounds__(256) rk45ps_control_kernel(Rk45State* st, const double* part, int chunks, int m) {
+    __shared__ double red[256];
+    const int b = blockIdx.x;
+    Rk45State* sb = st + b;
+    if (!rk45_live(*sb)) {
+        if (threadIdx.x == 0) sb->accepted_last = 0;
+        return;
+    }
+    const double s = reduce_parts(part + 2 * (size_t)b * chunks, chunks, 2, 0, red);
+    if (threadIdx.x != 0) return;
+    rk45_decide(sb, sqrt(s) / sqrt((double)m));
+    rk45ps_freeze(sb);
+}
+
+__global__ void __launch_bounds__(256) rk45ps_commit_kernel(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6,
+                                                            int m) {
+    const int b = blockIdx.y, base = b * m;
+    if (!st[b].accepted_last) return;
+    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+        const int i = base + jj;
+        *reinterpret_cast<double2*>(y + i) = *reinterpret_cast<const double2*>(y_new + i);
+        *reinterpret_cast<double2*>(y + i + 2) = *reinterpret_cast<const double2*>(y_new + i + 2);
+        *reinterpret_cast<float4*>(k0 + i) = *reinterpret_cast<const float4*>(k6 + i);
+    }
+}
+
+// one workgroup: how many samples still step, how many failed
+__global__ void __launch_bounds__(256) rk45ps_status_kernel(const Rk45State* st, int B, Rk45Status* out) {
+    __shared__ double red[256];
+    double live = 0.0, failed = 0.0;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        live += rk45_live(st[b]) ? 1.0 : 0.0;
+        failed += st[b].failed ? 1.0 : 0.0;
+    }
+    const double rl = block_sum(live, red);
+    __syncthreads();
+    const double rf = block_sum(failed, red);
+    if (threadIdx.x == 0) { out->unfinished = (int)rl; out->failed = (int)rf; }
+}
+
+#define RK45PS_LAUNCH(kern, grid, ...)                                                                       \
+    do {                                                                                                     \
+        if ((m & 3) || m < 4 || B < 1) return fail(FC_E_SHAPE, "rk45: per-sample element count must be a positive multiple of 4"); \
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, __VA_ARGS__);                                        \
+        FC_HIP(hipGetLastError());                                                                           \
+        return FC_OK;                                                                                        \
+    } while (0)
+#define PS_GRID dim3(rk45ps_chunks(m), B)
+
+int rk45ps_setup_launch(const float* x, double* y, float* xs, int B, int m, Rk45State* st, double t0, double t1, double rtol, double atol,
+                        int max_attempts, float t_scale, float* tvec, int cfg_on, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_setup_kernel, PS_GRID, x, y, xs, m, st, t0, t1, rtol, atol, max_attempts, t_scale, tvec, cfg_on);
+}
+int rk45ps_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
+                      hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_d01_kernel, PS_GRID, st, y, k0, v2, m, cfg_on, cfg, part);
+}
+int rk45ps_h0_launch(Rk45State* st, const double* part, int B, int m, float t_scale, float* tvec, int cfg_on, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_h0_kernel, dim3(B), st, part, rk45ps_chunks(m), m, t_scale, tvec, cfg_on);
+}
+int rk45ps_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int B, int m, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_y1_kernel, PS_GRID, st, y, k0, xs, m);
+}
+int rk45ps_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
+                     hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_d2_kernel, PS_GRID, st, y, k0, v2, m, cfg_on, cfg, part);
+}
+int rk45ps_h1_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_h1_kernel, dim3(B), st, part, rk45ps_chunks(m), m);
+}
+int rk45ps_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
+                        float* xs, float t_scale, float* tvec, hipStream_t s) {
+    switch (stage) {
+        case 1: RK45PS_LAUNCH(rk45ps_stage_kernel<1>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
+        case 2: RK45PS_LAUNCH(rk45ps_stage_kernel<2>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
+        case 3: RK45PS_LAUNCH(rk45ps_stage_kernel<3>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
+        case 4: RK45PS_LAUNCH(rk45ps_stage_kernel<4>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
+        case 5: RK45PS_LAUNCH(rk45ps_stage_kernel<5>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
+        default: return fail(FC_E_ARG, "rk45: stage must lie in [1, 5]");
+    }
+}
+int rk45ps_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
+                         float* xs, float t_scale, float* tvec, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_finish_kernel, PS_GRID, st, y, y_new, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
+}
+int rk45ps_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on,
+                        float cfg, double* part, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_error_kernel, PS_GRID, st, y, y_new, kk, v2, m, cfg_on, cfg, part);
+}
+int rk45ps_control_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_control_kernel, dim3(B), st, part, rk45ps_chunks(m), m);
+}
+int rk45ps_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int B, int m, hipStream_t s) {
+    RK45PS_LAUNCH(rk45ps_commit_kernel, PS_GRID, st, y, y_new, k0, k6, m);
+}
+int rk45ps_status_launch(const Rk45State* st, int B, Rk45Status* out, hipStream_t s) {
+    if (B < 1) return fail(FC_E_ARG, "rk45: batch must be positive");
+    hipLaunchKernelGGL(rk45ps_status_kernel, dim3(1), dim3(256), 0, s, st, B, out);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+#undef PS_GRID
+#undef RK45PS_LAUNCH
 
 }  // namespace fc

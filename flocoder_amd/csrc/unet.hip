@@ -363,6 +363,7 @@ static void free_plan(fc_unet* u) {
     for (void* p : u->int_allocs) dev_free(p);
     u->int_allocs.clear();
     u->rk_y = u->rk_ynew = u->rk_part = nullptr; u->rk_k = Rk45K{}; u->rk_st = nullptr;   // (were in int_allocs)
+    u->rkp_st = nullptr; u->rkp_part = nullptr; u->rkp_sum = nullptr;
     u->maxB = 0;
     // a rebuilt plan starts clean (callers of free_plan have synchronised the device)
     if (u->dev_err) (void)hipMemset(u->dev_err, 0, sizeof(int));
@@ -932,6 +933,7 @@ void fc_unet_destroy(fc_unet* u) {
     if (u->dev_err) (void)hipFree(u->dev_err);
     if (u->host_err) (void)hipHostFree(const_cast<int*>(u->host_err));
     if (u->rk_host) (void)hipHostFree(u->rk_host);
+    if (u->rkp_host) (void)hipHostFree(u->rkp_host);
     if (u->ev_rk) (void)hipEventDestroy(u->ev_rk);
     delete u;
 }
@@ -1406,6 +1408,144 @@ int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int B, int H, int W, double
     if (st.failed == 1) return fail(FC_E_STATE, "rk45: Required step size is less than spacing between numbers.");
     if (st.failed) return fail(FC_E_STATE, "rk45: no convergence after " + std::to_string(st.attempts) + " attempts (t = " +
                                                std::to_string(st.t) + ", h = " + std::to_string(st.h_abs) + ")");
+    return FC_OK;
+}
+
+// ---- per-sample adaptive RK45 -----------------------------------------------------------------------------------------------------
+static constexpr int kRk45PerSampleMethod = 3;     // graph-cache key of a per-sample attempt (beside kRk45Method)
+
+static int alloc_rk45_per_sample(fc_unet* u) {
+    const int m = u->cfg.channels * u->H * u->W;
+    auto get = [&](size_t bytes, void** out) -> int {
+        FC_TRY(dev_alloc(out, bytes, "integrator.rk45_per_sample"));
+        u->int_allocs.push_back(*out);
+        return FC_OK;
+    };
+    void* p = nullptr;
+    FC_TRY(get((size_t)u->maxB * sizeof(Rk45State), &p)); u->rkp_st = static_cast<Rk45State*>(p);
+    FC_TRY(get(2 * (size_t)u->maxB * rk45ps_chunks(m) * sizeof(double), &p)); u->rkp_part = static_cast<double*>(p);
+    FC_TRY(get(sizeof(Rk45Status), &p)); u->rkp_sum = static_cast<Rk45Status*>(p);
+    return FC_OK;
+}
+
+// one attempt of every sample that still steps: five stages, y_new and f(t + h, y_new), the error norms, the controllers, the commit,
+// the status summary
+static int enqueue_rk45ps_attempt(fc_unet* u, int B, bool cfg_on, float cfg, float t_scale, bool has_ids, int mask_mode, hipStream_t s) {
+    const int rows = cfg_on ? 2 * B : B, m = u->cfg.channels * u->H * u->W, cf = cfg_on ? 1 : 0;
+    FwdCtx c;   // no conditioning table: each forward takes its per-row time from u->tvec
+    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
+    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
+    c.out = u->v2; c.B = rows;
+    for (int st = 1; st <= 5; ++st) {
+        FC_TRY(rk45ps_stage_launch(u->rkp_st, st, u->rk_y, u->rk_k, u->v2, B, m, cf, cfg, u->xs, t_scale, u->tvec, s));
+        FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
+    }
+    FC_TRY(rk45ps_finish_launch(u->rkp_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, B, m, cf, cfg, u->xs, t_scale, u->tvec, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
+    FC_TRY(rk45ps_error_launch(u->rkp_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, B, m, cf, cfg, u->rkp_part, s));
+    FC_TRY(rk45ps_control_launch(u->rkp_st, u->rkp_part, B, m, s));
+    FC_TRY(rk45ps_commit_launch(u->rkp_st, u->rk_y, u->rk_ynew, u->rk_k.k[0], u->rk_k.k[6], B, m, s));
+    return rk45ps_status_launch(u->rkp_st, B, u->rkp_sum, s);
+}
+
+int fc_unet_integrate_rk45_per_sample(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
+                                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
+                                      int* counters, void* stream) {
+    if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, "fc_unet_integrate_rk45_per_sample: bad argument");
+    if (!(atol >= 0)) return fail(FC_E_ARG, "fc_unet_integrate_rk45_per_sample: `atol` must be positive.");      // validate_tol
+    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, "fc_unet_integrate_rk45_per_sample: t0 and t1 must be finite");
+    const double eps100 = 100 * 2.220446049250313e-16;
+    if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
+    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
+    const bool cfg_on = has_ids && cfg_strength != 0.0f;
+    const int rows = cfg_on ? 2 * B : B;
+    FC_TRY(check_ready(u, rows, H, W));
+    FC_TRY(check_poison(u));
+    for (int b = 0; b < B; ++b) { counters[3 * b] = 1; counters[3 * b + 1] = counters[3 * b + 2] = 0; }
+    if (t0 == t1) return FC_OK;                  // scipy: one evaluation, no step, y0 returned
+    u->arena_touched(0);
+    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
+    const int m = u->cfg.channels * H * W, n = B * m;
+    const size_t nbytes = (size_t)n * sizeof(float);
+    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
+    FC_HIP(hipSetDevice(u->device));
+    if (!u->rk_st) FC_TRY(alloc_rk45(u));
+    if (!u->rkp_st) FC_TRY(alloc_rk45_per_sample(u));
+    if (!u->rkp_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); u->rkp_host = static_cast<Rk45Status*>(hp); }
+    if (!u->ev_rk) FC_HIP(hipEventCreateWithFlags(&u->ev_rk, hipEventDisableTiming));
+
+    FC_HIP(hipEventRecord(u->ev_in, caller));
+    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
+    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
+    FC_TRY(meet_enter(u, s));
+
+    // f(t0, y0) and select_initial_step of every sample (two forwards, no graph)
+    FwdCtx c;
+    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
+    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
+    c.out = u->v2; c.B = rows;
+    const int cf = cfg_on ? 1 : 0;
+    FC_TRY(rk45ps_setup_launch(x_dev, u->rk_y, u->xs, B, m, u->rkp_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, u->tvec, cf, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
+    FC_TRY(rk45ps_d01_launch(u->rkp_st, u->rk_y, u->rk_k.k[0], u->v2, B, m, cf, cfg_strength, u->rkp_part, s));
+    FC_TRY(rk45ps_h0_launch(u->rkp_st, u->rkp_part, B, m, t_scale, u->tvec, cf, s));
+    FC_TRY(rk45ps_y1_launch(u->rkp_st, u->rk_y, u->rk_k.k[0], u->xs, B, m, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
+    FC_TRY(rk45ps_d2_launch(u->rkp_st, u->rk_y, u->rk_k.k[0], u->v2, B, m, cf, cfg_strength, u->rkp_part, s));
+    FC_TRY(rk45ps_h1_launch(u->rkp_st, u->rkp_part, B, m, s));
+    FC_TRY(rk45ps_status_launch(u->rkp_st, B, u->rkp_sum, s));
+    FC_HIP(hipMemcpyAsync(u->rkp_host, u->rkp_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
+    // the host wait fc_unet_integrate_rk45 makes before its first replay, for the same reason (AMD_DIRECT_DISPATCH=0)
+    FC_HIP(hipStreamSynchronize(s));
+
+    static const bool no_graph = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
+    const auto key = std::make_tuple(kRk45PerSampleMethod, B, (int)cfg_on, mask_mode, fbits(cfg_strength), 0u, fbits(t_scale), (int)has_ids);
+    int r = FC_OK;
+    while (r == FC_OK && u->rkp_host->unfinished > 0) {
+        if (no_graph) {
+            r = enqueue_rk45ps_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
+            if (r != FC_OK) break;
+        } else {
+            auto it = u->graphs.find(key);
+            if (it == u->graphs.end()) {    // one attempt = one graph: 6 plan runs and 10 small launches, a single chain (no parallel branches)
+                hipGraph_t graph = nullptr;
+                FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+                r = enqueue_rk45ps_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
+                const hipError_t e = hipStreamEndCapture(s, &graph);
+                if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
+                if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+                hipGraphExec_t exec = nullptr;
+                FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+                FC_HIP(hipGraphDestroy(graph));
+                it = u->graphs.emplace(key, exec).first;
+            }
+            FC_HIP(hipGraphLaunch(it->second, s));
+        }
+        // the 16-byte summary behind every attempt: one small host wait per six forwards
+        FC_HIP(hipMemcpyAsync(u->rkp_host, u->rkp_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
+        FC_HIP(hipEventRecord(u->ev_rk, s));
+        FC_HIP(hipEventSynchronize(u->ev_rk));
+    }
+    if (r != FC_OK) return r;
+    std::vector<Rk45State> st(B);      // the per-sample records, once at the end
+    FC_HIP(hipMemcpyAsync(st.data(), u->rkp_st, (size_t)B * sizeof(Rk45State), hipMemcpyDeviceToHost, s));
+    FC_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) { counters[3 * b] = st[b].nfev; counters[3 * b + 1] = st[b].accepted; counters[3 * b + 2] = st[b].rejected; }
+    const bool failed = u->rkp_host->failed > 0;
+    if (!failed) FC_TRY(rk45_out_launch(u->rk_y, x_dev, n, s));
+    FC_TRY(meet_leave(u, s));
+    FC_HIP(hipEventRecord(u->ev_out, s));
+    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
+    if (failed) {
+        std::string msg = "rk45 per sample: " + std::to_string(u->rkp_host->failed) + " of " + std::to_string(B) + " samples failed;";
+        for (int b = 0; b < B; ++b) {
+            if (st[b].failed == 1) msg += " sample " + std::to_string(b) + ": Required step size is less than spacing between numbers.";
+            else if (st[b].failed) msg += " sample " + std::to_string(b) + ": no convergence after " + std::to_string(st[b].attempts) +
+                                          " attempts (t = " + std::to_string(st[b].t) + ", h = " + std::to_string(st[b].h_abs) + ").";
+        }
+        return fail(FC_E_STATE, msg);
+    }
     return FC_OK;
 }
 

@@ -39,6 +39,12 @@ struct fc_unet : fc::ParamStore {
     fc::Rk45State* rk_st = nullptr;
     fc::Rk45State* rk_host = nullptr;
     hipEvent_t ev_rk = nullptr;
+    // per-sample RK45 (fc_unet_integrate_rk45_per_sample) shares rk_y / rk_ynew / rk_k and adds one controller per reserved row, its
+    // partial sums and the status summary (in int_allocs, allocated by its first call); the pinned summary lives as long as the handle
+    fc::Rk45State* rkp_st = nullptr;
+    double* rkp_part = nullptr;
+    fc::Rk45Status* rkp_sum = nullptr;
+    fc::Rk45Status* rkp_host = nullptr;
 
     // Fused Block tails whose workgroups wait for each other (conv_dev.h) need the device to themselves.  `shared` = the caller said the
     // device is shared with other streams / processes (fc_unet_set_shared): plans are then built without such launches.  A wait that

@@ -143,7 +143,7 @@ def _validate_tol(rtol, atol):
 
 
 @torch.no_grad()
-def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rtol=1e-5, atol=1e-5, cfg_strength=0.0):
+def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rtol=1e-5, atol=1e-5, cfg_strength=0.0, per_sample=False):
     """Legacy adaptive sampler, train_sd_flowers.py:78-107: ``scipy.integrate.solve_ivp(method="RK45")`` over ``(eps, 1)`` on
     ``model(float32(x), float32(t) * 999, cond)``; returns ``(latents, nfe)`` with nfe = scipy's ``solution.nfev``.  ``cond`` is a class-id
     tensor as upstream or a cond dict; ``source`` replaces the randn start; ``cfg_strength`` is an extension (0 keeps upstream behaviour;
@@ -151,7 +151,12 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
     upstream, so a sample's trajectory depends on the rest of its batch.  A ``flocoder_amd.Unet`` runs the whole solve in the library
     (Unet.integrate_rk45: stages, error norm and step controller on the device); any other model takes the legacy host path through
     numpy.  Where scipy would return ``success=False`` (step size below the spacing of t) this raises RuntimeError -- the legacy code
-    silently used the last state."""
+    silently used the last state.
+
+    ``per_sample=True`` is an extension: every sample is its own solve_ivp problem over its C*H*W unknowns (own initial step, error
+    norm, step size, counters), so a sample's result depends only on its own source, class id and mask, not on how samples are
+    grouped into batches.  nfe is then the largest per-sample nfev: the number of batch forwards the device path makes.  A failing
+    sample raises RuntimeError naming it."""
     rtol, atol = _validate_tol(rtol, atol)
     p0 = next(model.parameters())
     device = p0.device if device is None else torch.device(device)
@@ -162,8 +167,11 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
         cls = cond.get('class_cond') if cond else None
         mask, ones = _mask_flags(cond)
         nfev, _, _ = model.integrate_rk45(x, eps, 1.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
-                                          mask_is_ones=ones)
-        return x, nfev
+                                          mask_is_ones=ones, per_sample=per_sample)
+        return x, (int(nfev.max()) if per_sample else nfev)
+
+    if per_sample:
+        return _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength)
 
     import numpy as np
     from scipy import integrate
@@ -181,22 +189,51 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
     return torch.tensor(solution.y[:, -1]).reshape(shape).type(torch.float32).to(device), solution.nfev
 
 
+def _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength):
+    """rk45_sampler(per_sample=True) for models that are not a flocoder_amd.Unet: one legacy solve_ivp per sample, the model called on
+    that sample alone (its class id and mask row)."""
+    import numpy as np
+    from scipy import integrate
+    out, nfevs, failed = x.clone(), [], []
+    for b in range(x.shape[0]):
+        shape = (1,) + tuple(x.shape[1:])
+        cond_b = {k: (v[b:b + 1] if torch.is_tensor(v) else v) for k, v in cond.items()} if cond else cond
+        t_vec_template = torch.zeros(1, device=x.device)
+
+        def ode_func(t, y):
+            xt = torch.from_numpy(np.asarray(y).reshape(shape)).to(x.device).type(torch.float32)
+            drift = v_func_cfg(model, cond_b, cfg_strength, t_vec_template, xt, t)
+            return drift.detach().cpu().numpy().reshape((-1,))
+
+        solution = integrate.solve_ivp(ode_func, (eps, 1), x[b].detach().cpu().numpy().reshape((-1,)), rtol=rtol, atol=atol, method="RK45")
+        if not solution.success:
+            failed.append(f"sample {b}: {solution.message}")
+            continue
+        out[b] = torch.tensor(solution.y[:, -1]).reshape(shape[1:]).type(torch.float32).to(x.device)
+        nfevs.append(int(solution.nfev))
+    if failed:
+        raise RuntimeError(f"rk45_sampler: {len(failed)} of {x.shape[0]} samples failed; " + " ".join(failed))
+    return out, max(nfevs)
+
+
 @torch.no_grad()
-def generate_latents_rk45(model, shape, device=None, cond=None, cfg_strength=3.0, source=None, rtol=1e-5, atol=1e-5):
+def generate_latents_rk45(model, shape, device=None, cond=None, cfg_strength=3.0, source=None, rtol=1e-5, atol=1e-5, per_sample=False):
     """The function sampling.py:142-143 dispatches to (undefined upstream): the legacy RK45 sampler over (1e-3, 1), no time warp, with
-    classifier-free guidance as generate_latents_rk4 applies it.  Returns (latents, nfe)."""
-    return rk45_sampler(model, shape, device=device, cond=cond, source=source, eps=1e-3, rtol=rtol, atol=atol, cfg_strength=cfg_strength)
+    classifier-free guidance as generate_latents_rk4 applies it.  ``per_sample=True`` solves every sample on its own (rk45_sampler).
+    Returns (latents, nfe)."""
+    return rk45_sampler(model, shape, device=device, cond=cond, source=source, eps=1e-3, rtol=rtol, atol=atol, cfg_strength=cfg_strength,
+                        per_sample=per_sample)
 
 
 @torch.no_grad()
 def generate_latents(model, shape, method='rk4', n_steps=50, cond=None, cfg_strength=3.0, device=None, source=None,
                      init_latents=None, init_strength=0.0, debug=False):
     """sampling.py:128-146.  'rk45' selects generate_latents_rk45 (undefined upstream; built here from the legacy RK45
-    sampler); 'euler' selects the legacy sampler."""
-    if method == "rk45":
+    sampler); 'rk45_per_sample' selects it with one solve per sample (an extension); 'euler' selects the legacy sampler."""
+    if method in ("rk45", "rk45_per_sample"):
         if init_latents is not None:
-            raise ValueError("init_latents is not defined for method='rk45' (upstream has no such integration)")
-        return generate_latents_rk45(model, shape, device, cond, cfg_strength, source=source)
+            raise ValueError(f"init_latents is not defined for method={method!r} (upstream has no such integration)")
+        return generate_latents_rk45(model, shape, device, cond, cfg_strength, source=source, per_sample=method == "rk45_per_sample")
     if method == "euler":
         # (the legacy sampler has no guidance upstream: generate_latents keeps that; sample_many forwards its cfg_strength itself)
         return euler_sampler(model, shape, n_steps, device=device, cond=cond, source=source)
@@ -276,6 +313,9 @@ def sample_many(model, shape, batches, method="euler", n_steps=64, cfg_strength=
     of ~4500 dependent launches with the chip mostly waiting on launch-to-launch latency, and a second chain fills those gaps: measured
     955-975 samples/s against 782-789 for one batch of 64 at a time (tools/inflight_sweep.py, under AMD_DIRECT_DISPATCH=0 --
     ``flocoder_amd.apply_runtime_defaults("sampling")``).  The replicas run the plan without cross-workgroup waits (``set_shared_device``).
+    ``method="rk45_per_sample"`` solves every sample on its own, so its results equal the one-at-a-time calls however the samples are
+    grouped; but each such call waits on the host behind every attempt until its solve ends, so batches in flight do not overlap and
+    ``in_flight`` buys no throughput there.  (The batch-coupled "rk45" couples the samples of a batch and is not meant for this mode.)
     Returns the list of latents in the order of ``batches``."""
     if not isinstance(model, Unet):
         raise TypeError("sample_many drives flocoder_amd.Unet replicas")

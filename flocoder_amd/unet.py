@@ -443,12 +443,17 @@ class Unet(nn.Module):
 
     def integrate_rk45(self, x: torch.Tensor, t0: float, t1: float, *, rtol: float, atol: float, t_scale: float = 999.0,
                        class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,
-                       mask_is_ones: bool = False, check: bool = True) -> Tuple[int, int, int]:
+                       mask_is_ones: bool = False, check: bool = True, per_sample: bool = False):
         """Integrate ``x`` in place from ``t0`` to ``t1`` with scipy's adaptive RK45 (``fc_unet_integrate_rk45``: solve_ivp semantics,
         one step size and one error norm for the whole batch, so a sample's trajectory depends on the rest of its batch as upstream).
         Synchronous: the host waits for a small status record behind every attempt of six evaluations.  Returns ``(nfev, accepted,
         rejected)``; ``nfev`` is scipy's ``solution.nfev`` (a CFG pair counts once).  Raises RuntimeError when the step size falls below
-        the spacing of t (scipy's ``success=False``) and ValueError for ``atol < 0``."""
+        the spacing of t (scipy's ``success=False``) and ValueError for ``atol < 0``.
+
+        ``per_sample=True`` (``fc_unet_integrate_rk45_per_sample``) solves every sample as its own solve_ivp problem (own initial step,
+        error norm, step size and counters), so a sample's result depends only on its own source, class id and mask.  It then returns
+        ``(nfev, accepted, rejected)`` as int64 CPU tensors of shape [B]; the call makes ``nfev.max()`` batch forwards.  A failing
+        sample raises RuntimeError naming it, and ``x`` is left untouched."""
         if not x.is_cuda:
             raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
         if atol < 0:
@@ -478,12 +483,15 @@ class Unet(nn.Module):
         rows = bsz * (2 if (class_ids is not None and cfg_strength) else 1)
         hnd = self._native(dev)
         B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
-        counters = (C.c_int * 3)()
-        B.check(B.lib().fc_unet_integrate_rk45(hnd, B.ptr(x), bsz, h, w, float(t0), float(t1), float(rtol), float(atol), float(t_scale),
-                                               B.ptr(class_ids), float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), counters,
-                                               B.current_stream(dev)))
+        fn = B.lib().fc_unet_integrate_rk45_per_sample if per_sample else B.lib().fc_unet_integrate_rk45
+        counters = (C.c_int * (3 * bsz if per_sample else 3))()
+        B.check(fn(hnd, B.ptr(x), bsz, h, w, float(t0), float(t1), float(rtol), float(atol), float(t_scale), B.ptr(class_ids),
+                   float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), counters, B.current_stream(dev)))
         if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
             B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
+        if per_sample:
+            c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
+            return c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone()
         return int(counters[0]), int(counters[1]), int(counters[2])
 
     def profile_ops(self, batch: int, repeats: int = 20):

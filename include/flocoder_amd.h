@@ -122,6 +122,23 @@ int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int batch, int height, int 
                            float t_scale, const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev, int mask_is_ones,
                            int* counters, void* stream);
 
+/* Adaptive RK45 with one solve per sample: every sample b is its OWN scipy.integrate.solve_ivp(f_b, (t0, t1), y0_b, method="RK45",
+ * rtol, atol) problem over its C*H*W unknowns, f_b = the U-Net forward on that sample alone (its class id, its mask row, CFG as
+ * fc_unet_integrate_rk45).  Each sample has its own select_initial_step, RMS error norm, step size, accept / reject decisions and
+ * counters, so its result depends only on its own source, class id and mask -- not on the batch size or on its batchmates -- and a
+ * batch may be split across calls or ranks.  The arithmetic is fc_unet_integrate_rk45's (fp64 state, stage sums and norms, fp32
+ * forwards); the norms' partial sums are partitioned by C*H*W alone and reduced in a fixed order.  A sample that has finished stays
+ * in the batch with h = 0 (its rows are still evaluated; its state and counters are frozen), so the call makes max_b nfev_b batch
+ * forwards.  counters[3 * batch] (host) = { nfev, accepted, rejected } per sample.  atol < 0 -> FC_E_ARG; rtol below 100 eps is
+ * raised to 100 eps; t0 == t1 -> nfev 1 each, x_dev untouched.  If any sample fails (step below the spacing of its t, or the attempt
+ * cap) -> FC_E_STATE with the failing sample indices and reasons in fc_last_error(), x_dev untouched.  One attempt (6 forwards + 10
+ * small launches) is a captured hipGraph per (B, cfg, mask, class ids) variant; the host reads a 16-byte summary (samples still
+ * stepping, samples failed) behind each replay, so the call is SYNCHRONOUS like its sibling.  Its extra state is allocated by the
+ * first call, sized by the reserved batch. */
+int fc_unet_integrate_rk45_per_sample(fc_unet* u, float* x_dev, int batch, int height, int width, double t0, double t1, double rtol,
+                                      double atol, float t_scale, const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev,
+                                      int mask_is_ones, int* counters /* host, [3*batch] */, void* stream);
+
 /* Kept for compatibility: the reserved batch always runs as ONE chain of rows on one stream, so this returns 1 and sets
  * *rows_per_chain to the reserved batch (0 before fc_unet_reserve). */
 int fc_unet_chains(const fc_unet* u, int* rows_per_chain);
