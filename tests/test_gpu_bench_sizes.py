@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from conftest import ROOT, load_golden, rel_l2
+from unet_taps import worst_sample
 from oracle import flow_oracle as fo
 from oracle import sdvae_oracle as vo
 from oracle.synth import synth_input, synth_state_dict
@@ -111,6 +112,8 @@ def test_c_default_plan_forward_at_bench_batch(unet32):
     ref = fo.unet_forward(sd, x[:8], t[:8], {"class_cond": ids[:8]})
     e = rel_l2(v[:8].cpu(), ref)
     assert e < 2e-5, f"B=64 default plan, rows 0-7: {e:.3e}"
+    e = worst_sample(v[:8], ref)
+    assert e < 2e-5, f"B=64 default plan, rows 0-7: worst sample {e:.3e}"
     plan_fwd = [r["kernel"] for r in model.profile_ops(B, repeats=1)]
     # ... and the sampler bench.py times replays exactly this plan
     S.euler_sampler(model, (B, 4, 32, 32), 2, cond=ids.to(DEV), source=x.to(DEV))

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import ROOT, load_golden, rel_l2
+from unet_taps import worst_sample
 from oracle import flow_oracle as fo
 from oracle.synth import synth_input, synth_state_dict
 
@@ -91,6 +92,8 @@ def test_forward_batch_sizes_and_determinism():
         assert torch.equal(a, b)
         err = rel_l2(a.cpu(), ref)
         assert err < FWD_TOL, f"B={B}: {err:.3e}\n" + first_bad_tap(model, sd, x, t, {"class_cond": cls}, B)
+        err = worst_sample(a, ref)                        # per sample: a batch-tail error is not diluted by the batch
+        assert err < FWD_TOL, f"B={B}: worst sample {err:.3e}\n" + first_bad_tap(model, sd, x, t, {"class_cond": cls}, B)
 
 
 @pytest.mark.parametrize("dim,H,W,B", [(32, 64, 64, 2), (16, 64, 64, 1), (32, 8, 8, 3), (32, 32, 16, 2), (64, 16, 16, 2)])
@@ -127,19 +130,24 @@ def test_rk4_and_euler_trajectories_match_reference_goldens():
         lat, nfe = S.generate_latents_rk4(model, (2, 4, 16, 16), n_steps=5, cond={"class_cond": cls}, cfg_strength=float(cfg), source=src.clone())
         assert nfe == 20
         assert rel_l2(lat.cpu(), g[f"rk4_n5_cfg{cfg}"]) < TRAJ_TOL, cfg
+        assert worst_sample(lat, g[f"rk4_n5_cfg{cfg}"]) < TRAJ_TOL, cfg
     lat, _ = S.generate_latents_rk4(model, (2, 4, 16, 16), n_steps=4, cond={}, cfg_strength=3.0, source=src.clone())
     assert rel_l2(lat.cpu(), g["rk4_n4_nocond"]) < TRAJ_TOL
+    assert worst_sample(lat, g["rk4_n4_nocond"]) < TRAJ_TOL
     init = synth_input("g5.init", (2, 4, 16, 16), 5).to(DEV)
     lat, nfe = S.generate_latents_rk4(model, (2, 4, 16, 16), n_steps=8, cond={"class_cond": cls}, cfg_strength=3.0, source=src.clone(),
                                       init_latents=init, init_strength=0.5)
     assert nfe == 16 and rel_l2(lat.cpu(), g["rk4_n8_init05"]) < TRAJ_TOL
+    assert worst_sample(lat, g["rk4_n8_init05"]) < TRAJ_TOL
     for n in (4, 16):
         lat, nfe = S.euler_sampler(model, (2, 4, 16, 16), n, cond=cls, source=src)
         assert nfe == n and rel_l2(lat.cpu(), g[f"euler_n{n}"]) < TRAJ_TOL, n
+        assert worst_sample(lat, g[f"euler_n{n}"]) < TRAJ_TOL, n
     # generate_latents dispatch + graph replay of a cached variant gives the same bits
     a, _ = S.generate_latents(model, (2, 4, 16, 16), "rk4", 5, {"class_cond": cls}, 3.0, source=src.clone())
     b, _ = S.generate_latents(model, (2, 4, 16, 16), "rk4", 5, {"class_cond": cls}, 3.0, source=src.clone())
     assert torch.equal(a, b) and rel_l2(a.cpu(), g["rk4_n5_cfg3"]) < TRAJ_TOL
+    assert worst_sample(a, g["rk4_n5_cfg3"]) < TRAJ_TOL
 
 
 def test_euler64_flowers_shape_vs_oracle():
@@ -155,12 +163,15 @@ def test_euler64_flowers_shape_vs_oracle():
     assert nfe == 64
     err = rel_l2(lat.cpu(), ref)
     assert err < TRAJ_TOL, f"{err:.3e}"
+    err = worst_sample(lat, ref)
+    assert err < TRAJ_TOL, f"worst sample {err:.3e}"
     # linearity-free sanity property at a size the oracle would not finish quickly: batch independence
     big = synth_input("e64.big", (32, 4, 32, 32), 1).to(DEV)
     big[:B] = src.to(DEV)
     ids = torch.cat([cls, torch.arange(29) % 102]).to(DEV)
     lat2, _ = S.euler_sampler(model, (32, 4, 32, 32), 64, cond=ids, source=big)
     assert rel_l2(lat2[:B].cpu(), lat.cpu()) < 1e-5      # a sample's trajectory does not depend on its batch mates
+    assert worst_sample(lat2[:B], lat) < 1e-5
 
 
 def test_mask_cond_sampling_vs_oracle():
@@ -206,6 +217,7 @@ def _fused_tail_body(Unet):
     assert any("+fin" in r["kernel"] for r in m.profile_ops(64, repeats=1))          # the fused path is the one that ran
     ref = fo.unet_forward(sd, x[:8], t[:8], {"class_cond": ids[:8]})
     assert rel_l2(v[:8].cpu(), ref) < FWD_TOL
+    assert worst_sample(v[:8], ref) < FWD_TOL
     assert m.fused_tail_errors() == 0
 
 
@@ -340,6 +352,7 @@ def test_one_workgroup_per_sample_kernel_is_the_default_where_it_fits_and_both_p
         n_big = model.launches_per_forward
     assert n_small <= 4 < n_big, (n_small, n_big)                             # conditioning + ONE U-Net launch, against the ~115 of the ordinary plan
     assert rel_l2(big[:2].cpu(), small.cpu()) < 2e-6                          # the two plans agree (summation order apart)
+    assert worst_sample(big, small.repeat(reps, 1, 1, 1)) < 2e-6              # every row of the ordinary plan's batch, tail included
     env = dict(os.environ, FLOCODER_AMD_SAMPLE_KERNEL="0")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider",
                         "-k", "d8mask or mask_cond_sampling"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
