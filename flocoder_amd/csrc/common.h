@@ -284,51 +284,36 @@ struct Rk45State {
     int nfev, accepted, rejected, attempts, done, failed, step_rejected, accepted_last, max_attempts, pad;
 };
 struct Rk45K { float* k[7]; };             // stage derivatives K0..K6 (fp32, CFG-blended)
-int rk45_parts(int n);                     // partial sums the reduction kernels write (pairs of doubles)
-// y = double(x), xs = x, state for (t0 -> t1), time row of f(t0)
-int rk45_setup_launch(const float* x, double* y, float* xs, int n, Rk45State* st, double t0, double t1, double rtol, double atol,
-                      int max_attempts, float t_scale, float* tvec, int rows, hipStream_t s);
-// select_initial_step: K0 = f0 and d0/d1 partials | h0 and the time row of f1 | xs = y0 + h0 f0 | d2 partials | h1, first attempt
-int rk45_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int n, int cfg_on, float cfg, double* part, hipStream_t s);
-int rk45_h0_launch(Rk45State* st, const double* part, int n, float t_scale, float* tvec, int rows, hipStream_t s);
-int rk45_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int n, hipStream_t s);
-int rk45_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int n, int cfg_on, float cfg, double* part,
-                   hipStream_t s);
-int rk45_h1_launch(Rk45State* st, const double* part, int n, hipStream_t s);
-// one attempt: stages 1..5 (K[s-1] = blend(v2), xs = y + h sum A K), finish (K5, y_new), error partials (K6), controller, commit
-int rk45_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
-                      float* xs, float t_scale, float* tvec, int rows, hipStream_t s);
-int rk45_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
-                       float* xs, float t_scale, float* tvec, int rows, hipStream_t s);
-int rk45_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int n, int cfg_on,
-                      float cfg, double* part, hipStream_t s);
-int rk45_control_launch(Rk45State* st, const double* part, int n, hipStream_t s);
-int rk45_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int n, hipStream_t s);
+struct Rk45Status { int unfinished, failed, pad0, pad1; };   // groups still stepping / failed: what the host reads behind an attempt
+// Controller groups of one solve: st[G] holds one controller per group, group g owns the m unknowns of rows g*spg .. g*spg + spg - 1
+// (with CFG also their unguided twins G*spg + row).  Batch-coupled: G = 1, spg = B; per sample: G = B, spg = 1.  The elementwise and
+// partial-sum kernels run on a (chunks, G) grid; partial sums are [G][chunks][2] and `chunks` fixes their summation order.
+struct Rk45Groups { int G, spg, m, chunks; };
+int rk45_chunks(int m, int cap);           // workgroups per group over m unknowns: one per 1024, at most `cap`
+// y = double(x), xs = x, states for (t0 -> t1), time rows of f(t0)
+int rk45_setup_launch(const Rk45Groups& g, const float* x, double* y, float* xs, Rk45State* st, double t0, double t1, double rtol,
+                      double atol, int max_attempts, float t_scale, float* tvec, int cfg_on, hipStream_t s);
+// select_initial_step: K0 = f0 and d0/d1 partials | h0 and the time rows of f1 | xs = y0 + h0 f0 | d2 partials | h1, first attempt
+int rk45_d01_launch(const Rk45Groups& g, const Rk45State* st, const double* y, float* k0, const float* v2, int cfg_on, float cfg,
+                    double* part, hipStream_t s);
+int rk45_h0_launch(const Rk45Groups& g, Rk45State* st, const double* part, float t_scale, float* tvec, int cfg_on, hipStream_t s);
+int rk45_y1_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, float* xs, hipStream_t s);
+int rk45_d2_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, const float* v2, int cfg_on, float cfg,
+                   double* part, hipStream_t s);
+int rk45_h1_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s);
+// one attempt: stages 1..5 (K[s-1] = blend(v2), xs = y + h sum A K), finish (K5, y_new), error partials (K6), controllers, commit,
+// status summary
+int rk45_stage_launch(const Rk45Groups& g, const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int cfg_on,
+                      float cfg, float* xs, float t_scale, float* tvec, hipStream_t s);
+int rk45_finish_launch(const Rk45Groups& g, const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int cfg_on,
+                       float cfg, float* xs, float t_scale, float* tvec, hipStream_t s);
+int rk45_error_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2,
+                      int cfg_on, float cfg, double* part, hipStream_t s);
+int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s);
+int rk45_commit_launch(const Rk45Groups& g, const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6,
+                       hipStream_t s);
+int rk45_status_launch(const Rk45Groups& g, const Rk45State* st, Rk45Status* out, hipStream_t s);
 int rk45_out_launch(const double* y, float* x, int n, hipStream_t s);
-
-// ---- per-sample adaptive RK45 (ode.hip): every sample of B its own solve_ivp problem over its m = C*H*W unknowns --------------
-// st[B] holds one controller per sample; partial sums are [B][rk45ps_chunks(m)][2] (the partition depends on m only); the rows of
-// sample b are b and, with CFG, B + b.  The launches mirror the batch-coupled ones above.
-struct Rk45Status { int unfinished, failed, pad0, pad1; };   // samples still stepping / failed: what the host reads behind an attempt
-int rk45ps_chunks(int m);                  // workgroups per sample of the elementwise and partial-sum kernels
-int rk45ps_setup_launch(const float* x, double* y, float* xs, int B, int m, Rk45State* st, double t0, double t1, double rtol, double atol,
-                        int max_attempts, float t_scale, float* tvec, int cfg_on, hipStream_t s);
-int rk45ps_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
-                      hipStream_t s);
-int rk45ps_h0_launch(Rk45State* st, const double* part, int B, int m, float t_scale, float* tvec, int cfg_on, hipStream_t s);
-int rk45ps_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int B, int m, hipStream_t s);
-int rk45ps_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
-                     hipStream_t s);
-int rk45ps_h1_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s);
-int rk45ps_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
-                        float* xs, float t_scale, float* tvec, hipStream_t s);
-int rk45ps_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
-                         float* xs, float t_scale, float* tvec, hipStream_t s);
-int rk45ps_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on,
-                        float cfg, double* part, hipStream_t s);
-int rk45ps_control_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s);
-int rk45ps_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int B, int m, hipStream_t s);
-int rk45ps_status_launch(const Rk45State* st, int B, Rk45Status* out, hipStream_t s);
 
 // ---- weight packing (pack.hip) ----------------------------------------------------------------
 struct PackJob { const float* src; float* dst; int kind, a, b, c, d, e; size_t total; };

@@ -146,10 +146,19 @@ int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float
 
 // ================================================================================================ adaptive RK45
 // scipy.integrate.solve_ivp(method="RK45") as the legacy sampler calls it (legacy/train_sd_flowers.py:78-107): scipy 1.15's
-// _ivp/rk.py (rk_step, RungeKutta._step_impl, RK45 tableau) and _ivp/common.py (select_initial_step, norm).  One step size and one error
-// norm for the whole batch, as there.  y, y_new, the stage sums, the scale and the error are fp64; every forward gets float32(y_stage) and
-// time float32(t + c h) * t_scale (fp32); the stage derivatives K_i are the fp32 forwards (scipy's fp64 copies of them are exact).
-// Controller decisions happen on the device (Rk45State); the host only reads the status record behind each attempt.
+// _ivp/rk.py (rk_step, RungeKutta._step_impl, RK45 tableau) and _ivp/common.py (select_initial_step, norm).  y, y_new, the stage sums,
+// the scale and the error are fp64; every forward gets float32(y_stage) and time float32(t + c h) * t_scale (fp32); the stage
+// derivatives K_i are the fp32 forwards (scipy's fp64 copies of them are exact).  Controller decisions happen on the device
+// (Rk45State); the host only reads the status summary behind each attempt.
+//
+// Controller groups (Rk45Groups): st[g] is one solve_ivp problem over the m unknowns of rows g*spg .. g*spg + spg - 1 (with CFG also
+// their unguided twins B + row, B = G*spg), with its own select_initial_step, error norm, step size, accept / reject decisions and
+// counters.  The batch-coupled sampler is ONE group of all B rows, as the legacy sampler (one step size and one error norm for the
+// whole batch); the per-sample sampler is one group per sample.  The elementwise and partial-sum kernels run on a (chunks, G) grid:
+// blockIdx.y is the group, and its `chunks` workgroups stride over its m unknowns; one workgroup per group reduces the fp64 partial
+// sums ([G][chunks][2]) in a fixed order.  `chunks` fixes the summation order and with it the bits of the norms (the host picks it).
+// A group that has finished or failed keeps h = 0: its rows are still evaluated (at float32(y), t), its state, counters and K stay
+// as they are.
 
 __constant__ double c_rk45_C[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
 __constant__ double c_rk45_A[6][5] = {
@@ -190,9 +199,23 @@ __device__ __forceinline__ double reduce_parts(const double* part, int nblk, int
 
 __device__ __forceinline__ float stage_time(double t, float t_scale) { return mul_((float)t, t_scale); }   // ones(B) * t * 999
 
-__device__ __forceinline__ void write_tvec(float* tvec, int rows, float tv) {
-    for (int r = threadIdx.x; r < rows; r += 256) tvec[r] = tv;
+// the time rows of group g (every thread of one workgroup): its spg rows and, with CFG, their unguided twins G*spg + row
+__device__ __forceinline__ void write_trows(float* tvec, int g, int G, int spg, int cfg_on, float tv) {
+    for (int r = g * spg + threadIdx.x; r < (g + 1) * spg; r += 256) {
+        tvec[r] = tv;
+        if (cfg_on) tvec[G * spg + r] = tv;
+    }
 }
+
+__device__ __forceinline__ bool rk45_live(const Rk45State& s) { return !s.done && !s.failed; }
+
+// after a decision: a finished or failed group keeps h = 0
+__device__ __forceinline__ void rk45_freeze(Rk45State* st) {
+    if (!rk45_live(*st)) { st->h = 0.0; st->t_new = st->t; }
+}
+
+// this workgroup's pair of partial sums in the [G][chunks][2] buffer
+__device__ __forceinline__ double* group_part(double* part, int g) { return part + 2 * ((size_t)g * gridDim.x + blockIdx.x); }
 
 // RungeKutta._step_impl up to rk_step: the h and t_new of the next attempt.  `start`: a new step (after select_initial_step or an
 // acceptance) -- h_abs is raised to min_step there; after a rejection it is not, and h_abs < min_step fails.
@@ -210,53 +233,66 @@ __device__ void rk45_next_attempt(Rk45State* st, bool start) {
     st->h = h; st->t_new = t_new; st->h_abs = fabs(h);
 }
 
-// y = double(x), xs = x (the first forward's input), controller state, time row of f(t0, y0)
-__global__ void __launch_bounds__(256) rk45_setup_kernel(const float* x, double* y, float* xs, int n, Rk45State* st, double t0, double t1,
-                                                         double rtol, double atol, int max_attempts, float t_scale, float* tvec, int rows) {
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) {
-            Rk45State s{};
-            s.t = t0; s.t_bound = t1; s.dir = t1 > t0 ? 1.0 : -1.0; s.rtol = rtol; s.atol = atol; s.max_attempts = max_attempts;
-            s.nfev = 1;
-            *st = s;
-        }
-        write_tvec(tvec, rows, stage_time(t0, t_scale));
-    }
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
-        const float4 v = *reinterpret_cast<const float4*>(x + i);
-        *reinterpret_cast<float4*>(xs + i) = v;
-        *reinterpret_cast<double2*>(y + i) = make_double2(v.x, v.y);
-        *reinterpret_cast<double2*>(y + i + 2) = make_double2(v.z, v.w);
-    }
-}
-
 __device__ __forceinline__ void load_y4(const double* y, int i, double o[4]) {
     const double2 a = *reinterpret_cast<const double2*>(y + i), b = *reinterpret_cast<const double2*>(y + i + 2);
     o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
 }
 __device__ __forceinline__ void f4_to(const float4 v, double o[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
 
+// xs = float32(y) over this workgroup's part of a group (the rows of a group that no longer steps)
+__device__ __forceinline__ void rk45_hold(const double* y, float* xs, int base, int m) {
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        double yv[4];
+        load_y4(y, base + j, yv);
+        *reinterpret_cast<float4*>(xs + base + j) = make_float4((float)yv[0], (float)yv[1], (float)yv[2], (float)yv[3]);
+    }
+}
+
+// y = double(x), xs = x (the first forward's input), controller state, time rows of f(t0, y0)
+__global__ void __launch_bounds__(256) rk45_setup_kernel(const float* x, double* y, float* xs, int m, int spg, Rk45State* st, double t0,
+                                                         double t1, double rtol, double atol, int max_attempts, float t_scale, float* tvec,
+                                                         int cfg_on) {
+    const int g = blockIdx.y, base = g * m;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) {
+            Rk45State s{};
+            s.t = t0; s.t_bound = t1; s.dir = t1 > t0 ? 1.0 : -1.0; s.rtol = rtol; s.atol = atol; s.max_attempts = max_attempts;
+            s.nfev = 1;
+            st[g] = s;
+        }
+        write_trows(tvec, g, gridDim.y, spg, cfg_on, stage_time(t0, t_scale));
+    }
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const float4 v = *reinterpret_cast<const float4*>(x + base + j);
+        *reinterpret_cast<float4*>(xs + base + j) = v;
+        *reinterpret_cast<double2*>(y + base + j) = make_double2(v.x, v.y);
+        *reinterpret_cast<double2*>(y + base + j + 2) = make_double2(v.z, v.w);
+    }
+}
+
 // select_initial_step, part 1: f0 = blend(v2) -> K0; partial sums of (y0/scale)^2 and (f0/scale)^2, scale = atol + |y0| rtol
-__global__ void __launch_bounds__(256) rk45_d01_kernel(const Rk45State* st, const double* y, float* k0, const float* v2, int n, int cfg_on,
-                                                       float cfg, double* part) {
+__global__ void __launch_bounds__(256) rk45_d01_kernel(const Rk45State* st, const double* y, float* k0, const float* v2, int m,
+                                                       int cfg_on, float cfg, double* part) {
     __shared__ double red[256];
-    const double rtol = st->rtol, atol = st->atol;
+    const int g = blockIdx.y, base = g * m, n = gridDim.y * m;
+    const double rtol = st[g].rtol, atol = st[g].atol;
     double s0 = 0.0, s1 = 0.0;
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const int i = base + j;
         const float4 f = load_v(v2, i, n, cfg_on, cfg);
         *reinterpret_cast<float4*>(k0 + i) = f;
         double yv[4], fv[4];
         load_y4(y, i, yv); f4_to(f, fv);
-        for (int j = 0; j < 4; ++j) {
-            const double sc = atol + fabs(yv[j]) * rtol;
-            const double a = yv[j] / sc, b = fv[j] / sc;
-            s0 += a * a; s1 += b * b;
+        for (int q = 0; q < 4; ++q) {
+            const double sc = atol + fabs(yv[q]) * rtol;
+            const double a = yv[q] / sc, c = fv[q] / sc;
+            s0 += a * a; s1 += c * c;
         }
     }
     const double r0 = block_sum(s0, red);
     __syncthreads();
     const double r1 = block_sum(s1, red);
-    if (threadIdx.x == 0) { part[2 * blockIdx.x] = r0; part[2 * blockIdx.x + 1] = r1; }
+    if (threadIdx.x == 0) { double* p = group_part(part, g); p[0] = r0; p[1] = r1; }
 }
 
 // select_initial_step up to h0, from the sums of (y0/scale)^2 and (f0/scale)^2 over n unknowns; returns h0
@@ -269,21 +305,30 @@ __device__ __forceinline__ double rk45_select_h0(Rk45State* st, double s0, doubl
     return h0;
 }
 
-// select_initial_step, part 2 (one workgroup): d0, d1 -> h0; time row of f(t0 + h0 dir, y1)
-__global__ void __launch_bounds__(256) rk45_h0_kernel(Rk45State* st, const double* part, int nblk, int n, float t_scale, float* tvec,
-                                                      int rows) {
+// select_initial_step, part 2 (one workgroup per group): d0, d1 -> h0; time rows of f(t0 + h0 dir, y1)
+__global__ void __launch_bounds__(256) rk45_h0_kernel(Rk45State* st, const double* part, int chunks, int m, int spg, float t_scale,
+                                                      float* tvec, int cfg_on) {
     __shared__ double red[256];
-    __shared__ double sh_h0;
-    const double s0 = reduce_parts(part, nblk, 2, 0, red), s1 = reduce_parts(part, nblk, 2, 1, red);
-    if (threadIdx.x == 0) sh_h0 = rk45_select_h0(st, s0, s1, n);
-    __syncthreads();
-    write_tvec(tvec, rows, stage_time(st->t + sh_h0 * st->dir, t_scale));
+    const int g = blockIdx.x;
+    const double* p = part + 2 * (size_t)g * chunks;
+    const double s0 = reduce_parts(p, chunks, 2, 0, red), s1 = reduce_parts(p, chunks, 2, 1, red);
+    if (threadIdx.x == 0) {
+        Rk45State* sg = st + g;
+        const double h0 = rk45_select_h0(sg, s0, s1, m);
+        const float tv = stage_time(sg->t + h0 * sg->dir, t_scale);
+        for (int r = g * spg; r < (g + 1) * spg; ++r) {   // (runs once per solve: one thread writes the group's rows)
+            tvec[r] = tv;
+            if (cfg_on) tvec[gridDim.x * spg + r] = tv;
+        }
+    }
 }
 
 // xs = float32(y0 + h0 dir f0)
-__global__ void __launch_bounds__(256) rk45_y1_kernel(const Rk45State* st, const double* y, const float* k0, float* xs, int n) {
-    const double hd = st->h0 * st->dir;
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+__global__ void __launch_bounds__(256) rk45_y1_kernel(const Rk45State* st, const double* y, const float* k0, float* xs, int m) {
+    const int g = blockIdx.y, base = g * m;
+    const double hd = st[g].h0 * st[g].dir;
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const int i = base + j;
         double yv[4], fv[4];
         load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), fv);
         float4 o;
@@ -294,21 +339,23 @@ __global__ void __launch_bounds__(256) rk45_y1_kernel(const Rk45State* st, const
 }
 
 // select_initial_step, part 3: partial sums of ((f1 - f0)/scale)^2
-__global__ void __launch_bounds__(256) rk45_d2_kernel(const Rk45State* st, const double* y, const float* k0, const float* v2, int n,
+__global__ void __launch_bounds__(256) rk45_d2_kernel(const Rk45State* st, const double* y, const float* k0, const float* v2, int m,
                                                       int cfg_on, float cfg, double* part) {
     __shared__ double red[256];
-    const double rtol = st->rtol, atol = st->atol;
+    const int g = blockIdx.y, base = g * m, n = gridDim.y * m;
+    const double rtol = st[g].rtol, atol = st[g].atol;
     double s = 0.0;
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
+        const int i = base + j;
         double yv[4], f0[4], f1[4];
         load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), f0); f4_to(load_v(v2, i, n, cfg_on, cfg), f1);
-        for (int j = 0; j < 4; ++j) {
-            const double a = (f1[j] - f0[j]) / (atol + fabs(yv[j]) * rtol);
+        for (int q = 0; q < 4; ++q) {
+            const double a = (f1[q] - f0[q]) / (atol + fabs(yv[q]) * rtol);
             s += a * a;
         }
     }
     const double r = block_sum(s, red);
-    if (threadIdx.x == 0) part[2 * blockIdx.x] = r;
+    if (threadIdx.x == 0) group_part(part, g)[0] = r;
 }
 
 // select_initial_step from the sum of ((f1 - f0)/scale)^2 over n unknowns: h1, the first step, the first attempt
@@ -321,22 +368,29 @@ __device__ __forceinline__ void rk45_select_h1(Rk45State* st, double s2, int n) 
     rk45_next_attempt(st, true);
 }
 
-// select_initial_step, part 4 (one workgroup): d2 -> h1 -> first step; the first attempt's h and t_new
-__global__ void __launch_bounds__(256) rk45_h1_kernel(Rk45State* st, const double* part, int nblk, int n) {
+// select_initial_step, part 4 (one workgroup per group): d2 -> h1 -> first step; the first attempt's h and t_new
+__global__ void __launch_bounds__(256) rk45_h1_kernel(Rk45State* st, const double* part, int chunks, int m) {
     __shared__ double red[256];
-    const double s2 = reduce_parts(part, nblk, 2, 0, red);
-    if (threadIdx.x == 0) rk45_select_h1(st, s2, n);
+    const int g = blockIdx.x;
+    const double s2 = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
+    if (threadIdx.x == 0) {
+        rk45_select_h1(st + g, s2, m);
+        rk45_freeze(st + g);
+    }
 }
 
 // Stage s = 1..5 of rk_step: K[s-1] = blend(v2) (s >= 2; K0 is the committed f); xs = float32(y + (sum_{j<s} A[s][j] K_j) h);
-// time row of stage s.
+// time rows of stage s.
 template <int s>
-__global__ void __launch_bounds__(256) rk45_stage_kernel(const Rk45State* st, const double* y, Rk45K kk, const float* v2, int n,
-                                                         int cfg_on, float cfg, float* xs, float t_scale, float* tvec, int rows) {
-    const double h = st->h;
-    if (blockIdx.x == 0) write_tvec(tvec, rows, stage_time(st->t + c_rk45_C[s] * h, t_scale));
+__global__ void __launch_bounds__(256) rk45_stage_kernel(const Rk45State* st, const double* y, Rk45K kk, const float* v2, int m, int spg,
+                                                         int cfg_on, float cfg, float* xs, float t_scale, float* tvec) {
+    const int g = blockIdx.y, base = g * m, n = gridDim.y * m;
+    const double h = st[g].h;
+    if (blockIdx.x == 0) write_trows(tvec, g, gridDim.y, spg, cfg_on, stage_time(st[g].t + c_rk45_C[s] * h, t_scale));
+    if (!rk45_live(st[g])) { rk45_hold(y, xs, base, m); return; }
     float* kprev = kk.k[s - 1];
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+        const int i = base + jj;
         double acc[4] = {0.0, 0.0, 0.0, 0.0}, kv[4];
 #pragma unroll
         for (int j = 0; j < s; ++j) {
@@ -356,13 +410,16 @@ __global__ void __launch_bounds__(256) rk45_stage_kernel(const Rk45State* st, co
     }
 }
 
-// K5 = blend(v2); y_new = y + h (sum_j B_j K_j); xs = float32(y_new); time row of f(t + h, y_new)
+// K5 = blend(v2); y_new = y + h (sum_j B_j K_j); xs = float32(y_new); time rows of f(t + h, y_new)
 __global__ void __launch_bounds__(256) rk45_finish_kernel(const Rk45State* st, const double* y, double* y_new, Rk45K kk,
-                                                          const float* v2, int n, int cfg_on, float cfg, float* xs, float t_scale,
-                                                          float* tvec, int rows) {
-    const double h = st->h;
-    if (blockIdx.x == 0) write_tvec(tvec, rows, stage_time(st->t + h, t_scale));
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+                                                          const float* v2, int m, int spg, int cfg_on, float cfg, float* xs,
+                                                          float t_scale, float* tvec) {
+    const int g = blockIdx.y, base = g * m, n = gridDim.y * m;
+    const double h = st[g].h;
+    if (blockIdx.x == 0) write_trows(tvec, g, gridDim.y, spg, cfg_on, stage_time(st[g].t + h, t_scale));
+    if (!rk45_live(st[g])) { rk45_hold(y, xs, base, m); return; }
+    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+        const int i = base + jj;
         double acc[4], kv[4];
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
@@ -370,8 +427,8 @@ __global__ void __launch_bounds__(256) rk45_finish_kernel(const Rk45State* st, c
             if (j == 5) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[5] + i) = k; }
             else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
             f4_to(k, kv);
-            const double b = c_rk45_B[j];
-            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * b : acc[q] + kv[q] * b;
+            const double c = c_rk45_B[j];
+            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * c : acc[q] + kv[q] * c;
         }
         double yv[4], o[4];
         load_y4(y, i, yv);
@@ -384,31 +441,35 @@ __global__ void __launch_bounds__(256) rk45_finish_kernel(const Rk45State* st, c
 
 // K6 = blend(v2) = f(t + h, y_new); partial sums of ((sum_j E_j K_j) h / scale)^2, scale = atol + max(|y|, |y_new|) rtol
 __global__ void __launch_bounds__(256) rk45_error_kernel(const Rk45State* st, const double* y, const double* y_new, Rk45K kk,
-                                                         const float* v2, int n, int cfg_on, float cfg, double* part) {
+                                                         const float* v2, int m, int cfg_on, float cfg, double* part) {
     __shared__ double red[256];
-    const double h = st->h, rtol = st->rtol, atol = st->atol;
+    const int g = blockIdx.y, base = g * m, n = gridDim.y * m;
+    const double h = st[g].h, rtol = st[g].rtol, atol = st[g].atol;
     double s = 0.0;
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
-        double acc[4], kv[4];
+    if (rk45_live(st[g])) {
+        for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+            const int i = base + jj;
+            double acc[4], kv[4];
 #pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            float4 k;
-            if (j == 6) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[6] + i) = k; }
-            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
-            f4_to(k, kv);
-            const double e = c_rk45_E[j];
-            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * e : acc[q] + kv[q] * e;
-        }
-        double yv[4], yn[4];
-        load_y4(y, i, yv); load_y4(y_new, i, yn);
-        for (int q = 0; q < 4; ++q) {
-            const double sc = atol + np_maximum(fabs(yv[q]), fabs(yn[q])) * rtol;
-            const double a = acc[q] * h / sc;
-            s += a * a;
+            for (int j = 0; j < 7; ++j) {
+                float4 k;
+                if (j == 6) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[6] + i) = k; }
+                else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
+                f4_to(k, kv);
+                const double e = c_rk45_E[j];
+                for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * e : acc[q] + kv[q] * e;
+            }
+            double yv[4], yn[4];
+            load_y4(y, i, yv); load_y4(y_new, i, yn);
+            for (int q = 0; q < 4; ++q) {
+                const double sc = atol + np_maximum(fabs(yv[q]), fabs(yn[q])) * rtol;
+                const double a = acc[q] * h / sc;
+                s += a * a;
+            }
         }
     }
     const double r = block_sum(s, red);
-    if (threadIdx.x == 0) part[2 * blockIdx.x] = r;
+    if (threadIdx.x == 0) group_part(part, g)[0] = r;
 }
 
 // Accept / reject on the error norm `en` (RungeKutta._step_impl), the next attempt, the status record
@@ -437,22 +498,46 @@ __device__ __forceinline__ void rk45_decide(Rk45State* st, double en) {
     }
 }
 
-// One workgroup: error norm, then rk45_decide
-__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int nblk, int n) {
+// one workgroup per group: its error norm and decision; a group that no longer steps only clears accepted_last
+__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int chunks, int m) {
     __shared__ double red[256];
-    const double s = reduce_parts(part, nblk, 2, 0, red);
+    const int g = blockIdx.x;
+    Rk45State* sg = st + g;
+    if (!rk45_live(*sg)) {
+        if (threadIdx.x == 0) sg->accepted_last = 0;
+        return;
+    }
+    const double s = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
     if (threadIdx.x != 0) return;
-    rk45_decide(st, sqrt(s) / sqrt((double)n));
+    rk45_decide(sg, sqrt(s) / sqrt((double)m));
+    rk45_freeze(sg);
 }
 
 // on acceptance: y <- y_new, K0 <- K6 (FSAL)
-__global__ void __launch_bounds__(256) rk45_commit_kernel(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int n) {
-    if (!st->accepted_last) return;
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+__global__ void __launch_bounds__(256) rk45_commit_kernel(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6,
+                                                          int m) {
+    const int g = blockIdx.y, base = g * m;
+    if (!st[g].accepted_last) return;
+    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+        const int i = base + jj;
         *reinterpret_cast<double2*>(y + i) = *reinterpret_cast<const double2*>(y_new + i);
         *reinterpret_cast<double2*>(y + i + 2) = *reinterpret_cast<const double2*>(y_new + i + 2);
         *reinterpret_cast<float4*>(k0 + i) = *reinterpret_cast<const float4*>(k6 + i);
     }
+}
+
+// one workgroup: how many groups still step, how many failed
+__global__ void __launch_bounds__(256) rk45_status_kernel(const Rk45State* st, int G, Rk45Status* out) {
+    __shared__ double red[256];
+    double live = 0.0, failed = 0.0;
+    for (int g = threadIdx.x; g < G; g += 256) {
+        live += rk45_live(st[g]) ? 1.0 : 0.0;
+        failed += st[g].failed ? 1.0 : 0.0;
+    }
+    const double rl = block_sum(live, red);
+    __syncthreads();
+    const double rf = block_sum(failed, red);
+    if (threadIdx.x == 0) { out->unfinished = (int)rl; out->failed = (int)rf; }
 }
 
 __global__ void __launch_bounds__(256) rk45_out_kernel(const double* y, float* x, int n) {
@@ -463,393 +548,76 @@ __global__ void __launch_bounds__(256) rk45_out_kernel(const double* y, float* x
     }
 }
 
-int rk45_parts(int n) { return egrid(n); }
+int rk45_chunks(int m, int cap) { int c = (m / 4 + 255) / 256; return c < 1 ? 1 : (c > cap ? cap : c); }
 
-#define RK45_LAUNCH(kern, grid, ...)                                                    \
-    do {                                                                                \
-        if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4"); \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, __VA_ARGS__);             \
-        FC_HIP(hipGetLastError());                                                      \
-        return FC_OK;                                                                   \
+#define RK45_LAUNCH(kern, grid, ...)                                                                                   \
+    do {                                                                                                               \
+        if ((g.m & 3) || g.m < 4 || g.G < 1 || g.spg < 1 || g.chunks < 1)                                              \
+            return fail(FC_E_SHAPE, "rk45: element count of a controller group must be a positive multiple of 4");     \
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, __VA_ARGS__);                                                  \
+        FC_HIP(hipGetLastError());                                                                                     \
+        return FC_OK;                                                                                                  \
     } while (0)
+#define RK45_GRID dim3(g.chunks, g.G)
 
-int rk45_setup_launch(const float* x, double* y, float* xs, int n, Rk45State* st, double t0, double t1, double rtol, double atol,
-                      int max_attempts, float t_scale, float* tvec, int rows, hipStream_t s) {
-    RK45_LAUNCH(rk45_setup_kernel, egrid(n), x, y, xs, n, st, t0, t1, rtol, atol, max_attempts, t_scale, tvec, rows);
+int rk45_setup_launch(const Rk45Groups& g, const float* x, double* y, float* xs, Rk45State* st, double t0, double t1, double rtol,
+                      double atol, int max_attempts, float t_scale, float* tvec, int cfg_on, hipStream_t s) {
+    RK45_LAUNCH(rk45_setup_kernel, RK45_GRID, x, y, xs, g.m, g.spg, st, t0, t1, rtol, atol, max_attempts, t_scale, tvec, cfg_on);
 }
-int rk45_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int n, int cfg_on, float cfg, double* part, hipStream_t s) {
-    RK45_LAUNCH(rk45_d01_kernel, egrid(n), st, y, k0, v2, n, cfg_on, cfg, part);
+int rk45_d01_launch(const Rk45Groups& g, const Rk45State* st, const double* y, float* k0, const float* v2, int cfg_on, float cfg,
+                    double* part, hipStream_t s) {
+    RK45_LAUNCH(rk45_d01_kernel, RK45_GRID, st, y, k0, v2, g.m, cfg_on, cfg, part);
 }
-int rk45_h0_launch(Rk45State* st, const double* part, int n, float t_scale, float* tvec, int rows, hipStream_t s) {
-    RK45_LAUNCH(rk45_h0_kernel, 1, st, part, egrid(n), n, t_scale, tvec, rows);
+int rk45_h0_launch(const Rk45Groups& g, Rk45State* st, const double* part, float t_scale, float* tvec, int cfg_on, hipStream_t s) {
+    RK45_LAUNCH(rk45_h0_kernel, dim3(g.G), st, part, g.chunks, g.m, g.spg, t_scale, tvec, cfg_on);
 }
-int rk45_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int n, hipStream_t s) {
-    RK45_LAUNCH(rk45_y1_kernel, egrid(n), st, y, k0, xs, n);
+int rk45_y1_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, float* xs, hipStream_t s) {
+    RK45_LAUNCH(rk45_y1_kernel, RK45_GRID, st, y, k0, xs, g.m);
 }
-int rk45_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int n, int cfg_on, float cfg, double* part,
-                   hipStream_t s) {
-    RK45_LAUNCH(rk45_d2_kernel, egrid(n), st, y, k0, v2, n, cfg_on, cfg, part);
+int rk45_d2_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, const float* v2, int cfg_on, float cfg,
+                   double* part, hipStream_t s) {
+    RK45_LAUNCH(rk45_d2_kernel, RK45_GRID, st, y, k0, v2, g.m, cfg_on, cfg, part);
 }
-int rk45_h1_launch(Rk45State* st, const double* part, int n, hipStream_t s) {
-    RK45_LAUNCH(rk45_h1_kernel, 1, st, part, egrid(n), n);
+int rk45_h1_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s) {
+    RK45_LAUNCH(rk45_h1_kernel, dim3(g.G), st, part, g.chunks, g.m);
 }
-int rk45_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
-                      float* xs, float t_scale, float* tvec, int rows, hipStream_t s) {
+int rk45_stage_launch(const Rk45Groups& g, const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int cfg_on,
+                      float cfg, float* xs, float t_scale, float* tvec, hipStream_t s) {
     switch (stage) {
-        case 1: RK45_LAUNCH(rk45_stage_kernel<1>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
-        case 2: RK45_LAUNCH(rk45_stage_kernel<2>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
-        case 3: RK45_LAUNCH(rk45_stage_kernel<3>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
-        case 4: RK45_LAUNCH(rk45_stage_kernel<4>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
-        case 5: RK45_LAUNCH(rk45_stage_kernel<5>, egrid(n), st, y, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+        case 1: RK45_LAUNCH(rk45_stage_kernel<1>, RK45_GRID, st, y, kk, v2, g.m, g.spg, cfg_on, cfg, xs, t_scale, tvec);
+        case 2: RK45_LAUNCH(rk45_stage_kernel<2>, RK45_GRID, st, y, kk, v2, g.m, g.spg, cfg_on, cfg, xs, t_scale, tvec);
+        case 3: RK45_LAUNCH(rk45_stage_kernel<3>, RK45_GRID, st, y, kk, v2, g.m, g.spg, cfg_on, cfg, xs, t_scale, tvec);
+        case 4: RK45_LAUNCH(rk45_stage_kernel<4>, RK45_GRID, st, y, kk, v2, g.m, g.spg, cfg_on, cfg, xs, t_scale, tvec);
+        case 5: RK45_LAUNCH(rk45_stage_kernel<5>, RK45_GRID, st, y, kk, v2, g.m, g.spg, cfg_on, cfg, xs, t_scale, tvec);
         default: return fail(FC_E_ARG, "rk45: stage must lie in [1, 5]");
     }
 }
-int rk45_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int n, int cfg_on, float cfg,
-                       float* xs, float t_scale, float* tvec, int rows, hipStream_t s) {
-    RK45_LAUNCH(rk45_finish_kernel, egrid(n), st, y, y_new, kk, v2, n, cfg_on, cfg, xs, t_scale, tvec, rows);
+int rk45_finish_launch(const Rk45Groups& g, const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int cfg_on,
+                       float cfg, float* xs, float t_scale, float* tvec, hipStream_t s) {
+    RK45_LAUNCH(rk45_finish_kernel, RK45_GRID, st, y, y_new, kk, v2, g.m, g.spg, cfg_on, cfg, xs, t_scale, tvec);
 }
-int rk45_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int n, int cfg_on,
-                      float cfg, double* part, hipStream_t s) {
-    RK45_LAUNCH(rk45_error_kernel, egrid(n), st, y, y_new, kk, v2, n, cfg_on, cfg, part);
+int rk45_error_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2,
+                      int cfg_on, float cfg, double* part, hipStream_t s) {
+    RK45_LAUNCH(rk45_error_kernel, RK45_GRID, st, y, y_new, kk, v2, g.m, cfg_on, cfg, part);
 }
-int rk45_control_launch(Rk45State* st, const double* part, int n, hipStream_t s) {
-    RK45_LAUNCH(rk45_control_kernel, 1, st, part, egrid(n), n);
+int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s) {
+    RK45_LAUNCH(rk45_control_kernel, dim3(g.G), st, part, g.chunks, g.m);
 }
-int rk45_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int n, hipStream_t s) {
-    RK45_LAUNCH(rk45_commit_kernel, egrid(n), st, y, y_new, k0, k6, n);
+int rk45_commit_launch(const Rk45Groups& g, const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6,
+                       hipStream_t s) {
+    RK45_LAUNCH(rk45_commit_kernel, RK45_GRID, st, y, y_new, k0, k6, g.m);
 }
-int rk45_out_launch(const double* y, float* x, int n, hipStream_t s) {
-    RK45_LAUNCH(rk45_out_kernel, egrid(n), y, x, n);
+int rk45_status_launch(const Rk45Groups& g, const Rk45State* st, Rk45Status* out, hipStream_t s) {
+    RK45_LAUNCH(rk45_status_kernel, dim3(1), st, g.G, out);
 }
+#undef RK45_GRID
 #undef RK45_LAUNCH
 
-// ================================================================================================ per-sample adaptive RK45
-// Every sample b is its own solve_ivp problem over its m = C*H*W unknowns: its own select_initial_step, error norm, step size,
-// accept / reject decisions and counters (st[b]), with the arithmetic of the batch-coupled kernels above.  The elementwise and
-// reduction kernels run on a (chunks, B) grid: blockIdx.y is the sample, and its `chunks` workgroups stride over its m unknowns.
-// `chunks` depends on m alone, so the fp64 partial sums of a sample's norms ([B][chunks][2]) -- reduced in a fixed order by one
-// workgroup per sample -- and with them its step sequence do not depend on the batch size or on the other samples.  A sample that
-// has finished or failed keeps h = 0: its rows are still evaluated (at float32(y), t), its state, counters and K stay as they are.
-
-int rk45ps_chunks(int m) { int g = (m / 4 + 255) / 256; return g < 1 ? 1 : (g > 64 ? 64 : g); }
-
-__device__ __forceinline__ bool rk45_live(const Rk45State& s) { return !s.done && !s.failed; }
-
-// after a decision: a finished or failed sample keeps h = 0
-__device__ __forceinline__ void rk45ps_freeze(Rk45State* st) {
-    if (!rk45_live(*st)) { st->h = 0.0; st->t_new = st->t; }
-}
-
-// the time rows of sample b: row b, and with CFG its unguided twin B + b
-__device__ __forceinline__ void write_trow(float* tvec, int b, int B, int cfg_on, float tv) {
-    tvec[b] = tv;
-    if (cfg_on) tvec[B + b] = tv;
-}
-
-// xs = float32(y) over this workgroup's part of sample b (the rows of a sample that no longer steps)
-__device__ __forceinline__ void rk45ps_hold(const double* y, float* xs, int base, int m) {
-    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
-        double yv[4];
-        load_y4(y, base + j, yv);
-        *reinterpret_cast<float4*>(xs + base + j) = make_float4((float)yv[0], (float)yv[1], (float)yv[2], (float)yv[3]);
-    }
-}
-
-__device__ __forceinline__ double* ps_part(double* part, int b) { return part + 2 * ((size_t)b * gridDim.x + blockIdx.x); }
-
-__global__ void __launch_bounds__(256) rk45ps_setup_kernel(const float* x, double* y, float* xs, int m, Rk45State* st, double t0, double t1,
-                                                           double rtol, double atol, int max_attempts, float t_scale, float* tvec,
-                                                           int cfg_on) {
-    const int b = blockIdx.y, base = b * m;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        Rk45State s{};
-        s.t = t0; s.t_bound = t1; s.dir = t1 > t0 ? 1.0 : -1.0; s.rtol = rtol; s.atol = atol; s.max_attempts = max_attempts;
-        s.nfev = 1;
-        st[b] = s;
-        write_trow(tvec, b, gridDim.y, cfg_on, stage_time(t0, t_scale));
-    }
-    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
-        const float4 v = *reinterpret_cast<const float4*>(x + base + j);
-        *reinterpret_cast<float4*>(xs + base + j) = v;
-        *reinterpret_cast<double2*>(y + base + j) = make_double2(v.x, v.y);
-        *reinterpret_cast<double2*>(y + base + j + 2) = make_double2(v.z, v.w);
-    }
-}
-
-__global__ void __launch_bounds__(256) rk45ps_d01_kernel(const Rk45State* st, const double* y, float* k0, const float* v2, int m,
-                                                         int cfg_on, float cfg, double* part) {
-    __shared__ double red[256];
-    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
-    const double rtol = st[b].rtol, atol = st[b].atol;
-    double s0 = 0.0, s1 = 0.0;
-    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
-        const int i = base + j;
-        const float4 f = load_v(v2, i, n, cfg_on, cfg);
-        *reinterpret_cast<float4*>(k0 + i) = f;
-        double yv[4], fv[4];
-        load_y4(y, i, yv); f4_to(f, fv);
-        for (int q = 0; q < 4; ++q) {
-            const double sc = atol + fabs(yv[q]) * rtol;
-            const double a = yv[q] / sc, c = fv[q] / sc;
-            s0 += a * a; s1 += c * c;
-        }
-    }
-    const double r0 = block_sum(s0, red);
-    __syncthreads();
-    const double r1 = block_sum(s1, red);
-    if (threadIdx.x == 0) { double* p = ps_part(part, b); p[0] = r0; p[1] = r1; }
-}
-
-// one workgroup per sample
-__global__ void __launch_bounds__(256) rk45ps_h0_kernel(Rk45State* st, const double* part, int chunks, int m, float t_scale, float* tvec,
-                                                        int cfg_on) {
-    __shared__ double red[256];
-    const int b = blockIdx.x;
-    const double* p = part + 2 * (size_t)b * chunks;
-    const double s0 = reduce_parts(p, chunks, 2, 0, red), s1 = reduce_parts(p, chunks, 2, 1, red);
-    if (threadIdx.x == 0) {
-        Rk45State* sb = st + b;
-        const double h0 = rk45_select_h0(sb, s0, s1, m);
-        write_trow(tvec, b, gridDim.x, cfg_on, stage_time(sb->t + h0 * sb->dir, t_scale));
-    }
-}
-
-__global__ void __launch_bounds__(256) rk45ps_y1_kernel(const Rk45State* st, const double* y, const float* k0, float* xs, int m) {
-    const int b = blockIdx.y, base = b * m;
-    const double hd = st[b].h0 * st[b].dir;
-    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
-        const int i = base + j;
-        double yv[4], fv[4];
-        load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), fv);
-        float4 o;
-        o.x = (float)(yv[0] + hd * fv[0]); o.y = (float)(yv[1] + hd * fv[1]);
-        o.z = (float)(yv[2] + hd * fv[2]); o.w = (float)(yv[3] + hd * fv[3]);
-        *reinterpret_cast<float4*>(xs + i) = o;
-    }
-}
-
-__global__ void __launch_bounds__(256) rk45ps_d2_kernel(const Rk45State* st, const double* y, const float* k0, const float* v2, int m,
-                                                        int cfg_on, float cfg, double* part) {
-    __shared__ double red[256];
-    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
-    const double rtol = st[b].rtol, atol = st[b].atol;
-    double s = 0.0;
-    for (int j = 4 * (blockIdx.x * 256 + threadIdx.x); j < m; j += 4 * gridDim.x * 256) {
-        const int i = base + j;
-        double yv[4], f0[4], f1[4];
-        load_y4(y, i, yv); f4_to(*reinterpret_cast<const float4*>(k0 + i), f0); f4_to(load_v(v2, i, n, cfg_on, cfg), f1);
-        for (int q = 0; q < 4; ++q) {
-            const double a = (f1[q] - f0[q]) / (atol + fabs(yv[q]) * rtol);
-            s += a * a;
-        }
-    }
-    const double r = block_sum(s, red);
-    if (threadIdx.x == 0) ps_part(part, b)[0] = r;
-}
-
-// one workgroup per sample
-__global__ void __launch_bounds__(256) rk45ps_h1_kernel(Rk45State* st, const double* part, int chunks, int m) {
-    __shared__ double red[256];
-    const int b = blockIdx.x;
-    const double s2 = reduce_parts(part + 2 * (size_t)b * chunks, chunks, 2, 0, red);
-    if (threadIdx.x == 0) {
-        rk45_select_h1(st + b, s2, m);
-        rk45ps_freeze(st + b);
-    }
-}
-
-template <int s>
-__global__ void __launch_bounds__(256) rk45ps_stage_kernel(const Rk45State* st, const double* y, Rk45K kk, const float* v2, int m,
-                                                           int cfg_on, float cfg, float* xs, float t_scale, float* tvec) {
-    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
-    const double h = st[b].h;
-    if (blockIdx.x == 0 && threadIdx.x == 0) write_trow(tvec, b, gridDim.y, cfg_on, stage_time(st[b].t + c_rk45_C[s] * h, t_scale));
-    if (!rk45_live(st[b])) { rk45ps_hold(y, xs, base, m); return; }
-    float* kprev = kk.k[s - 1];
-    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
-        const int i = base + jj;
-        double acc[4] = {0.0, 0.0, 0.0, 0.0}, kv[4];
-#pragma unroll
-        for (int j = 0; j < s; ++j) {
-            float4 k;
-            if (j == s - 1 && s >= 2) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kprev + i) = k; }
-            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
-            f4_to(k, kv);
-            const double a = c_rk45_A[s][j];
-            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * a : acc[q] + kv[q] * a;
-        }
-        double yv[4];
-        load_y4(y, i, yv);
-        float4 o;
-        o.x = (float)(yv[0] + acc[0] * h); o.y = (float)(yv[1] + acc[1] * h);
-        o.z = (float)(yv[2] + acc[2] * h); o.w = (float)(yv[3] + acc[3] * h);
-        *reinterpret_cast<float4*>(xs + i) = o;
-    }
-}
-
-__global__ void __launch_bounds__(256) rk45ps_finish_kernel(const Rk45State* st, const double* y, double* y_new, Rk45K kk,
-                                                            const float* v2, int m, int cfg_on, float cfg, float* xs, float t_scale,
-                                                            float* tvec) {
-    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
-    const double h = st[b].h;
-    if (blockIdx.x == 0 && threadIdx.x == 0) write_trow(tvec, b, gridDim.y, cfg_on, stage_time(st[b].t + h, t_scale));
-    if (!rk45_live(st[b])) { rk45ps_hold(y, xs, base, m); return; }
-    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
-        const int i = base + jj;
-        double acc[4], kv[4];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            float4 k;
-            if (j == 5) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[5] + i) = k; }
-            else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
-            f4_to(k, kv);
-            const double c = c_rk45_B[j];
-            for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * c : acc[q] + kv[q] * c;
-        }
-        double yv[4], o[4];
-        load_y4(y, i, yv);
-        for (int q = 0; q < 4; ++q) o[q] = yv[q] + h * acc[q];
-        *reinterpret_cast<double2*>(y_new + i) = make_double2(o[0], o[1]);
-        *reinterpret_cast<double2*>(y_new + i + 2) = make_double2(o[2], o[3]);
-        *reinterpret_cast<float4*>(xs + i) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
-    }
-}
-
-__global__ void __launch_bounds__(256) rk45ps_error_kernel(const Rk45State* st, const double* y, const double* y_new, Rk45K kk,
-                                                           const float* v2, int m, int cfg_on, float cfg, double* part) {
-    __shared__ double red[256];
-    const int b = blockIdx.y, base = b * m, n = gridDim.y * m;
-    const double h = st[b].h, rtol = st[b].rtol, atol = st[b].atol;
-    double s = 0.0;
-    if (rk45_live(st[b])) {
-        for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
-            const int i = base + jj;
-            double acc[4], kv[4];
-#pragma unroll
-            for (int j = 0; j < 7; ++j) {
-                float4 k;
-                if (j == 6) { k = load_v(v2, i, n, cfg_on, cfg); *reinterpret_cast<float4*>(kk.k[6] + i) = k; }
-                else k = *reinterpret_cast<const float4*>(kk.k[j] + i);
-                f4_to(k, kv);
-                const double e = c_rk45_E[j];
-                for (int q = 0; q < 4; ++q) acc[q] = j == 0 ? kv[q] * e : acc[q] + kv[q] * e;
-            }
-            double yv[4], yn[4];
-            load_y4(y, i, yv); load_y4(y_new, i, yn);
-            for (int q = 0; q < 4; ++q) {
-                const double sc = atol + np_maximum(fabs(yv[q]), fabs(yn[q])) * rtol;
-                const double a = acc[q] * h / sc;
-                s += a * a;
-            }
-        }
-    }
-    const double r = block_sum(s, red);
-    if (threadIdx.x == 0) ps_part(part, b)[0] = r;
-}
-
-// one workgroup per sample: its error norm and decision; a sample that no longer steps only clears accepted_last
-__global__ void __launch_bounds__(256) rk45ps_control_kernel(Rk45State* st, const double* part, int chunks, int m) {
-    __shared__ double red[256];
-    const int b = blockIdx.x;
-    Rk45State* sb = st + b;
-    if (!rk45_live(*sb)) {
-        if (threadIdx.x == 0) sb->accepted_last = 0;
-        return;
-    }
-    const double s = reduce_parts(part + 2 * (size_t)b * chunks, chunks, 2, 0, red);
-    if (threadIdx.x != 0) return;
-    rk45_decide(sb, sqrt(s) / sqrt((double)m));
-    rk45ps_freeze(sb);
-}
-
-__global__ void __launch_bounds__(256) rk45ps_commit_kernel(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6,
-                                                            int m) {
-    const int b = blockIdx.y, base = b * m;
-    if (!st[b].accepted_last) return;
-    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
-        const int i = base + jj;
-        *reinterpret_cast<double2*>(y + i) = *reinterpret_cast<const double2*>(y_new + i);
-        *reinterpret_cast<double2*>(y + i + 2) = *reinterpret_cast<const double2*>(y_new + i + 2);
-        *reinterpret_cast<float4*>(k0 + i) = *reinterpret_cast<const float4*>(k6 + i);
-    }
-}
-
-// one workgroup: how many samples still step, how many failed
-__global__ void __launch_bounds__(256) rk45ps_status_kernel(const Rk45State* st, int B, Rk45Status* out) {
-    __shared__ double red[256];
-    double live = 0.0, failed = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        live += rk45_live(st[b]) ? 1.0 : 0.0;
-        failed += st[b].failed ? 1.0 : 0.0;
-    }
-    const double rl = block_sum(live, red);
-    __syncthreads();
-    const double rf = block_sum(failed, red);
-    if (threadIdx.x == 0) { out->unfinished = (int)rl; out->failed = (int)rf; }
-}
-
-#define RK45PS_LAUNCH(kern, grid, ...)                                                                       \
-    do {                                                                                                     \
-        if ((m & 3) || m < 4 || B < 1) return fail(FC_E_SHAPE, "rk45: per-sample element count must be a positive multiple of 4"); \
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, __VA_ARGS__);                                        \
-        FC_HIP(hipGetLastError());                                                                           \
-        return FC_OK;                                                                                        \
-    } while (0)
-#define PS_GRID dim3(rk45ps_chunks(m), B)
-
-int rk45ps_setup_launch(const float* x, double* y, float* xs, int B, int m, Rk45State* st, double t0, double t1, double rtol, double atol,
-                        int max_attempts, float t_scale, float* tvec, int cfg_on, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_setup_kernel, PS_GRID, x, y, xs, m, st, t0, t1, rtol, atol, max_attempts, t_scale, tvec, cfg_on);
-}
-int rk45ps_d01_launch(const Rk45State* st, const double* y, float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
-                      hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_d01_kernel, PS_GRID, st, y, k0, v2, m, cfg_on, cfg, part);
-}
-int rk45ps_h0_launch(Rk45State* st, const double* part, int B, int m, float t_scale, float* tvec, int cfg_on, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_h0_kernel, dim3(B), st, part, rk45ps_chunks(m), m, t_scale, tvec, cfg_on);
-}
-int rk45ps_y1_launch(const Rk45State* st, const double* y, const float* k0, float* xs, int B, int m, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_y1_kernel, PS_GRID, st, y, k0, xs, m);
-}
-int rk45ps_d2_launch(const Rk45State* st, const double* y, const float* k0, const float* v2, int B, int m, int cfg_on, float cfg, double* part,
-                     hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_d2_kernel, PS_GRID, st, y, k0, v2, m, cfg_on, cfg, part);
-}
-int rk45ps_h1_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_h1_kernel, dim3(B), st, part, rk45ps_chunks(m), m);
-}
-int rk45ps_stage_launch(const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
-                        float* xs, float t_scale, float* tvec, hipStream_t s) {
-    switch (stage) {
-        case 1: RK45PS_LAUNCH(rk45ps_stage_kernel<1>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
-        case 2: RK45PS_LAUNCH(rk45ps_stage_kernel<2>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
-        case 3: RK45PS_LAUNCH(rk45ps_stage_kernel<3>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
-        case 4: RK45PS_LAUNCH(rk45ps_stage_kernel<4>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
-        case 5: RK45PS_LAUNCH(rk45ps_stage_kernel<5>, PS_GRID, st, y, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
-        default: return fail(FC_E_ARG, "rk45: stage must lie in [1, 5]");
-    }
-}
-int rk45ps_finish_launch(const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on, float cfg,
-                         float* xs, float t_scale, float* tvec, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_finish_kernel, PS_GRID, st, y, y_new, kk, v2, m, cfg_on, cfg, xs, t_scale, tvec);
-}
-int rk45ps_error_launch(const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2, int B, int m, int cfg_on,
-                        float cfg, double* part, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_error_kernel, PS_GRID, st, y, y_new, kk, v2, m, cfg_on, cfg, part);
-}
-int rk45ps_control_launch(Rk45State* st, const double* part, int B, int m, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_control_kernel, dim3(B), st, part, rk45ps_chunks(m), m);
-}
-int rk45ps_commit_launch(const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6, int B, int m, hipStream_t s) {
-    RK45PS_LAUNCH(rk45ps_commit_kernel, PS_GRID, st, y, y_new, k0, k6, m);
-}
-int rk45ps_status_launch(const Rk45State* st, int B, Rk45Status* out, hipStream_t s) {
-    if (B < 1) return fail(FC_E_ARG, "rk45: batch must be positive");
-    hipLaunchKernelGGL(rk45ps_status_kernel, dim3(1), dim3(256), 0, s, st, B, out);
+int rk45_out_launch(const double* y, float* x, int n, hipStream_t s) {
+    if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
+    hipLaunchKernelGGL(rk45_out_kernel, dim3(egrid(n)), dim3(256), 0, s, y, x, n);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
-#undef PS_GRID
-#undef RK45PS_LAUNCH
 
 }  // namespace fc

@@ -4,6 +4,7 @@
 // Topology follows Unet._forward (unet.py:289-372); every kernel launch below cites the reference lines it
 // covers.  The plan is built once per (max_batch, H, W) -- buffers never move, so one integration step can be
 // captured in a hipGraph and replayed (the reference's per-call host syncs are gone).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -353,17 +354,21 @@ struct Builder : PlanBuilder {
     }
 };
 
-static void free_plan(fc_unet* u) {
+// every cached graph: they bake the addresses of the buffers they were captured with
+static void drop_graphs(fc_unet* u) {
     for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
     u->graphs.clear();
+}
+
+static void free_plan(fc_unet* u) {
+    drop_graphs(u);
     u->plan.release();
     u->bwd.release();                       // the backward plan points into the forward arena
     u->dgrad_packs.clear();
     u->dgrad_table.release();
     for (void* p : u->int_allocs) dev_free(p);
     u->int_allocs.clear();
-    u->rk_y = u->rk_ynew = u->rk_part = nullptr; u->rk_k = Rk45K{}; u->rk_st = nullptr;   // (were in int_allocs)
-    u->rkp_st = nullptr; u->rkp_part = nullptr; u->rkp_sum = nullptr;
+    u->rk_y = u->rk_ynew = u->rk_part = nullptr; u->rk_k = Rk45K{}; u->rk_st = nullptr; u->rk_sum = nullptr;   // (were in int_allocs)
     u->maxB = 0;
     // a rebuilt plan starts clean (callers of free_plan have synchronised the device)
     if (u->dev_err) (void)hipMemset(u->dev_err, 0, sizeof(int));
@@ -933,7 +938,6 @@ void fc_unet_destroy(fc_unet* u) {
     if (u->dev_err) (void)hipFree(u->dev_err);
     if (u->host_err) (void)hipHostFree(const_cast<int*>(u->host_err));
     if (u->rk_host) (void)hipHostFree(u->rk_host);
-    if (u->rkp_host) (void)hipHostFree(u->rkp_host);
     if (u->ev_rk) (void)hipEventDestroy(u->ev_rk);
     delete u;
 }
@@ -1119,6 +1123,42 @@ double fc_unet_flops_per_sample(const fc_unet* u) { return u ? u->plan.flops : 0
 // -------------------------------------------------------------------------------- integrator
 static uint32_t fbits(float f) { uint32_t v; std::memcpy(&v, &f, 4); return v; }
 
+// FLOCODER_AMD_NO_GRAPH: every integrator enqueues its launches directly instead of capturing and replaying graphs
+static bool no_graph() {
+    static const bool v = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
+    return v;
+}
+
+// the graph cached under `key`; on first use it is captured from `enqueue` on `s` and instantiated
+static int cached_graph(fc_unet* u, const decltype(fc_unet::graphs)::key_type& key, hipStream_t s, const std::function<int()>& enqueue,
+                        hipGraphExec_t* out) {
+    auto it = u->graphs.find(key);
+    if (it == u->graphs.end()) {
+        hipGraph_t graph = nullptr;
+        FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int r = enqueue();
+        const hipError_t e = hipStreamEndCapture(s, &graph);
+        if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
+        if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+        hipGraphExec_t exec = nullptr;
+        FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        FC_HIP(hipGraphDestroy(graph));
+        it = u->graphs.emplace(key, exec).first;
+    }
+    *out = it->second;
+    return FC_OK;
+}
+
+// the forward of one integrator evaluation (the caller sets its input x): B rows and, with CFG, their unguided twins B..2B-1, the
+// per-row time from u->tvec, into u->v2
+static FwdCtx integrator_ctx(const fc_unet* u, int B, bool cfg_on, bool has_ids, int mask_mode) {
+    FwdCtx c;
+    c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
+    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
+    c.out = u->v2; c.B = cfg_on ? 2 * B : B;
+    return c;
+}
+
 // enqueue one integration step on `s` (captured into a graph by the caller)
 // Legacy Euler without CFG: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
 static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_EULER && !cfg_on; }
@@ -1126,14 +1166,11 @@ static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_
 static int enqueue_step(fc_unet* u, int method, int B, bool cfg_on, float cfg, float dt_euler, float t_scale, bool has_ids, int mask_mode,
                         bool pre_on, hipStream_t s) {
     const int rows = cfg_on ? 2 * B : B, n = B * u->cfg.channels * u->H * u->W;
-    FwdCtx c;
+    FwdCtx c = integrator_ctx(u, B, cfg_on, has_ids, mask_mode);
     if (pre_on) {   // conditioning rows of every evaluation are in u->pre: init_conv fetches slice *evalc, final_conv advances the counter
         c.fetch.all = u->pre_ss; c.fetch.evalc = u->step + 1; c.fetch.dst = u->plan.ss; c.fetch.n4 = rows * u->S / 4;
         c.euler.evalc = u->step + 1;
     }
-    c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
-    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
-    c.out = u->v2; c.B = rows;
     if (euler_tail_ok(method, cfg_on)) {   // the update and the next interval's time ride in final_conv: no launches around the plan
         c.x = u->y;
         c.euler.y = u->y; c.euler.dt = dt_euler; c.euler.step = u->step; c.euler.ts = u->ts_dev; c.euler.t_scale = t_scale;
@@ -1177,8 +1214,7 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
         if (u->ts_dev) dev_free(u->ts_dev);
         u->ts_cap = n_points < 1024 ? 1024 : n_points + 1;   // + 1: the fused Euler tail reads one entry past the grid after the last step
         FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->ts_dev), u->ts_cap * sizeof(float), "integrator.ts"));
-        for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
-        u->graphs.clear();  // captured graphs hold the old ts pointer
+        drop_graphs(u);  // captured graphs hold the old ts pointer
     }
     const size_t nbytes = (size_t)B * u->cfg.channels * H * W * sizeof(float);
     // the library stream picks up after everything already queued on the caller's stream
@@ -1205,14 +1241,11 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
             u->pre = nullptr; u->pre_cap = 0;
             FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->pre), need * sizeof(float), "integrator.cond_table"));
             u->pre_cap = need;
-            for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
-            u->graphs.clear();  // captured graphs hold the old table pointer
+            drop_graphs(u);  // captured graphs hold the old table pointer
         }
         float *tv = u->pre, *te = tv + tvn, *hh = te + R * u->td, *c1 = hh + R * u->td;
-        if (u->pre_ss != c1 + R * u->td) {   // the table moved inside the buffer (another number of evaluations): graphs bake its address
-            for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
-            u->graphs.clear();
-        }
+        if (u->pre_ss != c1 + R * u->td)   // the table moved inside the buffer (another number of evaluations): graphs bake its address
+            drop_graphs(u);
         u->pre_ss = c1 + R * u->td;
         FC_TRY(ode_all_times_launch(u->ts_dev, n_steps, method == FC_METHOD_RK4, t_scale, tv, s));
         TembArgs ta = u->temb_proto;
@@ -1231,8 +1264,7 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
     if (euler_tail_ok(method, cfg_on))   // time of the first interval; every step publishes its successor's
         FC_TRY(ode_time_launch(u->step, u->ts_dev, t_scale, 0, u->sc, u->tvec, rows, s));
     FC_TRY(meet_enter(u, s));
-    static const bool no_graph = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
-    if (no_graph) {
+    if (no_graph()) {
         for (int i = 0; i < n_steps; ++i) FC_TRY(enqueue_step(u, method, B, cfg_on, cfg_strength, dt_euler, t_scale, has_ids, mask_mode, pre_on, s));
     } else {
         // One graph holds SEVERAL consecutive intervals (round 3): the step counter, the time grid and the conditioning slice index all
@@ -1246,21 +1278,13 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
             const int k = left < per ? left : per;
             const auto key = std::make_tuple(method, B, (int)cfg_on, mask_mode, fbits(cfg_strength), fbits(dt_euler), fbits(t_scale),
                                              (int)has_ids | ((int)pre_on << 1) | (k << 2));
-            auto it = u->graphs.find(key);
-            if (it == u->graphs.end()) {
-                hipGraph_t graph = nullptr;
-                FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            hipGraphExec_t exec = nullptr;
+            FC_TRY(cached_graph(u, key, s, [&] {
                 int r = FC_OK;
                 for (int j = 0; j < k && r == FC_OK; ++j)
                     r = enqueue_step(u, method, B, cfg_on, cfg_strength, dt_euler, t_scale, has_ids, mask_mode, pre_on, s);
-                const hipError_t e = hipStreamEndCapture(s, &graph);
-                if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
-                if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-                hipGraphExec_t exec = nullptr;
-                FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                FC_HIP(hipGraphDestroy(graph));
-                it = u->graphs.emplace(key, exec).first;
-            }
+                return r;
+            }, &exec));
             // The FIRST replay of a call waits, on the host, for everything this call has put on the stream in front of it (round 4).  Under
             // AMD_DIRECT_DISPATCH=0 -- the mode the sampler ships with -- ROCm 7.2 submits a graph from the calling thread while the plain
             // launches and copies issued just before it are still queued in the runtime's own submission thread: the replay overtook them.
@@ -1271,7 +1295,7 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
             // one.  Replays that follow a replay are ordered (RK4: five graphs per call); work issued behind a replay is ordered as well.
             // Cost: the host idles for the prologue (~0.1 ms per call of 80 ms).
             if (left == n_steps) FC_HIP(hipStreamSynchronize(s));
-            FC_HIP(hipGraphLaunch(it->second, s));
+            FC_HIP(hipGraphLaunch(exec, s));
             left -= k;
         }
     }
@@ -1283,9 +1307,23 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
 }
 
 // ---- adaptive RK45 ----------------------------------------------------------------------------------------------------------------
+// Both modes run ode.hip's grouped kernels: the batch-coupled solve is one controller over all B*C*H*W unknowns, the per-sample solve
+// one controller per sample.  Each mode keeps the partition it was introduced with -- it fixes the summation order of the norms and
+// with it the bits: coupled, one workgroup per 1024 unknowns of the batch, at most 2048 (the elementwise grid of ode.hip); per sample,
+// at most 64, so that a sample's step sequence depends on C*H*W alone, not on the batch size.
 static constexpr int kRk45MaxAttempts = 10000;     // a field that never settles raises instead of spinning (scipy has no such cap)
-static constexpr int kRk45Method = 2;              // graph-cache key of an attempt (beside FC_METHOD_EULER / FC_METHOD_RK4)
+static constexpr int kRk45Method = 2;              // graph-cache keys of a coupled / per-sample attempt (beside FC_METHOD_EULER /
+static constexpr int kRk45PerSampleMethod = 3;     // FC_METHOD_RK4): the two modes' attempts are different graphs
+static constexpr int kRk45CoupledChunks = 2048, kRk45PerSampleChunks = 64;
 
+static Rk45Groups rk45_groups(const fc_unet* u, int B, bool per_sample) {
+    const int m = u->cfg.channels * u->H * u->W;
+    return per_sample ? Rk45Groups{B, 1, m, rk45_chunks(m, kRk45PerSampleChunks)}
+                      : Rk45Groups{1, B, B * m, rk45_chunks(B * m, kRk45CoupledChunks)};
+}
+
+// The controller state, allocated by the first RK45 call (in int_allocs, released with the plan) so handles that never use it keep
+// their footprint; the partial sums fit either mode's partition.
 static int alloc_rk45(fc_unet* u) {
     const size_t nstate = (size_t)u->maxB * u->cfg.channels * u->H * u->W;
     auto get = [&](size_t bytes, void** out) -> int {
@@ -1293,260 +1331,134 @@ static int alloc_rk45(fc_unet* u) {
         u->int_allocs.push_back(*out);
         return FC_OK;
     };
+    const Rk45Groups cg = rk45_groups(u, u->maxB, false), pg = rk45_groups(u, u->maxB, true);
+    const size_t parts = std::max((size_t)cg.G * cg.chunks, (size_t)pg.G * pg.chunks);
     void* p = nullptr;
     FC_TRY(get(nstate * sizeof(double), &p)); u->rk_y = static_cast<double*>(p);
     FC_TRY(get(nstate * sizeof(double), &p)); u->rk_ynew = static_cast<double*>(p);
     for (int j = 0; j < 7; ++j) { FC_TRY(get(nstate * sizeof(float), &p)); u->rk_k.k[j] = static_cast<float*>(p); }
-    FC_TRY(get(2 * (size_t)rk45_parts((int)nstate) * sizeof(double), &p)); u->rk_part = static_cast<double*>(p);
-    FC_TRY(get(sizeof(Rk45State), &p)); u->rk_st = static_cast<Rk45State*>(p);
+    FC_TRY(get(2 * parts * sizeof(double), &p)); u->rk_part = static_cast<double*>(p);
+    FC_TRY(get((size_t)u->maxB * sizeof(Rk45State), &p)); u->rk_st = static_cast<Rk45State*>(p);
+    FC_TRY(get(sizeof(Rk45Status), &p)); u->rk_sum = static_cast<Rk45Status*>(p);
     return FC_OK;
 }
 
-// one attempt of RungeKutta._step_impl: five stages, y_new and f(t + h, y_new), the error norm, the controller, the commit
-static int enqueue_rk45_attempt(fc_unet* u, int B, bool cfg_on, float cfg, float t_scale, bool has_ids, int mask_mode, hipStream_t s) {
-    const int rows = cfg_on ? 2 * B : B, n = B * u->cfg.channels * u->H * u->W;
-    FwdCtx c;   // no conditioning table: each forward takes its time from u->tvec
-    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
-    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
-    c.out = u->v2; c.B = rows;
+// one attempt of RungeKutta._step_impl for every group that still steps: five stages, y_new and f(t + h, y_new), the error norms,
+// the controllers, the commit, the status summary
+static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const FwdCtx& c, int cf, float cfg, float t_scale, hipStream_t s) {
     for (int st = 1; st <= 5; ++st) {
-        FC_TRY(rk45_stage_launch(u->rk_st, st, u->rk_y, u->rk_k, u->v2, n, cfg_on, cfg, u->xs, t_scale, u->tvec, rows, s));
+        FC_TRY(rk45_stage_launch(g, u->rk_st, st, u->rk_y, u->rk_k, u->v2, cf, cfg, u->xs, t_scale, u->tvec, s));
         FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
     }
-    FC_TRY(rk45_finish_launch(u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, n, cfg_on, cfg, u->xs, t_scale, u->tvec, rows, s));
+    FC_TRY(rk45_finish_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, cf, cfg, u->xs, t_scale, u->tvec, s));
     FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
-    FC_TRY(rk45_error_launch(u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, n, cfg_on, cfg, u->rk_part, s));
-    FC_TRY(rk45_control_launch(u->rk_st, u->rk_part, n, s));
-    return rk45_commit_launch(u->rk_st, u->rk_y, u->rk_ynew, u->rk_k.k[0], u->rk_k.k[6], n, s);
+    FC_TRY(rk45_error_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, cf, cfg, u->rk_part, s));
+    FC_TRY(rk45_control_launch(g, u->rk_st, u->rk_part, s));
+    FC_TRY(rk45_commit_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k.k[0], u->rk_k.k[6], s));
+    return rk45_status_launch(g, u->rk_st, u->rk_sum, s);
+}
+
+// fc_unet_integrate_rk45 (per_sample = false) and fc_unet_integrate_rk45_per_sample; `fn` names the entry point in argument errors
+static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_dev, int B, int H, int W, double t0, double t1,
+                          double rtol, double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask,
+                          int mask_is_ones, int* counters, void* stream) {
+    if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, std::string(fn) + ": bad argument");
+    if (!(atol >= 0)) return fail(FC_E_ARG, std::string(fn) + ": `atol` must be positive.");      // validate_tol
+    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, std::string(fn) + ": t0 and t1 must be finite");
+    const double eps100 = 100 * 2.220446049250313e-16;
+    if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
+    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
+    const bool cfg_on = has_ids && cfg_strength != 0.0f;
+    FC_TRY(check_ready(u, cfg_on ? 2 * B : B, H, W));
+    FC_TRY(check_poison(u));
+    const Rk45Groups g = rk45_groups(u, B, per_sample);
+    for (int i = 0; i < g.G; ++i) { counters[3 * i] = 1; counters[3 * i + 1] = counters[3 * i + 2] = 0; }   // nfev, accepted, rejected
+    if (t0 == t1) return FC_OK;                  // scipy: one evaluation, no step, y0 returned
+    u->arena_touched(0);
+    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
+    const int n = B * u->cfg.channels * H * W, cf = cfg_on ? 1 : 0;
+    const size_t nbytes = (size_t)n * sizeof(float);
+    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
+    FC_HIP(hipSetDevice(u->device));
+    if (!u->rk_st) FC_TRY(alloc_rk45(u));
+    if (!u->rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); u->rk_host = static_cast<Rk45Status*>(hp); }
+    if (!u->ev_rk) FC_HIP(hipEventCreateWithFlags(&u->ev_rk, hipEventDisableTiming));
+
+    FC_HIP(hipEventRecord(u->ev_in, caller));
+    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
+    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
+    FC_TRY(meet_enter(u, s));
+
+    // f(t0, y0) and select_initial_step of every group (two forwards, no graph)
+    FwdCtx c = integrator_ctx(u, B, cfg_on, has_ids, mask_mode);
+    c.x = u->xs;   // every forward of the solve reads the stage input the RK45 kernels write
+    FC_TRY(rk45_setup_launch(g, x_dev, u->rk_y, u->xs, u->rk_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, u->tvec, cf, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
+    FC_TRY(rk45_d01_launch(g, u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, cf, cfg_strength, u->rk_part, s));
+    FC_TRY(rk45_h0_launch(g, u->rk_st, u->rk_part, t_scale, u->tvec, cf, s));
+    FC_TRY(rk45_y1_launch(g, u->rk_st, u->rk_y, u->rk_k.k[0], u->xs, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
+    FC_TRY(rk45_d2_launch(g, u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, cf, cfg_strength, u->rk_part, s));
+    FC_TRY(rk45_h1_launch(g, u->rk_st, u->rk_part, s));
+    FC_TRY(rk45_status_launch(g, u->rk_st, u->rk_sum, s));
+    FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
+    // This wait is also the one fc_unet_integrate makes before its first replay: under AMD_DIRECT_DISPATCH=0 a graph submitted from this
+    // thread can overtake the plain launches and copies queued just before it (see there).
+    FC_HIP(hipStreamSynchronize(s));
+
+    const auto key = std::make_tuple(per_sample ? kRk45PerSampleMethod : kRk45Method, B, (int)cfg_on, mask_mode, fbits(cfg_strength), 0u,
+                                     fbits(t_scale), (int)has_ids);
+    auto attempt = [&] { return enqueue_rk45_attempt(u, g, c, cf, cfg_strength, t_scale, s); };
+    while (u->rk_host->unfinished > 0) {
+        if (no_graph()) {
+            FC_TRY(attempt());
+        } else {   // one attempt = one graph: 6 plan runs and 10 small launches, a single chain (no parallel branches)
+            hipGraphExec_t exec = nullptr;
+            FC_TRY(cached_graph(u, key, s, attempt, &exec));
+            FC_HIP(hipGraphLaunch(exec, s));
+        }
+        // the 16-byte summary behind every attempt: one small host wait per six forwards
+        FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
+        FC_HIP(hipEventRecord(u->ev_rk, s));
+        FC_HIP(hipEventSynchronize(u->ev_rk));
+    }
+    std::vector<Rk45State> st(g.G);      // the controller records, once at the end
+    FC_HIP(hipMemcpyAsync(st.data(), u->rk_st, (size_t)g.G * sizeof(Rk45State), hipMemcpyDeviceToHost, s));
+    FC_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < g.G; ++i) { counters[3 * i] = st[i].nfev; counters[3 * i + 1] = st[i].accepted; counters[3 * i + 2] = st[i].rejected; }
+    const int failed = u->rk_host->failed;
+    if (!failed) FC_TRY(rk45_out_launch(u->rk_y, x_dev, n, s));
+    FC_TRY(meet_leave(u, s));
+    FC_HIP(hipEventRecord(u->ev_out, s));
+    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
+    if (!failed) return FC_OK;
+    if (!per_sample) {
+        if (st[0].failed == 1) return fail(FC_E_STATE, "rk45: Required step size is less than spacing between numbers.");
+        return fail(FC_E_STATE, "rk45: no convergence after " + std::to_string(st[0].attempts) + " attempts (t = " +
+                                    std::to_string(st[0].t) + ", h = " + std::to_string(st[0].h_abs) + ")");
+    }
+    std::string msg = "rk45 per sample: " + std::to_string(failed) + " of " + std::to_string(B) + " samples failed;";
+    for (int b = 0; b < B; ++b) {
+        if (st[b].failed == 1) msg += " sample " + std::to_string(b) + ": Required step size is less than spacing between numbers.";
+        else if (st[b].failed) msg += " sample " + std::to_string(b) + ": no convergence after " + std::to_string(st[b].attempts) +
+                                      " attempts (t = " + std::to_string(st[b].t) + ", h = " + std::to_string(st[b].h_abs) + ").";
+    }
+    return fail(FC_E_STATE, msg);
 }
 
 int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
                                       float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
                                       int* counters, void* stream) {
-    if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, "fc_unet_integrate_rk45: bad argument");
-    if (!(atol >= 0)) return fail(FC_E_ARG, "fc_unet_integrate_rk45: `atol` must be positive.");      // validate_tol
-    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, "fc_unet_integrate_rk45: t0 and t1 must be finite");
-    const double eps100 = 100 * 2.220446049250313e-16;
-    if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
-    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
-    const bool cfg_on = has_ids && cfg_strength != 0.0f;
-    const int rows = cfg_on ? 2 * B : B;
-    FC_TRY(check_ready(u, rows, H, W));
-    FC_TRY(check_poison(u));
-    counters[0] = 1; counters[1] = counters[2] = 0;
-    if (t0 == t1) return FC_OK;                  // scipy: one evaluation, no step, y0 returned
-    u->arena_touched(0);
-    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
-    const int n = B * u->cfg.channels * H * W;
-    const size_t nbytes = (size_t)n * sizeof(float);
-    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
-    FC_HIP(hipSetDevice(u->device));
-    if (!u->rk_st) FC_TRY(alloc_rk45(u));
-    if (!u->rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45State), hipHostMallocDefault)); u->rk_host = static_cast<Rk45State*>(hp); }
-    if (!u->ev_rk) FC_HIP(hipEventCreateWithFlags(&u->ev_rk, hipEventDisableTiming));
-
-    FC_HIP(hipEventRecord(u->ev_in, caller));
-    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
-    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
-    FC_TRY(meet_enter(u, s));
-
-    // f(t0, y0) and select_initial_step (two forwards, no graph)
-    FwdCtx c;
-    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
-    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
-    c.out = u->v2; c.B = rows;
-    const int cf = cfg_on ? 1 : 0;
-    FC_TRY(rk45_setup_launch(x_dev, u->rk_y, u->xs, n, u->rk_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, u->tvec, rows, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
-    FC_TRY(rk45_d01_launch(u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, n, cf, cfg_strength, u->rk_part, s));
-    FC_TRY(rk45_h0_launch(u->rk_st, u->rk_part, n, t_scale, u->tvec, rows, s));
-    FC_TRY(rk45_y1_launch(u->rk_st, u->rk_y, u->rk_k.k[0], u->xs, n, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
-    FC_TRY(rk45_d2_launch(u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, n, cf, cfg_strength, u->rk_part, s));
-    FC_TRY(rk45_h1_launch(u->rk_st, u->rk_part, n, s));
-    FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_st, sizeof(Rk45State), hipMemcpyDeviceToHost, s));
-    // This wait is also the one fc_unet_integrate makes before its first replay: under AMD_DIRECT_DISPATCH=0 a graph submitted from this
-    // thread can overtake the plain launches and copies queued just before it (see there).
-    FC_HIP(hipStreamSynchronize(s));
-
-    static const bool no_graph = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
-    const auto key = std::make_tuple(kRk45Method, B, (int)cfg_on, mask_mode, fbits(cfg_strength), 0u, fbits(t_scale), (int)has_ids);
-    int r = FC_OK;
-    while (r == FC_OK && !u->rk_host->done && !u->rk_host->failed) {
-        if (no_graph) {
-            r = enqueue_rk45_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
-            if (r != FC_OK) break;
-        } else {
-            auto it = u->graphs.find(key);
-            if (it == u->graphs.end()) {    // one attempt = one graph: 6 plan runs and 8 small launches, a single chain (no parallel branches)
-                hipGraph_t graph = nullptr;
-                FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                r = enqueue_rk45_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
-                const hipError_t e = hipStreamEndCapture(s, &graph);
-                if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
-                if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-                hipGraphExec_t exec = nullptr;
-                FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                FC_HIP(hipGraphDestroy(graph));
-                it = u->graphs.emplace(key, exec).first;
-            }
-            FC_HIP(hipGraphLaunch(it->second, s));
-        }
-        // the status record behind every attempt: one small host wait per six forwards
-        FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_st, sizeof(Rk45State), hipMemcpyDeviceToHost, s));
-        FC_HIP(hipEventRecord(u->ev_rk, s));
-        FC_HIP(hipEventSynchronize(u->ev_rk));
-    }
-    if (r != FC_OK) return r;
-    const Rk45State st = *u->rk_host;
-    counters[0] = st.nfev; counters[1] = st.accepted; counters[2] = st.rejected;
-    if (st.done) FC_TRY(rk45_out_launch(u->rk_y, x_dev, n, s));
-    FC_TRY(meet_leave(u, s));
-    FC_HIP(hipEventRecord(u->ev_out, s));
-    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
-    if (st.failed == 1) return fail(FC_E_STATE, "rk45: Required step size is less than spacing between numbers.");
-    if (st.failed) return fail(FC_E_STATE, "rk45: no convergence after " + std::to_string(st.attempts) + " attempts (t = " +
-                                               std::to_string(st.t) + ", h = " + std::to_string(st.h_abs) + ")");
-    return FC_OK;
-}
-
-// ---- per-sample adaptive RK45 -----------------------------------------------------------------------------------------------------
-static constexpr int kRk45PerSampleMethod = 3;     // graph-cache key of a per-sample attempt (beside kRk45Method)
-
-static int alloc_rk45_per_sample(fc_unet* u) {
-    const int m = u->cfg.channels * u->H * u->W;
-    auto get = [&](size_t bytes, void** out) -> int {
-        FC_TRY(dev_alloc(out, bytes, "integrator.rk45_per_sample"));
-        u->int_allocs.push_back(*out);
-        return FC_OK;
-    };
-    void* p = nullptr;
-    FC_TRY(get((size_t)u->maxB * sizeof(Rk45State), &p)); u->rkp_st = static_cast<Rk45State*>(p);
-    FC_TRY(get(2 * (size_t)u->maxB * rk45ps_chunks(m) * sizeof(double), &p)); u->rkp_part = static_cast<double*>(p);
-    FC_TRY(get(sizeof(Rk45Status), &p)); u->rkp_sum = static_cast<Rk45Status*>(p);
-    return FC_OK;
-}
-
-// one attempt of every sample that still steps: five stages, y_new and f(t + h, y_new), the error norms, the controllers, the commit,
-// the status summary
-static int enqueue_rk45ps_attempt(fc_unet* u, int B, bool cfg_on, float cfg, float t_scale, bool has_ids, int mask_mode, hipStream_t s) {
-    const int rows = cfg_on ? 2 * B : B, m = u->cfg.channels * u->H * u->W, cf = cfg_on ? 1 : 0;
-    FwdCtx c;   // no conditioning table: each forward takes its per-row time from u->tvec
-    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
-    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
-    c.out = u->v2; c.B = rows;
-    for (int st = 1; st <= 5; ++st) {
-        FC_TRY(rk45ps_stage_launch(u->rkp_st, st, u->rk_y, u->rk_k, u->v2, B, m, cf, cfg, u->xs, t_scale, u->tvec, s));
-        FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
-    }
-    FC_TRY(rk45ps_finish_launch(u->rkp_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, B, m, cf, cfg, u->xs, t_scale, u->tvec, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
-    FC_TRY(rk45ps_error_launch(u->rkp_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, B, m, cf, cfg, u->rkp_part, s));
-    FC_TRY(rk45ps_control_launch(u->rkp_st, u->rkp_part, B, m, s));
-    FC_TRY(rk45ps_commit_launch(u->rkp_st, u->rk_y, u->rk_ynew, u->rk_k.k[0], u->rk_k.k[6], B, m, s));
-    return rk45ps_status_launch(u->rkp_st, B, u->rkp_sum, s);
+    return integrate_rk45(u, false, "fc_unet_integrate_rk45", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength, mask,
+                          mask_is_ones, counters, stream);
 }
 
 int fc_unet_integrate_rk45_per_sample(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
                                       float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
                                       int* counters, void* stream) {
-    if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, "fc_unet_integrate_rk45_per_sample: bad argument");
-    if (!(atol >= 0)) return fail(FC_E_ARG, "fc_unet_integrate_rk45_per_sample: `atol` must be positive.");      // validate_tol
-    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, "fc_unet_integrate_rk45_per_sample: t0 and t1 must be finite");
-    const double eps100 = 100 * 2.220446049250313e-16;
-    if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
-    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
-    const bool cfg_on = has_ids && cfg_strength != 0.0f;
-    const int rows = cfg_on ? 2 * B : B;
-    FC_TRY(check_ready(u, rows, H, W));
-    FC_TRY(check_poison(u));
-    for (int b = 0; b < B; ++b) { counters[3 * b] = 1; counters[3 * b + 1] = counters[3 * b + 2] = 0; }
-    if (t0 == t1) return FC_OK;                  // scipy: one evaluation, no step, y0 returned
-    u->arena_touched(0);
-    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
-    const int m = u->cfg.channels * H * W, n = B * m;
-    const size_t nbytes = (size_t)n * sizeof(float);
-    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
-    FC_HIP(hipSetDevice(u->device));
-    if (!u->rk_st) FC_TRY(alloc_rk45(u));
-    if (!u->rkp_st) FC_TRY(alloc_rk45_per_sample(u));
-    if (!u->rkp_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); u->rkp_host = static_cast<Rk45Status*>(hp); }
-    if (!u->ev_rk) FC_HIP(hipEventCreateWithFlags(&u->ev_rk, hipEventDisableTiming));
-
-    FC_HIP(hipEventRecord(u->ev_in, caller));
-    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
-    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
-    FC_TRY(meet_enter(u, s));
-
-    // f(t0, y0) and select_initial_step of every sample (two forwards, no graph)
-    FwdCtx c;
-    c.x = u->xs; c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
-    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
-    c.out = u->v2; c.B = rows;
-    const int cf = cfg_on ? 1 : 0;
-    FC_TRY(rk45ps_setup_launch(x_dev, u->rk_y, u->xs, B, m, u->rkp_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, u->tvec, cf, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
-    FC_TRY(rk45ps_d01_launch(u->rkp_st, u->rk_y, u->rk_k.k[0], u->v2, B, m, cf, cfg_strength, u->rkp_part, s));
-    FC_TRY(rk45ps_h0_launch(u->rkp_st, u->rkp_part, B, m, t_scale, u->tvec, cf, s));
-    FC_TRY(rk45ps_y1_launch(u->rkp_st, u->rk_y, u->rk_k.k[0], u->xs, B, m, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
-    FC_TRY(rk45ps_d2_launch(u->rkp_st, u->rk_y, u->rk_k.k[0], u->v2, B, m, cf, cfg_strength, u->rkp_part, s));
-    FC_TRY(rk45ps_h1_launch(u->rkp_st, u->rkp_part, B, m, s));
-    FC_TRY(rk45ps_status_launch(u->rkp_st, B, u->rkp_sum, s));
-    FC_HIP(hipMemcpyAsync(u->rkp_host, u->rkp_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
-    // the host wait fc_unet_integrate_rk45 makes before its first replay, for the same reason (AMD_DIRECT_DISPATCH=0)
-    FC_HIP(hipStreamSynchronize(s));
-
-    static const bool no_graph = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
-    const auto key = std::make_tuple(kRk45PerSampleMethod, B, (int)cfg_on, mask_mode, fbits(cfg_strength), 0u, fbits(t_scale), (int)has_ids);
-    int r = FC_OK;
-    while (r == FC_OK && u->rkp_host->unfinished > 0) {
-        if (no_graph) {
-            r = enqueue_rk45ps_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
-            if (r != FC_OK) break;
-        } else {
-            auto it = u->graphs.find(key);
-            if (it == u->graphs.end()) {    // one attempt = one graph: 6 plan runs and 10 small launches, a single chain (no parallel branches)
-                hipGraph_t graph = nullptr;
-                FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                r = enqueue_rk45ps_attempt(u, B, cfg_on, cfg_strength, t_scale, has_ids, mask_mode, s);
-                const hipError_t e = hipStreamEndCapture(s, &graph);
-                if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
-                if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-                hipGraphExec_t exec = nullptr;
-                FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                FC_HIP(hipGraphDestroy(graph));
-                it = u->graphs.emplace(key, exec).first;
-            }
-            FC_HIP(hipGraphLaunch(it->second, s));
-        }
-        // the 16-byte summary behind every attempt: one small host wait per six forwards
-        FC_HIP(hipMemcpyAsync(u->rkp_host, u->rkp_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
-        FC_HIP(hipEventRecord(u->ev_rk, s));
-        FC_HIP(hipEventSynchronize(u->ev_rk));
-    }
-    if (r != FC_OK) return r;
-    std::vector<Rk45State> st(B);      // the per-sample records, once at the end
-    FC_HIP(hipMemcpyAsync(st.data(), u->rkp_st, (size_t)B * sizeof(Rk45State), hipMemcpyDeviceToHost, s));
-    FC_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < B; ++b) { counters[3 * b] = st[b].nfev; counters[3 * b + 1] = st[b].accepted; counters[3 * b + 2] = st[b].rejected; }
-    const bool failed = u->rkp_host->failed > 0;
-    if (!failed) FC_TRY(rk45_out_launch(u->rk_y, x_dev, n, s));
-    FC_TRY(meet_leave(u, s));
-    FC_HIP(hipEventRecord(u->ev_out, s));
-    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
-    if (failed) {
-        std::string msg = "rk45 per sample: " + std::to_string(u->rkp_host->failed) + " of " + std::to_string(B) + " samples failed;";
-        for (int b = 0; b < B; ++b) {
-            if (st[b].failed == 1) msg += " sample " + std::to_string(b) + ": Required step size is less than spacing between numbers.";
-            else if (st[b].failed) msg += " sample " + std::to_string(b) + ": no convergence after " + std::to_string(st[b].attempts) +
-                                          " attempts (t = " + std::to_string(st[b].t) + ", h = " + std::to_string(st[b].h_abs) + ").";
-        }
-        return fail(FC_E_STATE, msg);
-    }
-    return FC_OK;
+    return integrate_rk45(u, true, "fc_unet_integrate_rk45_per_sample", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength,
+                          mask, mask_is_ones, counters, stream);
 }
 
 // ---- debug / test hooks --------------------------------------------------------------------------

@@ -32,19 +32,15 @@ struct fc_unet : fc::ParamStore {
     float* pre_ss = nullptr;                 // the [evaluation][row][S] part of `pre`
     fc::TembArgs temb_proto;                 // weights of the conditioning chain as the plan's own launches use them
     std::map<std::tuple<int, int, int, int, uint32_t, uint32_t, uint32_t, int>, hipGraphExec_t> graphs;
-    // adaptive RK45 (fc_unet_integrate_rk45): allocated by its first call (in int_allocs, released with the plan), so handles that never
-    // use it keep their footprint; the pinned status record and its event live as long as the handle
+    // adaptive RK45 (fc_unet_integrate_rk45 / _per_sample): state, stage derivatives, up to maxB controllers, their partial sums and the
+    // status summary, allocated by the first call (in int_allocs, released with the plan), so handles that never use it keep their
+    // footprint; the pinned status summary and its event live as long as the handle
     double *rk_y = nullptr, *rk_ynew = nullptr, *rk_part = nullptr;
     fc::Rk45K rk_k{};
     fc::Rk45State* rk_st = nullptr;
-    fc::Rk45State* rk_host = nullptr;
+    fc::Rk45Status* rk_sum = nullptr;
+    fc::Rk45Status* rk_host = nullptr;
     hipEvent_t ev_rk = nullptr;
-    // per-sample RK45 (fc_unet_integrate_rk45_per_sample) shares rk_y / rk_ynew / rk_k and adds one controller per reserved row, its
-    // partial sums and the status summary (in int_allocs, allocated by its first call); the pinned summary lives as long as the handle
-    fc::Rk45State* rkp_st = nullptr;
-    double* rkp_part = nullptr;
-    fc::Rk45Status* rkp_sum = nullptr;
-    fc::Rk45Status* rkp_host = nullptr;
 
     // Fused Block tails whose workgroups wait for each other (conv_dev.h) need the device to themselves.  `shared` = the caller said the
     // device is shared with other streams / processes (fc_unet_set_shared): plans are then built without such launches.  A wait that

@@ -114,8 +114,8 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int batch, int heigh
  * counters[3] (host) = { nfev (scipy's solution.nfev; a CFG pair counts once), accepted steps, rejected attempts }.
  * atol < 0 -> FC_E_ARG; rtol below 100 eps is raised to 100 eps.  A step below the spacing of t ("Required step size is less than
  * spacing between numbers.") or an internal cap on attempts -> FC_E_STATE, x_dev untouched.
- * One attempt (6 forwards + 8 small launches) is a captured hipGraph per (B, cfg, mask, class ids) variant; the controller runs on the
- * device and the host reads a status record behind each replay.  Unlike fc_unet_integrate this call is SYNCHRONOUS with respect to
+ * One attempt (6 forwards + 10 small launches) is a captured hipGraph per (B, cfg, mask, class ids) variant; the controller runs on
+ * the device and the host reads a 16-byte status summary behind each replay.  Unlike fc_unet_integrate this call is SYNCHRONOUS with respect to
  * the library stream (it must see when the solve ends): on return the result is queued on `stream` behind the solve.  The extra
  * state (fp64 y / y_new, K0..K6) is allocated by the first call, not by fc_unet_reserve. */
 int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int batch, int height, int width, double t0, double t1, double rtol, double atol,
