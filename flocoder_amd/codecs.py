@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _binding as B
+from ._native import NativeModule, _Node, read_param_table
 from .general import ldcfg
 
 
@@ -62,29 +63,72 @@ _LEGACY = {".query.": ".to_q.", ".key.": ".to_k.", ".value.": ".to_v.", ".proj_a
 
 
 def vae_param_table():
-    """(name, shape, offset) of the native AutoencoderKL parameter table (no GPU needed)."""
-    lib = B.lib()
-    h = C.c_void_p()
-    B.check(lib.fc_vae_create(-1, C.byref(h)))
-    try:
-        out = []
-        for i in range(lib.fc_vae_param_count(h)):
-            name, shape, off = C.c_char_p(), (C.c_int64 * 4)(), C.c_int64()
-            B.check(lib.fc_vae_param_info(h, i, C.byref(name), C.byref(shape), C.byref(off)))
-            out.append((name.value.decode(), tuple(int(s) for s in shape if s), int(off.value)))
-        return out, int(lib.fc_vae_param_numel(h))
-    finally:
-        lib.fc_vae_destroy(h)
-
-
-class _Node(nn.Module):
-    pass
+    """(name, shape, offset) of the native AutoencoderKL parameter table, and its flat numel (no GPU needed)."""
+    return read_param_table("fc_vae", "create")
 
 
 _PRECISIONS = {"fp32": 0, "bf16x3": 1}
 
 
-class SD_VAE_Wrapper(nn.Module):
+class _NativeCodec(NativeModule):
+    """What the two native codecs share: precision, the reserve-then-run body of encode / decode, and the plan tables."""
+
+    def set_precision(self, mode: str = "fp32") -> None:
+        """Arithmetic of the codec's convolutions: "fp32" (default, exact fp32 on the matrix pipe -- what parity tests and the headline use)
+        or "bf16x3" (every operand as bf16 hi + lo, three bf16 MFMAs per product, fp32 accumulation: ~1e-5 relative per layer; an opt-in for
+        callers that decode many images, ``<codec>_set_precision``)."""
+        if mode not in _PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
+        self._precision = mode
+
+    def _on_use(self, handle, device):
+        B.check(self._fn("set_precision")(handle, _PRECISIONS[getattr(self, "_precision", "fp32")]))
+
+    def _need_gpu(self, t):
+        if not t.is_cuda:
+            raise RuntimeError(f"flocoder_amd.{type(self).__name__} runs on MI355X (gfx950) only; there is no CPU path")
+
+    def _run(self, op: str, x, out_shape):
+        """``op`` = "encode" | "decode" of the GPU tensor ``x`` into a new fp32 tensor of ``out_shape``, the plan reserved for x's shape first."""
+        bsz, _, h, w = x.shape
+        x = x.contiguous().float()
+        hnd = self._native(x.device)
+        B.check(self._fn("reserve_" + op)(hnd, bsz, h, w))
+        out = torch.empty(out_shape, device=x.device, dtype=torch.float32)
+        B.check(self._fn(op)(hnd, B.ptr(x), B.ptr(out), bsz, h, w, B.current_stream(x.device)))
+        return out
+
+    def flops_per_sample(self, decode=True) -> float:
+        return float(self._fn("flops_per_sample")(self._handle, int(decode))) if self._handle else 0.0
+
+    def _op_record(self, decode, i):
+        """(kernel family, reference module, FLOPs per sample, HBM bytes per sample, HBM bytes per launch) of launch i of a plan."""
+        raise NotImplementedError
+
+    def _plan_records(self, decode):
+        n = self._fn("plan_launches")(self._handle, int(decode)) if self._handle else 0
+        return [self._op_record(decode, i) for i in range(n)]
+
+    def plan_ops(self, decode=True):
+        """(kernel family, reference module, algorithmic FLOPs per sample) of every launch of the current decode / encode plan."""
+        return [r[:3] for r in self._plan_records(decode)]
+
+    def plan_kernels(self, decode=True):
+        return [k for k, _, _ in self.plan_ops(decode)]
+
+    def profile_ops(self, inp: torch.Tensor, out: torch.Tensor, decode=True, repeats: int = 5):
+        """Per-launch device milliseconds of the decode (or encode) plan for the batch ``inp`` -> ``out`` with each launch's kernel
+        family, algorithmic FLOPs per sample and algorithmic HBM bytes (bench.py's live roofline measurement for the codecs).  Run
+        decode()/encode() at this batch first so the plan exists."""
+        recs = self._plan_records(decode)
+        ms = (C.c_float * max(len(recs), 1))()
+        B.check(self._fn("profile_ops")(self._handle, int(decode), B.ptr(inp.contiguous()), B.ptr(out), inp.shape[0], repeats, ms, len(recs),
+                                        B.current_stream(inp.device)))
+        return [dict(kernel=k, module=m, flops_per_sample=f, ms=float(ms[i]), rows=inp.shape[0], bytes=bp * inp.shape[0] + bf)
+                for i, (k, m, f, bp, bf) in enumerate(recs)]
+
+
+class SD_VAE_Wrapper(_NativeCodec):
     """codecs.py:631-663 over the native AutoencoderKL.  Parameters live under ``self.vae.*`` with the upstream key names, so a
     ``state_dict`` saved from the reference's wrapper loads here unchanged.
 
@@ -93,21 +137,15 @@ class SD_VAE_Wrapper(nn.Module):
     ``diffusion_pytorch_model.safetensors`` (also taken from ``$FLOCODER_SD_VAE_PATH``); ``weights="random"`` draws seeded random
     weights (benchmarks / tests).  Without any of these it raises FileNotFoundError -- it never downloads."""
 
+    _fc = "fc_vae"
+
     def __init__(self, pretrained_model_name="stabilityai/sd-vae-ft-mse", weights=None, seed: int = 0):
         super().__init__()
         self.in_channels = 3
         self.pretrained_model_name = pretrained_model_name
-        self._table, self._flat_numel = vae_param_table()
+        self._read_table()
         self.vae = _Node()
-        for name, shape, _ in self._table:
-            node = self.vae
-            *path, leaf = name.split(".")
-            for part in path:
-                if not hasattr(node, part):
-                    node.add_module(part, _Node())
-                node = getattr(node, part)
-            node.register_parameter(leaf, nn.Parameter(torch.empty(shape, dtype=torch.float32), requires_grad=False))
-        self._handle, self._handle_device, self._synced = None, None, None
+        self._register_table(requires_grad=False)
         if weights is None:
             weights = os.environ.get("FLOCODER_SD_VAE_PATH")
         if weights is None:
@@ -145,55 +183,11 @@ class SD_VAE_Wrapper(nn.Module):
         with torch.no_grad():
             for k, p in own.items():
                 p.copy_(sd[k].reshape(p.shape).to(p.dtype))      # legacy attention weights are [C,C,1,1]
-        self._synced = None
+        self.mark_dirty()
 
-    # ---- native object
-    def mark_dirty(self) -> None:
-        """Re-upload the weights on the next use (for writes that bypass the (data_ptr, _version) key, e.g. ``p.data.copy_``)."""
-        self._synced = None
-
-    def _native(self, device):
-        lib = B.lib()
-        if self._handle is None or self._handle_device != device:
-            self._release()
-            h = C.c_void_p()
-            B.check(lib.fc_vae_create(device.index or 0, C.byref(h)))
-            self._handle, self._handle_device, self._synced = h, device, None
-        B.check(lib.fc_vae_set_precision(self._handle, _PRECISIONS[getattr(self, "_precision", "fp32")]))
-        ver = tuple((p.data_ptr(), p._version) for p in self.vae.parameters())
-        if ver != self._synced:
-            flat = torch.zeros(self._flat_numel, dtype=torch.float32, device=device)
-            sd = dict(self.vae.named_parameters())
-            for name, shape, off in self._table:
-                flat[off:off + math.prod(shape)] = sd[name].detach().reshape(-1).to(device)
-            B.check(lib.fc_vae_load_params(self._handle, flat.data_ptr(), flat.numel(), 1, B.current_stream(device)))
-            torch.cuda.current_stream(device).synchronize()
-            self._synced = ver
-        return self._handle
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            B.lib().fc_vae_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def set_precision(self, mode: str = "fp32") -> None:
-        """Arithmetic of the codec's convolutions: "fp32" (default, exact fp32 on the matrix pipe -- what parity tests and the headline use)
-        or "bf16x3" (every operand as bf16 hi + lo, three bf16 MFMAs per product, fp32 accumulation: ~1e-5 relative per layer; an opt-in for
-        callers that decode many images, ``fc_vae_set_precision``)."""
-        if mode not in _PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
-        self._precision = mode
-
-    @staticmethod
-    def _need_gpu(t):
-        if not t.is_cuda:
-            raise RuntimeError("flocoder_amd.SD_VAE_Wrapper runs on MI355X (gfx950) only; there is no CPU path")
+    @property
+    def _root(self):
+        return self.vae
 
     # ---- codec protocol
     @torch.no_grad()
@@ -203,12 +197,7 @@ class SD_VAE_Wrapper(nn.Module):
         bsz, ch, h, w = x.shape
         if ch != 3:
             raise ValueError("SD-VAE expects 3-channel images")
-        x = x.contiguous().float()
-        hnd = self._native(x.device)
-        B.check(B.lib().fc_vae_reserve_encode(hnd, bsz, h, w))
-        out = torch.empty(bsz, 4, h // 8, w // 8, device=x.device, dtype=torch.float32)
-        B.check(B.lib().fc_vae_encode(hnd, B.ptr(x), B.ptr(out), bsz, h, w, B.current_stream(x.device)))
-        return out
+        return self._run("encode", x, (bsz, 4, h // 8, w // 8))
 
     @torch.no_grad()
     def decode(self, z, orig_size=None, noise_strength=0.0):
@@ -217,12 +206,7 @@ class SD_VAE_Wrapper(nn.Module):
         bsz, ch, h, w = z.shape
         if ch != 4:
             raise ValueError("SD-VAE latents have 4 channels")
-        z = z.contiguous().float()
-        hnd = self._native(z.device)
-        B.check(B.lib().fc_vae_reserve_decode(hnd, bsz, h, w))
-        out = torch.empty(bsz, 3, 8 * h, 8 * w, device=z.device, dtype=torch.float32)
-        B.check(B.lib().fc_vae_decode(hnd, B.ptr(z), B.ptr(out), bsz, h, w, B.current_stream(z.device)))
-        return out
+        return self._run("decode", z, (bsz, 3, 8 * h, 8 * w))
 
     def forward(self, x, noise_strength=0.0, minval=0, get_stats=False):
         """codecs.py:657-663."""
@@ -230,36 +214,12 @@ class SD_VAE_Wrapper(nn.Module):
         recon = self.decode(self.encode(x))
         return (recon, 0.0, {'codebook_mean_dist': 0.0, 'codebook_max_dist': 0.0}) if get_stats else (recon, 0.0)
 
-    def flops_per_sample(self, decode=True) -> float:
-        return float(B.lib().fc_vae_flops_per_sample(self._handle, int(decode))) if self._handle else 0.0
-
-    def plan_ops(self, decode=True):
-        """(kernel family, reference module, algorithmic FLOPs per sample) of every launch of the current decode / encode plan."""
+    def _op_record(self, decode, i):
         lib, h = B.lib(), self._handle
-        out = []
-        for i in range(lib.fc_vae_plan_launches(h, int(decode)) if h else 0):
-            k, m, f = C.c_char_p(), C.c_char_p(), C.c_double()
-            B.check(lib.fc_vae_op_info(h, int(decode), i, C.byref(k), C.byref(m), C.byref(f)))
-            out.append((k.value.decode(), m.value.decode(), f.value))
-        return out
-
-    def plan_kernels(self, decode=True):
-        return [k for k, _, _ in self.plan_ops(decode)]
-
-    def profile_ops(self, inp: torch.Tensor, out: torch.Tensor, decode=True, repeats: int = 5):
-        """Per-launch device milliseconds of the decode (or encode) plan for the batch ``inp`` -> ``out`` (bench.py's live
-        roofline measurement for the codec).  Run decode()/encode() at this batch first so the plan exists."""
-        lib, h = B.lib(), self._handle
-        ops = self.plan_ops(decode)
-        ms = (C.c_float * len(ops))()
-        B.check(lib.fc_vae_profile_ops(h, int(decode), B.ptr(inp.contiguous()), B.ptr(out), inp.shape[0], repeats, ms, len(ops),
-                                       B.current_stream(inp.device)))
-        rows = []
-        for i, (k, m, f) in enumerate(ops):
-            bp, bf = C.c_double(), C.c_double()
-            B.check(lib.fc_vae_op_bytes(h, int(decode), i, C.byref(bp), C.byref(bf)))
-            rows.append(dict(kernel=k, module=m, flops_per_sample=f, ms=float(ms[i]), rows=inp.shape[0], bytes=bp.value * inp.shape[0] + bf.value))
-        return rows
+        k, m, f, bp, bf = C.c_char_p(), C.c_char_p(), C.c_double(), C.c_double(), C.c_double()
+        B.check(lib.fc_vae_op_info(h, int(decode), i, C.byref(k), C.byref(m), C.byref(f)))
+        B.check(lib.fc_vae_op_bytes(h, int(decode), i, C.byref(bp), C.byref(bf)))
+        return k.value.decode(), m.value.decode(), f.value, bp.value, bf.value
 
 
 class _NoiseInjectionParams(nn.Module):
@@ -331,13 +291,15 @@ class ResidualVQ(nn.Module):
         return zq.view(x.shape[-1], flat.shape[0]).t().reshape(x.shape), idx.view(*x.shape[:-1], self.num_quantizers), loss
 
 
-class VQVAE(nn.Module):
+class VQVAE(_NativeCodec):
     """codecs.py:395-574 -- encode / decode on the gfx950 library (``fc_vqvae_*``), NATTEN-less, eval mode.
 
     Parameters carry the reference's state_dict names (``encoder.0.conv1.weight`` ... ``decoder.layers.0.q_proj.weight`` ...), so
     ``load_state_dict(ckpt['model_state_dict'], strict=False)`` takes a reference checkpoint as is.  ``quantize`` / ``forward`` run the
     inference form of ResidualVQ (third party, parity unpinned -- see ``ResidualVQ`` above); ``decode`` with a non-zero
     ``noise_strength`` (training-time NoiseInjection) raises NotImplementedError."""
+
+    _fc, _create = "fc_vqvae", "create_ex"
 
     def __init__(self, in_channels=3, hidden_channels=256, num_downsamples=3, vq_num_embeddings=512, internal_dim=256,
                  codebook_levels=3, vq_embedding_dim=4, commitment_weight=0.25, use_checkpoint=False, no_natten=False,
@@ -355,44 +317,24 @@ class VQVAE(nn.Module):
         self.vq_embedding_dim, self.indices, self.info = vq_embedding_dim, None, None
         self._cfg = (in_channels, hidden_channels, num_downsamples, internal_dim, vq_embedding_dim, int(bool(decoder_nonlocal)), natten_layout)
         self.natten_layout = natten_layout
-        lib = B.lib()
-        h = C.c_void_p()
-        B.check(lib.fc_vqvae_create_ex(*self._cfg, -1, C.byref(h)))
-        try:
-            self._table = []
-            for i in range(lib.fc_vqvae_param_count(h)):
-                name, shape, off = C.c_char_p(), (C.c_int64 * 4)(), C.c_int64()
-                B.check(lib.fc_vqvae_param_info(h, i, C.byref(name), C.byref(shape), C.byref(off)))
-                self._table.append((name.value.decode(), tuple(int(s) for s in shape if s), int(off.value)))
-            self._flat_numel = int(lib.fc_vqvae_param_numel(h))
-        finally:
-            lib.fc_vqvae_destroy(h)
-        for name, shape, _ in self._table:
-            node = self
-            *path, leaf = name.split(".")
-            for part in path:
-                if not hasattr(node, part):
-                    node.add_module(part, _Node())
-                node = getattr(node, part)
-            p = torch.empty(shape, dtype=torch.float32)
-            if leaf == "gamma":
-                p.zero_()                                                 # NATTENBlock's residual gate starts closed (codecs.py:105)
-                node.register_parameter(leaf, nn.Parameter(p, requires_grad=False))
-                continue
-            if name.endswith((".attn.qkv.weight", ".attn.proj.weight")):
-                p.normal_(0.0, 0.02)                                      # codecs.py:108-109
-                node.register_parameter(leaf, nn.Parameter(p, requires_grad=False))
-                continue
-            if leaf == "weight" and len(shape) > 1:                       # nn.Conv2d default init (kaiming_uniform, a=sqrt(5))
-                nn.init.kaiming_uniform_(p, a=math.sqrt(5))
-            elif leaf == "weight":
-                p.fill_(1.0)                                              # GroupNorm
-            else:
-                wname = name[:-4] + "weight"
-                wshape = next(s for n, s, _ in self._table if n == wname)
-                bound = 1.0 / math.sqrt(math.prod(wshape[1:])) if len(wshape) > 1 else 0.0
-                p.uniform_(-bound, bound) if bound else p.zero_()
-            node.register_parameter(leaf, nn.Parameter(p, requires_grad=False))
+        self._read_table()
+        self._register_table(requires_grad=False)
+        with torch.no_grad():
+            for name, shape, _ in self._table:
+                p, leaf = self.get_parameter(name), name.rsplit(".", 1)[1]
+                if leaf == "gamma":
+                    p.zero_()                                             # NATTENBlock's residual gate starts closed (codecs.py:105)
+                elif name.endswith((".attn.qkv.weight", ".attn.proj.weight")):
+                    p.normal_(0.0, 0.02)                                  # codecs.py:108-109
+                elif leaf == "weight" and len(shape) > 1:                 # nn.Conv2d default init (kaiming_uniform, a=sqrt(5))
+                    nn.init.kaiming_uniform_(p, a=math.sqrt(5))
+                elif leaf == "weight":
+                    p.fill_(1.0)                                          # GroupNorm
+                else:
+                    wname = name[:-4] + "weight"
+                    wshape = next(s for n, s, _ in self._table if n == wname)
+                    bound = 1.0 / math.sqrt(math.prod(wshape[1:])) if len(wshape) > 1 else 0.0
+                    p.uniform_(-bound, bound) if bound else p.zero_()
         # NoiseInjection tensors of the reference's Decoder (codecs.py:259,283-300): present in checkpoints, unused at strength 0
         i0 = 1 if decoder_nonlocal else 0
         cur = hidden_channels * 2 ** (num_downsamples - 1)
@@ -408,81 +350,31 @@ class VQVAE(nn.Module):
         self.vq = ResidualVQ(dim=vq_embedding_dim, codebook_size=vq_num_embeddings, num_quantizers=codebook_levels)
         self.register_buffer('codebook_usage', torch.zeros(codebook_levels, vq_num_embeddings))
         self.usage_count = 0
-        self._handle, self._handle_device, self._synced = None, None, None
 
-    def mark_dirty(self) -> None:
-        """Re-upload the weights on the next use (for writes that bypass the (data_ptr, _version) key, e.g. ``p.data.copy_``)."""
-        self._synced = None
-
-    def set_precision(self, mode: str = "fp32") -> None:
-        """"fp32" (default) or "bf16x3" -- see ``SD_VAE_Wrapper.set_precision`` (``fc_vqvae_set_precision``)."""
-        if mode not in _PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
-        self._precision = mode
-
-    def _native(self, device):
-        lib = B.lib()
-        if self._handle is None or self._handle_device != device:
-            self._release()
-            h = C.c_void_p()
-            B.check(lib.fc_vqvae_create_ex(*self._cfg, device.index or 0, C.byref(h)))
-            self._handle, self._handle_device, self._synced = h, device, None
-        B.check(lib.fc_vqvae_set_precision(self._handle, _PRECISIONS[getattr(self, "_precision", "fp32")]))
-        sd = dict(self.named_parameters())
-        ver = tuple((sd[n].data_ptr(), sd[n]._version) for n, _, _ in self._table)
-        if ver != self._synced:
-            flat = torch.zeros(self._flat_numel, dtype=torch.float32, device=device)
-            for name, shape, off in self._table:
-                flat[off:off + math.prod(shape)] = sd[name].detach().reshape(-1).to(device)
-            B.check(lib.fc_vqvae_load_params(self._handle, flat.data_ptr(), flat.numel(), 1, B.current_stream(device)))
-            torch.cuda.current_stream(device).synchronize()
-            self._synced = ver
-        return self._handle
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            B.lib().fc_vqvae_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+    def _create_args(self):
+        return self._cfg
 
     @torch.no_grad()
     def encode(self, x, debug=False):
         """z = self.encoder(x) (codecs.py:492-502): [B,in_channels,H,W] -> [B,vq_embedding_dim,H>>nd,W>>nd], pre-quantisation."""
-        if not x.is_cuda:
-            raise RuntimeError("flocoder_amd.VQVAE runs on MI355X (gfx950) only; there is no CPU path")
+        self._need_gpu(x)
         bsz, ch, h, w = x.shape
         if ch != self.in_channels:
             raise ValueError(f"VQVAE expects {self.in_channels}-channel input, got {ch}")
-        x = x.contiguous().float()
-        hnd = self._native(x.device)
-        B.check(B.lib().fc_vqvae_reserve_encode(hnd, bsz, h, w))
         nd = self.num_downsamples
-        out = torch.empty(bsz, self.vq_embedding_dim, h >> nd, w >> nd, device=x.device, dtype=torch.float32)
-        B.check(B.lib().fc_vqvae_encode(hnd, B.ptr(x), B.ptr(out), bsz, h, w, B.current_stream(x.device)))
-        return out
+        return self._run("encode", x, (bsz, self.vq_embedding_dim, h >> nd, w >> nd))
 
     @torch.no_grad()
     def decode(self, z_q, noise_strength=0.0):
         """self.decoder(z_q, noise_strength) (codecs.py:523-525) at noise_strength 0."""
         if noise_strength:
             raise NotImplementedError("VQVAE.decode: noise_strength != 0 (training-time NoiseInjection) is not built")
-        if not z_q.is_cuda:
-            raise RuntimeError("flocoder_amd.VQVAE runs on MI355X (gfx950) only; there is no CPU path")
+        self._need_gpu(z_q)
         bsz, ch, h, w = z_q.shape
         if ch != self.vq_embedding_dim:
             raise ValueError(f"VQVAE latents have {self.vq_embedding_dim} channels, got {ch}")
-        z = z_q.contiguous().float()
-        hnd = self._native(z.device)
-        B.check(B.lib().fc_vqvae_reserve_decode(hnd, bsz, h, w))
         nd = self.num_downsamples
-        out = torch.empty(bsz, self.in_channels, h << nd, w << nd, device=z.device, dtype=torch.float32)
-        B.check(B.lib().fc_vqvae_decode(hnd, B.ptr(z), B.ptr(out), bsz, h, w, B.current_stream(z.device)))
-        return out
+        return self._run("decode", z_q, (bsz, self.in_channels, h << nd, w << nd))
 
     def quantize(self, z, debug=False):
         """codecs.py:504-521: z [B,C,h,w] -> (z_q [B,C,h,w], commit_loss); the indices of the last call stay in ``self.indices``."""
@@ -511,25 +403,10 @@ class VQVAE(nn.Module):
             return x_recon, commit_loss.mean(), self.calc_distance_stats(z, z_q)
         return x_recon, commit_loss.mean()
 
-    def flops_per_sample(self, decode=True) -> float:
-        return float(B.lib().fc_vqvae_flops_per_sample(self._handle, int(decode))) if self._handle else 0.0
-
-    def profile_ops(self, inp: torch.Tensor, out: torch.Tensor, decode=True, repeats: int = 5):
-        """Per-launch device milliseconds of the decode (or encode) plan for the batch ``inp`` -> ``out`` with each launch's kernel
-        family, algorithmic FLOPs per sample and algorithmic HBM bytes (bench.py's config-5 leg).  Run decode()/encode() at this
-        batch first so the plan exists."""
-        lib, h = B.lib(), self._handle
-        n = lib.fc_vqvae_plan_launches(h, int(decode)) if h else 0
-        ms = (C.c_float * max(n, 1))()
-        B.check(lib.fc_vqvae_profile_ops(h, int(decode), B.ptr(inp.contiguous()), B.ptr(out), inp.shape[0], repeats, ms, n,
-                                         B.current_stream(inp.device)))
-        rows = []
-        for i in range(n):
-            k, m, f, bp, bf = C.c_char_p(), C.c_char_p(), C.c_double(), C.c_double(), C.c_double()
-            B.check(lib.fc_vqvae_op_info(h, int(decode), i, C.byref(k), C.byref(m), C.byref(f), C.byref(bp), C.byref(bf)))
-            rows.append(dict(kernel=k.value.decode(), module=m.value.decode(), flops_per_sample=f.value, ms=float(ms[i]), rows=inp.shape[0],
-                             bytes=bp.value * inp.shape[0] + bf.value))
-        return rows
+    def _op_record(self, decode, i):
+        k, m, f, bp, bf = C.c_char_p(), C.c_char_p(), C.c_double(), C.c_double(), C.c_double()
+        B.check(B.lib().fc_vqvae_op_info(self._handle, int(decode), i, C.byref(k), C.byref(m), C.byref(f), C.byref(bp), C.byref(bf)))
+        return k.value.decode(), m.value.decode(), f.value, bp.value, bf.value
 
 
 def _read_weights(path: str) -> Dict[str, torch.Tensor]:

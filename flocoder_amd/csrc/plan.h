@@ -448,8 +448,10 @@ inline int run_plan(const Plan& pl, const FwdCtx& c, hipStream_t s) {
 }
 
 // Measurement: every launch of `pl` timed alone -- `repeats` back-to-back launches between two HIP events on `s` (ops only read their
-// inputs, so repeating one is idempotent).  ms_out[i] = average milliseconds of op i.  Synchronises.
-inline int profile_plan(const Plan& pl, const FwdCtx& c, int repeats, float* ms_out, int n_out, hipStream_t s) {
+// inputs, so repeating one is idempotent; host launch gaps do not pollute kernels that run longer than a launch takes to issue).
+// ms_out[i] = average milliseconds of op i.  `after_op` (optional) runs behind op i's closing event, outside its timing.  Synchronises.
+inline int profile_plan(const Plan& pl, const FwdCtx& c, int repeats, float* ms_out, int n_out, hipStream_t s,
+                        const std::function<int(int)>& after_op = nullptr) {
     const int n = (int)pl.ops.size();
     if (n_out < n) return fail(FC_E_ARG, "profile_ops: output array too small");
     FC_TRY(run_plan(pl, c, s));   // warm: every buffer holds finite data
@@ -460,6 +462,7 @@ inline int profile_plan(const Plan& pl, const FwdCtx& c, int repeats, float* ms_
         (void)hipEventRecord(ev[2 * i], s);
         for (int r = 0; r < repeats && rc == FC_OK; ++r) rc = pl.ops[i](c, s);
         (void)hipEventRecord(ev[2 * i + 1], s);
+        if (after_op && rc == FC_OK) rc = after_op(i);
     }
     (void)hipStreamSynchronize(s);
     for (int i = 0; i < n; ++i) {

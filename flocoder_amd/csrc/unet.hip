@@ -1043,9 +1043,7 @@ int fc_unet_check(fc_unet* u, void* stream, int synchronize) {
 
 uint64_t fc_unet_arena_serial(const fc_unet* u) { return u ? u->arena_serial : 0; }
 
-// Time every launch of the current plan on its own: each op is enqueued `repeats` times back to back between two
-// events on `stream` (ops are idempotent: they only read their inputs), so host launch gaps do not pollute kernels
-// that run longer than a launch takes to issue.  ms_out[i] = average milliseconds of op i.
+// Time every launch of the current plan on its own (profile_plan).
 static int g_stamp_op = -1;                     // diagnostics: fc_unet_profile_ops runs this plan entry once more with the conv stamps on
 static unsigned long long* g_stamp_op_buf = nullptr;
 int fc_debug_set_stamp_op(int op_index, void* buf_dev) { g_stamp_op = buf_dev ? op_index : -1; g_stamp_op_buf = static_cast<unsigned long long*>(buf_dev); return FC_OK; }
@@ -1055,35 +1053,19 @@ int fc_unet_profile_ops(fc_unet* u, int batch, int repeats, float* ms_out, int n
     FC_TRY(check_ready(u, batch, u->H, u->W));
     const Plan& pl0 = u->plan;
     u->arena_touched(0);
-    const int n = (int)pl0.ops.size();
-    if (n_out < n) return fail(FC_E_ARG, "fc_unet_profile_ops: output array too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     FwdCtx c;
     c.x = u->y; c.x_mod = batch; c.time = u->tvec; c.ids = nullptr; c.ids_mod = batch; c.out = u->v2; c.B = batch;
     FC_HIP(hipMemsetAsync(u->tvec, 0, batch * sizeof(float), s));
-    FC_TRY(run_plan(pl0, c, s));  // warm: every buffer holds finite data
-    std::vector<hipEvent_t> ev(2 * n);
-    for (auto& e : ev) FC_HIP(hipEventCreate(&e));
-    int rc = FC_OK;
-    for (int i = 0; i < n && rc == FC_OK; ++i) {
-        (void)hipEventRecord(ev[2 * i], s);
-        for (int r = 0; r < repeats && rc == FC_OK; ++r) rc = pl0.ops[i](c, s);
-        (void)hipEventRecord(ev[2 * i + 1], s);
-        if (i == g_stamp_op && g_stamp_op_buf && rc == FC_OK) {      // the same launch once more, writing its in-kernel phase stamps
-            conv_set_stamp_buffer(g_stamp_op_buf);
-            rc = pl0.ops[i](c, s);
-            (void)hipStreamSynchronize(s);
-            conv_set_stamp_buffer(nullptr);
-        }
-    }
-    (void)hipStreamSynchronize(s);
-    for (int i = 0; i < n; ++i) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
-        ms_out[i] = ms / repeats;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    return rc;
+    auto stamp = [&](int i) -> int {            // the same launch once more, writing its in-kernel phase stamps
+        if (i != g_stamp_op || !g_stamp_op_buf) return FC_OK;
+        conv_set_stamp_buffer(g_stamp_op_buf);
+        const int rc = pl0.ops[i](c, s);
+        (void)hipStreamSynchronize(s);
+        conv_set_stamp_buffer(nullptr);
+        return rc;
+    };
+    return profile_plan(pl0, c, repeats, ms_out, n_out, s, stamp);
 }
 
 int fc_unet_op_info(const fc_unet* u, int i, const char** kernel, const char** module, double* flops_per_sample) {

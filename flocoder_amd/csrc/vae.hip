@@ -13,17 +13,13 @@
 #include <cstring>
 #include <memory>
 
-#include "plan.h"
+#include "codec.h"
 
 using namespace fc;
 
-struct fc_vae : fc::ParamStore {
-    int device = 0;
+struct fc_vae : fc::Codec {
     int in_ch = 3, latent = 4, lpb = 2, groups = 32;
     std::vector<int> bo{128, 256, 512, 512};
-    fc::Plan enc, dec;
-    int enc_B = 0, enc_H = 0, enc_W = 0, dec_B = 0, dec_h = 0, dec_w = 0;
-    int prec = 0;     // fc_vae_set_precision: arithmetic of the plans built from now on (0 exact fp32, 1 split-bf16)
 };
 
 namespace fc {
@@ -315,31 +311,9 @@ extern "C" {
 
 int fc_vae_create(int device, fc_vae** out) {
     if (!out) return fail(FC_E_ARG, "fc_vae_create: null argument");
-    std::unique_ptr<fc_vae> v(new fc_vae);
-    v->device = device;
-    v->want_b3 = device >= 0;      // the split-bf16 copies of the conv weights (set_precision): +1x the conv weights in HBM
-    FC_TRY(declare_all(v.get()));
-    if (device < 0) { *out = v.release(); return FC_OK; }
-    FC_TRY(fc_check_device(device));
-    FC_HIP(hipSetDevice(device));
-    FC_TRY(conv_init());
-    FC_TRY(v->alloc_device());
-    FC_HIP(hipMemset(v->packed, 0, (size_t)v->packed_numel * sizeof(float)));   // padded bias slots stay zero beyond the copy
-    *out = v.release();
-    return FC_OK;
+    return codec_create(std::unique_ptr<fc_vae>(new fc_vae), device, declare_all, out);
 }
-
-void fc_vae_destroy(fc_vae* v) {
-    if (!v) return;
-    if (v->device >= 0) {
-        (void)hipSetDevice(v->device);
-        (void)hipDeviceSynchronize();
-        v->enc.release();
-        v->dec.release();
-        v->free_device();
-    }
-    delete v;
-}
+void fc_vae_destroy(fc_vae* v) { codec_destroy(v); }
 
 int fc_vae_param_count(const fc_vae* v) { return v ? (int)v->params.size() : 0; }
 int64_t fc_vae_param_numel(const fc_vae* v) { return v ? v->raw_numel : 0; }
@@ -348,108 +322,31 @@ int fc_vae_param_info(const fc_vae* v, int i, const char** name, int64_t shape[4
     return v->info(i, name, shape, offset);
 }
 int fc_vae_load_params(fc_vae* v, const float* flat, int64_t numel, int on_device, void* stream) {
-    if (!v || !flat) return fail(FC_E_ARG, "fc_vae_load_params: null argument");
-    if (v->device < 0) return fail(FC_E_STATE, "vae: created with device < 0 (description only)");
-    FC_HIP(hipSetDevice(v->device));
-    return v->load(flat, numel, on_device, static_cast<hipStream_t>(stream));
+    return codec_load(v, "fc_vae_load_params", flat, numel, on_device, stream);
 }
-
+int fc_vae_set_precision(fc_vae* v, int mode) { return codec_set_precision(v, "fc_vae_set_precision", mode); }
 int fc_vae_reserve_encode(fc_vae* v, int max_batch, int height, int width) {
-    if (!v || max_batch < 1 || v->device < 0) return fail(FC_E_ARG, "fc_vae_reserve_encode: bad argument");
-    if (v->enc.maxB >= max_batch && v->enc.H == height && v->enc.W == width) return FC_OK;
-    FC_HIP(hipSetDevice(v->device));
-    FC_HIP(hipDeviceSynchronize());
-    const int r = build_encoder(v, max_batch, height, width);
-    if (r != FC_OK) v->enc.release();
-    return r;
+    return codec_reserve(v, "fc_vae_reserve_encode", 0, build_encoder, max_batch, height, width);
 }
-int fc_vae_set_precision(fc_vae* v, int mode) {
-    if (!v || (mode != 0 && mode != 1)) return fail(FC_E_ARG, "fc_vae_set_precision: mode is 0 (fp32) or 1 (split-bf16)");
-    if (v->prec == mode) return FC_OK;
-    v->prec = mode;
-    if (v->device >= 0) {          // plans in place were built for the other arithmetic: drop them, the next reserve rebuilds
-        FC_HIP(hipSetDevice(v->device));
-        FC_HIP(hipDeviceSynchronize());
-        v->enc.release(); v->dec.release();
-    }
-    return FC_OK;
-}
-
 int fc_vae_reserve_decode(fc_vae* v, int max_batch, int lat_height, int lat_width) {
-    if (!v || max_batch < 1 || v->device < 0) return fail(FC_E_ARG, "fc_vae_reserve_decode: bad argument");
-    if (v->dec.maxB >= max_batch && v->dec.H == lat_height && v->dec.W == lat_width) return FC_OK;
-    FC_HIP(hipSetDevice(v->device));
-    FC_HIP(hipDeviceSynchronize());
-    const int r = build_decoder(v, max_batch, lat_height, lat_width);
-    if (r != FC_OK) v->dec.release();
-    return r;
-}
-
-static int run_vae(const fc_vae* v, bool decode, const float* in, float* out, int B, int H, int W, void* stream) {
-    if (!v || !in || !out || B < 1) return fail(FC_E_ARG, "vae: null argument");
-    const Plan& pl = decode ? v->dec : v->enc;
-    if (!v->loaded) return fail(FC_E_STATE, "vae: weights not loaded (fc_vae_load_params)");
-    if (pl.maxB < B || pl.H != H || pl.W != W) return fail(FC_E_STATE, "vae: no plan for this shape; call fc_vae_reserve_* first");
-    FwdCtx c;
-    c.x = in; c.x_mod = B; c.out = out; c.B = B;
-    return run_plan(pl, c, static_cast<hipStream_t>(stream));
+    return codec_reserve(v, "fc_vae_reserve_decode", 1, build_decoder, max_batch, lat_height, lat_width);
 }
 int fc_vae_encode(fc_vae* v, const float* x_dev, float* mean_out_dev, int batch, int height, int width, void* stream) {
-    return run_vae(v, false, x_dev, mean_out_dev, batch, height, width, stream);
+    return codec_run(v, "fc_vae_encode", 0, x_dev, mean_out_dev, batch, height, width, stream);
 }
 int fc_vae_decode(fc_vae* v, const float* z_dev, float* x_out_dev, int batch, int lat_height, int lat_width, void* stream) {
-    return run_vae(v, true, z_dev, x_out_dev, batch, lat_height, lat_width, stream);
+    return codec_run(v, "fc_vae_decode", 1, z_dev, x_out_dev, batch, lat_height, lat_width, stream);
 }
-double fc_vae_flops_per_sample(const fc_vae* v, int decode) { return v ? (decode ? v->dec.flops : v->enc.flops) : 0.0; }
-int fc_vae_plan_launches(const fc_vae* v, int decode) { return v ? (int)(decode ? v->dec.ops.size() : v->enc.ops.size()) : 0; }
-
+double fc_vae_flops_per_sample(const fc_vae* v, int decode) { return v ? v->plan(decode).flops : 0.0; }
+int fc_vae_plan_launches(const fc_vae* v, int decode) { return v ? (int)v->plan(decode).ops.size() : 0; }
 int fc_vae_op_info(const fc_vae* v, int decode, int i, const char** kernel, const char** module, double* flops_per_sample) {
-    if (!v) return fail(FC_E_ARG, "fc_vae_op_info: null handle");
-    const Plan& pl = decode ? v->dec : v->enc;
-    if (i < 0 || i >= (int)pl.ops.size()) return fail(FC_E_ARG, "fc_vae_op_info: index out of range");
-    if (kernel) *kernel = pl.op_kernel[i].c_str();
-    if (module) *module = pl.op_what[i].c_str();
-    if (flops_per_sample) *flops_per_sample = pl.op_flops[i];
-    return FC_OK;
+    return codec_op_info(v, "fc_vae_op_info", decode, i, kernel, module, flops_per_sample, nullptr, nullptr);
 }
-
 int fc_vae_op_bytes(const fc_vae* v, int decode, int i, double* bytes_per_sample, double* bytes_per_launch) {
-    if (!v) return fail(FC_E_ARG, "fc_vae_op_bytes: null handle");
-    const Plan& pl = decode ? v->dec : v->enc;
-    if (i < 0 || i >= (int)pl.ops.size()) return fail(FC_E_ARG, "fc_vae_op_bytes: index out of range");
-    if (bytes_per_sample) *bytes_per_sample = pl.op_bytes_ps[i];
-    if (bytes_per_launch) *bytes_per_launch = pl.op_bytes_fixed[i];
-    return FC_OK;
+    return codec_op_info(v, "fc_vae_op_bytes", decode, i, nullptr, nullptr, nullptr, bytes_per_sample, bytes_per_launch);
 }
-
-// Measurement hook: every launch of the encode / decode plan timed alone (`repeats` back-to-back launches between two events).
-// in_dev / out_dev: valid input and output tensors for `batch` samples at the plan's shape.  Synchronises.
 int fc_vae_profile_ops(fc_vae* v, int decode, const float* in_dev, float* out_dev, int batch, int repeats, float* ms_out, int n_out, void* stream) {
-    if (!v || !in_dev || !out_dev || !ms_out || repeats < 1) return fail(FC_E_ARG, "fc_vae_profile_ops: bad argument");
-    const Plan& pl = decode ? v->dec : v->enc;
-    const int n = (int)pl.ops.size();
-    if (pl.maxB < batch || n == 0) return fail(FC_E_STATE, "vae: reserve the plan first");
-    if (n_out < n) return fail(FC_E_ARG, "fc_vae_profile_ops: output array too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    FwdCtx c;
-    c.x = in_dev; c.x_mod = batch; c.out = out_dev; c.B = batch;
-    FC_TRY(run_plan(pl, c, s));
-    std::vector<hipEvent_t> ev(2 * n);
-    for (auto& e : ev) FC_HIP(hipEventCreate(&e));
-    int rc = FC_OK;
-    for (int i = 0; i < n && rc == FC_OK; ++i) {
-        (void)hipEventRecord(ev[2 * i], s);
-        for (int r = 0; r < repeats && rc == FC_OK; ++r) rc = pl.ops[i](c, s);
-        (void)hipEventRecord(ev[2 * i + 1], s);
-    }
-    (void)hipStreamSynchronize(s);
-    for (int i = 0; i < n; ++i) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
-        ms_out[i] = ms / repeats;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    return rc;
+    return codec_profile(v, "fc_vae_profile_ops", decode, in_dev, out_dev, batch, repeats, ms_out, n_out, stream);
 }
 
 }  // extern "C"

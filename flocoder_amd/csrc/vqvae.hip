@@ -8,17 +8,14 @@
 // conv3x3 -> SiLU (epilogue) -> PixelShuffle(2) (one re-layout pass).
 #include <memory>
 
-#include "plan.h"
+#include "codec.h"
 
 using namespace fc;
 
 struct fc_vqvae_config_s { int in_channels, hidden_channels, num_downsamples, internal_dim, vq_embedding_dim, decoder_nonlocal, natten = 0; };
 
-struct fc_vqvae : fc::ParamStore {
-    int device = 0;
+struct fc_vqvae : fc::Codec {
     fc_vqvae_config_s c{3, 256, 3, 256, 4, 1, 0};
-    fc::Plan enc, dec;
-    int prec = 0;     // fc_vqvae_set_precision
 };
 
 namespace fc {
@@ -367,28 +364,14 @@ int fc_vqvae_create_ex(int in_channels, int hidden_channels, int num_downsamples
     if (natten_layout && ((hidden_channels % 32) || (internal_dim % 32)))
         return fail(FC_E_SHAPE, "vqvae: NATTEN blocks need widths that are multiples of 32 (8 heads, head_dim a multiple of 4)");
     std::unique_ptr<fc_vqvae> v(new fc_vqvae);
-    v->device = device;
     v->c = {in_channels, hidden_channels, num_downsamples, internal_dim, vq_embedding_dim, decoder_nonlocal, natten_layout};
-    v->want_b3 = device >= 0;      // the split-bf16 copies of the conv weights (set_precision): +1x the conv weights in HBM
-    FC_TRY(declare_all(v.get()));
-    if (device < 0) { *out = v.release(); return FC_OK; }
-    FC_TRY(fc_check_device(device));
-    FC_HIP(hipSetDevice(device));
-    FC_TRY(conv_init());
-    FC_TRY(v->alloc_device());
-    FC_HIP(hipMemset(v->packed, 0, (size_t)(v->packed_numel ? v->packed_numel : 4) * sizeof(float)));
-    *out = v.release();
-    return FC_OK;
+    return codec_create(std::move(v), device, declare_all, out);
 }
 int fc_vqvae_create(int in_channels, int hidden_channels, int num_downsamples, int internal_dim, int vq_embedding_dim, int decoder_nonlocal,
                     int device, fc_vqvae** out) {
     return fc_vqvae_create_ex(in_channels, hidden_channels, num_downsamples, internal_dim, vq_embedding_dim, decoder_nonlocal, 0, device, out);
 }
-void fc_vqvae_destroy(fc_vqvae* v) {
-    if (!v) return;
-    if (v->device >= 0) { (void)hipSetDevice(v->device); (void)hipDeviceSynchronize(); v->enc.release(); v->dec.release(); v->free_device(); }
-    delete v;
-}
+void fc_vqvae_destroy(fc_vqvae* v) { codec_destroy(v); }
 int fc_vqvae_param_count(const fc_vqvae* v) { return v ? (int)v->params.size() : 0; }
 int64_t fc_vqvae_param_numel(const fc_vqvae* v) { return v ? v->raw_numel : 0; }
 int fc_vqvae_param_info(const fc_vqvae* v, int i, const char** name, int64_t shape[4], int64_t* offset) {
@@ -396,79 +379,29 @@ int fc_vqvae_param_info(const fc_vqvae* v, int i, const char** name, int64_t sha
     return v->info(i, name, shape, offset);
 }
 int fc_vqvae_load_params(fc_vqvae* v, const float* flat, int64_t numel, int on_device, void* stream) {
-    if (!v || !flat || v->device < 0) return fail(FC_E_ARG, "fc_vqvae_load_params: bad argument");
-    FC_HIP(hipSetDevice(v->device));
-    return v->load(flat, numel, on_device, static_cast<hipStream_t>(stream));
+    return codec_load(v, "fc_vqvae_load_params", flat, numel, on_device, stream);
 }
-int fc_vqvae_set_precision(fc_vqvae* v, int mode) {
-    if (!v || (mode != 0 && mode != 1)) return fail(FC_E_ARG, "fc_vqvae_set_precision: mode is 0 (fp32) or 1 (split-bf16)");
-    if (v->prec == mode) return FC_OK;
-    v->prec = mode;
-    if (v->device >= 0) {
-        FC_HIP(hipSetDevice(v->device));
-        FC_HIP(hipDeviceSynchronize());
-        v->enc.release(); v->dec.release();
-    }
-    return FC_OK;
-}
-
+int fc_vqvae_set_precision(fc_vqvae* v, int mode) { return codec_set_precision(v, "fc_vqvae_set_precision", mode); }
 int fc_vqvae_reserve_encode(fc_vqvae* v, int max_batch, int height, int width) {
-    if (!v || max_batch < 1 || v->device < 0) return fail(FC_E_ARG, "fc_vqvae_reserve_encode: bad argument");
-    if (v->enc.maxB >= max_batch && v->enc.H == height && v->enc.W == width) return FC_OK;
-    FC_HIP(hipSetDevice(v->device));
-    FC_HIP(hipDeviceSynchronize());
-    const int r = build_encoder(v, max_batch, height, width);
-    if (r != FC_OK) v->enc.release();
-    return r;
+    return codec_reserve(v, "fc_vqvae_reserve_encode", 0, build_encoder, max_batch, height, width);
 }
 int fc_vqvae_reserve_decode(fc_vqvae* v, int max_batch, int lat_height, int lat_width) {
-    if (!v || max_batch < 1 || v->device < 0) return fail(FC_E_ARG, "fc_vqvae_reserve_decode: bad argument");
-    if (v->dec.maxB >= max_batch && v->dec.H == lat_height && v->dec.W == lat_width) return FC_OK;
-    FC_HIP(hipSetDevice(v->device));
-    FC_HIP(hipDeviceSynchronize());
-    const int r = build_decoder(v, max_batch, lat_height, lat_width);
-    if (r != FC_OK) v->dec.release();
-    return r;
-}
-static int run_vq(const fc_vqvae* v, bool decode, const float* in, float* out, int B, int H, int W, void* stream) {
-    if (!v || !in || !out || B < 1) return fail(FC_E_ARG, "vqvae: null argument");
-    if (!v->loaded) return fail(FC_E_STATE, "vqvae: weights not loaded (fc_vqvae_load_params)");
-    const Plan& pl = decode ? v->dec : v->enc;
-    if (pl.maxB < B || pl.H != H || pl.W != W) return fail(FC_E_STATE, "vqvae: no plan for this shape; call fc_vqvae_reserve_* first");
-    FwdCtx c;
-    c.x = in; c.x_mod = B; c.out = out; c.B = B;
-    return run_plan(pl, c, static_cast<hipStream_t>(stream));
+    return codec_reserve(v, "fc_vqvae_reserve_decode", 1, build_decoder, max_batch, lat_height, lat_width);
 }
 int fc_vqvae_encode(fc_vqvae* v, const float* x_dev, float* z_out_dev, int batch, int height, int width, void* stream) {
-    return run_vq(v, false, x_dev, z_out_dev, batch, height, width, stream);
+    return codec_run(v, "fc_vqvae_encode", 0, x_dev, z_out_dev, batch, height, width, stream);
 }
 int fc_vqvae_decode(fc_vqvae* v, const float* z_dev, float* x_out_dev, int batch, int lat_height, int lat_width, void* stream) {
-    return run_vq(v, true, z_dev, x_out_dev, batch, lat_height, lat_width, stream);
+    return codec_run(v, "fc_vqvae_decode", 1, z_dev, x_out_dev, batch, lat_height, lat_width, stream);
 }
-double fc_vqvae_flops_per_sample(const fc_vqvae* v, int decode) { return v ? (decode ? v->dec.flops : v->enc.flops) : 0.0; }
-int fc_vqvae_plan_launches(const fc_vqvae* v, int decode) { return v ? (int)(decode ? v->dec.ops.size() : v->enc.ops.size()) : 0; }
-
+double fc_vqvae_flops_per_sample(const fc_vqvae* v, int decode) { return v ? v->plan(decode).flops : 0.0; }
+int fc_vqvae_plan_launches(const fc_vqvae* v, int decode) { return v ? (int)v->plan(decode).ops.size() : 0; }
 int fc_vqvae_op_info(const fc_vqvae* v, int decode, int i, const char** kernel, const char** module, double* flops_per_sample,
                      double* bytes_per_sample, double* bytes_per_launch) {
-    if (!v) return fail(FC_E_ARG, "fc_vqvae_op_info: null handle");
-    const Plan& pl = decode ? v->dec : v->enc;
-    if (i < 0 || i >= (int)pl.ops.size()) return fail(FC_E_ARG, "fc_vqvae_op_info: index out of range");
-    if (kernel) *kernel = pl.op_kernel[i].c_str();
-    if (module) *module = pl.op_what[i].c_str();
-    if (flops_per_sample) *flops_per_sample = pl.op_flops[i];
-    if (bytes_per_sample) *bytes_per_sample = pl.op_bytes_ps[i];
-    if (bytes_per_launch) *bytes_per_launch = pl.op_bytes_fixed[i];
-    return FC_OK;
+    return codec_op_info(v, "fc_vqvae_op_info", decode, i, kernel, module, flops_per_sample, bytes_per_sample, bytes_per_launch);
 }
-
 int fc_vqvae_profile_ops(fc_vqvae* v, int decode, const float* in_dev, float* out_dev, int batch, int repeats, float* ms_out, int n_out, void* stream) {
-    if (!v || !in_dev || !out_dev || !ms_out || repeats < 1) return fail(FC_E_ARG, "fc_vqvae_profile_ops: bad argument");
-    const Plan& pl = decode ? v->dec : v->enc;
-    if (pl.maxB < batch || pl.ops.empty()) return fail(FC_E_STATE, "vqvae: reserve the plan first");
-    if (!v->loaded) return fail(FC_E_STATE, "vqvae: weights not loaded (fc_vqvae_load_params)");
-    FwdCtx c;
-    c.x = in_dev; c.x_mod = batch; c.out = out_dev; c.B = batch;
-    return profile_plan(pl, c, repeats, ms_out, n_out, static_cast<hipStream_t>(stream));
+    return codec_profile(v, "fc_vqvae_profile_ops", decode, in_dev, out_dev, batch, repeats, ms_out, n_out, stream);
 }
 
 }  // extern "C"

@@ -3,17 +3,13 @@
 file are data preparation and stay out of scope."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 from torch import nn
 
 from . import _binding as B
-
-
-class _Node(nn.Module):
-    pass
+from ._native import NativeModule
 
 
 class _MaskEncoderFunction(torch.autograd.Function):
@@ -35,74 +31,27 @@ class _MaskEncoderFunction(torch.autograd.Function):
         return (None, None, *[flat[off:off + math.prod(shape)].view(shape).clone() for _, shape, off in model._table])
 
 
-class MaskEncoder(nn.Module):
+class MaskEncoder(NativeModule):
     """inpainting.py:182-245 with the defaults the flow trainer uses (output_channels=4, shrink_fac=4, mode='pool', sigmoid):
     pixel mask [B,1,H,W] -> [B,4,H/16,W/16]; channel 0 is the 16x average-pooled raw mask, channels 1-3 are learned.
     Same ``state_dict`` keys as upstream (``layers.0.conv1.weight`` ...) and the same default init / RNG order."""
+
+    _fc = "fc_mask_encoder"
 
     def __init__(self, output_channels=4, shrink_fac=4, mode='pool', final_act=torch.sigmoid):
         super().__init__()
         if output_channels != 4 or shrink_fac != 4 or mode != 'pool':
             raise NotImplementedError("only the configuration train_flow.py instantiates (MaskEncoder()) is built")
-        lib = B.lib()
-        h = C.c_void_p()
-        B.check(lib.fc_mask_encoder_create(-1, C.byref(h)))
-        self._table = []
-        for i in range(lib.fc_mask_encoder_param_count(h)):
-            name, shape, off = C.c_char_p(), (C.c_int64 * 4)(), C.c_int64()
-            B.check(lib.fc_mask_encoder_param_info(h, i, C.byref(name), C.byref(shape), C.byref(off)))
-            self._table.append((name.value.decode(), tuple(int(s) for s in shape if s), int(off.value)))
-        self._flat_numel = int(lib.fc_mask_encoder_param_numel(h))
-        lib.fc_mask_encoder_destroy(h)
-        for name, shape, _ in self._table:                     # registration order = upstream construction order
-            node = self
-            *path, leaf = name.split(".")
-            for part in path:
-                if not hasattr(node, part):
-                    node.add_module(part, _Node())
-                node = getattr(node, part)
-            p = nn.Parameter(torch.empty(shape))
-            with torch.no_grad():                              # nn.Conv2d defaults, weight then bias
+        self._read_table()
+        self._register_table()                                 # registration order = upstream construction order
+        with torch.no_grad():                                  # nn.Conv2d defaults, weight then bias
+            for name, shape, _ in self._table:
+                p = self.get_parameter(name)
                 if len(shape) > 1:
                     nn.init.kaiming_uniform_(p, a=math.sqrt(5))
                     fan_in = math.prod(shape[1:])
                 else:
                     p.uniform_(-1.0 / math.sqrt(fan_in), 1.0 / math.sqrt(fan_in))
-            node.register_parameter(leaf, p)
-        self._handle, self._handle_device, self._synced = None, None, None
-
-    def mark_dirty(self) -> None:
-        """Re-upload the weights on the next use (for writes that bypass the (data_ptr, _version) key, e.g. ``p.data.copy_``)."""
-        self._synced = None
-
-    def _native(self, device):
-        lib = B.lib()
-        if self._handle is None or self._handle_device != device:
-            self._release()
-            h = C.c_void_p()
-            B.check(lib.fc_mask_encoder_create(device.index or 0, C.byref(h)))
-            self._handle, self._handle_device, self._synced = h, device, None
-        ver = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if ver != self._synced:
-            flat = torch.zeros(self._flat_numel, device=device)
-            sd = dict(self.named_parameters())
-            for name, shape, off in self._table:
-                flat[off:off + math.prod(shape)] = sd[name].detach().reshape(-1).to(device)
-            B.check(lib.fc_mask_encoder_load_params(self._handle, flat.data_ptr(), flat.numel(), 1, B.current_stream(device)))
-            torch.cuda.current_stream(device).synchronize()
-            self._synced = ver
-        return self._handle
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            B.lib().fc_mask_encoder_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def forward(self, mask_pixels):
         if not mask_pixels.is_cuda:

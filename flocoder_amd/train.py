@@ -464,7 +464,7 @@ class FlowTrainer:
         B.check(lib.fc_adam_ema_step(self.me_params.data_ptr(), self.me_grads.data_ptr(), self.me_m.data_ptr(), self.me_v.data_ptr(),
                                      self.me_ema.data_ptr(), nm, self._me_scal.data_ptr() + 8, self.me_lr, b1, b2, self.eps, self.me_step,
                                      self.ema_decay, 1, st))
-        me._synced = None                                     # its flat vector changed under the views: re-upload on next use
+        me.mark_dirty()                                       # its flat vector changed under the views: re-upload on next use
         return loss
 
     def train_batch(self, batch, epoch=None, cfg_drop: float = 0.1, mask_encoder=None, blank_latents=None):

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import _binding as B
+from ._native import NativeModule, read_param_table
 
 # construction order of the reference's Unet.__init__ (unet.py:185-286); state_dict order differs (ups before mid)
 _CTOR_ORDER = ["init_conv", "time_mlp", "class_cond_mlp", "mask_fusion_conv", "down_mask_fusions", "up_mask_fusions",
@@ -36,22 +37,7 @@ def _make_config(dim, dim_mults, channels, groups, n_classes, mask_cond) -> B.fc
 
 def param_table(cfg: B.fc_unet_config) -> List[Tuple[str, Tuple[int, ...], int]]:
     """(name, shape, offset into the flat padded vector) as the library lays parameters out.  Needs no GPU."""
-    lib = B.lib()
-    h = C.c_void_p()
-    B.check(lib.fc_unet_create(C.byref(cfg), -1, C.byref(h)))
-    try:
-        out = []
-        for i in range(lib.fc_unet_param_count(h)):
-            name, shape, off = C.c_char_p(), (C.c_int64 * 4)(), C.c_int64()
-            B.check(lib.fc_unet_param_info(h, i, C.byref(name), C.byref(shape), C.byref(off)))
-            out.append((name.value.decode(), tuple(int(s) for s in shape if s), int(off.value)))
-        return out
-    finally:
-        lib.fc_unet_destroy(h)
-
-
-class _Node(nn.Module):
-    """Parameter container; attribute names reproduce the reference's module tree."""
+    return read_param_table("fc_unet", "create", C.byref(cfg))[0]
 
 
 class _UnetFunction(torch.autograd.Function):
@@ -89,7 +75,9 @@ class _UnetFunction(torch.autograd.Function):
         return (None, dx, None, None, dm, *grads)
 
 
-class Unet(nn.Module):
+class Unet(NativeModule):
+    _fc = "fc_unet"
+
     def __init__(self, dim, dim_mults=(1, 2, 4, 8), channels=3, resnet_block_groups=4, n_classes=10, mask_cond=False,
                  use_checkpoint=False):
         super().__init__()
@@ -99,38 +87,21 @@ class Unet(nn.Module):
         self.class_condition = n_classes > 0
         self.dim, self.dim_mults = int(dim), tuple(int(m) for m in dim_mults)
         self._cfg = _make_config(dim, self.dim_mults, channels, resnet_block_groups, n_classes, mask_cond)
-        table = param_table(self._cfg)
-        self._table = table
-        self._flat_numel = max(off + int(math.prod(shape)) for _, shape, off in table)
-        self._flat_numel = (self._flat_numel + 3) // 4 * 4
+        self._read_table()
 
         # registration in state_dict order, initialisation in constructor order (RNG parity with the reference)
         by_top: Dict[str, List[Tuple[str, Tuple[int, ...]]]] = {}
-        for name, shape, _ in table:
+        for name, shape, _ in self._table:
             by_top.setdefault(name.split(".")[0], []).append((name, shape))
-        for top in _STATE_ORDER:
-            for name, shape in by_top.get(top, []):
-                self._register(name, shape)
+        self._register_table([e for top in _STATE_ORDER for e in by_top.get(top, [])])
         with torch.no_grad():
             for top in _CTOR_ORDER:
                 for name, shape in by_top.get(top, []):
                     self._init(name, self.get_parameter(name), by_top[top])
 
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_device: Optional[torch.device] = None
-        self._synced_version = None
         self._shared = None          # None: decide per call (see _device_is_shared); True / False: set_shared_device
 
     # ------------------------------------------------------------------ parameters
-    def _register(self, name: str, shape: Tuple[int, ...]) -> None:
-        node = self
-        *path, leaf = name.split(".")
-        for part in path:
-            if not hasattr(node, part):
-                node.add_module(part, _Node())
-            node = getattr(node, part)
-        node.register_parameter(leaf, nn.Parameter(torch.empty(shape, dtype=torch.float32)))
-
     @staticmethod
     def _init(name: str, p: nn.Parameter, siblings) -> None:
         """nn.Conv2d / nn.Linear / nn.Embedding / nn.GroupNorm defaults, drawn in the reference's order."""
@@ -150,52 +121,18 @@ class Unet(nn.Module):
         else:
             nn.init.kaiming_uniform_(p, a=math.sqrt(5))         # Conv2d / Linear weight
 
-    def _flat_params(self, device) -> torch.Tensor:
-        flat = torch.zeros(self._flat_numel, dtype=torch.float32, device=device)
-        sd = dict(self.named_parameters())
-        for name, shape, off in self._table:
-            flat[off:off + math.prod(shape)] = sd[name].detach().reshape(-1)
-        return flat
-
-    def _version(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
-    def mark_dirty(self) -> None:
-        """Force a re-upload of the parameters on the next use.  Needed after writes the (data_ptr, _version) key cannot see:
-        ``param.data.copy_(...)`` changes neither (the reference's EMA swaps weights that way, train_flow.py:56-71)."""
-        self._synced_version = None
-
     # ------------------------------------------------------------------ native object
-    def _native(self, device: torch.device):
-        lib = B.lib()
-        if self._handle is None or self._handle_device != device:
-            self._release()
-            h = C.c_void_p()
-            B.check(lib.fc_unet_create(C.byref(self._cfg), device.index or 0, C.byref(h)))
-            self._handle, self._handle_device, self._synced_version = h, device, None
-            half = self.dim // 2    # frequency table exactly as torch computes it (unet.py:26-27)
-            fr = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1))).contiguous()
-            B.check(lib.fc_unet_set_time_freqs(h, fr.numpy().ctypes.data_as(C.POINTER(C.c_float)), half))
-        B.check(lib.fc_unet_set_shared(self._handle, int(self._device_is_shared(device))))
-        B.check(lib.fc_unet_set_grad_buckets(self._handle, int(getattr(self, "_grad_buckets", False))))
-        ver = self._version()
-        if ver != self._synced_version:
-            flat = self._flat_params(device)
-            B.check(lib.fc_unet_load_params(self._handle, flat.data_ptr(), flat.numel(), 1, B.current_stream(device)))
-            torch.cuda.current_stream(device).synchronize()      # `flat` dies when this frame returns
-            self._synced_version = ver
-        return self._handle
+    def _create_args(self):
+        return (C.byref(self._cfg),)
 
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            B.lib().fc_unet_destroy(self._handle)
-            self._handle = None
+    def _on_create(self, handle):
+        half = self.dim // 2    # frequency table exactly as torch computes it (unet.py:26-27)
+        fr = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1))).contiguous()
+        B.check(B.lib().fc_unet_set_time_freqs(handle, fr.numpy().ctypes.data_as(C.POINTER(C.c_float)), half))
 
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+    def _on_use(self, handle, device):
+        B.check(B.lib().fc_unet_set_shared(handle, int(self._device_is_shared(device))))
+        B.check(B.lib().fc_unet_set_grad_buckets(handle, int(getattr(self, "_grad_buckets", False))))
 
     def arena_serial(self) -> int:
         """Counter of writes to the library's activation arena (fc_unet_arena_serial)."""
@@ -400,7 +337,7 @@ class Unet(nn.Module):
         flat = self._flat
         hnd = self._native(flat.device) if self._handle is None else self._handle
         B.check(B.lib().fc_unet_load_params(hnd, flat.data_ptr(), flat.numel(), 1, B.current_stream(flat.device)))
-        self._synced_version = self._version()
+        self._synced = self._weights_version()
 
     # ------------------------------------------------------------------ integrators (used by flocoder_amd.sampling)
     def integrate(self, method: str, x: torch.Tensor, ts: torch.Tensor, *, dt_euler: float = 0.0, t_scale: float = 999.0,

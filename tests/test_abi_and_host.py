@@ -82,6 +82,39 @@ def test_param_table_needs_no_gpu_and_is_16_byte_aligned():
     assert "downs.2.3.1.weight" in names and "ups.3.3.weight" in names and "mid_attn.fn.fn.to_out.bias" in names
 
 
+def test_native_models_take_flat_size_from_the_library_and_key_uploads_on_their_root():
+    """All four native models: the flat vector has ``<fc>_param_numel`` floats (for the U-Net also the padded end of its table), and
+    the (data_ptr, _version) key behind the re-upload covers exactly the root's parameters (the VQVAE's: its table, without the
+    NoiseInjection tensors the library never reads) and sees an in-place update."""
+    import math
+    from flocoder_amd import _binding as B
+    from flocoder_amd.codecs import SD_VAE_Wrapper, VQVAE
+    from flocoder_amd.inpainting import MaskEncoder
+    from flocoder_amd.unet import Unet
+    lib = B.lib()
+    torch.manual_seed(0)
+    unet = Unet(dim=32, dim_mults=(1, 2, 4, 8), channels=4, n_classes=102)
+    assert unet._flat_numel == (max(off + math.prod(s) for _, s, off in unet._table) + 3) // 4 * 4
+    vq = VQVAE(in_channels=1, hidden_channels=32, num_downsamples=4, internal_dim=32, vq_embedding_dim=4)
+    for m in (unet, SD_VAE_Wrapper(weights="random"), vq, MaskEncoder()):
+        h = C.c_void_p()
+        B.check(getattr(lib, f"{m._fc}_{m._create}")(*m._create_args(), -1, C.byref(h)))
+        try:
+            assert m._flat_numel == getattr(lib, f"{m._fc}_param_numel")(h)
+        finally:
+            getattr(lib, f"{m._fc}_destroy")(h)
+        keyed = {id(p) for p in m._table_params()}
+        assert len(keyed) == len(m._table)
+        if m is vq:
+            assert keyed == {id(vq.get_parameter(n)) for n, _, _ in vq._table} and keyed < {id(p) for p in vq.parameters()}
+        else:
+            assert keyed == {id(p) for p in m._root.parameters()} and len(keyed) == len(list(m.parameters()))
+        v0 = m._weights_version()
+        with torch.no_grad():
+            m._table_params()[-1].add_(1.0)
+        assert m._weights_version() != v0
+
+
 def test_time_grids_match_reference_bitwise():
     from flocoder_amd import sampling as S
     g = load_golden("g4_timegrids")

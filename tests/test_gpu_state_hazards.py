@@ -75,6 +75,26 @@ def test_data_copy_needs_mark_dirty_and_gets_it_from_the_codecs_too():
         p.data.mul_(1.05)
     w.mark_dirty()
     assert rel_l2(w.decode(z), y0) > 1e-3
+    from flocoder_amd.codecs import VQVAE
+    torch.manual_seed(4)
+    q = VQVAE(in_channels=1, hidden_channels=32, num_downsamples=4, internal_dim=32, vq_embedding_dim=4).eval().to(DEV)
+    img = torch.randn(1, 1, 64, 64, device=DEV)
+    e0 = q.encode(img).clone()
+    for p in q.parameters():
+        p.data.mul_(1.05)
+    q.mark_dirty()
+    assert rel_l2(q.encode(img), e0) > 1e-3
+    from flocoder_amd.inpainting import MaskEncoder
+    torch.manual_seed(5)
+    me = MaskEncoder().eval().to(DEV)
+    mask = (torch.rand(2, 1, 64, 64, device=DEV) > 0.5).float()
+    with torch.no_grad():
+        m0 = me(mask).clone()
+        for p in me.parameters():
+            p.data.mul_(1.25)
+        me.mark_dirty()
+        m1 = me(mask)
+    assert torch.equal(m1[:, 0], m0[:, 0]) and rel_l2(m1[:, 1:], m0[:, 1:]) > 1e-3       # channel 0 is the pooled mask itself
 
 
 def _free_port():
