@@ -699,6 +699,15 @@ int fc_unet_grad_buckets(const fc_unet* u, int64_t* split_offset) {
     return u->bwd.maxB > 0 ? (u->bwd_split_op >= 0 ? 2 : 1) : 0;
 }
 
+int fc_unet_backward_launches(const fc_unet* u) { return u ? (int)u->bwd.ops.size() : 0; }
+
+int fc_unet_backward_op_info(const fc_unet* u, int i, const char** kernel, const char** module) {
+    if (!u || i < 0 || i >= (int)u->bwd.ops.size()) return fail(FC_E_ARG, "fc_unet_backward_op_info: index out of range");
+    if (kernel) *kernel = u->bwd.op_kernel[i].c_str();
+    if (module) *module = u->bwd.op_what[i].c_str();
+    return FC_OK;
+}
+
 int fc_unet_backward_parts(fc_unet* u, const float* x, const float* time, const int64_t* ids, const float* mask, int mask_is_ones,
                            const float* d_out, float* grads, int64_t numel, float* dx_out, float* dmask_out, int B, int H, int W,
                            int first_part, int last_part, void* stream) {

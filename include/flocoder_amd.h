@@ -242,6 +242,10 @@ int fc_unet_backward_parts(fc_unet* u, const float* x_dev, const float* time_dev
 int fc_unet_set_grad_buckets(fc_unet* u, int on);
 /* Number of gradient buckets of the current backward plan (0 none, 1, 2) and the flat offset where the early bucket starts. */
 int fc_unet_grad_buckets(const fc_unet* u, int64_t* split_offset);
+/* Test hooks: number of entries of the current backward plan (0 before fc_unet_train_reserve), and entry i's kernel family and the
+ * reference module it serves -- fc_unet_plan_launches / fc_unet_op_info for the backward plan. */
+int fc_unet_backward_launches(const fc_unet* u);
+int fc_unet_backward_op_info(const fc_unet* u, int i, const char** kernel, const char** module);
 /* The backward reads the activations the last training forward left in the handle's single arena.  Every call that writes the arena
  * (fc_unet_forward, fc_unet_integrate, fc_unet_profile_ops, a re-plan by fc_unet_reserve) moves this counter; a caller that keeps
  * several forwards in flight (autograd with two micro-batches, gradient accumulation) compares the value it saw after ITS forward
