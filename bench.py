@@ -2,21 +2,24 @@
 """Headline benchmark: latent samples/sec of the 64-step Euler sampler on SD-VAE-shaped latents (4x32x32),
 flowers_sd U-Net (dim=32, dim_mults [1,2,4,8], n_classes=102), batch 64 per GPU  (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: starts its N rank processes itself)
+    python bench.py --gpus N --steps K --warmup W [--full]          (N > 1: starts its N rank processes itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is ONE pass of the hot path over one batch: noise -> 64 Euler steps (64 U-Net evaluations) -> final latents,
 inputs already resident in HBM.  Weak scaling: every rank integrates its own 64-sample shard, weights are broadcast
 once from rank 0 over RCCL before the timed region, there is no per-step communication.  Rank 0 prints ONE JSON line.
 
-Objects in the line besides the contract's fields:
+A plain run does only what the headline needs: set up, warm up, time the K steps, check the device's error words, write
+--dump-outputs DIR if given (`dump_outputs` in the line: the arrays written there, see dump_outputs below), print the line.
+Everything else runs only with --full (--no-roofline, --no-secondary and --cpu-baseline then leave out single parts of it) and
+adds these objects to the line:
+  parity        rows 0..3 of the last timed step against the CPU oracle's trajectories (non-zero exit beyond the gate)
   roofline      the dominant kernel (largest share of device time) of the U-Net forward priced against the exact-fp32 MFMA peak;
                 its per-launch duration is measured live by HIP events on the launching stream (fc_unet_profile_ops)
   cpu_baseline  the CPU oracle (oracle/flow_oracle.py + oracle/sdvae_oracle.py, a port of the reference's PyTorch path) timed on this
                 box's host cores on BASELINE config 1 (B=4, 16-step Euler), rank 0 at N=1 only
   secondary     the other BASELINE numbers on the same box: Euler with CFG, "100-step" RK4 with CFG at config 3's per-GPU share,
                 SD-VAE decode (its own roofline entry) / encode, decoded images/s  (N=1: all; N>1: the RK4 share only)
-  dump_outputs  with --dump-outputs DIR: the arrays written there (see dump_outputs below)
 """
 from __future__ import annotations
 
@@ -619,15 +622,55 @@ def launch_ranks(n: int) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
+def full_legs(args, model, line, rank, world, device):
+    """--full: the measurements beside the headline, after its steps and into its line -- the RK4 share (every rank), then on rank 0
+    the roofline, the secondary legs (N=1, in a child process) and the CPU baseline (N=1)."""
+    sec = {}
+    if not args.no_secondary:
+        _phase("rk4 share")
+        sec["rk4_100_cfg"] = rk4_share(model, rank, world, device)         # every rank takes part (max over ranks)
+    if rank == 0:
+        if not args.no_roofline:
+            _phase("roofline (per-launch timing)")
+            line["roofline"] = roofline(model, BATCH)
+        if world == 1 and not args.no_secondary:
+            # the secondary legs (codecs, two trajectories in flight, training steps, config 5) run in a process of their own: they are
+            # informative, a failure in one of them must not cost the headline line above
+            _phase("secondary legs (child process)")
+            r = None
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--secondary-only"], capture_output=True, text=True, timeout=900)
+                sys.stderr.write(r.stderr[-4000:])
+                lines = r.stdout.strip().splitlines()
+                if lines:
+                    sec.update(json.loads(lines[-1]))
+                if r.returncode != 0 or not lines:      # the child died (a fault, a kill): say so, with what it last wrote
+                    sec["secondary_error"] = f"secondary child process exited with code {r.returncode}; stderr tail: {r.stderr[-600:]!r}"
+            except Exception as e:      # noqa: BLE001
+                sec["secondary_error"] = repr(e)[:300] + (f"; child stderr tail: {r.stderr[-400:]!r}" if r is not None else "")
+            if "secondary_error" in sec:
+                sec["secondary_failed"] = sec.get("secondary_failed", 0) + 1
+        if sec:
+            line["secondary"] = sec
+            line["secondary_failed"] = int(sec.get("secondary_failed", 0))
+        mode = "none" if args.no_cpu_baseline else args.cpu_baseline
+        if world == 1 and mode != "none":
+            _phase("cpu baseline")
+            line["cpu_baseline"] = cpu_baseline(model, mode)
+            line["speedup_vs_cpu_baseline"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--cpu-baseline", choices=("full", "quick", "none"), default="full")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, also check the last timed step against the CPU oracle and "
+                    "measure the roofline, the secondary legs and the CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--cpu-baseline", choices=("full", "quick", "none"), default="full", help="with --full: how the CPU baseline is measured")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary legs")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output arrays to DIR/<name>.npy (float32)")
     ap.add_argument("--secondary-only", action="store_true", help="(internal) run the one-GPU secondary legs and print their JSON: the main run "
                     "starts this in a child process, so that nothing in them can cost the headline line")
@@ -709,8 +752,11 @@ def main():
     assert torch.isfinite(out).all()
     model.check_errors()                             # (every euler_sampler call above checked already: Unet.integrate(check=True))
     dumped = dump_outputs(args.dump_outputs, out, world) if args.dump_outputs else None
-    last_noise, last_ids = variants[(calls["n"] - 1) % len(variants)]
-    parity = headline_parity(model, out, last_noise, last_ids) if rank == 0 else None     # the timed configuration's own output against the CPU oracle
+    parity = None
+    if args.full and rank == 0:
+        _phase("parity against the CPU oracle")
+        last_noise, last_ids = variants[(calls["n"] - 1) % len(variants)]
+        parity = headline_parity(model, out, last_noise, last_ids)      # the timed configuration's own output against the CPU oracle
     assert model.fused_tail_errors() == 0, "a fused Block tail timed out waiting for its sample group: results invalid"
 
     line = {
@@ -744,39 +790,9 @@ def main():
         comm["per_rank_samples_per_s"] = per_rank          # value = global batch x steps / the SLOWEST rank's time; these are each rank's own
         comm["per_step_collectives"] = 0                   # the sampling path has none: one weight broadcast before the loop
         line["comm"] = comm
-    sec = {}
-    _phase("rk4 share")
-    if not args.no_secondary:
-        sec["rk4_100_cfg"] = rk4_share(model, rank, world, device)         # every rank takes part (max over ranks)
+    if args.full:
+        full_legs(args, model, line, rank, world, device)
     if rank == 0:
-        if not args.no_roofline:
-            _phase("roofline (per-launch timing)")
-            line["roofline"] = roofline(model, BATCH)
-        if world == 1 and not args.no_secondary:
-            # the secondary legs (codecs, two trajectories in flight, training steps, config 5) run in a process of their own: they are
-            # informative, a failure in one of them must not cost the headline line above
-            _phase("secondary legs (child process)")
-            r = None
-            try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--secondary-only"], capture_output=True, text=True, timeout=900)
-                sys.stderr.write(r.stderr[-4000:])
-                lines = r.stdout.strip().splitlines()
-                if lines:
-                    sec.update(json.loads(lines[-1]))
-                if r.returncode != 0 or not lines:      # the child died (a fault, a kill): say so, with what it last wrote
-                    sec["secondary_error"] = f"secondary child process exited with code {r.returncode}; stderr tail: {r.stderr[-600:]!r}"
-            except Exception as e:      # noqa: BLE001
-                sec["secondary_error"] = repr(e)[:300] + (f"; child stderr tail: {r.stderr[-400:]!r}" if r is not None else "")
-            if "secondary_error" in sec:
-                sec["secondary_failed"] = sec.get("secondary_failed", 0) + 1
-        if sec:
-            line["secondary"] = sec
-            line["secondary_failed"] = int(sec.get("secondary_failed", 0))
-        mode = "none" if args.no_cpu_baseline else args.cpu_baseline
-        if world == 1 and mode != "none":
-            _phase("cpu baseline")
-            line["cpu_baseline"] = cpu_baseline(model, mode)
-            line["speedup_vs_cpu_baseline"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.barrier()

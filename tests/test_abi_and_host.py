@@ -150,3 +150,11 @@ def test_bench_refuses_a_run_without_timed_steps():
     for args in (["--steps", "0"], ["--steps", "2", "--warmup", "-1"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=300)
         assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, (args, r.returncode, r.stderr[-500:])
+
+
+def test_bench_takes_full_as_an_option():
+    """`--full` (everything beyond the headline) is one of bench.py's options: with it the same usage check still runs first."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, (r.returncode, r.stderr[-500:])

@@ -7,6 +7,7 @@
   (d) "100-step" RK4 (99 intervals, 396 evaluations) with CFG 3.0 on the dim-32 model: error growth over BASELINE config 3's length;
   (e) decode_latents with chunk_size < batch (sampling.py:169-183);
   (f) bench.py --dump-outputs: the arrays it writes are the last timed step's latents, and the line counts the steps it was given.
+  (g) a plain bench.py run (no --full) prints the headline fields and none of the measurements that --full adds.
 
 Tolerances: single forward rel-L2 <= 2e-5; trajectories <= 2e-4 (64 evaluations) / 1e-3 (396 evaluations with CFG); decoded images
 <= 1e-3 (north_star).  The SD-VAE oracle is PARITY UNPINNED (diffusers + weights absent): those cases are GPU <-> own restatement."""
@@ -178,3 +179,17 @@ def test_f_bench_dumps_the_last_timed_step(tmp_path):
     sd = {n: v.detach() for n, v in bench.build_model("cpu").state_dict().items()}
     ref, _ = fo.euler_sampler(sd, noise.roll(k, 0)[:1], bench.N_EULER, ids.roll(k, 0)[:1])
     assert rel_l2(torch.from_numpy(lat[:1]), ref) < 2e-4
+
+
+@pytest.mark.skipif(os.environ.get("FLOCODER_AMD_IN_CHILD_SUITE") == "1", reason="already inside the child suite")
+def test_g_plain_bench_times_the_headline_only():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full (a child process, as it is run): exit 0, one line with the headline's
+    fields, and no oracle parity, roofline, secondary legs or CPU baseline -- those run only with --full."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-1500:])
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["unit"] == "samples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    for key in ("parity", "parity_rel_l2", "roofline", "secondary", "secondary_failed", "cpu_baseline", "speedup_vs_cpu_baseline"):
+        assert key not in line, key

@@ -10,7 +10,7 @@ for r in $(seq 1 $ROUNDS); do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    env $v timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary --no-roofline --steps 10 --warmup 3 > $OUT/ab_${i}_$r.json 2> $OUT/ab_${i}_$r.err
+    env $v timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --no-roofline --steps 10 --warmup 3 > $OUT/ab_${i}_$r.json 2> $OUT/ab_${i}_$r.err
     rc=$?
     if [ $rc -ne 0 ]; then
       echo "variant $i [$v] failed in round $r with exit status $rc"
