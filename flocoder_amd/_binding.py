@@ -45,6 +45,8 @@ SIGNATURES = {
     "fc_unet_integrate_rk45": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _f, _vp, _i, _pi, _vp]),
     "fc_unet_integrate_rk45_per_sample": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _f, _vp, _i,
                                               _pi, _vp]),
+    "fc_unet_integrate_rk45_dense": (_i, [_vp, _i, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _f, _vp, _i,
+                                         C.POINTER(C.c_double), _i, _vp, _pi, _vp]),
     "fc_unet_chains": (_i, [_vp, _pi]),
     "fc_unet_plan_launches": (_i, [_vp]),
     "fc_unet_flops_per_sample": (C.c_double, [_vp]),

@@ -279,11 +279,17 @@ int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float
 
 // ---- adaptive RK45 (ode.hip): scipy's solve_ivp(method="RK45") with the controller on the device ----------------------------
 // Controller state and status record of one solve (fp64 as scipy; `failed`: 1 step size below spacing, 2 attempt cap).
+// `t_old`: where the last accepted step began (scipy's solver.t_old; `t` is where it ended).  Dense output: `ev_cursor` counts the
+// requested times this controller has served, and [ev_first, ev_end) are the ones the last accepted step serves.
 struct Rk45State {
-    double t, t_new, t_bound, dir, h, h_abs, rtol, atol, h0, d1, err;
-    int nfev, accepted, rejected, attempts, done, failed, step_rejected, accepted_last, max_attempts, pad;
+    double t, t_new, t_bound, dir, h, h_abs, rtol, atol, h0, d1, err, t_old;
+    int nfev, accepted, rejected, attempts, done, failed, step_rejected, accepted_last, max_attempts, ev_cursor, ev_first, ev_end;
 };
 struct Rk45K { float* k[7]; };             // stage derivatives K0..K6 (fp32, CFG-blended)
+// The dense-output request of one call (solve_ivp's t_eval), in device memory so that a replayed attempt serves any times and any
+// destination: this header, then `n_eval` fp64 times in the same buffer.  `frames` is [n_eval][G*m] fp32.
+struct Rk45Eval { float* frames; int n_eval, pad; };
+__host__ __device__ inline const double* rk45_eval_times(const Rk45Eval* ev) { return reinterpret_cast<const double*>(ev + 1); }
 struct Rk45Status { int unfinished, failed, pad0, pad1; };   // groups still stepping / failed: what the host reads behind an attempt
 // Controller groups of one solve: st[G] holds one controller per group, group g owns the m unknowns of rows g*spg .. g*spg + spg - 1
 // (with CFG also their unguided twins G*spg + row).  Batch-coupled: G = 1, spg = B; per sample: G = B, spg = 1.  The elementwise and
@@ -301,15 +307,19 @@ int rk45_y1_launch(const Rk45Groups& g, const Rk45State* st, const double* y, co
 int rk45_d2_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, const float* v2, int cfg_on, float cfg,
                    double* part, hipStream_t s);
 int rk45_h1_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s);
-// one attempt: stages 1..5 (K[s-1] = blend(v2), xs = y + h sum A K), finish (K5, y_new), error partials (K6), controllers, commit,
-// status summary
+// one attempt: stages 1..5 (K[s-1] = blend(v2), xs = y + h sum A K), finish (K5, y_new), error partials (K6), controllers, [dense
+// output,] commit, status summary
 int rk45_stage_launch(const Rk45Groups& g, const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int cfg_on,
                       float cfg, float* xs, float t_scale, float* tvec, hipStream_t s);
 int rk45_finish_launch(const Rk45Groups& g, const Rk45State* st, const double* y, double* y_new, Rk45K kk, const float* v2, int cfg_on,
                        float cfg, float* xs, float t_scale, float* tvec, hipStream_t s);
 int rk45_error_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2,
                       int cfg_on, float cfg, double* part, hipStream_t s);
-int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s);
+// `ev` (may be null): the controller of an accepted step also records the range of requested times that step serves
+int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45Eval* ev, hipStream_t s);
+// dense output, between control and commit: frames[j] = float32(y + h Q p(x_j)) for every j in the range an accepted step serves
+// (scipy's RkDenseOutput, from y and K0..K6 of that step)
+int rk45_dense_launch(const Rk45Groups& g, const Rk45State* st, const Rk45Eval* ev, const double* y, Rk45K kk, hipStream_t s);
 int rk45_commit_launch(const Rk45Groups& g, const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6,
                        hipStream_t s);
 int rk45_status_launch(const Rk45Groups& g, const Rk45State* st, Rk45Status* out, hipStream_t s);

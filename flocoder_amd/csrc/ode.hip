@@ -159,6 +159,10 @@ int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float
 // sums ([G][chunks][2]) in a fixed order.  `chunks` fixes the summation order and with it the bits of the norms (the host picks it).
 // A group that has finished or failed keeps h = 0: its rows are still evaluated (at float32(y), t), its state, counters and K stay
 // as they are.
+//
+// Dense output (solve_ivp's t_eval, Rk45Eval): the step sequence is untouched.  The controller of an accepted step records which
+// requested times fall into it, and rk45_dense -- between the decision and the commit, while y and K0..K6 of the step still stand --
+// writes the step's quartic interpolant (RkDenseOutput) at those times into the caller's frames.
 
 __constant__ double c_rk45_C[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
 __constant__ double c_rk45_A[6][5] = {
@@ -472,6 +476,18 @@ __global__ void __launch_bounds__(256) rk45_error_kernel(const Rk45State* st, co
     if (threadIdx.x == 0) group_part(part, g)[0] = r;
 }
 
+// solve_ivp's t_eval bookkeeping behind an accepted step that ended at st->t: the not-yet-served requested times with
+// dir (te - t) <= 0 ("the value in t_eval equal to t will be included": searchsorted side='right', 'left' on the reversed array when
+// integrating backwards).  Only this thread moves the cursor; rk45_dense reads the finished record in the next launch.
+__device__ __forceinline__ void rk45_eval_range(Rk45State* st, const Rk45Eval* ev) {
+    const double* te = rk45_eval_times(ev);
+    const int n_eval = ev->n_eval;
+    int end = st->ev_cursor;
+    st->ev_first = end;
+    while (end < n_eval && st->dir * (te[end] - st->t) <= 0) ++end;
+    st->ev_end = st->ev_cursor = end;
+}
+
 // Accept / reject on the error norm `en` (RungeKutta._step_impl), the next attempt, the status record
 __device__ __forceinline__ void rk45_decide(Rk45State* st, double en) {
     const double expo = -1.0 / (4 + 1);
@@ -483,6 +499,7 @@ __device__ __forceinline__ void rk45_decide(Rk45State* st, double en) {
         double factor = en == 0 ? 10.0 : py_min(10.0, 0.9 * pow(en, expo));
         if (st->step_rejected) factor = py_min(1.0, factor);
         st->h_abs = h_abs * factor;
+        st->t_old = st->t;
         st->t = st->t_new;
         st->accepted += 1;
         st->accepted_last = 1;
@@ -498,8 +515,9 @@ __device__ __forceinline__ void rk45_decide(Rk45State* st, double en) {
     }
 }
 
-// one workgroup per group: its error norm and decision; a group that no longer steps only clears accepted_last
-__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int chunks, int m) {
+// one workgroup per group: its error norm and decision, and with a dense-output request (`ev`) the requested times an accepted step
+// serves; a group that no longer steps only clears accepted_last
+__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int chunks, int m, const Rk45Eval* ev) {
     __shared__ double red[256];
     const int g = blockIdx.x;
     Rk45State* sg = st + g;
@@ -510,7 +528,54 @@ __global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const 
     const double s = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
     if (threadIdx.x != 0) return;
     rk45_decide(sg, sqrt(s) / sqrt((double)m));
+    if (ev && sg->accepted_last) rk45_eval_range(sg, ev);
     rk45_freeze(sg);
+}
+
+// scipy's RK45.P: the quartic interpolant of a step is y_old + h (Q p), Q = K^T P, p = (x, x^2, x^3, x^4), x = (t - t_old) / h
+__constant__ double c_rk45_P[7][4] = {
+    {1, -8048581381.0 / 2820520608, 8663915743.0 / 2820520608, -12715105075.0 / 11282082432},
+    {0, 0, 0, 0},
+    {0, 131558114200.0 / 32700410799, -68118460800.0 / 10900136933, 87487479700.0 / 32700410799},
+    {0, -1754552775.0 / 470086768, 14199869525.0 / 1410260304, -10690763975.0 / 1880347072},
+    {0, 127303824393.0 / 49829197408, -318862633887.0 / 49829197408, 701980252875.0 / 199316789632},
+    {0, -282668133.0 / 205662961, 2019193451.0 / 616988883, -1453857185.0 / 822651844},
+    {0, 40617522.0 / 29380423, -110615467.0 / 29380423, 69997945.0 / 29380423}};
+
+// Dense output of the step just accepted (RkDenseOutput._call_impl), before the commit overwrites y and K0: for every requested time
+// j in the range the controller recorded, frames[j] = float32(y + h (Q p_j)) over this group's unknowns.  All fp64 with the fp32 K_s
+// widened exactly, sums left to right; Q is formed once per element and serves every j of the step.  Elementwise: the bits do not
+// depend on `chunks`.  (Row 1 of P is zero; K1 is read all the same so that a non-finite K1 spreads as it does in scipy.)
+__global__ void __launch_bounds__(256) rk45_dense_kernel(const Rk45State* st, const Rk45Eval* ev, const double* y, Rk45K kk, int m) {
+    const int g = blockIdx.y, base = g * m;
+    if (!st[g].accepted_last) return;
+    const int first = st[g].ev_first, end = st[g].ev_end;
+    if (first >= end) return;
+    const double t_old = st[g].t_old, h = st[g].t - t_old;
+    const double* te = rk45_eval_times(ev);
+    float* frames = ev->frames;
+    const size_t n = (size_t)gridDim.y * m;
+    for (int jj = 4 * (blockIdx.x * 256 + threadIdx.x); jj < m; jj += 4 * gridDim.x * 256) {
+        const int i = base + jj;
+        double q[4][4], kv[4];
+#pragma unroll
+        for (int s = 0; s < 7; ++s) {
+            f4_to(*reinterpret_cast<const float4*>(kk.k[s] + i), kv);
+            for (int c = 0; c < 4; ++c) {
+                const double pc = c_rk45_P[s][c];
+                for (int l = 0; l < 4; ++l) q[c][l] = s == 0 ? kv[l] * pc : q[c][l] + kv[l] * pc;
+            }
+        }
+        double yv[4];
+        load_y4(y, i, yv);
+        for (int j = first; j < end; ++j) {
+            const double x = (te[j] - t_old) / h;
+            const double p1 = x * x, p2 = p1 * x, p3 = p2 * x;          // cumprod([x, x, x, x])
+            double o[4];
+            for (int l = 0; l < 4; ++l) o[l] = yv[l] + h * (q[0][l] * x + q[1][l] * p1 + q[2][l] * p2 + q[3][l] * p3);
+            *reinterpret_cast<float4*>(frames + (size_t)j * n + i) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+        }
+    }
 }
 
 // on acceptance: y <- y_new, K0 <- K6 (FSAL)
@@ -600,8 +665,12 @@ int rk45_error_launch(const Rk45Groups& g, const Rk45State* st, const double* y,
                       int cfg_on, float cfg, double* part, hipStream_t s) {
     RK45_LAUNCH(rk45_error_kernel, RK45_GRID, st, y, y_new, kk, v2, g.m, cfg_on, cfg, part);
 }
-int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s) {
-    RK45_LAUNCH(rk45_control_kernel, dim3(g.G), st, part, g.chunks, g.m);
+int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45Eval* ev, hipStream_t s) {
+    RK45_LAUNCH(rk45_control_kernel, dim3(g.G), st, part, g.chunks, g.m, ev);
+}
+int rk45_dense_launch(const Rk45Groups& g, const Rk45State* st, const Rk45Eval* ev, const double* y, Rk45K kk, hipStream_t s) {
+    if (!ev) return fail(FC_E_ARG, "rk45: dense output without a request record");
+    RK45_LAUNCH(rk45_dense_kernel, RK45_GRID, st, ev, y, kk, g.m);
 }
 int rk45_commit_launch(const Rk45Groups& g, const Rk45State* st, double* y, const double* y_new, float* k0, const float* k6,
                        hipStream_t s) {

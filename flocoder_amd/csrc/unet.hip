@@ -927,6 +927,7 @@ void fc_unet_destroy(fc_unet* u) {
     (void)hipDeviceSynchronize();
     free_plan(u);
     if (u->ts_dev) dev_free(u->ts_dev);
+    if (u->rk_ev) dev_free(u->rk_ev);
     if (u->pre) dev_free(u->pre);
     u->free_device();
     if (u->freqs) (void)hipFree(u->freqs);
@@ -1326,8 +1327,9 @@ static int alloc_rk45(fc_unet* u) {
 }
 
 // one attempt of RungeKutta._step_impl for every group that still steps: five stages, y_new and f(t + h, y_new), the error norms,
-// the controllers, the commit, the status summary
-static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const FwdCtx& c, int cf, float cfg, float t_scale, hipStream_t s) {
+// the controllers, with a dense-output request (`ev`) the frames an accepted step serves, the commit, the status summary
+static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const FwdCtx& c, int cf, float cfg, float t_scale, const Rk45Eval* ev,
+                                hipStream_t s) {
     for (int st = 1; st <= 5; ++st) {
         FC_TRY(rk45_stage_launch(g, u->rk_st, st, u->rk_y, u->rk_k, u->v2, cf, cfg, u->xs, t_scale, u->tvec, s));
         FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
@@ -1335,33 +1337,75 @@ static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const FwdCtx& c
     FC_TRY(rk45_finish_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, cf, cfg, u->xs, t_scale, u->tvec, s));
     FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
     FC_TRY(rk45_error_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, cf, cfg, u->rk_part, s));
-    FC_TRY(rk45_control_launch(g, u->rk_st, u->rk_part, s));
+    FC_TRY(rk45_control_launch(g, u->rk_st, u->rk_part, ev, s));
+    if (ev) FC_TRY(rk45_dense_launch(g, u->rk_st, ev, u->rk_y, u->rk_k, s));       // reads y and K0..K6 before the commit replaces them
     FC_TRY(rk45_commit_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k.k[0], u->rk_k.k[6], s));
     return rk45_status_launch(g, u->rk_st, u->rk_sum, s);
 }
 
-// fc_unet_integrate_rk45 (per_sample = false) and fc_unet_integrate_rk45_per_sample; `fn` names the entry point in argument errors
+// solve_ivp's checks of t_eval, with its messages
+static int check_t_eval(const char* fn, const double* te, int n_eval, double t0, double t1) {
+    const double lo = std::min(t0, t1), hi = std::max(t0, t1);
+    for (int j = 0; j < n_eval; ++j)
+        if (!(te[j] >= lo && te[j] <= hi)) return fail(FC_E_ARG, std::string(fn) + ": Values in `t_eval` are not within `t_span`.");
+    for (int j = 1; j < n_eval; ++j) {
+        const double d = te[j] - te[j - 1];
+        if ((t1 > t0 && d <= 0) || (t1 < t0 && d >= 0))
+            return fail(FC_E_ARG, std::string(fn) + ": Values in `t_eval` are not properly sorted.");
+    }
+    return FC_OK;
+}
+
+// The dense-output request of this call in the handle's device record (header, then the times), ahead of the solve on `s`.  The record
+// grows only when a call brings more times than any before; captured attempts bake its address.
+static int stage_rk45_eval(fc_unet* u, const double* te, int n_eval, float* frames_dev, hipStream_t s) {
+    if (n_eval > u->rk_ev_cap) {
+        FC_HIP(hipStreamSynchronize(s));
+        if (u->rk_ev) dev_free(u->rk_ev);
+        u->rk_ev = nullptr; u->rk_ev_cap = 0;
+        const int cap = n_eval < 1024 ? 1024 : n_eval;
+        FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->rk_ev), sizeof(Rk45Eval) + (size_t)cap * sizeof(double), "integrator.rk45_eval"));
+        u->rk_ev_cap = cap;
+        drop_graphs(u);
+    }
+    std::vector<unsigned char> rec(sizeof(Rk45Eval) + (size_t)n_eval * sizeof(double));
+    const Rk45Eval head{frames_dev, n_eval, 0};
+    std::memcpy(rec.data(), &head, sizeof(head));
+    std::memcpy(rec.data() + sizeof(head), te, (size_t)n_eval * sizeof(double));
+    // pageable source: the runtime stages it before returning (as the time grid of fc_unet_integrate)
+    FC_HIP(hipMemcpyAsync(u->rk_ev, rec.data(), rec.size(), hipMemcpyHostToDevice, s));
+    return FC_OK;
+}
+
+// fc_unet_integrate_rk45 (per_sample = false), fc_unet_integrate_rk45_per_sample and, with n_eval > 0, fc_unet_integrate_rk45_dense;
+// `fn` names the entry point in argument errors
 static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_dev, int B, int H, int W, double t0, double t1,
                           double rtol, double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask,
-                          int mask_is_ones, int* counters, void* stream) {
+                          int mask_is_ones, const double* t_eval, int n_eval, float* frames_dev, int* counters, void* stream) {
     if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, std::string(fn) + ": bad argument");
+    if (n_eval < 0 || (n_eval > 0 && (!t_eval || !frames_dev || (reinterpret_cast<uintptr_t>(frames_dev) & 15))))
+        return fail(FC_E_ARG, std::string(fn) + ": t_eval needs its times and a 16-byte aligned frames buffer");
     if (!(atol >= 0)) return fail(FC_E_ARG, std::string(fn) + ": `atol` must be positive.");      // validate_tol
     if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, std::string(fn) + ": t0 and t1 must be finite");
     const double eps100 = 100 * 2.220446049250313e-16;
     if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
+    FC_TRY(check_t_eval(fn, t_eval, n_eval, t0, t1));
     const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
     const bool cfg_on = has_ids && cfg_strength != 0.0f;
     FC_TRY(check_ready(u, cfg_on ? 2 * B : B, H, W));
     FC_TRY(check_poison(u));
     const Rk45Groups g = rk45_groups(u, B, per_sample);
     for (int i = 0; i < g.G; ++i) { counters[3 * i] = 1; counters[3 * i + 1] = counters[3 * i + 2] = 0; }   // nfev, accepted, rejected
-    if (t0 == t1) return FC_OK;                  // scipy: one evaluation, no step, y0 returned
-    u->arena_touched(0);
-    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
     const int n = B * u->cfg.channels * H * W, cf = cfg_on ? 1 : 0;
     const size_t nbytes = (size_t)n * sizeof(float);
     hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
     FC_HIP(hipSetDevice(u->device));
+    if (t0 == t1) {                              // scipy: one evaluation, no step, y0 returned; every requested time is t0
+        for (int j = 0; j < n_eval; ++j) FC_HIP(hipMemcpyAsync(frames_dev + (size_t)j * n, x_dev, nbytes, hipMemcpyDeviceToDevice, caller));
+        return FC_OK;
+    }
+    u->arena_touched(0);
+    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
     if (!u->rk_st) FC_TRY(alloc_rk45(u));
     if (!u->rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); u->rk_host = static_cast<Rk45Status*>(hp); }
     if (!u->ev_rk) FC_HIP(hipEventCreateWithFlags(&u->ev_rk, hipEventDisableTiming));
@@ -1370,6 +1414,8 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
     if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
+    if (n_eval > 0) FC_TRY(stage_rk45_eval(u, t_eval, n_eval, frames_dev, s));
+    const Rk45Eval* ev = n_eval > 0 ? u->rk_ev : nullptr;
     FC_TRY(meet_enter(u, s));
 
     // f(t0, y0) and select_initial_step of every group (two forwards, no graph)
@@ -1389,13 +1435,14 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     // thread can overtake the plain launches and copies queued just before it (see there).
     FC_HIP(hipStreamSynchronize(s));
 
+    // (an attempt with dense output has one more launch: a different graph)
     const auto key = std::make_tuple(per_sample ? kRk45PerSampleMethod : kRk45Method, B, (int)cfg_on, mask_mode, fbits(cfg_strength), 0u,
-                                     fbits(t_scale), (int)has_ids);
-    auto attempt = [&] { return enqueue_rk45_attempt(u, g, c, cf, cfg_strength, t_scale, s); };
+                                     fbits(t_scale), (int)has_ids | (ev ? 2 : 0));
+    auto attempt = [&] { return enqueue_rk45_attempt(u, g, c, cf, cfg_strength, t_scale, ev, s); };
     while (u->rk_host->unfinished > 0) {
         if (no_graph()) {
             FC_TRY(attempt());
-        } else {   // one attempt = one graph: 6 plan runs and 10 small launches, a single chain (no parallel branches)
+        } else {   // one attempt = one graph: 6 plan runs and 10 (11 with dense output) small launches, a single chain (no parallel branches)
             hipGraphExec_t exec = nullptr;
             FC_TRY(cached_graph(u, key, s, attempt, &exec));
             FC_HIP(hipGraphLaunch(exec, s));
@@ -1433,14 +1480,21 @@ int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int B, int H, int W, double
                                       float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
                                       int* counters, void* stream) {
     return integrate_rk45(u, false, "fc_unet_integrate_rk45", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength, mask,
-                          mask_is_ones, counters, stream);
+                          mask_is_ones, nullptr, 0, nullptr, counters, stream);
 }
 
 int fc_unet_integrate_rk45_per_sample(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
                                       float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
                                       int* counters, void* stream) {
     return integrate_rk45(u, true, "fc_unet_integrate_rk45_per_sample", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength,
-                          mask, mask_is_ones, counters, stream);
+                          mask, mask_is_ones, nullptr, 0, nullptr, counters, stream);
+}
+
+int fc_unet_integrate_rk45_dense(fc_unet* u, int per_sample, float* x_dev, int B, int H, int W, double t0, double t1, double rtol,
+                                 double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
+                                 const double* t_eval_host, int n_eval, float* frames_dev, int* counters, void* stream) {
+    return integrate_rk45(u, per_sample != 0, "fc_unet_integrate_rk45_dense", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids,
+                          cfg_strength, mask, mask_is_ones, t_eval_host, n_eval, frames_dev, counters, stream);
 }
 
 // ---- debug / test hooks --------------------------------------------------------------------------

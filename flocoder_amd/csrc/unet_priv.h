@@ -41,6 +41,11 @@ struct fc_unet : fc::ParamStore {
     fc::Rk45Status* rk_sum = nullptr;
     fc::Rk45Status* rk_host = nullptr;
     hipEvent_t ev_rk = nullptr;
+    // dense output (fc_unet_integrate_rk45_dense): the call's requested times, their count and the frames pointer, on the device like the
+    // fixed-step integrator's time grid (`ts_dev`), so a replayed attempt serves any request; allocated by the first such call, grows
+    // with the longest t_eval seen, lives as long as the handle
+    fc::Rk45Eval* rk_ev = nullptr;
+    int rk_ev_cap = 0;                       // times
 
     // Fused Block tails whose workgroups wait for each other (conv_dev.h) need the device to themselves.  `shared` = the caller said the
     // device is shared with other streams / processes (fc_unet_set_shared): plans are then built without such launches.  A wait that

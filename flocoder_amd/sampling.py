@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from .unet import Unet
+from .unet import Unet, validate_t_eval
 
 
 def warp_time(t, dt=None, s=.5):
@@ -142,8 +142,37 @@ def _validate_tol(rtol, atol):
     return rtol, atol
 
 
+def _solve_ivp_rk45(ode_func, eps, y0, rtol, atol, t_eval):
+    """The legacy ``solve_ivp(method="RK45")`` call -> ``(solution, y(1))``.  With ``t_eval`` scipy returns the requested times only
+    (``solution.y`` are the frames), so the solver's own final state is taken from an event function that never fires: solve_ivp hands
+    it every accepted ``(t, y)`` and changes nothing else, the steps and ``y(1)`` are those of the call without ``t_eval``."""
+    import numpy as np
+    from scipy import integrate
+    if t_eval is None:
+        solution = integrate.solve_ivp(ode_func, (eps, 1), y0, rtol=rtol, atol=atol, method="RK45")
+        return solution, solution.y[:, -1]
+    last = [np.asarray(y0)]
+
+    def watch(t, y):
+        last[0] = np.array(y)
+        return 1.0
+
+    solution = integrate.solve_ivp(ode_func, (eps, 1), y0, rtol=rtol, atol=atol, method="RK45", t_eval=t_eval, events=watch)
+    return solution, last[0]
+
+
+def _host_frames(solution, n_eval, shape, device):
+    """``solution.y`` of a solve with ``t_eval`` ([unknowns, F]; an empty list for no times) -> fp32 ``[F, *shape]``."""
+    import numpy as np
+    if n_eval == 0:
+        return torch.empty((0,) + tuple(shape), dtype=torch.float32, device=device)
+    y = np.asarray(solution.y, dtype=np.float64).reshape(-1, n_eval)
+    return torch.tensor(y.T.copy()).reshape((n_eval,) + tuple(shape)).type(torch.float32).to(device)
+
+
 @torch.no_grad()
-def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rtol=1e-5, atol=1e-5, cfg_strength=0.0, per_sample=False):
+def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rtol=1e-5, atol=1e-5, cfg_strength=0.0, per_sample=False,
+                 t_eval=None):
     """Legacy adaptive sampler, train_sd_flowers.py:78-107: ``scipy.integrate.solve_ivp(method="RK45")`` over ``(eps, 1)`` on
     ``model(float32(x), float32(t) * 999, cond)``; returns ``(latents, nfe)`` with nfe = scipy's ``solution.nfev``.  ``cond`` is a class-id
     tensor as upstream or a cond dict; ``source`` replaces the randn start; ``cfg_strength`` is an extension (0 keeps upstream behaviour;
@@ -151,13 +180,21 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
     upstream, so a sample's trajectory depends on the rest of its batch.  A ``flocoder_amd.Unet`` runs the whole solve in the library
     (Unet.integrate_rk45: stages, error norm and step controller on the device); any other model takes the legacy host path through
     numpy.  Where scipy would return ``success=False`` (step size below the spacing of t) this raises RuntimeError -- the legacy code
-    silently used the last state.
+    silently used the last state -- and no frames are returned either.
 
     ``per_sample=True`` is an extension: every sample is its own solve_ivp problem over its C*H*W unknowns (own initial step, error
     norm, step size, counters), so a sample's result depends only on its own source, class id and mask, not on how samples are
     grouped into batches.  nfe is then the largest per-sample nfev: the number of batch forwards the device path makes.  A failing
-    sample raises RuntimeError naming it."""
+    sample raises RuntimeError naming it.
+
+    ``t_eval`` (a sequence, array or tensor of times in ``[eps, 1]``, increasing) is solve_ivp's: the solver steps exactly as it would
+    have, and every accepted step evaluates its quartic interpolant at the requested times inside it (per sample: each sample's own
+    steps).  Returns ``(latents, nfe, frames)`` with ``frames`` fp32 ``[F, B, C, H, W]``; ``latents`` and ``nfe`` are bit for bit those
+    of the call without ``t_eval``.  ``latents`` is still the solver's state at t = 1 -- unlike ``solve_ivp(..., t_eval=...).y[:, -1]``,
+    which is the LAST REQUESTED time (at ``t_eval[-1] == 1`` the interpolant there: equal to ``latents`` to rounding, not in bits).
+    Bad times raise solve_ivp's ValueErrors before any work."""
     rtol, atol = _validate_tol(rtol, atol)
+    te = None if t_eval is None else validate_t_eval(t_eval, eps, 1)
     p0 = next(model.parameters())
     device = p0.device if device is None else torch.device(device)
     if cond is not None and not isinstance(cond, dict):
@@ -166,15 +203,15 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
     if isinstance(model, Unet):
         cls = cond.get('class_cond') if cond else None
         mask, ones = _mask_flags(cond)
-        nfev, _, _ = model.integrate_rk45(x, eps, 1.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
-                                          mask_is_ones=ones, per_sample=per_sample)
-        return x, (int(nfev.max()) if per_sample else nfev)
+        nfev, *rest = model.integrate_rk45(x, eps, 1.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
+                                           mask_is_ones=ones, per_sample=per_sample, t_eval=te)
+        nfe = int(nfev.max()) if per_sample else nfev
+        return (x, nfe) if te is None else (x, nfe, rest[2])
 
     if per_sample:
-        return _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength)
+        return _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength, te)
 
     import numpy as np
-    from scipy import integrate
     shape = tuple(x.shape)
     t_vec_template = torch.zeros(shape[0], device=device)
 
@@ -183,18 +220,19 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
         drift = v_func_cfg(model, cond, cfg_strength, t_vec_template, xt, t)
         return drift.detach().cpu().numpy().reshape((-1,))
 
-    solution = integrate.solve_ivp(ode_func, (eps, 1), x.detach().cpu().numpy().reshape((-1,)), rtol=rtol, atol=atol, method="RK45")
+    solution, y1 = _solve_ivp_rk45(ode_func, eps, x.detach().cpu().numpy().reshape((-1,)), rtol, atol, te)
     if not solution.success:
         raise RuntimeError(f"rk45_sampler: {solution.message}")
-    return torch.tensor(solution.y[:, -1]).reshape(shape).type(torch.float32).to(device), solution.nfev
+    lat = torch.tensor(y1).reshape(shape).type(torch.float32).to(device)
+    return (lat, solution.nfev) if te is None else (lat, solution.nfev, _host_frames(solution, len(te), shape, device))
 
 
-def _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength):
+def _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength, te=None):
     """rk45_sampler(per_sample=True) for models that are not a flocoder_amd.Unet: one legacy solve_ivp per sample, the model called on
-    that sample alone (its class id and mask row)."""
+    that sample alone (its class id and mask row); with ``te`` (validated times) also the frames [F, B, C, H, W]."""
     import numpy as np
-    from scipy import integrate
     out, nfevs, failed = x.clone(), [], []
+    frames = None if te is None else torch.empty((len(te),) + tuple(x.shape), dtype=torch.float32, device=x.device)
     for b in range(x.shape[0]):
         shape = (1,) + tuple(x.shape[1:])
         cond_b = {k: (v[b:b + 1] if torch.is_tensor(v) else v) for k, v in cond.items()} if cond else cond
@@ -205,24 +243,28 @@ def _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength):
             drift = v_func_cfg(model, cond_b, cfg_strength, t_vec_template, xt, t)
             return drift.detach().cpu().numpy().reshape((-1,))
 
-        solution = integrate.solve_ivp(ode_func, (eps, 1), x[b].detach().cpu().numpy().reshape((-1,)), rtol=rtol, atol=atol, method="RK45")
+        solution, y1 = _solve_ivp_rk45(ode_func, eps, x[b].detach().cpu().numpy().reshape((-1,)), rtol, atol, te)
         if not solution.success:
             failed.append(f"sample {b}: {solution.message}")
             continue
-        out[b] = torch.tensor(solution.y[:, -1]).reshape(shape[1:]).type(torch.float32).to(x.device)
+        out[b] = torch.tensor(y1).reshape(shape[1:]).type(torch.float32).to(x.device)
+        if te is not None:
+            frames[:, b] = _host_frames(solution, len(te), shape[1:], x.device)
         nfevs.append(int(solution.nfev))
     if failed:
         raise RuntimeError(f"rk45_sampler: {len(failed)} of {x.shape[0]} samples failed; " + " ".join(failed))
-    return out, max(nfevs)
+    return (out, max(nfevs)) if te is None else (out, max(nfevs), frames)
 
 
 @torch.no_grad()
-def generate_latents_rk45(model, shape, device=None, cond=None, cfg_strength=3.0, source=None, rtol=1e-5, atol=1e-5, per_sample=False):
+def generate_latents_rk45(model, shape, device=None, cond=None, cfg_strength=3.0, source=None, rtol=1e-5, atol=1e-5, per_sample=False,
+                          t_eval=None):
     """The function sampling.py:142-143 dispatches to (undefined upstream): the legacy RK45 sampler over (1e-3, 1), no time warp, with
     classifier-free guidance as generate_latents_rk4 applies it.  ``per_sample=True`` solves every sample on its own (rk45_sampler).
-    Returns (latents, nfe)."""
+    Returns (latents, nfe); with ``t_eval`` (times in [1e-3, 1], see rk45_sampler) ``(latents, nfe, frames)``: the trajectory at those
+    times as ``[F, B, C, H, W]``, e.g. for ``decode_latents(codec, frames.flatten(0, 1))``; ``latents`` stays the state at t = 1."""
     return rk45_sampler(model, shape, device=device, cond=cond, source=source, eps=1e-3, rtol=rtol, atol=atol, cfg_strength=cfg_strength,
-                        per_sample=per_sample)
+                        per_sample=per_sample, t_eval=t_eval)
 
 
 @torch.no_grad()

@@ -40,6 +40,24 @@ def param_table(cfg: B.fc_unet_config) -> List[Tuple[str, Tuple[int, ...], int]]
     return read_param_table("fc_unet", "create", C.byref(cfg))[0]
 
 
+def validate_t_eval(t_eval, t0: float, t1: float):
+    """solve_ivp's checks of ``t_eval`` over ``(t0, t1)``, with its messages: a sequence, array or tensor -> contiguous fp64 numpy
+    array.  (Unlike scipy, a NaN counts as outside the span: no step would ever serve it.)"""
+    import numpy as np
+    if torch.is_tensor(t_eval):
+        t_eval = t_eval.detach().cpu().numpy()
+    te = np.asarray(t_eval, dtype=np.float64)
+    if te.ndim != 1:
+        raise ValueError("`t_eval` must be 1-dimensional.")
+    te = np.ascontiguousarray(te)
+    if not np.all((te >= min(t0, t1)) & (te <= max(t0, t1))):
+        raise ValueError("Values in `t_eval` are not within `t_span`.")
+    d = np.diff(te)
+    if (t1 > t0 and np.any(d <= 0)) or (t1 < t0 and np.any(d >= 0)):
+        raise ValueError("Values in `t_eval` are not properly sorted.")
+    return te
+
+
 class _UnetFunction(torch.autograd.Function):
     """Autograd bridge: forward and backward both run in the library; parameters receive ``.grad`` as torch expects, and so do
     ``x`` and the mask when they require it (the inpainting step reaches the MaskEncoder through both, train_flow.py:146-147)."""
@@ -380,7 +398,7 @@ class Unet(NativeModule):
 
     def integrate_rk45(self, x: torch.Tensor, t0: float, t1: float, *, rtol: float, atol: float, t_scale: float = 999.0,
                        class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,
-                       mask_is_ones: bool = False, check: bool = True, per_sample: bool = False):
+                       mask_is_ones: bool = False, check: bool = True, per_sample: bool = False, t_eval=None):
         """Integrate ``x`` in place from ``t0`` to ``t1`` with scipy's adaptive RK45 (``fc_unet_integrate_rk45``: solve_ivp semantics,
         one step size and one error norm for the whole batch, so a sample's trajectory depends on the rest of its batch as upstream).
         Synchronous: the host waits for a small status record behind every attempt of six evaluations.  Returns ``(nfev, accepted,
@@ -390,7 +408,15 @@ class Unet(NativeModule):
         ``per_sample=True`` (``fc_unet_integrate_rk45_per_sample``) solves every sample as its own solve_ivp problem (own initial step,
         error norm, step size and counters), so a sample's result depends only on its own source, class id and mask.  It then returns
         ``(nfev, accepted, rejected)`` as int64 CPU tensors of shape [B]; the call makes ``nfev.max()`` batch forwards.  A failing
-        sample raises RuntimeError naming it, and ``x`` is left untouched."""
+        sample raises RuntimeError naming it, and ``x`` is left untouched.
+
+        ``t_eval`` (a sequence, array or tensor of times; ``fc_unet_integrate_rk45_dense``) is solve_ivp's: the steps, ``x`` and the
+        counters are those of the call without it, and the return value gains ``frames``, an fp32 tensor ``[F, B, C, H, W]`` on
+        ``x``'s device: frame j is the trajectory at ``t_eval[j]``, evaluated from the quartic interpolant of the accepted step that
+        contains it (in per-sample mode each sample's own step).  The times must lie in ``[t0, t1]`` and be strictly monotonic in the
+        direction of integration (ValueError with scipy's messages otherwise, before anything else is looked at).  When the solve
+        fails the frames are discarded with it."""
+        te = None if t_eval is None else validate_t_eval(t_eval, t0, t1)
         if not x.is_cuda:
             raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
         if atol < 0:
@@ -420,16 +446,25 @@ class Unet(NativeModule):
         rows = bsz * (2 if (class_ids is not None and cfg_strength) else 1)
         hnd = self._native(dev)
         B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
-        fn = B.lib().fc_unet_integrate_rk45_per_sample if per_sample else B.lib().fc_unet_integrate_rk45
         counters = (C.c_int * (3 * bsz if per_sample else 3))()
-        B.check(fn(hnd, B.ptr(x), bsz, h, w, float(t0), float(t1), float(rtol), float(atol), float(t_scale), B.ptr(class_ids),
-                   float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), counters, B.current_stream(dev)))
+        head = (B.ptr(x), bsz, h, w, float(t0), float(t1), float(rtol), float(atol), float(t_scale), B.ptr(class_ids),
+                float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones))
+        frames = None
+        if te is None:
+            fn = B.lib().fc_unet_integrate_rk45_per_sample if per_sample else B.lib().fc_unet_integrate_rk45
+            B.check(fn(hnd, *head, counters, B.current_stream(dev)))
+        else:
+            frames = torch.empty((len(te),) + tuple(x.shape), dtype=torch.float32, device=dev)
+            B.check(B.lib().fc_unet_integrate_rk45_dense(hnd, int(per_sample), *head, te.ctypes.data_as(C.POINTER(C.c_double)), len(te),
+                                                         B.ptr(frames), counters, B.current_stream(dev)))
         if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
             B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
         if per_sample:
             c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
-            return c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone()
-        return int(counters[0]), int(counters[1]), int(counters[2])
+            out = (c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone())
+        else:
+            out = (int(counters[0]), int(counters[1]), int(counters[2]))
+        return out if te is None else out + (frames,)
 
     def profile_ops(self, batch: int, repeats: int = 20):
         """Per-launch device time of the current plan (bench.py's live roofline measurement).  Run a forward or an

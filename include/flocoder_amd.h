@@ -139,6 +139,24 @@ int fc_unet_integrate_rk45_per_sample(fc_unet* u, float* x_dev, int batch, int h
                                       double atol, float t_scale, const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev,
                                       int mask_is_ones, int* counters /* host, [3*batch] */, void* stream);
 
+/* Either adaptive RK45 solve with the trajectory at requested times: solve_ivp's `t_eval`.  per_sample == 0 is
+ * fc_unet_integrate_rk45, otherwise fc_unet_integrate_rk45_per_sample; every argument they share means what it means there
+ * (counters[3] or counters[3 * batch]).  The step sequence is untouched: x_dev and the counters get the bits of the call without
+ * t_eval.  After every accepted step of a controller (the batch's one, or each sample's own) every not-yet-served t_eval[j] with
+ * dir * (t_eval[j] - t) <= 0 is evaluated from that step's quartic interpolant (scipy's RkDenseOutput: y_old + h Q p, Q = K^T P over the
+ * seven stage derivatives the step already holds; fp64, no extra evaluation) and written as frame j of that controller's rows:
+ * frames_dev [n_eval, batch, C, H, W] fp32, caller-owned, 16-byte aligned, written on the library's stream and ordered before `stream`
+ * continues, like x_dev.  A time equal to t0 yields the source; the frame at t1 is the interpolant there, equal to x_dev to rounding.
+ * t_eval_host: n_eval fp64 times on the host (read before the call returns), inside [t0, t1] and strictly monotonic in the direction
+ * of integration, else FC_E_ARG with scipy's wording ("Values in `t_eval` are not within `t_span`." / "Values in `t_eval` are not
+ * properly sorted.").  n_eval == 0 is the plain call.  t0 == t1: every frame is the source.  On FC_E_STATE (a failed solve) the
+ * frames hold no promise.  The times, their count and frames_dev live in device memory of the handle, so the captured attempt (one
+ * more small launch than the plain one, its own graph) is replayed for any request. */
+int fc_unet_integrate_rk45_dense(fc_unet* u, int per_sample, float* x_dev, int batch, int height, int width, double t0, double t1,
+                                 double rtol, double atol, float t_scale, const int64_t* class_ids_dev, float cfg_strength,
+                                 const float* mask_dev, int mask_is_ones, const double* t_eval_host, int n_eval, float* frames_dev,
+                                 int* counters, void* stream);
+
 /* Kept for compatibility: the reserved batch always runs as ONE chain of rows on one stream, so this returns 1 and sets
  * *rows_per_chain to the reserved batch (0 before fc_unet_reserve). */
 int fc_unet_chains(const fc_unet* u, int* rows_per_chain);

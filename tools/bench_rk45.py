@@ -11,6 +11,10 @@ seeded as bench.py seeds them), B=64 latents of 4x32x32, class ids, no guidance.
                                model.forward through numpy copies, one solve
 
     python tools/bench_rk45.py [--reps 5] [--rk4-steps 26] [--no-legacy]
+
+With ``--t-eval N [N ...]`` (e.g. ``--t-eval 8 64``) it measures dense output instead: the same solve with 0 and with N evenly spaced
+requested times over [1e-3, 1], alternating in this process, and prints ONE JSON line with the per-solve medians, their spreads and the
+ratios against 0 times (profiles/rk45_dense_bench.json), after checking that the latents and nfev do not depend on t_eval.
 """
 import argparse
 import json
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rk4-steps", type=int, default=26)
     ap.add_argument("--no-legacy", action="store_true")
+    ap.add_argument("--t-eval", type=int, nargs="+", metavar="N", help="time dense output with 0 and N requested times instead")
     a = ap.parse_args()
     from flocoder_amd import sampling as S
     from flocoder_amd.unet import Unet
@@ -57,6 +62,33 @@ def main():
         out = fn()
         torch.cuda.synchronize(dev)
         return time.perf_counter() - t0, out
+
+    if a.t_eval:
+        counts = [0] + [n for n in a.t_eval if n > 0]
+        times = {n: (torch.linspace(1e-3, 1.0, n, dtype=torch.float64).tolist() if n else None) for n in counts}
+
+        def dense(n):
+            return S.generate_latents_rk45(model, shape, cond=cond, cfg_strength=0.0, source=noise, t_eval=times[n])
+
+        ref = None
+        for n in counts:                                     # warm both graph shapes; t_eval must not change the solve
+            out = dense(n)
+            ref = ref or out
+            assert torch.equal(out[0], ref[0]) and out[1] == ref[1] and (n == 0 or torch.isfinite(out[2]).all())
+        ts = {n: [] for n in counts}
+        for _ in range(a.reps):
+            for n in counts:
+                ts[n].append(timed(lambda: dense(n))[0])
+        med = {n: statistics.median(v) * 1e3 for n, v in ts.items()}
+        rec = {"tool": "bench_rk45 --t-eval", "device": torch.cuda.get_device_name(dev), "batch": BATCH, "latent": list(LATENT), "dim": DIM,
+               "n_classes": NCLS, "rtol": 1e-5, "atol": 1e-5, "reps": a.reps, "AMD_DIRECT_DISPATCH": os.environ.get("AMD_DIRECT_DISPATCH"),
+               "nfev": ref[1], "t_eval_counts": counts,
+               "ms_per_solve": {str(n): round(med[n], 2) for n in counts},
+               "spread_ms": {str(n): [round(min(v) * 1e3, 2), round(max(v) * 1e3, 2)] for n, v in ts.items()},
+               "ratio_to_0": {str(n): round(med[n] / med[0], 4) for n in counts if n},
+               "frame_mbytes": {str(n): round(n * BATCH * LATENT[0] * LATENT[1] * LATENT[2] * 4 / 1e6, 2) for n in counts if n}}
+        print(json.dumps(rec), flush=True)
+        return
 
     rk45(); rk4()                                            # warm: plans, graphs, code objects
     t45, t4 = [], []
