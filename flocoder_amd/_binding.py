@@ -75,6 +75,13 @@ SIGNATURES = {
     "fc_unet_set_grad_buckets": (_i, [_vp, _i]),
     "fc_unet_backward_launches": (_i, [_vp]),
     "fc_unet_backward_op_info": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    "fc_unet_vjp_x": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "fc_unet_vjp_launches": (_i, [_vp]),
+    "fc_unet_train_form": (_i, [_vp]),
+    "fc_unet_train_release": (_i, [_vp]),
+    "fc_unet_vjp_op_info": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    "fc_unet_log_likelihood": (_i, [_vp, _vp, _i, _i, _i, _pf, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fc_debug_probe_dot": (_i, [_vp, _vp, _vp, _i, _i64, _vp]),
     "fc_unet_arena_serial": (C.c_uint64, [_vp]),
     "fc_unet_class_param_range": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "fc_flow_interp": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),

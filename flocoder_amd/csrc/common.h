@@ -276,6 +276,15 @@ int ode_rk4_stage_launch(const float* sc, const float* y, float* xs, float* k_ou
 // y += (dt/6) * (k1 + 2*k2 + 2*k3 + v)
 int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v2, int n,
                          int cfg_on, float cfg, hipStream_t s);
+// likelihood on the RK4 grid (one workgroup per sample of m elements, no CFG): the stage / final updates above plus
+// dst[3 b + slot] = sum eps g (stages 1..3), a[b] += (double(dt)/6)(d1 + 2 d2 + 2 d3 + sum eps g) (stage 4); tvec[b] as the stage kernel
+int ode_ll_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v, const float* g, const float* eps,
+                        double* dst, int slot, int B, int m, int full, int tsel, float t_scale, float* tvec, hipStream_t s);
+int ode_ll_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v, const float* g,
+                        const float* eps, const double* dst, double* a, int B, int m, hipStream_t s);
+// logp[b] = -|z_b|^2/2 - (m/2) ln 2pi + a[b]
+int ode_ll_logp_launch(const float* z, const double* a, double* logp, int B, int m, hipStream_t s);
+int ode_ll_dot_launch(const float* eps, const float* g, double* out, int B, int m, hipStream_t s);
 
 // ---- adaptive RK45 (ode.hip): scipy's solve_ivp(method="RK45") with the controller on the device ----------------------------
 // Controller state and status record of one solve (fp64 as scipy; `failed`: 1 step size below spacing, 2 attempt cap).

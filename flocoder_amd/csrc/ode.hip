@@ -689,4 +689,132 @@ int rk45_out_launch(const double* y, float* x, int n, hipStream_t s) {
     return FC_OK;
 }
 
+// ================================================================================================ likelihood on the RK4 grid
+// fc_unet_log_likelihood: the RK4 step above (any grid direction; cfg off) carrying, per sample b, the integral of the Hutchinson
+// divergence estimate next to x.  Every stage j has, besides its velocity v_j, the input gradient g_j = (dv_j/dx_j)^T eps of the same
+// forward (fc_unet_vjp_x's chain); the kernel that closes the stage forms d_j[b] = sum_i eps[b,i] g_j[b,i] in the pass that does the
+// state arithmetic, and the kernel that closes the interval adds (double(dt)/6)(d1 + 2 d2 + 2 d3 + d4) to a[b].
+//
+// One workgroup per sample: each thread's fp64 products are summed in index order, the 256 thread sums by block_sum's fixed tree, so
+// d_j[b] depends on neither the batch size nor the scheduling, and no partial sums cross a launch.  (A sample is C*H*W <= a few 10^4
+// floats, three streams of it per stage: the launches are latency-sized either way.)  The state arithmetic is that of
+// ode_rk4_stage_kernel / ode_rk4_final_kernel, operation for operation.
+
+// sum_i eps[base + i] g[base + i] over one sample, fp64 products and sums; the same value in every thread
+__device__ __forceinline__ double probe_dot_acc(double s, const float4 e, const float4 q) {
+    s += (double)e.x * (double)q.x; s += (double)e.y * (double)q.y;
+    s += (double)e.z * (double)q.z; s += (double)e.w * (double)q.w;
+    return s;
+}
+
+__global__ void __launch_bounds__(256) ode_ll_stage_kernel(const float* sc, const float* y, float* xs, float* k_out, const float* v,
+                                                           const float* g, const float* eps, double* dst, int slot, int m, int full,
+                                                           int tsel, float t_scale, float* tvec) {
+    __shared__ double red[256];
+    const int b = blockIdx.x, base = b * m;
+    const float t = sc[0], dt = sc[1];
+    if (threadIdx.x == 0) {
+        const float tn = tsel == 1 ? add_(t, dt * 0.5f) : add_(t, dt);     // t + dt/2 | t + dt
+        tvec[b] = mul_(tn, t_scale);
+    }
+    double d = 0.0;
+    for (int j = 4 * threadIdx.x; j < m; j += 4 * 256) {
+        const int i = base + j;
+        const float4 k = *reinterpret_cast<const float4*>(v + i);
+        *reinterpret_cast<float4*>(k_out + i) = k;
+        const float4 yv = *reinterpret_cast<const float4*>(y + i);
+        float4 o;
+        if (full) {   // y + dt*k3
+            o.x = add_(yv.x, mul_(dt, k.x)); o.y = add_(yv.y, mul_(dt, k.y));
+            o.z = add_(yv.z, mul_(dt, k.z)); o.w = add_(yv.w, mul_(dt, k.w));
+        } else {      // y + dt*k/2
+            o.x = add_(yv.x, mul_(dt, k.x) * 0.5f); o.y = add_(yv.y, mul_(dt, k.y) * 0.5f);
+            o.z = add_(yv.z, mul_(dt, k.z) * 0.5f); o.w = add_(yv.w, mul_(dt, k.w) * 0.5f);
+        }
+        *reinterpret_cast<float4*>(xs + i) = o;
+        d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + i), *reinterpret_cast<const float4*>(g + i));
+    }
+    const double r = block_sum(d, red);
+    if (threadIdx.x == 0) dst[3 * b + slot] = r;
+}
+
+__global__ void __launch_bounds__(256) ode_ll_final_kernel(const float* sc, float* y, const float* k1, const float* k2, const float* k3,
+                                                           const float* v, const float* g, const float* eps, const double* dst, double* a,
+                                                           int m) {
+    __shared__ double red[256];
+    const int b = blockIdx.x, base = b * m;
+    const float dt6 = __fdiv_rn(sc[1], 6.0f);
+    double d = 0.0;
+    for (int j = 4 * threadIdx.x; j < m; j += 4 * 256) {
+        const int i = base + j;
+        const float4 k4 = *reinterpret_cast<const float4*>(v + i);
+        const float4 p = *reinterpret_cast<const float4*>(k1 + i), q = *reinterpret_cast<const float4*>(k2 + i),
+                     c = *reinterpret_cast<const float4*>(k3 + i);
+        float4 yv = *reinterpret_cast<float4*>(y + i);
+        yv.x = rk4_comb(yv.x, p.x, q.x, c.x, k4.x, dt6); yv.y = rk4_comb(yv.y, p.y, q.y, c.y, k4.y, dt6);
+        yv.z = rk4_comb(yv.z, p.z, q.z, c.z, k4.z, dt6); yv.w = rk4_comb(yv.w, p.w, q.w, c.w, k4.w, dt6);
+        *reinterpret_cast<float4*>(y + i) = yv;
+        d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + i), *reinterpret_cast<const float4*>(g + i));
+    }
+    const double d4 = block_sum(d, red);
+    if (threadIdx.x == 0) {   // a + (dt/6)(d1 + 2 d2 + 2 d3 + d4), left to right
+        const double* ds = dst + 3 * b;
+        a[b] = a[b] + ((double)sc[1] / 6.0) * (((ds[0] + 2.0 * ds[1]) + 2.0 * ds[2]) + d4);
+    }
+}
+
+// logp[b] = -|z_b|^2 / 2 - (m/2) ln(2 pi) + a[b]: the standard normal at the noise end plus the integrated divergence
+__global__ void __launch_bounds__(256) ode_ll_logp_kernel(const float* z, const double* a, double* logp, int m) {
+    __shared__ double red[256];
+    const int b = blockIdx.x, base = b * m;
+    double s = 0.0;
+    for (int j = 4 * threadIdx.x; j < m; j += 4 * 256) s = probe_dot_acc(s, *reinterpret_cast<const float4*>(z + base + j), *reinterpret_cast<const float4*>(z + base + j));
+    const double r = block_sum(s, red);
+    if (threadIdx.x == 0) logp[b] = (-0.5 * r - 0.5 * (double)m * 1.8378770664093454835606594728112) + a[b];
+}
+
+// test hook (fc_debug_probe_dot): the stage kernels' reduction on its own
+__global__ void __launch_bounds__(256) ode_ll_dot_kernel(const float* eps, const float* g, double* out, int m) {
+    __shared__ double red[256];
+    const int b = blockIdx.x, base = b * m;
+    double d = 0.0;
+    for (int j = 4 * threadIdx.x; j < m; j += 4 * 256)
+        d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + base + j), *reinterpret_cast<const float4*>(g + base + j));
+    const double r = block_sum(d, red);
+    if (threadIdx.x == 0) out[b] = r;
+}
+
+static int ll_shape_ok(int B, int m) {
+    if (B < 1 || m < 4 || (m & 3)) return fail(FC_E_SHAPE, "ode: elements per sample must be a positive multiple of 4");
+    if ((long long)B * m > 0x7fffffffLL) return fail(FC_E_SHAPE, "ode: the kernels index the batch with int (batch * elements per sample < 2^31)");
+    return FC_OK;
+}
+int ode_ll_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v, const float* g, const float* eps,
+                        double* dst, int slot, int B, int m, int full, int tsel, float t_scale, float* tvec, hipStream_t s) {
+    FC_TRY(ll_shape_ok(B, m));
+    if (slot < 0 || slot > 2) return fail(FC_E_ARG, "ode: stage slot must lie in [0, 2]");
+    hipLaunchKernelGGL(ode_ll_stage_kernel, dim3(B), dim3(256), 0, s, sc, y, xs, k_out, v, g, eps, dst, slot, m, full, tsel, t_scale, tvec);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_ll_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v, const float* g,
+                        const float* eps, const double* dst, double* a, int B, int m, hipStream_t s) {
+    FC_TRY(ll_shape_ok(B, m));
+    hipLaunchKernelGGL(ode_ll_final_kernel, dim3(B), dim3(256), 0, s, sc, y, k1, k2, k3, v, g, eps, dst, a, m);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_ll_logp_launch(const float* z, const double* a, double* logp, int B, int m, hipStream_t s) {
+    FC_TRY(ll_shape_ok(B, m));
+    hipLaunchKernelGGL(ode_ll_logp_kernel, dim3(B), dim3(256), 0, s, z, a, logp, m);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_ll_dot_launch(const float* eps, const float* g, double* out, int B, int m, hipStream_t s) {
+    FC_TRY(ll_shape_ok(B, m));
+    hipLaunchKernelGGL(ode_ll_dot_kernel, dim3(B), dim3(256), 0, s, eps, g, out, m);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
 }  // namespace fc

@@ -54,6 +54,7 @@ struct Plan {                 // one launch plan + activation arena for up to ma
     std::vector<Op> ops;
     std::vector<std::string> op_kernel, op_what;  // parallel to ops: kernel family, reference module it serves
     std::vector<double> op_flops;                  // algorithmic FLOPs per sample of that launch
+    std::vector<char> op_param_only;               // backward plans: the launch's only products are parameter gradients (fc_unet_vjp_x leaves it out)
     std::vector<double> op_bytes_ps, op_bytes_fixed;   // algorithmic HBM bytes of that launch: per sample (activations in + out, each once) and per launch (weights); 0 = not stated
     std::vector<void*> allocs;
     double flops = 0.0;            // per sample, the reference's arithmetic (2 x MACs of every module as upstream computes it)
@@ -223,6 +224,8 @@ struct PlanBuilder {
 
     // guard: 0 always | 1 only when the call has a mask | 2 only when it runs mask_fusion_conv | 3 only when it has NO mask | 4 mask but no fusion
     int guard = 0;
+    // backward plans: the entries pushed while this is set produce nothing the data-gradient chain towards d(x) reads (Plan::op_param_only)
+    bool param_only = false;
     // flops: what the launch executes per sample (per-launch tables, rooflines); flops_ref (> 0): what the reference's arithmetic for the same
     // module is, when that differs (folded upsampling) -- Plan::flops, the per-sample figure of SURVEY 8(d), adds up the reference's
     void push(Op op, const std::string& kernel, double flops = 0.0, double bytes_ps = 0.0, double bytes_fixed = 0.0, double flops_ref = 0.0) {
@@ -238,6 +241,7 @@ struct PlanBuilder {
         pl->op_kernel.push_back(kernel);
         pl->op_what.push_back(scope);
         pl->op_flops.push_back(flops);
+        pl->op_param_only.push_back(param_only ? 1 : 0);
         pl->op_bytes_ps.push_back(bytes_ps);
         pl->op_bytes_fixed.push_back(bytes_fixed);
         pl->flops += flops_ref > 0.0 ? flops_ref : flops;

@@ -6,6 +6,7 @@
 // captured in a hipGraph and replayed (the reference's per-call host syncs are gone).
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -369,6 +370,7 @@ static void free_plan(fc_unet* u) {
     for (void* p : u->int_allocs) dev_free(p);
     u->int_allocs.clear();
     u->rk_y = u->rk_ynew = u->rk_part = nullptr; u->rk_k = Rk45K{}; u->rk_st = nullptr; u->rk_sum = nullptr;   // (were in int_allocs)
+    u->ll_g = nullptr; u->ll_d = nullptr;
     u->maxB = 0;
     // a rebuilt plan starts clean (callers of free_plan have synchronised the device)
     if (u->dev_err) (void)hipMemset(u->dev_err, 0, sizeof(int));
@@ -1178,6 +1180,30 @@ static int enqueue_step(fc_unet* u, int method, int B, bool cfg_on, float cfg, f
     return ode_rk4_final_launch(u->sc, u->y, u->k1, u->k2, u->k3, u->v2, n, cfg_on, cfg, s);
 }
 
+// The head of every fixed-grid call on the library stream (fc_unet_integrate, fc_unet_log_likelihood): the time grid's device buffer
+// (grows only when a longer grid than ever before arrives; captured graphs hold its address), the hand-over from the caller's stream,
+// and the call's grid, counters, state, class ids and mask copied into the library's own buffers.
+static int integrator_prologue(fc_unet* u, hipStream_t caller, hipStream_t s, const float* x_dev, size_t nbytes, const float* ts_host,
+                               int n_points, const int64_t* ids, int B, bool has_ids, const float* mask, int mask_mode) {
+    if (n_points + 1 > u->ts_cap) {
+        FC_HIP(hipStreamSynchronize(s));
+        if (u->ts_dev) dev_free(u->ts_dev);
+        u->ts_cap = n_points < 1024 ? 1024 : n_points + 1;   // + 1: the fused Euler tail reads one entry past the grid after the last step
+        FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->ts_dev), u->ts_cap * sizeof(float), "integrator.ts"));
+        drop_graphs(u);  // captured graphs hold the old ts pointer
+    }
+    // the library stream picks up after everything already queued on the caller's stream
+    FC_HIP(hipEventRecord(u->ev_in, caller));
+    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
+    // pageable source: the runtime stages it before returning, so ts_host may be freed by the caller right away
+    FC_HIP(hipMemcpyAsync(u->ts_dev, ts_host, n_points * sizeof(float), hipMemcpyHostToDevice, s));
+    FC_HIP(hipMemsetAsync(u->step, 0, 2 * sizeof(int), s));   // step counter | evaluation counter
+    FC_HIP(hipMemcpyAsync(u->y, x_dev, nbytes, hipMemcpyDeviceToDevice, s));
+    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
+    return FC_OK;
+}
+
 int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float dt_euler,
                       float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, void* stream) {
     if (!u || !x_dev || !ts_host || B < 1 || n_points < 1) return fail(FC_E_ARG, "fc_unet_integrate: bad argument");
@@ -1192,23 +1218,8 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
     const int n_steps = method == FC_METHOD_RK4 ? n_points - 1 : n_points;
     hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
     FC_HIP(hipSetDevice(u->device));
-    if (n_points + 1 > u->ts_cap) {  // grows only when a longer grid than ever before arrives
-        FC_HIP(hipStreamSynchronize(s));
-        if (u->ts_dev) dev_free(u->ts_dev);
-        u->ts_cap = n_points < 1024 ? 1024 : n_points + 1;   // + 1: the fused Euler tail reads one entry past the grid after the last step
-        FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->ts_dev), u->ts_cap * sizeof(float), "integrator.ts"));
-        drop_graphs(u);  // captured graphs hold the old ts pointer
-    }
     const size_t nbytes = (size_t)B * u->cfg.channels * H * W * sizeof(float);
-    // the library stream picks up after everything already queued on the caller's stream
-    FC_HIP(hipEventRecord(u->ev_in, caller));
-    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
-    // pageable source: the runtime stages it before returning, so ts_host may be freed by the caller right away
-    FC_HIP(hipMemcpyAsync(u->ts_dev, ts_host, n_points * sizeof(float), hipMemcpyHostToDevice, s));
-    FC_HIP(hipMemsetAsync(u->step, 0, 2 * sizeof(int), s));   // step counter | evaluation counter
-    FC_HIP(hipMemcpyAsync(u->y, x_dev, nbytes, hipMemcpyDeviceToDevice, s));
-    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
+    FC_TRY(integrator_prologue(u, caller, s, x_dev, nbytes, ts_host, n_points, ids, B, has_ids, mask, mask_mode));
 
     // Conditioning of every evaluation, once: the grid is known, so time MLP / class MLP / FiLM projections of all (evaluation, row)
     // pairs are three launches here instead of three at the head of each forward (44 us of every 1.6 ms step inside the replayed graph:
@@ -1287,6 +1298,87 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
     FC_HIP(hipEventRecord(u->ev_out, s));
     FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
     return FC_OK;
+}
+
+// fc_unet_train_reserve switches a handle to plans that keep every intermediate, for good.  A caller that needed the backward plan for
+// one call only (Unet.log_likelihood on a model that otherwise samples) asks which form the handle is in and puts the inference form back:
+// the plans are dropped and the next fc_unet_reserve builds the inference plan a handle that never trained would build.  Synchronises.
+int fc_unet_train_form(const fc_unet* u) { return (u && u->keep_all) ? 1 : 0; }
+
+int fc_unet_train_release(fc_unet* u) {
+    if (!u) return fail(FC_E_ARG, "fc_unet_train_release: null handle");
+    if (u->device < 0 || !u->keep_all) return FC_OK;
+    FC_HIP(hipSetDevice(u->device));
+    FC_HIP(hipDeviceSynchronize());
+    free_plan(u);
+    u->keep_all = false;
+    u->arena_touched(0);
+    return FC_OK;
+}
+
+// ---- likelihood / inversion on the RK4 grid ------------------------------------------------------------------------------------------
+// x from ts[0] to ts[n_points-1] with rk4_step on the caller's grid (log p needs it walked from t = 1 to t = 0), every evaluation a
+// training-mode forward followed by the backward plan's data-gradient chain with the probe as output cotangent (vjp_run), the stage
+// kernels of ode.hip carrying a[b] = integral of eps^T (dv/dx) eps dt.  The grid is known, so nothing is decided on the host: the call
+// returns with the whole loop queued.  Direct launches (4 (n_points - 1) forwards + chains); the arena ends up holding the last stage's
+// forward, which belongs to nobody: the serial moves and a later backward re-runs its own forward.
+int fc_unet_log_likelihood(fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
+                           const int64_t* ids, const float* mask, int mask_is_ones, const float* probe_dev, double* a_out_dev,
+                           double* logp_out_dev, void* stream) {
+    if (!u || !x_dev || !ts_host || !probe_dev || !a_out_dev || !logp_out_dev || B < 1) return fail(FC_E_ARG, "fc_unet_log_likelihood: null argument");
+    if (n_points < 2) return fail(FC_E_ARG, "fc_unet_log_likelihood: the time grid needs at least two points");
+    if (reinterpret_cast<uintptr_t>(probe_dev) & 15) return fail(FC_E_ARG, "fc_unet_log_likelihood: probe_dev must be 16-byte aligned (the kernels read it as float4)");
+    FC_TRY(check_ready(u, B, H, W));
+    if (!u->keep_all) return fail(FC_E_STATE, "fc_unet_log_likelihood: no backward plan for this shape; call fc_unet_train_reserve");
+    FC_TRY(vjp_check(u, B, H, W, "fc_unet_log_likelihood"));
+    FC_TRY(check_poison(u));
+    u->arena_touched(0);
+    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
+    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
+    const int m = u->cfg.channels * H * W;
+    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
+    FC_HIP(hipSetDevice(u->device));
+    if (!u->ll_g) {
+        void* p = nullptr;
+        FC_TRY(dev_alloc(&p, (size_t)u->maxB * m * sizeof(float), "integrator.likelihood")); u->int_allocs.push_back(p); u->ll_g = static_cast<float*>(p);
+        FC_TRY(dev_alloc(&p, (size_t)u->maxB * 3 * sizeof(double), "integrator.likelihood")); u->int_allocs.push_back(p); u->ll_d = static_cast<double*>(p);
+    }
+    const size_t nbytes = (size_t)B * m * sizeof(float);
+    FC_TRY(integrator_prologue(u, caller, s, x_dev, nbytes, ts_host, n_points, ids, B, has_ids, mask, mask_mode));
+    FC_HIP(hipMemsetAsync(a_out_dev, 0, (size_t)B * sizeof(double), s));
+    FwdCtx c = integrator_ctx(u, B, false, has_ids, mask_mode);
+    c.d_out = probe_dev; c.dx_out = u->ll_g;
+    FC_TRY(meet_enter(u, s));
+    auto eval = [&](const float* x) -> int {      // v2 = v(x, tvec), ll_g = (dv/dx)^T probe
+        c.x = x;
+        FC_TRY(run_plan(u->plan, c, s));
+        return vjp_run(u, c, s);
+    };
+    for (int i = 0; i + 1 < n_points; ++i) {
+        FC_TRY(ode_time_launch(u->step, u->ts_dev, t_scale, 1, u->sc, u->tvec, B, s));
+        FC_TRY(eval(u->y));                                                                                                              // k1, g1
+        FC_TRY(ode_ll_stage_launch(u->sc, u->y, u->xs, u->k1, u->v2, u->ll_g, probe_dev, u->ll_d, 0, B, m, 0, 1, t_scale, u->tvec, s));  // y + dt*k1/2, t+dt/2
+        FC_TRY(eval(u->xs));                                                                                                             // k2, g2
+        FC_TRY(ode_ll_stage_launch(u->sc, u->y, u->xs, u->k2, u->v2, u->ll_g, probe_dev, u->ll_d, 1, B, m, 0, 1, t_scale, u->tvec, s));  // y + dt*k2/2, t+dt/2
+        FC_TRY(eval(u->xs));                                                                                                             // k3, g3
+        FC_TRY(ode_ll_stage_launch(u->sc, u->y, u->xs, u->k3, u->v2, u->ll_g, probe_dev, u->ll_d, 2, B, m, 1, 2, t_scale, u->tvec, s));  // y + dt*k3, t+dt
+        FC_TRY(eval(u->xs));                                                                                                             // k4, g4
+        FC_TRY(ode_ll_final_launch(u->sc, u->y, u->k1, u->k2, u->k3, u->v2, u->ll_g, probe_dev, u->ll_d, a_out_dev, B, m, s));
+    }
+    FC_TRY(ode_ll_logp_launch(u->y, a_out_dev, logp_out_dev, B, m, s));
+    FC_HIP(hipMemcpyAsync(x_dev, u->y, nbytes, hipMemcpyDeviceToDevice, s));
+    FC_TRY(meet_leave(u, s));
+    FC_HIP(hipEventRecord(u->ev_out, s));
+    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
+    return FC_OK;
+}
+
+int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_dev, int batch, int64_t per_sample, void* stream) {
+    if (!probe_dev || !g_dev || !out_dev) return fail(FC_E_ARG, "fc_debug_probe_dot: null argument");
+    if ((reinterpret_cast<uintptr_t>(probe_dev) | reinterpret_cast<uintptr_t>(g_dev)) & 15)
+        return fail(FC_E_ARG, "fc_debug_probe_dot: inputs must be 16-byte aligned (read as float4)");
+    if (per_sample < 1 || per_sample > 0x7fffffff) return fail(FC_E_SHAPE, "fc_debug_probe_dot: bad element count");
+    return ode_ll_dot_launch(probe_dev, g_dev, out_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
 }
 
 // ---- adaptive RK45 ----------------------------------------------------------------------------------------------------------------

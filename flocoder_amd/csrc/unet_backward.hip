@@ -13,6 +13,10 @@
 // kernel on flipped, transposed weights (re-packed whenever the parameters change); a tensor with several consumers gets its
 // gradient contributions through the kernels' accumulate paths in a fixed order.  Parameter gradients land in the caller's flat
 // vector in the parameter table's layout, each written exactly once.
+//
+// Every entry carries a flag (Plan::op_param_only, set through PlanBuilder::param_only while it is pushed): its products are parameter
+// gradients, or something only parameter gradients read.  fc_unet_vjp_x / fc_unet_log_likelihood run the unflagged entries alone -- the
+// data-gradient chain towards d(x), the same kernels in the same order as the full backward runs them.
 #include <cstdlib>
 #include <memory>
 #include <set>
@@ -23,6 +27,15 @@
 using namespace fc;
 
 namespace fc {
+
+// sets PlanBuilder::param_only for a scope and puts the previous value back (regions nest)
+struct ParamOnly {
+    PlanBuilder* b; bool was;
+    ParamOnly(PlanBuilder* b_, bool on) : b(b_), was(b_->param_only) { b->param_only = on; }
+    ~ParamOnly() { b->param_only = was; }
+    ParamOnly(const ParamOnly&) = delete;
+    ParamOnly& operator=(const ParamOnly&) = delete;
+};
 
 struct BwdBuilder : PlanBuilder {
     fc_unet* u;
@@ -106,6 +119,7 @@ struct BwdBuilder : PlanBuilder {
             if (deferred) { *pending_mat.flag = true; fin_jobs.push_back(pending_mat.f); pinned.insert(pending_mat.y); }
             pending_mat = PendingMat();
         }
+        const ParamOnly flagged(this, true);
         push([a, wo, bo, own, own_floats, maxB, deferred](const FwdCtx& c, hipStream_t s) -> int {
             if (deferred && c.B == maxB) return FC_OK;      // runs in the table launch at the end of the plan
             WgradArgs b = a;
@@ -168,6 +182,7 @@ struct BwdBuilder : PlanBuilder {
         auto deferred = std::make_shared<bool>(false);      // set by the wgrad() that reads y, if and only if that entry joins the table launch
         if (for_wgrad) { pending_mat.f = f; pending_mat.f.B = B; pending_mat.flag = deferred; pending_mat.y = y.p; }
         const int maxB = B;
+        const ParamOnly flagged(this, for_wgrad || param_only);
         push([f, deferred, maxB](const FwdCtx& c, hipStream_t s) -> int {
             if (*deferred && c.B == maxB) return FC_OK;
             FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s);
@@ -431,6 +446,7 @@ int build_backward(fc_unet* u) {
     // parallel trainer can put that bucket on the wire while the rest of the chain runs (fc_unet_backward_parts) -- and once at the end.
     const float* te_film = fw.t_emb;
     auto emit_deferred = [&]() -> int {
+    const ParamOnly flagged(&b, true);      // everything below ends in the flat gradient vector
     // -- the activations only the deferred weight gradients read, recomputed in one launch --
     if (!b.fin_jobs.empty()) {
         b.scope = "wgrad";
@@ -555,7 +571,10 @@ int build_backward(fc_unet* u) {
         b.scope = "init_conv";
         Act xin = b.act(ch, H, W);
         float* xp = xin.p;
-        b.push([=](const FwdCtx& cx, hipStream_t s) { return nchw_to_nhwc_launch(cx.x, xp, cx.B, ch, HW, ch, cx.B, s); }, "nchw_to_nhwc");
+        {
+            const ParamOnly flagged(&b, true);       // the NHWC copy of x has one reader, init_conv's weight gradient
+            b.push([=](const FwdCtx& cx, hipStream_t s) { return nchw_to_nhwc_launch(cx.x, xp, cx.B, ch, HW, ch, cx.B, s); }, "nchw_to_nhwc");
+        }
         const Act g0 = b.grad_of(fw.x0);
         if (b.err) return b.err;
         const float* gx0 = g0.p;
@@ -565,11 +584,14 @@ int build_backward(fc_unet* u) {
         a.x0 = xin.p; a.C0 = ch; a.H = H; a.W = W; a.Hs = H; a.Ws = W; a.Cin = ch; a.Cout = dim; a.KS = 1; a.B = B;
         a.ws = b.ws; a.ws_floats = b.ws_floats;
         const int64_t wo = b.off("init_conv.weight"), bo = b.off("init_conv.bias");
+        {
+        const ParamOnly flagged(&b, true);
         b.push([=](const FwdCtx& cx, hipStream_t s) {
             WgradArgs q = a;
             q.B = cx.B; q.dy = cx.mask_fuse ? gxi : gx0; q.dw = cx.grads + wo; q.db = cx.grads + bo;
             return conv_wgrad_launch(q, s);
         }, "conv_wgrad", 2.0 * HW * (double)ch * dim);
+        }
         // d(x) = init_conv^T d(.) as an NHWC tensor, converted to the NCHW boundary layout on request (fc_unet_backward_ex)
         Act dxn = b.act(ch, H, W);
         float* wp = b.dmalloc((size_t)dim * ch);
@@ -601,6 +623,7 @@ int build_backward(fc_unet* u) {
     if (emit_deferred() != FC_OK) return b.err;
     // -- conditioning: every ResnetBlock.mlp (unet.py:79-82,90-92), then time_mlp / class_cond_mlp (unet.py:199-212,310-316) --
     {
+        const ParamOnly flagged(&b, true);       // d(t_emb) feeds the time / class MLPs' parameters only: x does not reach the conditioning vector
         b.scope = "resblock.mlp";
         const float* te = fw.t_emb;
         float* dss = b.dss;
@@ -651,9 +674,62 @@ int build_backward(fc_unet* u) {
     return pack_table_build(jobs, &u->dgrad_table);
 }
 
+// The data-gradient chain of the backward plan alone: the entries that are not parameter-only, in plan order, for the activations the
+// LAST training forward left in the arena.  `c` carries d_out, dx_out and the forward's mask / batch; c.grads stays null (no entry that
+// runs reads it).  Same kernels in the same order as the full backward, so d(x) has the same bits.
+int vjp_check(fc_unet* u, int B, int H, int W, const char* who) {
+    if (u->bwd.maxB < B || u->bwd.H != H || u->bwd.W != W || u->plan.maxB < B)
+        return fail(FC_E_STATE, std::string(who) + ": no backward plan for this shape; call fc_unet_train_reserve");
+    if (!u->loaded) return fail(FC_E_STATE, "unet: weights not loaded");
+    return FC_OK;
+}
+int vjp_run(fc_unet* u, const FwdCtx& c, hipStream_t s) {
+    if (u->dgrad_version != u->param_version) {     // data-gradient operands follow the parameters
+        FC_TRY(pack_table_launch(u->dgrad_table, s));
+        u->dgrad_version = u->param_version;
+    }
+    const Plan& pl = u->bwd;
+    for (size_t i = 0; i < pl.ops.size(); ++i)
+        if (!pl.op_param_only[i]) FC_TRY(pl.ops[i](c, s));
+    return FC_OK;
+}
+
 }  // namespace fc
 
 extern "C" {
+
+int fc_unet_vjp_x(fc_unet* u, const float* x, const float* time, const int64_t* ids, const float* mask, int mask_is_ones, const float* d_out,
+                  float* dx_out, int B, int H, int W, void* stream) {
+    if (!u || !x || !time || !d_out || !dx_out || B < 1) return fail(FC_E_ARG, "fc_unet_vjp_x: null argument");
+    FC_TRY(vjp_check(u, B, H, W, "fc_unet_vjp_x"));
+    if (u->arena_train_rows != B)
+        return fail(FC_E_STATE, "fc_unet_vjp_x: the activation arena does not hold a training forward of this batch (another forward, an "
+                                "integration, a profile run or a re-plan came in between); run fc_unet_forward after fc_unet_train_reserve again first");
+    FC_HIP(hipSetDevice(u->device));
+    FwdCtx c;
+    c.x = x; c.x_mod = B; c.time = time; c.ids = u->cfg.n_classes > 0 ? ids : nullptr; c.ids_mod = B; c.B = B;
+    c.mask = u->cfg.mask_cond ? mask : nullptr;
+    c.mask_fuse = (c.mask && !mask_is_ones) ? 1 : 0;
+    c.d_out = d_out; c.dx_out = dx_out;
+    return vjp_run(u, c, static_cast<hipStream_t>(stream));
+}
+
+int fc_unet_vjp_launches(const fc_unet* u) {
+    int n = 0;
+    if (u) for (char f : u->bwd.op_param_only) n += f ? 0 : 1;
+    return n;
+}
+
+int fc_unet_vjp_op_info(const fc_unet* u, int i, const char** kernel, const char** module) {
+    if (u && i >= 0)
+        for (size_t j = 0; j < u->bwd.ops.size(); ++j)
+            if (!u->bwd.op_param_only[j] && i-- == 0) {
+                if (kernel) *kernel = u->bwd.op_kernel[j].c_str();
+                if (module) *module = u->bwd.op_what[j].c_str();
+                return FC_OK;
+            }
+    return fail(FC_E_ARG, "fc_unet_vjp_op_info: index out of range");
+}
 
 int fc_unet_train_reserve(fc_unet* u, int max_batch, int height, int width) {
     if (!u) return fail(FC_E_ARG, "fc_unet_train_reserve: null handle");

@@ -46,6 +46,10 @@ struct fc_unet : fc::ParamStore {
     // with the longest t_eval seen, lives as long as the handle
     fc::Rk45Eval* rk_ev = nullptr;
     int rk_ev_cap = 0;                       // times
+    // likelihood (fc_unet_log_likelihood): g = (dv/dx)^T eps of the running stage and the per-sample stage sums d1..d3 of the running
+    // interval, allocated by the first call (in int_allocs, released with the plan)
+    float* ll_g = nullptr;
+    double* ll_d = nullptr;
 
     // Fused Block tails whose workgroups wait for each other (conv_dev.h) need the device to themselves.  `shared` = the caller said the
     // device is shared with other streams / processes (fc_unet_set_shared): plans are then built without such launches.  A wait that
@@ -81,3 +85,9 @@ struct fc_unet : fc::ParamStore {
     void arena_touched(int train_rows) { ++arena_serial; arena_train_rows = train_rows; }
 
 };
+
+namespace fc {
+// unet_backward.hip: the backward plan's data-gradient chain alone (fc_unet_vjp_x, fc_unet_log_likelihood)
+int vjp_check(fc_unet* u, int B, int H, int W, const char* who);
+int vjp_run(fc_unet* u, const FwdCtx& c, hipStream_t s);
+}  // namespace fc

@@ -7,7 +7,8 @@
   statistics and the distance are computed here in float64; the feature network is a LOCAL TorchScript file (``inception=`` or
   ``$FLOCODER_FID_INCEPTION``) mapping uint8 images [B,3,H,W] to features [B,F] -- torchmetrics downloads its weights, this build
   never touches the network and raises FileNotFoundError without one;
-* ``compute_sample_metrics`` (metrics.py:493-555) -- the same dictionary of numbers.
+* ``compute_sample_metrics`` (metrics.py:493-555) -- the same dictionary of numbers;
+* ``bits_per_dim`` -- the flow's log-likelihood (``sampling.log_likelihood``) as bits per latent dimension (no upstream counterpart).
 """
 import ctypes as C
 import os
@@ -56,6 +57,14 @@ def rel_l2(a, b):
     """||a-b|| / ||b|| in fp64 -- the parity gate of BASELINE.md section 4."""
     a, b = a.double().flatten(), b.double().flatten()
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+def bits_per_dim(logp, numel):
+    """Bits per dimension of ``sampling.log_likelihood``'s ``logp`` (natural log, per sample) over ``numel`` = C*H*W unknowns:
+    ``-logp / (numel ln 2)``.  For latents of a codec (SD-VAE, VQVAE) these are bits per LATENT dimension: the codec's own change of
+    volume is not in it, so the figure compares flows over the same latent space, not models of the pixels."""
+    import math
+    return -logp / (float(numel) * math.log(2.0))
 
 
 def sample_stats(pred_latents, target_latents, decoded_pred, decoded_target):

@@ -130,6 +130,137 @@ def euler_sampler(model, shape, sample_N, device=None, cond=None, source=None, e
     return x, sample_N
 
 
+def _reverse_grid(n_steps, dtype=torch.float32):
+    if int(n_steps) < 2:
+        raise ValueError(f"n_steps={n_steps}: the grid needs at least two points (one interval)")
+    return rk4_time_grid(int(n_steps), dtype=dtype).flip(0)
+
+
+def _cond_dict(cond):
+    if cond is not None and not isinstance(cond, dict):
+        cond = {'class_cond': cond}
+    return cond
+
+
+@torch.no_grad()
+def invert_latents(model, latents, n_steps=50, cond=None):
+    """Data -> noise: the probability-flow ODE from t = 1 back to t = 0 on ``rk4_time_grid(n_steps)`` REVERSED, with the RK4 step and
+    without guidance -- the ``z`` that ``generate_latents_rk4(..., source=z, cfg_strength=0)`` maps back to ``latents`` up to the
+    discretisation error of the two solves.  ``cond`` as the samplers (a cond dict, or class ids).  Returns ``(z, nfe)`` with nfe the
+    true number of velocity evaluations, ``4 (n_steps - 1)`` -- not ``generate_latents_rk4``'s ``n_steps * 4`` bookkeeping.
+    A ``flocoder_amd.Unet`` runs the captured inference path (``Unet.integrate`` takes a grid in either direction); any other callable
+    goes through ``rk4_step`` on the latents' device."""
+    cond = _cond_dict(cond)
+    ts = _reverse_grid(n_steps, torch.float32 if isinstance(model, Unet) else latents.dtype)
+    nfe = 4 * (len(ts) - 1)
+    if isinstance(model, Unet):
+        if not latents.is_cuda:
+            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only")
+        x = latents.to(dtype=torch.float32).contiguous().clone()
+        cls = cond.get('class_cond') if cond else None
+        mask, ones = _mask_flags(cond)
+        model.integrate("rk4", x, ts, class_ids=cls, cfg_strength=0.0, mask=mask, mask_is_ones=ones)
+        return x, nfe
+    x = latents
+    ts = ts.to(x.device)
+    t_vec_template = torch.zeros(x.shape[0], device=x.device, dtype=x.dtype)
+    v_func = partial(v_func_cfg, model, cond, 0.0, t_vec_template)
+    for i in range(len(ts) - 1):
+        x = rk4_step(v_func, x, ts[i], ts[i + 1] - ts[i])
+    return x, nfe
+
+
+def _make_probe(probe, latents, generator):
+    if torch.is_tensor(probe):
+        if probe.shape != latents.shape:
+            raise ValueError(f"probe must have the shape of latents {tuple(latents.shape)}, got {tuple(probe.shape)}")
+        return probe.to(device=latents.device, dtype=latents.dtype).contiguous()
+    if probe not in ("rademacher", "gaussian"):
+        raise ValueError(f"probe={probe!r}: 'rademacher', 'gaussian' or a tensor of the latents' shape")
+    gdev = generator.device if generator is not None else latents.device
+    if probe == "gaussian":
+        e = torch.randn(latents.shape, generator=generator, device=gdev, dtype=latents.dtype)
+    else:
+        e = torch.randint(0, 2, latents.shape, generator=generator, device=gdev).to(latents.dtype) * 2 - 1
+    return e.to(latents.device).contiguous()
+
+
+def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", generator=None, cfg_strength=None):
+    """log p_1(latents) under the flow: the change of variables along the probability-flow ODE walked from t = 1 to t = 0 on
+    ``rk4_time_grid(n_steps)`` reversed, with Hutchinson's estimate of the divergence.  Interval by interval (dt < 0), every RK4 stage j
+    gives ``v_j = model(x_j, 999 t_j, cond)`` and ``d_j[b] = sum_i eps[b,i] ((dv_j/dx_j)^T eps)[b,i]`` (one VJP of the same forward);
+
+        x <- x + (dt/6)(v1 + 2 v2 + 2 v3 + v4)              a <- a + (dt/6)(d1 + 2 d2 + 2 d3 + d4)      (a = 0 at t = 1)
+
+    and with ``z`` = x at t = 0:  ``logp[b] = -|z_b|^2 / 2 - (D/2) ln 2pi + a[b]``, D = C*H*W (a is the integral of div v from 1 to 0,
+    hence the plus sign).  Returns ``(logp, z, nfe)``: ``logp`` fp64 ``[B]`` on the latents' device, ``z`` like ``latents``, nfe = the true
+    number of velocity evaluations ``4 (n_steps - 1)`` (not ``generate_latents_rk4``'s ``n_steps * 4`` bookkeeping).
+    ``metrics.bits_per_dim(logp, D)`` turns it into bits per (latent) dimension.
+
+    ``probe``: ``"rademacher"`` (default: +-1 entries, exact for a diagonal Jacobian), ``"gaussian"``, or a tensor of the latents' shape;
+    ONE probe per call, the same for all stages.  The trajectory does not depend on it, so the mean over K probes is K calls averaged.
+    ``generator`` seeds the drawn probes.  ``cond``: ``class_cond`` gives log p(x | class); ``mask_cond`` is carried as data, as the
+    samplers do.  Classifier-free guidance is refused (``cfg_strength`` other than 0 / None raises ValueError): the guided field is not
+    the flow of a density the model defines.
+
+    A ``flocoder_amd.Unet`` on the GPU runs the whole loop in the library (``Unet.log_likelihood``: training-mode forward, the backward
+    plan's data-gradient chain and one small kernel per evaluation; x in fp32, d_j and a in fp64); on the CPU it raises like the other
+    integrators.  Any other callable takes the torch path below in the dtype of ``latents`` (fp64 latents give an fp64 solve; d_j and a
+    are fp64 either way).  The model's ``training`` flag, its parameters' ``requires_grad`` and ``.grad`` are left as found, and so is the
+    form of a ``flocoder_amd.Unet``'s launch plans: a model that samples (inference-form plans) gets them back before the call returns, so a
+    sampler call after it gives the bits of a model that never computed a likelihood (``Unet.log_likelihood``'s ``restore_plan``; it
+    costs a device synchronisation and two plan builds per call -- for many calls in a row use ``Unet.log_likelihood(...,
+    restore_plan=False)`` and ``Unet.release_training_plan()``)."""
+    if cfg_strength:
+        raise ValueError("log_likelihood takes no classifier-free guidance: the guided field is not the flow of a density the model defines")
+    cond = _cond_dict(cond)
+    unet = isinstance(model, Unet)
+    ts = _reverse_grid(n_steps, torch.float32 if unet else latents.dtype)
+    nfe = 4 * (len(ts) - 1)
+    if unet and not latents.is_cuda:
+        raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+    eps = _make_probe(probe, latents.float() if unet else latents, generator)
+    if unet:
+        x = latents.to(dtype=torch.float32).contiguous().clone()
+        cls = cond.get('class_cond') if cond else None
+        mask, ones = _mask_flags(cond)
+        _, logp = model.log_likelihood(x, ts, eps, class_ids=cls, mask=mask, mask_is_ones=ones)
+        return logp, x, nfe
+    logp, z, _ = _log_likelihood_torch(model, latents, ts.to(latents.device), cond, eps)
+    return logp, z, nfe
+
+
+def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999):
+    """The loop of ``log_likelihood`` with torch ops: ``torch.autograd.grad(v, x, eps)`` per stage.  Returns (logp, z, a)."""
+    import math
+    bsz = latents.shape[0]
+    e64 = eps.double()
+
+    def stage(x, t):
+        with torch.enable_grad():
+            xr = x.detach().requires_grad_(True)
+            t_vec = torch.full((bsz,), float(t), device=x.device, dtype=x.dtype)
+            v = model(xr, t_vec * t_scale, cond=cond)
+            g, = torch.autograd.grad(v, xr, eps)
+        return v.detach(), (e64 * g.double()).flatten(1).sum(dim=1)
+
+    x = latents.detach()
+    a = torch.zeros(bsz, dtype=torch.float64, device=x.device)
+    for i in range(len(ts) - 1):
+        t, dt = ts[i], ts[i + 1] - ts[i]
+        tpdto2 = t + dt / 2
+        k1, d1 = stage(x, t)
+        k2, d2 = stage(x + dt * k1 / 2, tpdto2)
+        k3, d3 = stage(x + dt * k2 / 2, tpdto2)
+        k4, d4 = stage(x + dt * k3, t + dt)
+        x = x + (dt / 6) * (k1 + 2 * k2 + 2 * k3 + k4)
+        a = a + (dt.double() / 6) * (d1 + 2 * d2 + 2 * d3 + d4)
+    z = x
+    D = z[0].numel()
+    logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
+    return logp, z, a
+
+
 def _validate_tol(rtol, atol):
     """scipy/integrate/_ivp/common.py validate_tol for scalar tolerances."""
     eps100 = 100 * float(torch.finfo(torch.float64).eps)

@@ -329,6 +329,27 @@ class Unet(NativeModule):
                                                B.current_stream(dev)))
         return grads, dx, dm
 
+    def vjp_x(self, x, time, cls, d_out, mask=None) -> torch.Tensor:
+        """d(x) of the LAST training forward (same x / time / class ids / mask) for d(out) = ``d_out``, and nothing else
+        (``fc_unet_vjp_x``): the backward plan's data-gradient chain without any launch that only serves parameter gradients.  The bits
+        are those of ``backward_native(..., want_dx=True)[1]``; no flat gradient vector is touched."""
+        dev = x.device
+        bsz, _, h, w = x.shape
+        ones = int(torch.allclose(mask, torch.ones_like(mask))) if mask is not None else 0
+        dx = torch.empty_like(x)
+        B.check(B.lib().fc_unet_vjp_x(self._native(dev), B.ptr(x), B.ptr(time), B.ptr(cls), B.ptr(mask), ones, B.ptr(d_out.contiguous()),
+                                      B.ptr(dx), bsz, h, w, B.current_stream(dev)))
+        return dx
+
+    def vjp_forms(self) -> List[Tuple[str, str]]:
+        """(kernel family, module) of every backward-plan entry ``vjp_x`` runs (``fc_unet_vjp_op_info``; tests, tools)."""
+        out = []
+        for i in range(B.lib().fc_unet_vjp_launches(self._handle) if self._handle else 0):
+            k, m = C.c_char_p(), C.c_char_p()
+            B.check(B.lib().fc_unet_vjp_op_info(self._handle, i, C.byref(k), C.byref(m)))
+            out.append((k.value.decode(), m.value.decode()))
+        return out
+
     def grad_views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         return {name: flat[off:off + math.prod(shape)].view(shape) for name, shape, off in self._table}
 
@@ -395,6 +416,71 @@ class Unet(NativeModule):
         if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
             B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
         return x
+
+    def log_likelihood(self, x: torch.Tensor, ts: torch.Tensor, probe: torch.Tensor, *, t_scale: float = 999.0,
+                       class_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, mask_is_ones: bool = False,
+                       check: bool = True, restore_plan: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``fc_unet_log_likelihood``: integrate ``x`` in place along the fp32 grid ``ts`` (the sampler's grid reversed: data -> noise)
+        with the RK4 step, carrying the Hutchinson divergence estimate for ``probe`` (x's shape) next to it.  Returns ``(a, logp)``, fp64
+        ``[B]`` on x's device: the integrated divergence and ``-|z|^2/2 - (CHW/2) ln 2pi + a`` with ``z`` = the ``x`` left behind.  Argument
+        checks and ``check`` as in ``integrate``; no guidance.
+
+        The loop needs the backward plan, and ``fc_unet_train_reserve`` switches a handle to the training form of its plans (every
+        intermediate kept, none of the fused inference launches) for good.  A model that was NOT in that form when the call came gets its
+        inference form back before the call returns (``restore_plan``, default): later sampler calls run the plan, and give the bits,
+        of a model that never computed a likelihood.  That costs a device synchronisation and two plan builds per call; a caller who makes
+        many likelihood calls in a row passes ``restore_plan=False`` and calls ``release_training_plan()`` once at the end.  A model
+        that trains (it already is in the training form) is left as it is."""
+        if not x.is_cuda:
+            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+        dev = x.device
+        bsz, ch, h, w = x.shape
+        if not x.is_contiguous() or x.dtype != torch.float32:
+            raise ValueError("x must be a contiguous fp32 tensor (it is updated in place)")
+        if probe.shape != x.shape or probe.device != dev or probe.dtype != torch.float32 or not probe.is_contiguous():
+            raise ValueError("probe must be a contiguous fp32 tensor of x's shape on x's device")
+        if probe.data_ptr() % 16:
+            probe = probe.clone()                       # a view at an odd storage offset: the kernels read the probe as float4
+        if ts.numel() < 2:
+            raise ValueError("the time grid needs at least two points")
+        if class_ids is not None and not self.class_condition:
+            class_ids = None
+        if class_ids is not None:
+            class_ids = class_ids.to(device=dev, dtype=torch.int64).contiguous()
+            if class_ids.shape != (bsz,):
+                raise ValueError("class ids must have shape [batch]")
+            self.check_class_ids(class_ids)
+        if mask is not None and not self._cfg.mask_cond:
+            mask = None
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+            if mask.shape != x.shape:
+                raise ValueError("mask_cond must have the shape of x")
+        hnd = self._native(dev)
+        lib = B.lib()
+        was_training_form = bool(lib.fc_unet_train_form(hnd))
+        rows0, h0, w0 = C.c_int(0), C.c_int(0), C.c_int(0)
+        B.check(lib.fc_unet_reserved(hnd, C.byref(rows0), C.byref(h0), C.byref(w0)))
+        B.check(lib.fc_unet_train_reserve(hnd, bsz, h, w))
+        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
+        a = torch.empty(bsz, dtype=torch.float64, device=dev)
+        logp = torch.empty(bsz, dtype=torch.float64, device=dev)
+        B.check(B.lib().fc_unet_log_likelihood(hnd, B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)),
+                                               ts_host.numel(), float(t_scale), B.ptr(class_ids), B.ptr(mask), int(mask_is_ones),
+                                               B.ptr(probe), B.ptr(a), B.ptr(logp), B.current_stream(dev)))
+        if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
+            B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
+        if restore_plan and not was_training_form:
+            self.release_training_plan()
+            if rows0.value > 0:                         # the reservation the caller had, in the form it had
+                B.check(lib.fc_unet_reserve(hnd, rows0.value, h0.value, w0.value))
+        return a, logp
+
+    def release_training_plan(self) -> None:
+        """Put the handle's plans back into the inference form (``fc_unet_train_release``): waits for the device, drops the training-form
+        plans, the backward plan and the captured graphs; the next call builds what a model that never trained builds."""
+        if self._handle:
+            B.check(B.lib().fc_unet_train_release(self._handle))
 
     def integrate_rk45(self, x: torch.Tensor, t0: float, t1: float, *, rtol: float, atol: float, t_scale: float = 999.0,
                        class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,

@@ -203,7 +203,22 @@ int fc_unet_profile_ops(fc_unet* u, int batch, int repeats, float* ms_out, int n
  * precision; a host that wants the exact fp32 values its own framework produces may override it. */
 int fc_unet_set_time_freqs(fc_unet* u, const float* freqs_host, int n);
 
+/* Log-likelihood of x_inout_dev [B,C,H,W] under the flow, with a Hutchinson estimate of the divergence: the classic RK4 step along
+ * ts_host (n_points >= 2 entries; the caller passes the sampler's grid reversed, t = 1 -> 0), every stage a training-mode forward plus
+ * fc_unet_vjp_x's chain with probe_dev [B,C,H,W] as output cotangent:
+ *     x <- x + (dt/6)(v1 + 2 v2 + 2 v3 + v4)                         fp32, the arithmetic of fc_unet_integrate(FC_METHOD_RK4)
+ *     a[b] <- a[b] + (double(dt)/6)(d1 + 2 d2 + 2 d3 + d4)[b]        d_j[b] = sum_i probe[b,i] ((dv_j/dx_j)^T probe)[b,i], fp64, fixed order
+ * On return (queued on `stream`, asynchronous like fc_unet_integrate) x_inout_dev is the state at ts[n_points-1] (the noise z),
+ * a_out_dev [B] the integrated divergence and logp_out_dev [B] = -|z_b|^2/2 - (CHW/2) ln 2pi + a[b].  No classifier-free guidance (the
+ * guided field is not the flow of a density the model defines).  probe_dev must be 16-byte aligned.  Needs fc_unet_train_reserve for this shape; writes the activation
+ * arena (fc_unet_arena_serial moves; a backward must re-run its forward). */
+int fc_unet_log_likelihood(fc_unet* u, float* x_inout_dev, int batch, int height, int width, const float* ts_host, int n_points,
+                           float t_scale, const int64_t* class_ids_dev, const float* mask_dev, int mask_is_ones, const float* probe_dev,
+                           double* a_out_dev, double* logp_out_dev, void* stream);
+
 /* ---- debug / test hooks: not part of the drop-in surface --------------------------------------- */
+/* out_dev[b] (double) = sum_i probe_dev[b,i] g_dev[b,i] over per_sample elements: the likelihood stage kernels' reduction alone. */
+int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_dev, int batch, int64_t per_sample, void* stream);
 /* Device pointer + NHWC extent of an internal activation of the current plan, by reference module name
  * ("downs.0.0", "downs.0.2", "mid_attn", "ups.3.3", ...). */
 int fc_unet_debug_tensor(const fc_unet* u, const char* name, const float** ptr, int* channels, int* height, int* width);
@@ -264,6 +279,21 @@ int fc_unet_grad_buckets(const fc_unet* u, int64_t* split_offset);
  * reference module it serves -- fc_unet_plan_launches / fc_unet_op_info for the backward plan. */
 int fc_unet_backward_launches(const fc_unet* u);
 int fc_unet_backward_op_info(const fc_unet* u, int i, const char** kernel, const char** module);
+/* 1 when the handle's plans are in the training form fc_unet_train_reserve switches to (they keep every intermediate for the backward; the
+ * fused inference launches are not used), else 0.  fc_unet_train_release puts the inference form back: plans and captured graphs are
+ * dropped (synchronises the device) and the next fc_unet_reserve builds what a handle that never trained builds, with the same bits. */
+int fc_unet_train_form(const fc_unet* u);
+int fc_unet_train_release(fc_unet* u);
+/* The input gradient alone: d(x) of the LAST training forward for d(out) = d_out_dev, written to dx_out_dev [B,C,H,W].  Same
+ * preconditions and FC_E_STATE rule as fc_unet_backward_ex.  Runs the data-gradient chain of the backward plan and nothing whose only
+ * products are parameter gradients (weight-gradient launches and tables, their reductions, the activations recomputed for them, the
+ * norm / FiLM parameter gradients, the time / class MLP backward): the same kernels in the same order as the full backward, so
+ * dx_out_dev has the bits fc_unet_backward_ex would give.  No flat gradient vector is read or written. */
+int fc_unet_vjp_x(fc_unet* u, const float* x_dev, const float* time_dev, const int64_t* class_ids_dev, const float* mask_dev,
+                  int mask_is_ones, const float* d_out_dev, float* dx_out_dev, int batch, int height, int width, void* stream);
+/* Test hooks: the entries of the backward plan fc_unet_vjp_x runs (count; entry i's kernel family and module), as the pair above. */
+int fc_unet_vjp_launches(const fc_unet* u);
+int fc_unet_vjp_op_info(const fc_unet* u, int i, const char** kernel, const char** module);
 /* The backward reads the activations the last training forward left in the handle's single arena.  Every call that writes the arena
  * (fc_unet_forward, fc_unet_integrate, fc_unet_profile_ops, a re-plan by fc_unet_reserve) moves this counter; a caller that keeps
  * several forwards in flight (autograd with two micro-batches, gradient accumulation) compares the value it saw after ITS forward
