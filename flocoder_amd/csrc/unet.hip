@@ -9,12 +9,10 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -355,22 +353,12 @@ struct Builder : PlanBuilder {
     }
 };
 
-// every cached graph: they bake the addresses of the buffers they were captured with
-static void drop_graphs(fc_unet* u) {
-    for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
-    u->graphs.clear();
-}
-
 static void free_plan(fc_unet* u) {
-    drop_graphs(u);
+    u->ig.release_plan();                   // the captured graphs first: they bake the addresses of the buffers they were captured with
     u->plan.release();
     u->bwd.release();                       // the backward plan points into the forward arena
     u->dgrad_packs.clear();
     u->dgrad_table.release();
-    for (void* p : u->int_allocs) dev_free(p);
-    u->int_allocs.clear();
-    u->rk_y = u->rk_ynew = u->rk_part = nullptr; u->rk_k = Rk45K{}; u->rk_st = nullptr; u->rk_sum = nullptr;   // (were in int_allocs)
-    u->ll_g = nullptr; u->ll_d = nullptr;
     u->maxB = 0;
     // a rebuilt plan starts clean (callers of free_plan have synchronised the device)
     if (u->dev_err) (void)hipMemset(u->dev_err, 0, sizeof(int));
@@ -801,27 +789,6 @@ static int build_plan(fc_unet* u, Plan* pl, int maxB, int H, int W) {
     return FC_OK;
 }
 
-// integrator state for `rows` U-Net rows (library-owned so captured graphs never see caller pointers)
-static int alloc_integrator(fc_unet* u, int rows, int H, int W) {
-    const size_t nstate = (size_t)rows * u->cfg.channels * H * W;
-    auto get = [&](size_t floats, float** out) -> int {
-        void* p = nullptr;
-        FC_TRY(dev_alloc(&p, (floats ? floats : 1) * sizeof(float), "integrator"));
-        u->int_allocs.push_back(p);
-        *out = static_cast<float*>(p);
-        return FC_OK;
-    };
-    float* tmp = nullptr;
-    FC_TRY(get(nstate, &u->y)); FC_TRY(get(nstate, &u->xs));
-    FC_TRY(get(nstate, &u->k1)); FC_TRY(get(nstate, &u->k2)); FC_TRY(get(nstate, &u->k3));
-    FC_TRY(get(nstate, &u->v2)); FC_TRY(get(nstate, &u->mask_own));
-    FC_TRY(get(rows, &u->tvec));
-    FC_TRY(get(4, &u->sc));
-    FC_TRY(get(4, &tmp)); u->step = reinterpret_cast<int*>(tmp);
-    FC_TRY(get(2 * (size_t)rows, &tmp)); u->ids_own = reinterpret_cast<int64_t*>(tmp);
-    return FC_OK;
-}
-
 // ---- process-wide guard of the meeting launches ------------------------------------------------------------------------------
 // A launch whose workgroups wait for each other is only safe while no OTHER such launch can hold part of the CUs: two of them, each
 // half resident, would wait for workgroups that cannot start (bounded by the spin limit, then NaN + error -- never a hang, never silent).
@@ -834,14 +801,14 @@ static MeetGuard& meet_guard(int device) { return g_meet[device & 15]; }
 
 static int plan_meets(const fc_unet* u) { return u->plan.n_meet; }
 
-static int meet_enter(fc_unet* u, hipStream_t s) {
+int meet_enter(fc_unet* u, hipStream_t s) {
     if (!plan_meets(u)) return FC_OK;
     MeetGuard& g = meet_guard(u->device);
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.ev && g.s != s && hipEventQuery(g.ev) != hipSuccess) FC_HIP(hipStreamWaitEvent(s, g.ev, 0));
     return FC_OK;
 }
-static int meet_leave(fc_unet* u, hipStream_t s) {
+int meet_leave(fc_unet* u, hipStream_t s) {
     if (!plan_meets(u)) return FC_OK;
     MeetGuard& g = meet_guard(u->device);
     std::lock_guard<std::mutex> lk(g.mu);
@@ -857,12 +824,21 @@ static void meet_forget(const fc_unet* u) {
     if (g.owner == u) { g.ev = nullptr; g.s = nullptr; g.owner = nullptr; }
 }
 // refuse to go on after a timed-out meeting: the arena holds NaN-poisoned activations and whatever was returned since is invalid
-static int check_poison(fc_unet* u) {
+int check_poison(fc_unet* u) {
     if (u->host_err && *u->host_err) u->tail_failed = true;
     if (u->tail_failed)
         return fail(FC_E_STATE, "unet: a fused Block tail timed out waiting for its sample group (the GPU was shared with other work while "
                                 "the exclusive plan ran); the affected samples are NaN.  Rebuild the plan -- fc_unet_set_shared(handle, 1) "
                                 "selects the plan without cross-workgroup waits");
+    return FC_OK;
+}
+
+int check_ready(const fc_unet* u, int rows, int H, int W) {
+    if (!u) return fail(FC_E_ARG, "null fc_unet");
+    if (u->device < 0) return fail(FC_E_STATE, "unet: created with device < 0 (description only)");
+    if (!u->loaded) return fail(FC_E_STATE, "unet: weights not loaded (fc_unet_load_params)");
+    if (u->maxB < rows || u->H != H || u->W != W)
+        return fail(FC_E_STATE, "unet: no plan for this shape; call fc_unet_reserve(rows >= " + std::to_string(rows) + ")");
     return FC_OK;
 }
 
@@ -911,9 +887,9 @@ int fc_unet_create(const fc_unet_config* cfg, int device, fc_unet** out) {
     for (int k = 0; k < half; ++k) fr[k] = (float)std::exp((double)((float)k * (float)-lf));
     FC_HIP(hipMalloc(reinterpret_cast<void**>(&u->freqs), half * sizeof(float)));
     FC_HIP(hipMemcpy(u->freqs, fr.data(), half * sizeof(float), hipMemcpyHostToDevice));
-    FC_HIP(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
-    FC_HIP(hipEventCreateWithFlags(&u->ev_in, hipEventDisableTiming));
-    FC_HIP(hipEventCreateWithFlags(&u->ev_out, hipEventDisableTiming));
+    FC_HIP(hipStreamCreateWithFlags(&u->ig.stream, hipStreamNonBlocking));
+    FC_HIP(hipEventCreateWithFlags(&u->ig.ev_in, hipEventDisableTiming));
+    FC_HIP(hipEventCreateWithFlags(&u->ig.ev_out, hipEventDisableTiming));
     FC_HIP(hipEventCreateWithFlags(&u->ev_meet, hipEventDisableTiming));
     FC_HIP(hipMalloc(reinterpret_cast<void**>(&u->dev_err), sizeof(int)));
     FC_HIP(hipMemset(u->dev_err, 0, sizeof(int)));
@@ -928,20 +904,13 @@ void fc_unet_destroy(fc_unet* u) {
     (void)hipSetDevice(u->device);
     (void)hipDeviceSynchronize();
     free_plan(u);
-    if (u->ts_dev) dev_free(u->ts_dev);
-    if (u->rk_ev) dev_free(u->rk_ev);
-    if (u->pre) dev_free(u->pre);
+    u->ig.release_handle();
     u->free_device();
     if (u->freqs) (void)hipFree(u->freqs);
-    if (u->stream) (void)hipStreamDestroy(u->stream);
-    if (u->ev_in) (void)hipEventDestroy(u->ev_in);
-    if (u->ev_out) (void)hipEventDestroy(u->ev_out);
     meet_forget(u);
     if (u->ev_meet) (void)hipEventDestroy(u->ev_meet);
     if (u->dev_err) (void)hipFree(u->dev_err);
     if (u->host_err) (void)hipHostFree(const_cast<int*>(u->host_err));
-    if (u->rk_host) (void)hipHostFree(u->rk_host);
-    if (u->ev_rk) (void)hipEventDestroy(u->ev_rk);
     delete u;
 }
 
@@ -988,15 +957,6 @@ int fc_unet_reserve(fc_unet* u, int max_batch, int height, int width) {
     if (r == FC_OK) r = alloc_integrator(u, max_batch, height, width);
     if (r != FC_OK) { free_plan(u); return r; }
     u->maxB = max_batch; u->H = height; u->W = width;
-    return FC_OK;
-}
-
-static int check_ready(const fc_unet* u, int rows, int H, int W) {
-    if (!u) return fail(FC_E_ARG, "null fc_unet");
-    if (u->device < 0) return fail(FC_E_STATE, "unet: created with device < 0 (description only)");
-    if (!u->loaded) return fail(FC_E_STATE, "unet: weights not loaded (fc_unet_load_params)");
-    if (u->maxB < rows || u->H != H || u->W != W)
-        return fail(FC_E_STATE, "unet: no plan for this shape; call fc_unet_reserve(rows >= " + std::to_string(rows) + ")");
     return FC_OK;
 }
 
@@ -1058,8 +1018,8 @@ int fc_unet_profile_ops(fc_unet* u, int batch, int repeats, float* ms_out, int n
     u->arena_touched(0);
     hipStream_t s = static_cast<hipStream_t>(stream);
     FwdCtx c;
-    c.x = u->y; c.x_mod = batch; c.time = u->tvec; c.ids = nullptr; c.ids_mod = batch; c.out = u->v2; c.B = batch;
-    FC_HIP(hipMemsetAsync(u->tvec, 0, batch * sizeof(float), s));
+    c.x = u->ig.y; c.x_mod = batch; c.time = u->ig.tvec; c.ids = nullptr; c.ids_mod = batch; c.out = u->ig.v2; c.B = batch;
+    FC_HIP(hipMemsetAsync(u->ig.tvec, 0, batch * sizeof(float), s));
     auto stamp = [&](int i) -> int {            // the same launch once more, writing its in-kernel phase stamps
         if (i != g_stamp_op || !g_stamp_op_buf) return FC_OK;
         conv_set_stamp_buffer(g_stamp_op_buf);
@@ -1105,201 +1065,6 @@ int fc_unet_fused_tail_errors(const fc_unet* u, int* count) {
 int fc_unet_plan_launches(const fc_unet* u) { return u ? (int)u->plan.ops.size() : 0; }
 double fc_unet_flops_per_sample(const fc_unet* u) { return u ? u->plan.flops : 0.0; }
 
-// -------------------------------------------------------------------------------- integrator
-static uint32_t fbits(float f) { uint32_t v; std::memcpy(&v, &f, 4); return v; }
-
-// FLOCODER_AMD_NO_GRAPH: every integrator enqueues its launches directly instead of capturing and replaying graphs
-static bool no_graph() {
-    static const bool v = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
-    return v;
-}
-
-// the graph cached under `key`; on first use it is captured from `enqueue` on `s` and instantiated
-static int cached_graph(fc_unet* u, const decltype(fc_unet::graphs)::key_type& key, hipStream_t s, const std::function<int()>& enqueue,
-                        hipGraphExec_t* out) {
-    auto it = u->graphs.find(key);
-    if (it == u->graphs.end()) {
-        hipGraph_t graph = nullptr;
-        FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int r = enqueue();
-        const hipError_t e = hipStreamEndCapture(s, &graph);
-        if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
-        if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        hipGraphExec_t exec = nullptr;
-        FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        FC_HIP(hipGraphDestroy(graph));
-        it = u->graphs.emplace(key, exec).first;
-    }
-    *out = it->second;
-    return FC_OK;
-}
-
-// the forward of one integrator evaluation (the caller sets its input x): B rows and, with CFG, their unguided twins B..2B-1, the
-// per-row time from u->tvec, into u->v2
-static FwdCtx integrator_ctx(const fc_unet* u, int B, bool cfg_on, bool has_ids, int mask_mode) {
-    FwdCtx c;
-    c.x_mod = B; c.time = u->tvec; c.ids = has_ids ? u->ids_own : nullptr; c.ids_mod = B; c.null_from = cfg_on ? B : 0;
-    c.mask = mask_mode ? u->mask_own : nullptr; c.mask_fuse = mask_mode == 1;
-    c.out = u->v2; c.B = cfg_on ? 2 * B : B;
-    return c;
-}
-
-// enqueue one integration step on `s` (captured into a graph by the caller)
-// Legacy Euler without CFG: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
-static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_EULER && !cfg_on; }
-
-static int enqueue_step(fc_unet* u, int method, int B, bool cfg_on, float cfg, float dt_euler, float t_scale, bool has_ids, int mask_mode,
-                        bool pre_on, hipStream_t s) {
-    const int rows = cfg_on ? 2 * B : B, n = B * u->cfg.channels * u->H * u->W;
-    FwdCtx c = integrator_ctx(u, B, cfg_on, has_ids, mask_mode);
-    if (pre_on) {   // conditioning rows of every evaluation are in u->pre: init_conv fetches slice *evalc, final_conv advances the counter
-        c.fetch.all = u->pre_ss; c.fetch.evalc = u->step + 1; c.fetch.dst = u->plan.ss; c.fetch.n4 = rows * u->S / 4;
-        c.euler.evalc = u->step + 1;
-    }
-    if (euler_tail_ok(method, cfg_on)) {   // the update and the next interval's time ride in final_conv: no launches around the plan
-        c.x = u->y;
-        c.euler.y = u->y; c.euler.dt = dt_euler; c.euler.step = u->step; c.euler.ts = u->ts_dev; c.euler.t_scale = t_scale;
-        c.euler.sc = u->sc; c.euler.tvec = u->tvec; c.euler.rows = rows;
-        return run_plan(u->plan, c, s);
-    }
-    FC_TRY(ode_time_launch(u->step, u->ts_dev, t_scale, method == FC_METHOD_RK4, u->sc, u->tvec, rows, s));
-    if (method == FC_METHOD_EULER) {
-        c.x = u->y;
-        FC_TRY(run_plan(u->plan, c, s));
-        return ode_euler_update_launch(u->y, u->v2, n, cfg_on, cfg, dt_euler, s);
-    }
-    c.x = u->y;
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k1 = f(y, t)
-    FC_TRY(ode_rk4_stage_launch(u->sc, u->y, u->xs, u->k1, u->v2, n, cfg_on, cfg, 0, 1, t_scale, u->tvec, rows, s));      // y + dt*k1/2, t+dt/2
-    c.x = u->xs;
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k2
-    FC_TRY(ode_rk4_stage_launch(u->sc, u->y, u->xs, u->k2, u->v2, n, cfg_on, cfg, 0, 1, t_scale, u->tvec, rows, s));      // y + dt*k2/2, t+dt/2
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k3
-    FC_TRY(ode_rk4_stage_launch(u->sc, u->y, u->xs, u->k3, u->v2, n, cfg_on, cfg, 1, 2, t_scale, u->tvec, rows, s));      // y + dt*k3, t+dt
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k4
-    return ode_rk4_final_launch(u->sc, u->y, u->k1, u->k2, u->k3, u->v2, n, cfg_on, cfg, s);
-}
-
-// The head of every fixed-grid call on the library stream (fc_unet_integrate, fc_unet_log_likelihood): the time grid's device buffer
-// (grows only when a longer grid than ever before arrives; captured graphs hold its address), the hand-over from the caller's stream,
-// and the call's grid, counters, state, class ids and mask copied into the library's own buffers.
-static int integrator_prologue(fc_unet* u, hipStream_t caller, hipStream_t s, const float* x_dev, size_t nbytes, const float* ts_host,
-                               int n_points, const int64_t* ids, int B, bool has_ids, const float* mask, int mask_mode) {
-    if (n_points + 1 > u->ts_cap) {
-        FC_HIP(hipStreamSynchronize(s));
-        if (u->ts_dev) dev_free(u->ts_dev);
-        u->ts_cap = n_points < 1024 ? 1024 : n_points + 1;   // + 1: the fused Euler tail reads one entry past the grid after the last step
-        FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->ts_dev), u->ts_cap * sizeof(float), "integrator.ts"));
-        drop_graphs(u);  // captured graphs hold the old ts pointer
-    }
-    // the library stream picks up after everything already queued on the caller's stream
-    FC_HIP(hipEventRecord(u->ev_in, caller));
-    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
-    // pageable source: the runtime stages it before returning, so ts_host may be freed by the caller right away
-    FC_HIP(hipMemcpyAsync(u->ts_dev, ts_host, n_points * sizeof(float), hipMemcpyHostToDevice, s));
-    FC_HIP(hipMemsetAsync(u->step, 0, 2 * sizeof(int), s));   // step counter | evaluation counter
-    FC_HIP(hipMemcpyAsync(u->y, x_dev, nbytes, hipMemcpyDeviceToDevice, s));
-    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
-    return FC_OK;
-}
-
-int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float dt_euler,
-                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, void* stream) {
-    if (!u || !x_dev || !ts_host || B < 1 || n_points < 1) return fail(FC_E_ARG, "fc_unet_integrate: bad argument");
-    if (method != FC_METHOD_EULER && method != FC_METHOD_RK4) return fail(FC_E_ARG, "fc_unet_integrate: unknown method");
-    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
-    const bool cfg_on = has_ids && cfg_strength != 0.0f;   // sampling.py:69
-    const int rows = cfg_on ? 2 * B : B;
-    FC_TRY(check_ready(u, rows, H, W));
-    FC_TRY(check_poison(u));
-    u->arena_touched(0);
-    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
-    const int n_steps = method == FC_METHOD_RK4 ? n_points - 1 : n_points;
-    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
-    FC_HIP(hipSetDevice(u->device));
-    const size_t nbytes = (size_t)B * u->cfg.channels * H * W * sizeof(float);
-    FC_TRY(integrator_prologue(u, caller, s, x_dev, nbytes, ts_host, n_points, ids, B, has_ids, mask, mask_mode));
-
-    // Conditioning of every evaluation, once: the grid is known, so time MLP / class MLP / FiLM projections of all (evaluation, row)
-    // pairs are three launches here instead of three at the head of each forward (44 us of every 1.6 ms step inside the replayed graph:
-    // cold weights, latency-bound).  Rows are bit-identical to the per-forward ones (same kernels, same time arithmetic).
-    const int n_evals = method == FC_METHOD_RK4 ? 4 * n_steps : n_steps;
-    const size_t R = (size_t)n_evals * rows, tvn = ((size_t)n_evals + 3) & ~(size_t)3;
-    const size_t need = tvn + R * u->td * 3 + R * u->S;
-    const bool pre_on = n_steps >= 2 && need * sizeof(float) <= (2ull << 30) && R < (1u << 30) / (unsigned)u->S;
-    if (pre_on) {
-        if (need > u->pre_cap) {
-            FC_HIP(hipStreamSynchronize(s));
-            if (u->pre) dev_free(u->pre);
-            u->pre = nullptr; u->pre_cap = 0;
-            FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->pre), need * sizeof(float), "integrator.cond_table"));
-            u->pre_cap = need;
-            drop_graphs(u);  // captured graphs hold the old table pointer
-        }
-        float *tv = u->pre, *te = tv + tvn, *hh = te + R * u->td, *c1 = hh + R * u->td;
-        if (u->pre_ss != c1 + R * u->td)   // the table moved inside the buffer (another number of evaluations): graphs bake its address
-            drop_graphs(u);
-        u->pre_ss = c1 + R * u->td;
-        FC_TRY(ode_all_times_launch(u->ts_dev, n_steps, method == FC_METHOD_RK4, t_scale, tv, s));
-        TembArgs ta = u->temb_proto;
-        ta.B = (int)R; ta.time = tv; ta.rows_per_eval = rows; ta.class_ids = has_ids ? u->ids_own : nullptr; ta.class_batch_mod = B;
-        ta.null_from = cfg_on ? B : 0; ta.t_out = te;
-        FC_TRY(temb_launch(ta, hh, c1, s));
-        // every ResnetBlock.mlp (SiLU -> Linear td -> 2*Cout, unet.py:79-82) of every row as ONE GEMM [R x td] . [td x S] on the
-        // implicit-GEMM kernel (a 1x1 convolution over R one-pixel "images"): the per-forward VALU kernel re-reads the 4 MB weight
-        // matrix for every eight rows (1.7 ms at R = 4096), this takes a tenth of that
-        FC_TRY(silu_fwd_launch(te, nullptr, hh, R * u->td, s));
-        ConvArgs ca;
-        ca.s0.p = hh; ca.s0.C = u->td; ca.Cin = u->td; ca.Cout = u->S; ca.B = (int)R; ca.H = ca.W = ca.Hs = ca.Ws = 1; ca.KS = 1;
-        ca.w = u->P("__ss_wt"); ca.bias = u->P("__ss_bias"); ca.out = u->pre_ss;
-        FC_TRY(conv_launch(ca, TILE_AUTO, s));
-    }
-    if (euler_tail_ok(method, cfg_on))   // time of the first interval; every step publishes its successor's
-        FC_TRY(ode_time_launch(u->step, u->ts_dev, t_scale, 0, u->sc, u->tvec, rows, s));
-    FC_TRY(meet_enter(u, s));
-    if (no_graph()) {
-        for (int i = 0; i < n_steps; ++i) FC_TRY(enqueue_step(u, method, B, cfg_on, cfg_strength, dt_euler, t_scale, has_ids, mask_mode, pre_on, s));
-    } else {
-        // One graph holds SEVERAL consecutive intervals (round 3): the step counter, the time grid and the conditioning slice index all
-        // live on the device, so a captured interval is position-independent and k of them in a row are one hipGraphLaunch instead
-        // of k (the per-interval form left ~4 % of the trajectory between replays: 64 launches of a 70-node graph).  Capped by node
-        // count.
-        const int nodes_per_step = (int)u->plan.ops.size() * (method == FC_METHOD_RK4 ? 4 : 1) + 16;
-        int per = 6144 / nodes_per_step > 0 ? 6144 / nodes_per_step : 1;
-        if (per > 255) per = 255;
-        for (int left = n_steps; left > 0;) {
-            const int k = left < per ? left : per;
-            const auto key = std::make_tuple(method, B, (int)cfg_on, mask_mode, fbits(cfg_strength), fbits(dt_euler), fbits(t_scale),
-                                             (int)has_ids | ((int)pre_on << 1) | (k << 2));
-            hipGraphExec_t exec = nullptr;
-            FC_TRY(cached_graph(u, key, s, [&] {
-                int r = FC_OK;
-                for (int j = 0; j < k && r == FC_OK; ++j)
-                    r = enqueue_step(u, method, B, cfg_on, cfg_strength, dt_euler, t_scale, has_ids, mask_mode, pre_on, s);
-                return r;
-            }, &exec));
-            // The FIRST replay of a call waits, on the host, for everything this call has put on the stream in front of it (round 4).  Under
-            // AMD_DIRECT_DISPATCH=0 -- the mode the sampler ships with -- ROCm 7.2 submits a graph from the calling thread while the plain
-            // launches and copies issued just before it are still queued in the runtime's own submission thread: the replay overtook them.
-            // Measured (tools/inflight_distinct.py: five calls with different noise / class ids, one at a time): a call's trajectory ran on
-            // the PREVIOUS call's conditioning table (rel-L2 1.6e-2 against the oracle, the same value every time, in two or three calls of
-            // five); FLOCODER_AMD_NO_GRAPH=1, AMD_DIRECT_DISPATCH=1 and this wait each give 1e-7 in all of them, an event wait on the
-            // same stream does not.  bench.py never saw it: every timed step integrates the same samples, so a stale table is the right
-            // one.  Replays that follow a replay are ordered (RK4: five graphs per call); work issued behind a replay is ordered as well.
-            // Cost: the host idles for the prologue (~0.1 ms per call of 80 ms).
-            if (left == n_steps) FC_HIP(hipStreamSynchronize(s));
-            FC_HIP(hipGraphLaunch(exec, s));
-            left -= k;
-        }
-    }
-    FC_HIP(hipMemcpyAsync(x_dev, u->y, nbytes, hipMemcpyDeviceToDevice, s));
-    FC_TRY(meet_leave(u, s));
-    FC_HIP(hipEventRecord(u->ev_out, s));
-    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
-    return FC_OK;
-}
-
 // fc_unet_train_reserve switches a handle to plans that keep every intermediate, for good.  A caller that needed the backward plan for
 // one call only (Unet.log_likelihood on a model that otherwise samples) asks which form the handle is in and puts the inference form back:
 // the plans are dropped and the next fc_unet_reserve builds the inference plan a handle that never trained would build.  Synchronises.
@@ -1314,279 +1079,6 @@ int fc_unet_train_release(fc_unet* u) {
     u->keep_all = false;
     u->arena_touched(0);
     return FC_OK;
-}
-
-// ---- likelihood / inversion on the RK4 grid ------------------------------------------------------------------------------------------
-// x from ts[0] to ts[n_points-1] with rk4_step on the caller's grid (log p needs it walked from t = 1 to t = 0), every evaluation a
-// training-mode forward followed by the backward plan's data-gradient chain with the probe as output cotangent (vjp_run), the stage
-// kernels of ode.hip carrying a[b] = integral of eps^T (dv/dx) eps dt.  The grid is known, so nothing is decided on the host: the call
-// returns with the whole loop queued.  Direct launches (4 (n_points - 1) forwards + chains); the arena ends up holding the last stage's
-// forward, which belongs to nobody: the serial moves and a later backward re-runs its own forward.
-int fc_unet_log_likelihood(fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
-                           const int64_t* ids, const float* mask, int mask_is_ones, const float* probe_dev, double* a_out_dev,
-                           double* logp_out_dev, void* stream) {
-    if (!u || !x_dev || !ts_host || !probe_dev || !a_out_dev || !logp_out_dev || B < 1) return fail(FC_E_ARG, "fc_unet_log_likelihood: null argument");
-    if (n_points < 2) return fail(FC_E_ARG, "fc_unet_log_likelihood: the time grid needs at least two points");
-    if (reinterpret_cast<uintptr_t>(probe_dev) & 15) return fail(FC_E_ARG, "fc_unet_log_likelihood: probe_dev must be 16-byte aligned (the kernels read it as float4)");
-    FC_TRY(check_ready(u, B, H, W));
-    if (!u->keep_all) return fail(FC_E_STATE, "fc_unet_log_likelihood: no backward plan for this shape; call fc_unet_train_reserve");
-    FC_TRY(vjp_check(u, B, H, W, "fc_unet_log_likelihood"));
-    FC_TRY(check_poison(u));
-    u->arena_touched(0);
-    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
-    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
-    const int m = u->cfg.channels * H * W;
-    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
-    FC_HIP(hipSetDevice(u->device));
-    if (!u->ll_g) {
-        void* p = nullptr;
-        FC_TRY(dev_alloc(&p, (size_t)u->maxB * m * sizeof(float), "integrator.likelihood")); u->int_allocs.push_back(p); u->ll_g = static_cast<float*>(p);
-        FC_TRY(dev_alloc(&p, (size_t)u->maxB * 3 * sizeof(double), "integrator.likelihood")); u->int_allocs.push_back(p); u->ll_d = static_cast<double*>(p);
-    }
-    const size_t nbytes = (size_t)B * m * sizeof(float);
-    FC_TRY(integrator_prologue(u, caller, s, x_dev, nbytes, ts_host, n_points, ids, B, has_ids, mask, mask_mode));
-    FC_HIP(hipMemsetAsync(a_out_dev, 0, (size_t)B * sizeof(double), s));
-    FwdCtx c = integrator_ctx(u, B, false, has_ids, mask_mode);
-    c.d_out = probe_dev; c.dx_out = u->ll_g;
-    FC_TRY(meet_enter(u, s));
-    auto eval = [&](const float* x) -> int {      // v2 = v(x, tvec), ll_g = (dv/dx)^T probe
-        c.x = x;
-        FC_TRY(run_plan(u->plan, c, s));
-        return vjp_run(u, c, s);
-    };
-    for (int i = 0; i + 1 < n_points; ++i) {
-        FC_TRY(ode_time_launch(u->step, u->ts_dev, t_scale, 1, u->sc, u->tvec, B, s));
-        FC_TRY(eval(u->y));                                                                                                              // k1, g1
-        FC_TRY(ode_ll_stage_launch(u->sc, u->y, u->xs, u->k1, u->v2, u->ll_g, probe_dev, u->ll_d, 0, B, m, 0, 1, t_scale, u->tvec, s));  // y + dt*k1/2, t+dt/2
-        FC_TRY(eval(u->xs));                                                                                                             // k2, g2
-        FC_TRY(ode_ll_stage_launch(u->sc, u->y, u->xs, u->k2, u->v2, u->ll_g, probe_dev, u->ll_d, 1, B, m, 0, 1, t_scale, u->tvec, s));  // y + dt*k2/2, t+dt/2
-        FC_TRY(eval(u->xs));                                                                                                             // k3, g3
-        FC_TRY(ode_ll_stage_launch(u->sc, u->y, u->xs, u->k3, u->v2, u->ll_g, probe_dev, u->ll_d, 2, B, m, 1, 2, t_scale, u->tvec, s));  // y + dt*k3, t+dt
-        FC_TRY(eval(u->xs));                                                                                                             // k4, g4
-        FC_TRY(ode_ll_final_launch(u->sc, u->y, u->k1, u->k2, u->k3, u->v2, u->ll_g, probe_dev, u->ll_d, a_out_dev, B, m, s));
-    }
-    FC_TRY(ode_ll_logp_launch(u->y, a_out_dev, logp_out_dev, B, m, s));
-    FC_HIP(hipMemcpyAsync(x_dev, u->y, nbytes, hipMemcpyDeviceToDevice, s));
-    FC_TRY(meet_leave(u, s));
-    FC_HIP(hipEventRecord(u->ev_out, s));
-    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
-    return FC_OK;
-}
-
-int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_dev, int batch, int64_t per_sample, void* stream) {
-    if (!probe_dev || !g_dev || !out_dev) return fail(FC_E_ARG, "fc_debug_probe_dot: null argument");
-    if ((reinterpret_cast<uintptr_t>(probe_dev) | reinterpret_cast<uintptr_t>(g_dev)) & 15)
-        return fail(FC_E_ARG, "fc_debug_probe_dot: inputs must be 16-byte aligned (read as float4)");
-    if (per_sample < 1 || per_sample > 0x7fffffff) return fail(FC_E_SHAPE, "fc_debug_probe_dot: bad element count");
-    return ode_ll_dot_launch(probe_dev, g_dev, out_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
-}
-
-// ---- adaptive RK45 ----------------------------------------------------------------------------------------------------------------
-// Both modes run ode.hip's grouped kernels: the batch-coupled solve is one controller over all B*C*H*W unknowns, the per-sample solve
-// one controller per sample.  Each mode keeps the partition it was introduced with -- it fixes the summation order of the norms and
-// with it the bits: coupled, one workgroup per 1024 unknowns of the batch, at most 2048 (the elementwise grid of ode.hip); per sample,
-// at most 64, so that a sample's step sequence depends on C*H*W alone, not on the batch size.
-static constexpr int kRk45MaxAttempts = 10000;     // a field that never settles raises instead of spinning (scipy has no such cap)
-static constexpr int kRk45Method = 2;              // graph-cache keys of a coupled / per-sample attempt (beside FC_METHOD_EULER /
-static constexpr int kRk45PerSampleMethod = 3;     // FC_METHOD_RK4): the two modes' attempts are different graphs
-static constexpr int kRk45CoupledChunks = 2048, kRk45PerSampleChunks = 64;
-
-static Rk45Groups rk45_groups(const fc_unet* u, int B, bool per_sample) {
-    const int m = u->cfg.channels * u->H * u->W;
-    return per_sample ? Rk45Groups{B, 1, m, rk45_chunks(m, kRk45PerSampleChunks)}
-                      : Rk45Groups{1, B, B * m, rk45_chunks(B * m, kRk45CoupledChunks)};
-}
-
-// The controller state, allocated by the first RK45 call (in int_allocs, released with the plan) so handles that never use it keep
-// their footprint; the partial sums fit either mode's partition.
-static int alloc_rk45(fc_unet* u) {
-    const size_t nstate = (size_t)u->maxB * u->cfg.channels * u->H * u->W;
-    auto get = [&](size_t bytes, void** out) -> int {
-        FC_TRY(dev_alloc(out, bytes, "integrator.rk45"));
-        u->int_allocs.push_back(*out);
-        return FC_OK;
-    };
-    const Rk45Groups cg = rk45_groups(u, u->maxB, false), pg = rk45_groups(u, u->maxB, true);
-    const size_t parts = std::max((size_t)cg.G * cg.chunks, (size_t)pg.G * pg.chunks);
-    void* p = nullptr;
-    FC_TRY(get(nstate * sizeof(double), &p)); u->rk_y = static_cast<double*>(p);
-    FC_TRY(get(nstate * sizeof(double), &p)); u->rk_ynew = static_cast<double*>(p);
-    for (int j = 0; j < 7; ++j) { FC_TRY(get(nstate * sizeof(float), &p)); u->rk_k.k[j] = static_cast<float*>(p); }
-    FC_TRY(get(2 * parts * sizeof(double), &p)); u->rk_part = static_cast<double*>(p);
-    FC_TRY(get((size_t)u->maxB * sizeof(Rk45State), &p)); u->rk_st = static_cast<Rk45State*>(p);
-    FC_TRY(get(sizeof(Rk45Status), &p)); u->rk_sum = static_cast<Rk45Status*>(p);
-    return FC_OK;
-}
-
-// one attempt of RungeKutta._step_impl for every group that still steps: five stages, y_new and f(t + h, y_new), the error norms,
-// the controllers, with a dense-output request (`ev`) the frames an accepted step serves, the commit, the status summary
-static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const FwdCtx& c, int cf, float cfg, float t_scale, const Rk45Eval* ev,
-                                hipStream_t s) {
-    for (int st = 1; st <= 5; ++st) {
-        FC_TRY(rk45_stage_launch(g, u->rk_st, st, u->rk_y, u->rk_k, u->v2, cf, cfg, u->xs, t_scale, u->tvec, s));
-        FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
-    }
-    FC_TRY(rk45_finish_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, cf, cfg, u->xs, t_scale, u->tvec, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
-    FC_TRY(rk45_error_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k, u->v2, cf, cfg, u->rk_part, s));
-    FC_TRY(rk45_control_launch(g, u->rk_st, u->rk_part, ev, s));
-    if (ev) FC_TRY(rk45_dense_launch(g, u->rk_st, ev, u->rk_y, u->rk_k, s));       // reads y and K0..K6 before the commit replaces them
-    FC_TRY(rk45_commit_launch(g, u->rk_st, u->rk_y, u->rk_ynew, u->rk_k.k[0], u->rk_k.k[6], s));
-    return rk45_status_launch(g, u->rk_st, u->rk_sum, s);
-}
-
-// solve_ivp's checks of t_eval, with its messages
-static int check_t_eval(const char* fn, const double* te, int n_eval, double t0, double t1) {
-    const double lo = std::min(t0, t1), hi = std::max(t0, t1);
-    for (int j = 0; j < n_eval; ++j)
-        if (!(te[j] >= lo && te[j] <= hi)) return fail(FC_E_ARG, std::string(fn) + ": Values in `t_eval` are not within `t_span`.");
-    for (int j = 1; j < n_eval; ++j) {
-        const double d = te[j] - te[j - 1];
-        if ((t1 > t0 && d <= 0) || (t1 < t0 && d >= 0))
-            return fail(FC_E_ARG, std::string(fn) + ": Values in `t_eval` are not properly sorted.");
-    }
-    return FC_OK;
-}
-
-// The dense-output request of this call in the handle's device record (header, then the times), ahead of the solve on `s`.  The record
-// grows only when a call brings more times than any before; captured attempts bake its address.
-static int stage_rk45_eval(fc_unet* u, const double* te, int n_eval, float* frames_dev, hipStream_t s) {
-    if (n_eval > u->rk_ev_cap) {
-        FC_HIP(hipStreamSynchronize(s));
-        if (u->rk_ev) dev_free(u->rk_ev);
-        u->rk_ev = nullptr; u->rk_ev_cap = 0;
-        const int cap = n_eval < 1024 ? 1024 : n_eval;
-        FC_TRY(dev_alloc(reinterpret_cast<void**>(&u->rk_ev), sizeof(Rk45Eval) + (size_t)cap * sizeof(double), "integrator.rk45_eval"));
-        u->rk_ev_cap = cap;
-        drop_graphs(u);
-    }
-    std::vector<unsigned char> rec(sizeof(Rk45Eval) + (size_t)n_eval * sizeof(double));
-    const Rk45Eval head{frames_dev, n_eval, 0};
-    std::memcpy(rec.data(), &head, sizeof(head));
-    std::memcpy(rec.data() + sizeof(head), te, (size_t)n_eval * sizeof(double));
-    // pageable source: the runtime stages it before returning (as the time grid of fc_unet_integrate)
-    FC_HIP(hipMemcpyAsync(u->rk_ev, rec.data(), rec.size(), hipMemcpyHostToDevice, s));
-    return FC_OK;
-}
-
-// fc_unet_integrate_rk45 (per_sample = false), fc_unet_integrate_rk45_per_sample and, with n_eval > 0, fc_unet_integrate_rk45_dense;
-// `fn` names the entry point in argument errors
-static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_dev, int B, int H, int W, double t0, double t1,
-                          double rtol, double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask,
-                          int mask_is_ones, const double* t_eval, int n_eval, float* frames_dev, int* counters, void* stream) {
-    if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, std::string(fn) + ": bad argument");
-    if (n_eval < 0 || (n_eval > 0 && (!t_eval || !frames_dev || (reinterpret_cast<uintptr_t>(frames_dev) & 15))))
-        return fail(FC_E_ARG, std::string(fn) + ": t_eval needs its times and a 16-byte aligned frames buffer");
-    if (!(atol >= 0)) return fail(FC_E_ARG, std::string(fn) + ": `atol` must be positive.");      // validate_tol
-    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, std::string(fn) + ": t0 and t1 must be finite");
-    const double eps100 = 100 * 2.220446049250313e-16;
-    if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
-    FC_TRY(check_t_eval(fn, t_eval, n_eval, t0, t1));
-    const bool has_ids = ids != nullptr && u->cfg.n_classes > 0;
-    const bool cfg_on = has_ids && cfg_strength != 0.0f;
-    FC_TRY(check_ready(u, cfg_on ? 2 * B : B, H, W));
-    FC_TRY(check_poison(u));
-    const Rk45Groups g = rk45_groups(u, B, per_sample);
-    for (int i = 0; i < g.G; ++i) { counters[3 * i] = 1; counters[3 * i + 1] = counters[3 * i + 2] = 0; }   // nfev, accepted, rejected
-    const int n = B * u->cfg.channels * H * W, cf = cfg_on ? 1 : 0;
-    const size_t nbytes = (size_t)n * sizeof(float);
-    hipStream_t caller = static_cast<hipStream_t>(stream), s = u->stream;
-    FC_HIP(hipSetDevice(u->device));
-    if (t0 == t1) {                              // scipy: one evaluation, no step, y0 returned; every requested time is t0
-        for (int j = 0; j < n_eval; ++j) FC_HIP(hipMemcpyAsync(frames_dev + (size_t)j * n, x_dev, nbytes, hipMemcpyDeviceToDevice, caller));
-        return FC_OK;
-    }
-    u->arena_touched(0);
-    const int mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
-    if (!u->rk_st) FC_TRY(alloc_rk45(u));
-    if (!u->rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); u->rk_host = static_cast<Rk45Status*>(hp); }
-    if (!u->ev_rk) FC_HIP(hipEventCreateWithFlags(&u->ev_rk, hipEventDisableTiming));
-
-    FC_HIP(hipEventRecord(u->ev_in, caller));
-    FC_HIP(hipStreamWaitEvent(s, u->ev_in, 0));
-    if (has_ids) FC_HIP(hipMemcpyAsync(u->ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (mask_mode) FC_HIP(hipMemcpyAsync(u->mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
-    if (n_eval > 0) FC_TRY(stage_rk45_eval(u, t_eval, n_eval, frames_dev, s));
-    const Rk45Eval* ev = n_eval > 0 ? u->rk_ev : nullptr;
-    FC_TRY(meet_enter(u, s));
-
-    // f(t0, y0) and select_initial_step of every group (two forwards, no graph)
-    FwdCtx c = integrator_ctx(u, B, cfg_on, has_ids, mask_mode);
-    c.x = u->xs;   // every forward of the solve reads the stage input the RK45 kernels write
-    FC_TRY(rk45_setup_launch(g, x_dev, u->rk_y, u->xs, u->rk_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, u->tvec, cf, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
-    FC_TRY(rk45_d01_launch(g, u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, cf, cfg_strength, u->rk_part, s));
-    FC_TRY(rk45_h0_launch(g, u->rk_st, u->rk_part, t_scale, u->tvec, cf, s));
-    FC_TRY(rk45_y1_launch(g, u->rk_st, u->rk_y, u->rk_k.k[0], u->xs, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
-    FC_TRY(rk45_d2_launch(g, u->rk_st, u->rk_y, u->rk_k.k[0], u->v2, cf, cfg_strength, u->rk_part, s));
-    FC_TRY(rk45_h1_launch(g, u->rk_st, u->rk_part, s));
-    FC_TRY(rk45_status_launch(g, u->rk_st, u->rk_sum, s));
-    FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
-    // This wait is also the one fc_unet_integrate makes before its first replay: under AMD_DIRECT_DISPATCH=0 a graph submitted from this
-    // thread can overtake the plain launches and copies queued just before it (see there).
-    FC_HIP(hipStreamSynchronize(s));
-
-    // (an attempt with dense output has one more launch: a different graph)
-    const auto key = std::make_tuple(per_sample ? kRk45PerSampleMethod : kRk45Method, B, (int)cfg_on, mask_mode, fbits(cfg_strength), 0u,
-                                     fbits(t_scale), (int)has_ids | (ev ? 2 : 0));
-    auto attempt = [&] { return enqueue_rk45_attempt(u, g, c, cf, cfg_strength, t_scale, ev, s); };
-    while (u->rk_host->unfinished > 0) {
-        if (no_graph()) {
-            FC_TRY(attempt());
-        } else {   // one attempt = one graph: 6 plan runs and 10 (11 with dense output) small launches, a single chain (no parallel branches)
-            hipGraphExec_t exec = nullptr;
-            FC_TRY(cached_graph(u, key, s, attempt, &exec));
-            FC_HIP(hipGraphLaunch(exec, s));
-        }
-        // the 16-byte summary behind every attempt: one small host wait per six forwards
-        FC_HIP(hipMemcpyAsync(u->rk_host, u->rk_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
-        FC_HIP(hipEventRecord(u->ev_rk, s));
-        FC_HIP(hipEventSynchronize(u->ev_rk));
-    }
-    std::vector<Rk45State> st(g.G);      // the controller records, once at the end
-    FC_HIP(hipMemcpyAsync(st.data(), u->rk_st, (size_t)g.G * sizeof(Rk45State), hipMemcpyDeviceToHost, s));
-    FC_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < g.G; ++i) { counters[3 * i] = st[i].nfev; counters[3 * i + 1] = st[i].accepted; counters[3 * i + 2] = st[i].rejected; }
-    const int failed = u->rk_host->failed;
-    if (!failed) FC_TRY(rk45_out_launch(u->rk_y, x_dev, n, s));
-    FC_TRY(meet_leave(u, s));
-    FC_HIP(hipEventRecord(u->ev_out, s));
-    FC_HIP(hipStreamWaitEvent(caller, u->ev_out, 0));
-    if (!failed) return FC_OK;
-    if (!per_sample) {
-        if (st[0].failed == 1) return fail(FC_E_STATE, "rk45: Required step size is less than spacing between numbers.");
-        return fail(FC_E_STATE, "rk45: no convergence after " + std::to_string(st[0].attempts) + " attempts (t = " +
-                                    std::to_string(st[0].t) + ", h = " + std::to_string(st[0].h_abs) + ")");
-    }
-    std::string msg = "rk45 per sample: " + std::to_string(failed) + " of " + std::to_string(B) + " samples failed;";
-    for (int b = 0; b < B; ++b) {
-        if (st[b].failed == 1) msg += " sample " + std::to_string(b) + ": Required step size is less than spacing between numbers.";
-        else if (st[b].failed) msg += " sample " + std::to_string(b) + ": no convergence after " + std::to_string(st[b].attempts) +
-                                      " attempts (t = " + std::to_string(st[b].t) + ", h = " + std::to_string(st[b].h_abs) + ").";
-    }
-    return fail(FC_E_STATE, msg);
-}
-
-int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
-                                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
-                                      int* counters, void* stream) {
-    return integrate_rk45(u, false, "fc_unet_integrate_rk45", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength, mask,
-                          mask_is_ones, nullptr, 0, nullptr, counters, stream);
-}
-
-int fc_unet_integrate_rk45_per_sample(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
-                                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
-                                      int* counters, void* stream) {
-    return integrate_rk45(u, true, "fc_unet_integrate_rk45_per_sample", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength,
-                          mask, mask_is_ones, nullptr, 0, nullptr, counters, stream);
-}
-
-int fc_unet_integrate_rk45_dense(fc_unet* u, int per_sample, float* x_dev, int B, int H, int W, double t0, double t1, double rtol,
-                                 double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
-                                 const double* t_eval_host, int n_eval, float* frames_dev, int* counters, void* stream) {
-    return integrate_rk45(u, per_sample != 0, "fc_unet_integrate_rk45_dense", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids,
-                          cfg_strength, mask, mask_is_ones, t_eval_host, n_eval, frames_dev, counters, stream);
 }
 
 // ---- debug / test hooks --------------------------------------------------------------------------

@@ -1,0 +1,547 @@
+// The integrators of the velocity U-Net: fixed-grid Euler / RK4 (fc_unet_integrate), likelihood / inversion on the RK4 grid
+// (fc_unet_log_likelihood) and adaptive RK45 (fc_unet_integrate_rk45*).  Host code only: the kernels are ode.hip's, the forward is the
+// handle's launch plan (unet.hip).  Every call runs on the library's own stream inside one CallFrame; its state is fc_unet::ig.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+
+#include "plan.h"
+#include "unet_priv.h"
+
+using namespace fc;
+
+namespace fc {
+
+// ------------------------------------------------------------------------------------------- state
+void IntegratorState::drop_graphs() {
+    for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
+    graphs.clear();
+}
+void IntegratorState::release_plan() {
+    drop_graphs();
+    for (void* p : allocs) dev_free(p);
+    static_cast<IntegratorPlanState&>(*this) = IntegratorPlanState{};
+}
+void IntegratorState::release_handle() {
+    release_plan();
+    for (void* p : {(void*)ts_dev, (void*)rk_ev, (void*)pre}) if (p) dev_free(p);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (ev_in) (void)hipEventDestroy(ev_in);
+    if (ev_out) (void)hipEventDestroy(ev_out);
+    if (rk_host) (void)hipHostFree(rk_host);
+    if (ev_rk) (void)hipEventDestroy(ev_rk);
+}
+
+// integrator state for `rows` U-Net rows
+int alloc_integrator(fc_unet* u, int rows, int H, int W) {
+    IntegratorState& ig = u->ig;
+    const size_t nstate = (size_t)rows * u->cfg.channels * H * W;
+    for (float** b : {&ig.y, &ig.xs, &ig.k1, &ig.k2, &ig.k3, &ig.v2, &ig.mask_own}) FC_TRY(ig.get(b, nstate, "integrator"));
+    FC_TRY(ig.get(&ig.tvec, rows, "integrator"));
+    FC_TRY(ig.get(&ig.sc, 4, "integrator"));
+    FC_TRY(ig.get(&ig.step, 4, "integrator"));
+    return ig.get(&ig.ids_own, rows, "integrator");
+}
+
+// ------------------------------------------------------------------------------------------- call frame
+// One integrator call.  begin() derives what every path derives from its arguments and checks that the handle can run them; nothing is
+// touched yet.  enter() moves the call onto the library stream: the hand-over from the caller's stream, the call's class ids and mask
+// copied into the library's own buffers, the meeting guard.  leave() hands back; a call that returns early after enter() leaves through
+// the destructor, so the caller's stream is ordered behind whatever the library stream still holds and the meeting guard knows this
+// handle's last plan -- whichever FC_TRY failed.
+struct CallFrame {
+    fc_unet* u = nullptr;
+    hipStream_t caller = nullptr, s = nullptr;
+    const int64_t* ids = nullptr;
+    const float* mask = nullptr;
+    bool has_ids = false, cfg_on = false, entered = false;
+    int B = 0, rows = 0, mask_mode = 0, n = 0;      // rows: U-Net rows per evaluation (2B with CFG); n: unknowns of the batch
+    size_t nbytes = 0;                              // of the state (and of the mask)
+
+    int begin(fc_unet* u_, int B_, int H, int W, const int64_t* ids_, float cfg_strength, const float* mask_, int mask_is_ones, void* stream) {
+        u = u_; B = B_; ids = ids_; mask = mask_; caller = static_cast<hipStream_t>(stream); s = u->ig.stream;
+        has_ids = ids != nullptr && u->cfg.n_classes > 0;
+        cfg_on = has_ids && cfg_strength != 0.0f;   // sampling.py:69
+        rows = cfg_on ? 2 * B : B;
+        mask_mode = (mask && u->cfg.mask_cond) ? (mask_is_ones ? 2 : 1) : 0;
+        n = B * u->cfg.channels * H * W; nbytes = (size_t)n * sizeof(float);
+        FC_TRY(check_ready(u, rows, H, W));
+        FC_TRY(check_poison(u));
+        FC_HIP(hipSetDevice(u->device));
+        return FC_OK;
+    }
+    int enter() {
+        u->arena_touched(0);
+        // the library stream picks up after everything already queued on the caller's stream
+        FC_HIP(hipEventRecord(u->ig.ev_in, caller));
+        FC_HIP(hipStreamWaitEvent(s, u->ig.ev_in, 0));
+        entered = true;
+        if (has_ids) FC_HIP(hipMemcpyAsync(u->ig.ids_own, ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        if (mask_mode) FC_HIP(hipMemcpyAsync(u->ig.mask_own, mask, nbytes, hipMemcpyDeviceToDevice, s));
+        return meet_enter(u, s);
+    }
+    int leave() {
+        entered = false;
+        FC_TRY(meet_leave(u, s));
+        FC_HIP(hipEventRecord(u->ig.ev_out, s));
+        FC_HIP(hipStreamWaitEvent(caller, u->ig.ev_out, 0));
+        return FC_OK;
+    }
+    ~CallFrame() {
+        if (!entered) return;
+        const std::string first = fc_last_error();   // the error that ended the call stays the one reported
+        if (leave() != FC_OK) set_error(first);
+    }
+};
+
+}  // namespace fc
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------- graph cache
+static uint32_t fbits(float f) { uint32_t v; std::memcpy(&v, &f, 4); return v; }
+
+// FLOCODER_AMD_NO_GRAPH: every integrator enqueues its launches directly instead of capturing and replaying graphs
+static bool no_graph() {
+    static const bool v = std::getenv("FLOCODER_AMD_NO_GRAPH") != nullptr;
+    return v;
+}
+
+// the graph cached under `key`; on first use it is captured from `enqueue` on `s` and instantiated
+static int cached_graph(fc_unet* u, const GraphKey& key, hipStream_t s, const std::function<int()>& enqueue, hipGraphExec_t* out) {
+    IntegratorState& ig = u->ig;
+    auto it = ig.graphs.find(key);
+    if (it == ig.graphs.end()) {
+        hipGraph_t graph = nullptr;
+        FC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int r = enqueue();
+        const hipError_t e = hipStreamEndCapture(s, &graph);
+        if (r != FC_OK) { if (graph) (void)hipGraphDestroy(graph); return r; }
+        if (e != hipSuccess) return fail(FC_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+        hipGraphExec_t exec = nullptr;
+        FC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        FC_HIP(hipGraphDestroy(graph));
+        it = ig.graphs.emplace(key, exec).first;
+    }
+    *out = it->second;
+    return FC_OK;
+}
+
+// the part of a key every path fills the same way
+static GraphKey graph_key(const CallFrame& f, GraphKey::Kind kind, float cfg_strength, float t_scale) {
+    GraphKey k;
+    k.kind = kind; k.B = f.B; k.cfg_on = f.cfg_on; k.mask_mode = f.mask_mode; k.has_ids = f.has_ids;
+    k.cfg_strength = fbits(cfg_strength); k.t_scale = fbits(t_scale);
+    return k;
+}
+
+// the forward of one integrator evaluation (the caller sets its input x): B rows and, with CFG, their unguided twins B..2B-1, the
+// per-row time from ig.tvec, into ig.v2
+static FwdCtx integrator_ctx(const CallFrame& f) {
+    const IntegratorState& ig = f.u->ig;
+    FwdCtx c;
+    c.x_mod = f.B; c.time = ig.tvec; c.ids = f.has_ids ? ig.ids_own : nullptr; c.ids_mod = f.B; c.null_from = f.cfg_on ? f.B : 0;
+    c.mask = f.mask_mode ? ig.mask_own : nullptr; c.mask_fuse = f.mask_mode == 1;
+    c.out = ig.v2; c.B = f.rows;
+    return c;
+}
+
+// enqueue one integration step on `s` (captured into a graph by the caller)
+// Legacy Euler without CFG: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
+static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_EULER && !cfg_on; }
+
+static int enqueue_step(const CallFrame& f, int method, float cfg, float dt_euler, float t_scale, bool pre_on) {
+    fc_unet* u = f.u;
+    const IntegratorState& ig = u->ig;
+    const bool cfg_on = f.cfg_on;
+    const int rows = f.rows, n = f.n;
+    hipStream_t s = f.s;
+    FwdCtx c = integrator_ctx(f);
+    if (pre_on) {   // conditioning rows of every evaluation are in ig.pre: init_conv fetches slice *evalc, final_conv advances the counter
+        c.fetch.all = ig.pre_ss; c.fetch.evalc = ig.step + 1; c.fetch.dst = u->plan.ss; c.fetch.n4 = rows * u->S / 4;
+        c.euler.evalc = ig.step + 1;
+    }
+    if (euler_tail_ok(method, cfg_on)) {   // the update and the next interval's time ride in final_conv: no launches around the plan
+        c.x = ig.y;
+        c.euler.y = ig.y; c.euler.dt = dt_euler; c.euler.step = ig.step; c.euler.ts = ig.ts_dev; c.euler.t_scale = t_scale;
+        c.euler.sc = ig.sc; c.euler.tvec = ig.tvec; c.euler.rows = rows;
+        return run_plan(u->plan, c, s);
+    }
+    FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, method == FC_METHOD_RK4, ig.sc, ig.tvec, rows, s));
+    if (method == FC_METHOD_EULER) {
+        c.x = ig.y;
+        FC_TRY(run_plan(u->plan, c, s));
+        return ode_euler_update_launch(ig.y, ig.v2, n, cfg_on, cfg, dt_euler, s);
+    }
+    c.x = ig.y;
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k1 = f(y, t)
+    FC_TRY(ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, ig.k1, ig.v2, n, cfg_on, cfg, 0, 1, t_scale, ig.tvec, rows, s));      // y + dt*k1/2, t+dt/2
+    c.x = ig.xs;
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k2
+    FC_TRY(ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, ig.k2, ig.v2, n, cfg_on, cfg, 0, 1, t_scale, ig.tvec, rows, s));      // y + dt*k2/2, t+dt/2
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k3
+    FC_TRY(ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, ig.k3, ig.v2, n, cfg_on, cfg, 1, 2, t_scale, ig.tvec, rows, s));      // y + dt*k3, t+dt
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k4
+    return ode_rk4_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, n, cfg_on, cfg, s);
+}
+
+// What a fixed-grid call puts behind its frame's hand-over (fc_unet_integrate, fc_unet_log_likelihood): the time grid's device buffer
+// (grows only when a longer grid than ever before arrives; captured graphs hold its address) and the call's grid, counters and state
+// copied into the library's own buffers.
+static int integrator_prologue(const CallFrame& f, const float* x_dev, const float* ts_host, int n_points) {
+    IntegratorState& ig = f.u->ig;
+    hipStream_t s = f.s;
+    if (n_points + 1 > ig.ts_cap) {
+        FC_HIP(hipStreamSynchronize(s));
+        if (ig.ts_dev) dev_free(ig.ts_dev);
+        ig.ts_cap = n_points < 1024 ? 1024 : n_points + 1;   // + 1: the fused Euler tail reads one entry past the grid after the last step
+        FC_TRY(dev_alloc(reinterpret_cast<void**>(&ig.ts_dev), ig.ts_cap * sizeof(float), "integrator.ts"));
+        ig.drop_graphs();  // captured graphs hold the old ts pointer
+    }
+    // pageable source: the runtime stages it before returning, so ts_host may be freed by the caller right away
+    FC_HIP(hipMemcpyAsync(ig.ts_dev, ts_host, n_points * sizeof(float), hipMemcpyHostToDevice, s));
+    FC_HIP(hipMemsetAsync(ig.step, 0, 2 * sizeof(int), s));   // step counter | evaluation counter
+    FC_HIP(hipMemcpyAsync(ig.y, x_dev, f.nbytes, hipMemcpyDeviceToDevice, s));
+    return FC_OK;
+}
+
+int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float dt_euler,
+                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, void* stream) {
+    if (!u || !x_dev || !ts_host || B < 1 || n_points < 1) return fail(FC_E_ARG, "fc_unet_integrate: bad argument");
+    if (method != FC_METHOD_EULER && method != FC_METHOD_RK4) return fail(FC_E_ARG, "fc_unet_integrate: unknown method");
+    CallFrame f;
+    FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
+    FC_TRY(f.enter());
+    IntegratorState& ig = u->ig;
+    const bool has_ids = f.has_ids, cfg_on = f.cfg_on;
+    const int rows = f.rows, n_steps = method == FC_METHOD_RK4 ? n_points - 1 : n_points;
+    hipStream_t s = f.s;
+    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
+
+    // Conditioning of every evaluation, once: the grid is known, so time MLP / class MLP / FiLM projections of all (evaluation, row)
+    // pairs are three launches here instead of three at the head of each forward (44 us of every 1.6 ms step inside the replayed graph:
+    // cold weights, latency-bound).  Rows are bit-identical to the per-forward ones (same kernels, same time arithmetic).
+    const int n_evals = method == FC_METHOD_RK4 ? 4 * n_steps : n_steps;
+    const size_t R = (size_t)n_evals * rows, tvn = ((size_t)n_evals + 3) & ~(size_t)3;
+    const size_t need = tvn + R * u->td * 3 + R * u->S;
+    const bool pre_on = n_steps >= 2 && need * sizeof(float) <= (2ull << 30) && R < (1u << 30) / (unsigned)u->S;
+    if (pre_on) {
+        if (need > ig.pre_cap) {
+            FC_HIP(hipStreamSynchronize(s));
+            if (ig.pre) dev_free(ig.pre);
+            ig.pre = nullptr; ig.pre_cap = 0;
+            FC_TRY(dev_alloc(reinterpret_cast<void**>(&ig.pre), need * sizeof(float), "integrator.cond_table"));
+            ig.pre_cap = need;
+            ig.drop_graphs();  // captured graphs hold the old table pointer
+        }
+        float *tv = ig.pre, *te = tv + tvn, *hh = te + R * u->td, *c1 = hh + R * u->td;
+        if (ig.pre_ss != c1 + R * u->td)   // the table moved inside the buffer (another number of evaluations): graphs bake its address
+            ig.drop_graphs();
+        ig.pre_ss = c1 + R * u->td;
+        FC_TRY(ode_all_times_launch(ig.ts_dev, n_steps, method == FC_METHOD_RK4, t_scale, tv, s));
+        TembArgs ta = u->temb_proto;
+        ta.B = (int)R; ta.time = tv; ta.rows_per_eval = rows; ta.class_ids = has_ids ? ig.ids_own : nullptr; ta.class_batch_mod = B;
+        ta.null_from = cfg_on ? B : 0; ta.t_out = te;
+        FC_TRY(temb_launch(ta, hh, c1, s));
+        // every ResnetBlock.mlp (SiLU -> Linear td -> 2*Cout, unet.py:79-82) of every row as ONE GEMM [R x td] . [td x S] on the
+        // implicit-GEMM kernel (a 1x1 convolution over R one-pixel "images"): the per-forward VALU kernel re-reads the 4 MB weight
+        // matrix for every eight rows (1.7 ms at R = 4096), this takes a tenth of that
+        FC_TRY(silu_fwd_launch(te, nullptr, hh, R * u->td, s));
+        ConvArgs ca;
+        ca.s0.p = hh; ca.s0.C = u->td; ca.Cin = u->td; ca.Cout = u->S; ca.B = (int)R; ca.H = ca.W = ca.Hs = ca.Ws = 1; ca.KS = 1;
+        ca.w = u->P("__ss_wt"); ca.bias = u->P("__ss_bias"); ca.out = ig.pre_ss;
+        FC_TRY(conv_launch(ca, TILE_AUTO, s));
+    }
+    if (euler_tail_ok(method, cfg_on))   // time of the first interval; every step publishes its successor's
+        FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 0, ig.sc, ig.tvec, rows, s));
+    if (no_graph()) {
+        for (int i = 0; i < n_steps; ++i) FC_TRY(enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on));
+    } else {
+        // One graph holds SEVERAL consecutive intervals (round 3): the step counter, the time grid and the conditioning slice index all
+        // live on the device, so a captured interval is position-independent and k of them in a row are one hipGraphLaunch instead
+        // of k (the per-interval form left ~4 % of the trajectory between replays: 64 launches of a 70-node graph).  Capped by node
+        // count.
+        const int nodes_per_step = (int)u->plan.ops.size() * (method == FC_METHOD_RK4 ? 4 : 1) + 16;
+        int per = 6144 / nodes_per_step > 0 ? 6144 / nodes_per_step : 1;
+        if (per > 255) per = 255;
+        for (int left = n_steps; left > 0;) {
+            const int k = left < per ? left : per;
+            GraphKey key = graph_key(f, method == FC_METHOD_RK4 ? GraphKey::Rk4 : GraphKey::Euler, cfg_strength, t_scale);
+            key.pre_on = pre_on; key.steps = k; key.dt_euler = fbits(dt_euler);
+            hipGraphExec_t exec = nullptr;
+            FC_TRY(cached_graph(u, key, s, [&] {
+                int r = FC_OK;
+                for (int j = 0; j < k && r == FC_OK; ++j)
+                    r = enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on);
+                return r;
+            }, &exec));
+            // The FIRST replay of a call waits, on the host, for everything this call has put on the stream in front of it (round 4).  Under
+            // AMD_DIRECT_DISPATCH=0 -- the mode the sampler ships with -- ROCm 7.2 submits a graph from the calling thread while the plain
+            // launches and copies issued just before it are still queued in the runtime's own submission thread: the replay overtook them.
+            // Measured (tools/inflight_distinct.py: five calls with different noise / class ids, one at a time): a call's trajectory ran on
+            // the PREVIOUS call's conditioning table (rel-L2 1.6e-2 against the oracle, the same value every time, in two or three calls of
+            // five); FLOCODER_AMD_NO_GRAPH=1, AMD_DIRECT_DISPATCH=1 and this wait each give 1e-7 in all of them, an event wait on the
+            // same stream does not.  bench.py never saw it: every timed step integrates the same samples, so a stale table is the right
+            // one.  Replays that follow a replay are ordered (RK4: five graphs per call); work issued behind a replay is ordered as well.
+            // Cost: the host idles for the prologue (~0.1 ms per call of 80 ms).
+            if (left == n_steps) FC_HIP(hipStreamSynchronize(s));
+            FC_HIP(hipGraphLaunch(exec, s));
+            left -= k;
+        }
+    }
+    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
+    return f.leave();
+}
+
+// ---- likelihood / inversion on the RK4 grid ------------------------------------------------------------------------------------------
+// x from ts[0] to ts[n_points-1] with rk4_step on the caller's grid (log p needs it walked from t = 1 to t = 0), every evaluation a
+// training-mode forward followed by the backward plan's data-gradient chain with the probe as output cotangent (vjp_run), the stage
+// kernels of ode.hip carrying a[b] = integral of eps^T (dv/dx) eps dt.  The grid is known, so nothing is decided on the host: the call
+// returns with the whole loop queued.  Direct launches (4 (n_points - 1) forwards + chains); the arena ends up holding the last stage's
+// forward, which belongs to nobody: the serial moves and a later backward re-runs its own forward.
+int fc_unet_log_likelihood(fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
+                           const int64_t* ids, const float* mask, int mask_is_ones, const float* probe_dev, double* a_out_dev,
+                           double* logp_out_dev, void* stream) {
+    if (!u || !x_dev || !ts_host || !probe_dev || !a_out_dev || !logp_out_dev || B < 1) return fail(FC_E_ARG, "fc_unet_log_likelihood: null argument");
+    if (n_points < 2) return fail(FC_E_ARG, "fc_unet_log_likelihood: the time grid needs at least two points");
+    if (reinterpret_cast<uintptr_t>(probe_dev) & 15) return fail(FC_E_ARG, "fc_unet_log_likelihood: probe_dev must be 16-byte aligned (the kernels read it as float4)");
+    CallFrame f;
+    FC_TRY(f.begin(u, B, H, W, ids, 0.0f, mask, mask_is_ones, stream));      // no guidance
+    if (!u->keep_all) return fail(FC_E_STATE, "fc_unet_log_likelihood: no backward plan for this shape; call fc_unet_train_reserve");
+    FC_TRY(vjp_check(u, B, H, W, "fc_unet_log_likelihood"));
+    IntegratorState& ig = u->ig;
+    const int m = u->cfg.channels * H * W;
+    hipStream_t s = f.s;
+    if (!ig.ll_g) {
+        FC_TRY(ig.get(&ig.ll_d, (size_t)u->maxB * 3, "integrator.likelihood"));
+        FC_TRY(ig.get(&ig.ll_g, (size_t)u->maxB * m, "integrator.likelihood"));
+    }
+    FC_TRY(f.enter());
+    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
+    FC_HIP(hipMemsetAsync(a_out_dev, 0, (size_t)B * sizeof(double), s));
+    FwdCtx c = integrator_ctx(f);
+    c.d_out = probe_dev; c.dx_out = ig.ll_g;
+    auto eval = [&](const float* x) -> int {      // v2 = v(x, tvec), ll_g = (dv/dx)^T probe
+        c.x = x;
+        FC_TRY(run_plan(u->plan, c, s));
+        return vjp_run(u, c, s);
+    };
+    for (int i = 0; i + 1 < n_points; ++i) {
+        FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, B, s));
+        FC_TRY(eval(ig.y));                                                                                                              // k1, g1
+        FC_TRY(ode_ll_stage_launch(ig.sc, ig.y, ig.xs, ig.k1, ig.v2, ig.ll_g, probe_dev, ig.ll_d, 0, B, m, 0, 1, t_scale, ig.tvec, s));  // y + dt*k1/2, t+dt/2
+        FC_TRY(eval(ig.xs));                                                                                                             // k2, g2
+        FC_TRY(ode_ll_stage_launch(ig.sc, ig.y, ig.xs, ig.k2, ig.v2, ig.ll_g, probe_dev, ig.ll_d, 1, B, m, 0, 1, t_scale, ig.tvec, s));  // y + dt*k2/2, t+dt/2
+        FC_TRY(eval(ig.xs));                                                                                                             // k3, g3
+        FC_TRY(ode_ll_stage_launch(ig.sc, ig.y, ig.xs, ig.k3, ig.v2, ig.ll_g, probe_dev, ig.ll_d, 2, B, m, 1, 2, t_scale, ig.tvec, s));  // y + dt*k3, t+dt
+        FC_TRY(eval(ig.xs));                                                                                                             // k4, g4
+        FC_TRY(ode_ll_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.ll_g, probe_dev, ig.ll_d, a_out_dev, B, m, s));
+    }
+    FC_TRY(ode_ll_logp_launch(ig.y, a_out_dev, logp_out_dev, B, m, s));
+    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
+    return f.leave();
+}
+
+int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_dev, int batch, int64_t per_sample, void* stream) {
+    if (!probe_dev || !g_dev || !out_dev) return fail(FC_E_ARG, "fc_debug_probe_dot: null argument");
+    if ((reinterpret_cast<uintptr_t>(probe_dev) | reinterpret_cast<uintptr_t>(g_dev)) & 15)
+        return fail(FC_E_ARG, "fc_debug_probe_dot: inputs must be 16-byte aligned (read as float4)");
+    if (per_sample < 1 || per_sample > 0x7fffffff) return fail(FC_E_SHAPE, "fc_debug_probe_dot: bad element count");
+    return ode_ll_dot_launch(probe_dev, g_dev, out_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
+}
+
+// ---- adaptive RK45 ----------------------------------------------------------------------------------------------------------------
+// Both modes run ode.hip's grouped kernels: the batch-coupled solve is one controller over all B*C*H*W unknowns, the per-sample solve
+// one controller per sample.  Each mode keeps the partition it was introduced with -- it fixes the summation order of the norms and
+// with it the bits: coupled, one workgroup per 1024 unknowns of the batch, at most 2048 (the elementwise grid of ode.hip); per sample,
+// at most 64, so that a sample's step sequence depends on C*H*W alone, not on the batch size.
+static constexpr int kRk45MaxAttempts = 10000;     // a field that never settles raises instead of spinning (scipy has no such cap)
+static constexpr int kRk45CoupledChunks = 2048, kRk45PerSampleChunks = 64;
+
+static Rk45Groups rk45_groups(const fc_unet* u, int B, bool per_sample) {
+    const int m = u->cfg.channels * u->H * u->W;
+    return per_sample ? Rk45Groups{B, 1, m, rk45_chunks(m, kRk45PerSampleChunks)}
+                      : Rk45Groups{1, B, B * m, rk45_chunks(B * m, kRk45CoupledChunks)};
+}
+
+// The controller state, allocated by the first RK45 call (plan lifetime) so handles that never use it keep their footprint; the
+// partial sums fit either mode's partition.
+static int alloc_rk45(fc_unet* u) {
+    IntegratorState& ig = u->ig;
+    const size_t nstate = (size_t)u->maxB * u->cfg.channels * u->H * u->W;
+    const char* tag = "integrator.rk45";
+    const Rk45Groups cg = rk45_groups(u, u->maxB, false), pg = rk45_groups(u, u->maxB, true);
+    const size_t parts = std::max((size_t)cg.G * cg.chunks, (size_t)pg.G * pg.chunks);
+    FC_TRY(ig.get(&ig.rk_y, nstate, tag));
+    FC_TRY(ig.get(&ig.rk_ynew, nstate, tag));
+    for (int j = 0; j < 7; ++j) FC_TRY(ig.get(&ig.rk_k.k[j], nstate, tag));
+    FC_TRY(ig.get(&ig.rk_part, 2 * parts, tag));
+    FC_TRY(ig.get(&ig.rk_sum, 1, tag));
+    return ig.get(&ig.rk_st, u->maxB, tag);       // last: a first call that failed half-way allocates again
+}
+
+// one attempt of RungeKutta._step_impl for every group that still steps: five stages, y_new and f(t + h, y_new), the error norms,
+// the controllers, with a dense-output request (`ev`) the frames an accepted step serves, the commit, the status summary
+static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const FwdCtx& c, int cf, float cfg, float t_scale, const Rk45Eval* ev,
+                                hipStream_t s) {
+    const IntegratorState& ig = u->ig;
+    for (int st = 1; st <= 5; ++st) {
+        FC_TRY(rk45_stage_launch(g, ig.rk_st, st, ig.rk_y, ig.rk_k, ig.v2, cf, cfg, ig.xs, t_scale, ig.tvec, s));
+        FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
+    }
+    FC_TRY(rk45_finish_launch(g, ig.rk_st, ig.rk_y, ig.rk_ynew, ig.rk_k, ig.v2, cf, cfg, ig.xs, t_scale, ig.tvec, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
+    FC_TRY(rk45_error_launch(g, ig.rk_st, ig.rk_y, ig.rk_ynew, ig.rk_k, ig.v2, cf, cfg, ig.rk_part, s));
+    FC_TRY(rk45_control_launch(g, ig.rk_st, ig.rk_part, ev, s));
+    if (ev) FC_TRY(rk45_dense_launch(g, ig.rk_st, ev, ig.rk_y, ig.rk_k, s));       // reads y and K0..K6 before the commit replaces them
+    FC_TRY(rk45_commit_launch(g, ig.rk_st, ig.rk_y, ig.rk_ynew, ig.rk_k.k[0], ig.rk_k.k[6], s));
+    return rk45_status_launch(g, ig.rk_st, ig.rk_sum, s);
+}
+
+// solve_ivp's checks of t_eval, with its messages
+static int check_t_eval(const char* fn, const double* te, int n_eval, double t0, double t1) {
+    const double lo = std::min(t0, t1), hi = std::max(t0, t1);
+    for (int j = 0; j < n_eval; ++j)
+        if (!(te[j] >= lo && te[j] <= hi)) return fail(FC_E_ARG, std::string(fn) + ": Values in `t_eval` are not within `t_span`.");
+    for (int j = 1; j < n_eval; ++j) {
+        const double d = te[j] - te[j - 1];
+        if ((t1 > t0 && d <= 0) || (t1 < t0 && d >= 0))
+            return fail(FC_E_ARG, std::string(fn) + ": Values in `t_eval` are not properly sorted.");
+    }
+    return FC_OK;
+}
+
+// The dense-output request of this call in the handle's device record (header, then the times), ahead of the solve on `s`.  The record
+// grows only when a call brings more times than any before; captured attempts bake its address.
+static int stage_rk45_eval(fc_unet* u, const double* te, int n_eval, float* frames_dev, hipStream_t s) {
+    IntegratorState& ig = u->ig;
+    if (n_eval > ig.rk_ev_cap) {
+        FC_HIP(hipStreamSynchronize(s));
+        if (ig.rk_ev) dev_free(ig.rk_ev);
+        ig.rk_ev = nullptr; ig.rk_ev_cap = 0;
+        const int cap = n_eval < 1024 ? 1024 : n_eval;
+        FC_TRY(dev_alloc(reinterpret_cast<void**>(&ig.rk_ev), sizeof(Rk45Eval) + (size_t)cap * sizeof(double), "integrator.rk45_eval"));
+        ig.rk_ev_cap = cap;
+        ig.drop_graphs();
+    }
+    std::vector<unsigned char> rec(sizeof(Rk45Eval) + (size_t)n_eval * sizeof(double));
+    const Rk45Eval head{frames_dev, n_eval, 0};
+    std::memcpy(rec.data(), &head, sizeof(head));
+    std::memcpy(rec.data() + sizeof(head), te, (size_t)n_eval * sizeof(double));
+    // pageable source: the runtime stages it before returning (as the time grid of fc_unet_integrate)
+    FC_HIP(hipMemcpyAsync(ig.rk_ev, rec.data(), rec.size(), hipMemcpyHostToDevice, s));
+    return FC_OK;
+}
+
+// fc_unet_integrate_rk45 (per_sample = false), fc_unet_integrate_rk45_per_sample and, with n_eval > 0, fc_unet_integrate_rk45_dense;
+// `fn` names the entry point in argument errors
+static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_dev, int B, int H, int W, double t0, double t1,
+                          double rtol, double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask,
+                          int mask_is_ones, const double* t_eval, int n_eval, float* frames_dev, int* counters, void* stream) {
+    if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, std::string(fn) + ": bad argument");
+    if (n_eval < 0 || (n_eval > 0 && (!t_eval || !frames_dev || (reinterpret_cast<uintptr_t>(frames_dev) & 15))))
+        return fail(FC_E_ARG, std::string(fn) + ": t_eval needs its times and a 16-byte aligned frames buffer");
+    if (!(atol >= 0)) return fail(FC_E_ARG, std::string(fn) + ": `atol` must be positive.");      // validate_tol
+    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(FC_E_ARG, std::string(fn) + ": t0 and t1 must be finite");
+    const double eps100 = 100 * 2.220446049250313e-16;
+    if (rtol < eps100) rtol = eps100;                                                                         // validate_tol (host warns)
+    FC_TRY(check_t_eval(fn, t_eval, n_eval, t0, t1));
+    CallFrame f;
+    FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
+    IntegratorState& ig = u->ig;
+    const Rk45Groups g = rk45_groups(u, B, per_sample);
+    for (int i = 0; i < g.G; ++i) { counters[3 * i] = 1; counters[3 * i + 1] = counters[3 * i + 2] = 0; }   // nfev, accepted, rejected
+    const int n = f.n, cf = f.cfg_on ? 1 : 0;
+    hipStream_t s = f.s;
+    if (t0 == t1) {                              // scipy: one evaluation, no step, y0 returned; every requested time is t0
+        for (int j = 0; j < n_eval; ++j) FC_HIP(hipMemcpyAsync(frames_dev + (size_t)j * n, x_dev, f.nbytes, hipMemcpyDeviceToDevice, f.caller));
+        return FC_OK;
+    }
+    if (!ig.rk_st) FC_TRY(alloc_rk45(u));
+    if (!ig.rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); ig.rk_host = static_cast<Rk45Status*>(hp); }
+    if (!ig.ev_rk) FC_HIP(hipEventCreateWithFlags(&ig.ev_rk, hipEventDisableTiming));
+
+    FC_TRY(f.enter());
+    if (n_eval > 0) FC_TRY(stage_rk45_eval(u, t_eval, n_eval, frames_dev, s));
+    const Rk45Eval* ev = n_eval > 0 ? ig.rk_ev : nullptr;
+
+    // f(t0, y0) and select_initial_step of every group (two forwards, no graph)
+    FwdCtx c = integrator_ctx(f);
+    c.x = ig.xs;   // every forward of the solve reads the stage input the RK45 kernels write
+    FC_TRY(rk45_setup_launch(g, x_dev, ig.rk_y, ig.xs, ig.rk_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, ig.tvec, cf, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
+    FC_TRY(rk45_d01_launch(g, ig.rk_st, ig.rk_y, ig.rk_k.k[0], ig.v2, cf, cfg_strength, ig.rk_part, s));
+    FC_TRY(rk45_h0_launch(g, ig.rk_st, ig.rk_part, t_scale, ig.tvec, cf, s));
+    FC_TRY(rk45_y1_launch(g, ig.rk_st, ig.rk_y, ig.rk_k.k[0], ig.xs, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
+    FC_TRY(rk45_d2_launch(g, ig.rk_st, ig.rk_y, ig.rk_k.k[0], ig.v2, cf, cfg_strength, ig.rk_part, s));
+    FC_TRY(rk45_h1_launch(g, ig.rk_st, ig.rk_part, s));
+    FC_TRY(rk45_status_launch(g, ig.rk_st, ig.rk_sum, s));
+    FC_HIP(hipMemcpyAsync(ig.rk_host, ig.rk_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
+    // This wait is also the one fc_unet_integrate makes before its first replay: under AMD_DIRECT_DISPATCH=0 a graph submitted from this
+    // thread can overtake the plain launches and copies queued just before it (see there).
+    FC_HIP(hipStreamSynchronize(s));
+
+    // (an attempt with dense output has one more launch: a different graph)
+    GraphKey key = graph_key(f, per_sample ? GraphKey::Rk45PerSample : GraphKey::Rk45Coupled, cfg_strength, t_scale);
+    key.dense = ev != nullptr;
+    auto attempt = [&] { return enqueue_rk45_attempt(u, g, c, cf, cfg_strength, t_scale, ev, s); };
+    while (ig.rk_host->unfinished > 0) {
+        if (no_graph()) {
+            FC_TRY(attempt());
+        } else {   // one attempt = one graph: 6 plan runs and 10 (11 with dense output) small launches, a single chain (no parallel branches)
+            hipGraphExec_t exec = nullptr;
+            FC_TRY(cached_graph(u, key, s, attempt, &exec));
+            FC_HIP(hipGraphLaunch(exec, s));
+        }
+        // the 16-byte summary behind every attempt: one small host wait per six forwards
+        FC_HIP(hipMemcpyAsync(ig.rk_host, ig.rk_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
+        FC_HIP(hipEventRecord(ig.ev_rk, s));
+        FC_HIP(hipEventSynchronize(ig.ev_rk));
+    }
+    std::vector<Rk45State> st(g.G);      // the controller records, once at the end
+    FC_HIP(hipMemcpyAsync(st.data(), ig.rk_st, (size_t)g.G * sizeof(Rk45State), hipMemcpyDeviceToHost, s));
+    FC_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < g.G; ++i) { counters[3 * i] = st[i].nfev; counters[3 * i + 1] = st[i].accepted; counters[3 * i + 2] = st[i].rejected; }
+    const int failed = ig.rk_host->failed;
+    if (!failed) FC_TRY(rk45_out_launch(ig.rk_y, x_dev, n, s));
+    FC_TRY(f.leave());
+    if (!failed) return FC_OK;
+    if (!per_sample) {
+        if (st[0].failed == 1) return fail(FC_E_STATE, "rk45: Required step size is less than spacing between numbers.");
+        return fail(FC_E_STATE, "rk45: no convergence after " + std::to_string(st[0].attempts) + " attempts (t = " +
+                                    std::to_string(st[0].t) + ", h = " + std::to_string(st[0].h_abs) + ")");
+    }
+    std::string msg = "rk45 per sample: " + std::to_string(failed) + " of " + std::to_string(B) + " samples failed;";
+    for (int b = 0; b < B; ++b) {
+        if (st[b].failed == 1) msg += " sample " + std::to_string(b) + ": Required step size is less than spacing between numbers.";
+        else if (st[b].failed) msg += " sample " + std::to_string(b) + ": no convergence after " + std::to_string(st[b].attempts) +
+                                      " attempts (t = " + std::to_string(st[b].t) + ", h = " + std::to_string(st[b].h_abs) + ").";
+    }
+    return fail(FC_E_STATE, msg);
+}
+
+int fc_unet_integrate_rk45(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
+                                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
+                                      int* counters, void* stream) {
+    return integrate_rk45(u, false, "fc_unet_integrate_rk45", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength, mask,
+                          mask_is_ones, nullptr, 0, nullptr, counters, stream);
+}
+
+int fc_unet_integrate_rk45_per_sample(fc_unet* u, float* x_dev, int B, int H, int W, double t0, double t1, double rtol, double atol,
+                                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
+                                      int* counters, void* stream) {
+    return integrate_rk45(u, true, "fc_unet_integrate_rk45_per_sample", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids, cfg_strength,
+                          mask, mask_is_ones, nullptr, 0, nullptr, counters, stream);
+}
+
+int fc_unet_integrate_rk45_dense(fc_unet* u, int per_sample, float* x_dev, int B, int H, int W, double t0, double t1, double rtol,
+                                 double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones,
+                                 const double* t_eval_host, int n_eval, float* frames_dev, int* counters, void* stream) {
+    return integrate_rk45(u, per_sample != 0, "fc_unet_integrate_rk45_dense", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids,
+                          cfg_strength, mask, mask_is_ones, t_eval_host, n_eval, frames_dev, counters, stream);
+}
+
+}  // extern "C"

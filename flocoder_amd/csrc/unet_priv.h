@@ -1,10 +1,79 @@
-// The velocity U-Net object behind the fc_unet_* entry points (unet.hip: parameters, forward plan, integrator;
-// unet_backward.hip: backward plan of the training step).
+// The velocity U-Net object behind the fc_unet_* entry points (unet.hip: parameters, forward plan, handle lifecycle;
+// unet_integrate.hip: the integrators; unet_backward.hip: backward plan of the training step).
 #pragma once
 #include <map>
 #include <tuple>
 
 #include "plan.h"
+
+namespace fc {
+
+// What a cached graph was captured for: two calls share a graph exactly when every field agrees.
+struct GraphKey {
+    enum Kind { Euler, Rk4, Rk45Coupled, Rk45PerSample };
+    Kind kind = Euler;
+    int B = 0, mask_mode = 0;
+    bool cfg_on = false, has_ids = false;
+    bool pre_on = false;                                    // fixed grids: the conditioning table is in use
+    int steps = 0;                                          // fixed grids: consecutive intervals in the graph
+    bool dense = false;                                     // RK45: an attempt with t_eval has one more launch
+    uint32_t cfg_strength = 0, dt_euler = 0, t_scale = 0;   // the floats' bits (dt_euler: 0 for RK45)
+    auto tie() const { return std::tie(kind, B, mask_mode, cfg_on, has_ids, pre_on, steps, dense, cfg_strength, dt_euler, t_scale); }
+    bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
+};
+
+// Integrator state, library-owned so captured graphs never see caller pointers.  This part lives as long as the PLAN: allocated by
+// fc_unet_reserve (alloc_integrator) or by the first call that needs it, always through get(); release_plan() frees and nulls the
+// lot, so a lazy `if (!rk_st)` never trusts a pointer of a plan that is gone.
+struct IntegratorPlanState {
+    std::vector<void*> allocs;
+    int* step = nullptr;                     // step counter | evaluation counter
+    float *sc = nullptr, *tvec = nullptr;
+    float *y = nullptr, *xs = nullptr, *k1 = nullptr, *k2 = nullptr, *k3 = nullptr, *v2 = nullptr, *mask_own = nullptr;
+    int64_t* ids_own = nullptr;
+    // adaptive RK45 (fc_unet_integrate_rk45 / _per_sample): state, stage derivatives, up to maxB controllers, their partial sums and the
+    // status summary, allocated by the first call, so handles that never use it keep their footprint
+    double *rk_y = nullptr, *rk_ynew = nullptr, *rk_part = nullptr;
+    Rk45K rk_k{};
+    Rk45State* rk_st = nullptr;
+    Rk45Status* rk_sum = nullptr;
+    // likelihood (fc_unet_log_likelihood): g = (dv/dx)^T eps of the running stage and the per-sample stage sums d1..d3 of the running
+    // interval, allocated by the first call
+    float* ll_g = nullptr;
+    double* ll_d = nullptr;
+
+    template <class T> int get(T** out, size_t count, const char* tag) {
+        void* p = nullptr;
+        FC_TRY(dev_alloc(&p, (count ? count : 1) * sizeof(T), tag));
+        allocs.push_back(p);
+        *out = static_cast<T*>(p);
+        return FC_OK;
+    }
+};
+// ... and this part as long as the HANDLE (fc_unet_create makes the stream and its two events, release_handle() frees all of it).
+struct IntegratorState : IntegratorPlanState {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    fc::Rk45Status* rk_host = nullptr;       // the pinned RK45 status summary and its event: made by the first RK45 call
+    hipEvent_t ev_rk = nullptr;
+    // buffers that grow on demand; captured graphs bake their addresses, so whoever moves one drops the graphs
+    float* ts_dev = nullptr;                 // the time grid of the running fixed-grid call
+    int ts_cap = 0;
+    float* pre = nullptr;                    // conditioning of every evaluation of the running integration (CondFetch): tv | t_emb | h | c1 | ss
+    size_t pre_cap = 0;                      // floats
+    float* pre_ss = nullptr;                 // the [evaluation][row][S] part of `pre`
+    // dense output (fc_unet_integrate_rk45_dense): the call's requested times, their count and the frames pointer, on the device like the
+    // time grid, so a replayed attempt serves any request; allocated by the first such call, grows with the longest t_eval seen
+    Rk45Eval* rk_ev = nullptr;
+    int rk_ev_cap = 0;                       // times
+    std::map<GraphKey, hipGraphExec_t> graphs;   // every cached graph: they bake the addresses of the buffers they were captured with
+
+    void drop_graphs();
+    void release_plan();
+    void release_handle();
+};
+
+}  // namespace fc
 
 struct fc_unet : fc::ParamStore {
     fc_unet_config cfg{};
@@ -17,39 +86,8 @@ struct fc_unet : fc::ParamStore {
 
     int maxB = 0, H = 0, W = 0;
     fc::Plan plan;                           // the forward launch plan for up to maxB rows
-    std::vector<void*> int_allocs;           // integrator state
-
-    // integrator state (library-owned so captured graphs never see caller pointers)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    int* step = nullptr;
-    float *ts_dev = nullptr, *sc = nullptr, *tvec = nullptr;
-    int ts_cap = 0;
-    float *y = nullptr, *xs = nullptr, *k1 = nullptr, *k2 = nullptr, *k3 = nullptr, *v2 = nullptr, *mask_own = nullptr;
-    int64_t* ids_own = nullptr;
-    float* pre = nullptr;                    // conditioning of every evaluation of the running integration (CondFetch): tv | t_emb | h | c1 | ss
-    size_t pre_cap = 0;                      // floats
-    float* pre_ss = nullptr;                 // the [evaluation][row][S] part of `pre`
     fc::TembArgs temb_proto;                 // weights of the conditioning chain as the plan's own launches use them
-    std::map<std::tuple<int, int, int, int, uint32_t, uint32_t, uint32_t, int>, hipGraphExec_t> graphs;
-    // adaptive RK45 (fc_unet_integrate_rk45 / _per_sample): state, stage derivatives, up to maxB controllers, their partial sums and the
-    // status summary, allocated by the first call (in int_allocs, released with the plan), so handles that never use it keep their
-    // footprint; the pinned status summary and its event live as long as the handle
-    double *rk_y = nullptr, *rk_ynew = nullptr, *rk_part = nullptr;
-    fc::Rk45K rk_k{};
-    fc::Rk45State* rk_st = nullptr;
-    fc::Rk45Status* rk_sum = nullptr;
-    fc::Rk45Status* rk_host = nullptr;
-    hipEvent_t ev_rk = nullptr;
-    // dense output (fc_unet_integrate_rk45_dense): the call's requested times, their count and the frames pointer, on the device like the
-    // fixed-step integrator's time grid (`ts_dev`), so a replayed attempt serves any request; allocated by the first such call, grows
-    // with the longest t_eval seen, lives as long as the handle
-    fc::Rk45Eval* rk_ev = nullptr;
-    int rk_ev_cap = 0;                       // times
-    // likelihood (fc_unet_log_likelihood): g = (dv/dx)^T eps of the running stage and the per-sample stage sums d1..d3 of the running
-    // interval, allocated by the first call (in int_allocs, released with the plan)
-    float* ll_g = nullptr;
-    double* ll_d = nullptr;
+    fc::IntegratorState ig;                  // everything the integrators own (unet_integrate.hip)
 
     // Fused Block tails whose workgroups wait for each other (conv_dev.h) need the device to themselves.  `shared` = the caller said the
     // device is shared with other streams / processes (fc_unet_set_shared): plans are then built without such launches.  A wait that
@@ -87,6 +125,13 @@ struct fc_unet : fc::ParamStore {
 };
 
 namespace fc {
+// unet.hip: what every entry point that runs the plan checks, and the process-wide guard of the meeting launches
+int check_ready(const fc_unet* u, int rows, int H, int W);
+int check_poison(fc_unet* u);
+int meet_enter(fc_unet* u, hipStream_t s);
+int meet_leave(fc_unet* u, hipStream_t s);
+// unet_integrate.hip: integrator state for `rows` U-Net rows of the plan just built
+int alloc_integrator(fc_unet* u, int rows, int H, int W);
 // unet_backward.hip: the backward plan's data-gradient chain alone (fc_unet_vjp_x, fc_unet_log_likelihood)
 int vjp_check(fc_unet* u, int B, int H, int W, const char* who);
 int vjp_run(fc_unet* u, const FwdCtx& c, hipStream_t s);

@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from .unet import Unet, validate_t_eval
+from .unet import Unet, validate_t_eval, validate_tol
 
 
 def warp_time(t, dt=None, s=.5):
@@ -73,6 +73,33 @@ def _mask_flags(cond):
     return mask, ones
 
 
+def _conditioning(model, cond):
+    """``cond`` as the samplers take it (a cond dict, a class-id tensor as the legacy samplers, or None) -> ``(cond dict, class ids,
+    mask, mask_is_ones)``.  The last three are what the integrators of a ``flocoder_amd.Unet`` take and are made for one only: the mask
+    test is a host sync, so call this where the native path is taken."""
+    if cond is not None and not isinstance(cond, dict):
+        cond = {'class_cond': cond}
+    if not isinstance(model, Unet):
+        return cond, None, None, False
+    return (cond, cond.get('class_cond') if cond else None) + _mask_flags(cond)
+
+
+def _start(source, shape, device):
+    """The fp32 contiguous tensor an integrator updates in place: a copy of ``source`` on ``device``, or noise of ``shape``."""
+    x = source if source is not None else torch.randn(shape, device=device)
+    return x.to(device=device, dtype=torch.float32).contiguous().clone()
+
+
+def _rk4_loop(v_func, x, ts, jitter_strength=None):
+    """``rk4_step`` along ``ts`` for models that are not a ``flocoder_amd.Unet``; with ``jitter_strength`` generate_latents_rk4's
+    random kicks (sampling.py:117-119)."""
+    for i in range(len(ts) - 1):
+        x = rk4_step(v_func, x, ts[i], ts[i + 1] - ts[i])
+        if jitter_strength is not None and random.random() < 0.1 and jitter_strength > 0:
+            x += torch.randn_like(x) * jitter_strength * (1 - ts[i])
+    return x
+
+
 @torch.no_grad()
 def generate_latents_rk4(model, shape, n_steps=50, cond=None, cfg_strength=3.0, source=None, init_latents=None,
                          init_strength=0.0, jitter_strength=0, debug=False):
@@ -89,21 +116,16 @@ def generate_latents_rk4(model, shape, n_steps=50, cond=None, cfg_strength=3.0, 
         n_steps = max(1, int(n_steps * (1.0 - init_strength)))
 
     if isinstance(model, Unet) and not jitter_strength:
-        x = current_points.to(device=device, dtype=torch.float32).contiguous().clone()
+        x = _start(current_points, None, device)
         if len(ts) > 1:
-            cls = cond.get('class_cond') if isinstance(cond, dict) else None
-            mask, ones = _mask_flags(cond)
+            _, cls, mask, ones = _conditioning(model, cond)
             model.integrate("rk4", x, ts, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask, mask_is_ones=ones)
         return x, n_steps * 4
 
     ts = ts.to(device)
     t_vec_template = torch.zeros(shape[0], device=device, dtype=dtype)
     v_func = partial(v_func_cfg, model, cond, cfg_strength, t_vec_template)
-    for i in range(len(ts) - 1):
-        current_points = rk4_step(v_func, current_points, ts[i], ts[i + 1] - ts[i])
-        if random.random() < 0.1 and jitter_strength > 0:
-            current_points += torch.randn_like(current_points) * jitter_strength * (1 - ts[i])
-    return current_points, n_steps * 4
+    return _rk4_loop(v_func, current_points, ts, jitter_strength), n_steps * 4
 
 
 @torch.no_grad()
@@ -114,14 +136,11 @@ def euler_sampler(model, shape, sample_N, device=None, cond=None, source=None, e
     CFG here; 0 keeps upstream behaviour).  Returns (latents on `device`, nfe)."""
     p0 = next(model.parameters())
     device = p0.device if device is None else torch.device(device)
-    if cond is not None and not isinstance(cond, dict):
-        cond = {'class_cond': cond}
-    x = (source if source is not None else torch.randn(shape, device=device)).to(device=device, dtype=torch.float32).contiguous().clone()
+    x = _start(source, shape, device)
     ts = euler_time_grid(sample_N, eps)
     dt = 1.0 / sample_N
+    cond, cls, mask, ones = _conditioning(model, cond)
     if isinstance(model, Unet):
-        cls = cond.get('class_cond') if cond else None
-        mask, ones = _mask_flags(cond)
         model.integrate("euler", x, ts, dt_euler=dt, class_ids=cls, cfg_strength=cfg_strength, mask=mask, mask_is_ones=ones)
         return x, sample_N
     for t in ts.tolist():
@@ -136,12 +155,6 @@ def _reverse_grid(n_steps, dtype=torch.float32):
     return rk4_time_grid(int(n_steps), dtype=dtype).flip(0)
 
 
-def _cond_dict(cond):
-    if cond is not None and not isinstance(cond, dict):
-        cond = {'class_cond': cond}
-    return cond
-
-
 @torch.no_grad()
 def invert_latents(model, latents, n_steps=50, cond=None):
     """Data -> noise: the probability-flow ODE from t = 1 back to t = 0 on ``rk4_time_grid(n_steps)`` REVERSED, with the RK4 step and
@@ -150,24 +163,19 @@ def invert_latents(model, latents, n_steps=50, cond=None):
     true number of velocity evaluations, ``4 (n_steps - 1)`` -- not ``generate_latents_rk4``'s ``n_steps * 4`` bookkeeping.
     A ``flocoder_amd.Unet`` runs the captured inference path (``Unet.integrate`` takes a grid in either direction); any other callable
     goes through ``rk4_step`` on the latents' device."""
-    cond = _cond_dict(cond)
     ts = _reverse_grid(n_steps, torch.float32 if isinstance(model, Unet) else latents.dtype)
     nfe = 4 * (len(ts) - 1)
     if isinstance(model, Unet):
         if not latents.is_cuda:
             raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only")
-        x = latents.to(dtype=torch.float32).contiguous().clone()
-        cls = cond.get('class_cond') if cond else None
-        mask, ones = _mask_flags(cond)
+        x = _start(latents, None, latents.device)
+        _, cls, mask, ones = _conditioning(model, cond)
         model.integrate("rk4", x, ts, class_ids=cls, cfg_strength=0.0, mask=mask, mask_is_ones=ones)
         return x, nfe
-    x = latents
-    ts = ts.to(x.device)
-    t_vec_template = torch.zeros(x.shape[0], device=x.device, dtype=x.dtype)
+    cond = _conditioning(model, cond)[0]
+    t_vec_template = torch.zeros(latents.shape[0], device=latents.device, dtype=latents.dtype)
     v_func = partial(v_func_cfg, model, cond, 0.0, t_vec_template)
-    for i in range(len(ts) - 1):
-        x = rk4_step(v_func, x, ts[i], ts[i + 1] - ts[i])
-    return x, nfe
+    return _rk4_loop(v_func, latents, ts.to(latents.device)), nfe
 
 
 def _make_probe(probe, latents, generator):
@@ -213,17 +221,15 @@ def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", ge
     restore_plan=False)`` and ``Unet.release_training_plan()``)."""
     if cfg_strength:
         raise ValueError("log_likelihood takes no classifier-free guidance: the guided field is not the flow of a density the model defines")
-    cond = _cond_dict(cond)
     unet = isinstance(model, Unet)
     ts = _reverse_grid(n_steps, torch.float32 if unet else latents.dtype)
     nfe = 4 * (len(ts) - 1)
     if unet and not latents.is_cuda:
         raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
     eps = _make_probe(probe, latents.float() if unet else latents, generator)
+    cond, cls, mask, ones = _conditioning(model, cond)
     if unet:
-        x = latents.to(dtype=torch.float32).contiguous().clone()
-        cls = cond.get('class_cond') if cond else None
-        mask, ones = _mask_flags(cond)
+        x = _start(latents, None, latents.device)
         _, logp = model.log_likelihood(x, ts, eps, class_ids=cls, mask=mask, mask_is_ones=ones)
         return logp, x, nfe
     logp, z, _ = _log_likelihood_torch(model, latents, ts.to(latents.device), cond, eps)
@@ -259,18 +265,6 @@ def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999):
     D = z[0].numel()
     logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
     return logp, z, a
-
-
-def _validate_tol(rtol, atol):
-    """scipy/integrate/_ivp/common.py validate_tol for scalar tolerances."""
-    eps100 = 100 * float(torch.finfo(torch.float64).eps)
-    if rtol < eps100:
-        import warnings
-        warnings.warn(f"At least one element of `rtol` is too small. Setting `rtol = np.maximum(rtol, {eps100})`.", stacklevel=3)
-        rtol = eps100
-    if atol < 0:
-        raise ValueError("`atol` must be positive.")
-    return rtol, atol
 
 
 def _solve_ivp_rk45(ode_func, eps, y0, rtol, atol, t_eval):
@@ -324,16 +318,13 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
     of the call without ``t_eval``.  ``latents`` is still the solver's state at t = 1 -- unlike ``solve_ivp(..., t_eval=...).y[:, -1]``,
     which is the LAST REQUESTED time (at ``t_eval[-1] == 1`` the interpolant there: equal to ``latents`` to rounding, not in bits).
     Bad times raise solve_ivp's ValueErrors before any work."""
-    rtol, atol = _validate_tol(rtol, atol)
+    rtol, atol = validate_tol(rtol, atol)
     te = None if t_eval is None else validate_t_eval(t_eval, eps, 1)
     p0 = next(model.parameters())
     device = p0.device if device is None else torch.device(device)
-    if cond is not None and not isinstance(cond, dict):
-        cond = {'class_cond': cond}
-    x = (source if source is not None else torch.randn(shape, device=device)).to(device=device, dtype=torch.float32).contiguous().clone()
+    x = _start(source, shape, device)
+    cond, cls, mask, ones = _conditioning(model, cond)
     if isinstance(model, Unet):
-        cls = cond.get('class_cond') if cond else None
-        mask, ones = _mask_flags(cond)
         nfev, *rest = model.integrate_rk45(x, eps, 1.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
                                            mask_is_ones=ones, per_sample=per_sample, t_eval=te)
         nfe = int(nfev.max()) if per_sample else nfev

@@ -58,6 +58,22 @@ def validate_t_eval(t_eval, t0: float, t1: float):
     return te
 
 
+def validate_tol(rtol, atol):
+    """scipy/integrate/_ivp/common.py validate_tol for scalar tolerances (the warning names the caller of the sampler / integrator
+    that was given them)."""
+    eps100 = 100 * float(torch.finfo(torch.float64).eps)
+    if rtol < eps100:
+        import warnings
+        warnings.warn(f"At least one element of `rtol` is too small. Setting `rtol = np.maximum(rtol, {eps100})`.", stacklevel=3)
+        rtol = eps100
+    if atol < 0:
+        raise ValueError("`atol` must be positive.")
+    return rtol, atol
+
+
+_GPU_ONLY = "flocoder_amd integrators run on MI355X (gfx950) only"
+
+
 class _UnetFunction(torch.autograd.Function):
     """Autograd bridge: forward and backward both run in the library; parameters receive ``.grad`` as torch expects, and so do
     ``x`` and the mask when they require it (the inpainting step reaches the MaskEncoder through both, train_flow.py:146-147)."""
@@ -379,20 +395,16 @@ class Unet(NativeModule):
         self._synced = self._weights_version()
 
     # ------------------------------------------------------------------ integrators (used by flocoder_amd.sampling)
-    def integrate(self, method: str, x: torch.Tensor, ts: torch.Tensor, *, dt_euler: float = 0.0, t_scale: float = 999.0,
-                  class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,
-                  mask_is_ones: bool = False, check: bool = True) -> torch.Tensor:
-        """Integrate ``x`` in place along the fp32 grid ``ts`` with the hipGraph-captured step; returns ``x``.  With ``check`` (default)
-        the call waits for the trajectory when the plan contains cross-workgroup waits and raises if one timed out -- a caller never
-        receives samples from a plan whose residency assumption broke.  ``check=False`` keeps the call asynchronous; the error then
-        surfaces at the next call on the model or at ``check_errors()``."""
+    def _integrator_args(self, x, class_ids, mask, cfg_strength=0.0, cpu_error=_GPU_ONLY):
+        """What every integrator method checks of ``x`` and does to its conditioning -> ``(class ids, mask, U-Net rows per evaluation,
+        native handle)``: ids as int64 ``[batch]`` in range, or None for a model without classes; the mask as fp32 of x's shape, or None
+        for a model without mask conditioning; a guided call evaluates two rows per sample."""
         if not x.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only")
+            raise RuntimeError(cpu_error)
         dev = x.device
-        bsz, ch, h, w = x.shape
+        bsz = x.shape[0]
         if not x.is_contiguous() or x.dtype != torch.float32:
             raise ValueError("x must be a contiguous fp32 tensor (it is updated in place)")
-        code = {"euler": B.FC_METHOD_EULER, "rk4": B.FC_METHOD_RK4}[method]
         if class_ids is not None and not self.class_condition:
             class_ids = None
         if class_ids is not None:
@@ -407,14 +419,32 @@ class Unet(NativeModule):
             if mask.shape != x.shape:
                 raise ValueError("mask_cond must have the shape of x")
         rows = bsz * (2 if (class_ids is not None and cfg_strength) else 1)
-        hnd = self._native(dev)
+        return class_ids, mask, rows, self._native(dev)
+
+    @staticmethod
+    def _integrator_check(hnd, dev, check: bool) -> None:
+        """The tail of every integrator method: with ``check``, wait for the trajectory when the plan contains cross-workgroup waits and
+        raise if one timed out."""
+        if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
+            B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
+
+    def integrate(self, method: str, x: torch.Tensor, ts: torch.Tensor, *, dt_euler: float = 0.0, t_scale: float = 999.0,
+                  class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,
+                  mask_is_ones: bool = False, check: bool = True) -> torch.Tensor:
+        """Integrate ``x`` in place along the fp32 grid ``ts`` with the hipGraph-captured step; returns ``x``.  With ``check`` (default)
+        the call waits for the trajectory when the plan contains cross-workgroup waits and raises if one timed out -- a caller never
+        receives samples from a plan whose residency assumption broke.  ``check=False`` keeps the call asynchronous; the error then
+        surfaces at the next call on the model or at ``check_errors()``."""
+        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength)
+        code = {"euler": B.FC_METHOD_EULER, "rk4": B.FC_METHOD_RK4}[method]
+        dev = x.device
+        bsz, _, h, w = x.shape
         B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
         ts_host = ts.detach().to("cpu", torch.float32).contiguous()
         B.check(B.lib().fc_unet_integrate(hnd, code, B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)),
                                           ts_host.numel(), float(dt_euler), float(t_scale), B.ptr(class_ids),
                                           float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), B.current_stream(dev)))
-        if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
-            B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
+        self._integrator_check(hnd, dev, check)
         return x
 
     def log_likelihood(self, x: torch.Tensor, ts: torch.Tensor, probe: torch.Tensor, *, t_scale: float = 999.0,
@@ -431,32 +461,15 @@ class Unet(NativeModule):
         of a model that never computed a likelihood.  That costs a device synchronisation and two plan builds per call; a caller who makes
         many likelihood calls in a row passes ``restore_plan=False`` and calls ``release_training_plan()`` once at the end.  A model
         that trains (it already is in the training form) is left as it is."""
-        if not x.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+        class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask, cpu_error=_GPU_ONLY + "; there is no CPU path")
         dev = x.device
-        bsz, ch, h, w = x.shape
-        if not x.is_contiguous() or x.dtype != torch.float32:
-            raise ValueError("x must be a contiguous fp32 tensor (it is updated in place)")
+        bsz, _, h, w = x.shape
         if probe.shape != x.shape or probe.device != dev or probe.dtype != torch.float32 or not probe.is_contiguous():
             raise ValueError("probe must be a contiguous fp32 tensor of x's shape on x's device")
         if probe.data_ptr() % 16:
             probe = probe.clone()                       # a view at an odd storage offset: the kernels read the probe as float4
         if ts.numel() < 2:
             raise ValueError("the time grid needs at least two points")
-        if class_ids is not None and not self.class_condition:
-            class_ids = None
-        if class_ids is not None:
-            class_ids = class_ids.to(device=dev, dtype=torch.int64).contiguous()
-            if class_ids.shape != (bsz,):
-                raise ValueError("class ids must have shape [batch]")
-            self.check_class_ids(class_ids)
-        if mask is not None and not self._cfg.mask_cond:
-            mask = None
-        if mask is not None:
-            mask = mask.to(device=dev, dtype=torch.float32).contiguous()
-            if mask.shape != x.shape:
-                raise ValueError("mask_cond must have the shape of x")
-        hnd = self._native(dev)
         lib = B.lib()
         was_training_form = bool(lib.fc_unet_train_form(hnd))
         rows0, h0, w0 = C.c_int(0), C.c_int(0), C.c_int(0)
@@ -468,8 +481,7 @@ class Unet(NativeModule):
         B.check(B.lib().fc_unet_log_likelihood(hnd, B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)),
                                                ts_host.numel(), float(t_scale), B.ptr(class_ids), B.ptr(mask), int(mask_is_ones),
                                                B.ptr(probe), B.ptr(a), B.ptr(logp), B.current_stream(dev)))
-        if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
-            B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
+        self._integrator_check(hnd, dev, check)
         if restore_plan and not was_training_form:
             self.release_training_plan()
             if rows0.value > 0:                         # the reservation the caller had, in the form it had
@@ -503,34 +515,10 @@ class Unet(NativeModule):
         direction of integration (ValueError with scipy's messages otherwise, before anything else is looked at).  When the solve
         fails the frames are discarded with it."""
         te = None if t_eval is None else validate_t_eval(t_eval, t0, t1)
-        if not x.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
-        if atol < 0:
-            raise ValueError("`atol` must be positive.")
-        eps100 = 100 * float(torch.finfo(torch.float64).eps)
-        if rtol < eps100:
-            import warnings
-            warnings.warn(f"At least one element of `rtol` is too small. Setting `rtol = np.maximum(rtol, {eps100})`.", stacklevel=2)
-            rtol = eps100
+        rtol, atol = validate_tol(rtol, atol)
+        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength, cpu_error=_GPU_ONLY + "; there is no CPU path")
         dev = x.device
-        bsz, ch, h, w = x.shape
-        if not x.is_contiguous() or x.dtype != torch.float32:
-            raise ValueError("x must be a contiguous fp32 tensor (it is updated in place)")
-        if class_ids is not None and not self.class_condition:
-            class_ids = None
-        if class_ids is not None:
-            class_ids = class_ids.to(device=dev, dtype=torch.int64).contiguous()
-            if class_ids.shape != (bsz,):
-                raise ValueError("class ids must have shape [batch]")
-            self.check_class_ids(class_ids)
-        if mask is not None and not self._cfg.mask_cond:
-            mask = None
-        if mask is not None:
-            mask = mask.to(device=dev, dtype=torch.float32).contiguous()
-            if mask.shape != x.shape:
-                raise ValueError("mask_cond must have the shape of x")
-        rows = bsz * (2 if (class_ids is not None and cfg_strength) else 1)
-        hnd = self._native(dev)
+        bsz, _, h, w = x.shape
         B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
         counters = (C.c_int * (3 * bsz if per_sample else 3))()
         head = (B.ptr(x), bsz, h, w, float(t0), float(t1), float(rtol), float(atol), float(t_scale), B.ptr(class_ids),
@@ -543,8 +531,7 @@ class Unet(NativeModule):
             frames = torch.empty((len(te),) + tuple(x.shape), dtype=torch.float32, device=dev)
             B.check(B.lib().fc_unet_integrate_rk45_dense(hnd, int(per_sample), *head, te.ctypes.data_as(C.POINTER(C.c_double)), len(te),
                                                          B.ptr(frames), counters, B.current_stream(dev)))
-        if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
-            B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
+        self._integrator_check(hnd, dev, check)
         if per_sample:
             c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
             out = (c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone())
