@@ -276,6 +276,21 @@ int ode_rk4_stage_launch(const float* sc, const float* y, float* xs, float* k_ou
 // y += (dt/6) * (k1 + 2*k2 + 2*k3 + v)
 int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v2, int n,
                          int cfg_on, float cfg, hipStream_t s);
+// measurement guidance (fc_unet_integrate_guided): the two launches above with v corrected towards ym = keep (.) x1 before it is used.
+// xin = the state the stage's forward read, tcur its time (0: t, 1: t + dt/2, 2: t + dt), gsc = {sigma_y^2, gamma} on the device,
+// q = (dv/dx)^T w of the same forward or NULL (identity form)
+int ode_rk4_gstage_launch(const float* sc, const float* gsc, const float* y, float* xs, float* k_out, const float* v2, const float* xin,
+                          const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg, int full, int tcur, int tsel,
+                          float t_scale, float* tvec, int rows, hipStream_t s);
+int ode_rk4_gfinal_launch(const float* sc, const float* gsc, float* y, const float* k1, const float* k2, const float* k3, const float* v2,
+                          const float* xin, const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg,
+                          hipStream_t s);
+// w = keep (ym - keep (xin + (1-t) v)) / (r2 keep^2 + s2): the cotangent of the exact form's data-gradient chain
+int ode_guide_w_launch(const float* sc, const float* gsc, const float* v, const float* xin, const float* ym, const float* keep, float* w,
+                       int n, int tcur, hipStream_t s);
+// out = v + gamma ((1-t)/t) w on caller tensors (fc_ode_guided_correct)
+int ode_guided_correct_launch(const float* v, const float* x, const float* ym, const float* keep, float* out, int n, float t, float s2,
+                              float gamma, hipStream_t s);
 // likelihood on the RK4 grid (one workgroup per sample of m elements, no CFG): the stage / final updates above plus
 // dst[3 b + slot] = sum eps g (stages 1..3), a[b] += (double(dt)/6)(d1 + 2 d2 + 2 d3 + sum eps g) (stage 4); tvec[b] as the stage kernel
 int ode_ll_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v, const float* g, const float* eps,

@@ -143,6 +143,152 @@ int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float
     return FC_OK;
 }
 
+// ================================================================================================ measurement guidance on the RK4 grid
+// fc_unet_integrate_guided: the RK4 step above with every stage velocity corrected towards a measurement ym = keep (.) x1 (the
+// reference's inpainting.py algorithm3 for a diagonal operator on the conditional-OT path).  With t the time of
+// the stage that produced v and x that stage's input state:
+//     x1 = x + (1-t) v      w = keep (ym - keep x1) / (r2 keep^2 + s2)   (0 where the denominator is 0)      r2 = (1-t)^2 / (t^2 + (1-t)^2)
+//     g  = w                      (identity)          g = w + (1-t) q,  q = (dv/dx)^T w      (exact)
+//     vc = v + c g                c = gamma (1-t) / t
+// The scalars om = 1-t, r2, c are formed in fp64 from the fp32 stage time and gamma and rounded once to fp32; s2 = sigma_y^2 is formed
+// the same way on the host.  The elementwise part is eleven single-rounded fp32 operations in the order written in guide_w /
+// guide_apply.  A correction term that is zero (gamma = 0, t = 1, keep = 0) leaves v's bits alone.
+struct GuideScalars { float om, r2, c, s2; };
+
+__device__ __forceinline__ GuideScalars guide_scalars(float t, float s2, float gamma) {
+    const double td = (double)t, om = 1.0 - td;
+    GuideScalars g;
+    g.om = (float)om;
+    g.r2 = (float)((om * om) / (td * td + om * om));
+    g.c = (float)(((double)gamma * om) / td);
+    g.s2 = s2;
+    return g;
+}
+__device__ __forceinline__ float guide_w(float v, float x, float ym, float a, const GuideScalars& g) {
+    const float x1 = add_(x, mul_(g.om, v));
+    const float res = sub_(ym, mul_(a, x1));
+    const float den = add_(mul_(g.r2, mul_(a, a)), g.s2);
+    return den == 0.f ? 0.f : __fdiv_rn(mul_(a, res), den);
+}
+__device__ __forceinline__ float guide_apply(float v, float g, const GuideScalars& gs) {
+    const float d = mul_(gs.c, g);
+    return d == 0.f ? v : add_(v, d);
+}
+__device__ __forceinline__ float4 guide_w4(const float4 v, const float4 x, const float4 ym, const float4 a, const GuideScalars& g) {
+    return make_float4(guide_w(v.x, x.x, ym.x, a.x, g), guide_w(v.y, x.y, ym.y, a.y, g), guide_w(v.z, x.z, ym.z, a.z, g),
+                       guide_w(v.w, x.w, ym.w, a.w, g));
+}
+// v corrected at element i; q == nullptr: identity form
+__device__ __forceinline__ float4 guide_v4(const float4 v, const float* xin, const float* ym, const float* keep, const float* q, int i,
+                                           const GuideScalars& g) {
+    float4 w = guide_w4(v, *reinterpret_cast<const float4*>(xin + i), *reinterpret_cast<const float4*>(ym + i),
+                        *reinterpret_cast<const float4*>(keep + i), g);
+    if (q) {
+        const float4 qv = *reinterpret_cast<const float4*>(q + i);
+        w.x = add_(w.x, mul_(g.om, qv.x)); w.y = add_(w.y, mul_(g.om, qv.y));
+        w.z = add_(w.z, mul_(g.om, qv.z)); w.w = add_(w.w, mul_(g.om, qv.w));
+    }
+    return make_float4(guide_apply(v.x, w.x, g), guide_apply(v.y, w.y, g), guide_apply(v.z, w.z, g), guide_apply(v.w, w.w, g));
+}
+// time of stage `sel` of the interval in flight, with the operations that published it to the U-Net: t | t + dt/2 | t + dt
+__device__ __forceinline__ float stage_t(float t, float dt, int sel) { return sel == 0 ? t : (sel == 1 ? add_(t, dt * 0.5f) : add_(t, dt)); }
+
+// ode_rk4_stage_kernel with the correction between load_v and the store of k.  xin: the state this stage's forward read (y for k1, xs
+// for k2 and k3; xs[i] is read before this thread overwrites it); tcur: that stage's time; gsc = {s2, gamma}.
+__global__ void __launch_bounds__(256) ode_rk4_gstage_kernel(const float* sc, const float* gsc, const float* y, float* xs, float* k_out,
+                                                             const float* v2, const float* xin, const float* ym, const float* keep,
+                                                             const float* q, int n, int cfg_on, float cfg, int full, int tcur, int tsel,
+                                                             float t_scale, float* tvec, int rows) {
+    const float t = sc[0], dt = sc[1];
+    if (blockIdx.x == 0) {
+        const float tv = mul_(stage_t(t, dt, tsel), t_scale);
+        for (int r = threadIdx.x; r < rows; r += 256) tvec[r] = tv;
+    }
+    const GuideScalars g = guide_scalars(stage_t(t, dt, tcur), gsc[0], gsc[1]);
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const float4 k = guide_v4(load_v(v2, i, n, cfg_on, cfg), xin, ym, keep, q, i, g);
+        *reinterpret_cast<float4*>(k_out + i) = k;
+        const float4 yv = *reinterpret_cast<const float4*>(y + i);
+        float4 o;
+        if (full) {   // y + dt*k3
+            o.x = add_(yv.x, mul_(dt, k.x)); o.y = add_(yv.y, mul_(dt, k.y));
+            o.z = add_(yv.z, mul_(dt, k.z)); o.w = add_(yv.w, mul_(dt, k.w));
+        } else {      // y + dt*k/2
+            o.x = add_(yv.x, mul_(dt, k.x) * 0.5f); o.y = add_(yv.y, mul_(dt, k.y) * 0.5f);
+            o.z = add_(yv.z, mul_(dt, k.z) * 0.5f); o.w = add_(yv.w, mul_(dt, k.w) * 0.5f);
+        }
+        *reinterpret_cast<float4*>(xs + i) = o;
+    }
+}
+
+// ode_rk4_final_kernel with k4 corrected at (xs, t + dt)
+__global__ void __launch_bounds__(256) ode_rk4_gfinal_kernel(const float* sc, const float* gsc, float* y, const float* k1, const float* k2,
+                                                             const float* k3, const float* v2, const float* xin, const float* ym,
+                                                             const float* keep, const float* q, int n, int cfg_on, float cfg) {
+    const float dt6 = __fdiv_rn(sc[1], 6.0f);
+    const GuideScalars g = guide_scalars(stage_t(sc[0], sc[1], 2), gsc[0], gsc[1]);
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const float4 k4 = guide_v4(load_v(v2, i, n, cfg_on, cfg), xin, ym, keep, q, i, g);
+        const float4 a = *reinterpret_cast<const float4*>(k1 + i), b = *reinterpret_cast<const float4*>(k2 + i),
+                     c = *reinterpret_cast<const float4*>(k3 + i);
+        float4 yv = *reinterpret_cast<float4*>(y + i);
+        yv.x = rk4_comb(yv.x, a.x, b.x, c.x, k4.x, dt6); yv.y = rk4_comb(yv.y, a.y, b.y, c.y, k4.y, dt6);
+        yv.z = rk4_comb(yv.z, a.z, b.z, c.z, k4.z, dt6); yv.w = rk4_comb(yv.w, a.w, b.w, c.w, k4.w, dt6);
+        *reinterpret_cast<float4*>(y + i) = yv;
+    }
+}
+
+// exact mode: w of the running stage, the cotangent the data-gradient chain takes (no guidance pair: v is the forward's output)
+__global__ void __launch_bounds__(256) ode_guide_w_kernel(const float* sc, const float* gsc, const float* v, const float* xin,
+                                                          const float* ym, const float* keep, float* w, int n, int tcur) {
+    const GuideScalars g = guide_scalars(stage_t(sc[0], sc[1], tcur), gsc[0], gsc[1]);
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256)
+        *reinterpret_cast<float4*>(w + i) = guide_w4(*reinterpret_cast<const float4*>(v + i), *reinterpret_cast<const float4*>(xin + i),
+                                                     *reinterpret_cast<const float4*>(ym + i), *reinterpret_cast<const float4*>(keep + i), g);
+}
+
+// fc_ode_guided_correct: the identity-form correction of one evaluation on caller tensors
+__global__ void __launch_bounds__(256) ode_guided_correct_kernel(const float* v, const float* x, const float* ym, const float* keep,
+                                                                 float* out, int n, float t, float s2, float gamma) {
+    const GuideScalars g = guide_scalars(t, s2, gamma);
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256)
+        *reinterpret_cast<float4*>(out + i) = guide_v4(*reinterpret_cast<const float4*>(v + i), x, ym, keep, nullptr, i, g);
+}
+
+int ode_rk4_gstage_launch(const float* sc, const float* gsc, const float* y, float* xs, float* k_out, const float* v2, const float* xin,
+                          const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg, int full, int tcur, int tsel,
+                          float t_scale, float* tvec, int rows, hipStream_t s) {
+    if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
+    if (tcur < 0 || tcur > 2) return fail(FC_E_ARG, "ode: stage time selector must lie in [0, 2]");
+    hipLaunchKernelGGL(ode_rk4_gstage_kernel, dim3(egrid(n)), dim3(256), 0, s, sc, gsc, y, xs, k_out, v2, xin, ym, keep, q, n, cfg_on, cfg,
+                       full, tcur, tsel, t_scale, tvec, rows);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_rk4_gfinal_launch(const float* sc, const float* gsc, float* y, const float* k1, const float* k2, const float* k3, const float* v2,
+                          const float* xin, const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg,
+                          hipStream_t s) {
+    if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
+    hipLaunchKernelGGL(ode_rk4_gfinal_kernel, dim3(egrid(n)), dim3(256), 0, s, sc, gsc, y, k1, k2, k3, v2, xin, ym, keep, q, n, cfg_on, cfg);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_guide_w_launch(const float* sc, const float* gsc, const float* v, const float* xin, const float* ym, const float* keep, float* w,
+                       int n, int tcur, hipStream_t s) {
+    if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
+    if (tcur < 0 || tcur > 2) return fail(FC_E_ARG, "ode: stage time selector must lie in [0, 2]");
+    hipLaunchKernelGGL(ode_guide_w_kernel, dim3(egrid(n)), dim3(256), 0, s, sc, gsc, v, xin, ym, keep, w, n, tcur);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_guided_correct_launch(const float* v, const float* x, const float* ym, const float* keep, float* out, int n, float t, float s2,
+                              float gamma, hipStream_t s) {
+    if (n < 4 || (n & 3)) return fail(FC_E_SHAPE, "ode: element count must be a positive multiple of 4");
+    hipLaunchKernelGGL(ode_guided_correct_kernel, dim3(egrid(n)), dim3(256), 0, s, v, x, ym, keep, out, n, t, s2, gamma);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
 
 // ================================================================================================ adaptive RK45
 // scipy.integrate.solve_ivp(method="RK45") as the legacy sampler calls it (legacy/train_sd_flowers.py:78-107): scipy 1.15's

@@ -148,6 +148,19 @@ static FwdCtx integrator_ctx(const CallFrame& f) {
     return c;
 }
 
+// integrator_ctx for a step of a fixed grid.  pre_on: the conditioning rows of every evaluation are in ig.pre (cond_table): init_conv
+// fetches slice *evalc, final_conv advances the counter
+static FwdCtx step_ctx(const CallFrame& f, bool pre_on) {
+    const fc_unet* u = f.u;
+    const IntegratorState& ig = u->ig;
+    FwdCtx c = integrator_ctx(f);
+    if (pre_on) {
+        c.fetch.all = ig.pre_ss; c.fetch.evalc = ig.step + 1; c.fetch.dst = u->plan.ss; c.fetch.n4 = f.rows * u->S / 4;
+        c.euler.evalc = ig.step + 1;
+    }
+    return c;
+}
+
 // enqueue one integration step on `s` (captured into a graph by the caller)
 // Legacy Euler without CFG: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
 static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_EULER && !cfg_on; }
@@ -158,11 +171,7 @@ static int enqueue_step(const CallFrame& f, int method, float cfg, float dt_eule
     const bool cfg_on = f.cfg_on;
     const int rows = f.rows, n = f.n;
     hipStream_t s = f.s;
-    FwdCtx c = integrator_ctx(f);
-    if (pre_on) {   // conditioning rows of every evaluation are in ig.pre: init_conv fetches slice *evalc, final_conv advances the counter
-        c.fetch.all = ig.pre_ss; c.fetch.evalc = ig.step + 1; c.fetch.dst = u->plan.ss; c.fetch.n4 = rows * u->S / 4;
-        c.euler.evalc = ig.step + 1;
-    }
+    FwdCtx c = step_ctx(f, pre_on);
     if (euler_tail_ok(method, cfg_on)) {   // the update and the next interval's time ride in final_conv: no launches around the plan
         c.x = ig.y;
         c.euler.y = ig.y; c.euler.dt = dt_euler; c.euler.step = ig.step; c.euler.ts = ig.ts_dev; c.euler.t_scale = t_scale;
@@ -207,27 +216,23 @@ static int integrator_prologue(const CallFrame& f, const float* x_dev, const flo
     return FC_OK;
 }
 
-int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float dt_euler,
-                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, void* stream) {
-    if (!u || !x_dev || !ts_host || B < 1 || n_points < 1) return fail(FC_E_ARG, "fc_unet_integrate: bad argument");
-    if (method != FC_METHOD_EULER && method != FC_METHOD_RK4) return fail(FC_E_ARG, "fc_unet_integrate: unknown method");
-    CallFrame f;
-    FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
-    FC_TRY(f.enter());
+// Conditioning of every evaluation of a fixed-grid call, once, into ig.pre (*pre_on_out: the table is in use; not for a single interval
+// or a table beyond 2 GiB).
+static int cond_table(const CallFrame& f, int method, int n_steps, float t_scale, bool* pre_on_out) {
+    fc_unet* u = f.u;
     IntegratorState& ig = u->ig;
     const bool has_ids = f.has_ids, cfg_on = f.cfg_on;
-    const int rows = f.rows, n_steps = method == FC_METHOD_RK4 ? n_points - 1 : n_points;
+    const int rows = f.rows, B = f.B;
     hipStream_t s = f.s;
-    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
-
     // Conditioning of every evaluation, once: the grid is known, so time MLP / class MLP / FiLM projections of all (evaluation, row)
     // pairs are three launches here instead of three at the head of each forward (44 us of every 1.6 ms step inside the replayed graph:
     // cold weights, latency-bound).  Rows are bit-identical to the per-forward ones (same kernels, same time arithmetic).
     const int n_evals = method == FC_METHOD_RK4 ? 4 * n_steps : n_steps;
     const size_t R = (size_t)n_evals * rows, tvn = ((size_t)n_evals + 3) & ~(size_t)3;
     const size_t need = tvn + R * u->td * 3 + R * u->S;
-    const bool pre_on = n_steps >= 2 && need * sizeof(float) <= (2ull << 30) && R < (1u << 30) / (unsigned)u->S;
-    if (pre_on) {
+    const bool pre_on = *pre_on_out = n_steps >= 2 && need * sizeof(float) <= (2ull << 30) && R < (1u << 30) / (unsigned)u->S;
+    if (!pre_on) return FC_OK;
+    {
         if (need > ig.pre_cap) {
             FC_HIP(hipStreamSynchronize(s));
             if (ig.pre) dev_free(ig.pre);
@@ -254,27 +259,34 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
         ca.w = u->P("__ss_wt"); ca.bias = u->P("__ss_bias"); ca.out = ig.pre_ss;
         FC_TRY(conv_launch(ca, TILE_AUTO, s));
     }
-    if (euler_tail_ok(method, cfg_on))   // time of the first interval; every step publishes its successor's
-        FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 0, ig.sc, ig.tvec, rows, s));
+    return FC_OK;
+}
+
+// The n_steps intervals of a fixed-grid call, each enqueued by `step`: direct launches under FLOCODER_AMD_NO_GRAPH, else replays of
+// graphs cached under `key` (every field but `steps` filled by the caller).
+static int replay_steps(const CallFrame& f, GraphKey key, int n_steps, int evals_per_step, const std::function<int()>& step) {
+    fc_unet* u = f.u;
+    hipStream_t s = f.s;
     if (no_graph()) {
-        for (int i = 0; i < n_steps; ++i) FC_TRY(enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on));
-    } else {
+        for (int i = 0; i < n_steps; ++i) FC_TRY(step());
+        return FC_OK;
+    }
+    {
         // One graph holds SEVERAL consecutive intervals (round 3): the step counter, the time grid and the conditioning slice index all
         // live on the device, so a captured interval is position-independent and k of them in a row are one hipGraphLaunch instead
         // of k (the per-interval form left ~4 % of the trajectory between replays: 64 launches of a 70-node graph).  Capped by node
         // count.
-        const int nodes_per_step = (int)u->plan.ops.size() * (method == FC_METHOD_RK4 ? 4 : 1) + 16;
+        const int nodes_per_step = (int)u->plan.ops.size() * evals_per_step + 16;
         int per = 6144 / nodes_per_step > 0 ? 6144 / nodes_per_step : 1;
         if (per > 255) per = 255;
         for (int left = n_steps; left > 0;) {
             const int k = left < per ? left : per;
-            GraphKey key = graph_key(f, method == FC_METHOD_RK4 ? GraphKey::Rk4 : GraphKey::Euler, cfg_strength, t_scale);
-            key.pre_on = pre_on; key.steps = k; key.dt_euler = fbits(dt_euler);
+            key.steps = k;
             hipGraphExec_t exec = nullptr;
             FC_TRY(cached_graph(u, key, s, [&] {
                 int r = FC_OK;
                 for (int j = 0; j < k && r == FC_OK; ++j)
-                    r = enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on);
+                    r = step();
                 return r;
             }, &exec));
             // The FIRST replay of a call waits, on the host, for everything this call has put on the stream in front of it (round 4).  Under
@@ -291,6 +303,29 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
             left -= k;
         }
     }
+    return FC_OK;
+}
+
+int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float dt_euler,
+                      float t_scale, const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, void* stream) {
+    if (!u || !x_dev || !ts_host || B < 1 || n_points < 1) return fail(FC_E_ARG, "fc_unet_integrate: bad argument");
+    if (method != FC_METHOD_EULER && method != FC_METHOD_RK4) return fail(FC_E_ARG, "fc_unet_integrate: unknown method");
+    CallFrame f;
+    FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
+    FC_TRY(f.enter());
+    IntegratorState& ig = u->ig;
+    const bool cfg_on = f.cfg_on;
+    const int rows = f.rows, n_steps = method == FC_METHOD_RK4 ? n_points - 1 : n_points;
+    hipStream_t s = f.s;
+    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
+    bool pre_on = false;
+    FC_TRY(cond_table(f, method, n_steps, t_scale, &pre_on));
+    if (euler_tail_ok(method, cfg_on))   // time of the first interval; every step publishes its successor's
+        FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 0, ig.sc, ig.tvec, rows, s));
+    GraphKey key = graph_key(f, method == FC_METHOD_RK4 ? GraphKey::Rk4 : GraphKey::Euler, cfg_strength, t_scale);
+    key.pre_on = pre_on; key.dt_euler = fbits(dt_euler);
+    FC_TRY(replay_steps(f, key, n_steps, method == FC_METHOD_RK4 ? 4 : 1,
+                        [&] { return enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on); }));
     FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
     return f.leave();
 }
@@ -350,6 +385,142 @@ int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_d
         return fail(FC_E_ARG, "fc_debug_probe_dot: inputs must be 16-byte aligned (read as float4)");
     if (per_sample < 1 || per_sample > 0x7fffffff) return fail(FC_E_SHAPE, "fc_debug_probe_dot: bad element count");
     return ode_ll_dot_launch(probe_dev, g_dev, out_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
+}
+
+// ---- measurement guidance on the RK4 grid ------------------------------------------------------------------------------------------
+// fc_unet_integrate_guided: fc_unet_integrate(FC_METHOD_RK4) with every stage velocity corrected towards the measurement (ode.hip).
+// sigma_y^2 and gamma reach the kernels through a device scalar block (ig.g_sc), not as kernel arguments: a captured interval then
+// serves every (sigma_y, gamma) -- a caller tuning them replays one graph instead of capturing one per value -- and the key of a guided
+// graph is the key of the plain one plus its kind.
+static int alloc_guided(fc_unet* u, bool exact) {
+    IntegratorState& ig = u->ig;
+    const size_t nstate = (size_t)u->maxB * u->cfg.channels * u->H * u->W;
+    const char* tag = "integrator.guided";
+    if (!ig.g_sc) {
+        FC_TRY(ig.get(&ig.g_y, nstate, tag));
+        FC_TRY(ig.get(&ig.g_keep, nstate, tag));
+        FC_TRY(ig.get(&ig.g_sc, 4, tag));            // last: a first call that failed half-way allocates again
+        ig.drop_graphs();
+    }
+    if (exact && !ig.g_q) {
+        FC_TRY(ig.get(&ig.g_w, nstate, tag));
+        FC_TRY(ig.get(&ig.g_q, nstate, tag));
+        ig.drop_graphs();
+    }
+    return FC_OK;
+}
+
+// one interval, identity form (captured): enqueue_step's RK4 branch with the guided stage kernels
+static int enqueue_guided_step(const CallFrame& f, float cfg, float t_scale, bool pre_on) {
+    fc_unet* u = f.u;
+    const IntegratorState& ig = u->ig;
+    const int rows = f.rows, n = f.n, cf = f.cfg_on ? 1 : 0;
+    hipStream_t s = f.s;
+    FwdCtx c = step_ctx(f, pre_on);
+    FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, rows, s));
+    c.x = ig.y;
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k1 at (y, t)
+    FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k1, ig.v2, ig.y, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, 0, 0, 1, t_scale,
+                                 ig.tvec, rows, s));
+    c.x = ig.xs;
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k2 at (xs, t+dt/2)
+    FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k2, ig.v2, ig.xs, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, 0, 1, 1, t_scale,
+                                 ig.tvec, rows, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k3 at (xs, t+dt/2)
+    FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, 1, 1, 2, t_scale,
+                                 ig.tvec, rows, s));
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k4 at (xs, t+dt)
+    return ode_rk4_gfinal_launch(ig.sc, ig.g_sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, s);
+}
+
+int fc_unet_integrate_guided(fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
+                             const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, const float* y_meas,
+                             const float* keep, float sigma_y, float gamma, int jacobian, void* stream) {
+    if (!u || !x_dev || !ts_host || !y_meas || !keep || B < 1) return fail(FC_E_ARG, "fc_unet_integrate_guided: null argument");
+    if (n_points < 2) return fail(FC_E_ARG, "fc_unet_integrate_guided: the time grid needs at least two points");
+    if (jacobian != FC_JACOBIAN_IDENTITY && jacobian != FC_JACOBIAN_EXACT) return fail(FC_E_ARG, "fc_unet_integrate_guided: unknown jacobian mode");
+    for (int i = 0; i < n_points; ++i)
+        if (!(ts_host[i] > 0.0f)) return fail(FC_E_ARG, "fc_unet_integrate_guided: every grid point must be > 0 (the correction is gamma (1-t)/t g)");
+    if (!(sigma_y >= 0.0f)) return fail(FC_E_ARG, "fc_unet_integrate_guided: sigma_y must be >= 0");
+    if (!std::isfinite(gamma)) return fail(FC_E_ARG, "fc_unet_integrate_guided: gamma must be finite");
+    if ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(y_meas) | reinterpret_cast<uintptr_t>(keep)) & 15)
+        return fail(FC_E_ARG, "fc_unet_integrate_guided: x, measurement and keep must be 16-byte aligned (the kernels read them as float4)");
+    const bool exact = jacobian == FC_JACOBIAN_EXACT;
+    CallFrame f;
+    FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
+    if (exact) {
+        if (f.cfg_on)
+            return fail(FC_E_ARG, "fc_unet_integrate_guided: the exact Jacobian takes no classifier-free guidance (the chain differentiates one "
+                                  "forward, not the guided pair)");
+        if (!u->keep_all) return fail(FC_E_STATE, "fc_unet_integrate_guided: no backward plan for this shape; call fc_unet_train_reserve");
+        FC_TRY(vjp_check(u, B, H, W, "fc_unet_integrate_guided"));
+    }
+    IntegratorState& ig = u->ig;
+    FC_TRY(alloc_guided(u, exact));
+    const int n = f.n, n_steps = n_points - 1;
+    hipStream_t s = f.s;
+    FC_TRY(f.enter());
+    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
+    FC_HIP(hipMemcpyAsync(ig.g_y, y_meas, f.nbytes, hipMemcpyDeviceToDevice, s));
+    FC_HIP(hipMemcpyAsync(ig.g_keep, keep, f.nbytes, hipMemcpyDeviceToDevice, s));
+    const float gsc[4] = {(float)((double)sigma_y * (double)sigma_y), gamma, 0.f, 0.f};
+    FC_HIP(hipMemcpyAsync(ig.g_sc, gsc, sizeof(gsc), hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns
+    if (!exact) {
+        bool pre_on = false;
+        FC_TRY(cond_table(f, FC_METHOD_RK4, n_steps, t_scale, &pre_on));
+        GraphKey key = graph_key(f, GraphKey::Rk4Guided, cfg_strength, t_scale);
+        key.pre_on = pre_on;
+        FC_TRY(replay_steps(f, key, n_steps, 4, [&] { return enqueue_guided_step(f, cfg_strength, t_scale, pre_on); }));
+    } else {
+        // the likelihood's structure: every evaluation a training-form forward, w, the data-gradient chain with w as output cotangent,
+        // then the stage kernel with q = (dv/dx)^T w; direct launches, nothing decided on the host
+        FwdCtx c = integrator_ctx(f);
+        c.d_out = ig.g_w; c.dx_out = ig.g_q;
+        auto eval = [&](const float* x, int tcur) -> int {
+            c.x = x;
+            FC_TRY(run_plan(u->plan, c, s));
+            FC_TRY(ode_guide_w_launch(ig.sc, ig.g_sc, ig.v2, x, ig.g_y, ig.g_keep, ig.g_w, n, tcur, s));
+            return vjp_run(u, c, s);
+        };
+        for (int i = 0; i < n_steps; ++i) {
+            FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, B, s));
+            FC_TRY(eval(ig.y, 0));
+            FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k1, ig.v2, ig.y, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, 0, 0, 1, t_scale,
+                                         ig.tvec, B, s));
+            FC_TRY(eval(ig.xs, 1));
+            FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k2, ig.v2, ig.xs, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, 0, 1, 1, t_scale,
+                                         ig.tvec, B, s));
+            FC_TRY(eval(ig.xs, 1));
+            FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, 1, 1, 2, t_scale,
+                                         ig.tvec, B, s));
+            FC_TRY(eval(ig.xs, 2));
+            FC_TRY(ode_rk4_gfinal_launch(ig.sc, ig.g_sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, s));
+        }
+    }
+    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
+    return f.leave();
+}
+
+int fc_ode_guided_correct(const float* v_dev, const float* x_dev, const float* y_dev, const float* a_dev, int64_t n, float t, float sigma_y,
+                          float gamma, float* out_dev, void* stream) {
+    if (!v_dev || !x_dev || !y_dev || !a_dev || !out_dev) return fail(FC_E_ARG, "fc_ode_guided_correct: null argument");
+    if ((reinterpret_cast<uintptr_t>(v_dev) | reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(y_dev) |
+         reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15)
+        return fail(FC_E_ARG, "fc_ode_guided_correct: tensors must be 16-byte aligned (read as float4)");
+    if (!(t > 0.0f)) return fail(FC_E_ARG, "fc_ode_guided_correct: t must be > 0");
+    if (!(sigma_y >= 0.0f)) return fail(FC_E_ARG, "fc_ode_guided_correct: sigma_y must be >= 0");
+    if (n < 1 || n > 0x7fffffff) return fail(FC_E_SHAPE, "fc_ode_guided_correct: bad element count");
+    return ode_guided_correct_launch(v_dev, x_dev, y_dev, a_dev, out_dev, (int)n, t, (float)((double)sigma_y * (double)sigma_y), gamma,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int fc_debug_unet_guided_buffers(const fc_unet* u, const float** stage_x, const float** stage_time, const float** w, const float** q) {
+    if (!u || !u->ig.g_q) return fail(FC_E_STATE, "fc_debug_unet_guided_buffers: no exact-form guided call on the current plan");
+    if (stage_x) *stage_x = u->ig.xs;
+    if (stage_time) *stage_time = u->ig.tvec;
+    if (w) *w = u->ig.g_w;
+    if (q) *q = u->ig.g_q;
+    return FC_OK;
 }
 
 // ---- adaptive RK45 ----------------------------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@ namespace fc {
 
 // What a cached graph was captured for: two calls share a graph exactly when every field agrees.
 struct GraphKey {
-    enum Kind { Euler, Rk4, Rk45Coupled, Rk45PerSample };
+    enum Kind { Euler, Rk4, Rk45Coupled, Rk45PerSample, Rk4Guided };
     Kind kind = Euler;
     int B = 0, mask_mode = 0;
     bool cfg_on = false, has_ids = false;
@@ -41,6 +41,10 @@ struct IntegratorPlanState {
     // interval, allocated by the first call
     float* ll_g = nullptr;
     double* ll_d = nullptr;
+    // measurement guidance (fc_unet_integrate_guided): the call's measurement and keep weights in the library's own buffers (made like
+    // mask_own), {sigma_y^2, gamma} of the call, and for the exact form w and q = (dv/dx)^T w of the running stage; allocated by the
+    // first call
+    float *g_y = nullptr, *g_keep = nullptr, *g_sc = nullptr, *g_w = nullptr, *g_q = nullptr;
 
     template <class T> int get(T** out, size_t count, const char* tag) {
         void* p = nullptr;

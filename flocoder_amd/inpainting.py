@@ -1,6 +1,8 @@
 """Inpainting conditioning: host-side mirror of ``flocoder/inpainting.py``'s ``MaskEncoder`` / ``mask_blending``
-(inpainting.py:161-253) over the gfx950 library.  The mask *generators*, ``InpaintingDataset`` and the diagnostics of that
-file are data preparation and stay out of scope."""
+(inpainting.py:161-253) over the gfx950 library, and ``algorithm3`` (inpainting.py:92-130), the training-free measurement guidance the
+guided sampler applies (``sampling.generate_latents_guided``; on a ``flocoder_amd.Unet`` the correction runs inside the library's RK4
+stage kernels).  The mask *generators*, ``InpaintingDataset`` and the diagnostics of that file are data preparation and stay out of
+scope."""
 from __future__ import annotations
 
 import math
@@ -101,3 +103,42 @@ def mask_blending(source, mask, noise=None):
     out = torch.empty_like(s)
     B.check(B.lib().fc_mask_blend(B.ptr(s), B.ptr(m), B.ptr(n), B.ptr(out), s.numel(), B.current_stream(s.device)))
     return out
+
+
+def guidance_weight(v, x, tp, y, a, sigma_y=0.05):
+    """``w = a (y - a x1) / (r2 a^2 + sigma_y^2)`` with ``x1 = x + (1 - tp) v`` and ``r2 = (1-tp)^2 / (tp^2 + (1-tp)^2)``: algorithm3's
+    ``(y - A x1)^T (r2 A A^T + sigma_y^2 I)^-1 A`` for the diagonal operator ``A = diag(a)`` (``a`` of x's shape or broadcastable to it),
+    elementwise and batched; 0 where the denominator is 0 (``a = 0`` with ``sigma_y = 0``: nothing is measured there)."""
+    om = 1 - tp
+    x1 = x + om * v
+    r2 = om ** 2 / (tp ** 2 + om ** 2)
+    den = r2 * (a * a) + sigma_y ** 2
+    num = a * (y - a * x1)
+    return torch.where(den == 0, torch.zeros_like(num), num / torch.where(den == 0, torch.ones_like(den), den))
+
+
+def algorithm3(v, x, t, tp, y, A, sigma_y=0.05, gamma_t=1.0):
+    """inpainting.py:92-130, "solve inverse problems via flows with a pretrained vector field" on the conditional-OT path (alpha_t = t,
+    sigma_t = 1 - t): the velocity ``v`` a pretrained flow gives at ``(x, tp)`` corrected so that the trajectory agrees with the
+    measurement ``y = A x_1``.  ``t`` is accepted for signature parity (upstream never reads it).  With the upstream coefficients
+    reduced -- ``(alpha d ln(alpha/sigma)/dt)^-1 = 1 - tp``, ``sigma^2 d ln(alpha/sigma)/dt = (1 - tp)/tp`` -- no intermediate is singular:
+
+        x1 = x + (1 - tp) v        g = (y - A x1)^T (r2 A A^T + sigma_y^2 I)^-1 A        v_c = v + gamma_t ((1 - tp)/tp) g
+
+    (d x1 / d x is taken as the identity, as upstream; ``sampling.generate_latents_guided(jacobian="exact")`` adds the rest.)  ``A`` is
+    either a dense ``[k, n]`` matrix -- one flattened sample of n elements, ``y`` of k, the ``k x k`` solve of upstream -- or a tensor of
+    x's shape / ``[B,1,H,W]``: the diagonal operator, for which the solve is the elementwise ``guidance_weight``, batched.  Finite for
+    ``0 < tp <= 1`` (at ``tp = 1`` the result is ``v``); ``tp <= 0`` raises ValueError (upstream returns NaN at both ends)."""
+    if not float(tp) > 0:
+        raise ValueError(f"algorithm3: tp={float(tp)} must be > 0 (the correction carries the factor (1 - tp)/tp)")
+    om = 1 - tp
+    coef = gamma_t * om / tp
+    if A.dim() == 2 and A.shape[1] == x.numel() and tuple(A.shape) != tuple(x.shape):      # the dense form
+        x1 = x + om * v
+        r2 = om ** 2 / (tp ** 2 + om ** 2)
+        residual = y - A @ x1.flatten()
+        cov = r2 * (A @ A.T) + sigma_y ** 2 * torch.eye(A.shape[0], device=x.device, dtype=A.dtype)
+        g = (residual @ torch.linalg.solve(cov, A)).view_as(x)
+    else:
+        g = guidance_weight(v, x, tp, y, A, sigma_y)
+    return v + coef * g

@@ -129,6 +129,82 @@ def generate_latents_rk4(model, shape, n_steps=50, cond=None, cfg_strength=3.0, 
 
 
 @torch.no_grad()
+def generate_latents_guided(model, shape, measurement, keep, n_steps=50, init_strength=0.2, init_latents=None, cond=None, cfg_strength=3.0,
+                            source=None, sigma_y=0.05, gamma=1.0, jacobian="identity"):
+    """Training-free inpainting / editing with any pretrained flow (``inpainting.algorithm3``, the reference's inpainting.py:92-130, for a
+    diagonal measurement operator): ``generate_latents_rk4(..., init_latents=..., init_strength=...)`` -- the same start
+    ``(1 - s) source + s init_latents`` (``init_latents`` defaults to ``measurement``), the same grid ``rk4_time_grid(n_steps, s)``, the
+    same nfe bookkeeping -- with every stage velocity (after classifier-free guidance) corrected towards ``measurement = keep * x_1``:
+
+        x1 = x + (1-t) v      w = keep (measurement - keep x1) / (r2 keep^2 + sigma_y^2)      r2 = (1-t)^2 / (t^2 + (1-t)^2)
+        v <- v + gamma ((1-t)/t) g        g = w (jacobian="identity", upstream)  |  w + (1-t) (dv/dx)^T w (jacobian="exact")
+
+    at the stage's own state x and time t.  ``keep`` holds the weights in [0, 1] of the measured elements (x's shape or ``[B,1,H,W]``); for
+    inpainting ``measurement = keep * known_latents``.  ``init_strength <= 0`` raises ValueError (the grid would contain t = 0, where
+    the correction is unbounded), and so does ``jacobian="exact"`` together with class ids and a non-zero ``cfg_strength`` (the exact
+    term differentiates one forward, not the guided pair).  Returns ``(latents, nfe)``.
+
+    A ``flocoder_amd.Unet`` runs the loop in the library (``Unet.integrate_guided``: the identity form replays the captured RK4 step with
+    guided stage kernels; the exact form runs a training-form forward and the backward plan's data-gradient chain per evaluation, and
+    leaves the model's plans as it found them); on the CPU it raises like the other integrators.  Any other callable takes the torch
+    path: ``rk4_step`` over the corrected field, ``torch.autograd.grad`` for the exact term."""
+    from .inpainting import guidance_weight
+    if jacobian not in ("identity", "exact"):
+        raise ValueError(f"jacobian={jacobian!r}: 'identity' or 'exact'")
+    if init_strength is None or not init_strength > 0:
+        raise ValueError(f"init_strength={init_strength} must be > 0: the grid would contain t = 0, where the correction (1-t)/t is unbounded")
+    if sigma_y < 0:
+        raise ValueError("sigma_y must be >= 0")
+    if tuple(measurement.shape) != tuple(shape):
+        raise ValueError(f"measurement must have shape {tuple(shape)}, got {tuple(measurement.shape)}")
+    if tuple(keep.shape) not in (tuple(shape), (shape[0], 1) + tuple(shape[2:])):
+        raise ValueError(f"keep must have shape {tuple(shape)} or [B,1,H,W], got {tuple(keep.shape)}")
+    unet = isinstance(model, Unet)
+    cond, cls, mask, ones = _conditioning(model, cond)
+    if jacobian == "exact" and cfg_strength and cond and cond.get('class_cond') is not None:
+        raise ValueError("jacobian='exact' takes no classifier-free guidance (pass cfg_strength=0): the exact term differentiates one "
+                         "forward, not the guided pair")
+    p0 = next(model.parameters()) if hasattr(model, "parameters") else measurement
+    device, dtype = p0.device, p0.dtype
+    current_points = source if source is not None else torch.randn(shape, device=device, dtype=dtype)
+    if init_latents is None:
+        init_latents = measurement
+    current_points = (1 - init_strength) * current_points + init_strength * init_latents
+    ts = rk4_time_grid(n_steps, init_strength, dtype=dtype)
+    nfe = max(1, int(n_steps * (1.0 - init_strength))) * 4
+
+    if unet:
+        if not current_points.is_cuda:
+            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+        x = _start(current_points, None, device)
+        if len(ts) > 1:
+            model.integrate_guided(x, ts, measurement, keep, sigma_y=sigma_y, gamma=gamma, jacobian=jacobian, class_ids=cls,
+                                   cfg_strength=cfg_strength or 0.0, mask=mask, mask_is_ones=ones)
+        return x, nfe
+
+    ts = ts.to(device)
+    y, a = measurement.to(device=device, dtype=dtype), keep.to(device=device, dtype=dtype)
+    t_vec_template = torch.zeros(shape[0], device=device, dtype=dtype)
+
+    def v_func(x, t):
+        om = 1 - t
+        if jacobian == "identity":
+            v = v_func_cfg(model, cond, cfg_strength, t_vec_template, x, t)
+            g = guidance_weight(v, x, t, y, a, sigma_y)
+        else:
+            with torch.enable_grad():
+                xr = x.detach().requires_grad_(True)
+                vr = model(xr, t_vec_template.fill_(float(t)) * 999, cond=cond)
+                w = guidance_weight(vr.detach(), x, t, y, a, sigma_y)
+                q, = torch.autograd.grad(vr, xr, w)
+            v = vr.detach()
+            g = w + om * q
+        return v + (gamma * om / t) * g
+
+    return _rk4_loop(v_func, current_points, ts), nfe
+
+
+@torch.no_grad()
 def euler_sampler(model, shape, sample_N, device=None, cond=None, source=None, eps=1e-3, cfg_strength=0.0):
     """Legacy Euler sampler, train_sd_flowers.py:50-67: x += model(x, 999 t_i, cond)/N on the un-warped grid, nfe = N.
     ``cond`` is a class-id tensor as upstream (wrapped into the dict the live Unet needs) or a cond dict;

@@ -488,6 +488,60 @@ class Unet(NativeModule):
                 B.check(lib.fc_unet_reserve(hnd, rows0.value, h0.value, w0.value))
         return a, logp
 
+    def integrate_guided(self, x: torch.Tensor, ts: torch.Tensor, measurement: torch.Tensor, keep: torch.Tensor, *, sigma_y: float = 0.05,
+                         gamma: float = 1.0, jacobian: str = "identity", t_scale: float = 999.0, class_ids: Optional[torch.Tensor] = None,
+                         cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None, mask_is_ones: bool = False, check: bool = True,
+                         restore_plan: bool = True) -> torch.Tensor:
+        """``fc_unet_integrate_guided``: integrate ``x`` in place along the fp32 grid ``ts`` (every point > 0) with the RK4 step, every stage
+        velocity corrected towards ``measurement = keep * x1`` (``inpainting.algorithm3`` for a diagonal operator); returns ``x``.
+        ``measurement`` has x's shape, ``keep`` x's shape or ``[B,1,H,W]``.  ``jacobian="identity"`` is the captured path: class ids,
+        guidance, mask and ``check`` as ``integrate``.  ``jacobian="exact"`` adds ``(1-t) (dv/dx)^T w`` through the backward plan's
+        data-gradient chain; it takes no classifier-free guidance and needs the training form of the plans, which it handles as
+        ``log_likelihood`` does: a model that was not in that form gets its inference plans and reservation back before the call returns
+        unless ``restore_plan=False`` (then ``release_training_plan()`` is the caller's)."""
+        if jacobian not in ("identity", "exact"):
+            raise ValueError(f"jacobian={jacobian!r}: 'identity' or 'exact'")
+        exact = jacobian == "exact"
+        if exact and class_ids is not None and self.class_condition and cfg_strength:
+            raise ValueError("jacobian='exact' takes no classifier-free guidance: the chain differentiates one forward, not the guided pair")
+        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength, cpu_error=_GPU_ONLY + "; there is no CPU path")
+        dev = x.device
+        bsz, _, h, w = x.shape
+        if measurement.shape != x.shape:
+            raise ValueError(f"measurement must have the shape of x {tuple(x.shape)}, got {tuple(measurement.shape)}")
+        if tuple(keep.shape) not in (tuple(x.shape), (bsz, 1, h, w)):
+            raise ValueError(f"keep must have the shape of x or [B,1,H,W], got {tuple(keep.shape)}")
+        if sigma_y < 0:
+            raise ValueError("sigma_y must be >= 0")
+        if ts.numel() < 2:
+            raise ValueError("the time grid needs at least two points")
+        if x.data_ptr() % 16:
+            raise ValueError("x must be 16-byte aligned (the kernels read it as float4)")
+        # fresh aligned fp32 copies on x's device (the library copies them again into its own buffers)
+        ym = measurement.to(device=dev, dtype=torch.float32).contiguous().clone()
+        kp = keep.to(device=dev, dtype=torch.float32).expand_as(x).contiguous().clone()
+        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
+        if not bool((ts_host > 0).all()):
+            raise ValueError("every grid point must be > 0: the correction is gamma (1-t)/t g")
+        lib = B.lib()
+        if exact:
+            was_training_form = bool(lib.fc_unet_train_form(hnd))
+            rows0, h0, w0 = C.c_int(0), C.c_int(0), C.c_int(0)
+            B.check(lib.fc_unet_reserved(hnd, C.byref(rows0), C.byref(h0), C.byref(w0)))
+            B.check(lib.fc_unet_train_reserve(hnd, bsz, h, w))
+        else:
+            B.check(lib.fc_unet_reserve(hnd, rows, h, w))
+        B.check(lib.fc_unet_integrate_guided(hnd, B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)), ts_host.numel(),
+                                             float(t_scale), B.ptr(class_ids), float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones),
+                                             B.ptr(ym), B.ptr(kp), float(sigma_y), float(gamma),
+                                             B.FC_JACOBIAN_EXACT if exact else B.FC_JACOBIAN_IDENTITY, B.current_stream(dev)))
+        self._integrator_check(hnd, dev, check)
+        if exact and restore_plan and not was_training_form:
+            self.release_training_plan()
+            if rows0.value > 0:                         # the reservation the caller had, in the form it had
+                B.check(lib.fc_unet_reserve(hnd, rows0.value, h0.value, w0.value))
+        return x
+
     def release_training_plan(self) -> None:
         """Put the handle's plans back into the inference form (``fc_unet_train_release``): waits for the device, drops the training-form
         plans, the backward plan and the captured graphs; the next call builds what a model that never trained builds."""

@@ -216,7 +216,34 @@ int fc_unet_log_likelihood(fc_unet* u, float* x_inout_dev, int batch, int height
                            float t_scale, const int64_t* class_ids_dev, const float* mask_dev, int mask_is_ones, const float* probe_dev,
                            double* a_out_dev, double* logp_out_dev, void* stream);
 
+/* Measurement-guided RK4 sampling: the training-free inverse-problem method of the reference (flocoder/inpainting.py:92-130 algorithm3)
+ * for a diagonal measurement operator on the conditional-OT path.  fc_unet_integrate(FC_METHOD_RK4) along ts_host (n_points >= 2, every
+ * point > 0) in which every stage velocity v -- after classifier-free guidance -- produced at stage state x and stage time t becomes
+ *     x1 = x + (1-t) v     w = keep (y_meas - keep x1) / (r2 keep^2 + sigma_y^2)  (0 where that is 0/0)     r2 = (1-t)^2 / (t^2 + (1-t)^2)
+ *     v <- v + gamma ((1-t)/t) g        g = w (FC_JACOBIAN_IDENTITY, what the reference computes)
+ *                                       g = w + (1-t) (dv/dx)^T w (FC_JACOBIAN_EXACT: d x1 / d x = I + (1-t) dv/dx)
+ * y_meas_dev, keep_dev [B,C,H,W] (keep weights in [0,1]; for inpainting y_meas = keep * known latents) are copied into the library's
+ * own buffers; they and x_dev must be 16-byte aligned.  1-t, r2 and gamma (1-t)/t are formed in fp64 from the fp32 stage time and
+ * rounded once; the elementwise part is single-rounded fp32 in the order written above.  A zero correction term (gamma = 0, keep = 0,
+ * t = 1) leaves the bits of fc_unet_integrate.
+ * Identity: captured and replayed like fc_unet_integrate (sigma_y and gamma live in device memory, so one graph serves all values);
+ * class ids, guidance and mask conditioning as there.  Exact: every evaluation is a training-form forward plus fc_unet_vjp_x's chain with
+ * w as cotangent, direct launches as fc_unet_log_likelihood; needs fc_unet_train_reserve (else FC_E_STATE) and takes no classifier-free
+ * guidance (FC_E_ARG).  A grid point <= 0, sigma_y < 0 or a misaligned pointer -> FC_E_ARG.  Asynchronous like fc_unet_integrate. */
+#define FC_JACOBIAN_IDENTITY 0
+#define FC_JACOBIAN_EXACT 1
+int fc_unet_integrate_guided(fc_unet* u, float* x_dev, int batch, int height, int width, const float* ts_host, int n_points, float t_scale,
+                             const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev, int mask_is_ones,
+                             const float* y_meas_dev, const float* keep_dev, float sigma_y, float gamma, int jacobian, void* stream);
+/* The identity-form correction of one evaluation on caller tensors of n elements (a multiple of 4, 16-byte aligned):
+ * out = v + gamma ((1-t)/t) w with the arithmetic of fc_unet_integrate_guided; t > 0, sigma_y >= 0.  out_dev may be v_dev. */
+int fc_ode_guided_correct(const float* v_dev, const float* x_dev, const float* y_dev, const float* a_dev, int64_t n, float t, float sigma_y,
+                          float gamma, float* out_dev, void* stream);
+
 /* ---- debug / test hooks: not part of the drop-in surface --------------------------------------- */
+/* After an exact-form fc_unet_integrate_guided call: device pointers to the last stage's input state [B,C,H,W], its scaled time rows [B],
+ * its w and q = (dv/dx)^T w, while the plan that ran it stands. */
+int fc_debug_unet_guided_buffers(const fc_unet* u, const float** stage_x, const float** stage_time, const float** w, const float** q);
 /* out_dev[b] (double) = sum_i probe_dev[b,i] g_dev[b,i] over per_sample elements: the likelihood stage kernels' reduction alone. */
 int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_dev, int batch, int64_t per_sample, void* stream);
 /* Device pointer + NHWC extent of an internal activation of the current plan, by reference module name
