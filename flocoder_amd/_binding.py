@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("FLOCODER_AMD_LIB") or os.path.join(_HERE, "_lib", "li
 FC_OK, FC_E_ARG, FC_E_SHAPE, FC_E_ARCH, FC_E_HIP, FC_E_STATE = 0, -1, -2, -3, -4, -5
 FC_METHOD_EULER, FC_METHOD_RK4 = 0, 1
 FC_JACOBIAN_IDENTITY, FC_JACOBIAN_EXACT = 0, 1
+FC_SDE_EULER_MARUYAMA, FC_SDE_HEUN = 0, 1
 TILE_AUTO = -1
 TILES = {"M128N32": 0, "M128N64": 1, "M64N32K2": 2, "M32N32K4": 3, "M64N64K2": 4, "M256N64": 5}
 
@@ -85,6 +86,8 @@ SIGNATURES = {
     "fc_debug_probe_dot": (_i, [_vp, _vp, _vp, _i, _i64, _vp]),
     "fc_unet_integrate_guided": (_i, [_vp, _vp, _i, _i, _i, _pf, _i, _f, _vp, _f, _vp, _i, _vp, _vp, _f, _f, _i, _vp]),
     "fc_ode_guided_correct": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _vp]),
+    "fc_unet_integrate_sde": (_i, [_vp, _i, _vp, _i, _i, _i, _pf, _i, _f, _vp, _f, _vp, _i, _f, C.c_uint64, _vp, _vp, _vp]),
+    "fc_ode_normal_field": (_i, [_vp, C.c_uint64, _i64, _vp, _i, _i64, _vp]),
     "fc_debug_unet_guided_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "fc_unet_arena_serial": (C.c_uint64, [_vp]),
     "fc_unet_class_param_range": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

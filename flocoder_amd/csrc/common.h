@@ -266,7 +266,7 @@ int na2d_launch(const float* qkv, float* out, const float* gamma, int B, int H, 
 // interval in flight.  All arithmetic is fp32 in the reference's operation order (sampling.py:43-48,74),
 // with FMA contraction disabled, so a step is reproducible against the CPU oracle to rounding.
 // First kernel of a step: reads ts[*step], publishes sc/tvec, then advances the counter.
-int ode_all_times_launch(const float* ts, int n_steps, int rk4, float t_scale, float* tv_out, hipStream_t s);
+int ode_all_times_launch(const float* ts, int n_steps, int rk4 /* 2: the pairs ts[i], ts[i+1] */, float t_scale, float* tv_out, hipStream_t s);
 int ode_time_launch(int* step, const float* ts, float t_scale, int rk4, float* sc, float* tvec, int rows, hipStream_t s);
 // v = cfg_on ? v_nc + cfg*(v_c - v_nc) : v   with v2 = [v_c ; v_nc] (n elements each)
 int ode_euler_update_launch(float* x, const float* v2, int n, int cfg_on, float cfg, float dt, hipStream_t s);
@@ -300,6 +300,17 @@ int ode_ll_final_launch(const float* sc, float* y, const float* k1, const float*
 // logp[b] = -|z_b|^2/2 - (m/2) ln 2pi + a[b]
 int ode_ll_logp_launch(const float* z, const double* a, double* logp, int B, int m, hipStream_t s);
 int ode_ll_dot_launch(const float* eps, const float* g, double* out, int B, int m, hipStream_t s);
+// stochastic sampling (fc_unet_integrate_sde).  SdeParams: the call's seed and supplied-noise pointer, in device memory like the time
+// grid, so one captured interval serves every seed and every noise tensor.  The update kernel runs behind a forward of the interval that
+// ode_time_launch opened (interval index *step - 1): stage 0 Euler-Maruyama (y in place), 1 Heun's predictor (b1, xs; publishes
+// ts[i+1] * t_scale), 2 Heun's corrector (y in place); xi = the generated normal field, or with use_noise slice i of prm->noise.
+struct SdeParams { unsigned long long seed; const float* noise; };
+int ode_sde_update_launch(const int* step, const float* ts, const SdeParams* prm, const int64_t* sids, float* y, float* xs, float* b1,
+                          const float* v2, int n, int m, int cfg_on, float cfg, float sigma, int stage, int use_noise, float t_scale,
+                          float* tvec, int rows, hipStream_t s);
+// out[b][:] = the field's normals of (seed, draw, sample id sids[b] or b), m per sample, n = batch * m
+int ode_normal_field_launch(float* out, unsigned long long seed, unsigned draw, const int64_t* sids, int n, int m, hipStream_t s);
+int ode_iota_launch(int64_t* ids, int B, hipStream_t s);
 
 // ---- adaptive RK45 (ode.hip): scipy's solve_ivp(method="RK45") with the controller on the device ----------------------------
 // Controller state and status record of one solve (fp64 as scipy; `failed`: 1 step size below spacing, 2 attempt cap).

@@ -95,12 +95,18 @@ __global__ void __launch_bounds__(256) ode_rk4_final_kernel(const float* sc, flo
 
 // Scaled time of EVERY evaluation of an integration, with the very operations the per-step kernels above use (so a conditioning table
 // built from it is bit-identical to what the per-forward launches would compute): Euler: ts[i] * t_scale; RK4, interval i:
-// t, t + dt/2, t + dt/2, t + dt with dt = ts[i+1] - ts[i].
+// t, t + dt/2, t + dt/2, t + dt with dt = ts[i+1] - ts[i]; rk4 == 2 (stochastic Heun), interval i: ts[i], ts[i+1].  The Euler-Maruyama
+// step evaluates at ts[i] alone: the Euler pattern over its n_points - 1 intervals.
 __global__ void __launch_bounds__(256) ode_all_times_kernel(const float* ts, int n_steps, int rk4, float t_scale, float* tv) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_steps) return;
     const float t = ts[i];
     if (!rk4) { tv[i] = mul_(t, t_scale); return; }
+    if (rk4 == 2) {   // the stochastic Heun step: t_i, t_{i+1}, both read from the grid (ode_sde_update_kernel publishes the same product)
+        tv[2 * i] = mul_(t, t_scale);
+        tv[2 * i + 1] = mul_(ts[i + 1], t_scale);
+        return;
+    }
     const float dt = sub_(ts[i + 1], t);
     const float th = mul_(add_(t, dt * 0.5f), t_scale);
     tv[4 * i] = mul_(t, t_scale);
@@ -959,6 +965,144 @@ int ode_ll_logp_launch(const float* z, const double* a, double* logp, int B, int
 int ode_ll_dot_launch(const float* eps, const float* g, double* out, int B, int m, hipStream_t s) {
     FC_TRY(ll_shape_ok(B, m));
     hipLaunchKernelGGL(ode_ll_dot_kernel, dim3(B), dim3(256), 0, s, eps, g, out, m);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
+// ================================================================================================ stochastic sampling (SDE)
+// fc_unet_integrate_sde: the SDE with the marginals of the probability-flow ODE on the linear path x_t = (1-t) x0 + t x1 (DESIGN.md
+// section 4b),
+//     dx = b(x,t) dt + sigma sqrt(1-t) dW        b(x,t) = (1 + sigma^2 t / 2) v(x,t) - (sigma^2 / 2) x
+// on the caller's grid.  Interval i, h = t1 - t0, a = sigma sqrt(h (1 - (t0 + t1)/2)) (the exact standard deviation of the noise integral),
+// xi ~ N(0, I):
+//     Euler-Maruyama   x+ = x + h b(x,t0) + a xi
+//     Heun             xp = x + h b(x,t0) + a xi ;  x+ = x + (h/2)(b(x,t0) + b(xp,t1)) + a xi      (the same xi)
+// Scalars: h, a, c1 = 1 + sigma^2 t / 2 (t = the evaluation's time) and c2 = sigma^2 / 2 are formed in fp64 from the fp32 grid entries and
+// the fp32 sigma and rounded once to fp32; h/2 is exact.  Elementwise, single-rounded fp32 in this order: b = c1 v - c2 x (two products,
+// one difference); x+ = (x + h b) + a xi; Heun's corrector (x + (h/2)(b1 + b2)) + a xi.  With sigma = 0: c1 = 1, c2 = 0, a = 0 and the
+// step is deterministic Euler / Heun whatever xi.
+//
+// The noise field (flocoder_amd/noise.py is its host form): Philox4x32-10 with key (seed lo, seed hi) and counter (j, draw, sample id lo,
+// sample id hi), j = the float4 group inside the sample's m elements, draw = the interval index counted from the call's first interval.
+// The four output words r_k give u_k = ((r_k >> 9) + 0.5) 2^-23 (exact in fp32, in (0, 1)) and elements 4j .. 4j+3 are
+//     R0 cos(pi w1), R0 sin(pi w1), R1 cos(pi w3), R1 sin(pi w3)       R = sqrt(-2 ln u) (logf, then a correctly rounded square root),
+//     w = 2 u (exact), sincospif
+// so |z| <= sqrt(48 ln 2) = 5.77 (u >= 2^-24).  A value depends on (seed, draw, sample id, position in the sample) alone: not on the row
+// the sample sits in, the batch size or the launch geometry.
+
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__device__ __forceinline__ float philox_u01(unsigned r) { return mul_(add_((float)(r >> 9), 0.5f), 1.1920928955078125e-07f); }   // 2^-23
+__device__ __forceinline__ void box_muller(float u, float w_half, float* zc, float* zs) {
+    const float R = __fsqrt_rn(mul_(-2.0f, logf(u)));
+    float sn, cs;
+    sincospif(mul_(2.0f, w_half), &sn, &cs);
+    *zc = mul_(R, cs); *zs = mul_(R, sn);
+}
+__device__ __forceinline__ float4 normal4(unsigned long long seed, unsigned draw, unsigned long long sid, unsigned j) {
+    unsigned r[4];
+    philox4x32_10(j, draw, (unsigned)sid, (unsigned)(sid >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+    float4 z;
+    box_muller(philox_u01(r[0]), philox_u01(r[1]), &z.x, &z.y);
+    box_muller(philox_u01(r[2]), philox_u01(r[3]), &z.z, &z.w);
+    return z;
+}
+
+// fc_ode_normal_field: out[b][4j .. 4j+3] of the field; sids == nullptr: sample id = b
+__global__ void __launch_bounds__(256) ode_normal_field_kernel(float* out, unsigned long long seed, unsigned draw, const long long* sids,
+                                                               int n, int m) {
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const int b = i / m;
+        const unsigned long long sid = sids ? (unsigned long long)sids[b] : (unsigned long long)b;
+        *reinterpret_cast<float4*>(out + i) = normal4(seed, draw, sid, (unsigned)((i - b * m) >> 2));
+    }
+}
+
+__device__ __forceinline__ float sde_drift(float c1, float c2, float v, float x) { return sub_(mul_(c1, v), mul_(c2, x)); }
+__device__ __forceinline__ float sde_step(float x, float hb, float b, float a, float xi) { return add_(add_(x, mul_(hb, b)), mul_(a, xi)); }
+
+// One launch behind each forward of an interval.  The interval index is *step - 1: ode_time_kernel opened the interval and moved the
+// counter, so a captured interval is position-independent.  stage 0: Euler-Maruyama, y updated in place.  stage 1: Heun's predictor --
+// b1 = b(y, t0) kept, xs = the predicted state, and block 0 publishes t1's scaled time rows for the second forward.  stage 2: Heun's
+// corrector from v2 = v(xs, t1), y updated in place.  use_noise: xi is slice *step - 1 of prm->noise ([intervals][B][m] fp32) instead of
+// the generated field.
+__global__ void __launch_bounds__(256) ode_sde_update_kernel(const int* step, const float* ts, const SdeParams* prm, const long long* sids,
+                                                             float* y, float* xs, float* b1, const float* v2, int n, int m, int cfg_on,
+                                                             float cfg, float sigma, int stage, int use_noise, float t_scale, float* tvec,
+                                                             int rows) {
+    const int it = *step - 1;
+    const float t0 = ts[it], t1 = ts[it + 1];
+    if (stage == 1 && blockIdx.x == 0) {
+        const float tv = mul_(t1, t_scale);
+        for (int r = threadIdx.x; r < rows; r += 256) tvec[r] = tv;
+    }
+    const double hd = (double)t1 - (double)t0, s2 = 0.5 * (double)sigma * (double)sigma;
+    const double rem = 1.0 - 0.5 * ((double)t0 + (double)t1);
+    const float h = (float)hd, a = (float)((double)sigma * sqrt(hd * (rem > 0.0 ? rem : 0.0)));
+    const float c1 = (float)(1.0 + s2 * (double)(stage == 2 ? t1 : t0)), c2 = (float)s2;
+    const float hb = stage == 2 ? h * 0.5f : h;
+    const unsigned long long seed = prm->seed;
+    const float* xi_all = use_noise ? prm->noise + (size_t)it * (size_t)n : nullptr;
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const float4 v = load_v(v2, i, n, cfg_on, cfg);
+        const float4 yv = *reinterpret_cast<const float4*>(y + i);
+        float4 xi;
+        if (xi_all) xi = *reinterpret_cast<const float4*>(xi_all + i);
+        else {
+            const int b = i / m;
+            xi = normal4(seed, (unsigned)it, (unsigned long long)sids[b], (unsigned)((i - b * m) >> 2));
+        }
+        float4 bv, o;
+        if (stage == 2) {
+            const float4 xp = *reinterpret_cast<const float4*>(xs + i), p = *reinterpret_cast<const float4*>(b1 + i);
+            bv.x = add_(p.x, sde_drift(c1, c2, v.x, xp.x)); bv.y = add_(p.y, sde_drift(c1, c2, v.y, xp.y));      // b1 + b2
+            bv.z = add_(p.z, sde_drift(c1, c2, v.z, xp.z)); bv.w = add_(p.w, sde_drift(c1, c2, v.w, xp.w));
+        } else {
+            bv.x = sde_drift(c1, c2, v.x, yv.x); bv.y = sde_drift(c1, c2, v.y, yv.y);
+            bv.z = sde_drift(c1, c2, v.z, yv.z); bv.w = sde_drift(c1, c2, v.w, yv.w);
+            if (stage == 1) *reinterpret_cast<float4*>(b1 + i) = bv;
+        }
+        o.x = sde_step(yv.x, hb, bv.x, a, xi.x); o.y = sde_step(yv.y, hb, bv.y, a, xi.y);
+        o.z = sde_step(yv.z, hb, bv.z, a, xi.z); o.w = sde_step(yv.w, hb, bv.w, a, xi.w);
+        *reinterpret_cast<float4*>((stage == 1 ? xs : y) + i) = o;
+    }
+}
+
+// sample ids of a call that passes none: 0 .. B-1
+__global__ void __launch_bounds__(256) ode_iota_kernel(long long* ids, int B) {
+    for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) ids[b] = b;
+}
+
+static int sde_shape_ok(int n, int m) {
+    if (n < 4 || m < 4 || (m & 3) || n % m) return fail(FC_E_SHAPE, "ode: elements per sample must be a positive multiple of 4 and divide the batch's");
+    return FC_OK;
+}
+int ode_normal_field_launch(float* out, unsigned long long seed, unsigned draw, const int64_t* sids, int n, int m, hipStream_t s) {
+    FC_TRY(sde_shape_ok(n, m));
+    hipLaunchKernelGGL(ode_normal_field_kernel, dim3(egrid(n)), dim3(256), 0, s, out, seed, draw, reinterpret_cast<const long long*>(sids), n, m);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_sde_update_launch(const int* step, const float* ts, const SdeParams* prm, const int64_t* sids, float* y, float* xs, float* b1,
+                          const float* v2, int n, int m, int cfg_on, float cfg, float sigma, int stage, int use_noise, float t_scale,
+                          float* tvec, int rows, hipStream_t s) {
+    FC_TRY(sde_shape_ok(n, m));
+    if (stage < 0 || stage > 2) return fail(FC_E_ARG, "ode: SDE stage must lie in [0, 2]");
+    hipLaunchKernelGGL(ode_sde_update_kernel, dim3(egrid(n)), dim3(256), 0, s, step, ts, prm,
+                       reinterpret_cast<const long long*>(sids), y, xs, b1, v2, n, m, cfg_on, cfg, sigma, stage, use_noise, t_scale, tvec, rows);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_iota_launch(int64_t* ids, int B, hipStream_t s) {
+    hipLaunchKernelGGL(ode_iota_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, reinterpret_cast<long long*>(ids), B);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }

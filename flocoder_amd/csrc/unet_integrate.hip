@@ -218,7 +218,10 @@ static int integrator_prologue(const CallFrame& f, const float* x_dev, const flo
 
 // Conditioning of every evaluation of a fixed-grid call, once, into ig.pre (*pre_on_out: the table is in use; not for a single interval
 // or a table beyond 2 GiB).
-static int cond_table(const CallFrame& f, int method, int n_steps, float t_scale, bool* pre_on_out) {
+// `pattern`: the evaluation times of an interval -- FC_METHOD_EULER: t_i; FC_METHOD_RK4: the four stage times; kTimesPair: t_i, t_{i+1}.
+static constexpr int kTimesPair = 2;
+static_assert(FC_METHOD_EULER == 0 && FC_METHOD_RK4 == 1, "ode_all_times_launch takes the method codes as its pattern");
+static int cond_table(const CallFrame& f, int pattern, int n_steps, float t_scale, bool* pre_on_out) {
     fc_unet* u = f.u;
     IntegratorState& ig = u->ig;
     const bool has_ids = f.has_ids, cfg_on = f.cfg_on;
@@ -227,7 +230,7 @@ static int cond_table(const CallFrame& f, int method, int n_steps, float t_scale
     // Conditioning of every evaluation, once: the grid is known, so time MLP / class MLP / FiLM projections of all (evaluation, row)
     // pairs are three launches here instead of three at the head of each forward (44 us of every 1.6 ms step inside the replayed graph:
     // cold weights, latency-bound).  Rows are bit-identical to the per-forward ones (same kernels, same time arithmetic).
-    const int n_evals = method == FC_METHOD_RK4 ? 4 * n_steps : n_steps;
+    const int n_evals = pattern == FC_METHOD_RK4 ? 4 * n_steps : (pattern == kTimesPair ? 2 * n_steps : n_steps);
     const size_t R = (size_t)n_evals * rows, tvn = ((size_t)n_evals + 3) & ~(size_t)3;
     const size_t need = tvn + R * u->td * 3 + R * u->S;
     const bool pre_on = *pre_on_out = n_steps >= 2 && need * sizeof(float) <= (2ull << 30) && R < (1u << 30) / (unsigned)u->S;
@@ -245,7 +248,7 @@ static int cond_table(const CallFrame& f, int method, int n_steps, float t_scale
         if (ig.pre_ss != c1 + R * u->td)   // the table moved inside the buffer (another number of evaluations): graphs bake its address
             ig.drop_graphs();
         ig.pre_ss = c1 + R * u->td;
-        FC_TRY(ode_all_times_launch(ig.ts_dev, n_steps, method == FC_METHOD_RK4, t_scale, tv, s));
+        FC_TRY(ode_all_times_launch(ig.ts_dev, n_steps, pattern, t_scale, tv, s));
         TembArgs ta = u->temb_proto;
         ta.B = (int)R; ta.time = tv; ta.rows_per_eval = rows; ta.class_ids = has_ids ? ig.ids_own : nullptr; ta.class_batch_mod = B;
         ta.null_from = cfg_on ? B : 0; ta.t_out = te;
@@ -521,6 +524,83 @@ int fc_debug_unet_guided_buffers(const fc_unet* u, const float** stage_x, const 
     if (w) *w = u->ig.g_w;
     if (q) *q = u->ig.g_q;
     return FC_OK;
+}
+
+// ---- stochastic sampling on a fixed grid ---------------------------------------------------------------------------------------------
+// fc_unet_integrate_sde: fc_unet_integrate's frame with ode.hip's SDE update behind each forward.  An interval is ode_time_launch (opens
+// the interval: scaled time rows of t_i, the counter moves), the plan, the update -- the launch structure of the Euler step with guidance;
+// Heun adds a second plan run and update.  The seed, the noise pointer and the sample ids reach the kernel through device memory
+// (ig.sde_prm, ig.sde_ids), so the key of a captured interval carries the scheme, sigma's bits and the noise source and nothing of the call.
+static int alloc_sde(fc_unet* u) {
+    IntegratorState& ig = u->ig;
+    if (ig.sde_prm) return FC_OK;
+    FC_TRY(ig.get(&ig.sde_ids, (size_t)u->maxB, "integrator.sde"));
+    return ig.get(&ig.sde_prm, 1, "integrator.sde");       // last: a first call that failed half-way allocates again
+}
+
+static int enqueue_sde_step(const CallFrame& f, int scheme, float cfg, float sigma, int use_noise, float t_scale, bool pre_on) {
+    fc_unet* u = f.u;
+    const IntegratorState& ig = u->ig;
+    const int rows = f.rows, n = f.n, m = f.n / f.B, cf = f.cfg_on ? 1 : 0;
+    hipStream_t s = f.s;
+    FwdCtx c = step_ctx(f, pre_on);
+    FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, rows, s));
+    c.x = ig.y;
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // v(y, t_i)
+    if (scheme == FC_SDE_EULER_MARUYAMA)
+        return ode_sde_update_launch(ig.step, ig.ts_dev, ig.sde_prm, ig.sde_ids, ig.y, ig.xs, ig.k1, ig.v2, n, m, cf, cfg, sigma, 0, use_noise,
+                                     t_scale, ig.tvec, rows, s);
+    FC_TRY(ode_sde_update_launch(ig.step, ig.ts_dev, ig.sde_prm, ig.sde_ids, ig.y, ig.xs, ig.k1, ig.v2, n, m, cf, cfg, sigma, 1, use_noise,
+                                 t_scale, ig.tvec, rows, s));                                                            // predictor, t_{i+1}
+    c.x = ig.xs;
+    FC_TRY(run_plan(u->plan, c, s));                                                                                     // v(xs, t_{i+1})
+    return ode_sde_update_launch(ig.step, ig.ts_dev, ig.sde_prm, ig.sde_ids, ig.y, ig.xs, ig.k1, ig.v2, n, m, cf, cfg, sigma, 2, use_noise,
+                                 t_scale, ig.tvec, rows, s);
+}
+
+int fc_unet_integrate_sde(fc_unet* u, int scheme, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
+                          const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, float sigma, uint64_t seed,
+                          const int64_t* sample_ids, const float* noise, void* stream) {
+    if (!u || !x_dev || !ts_host || B < 1) return fail(FC_E_ARG, "fc_unet_integrate_sde: null argument");
+    if (scheme != FC_SDE_EULER_MARUYAMA && scheme != FC_SDE_HEUN) return fail(FC_E_ARG, "fc_unet_integrate_sde: unknown scheme");
+    if (n_points < 2) return fail(FC_E_ARG, "fc_unet_integrate_sde: the time grid needs at least two points");
+    for (int i = 0; i < n_points; ++i)
+        if (!(ts_host[i] >= 0.0f && ts_host[i] <= 1.0f) || (i > 0 && ts_host[i] < ts_host[i - 1]))
+            return fail(FC_E_ARG, "fc_unet_integrate_sde: the grid must be non-decreasing within [0, 1] (the diffusion is sigma sqrt(1-t))");
+    if (!(sigma >= 0.0f) || !std::isfinite(sigma)) return fail(FC_E_ARG, "fc_unet_integrate_sde: sigma must be finite and >= 0");
+    if ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(noise)) & 15)
+        return fail(FC_E_ARG, "fc_unet_integrate_sde: x and the noise must be 16-byte aligned (the kernels read them as float4)");
+    CallFrame f;
+    FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
+    IntegratorState& ig = u->ig;
+    FC_TRY(alloc_sde(u));
+    const int n_steps = n_points - 1, use_noise = noise ? 1 : 0, heun = scheme == FC_SDE_HEUN;
+    hipStream_t s = f.s;
+    FC_TRY(f.enter());
+    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
+    const SdeParams prm{seed, noise};
+    FC_HIP(hipMemcpyAsync(ig.sde_prm, &prm, sizeof(prm), hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns
+    if (sample_ids) FC_HIP(hipMemcpyAsync(ig.sde_ids, sample_ids, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    else FC_TRY(ode_iota_launch(ig.sde_ids, B, s));
+    bool pre_on = false;
+    FC_TRY(cond_table(f, heun ? kTimesPair : FC_METHOD_EULER, n_steps, t_scale, &pre_on));
+    GraphKey key = graph_key(f, GraphKey::Sde, cfg_strength, t_scale);
+    key.pre_on = pre_on; key.sde_scheme = scheme; key.sde_noise = use_noise; key.sde_sigma = fbits(sigma);
+    FC_TRY(replay_steps(f, key, n_steps, heun ? 2 : 1,
+                        [&] { return enqueue_sde_step(f, scheme, cfg_strength, sigma, use_noise, t_scale, pre_on); }));
+    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
+    return f.leave();
+}
+
+int fc_ode_normal_field(float* out_dev, uint64_t seed, int64_t draw_index, const int64_t* sample_ids_dev, int batch, int64_t per_sample,
+                        void* stream) {
+    if (!out_dev) return fail(FC_E_ARG, "fc_ode_normal_field: null argument");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 15) return fail(FC_E_ARG, "fc_ode_normal_field: out must be 16-byte aligned (written as float4)");
+    if (draw_index < 0 || draw_index > 0xffffffffLL) return fail(FC_E_ARG, "fc_ode_normal_field: the draw index is a 32-bit counter word");
+    if (batch < 1 || per_sample < 4 || (per_sample & 3) || (long long)batch * per_sample > 0x7fffffffLL)
+        return fail(FC_E_SHAPE, "fc_ode_normal_field: elements per sample must be a positive multiple of 4, batch * per_sample < 2^31");
+    return ode_normal_field_launch(out_dev, seed, (unsigned)draw_index, sample_ids_dev, batch * (int)per_sample, (int)per_sample,
+                                   static_cast<hipStream_t>(stream));
 }
 
 // ---- adaptive RK45 ----------------------------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@ namespace fc {
 
 // What a cached graph was captured for: two calls share a graph exactly when every field agrees.
 struct GraphKey {
-    enum Kind { Euler, Rk4, Rk45Coupled, Rk45PerSample, Rk4Guided };
+    enum Kind { Euler, Rk4, Rk45Coupled, Rk45PerSample, Rk4Guided, Sde };
     Kind kind = Euler;
     int B = 0, mask_mode = 0;
     bool cfg_on = false, has_ids = false;
@@ -18,7 +18,12 @@ struct GraphKey {
     int steps = 0;                                          // fixed grids: consecutive intervals in the graph
     bool dense = false;                                     // RK45: an attempt with t_eval has one more launch
     uint32_t cfg_strength = 0, dt_euler = 0, t_scale = 0;   // the floats' bits (dt_euler: 0 for RK45)
-    auto tie() const { return std::tie(kind, B, mask_mode, cfg_on, has_ids, pre_on, steps, dense, cfg_strength, dt_euler, t_scale); }
+    int sde_scheme = 0, sde_noise = 0;                      // SDE: the scheme and the noise source (0 generated, 1 supplied)
+    uint32_t sde_sigma = 0;                                 // SDE: sigma's bits
+    auto tie() const {
+        return std::tie(kind, B, mask_mode, cfg_on, has_ids, pre_on, steps, dense, cfg_strength, dt_euler, t_scale, sde_scheme, sde_noise,
+                        sde_sigma);
+    }
     bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
 };
 
@@ -45,6 +50,9 @@ struct IntegratorPlanState {
     // mask_own), {sigma_y^2, gamma} of the call, and for the exact form w and q = (dv/dx)^T w of the running stage; allocated by the
     // first call
     float *g_y = nullptr, *g_keep = nullptr, *g_sc = nullptr, *g_w = nullptr, *g_q = nullptr;
+    // stochastic sampling (fc_unet_integrate_sde): the call's seed / noise pointer and its sample ids; allocated by the first call
+    SdeParams* sde_prm = nullptr;
+    int64_t* sde_ids = nullptr;
 
     template <class T> int get(T** out, size_t count, const char* tag) {
         void* p = nullptr;

@@ -204,6 +204,115 @@ def generate_latents_guided(model, shape, measurement, keep, n_steps=50, init_st
     return _rk4_loop(v_func, current_points, ts), nfe
 
 
+def normal_field(seed, draw_index, sample_ids, shape, device=None, dtype=torch.float32):
+    """The counter-based normal field of the stochastic samplers as a tensor ``[B, *shape[1:]]``: row b holds the normals of
+    ``(seed, draw_index, sample_ids[b])`` (``flocoder_amd.noise``).  On a GPU device the library generates it (``fc_ode_normal_field``, fp32
+    arithmetic); on the CPU ``noise.normal_field`` does (fp64 arithmetic, then rounded to ``dtype``)."""
+    from . import _binding as B
+    from . import noise as N
+    device = torch.device("cpu" if device is None else device)
+    bsz, per = int(shape[0]), 1
+    for d in shape[1:]:
+        per *= int(d)
+    if device.type != "cuda":
+        ids = sample_ids.detach().cpu().numpy() if torch.is_tensor(sample_ids) else sample_ids
+        return torch.from_numpy(N.normal_field(seed, draw_index, ids, per)).reshape(tuple(shape)).to(device=device, dtype=dtype)
+    ids = torch.as_tensor(sample_ids, dtype=torch.int64).to(device).contiguous()
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    B.check(B.lib().fc_ode_normal_field(B.ptr(out), int(seed) & 0xffffffffffffffff, int(draw_index), B.ptr(ids), bsz, per,
+                                        B.current_stream(device)))
+    return out.to(dtype)
+
+
+_SDE_EVALS = {"euler_maruyama": 1, "heun": 2}
+
+
+@torch.no_grad()
+def generate_latents_sde(model, shape, n_steps=50, cond=None, cfg_strength=3.0, source=None, init_latents=None, init_strength=0.0,
+                         sigma=1.0, method="euler_maruyama", seed=0, sample_ids=None, noise=None):
+    """Stochastic sampling: the SDE with the marginals of the probability-flow ODE that ``generate_latents_rk4`` integrates.  On the
+    linear path ``x_t = (1-t) x0 + t x1`` with ``x0 ~ N(0, I)`` the score is ``(t v - x)/(1-t)``, and with diffusion ``sigma^2 (1-t)``
+
+        dx = b(x,t) dt + sigma sqrt(1-t) dW          b(x,t) = (1 + sigma^2 t / 2) v(x,t) - (sigma^2 / 2) x
+
+    (``v`` after classifier-free guidance; finite on all of [0, 1]).  Start and grid are ``generate_latents_rk4``'s: ``source`` (or randn),
+    with ``init_latents`` the blend ``(1 - s) source + s init_latents`` on ``rk4_time_grid(n_steps, s)`` -- SDEdit-style editing.  Interval i
+    with ``h = t_{i+1} - t_i``, ``a = sigma sqrt(h (1 - (t_i + t_{i+1})/2))`` (the exact standard deviation of the noise integral) and
+    ``xi ~ N(0, I)``:
+
+        method="euler_maruyama"   x+ = x + h b(x,t_i) + a xi
+        method="heun"             xp = x + h b(x,t_i) + a xi;   x+ = x + (h/2) (b(x,t_i) + b(xp,t_{i+1})) + a xi      (the same xi)
+
+    ``sigma = 0`` is deterministic Euler / Heun on the grid.  The noise is reproducible and independent of batching: ``xi`` of interval i
+    and row b is the counter-based normal field of ``(seed, i, sample_ids[b])`` (``flocoder_amd.noise``; ``sample_ids`` int64 ``[B]``,
+    default ``arange(B)`` -- a sharded caller passes the global indices of its rows), or ``noise[i]`` when a tensor
+    ``[len(ts) - 1, *shape]`` is supplied.  Returns ``(latents, nfe)`` with nfe the true number of evaluations, ``(len(ts) - 1)`` times 1
+    or 2 (a guided pair counts once).
+
+    A ``flocoder_amd.Unet`` runs the loop in the library (``Unet.integrate_sde``: captured intervals, the noise generated inside the
+    update kernel); on the CPU it raises like the other integrators.  Any other callable takes the torch path with the same field
+    (``fc_ode_normal_field`` for GPU tensors, the NumPy form on the CPU)."""
+    if method not in _SDE_EVALS:
+        raise ValueError(f"method={method!r}: 'euler_maruyama' or 'heun'")
+    sigma = float(sigma)
+    if not sigma >= 0:
+        raise ValueError("sigma must be >= 0")
+    unet = isinstance(model, Unet)
+    if hasattr(model, "parameters") and any(True for _ in model.parameters()):
+        p0 = next(model.parameters())
+    else:
+        p0 = source if source is not None else torch.zeros(())
+    device, dtype = p0.device, p0.dtype
+    current_points = source if source is not None else torch.randn(shape, device=device, dtype=dtype)
+    if init_latents is None:
+        ts = rk4_time_grid(n_steps, dtype=dtype)
+    else:
+        current_points = (1 - init_strength) * current_points + init_strength * init_latents
+        ts = rk4_time_grid(n_steps, init_strength, dtype=dtype)
+    n_int = len(ts) - 1
+    if n_int < 1:
+        raise ValueError(f"n_steps={n_steps}, init_strength={init_strength}: the grid needs at least two points (one interval)")
+    nfe = n_int * _SDE_EVALS[method]
+    bsz = int(shape[0])
+    if sample_ids is not None:
+        sample_ids = torch.as_tensor(sample_ids)
+        if sample_ids.dtype != torch.int64 or tuple(sample_ids.shape) != (bsz,):
+            raise ValueError("sample_ids must be an int64 tensor of shape [batch]")
+    if noise is not None and tuple(noise.shape) != (n_int,) + tuple(shape):
+        raise ValueError(f"noise must have shape {(n_int,) + tuple(shape)}, got {tuple(noise.shape)}")
+
+    if unet:
+        if not current_points.is_cuda:
+            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+        x = _start(current_points, None, device)
+        _, cls, mask, ones = _conditioning(model, cond)
+        model.integrate_sde(x, ts, sigma=sigma, method=method, seed=seed, sample_ids=sample_ids,
+                            noise=None if noise is None else noise.to(device), class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
+                            mask_is_ones=ones)
+        return x, nfe
+
+    cond = _conditioning(model, cond)[0]
+    x = current_points.to(device)
+    ts = ts.to(device)
+    ids = torch.arange(bsz, dtype=torch.int64) if sample_ids is None else sample_ids
+    t_vec_template = torch.zeros(bsz, device=device, dtype=dtype)
+    v_func = partial(v_func_cfg, model, cond, cfg_strength, t_vec_template)
+    s2 = 0.5 * sigma * sigma
+    drift = lambda xx, t: (1 + s2 * t) * v_func(xx, t) - s2 * xx
+    for i in range(n_int):
+        t0, t1 = ts[i], ts[i + 1]
+        h = t1 - t0
+        a = sigma * torch.sqrt(h * (1 - (t0 + t1) / 2))
+        xi = noise[i].to(device=device, dtype=x.dtype) if noise is not None else normal_field(seed, i, ids, shape, device, x.dtype)
+        b0 = drift(x, t0)
+        if method == "euler_maruyama":
+            x = x + h * b0 + a * xi
+        else:
+            xp = x + h * b0 + a * xi
+            x = x + (h / 2) * (b0 + drift(xp, t1)) + a * xi
+    return x, nfe
+
+
 @torch.no_grad()
 def euler_sampler(model, shape, sample_N, device=None, cond=None, source=None, eps=1e-3, cfg_strength=0.0):
     """Legacy Euler sampler, train_sd_flowers.py:50-67: x += model(x, 999 t_i, cond)/N on the un-warped grid, nfe = N.
@@ -467,9 +576,16 @@ def generate_latents_rk45(model, shape, device=None, cond=None, cfg_strength=3.0
 
 @torch.no_grad()
 def generate_latents(model, shape, method='rk4', n_steps=50, cond=None, cfg_strength=3.0, device=None, source=None,
-                     init_latents=None, init_strength=0.0, debug=False):
+                     init_latents=None, init_strength=0.0, debug=False, **sde_kw):
     """sampling.py:128-146.  'rk45' selects generate_latents_rk45 (undefined upstream; built here from the legacy RK45
-    sampler); 'rk45_per_sample' selects it with one solve per sample (an extension); 'euler' selects the legacy sampler."""
+    sampler); 'rk45_per_sample' selects it with one solve per sample (an extension); 'euler' selects the legacy sampler; 'sde' /
+    'sde_heun' select generate_latents_sde with the Euler-Maruyama / Heun step (an extension; its keywords ``sigma``, ``seed``,
+    ``sample_ids``, ``noise`` pass through and are refused for every other method)."""
+    if method in ("sde", "sde_heun"):
+        return generate_latents_sde(model, shape, n_steps, cond, cfg_strength, source=source, init_latents=init_latents,
+                                    init_strength=init_strength, method="heun" if method == "sde_heun" else "euler_maruyama", **sde_kw)
+    if sde_kw:
+        raise TypeError(f"generate_latents(method={method!r}) takes no {sorted(sde_kw)}")
     if method in ("rk45", "rk45_per_sample"):
         if init_latents is not None:
             raise ValueError(f"init_latents is not defined for method={method!r} (upstream has no such integration)")
@@ -505,8 +621,9 @@ def decode_latents(codec, latents, is_midi=False, keep_gray=False, device=None, 
 @torch.no_grad()
 def sampler(model, codec, method='rk4', batch_size=256, n_steps=100, cond=None, n_classes=0, latent_shape=(4, 16, 16),
             cfg_strength=3.0, is_midi=False, keep_gray=False, device=None, source=None, init_image=None, init_strength=0.0,
-            debug=False):
-    """sampling.py:186-229: integrate, then decode.  Returns (pred_latents, decoded_pred, nfe).
+            debug=False, **sde_kw):
+    """sampling.py:186-229: integrate, then decode.  Returns (pred_latents, decoded_pred, nfe).  ``method`` as ``generate_latents``,
+    'sde' / 'sde_heun' included (their keywords pass through).
     Tolerates parameter-less codecs and cond=None, which crash upstream."""
     if device is None:
         device = next(model.parameters()).device
@@ -539,7 +656,7 @@ def sampler(model, codec, method='rk4', batch_size=256, n_steps=100, cond=None, 
         cond['mask_cond'] = cond['mask_cond'][:batch_size]
 
     pred_latents, nfe = generate_latents(model, shape, method, n_steps, cond, cfg_strength, device=device, source=source,
-                                         init_latents=init_latents, init_strength=init_strength)
+                                         init_latents=init_latents, init_strength=init_strength, **sde_kw)
     decoded_pred = decode_latents(codec, pred_latents, is_midi, keep_gray, device=device)
     return pred_latents, decoded_pred, nfe
 

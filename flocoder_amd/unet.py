@@ -72,6 +72,7 @@ def validate_tol(rtol, atol):
 
 
 _GPU_ONLY = "flocoder_amd integrators run on MI355X (gfx950) only"
+_SDE_METHODS = {"euler_maruyama": B.FC_SDE_EULER_MARUYAMA, "heun": B.FC_SDE_HEUN}
 
 
 class _UnetFunction(torch.autograd.Function):
@@ -540,6 +541,52 @@ class Unet(NativeModule):
             self.release_training_plan()
             if rows0.value > 0:                         # the reservation the caller had, in the form it had
                 B.check(lib.fc_unet_reserve(hnd, rows0.value, h0.value, w0.value))
+        return x
+
+    def integrate_sde(self, x: torch.Tensor, ts: torch.Tensor, *, sigma: float, method: str, seed: int = 0,
+                      sample_ids: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                      class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,
+                      mask_is_ones: bool = False, t_scale: float = 999.0, check: bool = True) -> torch.Tensor:
+        """``fc_unet_integrate_sde``: integrate ``x`` in place along the fp32 grid ``ts`` (non-decreasing, within [0, 1]) with the SDE that
+        shares the flow's marginals, ``dx = ((1 + sigma^2 t/2) v - sigma^2 x/2) dt + sigma sqrt(1-t) dW``; returns ``x``.  ``method``:
+        ``"euler_maruyama"`` (one evaluation per interval) or ``"heun"`` (two, one noise draw).  The noise of interval i is ``noise[i]``
+        (fp32 ``[len(ts)-1, *x.shape]`` on x's device) or, without ``noise``, the library's counter-based normal field
+        (``flocoder_amd.noise``) of ``seed`` and the per-row ``sample_ids`` (int64 ``[B]``, default ``arange(B)``): a row's noise follows its
+        id, not its position or the batch size.  Class ids, guidance, mask and ``check`` as ``integrate``."""
+        if method not in _SDE_METHODS:
+            raise ValueError(f"method={method!r}: one of {sorted(_SDE_METHODS)}")
+        sigma = float(sigma)
+        if not (sigma >= 0 and math.isfinite(sigma)):
+            raise ValueError("sigma must be finite and >= 0")
+        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength, cpu_error=_GPU_ONLY + "; there is no CPU path")
+        dev = x.device
+        bsz, _, h, w = x.shape
+        if x.data_ptr() % 16:
+            raise ValueError("x must be 16-byte aligned (the kernels read it as float4)")
+        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
+        if ts_host.dim() != 1 or ts_host.numel() < 2:
+            raise ValueError("the time grid needs at least two points")
+        if not bool(((ts_host >= 0) & (ts_host <= 1)).all()) or not bool((ts_host[1:] >= ts_host[:-1]).all()):
+            raise ValueError("the time grid must be non-decreasing within [0, 1]")
+        if noise is not None:
+            if tuple(noise.shape) != (ts_host.numel() - 1,) + tuple(x.shape) or noise.device != dev:
+                raise ValueError(f"noise must have shape {(ts_host.numel() - 1,) + tuple(x.shape)} on x's device, got {tuple(noise.shape)} "
+                                 f"on {noise.device}")
+            noise = noise.to(torch.float32).contiguous()
+            if noise.data_ptr() % 16:
+                noise = noise.clone()
+        if sample_ids is None:
+            sample_ids = torch.arange(bsz, dtype=torch.int64, device=dev)
+        if sample_ids.dtype != torch.int64 or tuple(sample_ids.shape) != (bsz,):
+            raise ValueError("sample_ids must be an int64 tensor of shape [batch]")
+        sample_ids = sample_ids.to(dev).contiguous()
+        lib = B.lib()
+        B.check(lib.fc_unet_reserve(hnd, rows, h, w))
+        B.check(lib.fc_unet_integrate_sde(hnd, _SDE_METHODS[method], B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)),
+                                          ts_host.numel(), float(t_scale), B.ptr(class_ids), float(cfg_strength or 0.0), B.ptr(mask),
+                                          int(mask_is_ones), sigma, int(seed) & 0xffffffffffffffff, B.ptr(sample_ids), B.ptr(noise),
+                                          B.current_stream(dev)))
+        self._integrator_check(hnd, dev, check)
         return x
 
     def release_training_plan(self) -> None:

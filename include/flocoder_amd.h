@@ -240,6 +240,29 @@ int fc_unet_integrate_guided(fc_unet* u, float* x_dev, int batch, int height, in
 int fc_ode_guided_correct(const float* v_dev, const float* x_dev, const float* y_dev, const float* a_dev, int64_t n, float t, float sigma_y,
                           float gamma, float* out_dev, void* stream);
 
+/* Stochastic sampling: the SDE that shares the marginals of the probability-flow ODE on the linear path x_t = (1-t) x0 + t x1 with
+ * diffusion sigma^2 (1-t),
+ *     dx = b(x,t) dt + sigma sqrt(1-t) dW        b(x,t) = (1 + sigma^2 t / 2) v(x,t) - (sigma^2 / 2) x
+ * (v after classifier-free guidance), along ts_host (n_points >= 2, non-decreasing, within [0, 1]).  Interval i with h = t_{i+1} - t_i,
+ * a = sigma sqrt(h (1 - (t_i + t_{i+1})/2)) and xi ~ N(0, I):
+ *     FC_SDE_EULER_MARUYAMA   x+ = x + h b(x,t_i) + a xi                                             (1 evaluation)
+ *     FC_SDE_HEUN             xp = x + h b(x,t_i) + a xi;  x+ = x + (h/2)(b(x,t_i) + b(xp,t_{i+1})) + a xi   (2 evaluations, one xi)
+ * sigma = 0 is deterministic Euler / Heun on the grid.  xi is slice i of noise_dev (fp32 [n_points-1, B, C, H, W], 16-byte aligned, read
+ * while the call runs) or, with noise_dev NULL, the library's counter-based normal field: Philox4x32-10, key = seed, counter =
+ * (float4 group inside the sample, i, sample id) with sample_ids_dev [B] (int64; NULL: 0 .. B-1) -- a sample's noise depends on its id,
+ * not on its row or the batch size.  h, a and the two drift coefficients are formed in fp64 from the fp32 grid and sigma and rounded
+ * once; the elementwise part is single-rounded fp32.  Captured and replayed like fc_unet_integrate (seed, ids and the noise pointer live
+ * in device memory: one graph serves all of them); class ids, guidance, mask conditioning and asynchrony as there. */
+#define FC_SDE_EULER_MARUYAMA 0
+#define FC_SDE_HEUN 1
+int fc_unet_integrate_sde(fc_unet* u, int scheme, float* x_dev, int batch, int height, int width, const float* ts_host, int n_points,
+                          float t_scale, const int64_t* class_ids_dev, float cfg_strength, const float* mask_dev, int mask_is_ones,
+                          float sigma, uint64_t seed, const int64_t* sample_ids_dev, const float* noise_dev, void* stream);
+/* out_dev [batch, per_sample] (fp32, 16-byte aligned, per_sample a multiple of 4) = the normal field of fc_unet_integrate_sde for draw
+ * (interval) index draw_index and the given sample ids (NULL: 0 .. batch-1).  |value| <= sqrt(48 ln 2) = 5.77. */
+int fc_ode_normal_field(float* out_dev, uint64_t seed, int64_t draw_index, const int64_t* sample_ids_dev, int batch, int64_t per_sample,
+                        void* stream);
+
 /* ---- debug / test hooks: not part of the drop-in surface --------------------------------------- */
 /* After an exact-form fc_unet_integrate_guided call: device pointers to the last stage's input state [B,C,H,W], its scaled time rows [B],
  * its w and q = (dv/dx)^T w, while the plan that ran it stands. */
