@@ -270,21 +270,16 @@ int ode_all_times_launch(const float* ts, int n_steps, int rk4 /* 2: the pairs t
 int ode_time_launch(int* step, const float* ts, float t_scale, int rk4, float* sc, float* tvec, int rows, hipStream_t s);
 // v = cfg_on ? v_nc + cfg*(v_c - v_nc) : v   with v2 = [v_c ; v_nc] (n elements each)
 int ode_euler_update_launch(float* x, const float* v2, int n, int cfg_on, float cfg, float dt, hipStream_t s);
-// k_out = v ; xs = y + (full ? dt*k : dt*k/2) ; tvec[:] = (t + (tsel==1 ? dt/2 : dt)) * t_scale
+// measurement guidance (fc_unet_integrate_guided) of the two launches below: v corrected towards ym = keep (.) x1 before it is used.
+// xin = the state the stage's forward read, tcur its time (0: t, 1: t + dt/2, 2: t + dt; the final launch corrects at t + dt),
+// gsc = {sigma_y^2, gamma} on the device, q = (dv/dx)^T w of the same forward or NULL (identity form)
+struct Rk4Guide { const float *gsc, *xin, *ym, *keep, *q; int tcur; };
+// k_out = v ; xs = y + (full ? dt*k : dt*k/2) ; tvec[:] = (t + (tsel==1 ? dt/2 : dt)) * t_scale.  g == NULL: no guidance
 int ode_rk4_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v2, int n, int cfg_on, float cfg,
-                         int full, int tsel, float t_scale, float* tvec, int rows, hipStream_t s);
+                         int full, int tsel, float t_scale, float* tvec, int rows, const Rk4Guide* g, hipStream_t s);
 // y += (dt/6) * (k1 + 2*k2 + 2*k3 + v)
 int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v2, int n,
-                         int cfg_on, float cfg, hipStream_t s);
-// measurement guidance (fc_unet_integrate_guided): the two launches above with v corrected towards ym = keep (.) x1 before it is used.
-// xin = the state the stage's forward read, tcur its time (0: t, 1: t + dt/2, 2: t + dt), gsc = {sigma_y^2, gamma} on the device,
-// q = (dv/dx)^T w of the same forward or NULL (identity form)
-int ode_rk4_gstage_launch(const float* sc, const float* gsc, const float* y, float* xs, float* k_out, const float* v2, const float* xin,
-                          const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg, int full, int tcur, int tsel,
-                          float t_scale, float* tvec, int rows, hipStream_t s);
-int ode_rk4_gfinal_launch(const float* sc, const float* gsc, float* y, const float* k1, const float* k2, const float* k3, const float* v2,
-                          const float* xin, const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg,
-                          hipStream_t s);
+                         int cfg_on, float cfg, const Rk4Guide* g, hipStream_t s);
 // w = keep (ym - keep (xin + (1-t) v)) / (r2 keep^2 + s2): the cotangent of the exact form's data-gradient chain
 int ode_guide_w_launch(const float* sc, const float* gsc, const float* v, const float* xin, const float* ym, const float* keep, float* w,
                        int n, int tcur, hipStream_t s);

@@ -2,6 +2,10 @@
 // train_sd_flowers.py:58-64).  The state lives in the reference's NCHW boundary layout; every op is a
 // single rounded fp32 operation in the reference's order (no FMA contraction), so the only differences
 // against the CPU path come from the U-Net itself.
+//
+// rk4_step's state arithmetic is written once (stage_t, rk4_stage_state, rk4_comb4) and used by every kernel that closes a stage or an
+// interval: ode_rk4_stage_kernel / ode_rk4_final_kernel (one template each, plain and measurement-guided) and the likelihood pair
+// ode_ll_stage_kernel / ode_ll_final_kernel, which differs in its partition (one workgroup per sample), not in its arithmetic.
 #include "common.h"
 
 namespace fc {
@@ -48,49 +52,36 @@ __global__ void __launch_bounds__(256) ode_euler_update_kernel(float* x, const f
     }
 }
 
-__global__ void __launch_bounds__(256) ode_rk4_stage_kernel(const float* sc, const float* y, float* xs, float* k_out, const float* v2,
-                                                            int n, int cfg_on, float cfg, int full, int tsel, float t_scale,
-                                                            float* tvec, int rows) {
-    const float t = sc[0], dt = sc[1];
-    if (blockIdx.x == 0) {
-        const float tn = tsel == 1 ? add_(t, dt * 0.5f) : add_(t, dt);     // t + dt/2 | t + dt
-        const float tv = mul_(tn, t_scale);
-        for (int r = threadIdx.x; r < rows; r += 256) tvec[r] = tv;
-    }
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
-        const float4 k = load_v(v2, i, n, cfg_on, cfg);
-        *reinterpret_cast<float4*>(k_out + i) = k;
-        const float4 yv = *reinterpret_cast<const float4*>(y + i);
-        float4 o;
-        if (full) {   // y + dt*k3
-            o.x = add_(yv.x, mul_(dt, k.x)); o.y = add_(yv.y, mul_(dt, k.y));
-            o.z = add_(yv.z, mul_(dt, k.z)); o.w = add_(yv.w, mul_(dt, k.w));
-        } else {      // y + dt*k/2
-            o.x = add_(yv.x, mul_(dt, k.x) * 0.5f); o.y = add_(yv.y, mul_(dt, k.y) * 0.5f);
-            o.z = add_(yv.z, mul_(dt, k.z) * 0.5f); o.w = add_(yv.w, mul_(dt, k.w) * 0.5f);
-        }
-        *reinterpret_cast<float4*>(xs + i) = o;
-    }
+// time of stage `sel` of the interval in flight, with the operations that publish it to the U-Net: t | t + dt/2 | t + dt
+__device__ __forceinline__ float stage_t(float t, float dt, int sel) { return sel == 0 ? t : (sel == 1 ? add_(t, dt * 0.5f) : add_(t, dt)); }
+// the scaled time a kernel that closes stage 1..3 publishes for the next evaluation: tsel is 1 or 2, never t itself (the launch
+// wrappers check it), so the kernels carry no arm for it
+__device__ __forceinline__ float next_stage_tv(float t, float dt, int tsel, float t_scale) {
+    __builtin_assume(tsel != 0);
+    return mul_(stage_t(t, dt, tsel), t_scale);
 }
 
+// The state arithmetic of rk4_step, written once for every kernel that closes a stage or an interval (plain, guided, likelihood).
+// the next evaluation's input: y + dt*k (full, after k3) | y + dt*k/2
+__device__ __forceinline__ float4 rk4_stage_state(const float4 yv, const float4 k, float dt, int full) {
+    float4 o;
+    if (full) {
+        o.x = add_(yv.x, mul_(dt, k.x)); o.y = add_(yv.y, mul_(dt, k.y));
+        o.z = add_(yv.z, mul_(dt, k.z)); o.w = add_(yv.w, mul_(dt, k.w));
+    } else {
+        o.x = add_(yv.x, mul_(dt, k.x) * 0.5f); o.y = add_(yv.y, mul_(dt, k.y) * 0.5f);
+        o.z = add_(yv.z, mul_(dt, k.z) * 0.5f); o.w = add_(yv.w, mul_(dt, k.w) * 0.5f);
+    }
+    return o;
+}
 __device__ __forceinline__ float rk4_comb(float y, float k1, float k2, float k3, float k4, float dt6) {
     // y + (dt/6)*(k1 + 2*k2 + 2*k3 + k4), left to right
     const float s = add_(add_(add_(k1, 2.0f * k2), 2.0f * k3), k4);
     return add_(y, mul_(dt6, s));
 }
-
-__global__ void __launch_bounds__(256) ode_rk4_final_kernel(const float* sc, float* y, const float* k1, const float* k2, const float* k3,
-                                                            const float* v2, int n, int cfg_on, float cfg) {
-    const float dt6 = __fdiv_rn(sc[1], 6.0f);
-    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
-        const float4 k4 = load_v(v2, i, n, cfg_on, cfg);
-        const float4 a = *reinterpret_cast<const float4*>(k1 + i), b = *reinterpret_cast<const float4*>(k2 + i),
-                     c = *reinterpret_cast<const float4*>(k3 + i);
-        float4 yv = *reinterpret_cast<float4*>(y + i);
-        yv.x = rk4_comb(yv.x, a.x, b.x, c.x, k4.x, dt6); yv.y = rk4_comb(yv.y, a.y, b.y, c.y, k4.y, dt6);
-        yv.z = rk4_comb(yv.z, a.z, b.z, c.z, k4.z, dt6); yv.w = rk4_comb(yv.w, a.w, b.w, c.w, k4.w, dt6);
-        *reinterpret_cast<float4*>(y + i) = yv;
-    }
+__device__ __forceinline__ float4 rk4_comb4(const float4 yv, const float4 a, const float4 b, const float4 c, const float4 k4, float dt6) {
+    return make_float4(rk4_comb(yv.x, a.x, b.x, c.x, k4.x, dt6), rk4_comb(yv.y, a.y, b.y, c.y, k4.y, dt6),
+                       rk4_comb(yv.z, a.z, b.z, c.z, k4.z, dt6), rk4_comb(yv.w, a.w, b.w, c.w, k4.w, dt6));
 }
 
 // Scaled time of EVERY evaluation of an integration, with the very operations the per-step kernels above use (so a conditioning table
@@ -130,21 +121,6 @@ int ode_time_launch(int* step, const float* ts, float t_scale, int rk4, float* s
 int ode_euler_update_launch(float* x, const float* v2, int n, int cfg_on, float cfg, float dt, hipStream_t s) {
     if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
     hipLaunchKernelGGL(ode_euler_update_kernel, dim3(egrid(n)), dim3(256), 0, s, x, v2, n, cfg_on, cfg, dt);
-    FC_HIP(hipGetLastError());
-    return FC_OK;
-}
-int ode_rk4_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v2, int n, int cfg_on, float cfg, int full,
-                         int tsel, float t_scale, float* tvec, int rows, hipStream_t s) {
-    if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
-    hipLaunchKernelGGL(ode_rk4_stage_kernel, dim3(egrid(n)), dim3(256), 0, s, sc, y, xs, k_out, v2, n, cfg_on, cfg, full, tsel, t_scale,
-                       tvec, rows);
-    FC_HIP(hipGetLastError());
-    return FC_OK;
-}
-int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v2, int n, int cfg_on,
-                         float cfg, hipStream_t s) {
-    if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
-    hipLaunchKernelGGL(ode_rk4_final_kernel, dim3(egrid(n)), dim3(256), 0, s, sc, y, k1, k2, k3, v2, n, cfg_on, cfg);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -196,51 +172,42 @@ __device__ __forceinline__ float4 guide_v4(const float4 v, const float* xin, con
     }
     return make_float4(guide_apply(v.x, w.x, g), guide_apply(v.y, w.y, g), guide_apply(v.z, w.z, g), guide_apply(v.w, w.w, g));
 }
-// time of stage `sel` of the interval in flight, with the operations that published it to the U-Net: t | t + dt/2 | t + dt
-__device__ __forceinline__ float stage_t(float t, float dt, int sel) { return sel == 0 ? t : (sel == 1 ? add_(t, dt * 0.5f) : add_(t, dt)); }
 
-// ode_rk4_stage_kernel with the correction between load_v and the store of k.  xin: the state this stage's forward read (y for k1, xs
-// for k2 and k3; xs[i] is read before this thread overwrites it); tcur: that stage's time; gsc = {s2, gamma}.
-__global__ void __launch_bounds__(256) ode_rk4_gstage_kernel(const float* sc, const float* gsc, const float* y, float* xs, float* k_out,
-                                                             const float* v2, const float* xin, const float* ym, const float* keep,
-                                                             const float* q, int n, int cfg_on, float cfg, int full, int tcur, int tsel,
-                                                             float t_scale, float* tvec, int rows) {
+// One stage of rk4_step closed: k_out = the evaluation's velocity, xs = the next evaluation's input, tvec = its time (stage `tsel`).
+// Guided: the correction sits between load_v and the store of k; g.xin is the state this stage's forward read (y for k1, xs for k2 and
+// k3; xs[i] is read before this thread overwrites it), g.tcur that stage's time.  The plain instantiation holds no guidance code.
+template <bool Guided>
+__global__ void __launch_bounds__(256) ode_rk4_stage_kernel(const float* sc, const float* y, float* xs, float* k_out, const float* v2,
+                                                            int n, int cfg_on, float cfg, int full, int tsel, float t_scale,
+                                                            float* tvec, int rows, Rk4Guide g) {
     const float t = sc[0], dt = sc[1];
     if (blockIdx.x == 0) {
-        const float tv = mul_(stage_t(t, dt, tsel), t_scale);
+        const float tv = next_stage_tv(t, dt, tsel, t_scale);
         for (int r = threadIdx.x; r < rows; r += 256) tvec[r] = tv;
     }
-    const GuideScalars g = guide_scalars(stage_t(t, dt, tcur), gsc[0], gsc[1]);
+    GuideScalars gs{};
+    if constexpr (Guided) gs = guide_scalars(stage_t(t, dt, g.tcur), g.gsc[0], g.gsc[1]);
     for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
-        const float4 k = guide_v4(load_v(v2, i, n, cfg_on, cfg), xin, ym, keep, q, i, g);
+        float4 k = load_v(v2, i, n, cfg_on, cfg);
+        if constexpr (Guided) k = guide_v4(k, g.xin, g.ym, g.keep, g.q, i, gs);
         *reinterpret_cast<float4*>(k_out + i) = k;
-        const float4 yv = *reinterpret_cast<const float4*>(y + i);
-        float4 o;
-        if (full) {   // y + dt*k3
-            o.x = add_(yv.x, mul_(dt, k.x)); o.y = add_(yv.y, mul_(dt, k.y));
-            o.z = add_(yv.z, mul_(dt, k.z)); o.w = add_(yv.w, mul_(dt, k.w));
-        } else {      // y + dt*k/2
-            o.x = add_(yv.x, mul_(dt, k.x) * 0.5f); o.y = add_(yv.y, mul_(dt, k.y) * 0.5f);
-            o.z = add_(yv.z, mul_(dt, k.z) * 0.5f); o.w = add_(yv.w, mul_(dt, k.w) * 0.5f);
-        }
-        *reinterpret_cast<float4*>(xs + i) = o;
+        *reinterpret_cast<float4*>(xs + i) = rk4_stage_state(*reinterpret_cast<const float4*>(y + i), k, dt, full);
     }
 }
 
-// ode_rk4_final_kernel with k4 corrected at (xs, t + dt)
-__global__ void __launch_bounds__(256) ode_rk4_gfinal_kernel(const float* sc, const float* gsc, float* y, const float* k1, const float* k2,
-                                                             const float* k3, const float* v2, const float* xin, const float* ym,
-                                                             const float* keep, const float* q, int n, int cfg_on, float cfg) {
+// The interval closed: y += (dt/6)(k1 + 2 k2 + 2 k3 + k4).  Guided: k4 corrected at (g.xin = xs, t + dt)
+template <bool Guided>
+__global__ void __launch_bounds__(256) ode_rk4_final_kernel(const float* sc, float* y, const float* k1, const float* k2, const float* k3,
+                                                            const float* v2, int n, int cfg_on, float cfg, Rk4Guide g) {
     const float dt6 = __fdiv_rn(sc[1], 6.0f);
-    const GuideScalars g = guide_scalars(stage_t(sc[0], sc[1], 2), gsc[0], gsc[1]);
+    GuideScalars gs{};
+    if constexpr (Guided) gs = guide_scalars(stage_t(sc[0], sc[1], 2), g.gsc[0], g.gsc[1]);
     for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
-        const float4 k4 = guide_v4(load_v(v2, i, n, cfg_on, cfg), xin, ym, keep, q, i, g);
+        float4 k4 = load_v(v2, i, n, cfg_on, cfg);
+        if constexpr (Guided) k4 = guide_v4(k4, g.xin, g.ym, g.keep, g.q, i, gs);
         const float4 a = *reinterpret_cast<const float4*>(k1 + i), b = *reinterpret_cast<const float4*>(k2 + i),
                      c = *reinterpret_cast<const float4*>(k3 + i);
-        float4 yv = *reinterpret_cast<float4*>(y + i);
-        yv.x = rk4_comb(yv.x, a.x, b.x, c.x, k4.x, dt6); yv.y = rk4_comb(yv.y, a.y, b.y, c.y, k4.y, dt6);
-        yv.z = rk4_comb(yv.z, a.z, b.z, c.z, k4.z, dt6); yv.w = rk4_comb(yv.w, a.w, b.w, c.w, k4.w, dt6);
-        *reinterpret_cast<float4*>(y + i) = yv;
+        *reinterpret_cast<float4*>(y + i) = rk4_comb4(*reinterpret_cast<float4*>(y + i), a, b, c, k4, dt6);
     }
 }
 
@@ -261,21 +228,21 @@ __global__ void __launch_bounds__(256) ode_guided_correct_kernel(const float* v,
         *reinterpret_cast<float4*>(out + i) = guide_v4(*reinterpret_cast<const float4*>(v + i), x, ym, keep, nullptr, i, g);
 }
 
-int ode_rk4_gstage_launch(const float* sc, const float* gsc, const float* y, float* xs, float* k_out, const float* v2, const float* xin,
-                          const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg, int full, int tcur, int tsel,
-                          float t_scale, float* tvec, int rows, hipStream_t s) {
+int ode_rk4_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v2, int n, int cfg_on, float cfg, int full,
+                         int tsel, float t_scale, float* tvec, int rows, const Rk4Guide* g, hipStream_t s) {
     if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
-    if (tcur < 0 || tcur > 2) return fail(FC_E_ARG, "ode: stage time selector must lie in [0, 2]");
-    hipLaunchKernelGGL(ode_rk4_gstage_kernel, dim3(egrid(n)), dim3(256), 0, s, sc, gsc, y, xs, k_out, v2, xin, ym, keep, q, n, cfg_on, cfg,
-                       full, tcur, tsel, t_scale, tvec, rows);
+    if (g && (g->tcur < 0 || g->tcur > 2)) return fail(FC_E_ARG, "ode: stage time selector must lie in [0, 2]");
+    if (tsel < 1 || tsel > 2) return fail(FC_E_ARG, "ode: the next stage's time selector must lie in [1, 2]");
+    hipLaunchKernelGGL(g ? ode_rk4_stage_kernel<true> : ode_rk4_stage_kernel<false>, dim3(egrid(n)), dim3(256), 0, s, sc, y, xs, k_out, v2,
+                       n, cfg_on, cfg, full, tsel, t_scale, tvec, rows, g ? *g : Rk4Guide{});
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
-int ode_rk4_gfinal_launch(const float* sc, const float* gsc, float* y, const float* k1, const float* k2, const float* k3, const float* v2,
-                          const float* xin, const float* ym, const float* keep, const float* q, int n, int cfg_on, float cfg,
-                          hipStream_t s) {
+int ode_rk4_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v2, int n, int cfg_on,
+                         float cfg, const Rk4Guide* g, hipStream_t s) {
     if (n & 3) return fail(FC_E_SHAPE, "ode: element count must be a multiple of 4");
-    hipLaunchKernelGGL(ode_rk4_gfinal_kernel, dim3(egrid(n)), dim3(256), 0, s, sc, gsc, y, k1, k2, k3, v2, xin, ym, keep, q, n, cfg_on, cfg);
+    hipLaunchKernelGGL(g ? ode_rk4_final_kernel<true> : ode_rk4_final_kernel<false>, dim3(egrid(n)), dim3(256), 0, s, sc, y, k1, k2, k3, v2,
+                       n, cfg_on, cfg, g ? *g : Rk4Guide{});
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -849,8 +816,8 @@ int rk45_out_launch(const double* y, float* x, int n, hipStream_t s) {
 //
 // One workgroup per sample: each thread's fp64 products are summed in index order, the 256 thread sums by block_sum's fixed tree, so
 // d_j[b] depends on neither the batch size nor the scheduling, and no partial sums cross a launch.  (A sample is C*H*W <= a few 10^4
-// floats, three streams of it per stage: the launches are latency-sized either way.)  The state arithmetic is that of
-// ode_rk4_stage_kernel / ode_rk4_final_kernel, operation for operation.
+// floats, three streams of it per stage: the launches are latency-sized either way.)  That partition is why these are kernels of their
+// own; the state arithmetic is ode_rk4_stage_kernel's / ode_rk4_final_kernel's by construction (rk4_stage_state, rk4_comb4, next_stage_tv).
 
 // sum_i eps[base + i] g[base + i] over one sample, fp64 products and sums; the same value in every thread
 __device__ __forceinline__ double probe_dot_acc(double s, const float4 e, const float4 q) {
@@ -865,25 +832,13 @@ __global__ void __launch_bounds__(256) ode_ll_stage_kernel(const float* sc, cons
     __shared__ double red[256];
     const int b = blockIdx.x, base = b * m;
     const float t = sc[0], dt = sc[1];
-    if (threadIdx.x == 0) {
-        const float tn = tsel == 1 ? add_(t, dt * 0.5f) : add_(t, dt);     // t + dt/2 | t + dt
-        tvec[b] = mul_(tn, t_scale);
-    }
+    if (threadIdx.x == 0) tvec[b] = next_stage_tv(t, dt, tsel, t_scale);
     double d = 0.0;
     for (int j = 4 * threadIdx.x; j < m; j += 4 * 256) {
         const int i = base + j;
         const float4 k = *reinterpret_cast<const float4*>(v + i);
         *reinterpret_cast<float4*>(k_out + i) = k;
-        const float4 yv = *reinterpret_cast<const float4*>(y + i);
-        float4 o;
-        if (full) {   // y + dt*k3
-            o.x = add_(yv.x, mul_(dt, k.x)); o.y = add_(yv.y, mul_(dt, k.y));
-            o.z = add_(yv.z, mul_(dt, k.z)); o.w = add_(yv.w, mul_(dt, k.w));
-        } else {      // y + dt*k/2
-            o.x = add_(yv.x, mul_(dt, k.x) * 0.5f); o.y = add_(yv.y, mul_(dt, k.y) * 0.5f);
-            o.z = add_(yv.z, mul_(dt, k.z) * 0.5f); o.w = add_(yv.w, mul_(dt, k.w) * 0.5f);
-        }
-        *reinterpret_cast<float4*>(xs + i) = o;
+        *reinterpret_cast<float4*>(xs + i) = rk4_stage_state(*reinterpret_cast<const float4*>(y + i), k, dt, full);
         d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + i), *reinterpret_cast<const float4*>(g + i));
     }
     const double r = block_sum(d, red);
@@ -902,10 +857,7 @@ __global__ void __launch_bounds__(256) ode_ll_final_kernel(const float* sc, floa
         const float4 k4 = *reinterpret_cast<const float4*>(v + i);
         const float4 p = *reinterpret_cast<const float4*>(k1 + i), q = *reinterpret_cast<const float4*>(k2 + i),
                      c = *reinterpret_cast<const float4*>(k3 + i);
-        float4 yv = *reinterpret_cast<float4*>(y + i);
-        yv.x = rk4_comb(yv.x, p.x, q.x, c.x, k4.x, dt6); yv.y = rk4_comb(yv.y, p.y, q.y, c.y, k4.y, dt6);
-        yv.z = rk4_comb(yv.z, p.z, q.z, c.z, k4.z, dt6); yv.w = rk4_comb(yv.w, p.w, q.w, c.w, k4.w, dt6);
-        *reinterpret_cast<float4*>(y + i) = yv;
+        *reinterpret_cast<float4*>(y + i) = rk4_comb4(*reinterpret_cast<float4*>(y + i), p, q, c, k4, dt6);
         d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + i), *reinterpret_cast<const float4*>(g + i));
     }
     const double d4 = block_sum(d, red);
@@ -945,6 +897,7 @@ int ode_ll_stage_launch(const float* sc, const float* y, float* xs, float* k_out
                         double* dst, int slot, int B, int m, int full, int tsel, float t_scale, float* tvec, hipStream_t s) {
     FC_TRY(ll_shape_ok(B, m));
     if (slot < 0 || slot > 2) return fail(FC_E_ARG, "ode: stage slot must lie in [0, 2]");
+    if (tsel < 1 || tsel > 2) return fail(FC_E_ARG, "ode: the next stage's time selector must lie in [1, 2]");
     hipLaunchKernelGGL(ode_ll_stage_kernel, dim3(B), dim3(256), 0, s, sc, y, xs, k_out, v, g, eps, dst, slot, m, full, tsel, t_scale, tvec);
     FC_HIP(hipGetLastError());
     return FC_OK;

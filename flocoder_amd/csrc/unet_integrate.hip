@@ -1,6 +1,8 @@
-// The integrators of the velocity U-Net: fixed-grid Euler / RK4 (fc_unet_integrate), likelihood / inversion on the RK4 grid
-// (fc_unet_log_likelihood) and adaptive RK45 (fc_unet_integrate_rk45*).  Host code only: the kernels are ode.hip's, the forward is the
-// handle's launch plan (unet.hip).  Every call runs on the library's own stream inside one CallFrame; its state is fc_unet::ig.
+// The integrators of the velocity U-Net: fixed-grid Euler / RK4 (fc_unet_integrate), likelihood / inversion (fc_unet_log_likelihood) and
+// measurement guidance (fc_unet_integrate_guided) on the RK4 grid, the stochastic sampler (fc_unet_integrate_sde) and adaptive RK45
+// (fc_unet_integrate_rk45*).  Host code only: the kernels are ode.hip's, the forward is the handle's launch plan (unet.hip).  Every call
+// runs on the library's own stream inside one CallFrame; its state is fc_unet::ig.  Every RK4 integrator enqueues its intervals through
+// enqueue_rk4_interval, the one place that holds rk4_step's launch sequence and stage constants.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -50,7 +52,8 @@ int alloc_integrator(fc_unet* u, int rows, int H, int W) {
 // touched yet.  enter() moves the call onto the library stream: the hand-over from the caller's stream, the call's class ids and mask
 // copied into the library's own buffers, the meeting guard.  leave() hands back; a call that returns early after enter() leaves through
 // the destructor, so the caller's stream is ordered behind whatever the library stream still holds and the meeting guard knows this
-// handle's last plan -- whichever FC_TRY failed.
+// handle's last plan -- whichever FC_TRY failed.  A fixed-grid entry point reads: checks, begin, own allocations, enter, prologue, own
+// staging, intervals, finish.
 struct CallFrame {
     fc_unet* u = nullptr;
     hipStream_t caller = nullptr, s = nullptr;
@@ -89,6 +92,11 @@ struct CallFrame {
         FC_HIP(hipStreamWaitEvent(caller, u->ig.ev_out, 0));
         return FC_OK;
     }
+    // the tail of every fixed-grid call: the state back into the caller's tensor, then leave()
+    int finish(float* x_dev) {
+        FC_HIP(hipMemcpyAsync(x_dev, u->ig.y, nbytes, hipMemcpyDeviceToDevice, s));
+        return leave();
+    }
     ~CallFrame() {
         if (!entered) return;
         const std::string first = fc_last_error();   // the error that ended the call stays the one reported
@@ -102,6 +110,12 @@ extern "C" {
 
 // ------------------------------------------------------------------------------------------- graph cache
 static uint32_t fbits(float f) { uint32_t v; std::memcpy(&v, &f, 4); return v; }
+
+// the kernels read and write these as float4 (NULL passes); `msg`: the entry point's own text
+static int check_aligned16(std::initializer_list<const void*> ptrs, const char* msg) {
+    for (const void* p : ptrs) if (reinterpret_cast<uintptr_t>(p) & 15) return fail(FC_E_ARG, msg);
+    return FC_OK;
+}
 
 // FLOCODER_AMD_NO_GRAPH: every integrator enqueues its launches directly instead of capturing and replaying graphs
 static bool no_graph() {
@@ -161,7 +175,52 @@ static FwdCtx step_ctx(const CallFrame& f, bool pre_on) {
     return c;
 }
 
-// enqueue one integration step on `s` (captured into a graph by the caller)
+// ---- the RK4 interval -----------------------------------------------------------------------------------------------------------------
+// rk4_step (sampling.py:36-48) as every RK4 integrator enqueues it, captured or direct: the interval's time (ode_time_launch), then four
+// evaluations, each a forward, what the variant puts behind it, and the kernel that closes the stage -- it stores k and hands the next
+// evaluation its state and time -- or, behind the fourth, the interval.  The integrators differ in the variant alone.
+struct Rk4Variant {
+    enum Eval { Forward, ForwardVjp, ForwardGuideWVjp };   // a forward | + vjp_run | + ode_guide_w_launch at the stage's time + vjp_run
+    enum Close { Plain, Guided, Likelihood };              // the kernels of ode.hip that close a stage and the interval
+    Eval eval;
+    Close close;
+    int trows;                                             // rows of the time vector: f.rows, or B where there is no guidance pair
+    FwdCtx c;                                              // the forward (and, with vjp_run, the chain's d_out / dx_out)
+    const float* q = nullptr;                              // Guided: (dv/dx)^T w of the same forward (exact form), or NULL
+    const float* probe = nullptr;                          // Likelihood: eps ...
+    double* a = nullptr;                                   // ... and the accumulator the interval adds to
+};
+
+static int enqueue_rk4_interval(const CallFrame& f, const Rk4Variant& v, float cfg, float t_scale) {
+    fc_unet* u = f.u;
+    const IntegratorState& ig = u->ig;
+    const int n = f.n, m = f.n / f.B, cf = f.cfg_on ? 1 : 0;
+    hipStream_t s = f.s;
+    // stage j closes evaluation j at time `tcur` (0: t, 1: t + dt/2, 2: t + dt): k_out = its velocity, the next state y + dt*k (full) or
+    // y + dt*k/2, the next time `tsel`.  The fourth evaluation closes the interval.
+    const struct { float* k_out; int full, tcur, tsel; } stages[4] = {{ig.k1, 0, 0, 1}, {ig.k2, 0, 1, 1}, {ig.k3, 1, 1, 2}, {nullptr, 0, 2, 0}};
+    FwdCtx c = v.c;
+    FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, v.trows, s));
+    for (int j = 0; j < 4; ++j) {
+        const auto& st = stages[j];
+        const float* x = c.x = j == 0 ? ig.y : ig.xs;      // k1 = f(y, t); k2, k3, k4 at the state the stage before wrote
+        FC_TRY(run_plan(u->plan, c, s));
+        if (v.eval == Rk4Variant::ForwardGuideWVjp) FC_TRY(ode_guide_w_launch(ig.sc, ig.g_sc, ig.v2, x, ig.g_y, ig.g_keep, ig.g_w, n, st.tcur, s));
+        if (v.eval != Rk4Variant::Forward) FC_TRY(vjp_run(u, c, s));
+        if (v.close == Rk4Variant::Likelihood) {
+            FC_TRY(j < 3 ? ode_ll_stage_launch(ig.sc, ig.y, ig.xs, st.k_out, ig.v2, ig.ll_g, v.probe, ig.ll_d, j, f.B, m, st.full, st.tsel, t_scale, ig.tvec, s)
+                         : ode_ll_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.ll_g, v.probe, ig.ll_d, v.a, f.B, m, s));
+            continue;
+        }
+        const Rk4Guide guide{ig.g_sc, x, ig.g_y, ig.g_keep, v.q, st.tcur};
+        const Rk4Guide* g = v.close == Rk4Variant::Guided ? &guide : nullptr;
+        FC_TRY(j < 3 ? ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, st.k_out, ig.v2, n, cf, cfg, st.full, st.tsel, t_scale, ig.tvec, v.trows, g, s)
+                     : ode_rk4_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, n, cf, cfg, g, s));
+    }
+    return FC_OK;
+}
+
+// enqueue one step of fc_unet_integrate on `s` (captured into a graph by the caller)
 // Legacy Euler without CFG: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
 static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_EULER && !cfg_on; }
 
@@ -172,28 +231,17 @@ static int enqueue_step(const CallFrame& f, int method, float cfg, float dt_eule
     const int rows = f.rows, n = f.n;
     hipStream_t s = f.s;
     FwdCtx c = step_ctx(f, pre_on);
+    if (method == FC_METHOD_RK4) return enqueue_rk4_interval(f, {Rk4Variant::Forward, Rk4Variant::Plain, rows, c}, cfg, t_scale);
     if (euler_tail_ok(method, cfg_on)) {   // the update and the next interval's time ride in final_conv: no launches around the plan
         c.x = ig.y;
         c.euler.y = ig.y; c.euler.dt = dt_euler; c.euler.step = ig.step; c.euler.ts = ig.ts_dev; c.euler.t_scale = t_scale;
         c.euler.sc = ig.sc; c.euler.tvec = ig.tvec; c.euler.rows = rows;
         return run_plan(u->plan, c, s);
     }
-    FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, method == FC_METHOD_RK4, ig.sc, ig.tvec, rows, s));
-    if (method == FC_METHOD_EULER) {
-        c.x = ig.y;
-        FC_TRY(run_plan(u->plan, c, s));
-        return ode_euler_update_launch(ig.y, ig.v2, n, cfg_on, cfg, dt_euler, s);
-    }
+    FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 0, ig.sc, ig.tvec, rows, s));
     c.x = ig.y;
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k1 = f(y, t)
-    FC_TRY(ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, ig.k1, ig.v2, n, cfg_on, cfg, 0, 1, t_scale, ig.tvec, rows, s));      // y + dt*k1/2, t+dt/2
-    c.x = ig.xs;
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k2
-    FC_TRY(ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, ig.k2, ig.v2, n, cfg_on, cfg, 0, 1, t_scale, ig.tvec, rows, s));      // y + dt*k2/2, t+dt/2
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k3
-    FC_TRY(ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, ig.k3, ig.v2, n, cfg_on, cfg, 1, 2, t_scale, ig.tvec, rows, s));      // y + dt*k3, t+dt
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k4
-    return ode_rk4_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, n, cfg_on, cfg, s);
+    FC_TRY(run_plan(u->plan, c, s));
+    return ode_euler_update_launch(ig.y, ig.v2, n, cfg_on, cfg, dt_euler, s);
 }
 
 // What a fixed-grid call puts behind its frame's hand-over (fc_unet_integrate, fc_unet_log_likelihood): the time grid's device buffer
@@ -329,8 +377,7 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
     key.pre_on = pre_on; key.dt_euler = fbits(dt_euler);
     FC_TRY(replay_steps(f, key, n_steps, method == FC_METHOD_RK4 ? 4 : 1,
                         [&] { return enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on); }));
-    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
-    return f.leave();
+    return f.finish(x_dev);
 }
 
 // ---- likelihood / inversion on the RK4 grid ------------------------------------------------------------------------------------------
@@ -344,48 +391,30 @@ int fc_unet_log_likelihood(fc_unet* u, float* x_dev, int B, int H, int W, const 
                            double* logp_out_dev, void* stream) {
     if (!u || !x_dev || !ts_host || !probe_dev || !a_out_dev || !logp_out_dev || B < 1) return fail(FC_E_ARG, "fc_unet_log_likelihood: null argument");
     if (n_points < 2) return fail(FC_E_ARG, "fc_unet_log_likelihood: the time grid needs at least two points");
-    if (reinterpret_cast<uintptr_t>(probe_dev) & 15) return fail(FC_E_ARG, "fc_unet_log_likelihood: probe_dev must be 16-byte aligned (the kernels read it as float4)");
+    FC_TRY(check_aligned16({probe_dev}, "fc_unet_log_likelihood: probe_dev must be 16-byte aligned (the kernels read it as float4)"));
     CallFrame f;
     FC_TRY(f.begin(u, B, H, W, ids, 0.0f, mask, mask_is_ones, stream));      // no guidance
     if (!u->keep_all) return fail(FC_E_STATE, "fc_unet_log_likelihood: no backward plan for this shape; call fc_unet_train_reserve");
     FC_TRY(vjp_check(u, B, H, W, "fc_unet_log_likelihood"));
     IntegratorState& ig = u->ig;
     const int m = u->cfg.channels * H * W;
-    hipStream_t s = f.s;
     if (!ig.ll_g) {
         FC_TRY(ig.get(&ig.ll_d, (size_t)u->maxB * 3, "integrator.likelihood"));
         FC_TRY(ig.get(&ig.ll_g, (size_t)u->maxB * m, "integrator.likelihood"));
     }
     FC_TRY(f.enter());
     FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
-    FC_HIP(hipMemsetAsync(a_out_dev, 0, (size_t)B * sizeof(double), s));
-    FwdCtx c = integrator_ctx(f);
-    c.d_out = probe_dev; c.dx_out = ig.ll_g;
-    auto eval = [&](const float* x) -> int {      // v2 = v(x, tvec), ll_g = (dv/dx)^T probe
-        c.x = x;
-        FC_TRY(run_plan(u->plan, c, s));
-        return vjp_run(u, c, s);
-    };
-    for (int i = 0; i + 1 < n_points; ++i) {
-        FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, B, s));
-        FC_TRY(eval(ig.y));                                                                                                              // k1, g1
-        FC_TRY(ode_ll_stage_launch(ig.sc, ig.y, ig.xs, ig.k1, ig.v2, ig.ll_g, probe_dev, ig.ll_d, 0, B, m, 0, 1, t_scale, ig.tvec, s));  // y + dt*k1/2, t+dt/2
-        FC_TRY(eval(ig.xs));                                                                                                             // k2, g2
-        FC_TRY(ode_ll_stage_launch(ig.sc, ig.y, ig.xs, ig.k2, ig.v2, ig.ll_g, probe_dev, ig.ll_d, 1, B, m, 0, 1, t_scale, ig.tvec, s));  // y + dt*k2/2, t+dt/2
-        FC_TRY(eval(ig.xs));                                                                                                             // k3, g3
-        FC_TRY(ode_ll_stage_launch(ig.sc, ig.y, ig.xs, ig.k3, ig.v2, ig.ll_g, probe_dev, ig.ll_d, 2, B, m, 1, 2, t_scale, ig.tvec, s));  // y + dt*k3, t+dt
-        FC_TRY(eval(ig.xs));                                                                                                             // k4, g4
-        FC_TRY(ode_ll_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.ll_g, probe_dev, ig.ll_d, a_out_dev, B, m, s));
-    }
-    FC_TRY(ode_ll_logp_launch(ig.y, a_out_dev, logp_out_dev, B, m, s));
-    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
-    return f.leave();
+    FC_HIP(hipMemsetAsync(a_out_dev, 0, (size_t)B * sizeof(double), f.s));
+    Rk4Variant v{Rk4Variant::ForwardVjp, Rk4Variant::Likelihood, B, integrator_ctx(f)};   // v2 = v(x, tvec), ll_g = (dv/dx)^T probe
+    v.c.d_out = v.probe = probe_dev; v.c.dx_out = ig.ll_g; v.a = a_out_dev;
+    for (int i = 0; i + 1 < n_points; ++i) FC_TRY(enqueue_rk4_interval(f, v, 0.0f, t_scale));
+    FC_TRY(ode_ll_logp_launch(ig.y, a_out_dev, logp_out_dev, B, m, f.s));
+    return f.finish(x_dev);
 }
 
 int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_dev, int batch, int64_t per_sample, void* stream) {
     if (!probe_dev || !g_dev || !out_dev) return fail(FC_E_ARG, "fc_debug_probe_dot: null argument");
-    if ((reinterpret_cast<uintptr_t>(probe_dev) | reinterpret_cast<uintptr_t>(g_dev)) & 15)
-        return fail(FC_E_ARG, "fc_debug_probe_dot: inputs must be 16-byte aligned (read as float4)");
+    FC_TRY(check_aligned16({probe_dev, g_dev}, "fc_debug_probe_dot: inputs must be 16-byte aligned (read as float4)"));
     if (per_sample < 1 || per_sample > 0x7fffffff) return fail(FC_E_SHAPE, "fc_debug_probe_dot: bad element count");
     return ode_ll_dot_launch(probe_dev, g_dev, out_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
 }
@@ -413,29 +442,6 @@ static int alloc_guided(fc_unet* u, bool exact) {
     return FC_OK;
 }
 
-// one interval, identity form (captured): enqueue_step's RK4 branch with the guided stage kernels
-static int enqueue_guided_step(const CallFrame& f, float cfg, float t_scale, bool pre_on) {
-    fc_unet* u = f.u;
-    const IntegratorState& ig = u->ig;
-    const int rows = f.rows, n = f.n, cf = f.cfg_on ? 1 : 0;
-    hipStream_t s = f.s;
-    FwdCtx c = step_ctx(f, pre_on);
-    FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, rows, s));
-    c.x = ig.y;
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k1 at (y, t)
-    FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k1, ig.v2, ig.y, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, 0, 0, 1, t_scale,
-                                 ig.tvec, rows, s));
-    c.x = ig.xs;
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k2 at (xs, t+dt/2)
-    FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k2, ig.v2, ig.xs, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, 0, 1, 1, t_scale,
-                                 ig.tvec, rows, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k3 at (xs, t+dt/2)
-    FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, 1, 1, 2, t_scale,
-                                 ig.tvec, rows, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                                     // k4 at (xs, t+dt)
-    return ode_rk4_gfinal_launch(ig.sc, ig.g_sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, nullptr, n, cf, cfg, s);
-}
-
 int fc_unet_integrate_guided(fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
                              const int64_t* ids, float cfg_strength, const float* mask, int mask_is_ones, const float* y_meas,
                              const float* keep, float sigma_y, float gamma, int jacobian, void* stream) {
@@ -446,8 +452,7 @@ int fc_unet_integrate_guided(fc_unet* u, float* x_dev, int B, int H, int W, cons
         if (!(ts_host[i] > 0.0f)) return fail(FC_E_ARG, "fc_unet_integrate_guided: every grid point must be > 0 (the correction is gamma (1-t)/t g)");
     if (!(sigma_y >= 0.0f)) return fail(FC_E_ARG, "fc_unet_integrate_guided: sigma_y must be >= 0");
     if (!std::isfinite(gamma)) return fail(FC_E_ARG, "fc_unet_integrate_guided: gamma must be finite");
-    if ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(y_meas) | reinterpret_cast<uintptr_t>(keep)) & 15)
-        return fail(FC_E_ARG, "fc_unet_integrate_guided: x, measurement and keep must be 16-byte aligned (the kernels read them as float4)");
+    FC_TRY(check_aligned16({x_dev, y_meas, keep}, "fc_unet_integrate_guided: x, measurement and keep must be 16-byte aligned (the kernels read them as float4)"));
     const bool exact = jacobian == FC_JACOBIAN_EXACT;
     CallFrame f;
     FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
@@ -460,7 +465,7 @@ int fc_unet_integrate_guided(fc_unet* u, float* x_dev, int B, int H, int W, cons
     }
     IntegratorState& ig = u->ig;
     FC_TRY(alloc_guided(u, exact));
-    const int n = f.n, n_steps = n_points - 1;
+    const int n_steps = n_points - 1;
     hipStream_t s = f.s;
     FC_TRY(f.enter());
     FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
@@ -468,48 +473,27 @@ int fc_unet_integrate_guided(fc_unet* u, float* x_dev, int B, int H, int W, cons
     FC_HIP(hipMemcpyAsync(ig.g_keep, keep, f.nbytes, hipMemcpyDeviceToDevice, s));
     const float gsc[4] = {(float)((double)sigma_y * (double)sigma_y), gamma, 0.f, 0.f};
     FC_HIP(hipMemcpyAsync(ig.g_sc, gsc, sizeof(gsc), hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns
-    if (!exact) {
+    if (!exact) {   // fc_unet_integrate's captured RK4 interval with the guided stage kernels
         bool pre_on = false;
         FC_TRY(cond_table(f, FC_METHOD_RK4, n_steps, t_scale, &pre_on));
         GraphKey key = graph_key(f, GraphKey::Rk4Guided, cfg_strength, t_scale);
         key.pre_on = pre_on;
-        FC_TRY(replay_steps(f, key, n_steps, 4, [&] { return enqueue_guided_step(f, cfg_strength, t_scale, pre_on); }));
+        const Rk4Variant v{Rk4Variant::Forward, Rk4Variant::Guided, f.rows, step_ctx(f, pre_on)};
+        FC_TRY(replay_steps(f, key, n_steps, 4, [&] { return enqueue_rk4_interval(f, v, cfg_strength, t_scale); }));
     } else {
         // the likelihood's structure: every evaluation a training-form forward, w, the data-gradient chain with w as output cotangent,
         // then the stage kernel with q = (dv/dx)^T w; direct launches, nothing decided on the host
-        FwdCtx c = integrator_ctx(f);
-        c.d_out = ig.g_w; c.dx_out = ig.g_q;
-        auto eval = [&](const float* x, int tcur) -> int {
-            c.x = x;
-            FC_TRY(run_plan(u->plan, c, s));
-            FC_TRY(ode_guide_w_launch(ig.sc, ig.g_sc, ig.v2, x, ig.g_y, ig.g_keep, ig.g_w, n, tcur, s));
-            return vjp_run(u, c, s);
-        };
-        for (int i = 0; i < n_steps; ++i) {
-            FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 1, ig.sc, ig.tvec, B, s));
-            FC_TRY(eval(ig.y, 0));
-            FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k1, ig.v2, ig.y, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, 0, 0, 1, t_scale,
-                                         ig.tvec, B, s));
-            FC_TRY(eval(ig.xs, 1));
-            FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k2, ig.v2, ig.xs, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, 0, 1, 1, t_scale,
-                                         ig.tvec, B, s));
-            FC_TRY(eval(ig.xs, 1));
-            FC_TRY(ode_rk4_gstage_launch(ig.sc, ig.g_sc, ig.y, ig.xs, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, 1, 1, 2, t_scale,
-                                         ig.tvec, B, s));
-            FC_TRY(eval(ig.xs, 2));
-            FC_TRY(ode_rk4_gfinal_launch(ig.sc, ig.g_sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.xs, ig.g_y, ig.g_keep, ig.g_q, n, 0, 0.f, s));
-        }
+        Rk4Variant v{Rk4Variant::ForwardGuideWVjp, Rk4Variant::Guided, B, integrator_ctx(f)};
+        v.c.d_out = ig.g_w; v.q = v.c.dx_out = ig.g_q;
+        for (int i = 0; i < n_steps; ++i) FC_TRY(enqueue_rk4_interval(f, v, 0.0f, t_scale));
     }
-    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
-    return f.leave();
+    return f.finish(x_dev);
 }
 
 int fc_ode_guided_correct(const float* v_dev, const float* x_dev, const float* y_dev, const float* a_dev, int64_t n, float t, float sigma_y,
                           float gamma, float* out_dev, void* stream) {
     if (!v_dev || !x_dev || !y_dev || !a_dev || !out_dev) return fail(FC_E_ARG, "fc_ode_guided_correct: null argument");
-    if ((reinterpret_cast<uintptr_t>(v_dev) | reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(y_dev) |
-         reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15)
-        return fail(FC_E_ARG, "fc_ode_guided_correct: tensors must be 16-byte aligned (read as float4)");
+    FC_TRY(check_aligned16({v_dev, x_dev, y_dev, a_dev, out_dev}, "fc_ode_guided_correct: tensors must be 16-byte aligned (read as float4)"));
     if (!(t > 0.0f)) return fail(FC_E_ARG, "fc_ode_guided_correct: t must be > 0");
     if (!(sigma_y >= 0.0f)) return fail(FC_E_ARG, "fc_ode_guided_correct: sigma_y must be >= 0");
     if (n < 1 || n > 0x7fffffff) return fail(FC_E_SHAPE, "fc_ode_guided_correct: bad element count");
@@ -568,8 +552,7 @@ int fc_unet_integrate_sde(fc_unet* u, int scheme, float* x_dev, int B, int H, in
         if (!(ts_host[i] >= 0.0f && ts_host[i] <= 1.0f) || (i > 0 && ts_host[i] < ts_host[i - 1]))
             return fail(FC_E_ARG, "fc_unet_integrate_sde: the grid must be non-decreasing within [0, 1] (the diffusion is sigma sqrt(1-t))");
     if (!(sigma >= 0.0f) || !std::isfinite(sigma)) return fail(FC_E_ARG, "fc_unet_integrate_sde: sigma must be finite and >= 0");
-    if ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(noise)) & 15)
-        return fail(FC_E_ARG, "fc_unet_integrate_sde: x and the noise must be 16-byte aligned (the kernels read them as float4)");
+    FC_TRY(check_aligned16({x_dev, noise}, "fc_unet_integrate_sde: x and the noise must be 16-byte aligned (the kernels read them as float4)"));
     CallFrame f;
     FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
     IntegratorState& ig = u->ig;
@@ -588,14 +571,13 @@ int fc_unet_integrate_sde(fc_unet* u, int scheme, float* x_dev, int B, int H, in
     key.pre_on = pre_on; key.sde_scheme = scheme; key.sde_noise = use_noise; key.sde_sigma = fbits(sigma);
     FC_TRY(replay_steps(f, key, n_steps, heun ? 2 : 1,
                         [&] { return enqueue_sde_step(f, scheme, cfg_strength, sigma, use_noise, t_scale, pre_on); }));
-    FC_HIP(hipMemcpyAsync(x_dev, ig.y, f.nbytes, hipMemcpyDeviceToDevice, s));
-    return f.leave();
+    return f.finish(x_dev);
 }
 
 int fc_ode_normal_field(float* out_dev, uint64_t seed, int64_t draw_index, const int64_t* sample_ids_dev, int batch, int64_t per_sample,
                         void* stream) {
     if (!out_dev) return fail(FC_E_ARG, "fc_ode_normal_field: null argument");
-    if (reinterpret_cast<uintptr_t>(out_dev) & 15) return fail(FC_E_ARG, "fc_ode_normal_field: out must be 16-byte aligned (written as float4)");
+    FC_TRY(check_aligned16({out_dev}, "fc_ode_normal_field: out must be 16-byte aligned (written as float4)"));
     if (draw_index < 0 || draw_index > 0xffffffffLL) return fail(FC_E_ARG, "fc_ode_normal_field: the draw index is a 32-bit counter word");
     if (batch < 1 || per_sample < 4 || (per_sample & 3) || (long long)batch * per_sample > 0x7fffffffLL)
         return fail(FC_E_SHAPE, "fc_ode_normal_field: elements per sample must be a positive multiple of 4, batch * per_sample < 2^31");

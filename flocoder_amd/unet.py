@@ -8,6 +8,7 @@ with CPU tensors raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Dict, List, Optional, Tuple
@@ -429,6 +430,35 @@ class Unet(NativeModule):
         if check and B.lib().fc_unet_meeting_launches(hnd) > 0:
             B.check(B.lib().fc_unet_check(hnd, B.current_stream(dev), 1))
 
+    @staticmethod
+    def _host_grid(ts: torch.Tensor, min_points: int = 0):
+        """``ts`` as the library reads it -> ``(host fp32 tensor, its ctypes pointer, number of points)``; the tensor owns the memory."""
+        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
+        if ts_host.numel() < min_points:
+            raise ValueError(f"the time grid needs at least {'two' if min_points == 2 else min_points} points")
+        return ts_host, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)), ts_host.numel()
+
+    @staticmethod
+    def _check_aligned(x: torch.Tensor) -> None:
+        if x.data_ptr() % 16:
+            raise ValueError("x must be 16-byte aligned (the kernels read it as float4)")
+
+    @contextlib.contextmanager
+    def _training_form(self, hnd, bsz: int, h: int, w: int, restore: bool):
+        """The body runs with the plans in the training form (every intermediate kept, none of the fused inference launches), which
+        ``fc_unet_train_reserve`` switches a handle to for good.  With ``restore``, a model that was NOT in that form -- one that trains is
+        left as it is -- gets its inference plans and the reservation it had back behind the body."""
+        lib = B.lib()
+        was_training_form = bool(lib.fc_unet_train_form(hnd))
+        rows0, h0, w0 = C.c_int(0), C.c_int(0), C.c_int(0)
+        B.check(lib.fc_unet_reserved(hnd, C.byref(rows0), C.byref(h0), C.byref(w0)))
+        B.check(lib.fc_unet_train_reserve(hnd, bsz, h, w))
+        yield
+        if restore and not was_training_form:
+            self.release_training_plan()
+            if rows0.value > 0:                         # the reservation the caller had, in the form it had
+                B.check(lib.fc_unet_reserve(hnd, rows0.value, h0.value, w0.value))
+
     def integrate(self, method: str, x: torch.Tensor, ts: torch.Tensor, *, dt_euler: float = 0.0, t_scale: float = 999.0,
                   class_ids: Optional[torch.Tensor] = None, cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None,
                   mask_is_ones: bool = False, check: bool = True) -> torch.Tensor:
@@ -441,9 +471,8 @@ class Unet(NativeModule):
         dev = x.device
         bsz, _, h, w = x.shape
         B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
-        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
-        B.check(B.lib().fc_unet_integrate(hnd, code, B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)),
-                                          ts_host.numel(), float(dt_euler), float(t_scale), B.ptr(class_ids),
+        _, ts_ptr, n_points = self._host_grid(ts)
+        B.check(B.lib().fc_unet_integrate(hnd, code, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(dt_euler), float(t_scale), B.ptr(class_ids),
                                           float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), B.current_stream(dev)))
         self._integrator_check(hnd, dev, check)
         return x
@@ -456,12 +485,10 @@ class Unet(NativeModule):
         ``[B]`` on x's device: the integrated divergence and ``-|z|^2/2 - (CHW/2) ln 2pi + a`` with ``z`` = the ``x`` left behind.  Argument
         checks and ``check`` as in ``integrate``; no guidance.
 
-        The loop needs the backward plan, and ``fc_unet_train_reserve`` switches a handle to the training form of its plans (every
-        intermediate kept, none of the fused inference launches) for good.  A model that was NOT in that form when the call came gets its
-        inference form back before the call returns (``restore_plan``, default): later sampler calls run the plan, and give the bits,
-        of a model that never computed a likelihood.  That costs a device synchronisation and two plan builds per call; a caller who makes
-        many likelihood calls in a row passes ``restore_plan=False`` and calls ``release_training_plan()`` once at the end.  A model
-        that trains (it already is in the training form) is left as it is."""
+        The loop needs the backward plan, hence the training form of the plans (``_training_form``).  A model that was NOT in that form
+        gets its inference form back before the call returns (``restore_plan``, default): later sampler calls run the plan, and give the
+        bits, of a model that never computed a likelihood, at the cost of a device synchronisation and two plan builds per call.  For many
+        likelihood calls in a row pass ``restore_plan=False`` and call ``release_training_plan()`` once at the end."""
         class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask, cpu_error=_GPU_ONLY + "; there is no CPU path")
         dev = x.device
         bsz, _, h, w = x.shape
@@ -469,24 +496,12 @@ class Unet(NativeModule):
             raise ValueError("probe must be a contiguous fp32 tensor of x's shape on x's device")
         if probe.data_ptr() % 16:
             probe = probe.clone()                       # a view at an odd storage offset: the kernels read the probe as float4
-        if ts.numel() < 2:
-            raise ValueError("the time grid needs at least two points")
-        lib = B.lib()
-        was_training_form = bool(lib.fc_unet_train_form(hnd))
-        rows0, h0, w0 = C.c_int(0), C.c_int(0), C.c_int(0)
-        B.check(lib.fc_unet_reserved(hnd, C.byref(rows0), C.byref(h0), C.byref(w0)))
-        B.check(lib.fc_unet_train_reserve(hnd, bsz, h, w))
-        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
-        a = torch.empty(bsz, dtype=torch.float64, device=dev)
-        logp = torch.empty(bsz, dtype=torch.float64, device=dev)
-        B.check(B.lib().fc_unet_log_likelihood(hnd, B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)),
-                                               ts_host.numel(), float(t_scale), B.ptr(class_ids), B.ptr(mask), int(mask_is_ones),
-                                               B.ptr(probe), B.ptr(a), B.ptr(logp), B.current_stream(dev)))
-        self._integrator_check(hnd, dev, check)
-        if restore_plan and not was_training_form:
-            self.release_training_plan()
-            if rows0.value > 0:                         # the reservation the caller had, in the form it had
-                B.check(lib.fc_unet_reserve(hnd, rows0.value, h0.value, w0.value))
+        _, ts_ptr, n_points = self._host_grid(ts, 2)
+        a, logp = (torch.empty(bsz, dtype=torch.float64, device=dev) for _ in range(2))
+        with self._training_form(hnd, bsz, h, w, restore_plan):
+            B.check(B.lib().fc_unet_log_likelihood(hnd, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids), B.ptr(mask),
+                                                   int(mask_is_ones), B.ptr(probe), B.ptr(a), B.ptr(logp), B.current_stream(dev)))
+            self._integrator_check(hnd, dev, check)
         return a, logp
 
     def integrate_guided(self, x: torch.Tensor, ts: torch.Tensor, measurement: torch.Tensor, keep: torch.Tensor, *, sigma_y: float = 0.05,
@@ -514,33 +529,20 @@ class Unet(NativeModule):
             raise ValueError(f"keep must have the shape of x or [B,1,H,W], got {tuple(keep.shape)}")
         if sigma_y < 0:
             raise ValueError("sigma_y must be >= 0")
-        if ts.numel() < 2:
-            raise ValueError("the time grid needs at least two points")
-        if x.data_ptr() % 16:
-            raise ValueError("x must be 16-byte aligned (the kernels read it as float4)")
+        ts_host, ts_ptr, n_points = self._host_grid(ts, 2)
+        self._check_aligned(x)
         # fresh aligned fp32 copies on x's device (the library copies them again into its own buffers)
         ym = measurement.to(device=dev, dtype=torch.float32).contiguous().clone()
         kp = keep.to(device=dev, dtype=torch.float32).expand_as(x).contiguous().clone()
-        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
         if not bool((ts_host > 0).all()):
             raise ValueError("every grid point must be > 0: the correction is gamma (1-t)/t g")
-        lib = B.lib()
-        if exact:
-            was_training_form = bool(lib.fc_unet_train_form(hnd))
-            rows0, h0, w0 = C.c_int(0), C.c_int(0), C.c_int(0)
-            B.check(lib.fc_unet_reserved(hnd, C.byref(rows0), C.byref(h0), C.byref(w0)))
-            B.check(lib.fc_unet_train_reserve(hnd, bsz, h, w))
-        else:
-            B.check(lib.fc_unet_reserve(hnd, rows, h, w))
-        B.check(lib.fc_unet_integrate_guided(hnd, B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)), ts_host.numel(),
-                                             float(t_scale), B.ptr(class_ids), float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones),
-                                             B.ptr(ym), B.ptr(kp), float(sigma_y), float(gamma),
-                                             B.FC_JACOBIAN_EXACT if exact else B.FC_JACOBIAN_IDENTITY, B.current_stream(dev)))
-        self._integrator_check(hnd, dev, check)
-        if exact and restore_plan and not was_training_form:
-            self.release_training_plan()
-            if rows0.value > 0:                         # the reservation the caller had, in the form it had
-                B.check(lib.fc_unet_reserve(hnd, rows0.value, h0.value, w0.value))
+        if not exact:
+            B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
+        with self._training_form(hnd, bsz, h, w, restore_plan) if exact else contextlib.nullcontext():
+            B.check(B.lib().fc_unet_integrate_guided(hnd, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids),
+                                                     float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), B.ptr(ym), B.ptr(kp), float(sigma_y),
+                                                     float(gamma), B.FC_JACOBIAN_EXACT if exact else B.FC_JACOBIAN_IDENTITY, B.current_stream(dev)))
+            self._integrator_check(hnd, dev, check)
         return x
 
     def integrate_sde(self, x: torch.Tensor, ts: torch.Tensor, *, sigma: float, method: str, seed: int = 0,
@@ -561,10 +563,9 @@ class Unet(NativeModule):
         class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength, cpu_error=_GPU_ONLY + "; there is no CPU path")
         dev = x.device
         bsz, _, h, w = x.shape
-        if x.data_ptr() % 16:
-            raise ValueError("x must be 16-byte aligned (the kernels read it as float4)")
-        ts_host = ts.detach().to("cpu", torch.float32).contiguous()
-        if ts_host.dim() != 1 or ts_host.numel() < 2:
+        self._check_aligned(x)
+        ts_host, ts_ptr, n_points = self._host_grid(ts, 2)
+        if ts_host.dim() != 1:
             raise ValueError("the time grid needs at least two points")
         if not bool(((ts_host >= 0) & (ts_host <= 1)).all()) or not bool((ts_host[1:] >= ts_host[:-1]).all()):
             raise ValueError("the time grid must be non-decreasing within [0, 1]")
@@ -582,10 +583,9 @@ class Unet(NativeModule):
         sample_ids = sample_ids.to(dev).contiguous()
         lib = B.lib()
         B.check(lib.fc_unet_reserve(hnd, rows, h, w))
-        B.check(lib.fc_unet_integrate_sde(hnd, _SDE_METHODS[method], B.ptr(x), bsz, h, w, ts_host.numpy().ctypes.data_as(C.POINTER(C.c_float)),
-                                          ts_host.numel(), float(t_scale), B.ptr(class_ids), float(cfg_strength or 0.0), B.ptr(mask),
-                                          int(mask_is_ones), sigma, int(seed) & 0xffffffffffffffff, B.ptr(sample_ids), B.ptr(noise),
-                                          B.current_stream(dev)))
+        B.check(lib.fc_unet_integrate_sde(hnd, _SDE_METHODS[method], B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids),
+                                          float(cfg_strength or 0.0), B.ptr(mask), int(mask_is_ones), sigma, int(seed) & 0xffffffffffffffff,
+                                          B.ptr(sample_ids), B.ptr(noise), B.current_stream(dev)))
         self._integrator_check(hnd, dev, check)
         return x
 
