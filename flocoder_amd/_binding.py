@@ -73,6 +73,7 @@ SIGNATURES = {
     "fc_unet_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "fc_unet_backward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _vp]),
     "fc_unet_backward_parts": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fc_unet_backward_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fc_unet_grad_buckets": (_i, [_vp, C.POINTER(_i64)]),
     "fc_unet_set_grad_buckets": (_i, [_vp, _i]),
     "fc_unet_backward_launches": (_i, [_vp]),
@@ -93,6 +94,8 @@ SIGNATURES = {
     "fc_unet_class_param_range": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "fc_flow_interp": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "fc_flow_prepare": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
+    "fc_flow_prepare_rows": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
+    "fc_mse_loss_grad_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp]),
     "fc_mse_loss_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fc_grad_clip_coef": (_i, [_vp, _i64, _vp, _i64, C.c_float, _vp, _vp, _vp]),
     "fc_adam_ema_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.c_float, _i, _vp]),

@@ -333,7 +333,10 @@ int norm_param_grads_launch(const float* s12, const float* gamma, const float* b
 }
 
 // The same for every norm layer of the network in one launch (a step has ~55 of them, each a few microseconds of work).
-// grid (ceil(maxC/64), njobs); 256 threads = 4 batch rows x 64 channels
+// grid (ceil(maxC/64), njobs); 256 threads = 4 batch rows x 64 channels.  ACC (here and on the other writers of the flat gradient
+// vector below): the result is added to what the vector holds (gradient accumulation over micro-batches) -- one writer per element,
+// a plain read-modify-write, no atomics.
+template <bool ACC>
 __global__ void __launch_bounds__(256) norm_param_grads_table_kernel(const NormJob* jobs, float* grads, float* dss_base, int ss_stride, int B) {
     __shared__ float rg[4][64], rb[4][64];
     const NormJob j = jobs[blockIdx.y];
@@ -358,13 +361,17 @@ __global__ void __launch_bounds__(256) norm_param_grads_table_kernel(const NormJ
     rg[row][lane] = dg; rb[row][lane] = db;
     __syncthreads();
     if (row == 0 && c < j.C) {
-        grads[j.dgamma + c] = (rg[0][lane] + rg[1][lane]) + (rg[2][lane] + rg[3][lane]);
-        grads[j.dbeta + c] = (rb[0][lane] + rb[1][lane]) + (rb[2][lane] + rb[3][lane]);
+        const float vg = (rg[0][lane] + rg[1][lane]) + (rg[2][lane] + rg[3][lane]);
+        const float vb = (rb[0][lane] + rb[1][lane]) + (rb[2][lane] + rb[3][lane]);
+        if (ACC) { grads[j.dgamma + c] += vg; grads[j.dbeta + c] += vb; }
+        else { grads[j.dgamma + c] = vg; grads[j.dbeta + c] = vb; }
     }
 }
-int norm_param_grads_table_launch(const NormJob* jobs_dev, int njobs, int maxC, float* grads, float* dss, int ss_stride, int B, hipStream_t s) {
+int norm_param_grads_table_launch(const NormJob* jobs_dev, int njobs, int maxC, float* grads, float* dss, int ss_stride, int B, hipStream_t s,
+                                  bool acc) {
     if (!njobs) return FC_OK;
-    hipLaunchKernelGGL(norm_param_grads_table_kernel, dim3(cdiv(maxC, 64), njobs), dim3(256), 0, s, jobs_dev, grads, dss, ss_stride, B);
+    if (acc) hipLaunchKernelGGL(norm_param_grads_table_kernel<true>, dim3(cdiv(maxC, 64), njobs), dim3(256), 0, s, jobs_dev, grads, dss, ss_stride, B);
+    else hipLaunchKernelGGL(norm_param_grads_table_kernel<false>, dim3(cdiv(maxC, 64), njobs), dim3(256), 0, s, jobs_dev, grads, dss, ss_stride, B);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -644,6 +651,7 @@ int dense_fwd_launch(const float* xpre, int in_act, const float* w, const float*
     return FC_OK;
 }
 // dW[o][i] = sum_b dy[b][o] act(xpre[b][i]);  db[o] = sum_b dy[b][o]      (dy row stride ldy)
+template <bool ACC>
 __global__ void __launch_bounds__(256) dense_bwd_w_kernel(const float* dy, int ldy, const float* xpre, int in_act, float* dw, float* db, int B, int I, int O) {
     const size_t total = (size_t)O * I;
     for (size_t t = blockIdx.x * 256ull + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
@@ -654,17 +662,19 @@ __global__ void __launch_bounds__(256) dense_bwd_w_kernel(const float* dy, int l
             acc += d * act_apply(xpre[(size_t)b * I + i], in_act);
             bs += d;
         }
-        dw[t] = acc;
-        if (i == 0 && db) db[o] = bs;
+        if (ACC) dw[t] += acc; else dw[t] = acc;
+        if (i == 0 && db) { if (ACC) db[o] += bs; else db[o] = bs; }
     }
 }
-int dense_bwd_w_launch(const float* dy, int ldy, const float* xpre, int in_act, float* dw, float* db, int B, int I, int O, hipStream_t s) {
-    hipLaunchKernelGGL(dense_bwd_w_kernel, dim3(grid_1d((size_t)O * I)), dim3(256), 0, s, dy, ldy, xpre, in_act, dw, db, B, I, O);
+int dense_bwd_w_launch(const float* dy, int ldy, const float* xpre, int in_act, float* dw, float* db, int B, int I, int O, hipStream_t s, bool acc) {
+    if (acc) hipLaunchKernelGGL(dense_bwd_w_kernel<true>, dim3(grid_1d((size_t)O * I)), dim3(256), 0, s, dy, ldy, xpre, in_act, dw, db, B, I, O);
+    else hipLaunchKernelGGL(dense_bwd_w_kernel<false>, dim3(grid_1d((size_t)O * I)), dim3(256), 0, s, dy, ldy, xpre, in_act, dw, db, B, I, O);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
 // Every ResnetBlock.mlp weight / bias gradient in one launch: job j owns rows [col, col + O) of the concatenated FiLM gradient
 // dss [B][S]; x = act(xpre) is shared.   blocks[k] = (job, chunk of 256 (o, i) pairs)
+template <bool ACC>
 __global__ void __launch_bounds__(256) dense_bwd_w_table_kernel(const DenseWJob* jobs, const int2* blocks, const float* dss, int S, const float* xpre,
                                                                 int in_act, float* grads, int B, int I) {
     extern __shared__ float xs[];   // act(xpre) [B][I] when it fits, else read through
@@ -679,13 +689,14 @@ __global__ void __launch_bounds__(256) dense_bwd_w_table_kernel(const DenseWJob*
         acc += d * act_apply(xpre[(size_t)b * I + i], in_act);
         bs += d;
     }
-    grads[j.dw + t] = acc;
-    if (i == 0) grads[j.db + o] = bs;
+    if (ACC) grads[j.dw + t] += acc; else grads[j.dw + t] = acc;
+    if (i == 0) { if (ACC) grads[j.db + o] += bs; else grads[j.db + o] = bs; }
 }
 int dense_bwd_w_table_launch(const DenseWJob* jobs_dev, const int2* blocks_dev, int nblocks, const float* dss, int S, const float* xpre, int in_act,
-                             float* grads, int B, int I, hipStream_t s) {
+                             float* grads, int B, int I, hipStream_t s, bool acc) {
     if (!nblocks) return FC_OK;
-    hipLaunchKernelGGL(dense_bwd_w_table_kernel, dim3(nblocks), dim3(256), 0, s, jobs_dev, blocks_dev, dss, S, xpre, in_act, grads, B, I);
+    if (acc) hipLaunchKernelGGL(dense_bwd_w_table_kernel<true>, dim3(nblocks), dim3(256), 0, s, jobs_dev, blocks_dev, dss, S, xpre, in_act, grads, B, I);
+    else hipLaunchKernelGGL(dense_bwd_w_table_kernel<false>, dim3(nblocks), dim3(256), 0, s, jobs_dev, blocks_dev, dss, S, xpre, in_act, grads, B, I);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -793,16 +804,18 @@ int mask_rows_launch(const float* d, int ld, const int64_t* ids, float* out, int
     return FC_OK;
 }
 // dtable[r][k] = sum over rows b with ids[b] == r of d[b][k], in batch order
+template <bool ACC>
 __global__ void __launch_bounds__(256) scatter_rows_kernel(const float* d, const int64_t* ids, float* dtable, int B, int D, int R) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= R * D) return;
     const int k = t % D, r = t / D;
     float acc = 0.f;
     for (int b = 0; b < B; ++b) if (ids[b] == r) acc += d[(size_t)b * D + k];
-    dtable[t] = acc;
+    if (ACC) dtable[t] += acc; else dtable[t] = acc;
 }
-int scatter_rows_launch(const float* d, const int64_t* ids, float* dtable, int B, int D, int R, hipStream_t s) {
-    hipLaunchKernelGGL(scatter_rows_kernel, dim3(cdiv(R * D, 256)), dim3(256), 0, s, d, ids, dtable, B, D, R);
+int scatter_rows_launch(const float* d, const int64_t* ids, float* dtable, int B, int D, int R, hipStream_t s, bool acc) {
+    if (acc) hipLaunchKernelGGL(scatter_rows_kernel<true>, dim3(cdiv(R * D, 256)), dim3(256), 0, s, d, ids, dtable, B, D, R);
+    else hipLaunchKernelGGL(scatter_rows_kernel<false>, dim3(cdiv(R * D, 256)), dim3(256), 0, s, d, ids, dtable, B, D, R);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -946,7 +959,8 @@ int flow_interp_launch(const float* src, const float* tgt, const float* t, float
 // synchronises).   grid (blocks over a row, B)
 __global__ void __launch_bounds__(256) flow_prepare_kernel(const float* src, const float* tgt, const long long* perm, const float* u, float one_minus_eps,
                                                            float eps, float a3, float a2, float a1, float t_scale, const long long* ids, int n_classes,
-                                                           float* t_out, float* time_out, float* x, float* v, int* flag, int per) {
+                                                           float* t_out, float* time_out, float* x, float* v, int* flag, int per, int tgt_rows,
+                                                           int row0) {
     const int b = blockIdx.y;
     const float t0 = __fadd_rn(__fmul_rn(u[b], one_minus_eps), eps);
     const float t2 = __fmul_rn(t0, t0), t3 = __fmul_rn(t2, t0);
@@ -956,12 +970,13 @@ __global__ void __launch_bounds__(256) flow_prepare_kernel(const float* src, con
         time_out[b] = __fmul_rn(tt, t_scale);
         if (ids && flag) { const long long id = ids[b]; if (id < 0 || id >= n_classes) atomicOr(flag, 1); }
     }
-    // a pairing entry outside [0, B) would be an out-of-bounds read (target[ot_indices] raises IndexError in torch): the row falls back to
-    // its own target and the sticky flag's bit 1 tells the host
-    long long pb = perm ? perm[b] : b;
-    if (pb < 0 || pb >= (long long)gridDim.y) {
+    // a pairing entry outside [0, rows of the target) would be an out-of-bounds read (target[ot_indices] raises IndexError in torch): the row
+    // falls back to its own target and the sticky flag's bit 1 tells the host.  The launch's rows are rows [row0, row0 + B) of the step the
+    // target belongs to (a micro-batch of a larger step; row0 = 0 and tgt_rows = B otherwise): src / u / ids / perm are the micro-batch's.
+    long long pb = perm ? perm[b] : row0 + b;
+    if (pb < 0 || pb >= (long long)tgt_rows) {
         if (flag && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(flag, 2);
-        pb = b;
+        pb = row0 + b;
     }
     const float* s = src + (size_t)b * per;
     const float* g = tgt + (size_t)pb * per;
@@ -972,14 +987,16 @@ __global__ void __launch_bounds__(256) flow_prepare_kernel(const float* src, con
     }
 }
 int flow_prepare_launch(const float* src, const float* tgt, const int64_t* perm, const float* u, float t_eps, float warp_s, float t_scale,
-                        const int64_t* ids, int n_classes, float* t_out, float* time_out, float* x, float* v, int* flag, int B, int per, hipStream_t s) {
+                        const int64_t* ids, int n_classes, float* t_out, float* time_out, float* x, float* v, int* flag, int B, int per, hipStream_t s,
+                        int tgt_rows, int row0) {
+    if (tgt_rows <= 0) { tgt_rows = B; row0 = 0; }
     int gx = cdiv(per, 1024);
     if (gx < 1) gx = 1;
     if (gx > 64) gx = 64;
     const double ws = warp_s;
     hipLaunchKernelGGL(flow_prepare_kernel, dim3(gx, B), dim3(256), 0, s, src, tgt, reinterpret_cast<const long long*>(perm), u, (float)(1.0 - (double)t_eps),
                        t_eps, (float)(4.0 * (1.0 - ws)), (float)(6.0 * (ws - 1.0)), (float)(3.0 - 2.0 * ws), t_scale,
-                       reinterpret_cast<const long long*>(ids), n_classes, t_out, time_out, x, v, flag, per);
+                       reinterpret_cast<const long long*>(ids), n_classes, t_out, time_out, x, v, flag, per, tgt_rows, row0);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -1005,6 +1022,19 @@ __global__ void __launch_bounds__(256) mse_final_kernel(const float* ws, float* 
 int mse_loss_grad_launch(const float* v, const float* tgt, float* dv, float* loss, float* ws, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(mse_partial_kernel, dim3(kRedBlocks), dim3(256), 0, s, v, tgt, dv, ws, n, 2.0f / (float)n);
     hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, ws, loss, 1.0f / (float)n);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
+// A micro-batch's share of a step's MSELoss: the same partial sums, dv with the share folded in, the loss ADDED to a running scalar
+__global__ void __launch_bounds__(256) mse_final_acc_kernel(const float* ws, float* loss_acc, float scale_over_n) {
+    __shared__ float red[4];
+    const float tot = block_sum(ws[threadIdx.x], red);
+    if (threadIdx.x == 0) *loss_acc += tot * scale_over_n;
+}
+int mse_loss_grad_scaled_launch(const float* v, const float* tgt, float* dv, float* loss_acc, float* ws, size_t n, float scale, hipStream_t s) {
+    hipLaunchKernelGGL(mse_partial_kernel, dim3(kRedBlocks), dim3(256), 0, s, v, tgt, dv, ws, n, (float)(2.0 * (double)scale / (double)n));
+    hipLaunchKernelGGL(mse_final_acc_kernel, dim3(1), dim3(256), 0, s, ws, loss_acc, (float)((double)scale / (double)n));
     FC_HIP(hipGetLastError());
     return FC_OK;
 }

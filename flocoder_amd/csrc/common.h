@@ -405,7 +405,9 @@ struct WgradDev {            // a launch's geometry as the device sees it (conv_
 };
 int conv_wgrad_init();
 size_t conv_wgrad_workspace(const WgradArgs& a);
-int conv_wgrad_launch(const WgradArgs& a, hipStream_t s);
+// `acc` (here and on the launches below that end in the caller's flat gradient vector): add the result to what the destination holds
+// instead of replacing it -- gradient accumulation over micro-batches (fc_unet_backward_accumulate); same arithmetic up to that add
+int conv_wgrad_launch(const WgradArgs& a, hipStream_t s, bool acc = false);
 // The split partials of MANY weight-gradient launches summed by ONE table-driven launch at the end of the backward (each launch then
 // needs a workspace of its own): 53 five-microsecond reduce launches per training step become one.
 struct WredJob { const float* ws; int nsplit; int nb; size_t stride, nw; int64_t dw, db; int cin, kk; };   // dw / db: offsets into the flat gradient vector (db < 0: none)
@@ -413,8 +415,9 @@ int conv_wgrad_split(const WgradArgs& a, int* nsplit, size_t* part_stride);     
 int conv_wgrad_launch_noreduce(const WgradArgs& a, hipStream_t s);                           // partials into a.ws (nsplit > 1), nothing else
 // Every weight gradient of one kernel size in one launch (full-batch training steps): the entries' inputs must all still be alive
 int conv_wgrad_table_entry(const WgradArgs& a, int64_t dw_off, int64_t db_off, WgradDev* out, int* nblocks, size_t* lds_bytes);
-int conv_wgrad_table_launch(int KS, const WgradDev* jobs_dev, const int2* blocks_dev, int nblocks, size_t lds_bytes, float* grads, hipStream_t s);
-int wgrad_reduce_table_launch(const WredJob* jobs_dev, const int2* blocks_dev, int nblocks, float* grads, hipStream_t s);
+int conv_wgrad_table_launch(int KS, const WgradDev* jobs_dev, const int2* blocks_dev, int nblocks, size_t lds_bytes, float* grads, hipStream_t s,
+                            bool acc = false);
+int wgrad_reduce_table_launch(const WredJob* jobs_dev, const int2* blocks_dev, int nblocks, float* grads, hipStream_t s, bool acc = false);
 
 struct GnBwdArgs {          // backward of y = act((gamma xhat + beta)(sc+1) + sh); xf describes the forward (mode 1: no act, 2: SiLU)
     const float* dy = nullptr;  // NHWC [B][HW][C]
@@ -432,22 +435,24 @@ int gn_bwd_launch(const GnBwdArgs& a, hipStream_t s);
 int norm_param_grads_launch(const float* s12, const float* gamma, const float* beta, const float* ss, int ss_stride, float* dgamma,
                             float* dbeta, float* dss, int B, int C, hipStream_t s);
 struct NormJob { const float* s12; const float* gamma; const float* beta; const float* ss; int64_t dgamma, dbeta; int ss_col, C; };
-int norm_param_grads_table_launch(const NormJob* jobs_dev, int njobs, int maxC, float* grads, float* dss, int ss_stride, int B, hipStream_t s);
+int norm_param_grads_table_launch(const NormJob* jobs_dev, int njobs, int maxC, float* grads, float* dss, int ss_stride, int B, hipStream_t s,
+                                  bool acc = false);
 int linattn_bwd_launch(const float* qkv, const float* dout, const float* ctx, float* dctx, float* kst, float* rr, float* dqkv, int B, int n,
                        int heads, hipStream_t s);
 int attn_small_bwd_launch(const float* qkv, const float* dout, float* dqkv, int B, int n, int heads, hipStream_t s);
 // dense layers of the conditioning path; in_act: 0 none, 1 GELU(erf), 2 SiLU applied to `xpre` on the way in
 int dense_fwd_launch(const float* xpre, int in_act, const float* w, const float* bias, float* y, int B, int I, int O, hipStream_t s);
-int dense_bwd_w_launch(const float* dy, int ldy, const float* xpre, int in_act, float* dw, float* db, int B, int I, int O, hipStream_t s);
+int dense_bwd_w_launch(const float* dy, int ldy, const float* xpre, int in_act, float* dw, float* db, int B, int I, int O, hipStream_t s,
+                       bool acc = false);
 struct DenseWJob { int col, O; int64_t dw, db; };
 int dense_bwd_w_table_launch(const DenseWJob* jobs_dev, const int2* blocks_dev, int nblocks, const float* dss, int S, const float* xpre, int in_act,
-                             float* grads, int B, int I, hipStream_t s);
+                             float* grads, int B, int I, hipStream_t s, bool acc = false);
 int dense_bwd_x_launch(const float* dy, int ldy, const float* w, int w_t, int ldw, const float* xpre, int in_act, float* dx, int accumulate,
                        int B, int I, int O, hipStream_t s);
 int sin_emb_launch(const float* time, const float* freqs, float* e, int B, int dim, hipStream_t s);
 int gather_rows_launch(const float* table, const int64_t* ids, float* out, int B, int D, int R, hipStream_t s);
 int mask_rows_launch(const float* d, int ld, const int64_t* ids, float* out, int B, int D, int R, hipStream_t s);
-int scatter_rows_launch(const float* d, const int64_t* ids, float* dtable, int B, int D, int R, hipStream_t s);
+int scatter_rows_launch(const float* d, const int64_t* ids, float* dtable, int B, int D, int R, hipStream_t s, bool acc = false);
 int add_into_launch(float* dst, const float* src, size_t n, hipStream_t s);
 int silu_fwd_launch(const float* z, const float* add, float* y, size_t n, hipStream_t s);
 int silu_bwd_launch(const float* dy, const float* z, float* dz, size_t n, hipStream_t s);
@@ -456,8 +461,11 @@ int sumpool2_nhwc_launch(const float* src, float* dst, int B, int H, int W, int 
 int depth_to_space_launch(const float* src, float* dst, int B, int H, int W, int C, int accumulate, hipStream_t s);
 int flow_interp_launch(const float* src, const float* tgt, const float* t, float* x, float* v, int B, int per, hipStream_t s);
 int flow_prepare_launch(const float* src, const float* tgt, const int64_t* perm, const float* u, float t_eps, float warp_s, float t_scale,
-                        const int64_t* ids, int n_classes, float* t_out, float* time_out, float* x, float* v, int* flag, int B, int per, hipStream_t s);
+                        const int64_t* ids, int n_classes, float* t_out, float* time_out, float* x, float* v, int* flag, int B, int per, hipStream_t s,
+                        int tgt_rows = 0, int row0 = 0);     // tgt_rows > 0: the B rows are rows [row0, row0 + B) of a step of tgt_rows rows (tgt spans all of them)
 int mse_loss_grad_launch(const float* v, const float* tgt, float* dv, float* loss, float* ws /*256*/, size_t n, hipStream_t s);
+// dv = scale * 2 (v - v*) / n (dv may be null); *loss_acc += scale * mean((v - v*)^2)
+int mse_loss_grad_scaled_launch(const float* v, const float* tgt, float* dv, float* loss_acc, float* ws /*256*/, size_t n, float scale, hipStream_t s);
 int grad_clip_coef_launch(const float* g, size_t n0, const float* g2, size_t n1, float max_norm, float* out2 /*{norm, coef}*/, float* ws /*256*/,
                           hipStream_t s);
 int adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, const float* coef_dev, float lr, float b1, float b2,

@@ -14,9 +14,17 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CS = 33;
 
+// Where a finished gradient element goes: it replaces what the caller's vector holds, or (ACC: gradient accumulation over micro-batches,
+// fc_unet_backward_accumulate) is added to it.  Every element has exactly one writer thread, so the add is a plain read-modify-write:
+// no atomics, the same bits run to run.  Split partials in a workspace are always plain stores.
+template <bool ACC>
+__device__ __forceinline__ void grad_put(float* p, float v) {
+    if (ACC) *p += v; else *p = v;
+}
+
 // (split, cicoc): which share of the pixel tiles and which 32 x 32 block of every tap this workgroup owns; dw / db: where the
 // un-split result goes (the launch's own pointers, or offsets into the caller's flat gradient vector for a table-driven launch)
-template <int KS>
+template <int KS, bool ACC>
 __device__ __forceinline__ void wgrad_body(const WgradDev& p, const int split, const int cicoc, float* dw, float* db) {
     constexpr int KK = KS * KS, TPW = KS == 1 ? 1 : (KK + 3) / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -145,14 +153,17 @@ __device__ __forceinline__ void wgrad_body(const WgradDev& p, const int split, c
                     const int ci = ci0 + (r & 3) + 8 * (r >> 2) + 4 * half;
                     // partials are kept [tap][ci][co] (the 32 lanes of a store are 32 consecutive floats); the reduction writes the
                     // reference's [co][ci][tap] order.  In that order a store instruction touched 64 different cache lines.
-                    if (ci < a.Cin) dst[p.nsplit > 1 ? ((size_t)tap * a.Cin + ci) * a.Cout + co : ((size_t)co * a.Cin + ci) * KK + tap] = acc[t][r];
+                    if (ci < a.Cin) {
+                        if (p.nsplit > 1) dst[((size_t)tap * a.Cin + ci) * a.Cout + co] = acc[t][r];
+                        else grad_put<ACC>(dst + ((size_t)co * a.Cin + ci) * KK + tap, acc[t][r]);
+                    }
                 }
             }
         }
     }
     if (db && cic == 0 && tid < 32 && co0 + tid < a.Cout) {
-        float* bd = p.nsplit > 1 ? a.ws + (size_t)split * p.part_stride + (size_t)a.Cout * a.Cin * KK : db;
-        bd[co0 + tid] = bsum;
+        if (p.nsplit > 1) a.ws[(size_t)split * p.part_stride + (size_t)a.Cout * a.Cin * KK + co0 + tid] = bsum;
+        else grad_put<ACC>(db + co0 + tid, bsum);
     }
 }
 
@@ -160,6 +171,7 @@ __device__ __forceinline__ void wgrad_body(const WgradDev& p, const int split, c
 // operands are X[pix][ci0 + lane & 31] and dY[pix][co0 + lane & 31] for pix = 2j + (lane >> 5): two coalesced 128-byte rows per
 // operand straight from global memory, eight k-steps in flight per wave.  The LDS-staged form above spent its time staging 128-pixel
 // tiles for 16 MFMAs per wave (0.41 ms of the flowers-sized training step in one table launch).
+template <bool ACC>
 __device__ __forceinline__ void wgrad1x1_body(const WgradDev& p, const int split, const int cicoc, float* dw, float* db) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const WgradArgs& a = p.a;
@@ -212,32 +224,36 @@ __device__ __forceinline__ void wgrad1x1_body(const WgradDev& p, const int split
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int c = cic * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (c < a.Cin) dst[p.nsplit > 1 ? (size_t)c * a.Cout + co : (size_t)co * a.Cin + c] = acc[r];
+                if (c < a.Cin) {
+                    if (p.nsplit > 1) dst[(size_t)c * a.Cout + co] = acc[r];
+                    else grad_put<ACC>(dst + (size_t)co * a.Cin + c, acc[r]);
+                }
             }
         }
         if (db && cic == 0 && half == 0 && cook) {
             const float* br = red + 3 * 16 * 64;
-            float* bd = p.nsplit > 1 ? a.ws + (size_t)split * p.part_stride + (size_t)a.Cout * a.Cin : db;
-            bd[co] = (br[l31] + br[32 + l31]) + (br[64 + l31] + br[96 + l31]);
+            const float bv = (br[l31] + br[32 + l31]) + (br[64 + l31] + br[96 + l31]);
+            if (p.nsplit > 1) a.ws[(size_t)split * p.part_stride + (size_t)a.Cout * a.Cin + co] = bv;
+            else grad_put<ACC>(db + co, bv);
         }
     }
 }
 
-template <int KS>
+template <int KS, bool ACC>
 __global__ void __launch_bounds__(256) conv_wgrad_kernel(const WgradDev p) {
-    if (KS == 1 && p.direct1) { wgrad1x1_body(p, blockIdx.x, blockIdx.y, p.a.dw, p.a.db); return; }
-    wgrad_body<KS>(p, blockIdx.x, blockIdx.y, p.a.dw, p.a.db);
+    if (KS == 1 && p.direct1) { wgrad1x1_body<ACC>(p, blockIdx.x, blockIdx.y, p.a.dw, p.a.db); return; }
+    wgrad_body<KS, ACC>(p, blockIdx.x, blockIdx.y, p.a.dw, p.a.db);
 }
 
 // Every weight gradient of one kernel size in ONE launch: block -> (job, split + nsplit * cicoc) through a table.  At the training
 // shapes a single layer's launch is a few dozen workgroups and ~10-20 us of latency (staging -> MFMA -> store); 70 of them in a row
 // were a quarter of the step, side by side they fill the chip once.
-template <int KS>
+template <int KS, bool ACC>
 __global__ void __launch_bounds__(256) conv_wgrad_table_kernel(const WgradDev* __restrict__ jobs, const int2* __restrict__ blocks, float* grads) {
     const int2 bj = blocks[blockIdx.x];
     const WgradDev p = jobs[bj.x];
-    if (KS == 1 && p.direct1) { wgrad1x1_body(p, bj.y % p.nsplit, bj.y / p.nsplit, grads + p.dw_off, p.db_off >= 0 ? grads + p.db_off : nullptr); return; }
-    wgrad_body<KS>(p, bj.y % p.nsplit, bj.y / p.nsplit, grads + p.dw_off, p.db_off >= 0 ? grads + p.db_off : nullptr);
+    if (KS == 1 && p.direct1) { wgrad1x1_body<ACC>(p, bj.y % p.nsplit, bj.y / p.nsplit, grads + p.dw_off, p.db_off >= 0 ? grads + p.db_off : nullptr); return; }
+    wgrad_body<KS, ACC>(p, bj.y % p.nsplit, bj.y / p.nsplit, grads + p.dw_off, p.db_off >= 0 ? grads + p.db_off : nullptr);
 }
 
 // element e of a partial vector ([tap][ci][co] | bias) -> its place in the [co][ci][tap] | bias result
@@ -248,6 +264,7 @@ __device__ __forceinline__ size_t wgrad_final_index(size_t e, size_t nw, int cou
 }
 
 // 256 threads = 64 elements x 4 split lanes (fixed assignment and fixed combine order: bit-reproducible)
+template <bool ACC>
 __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* ws, int nsplit, size_t stride, float* dw, size_t nw, float* db, int nb, int cin,
                                                            int kk) {
     __shared__ float part[4][64];
@@ -263,13 +280,14 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* ws, int 
         __syncthreads();
         if (sl == 0 && e < total) {
             const float v = (part[0][el] + part[1][el]) + (part[2][el] + part[3][el]);
-            if (e < nw) dw[wgrad_final_index(e, nw, nb, cin, kk)] = v;
-            else db[e - nw] = v;
+            if (e < nw) grad_put<ACC>(dw + wgrad_final_index(e, nw, nb, cin, kk), v);
+            else grad_put<ACC>(db + (e - nw), v);
         }
     }
 }
 
 // block (job, chunk): 64 consecutive elements of one job's partial vector, 4 split lanes each (same fixed order as wgrad_reduce_kernel)
+template <bool ACC>
 __global__ void __launch_bounds__(256) wgrad_reduce_table_kernel(const WredJob* jobs, const int2* blocks, float* grads) {
     __shared__ float part[4][64];
     const int2 bj = blocks[blockIdx.x];
@@ -283,13 +301,14 @@ __global__ void __launch_bounds__(256) wgrad_reduce_table_kernel(const WredJob* 
     __syncthreads();
     if (sl == 0 && e < total) {
         const float v = (part[0][el] + part[1][el]) + (part[2][el] + part[3][el]);
-        if (e < j.nw) grads[j.dw + wgrad_final_index(e, j.nw, j.nb, j.cin, j.kk)] = v;
-        else grads[j.db + (e - j.nw)] = v;
+        if (e < j.nw) grad_put<ACC>(grads + j.dw + wgrad_final_index(e, j.nw, j.nb, j.cin, j.kk), v);
+        else grad_put<ACC>(grads + j.db + (e - j.nw), v);
     }
 }
-int wgrad_reduce_table_launch(const WredJob* jobs_dev, const int2* blocks_dev, int nblocks, float* grads, hipStream_t s) {
+int wgrad_reduce_table_launch(const WredJob* jobs_dev, const int2* blocks_dev, int nblocks, float* grads, hipStream_t s, bool acc) {
     if (!nblocks) return FC_OK;
-    hipLaunchKernelGGL(wgrad_reduce_table_kernel, dim3(nblocks), dim3(256), 0, s, jobs_dev, blocks_dev, grads);
+    if (acc) hipLaunchKernelGGL(wgrad_reduce_table_kernel<true>, dim3(nblocks), dim3(256), 0, s, jobs_dev, blocks_dev, grads);
+    else hipLaunchKernelGGL(wgrad_reduce_table_kernel<false>, dim3(nblocks), dim3(256), 0, s, jobs_dev, blocks_dev, grads);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -348,28 +367,35 @@ int conv_wgrad_split(const WgradArgs& a, int* nsplit, size_t* part_stride) {
     return FC_OK;
 }
 
-static int wgrad_launch_impl(const WgradArgs& a, bool reduce, hipStream_t s);
-int conv_wgrad_launch(const WgradArgs& a, hipStream_t s) { return wgrad_launch_impl(a, true, s); }
-int conv_wgrad_launch_noreduce(const WgradArgs& a, hipStream_t s) { return wgrad_launch_impl(a, false, s); }
+static int wgrad_launch_impl(const WgradArgs& a, bool reduce, bool acc, hipStream_t s);
+int conv_wgrad_launch(const WgradArgs& a, hipStream_t s, bool acc) { return wgrad_launch_impl(a, true, acc, s); }
+int conv_wgrad_launch_noreduce(const WgradArgs& a, hipStream_t s) { return wgrad_launch_impl(a, false, false, s); }
 
-static int wgrad_launch_impl(const WgradArgs& a, bool reduce, hipStream_t s) {
+template <bool ACC>
+static void wgrad_launch_ks(const WgradDev& d, int KS, dim3 grid, size_t lds, hipStream_t s) {
+    switch (KS) {
+        case 1: hipLaunchKernelGGL((conv_wgrad_kernel<1, ACC>), grid, dim3(256), lds, s, d); break;
+        case 2: hipLaunchKernelGGL((conv_wgrad_kernel<2, ACC>), grid, dim3(256), lds, s, d); break;
+        case 3: hipLaunchKernelGGL((conv_wgrad_kernel<3, ACC>), grid, dim3(256), lds, s, d); break;
+        default: hipLaunchKernelGGL((conv_wgrad_kernel<5, ACC>), grid, dim3(256), lds, s, d); break;
+    }
+}
+
+static int wgrad_launch_impl(const WgradArgs& a, bool reduce, bool acc, hipStream_t s) {
     WgradDev d;
     FC_TRY(wgrad_geometry(a, &d));
     if (d.nsplit > 1 && !a.ws) return fail(FC_E_ARG, "wgrad: workspace missing");
     const size_t lds = (size_t)(d.o_pix + 128) * sizeof(float);
     const dim3 grid(d.nsplit, d.nci * d.nco);
-    switch (a.KS) {
-        case 1: hipLaunchKernelGGL(conv_wgrad_kernel<1>, grid, dim3(256), lds, s, d); break;
-        case 2: hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(256), lds, s, d); break;
-        case 3: hipLaunchKernelGGL(conv_wgrad_kernel<3>, grid, dim3(256), lds, s, d); break;
-        default: hipLaunchKernelGGL(conv_wgrad_kernel<5>, grid, dim3(256), lds, s, d); break;
-    }
+    if (acc) wgrad_launch_ks<true>(d, a.KS, grid, lds, s);
+    else wgrad_launch_ks<false>(d, a.KS, grid, lds, s);
     FC_HIP(hipGetLastError());
     if (d.nsplit > 1 && reduce) {
         const size_t nw = (size_t)a.Cout * a.Cin * a.KS * a.KS;
         const size_t total = nw + (a.db ? a.Cout : 0);
         const int g = (int)((total + 63) / 64 < 4096 ? (total + 63) / 64 : 4096);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(g), dim3(256), 0, s, a.ws, d.nsplit, d.part_stride, a.dw, nw, a.db, a.Cout, a.Cin, a.KS * a.KS);
+        if (acc) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, dim3(g), dim3(256), 0, s, a.ws, d.nsplit, d.part_stride, a.dw, nw, a.db, a.Cout, a.Cin, a.KS * a.KS);
+        else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, dim3(g), dim3(256), 0, s, a.ws, d.nsplit, d.part_stride, a.dw, nw, a.db, a.Cout, a.Cin, a.KS * a.KS);
         FC_HIP(hipGetLastError());
     }
     return FC_OK;
@@ -387,30 +413,42 @@ int conv_wgrad_table_entry(const WgradArgs& a, int64_t dw_off, int64_t db_off, W
     return FC_OK;
 }
 
-int conv_wgrad_table_launch(int KS, const WgradDev* jobs_dev, const int2* blocks_dev, int nblocks, size_t lds_bytes, float* grads, hipStream_t s) {
-    if (!nblocks) return FC_OK;
-    const dim3 grid(nblocks);
+template <bool ACC>
+static int wgrad_table_launch_ks(int KS, const WgradDev* jobs_dev, const int2* blocks_dev, dim3 grid, size_t lds_bytes, float* grads, hipStream_t s) {
     switch (KS) {
-        case 1: hipLaunchKernelGGL(conv_wgrad_table_kernel<1>, grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
-        case 2: hipLaunchKernelGGL(conv_wgrad_table_kernel<2>, grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
-        case 3: hipLaunchKernelGGL(conv_wgrad_table_kernel<3>, grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
-        case 5: hipLaunchKernelGGL(conv_wgrad_table_kernel<5>, grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
+        case 1: hipLaunchKernelGGL((conv_wgrad_table_kernel<1, ACC>), grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
+        case 2: hipLaunchKernelGGL((conv_wgrad_table_kernel<2, ACC>), grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
+        case 3: hipLaunchKernelGGL((conv_wgrad_table_kernel<3, ACC>), grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
+        case 5: hipLaunchKernelGGL((conv_wgrad_table_kernel<5, ACC>), grid, dim3(256), lds_bytes, s, jobs_dev, blocks_dev, grads); break;
         default: return fail(FC_E_SHAPE, "wgrad table: kernel size not instantiated");
     }
+    return FC_OK;
+}
+
+int conv_wgrad_table_launch(int KS, const WgradDev* jobs_dev, const int2* blocks_dev, int nblocks, size_t lds_bytes, float* grads, hipStream_t s,
+                            bool acc) {
+    if (!nblocks) return FC_OK;
+    const dim3 grid(nblocks);
+    FC_TRY(acc ? wgrad_table_launch_ks<true>(KS, jobs_dev, blocks_dev, grid, lds_bytes, grads, s)
+               : wgrad_table_launch_ks<false>(KS, jobs_dev, blocks_dev, grid, lds_bytes, grads, s));
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
 
+template <int KS>
+static int wgrad_lds_attr() {    // > 64 KB of dynamic LDS needs the attribute on gfx950 too
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_table_kernel<KS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_table_kernel<KS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<KS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<KS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    return FC_OK;
+}
+
 int conv_wgrad_init() {
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_table_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_table_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_table_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_table_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    // > 64 KB of dynamic LDS needs the attribute on gfx950 too
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    FC_TRY(wgrad_lds_attr<1>());
+    FC_TRY(wgrad_lds_attr<2>());
+    FC_TRY(wgrad_lds_attr<3>());
+    FC_TRY(wgrad_lds_attr<5>());
     return FC_OK;
 }
 

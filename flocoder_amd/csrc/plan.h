@@ -33,6 +33,7 @@ struct FwdCtx {             // per-call inputs of one forward
     int B = 0;
     const float* d_out = nullptr;      // backward only: NCHW gradient of `out`
     float* grads = nullptr;            // backward only: flat parameter gradients, table layout
+    bool grads_acc = false;            // backward only: add to `grads` instead of replacing its contents (fc_unet_backward_accumulate)
     float* dx_out = nullptr;           // backward only, optional: NCHW gradient of the input x
     float* dmask_out = nullptr;        // backward only, optional: NCHW gradient of the mask
     EulerTail euler;                   // integrator only: the Euler update rides in final_conv

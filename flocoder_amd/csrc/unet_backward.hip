@@ -12,7 +12,8 @@
 // then the conditioning path: FiLM projections, time MLP, class-embedding MLP.  Data gradients reuse the forward implicit-GEMM
 // kernel on flipped, transposed weights (re-packed whenever the parameters change); a tensor with several consumers gets its
 // gradient contributions through the kernels' accumulate paths in a fixed order.  Parameter gradients land in the caller's flat
-// vector in the parameter table's layout, each written exactly once.
+// vector in the parameter table's layout, each written exactly once -- or, through fc_unet_backward_accumulate, added exactly once to
+// what the vector holds (FwdCtx::grads_acc: every writer of the flat vector has an add form; nothing else is touched).
 //
 // Every entry carries a flag (Plan::op_param_only, set through PlanBuilder::param_only while it is pushed): its products are parameter
 // gradients, or something only parameter gradients read.  fc_unet_vjp_x / fc_unet_log_likelihood run the unflagged entries alone -- the
@@ -126,7 +127,7 @@ struct BwdBuilder : PlanBuilder {
             if (!(own && c.B == maxB)) b.split_target = 1024;
             b.B = c.B; b.dw = c.grads + wo; b.db = bo >= 0 ? c.grads + bo : nullptr;
             if (own && c.B == maxB) { b.ws = own; b.ws_floats = own_floats; return conv_wgrad_launch_noreduce(b, s); }
-            return conv_wgrad_launch(b, s);
+            return conv_wgrad_launch(b, s, c.grads_acc);
         }, "conv_wgrad", 2.0 * dy.H * dy.W * KS * KS * (double)a.Cin * a.Cout);
     }
 
@@ -483,7 +484,7 @@ int build_backward(fc_unet* u) {
         const size_t lds = wc.lds;
         double fl = 0;
         for (const WgradDev& d : wc.jobs) fl += 2.0 * d.a.H * d.a.W * ks * ks * (double)d.a.Cin * d.a.Cout;
-        b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.B == B ? conv_wgrad_table_launch(ks, jd, bd, nblk, lds, cx.grads, s) : (int)FC_OK; },
+        b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.B == B ? conv_wgrad_table_launch(ks, jd, bd, nblk, lds, cx.grads, s, cx.grads_acc) : (int)FC_OK; },
                "conv_wgrad_table", fl);
     }
     // -- the split partials of every weight gradient above, summed in one launch (full-batch steps; smaller batches reduced per launch) --
@@ -501,7 +502,7 @@ int build_backward(fc_unet* u) {
         FC_HIP(hipMemcpy(jd, b.wred_jobs.data(), b.wred_jobs.size() * sizeof(WredJob), hipMemcpyHostToDevice));
         FC_HIP(hipMemcpy(bd, blocks.data(), blocks.size() * sizeof(int2), hipMemcpyHostToDevice));
         const int nblk = (int)blocks.size();
-        b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.B == B ? wgrad_reduce_table_launch(jd, bd, nblk, cx.grads, s) : (int)FC_OK; }, "wgrad_reduce");
+        b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.B == B ? wgrad_reduce_table_launch(jd, bd, nblk, cx.grads, s, cx.grads_acc) : (int)FC_OK; }, "wgrad_reduce");
     }
     // -- parameter gradients of every norm layer and the FiLM gradients, one launch --
     if (!b.norm_jobs.empty()) {
@@ -513,7 +514,7 @@ int build_backward(fc_unet* u) {
         int mc = 0;
         for (const NormJob& j : b.norm_jobs) if (j.C > mc) mc = j.C;
         float* dssp = b.dss;
-        b.push([=](const FwdCtx& cx, hipStream_t s) { return norm_param_grads_table_launch(jd, nj, mc, cx.grads, dssp, S, cx.B, s); }, "norm_param_grads");
+        b.push([=](const FwdCtx& cx, hipStream_t s) { return norm_param_grads_table_launch(jd, nj, mc, cx.grads, dssp, S, cx.B, s, cx.grads_acc); }, "norm_param_grads");
     }
         if (!b.film_blocks.empty()) {
             b.scope = "resblock.mlp";
@@ -534,7 +535,7 @@ int build_backward(fc_unet* u) {
             FC_HIP(hipMemcpy(jd, jobs.data(), jobs.size() * sizeof(DenseWJob), hipMemcpyHostToDevice));
             FC_HIP(hipMemcpy(bd, blocks.data(), blocks.size() * sizeof(int2), hipMemcpyHostToDevice));
             const int nblk = (int)blocks.size();
-            b.push([=](const FwdCtx& cx, hipStream_t s) { return dense_bwd_w_table_launch(jd, bd, nblk, dss, S, te, 2, cx.grads, cx.B, td, s); }, "dense_bwd_w");
+            b.push([=](const FwdCtx& cx, hipStream_t s) { return dense_bwd_w_table_launch(jd, bd, nblk, dss, S, te, 2, cx.grads, cx.B, td, s, cx.grads_acc); }, "dense_bwd_w");
         }
         }
         b.fin_jobs.clear(); b.wclasses.clear(); b.wred_jobs.clear(); b.norm_jobs.clear(); b.film_blocks.clear();
@@ -589,7 +590,7 @@ int build_backward(fc_unet* u) {
         b.push([=](const FwdCtx& cx, hipStream_t s) {
             WgradArgs q = a;
             q.B = cx.B; q.dy = cx.mask_fuse ? gxi : gx0; q.dw = cx.grads + wo; q.db = cx.grads + bo;
-            return conv_wgrad_launch(q, s);
+            return conv_wgrad_launch(q, s, cx.grads_acc);
         }, "conv_wgrad", 2.0 * HW * (double)ch * dim);
         }
         // d(x) = init_conv^T d(.) as an NHWC tensor, converted to the NCHW boundary layout on request (fc_unet_backward_ex)
@@ -638,9 +639,9 @@ int build_backward(fc_unet* u) {
         b.push([=](const FwdCtx& cx, hipStream_t s) -> int {
             FC_TRY(sin_emb_launch(cx.time, fr, se, cx.B, dim, s));
             FC_TRY(dense_fwd_launch(se, 0, w1, b1, z1, cx.B, dim, td, s));
-            FC_TRY(dense_bwd_w_launch(dT, td, z1, 1, cx.grads + o3w, cx.grads + o3b, cx.B, td, td, s));
+            FC_TRY(dense_bwd_w_launch(dT, td, z1, 1, cx.grads + o3w, cx.grads + o3b, cx.B, td, td, s, cx.grads_acc));
             FC_TRY(dense_bwd_x_launch(dT, td, w3, 0, 0, z1, 1, dz1, 0, cx.B, td, td, s));
-            return dense_bwd_w_launch(dz1, td, se, 0, cx.grads + o1w, cx.grads + o1b, cx.B, dim, td, s);
+            return dense_bwd_w_launch(dz1, td, se, 0, cx.grads + o1w, cx.grads + o1b, cx.B, dim, td, s, cx.grads_acc);
         }, "time_mlp_bwd");
         if (ncls > 0) {
             b.scope = "class_cond_mlp";
@@ -655,11 +656,11 @@ int build_backward(fc_unet* u) {
                 FC_TRY(gather_rows_launch(E, cx.ids, e, cx.B, td, ncls, s));
                 FC_TRY(dense_fwd_launch(e, 0, cw1, cb1, cz1, cx.B, td, td, s));
                 FC_TRY(mask_rows_launch(dT, td, cx.ids, dTm, cx.B, td, ncls, s));
-                FC_TRY(dense_bwd_w_launch(dTm, td, cz1, 1, cx.grads + c3w, cx.grads + c3b, cx.B, td, td, s));
+                FC_TRY(dense_bwd_w_launch(dTm, td, cz1, 1, cx.grads + c3w, cx.grads + c3b, cx.B, td, td, s, cx.grads_acc));
                 FC_TRY(dense_bwd_x_launch(dTm, td, cw3, 0, 0, cz1, 1, dcz1, 0, cx.B, td, td, s));
-                FC_TRY(dense_bwd_w_launch(dcz1, td, e, 0, cx.grads + c1w, cx.grads + c1b, cx.B, td, td, s));
+                FC_TRY(dense_bwd_w_launch(dcz1, td, e, 0, cx.grads + c1w, cx.grads + c1b, cx.B, td, td, s, cx.grads_acc));
                 FC_TRY(dense_bwd_x_launch(dcz1, td, cw1, 0, 0, nullptr, 0, de, 0, cx.B, td, td, s));
-                return scatter_rows_launch(de, cx.ids, cx.grads + oE, cx.B, td, ncls, s);
+                return scatter_rows_launch(de, cx.ids, cx.grads + oE, cx.B, td, ncls, s, cx.grads_acc);
             }, "class_mlp_bwd");
         }
     }
@@ -784,9 +785,11 @@ int fc_unet_backward_op_info(const fc_unet* u, int i, const char** kernel, const
     return FC_OK;
 }
 
-int fc_unet_backward_parts(fc_unet* u, const float* x, const float* time, const int64_t* ids, const float* mask, int mask_is_ones,
-                           const float* d_out, float* grads, int64_t numel, float* dx_out, float* dmask_out, int B, int H, int W,
-                           int first_part, int last_part, void* stream) {
+// fc_unet_backward_parts (accumulate = false: the vector is zeroed, then written) and fc_unet_backward_accumulate (true: no zeroing, every
+// writer adds) over the same plan entries
+static int backward_run(fc_unet* u, const float* x, const float* time, const int64_t* ids, const float* mask, int mask_is_ones,
+                        const float* d_out, float* grads, int64_t numel, float* dx_out, float* dmask_out, int B, int H, int W,
+                        int first_part, int last_part, bool accumulate, void* stream) {
     if (!u || !x || !time || !d_out || !grads || B < 1) return fail(FC_E_ARG, "fc_unet_backward: null argument");
     if (u->bwd.maxB < B || u->bwd.H != H || u->bwd.W != W || u->plan.maxB < B) return fail(FC_E_STATE, "unet: no backward plan for this shape; call fc_unet_train_reserve");
     if (numel != u->raw_numel) return fail(FC_E_ARG, "fc_unet_backward: gradient vector must have " + std::to_string(u->raw_numel) + " floats (padded table layout)");
@@ -801,16 +804,28 @@ int fc_unet_backward_parts(fc_unet* u, const float* x, const float* time, const 
         u->dgrad_version = u->param_version;
     }
     if (first_part < 0 || last_part > 1 || first_part > last_part) return fail(FC_E_ARG, "fc_unet_backward_parts: parts are 0 (through mid_block1) and 1 (the rest)");
-    if (first_part == 0) FC_HIP(hipMemsetAsync(grads, 0, (size_t)numel * sizeof(float), s));
+    if (first_part == 0 && !accumulate) FC_HIP(hipMemsetAsync(grads, 0, (size_t)numel * sizeof(float), s));
     FwdCtx c;
     c.x = x; c.x_mod = B; c.time = time; c.ids = u->cfg.n_classes > 0 ? ids : nullptr; c.ids_mod = B; c.B = B;
     c.mask = u->cfg.mask_cond ? mask : nullptr;
     c.mask_fuse = (c.mask && !mask_is_ones) ? 1 : 0;
-    c.d_out = d_out; c.grads = grads; c.dx_out = dx_out; c.dmask_out = c.mask ? dmask_out : nullptr;
+    c.d_out = d_out; c.grads = grads; c.grads_acc = accumulate; c.dx_out = dx_out; c.dmask_out = c.mask ? dmask_out : nullptr;
     const int nops = (int)u->bwd.ops.size(), split = (u->bwd_split_op >= 0 && u->bwd_split_op <= nops) ? u->bwd_split_op : nops;
     const int lo = first_part == 0 ? 0 : split, hi = last_part == 0 ? split : nops;
     for (int i = lo; i < hi; ++i) FC_TRY(u->bwd.ops[i](c, s));
     return FC_OK;
+}
+
+int fc_unet_backward_parts(fc_unet* u, const float* x, const float* time, const int64_t* ids, const float* mask, int mask_is_ones,
+                           const float* d_out, float* grads, int64_t numel, float* dx_out, float* dmask_out, int B, int H, int W,
+                           int first_part, int last_part, void* stream) {
+    return backward_run(u, x, time, ids, mask, mask_is_ones, d_out, grads, numel, dx_out, dmask_out, B, H, W, first_part, last_part, false, stream);
+}
+
+int fc_unet_backward_accumulate(fc_unet* u, const float* x, const float* time, const int64_t* ids, const float* mask, int mask_is_ones,
+                                const float* d_out, float* grads, int64_t numel, float* dx_out, float* dmask_out, int B, int H, int W,
+                                int first_part, int last_part, void* stream) {
+    return backward_run(u, x, time, ids, mask, mask_is_ones, d_out, grads, numel, dx_out, dmask_out, B, H, W, first_part, last_part, true, stream);
 }
 
 int fc_unet_backward(fc_unet* u, const float* x, const float* time, const int64_t* ids, const float* d_out, float* grads, int64_t numel,
@@ -838,6 +853,24 @@ int fc_flow_prepare(const float* source_dev, const float* target_dev, const int6
     if (warp_s < 0.f || warp_s > 1.5f) return fail(FC_E_ARG, "fc_flow_prepare: warp parameter s out of bounds (sampling.py:27)");
     return flow_prepare_launch(source_dev, target_dev, pairing_dev, u_dev, t_eps, warp_s, t_scale, class_ids_dev, n_classes, t_out_dev, time_out_dev,
                                x_out_dev, v_out_dev, id_flag_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
+}
+
+int fc_flow_prepare_rows(const float* source_dev, const float* target_dev, const int64_t* pairing_dev, const float* u_dev, float t_eps, float warp_s,
+                         float t_scale, const int64_t* class_ids_dev, int n_classes, float* t_out_dev, float* time_out_dev, float* x_out_dev,
+                         float* v_out_dev, int* id_flag_dev, int batch, int first_row, int target_rows, int64_t per_sample, void* stream) {
+    if (!source_dev || !target_dev || !u_dev || !t_out_dev || !time_out_dev || !x_out_dev || !v_out_dev || batch < 1 || per_sample < 1)
+        return fail(FC_E_ARG, "fc_flow_prepare_rows: null argument");
+    if (first_row < 0 || target_rows < 1 || (int64_t)first_row + batch > target_rows)
+        return fail(FC_E_ARG, "fc_flow_prepare_rows: rows [first_row, first_row + batch) must lie inside [0, target_rows)");
+    if (warp_s < 0.f || warp_s > 1.5f) return fail(FC_E_ARG, "fc_flow_prepare_rows: warp parameter s out of bounds (sampling.py:27)");
+    return flow_prepare_launch(source_dev, target_dev, pairing_dev, u_dev, t_eps, warp_s, t_scale, class_ids_dev, n_classes, t_out_dev, time_out_dev,
+                               x_out_dev, v_out_dev, id_flag_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream), target_rows, first_row);
+}
+
+int fc_mse_loss_grad_scaled(const float* v_dev, const float* target_dev, float* dv_out_dev, float* loss_acc_dev, float* ws256_dev, int64_t numel,
+                            float scale, void* stream) {
+    if (!v_dev || !target_dev || !loss_acc_dev || !ws256_dev || numel < 1) return fail(FC_E_ARG, "fc_mse_loss_grad_scaled: null argument");
+    return mse_loss_grad_scaled_launch(v_dev, target_dev, dv_out_dev, loss_acc_dev, ws256_dev, (size_t)numel, scale, static_cast<hipStream_t>(stream));
 }
 
 int fc_mse_loss_grad(const float* v_dev, const float* target_dev, float* dv_out_dev, float* loss_out_dev, float* ws256_dev, int64_t numel,

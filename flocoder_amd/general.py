@@ -4,6 +4,7 @@ list are composed the way Hydra composes them for this repo's layout).  Boundary
 """
 from __future__ import annotations
 
+import math
 import os
 import sys
 from pathlib import Path
@@ -153,6 +154,58 @@ def ldcfg(config, key, default=None, supply_defaults=False, debug=False, verbose
     if verbose:
         print(f'lcfg: {key} := {answer}')
     return answer
+
+
+class CosineAnnealingWarmRestartsDecay:
+    """The learning-rate schedule train_flow.py steps once per epoch (train_flow.py:319,456): cosine annealing with warm restarts
+    (``torch.optim.lr_scheduler.CosineAnnealingWarmRestarts``' documented formula) whose base learning rate shrinks by ``decay`` at
+    every restart.  No torch optimiser behind it: ``targets`` is an object with ``set_lr(lr)`` (a ``FlowTrainer``; its ``lr`` is the
+    base unless ``base_lr`` is given) or a list of ``(setter, base_lr)`` pairs, each driven from its own base -- two parameter
+    groups keep their ratio.
+
+    Epoch 0 runs at the base (set at construction); every ``step()`` moves one epoch on.  Inside a cycle of ``T_i`` epochs
+    ``lr = eta_min + (base - eta_min) (1 + cos(pi T_cur / T_i)) / 2``; when ``T_cur`` reaches ``T_i`` it restarts at 0 and
+    ``T_i *= T_mult``.  The base is multiplied by ``decay`` on the step that ends a cycle (``T_cur + 1 == T_i``), before that update,
+    so the first epoch of cycle k runs at ``decay**k * base``.  ``decay=1`` is torch's schedule."""
+
+    def __init__(self, targets, T_0: int, T_mult: int = 1, eta_min: float = 0.0, decay: float = 1.0, base_lr: Optional[float] = None):
+        if T_0 <= 0 or int(T_0) != T_0:
+            raise ValueError(f"Expected positive integer T_0, but got {T_0}")
+        if T_mult < 1 or int(T_mult) != T_mult:
+            raise ValueError(f"Expected integer T_mult >= 1, but got {T_mult}")
+        if hasattr(targets, "set_lr"):
+            targets = [(targets.set_lr, float(targets.lr if base_lr is None else base_lr))]
+        self.setters = [fn for fn, _ in targets]
+        self.base_lrs = [float(b) for _, b in targets]
+        self.T_0, self.T_i, self.T_mult, self.T_cur = int(T_0), int(T_0), int(T_mult), 0
+        self.eta_min, self.decay, self.last_epoch = float(eta_min), float(decay), 0
+        self._set()
+
+    def _set(self) -> None:
+        self._last_lr = [self.eta_min + (b - self.eta_min) * (1 + math.cos(math.pi * self.T_cur / self.T_i)) / 2 for b in self.base_lrs]
+        for fn, lr in zip(self.setters, self._last_lr):
+            fn(lr)
+
+    def step(self) -> None:
+        if self.T_cur + 1 == self.T_i:
+            self.base_lrs = [b * self.decay for b in self.base_lrs]
+        self.last_epoch += 1
+        self.T_cur += 1
+        if self.T_cur >= self.T_i:
+            self.T_cur -= self.T_i
+            self.T_i *= self.T_mult
+        self._set()
+
+    def get_last_lr(self) -> List[float]:
+        return list(self._last_lr)
+
+    def state_dict(self) -> dict:
+        return {k: getattr(self, k) for k in ("base_lrs", "T_0", "T_i", "T_mult", "T_cur", "eta_min", "decay", "last_epoch")}
+
+    def load_state_dict(self, sd: dict) -> None:
+        for k, v in sd.items():
+            setattr(self, k, list(v) if k == "base_lrs" else v)
+        self._set()
 
 
 def keep_recent_files(keep=5, directory='checkpoints', pattern='*.pt'):

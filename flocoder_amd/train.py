@@ -6,7 +6,11 @@ Two ways in:
 * ``FlowTrainer.step(source, target, cond)`` -- the whole step on the device through the C ABI: interpolation (``fc_flow_interp``),
   U-Net forward + backward (``fc_unet_forward`` / ``fc_unet_backward``), MSE loss and its gradient (``fc_mse_loss_grad``),
   gradient-norm clipping (``fc_grad_clip_coef``), Adam and the EMA in one pass over flat vectors (``fc_adam_ema_step``).  No host
-  synchronisation inside a step; data-parallel ranks add one all-reduce of the flat gradient vector (RCCL).
+  synchronisation inside a step; data-parallel ranks add one all-reduce of the flat gradient vector (RCCL).  ``micro_batch=m`` takes
+  the same ONE optimiser step over a batch larger than the activation arena holds: chunks of ``m`` rows, each prepare -> forward ->
+  scaled loss -> backward ADDED into the flat gradient vector (``fc_unet_backward_accumulate``), then one clip / Adam / EMA
+  (``accumulate`` / ``apply`` / ``discard`` are the same for loaders that already yield micro-batches).  ``eval_loss`` is the
+  validation loss (train_flow.py:407-418), ``set_lr`` what a schedule drives (``general.CosineAnnealingWarmRestartsDecay``).
 * the reference's own loop shape -- ``loss_fn(model(x, t*999, cond), v).backward(); clip_grad_norm_; optimizer.step(); ema.update()`` --
   works unchanged too: ``Unet.forward`` joins autograd through the same native backward, ``EMA`` below mirrors the reference class
   (kept on the device instead of round-tripping through host memory every step, train_flow.py:52-54).
@@ -141,6 +145,9 @@ class FlowTrainer:
         self._id_flag = torch.zeros(1, dtype=torch.int32, device=device)     # sticky: bit 0 = a class id, bit 1 = a pairing entry out of range (step prologue)
         self._id_flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()   # its mirror, refreshed asynchronously behind every prologue
         self._ws = torch.zeros(256, dtype=torch.float32, device=device)
+        self._acc = None                                                      # gradient accumulation in progress (``accumulate``): rows so far, presences
+        self._acc_loss = torch.zeros(1, dtype=torch.float32, device=device)   # ... and the running loss of its micro-batches
+        self._eval_scal = torch.zeros(1, dtype=torch.float32, device=device)  # ``eval_loss``'s own running scalar: a validation pass leaves ``_scal`` alone
         self.pg = process_group
         dist = torch.distributed
         self.distributed = (dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1) if distributed is None else distributed
@@ -176,6 +183,22 @@ class FlowTrainer:
             self._id_flag_host.copy_(self._id_flag, non_blocking=True)     # the host looks at it when it next passes by: no sync
         return t, time, x, v
 
+    def prepare_rows(self, source, target, u, cls=None, pairing=None, first_row: int = 0):
+        """``prepare`` for a micro-batch (``fc_flow_prepare_rows``): ``source`` / ``u`` / ``cls`` / ``pairing`` hold the micro-batch's rows,
+        ``target`` the WHOLE step's target; the rows are rows [first_row, first_row + b) of that step and ``pairing`` entries index the
+        whole target (the range check of the sticky flag uses its row count)."""
+        dev, bsz = self.device, source.shape[0]
+        t, time = torch.empty(bsz, device=dev), torch.empty(bsz, device=dev)
+        x, v = torch.empty_like(source), torch.empty_like(source)
+        ncls = self.model._cfg.n_classes if cls is not None else 0
+        check = cls is not None or pairing is not None
+        B.check(B.lib().fc_flow_prepare_rows(B.ptr(source), B.ptr(target), B.ptr(pairing), B.ptr(u), self.t_eps, 0.5, self.t_scale, B.ptr(cls), ncls,
+                                             B.ptr(t), B.ptr(time), B.ptr(x), B.ptr(v), self._id_flag.data_ptr() if check else None, bsz,
+                                             int(first_row), target.shape[0], source[0].numel(), B.current_stream(dev)))
+        if check:
+            self._id_flag_host.copy_(self._id_flag, non_blocking=True)
+        return t, time, x, v
+
     def check_class_ids(self) -> None:
         """Raise IndexError if any step so far was given a class id outside [0, n_classes) (nn.Embedding raises for those, unet.py:205)
         or a pairing entry outside [0, batch) (``target[ot_indices]`` raises, train_flow.py:350).  The optimiser launches are guarded
@@ -207,19 +230,26 @@ class FlowTrainer:
         dv = torch.empty_like(v)
         B.check(lib.fc_mse_loss_grad(B.ptr(v), B.ptr(v_target), B.ptr(dv), self._scal.data_ptr(), self._ws.data_ptr(), v.numel(), st))
         self._drain_pending()      # a collective an aborted step left in flight still writes self.grads: wait before the backward zeroes it
+        self._backward(x, time, cls, dv, mask, overlap, tail)
+        return self._scal[0], v
+
+    def _backward(self, x, time, cls, dv, mask, overlap: bool, tail: Optional[torch.Tensor], accumulate: bool = False) -> None:
+        """The backward of ``loss_and_grads`` into ``self.grads``, in its two overlapped parts when asked to; with ``accumulate`` the
+        gradients are added to what the vector holds (``fc_unet_backward_accumulate``) -- after part 0 of a step's LAST micro-batch the
+        early bucket is as final as after part 0 of a one-batch step."""
+        m = self.model
         nb, split = m.grad_buckets() if overlap else (1, 0)
         if overlap and nb == 2 and 0 < split < self.grads.numel() and all(hi <= split for _, hi in self._groups.values()):
-            m.backward_native(x, time, cls, dv, self.grads, mask=mask, parts=(0, 0))
+            m.backward_native(x, time, cls, dv, self.grads, mask=mask, parts=(0, 0), accumulate=accumulate)
             n, hi = self.grads.numel(), self.grads.numel()
             if tail is not None:                # the agreement flags ride behind the late layers' gradients: one collective fewer per step
                 self._gbuf[n:n + tail.numel()].copy_(tail)
                 hi = n + tail.numel()
             self._pending = (torch.distributed.all_reduce(self._gbuf[split:hi], op=torch.distributed.ReduceOp.SUM, group=self.pg, async_op=True), split,
                              tail is not None)
-            m.backward_native(x, time, cls, dv, self.grads, mask=mask, parts=(1, 1))
+            m.backward_native(x, time, cls, dv, self.grads, mask=mask, parts=(1, 1), accumulate=accumulate)
         else:
-            m.backward_native(x, time, cls, dv, self.grads, mask=mask)
-        return self._scal[0], v
+            m.backward_native(x, time, cls, dv, self.grads, mask=mask, accumulate=accumulate)
 
     def _drain_pending(self) -> None:
         """Wait for an early-bucket all-reduce that was started but never finished (a step that raised between ``loss_and_grads`` and
@@ -334,9 +364,178 @@ class FlowTrainer:
         return {k: bool(v) for k, v in zip(keys, vals)}
 
     # ---- the step -------------------------------------------------------------------------------------------------
-    def step(self, source, target, cond=None, u: Optional[torch.Tensor] = None, pairing: Optional[torch.Tensor] = None):
+    def _step_inputs(self, source, target, cond, u, pairing):
+        """What ``step`` / ``accumulate`` / ``eval_loss`` check of their inputs -> (source, target, u, class ids | None, mask | None,
+        pairing | None) on the device; ``target`` may carry more rows than ``source`` (a micro-batch against the whole step's target)."""
+        dev = self.device
+        source = source.to(dev, torch.float32).contiguous()
+        target = target.to(dev, torch.float32).contiguous()
+        bsz = source.shape[0]
+        if u is None:
+            u = torch.rand(bsz, device=dev)
+        u = u.to(dev, torch.float32).contiguous()
+        cls = cond.get('class_cond') if isinstance(cond, dict) else None
+        mask = cond.get('mask_cond') if isinstance(cond, dict) else None
+        if mask is not None and not self.model._cfg.mask_cond:
+            mask = None
+        if mask is not None:
+            mask = mask.detach().to(dev, torch.float32).contiguous()
+        if cls is not None and not self.model.class_condition:
+            cls = None
+        if cls is not None:
+            cls = cls.to(dev, torch.int64).contiguous()
+            if cls.shape != (bsz,):
+                raise ValueError("class_cond must have shape [batch]")
+        if pairing is not None:
+            pairing = pairing.to(dev, torch.int64).contiguous()
+            if pairing.shape != (bsz,):
+                raise ValueError(f"pairing must have shape [batch] = ({bsz},), got {tuple(pairing.shape)}")
+        if u.shape != (bsz,):
+            raise ValueError("u must have shape [batch]")
+        return source, target, u, cls, mask, pairing
+
+    # ---- one optimiser step over micro-batches ----------------------------------------------------------------------------
+    def accumulate(self, source, target, cond=None, u: Optional[torch.Tensor] = None, pairing: Optional[torch.Tensor] = None, *, of_total: int):
+        """One micro-batch of a step of ``of_total`` rows: prepare -> training forward -> loss and d(out) scaled by rows / of_total ->
+        backward ADDED into ``self.grads`` (the step's first micro-batch overwrites).  Nothing is clipped or stepped: ``apply`` does that
+        once, ``discard`` drops what has been accumulated.  ``target`` is either the micro-batch's own rows (``pairing`` then indexes
+        those) or the whole step's ``of_total`` rows -- the micro-batches are then consecutive row ranges of the step and ``pairing``
+        entries range over the whole target, as in ``step(..., micro_batch=m)``.  No collective runs here except on the micro-batch
+        that completes ``of_total`` rows, whose backward starts the early-bucket all-reduce of the accumulated vector."""
+        of_total = int(of_total)
+        if of_total < 1:
+            raise ValueError("of_total must be the number of rows of the whole optimiser step (>= 1)")
+        source, target, u, cls, mask, pairing = self._step_inputs(source, target, cond, u, pairing)
+        st = self._acc
+        if st is not None and st["total"] != of_total:
+            raise ValueError(f"accumulate: this step was started with of_total={st['total']}, got {of_total} (apply() or discard() first)")
+        rows, b = (st["rows"] if st is not None else 0), source.shape[0]
+        if target.shape[0] == b:
+            first_row = 0
+        elif target.shape[0] == of_total:
+            first_row = rows
+        else:
+            raise ValueError(f"target must hold the micro-batch's {b} rows or the whole step's {of_total}, got {target.shape[0]}")
+        if int(self._id_flag_host[0]):
+            self.check_class_ids()                                   # an earlier step's inputs were out of range: raise now
+        self._accumulate_rows(source, target, u, cls, mask, pairing, first_row, of_total)
+
+    def _accumulate_rows(self, source, target, u, cls, mask, pairing, first_row: int, total: int) -> None:
+        lib, dev = B.lib(), self.device
+        first = self._acc is None
+        if first:
+            self._acc = {"rows": 0, "total": total, "present": {k: False for k in self._groups}, "checked": False}
+            self._acc_loss.zero_()
+        st, b = self._acc, source.shape[0]
+        last = st["rows"] + b == total
+        t, time, x, v_target = self.prepare_rows(source, target, u, cls, pairing, first_row)
+        fused = mask is not None and not bool(torch.allclose(mask, torch.ones_like(mask)))    # unet.py:301 (host sync, as upstream)
+        for k, on in (("class", cls is not None), ("inject", mask is not None), ("fusion", fused)):
+            st["present"][k] = st["present"][k] or on            # a group is present in the step if ANY micro-batch gave it a gradient
+        st["checked"] = st["checked"] or cls is not None or pairing is not None
+        v = self.model._forward_native(x, time, cls, mask, train=True)
+        dv = torch.empty_like(v)
+        B.check(lib.fc_mse_loss_grad_scaled(B.ptr(v), B.ptr(v_target), B.ptr(dv), self._acc_loss.data_ptr(), self._ws.data_ptr(), v.numel(),
+                                            b / total, B.current_stream(dev)))
+        if first:
+            self._drain_pending()
+        overlap = last and self.distributed and self.overlap_comm            # the only micro-batch with a collective behind it
+        self._backward(x, time, cls, dv, mask, overlap, self._flag_tail(st["present"]) if overlap else None, accumulate=not first)
+        st["rows"] += b
+
+    def apply(self):
+        """Close the step ``accumulate`` built: (data-parallel: agreement on the OR of the micro-batches' presences, all-reduce of the
+        accumulated vector) -> one clip -> one Adam -> one EMA; Adam's step counters move once.  Returns the whole step's loss as a 0-d
+        device tensor (no host sync)."""
+        st = self._acc
+        if st is None:
+            raise RuntimeError("apply() without a preceding accumulate()")
+        if st["rows"] != st["total"]:
+            self.discard()
+            raise ValueError(f"apply: {st['rows']} rows were accumulated for a step declared with of_total={st['total']}; the step was discarded")
+        self._acc = None
+        loss = self._acc_loss[0].clone()
+        if st["checked"] and (self.step_main & 63) == 0 and not self.distributed:
+            self.check_class_ids()
+        mine = st["present"]
+        rode = self._pending is not None and len(self._pending) > 2 and self._pending[2]
+        present = self._agree_from_tail(mine) if rode else self._agree(mine)
+        if self.distributed:
+            self.finish_gradients()
+        self.optimizer_step(has_class_grads=present["class"], has_mask_grads=present["inject"], has_fusion_grads=present["fusion"])
+        return loss
+
+    def discard(self) -> None:
+        """Drop the micro-batches accumulated since the last ``apply``: no update; the next ``accumulate`` starts a new step."""
+        self._drain_pending()
+        self._acc = None
+
+    def _chunks(self, n: int, micro_batch: int):
+        if int(micro_batch) != micro_batch or micro_batch < 1:
+            raise ValueError(f"micro_batch must be a positive row count, got {micro_batch!r}")
+        m = int(micro_batch)
+        return [(a, min(a + m, n)) for a in range(0, n, m)]
+
+    def eval_loss(self, source, target, cond=None, u: Optional[torch.Tensor] = None, pairing: Optional[torch.Tensor] = None, *,
+                  micro_batch: Optional[int] = None):
+        """The validation loss of train_flow.py:407-418: ``step``'s prologue, an inference-mode forward and the MSE reduction alone (no
+        d(out), no backward), over chunks of ``micro_batch`` rows.  Returns a 0-d device tensor.  Gradients, Adam / EMA state, the step
+        counters and ``model.training`` are left as found, and so is the reservation: chunks never exceed the rows the model has
+        already reserved, so the training step behind it runs the plan -- and gives the bits -- it would have without this call."""
+        lib, dev = B.lib(), self.device
+        source, target, u, cls, mask, pairing = self._step_inputs(source, target, cond, u, pairing)
+        n = source.shape[0]
+        if target.shape[0] != n:
+            raise ValueError("eval_loss: source and target must have the same number of rows")
+        rows = n if micro_batch is None else micro_batch
+        spans = self._chunks(n, rows)
+        reserved = self.model.reserved_rows()
+        if 0 < reserved < spans[0][1] - spans[0][0]:
+            spans = self._chunks(n, reserved)
+        self._eval_scal.zero_()
+        for a, b in spans:
+            mk = mask[a:b] if mask is not None else None
+            ck = cls[a:b] if cls is not None else None
+            _, time, x, v_target = self.prepare_rows(source[a:b], target, u[a:b], ck, pairing[a:b] if pairing is not None else None, a)
+            v = self.model._forward_native(x, time, ck, mk, train=False)
+            B.check(lib.fc_mse_loss_grad_scaled(B.ptr(v), B.ptr(v_target), None, self._eval_scal.data_ptr(), self._ws.data_ptr(), v.numel(),
+                                                (b - a) / n, B.current_stream(dev)))
+        return self._eval_scal[0].clone()
+
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the next step (a schedule calls this once per epoch).  An attached MaskEncoder's group follows at the
+        ratio it was attached with (``lr_scale``, train_flow.py:313-318)."""
+        self.lr = float(lr)
+        if getattr(self, "me", None) is not None:
+            self.me_lr = self.lr * self.me_lr_scale
+
+    def _step_micro(self, source, target, cond, u, pairing, micro_batch):
+        source, target, u, cls, mask, pairing = self._step_inputs(source, target, cond, u, pairing)
+        n = target.shape[0]
+        if source.shape[0] != n:
+            raise ValueError("step: source and target must have the same number of rows")
+        spans = self._chunks(n, micro_batch)
+        if self._acc is not None:
+            raise RuntimeError("step: micro-batches of an unfinished accumulate() are pending (apply() or discard() first)")
+        if int(self._id_flag_host[0]):
+            self.check_class_ids()
+        try:
+            for a, b in spans:
+                self._accumulate_rows(source[a:b], target, u[a:b], cls[a:b] if cls is not None else None, mask[a:b] if mask is not None else None,
+                                      pairing[a:b] if pairing is not None else None, a, n)
+            return self.apply()
+        except BaseException:
+            self.discard()
+            raise
+
+    def step(self, source, target, cond=None, u: Optional[torch.Tensor] = None, pairing: Optional[torch.Tensor] = None, *,
+             micro_batch: Optional[int] = None):
         """train_flow.py:346-397 for one batch: returns the loss as a 0-d device tensor (no host sync).  ``pairing`` (int64 [B], e.g.
-        from ``compute_ot_pairing``) trains against ``target[pairing]`` without materialising the gather (train_flow.py:350)."""
+        from ``compute_ot_pairing``) trains against ``target[pairing]`` without materialising the gather (train_flow.py:350).
+        ``micro_batch=m``: the same optimiser step with the rows processed in consecutive chunks of ``m`` (the last may be smaller) whose
+        gradients are accumulated -- only ``m`` rows are ever reserved; ``pairing`` still ranges over the whole batch."""
+        if micro_batch is not None:
+            return self._step_micro(source, target, cond, u, pairing, micro_batch)
         dev = self.device
         source = source.to(dev, torch.float32).contiguous()
         target = target.to(dev, torch.float32).contiguous()
@@ -387,6 +586,7 @@ class FlowTrainer:
         n = me._flat_numel
         z = lambda: torch.zeros(n, dtype=torch.float32, device=self.device)
         self.me, self.me_lr, self.me_max_norm = me, self.lr * lr_scale, max_norm
+        self.me_lr_scale = lr_scale                           # set_lr keeps the two groups at this ratio
         self.me_params, self.me_grads, self.me_m, self.me_v = z(), z(), z(), z()
         with torch.no_grad():
             for name, shape, off in me._table:
@@ -402,7 +602,8 @@ class FlowTrainer:
         """One inpainting training step entirely on the device (batch_to_data's mask branch + train_flow.py:346-397):
         mask = MaskEncoder(mask_pixels); source = blend(source_latents, mask, noise); flow loss through the mask-conditioned U-Net;
         + MSE(MaskEncoder(1), 1) + MSE(MaskEncoder(0), 0); backward into both networks (the encoder is reached through the U-Net's
-        mask input AND through the blended source); joint clip at 1.0, the encoder's own at 0.5, Adam (lr, lr x 0.1), EMA of both."""
+        mask input AND through the blended source); joint clip at 1.0, the encoder's own at 0.5, Adam (lr, lr x 0.1), EMA of both.
+        One batch per optimiser step: the encoder's group takes no part in gradient accumulation (``step(..., micro_batch=m)``)."""
         lib, dev, st = B.lib(), self.device, B.current_stream(self.device)
         me = self.me
         f = lambda t_: t_.to(dev, torch.float32).contiguous()

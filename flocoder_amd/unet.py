@@ -174,6 +174,14 @@ class Unet(NativeModule):
         """Counter of writes to the library's activation arena (fc_unet_arena_serial)."""
         return int(B.lib().fc_unet_arena_serial(self._handle)) if self._handle else 0
 
+    def reserved_rows(self) -> int:
+        """Rows of the current launch plan / activation arena (``fc_unet_reserved``; 0 before the first reservation)."""
+        if not self._handle:
+            return 0
+        rows, h, w = C.c_int(0), C.c_int(0), C.c_int(0)
+        B.check(B.lib().fc_unet_reserved(self._handle, C.byref(rows), C.byref(h), C.byref(w)))
+        return int(rows.value)
+
     def reserve(self, rows: int, height: int, width: int, device=None) -> None:
         """Build the launch plan / activation arena for up to `rows` U-Net rows (a CFG sampler needs 2x batch)."""
         device = torch.device(device) if device is not None else next(self.parameters()).device
@@ -327,24 +335,28 @@ class Unet(NativeModule):
         return int(n), int(off.value)
 
     def backward_native(self, x, time, cls, d_out, grads: Optional[torch.Tensor] = None, mask=None, want_dx=False, want_dmask=False,
-                        parts: Tuple[int, int] = (0, 1), dx=None, dm=None):
+                        parts: Tuple[int, int] = (0, 1), dx=None, dm=None, accumulate: bool = False):
         """Parameter gradients of the LAST training forward (same x / time / class ids / mask) for d(out) = ``d_out``: a flat fp32
         vector in the library's table layout (``grad_views`` splits it), plus d(x) / d(mask) on request.  Returns
         ``(flat, dx | None, dmask | None)``.  train_flow.py:371 loss.backward().  ``parts`` = (first, last) of the two halves of the
         backward plan (``fc_unet_backward_parts``): (0, 0) stops behind mid_block1 with the late-layer gradients final, (1, 1) runs the
-        rest -- a data-parallel trainer all-reduces the first bucket in between."""
+        rest -- a data-parallel trainer all-reduces the first bucket in between.  ``accumulate`` (``fc_unet_backward_accumulate``): the
+        gradients are ADDED to what ``grads`` holds and every element without a gradient in this call is left untouched; d(x) / d(mask)
+        are overwritten as before."""
         dev = x.device
         bsz, _, h, w = x.shape
         if grads is None:
+            if accumulate:
+                raise ValueError("backward_native(accumulate=True) needs the gradient vector to add to")
             grads = torch.empty(self._flat_numel, dtype=torch.float32, device=dev)
         ones = int(torch.allclose(mask, torch.ones_like(mask))) if mask is not None else 0
         if dx is None:
             dx = torch.empty_like(x) if want_dx else None
         if dm is None:
             dm = torch.empty_like(x) if (want_dmask and mask is not None) else None
-        B.check(B.lib().fc_unet_backward_parts(self._native(dev), B.ptr(x), B.ptr(time), B.ptr(cls), B.ptr(mask), ones, B.ptr(d_out.contiguous()),
-                                               B.ptr(grads), grads.numel(), B.ptr(dx), B.ptr(dm), bsz, h, w, int(parts[0]), int(parts[1]),
-                                               B.current_stream(dev)))
+        entry = B.lib().fc_unet_backward_accumulate if accumulate else B.lib().fc_unet_backward_parts
+        B.check(entry(self._native(dev), B.ptr(x), B.ptr(time), B.ptr(cls), B.ptr(mask), ones, B.ptr(d_out.contiguous()),
+                      B.ptr(grads), grads.numel(), B.ptr(dx), B.ptr(dm), bsz, h, w, int(parts[0]), int(parts[1]), B.current_stream(dev)))
         return grads, dx, dm
 
     def vjp_x(self, x, time, cls, d_out, mask=None) -> torch.Tensor:

@@ -320,6 +320,16 @@ int fc_unet_backward_ex(fc_unet* u, const float* x_dev, const float* time_dev, c
 int fc_unet_backward_parts(fc_unet* u, const float* x_dev, const float* time_dev, const int64_t* class_ids_dev, const float* mask_dev,
                            int mask_is_ones, const float* d_out_dev, float* grads_flat_dev, int64_t numel, float* dx_out_dev,
                            float* dmask_out_dev, int batch, int height, int width, int first_part, int last_part, void* stream);
+/* Gradient accumulation: fc_unet_backward_parts with grads_flat_dev[i] += g[i] for every parameter that receives a gradient in this call
+ * (g: what fc_unet_backward_parts would have written, by the same arithmetic) and every other element left untouched -- padding, the
+ * class_cond_mlp.* range when class_ids_dev == NULL, the mask branches' ranges when they do not run.  Nothing is zeroed; the caller starts
+ * a sum with an overwriting backward or a vector it cleared.  dx_out_dev / dmask_out_dev are overwritten as before.  Every element has
+ * one writer and the adds follow the stream's order: the same inputs give the same bits run to run.  One optimiser step over more rows
+ * than the arena holds = one training forward + one call per micro-batch (d_out scaled by the micro-batch's share of the step,
+ * fc_mse_loss_grad_scaled), then fc_grad_clip_coef / fc_adam_ema_step once. */
+int fc_unet_backward_accumulate(fc_unet* u, const float* x_dev, const float* time_dev, const int64_t* class_ids_dev, const float* mask_dev,
+                                int mask_is_ones, const float* d_out_dev, float* grads_flat_dev, int64_t numel, float* dx_out_dev,
+                                float* dmask_out_dev, int batch, int height, int width, int first_part, int last_part, void* stream);
 /* Ask for (1) / do without (0, default) the two-bucket form of the backward plan; takes effect at the next fc_unet_train_reserve.  One
  * process gains nothing from it (the deferred table launches run twice); a data-parallel trainer sets it once. */
 int fc_unet_set_grad_buckets(fc_unet* u, int on);
@@ -364,6 +374,18 @@ int fc_flow_interp(const float* source_dev, const float* target_dev, const float
 int fc_flow_prepare(const float* source_dev, const float* target_dev, const int64_t* pairing_dev, const float* u_dev, float t_eps, float warp_s,
                     float t_scale, const int64_t* class_ids_dev, int n_classes, float* t_out_dev, float* time_out_dev, float* x_out_dev,
                     float* v_out_dev, int* id_flag_dev, int batch, int64_t per_sample, void* stream);
+/* fc_flow_prepare for rows [first_row, first_row + batch) of a step of target_rows rows (a micro-batch): source_dev, u_dev, class_ids_dev,
+ * pairing_dev and the four outputs hold the micro-batch's `batch` rows; target_dev is the WHOLE step's target [target_rows][per_sample],
+ * and pairing entries index it: they range over [0, target_rows), bit 1 of *id_flag_dev reports one outside.  Without a pairing row b
+ * reads target row first_row + b.  first_row = 0, target_rows = batch is fc_flow_prepare. */
+int fc_flow_prepare_rows(const float* source_dev, const float* target_dev, const int64_t* pairing_dev, const float* u_dev, float t_eps, float warp_s,
+                         float t_scale, const int64_t* class_ids_dev, int n_classes, float* t_out_dev, float* time_out_dev, float* x_out_dev,
+                         float* v_out_dev, int* id_flag_dev, int batch, int first_row, int target_rows, int64_t per_sample, void* stream);
+/* A micro-batch's share of a step's MSELoss: dv_out_dev = scale * 2 (v - v*) / numel when not NULL, and *loss_acc_dev += scale *
+ * mean((v - v*)^2) (the caller clears the scalar before the first micro-batch).  With scale = rows of the micro-batch / rows of the step
+ * the sum over the micro-batches is the whole batch's loss and the accumulated backward its gradient.  ws: 256 floats. */
+int fc_mse_loss_grad_scaled(const float* v_dev, const float* target_dev, float* dv_out_dev, float* loss_acc_dev, float* ws256_dev, int64_t numel,
+                            float scale, void* stream);
 /* loss = mean((v - v*)^2) (train_flow.py:359) and, when dv_out_dev != NULL, its gradient 2 (v - v*) / numel.  ws: 256 floats. */
 int fc_mse_loss_grad(const float* v_dev, const float* target_dev, float* dv_out_dev, float* loss_out_dev, float* ws256_dev, int64_t numel,
                      void* stream);
