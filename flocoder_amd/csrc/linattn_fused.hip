@@ -271,68 +271,73 @@ __global__ void __launch_bounds__(256) la_apply_kernel(const LaArgs a, int T, fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Fast path, C <= 64 and C % 8 == 0 (every n >= 256 level of the dim 16 / 32 models): the K loop is a single chunk, so all
-// weights stay in LDS for the life of the workgroup, the next 32-row tile of x travels HBM -> registers while the current one
-// is on the matrix pipe, and every LDS tile is private to its wave -- no workgroup barrier inside the loops (a wave's LDS
-// operations execute in order).
-template <int NQ>   // NQ = C / 8 float4 loads per lane per 32-row tile
-__device__ __forceinline__ void fetch_x(const LaArgs& a, int b, int r0, int lane, float4 (&pre)[NQ]) {
-    constexpr int q4 = NQ * 2;
+// Fast path, C in {8, 16, 32, 64} (every n >= 256 level of the dim 16 / 32 models).  The dependent MFMA phases of both kernels hand
+// their results on IN REGISTERS: a 32x32 accumulator (lane = column, registers = rows acc_row(r, half)) is already a legal B operand
+// of the next product (B[k][n]: lane = n, k chosen by half) once that product walks its reduction index in the order
+// k_r = acc_row(r, half) -- and a legal A operand of a transposed product in the same way.  The reduction order is free as long as the
+// other operand uses the same permutation, so no accumulator is ever stored to LDS and read back transposed.  The projections walk the
+// input channels in the order c_s = s + half * C/2: a lane then needs a contiguous half row of x, which it reads straight from global
+// memory (16-byte loads, normalised in registers) -- no x tile in LDS either.
+//
+// a lane's half row of x[b][r0 + l31]: channels [half * C/2, half * C/2 + C/2), NQ = C / 8 float4 loads; rows >= n are zero
+template <int NQ>
+__device__ __forceinline__ void fetch_xh(const LaArgs& a, int b, int r0, int lane, float4 (&pre)[NQ]) {
+    const int nn = r0 + (lane & 31);
+    const float* p = a.x + ((size_t)b * a.n + nn) * (NQ * 8) + (lane >> 5) * (NQ * 4);
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
-        const int idx = lane + 64 * j, row = idx / q4, q = idx - row * q4, nn = r0 + row;
         pre[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (nn < a.n) pre[j] = *reinterpret_cast<const float4*>(a.x + ((size_t)b * a.n + nn) * (NQ * 8) + 4 * q);
+        if (nn < a.n) pre[j] = *reinterpret_cast<const float4*>(p + 4 * j);
     }
 }
+// GroupNorm of the half row: xn[s] = channel c_s of the lane's position (Ab / Bb: the norm's scale and shift per channel, LDS)
 template <int NQ>
-__device__ __forceinline__ void store_x(const LaArgs& a, const float* Ab, const float* Bb, float* xw, int XS, int r0, int lane, const float4 (&pre)[NQ]) {
-    constexpr int q4 = NQ * 2;
+__device__ __forceinline__ void norm_xh(const LaArgs& a, const float* Ab, const float* Bb, int r0, int lane, const float4 (&pre)[NQ], float (&xn)[NQ * 4]) {
+    const bool in = r0 + (lane & 31) < a.n;
+    const float* ap = Ab + (lane >> 5) * (NQ * 4);
+    const float* bp = Bb + (lane >> 5) * (NQ * 4);
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
-        const int idx = lane + 64 * j, row = idx / q4, q = idx - row * q4, c = 4 * q;
+        const float4 A = *reinterpret_cast<const float4*>(ap + 4 * j), Bv = *reinterpret_cast<const float4*>(bp + 4 * j);
         float4 v = pre[j];
-        if (r0 + row < a.n) { v.x = Ab[c] * v.x + Bb[c]; v.y = Ab[c + 1] * v.y + Bb[c + 1]; v.z = Ab[c + 2] * v.z + Bb[c + 2]; v.w = Ab[c + 3] * v.w + Bb[c + 3]; }
-        float* d = xw + row * XS + c;
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        if (in) { v.x = A.x * v.x + Bv.x; v.y = A.y * v.y + Bv.y; v.z = A.z * v.z + Bv.z; v.w = A.w * v.w + Bv.w; }
+        xn[4 * j] = v.x; xn[4 * j + 1] = v.y; xn[4 * j + 2] = v.z; xn[4 * j + 3] = v.w;
     }
 }
 
-// NW = waves per workgroup (4 or 8).  Eight (round 4) where a (sample, head) has at least eight 32-position blocks: the workgroup is the
-// only one on its CU, so with four waves every SIMD held ONE wave and nothing covered its LDS round trips and softmax arithmetic between
-// the matrix phases; with eight, two waves share a SIMD's matrix pipe.  The split over positions stays inside the workgroup (the merge of
-// the partial (max, sum, context) triples is the same LDS pass over NW instead of four entries).
+// NW = waves per workgroup (4 or 8).  Eight where a (sample, head) has at least eight 32-position blocks: the workgroup is the only one
+// on its CU, so with four waves every SIMD held ONE wave and nothing covered its softmax arithmetic between the matrix phases; with
+// eight, two waves share a SIMD's matrix pipe.  The split over positions stays inside the workgroup (the merge of the partial
+// (max, sum, context) triples is one LDS pass over NW entries).
+//
+// Per 32-position tile: K = X Wk and V = X Wv (lane = channel, registers = positions; the lane's C weights live in registers for the
+// life of the kernel), E = exp(K - m) in K's registers, then the context TRANSPOSED, ctxT[e][d] += sum_pos V[pos][e] E[pos][d], with
+// A = V's and B = E's accumulator as they sit.  Transposed, the softmax channel d is the LANE of the context accumulator, so the online
+// rescale by exp(m_old - m_new) is one multiply by a value the lane already holds.  Nothing in the loop touches LDS but Ab / Bb.
 template <int NQ, int NW>
 __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    constexpr int C = NQ * 8, XS = C + 1, NT = 64 * NW;
+    constexpr int C = NQ * 8, H2 = C / 2, NT = 64 * NW;
     float* Ab = sm;
     float* Bb = Ab + C;
-    float* Wl = Bb + C;                 // [C][64]
-    float* xt = Wl + C * 64;            // [NW][32][XS]
-    float* Et = xt + NW * 32 * XS;      // [NW][32][PS]
-    float* Vt = Et + NW * 32 * PS;
-    float* sct = Vt + NW * 32 * PS;     // [NW][32]
+    float* Et = Bb + C;                 // [NW][32][PS]
+    float* sct = Et + NW * 32 * PS;     // [NW][32]
     float* mz = sct + NW * 32;          // [NW][2][32]
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
     const int nblk = (a.n + 31) >> 5;
     // every cold operand is requested before anything is waited for: first x tile, statistics, norm parameters, weights
     float4 pre[NQ];
-    if (wave < nblk) fetch_x<NQ>(a, b, wave * 32, lane, pre);
+    if (wave < nblk) fetch_xh<NQ>(a, b, wave * 32, lane, pre);
     PartPre pp;
     partials_request(a.xf, b, 0, pp);
     const float pg = tid < C ? a.xf.gamma[tid] : 0.f, pbt = tid < C ? a.xf.beta[tid] : 0.f;   // C <= 64 < 256 threads
-    // explicit registers: written as a load -> LDS store loop the compiler waits for every load before the next (ISA: vmcnt(0) per
-    // iteration) -- dependent cold round trips at the head of the kernel
-    constexpr int NWL = C * 64 / NT;
-    float wl[NWL];
+    float wk[H2], wv[H2];               // B operands: lane (column l31, half) supplies channel c_s of its k / v column
 #pragma unroll
-    for (int k = 0; k < NWL; ++k) {
-        const int i = tid + NT * k, c = i >> 6, j = i & 63;
-        wl[k] = a.wqkv[(size_t)c * LC3 + (j < 32 ? LHID + h * LDH + j : 2 * LHID + h * LDH + (j - 32))];
+    for (int s = 0; s < H2; ++s) {
+        const float* wr = a.wqkv + (size_t)(s + half * H2) * LC3 + h * LDH + l31;
+        wk[s] = wr[LHID];
+        wv[s] = wr[2 * LHID];
     }
-#pragma unroll
-    for (int k = 0; k < NWL; ++k) Wl[tid + NT * k] = wl[k];
     float mean, rstd;
     partials_finish(a.xf, b, 0, pp, &mean, &rstd);
     if (tid < C) {
@@ -341,28 +346,22 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
         Bb[tid] = pbt - mean * s;
     }
     __syncthreads();
-    float* xw = xt + wave * 32 * XS;
-    float* Ew = Et + wave * 32 * PS;
-    float* Vw = Vt + wave * 32 * PS;
-    float* scw = sct + wave * 32;
-    f32x16 cacc;
+    f32x16 cacc;                        // ctxT: lane = d, registers = e
 #pragma unroll
     for (int r = 0; r < 16; ++r) cacc[r] = 0.f;
     float m_run = -INFINITY, z_run = 0.f;
     for (int rb = wave; rb < nblk; rb += NW) {
         const int r0 = rb * 32;
-        store_x<NQ>(a, Ab, Bb, xw, XS, r0, lane, pre);
-        __builtin_amdgcn_wave_barrier();
-        if (rb + NW < nblk) fetch_x<NQ>(a, b, r0 + 32 * NW, lane, pre);
+        float xn[H2];
+        norm_xh<NQ>(a, Ab, Bb, r0, lane, pre, xn);
+        if (rb + NW < nblk) fetch_xh<NQ>(a, b, r0 + 32 * NW, lane, pre);
         f32x16 ak, av;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { ak[r] = 0.f; av[r] = 0.f; }
-#pragma unroll 4
-        for (int s = 0; s < (C >> 1); ++s) {
-            const float xa = xw[l31 * XS + 2 * s + half];
-            const float* wr = Wl + (2 * s + half) * 64 + l31;
-            ak = FC_MFMA(xa, wr[0], ak);
-            av = FC_MFMA(xa, wr[32], av);
+#pragma unroll
+        for (int s = 0; s < H2; ++s) {
+            ak = FC_MFMA(xn[s], wk[s], ak);
+            av = FC_MFMA(xn[s], wv[s], av);
         }
         float bm = -INFINITY;
 #pragma unroll
@@ -373,24 +372,18 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
         float zs = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = acc_row(r, half);
-            const float e = (r0 + row < a.n) ? __expf(ak[r] - m_new) : 0.f;
+            const float e = (r0 + acc_row(r, half) < a.n) ? __expf(ak[r] - m_new) : 0.f;
             zs += e;
-            Ew[row * PS + l31] = e;
-            Vw[row * PS + l31] = av[r];
+            ak[r] = e;
         }
         zs += __shfl_xor(zs, 32);
         z_run = z_run * sc + zs;
         m_run = m_new;
-        if (half == 0) scw[l31] = sc;
-        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cacc[r] *= scw[acc_row(r, half)];
-#pragma unroll 4
-        for (int s = 0; s < 16; ++s) cacc = FC_MFMA(Ew[(2 * s + half) * PS + l31], Vw[(2 * s + half) * PS + l31], cacc);
-        __builtin_amdgcn_wave_barrier();
+        for (int r = 0; r < 16; ++r) cacc[r] *= sc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cacc = FC_MFMA(av[r], ak[r], cacc);
     }
-    __syncthreads();
     if (half == 0) { mz[(wave * 2) * 32 + l31] = m_run; mz[(wave * 2 + 1) * 32 + l31] = z_run; }
     __syncthreads();
     if (tid < 32 * NW) {
@@ -402,11 +395,9 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
         sct[w * 32 + d] = __expf(mz[(w * 2) * 32 + d] - M) / Z;
     }
     __syncthreads();
+    const float fw = sct[wave * 32 + l31];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int d = acc_row(r, half);
-        Et[(wave * 32 + d) * PS + l31] = cacc[r] * sct[wave * 32 + d];
-    }
+    for (int r = 0; r < 16; ++r) Et[(wave * 32 + l31) * PS + acc_row(r, half)] = cacc[r] * fw;
     __syncthreads();
     for (int i = tid; i < LDH * LDH; i += NT) {
         const int d = i >> 5, e = i & 31;
@@ -416,41 +407,48 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
     }
 }
 
+// One 128-position tile per workgroup, 32 positions per wave, everything computed TRANSPOSED so that lane = position throughout:
+//   qT[d][pos]   = sum_c WqT[d][c] xnT[c][pos]        A = Wq, B = the lane's normalised half row          -> lane = pos, registers = d
+//   softmax over d: sixteen registers and one exchange with lane ^ 32, in place
+//   outT[e][pos] = sum_d ctxT[e][d] P[d][pos]         A = context, B = the softmax result as it sits        -> registers = e
+//   yT[c][pos]  += sum_e WoT[c][e] outT[e][pos]       A = Wout, B = the out accumulator as it sits          -> registers = c
+// one head at a time.  The A operands (the same for every wave) are staged once in LDS in the order each lane consumes them -- the
+// reduction index permuted to k_r = acc_row(r, half) -- with a row stride of (steps + 4) floats, so that four k-steps are one
+// conflict-free 16-byte read.  yT leaves a lane with 16 channels of its position in four runs of four: bias, statistics, the fused
+// close and the stores work on 16-byte channel quads.
+constexpr int AS = 20;                  // row stride of a 16-step A operand image
+__device__ __forceinline__ int acc_reg(int row) { return (row & 3) + 4 * (row >> 3); }   // acc_row(acc_reg(row), (row >> 2) & 1) == row
 template <int NQ, int CT>
 __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int T, float n_t) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    constexpr int C = NQ * 8, XS = C + 1 > PS ? C + 1 : PS, WO = CT * 32;
+    constexpr int C = NQ * 8, H2 = C / 2, SQ = H2 + 4, WO = CT * 32;
     float* Ab = sm;
     float* Bb = Ab + C;
-    float* Wq = Bb + C;                    // [C][128]
-    float* Wo = Wq + C * LHID;             // [128][WO]
-    float* ctxl = Wo + LHID * WO;          // [4][32][PS]
-    float* xt = ctxl + LHEADS * LDH * PS;  // [4][32][XS]: x tile, then the P / out tile of the head in flight
+    float* WqL = Bb + C;                          // [4 heads][half][32 d][SQ]: Wq[c_s][h * 32 + d] at s
+    float* ctxL = WqL + LHEADS * 64 * SQ;         // [4][half][32 e][AS]: ctx[h][acc_row(r, half)][e] at r
+    float* WoL = ctxL + LHEADS * 64 * AS;         // [4][CT][half][32 c][AS]: Wout[h * 32 + acc_row(r, half)][ct * 32 + c] at r
     __shared__ float red[4];
     __shared__ unsigned epoch_s;
     __shared__ float gv[2 * kPartPre];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const int ntiles = (a.n + 127) >> 7;
-    // the fused close (a.gran; one tile per workgroup, T <= kPartPre): this launch's epoch from the sample's arrival counter
+    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const int r0 = tile * 128 + wave * 32, nn = r0 + l31;
+    const bool in = nn < a.n;
+    // the fused close (a.gran; T <= kPartPre): this launch's epoch from the sample's arrival counter
     unsigned arrival = 0;
     if (a.gran && tid == 0) arrival = __hip_atomic_fetch_add(a.sync + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // every cold operand is requested before anything is waited for: x tile, statistics, norm parameters, to_out bias, weights, context
+    // every cold operand is requested before anything is waited for: x, statistics, norm parameters, weights, context
     float4 pre[NQ];
-    fetch_x<NQ>(a, b, blockIdx.x * 128 + wave * 32, lane, pre);
+    fetch_xh<NQ>(a, b, r0, lane, pre);
     PartPre pp;
     partials_request(a.xf, b, 0, pp);
     const float pg = tid < C ? a.xf.gamma[tid] : 0.f, pbt = tid < C ? a.xf.beta[tid] : 0.f;   // C <= 64 < 256 threads
-    float pbias[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) pbias[ct] = (ct * 32 + l31 < C && a.bout) ? a.bout[ct * 32 + l31] : 0.f;
-    // Wq, Wout and the context into explicit registers first, LDS after: as load -> store loops they were 4 + 8 + 16 dependent round
-    // trips (ISA: s_waitcnt vmcnt(0) inside each loop), about half of this kernel's 30 us inside a sampler step
+    // Wq, Wout and the context into explicit registers first, LDS after: as load -> store loops they are dependent round trips
     constexpr int NWO = WO / 2;
     float4 wq[NQ], cx[4];
     float wo[NWO];
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
-        const int i = tid + 256 * k, cc = i / (LHID / 4), j = (i - cc * (LHID / 4)) * 4;
+        const int i = tid + 256 * k, cc = (i >> 7) * 4 + (i & 3), j = ((i >> 2) & 31) * 4;   // four channels x 16 column quads per wave: LDS store banks
         wq[k] = *reinterpret_cast<const float4*>(a.wqkv + (size_t)cc * LC3 + j);
     }
 #pragma unroll
@@ -462,16 +460,21 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
     for (int k = 0; k < 4; ++k) cx[k] = *reinterpret_cast<const float4*>(a.ctx + (size_t)b * LHEADS * LDH * LDH + 4 * (tid + 256 * k));
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
-        const int i = tid + 256 * k, cc = i / (LHID / 4), j = (i - cc * (LHID / 4)) * 4;
-        *reinterpret_cast<float4*>(Wq + cc * LHID + j) = wq[k];
+        const int i = tid + 256 * k, cc = (i >> 7) * 4 + (i & 3), j = ((i >> 2) & 31) * 4;
+        const int hf = cc / H2, s = cc - hf * H2;
+        float* d = WqL + (((j >> 5) * 2 + hf) * 32 + (j & 31)) * SQ + s;
+        d[0] = wq[k].x; d[SQ] = wq[k].y; d[2 * SQ] = wq[k].z; d[3 * SQ] = wq[k].w;
     }
 #pragma unroll
-    for (int k = 0; k < NWO; ++k) Wo[tid + 256 * k] = wo[k];
+    for (int k = 0; k < NWO; ++k) {
+        const int i = tid + 256 * k, kk = i / WO, c = i - kk * WO, e = kk & 31;
+        WoL[((((kk >> 5) * CT + (c >> 5)) * 2 + ((e >> 2) & 1)) * 32 + (c & 31)) * AS + acc_reg(e)] = wo[k];
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int i = 4 * (tid + 256 * k);
-        float* d = ctxl + (i >> 5) * PS + (i & 31);
-        d[0] = cx[k].x; d[1] = cx[k].y; d[2] = cx[k].z; d[3] = cx[k].w;
+        const int i = 4 * (tid + 256 * k), d0 = (i >> 5) & 31;
+        float* d = ctxL + (((i >> 10) * 2 + ((d0 >> 2) & 1)) * 32 + (i & 31)) * AS + acc_reg(d0);
+        d[0] = cx[k].x; d[AS] = cx[k].y; d[2 * AS] = cx[k].z; d[3 * AS] = cx[k].w;
     }
     {
         float mean, rstd;
@@ -483,170 +486,172 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
         }
         if (a.gran && tid == 0) epoch_s = arrival / (unsigned)T + 1u;
     }
+    // the close's operands depend on nothing computed here: to_out.0's bias and the residual are requested now
+    float4 pbias[CT][4], rs[CT][4];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int c = ct * 32 + 8 * g + 4 * half;
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            pbias[ct][g] = z; rs[ct][g] = z;
+            if (c < C && a.bout) pbias[ct][g] = *reinterpret_cast<const float4*>(a.bout + c);
+            if (a.gran && c < C && in) rs[ct][g] = *reinterpret_cast<const float4*>(a.x + ((size_t)b * a.n + nn) * C + c);
+        }
     __syncthreads();
-    float* xw = xt + wave * 32 * XS;
+    float xn[H2];
+    norm_xh<NQ>(a, Ab, Bb, r0, lane, pre, xn);
     const float scale = 0.17677669529663687f;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int r0 = tile * 128 + wave * 32;
-        store_x<NQ>(a, Ab, Bb, xw, XS, r0, lane, pre);
-        __builtin_amdgcn_wave_barrier();
-        if (tile + (int)gridDim.x < ntiles) fetch_x<NQ>(a, b, r0 + 128 * gridDim.x, lane, pre);
-        f32x16 q[LHEADS];
+    f32x16 y[CT];
 #pragma unroll
-        for (int hh = 0; hh < LHEADS; ++hh)
+    for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) q[hh][r] = 0.f;
-#pragma unroll 2
-        for (int s = 0; s < (C >> 1); ++s) {
-            const float xa = xw[l31 * XS + 2 * s + half];
-            const float* wr = Wq + (2 * s + half) * LHID + l31;
+        for (int r = 0; r < 16; ++r) y[ct][r] = 0.f;
 #pragma unroll
-            for (int hh = 0; hh < LHEADS; ++hh) q[hh] = FC_MFMA(xa, wr[hh * 32], q[hh]);
+    for (int hh = 0; hh < LHEADS; ++hh) {
+        f32x16 q;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) q[r] = 0.f;
+        const float* wa = WqL + ((hh * 2 + half) * 32 + l31) * SQ;
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const float4 w = *reinterpret_cast<const float4*>(wa + 4 * j);
+            q = FC_MFMA(w.x, xn[4 * j], q);
+            q = FC_MFMA(w.y, xn[4 * j + 1], q);
+            q = FC_MFMA(w.z, xn[4 * j + 2], q);
+            q = FC_MFMA(w.w, xn[4 * j + 3], q);
         }
-        f32x16 y[CT];
+        // softmax over the head's 32 channels: this lane holds 16 of them, lane ^ 32 the other 16 of the same position
+        float m = q[0];
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
+        for (int r = 1; r < 16; ++r) m = fmaxf(m, q[r]);
+        m = fmaxf(m, __shfl_xor(m, 32));
+        float sum = 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) y[ct][r] = 0.f;
-        float* Pw = xw;                     // the x tile is dead: its buffer carries P, then out, of each head (row stride XS >= 33)
+        for (int r = 0; r < 16; ++r) { q[r] = __expf(q[r] - m); sum += q[r]; }
+        sum += __shfl_xor(sum, 32);
+        const float f = scale / sum;
 #pragma unroll
-        for (int hh = 0; hh < LHEADS; ++hh) {
-            __builtin_amdgcn_wave_barrier();
+        for (int r = 0; r < 16; ++r) q[r] *= f;
+        f32x16 o;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) Pw[acc_row(r, half) * XS + l31] = q[hh][r];
-            __builtin_amdgcn_wave_barrier();
-            {   // softmax over the head's 32 channels: lane (row l31, half) owns 16 of them
-                float v[16];
-                float* pr = Pw + l31 * XS + half * 16;
-                float m = -INFINITY;
+        for (int r = 0; r < 16; ++r) o[r] = 0.f;
+        const float* ca = ctxL + ((hh * 2 + half) * 32 + l31) * AS;
 #pragma unroll
-                for (int j = 0; j < 16; ++j) { v[j] = pr[j]; m = fmaxf(m, v[j]); }
-                m = fmaxf(m, __shfl_xor(m, 32));
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) { v[j] = __expf(v[j] - m); sum += v[j]; }
-                sum += __shfl_xor(sum, 32);
-                const float f = scale / sum;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) pr[j] = v[j] * f;
-            }
-            __builtin_amdgcn_wave_barrier();
-            f32x16 o;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[r] = 0.f;
-#pragma unroll 4
-            for (int s = 0; s < 16; ++s) o = FC_MFMA(Pw[l31 * XS + 2 * s + half], ctxl[(hh * LDH + 2 * s + half) * PS + l31], o);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Pw[acc_row(r, half) * XS + l31] = o[r];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll 2
-            for (int s = 0; s < 16; ++s) {
-                const float oa = Pw[l31 * XS + 2 * s + half];
-                const float* wr = Wo + (hh * LDH + 2 * s + half) * WO + l31;
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) y[ct] = FC_MFMA(oa, wr[ct * 32], y[ct]);
-            }
-        }
-        float S = 0.f, Q = 0.f;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const int c = ct * 32 + l31;
-            const float bias = pbias[ct];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = y[ct][r] + bias;
-                y[ct][r] = v;
-                if (r0 + acc_row(r, half) < a.n && c < C) { S += v; Q += v * v; }
-            }
-        }
-        const float St = block_sum(S, red);
-        const float Qt = block_sum(Q, red);
-        if (a.gran) {
-            // ---- the module closed here: out = GroupNorm(1)(y) * g2 + b2 + x, the statistics completed by the sample's other tiles ----
-            // The partials travel as ONE 8-byte write-through store each, {epoch, bits}: the data is its own flag (the convolution tails'
-            // hand-off, conv_dev.h); sc1 accesses that bypass the per-XCD L2, no fence.  finalize_kernel's arithmetic (stats_dev.h
-            // partials_finish) in the same order, so the exclusive and the shared plan agree to the last bit.
-            const unsigned epoch = epoch_s;
-            if (tid == 0) {
-                const float mt = St / n_t;
-                unsigned long long* gp = a.gran + ((size_t)b * T + tile) * 2;
-                const unsigned long long tag = (unsigned long long)epoch << 32;
-                __hip_atomic_store(gp, tag | __float_as_uint(mt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(gp + 1, tag | __float_as_uint(Qt - St * mt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            // the residual and the norm parameters are requested BEFORE the wait: they depend on nothing computed here
-            float rs[CT][16], g2[CT], b2[CT];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                const int c = ct * 32 + l31;
-                g2[ct] = c < C ? a.g2[c] : 0.f;
-                b2[ct] = c < C ? a.b2[c] : 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int nn = r0 + acc_row(r, half);
-                    rs[ct][r] = (nn < a.n && c < C) ? a.x[((size_t)b * a.n + nn) * C + c] : 0.f;
-                }
-            }
-            if (tid < 2 * T) {          // one granule per thread, polled until it carries this launch's epoch.  Bounded: a residency mistake
-                                        // must not hang the device -- the statistic becomes NaN and the handle's error word is set
-                const unsigned long long* gp = a.gran + (size_t)b * T * 2 + tid;
-                unsigned long long v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                int spins = 0;
-                while ((unsigned)(v >> 32) != epoch) {
-                    if (++spins > (1 << 20)) { if (a.err) *a.err = 1; v = 0x7fc00000ull; break; }
-                    __builtin_amdgcn_s_sleep(2);
-                    v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                gv[tid] = __uint_as_float((unsigned)v);
-            }
-            __syncthreads();
-            float sm2 = 0.f;
-            for (int t = 0; t < T; ++t) sm2 += gv[2 * t];
-            const float mean = sm2 / (float)T;
-            float m2 = 0.f, dv = 0.f;
-            for (int t = 0; t < T; ++t) {
-                const float d = gv[2 * t] - mean;
-                m2 += gv[2 * t + 1];
-                dv += d * d;
-            }
-            const float rstd = 1.0f / sqrtf((m2 + n_t * dv) / (n_t * (float)T) + a.eps2);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                const int c = ct * 32 + l31;
-                const float A = rstd * g2[ct], Bc = b2[ct] - mean * A;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int nn = r0 + acc_row(r, half);
-                    if (nn < a.n && c < C) a.out[((size_t)b * a.n + nn) * C + c] = (A * y[ct][r] + Bc) + rs[ct][r];
-                }
-            }
-            continue;                   // (one tile per workgroup: the loop ends here)
-        }
-        if (tid == 0) {
-            const float mt = St / n_t;
-            float* d = a.stats_out + ((size_t)b * T + tile) * 2;
-            d[0] = mt;
-            d[1] = Qt - St * mt;
+        for (int j = 0; j < 4; ++j) {
+            const float4 w = *reinterpret_cast<const float4*>(ca + 4 * j);
+            o = FC_MFMA(w.x, q[4 * j], o);
+            o = FC_MFMA(w.y, q[4 * j + 1], o);
+            o = FC_MFMA(w.z, q[4 * j + 2], o);
+            o = FC_MFMA(w.w, q[4 * j + 3], o);
         }
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
-            const int c = ct * 32 + l31;
+            const float* oa = WoL + (((hh * CT + ct) * 2 + half) * 32 + l31) * AS;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = r0 + acc_row(r, half);
-                if (nn < a.n && c < C) a.y[((size_t)b * a.n + nn) * C + c] = y[ct][r];
+            for (int j = 0; j < 4; ++j) {
+                const float4 w = *reinterpret_cast<const float4*>(oa + 4 * j);
+                y[ct] = FC_MFMA(w.x, o[4 * j], y[ct]);
+                y[ct] = FC_MFMA(w.y, o[4 * j + 1], y[ct]);
+                y[ct] = FC_MFMA(w.z, o[4 * j + 2], y[ct]);
+                y[ct] = FC_MFMA(w.w, o[4 * j + 3], y[ct]);
             }
         }
     }
+    // y[ct][4 g + i] is channel ct * 32 + 8 g + 4 half + i of position nn.  Statistics before the stores: a barrier after them would
+    // wait for the store round trip
+    float S = 0.f, Q = 0.f;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 bi = pbias[ct][g];
+            const float v0 = y[ct][4 * g] + bi.x, v1 = y[ct][4 * g + 1] + bi.y, v2 = y[ct][4 * g + 2] + bi.z, v3 = y[ct][4 * g + 3] + bi.w;
+            y[ct][4 * g] = v0; y[ct][4 * g + 1] = v1; y[ct][4 * g + 2] = v2; y[ct][4 * g + 3] = v3;
+            if (in && ct * 32 + 8 * g + 4 * half < C) {
+                S += v0; Q += v0 * v0; S += v1; Q += v1 * v1; S += v2; Q += v2 * v2; S += v3; Q += v3 * v3;
+            }
+        }
+    const float St = block_sum(S, red);
+    const float Qt = block_sum(Q, red);
+    if (a.gran) {
+        // ---- the module closed here: out = GroupNorm(1)(y) * g2 + b2 + x, the statistics completed by the sample's other tiles ----
+        // The partials travel as ONE 8-byte write-through store each, {epoch, bits}: the data is its own flag (the convolution tails'
+        // hand-off, conv_dev.h); sc1 accesses that bypass the per-XCD L2, no fence.  finalize_kernel's arithmetic (stats_dev.h
+        // partials_finish) in the same order, so the exclusive and the shared plan agree to the last bit.
+        const unsigned epoch = epoch_s;
+        float4 g2[CT][4], b2[CT][4];        // requested before the wait
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c = ct * 32 + 8 * g + 4 * half;
+                g2[ct][g] = make_float4(0.f, 0.f, 0.f, 0.f); b2[ct][g] = g2[ct][g];
+                if (c < C) { g2[ct][g] = *reinterpret_cast<const float4*>(a.g2 + c); b2[ct][g] = *reinterpret_cast<const float4*>(a.b2 + c); }
+            }
+        if (tid == 0) {
+            const float mt = St / n_t;
+            unsigned long long* gp = a.gran + ((size_t)b * T + tile) * 2;
+            const unsigned long long tag = (unsigned long long)epoch << 32;
+            __hip_atomic_store(gp, tag | __float_as_uint(mt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(gp + 1, tag | __float_as_uint(Qt - St * mt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (tid < 2 * T) {          // one granule per thread, polled until it carries this launch's epoch.  Bounded: a residency mistake
+                                    // must not hang the device -- the statistic becomes NaN and the handle's error word is set
+            const unsigned long long* gp = a.gran + (size_t)b * T * 2 + tid;
+            unsigned long long v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            int spins = 0;
+            while ((unsigned)(v >> 32) != epoch) {
+                if (++spins > (1 << 20)) { if (a.err) *a.err = 1; v = 0x7fc00000ull; break; }
+                __builtin_amdgcn_s_sleep(2);
+                v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            gv[tid] = __uint_as_float((unsigned)v);
+        }
+        __syncthreads();
+        float sm2 = 0.f;
+        for (int t = 0; t < T; ++t) sm2 += gv[2 * t];
+        const float mean = sm2 / (float)T;
+        float m2 = 0.f, dv = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const float d = gv[2 * t] - mean;
+            m2 += gv[2 * t + 1];
+            dv += d * d;
+        }
+        const float rstd = 1.0f / sqrtf((m2 + n_t * dv) / (n_t * (float)T) + a.eps2);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c = ct * 32 + 8 * g + 4 * half;
+                const float4 gg = g2[ct][g], bb = b2[ct][g], rr = rs[ct][g];
+                float4 ov;
+                { const float A = rstd * gg.x, Bc = bb.x - mean * A; ov.x = (A * y[ct][4 * g] + Bc) + rr.x; }
+                { const float A = rstd * gg.y, Bc = bb.y - mean * A; ov.y = (A * y[ct][4 * g + 1] + Bc) + rr.y; }
+                { const float A = rstd * gg.z, Bc = bb.z - mean * A; ov.z = (A * y[ct][4 * g + 2] + Bc) + rr.z; }
+                { const float A = rstd * gg.w, Bc = bb.w - mean * A; ov.w = (A * y[ct][4 * g + 3] + Bc) + rr.w; }
+                if (in && c < C) *reinterpret_cast<float4*>(a.out + ((size_t)b * a.n + nn) * C + c) = ov;
+            }
+        return;
+    }
+    if (tid == 0) {
+        const float mt = St / n_t;
+        float* d = a.stats_out + ((size_t)b * T + tile) * 2;
+        d[0] = mt;
+        d[1] = Qt - St * mt;
+    }
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int c = ct * 32 + 8 * g + 4 * half;
+            if (in && c < C) *reinterpret_cast<float4*>(a.y + ((size_t)b * a.n + nn) * C + c) = make_float4(y[ct][4 * g], y[ct][4 * g + 1], y[ct][4 * g + 2], y[ct][4 * g + 3]);
+        }
 }
 
-static size_t la_ctx_fast_lds(int C, int NW) { return (size_t)(2 * C + C * 64 + NW * 32 * (C + 1) + 2 * NW * 32 * PS + 32 * NW + 64 * NW) * sizeof(float); }
+static size_t la_ctx_fast_lds(int C, int NW) { return (size_t)(2 * C + NW * 32 * PS + 32 * NW + 64 * NW) * sizeof(float); }
 static int la_ctx_waves(int n) { return n >= 256 ? 8 : 4; }      // eight waves once every one of them has a 32-position block of its own
-static size_t la_apply_fast_lds(int C, int CT) {
-    const int XS = C + 1 > PS ? C + 1 : PS;
-    return (size_t)(2 * C + C * LHID + LHID * CT * 32 + LHEADS * LDH * PS + 4 * 32 * XS) * sizeof(float);
-}
+static size_t la_apply_fast_lds(int C, int CT) { return (size_t)(2 * C + LHEADS * 64 * (C / 2 + 4) + LHEADS * 64 * AS + LHEADS * CT * 64 * AS) * sizeof(float); }
 template <int NQ>
 static int launch_fast(const LaArgs& a, hipStream_t s) {
     if (la_ctx_waves(a.n) == 8) hipLaunchKernelGGL((la_ctx_fast_kernel<NQ, 8>), dim3(LHEADS, a.B), dim3(512), la_ctx_fast_lds(a.C, 8), s, a);
@@ -654,10 +659,8 @@ static int launch_fast(const LaArgs& a, hipStream_t s) {
     FC_HIP(hipGetLastError());
     const int T = linattn_fused_tiles(a.n);
     const float n_t = linattn_fused_nt(a.n, a.C);
-    // Round 4: one 128-position tile per workgroup.  Two tiles per workgroup (round 2: half the weight staging) leave 256 workgroups of
-    // four waves -- one wave per SIMD, nothing to cover the LDS round trips between the five dependent phases of a head; with one tile each,
-    // two workgroups share a CU (67 KB of LDS each).  Measured per module at n = 1024: 55.0 -> 51.0 and 50.9 -> 47.0 us; sampler 793 -> 805
-    // samples/s on one box (791 / 788 with four-wave la_ctx and two tiles).
+    // One 128-position tile per workgroup: the A operand images of a workgroup are 61 KB of LDS at C = 32, so two workgroups share a CU
+    // and two waves a SIMD -- one wave's softmax arithmetic runs under the other's matrix phases.
     const dim3 grid(cdiv(a.n, 128), a.B);
     if (a.C <= 32) hipLaunchKernelGGL((la_apply_fast_kernel<NQ, 1>), grid, dim3(256), la_apply_fast_lds(a.C, 1), s, a, T, n_t);
     else hipLaunchKernelGGL((la_apply_fast_kernel<NQ, 2>), grid, dim3(256), la_apply_fast_lds(a.C, 2), s, a, T, n_t);
