@@ -150,6 +150,8 @@ SIGNATURES = {
     "fc_sinkhorn_divergence": (_i, [_vp, _vp, _i, _i, _i64, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                _pi, _vp]),
     "fc_ot_pairing": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "fc_ot_pairing_exact": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
+    "fc_ot_assign": (_i, [_vp, _i, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

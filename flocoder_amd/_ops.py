@@ -72,6 +72,29 @@ def ot_pairing(source: torch.Tensor, target: torch.Tensor):
     return perm, dist
 
 
+def ot_pairing_exact(source: torch.Tensor, target: torch.Tensor, want_duals: bool = True):
+    """Exact OT pairing on the GPU; returns (perm int64 [B], cost [B,B] squared distances, duals fp64 [2,B] = (u, v), or None when
+    ``want_duals`` is off)."""
+    bsz = source.shape[0]
+    s = source.reshape(bsz, -1).float().contiguous()
+    t = target.reshape(bsz, -1).float().contiguous()
+    cost = torch.empty(bsz, bsz, device=s.device, dtype=torch.float32)
+    perm = torch.empty(bsz, device=s.device, dtype=torch.int64)
+    duals = torch.empty(2, bsz, device=s.device, dtype=torch.float64) if want_duals else None
+    B.check(B.lib().fc_ot_pairing_exact(B.ptr(s), B.ptr(t), bsz, s.shape[1], B.ptr(cost), B.ptr(perm), B.ptr(duals), B.current_stream(s.device)))
+    return perm, cost, duals
+
+
+def ot_assign(cost: torch.Tensor):
+    """The linear assignment solver alone on a [B,B] cost matrix; returns (perm int64 [B], duals fp64 [2,B] = (u, v))."""
+    bsz = cost.shape[0]
+    c = cost.reshape(bsz, bsz).float().contiguous()
+    perm = torch.empty(bsz, device=c.device, dtype=torch.int64)
+    duals = torch.empty(2, bsz, device=c.device, dtype=torch.float64)
+    B.check(B.lib().fc_ot_assign(B.ptr(c), bsz, B.ptr(perm), B.ptr(duals), B.current_stream(c.device)))
+    return perm, duals
+
+
 def conv_wgrad_debug(x0: torch.Tensor, dy: torch.Tensor, ks: int, x1=None, *, pad=0, stride=1, upsample=False):
     """Weight / bias gradient of one convolution from its NCHW input(s) and NCHW output gradient: (dW [O,I,KH,KW], db [O])."""
     dev = x0.device

@@ -473,5 +473,8 @@ int adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, si
 
 // ---- OT (ot.hip) ------------------------------------------------------------------------------
 int ot_launch(const float* src, const float* tgt, int B, int64_t D, float* dist, int64_t* perm, hipStream_t s);
+// exact pairing: cost = squared distances (non-finite -> FLT_MAX), then the linear assignment solver; duals null or [2B] (u then v)
+int ot_exact_launch(const float* src, const float* tgt, int B, int64_t D, float* cost, int64_t* perm, double* duals, hipStream_t s);
+int ot_assign_launch(const float* cost, int B, int64_t* perm, double* duals, hipStream_t s);
 
 }  // namespace fc

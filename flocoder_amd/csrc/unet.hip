@@ -1217,4 +1217,17 @@ int fc_ot_pairing(const float* source_dev, const float* target_dev, int batch, i
     return ot_launch(source_dev, target_dev, batch, dim, dist_ws_dev, perm_out_dev, static_cast<hipStream_t>(stream));
 }
 
+int fc_ot_pairing_exact(const float* source_dev, const float* target_dev, int batch, int64_t dim, float* cost_ws_dev, int64_t* perm_out_dev,
+                        double* duals_out_dev, void* stream) {
+    if (batch < 1 || batch > 1024) return fail(FC_E_SHAPE, "fc_ot_pairing_exact: batch must be in [1, 1024]");   // before the null test: an empty batch has no pointers
+    if (!source_dev || !target_dev || !cost_ws_dev || !perm_out_dev) return fail(FC_E_ARG, "fc_ot_pairing_exact: null argument");
+    return ot_exact_launch(source_dev, target_dev, batch, dim, cost_ws_dev, perm_out_dev, duals_out_dev, static_cast<hipStream_t>(stream));
+}
+
+int fc_ot_assign(const float* cost_dev, int batch, int64_t* perm_out_dev, double* duals_out_dev, void* stream) {
+    if (batch < 1 || batch > 1024) return fail(FC_E_SHAPE, "fc_ot_assign: batch must be in [1, 1024]");
+    if (!cost_dev || !perm_out_dev) return fail(FC_E_ARG, "fc_ot_assign: null argument");
+    return ot_assign_launch(cost_dev, batch, perm_out_dev, duals_out_dev, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

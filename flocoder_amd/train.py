@@ -78,10 +78,11 @@ def _mark_dirty(module) -> None:
 
 
 def batch_to_data(batch, device, pre_encoded=True, mask_encoder=None, epoch=None, curriculum_epochs=10, extend_epochs=20,
-                  blank_latents=None):
+                  blank_latents=None, ot_method="greedy"):
     """train_flow.py:90-182: unpack a (latents | dict, class) batch, draw the source noise, encode / blend the inpainting mask and
-    re-index the TARGET by the greedy OT pairing.  The on-the-fly mask augmentation is a no-op upstream (p_ones = p_zeros = 0,
-    train_flow.py:129-133) and is therefore absent.  Returns (source, target, class_cond, mask, mask_pixels)."""
+    re-index the TARGET by the OT pairing (``ot_method``: "greedy" as upstream, or "exact").  The on-the-fly mask augmentation is a
+    no-op upstream (p_ones = p_zeros = 0, train_flow.py:129-133) and is therefore absent.  Returns (source, target, class_cond, mask,
+    mask_pixels)."""
     source, mask, mask_pixels = None, None, None
     if not pre_encoded:
         raise NotImplementedError("batch_to_data: only pre-encoded latents are supported (pre_encoded=True is hard-wired upstream, train_flow.py:213)")
@@ -105,7 +106,7 @@ def batch_to_data(batch, device, pre_encoded=True, mask_encoder=None, epoch=None
         source = mask_blending(source, mask, noise)
     else:
         raise AssertionError("Unintended edge case in batch_to_data (train_flow.py:149)")
-    ot_indices = compute_ot_pairing(source, target)
+    ot_indices = compute_ot_pairing(source, target, method=ot_method)
     target = target[ot_indices]
     return source, target, class_cond, mask, mask_pixels
 
@@ -598,7 +599,8 @@ class FlowTrainer:
         self._me_scal = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.model.mask_encoder = me                          # as upstream (train_flow.py:333): checkpoints / EMA see it through the model
 
-    def inpaint_step(self, source_latents, target, mask_pixels, class_cond=None, noise=None, u=None, drop_cond=False, ot=False):
+    def inpaint_step(self, source_latents, target, mask_pixels, class_cond=None, noise=None, u=None, drop_cond=False, ot=False,
+                     ot_method="greedy"):
         """One inpainting training step entirely on the device (batch_to_data's mask branch + train_flow.py:346-397):
         mask = MaskEncoder(mask_pixels); source = blend(source_latents, mask, noise); flow loss through the mask-conditioned U-Net;
         + MSE(MaskEncoder(1), 1) + MSE(MaskEncoder(0), 0); backward into both networks (the encoder is reached through the U-Net's
@@ -627,8 +629,8 @@ class FlowTrainer:
             else:
                 mask = me._forward_native(mp)
                 source = mask_blending(s0, mask, noise)
-                if ot:                                        # batch_to_data re-indexes the TARGET by the greedy pairing (train_flow.py:160-163)
-                    tgt = tgt[compute_ot_pairing(source, tgt)].contiguous()
+                if ot:                                        # batch_to_data re-indexes the TARGET by the OT pairing (train_flow.py:160-163)
+                    tgt = tgt[compute_ot_pairing(source, tgt, method=ot_method)].contiguous()
                 x, v_target = self.interpolate(source, tgt, t)
                 v = self.model._forward_native(x, time, cls, mask, train=True)
                 dv = torch.empty_like(v)
@@ -668,15 +670,17 @@ class FlowTrainer:
         me.mark_dirty()                                       # its flat vector changed under the views: re-upload on next use
         return loss
 
-    def train_batch(self, batch, epoch=None, cfg_drop: float = 0.1, mask_encoder=None, blank_latents=None):
-        """batch_to_data + the 10 % conditioning drop of train_flow.py:338-345 + step.  With an attached MaskEncoder and an
-        inpainting batch (dict with mask_pixels) the encoder trains too (``inpaint_step``)."""
+    def train_batch(self, batch, epoch=None, cfg_drop: float = 0.1, mask_encoder=None, blank_latents=None, ot_method="greedy"):
+        """batch_to_data + the 10 % conditioning drop of train_flow.py:338-345 + step; ``ot_method`` selects the pairing ("greedy" |
+        "exact").  With an attached MaskEncoder and an inpainting batch (dict with mask_pixels) the encoder trains too
+        (``inpaint_step``)."""
         data = batch[0]
         if getattr(self, "me", None) is not None and isinstance(data, dict) and 'mask_pixels' in data:
             target = data['target_latents'].to(self.device)
             return self.inpaint_step(data['source_latents'], target, data['mask_pixels'].float(), class_cond=batch[1],
-                                     drop_cond=self._drop_rng.random() < cfg_drop, ot=True)
-        source, target, class_cond, mask_cond, _ = batch_to_data(batch, self.device, True, mask_encoder, epoch=epoch, blank_latents=blank_latents)
+                                     drop_cond=self._drop_rng.random() < cfg_drop, ot=True, ot_method=ot_method)
+        source, target, class_cond, mask_cond, _ = batch_to_data(batch, self.device, True, mask_encoder, epoch=epoch, blank_latents=blank_latents,
+                                                                    ot_method=ot_method)
         cond = {'class_cond': class_cond, 'mask_cond': mask_cond}
         if self._drop_rng.random() < cfg_drop:
             cond = None

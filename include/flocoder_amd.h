@@ -511,11 +511,17 @@ int fc_mask_encoder_backward(fc_mask_encoder* m, const float* mask_pixels_dev, c
 int fc_mask_blend(const float* source_dev, const float* mask_dev, const float* noise_dev, float* out_dev, int64_t numel, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Greedy OT pairing  (replaces flocoder/ot.py:63-84 compute_ot_pairing)
+ * OT pairing  (replaces flocoder/ot.py:63-84 compute_ot_pairing)
  * ---------------------------------------------------------------------------------------------- */
-/* source_dev/target_dev [B,D] fp32; dist_ws_dev workspace of B*B floats; perm_out_dev [B] int64. */
+/* The greedy matcher.  source_dev/target_dev [B,D] fp32; dist_ws_dev workspace of B*B floats; perm_out_dev [B] int64. */
 int fc_ot_pairing(const float* source_dev, const float* target_dev, int batch, int64_t dim, float* dist_ws_dev,
                   int64_t* perm_out_dev, void* stream);
+/* Exact mini-batch OT pairing: perm minimises sum_i |s_i - t_perm[i]|^2 over permutations.  cost_ws_dev: B*B floats, holds the
+ * squared-distance matrix on return; duals_out_dev: NULL or 2*B doubles (u then v) with u_i + v_j <= c_ij, equality on the pairing. */
+int fc_ot_pairing_exact(const float* source_dev, const float* target_dev, int batch, int64_t dim, float* cost_ws_dev,
+                        int64_t* perm_out_dev, double* duals_out_dev, void* stream);
+/* The solver alone on a caller's cost matrix cost_dev [B][B] fp32 (non-finite entries count as FLT_MAX). */
+int fc_ot_assign(const float* cost_dev, int batch, int64_t* perm_out_dev, double* duals_out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Parity metrics  (replace flocoder/metrics.py:40-54 sinkhorn_loss: geomloss SamplesLoss("sinkhorn", p=2, blur=0.05))
