@@ -133,6 +133,8 @@ bool conv_fin_possible(const ConvArgs& a, int tile);   // the fused tail's resid
 int conv_init();
 unsigned long long* conv_stamp_buffer();
 void conv_set_stamp_buffer(unsigned long long* p);  // diagnostics: phase stamps of the pipelined kernel
+void conv_route_log_set(bool on);                   // diagnostics: the instantiation each pipelined launch goes to (conv_pipe.hip)
+std::string conv_route_log_get();
 int conv_plan(const ConvArgs& a, int tile, ConvGeom* g);
 int conv_launch(const ConvArgs& a, int tile, hipStream_t s);
 

@@ -119,7 +119,27 @@ constexpr int FL_FIN = 1, FL_RES = 2, FL_POST = 4, FL_XF = 8, FL_CAT = 16, FL_ST
 // partials of the output, 128: GroupNorm(1) partials of the tail's result, 256: activation / addend on the output, 512: per-lane dword
 // stores when the LDS image for the wide stores does not fit, 1024: several samples per tile -- always on for the 32-row tile,
 // 2048: the fused tail may have to meet other workgroups (without it: only tails whose tile holds whole GroupNorm groups))
-template <int WM, int WN, int WK, int MT, int NT, int FL = FL_ALL>
+//
+// GEO: the tile GEOMETRY of a Block-closing launch as a second compile-time key (0: read from ConvDev at run time -- every flavour without
+// a fused tail, the all-in-one kernel, and the tail flavours that serve the geometries without a key).  The mask above removes the options a launch does not use; what is left of a tail is executed
+// once per launch, from a cold instruction cache, and was still written for every geometry: three statistics forms (twice with
+// GroupNorm(1) partials), shuffle trees, poll and combination loops with run-time trip counts, integer divisions by cpg / Cin / ngt.
+// A plan launches one geometry per layer, known when the plan is built, so a Block-closing lean flavour exists per (mask, geometry) the
+// dim-32 inference plan uses (conv_pipe.hip FC_FIN_GEOMS) and is launched for an exact match of both; any other geometry runs on the
+// flavour of its mask that reads the geometry at run time (GEO = 0).  Everything else about the geometry follows from the key and the tile: rps = BM / TB, TH = BM / (TB TW),
+// cpgt = min(cpg, BN), NPG = max(cpg / BN, 1), ngt = max(BN / cpg, 1); Tst = workgroups (statistics slots) per GroupNorm group.
+//   bits 0-1 statistics form (1 pair, 2 fast; the general multi-sample form has no specialised flavour), bit 2 TB == 2,
+//   bits 3-5 log2 TW, bits 6-9 log2 cpg, bits 10-15 Tst
+constexpr int GEO_PAIR = 1, GEO_FAST = 2;
+constexpr int geo_log2(int v) { return v <= 1 ? 0 : 1 + geo_log2(v >> 1); }
+constexpr int geo_key(int form, int TB, int TW, int cpg, int Tst) { return form | ((TB == 2 ? 1 : 0) << 2) | (geo_log2(TW) << 3) | (geo_log2(cpg) << 6) | (Tst << 10); }
+constexpr int geo_form(int k) { return k & 3; }
+constexpr int geo_TB(int k) { return 1 + ((k >> 2) & 1); }
+constexpr int geo_TWl(int k) { return (k >> 3) & 7; }
+constexpr int geo_cpg(int k) { return 1 << ((k >> 6) & 15); }
+constexpr int geo_Tst(int k) { return (k >> 10) & 63; }
+
+template <int WM, int WN, int WK, int MT, int NT, int FL = FL_ALL, int GEO = 0>
 __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT][NT], f32x16 (&accr)[MT][NT], float* smem, int tid, int lane,
                                               int wave, int b0, int y0, int x0, int n0, int tx, int ty, bool active = true,
                                               int nthr = 256, const float* pre = nullptr, bool staged_dead = false) {
@@ -131,7 +151,20 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
     const ConvArgs& a = p.a;
     const int half = lane >> 5, l31 = lane & 31;
     const int wk = wave % WK, wn = (wave / WK) % WN, wm = wave / (WK * WN);
-    const int TW = 1 << p.TWl, TH = 1 << p.THl, Cout = a.Cout;
+    // the tile geometry: constants of the flavour (GEO != 0), else the launch's values
+    constexpr bool GEOC = GEO != 0;
+    static_assert(!GEOC || (FL != FL_ALL && (FL & FL_FIN) && (FL & FL_STATS) && !(FL & (FL_MULTI | FL_POST | FL_RES))), "a geometry key belongs to a lean Block-closing flavour");
+    static_assert(!GEOC || (geo_Tst(GEO) >= 1 && geo_TB(GEO) * (geo_cpg(GEO) >= BN ? 1 : BN / geo_cpg(GEO)) * geo_Tst(GEO) * 2 <= 512), "one granule per thread");
+    const int g_TB = GEOC ? geo_TB(GEO) : p.TB;
+    const int g_TWl = GEOC ? geo_TWl(GEO) : p.TWl;
+    const int g_tbsh = GEOC ? geo_log2(BM / geo_TB(GEO)) : p.TWl + p.THl;            // log2 of a sample's pixels in the tile
+    const int g_THl = GEOC ? geo_log2(BM / geo_TB(GEO)) - geo_TWl(GEO) : p.THl;
+    const int g_rps = GEOC ? BM / geo_TB(GEO) : p.rps;
+    const int g_cpg = GEOC ? geo_cpg(GEO) : p.cpg;
+    const int g_cpgt = GEOC ? (geo_cpg(GEO) < BN ? geo_cpg(GEO) : BN) : p.cpgt;
+    const int g_NPG = GEOC ? (geo_cpg(GEO) >= BN ? geo_cpg(GEO) / BN : 1) : p.NPG;
+    const int g_mt = GEOC ? (geo_TB(GEO) > 1 ? 1 : geo_Tst(GEO) / (geo_cpg(GEO) >= BN ? geo_cpg(GEO) / BN : 1)) : (p.TB > 1 ? 1 : p.tiles_x * p.tiles_y);   // pixel tiles per sample
+    const int TW = 1 << g_TWl, TH = 1 << g_THl, Cout = a.Cout;
     // a lean flavour is only ever launched for an exact match of its mask (conv_pipe.hip), so there a set bit means "on", not "possible"
     constexpr bool LEAN = FL != FL_ALL;
     const bool has_res = LEAN ? bool(FL & FL_RES) : a.res_out != nullptr;
@@ -182,7 +215,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
     // pixel index (b * H + y) * W + x of accumulator row r of M tile mt in this lane, or -1 for a sample beyond B
     auto pix_of = [&](int mt, int r) {
         const int m = (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        const int tw = m & (TW - 1), th = (m >> p.TWl) & (TH - 1), tb = m >> (p.TWl + p.THl);
+        const int tw = m & (TW - 1), th = (m >> g_TWl) & (TH - 1), tb = m >> g_tbsh;
         const int b = b0 + tb;
         return b < a.B ? (b * (a.H << a.out_sh) + ((y0 + th) << a.out_sh) + a.out_oy) * (a.W << a.out_sh) + ((x0 + tw) << a.out_sh) + a.out_ox : -1;
     };
@@ -225,13 +258,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
     // group -- consecutive lanes of one wave, cpgt a power of two <= 64 -- meet by xor-shuffles; the group's first lane writes
     // (mean_t, M2_t) of this tile's share of group g of sample b.
     // (sum, sum of squares) of this tile's share of group (tb, gl) -> its (mean_t, M2_t) partial slot (or granules / the local table)
-    auto publish = [&](float* dst, int G, int cpg, int cpgt, int NPG, bool coherent, bool ltab_on, int tb, int gl, float s, float q) {
+    // (`whole`: the group is the whole channel axis -- GroupNorm(1) with Cout a multiple of BN --, so g = 0 and the column tile is the slot:
+    // no division by a run-time cpg)
+    auto publish = [&](float* dst, int G, int cpg, int cpgt, int NPG, bool coherent, bool ltab_on, int tb, int gl, float s, float q, bool whole = false) {
         const int b = b0 + tb;
-        const float n = (float)(p.rps * cpgt), mean = s / n;
-        const int g = n0 / cpg + (cpg >= BN ? 0 : gl);
-        const int nsub = (cpg >= BN) ? (n0 % cpg) / BN : 0;
-        const int msub = (p.TB > 1) ? 0 : ty * p.tiles_x + tx;
-        const int T = (p.TB > 1 ? 1 : p.tiles_x * p.tiles_y) * NPG;
+        const float n = (float)(g_rps * cpgt), mean = s / n;
+        const int g = whole ? 0 : n0 / cpg + (cpg >= BN ? 0 : gl);
+        const int nsub = whole ? n0 / BN : ((cpg >= BN) ? (n0 % cpg) / BN : 0);
+        const int msub = (g_TB > 1) ? 0 : ty * p.tiles_x + tx;
+        const int T = g_mt * NPG;
         float* d = dst + (((size_t)(b * G + g) * a.stats_tmul + a.stats_toff) * T + msub * NPG + nsub) * 2;
         if (ltab_on) {    // the tile holds the whole group: (mean, rstd) for the tail below, no trip through memory
             float* ltab = smem + p.o_fin;
@@ -273,7 +308,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
     // folds its own rows and its group's columns in registers (shuffles only), one LDS word pair per (wave row, group) crosses to the
     // publishing thread.  The general form above goes through [BM/16][BN] LDS tables and sums them again per thread: 5 k cycles of the
     // 10 k-cycle epilogue of a 32x32 layer, this is 2 k.
-    auto stats_fast = [&](float* dst, int G, int cpg, int cpgt, int NPG, bool coherent, bool ltab) {
+    auto stats_fast = [&](float* dst, int G, int cpg, int cpgt, int NPG, bool coherent, bool ltab, bool whole = false) {
         const int lanes = cpgt < 32 ? cpgt : 32;          // columns of a group inside one 32-column accumulator block
         const int per = cpgt <= 32 ? 1 : cpgt / 32;       // accumulator blocks a group spans (cpgt == 64 with NT == 2)
         if (owner) {
@@ -313,18 +348,19 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
             float s_ = 0.f, q_ = 0.f;
 #pragma unroll
             for (int w2 = 0; w2 < WM; ++w2) { s_ += partS[w2 * BN + col]; q_ += partQ[w2 * BN + col]; }
-            publish(dst, G, cpg, cpgt, NPG, coherent, ltab, 0, i, s_, q_);
+            publish(dst, G, cpg, cpgt, NPG, coherent, ltab, 0, i, s_, q_, whole);
         }
     };
     constexpr bool CAN_MULTI = (FL & FL_MULTI) || (WM * MT == 1);     // the 32-row tile is the small-image tile: samples share it
-    const bool fast_stats = !CAN_MULTI || p.TB == 1;
+    const bool fast_stats = GEOC ? geo_form(GEO) == GEO_FAST : (!CAN_MULTI || p.TB == 1);
     // The 32-row tile over two 16-pixel samples (every 4x4 layer of the U-Net): accumulator registers 0-7 of a lane are sample 0, 8-15
     // sample 1 (row = (r & 3) + 8 (r >> 2) + 4 half), so the partials are register sums + shuffles inside the one wave that owns the
     // tile -- no LDS tables, no barrier.  The general multi-sample form below costs 2.6 k cycles per pass here (stamps, round 3), and a
     // convolution that closes its Block runs it twice.
     constexpr bool PAIR_TILE = (WM * MT == 1 && WN * NT == 1);
-    const bool pair_stats = PAIR_TILE && p.TB == 2 && p.rps == 16;
-    auto stats_pair = [&](float* dst, int G, int cpg, int cpgt, int NPG, bool coherent, bool ltab) {
+    const bool pair_stats = GEOC ? geo_form(GEO) == GEO_PAIR : (PAIR_TILE && p.TB == 2 && p.rps == 16);
+    static_assert(!GEOC || geo_form(GEO) == GEO_FAST || (geo_form(GEO) == GEO_PAIR && PAIR_TILE && geo_TB(GEO) == 2), "statistics form of the key");
+    auto stats_pair = [&](float* dst, int G, int cpg, int cpgt, int NPG, bool coherent, bool ltab, bool whole = false) {
         if (owner) {
             float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
 #pragma unroll
@@ -335,8 +371,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
             }
             const int ncols = min(BN, Cout - n0);
             if (half == 0 && (l31 & (cpgt - 1)) == 0 && l31 < ncols) {
-                if (b0 < a.B) publish(dst, G, cpg, cpgt, NPG, coherent, ltab, 0, l31 / cpgt, s0, q0);
-                if (b0 + 1 < a.B) publish(dst, G, cpg, cpgt, NPG, coherent, ltab, 1, l31 / cpgt, s1, q1);
+                if (b0 < a.B) publish(dst, G, cpg, cpgt, NPG, coherent, ltab, 0, l31 / cpgt, s0, q0, whole);
+                if (b0 + 1 < a.B) publish(dst, G, cpg, cpgt, NPG, coherent, ltab, 1, l31 / cpgt, s1, q1, whole);
             }
         }
     };
@@ -375,8 +411,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
 
     if (FL & FL_STAMP) conv_stamp(p, 7);
     if (do_stats) {
-        if (pair_stats) stats_pair(a.stats_out, a.Gout, p.cpg, p.cpgt, p.NPG, meeting, fin && !meeting);
-        else if (fast_stats) stats_fast(a.stats_out, a.Gout, p.cpg, p.cpgt, p.NPG, meeting, fin && !meeting);
+        if (pair_stats) stats_pair(a.stats_out, a.Gout, g_cpg, g_cpgt, g_NPG, meeting, fin && !meeting);
+        else if (fast_stats) stats_fast(a.stats_out, a.Gout, g_cpg, g_cpgt, g_NPG, meeting, fin && !meeting);
         else {
             __syncthreads();
             emit(a.stats_out, a.Gout, p.cpg, p.cpgt, p.NPG, meeting, fin && !meeting);
@@ -390,7 +426,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
         // non-coherent per-XCD L2 -- ordered by vmcnt(0) + the workgroup barrier; no cache write-back / invalidate, which
         // a release/acquire fence pair would cost every workgroup (measured: 120 us per launch instead of 25).
         float* tab = smem + p.o_fin;
-        const int ngt = p.cpg >= BN ? 1 : BN / p.cpg;
+        const int ngt = g_cpg >= BN ? 1 : BN / g_cpg;
         // The residual is requested BEFORE the wait for the other workgroups' partials: it depends on nothing computed here, it is a cold
         // miss (another kernel wrote it), and behind the meeting it was a second memory round trip on the tail's critical path (round 3).
         // (Round 4 tried it earlier still -- in front of the statistics, with LDS-only barriers for the accumulator waves so that the
@@ -416,12 +452,14 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
             // One round trip when the others have already published: every thread polls ONE granule (sc1 loads that bypass this CU's
             // L1) until its tag is this launch's epoch, parks the value in LDS; then the Chan combination runs from LDS.  Bounded:
             // a residency mistake must not hang the device (err is checked by the host: fc_unet_fused_tail_errors).
-            const int Tst = (p.TB > 1 ? 1 : p.tiles_x * p.tiles_y) * p.NPG;
-            const int cnt = p.TB * ngt * Tst * 2;
+            // (a geometry flavour: Tst, ngt and with them every index below are constants, the granules are at most one per thread and the
+            // combination is a straight line of Tst terms, in the same order)
+            const int Tst = GEOC ? geo_Tst(GEO) : (p.TB > 1 ? 1 : p.tiles_x * p.tiles_y) * p.NPG;
+            const int cnt = g_TB * ngt * Tst * 2;
             float* gv = smem + p.o_gran;
             for (int i = tid; i < cnt; i += nthr) {
                 const int k = i & 1, t = (i >> 1) % Tst, j = (i >> 1) / Tst, tb = j / ngt, gl = j - tb * ngt;
-                const int b = b0 + tb, g = n0 / p.cpg + gl;
+                const int b = b0 + tb, g = n0 / g_cpg + gl;
                 float val = 0.f;
                 if (b < a.B && g < a.Gout) {
                     const gu64* gp = (const gu64*)(a.fin.gran + ((size_t)(b * a.Gout + g) * Tst + t) * 2 + k);
@@ -438,14 +476,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
                     val = __uint_as_float((unsigned)v);
                 }
                 gv[i] = val;
+                if (GEOC) break;      // cnt <= nthr (conv_pipe.hip fin_geo_key)
             }
             lds_only_barrier();
-            for (int i = tid; i < p.TB * ngt; i += nthr) {
-                const int tb = i / ngt, gl = i - tb * ngt, b = b0 + tb, g = n0 / p.cpg + gl;
+            for (int i = tid; i < g_TB * ngt; i += nthr) {
+                const int tb = i / ngt, gl = i - tb * ngt, b = b0 + tb, g = n0 / g_cpg + gl;
                 float mean = 0.f, rstd = 0.f;
                 if (b < a.B && g < a.Gout) {
                     const float* sp = gv + (size_t)i * Tst * 2;
-                    const float nt_ = (float)(p.rps * p.cpgt);
+                    const float nt_ = (float)(g_rps * g_cpgt);
                     float sm = 0.f;
                     for (int t = 0; t < Tst; ++t) sm += sp[2 * t];
                     mean = sm / (float)Tst;
@@ -459,6 +498,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
                 }
                 tab[2 * i] = mean;
                 tab[2 * i + 1] = rstd;
+                if (GEOC) break;
             }
         }
         lds_only_barrier();
@@ -470,12 +510,12 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
                 for (int nt = 0; nt < NT; ++nt) {
                     const int ncol = (wn * NT + nt) * 32 + l31, n = n0 + ncol;
                     const bool nok = n < Cout;
-                    const int gl = p.cpg >= BN ? 0 : ncol / p.cpg;
+                    const int gl = g_cpg >= BN ? 0 : ncol / g_cpg;
                     const float gam = pre ? pre[2 * NT + nt] : (nok ? a.fin.gamma[n] : 0.f), bet = pre ? pre[3 * NT + nt] : (nok ? a.fin.beta[n] : 0.f);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int m = (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                        const int tb = m >> (p.TWl + p.THl);
+                        const int tb = m >> g_tbsh;
                         const float mean = tab[2 * (tb * ngt + gl)], rstd = tab[2 * (tb * ngt + gl) + 1];
                         const float A = rstd * gam;
                         const float v = silu_f(A * acc[mt][nt][r] + (bet - mean * A)) + rs[mt][nt][r];
@@ -486,9 +526,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
         if ((FL & FL_STAMP) && active) conv_stamp(p, 2);   // (accumulator rows) normalised + activated + residual added
         if (LEAN ? bool(FL & FL_GN1) : a.fin.gn1_out != nullptr) {   // GroupNorm(1) partials of the final value for the PreNorm that follows (unet.py:156-160)
             lds_only_barrier();                    // every reader of part* / tab is done
-            const int cpg1 = Cout, cpgt1 = Cout < BN ? Cout : BN, NPG1 = Cout >= BN ? Cout / BN : 1;
-            if (pair_stats) stats_pair(a.fin.gn1_out, 1, cpg1, cpgt1, NPG1, false, false);
-            else if (fast_stats) stats_fast(a.fin.gn1_out, 1, cpg1, cpgt1, NPG1, false, false);
+            // (a geometry flavour is launched for whole column tiles only: Cout = ntiles BN)
+            const int cpg1 = Cout, cpgt1 = GEOC ? BN : (Cout < BN ? Cout : BN), NPG1 = GEOC ? p.ntiles : (Cout >= BN ? Cout / BN : 1);
+            if (pair_stats) stats_pair(a.fin.gn1_out, 1, cpg1, cpgt1, NPG1, false, false, GEOC);
+            else if (fast_stats) stats_fast(a.fin.gn1_out, 1, cpg1, cpgt1, NPG1, false, false, GEOC);
             else {
                 block_sums();
                 lds_only_barrier();
@@ -571,7 +612,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
             float* gout = pass ? a.res_out : a.out;
             for (int i = tid; i < BM * Q4; i += nthr) {
                 const int m = i / Q4, c4 = (i - m * Q4) * 4, n = n0 + c4;
-                const int tw = m & (TW - 1), th = (m >> p.TWl) & (TH - 1), tb = m >> (p.TWl + p.THl);
+                const int tw = m & (TW - 1), th = (m >> g_TWl) & (TH - 1), tb = m >> g_tbsh;
                 const int b = b0 + tb;
                 if (b < a.B && n < Cout) {
                     const float4 v = *reinterpret_cast<const float4*>(ot + m * OS + c4);

@@ -106,7 +106,7 @@ __device__ __forceinline__ void split_bf16x4(const f32x4& x, uint2& hi, uint2& l
     hi = make_uint2(H0.u, H1.u); lo = make_uint2(L0.u, L1.u);
 }
 
-template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0>
+template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEO = 0>
 __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev p_kernarg) {
     ConvDev p;
     conv_params_from_lanes(p);       // p_kernarg itself is never touched: see conv_dev.h
@@ -160,8 +160,18 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
     const int mt_i = p.ntiles == 1 ? bid : (p.magic_nt ? (int)__umulhi((unsigned)bid, p.magic_nt) : bid / p.ntiles);
     const int nt_i = bid - mt_i * p.ntiles;
     const int tx = mt_i & (p.tiles_x - 1), ty = (mt_i >> p.txl) & (p.tiles_y - 1), bg = mt_i >> (p.txl + p.tyl);
-    const int TW = 1 << p.TWl, TH = 1 << p.THl;
-    const int b0 = bg * p.TB, y0 = ty * TH, x0 = tx * TW, n0 = nt_i * BN;
+    // the tile geometry of a Block-closing flavour is a constant of the instantiation (GEO, conv_dev.h); a launch reaches it only when
+    // every condition of fin_geo_key() below holds: one source without concat whose GroupNorm groups and statistics slots are those of
+    // the output (Cin = Cout, same cpg, T = Tst), whole column tiles, tables of at most one entry per staging thread
+    constexpr bool GEOC = GEO != 0;
+    constexpr int BM = 32 * MT * WM;
+    static_assert(!GEOC || (!(FL & FL_CAT) && (FL & FL_XF) && geo_Tst(GEO) <= kPartPre), "geometry flavours: transform loader, one source");
+    const int g_TB = GEOC ? geo_TB(GEO) : p.TB;
+    const int g_TWl = GEOC ? geo_TWl(GEO) : p.TWl;
+    const int g_tbsh = GEOC ? geo_log2(BM / geo_TB(GEO)) : p.TWl + p.THl;
+    const int g_THl = GEOC ? geo_log2(BM / geo_TB(GEO)) - geo_TWl(GEO) : p.THl;
+    const int TW = 1 << g_TWl, TH = 1 << g_THl;
+    const int b0 = bg * g_TB, y0 = ty * TH, x0 = tx * TW, n0 = nt_i * BN;
     const int PW = p.PW, PHW = p.PH * p.PW;
     const int C0 = a.s0.C, C1 = a.s1.C, Cin = a.Cin, Cout = a.Cout;
     constexpr bool LEAN = FL != FL_ALL;        // launched for an exact match of the mask only: a set bit means "on"
@@ -176,7 +186,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
     // in front of everything else); here the wait sits where the value is used, after the GroupNorm tables.
     unsigned arrival = 0;
     if (meet && tid == 0) {
-        const gu32* cnt = (const gu32*)(a.fin.sync + b0 / p.TB);
+        const gu32* cnt = (const gu32*)(a.fin.sync + b0 / g_TB);
         asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(arrival) : "v"(cnt), "v"(1u) : "memory");
     }
 
@@ -193,14 +203,14 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         bool p_on = false, p_ss = false;
         int p_gs = 0;
        if (worker) {
-        if (id < p.TB * Cin) {
-            const int tb = id / Cin, c = id - tb * Cin, b = b0 + tb;
+        if (id < g_TB * Cin) {
+            const int tb = GEOC ? ((geo_TB(GEO) > 1 && id >= Cin) ? 1 : 0) : id / Cin, c = id - tb * Cin, b = b0 + tb;
             const bool first = !(FL & FL_CAT) || c < C0;
             const SrcXform& xf = first ? a.s0.xf : a.s1.xf;
             if (b < a.B && xf.mode) {
                 const int cs = first ? c : c - C0, Cs = first ? C0 : C1;
                 p_on = true;
-                p_gs = 2 * ((first ? 0 : p.TB * G0) + tb * xf.G + cs / (Cs / xf.G));
+                p_gs = 2 * ((first ? 0 : p.TB * G0) + tb * xf.G + (GEOC ? cs / geo_cpg(GEO) : cs / (Cs / xf.G)));
                 pg = xf.gamma[cs];
                 pbt = xf.beta[cs];
                 if (xf.ss) {
@@ -210,15 +220,19 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
                 }
             }
         }
-        for (int i = id; i < p.TB * (G0 + G1); i += nthr) {
+        for (int i = id; i < g_TB * (G0 + G1); i += nthr) {
             const bool first = !(FL & FL_CAT) || i < p.TB * G0;
             const SrcXform& xf = first ? a.s0.xf : a.s1.xf;
             const int j = first ? i : i - p.TB * G0;
-            const int tb = j / xf.G, g = j - tb * xf.G, b = b0 + tb;
+            const int tb = GEOC ? ((geo_TB(GEO) > 1 && j >= xf.G) ? 1 : 0) : j / xf.G, g = j - tb * xf.G, b = b0 + tb;
             float mean = 0.f, rstd = 0.f;
-            if (b < a.B) combine_partials(xf, b, g, &mean, &rstd);   // all partial pairs requested at once (stats_dev.h)
+            if (b < a.B) {           // all partial pairs requested at once (stats_dev.h)
+                if constexpr (GEOC) combine_partials_fixed<geo_Tst(GEO)>(xf, b, g, &mean, &rstd);
+                else combine_partials(xf, b, g, &mean, &rstd);
+            }
             gstat[2 * i] = mean;
             gstat[2 * i + 1] = rstd;
+            if (GEOC) break;         // at most one (sample, group) per staging thread
         }
        }
         if ((FL & FL_STAMP) && worker) conv_stamp(p, 2);      // (staging rows) statistics combined: the first cold round trip is over
@@ -229,7 +243,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         lds_only_barrier();
         if ((FL & FL_STAMP) && worker) conv_stamp(p, 4);
        if (worker) {
-        if (id < p.TB * Cin) {
+        if (id < g_TB * Cin) {
             float A = 1.f, Bv = 0.f;
             if (p_on) {
                 A = gstat[p_gs + 1] * pg;
@@ -242,6 +256,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
             }
             aff[id] = make_float2(A, Bv);
         }
+        if (!GEOC)                   // (a geometry flavour: TB Cin <= staging threads)
         for (int i = id + nthr; i < p.TB * Cin; i += nthr) {
             const int tb = i / Cin, c = i - tb * Cin, b = b0 + tb;
             float A = 1.f, Bv = 0.f;
@@ -462,7 +477,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int m = (wm * MT + mt) * 32 + l31;
-            const int tw = m & (TW - 1), th = (m >> p.TWl) & (TH - 1), tb = m >> (p.TWl + p.THl);
+            const int tw = m & (TW - 1), th = (m >> g_TWl) & (TH - 1), tb = m >> g_tbsh;
             abase[mt] = (tb * PHW + th * a.stride * PW + tw * a.stride) * CS + half;
         }
         const int bbase = half * BN + wn * NT * 32 + l31;
@@ -675,7 +690,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         if ((FL & FL_STAMP) && p.stamps && lane == 0) p.stamps[((size_t)blockIdx.x * 8 + wave8) * 16 + 11] = dbg_cbar;
         if (FL & FL_STAMP) conv_stamp(p, 5);
     }
-    conv_epilogue<WM, WN, WK, MT, NT, FL>(p, acc, accr, smem, tid, lane, wave, b0, y0, x0, n0, tx, ty, consumer, NTHR, pre, true);
+    conv_epilogue<WM, WN, WK, MT, NT, FL, GEO>(p, acc, accr, smem, tid, lane, wave, b0, y0, x0, n0, tx, ty, consumer, NTHR, pre, true);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -760,13 +775,31 @@ static int launch_or_query(K kernel, int nthr, const ConvDev& d, int grid, size_
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
+// Diagnostics (fc_debug_conv_routes, tools/flavour_sizes.py): the template arguments of the instantiation every launch went to, one line
+// per launch -- they are the instantiation's name in the code object's symbol table.
+static std::mutex g_route_mu;
+static bool g_route_on = false;
+static std::string g_route_log;
+void conv_route_log_set(bool on) { std::lock_guard<std::mutex> lk(g_route_mu); g_route_on = on; if (on) g_route_log.clear(); }
+std::string conv_route_log_get() { std::lock_guard<std::mutex> lk(g_route_mu); return g_route_log; }
+
+template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEO = 0>
+static int launch_pipe(const ConvDev& d, int grid, size_t lds, hipStream_t s, int* occ) {
+    if (!occ && g_route_on) {
+        std::lock_guard<std::mutex> lk(g_route_mu);
+        const int v[12] = {WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEO};
+        for (int i = 0; i < 12; ++i) g_route_log += std::to_string(v[i]) + (i < 11 ? " " : "\n");
+    }
+    return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEO>), 256 + 64 * NL, d, grid, lds, s, occ);
+}
+
 template <int FL>
 static int lean_launch_wide1(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
     switch (tile) {
 #define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                                       \
     case T:                                                                                                                       \
         if (d.P * (CC / 4) > 64 * NL * kLeanNPL) return -1;                                                                       \
-        return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>), 256 + 64 * NL, d, grid, lds, s, occ);
+        return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>(d, grid, lds, s, occ);
         FC_LEAN_TILES_WIDE1(X)
 #undef X
         default: return -1;
@@ -776,7 +809,7 @@ static int lean_launch_wide1(const ConvDev& d, int tile, int grid, size_t lds, h
 template <int FL>
 static int lean_launch_db4(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
     if (tile != TILE_M32N32K4 || d.P * (32 / 4) > 64 * 8 * kLeanNPL) return -1;
-    return launch_or_query((conv_pipe_kernel<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4>), 256 + 64 * 8, d, grid, lds, s, occ);
+    return launch_pipe<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4>(d, grid, lds, s, occ);
 }
 
 template <int KS, int FL>
@@ -785,11 +818,74 @@ static int lean_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStre
 #define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                                       \
     case T:                                                                                                                       \
         if (d.P * (CC / 4) > 64 * NL * kLeanNPL) return -1;    /* more window elements per staging thread than a lean kernel keeps */ \
-        return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>), 256 + 64 * NL, d, grid, lds, s, occ);
+        return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>(d, grid, lds, s, occ);
         FC_LEAN_TILES(X, KS)
 #undef X
         default: return -1;      // no lean flavour of this tile
     }
+}
+
+// Block-closing (fused tail) GEOMETRY flavours: one per tile geometry of the dim-32 inference plan at 4x32x32 (DESIGN.md section 4 lists the launches
+// behind each row), each as plain / + GroupNorm(1) partials / either with stamps.  X(tile, WM, WN, WK, MT, NT, CC, NL, weights, meeting, key);
+// key = geo_key(statistics form, TB, TW, cpg, Tst), conv_dev.h.  A Block-closing launch of any other geometry runs on the lean flavour of its
+// mask that reads the geometry at run time (FC_LEAN_FLAVOURS_3 above, as before) -- not on the all-in-one kernel, which has no register-fed
+// (FL_W4) form of the 32-row tile: it would sum those layers' products in another order, and be slower.
+#define FC_FIN_GEOMS(X)                                                                                      \
+    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 8, 8))       /* 32 ch @ 32x32 */  \
+    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 16, 2))      /* 64 ch @ 16x16 */  \
+    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 8, 4))      /* 32 ch @ 16x16 */  \
+    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, 0, geo_key(GEO_FAST, 1, 8, 32, 1))            /* 128 ch @ 8x8, a whole group per tile */ \
+    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_MEET, geo_key(GEO_FAST, 1, 8, 16, 2))  /* 64 ch @ 8x8 */    \
+    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, 0, geo_key(GEO_PAIR, 2, 4, 32, 1))        /* 128 ch @ 4x4, two samples per tile */ \
+    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_MEET, geo_key(GEO_PAIR, 2, 4, 64, 2))  /* 256 ch @ 4x4: a group spans two column tiles */
+#define FC_FIN_VARIANTS(Y) Y(0) Y(FL_GN1) Y(FL_STAMP) Y(FL_GN1 | FL_STAMP)
+constexpr int kFinBase = FL_STATS | FL_XF | FL_FIN;
+
+// The geometry key of a Block-closing launch on a tile of BM x BN with `nthr` threads, or 0 when the launch is not one a geometry flavour
+// may take: the flavours assume (and compile in) everything tested here.
+static int fin_geo_key(const ConvDev& d, int BM, int BN, int nthr, bool pair_tile) {
+    const ConvArgs& a = d.a;
+    if (!a.fin.gamma || !a.stats_out || a.par4 || a.stats_tmul != 1 || a.stats_toff != 0 || a.s1.C || !a.s0.xf.mode) return 0;
+    if (d.TB != 1 && d.TB != 2) return 0;
+    if (d.rps != BM / d.TB || (1 << (d.TWl + d.THl)) * d.TB != BM) return 0;
+    const int form = (pair_tile && d.TB == 2 && d.rps == 16) ? GEO_PAIR : (d.TB == 1 ? GEO_FAST : 0);
+    if (!form) return 0;
+    const int cpg = d.cpg, NPG = cpg >= BN ? cpg / BN : 1, ngt = cpg >= BN ? 1 : BN / cpg;
+    if (cpg < 1 || (cpg & (cpg - 1)) || cpg > (1 << 15) || d.cpgt != (cpg < BN ? cpg : BN) || d.NPG != NPG) return 0;
+    const int Tst = (d.TB > 1 ? 1 : d.tiles_x * d.tiles_y) * NPG;
+    if (Tst < 1 || Tst > kPartPre) return 0;
+    if (a.Cout % BN || a.Cin != a.Cout || a.s0.xf.G <= 0 || a.s0.C != a.s0.xf.G * cpg || a.s0.xf.T != Tst) return 0;   // the input is this Block's own h
+    if (d.TB * a.Cin > nthr - 256 || d.TB * a.s0.xf.G > nthr - 256 || d.TB * ngt * Tst * 2 > nthr) return 0;           // one table entry / granule per thread
+    return geo_key(form, d.TB, 1 << d.TWl, cpg, Tst);
+}
+
+static int fin_geom_attr() {
+#define Y(V) FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM_, WN_, WK_, MT_, NT_, CC_, kLeanNPL, 3, NL_, kFinBase | W4_ | MEET_ | (V), 0, GEO_>), \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO)                                                         \
+    {                                                                                                           \
+        constexpr int WM_ = WM, WN_ = WN, WK_ = WK, MT_ = MT, NT_ = NT, CC_ = CC, NL_ = NL, W4_ = W4, MEET_ = MEET, GEO_ = GEO; \
+        FC_FIN_VARIANTS(Y)                                                                                      \
+    }
+    FC_FIN_GEOMS(X)
+#undef X
+#undef Y
+    return FC_OK;
+}
+
+// -1: no flavour of this (tile, weights form, mask, geometry)
+static int fin_geom_launch(const ConvDev& d, int tile, bool w4, int need, int grid, size_t lds, hipStream_t s, int* occ) {
+#define Y(V) if (need == (kFinBase | MEET_ | (V))) return launch_pipe<WM_, WN_, WK_, MT_, NT_, CC_, kLeanNPL, 3, NL_, kFinBase | W4_ | MEET_ | (V), 0, GEO_>(d, grid, lds, s, occ);
+#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO)                                                         \
+    if (tile == T && (w4 ? FL_W4 : 0) == (W4) && d.P * (CC / 4) <= 64 * NL * kLeanNPL &&                        \
+        fin_geo_key(d, 32 * MT * WM, 32 * NT * WN, 256 + 64 * NL, WM * MT == 1 && WN * NT == 1) == (GEO)) {     \
+        constexpr int WM_ = WM, WN_ = WN, WK_ = WK, MT_ = MT, NT_ = NT, CC_ = CC, NL_ = NL, W4_ = W4, MEET_ = MEET, GEO_ = GEO; \
+        FC_FIN_VARIANTS(Y)                                                                                      \
+    }
+    FC_FIN_GEOMS(X)
+#undef X
+#undef Y
+    return -1;
 }
 
 // (four staging waves as in the fp32 form: eight measured 364 against 380 images/s on the SD-VAE decode)
@@ -810,7 +906,7 @@ template <int KS>
 static int bf3_launch_ks(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
     switch (tile) {
 #define X(T, WM, WN, WK, MT, NT, CC, K, NL) \
-    case T: return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, 8, K, NL, FL_ALL, 1>), 256 + 64 * NL, d, grid, lds, s, occ);
+    case T: return launch_pipe<WM, WN, WK, MT, NT, CC, 8, K, NL, FL_ALL, 1>(d, grid, lds, s, occ);
         FC_BF3_TILES(X, KS)
 #undef X
         default: return fail(FC_E_ARG, "conv: no split-bf16 form of this tile");
@@ -836,6 +932,7 @@ int conv_pipe_init() {
     FC_LEAN_FLAVOURS_1(X)
 #undef X
     FC_TRY((lean_attr<2, 0>()));
+    FC_TRY(fin_geom_attr());
     done = true;
     return FC_OK;
 }
@@ -846,7 +943,7 @@ template <int KS>
 static int pipe_launch_ks(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
     switch (tile) {
 #define X(T, WM, WN, WK, MT, NT, CC, K, NL) \
-    case T: return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, 8, K, NL>), 256 + 64 * NL, d, grid, lds, s, occ);
+    case T: return launch_pipe<WM, WN, WK, MT, NT, CC, 8, K, NL>(d, grid, lds, s, occ);
         FC_PIPE_TILES(X, KS)
 #undef X
         default: return fail(FC_E_ARG, "conv: bad tile id");
@@ -868,6 +965,7 @@ static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, 
             // register-fed weights in the k-step-quad layout: whole 32-channel chunks, whole 32-column tiles, the centre tap at (1, 1)
             const bool w4 = small_tile && d.a.w4 && d.a.Cin % 32 == 0 && d.a.Cout % 32 == 0 && d.a.pad == 1 && !d.a.w_batch_stride &&
                             (!d.a.res_out || d.a.res_w4);
+            if (need & FL_FIN) r = fin_geom_launch(d, tile, w4, need, grid, lds, s, occ);    // Block-closing: the flavour of exactly this geometry, if there is one
             if (w4) {
 #define X(F) if (r == -1 && need == (F)) r = lean_launch_db4<(F)>(d, tile, grid, lds, s, occ);
                 FC_LEAN_FLAVOURS_3(X)
@@ -897,15 +995,15 @@ static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, 
 int conv_pipe_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s) { return conv_pipe_dispatch(d, tile, grid, lds, s, nullptr); }
 
 // Workgroups of the instantiation this launch would go to that ONE CU holds at once (registers, waves and LDS as the runtime counts
-// them), cached per (tile, kernel size, flavour mask, LDS bytes).  0 = the query failed.
+// them), cached per (tile, kernel size, flavour mask, LDS bytes, statistics geometry: a Block-closing launch's flavour depends on it).  0 = the query failed.
 int conv_pipe_blocks_per_cu(const ConvDev& d, int tile, size_t lds) {
-    static std::map<std::tuple<int, int, int, size_t>, int> cache;
+    static std::map<std::tuple<int, int, int, size_t, int, int>, int> cache;
     static std::mutex mu;
     const int mask = (d.a.fin.gamma ? FL_FIN : 0) | (d.a.res_out ? FL_RES : 0) | (d.a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |
                      (d.a.s1.C ? FL_CAT : 0) | (d.stamps ? FL_STAMP : 0) | (d.a.stats_out ? FL_STATS : 0) | (d.a.fin.gn1_out ? FL_GN1 : 0) |
                      ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | (d.o_out < 0 ? FL_NARROW : 0) | (d.TB > 1 ? FL_MULTI : 0) |
                      ((d.a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
-    const auto key = std::make_tuple(tile, d.a.KS, mask, lds);
+    const auto key = std::make_tuple(tile, d.a.KS, mask | (d.a.w4 ? FL_W4 : 0), lds, d.cpg, d.TB * 4096 + (d.TWl << 8) + d.tiles_x * d.tiles_y * d.NPG);
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;

@@ -76,6 +76,30 @@ __device__ __forceinline__ void combine_partials(const SrcXform& xf, int b, int 
     partials_finish(xf, b, g, r, mean_out, rstd_out);
 }
 
+// The same for a compile-time T <= kPartPre: T loads, then a straight line of T terms in the same order (no predicated slots, no tail loops).
+template <int T>
+__device__ __forceinline__ void combine_partials_fixed(const SrcXform& xf, int b, int g, float* mean_out, float* rstd_out) {
+    static_assert(T >= 1 && T <= kPartPre, "a fixed T is one of the preloaded slots");
+    const float* sp = xf.stats + (size_t)(b * xf.G + g) * T * 2;
+    float m[T], q[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) { m[t] = sp[2 * t]; q[t] = sp[2 * t + 1]; }
+    float sm = 0.f;
+#pragma unroll
+    for (int t = 0; t < T; ++t) sm += m[t];
+    const float mean = sm / (float)T;
+    float m2 = 0.f, dv = 0.f;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const float d = m[t] - mean;
+        m2 += q[t];
+        dv += d * d;
+    }
+    const float var = (m2 + xf.n_t * dv) / (xf.n_t * (float)T);
+    *mean_out = mean;
+    *rstd_out = 1.0f / sqrtf(var + xf.eps);
+}
+
 __device__ __forceinline__ float silu_grad_e(float z) {   // d/dz [z sigmoid(z)]
     const float s = 1.0f / (1.0f + __expf(-z));
     return s * (1.0f + z * (1.0f - s));
