@@ -35,3 +35,4 @@ def apply_runtime_defaults(workload: str = "sampling") -> bool:
 
 
 from .unet import Unet  # noqa: F401,E402
+from .ot import OTPlanSampler, compute_ot_pairing, compute_ot_plan, sample_plan  # noqa: F401,E402

@@ -154,6 +154,10 @@ SIGNATURES = {
     "fc_ot_pairing": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "fc_ot_pairing_exact": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
     "fc_ot_assign": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "fc_ot_sinkhorn": (_i, [_vp, _i, C.c_double, _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "fc_ot_plan_sinkhorn": (_i, [_vp, _vp, _i, _i64, C.c_double, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "fc_ot_sample_plan": (_i, [_vp, _i, _i, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "fc_ot_plan_pairing": (_i, [_vp, _i, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -95,6 +95,57 @@ def ot_assign(cost: torch.Tensor):
     return perm, duals
 
 
+def _sinkhorn_outputs(bsz: int, dev):
+    return (torch.empty(bsz, bsz, device=dev, dtype=torch.float32), torch.empty(2, bsz, device=dev, dtype=torch.float64),
+            torch.empty(3, device=dev, dtype=torch.float64))
+
+
+def ot_sinkhorn(cost: torch.Tensor, reg: float, max_iter: int = 1000, stop_thr: float = 1e-9):
+    """The log-domain Sinkhorn solver alone on a [B,B] cost matrix; returns (plan fp32 [B,B], duals fp64 [2,B] = (f, g), info fp64 [3]
+    = (iterations, converged, err))."""
+    bsz = cost.shape[0]
+    c = cost.reshape(bsz, bsz).float().contiguous()
+    plan, duals, info = _sinkhorn_outputs(bsz, c.device)
+    B.check(B.lib().fc_ot_sinkhorn(B.ptr(c), bsz, float(reg), int(max_iter), float(stop_thr), B.ptr(plan), B.ptr(duals), B.ptr(info),
+                                   B.current_stream(c.device)))
+    return plan, duals, info
+
+
+def ot_plan_sinkhorn(source: torch.Tensor, target: torch.Tensor, reg: float, normalize_cost: bool = False, max_iter: int = 1000,
+                     stop_thr: float = 1e-9):
+    """Squared-distance matrix (optionally divided by its maximum) and the Sinkhorn solver; returns (plan, cost [B,B] as the solver saw
+    it, duals [2,B], info [3])."""
+    bsz = source.shape[0]
+    s = source.reshape(bsz, -1).float().contiguous()
+    t = target.reshape(bsz, -1).float().contiguous()
+    cost = torch.empty(bsz, bsz, device=s.device, dtype=torch.float32)
+    plan, duals, info = _sinkhorn_outputs(bsz, s.device)
+    B.check(B.lib().fc_ot_plan_sinkhorn(B.ptr(s), B.ptr(t), bsz, s.shape[1], float(reg), int(bool(normalize_cost)), int(max_iter),
+                                        float(stop_thr), B.ptr(plan), B.ptr(duals), B.ptr(info), B.ptr(cost), B.current_stream(s.device)))
+    return plan, cost, duals, info
+
+
+def ot_sample_plan(plan: torch.Tensor, n_pairs: int, seed: int = 0, draw_index: int = 0, info: Optional[torch.Tensor] = None):
+    """``n_pairs`` index pairs drawn with replacement from a [B,B] plan; returns (i, j) int64 [n_pairs].  ``info``: an int32 [1] device
+    tensor that is set to 1 when the plan's sum is not positive and finite."""
+    bsz = plan.shape[0]
+    p = plan.reshape(bsz, bsz).float().contiguous()
+    i = torch.empty(int(n_pairs), device=p.device, dtype=torch.int64)
+    j = torch.empty(int(n_pairs), device=p.device, dtype=torch.int64)
+    B.check(B.lib().fc_ot_sample_plan(B.ptr(p), bsz, int(n_pairs), int(seed) & 0xffffffffffffffff, int(draw_index), B.ptr(i), B.ptr(j),
+                                      B.ptr(info), B.current_stream(p.device)))
+    return i, j
+
+
+def ot_plan_pairing(plan: torch.Tensor):
+    """A [B,B] plan as a permutation: row by row the largest entry among the unused columns."""
+    bsz = plan.shape[0]
+    p = plan.reshape(bsz, bsz).float().contiguous()
+    perm = torch.empty(bsz, device=p.device, dtype=torch.int64)
+    B.check(B.lib().fc_ot_plan_pairing(B.ptr(p), bsz, B.ptr(perm), B.current_stream(p.device)))
+    return perm
+
+
 def conv_wgrad_debug(x0: torch.Tensor, dy: torch.Tensor, ks: int, x1=None, *, pad=0, stride=1, upsample=False):
     """Weight / bias gradient of one convolution from its NCHW input(s) and NCHW output gradient: (dW [O,I,KH,KW], db [O])."""
     dev = x0.device

@@ -474,9 +474,18 @@ int adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, si
                     float eps, int step, float ema_decay, int do_adam, hipStream_t s, const int* skip_flag_dev = nullptr);
 
 // ---- OT (ot.hip) ------------------------------------------------------------------------------
+// what the OT solvers may compare: NaN and +-inf become the one finite sentinel
+__device__ __forceinline__ float ot_finite(float x) { return fabsf(x) <= 3.402823466e+38f ? x : 3.402823466e+38f; }
 int ot_launch(const float* src, const float* tgt, int B, int64_t D, float* dist, int64_t* perm, hipStream_t s);
 // exact pairing: cost = squared distances (non-finite -> FLT_MAX), then the linear assignment solver; duals null or [2B] (u then v)
 int ot_exact_launch(const float* src, const float* tgt, int B, int64_t D, float* cost, int64_t* perm, double* duals, hipStream_t s);
 int ot_assign_launch(const float* cost, int B, int64_t* perm, double* duals, hipStream_t s);
+int ot_sqdist_launch(const float* src, const float* tgt, int B, int64_t D, float* cost, hipStream_t s);      // 1 <= B <= 1024, unchecked
+int ot_sweep_largest_launch(const float* plan, int B, int64_t* perm, hipStream_t s);
+// ---- OT plans (ot_plan.hip) -------------------------------------------------------------------
+int ot_sinkhorn_launch(const float* cost, int B, double reg, int max_iter, double stop_thr, float* plan, double* duals, double* info, hipStream_t s);
+int ot_normalize_launch(float* cost, int B, hipStream_t s);
+int ot_sample_plan_launch(const float* plan, int B, int n_pairs, uint64_t seed, uint32_t draw, int64_t* i_out, int64_t* j_out, int* info,
+                          hipStream_t s);
 
 }  // namespace fc

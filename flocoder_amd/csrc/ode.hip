@@ -7,6 +7,7 @@
 // interval: ode_rk4_stage_kernel / ode_rk4_final_kernel (one template each, plain and measurement-guided) and the likelihood pair
 // ode_ll_stage_kernel / ode_ll_final_kernel, which differs in its partition (one workgroup per sample), not in its arithmetic.
 #include "common.h"
+#include "philox.h"
 
 namespace fc {
 
@@ -943,16 +944,6 @@ int ode_ll_dot_launch(const float* eps, const float* g, double* out, int B, int 
 // so |z| <= sqrt(48 ln 2) = 5.77 (u >= 2^-24).  A value depends on (seed, draw, sample id, position in the sample) alone: not on the row
 // the sample sits in, the batch size or the launch geometry.
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 __device__ __forceinline__ float philox_u01(unsigned r) { return mul_(add_((float)(r >> 9), 0.5f), 1.1920928955078125e-07f); }   // 2^-23
 __device__ __forceinline__ void box_muller(float u, float w_half, float* zc, float* zs) {
     const float R = __fsqrt_rn(mul_(-2.0f, logf(u)));

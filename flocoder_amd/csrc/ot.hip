@@ -6,6 +6,8 @@
 // bit per owned column in a register, (value, index) lexicographic min by cross-lane shuffles -- no LDS,
 // no barriers, next row prefetched while the current one is reduced.
 //
+// Plans: ot_plan.hip (entropic plans, sampling from a plan) uses the squared-distance kernels and the sweep with the comparison turned round.
+//
 // Exact: c = squared distances (the same kernels with SQ set, non-finite entries stored as FLT_MAX), then the linear assignment
 // solver `ot_assign_kernel` below: shortest augmenting paths with fp64 duals, one wave64, every loop bounded by B.
 #include <float.h>
@@ -15,9 +17,6 @@
 namespace fc {
 
 constexpr int OT_T = 16, OT_K = 64;
-
-// what the assignment solver may compare: NaN and +-inf become the one finite sentinel
-__device__ __forceinline__ float ot_finite(float x) { return fabsf(x) <= FLT_MAX ? x : FLT_MAX; }
 
 // grid (ceil(B/16), ceil(B/16)), 256 threads: thread (r, c) of a 16x16 tile.  SQ: squared distances for the exact pairing.
 template <bool SQ = false>
@@ -59,7 +58,9 @@ __global__ void __launch_bounds__(256) ot_dist_small_kernel(const float* src, co
     if (in && kg == 0) dist[(size_t)i * B + j] = SQ ? ot_finite(acc) : sqrtf(acc);
 }
 
-// 1 block of 64 threads; B <= 4096
+// 1 block of 64 threads; B <= 4096.  LARGEST turns the comparison round: row by row the largest entry among the unused columns (first
+// maximum), the sweep that turns a transport plan into a permutation (fc_ot_plan_pairing).
+template <bool LARGEST = false>
 __global__ void __launch_bounds__(64) ot_sweep_kernel(const float* dist, int B, long long* perm) {
     // the sweep is one dependent step per row; with the matrix in LDS (B <= 128) a step is an LDS read and six shuffles instead of a
     // round trip to memory (59 -> 15 us at B = 64)
@@ -73,20 +74,20 @@ __global__ void __launch_bounds__(64) ot_sweep_kernel(const float* dist, int B, 
     unsigned long long used = 0ull;
     for (int i = 0; i < B; ++i) {
         const float* row = staged ? sd + i * B : dist + (size_t)i * B;
-        float best = INFINITY;
+        float best = LARGEST ? -INFINITY : INFINITY;
         int bj = 0x7fffffff;
         for (int q = 0; q < per; ++q) {
             const int j = q * 64 + lane;
             if (j < B && !((used >> q) & 1ull)) {
                 const float v = row[j];
-                if (v < best) { best = v; bj = j; }   // ascending j per lane: keeps the first minimum
+                if (LARGEST ? v > best : v < best) { best = v; bj = j; }   // ascending j per lane: keeps the first minimum
             }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(best, o);
             const int oj = __shfl_xor(bj, o);
-            if (ov < best || (ov == best && oj < bj)) { best = ov; bj = oj; }
+            if ((LARGEST ? ov > best : ov < best) || (ov == best && oj < bj)) { best = ov; bj = oj; }
         }
         if (bj == 0x7fffffff) {   // no finite minimum in this row (NaN / inf distances): take the first unused column, keep perm a permutation
             for (int q = 0; q < per; ++q) {
@@ -107,14 +108,21 @@ int ot_launch(const float* src, const float* tgt, int B, int64_t D, float* dist,
     else if (B <= 128) hipLaunchKernelGGL(ot_dist_small_kernel<8>, dim3(cdiv(B, 8), cdiv(B, 8)), dim3(256), 0, s, src, tgt, B, (long)D, dist);
     else hipLaunchKernelGGL(ot_dist_kernel<false>, dim3(cdiv(B, OT_T), cdiv(B, OT_T)), dim3(256), 0, s, src, tgt, B, (long)D, dist);
     FC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ot_sweep_kernel, dim3(1), dim3(64), 0, s, dist, B, reinterpret_cast<long long*>(perm));
+    hipLaunchKernelGGL(ot_sweep_kernel<false>, dim3(1), dim3(64), 0, s, dist, B, reinterpret_cast<long long*>(perm));
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
 
 int ot_sweep_only_launch(const float* dist, int B, int64_t* perm, hipStream_t s) {
     if (B < 1 || B > 4096) return fail(FC_E_SHAPE, "ot: batch must be in [1, 4096]");
-    hipLaunchKernelGGL(ot_sweep_kernel, dim3(1), dim3(64), 0, s, dist, B, reinterpret_cast<long long*>(perm));
+    hipLaunchKernelGGL(ot_sweep_kernel<false>, dim3(1), dim3(64), 0, s, dist, B, reinterpret_cast<long long*>(perm));
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
+int ot_sweep_largest_launch(const float* plan, int B, int64_t* perm, hipStream_t s) {
+    if (B < 1 || B > 4096) return fail(FC_E_SHAPE, "ot: batch must be in [1, 4096]");
+    hipLaunchKernelGGL(ot_sweep_kernel<true>, dim3(1), dim3(64), 0, s, plan, B, reinterpret_cast<long long*>(perm));
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -292,8 +300,7 @@ int ot_assign_launch(const float* cost, int B, int64_t* perm, double* duals, hip
     return ot_assign_run<16, false>(cost, B, perm, duals, s);
 }
 
-int ot_exact_launch(const float* src, const float* tgt, int B, int64_t D, float* cost, int64_t* perm, double* duals, hipStream_t s) {
-    if (B < 1 || B > 1024) return fail(FC_E_SHAPE, "ot (exact): batch must be in [1, 1024]");
+int ot_sqdist_launch(const float* src, const float* tgt, int B, int64_t D, float* cost, hipStream_t s) {
     if (B <= 64)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(ot_dist_small_kernel<4, true>), dim3(cdiv(B, 4), cdiv(B, 4)), dim3(256), 0, s, src, tgt, B, (long)D, cost);
     else if (B <= 128)
@@ -301,6 +308,12 @@ int ot_exact_launch(const float* src, const float* tgt, int B, int64_t D, float*
     else
         hipLaunchKernelGGL(ot_dist_kernel<true>, dim3(cdiv(B, OT_T), cdiv(B, OT_T)), dim3(256), 0, s, src, tgt, B, (long)D, cost);
     FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
+int ot_exact_launch(const float* src, const float* tgt, int B, int64_t D, float* cost, int64_t* perm, double* duals, hipStream_t s) {
+    if (B < 1 || B > 1024) return fail(FC_E_SHAPE, "ot (exact): batch must be in [1, 1024]");
+    FC_TRY(ot_sqdist_launch(src, tgt, B, D, cost, s));
     return ot_assign_launch(cost, B, perm, duals, s);
 }
 

@@ -1,0 +1,21 @@
+// The project's counter-based generator: one Philox4x32-10 block (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11).
+// flocoder_amd/noise.py (philox4x32) is its host form.  Users and their counter regions:
+//   ode.hip   the SDE samplers' normal field    counter (j, draw, sample id lo, sample id hi)
+//   ot_plan.hip   the plan sampler's uniforms   counter (k, draw, 0x4F54504C, 0xFFFFFFFF): a sample id with the top word all ones is negative
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace fc {
+
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+}  // namespace fc

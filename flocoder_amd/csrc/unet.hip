@@ -1239,4 +1239,39 @@ int fc_ot_assign(const float* cost_dev, int batch, int64_t* perm_out_dev, double
     return ot_assign_launch(cost_dev, batch, perm_out_dev, duals_out_dev, static_cast<hipStream_t>(stream));
 }
 
+int fc_ot_sinkhorn(const float* cost_dev, int batch, double reg, int max_iter, double stop_thr, float* plan_out_dev, double* duals_out_dev,
+                   double* info_out_dev, void* stream) {
+    if (batch < 1 || batch > 1024) return fail(FC_E_SHAPE, "fc_ot_sinkhorn: batch must be in [1, 1024]");
+    if (!cost_dev || !plan_out_dev || !duals_out_dev || !info_out_dev) return fail(FC_E_ARG, "fc_ot_sinkhorn: null argument");
+    return ot_sinkhorn_launch(cost_dev, batch, reg, max_iter, stop_thr, plan_out_dev, duals_out_dev, info_out_dev, static_cast<hipStream_t>(stream));
+}
+
+int fc_ot_plan_sinkhorn(const float* source_dev, const float* target_dev, int batch, int64_t dim, double reg, int normalize_cost, int max_iter,
+                        double stop_thr, float* plan_out_dev, double* duals_out_dev, double* info_out_dev, float* cost_ws_dev, void* stream) {
+    if (batch < 1 || batch > 1024) return fail(FC_E_SHAPE, "fc_ot_plan_sinkhorn: batch must be in [1, 1024]");
+    if (dim < 1) return fail(FC_E_SHAPE, "fc_ot_plan_sinkhorn: dim must be positive");
+    if (!source_dev || !target_dev || !plan_out_dev || !duals_out_dev || !info_out_dev || !cost_ws_dev)
+        return fail(FC_E_ARG, "fc_ot_plan_sinkhorn: null argument");
+    if (!(reg > 0.0) || !(stop_thr >= 0.0) || max_iter < 1 || max_iter > 10000)      // before anything is launched
+        return fail(FC_E_ARG, "fc_ot_plan_sinkhorn: reg must be positive, stop_thr >= 0 and max_iter in [1, 10000]");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FC_TRY(ot_sqdist_launch(source_dev, target_dev, batch, dim, cost_ws_dev, s));
+    if (normalize_cost) FC_TRY(ot_normalize_launch(cost_ws_dev, batch, s));
+    return ot_sinkhorn_launch(cost_ws_dev, batch, reg, max_iter, stop_thr, plan_out_dev, duals_out_dev, info_out_dev, s);
+}
+
+int fc_ot_sample_plan(const float* plan_dev, int batch, int n_pairs, uint64_t seed, uint32_t draw_index, int64_t* i_out_dev, int64_t* j_out_dev,
+                      int* info_dev, void* stream) {
+    if (batch < 1 || batch > 1024) return fail(FC_E_SHAPE, "fc_ot_sample_plan: batch must be in [1, 1024]");
+    if (n_pairs < 1 || n_pairs > 65536) return fail(FC_E_SHAPE, "fc_ot_sample_plan: n_pairs must be in [1, 65536]");
+    if (!plan_dev || !i_out_dev || !j_out_dev) return fail(FC_E_ARG, "fc_ot_sample_plan: null argument");
+    return ot_sample_plan_launch(plan_dev, batch, n_pairs, seed, draw_index, i_out_dev, j_out_dev, info_dev, static_cast<hipStream_t>(stream));
+}
+
+int fc_ot_plan_pairing(const float* plan_dev, int batch, int64_t* perm_out_dev, void* stream) {
+    if (batch < 1 || batch > 1024) return fail(FC_E_SHAPE, "fc_ot_plan_pairing: batch must be in [1, 1024]");
+    if (!plan_dev || !perm_out_dev) return fail(FC_E_ARG, "fc_ot_plan_pairing: null argument");
+    return ot_sweep_largest_launch(plan_dev, batch, perm_out_dev, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -73,3 +73,32 @@ def normal_field(seed: int, draw_index: int, sample_ids, per_sample: int) -> np.
     a0, a1 = 2.0 * np.pi * u[..., 1], 2.0 * np.pi * u[..., 3]
     z = np.stack([r0 * np.cos(a0), r0 * np.sin(a0), r1 * np.cos(a1), r1 * np.sin(a1)], axis=-1)
     return z.reshape(z.shape[0], int(per_sample))
+
+
+# ---- the plan sampler's uniforms (csrc/ot_plan.hip, fc_ot_sample_plan) ------------------------------------------------------------------
+PLAN_TAG = 0x4F54504C            # "OTPL": counter word 2 of the plan sampler; word 3 is 0xFFFFFFFF, a sample id no non-negative int64 has
+
+
+def uniforms53(r0, r1) -> np.ndarray:
+    """``((r0 >> 5) 2^26 + (r1 >> 6) + 0.5) 2^-53`` as fp64: a 53-bit uniform from two Philox words, in (0, 1) -- but for the single
+    pair of words with all 53 bits set, whose sum 2^53 - 1/2 rounds to 2^53 (u = 1); inversion clamps to the last cell."""
+    hi = (np.asarray(r0, dtype=np.uint32) >> np.uint32(5)).astype(np.float64)
+    lo = (np.asarray(r1, dtype=np.uint32) >> np.uint32(6)).astype(np.float64)
+    return (hi * 67108864.0 + lo + 0.5) * 2.0 ** -53
+
+
+def plan_uniforms(seed: int, draw_index: int, n: int) -> np.ndarray:
+    """fp64 ``[n]``: the uniform that ``fc_ot_sample_plan`` inverts for pair k of draw ``draw_index``: words 0 and 1 of the Philox block
+    with counter ``(k, draw_index, PLAN_TAG, 0xFFFFFFFF)`` and the seed's two words as the key."""
+    if not 0 <= int(draw_index) <= 0xffffffff:
+        raise ValueError("draw_index is a 32-bit counter word")
+    if not 0 <= int(n) <= 0xffffffff:
+        raise ValueError("n must fit a 32-bit counter word")
+    seed = int(seed) & 0xffffffffffffffff
+    ctr = np.empty((int(n), 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(int(n), dtype=np.uint64)
+    ctr[:, 1] = np.uint64(int(draw_index))
+    ctr[:, 2] = np.uint64(PLAN_TAG)
+    ctr[:, 3] = np.uint64(0xFFFFFFFF)
+    w = philox4x32(ctr, np.array([seed & 0xffffffff, seed >> 32], dtype=np.uint64))
+    return uniforms53(w[:, 0], w[:, 1])

@@ -28,7 +28,7 @@ import torch
 from . import _binding as B
 from .dist import average_gradients
 from .inpainting import mask_blending
-from .ot import compute_ot_pairing
+from .ot import compute_ot_pairing, compute_ot_plan, sample_plan
 from .sampling import warp_time
 
 
@@ -78,11 +78,15 @@ def _mark_dirty(module) -> None:
 
 
 def batch_to_data(batch, device, pre_encoded=True, mask_encoder=None, epoch=None, curriculum_epochs=10, extend_epochs=20,
-                  blank_latents=None, ot_method="greedy"):
+                  blank_latents=None, ot_method="greedy", ot_draw=(0, 0), ot_reg=None):
     """train_flow.py:90-182: unpack a (latents | dict, class) batch, draw the source noise, encode / blend the inpainting mask and
-    re-index the TARGET by the OT pairing (``ot_method``: "greedy" as upstream, or "exact").  The on-the-fly mask augmentation is a
-    no-op upstream (p_ones = p_zeros = 0, train_flow.py:129-133) and is therefore absent.  Returns (source, target, class_cond, mask,
-    mask_pixels)."""
+    re-index the TARGET by the OT pairing (``ot_method``: "greedy" as upstream, "exact", or "sinkhorn" -- the entropic plan as a
+    permutation).  ``ot_method="sinkhorn_sample"`` draws the batch's pairs (i, j) with replacement from the entropic plan instead
+    (torchcfm's sampler; ``ot_draw`` = (seed, draw_index) of the draw): the source rows are re-indexed by i, the target and the class
+    labels by j; with a mask batch it raises, because source, mask and target belong to one example there.  ``ot_reg``: the entropic
+    regularisation of the two sinkhorn methods, relative to the largest cost (the matrix is always normalised here: on raw squared
+    distances of latents the solver does not converge); None = upstream's 0.1 for "sinkhorn", 0.05 for "sinkhorn_sample".  The on-the-fly mask augmentation is a no-op upstream (p_ones = p_zeros = 0, train_flow.py:129-133) and is therefore
+    absent.  Returns (source, target, class_cond, mask, mask_pixels)."""
     source, mask, mask_pixels = None, None, None
     if not pre_encoded:
         raise NotImplementedError("batch_to_data: only pre-encoded latents are supported (pre_encoded=True is hard-wired upstream, train_flow.py:213)")
@@ -98,6 +102,9 @@ def batch_to_data(batch, device, pre_encoded=True, mask_encoder=None, epoch=None
             source = data['source_latents'].to(device)
     else:
         target, class_cond = data.to(device), class_cond.to(device)
+    if ot_method == "sinkhorn_sample" and mask is not None:
+        raise ValueError("batch_to_data: ot_method='sinkhorn_sample' re-draws source and target rows independently; an inpainting batch "
+                         "ties source, mask and target to one example")
     noise = torch.randn_like(target)
     if mask is None:
         source = noise
@@ -106,7 +113,11 @@ def batch_to_data(batch, device, pre_encoded=True, mask_encoder=None, epoch=None
         source = mask_blending(source, mask, noise)
     else:
         raise AssertionError("Unintended edge case in batch_to_data (train_flow.py:149)")
-    ot_indices = compute_ot_pairing(source, target, method=ot_method)
+    if ot_method == "sinkhorn_sample":
+        plan = compute_ot_plan(source, target, reg=0.05 if ot_reg is None else ot_reg, normalize_cost=True)
+        i, j = sample_plan(plan, seed=ot_draw[0], draw_index=ot_draw[1])
+        return source[i], target[j], class_cond[j], mask, mask_pixels
+    ot_indices = compute_ot_pairing(source, target, method=ot_method, **({} if ot_reg is None else {"reg": ot_reg}))
     target = target[ot_indices]
     return source, target, class_cond, mask, mask_pixels
 
@@ -154,6 +165,7 @@ class FlowTrainer:
         self.distributed = (dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1) if distributed is None else distributed
         # the 10 % conditioning drop (train_flow.py:343-345) is drawn from a generator every rank seeds alike, so replicas drop together
         self._drop_rng = random.Random(0x5EED) if self.distributed else random
+        self.ot_seed, self.ot_draws = 0, 0                    # train_batch(ot_method="sinkhorn_sample"): the plan sampler's seed and draw counter
         # data-parallel steps start the all-reduce of the late layers' gradients in the middle of the backward (loss_and_grads / finish_gradients)
         self.overlap_comm = os.environ.get("FLOCODER_AMD_NO_COMM_OVERLAP") is None
         self._pending = None
@@ -532,7 +544,8 @@ class FlowTrainer:
     def step(self, source, target, cond=None, u: Optional[torch.Tensor] = None, pairing: Optional[torch.Tensor] = None, *,
              micro_batch: Optional[int] = None):
         """train_flow.py:346-397 for one batch: returns the loss as a 0-d device tensor (no host sync).  ``pairing`` (int64 [B], e.g.
-        from ``compute_ot_pairing``) trains against ``target[pairing]`` without materialising the gather (train_flow.py:350).
+        from ``compute_ot_pairing``) trains against ``target[pairing]`` without materialising the gather (train_flow.py:350); it need not
+        be a permutation -- entries may repeat, as the j of pairs drawn from a plan do (``sample_plan``): the prologue only range-checks.
         ``micro_batch=m``: the same optimiser step with the rows processed in consecutive chunks of ``m`` (the last may be smaller) whose
         gradients are accumulated -- only ``m`` rows are ever reserved; ``pairing`` still ranges over the whole batch."""
         if micro_batch is not None:
@@ -600,7 +613,7 @@ class FlowTrainer:
         self.model.mask_encoder = me                          # as upstream (train_flow.py:333): checkpoints / EMA see it through the model
 
     def inpaint_step(self, source_latents, target, mask_pixels, class_cond=None, noise=None, u=None, drop_cond=False, ot=False,
-                     ot_method="greedy"):
+                     ot_method="greedy", ot_reg=None):
         """One inpainting training step entirely on the device (batch_to_data's mask branch + train_flow.py:346-397):
         mask = MaskEncoder(mask_pixels); source = blend(source_latents, mask, noise); flow loss through the mask-conditioned U-Net;
         + MSE(MaskEncoder(1), 1) + MSE(MaskEncoder(0), 0); backward into both networks (the encoder is reached through the U-Net's
@@ -630,7 +643,7 @@ class FlowTrainer:
                 mask = me._forward_native(mp)
                 source = mask_blending(s0, mask, noise)
                 if ot:                                        # batch_to_data re-indexes the TARGET by the OT pairing (train_flow.py:160-163)
-                    tgt = tgt[compute_ot_pairing(source, tgt, method=ot_method)].contiguous()
+                    tgt = tgt[compute_ot_pairing(source, tgt, method=ot_method, **({} if ot_reg is None else {"reg": ot_reg}))].contiguous()
                 x, v_target = self.interpolate(source, tgt, t)
                 v = self.model._forward_native(x, time, cls, mask, train=True)
                 dv = torch.empty_like(v)
@@ -670,17 +683,24 @@ class FlowTrainer:
         me.mark_dirty()                                       # its flat vector changed under the views: re-upload on next use
         return loss
 
-    def train_batch(self, batch, epoch=None, cfg_drop: float = 0.1, mask_encoder=None, blank_latents=None, ot_method="greedy"):
-        """batch_to_data + the 10 % conditioning drop of train_flow.py:338-345 + step; ``ot_method`` selects the pairing ("greedy" |
-        "exact").  With an attached MaskEncoder and an inpainting batch (dict with mask_pixels) the encoder trains too
-        (``inpaint_step``)."""
+    def train_batch(self, batch, epoch=None, cfg_drop: float = 0.1, mask_encoder=None, blank_latents=None, ot_method="greedy", ot_reg=None):
+        """batch_to_data + the 10 % conditioning drop of train_flow.py:338-345 + step; ``ot_method`` selects the coupling ("greedy" |
+        "exact" | "sinkhorn", permutations of the target, or "sinkhorn_sample": pairs drawn with replacement from the entropic plan,
+        seeded by ``ot_seed`` and counted in ``ot_draws``, both part of ``state_dict()``; not for inpainting batches; ``ot_reg`` as in
+        ``batch_to_data``).  With
+        an attached MaskEncoder and an inpainting batch (dict with mask_pixels) the encoder trains too (``inpaint_step``)."""
         data = batch[0]
+        sampled = ot_method == "sinkhorn_sample"
+        if sampled and isinstance(data, dict) and 'mask_pixels' in data:
+            raise ValueError("train_batch: ot_method='sinkhorn_sample' is not defined for inpainting batches (source, mask and target "
+                             "belong to one example)")
         if getattr(self, "me", None) is not None and isinstance(data, dict) and 'mask_pixels' in data:
             target = data['target_latents'].to(self.device)
             return self.inpaint_step(data['source_latents'], target, data['mask_pixels'].float(), class_cond=batch[1],
-                                     drop_cond=self._drop_rng.random() < cfg_drop, ot=True, ot_method=ot_method)
+                                     drop_cond=self._drop_rng.random() < cfg_drop, ot=True, ot_method=ot_method, ot_reg=ot_reg)
         source, target, class_cond, mask_cond, _ = batch_to_data(batch, self.device, True, mask_encoder, epoch=epoch, blank_latents=blank_latents,
-                                                                    ot_method=ot_method)
+                                                                    ot_method=ot_method, ot_draw=(self.ot_seed, self.ot_draws), ot_reg=ot_reg)
+        self.ot_draws += int(sampled)
         cond = {'class_cond': class_cond, 'mask_cond': mask_cond}
         if self._drop_rng.random() < cfg_drop:
             cond = None
@@ -705,8 +725,9 @@ class FlowTrainer:
     def state_dict(self):
         self.check_class_ids()
         return {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "ema": self.ema.clone(),
-                "step_main": self.step_main, "steps": dict(self.steps)}
+                "step_main": self.step_main, "steps": dict(self.steps), "ot_seed": self.ot_seed, "ot_draws": self.ot_draws}
 
     def load_state_dict(self, sd):
         self.exp_avg.copy_(sd["exp_avg"]); self.exp_avg_sq.copy_(sd["exp_avg_sq"]); self.ema.copy_(sd["ema"])
         self.step_main, self.steps = int(sd["step_main"]), {k: int(v) for k, v in sd["steps"].items()}
+        self.ot_seed, self.ot_draws = int(sd.get("ot_seed", 0)), int(sd.get("ot_draws", 0))      # absent from older checkpoints

@@ -528,6 +528,32 @@ int fc_ot_pairing_exact(const float* source_dev, const float* target_dev, int ba
 /* The solver alone on a caller's cost matrix cost_dev [B][B] fp32 (non-finite entries count as FLT_MAX). */
 int fc_ot_assign(const float* cost_dev, int batch, int64_t* perm_out_dev, double* duals_out_dev, void* stream);
 
+/* Entropic (Sinkhorn) plans between uniform marginals, 1 <= batch <= 1024.  Everything below runs on `stream`, allocates nothing and
+ * never synchronises.
+ *
+ * fc_ot_sinkhorn: the log-domain Sinkhorn-Knopp iteration on cost_dev [B][B] fp32 (non-finite entries count as FLT_MAX):
+ *     f = g = reg log(1/B);  per iteration  g_j = reg (log(1/B) - LSE_i((f_i - C_ij)/reg)),  f_i = reg (log(1/B) - LSE_j((g_j - C_ij)/reg));
+ *     after every 10th iteration err = | colsum(P) - 1/B |_2 with P_ij = exp((f_i + g_j - C_ij)/reg); stop when err < stop_thr or at max_iter.
+ * reg > 0, stop_thr >= 0, 1 <= max_iter <= 10000 (rounded up to a multiple of 10), else FC_E_ARG.  POT's defaults: 1000, 1e-9.
+ * plan_out_dev [B][B] fp32 (row sums 1/B to rounding: the row half comes last); duals_out_dev 2*B doubles, f then g;
+ * info_out_dev 3 doubles: {iterations run, converged (1.0 / 0.0), err at the last check}. */
+int fc_ot_sinkhorn(const float* cost_dev, int batch, double reg, int max_iter, double stop_thr, float* plan_out_dev, double* duals_out_dev,
+                   double* info_out_dev, void* stream);
+/* The plan between source_dev / target_dev [B,D] fp32 under the squared Euclidean cost; normalize_cost != 0 divides the matrix by its
+ * largest entry first (torchcfm's option; FLT_MAX sentinels are left out of the maximum and of the division, an all-zero matrix is left
+ * alone).  cost_ws_dev: B*B floats, the matrix the solver saw on return; the other outputs as fc_ot_sinkhorn. */
+int fc_ot_plan_sinkhorn(const float* source_dev, const float* target_dev, int batch, int64_t dim, double reg, int normalize_cost, int max_iter,
+                        double stop_thr, float* plan_out_dev, double* duals_out_dev, double* info_out_dev, float* cost_ws_dev, void* stream);
+/* n_pairs (1 .. 65536) index pairs drawn with replacement from plan_dev [B][B] read as a categorical over its cells (torchcfm's
+ * sample_map): pair k inverts the two-level fp64 cdf at the 53-bit uniform of Philox4x32-10 block (counter (k, draw_index, 0x4F54504C,
+ * 0xFFFFFFFF), key = seed); flocoder_amd/noise.py plan_uniforms is the host form.  i_out_dev / j_out_dev [n_pairs] int64.  A plan whose
+ * sum is not positive and finite gives the pairs (k mod B, k mod B) and sets *info_dev = 1 (info_dev may be NULL; never cleared here). */
+int fc_ot_sample_plan(const float* plan_dev, int batch, int n_pairs, uint64_t seed, uint32_t draw_index, int64_t* i_out_dev, int64_t* j_out_dev,
+                      int* info_dev, void* stream);
+/* A plan as a permutation (upstream's compute_ot_pairing_vanilla): for rows in order the largest entry among the unused columns, ties to
+ * the lowest column. */
+int fc_ot_plan_pairing(const float* plan_dev, int batch, int64_t* perm_out_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Parity metrics  (replace flocoder/metrics.py:40-54 sinkhorn_loss: geomloss SamplesLoss("sinkhorn", p=2, blur=0.05))
  * ---------------------------------------------------------------------------------------------- */
