@@ -114,7 +114,10 @@ __device__ __forceinline__ void conv_params_from_lanes(ConvDev& p) {
 // at every launch), and a launch is short.  Measured: with the tail code merely compiled OUT the un-fused sampler ran 2.9 % faster.
 constexpr int FL_FIN = 1, FL_RES = 2, FL_POST = 4, FL_XF = 8, FL_CAT = 16, FL_STAMP = 32, FL_STATS = 64, FL_GN1 = 128, FL_POSTOP = 256,
               FL_NARROW = 512, FL_MULTI = 1024, FL_MEET = 2048, FL_ALL = 4095, FL_W4 = 4096;
+constexpr int FL_WW = 8192;
 // (4096, outside FL_ALL: the 32-row tile at 3x3 reads its weights from the k-step-quad copy -- ConvArgs::w4 -- 16 bytes per lane)
+// (8192, FL_W4 Block-closing flavours only: the WHOLE input window -- every Cin chunk, transformed -- is staged into LDS once, in the
+// prologue, by all twelve waves; the K loop then holds neither staging nor chunk barriers.  conv_pipe.hip "WW")
 // (8: the input may carry a GroupNorm / FiLM / SiLU transform, 16: a second, concatenated source, 32: diagnostic phase stamps, 64: GroupNorm
 // partials of the output, 128: GroupNorm(1) partials of the tail's result, 256: activation / addend on the output, 512: per-lane dword
 // stores when the LDS image for the wide stores does not fit, 1024: several samples per tile -- always on for the 32-row tile,

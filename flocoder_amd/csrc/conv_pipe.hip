@@ -106,6 +106,10 @@ __device__ __forceinline__ void split_bf16x4(const f32x4& x, uint2& hi, uint2& l
     hi = make_uint2(H0.u, H1.u); lo = make_uint2(L0.u, L1.u);
 }
 
+// WW: GroupNorm groups of the layers the geometry flavours are made for (the dim-32 plan's; with the key's cpg: Cin = 4 cpg -- the launch
+// path checks it), and window elements a thread of the run-time-geometry form may hold
+constexpr int kFinGeomGroups = 4, kWWSlots = 8;
+
 template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEO = 0>
 __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev p_kernarg) {
     ConvDev p;
@@ -130,6 +134,13 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
 #define FC_DB4_CHAINS 2
 #endif
     constexpr int DB4_CHAINS = FC_DB4_CHAINS;
+    // WW ("whole window", Block-closing DB4 flavours): the staging waves' GroupNorm / FiLM / SiLU work does not overlap the MFMAs of the
+    // accumulator wave they share a SIMD with, and at 4x4 / 8x8 every column tile of a sample pair transforms the same
+    // window.  Here ALL twelve waves stage every Cin chunk of the window, transformed, before the first MFMA -- the accumulator waves had
+    // nothing to do until then -- at chunk i's place patch0 + i * patch_stride, in the per-chunk layout.  The K loop then holds no staging
+    // and no chunk barrier; the staging waves wait at the barrier in front of the tail.  The launch path sizes the LDS (ww_lds below).
+    constexpr bool WW = (FL & FL_WW) != 0;
+    static_assert(!WW || (DB4 && FL != FL_ALL && (FL & FL_FIN) && (FL & FL_XF) && !(FL & (FL_CAT | FL_RES))), "whole-window staging: register-fed Block-closing flavours");
     // Pixel stride of the staged window in LDS.  CC + 1 keeps the dword operand reads of the MFMA lanes (one pixel per lane) off each other's
     // banks.  DB4 reads a lane's four k-steps of a tap as ONE 16-byte LDS read instead: inside every 8-channel block the window is stored
     // as [parity][4] (channel c at 8 (c / 8) + 4 (c & 1) + ((c >> 1) & 3)), so the channels 8 wk + 2 kk + half, kk = 0..3, are contiguous, and
@@ -304,8 +315,66 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         }
     }
 
+    // ---- WW: this thread's share of the whole window.  Element e = tid + k NTHR is channel quad e % (Cin / 4) of window pixel e / (Cin / 4):
+    // a pixel's channels are read by consecutive lanes.  A geometry flavour knows every count (kFinGeomGroups GroupNorm groups of cpg
+    // channels, a TH x TW tile with its one-pixel halo) and unrolls fully; the run-time form keeps up to kWWSlots elements per thread.
+    constexpr int WW_CQ = GEOC ? geo_cpg(GEO) * kFinGeomGroups / 4 : 0, WW_PW = GEOC ? (1 << geo_TWl(GEO)) + 2 : 0;
+    constexpr int WW_PHW = GEOC ? (BM / geo_TB(GEO) / (1 << geo_TWl(GEO)) + 2) * WW_PW : 0, WW_E = GEOC ? geo_TB(GEO) * WW_PHW * WW_CQ : 0;
+    constexpr int WWK = !WW ? 1 : (GEOC ? (WW_E + NTHR - 1) / NTHR : kWWSlots);
+    f32x4 wv[WWK];
+    int w_lds[WWK], w_aff[WWK];    // LDS float offset (-1: no element) / index of the affine pair (-1: padding or a sample beyond B: stays zero)
+    const int ww_cq = GEOC ? WW_CQ : Cin >> 2, ww_pw = GEOC ? WW_PW : PW, ww_phw = GEOC ? WW_PHW : PHW, ww_E = GEOC ? WW_E : p.P * (Cin >> 2);
+    const int ww_nk = GEOC ? WWK : __builtin_amdgcn_readfirstlane((ww_E + NTHR - 1) / NTHR);
+    auto ww_request = [&]() {      // every load issued back to back; ordinary loads: they stay pending across gn_tables()
+        const int Hin = a.Hs << a.ups, Win = a.Ws << a.ups;
+        const float rcq = __builtin_amdgcn_rcpf((float)ww_cq);   // run-time form: e / ww_cq for e < 2^13 (ww_lds), exact with the half added
+#pragma unroll
+        for (int k = 0; k < WWK; ++k) {
+            if (!GEOC && k >= ww_nk) break;
+            const int e = tid + k * NTHR;
+            w_lds[k] = -1; w_aff[k] = -1;
+            const float* src = p.zeros16;
+            if (e < ww_E) {
+                const int pix = GEOC ? e / ww_cq : (int)(((float)e + 0.5f) * rcq), cq = e - pix * ww_cq;
+                const int tb = GEOC ? pix / ww_phw : fastdiv(pix, p.magic_phw), r = pix - tb * ww_phw;
+                const int py = GEOC ? r / ww_pw : fastdiv(r, p.magic_pw), px = r - py * ww_pw;
+                const int iy = y0 * a.stride - (a.pad_y >= 0 ? a.pad_y : a.pad) + py, ix = x0 * a.stride - (a.pad_x >= 0 ? a.pad_x : a.pad) + px, b = b0 + tb;
+                if (b < a.B && iy >= 0 && iy < Hin && ix >= 0 && ix < Win) {
+                    src = a.s0.p + (size_t)((b * a.Hs + (iy >> a.ups)) * a.Ws + (ix >> a.ups)) * C0 + 4 * cq;
+                    w_aff[k] = tb * Cin + 4 * cq;
+                }
+                w_lds[k] = (cq >> 3) * p.patch_stride + pix * CS + 8 * ((cq & 7) >> 1) + 2 * (cq & 1);
+            }
+            wv[k] = *reinterpret_cast<const f32x4*>(src);
+        }
+    };
+    auto ww_store = [&]() {        // ... and on into LDS, transformed exactly as the per-chunk loader's store_patch does
+#pragma unroll
+        for (int k = 0; k < WWK; ++k) {
+            if (!GEOC && k >= ww_nk) break;
+            if (w_lds[k] < 0) continue;
+            f32x4 x = wv[k];
+            if (w_aff[k] >= 0) {
+                const float2* ab = aff + w_aff[k];
+                x.x = ab[0].x * x.x + ab[0].y; x.y = ab[1].x * x.y + ab[1].y;
+                x.z = ab[2].x * x.z + ab[2].y; x.w = ab[3].x * x.w + ab[3].y;
+                if (p.act0) { x.x = silu_f(x.x); x.y = silu_f(x.y); x.z = silu_f(x.z); x.w = silu_f(x.w); }
+            }
+            float* d = patch0 + w_lds[k];
+            d[0] = x.x; d[1] = x.z; d[4] = x.y; d[5] = x.w;      // [parity][4] inside the 8-channel block
+        }
+    };
+
     if (!consumer) {
         // =========================================== LOADERS ===========================================
+      if constexpr (WW) {
+        ww_request();
+        if (FL & FL_STAMP) conv_stamp(p, 1);
+        gn_tables(true, ltid, LT);
+        ww_store();
+        if (FL & FL_STAMP) conv_stamp(p, 3);      // (staging rows) the whole window is in LDS
+        loader_handover();                        // every chunk ready; nothing left to stage: on to the barrier in front of the tail
+      } else {
         // Waves 4+ are the younger half of the workgroup: at equal priority the SIMD's issue arbitration (priority, then age) hands them
         // the slots the MFMA waves leave over, and the consumers then sit at the chunk barrier waiting for a stage the loaders could
         // not issue fast enough (stamps: 5 k cycles to issue three loads per thread).  s_setprio is scalar: the branch is wave-uniform.
@@ -471,6 +540,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
             d[9] = dbg_mem; d[10] = dbg_store; d[11] = dbg_bar; d[12] = dbg_issue; d[13] = dbg_dma;
         }
         __builtin_amdgcn_s_setprio(0);   // staging is over: in the epilogue the accumulator waves are the ones with work to do
+      }
     } else {
         // =========================================== CONSUMERS ===========================================
         int abase[MT];
@@ -517,8 +587,10 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         };
         if (DB4) fetch4(0, wA, rA);
         else if (DB) fetch_w(0, wcur, rcur);
+        if constexpr (WW) ww_request();
         if (FL & FL_STAMP) conv_stamp(p, 1);
         gn_tables(false, 0, 1);
+        if constexpr (WW) ww_store();
         if (meet && tid == 0) {
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(arrival) :: "memory");
             smem[p.o_epoch] = __uint_as_float(arrival / (unsigned)p.gsz + 1u);
@@ -533,7 +605,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
             // (a whole chunk of MFMAs of lookahead), and nothing is copied.  The A operands of tap t + 1 are read from LDS before the
             // MFMAs of tap t are issued.
             auto chunk = [&](int i, f32x4 (&wc)[NQ], f32x4& rc, f32x4 (&wn)[NQ], f32x4& rn) {
-                const float* patch = patch0 + (i & 1) * p.patch_stride;
+                const float* patch = patch0 + (WW ? i : (i & 1)) * p.patch_stride;
                 // UNCONDITIONAL (the last chunk re-requests itself): s_waitcnt takes an immediate, so with a conditional request the
                 // compiler must count for the path that skipped it -- vmcnt(8) instead of vmcnt(17) in front of the first MFMA, i.e. a wait
                 // for the request issued two lines above
@@ -544,7 +616,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
                 // Pinned schedule: the operand quad of tap t + 1 is requested (asm: the compiler neither counts nor moves it), then the four
                 // MFMAs of tap t run -- 256 cycles of cover for the LDS round trip --, then the wait.  Left to the scheduler the reads
                 // ended up directly in front of their first use (s_waitcnt lgkmcnt right behind ds_read, every eighth MFMA).
-                const unsigned pl = smem_lds + 4u * (unsigned)(p.o_patch + (i & 1) * p.patch_stride + abase4);
+                const unsigned pl = smem_lds + 4u * (unsigned)(p.o_patch + (WW ? i : (i & 1)) * p.patch_stride + abase4);
                 const unsigned prow = 4u * (unsigned)(PW * CS);
                 auto lds_quad = [&](f32x4& dst, int tapn) {
                     const unsigned ad = pl + (unsigned)(tapn / KS) * prow;
@@ -582,9 +654,11 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
 #pragma unroll
                     for (int kk = 0; kk < KPW; ++kk) accr[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], rc[kk], accr[0][0], 0, 0, 0);
                 }
+                if constexpr (!WW) {                     // (WW: every chunk is in LDS already, nothing is handed over)
                 unsigned long long t0 = ((FL & FL_STAMP) && p.stamps) ? __builtin_amdgcn_s_memtime() : 0ull;
                 loader_handover();                       // not __syncthreads(): its vmcnt(0) would wait for the weights requested above
                 if ((FL & FL_STAMP) && p.stamps) dbg_cbar += __builtin_amdgcn_s_memtime() - t0;
+                }
             };
             for (int i = 0; i < nchunks; i += 2) {
                 chunk(i, wA, rA, wB, rB);
@@ -690,6 +764,9 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         if ((FL & FL_STAMP) && p.stamps && lane == 0) p.stamps[((size_t)blockIdx.x * 8 + wave8) * 16 + 11] = dbg_cbar;
         if (FL & FL_STAMP) conv_stamp(p, 5);
     }
+    // WW: the one barrier the K loop no longer has -- every accumulator wave has read its last operands, the window (which the tail's
+    // scratch aliases) is dead.  lgkmcnt only: a wave's outstanding global requests are not waited for here
+    if constexpr (WW) loader_handover();
     conv_epilogue<WM, WN, WK, MT, NT, FL, GEO>(p, acc, accr, smem, tid, lane, wave, b0, y0, x0, n0, tx, ty, consumer, NTHR, pre, true);
 }
 
@@ -745,11 +822,16 @@ static int lean_attr() {
     return FC_OK;
 }
 
-// the k-step-quad (FL_W4) flavours exist for the one tile that feeds its weights from registers: M32N32K4 at 3x3
+// the k-step-quad (FL_W4) flavours exist for the one tile that feeds its weights from registers: M32N32K4 at 3x3; the Block-closing
+// ones among them also in the whole-window form (FL_WW)
+constexpr bool ww_flavour(int FL) { return (FL & FL_FIN) && (FL & FL_XF) && !(FL & (FL_CAT | FL_RES)); }
 template <int FL>
 static int lean_attr_db4() {
     FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if constexpr (ww_flavour(FL))
+        FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4 | FL_WW>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return FC_OK;
 }
 
@@ -812,6 +894,25 @@ static int lean_launch_db4(const ConvDev& d, int tile, int grid, size_t lds, hip
     return launch_pipe<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4>(d, grid, lds, s, occ);
 }
 
+// Whole-window staging (FL_WW): the LDS bytes of the launch in that form, or 0 when it keeps the per-chunk loader -- the window of all Cin
+// chunks (chunk i at o_patch + i patch_stride; the tail's scratch aliases it as before) does not fit, a thread would hold more than
+// kWWSlots elements, or the grid needs two workgroups per CU, which the larger LDS may not allow.  The caller has checked the
+// register-fed form's own conditions (`w4`: whole 32-channel chunks, pad 1).
+static int g_pipe_cus = 0;
+static size_t ww_lds(const ConvDev& d, int tile, size_t lds) {
+    const ConvArgs& a = d.a;
+    if (tile != TILE_M32N32K4 || a.KS != 3 || !a.fin.gamma || a.s1.C || !a.s0.xf.mode || a.res_out || a.stride != 1) return 0;
+    if ((long)d.P * (a.Cin / 4) > (long)kWWSlots * 768 || d.nblocks > g_pipe_cus) return 0;
+    const size_t win = (size_t)(d.o_patch + d.nchunks * d.patch_stride) * sizeof(float), tot = win > lds ? win : lds;
+    return tot <= 160 * 1024 ? tot : 0;
+}
+
+template <int FL>
+static int lean_launch_ww(const ConvDev& d, int tile, int grid, size_t lds_ww, hipStream_t s, int* occ) {
+    if constexpr (ww_flavour(FL)) return launch_pipe<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4 | FL_WW>(d, grid, lds_ww, s, occ);
+    else return -1;
+}
+
 template <int KS, int FL>
 static int lean_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
     switch (tile) {
@@ -859,32 +960,52 @@ static int fin_geo_key(const ConvDev& d, int BM, int BN, int nthr, bool pair_til
     return geo_key(form, d.TB, 1 << d.TWl, cpg, Tst);
 }
 
-static int fin_geom_attr() {
-#define Y(V) FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM_, WN_, WK_, MT_, NT_, CC_, kLeanNPL, 3, NL_, kFinBase | W4_ | MEET_ | (V), 0, GEO_>), \
+template <int WM, int WN, int WK, int MT, int NT, int CC, int NL, int W4, int MEET, int GEO>
+static int fin_geom_row_attr() {
+#define Y(V) FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | MEET | (V), 0, GEO>), \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO)                                                         \
-    {                                                                                                           \
-        constexpr int WM_ = WM, WN_ = WN, WK_ = WK, MT_ = MT, NT_ = NT, CC_ = CC, NL_ = NL, W4_ = W4, MEET_ = MEET, GEO_ = GEO; \
-        FC_FIN_VARIANTS(Y)                                                                                      \
+    FC_FIN_VARIANTS(Y)
+#undef Y
+    if constexpr (W4 != 0) {         // the register-fed rows also in the whole-window form
+#define Y(V) FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | FL_WW | MEET | (V), 0, GEO>), \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        FC_FIN_VARIANTS(Y)
+#undef Y
     }
+    return FC_OK;
+}
+static int fin_geom_attr() {
+#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO) FC_TRY((fin_geom_row_attr<WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO>()));
     FC_FIN_GEOMS(X)
 #undef X
-#undef Y
     return FC_OK;
 }
 
+// one row of FC_FIN_GEOMS, its geometry matched already: the whole-window form when the launch may take it (lds_ww != 0, and the layer
+// has the groups the flavour's trip counts assume), else the per-chunk form.  -1: no variant of this mask
+template <int WM, int WN, int WK, int MT, int NT, int CC, int NL, int W4, int MEET, int GEO>
+static int fin_geom_row_launch(const ConvDev& d, int need, int grid, size_t lds, size_t lds_ww, hipStream_t s, int* occ) {
+    if constexpr (W4 != 0) {
+        if (lds_ww && d.a.Cin == kFinGeomGroups * geo_cpg(GEO)) {
+#define Y(V) if (need == (kFinBase | MEET | (V))) return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | FL_WW | MEET | (V), 0, GEO>(d, grid, lds_ww, s, occ);
+            FC_FIN_VARIANTS(Y)
+#undef Y
+        }
+    }
+#define Y(V) if (need == (kFinBase | MEET | (V))) return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | MEET | (V), 0, GEO>(d, grid, lds, s, occ);
+    FC_FIN_VARIANTS(Y)
+#undef Y
+    return -1;
+}
+
 // -1: no flavour of this (tile, weights form, mask, geometry)
-static int fin_geom_launch(const ConvDev& d, int tile, bool w4, int need, int grid, size_t lds, hipStream_t s, int* occ) {
-#define Y(V) if (need == (kFinBase | MEET_ | (V))) return launch_pipe<WM_, WN_, WK_, MT_, NT_, CC_, kLeanNPL, 3, NL_, kFinBase | W4_ | MEET_ | (V), 0, GEO_>(d, grid, lds, s, occ);
+static int fin_geom_launch(const ConvDev& d, int tile, bool w4, int need, int grid, size_t lds, size_t lds_ww, hipStream_t s, int* occ) {
 #define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO)                                                         \
     if (tile == T && (w4 ? FL_W4 : 0) == (W4) && d.P * (CC / 4) <= 64 * NL * kLeanNPL &&                        \
-        fin_geo_key(d, 32 * MT * WM, 32 * NT * WN, 256 + 64 * NL, WM * MT == 1 && WN * NT == 1) == (GEO)) {     \
-        constexpr int WM_ = WM, WN_ = WN, WK_ = WK, MT_ = MT, NT_ = NT, CC_ = CC, NL_ = NL, W4_ = W4, MEET_ = MEET, GEO_ = GEO; \
-        FC_FIN_VARIANTS(Y)                                                                                      \
-    }
+        fin_geo_key(d, 32 * MT * WM, 32 * NT * WN, 256 + 64 * NL, WM * MT == 1 && WN * NT == 1) == (GEO))       \
+        return fin_geom_row_launch<WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO>(d, need, grid, lds, lds_ww, s, occ);
     FC_FIN_GEOMS(X)
 #undef X
-#undef Y
     return -1;
 }
 
@@ -919,6 +1040,13 @@ int conv_pipe_init() {
     FC_TRY(bf3_attr_ks<1>());
     FC_TRY(bf3_attr_ks<2>());
     FC_TRY(bf3_attr_ks<3>());
+    {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        FC_HIP(hipGetDevice(&dev));
+        FC_HIP(hipGetDeviceProperties(&prop, dev));
+        g_pipe_cus = prop.multiProcessorCount;
+    }
     FC_HIP(hipMalloc(reinterpret_cast<void**>(&g_zeros16), 256));
     FC_HIP(hipMemset(g_zeros16, 0, 256));
     FC_TRY(pipe_attr_ks<1>());
@@ -965,7 +1093,13 @@ static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, 
             // register-fed weights in the k-step-quad layout: whole 32-channel chunks, whole 32-column tiles, the centre tap at (1, 1)
             const bool w4 = small_tile && d.a.w4 && d.a.Cin % 32 == 0 && d.a.Cout % 32 == 0 && d.a.pad == 1 && !d.a.w_batch_stride &&
                             (!d.a.res_out || d.a.res_w4);
-            if (need & FL_FIN) r = fin_geom_launch(d, tile, w4, need, grid, lds, s, occ);    // Block-closing: the flavour of exactly this geometry, if there is one
+            const size_t lds_ww = (w4 && (need & FL_FIN)) ? ww_lds(d, tile, lds) : 0;        // whole-window staging, where the launch may take it
+            if (need & FL_FIN) r = fin_geom_launch(d, tile, w4, need, grid, lds, lds_ww, s, occ);    // Block-closing: the flavour of exactly this geometry, if there is one
+            if (lds_ww) {
+#define X(F) if (r == -1 && need == (F)) r = lean_launch_ww<(F)>(d, tile, grid, lds_ww, s, occ);
+                FC_LEAN_FLAVOURS_3(X)
+#undef X
+            }
             if (w4) {
 #define X(F) if (r == -1 && need == (F)) r = lean_launch_db4<(F)>(d, tile, grid, lds, s, occ);
                 FC_LEAN_FLAVOURS_3(X)
@@ -1003,7 +1137,9 @@ int conv_pipe_blocks_per_cu(const ConvDev& d, int tile, size_t lds) {
                      (d.a.s1.C ? FL_CAT : 0) | (d.stamps ? FL_STAMP : 0) | (d.a.stats_out ? FL_STATS : 0) | (d.a.fin.gn1_out ? FL_GN1 : 0) |
                      ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | (d.o_out < 0 ? FL_NARROW : 0) | (d.TB > 1 ? FL_MULTI : 0) |
                      ((d.a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
-    const auto key = std::make_tuple(tile, d.a.KS, mask | (d.a.w4 ? FL_W4 : 0), lds, d.cpg, d.TB * 4096 + (d.TWl << 8) + d.tiles_x * d.tiles_y * d.NPG);
+    // (whether a launch takes the whole-window form depends on its grid and Cin as well: part of the key)
+    const int ww = (d.a.KS == 3 && d.a.w4 && ww_lds(d, tile, lds)) ? d.a.Cin : 0;
+    const auto key = std::make_tuple(tile, d.a.KS, mask | (d.a.w4 ? FL_W4 : 0), lds, d.cpg, d.TB * 4096 + (d.TWl << 8) + d.tiles_x * d.tiles_y * d.NPG + (ww << 13));
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
