@@ -86,6 +86,8 @@ SIGNATURES = {
     "fc_unet_train_release": (_i, [_vp]),
     "fc_unet_vjp_op_info": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
     "fc_unet_log_likelihood": (_i, [_vp, _vp, _i, _i, _i, _pf, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fc_unet_log_likelihood_rk45": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _vp, _i, _vp, _i, _vp,
+                                         _vp, _pi, _vp]),
     "fc_debug_probe_dot": (_i, [_vp, _vp, _vp, _i, _i64, _vp]),
     "fc_unet_integrate_guided": (_i, [_vp, _vp, _i, _i, _i, _pf, _i, _f, _vp, _f, _vp, _i, _vp, _vp, _f, _f, _i, _vp]),
     "fc_ode_guided_correct": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _vp]),

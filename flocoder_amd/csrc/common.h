@@ -327,6 +327,11 @@ struct Rk45Status { int unfinished, failed, pad0, pad1; };   // groups still ste
 // (with CFG also their unguided twins G*spg + row).  Batch-coupled: G = 1, spg = B; per sample: G = B, spg = 1.  The elementwise and
 // partial-sum kernels run on a (chunks, G) grid; partial sums are [G][chunks][2] and `chunks` fixes their summation order.
 struct Rk45Groups { int G, spg, m, chunks; };
+// The divergence track of the adaptive likelihood (fc_unet_log_likelihood_rk45): row r carries a[r] beside its x, da/dt = d = sum eps g.
+// a: [2][B] fp64, a | a_new of the attempt in flight; d: [7][B] fp64, the a-component's K0..K6 (ode_ll_dot_launch behind evaluation s
+// writes row s; row 0 is the committed one).  B = G * spg.  The launches that take one (null: the sampler) run the instantiation in
+// which the a-components join the group's norms, n = m + spg unknowns.
+struct Rk45LL { double *a, *d; int B; };
 int rk45_chunks(int m, int cap);           // workgroups per group over m unknowns: one per 1024, at most `cap`
 // y = double(x), xs = x, states for (t0 -> t1), time rows of f(t0)
 int rk45_setup_launch(const Rk45Groups& g, const float* x, double* y, float* xs, Rk45State* st, double t0, double t1, double rtol,
@@ -334,11 +339,12 @@ int rk45_setup_launch(const Rk45Groups& g, const float* x, double* y, float* xs,
 // select_initial_step: K0 = f0 and d0/d1 partials | h0 and the time rows of f1 | xs = y0 + h0 f0 | d2 partials | h1, first attempt
 int rk45_d01_launch(const Rk45Groups& g, const Rk45State* st, const double* y, float* k0, const float* v2, int cfg_on, float cfg,
                     double* part, hipStream_t s);
-int rk45_h0_launch(const Rk45Groups& g, Rk45State* st, const double* part, float t_scale, float* tvec, int cfg_on, hipStream_t s);
+int rk45_h0_launch(const Rk45Groups& g, Rk45State* st, const double* part, float t_scale, float* tvec, int cfg_on, const Rk45LL* ll,
+                   hipStream_t s);
 int rk45_y1_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, float* xs, hipStream_t s);
 int rk45_d2_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, const float* v2, int cfg_on, float cfg,
                    double* part, hipStream_t s);
-int rk45_h1_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s);
+int rk45_h1_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45LL* ll, hipStream_t s);
 // one attempt: stages 1..5 (K[s-1] = blend(v2), xs = y + h sum A K), finish (K5, y_new), error partials (K6), controllers, [dense
 // output,] commit, status summary
 int rk45_stage_launch(const Rk45Groups& g, const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int cfg_on,
@@ -348,7 +354,7 @@ int rk45_finish_launch(const Rk45Groups& g, const Rk45State* st, const double* y
 int rk45_error_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const double* y_new, Rk45K kk, const float* v2,
                       int cfg_on, float cfg, double* part, hipStream_t s);
 // `ev` (may be null): the controller of an accepted step also records the range of requested times that step serves
-int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45Eval* ev, hipStream_t s);
+int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45Eval* ev, const Rk45LL* ll, hipStream_t s);
 // dense output, between control and commit: frames[j] = float32(y + h Q p(x_j)) for every j in the range an accepted step serves
 // (scipy's RkDenseOutput, from y and K0..K6 of that step)
 int rk45_dense_launch(const Rk45Groups& g, const Rk45State* st, const Rk45Eval* ev, const double* y, Rk45K kk, hipStream_t s);

@@ -283,6 +283,14 @@ int ode_guided_correct_launch(const float* v, const float* x, const float* ym, c
 // Dense output (solve_ivp's t_eval, Rk45Eval): the step sequence is untouched.  The controller of an accepted step records which
 // requested times fall into it, and rk45_dense -- between the decision and the commit, while y and K0..K6 of the step still stand --
 // writes the step's quartic interpolant (RkDenseOutput) at those times into the caller's frames.
+//
+// The likelihood's augmented state (fc_unet_log_likelihood_rk45, Rk45LL): a group's solve_ivp vector is y = [x (m), a (spg)] with
+// da[r]/dt = d[r] = sum eps g of row r, so n = m + spg unknowns enter every norm.  f does not read a, hence the stage states of the
+// a-component feed nothing and the x kernels are the sampler's as they stand; the a-component's seven K values are the fp64 row sums
+// ll.d[s][r] (ode_ll_dot_kernel behind every evaluation), and everything the a-component adds -- its terms of select_initial_step's
+// three norms, a_new = a + h sum B_s d_s, its term of the error norm with scale atol + rtol max(|a|, |a_new|), the commit a <- a_new,
+// d_0 <- d_6 -- is done by the one thread that owns the group's controller, after the x partials, one term per row in row order.
+// LL is a template flag of those three kernels: the sampler's instantiations hold none of it.
 
 __constant__ double c_rk45_C[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
 __constant__ double c_rk45_A[6][5] = {
@@ -430,15 +438,23 @@ __device__ __forceinline__ double rk45_select_h0(Rk45State* st, double s0, doubl
 }
 
 // select_initial_step, part 2 (one workgroup per group): d0, d1 -> h0; time rows of f(t0 + h0 dir, y1)
+template <bool LL>
 __global__ void __launch_bounds__(256) rk45_h0_kernel(Rk45State* st, const double* part, int chunks, int m, int spg, float t_scale,
-                                                      float* tvec, int cfg_on) {
+                                                      float* tvec, int cfg_on, Rk45LL ll) {
     __shared__ double red[256];
     const int g = blockIdx.x;
     const double* p = part + 2 * (size_t)g * chunks;
-    const double s0 = reduce_parts(p, chunks, 2, 0, red), s1 = reduce_parts(p, chunks, 2, 1, red);
+    double s0 = reduce_parts(p, chunks, 2, 0, red), s1 = reduce_parts(p, chunks, 2, 1, red);
     if (threadIdx.x == 0) {
         Rk45State* sg = st + g;
-        const double h0 = rk45_select_h0(sg, s0, s1, m);
+        if constexpr (LL) {   // the a-component: y0 = a, f0 = d_0
+            for (int r = g * spg; r < (g + 1) * spg; ++r) {
+                const double sc = sg->atol + fabs(ll.a[r]) * sg->rtol;
+                const double a = ll.a[r] / sc, c = ll.d[r] / sc;
+                s0 += a * a; s1 += c * c;
+            }
+        }
+        const double h0 = rk45_select_h0(sg, s0, s1, LL ? m + spg : m);
         const float tv = stage_time(sg->t + h0 * sg->dir, t_scale);
         for (int r = g * spg; r < (g + 1) * spg; ++r) {   // (runs once per solve: one thread writes the group's rows)
             tvec[r] = tv;
@@ -493,12 +509,19 @@ __device__ __forceinline__ void rk45_select_h1(Rk45State* st, double s2, int n) 
 }
 
 // select_initial_step, part 4 (one workgroup per group): d2 -> h1 -> first step; the first attempt's h and t_new
-__global__ void __launch_bounds__(256) rk45_h1_kernel(Rk45State* st, const double* part, int chunks, int m) {
+template <bool LL>
+__global__ void __launch_bounds__(256) rk45_h1_kernel(Rk45State* st, const double* part, int chunks, int m, int spg, Rk45LL ll) {
     __shared__ double red[256];
     const int g = blockIdx.x;
-    const double s2 = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
+    double s2 = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
     if (threadIdx.x == 0) {
-        rk45_select_h1(st + g, s2, m);
+        if constexpr (LL) {   // the a-component: f1 = d_1 (the evaluation at y0 + h0 f0), f0 = d_0
+            for (int r = g * spg; r < (g + 1) * spg; ++r) {
+                const double a = (ll.d[ll.B + r] - ll.d[r]) / (st[g].atol + fabs(ll.a[r]) * st[g].rtol);
+                s2 += a * a;
+            }
+        }
+        rk45_select_h1(st + g, s2, LL ? m + spg : m);
         rk45_freeze(st + g);
     }
 }
@@ -635,9 +658,28 @@ __device__ __forceinline__ void rk45_decide(Rk45State* st, double en) {
     }
 }
 
+// The a-component of row r in the attempt just evaluated (rk_step and the error estimate on ll.d[0..6][r], sums left to right as the x
+// kernels'): a_new into ll.a[B + r]; returns its term of the error norm's sum
+__device__ __forceinline__ double rk45_ll_row(const Rk45State& sg, const Rk45LL& ll, int r) {
+    double yn = 0.0, er = 0.0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const double k = ll.d[(size_t)j * ll.B + r];
+        if (j < 6) yn = j == 0 ? k * c_rk45_B[j] : yn + k * c_rk45_B[j];
+        er = j == 0 ? k * c_rk45_E[j] : er + k * c_rk45_E[j];
+    }
+    const double a = ll.a[r], a_new = a + sg.h * yn;
+    ll.a[ll.B + r] = a_new;
+    const double e = er * sg.h / (sg.atol + np_maximum(fabs(a), fabs(a_new)) * sg.rtol);
+    return e * e;
+}
+
 // one workgroup per group: its error norm and decision, and with a dense-output request (`ev`) the requested times an accepted step
-// serves; a group that no longer steps only clears accepted_last
-__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int chunks, int m, const Rk45Eval* ev) {
+// serves; a group that no longer steps only clears accepted_last.  LL: the rows' a-components join the norm, and an accepted step
+// commits them here (a <- a_new, d_0 <- d_6: FSAL), where the thread that owns them is
+template <bool LL>
+__global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const double* part, int chunks, int m, int spg, const Rk45Eval* ev,
+                                                           Rk45LL ll) {
     __shared__ double red[256];
     const int g = blockIdx.x;
     Rk45State* sg = st + g;
@@ -645,9 +687,15 @@ __global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const 
         if (threadIdx.x == 0) sg->accepted_last = 0;
         return;
     }
-    const double s = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
+    double s = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
     if (threadIdx.x != 0) return;
-    rk45_decide(sg, sqrt(s) / sqrt((double)m));
+    if constexpr (LL)
+        for (int r = g * spg; r < (g + 1) * spg; ++r) s += rk45_ll_row(*sg, ll, r);
+    rk45_decide(sg, sqrt(s) / sqrt((double)(LL ? m + spg : m)));
+    if constexpr (LL) {
+        if (sg->accepted_last)
+            for (int r = g * spg; r < (g + 1) * spg; ++r) { ll.a[r] = ll.a[ll.B + r]; ll.d[r] = ll.d[(size_t)6 * ll.B + r]; }
+    }
     if (ev && sg->accepted_last) rk45_eval_range(sg, ev);
     rk45_freeze(sg);
 }
@@ -753,8 +801,14 @@ int rk45_d01_launch(const Rk45Groups& g, const Rk45State* st, const double* y, f
                     double* part, hipStream_t s) {
     RK45_LAUNCH(rk45_d01_kernel, RK45_GRID, st, y, k0, v2, g.m, cfg_on, cfg, part);
 }
-int rk45_h0_launch(const Rk45Groups& g, Rk45State* st, const double* part, float t_scale, float* tvec, int cfg_on, hipStream_t s) {
-    RK45_LAUNCH(rk45_h0_kernel, dim3(g.G), st, part, g.chunks, g.m, g.spg, t_scale, tvec, cfg_on);
+// `ll` (may be null): the likelihood's instantiation, which needs its whole record and takes no guidance pair
+#define RK45_LL_CHECK                                                                                                   \
+    if (ll && (!ll->a || !ll->d || ll->B != g.G * g.spg)) return fail(FC_E_ARG, "rk45: the likelihood record does not fit the controller groups")
+int rk45_h0_launch(const Rk45Groups& g, Rk45State* st, const double* part, float t_scale, float* tvec, int cfg_on, const Rk45LL* ll,
+                   hipStream_t s) {
+    RK45_LL_CHECK;
+    if (ll) RK45_LAUNCH(rk45_h0_kernel<true>, dim3(g.G), st, part, g.chunks, g.m, g.spg, t_scale, tvec, cfg_on, *ll);
+    RK45_LAUNCH(rk45_h0_kernel<false>, dim3(g.G), st, part, g.chunks, g.m, g.spg, t_scale, tvec, cfg_on, Rk45LL{});
 }
 int rk45_y1_launch(const Rk45Groups& g, const Rk45State* st, const double* y, const float* k0, float* xs, hipStream_t s) {
     RK45_LAUNCH(rk45_y1_kernel, RK45_GRID, st, y, k0, xs, g.m);
@@ -763,8 +817,10 @@ int rk45_d2_launch(const Rk45Groups& g, const Rk45State* st, const double* y, co
                    double* part, hipStream_t s) {
     RK45_LAUNCH(rk45_d2_kernel, RK45_GRID, st, y, k0, v2, g.m, cfg_on, cfg, part);
 }
-int rk45_h1_launch(const Rk45Groups& g, Rk45State* st, const double* part, hipStream_t s) {
-    RK45_LAUNCH(rk45_h1_kernel, dim3(g.G), st, part, g.chunks, g.m);
+int rk45_h1_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45LL* ll, hipStream_t s) {
+    RK45_LL_CHECK;
+    if (ll) RK45_LAUNCH(rk45_h1_kernel<true>, dim3(g.G), st, part, g.chunks, g.m, g.spg, *ll);
+    RK45_LAUNCH(rk45_h1_kernel<false>, dim3(g.G), st, part, g.chunks, g.m, g.spg, Rk45LL{});
 }
 int rk45_stage_launch(const Rk45Groups& g, const Rk45State* st, int stage, const double* y, Rk45K kk, const float* v2, int cfg_on,
                       float cfg, float* xs, float t_scale, float* tvec, hipStream_t s) {
@@ -785,8 +841,10 @@ int rk45_error_launch(const Rk45Groups& g, const Rk45State* st, const double* y,
                       int cfg_on, float cfg, double* part, hipStream_t s) {
     RK45_LAUNCH(rk45_error_kernel, RK45_GRID, st, y, y_new, kk, v2, g.m, cfg_on, cfg, part);
 }
-int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45Eval* ev, hipStream_t s) {
-    RK45_LAUNCH(rk45_control_kernel, dim3(g.G), st, part, g.chunks, g.m, ev);
+int rk45_control_launch(const Rk45Groups& g, Rk45State* st, const double* part, const Rk45Eval* ev, const Rk45LL* ll, hipStream_t s) {
+    RK45_LL_CHECK;
+    if (ll) RK45_LAUNCH(rk45_control_kernel<true>, dim3(g.G), st, part, g.chunks, g.m, g.spg, ev, *ll);
+    RK45_LAUNCH(rk45_control_kernel<false>, dim3(g.G), st, part, g.chunks, g.m, g.spg, ev, Rk45LL{});
 }
 int rk45_dense_launch(const Rk45Groups& g, const Rk45State* st, const Rk45Eval* ev, const double* y, Rk45K kk, hipStream_t s) {
     if (!ev) return fail(FC_E_ARG, "rk45: dense output without a request record");
@@ -799,6 +857,7 @@ int rk45_commit_launch(const Rk45Groups& g, const Rk45State* st, double* y, cons
 int rk45_status_launch(const Rk45Groups& g, const Rk45State* st, Rk45Status* out, hipStream_t s) {
     RK45_LAUNCH(rk45_status_kernel, dim3(1), st, g.G, out);
 }
+#undef RK45_LL_CHECK
 #undef RK45_GRID
 #undef RK45_LAUNCH
 

@@ -615,19 +615,38 @@ static int alloc_rk45(fc_unet* u) {
     return ig.get(&ig.rk_st, u->maxB, tag);       // last: a first call that failed half-way allocates again
 }
 
+// What the adaptive likelihood adds to the controller state (plan lifetime, first use): the divergence track a | a_new and the seven
+// rows of its K values; g of the running evaluation is the RK4 likelihood's buffer.
+static int alloc_rk45_ll(fc_unet* u) {
+    IntegratorState& ig = u->ig;
+    const int m = u->cfg.channels * u->H * u->W;
+    if (!ig.ll_g) {
+        FC_TRY(ig.get(&ig.ll_d, (size_t)u->maxB * 3, "integrator.likelihood"));
+        FC_TRY(ig.get(&ig.ll_g, (size_t)u->maxB * m, "integrator.likelihood"));
+    }
+    if (ig.rk_a) return FC_OK;
+    FC_TRY(ig.get(&ig.rk_d, (size_t)u->maxB * 7, "integrator.rk45_likelihood"));
+    return ig.get(&ig.rk_a, (size_t)u->maxB * 2, "integrator.rk45_likelihood");
+}
+
+// The likelihood side of an adaptive solve (fc_unet_log_likelihood_rk45): every evaluation is the forward, the data-gradient chain with
+// the probe as output cotangent and the per-row reduction d = sum eps g into row `slot` of the divergence track's K values.
+struct Rk45Likelihood { const float* probe; double *a_out, *logp_out; };
+
 // one attempt of RungeKutta._step_impl for every group that still steps: five stages, y_new and f(t + h, y_new), the error norms,
 // the controllers, with a dense-output request (`ev`) the frames an accepted step serves, the commit, the status summary
-static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const FwdCtx& c, int cf, float cfg, float t_scale, const Rk45Eval* ev,
-                                hipStream_t s) {
+// `eval(slot)`: the evaluation that yields K_slot
+static int enqueue_rk45_attempt(fc_unet* u, const Rk45Groups& g, const std::function<int(int)>& eval, int cf, float cfg, float t_scale,
+                                const Rk45Eval* ev, const Rk45LL* ll, hipStream_t s) {
     const IntegratorState& ig = u->ig;
     for (int st = 1; st <= 5; ++st) {
         FC_TRY(rk45_stage_launch(g, ig.rk_st, st, ig.rk_y, ig.rk_k, ig.v2, cf, cfg, ig.xs, t_scale, ig.tvec, s));
-        FC_TRY(run_plan(u->plan, c, s));                                                                      // K_st
+        FC_TRY(eval(st));                                                                                     // K_st
     }
     FC_TRY(rk45_finish_launch(g, ig.rk_st, ig.rk_y, ig.rk_ynew, ig.rk_k, ig.v2, cf, cfg, ig.xs, t_scale, ig.tvec, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t + h, y_new)
+    FC_TRY(eval(6));                                                                                          // f(t + h, y_new)
     FC_TRY(rk45_error_launch(g, ig.rk_st, ig.rk_y, ig.rk_ynew, ig.rk_k, ig.v2, cf, cfg, ig.rk_part, s));
-    FC_TRY(rk45_control_launch(g, ig.rk_st, ig.rk_part, ev, s));
+    FC_TRY(rk45_control_launch(g, ig.rk_st, ig.rk_part, ev, ll, s));
     if (ev) FC_TRY(rk45_dense_launch(g, ig.rk_st, ev, ig.rk_y, ig.rk_k, s));       // reads y and K0..K6 before the commit replaces them
     FC_TRY(rk45_commit_launch(g, ig.rk_st, ig.rk_y, ig.rk_ynew, ig.rk_k.k[0], ig.rk_k.k[6], s));
     return rk45_status_launch(g, ig.rk_st, ig.rk_sum, s);
@@ -668,11 +687,13 @@ static int stage_rk45_eval(fc_unet* u, const double* te, int n_eval, float* fram
     return FC_OK;
 }
 
-// fc_unet_integrate_rk45 (per_sample = false), fc_unet_integrate_rk45_per_sample and, with n_eval > 0, fc_unet_integrate_rk45_dense;
-// `fn` names the entry point in argument errors
+// fc_unet_integrate_rk45 (per_sample = false), fc_unet_integrate_rk45_per_sample, with n_eval > 0 fc_unet_integrate_rk45_dense, and with
+// `lk` fc_unet_log_likelihood_rk45: the same solve over the augmented state [x, a] (ode.hip), every evaluation the training-form forward
+// with the data-gradient chain behind it, launched directly; `fn` names the entry point in argument errors
 static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_dev, int B, int H, int W, double t0, double t1,
                           double rtol, double atol, float t_scale, const int64_t* ids, float cfg_strength, const float* mask,
-                          int mask_is_ones, const double* t_eval, int n_eval, float* frames_dev, int* counters, void* stream) {
+                          int mask_is_ones, const double* t_eval, int n_eval, float* frames_dev, int* counters, void* stream,
+                          const Rk45Likelihood* lk = nullptr) {
     if (!u || !x_dev || !counters || B < 1) return fail(FC_E_ARG, std::string(fn) + ": bad argument");
     if (n_eval < 0 || (n_eval > 0 && (!t_eval || !frames_dev || (reinterpret_cast<uintptr_t>(frames_dev) & 15))))
         return fail(FC_E_ARG, std::string(fn) + ": t_eval needs its times and a 16-byte aligned frames buffer");
@@ -684,6 +705,10 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     CallFrame f;
     FC_TRY(f.begin(u, B, H, W, ids, cfg_strength, mask, mask_is_ones, stream));
     IntegratorState& ig = u->ig;
+    if (lk) {
+        if (!u->keep_all) return fail(FC_E_STATE, std::string(fn) + ": no backward plan for this shape; call fc_unet_train_reserve");
+        FC_TRY(vjp_check(u, B, H, W, fn));
+    }
     const Rk45Groups g = rk45_groups(u, B, per_sample);
     for (int i = 0; i < g.G; ++i) { counters[3 * i] = 1; counters[3 * i + 1] = counters[3 * i + 2] = 0; }   // nfev, accepted, rejected
     const int n = f.n, cf = f.cfg_on ? 1 : 0;
@@ -693,6 +718,7 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
         return FC_OK;
     }
     if (!ig.rk_st) FC_TRY(alloc_rk45(u));
+    if (lk) FC_TRY(alloc_rk45_ll(u));
     if (!ig.rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); ig.rk_host = static_cast<Rk45Status*>(hp); }
     if (!ig.ev_rk) FC_HIP(hipEventCreateWithFlags(&ig.ev_rk, hipEventDisableTiming));
 
@@ -703,14 +729,27 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     // f(t0, y0) and select_initial_step of every group (two forwards, no graph)
     FwdCtx c = integrator_ctx(f);
     c.x = ig.xs;   // every forward of the solve reads the stage input the RK45 kernels write
+    const Rk45LL track{ig.rk_a, ig.rk_d, B};
+    const Rk45LL* ll = lk ? &track : nullptr;
+    const int m1 = n / B;
+    if (lk) {      // v2 = v(xs, tvec), ll_g = (dv/dx)^T probe; a = 0 at t0
+        c.d_out = lk->probe; c.dx_out = ig.ll_g;
+        FC_HIP(hipMemsetAsync(ig.rk_a, 0, (size_t)2 * B * sizeof(double), s));
+    }
+    const std::function<int(int)> eval = [&](int slot) {
+        FC_TRY(run_plan(u->plan, c, s));
+        if (!lk) return (int)FC_OK;
+        FC_TRY(vjp_run(u, c, s));
+        return ode_ll_dot_launch(lk->probe, ig.ll_g, ig.rk_d + (size_t)slot * B, B, m1, s);
+    };
     FC_TRY(rk45_setup_launch(g, x_dev, ig.rk_y, ig.xs, ig.rk_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, ig.tvec, cf, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f0
+    FC_TRY(eval(0));                                                                                          // f0
     FC_TRY(rk45_d01_launch(g, ig.rk_st, ig.rk_y, ig.rk_k.k[0], ig.v2, cf, cfg_strength, ig.rk_part, s));
-    FC_TRY(rk45_h0_launch(g, ig.rk_st, ig.rk_part, t_scale, ig.tvec, cf, s));
+    FC_TRY(rk45_h0_launch(g, ig.rk_st, ig.rk_part, t_scale, ig.tvec, cf, ll, s));
     FC_TRY(rk45_y1_launch(g, ig.rk_st, ig.rk_y, ig.rk_k.k[0], ig.xs, s));
-    FC_TRY(run_plan(u->plan, c, s));                                                                          // f(t0 + h0, y0 + h0 f0)
+    FC_TRY(eval(1));                                                                                          // f(t0 + h0, y0 + h0 f0)
     FC_TRY(rk45_d2_launch(g, ig.rk_st, ig.rk_y, ig.rk_k.k[0], ig.v2, cf, cfg_strength, ig.rk_part, s));
-    FC_TRY(rk45_h1_launch(g, ig.rk_st, ig.rk_part, s));
+    FC_TRY(rk45_h1_launch(g, ig.rk_st, ig.rk_part, ll, s));
     FC_TRY(rk45_status_launch(g, ig.rk_st, ig.rk_sum, s));
     FC_HIP(hipMemcpyAsync(ig.rk_host, ig.rk_sum, sizeof(Rk45Status), hipMemcpyDeviceToHost, s));
     // This wait is also the one fc_unet_integrate makes before its first replay: under AMD_DIRECT_DISPATCH=0 a graph submitted from this
@@ -720,9 +759,9 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     // (an attempt with dense output has one more launch: a different graph)
     GraphKey key = graph_key(f, per_sample ? GraphKey::Rk45PerSample : GraphKey::Rk45Coupled, cfg_strength, t_scale);
     key.dense = ev != nullptr;
-    auto attempt = [&] { return enqueue_rk45_attempt(u, g, c, cf, cfg_strength, t_scale, ev, s); };
+    auto attempt = [&] { return enqueue_rk45_attempt(u, g, eval, cf, cfg_strength, t_scale, ev, ll, s); };
     while (ig.rk_host->unfinished > 0) {
-        if (no_graph()) {
+        if (no_graph() || lk) {   // (the training-form evaluation has never been captured: the likelihood launches directly)
             FC_TRY(attempt());
         } else {   // one attempt = one graph: 6 plan runs and 10 (11 with dense output) small launches, a single chain (no parallel branches)
             hipGraphExec_t exec = nullptr;
@@ -740,6 +779,10 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     for (int i = 0; i < g.G; ++i) { counters[3 * i] = st[i].nfev; counters[3 * i + 1] = st[i].accepted; counters[3 * i + 2] = st[i].rejected; }
     const int failed = ig.rk_host->failed;
     if (!failed) FC_TRY(rk45_out_launch(ig.rk_y, x_dev, n, s));
+    if (!failed && lk) {
+        FC_HIP(hipMemcpyAsync(lk->a_out, ig.rk_a, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s));
+        FC_TRY(ode_ll_logp_launch(x_dev, lk->a_out, lk->logp_out, B, m1, s));
+    }
     FC_TRY(f.leave());
     if (!failed) return FC_OK;
     if (!per_sample) {
@@ -775,6 +818,22 @@ int fc_unet_integrate_rk45_dense(fc_unet* u, int per_sample, float* x_dev, int B
                                  const double* t_eval_host, int n_eval, float* frames_dev, int* counters, void* stream) {
     return integrate_rk45(u, per_sample != 0, "fc_unet_integrate_rk45_dense", x_dev, B, H, W, t0, t1, rtol, atol, t_scale, ids,
                           cfg_strength, mask, mask_is_ones, t_eval_host, n_eval, frames_dev, counters, stream);
+}
+
+// ---- adaptive likelihood ----------------------------------------------------------------------------------------------------------
+// x from t0 back to t1 < t0 with the adaptive solve above over [x, a]: the integration error of a and z is the controller's, not a
+// grid's.  The host waits on the status summary behind every attempt, as the sampler; x_inout, a_out and logp_out are written only when
+// every group finished.
+int fc_unet_log_likelihood_rk45(fc_unet* u, float* x_inout, int batch, int H, int W, double t0, double t1, double rtol, double atol,
+                                float t_scale, const int64_t* class_ids, const float* mask, int mask_is_ones, const float* probe,
+                                int per_sample, double* a_out, double* logp_out, int* counters, void* stream) {
+    const char* fn = "fc_unet_log_likelihood_rk45";
+    if (!u || !x_inout || !probe || !a_out || !logp_out || !counters || batch < 1) return fail(FC_E_ARG, std::string(fn) + ": null argument");
+    if (!(t1 < t0) || !(t1 >= 0.0) || !(t0 <= 1.0)) return fail(FC_E_ARG, std::string(fn) + ": needs 0 <= t1 < t0 <= 1 (data at t0 towards noise)");
+    FC_TRY(check_aligned16({x_inout, probe}, "fc_unet_log_likelihood_rk45: x and the probe must be 16-byte aligned (the kernels read them as float4)"));
+    const Rk45Likelihood lk{probe, a_out, logp_out};
+    return integrate_rk45(u, per_sample != 0, fn, x_inout, batch, H, W, t0, t1, rtol, atol, t_scale, class_ids, 0.0f, mask, mask_is_ones,
+                          nullptr, 0, nullptr, counters, stream, &lk);
 }
 
 }  // extern "C"

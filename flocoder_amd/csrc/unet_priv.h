@@ -42,6 +42,9 @@ struct IntegratorPlanState {
     Rk45K rk_k{};
     Rk45State* rk_st = nullptr;
     Rk45Status* rk_sum = nullptr;
+    // adaptive likelihood (fc_unet_log_likelihood_rk45): the divergence track a | a_new ([2][maxB]) and its K values ([7][maxB]),
+    // allocated by the first call (g is ll_g below)
+    double *rk_a = nullptr, *rk_d = nullptr;
     // likelihood (fc_unet_log_likelihood): g = (dv/dx)^T eps of the running stage and the per-sample stage sums d1..d3 of the running
     // interval, allocated by the first call
     float* ll_g = nullptr;

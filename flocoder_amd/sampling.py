@@ -340,14 +340,76 @@ def _reverse_grid(n_steps, dtype=torch.float32):
     return rk4_time_grid(int(n_steps), dtype=dtype).flip(0)
 
 
+def _check_ode_method(method):
+    if method not in ("rk4", "rk45"):
+        raise ValueError(f"method={method!r}: 'rk4' (the reversed RK4 grid) or 'rk45' (adaptive, scipy's solve_ivp semantics)")
+
+
+def _host_rk45_groups(x, cond, per_sample):
+    """The controller groups of a host-side adaptive solve: ``(row slice, cond of those rows)`` -- the batch, or one per sample."""
+    if not per_sample:
+        return [(slice(0, x.shape[0]), cond)]
+    return [(slice(b, b + 1), {k: (v[b:b + 1] if torch.is_tensor(v) else v) for k, v in cond.items()} if cond else cond)
+            for b in range(x.shape[0])]
+
+
+def _raise_failed(who, failed, bsz):
+    if failed:
+        raise RuntimeError(f"{who}: {len(failed)} of {bsz} samples failed; " + " ".join(failed) if failed[0].startswith("sample")
+                           else f"{who}: {failed[0]}")
+
+
 @torch.no_grad()
-def invert_latents(model, latents, n_steps=50, cond=None):
+def _invert_rk45(model, latents, cond, rtol, atol, per_sample):
+    """``invert_latents(method="rk45")``: the legacy adaptive solve from t = 1 to t = 0, no guidance."""
+    rtol, atol = validate_tol(rtol, atol)
+    if isinstance(model, Unet):
+        if not latents.is_cuda:
+            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only")
+        x = _start(latents, None, latents.device)
+        _, cls, mask, ones = _conditioning(model, cond)
+        nfev, _, _ = model.integrate_rk45(x, 1.0, 0.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=0.0, mask=mask, mask_is_ones=ones,
+                                          per_sample=per_sample)
+        return x, (int(nfev.max()) if per_sample else nfev)
+    import numpy as np
+    from scipy import integrate
+    cond = _conditioning(model, cond)[0]
+    out, nfevs, failed = latents.detach().clone(), [], []
+    for rows, cond_g in _host_rk45_groups(latents, cond, per_sample):
+        xg = latents[rows]
+        shape = tuple(xg.shape)
+        t_vec_template = torch.zeros(shape[0], device=xg.device, dtype=xg.dtype)
+
+        def ode_func(t, y):
+            xt = torch.from_numpy(np.asarray(y).reshape(shape)).to(device=xg.device, dtype=xg.dtype)
+            return v_func_cfg(model, cond_g, 0.0, t_vec_template, xt, t).detach().double().cpu().numpy().reshape((-1,))
+
+        sol = integrate.solve_ivp(ode_func, (1.0, 0.0), xg.detach().double().cpu().numpy().reshape((-1,)), rtol=rtol, atol=atol, method="RK45")
+        if not sol.success:
+            failed.append(f"sample {rows.start}: {sol.message}" if per_sample else str(sol.message))
+            continue
+        out[rows] = torch.from_numpy(sol.y[:, -1].reshape(shape).copy()).to(device=xg.device, dtype=xg.dtype)
+        nfevs.append(int(sol.nfev))
+    _raise_failed("invert_latents", failed, latents.shape[0])
+    return out, max(nfevs)
+
+
+@torch.no_grad()
+def invert_latents(model, latents, n_steps=50, cond=None, method="rk4", rtol=1e-5, atol=1e-5, per_sample=True):
     """Data -> noise: the probability-flow ODE from t = 1 back to t = 0 on ``rk4_time_grid(n_steps)`` REVERSED, with the RK4 step and
     without guidance -- the ``z`` that ``generate_latents_rk4(..., source=z, cfg_strength=0)`` maps back to ``latents`` up to the
     discretisation error of the two solves.  ``cond`` as the samplers (a cond dict, or class ids).  Returns ``(z, nfe)`` with nfe the
     true number of velocity evaluations, ``4 (n_steps - 1)`` -- not ``generate_latents_rk4``'s ``n_steps * 4`` bookkeeping.
     A ``flocoder_amd.Unet`` runs the captured inference path (``Unet.integrate`` takes a grid in either direction); any other callable
-    goes through ``rk4_step`` on the latents' device."""
+    goes through ``rk4_step`` on the latents' device.
+
+    ``method="rk45"`` replaces the grid by the legacy adaptive solver run backwards: ``solve_ivp(method="RK45", rtol, atol)`` from
+    t = 1 to t = 0 (``n_steps`` is ignored), one problem per sample with ``per_sample`` (default) or one over the batch; nfe is scipy's
+    ``nfev`` (per sample: the largest).  A ``flocoder_amd.Unet`` runs it in the library (``Unet.integrate_rk45``), any other callable
+    through scipy on the host in the latents' dtype."""
+    _check_ode_method(method)
+    if method == "rk45":
+        return _invert_rk45(model, latents, cond, rtol, atol, per_sample)
     ts = _reverse_grid(n_steps, torch.float32 if isinstance(model, Unet) else latents.dtype)
     nfe = 4 * (len(ts) - 1)
     if isinstance(model, Unet):
@@ -378,7 +440,8 @@ def _make_probe(probe, latents, generator):
     return e.to(latents.device).contiguous()
 
 
-def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", generator=None, cfg_strength=None):
+def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", generator=None, cfg_strength=None, method="rk4", rtol=1e-5,
+                   atol=1e-5, per_sample=True, t_end=0.0):
     """log p_1(latents) under the flow: the change of variables along the probability-flow ODE walked from t = 1 to t = 0 on
     ``rk4_time_grid(n_steps)`` reversed, with Hutchinson's estimate of the divergence.  Interval by interval (dt < 0), every RK4 stage j
     gives ``v_j = model(x_j, 999 t_j, cond)`` and ``d_j[b] = sum_i eps[b,i] ((dv_j/dx_j)^T eps)[b,i]`` (one VJP of the same forward);
@@ -403,10 +466,37 @@ def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", ge
     form of a ``flocoder_amd.Unet``'s launch plans: a model that samples (inference-form plans) gets them back before the call returns, so a
     sampler call after it gives the bits of a model that never computed a likelihood (``Unet.log_likelihood``'s ``restore_plan``; it
     costs a device synchronisation and two plan builds per call -- for many calls in a row use ``Unet.log_likelihood(...,
-    restore_plan=False)`` and ``Unet.release_training_plan()``)."""
+    restore_plan=False)`` and ``Unet.release_training_plan()``).
+
+    ``method="rk45"`` puts the integration error under control instead of leaving it to ``n_steps`` (which is then ignored): the
+    literature's likelihood computation, ``scipy.integrate.solve_ivp(method="RK45", rtol, atol)`` from t = 1 to ``t_end`` (default 0; any
+    value in [0, 1)) on the concatenated state ``[x, a]`` with ``da/dt = d``, ``a = 0`` at t = 1 -- the divergence integral takes part in
+    the error norm (n = unknowns of x + one per sample) with the scale ``atol + rtol max(|a|, |a_new|)``.  ``per_sample=True`` (default: a
+    sample's likelihood is its own quantity) solves every sample as its own problem; ``per_sample=False`` solves one problem over the
+    batch, as the literature's code does.  ``logp`` is then ``-|z|^2/2 - (D/2) ln 2pi + a`` with ``z = x(t_end)``; nfe is scipy's
+    ``nfev`` (per sample: the largest).  A ``flocoder_amd.Unet`` runs the solve in the library (``Unet.log_likelihood_rk45``:
+    controller on the device, x in fp64 with fp32 evaluations, a entirely fp64); any other callable goes through ``solve_ivp`` on the
+    host with ``torch.autograd.grad`` per evaluation, in the dtype of ``latents``.  A failed solve raises RuntimeError."""
+    _check_ode_method(method)
     if cfg_strength:
         raise ValueError("log_likelihood takes no classifier-free guidance: the guided field is not the flow of a density the model defines")
     unet = isinstance(model, Unet)
+    if method == "rk45":
+        rtol, atol = validate_tol(rtol, atol)
+        t_end = float(t_end)
+        if not 0.0 <= t_end < 1.0:
+            raise ValueError(f"t_end={t_end} must lie in [0, 1)")
+        if unet and not latents.is_cuda:
+            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+        eps = _make_probe(probe, latents.float() if unet else latents, generator)
+        cond, cls, mask, ones = _conditioning(model, cond)
+        if unet:
+            x = _start(latents, None, latents.device)
+            (nfev, _, _), _, logp = model.log_likelihood_rk45(x, eps, 1.0, t_end, rtol=rtol, atol=atol, per_sample=per_sample, class_ids=cls,
+                                                              mask=mask, mask_is_ones=ones)
+            return logp, x, (int(nfev.max()) if per_sample else nfev)
+        logp, z, _, nfe = _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end)
+        return logp, z, nfe
     ts = _reverse_grid(n_steps, torch.float32 if unet else latents.dtype)
     nfe = 4 * (len(ts) - 1)
     if unet and not latents.is_cuda:
@@ -450,6 +540,42 @@ def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999):
     D = z[0].numel()
     logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
     return logp, z, a
+
+
+def _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end=0.0, t_scale=999):
+    """``log_likelihood(method="rk45")`` for any callable: ``solve_ivp(method="RK45")`` from 1 to ``t_end`` on the concatenated vector
+    ``[x, a]`` of every controller group (the batch, or each sample), ``torch.autograd.grad(v, x, eps)`` per evaluation.  Returns
+    (logp, z, a, nfe)."""
+    import math
+    import numpy as np
+    from scipy import integrate
+    z, a = latents.detach().clone(), torch.zeros(latents.shape[0], dtype=torch.float64, device=latents.device)
+    nfevs, failed = [], []
+    for rows, cond_g in _host_rk45_groups(latents, cond, per_sample):
+        xg, eg = latents[rows].detach(), eps[rows]
+        shape, n, e64 = tuple(xg.shape), xg.numel(), eps[rows].double()
+
+        def ode_func(t, y):
+            with torch.enable_grad():
+                xr = torch.from_numpy(np.ascontiguousarray(y[:n]).reshape(shape)).to(device=xg.device, dtype=xg.dtype).requires_grad_(True)
+                t_vec = torch.full((shape[0],), float(t), device=xg.device, dtype=xg.dtype)
+                v = model(xr, t_vec * t_scale, cond=cond_g)
+                g, = torch.autograd.grad(v, xr, eg)
+            d = (e64 * g.double()).flatten(1).sum(dim=1)
+            return np.concatenate([v.detach().double().cpu().numpy().reshape(-1), d.cpu().numpy()])
+
+        y0 = np.concatenate([xg.double().cpu().numpy().reshape(-1), np.zeros(shape[0])])
+        sol = integrate.solve_ivp(ode_func, (1.0, t_end), y0, rtol=rtol, atol=atol, method="RK45")
+        if not sol.success:
+            failed.append(f"sample {rows.start}: {sol.message}" if per_sample else str(sol.message))
+            continue
+        z[rows] = torch.from_numpy(sol.y[:n, -1].reshape(shape).copy()).to(device=xg.device, dtype=xg.dtype)
+        a[rows] = torch.from_numpy(sol.y[n:, -1].copy()).to(a.device)
+        nfevs.append(int(sol.nfev))
+    _raise_failed("log_likelihood", failed, latents.shape[0])
+    D = z[0].numel()
+    logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
+    return logp, z, a, max(nfevs)
 
 
 def _solve_ivp_rk45(ode_func, eps, y0, rtol, atol, t_eval):

@@ -516,6 +516,42 @@ class Unet(NativeModule):
             self._integrator_check(hnd, dev, check)
         return a, logp
 
+    def log_likelihood_rk45(self, x: torch.Tensor, eps: torch.Tensor, t0: float = 1.0, t1: float = 0.0, rtol: float = 1e-5,
+                            atol: float = 1e-5, per_sample: bool = True, *, t_scale: float = 999.0, class_ids: Optional[torch.Tensor] = None,
+                            mask: Optional[torch.Tensor] = None, mask_is_ones: bool = False, check: bool = True, restore_plan: bool = True):
+        """``fc_unet_log_likelihood_rk45``: ``log_likelihood`` with error control.  ``x`` is integrated in place from ``t0`` back to ``t1``
+        (``0 <= t1 < t0 <= 1``) by scipy's adaptive RK45 (``integrate_rk45``'s controller) on the concatenated state ``[x, a]``,
+        ``da[b]/dt = sum eps (dv/dx)^T eps`` with the probe ``eps`` (x's shape), ``a = 0`` at ``t0``: the divergence integral takes part
+        in the error norm and the step control.  ``per_sample=True`` (default: a sample's likelihood is its own quantity) solves every
+        sample as its own problem over its C*H*W + 1 unknowns; ``per_sample=False`` is one problem over the batch, as the literature's
+        code.  Returns ``(counters, a, logp)``: ``counters = (nfev, accepted, rejected)`` as ``integrate_rk45`` returns them (ints, or int64
+        CPU tensors ``[B]`` per sample); ``a`` and ``logp = -|z|^2/2 - (CHW/2) ln 2pi + a`` fp64 ``[B]`` on x's device, ``z`` = the ``x`` left
+        behind.  Synchronous.  A failed solve raises RuntimeError with scipy's message (per sample naming the samples) and leaves ``x``
+        untouched.  The form of the plans is handled as in ``log_likelihood`` (``restore_plan``)."""
+        rtol, atol = validate_tol(rtol, atol)
+        t0, t1 = float(t0), float(t1)
+        if not (0.0 <= t1 < t0 <= 1.0):
+            raise ValueError(f"t0={t0}, t1={t1}: the likelihood is integrated from the data end back towards noise, 0 <= t1 < t0 <= 1")
+        class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask, cpu_error=_GPU_ONLY + "; there is no CPU path")
+        dev = x.device
+        bsz, _, h, w = x.shape
+        if eps.shape != x.shape or eps.device != dev or eps.dtype != torch.float32 or not eps.is_contiguous():
+            raise ValueError("probe must be a contiguous fp32 tensor of x's shape on x's device")
+        if eps.data_ptr() % 16:
+            eps = eps.clone()                           # a view at an odd storage offset: the kernels read the probe as float4
+        self._check_aligned(x)
+        a, logp = (torch.empty(bsz, dtype=torch.float64, device=dev) for _ in range(2))
+        counters = (C.c_int * (3 * bsz if per_sample else 3))()
+        with self._training_form(hnd, bsz, h, w, restore_plan):
+            B.check(B.lib().fc_unet_log_likelihood_rk45(hnd, B.ptr(x), bsz, h, w, t0, t1, float(rtol), float(atol), float(t_scale),
+                                                        B.ptr(class_ids), B.ptr(mask), int(mask_is_ones), B.ptr(eps), int(per_sample), B.ptr(a),
+                                                        B.ptr(logp), counters, B.current_stream(dev)))
+            self._integrator_check(hnd, dev, check)
+        if per_sample:
+            c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
+            return (c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone()), a, logp
+        return (int(counters[0]), int(counters[1]), int(counters[2])), a, logp
+
     def integrate_guided(self, x: torch.Tensor, ts: torch.Tensor, measurement: torch.Tensor, keep: torch.Tensor, *, sigma_y: float = 0.05,
                          gamma: float = 1.0, jacobian: str = "identity", t_scale: float = 999.0, class_ids: Optional[torch.Tensor] = None,
                          cfg_strength: float = 0.0, mask: Optional[torch.Tensor] = None, mask_is_ones: bool = False, check: bool = True,

@@ -216,6 +216,23 @@ int fc_unet_log_likelihood(fc_unet* u, float* x_inout_dev, int batch, int height
                            float t_scale, const int64_t* class_ids_dev, const float* mask_dev, int mask_is_ones, const float* probe_dev,
                            double* a_out_dev, double* logp_out_dev, void* stream);
 
+/* fc_unet_log_likelihood with error control: scipy's solve_ivp(method="RK45") -- the controller of fc_unet_integrate_rk45 (per_sample
+ * == 0: one controller group over the batch) / fc_unet_integrate_rk45_per_sample (per_sample != 0: one per sample) -- from t0 back to
+ * t1 (0 <= t1 < t0 <= 1, else FC_E_ARG) on the concatenated state of a group, y = [x (m unknowns), a (one per row)], dy/dt = [v, d] with
+ * d[b] = sum_i probe[b,i] ((dv/dx)^T probe)[b,i] and a = 0 at t0: select_initial_step and the RMS error norm run over m + rows unknowns,
+ * the a-component's scale is atol + rtol max(|a|, |a_new|).  x as in fc_unet_integrate_rk45 (fp64 state, fp32 forwards as K); a, its
+ * seven K values and its terms of the norms fp64, added after the group's x partial sums, one term per row in row order (two calls
+ * give equal bits).  Every evaluation is a training-form forward plus fc_unet_vjp_x's chain with probe_dev as cotangent, launched
+ * directly; needs fc_unet_train_reserve for this shape (else FC_E_STATE); no classifier-free guidance.  Synchronous like
+ * fc_unet_integrate_rk45; counters: [3] (per_sample == 0) or [3 * batch] host ints, nfev / accepted / rejected per group.  On success
+ * x_inout_dev holds z = x(t1), a_out_dev [B] the integrated divergence, logp_out_dev [B] = -|z_b|^2/2 - (CHW/2) ln 2pi + a[b]; on
+ * FC_E_STATE (scipy's failure messages, per sample naming the samples) none of the three is written.  x_inout_dev and probe_dev must
+ * be 16-byte aligned.  Writes the activation arena like fc_unet_log_likelihood. */
+int fc_unet_log_likelihood_rk45(fc_unet* u, float* x_inout_dev, int batch, int height, int width, double t0, double t1, double rtol,
+                                double atol, float t_scale, const int64_t* class_ids_dev, const float* mask_dev, int mask_is_ones,
+                                const float* probe_dev, int per_sample, double* a_out_dev, double* logp_out_dev, int* counters,
+                                void* stream);
+
 /* Measurement-guided RK4 sampling: the training-free inverse-problem method of the reference (flocoder/inpainting.py:92-130 algorithm3)
  * for a diagonal measurement operator on the conditional-OT path.  fc_unet_integrate(FC_METHOD_RK4) along ts_host (n_points >= 2, every
  * point > 0) in which every stage velocity v -- after classifier-free guidance -- produced at stage state x and stage time t becomes
