@@ -17,6 +17,8 @@ FC_OK, FC_E_ARG, FC_E_SHAPE, FC_E_ARCH, FC_E_HIP, FC_E_STATE = 0, -1, -2, -3, -4
 FC_METHOD_EULER, FC_METHOD_RK4 = 0, 1
 FC_JACOBIAN_IDENTITY, FC_JACOBIAN_EXACT = 0, 1
 FC_SDE_EULER_MARUYAMA, FC_SDE_HEUN = 0, 1
+FC_LL_MAX_PROBES = 64
+FC_PROBE_RADEMACHER, FC_PROBE_GAUSSIAN = 0, 1
 TILE_AUTO = -1
 TILES = {"M128N32": 0, "M128N64": 1, "M64N32K2": 2, "M32N32K4": 3, "M64N64K2": 4, "M256N64": 5}
 
@@ -88,6 +90,10 @@ SIGNATURES = {
     "fc_unet_log_likelihood": (_i, [_vp, _vp, _i, _i, _i, _pf, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "fc_unet_log_likelihood_rk45": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _vp, _i, _vp, _i, _vp,
                                          _vp, _pi, _vp]),
+    "fc_unet_log_likelihood_probes": (_i, [_vp, _vp, _i, _i, _i, _pf, _i, _f, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fc_unet_log_likelihood_rk45_probes": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _vp, _vp, _i, _vp,
+                                                _i, _i, _vp, _vp, _vp, _vp, _pi, _vp]),
+    "fc_ode_probe_field": (_i, [_vp, _i, C.c_uint64, _i64, _vp, _i, _i64, _vp]),
     "fc_debug_probe_dot": (_i, [_vp, _vp, _vp, _i, _i64, _vp]),
     "fc_unet_integrate_guided": (_i, [_vp, _vp, _i, _i, _i, _pf, _i, _f, _vp, _f, _vp, _i, _vp, _vp, _f, _f, _i, _vp]),
     "fc_ode_guided_correct": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _vp]),

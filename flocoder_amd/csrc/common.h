@@ -288,15 +288,25 @@ int ode_guide_w_launch(const float* sc, const float* gsc, const float* v, const 
 // out = v + gamma ((1-t)/t) w on caller tensors (fc_ode_guided_correct)
 int ode_guided_correct_launch(const float* v, const float* x, const float* ym, const float* keep, float* out, int n, float t, float s2,
                               float gamma, hipStream_t s);
+// Several Hutchinson probes in one likelihood call: eps and g are [K][B][m], the stage sums [K][B][3], the integrals [K][B] (the stride
+// is the call's B everywhere).  FC_LL_MAX_PROBES (flocoder_amd.h) bounds the library's g buffer at that many times maxB * m floats.
 // likelihood on the RK4 grid (one workgroup per sample of m elements, no CFG): the stage / final updates above plus
 // dst[3 b + slot] = sum eps g (stages 1..3), a[b] += (double(dt)/6)(d1 + 2 d2 + 2 d3 + sum eps g) (stage 4); tvec[b] as the stage kernel
 int ode_ll_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v, const float* g, const float* eps,
-                        double* dst, int slot, int B, int m, int full, int tsel, float t_scale, float* tvec, hipStream_t s);
+                        double* dst, int slot, int B, int m, int full, int tsel, float t_scale, float* tvec, int K, hipStream_t s);
 int ode_ll_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v, const float* g,
-                        const float* eps, const double* dst, double* a, int B, int m, hipStream_t s);
+                        const float* eps, const double* dst, double* a, int B, int m, int K, hipStream_t s);
 // logp[b] = -|z_b|^2/2 - (m/2) ln 2pi + a[b]
 int ode_ll_logp_launch(const float* z, const double* a, double* logp, int B, int m, hipStream_t s);
-int ode_ll_dot_launch(const float* eps, const float* g, double* out, int B, int m, hipStream_t s);
+// K probes: eps, g [K][B][m]; dk [K][B] each probe's sum (may be null for K = 1); out[b] their mean, summed in probe order, one division
+int ode_ll_dot_launch(const float* eps, const float* g, double* out, double* dk, int B, int m, int K, hipStream_t s);
+// from ak [K][B]: abar[b] = (a_1[b] + ... + a_K[b]) / K (mean_given: abar is read instead, the adaptive solve's own a) and the
+// standard error se[b] = sqrt(sum_k (a_k[b] - abar[b])^2 / (K (K - 1))), NaN for K = 1
+int ode_ll_mean_launch(const double* ak, int K, int B, double* abar, double* se, int mean_given, hipStream_t s);
+// out[b][:] = the Rademacher probe field's +-1 of (seed, probe, sample id sids[b] or b), m per sample, n = batch * m
+// ... and its Gaussian kind: the normal field's uniforms and transform in fp64, rounded once to fp32
+int ode_probe_normal_field_launch(float* out, unsigned long long seed, unsigned probe, const int64_t* sids, int n, int m, hipStream_t s);
+int ode_rademacher_field_launch(float* out, unsigned long long seed, unsigned probe, const int64_t* sids, int n, int m, hipStream_t s);
 // stochastic sampling (fc_unet_integrate_sde).  SdeParams: the call's seed and supplied-noise pointer, in device memory like the time
 // grid, so one captured interval serves every seed and every noise tensor.  The update kernel runs behind a forward of the interval that
 // ode_time_launch opened (interval index *step - 1): stage 0 Euler-Maruyama (y in place), 1 Heun's predictor (b1, xs; publishes
@@ -331,7 +341,10 @@ struct Rk45Groups { int G, spg, m, chunks; };
 // a: [2][B] fp64, a | a_new of the attempt in flight; d: [7][B] fp64, the a-component's K0..K6 (ode_ll_dot_launch behind evaluation s
 // writes row s; row 0 is the committed one).  B = G * spg.  The launches that take one (null: the sampler) run the instantiation in
 // which the a-components join the group's norms, n = m + spg unknowns.
-struct Rk45LL { double *a, *d; int B; };
+// With per-probe rows (dk: [7][K][B], the K values of every probe, row 0 the committed one; ak: [K][B], each probe's own integral) d is
+// the probes' mean, which is what the norms read; the controller of an accepted step advances every a_k next to a.  dk may be null
+// for K = 1 (d is then the one probe's row and a its integral).
+struct Rk45LL { double *a, *d; int B; int K = 1; double *dk = nullptr, *ak = nullptr; };
 int rk45_chunks(int m, int cap);           // workgroups per group over m unknowns: one per 1024, at most `cap`
 // y = double(x), xs = x, states for (t0 -> t1), time rows of f(t0)
 int rk45_setup_launch(const Rk45Groups& g, const float* x, double* y, float* xs, Rk45State* st, double t0, double t1, double rtol,

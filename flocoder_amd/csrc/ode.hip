@@ -658,20 +658,42 @@ __device__ __forceinline__ void rk45_decide(Rk45State* st, double en) {
     }
 }
 
+// h sum_s B_s K_s over the seven K values k[s * stride] of one a-component (rk_step's sum, left to right as the x kernels'): the one
+// expression behind a_new of the mean row and behind every probe's own integral
+__device__ __forceinline__ double rk45_ll_bsum(const double* k, size_t stride) {
+    double yn = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) yn = j == 0 ? k[0] * c_rk45_B[j] : yn + k[(size_t)j * stride] * c_rk45_B[j];
+    return yn;
+}
+__device__ __forceinline__ double rk45_ll_advance(double a, double h, double yn) { return a + h * yn; }
+
 // The a-component of row r in the attempt just evaluated (rk_step and the error estimate on ll.d[0..6][r], sums left to right as the x
 // kernels'): a_new into ll.a[B + r]; returns its term of the error norm's sum
 __device__ __forceinline__ double rk45_ll_row(const Rk45State& sg, const Rk45LL& ll, int r) {
-    double yn = 0.0, er = 0.0;
+    double er = 0.0;
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
         const double k = ll.d[(size_t)j * ll.B + r];
-        if (j < 6) yn = j == 0 ? k * c_rk45_B[j] : yn + k * c_rk45_B[j];
         er = j == 0 ? k * c_rk45_E[j] : er + k * c_rk45_E[j];
     }
-    const double a = ll.a[r], a_new = a + sg.h * yn;
+    const double a = ll.a[r], a_new = rk45_ll_advance(a, sg.h, rk45_ll_bsum(ll.d + r, ll.B));
     ll.a[ll.B + r] = a_new;
     const double e = er * sg.h / (sg.atol + np_maximum(fabs(a), fabs(a_new)) * sg.rtol);
     return e * e;
+}
+
+// Row r's commit of an accepted step of size h: a <- a_new, d_0 <- d_6 (FSAL), and with per-probe rows (ll.dk) each probe's own
+// integral a_k <- a_k + h sum_s B_s d_{s,k} -- a by-product outside the norm, formed as a_new is -- and its d_{0,k} <- d_{6,k}.
+__device__ __forceinline__ void rk45_ll_commit(const Rk45LL& ll, int r, double h) {
+    ll.a[r] = ll.a[ll.B + r];
+    ll.d[r] = ll.d[(size_t)6 * ll.B + r];
+    const size_t KB = (size_t)ll.K * ll.B;
+    for (int k = 0; k < ll.K && ll.dk; ++k) {
+        double* dk = ll.dk + (size_t)k * ll.B + r;
+        ll.ak[(size_t)k * ll.B + r] = rk45_ll_advance(ll.ak[(size_t)k * ll.B + r], h, rk45_ll_bsum(dk, KB));
+        dk[0] = dk[6 * KB];
+    }
 }
 
 // one workgroup per group: its error norm and decision, and with a dense-output request (`ev`) the requested times an accepted step
@@ -689,12 +711,13 @@ __global__ void __launch_bounds__(256) rk45_control_kernel(Rk45State* st, const 
     }
     double s = reduce_parts(part + 2 * (size_t)g * chunks, chunks, 2, 0, red);
     if (threadIdx.x != 0) return;
+    const double h = sg->h;   // the attempt's step (rk45_decide writes the next attempt's)
     if constexpr (LL)
         for (int r = g * spg; r < (g + 1) * spg; ++r) s += rk45_ll_row(*sg, ll, r);
     rk45_decide(sg, sqrt(s) / sqrt((double)(LL ? m + spg : m)));
     if constexpr (LL) {
         if (sg->accepted_last)
-            for (int r = g * spg; r < (g + 1) * spg; ++r) { ll.a[r] = ll.a[ll.B + r]; ll.d[r] = ll.d[(size_t)6 * ll.B + r]; }
+            for (int r = g * spg; r < (g + 1) * spg; ++r) rk45_ll_commit(ll, r, h);
     }
     if (ev && sg->accepted_last) rk45_eval_range(sg, ev);
     rk45_freeze(sg);
@@ -803,7 +826,7 @@ int rk45_d01_launch(const Rk45Groups& g, const Rk45State* st, const double* y, f
 }
 // `ll` (may be null): the likelihood's instantiation, which needs its whole record and takes no guidance pair
 #define RK45_LL_CHECK                                                                                                   \
-    if (ll && (!ll->a || !ll->d || ll->B != g.G * g.spg)) return fail(FC_E_ARG, "rk45: the likelihood record does not fit the controller groups")
+    if (ll && (!ll->a || !ll->d || ll->B != g.G * g.spg || ll->K < 1 || (ll->dk && !ll->ak) || (ll->K > 1 && !ll->dk))) return fail(FC_E_ARG, "rk45: the likelihood record does not fit the controller groups")
 int rk45_h0_launch(const Rk45Groups& g, Rk45State* st, const double* part, float t_scale, float* tvec, int cfg_on, const Rk45LL* ll,
                    hipStream_t s) {
     RK45_LL_CHECK;
@@ -886,11 +909,22 @@ __device__ __forceinline__ double probe_dot_acc(double s, const float4 e, const 
     return s;
 }
 
+// K probes (layout: eps and g [K][B][m], dst [K][B][3], a [K][B], all strided by the call's B): the state arithmetic and probe 0's
+// reduction share the first pass as they always did, probes 1..K-1 are reduced behind it by the same workgroup with the same loop and
+// the same tree, so d_{j,k}[b] has the bits of a single-probe call with probe k.
+__device__ __forceinline__ double probe_dot_sample(const float* eps, const float* g, int base, int m, double* red) {
+    double d = 0.0;
+    for (int j = 4 * threadIdx.x; j < m; j += 4 * 256)
+        d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + base + j), *reinterpret_cast<const float4*>(g + base + j));
+    __syncthreads();   // the reduction before this one has been read
+    return block_sum(d, red);
+}
+
 __global__ void __launch_bounds__(256) ode_ll_stage_kernel(const float* sc, const float* y, float* xs, float* k_out, const float* v,
                                                            const float* g, const float* eps, double* dst, int slot, int m, int full,
-                                                           int tsel, float t_scale, float* tvec) {
+                                                           int tsel, float t_scale, float* tvec, int K) {
     __shared__ double red[256];
-    const int b = blockIdx.x, base = b * m;
+    const int b = blockIdx.x, base = b * m, B = gridDim.x;
     const float t = sc[0], dt = sc[1];
     if (threadIdx.x == 0) tvec[b] = next_stage_tv(t, dt, tsel, t_scale);
     double d = 0.0;
@@ -903,13 +937,23 @@ __global__ void __launch_bounds__(256) ode_ll_stage_kernel(const float* sc, cons
     }
     const double r = block_sum(d, red);
     if (threadIdx.x == 0) dst[3 * b + slot] = r;
+    for (int k = 1; k < K; ++k) {
+        const size_t pk = (size_t)k * B;
+        const double rk = probe_dot_sample(eps + pk * m, g + pk * m, base, m, red);
+        if (threadIdx.x == 0) dst[3 * (pk + b) + slot] = rk;
+    }
+}
+
+// a + (dt/6)(d1 + 2 d2 + 2 d3 + d4), left to right
+__device__ __forceinline__ double ll_interval_sum(double a, float dt, const double* ds, double d4) {
+    return a + ((double)dt / 6.0) * (((ds[0] + 2.0 * ds[1]) + 2.0 * ds[2]) + d4);
 }
 
 __global__ void __launch_bounds__(256) ode_ll_final_kernel(const float* sc, float* y, const float* k1, const float* k2, const float* k3,
                                                            const float* v, const float* g, const float* eps, const double* dst, double* a,
-                                                           int m) {
+                                                           int m, int K) {
     __shared__ double red[256];
-    const int b = blockIdx.x, base = b * m;
+    const int b = blockIdx.x, base = b * m, B = gridDim.x;
     const float dt6 = __fdiv_rn(sc[1], 6.0f);
     double d = 0.0;
     for (int j = 4 * threadIdx.x; j < m; j += 4 * 256) {
@@ -921,10 +965,30 @@ __global__ void __launch_bounds__(256) ode_ll_final_kernel(const float* sc, floa
         d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + i), *reinterpret_cast<const float4*>(g + i));
     }
     const double d4 = block_sum(d, red);
-    if (threadIdx.x == 0) {   // a + (dt/6)(d1 + 2 d2 + 2 d3 + d4), left to right
-        const double* ds = dst + 3 * b;
-        a[b] = a[b] + ((double)sc[1] / 6.0) * (((ds[0] + 2.0 * ds[1]) + 2.0 * ds[2]) + d4);
+    if (threadIdx.x == 0) a[b] = ll_interval_sum(a[b], sc[1], dst + 3 * b, d4);
+    for (int k = 1; k < K; ++k) {
+        const size_t pk = (size_t)k * B;
+        const double dk = probe_dot_sample(eps + pk * m, g + pk * m, base, m, red);
+        if (threadIdx.x == 0) a[pk + b] = ll_interval_sum(a[pk + b], sc[1], dst + 3 * (pk + b), dk);
     }
+}
+
+// The probes' mean and its standard error (thread b of an elementwise grid): abar[b] = (a_1[b] + ... + a_K[b]) / K, summed in probe
+// order with one division; se[b] = sqrt(sum_k (a_k[b] - abar[b])^2 / (K (K - 1))), NaN for K = 1 (0 / 0).
+// mean_given: abar[b] is the adaptive solve's own a and is read, not formed.
+__global__ void __launch_bounds__(256) ode_ll_mean_kernel(const double* ak, int K, int B, double* abar, double* se, int mean_given) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    double mean;
+    if (mean_given) mean = abar[b];
+    else {
+        double s = ak[b];
+        for (int k = 1; k < K; ++k) s += ak[(size_t)k * B + b];
+        abar[b] = mean = s / (double)K;
+    }
+    double q = 0.0;
+    for (int k = 0; k < K; ++k) { const double e = ak[(size_t)k * B + b] - mean; q += e * e; }
+    se[b] = sqrt(q / ((double)K * (double)(K - 1)));
 }
 
 // logp[b] = -|z_b|^2 / 2 - (m/2) ln(2 pi) + a[b]: the standard normal at the noise end plus the integrated divergence
@@ -937,35 +1001,56 @@ __global__ void __launch_bounds__(256) ode_ll_logp_kernel(const float* z, const 
     if (threadIdx.x == 0) logp[b] = (-0.5 * r - 0.5 * (double)m * 1.8378770664093454835606594728112) + a[b];
 }
 
-// test hook (fc_debug_probe_dot): the stage kernels' reduction on its own
-__global__ void __launch_bounds__(256) ode_ll_dot_kernel(const float* eps, const float* g, double* out, int m) {
+// the stage kernels' reduction on its own (fc_debug_probe_dot's test hook with K = 1, dk = NULL), and behind every evaluation of the
+// adaptive likelihood: for k in probe order dk[k][b] = sum eps_k g_k (eps, g [K][B][m]; dk [K][B], may be NULL for K = 1), then
+// out[b] = (d_1 + ... + d_K) / K, summed in that order with one division (K = 1: the reduction itself)
+__global__ void __launch_bounds__(256) ode_ll_dot_kernel(const float* eps, const float* g, double* out, double* dk, int m, int K) {
     __shared__ double red[256];
-    const int b = blockIdx.x, base = b * m;
+    const int b = blockIdx.x, base = b * m, B = gridDim.x;
     double d = 0.0;
     for (int j = 4 * threadIdx.x; j < m; j += 4 * 256)
         d = probe_dot_acc(d, *reinterpret_cast<const float4*>(eps + base + j), *reinterpret_cast<const float4*>(g + base + j));
-    const double r = block_sum(d, red);
-    if (threadIdx.x == 0) out[b] = r;
+    double r = block_sum(d, red);
+    if (K == 1) {
+        if (threadIdx.x == 0) { out[b] = r; if (dk) dk[b] = r; }
+        return;
+    }
+    if (threadIdx.x == 0) dk[b] = r;
+    for (int k = 1; k < K; ++k) {
+        const size_t pk = (size_t)k * B;
+        const double rk = probe_dot_sample(eps + pk * m, g + pk * m, base, m, red);
+        if (threadIdx.x == 0) dk[pk + b] = rk;
+        r += rk;
+    }
+    if (threadIdx.x == 0) out[b] = r / (double)K;
 }
 
+// probe k's slice starts at k * B * m: the whole [K][B][m] block is indexed with size_t, each slice with int
+static int ll_probes_ok(int K, int B, int m) {
+    (void)B; (void)m;
+    if (K < 1 || K > FC_LL_MAX_PROBES) return fail(FC_E_ARG, "ode: the number of probes must lie in [1, " + std::to_string(FC_LL_MAX_PROBES) + "]");
+    return FC_OK;
+}
 static int ll_shape_ok(int B, int m) {
     if (B < 1 || m < 4 || (m & 3)) return fail(FC_E_SHAPE, "ode: elements per sample must be a positive multiple of 4");
     if ((long long)B * m > 0x7fffffffLL) return fail(FC_E_SHAPE, "ode: the kernels index the batch with int (batch * elements per sample < 2^31)");
     return FC_OK;
 }
 int ode_ll_stage_launch(const float* sc, const float* y, float* xs, float* k_out, const float* v, const float* g, const float* eps,
-                        double* dst, int slot, int B, int m, int full, int tsel, float t_scale, float* tvec, hipStream_t s) {
+                        double* dst, int slot, int B, int m, int full, int tsel, float t_scale, float* tvec, int K, hipStream_t s) {
     FC_TRY(ll_shape_ok(B, m));
+    FC_TRY(ll_probes_ok(K, B, m));
     if (slot < 0 || slot > 2) return fail(FC_E_ARG, "ode: stage slot must lie in [0, 2]");
     if (tsel < 1 || tsel > 2) return fail(FC_E_ARG, "ode: the next stage's time selector must lie in [1, 2]");
-    hipLaunchKernelGGL(ode_ll_stage_kernel, dim3(B), dim3(256), 0, s, sc, y, xs, k_out, v, g, eps, dst, slot, m, full, tsel, t_scale, tvec);
+    hipLaunchKernelGGL(ode_ll_stage_kernel, dim3(B), dim3(256), 0, s, sc, y, xs, k_out, v, g, eps, dst, slot, m, full, tsel, t_scale, tvec, K);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
 int ode_ll_final_launch(const float* sc, float* y, const float* k1, const float* k2, const float* k3, const float* v, const float* g,
-                        const float* eps, const double* dst, double* a, int B, int m, hipStream_t s) {
+                        const float* eps, const double* dst, double* a, int B, int m, int K, hipStream_t s) {
     FC_TRY(ll_shape_ok(B, m));
-    hipLaunchKernelGGL(ode_ll_final_kernel, dim3(B), dim3(256), 0, s, sc, y, k1, k2, k3, v, g, eps, dst, a, m);
+    FC_TRY(ll_probes_ok(K, B, m));
+    hipLaunchKernelGGL(ode_ll_final_kernel, dim3(B), dim3(256), 0, s, sc, y, k1, k2, k3, v, g, eps, dst, a, m, K);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -975,9 +1060,17 @@ int ode_ll_logp_launch(const float* z, const double* a, double* logp, int B, int
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
-int ode_ll_dot_launch(const float* eps, const float* g, double* out, int B, int m, hipStream_t s) {
+int ode_ll_dot_launch(const float* eps, const float* g, double* out, double* dk, int B, int m, int K, hipStream_t s) {
     FC_TRY(ll_shape_ok(B, m));
-    hipLaunchKernelGGL(ode_ll_dot_kernel, dim3(B), dim3(256), 0, s, eps, g, out, m);
+    FC_TRY(ll_probes_ok(K, B, m));
+    if (K > 1 && !dk) return fail(FC_E_ARG, "ode: several probes need their per-probe rows");
+    hipLaunchKernelGGL(ode_ll_dot_kernel, dim3(B), dim3(256), 0, s, eps, g, out, dk, m, K);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_ll_mean_launch(const double* ak, int K, int B, double* abar, double* se, int mean_given, hipStream_t s) {
+    if (K < 1 || K > FC_LL_MAX_PROBES || B < 1 || !ak || !abar || !se) return fail(FC_E_ARG, "ode: bad probe mean arguments");
+    hipLaunchKernelGGL(ode_ll_mean_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, ak, K, B, abar, se, mean_given);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -1026,6 +1119,39 @@ __global__ void __launch_bounds__(256) ode_normal_field_kernel(float* out, unsig
         const int b = i / m;
         const unsigned long long sid = sids ? (unsigned long long)sids[b] : (unsigned long long)b;
         *reinterpret_cast<float4*>(out + i) = normal4(seed, draw, sid, (unsigned)((i - b * m) >> 2));
+    }
+}
+
+// fc_ode_probe_field, Rademacher: out[b][4j .. 4j+3] = +-1 from the top bit of the four words of the Philox block with counter
+// (j, probe, sample id lo, sample id hi) -- a clear bit gives +1, a set one -1; `seed` is the caller's already offset key
+__global__ void __launch_bounds__(256) ode_rademacher_field_kernel(float* out, unsigned long long seed, unsigned probe,
+                                                                   const long long* sids, int n, int m) {
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const int b = i / m;
+        const unsigned long long sid = sids ? (unsigned long long)sids[b] : (unsigned long long)b;
+        unsigned r[4];
+        philox4x32_10((unsigned)((i - b * m) >> 2), probe, (unsigned)sid, (unsigned)(sid >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+        *reinterpret_cast<float4*>(out + i) = make_float4(r[0] >> 31 ? -1.0f : 1.0f, r[1] >> 31 ? -1.0f : 1.0f, r[2] >> 31 ? -1.0f : 1.0f,
+                                                          r[3] >> 31 ? -1.0f : 1.0f);
+    }
+}
+
+// fc_ode_probe_field, Gaussian: the normal field's uniforms and Box-Muller transform (same counter layout, same tail cut at
+// sqrt(48 ln 2)) evaluated in fp64 and rounded once to fp32 -- what noise.probe_field computes on the host, so the two agree in bits
+// wherever the fp64 log / sqrt / sin / cos of the two sides agree to well inside an fp32 rounding.  A probe field is drawn once per
+// call, not once per interval like the sampler's noise: the fp64 transform costs nothing that shows.
+__device__ __forceinline__ double philox_u01_f64(unsigned r) { return ((double)(r >> 9) + 0.5) * 1.1920928955078125e-07; }   // exact
+__global__ void __launch_bounds__(256) ode_probe_normal_field_kernel(float* out, unsigned long long seed, unsigned probe,
+                                                                     const long long* sids, int n, int m) {
+    for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+        const int b = i / m;
+        const unsigned long long sid = sids ? (unsigned long long)sids[b] : (unsigned long long)b;
+        unsigned r[4];
+        philox4x32_10((unsigned)((i - b * m) >> 2), probe, (unsigned)sid, (unsigned)(sid >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+        const double two_pi = 2.0 * 3.141592653589793;
+        const double r0 = sqrt(-2.0 * log(philox_u01_f64(r[0]))), r1 = sqrt(-2.0 * log(philox_u01_f64(r[2])));
+        const double a0 = two_pi * philox_u01_f64(r[1]), a1 = two_pi * philox_u01_f64(r[3]);
+        *reinterpret_cast<float4*>(out + i) = make_float4((float)(r0 * cos(a0)), (float)(r0 * sin(a0)), (float)(r1 * cos(a1)), (float)(r1 * sin(a1)));
     }
 }
 
@@ -1101,6 +1227,18 @@ int ode_sde_update_launch(const int* step, const float* ts, const SdeParams* prm
     if (stage < 0 || stage > 2) return fail(FC_E_ARG, "ode: SDE stage must lie in [0, 2]");
     hipLaunchKernelGGL(ode_sde_update_kernel, dim3(egrid(n)), dim3(256), 0, s, step, ts, prm,
                        reinterpret_cast<const long long*>(sids), y, xs, b1, v2, n, m, cfg_on, cfg, sigma, stage, use_noise, t_scale, tvec, rows);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_probe_normal_field_launch(float* out, unsigned long long seed, unsigned probe, const int64_t* sids, int n, int m, hipStream_t s) {
+    FC_TRY(sde_shape_ok(n, m));
+    hipLaunchKernelGGL(ode_probe_normal_field_kernel, dim3(egrid(n)), dim3(256), 0, s, out, seed, probe, reinterpret_cast<const long long*>(sids), n, m);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+int ode_rademacher_field_launch(float* out, unsigned long long seed, unsigned probe, const int64_t* sids, int n, int m, hipStream_t s) {
+    FC_TRY(sde_shape_ok(n, m));
+    hipLaunchKernelGGL(ode_rademacher_field_kernel, dim3(egrid(n)), dim3(256), 0, s, out, seed, probe, reinterpret_cast<const long long*>(sids), n, m);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }

@@ -1,6 +1,7 @@
 // The project's counter-based generator: one Philox4x32-10 block (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11).
 // flocoder_amd/noise.py (philox4x32) is its host form.  Users and their counter regions:
 //   ode.hip   the SDE samplers' normal field    counter (j, draw, sample id lo, sample id hi)
+//   ode.hip   the likelihood's probe field      counter (j, probe, sample id lo, sample id hi), key = seed + FC_PROBE_KEY_OFFSET (mod 2^64)
 //   ot_plan.hip   the plan sampler's uniforms   counter (k, draw, 0x4F54504C, 0xFFFFFFFF): a sample id with the top word all ones is negative
 #pragma once
 #include <hip/hip_runtime.h>

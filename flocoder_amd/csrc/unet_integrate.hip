@@ -187,9 +187,46 @@ struct Rk4Variant {
     int trows;                                             // rows of the time vector: f.rows, or B where there is no guidance pair
     FwdCtx c;                                              // the forward (and, with vjp_run, the chain's d_out / dx_out)
     const float* q = nullptr;                              // Guided: (dv/dx)^T w of the same forward (exact form), or NULL
-    const float* probe = nullptr;                          // Likelihood: eps ...
-    double* a = nullptr;                                   // ... and the accumulator the interval adds to
+    const float* probe = nullptr;                          // Likelihood: eps [n_probes][B][m] ...
+    double* a = nullptr;                                   // ... and the accumulators [n_probes][B] the interval adds to
+    int n_probes = 1;
 };
+
+// The likelihood's chains behind one forward: for k in probe order the data-gradient chain with probe k as output cotangent into slice
+// k of ll_g.  The trajectory does not depend on the probe and a chain leaves the forward's saved activations as they are, so K probes
+// cost one forward and K chains.  n = B * m: the slices' stride is the call's B, in the probes and in ll_g alike.
+static int probe_chains(fc_unet* u, FwdCtx c, const float* probes, int n_probes, int n, hipStream_t s) {
+    for (int k = 0; k < n_probes; ++k) {
+        c.d_out = probes + (size_t)k * n; c.dx_out = u->ig.ll_g + (size_t)k * n;
+        FC_TRY(vjp_run(u, c, s));
+    }
+    return FC_OK;
+}
+
+// The likelihood's buffers for n_probes probes per call (plan lifetime; grown, behind the library stream's work, when a call brings
+// more probes than any before).  No captured graph holds them: the likelihood launches directly.
+static int ll_reserve(fc_unet* u, int n_probes, hipStream_t s) {
+    IntegratorState& ig = u->ig;
+    if (n_probes <= ig.ll_k) return FC_OK;
+    const size_t m = (size_t)u->cfg.channels * u->H * u->W;
+    if (ig.ll_k) FC_HIP(hipStreamSynchronize(s));
+    ig.ll_k = 0;
+    for (double** b : {&ig.ll_d, &ig.rk_dk, &ig.rk_ak}) ig.drop(b);
+    ig.drop(&ig.ll_g);
+    FC_TRY(ig.get(&ig.ll_d, (size_t)n_probes * u->maxB * 3, "integrator.likelihood"));
+    FC_TRY(ig.get(&ig.ll_g, (size_t)n_probes * u->maxB * m, "integrator.likelihood"));
+    ig.ll_k = n_probes;
+    return FC_OK;
+}
+
+// what the two likelihood entry points check of their probe arguments; `fn` names the entry point
+static int check_probes(const char* fn, int n_probes, const double* a_probes_out, const double* stderr_out) {
+    if (n_probes < 1 || n_probes > FC_LL_MAX_PROBES)
+        return fail(FC_E_ARG, std::string(fn) + ": n_probes must lie in [1, " + std::to_string(FC_LL_MAX_PROBES) + "] (the cap on probes per call)");
+    if (!a_probes_out != !stderr_out || (n_probes > 1 && !a_probes_out))
+        return fail(FC_E_ARG, std::string(fn) + ": several probes need a_probes_out_dev and stderr_out_dev");
+    return FC_OK;
+}
 
 static int enqueue_rk4_interval(const CallFrame& f, const Rk4Variant& v, float cfg, float t_scale) {
     fc_unet* u = f.u;
@@ -206,12 +243,13 @@ static int enqueue_rk4_interval(const CallFrame& f, const Rk4Variant& v, float c
         const float* x = c.x = j == 0 ? ig.y : ig.xs;      // k1 = f(y, t); k2, k3, k4 at the state the stage before wrote
         FC_TRY(run_plan(u->plan, c, s));
         if (v.eval == Rk4Variant::ForwardGuideWVjp) FC_TRY(ode_guide_w_launch(ig.sc, ig.g_sc, ig.v2, x, ig.g_y, ig.g_keep, ig.g_w, n, st.tcur, s));
-        if (v.eval != Rk4Variant::Forward) FC_TRY(vjp_run(u, c, s));
         if (v.close == Rk4Variant::Likelihood) {
-            FC_TRY(j < 3 ? ode_ll_stage_launch(ig.sc, ig.y, ig.xs, st.k_out, ig.v2, ig.ll_g, v.probe, ig.ll_d, j, f.B, m, st.full, st.tsel, t_scale, ig.tvec, s)
-                         : ode_ll_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.ll_g, v.probe, ig.ll_d, v.a, f.B, m, s));
+            FC_TRY(probe_chains(u, c, v.probe, v.n_probes, n, s));
+            FC_TRY(j < 3 ? ode_ll_stage_launch(ig.sc, ig.y, ig.xs, st.k_out, ig.v2, ig.ll_g, v.probe, ig.ll_d, j, f.B, m, st.full, st.tsel, t_scale, ig.tvec, v.n_probes, s)
+                         : ode_ll_final_launch(ig.sc, ig.y, ig.k1, ig.k2, ig.k3, ig.v2, ig.ll_g, v.probe, ig.ll_d, v.a, f.B, m, v.n_probes, s));
             continue;
         }
+        if (v.eval != Rk4Variant::Forward) FC_TRY(vjp_run(u, c, s));
         const Rk4Guide guide{ig.g_sc, x, ig.g_y, ig.g_keep, v.q, st.tcur};
         const Rk4Guide* g = v.close == Rk4Variant::Guided ? &guide : nullptr;
         FC_TRY(j < 3 ? ode_rk4_stage_launch(ig.sc, ig.y, ig.xs, st.k_out, ig.v2, n, cf, cfg, st.full, st.tsel, t_scale, ig.tvec, v.trows, g, s)
@@ -386,37 +424,54 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
 // kernels of ode.hip carrying a[b] = integral of eps^T (dv/dx) eps dt.  The grid is known, so nothing is decided on the host: the call
 // returns with the whole loop queued.  Direct launches (4 (n_points - 1) forwards + chains); the arena ends up holding the last stage's
 // forward, which belongs to nobody: the serial moves and a later backward re-runs its own forward.
+// K probes (fc_unet_log_likelihood_probes; K = 1 without per-probe outputs is fc_unet_log_likelihood): one forward per evaluation, K
+// chains behind it, every probe its own accumulator a_k in a_probes_out; a_out is their mean and logp is formed from it.
+static int log_likelihood_rk4(const char* fn, fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
+                              const int64_t* ids, const float* mask, int mask_is_ones, const float* probes_dev, int n_probes,
+                              double* a_out_dev, double* logp_out_dev, double* a_probes_out_dev, double* stderr_out_dev, void* stream) {
+    if (!u || !x_dev || !ts_host || !probes_dev || !a_out_dev || !logp_out_dev || B < 1) return fail(FC_E_ARG, std::string(fn) + ": null argument");
+    if (n_points < 2) return fail(FC_E_ARG, std::string(fn) + ": the time grid needs at least two points");
+    FC_TRY(check_probes(fn, n_probes, a_probes_out_dev, stderr_out_dev));
+    FC_TRY(check_aligned16({probes_dev}, (std::string(fn) + ": probe_dev must be 16-byte aligned (the kernels read it as float4)").c_str()));
+    CallFrame f;
+    FC_TRY(f.begin(u, B, H, W, ids, 0.0f, mask, mask_is_ones, stream));      // no guidance
+    if (!u->keep_all) return fail(FC_E_STATE, std::string(fn) + ": no backward plan for this shape; call fc_unet_train_reserve");
+    FC_TRY(vjp_check(u, B, H, W, fn));
+    IntegratorState& ig = u->ig;
+    const int m = u->cfg.channels * H * W;
+    FC_TRY(ll_reserve(u, n_probes, f.s));
+    FC_TRY(f.enter());
+    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
+    double* acc = a_probes_out_dev ? a_probes_out_dev : a_out_dev;           // one probe without per-probe outputs: a is its accumulator
+    FC_HIP(hipMemsetAsync(acc, 0, (size_t)n_probes * B * sizeof(double), f.s));
+    Rk4Variant v{Rk4Variant::ForwardVjp, Rk4Variant::Likelihood, B, integrator_ctx(f)};   // v2 = v(x, tvec), ll_g[k] = (dv/dx)^T probe k
+    v.probe = probes_dev; v.a = acc; v.n_probes = n_probes;
+    for (int i = 0; i + 1 < n_points; ++i) FC_TRY(enqueue_rk4_interval(f, v, 0.0f, t_scale));
+    if (a_probes_out_dev) FC_TRY(ode_ll_mean_launch(a_probes_out_dev, n_probes, B, a_out_dev, stderr_out_dev, 0, f.s));
+    FC_TRY(ode_ll_logp_launch(ig.y, a_out_dev, logp_out_dev, B, m, f.s));
+    return f.finish(x_dev);
+}
+
 int fc_unet_log_likelihood(fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
                            const int64_t* ids, const float* mask, int mask_is_ones, const float* probe_dev, double* a_out_dev,
                            double* logp_out_dev, void* stream) {
-    if (!u || !x_dev || !ts_host || !probe_dev || !a_out_dev || !logp_out_dev || B < 1) return fail(FC_E_ARG, "fc_unet_log_likelihood: null argument");
-    if (n_points < 2) return fail(FC_E_ARG, "fc_unet_log_likelihood: the time grid needs at least two points");
-    FC_TRY(check_aligned16({probe_dev}, "fc_unet_log_likelihood: probe_dev must be 16-byte aligned (the kernels read it as float4)"));
-    CallFrame f;
-    FC_TRY(f.begin(u, B, H, W, ids, 0.0f, mask, mask_is_ones, stream));      // no guidance
-    if (!u->keep_all) return fail(FC_E_STATE, "fc_unet_log_likelihood: no backward plan for this shape; call fc_unet_train_reserve");
-    FC_TRY(vjp_check(u, B, H, W, "fc_unet_log_likelihood"));
-    IntegratorState& ig = u->ig;
-    const int m = u->cfg.channels * H * W;
-    if (!ig.ll_g) {
-        FC_TRY(ig.get(&ig.ll_d, (size_t)u->maxB * 3, "integrator.likelihood"));
-        FC_TRY(ig.get(&ig.ll_g, (size_t)u->maxB * m, "integrator.likelihood"));
-    }
-    FC_TRY(f.enter());
-    FC_TRY(integrator_prologue(f, x_dev, ts_host, n_points));
-    FC_HIP(hipMemsetAsync(a_out_dev, 0, (size_t)B * sizeof(double), f.s));
-    Rk4Variant v{Rk4Variant::ForwardVjp, Rk4Variant::Likelihood, B, integrator_ctx(f)};   // v2 = v(x, tvec), ll_g = (dv/dx)^T probe
-    v.c.d_out = v.probe = probe_dev; v.c.dx_out = ig.ll_g; v.a = a_out_dev;
-    for (int i = 0; i + 1 < n_points; ++i) FC_TRY(enqueue_rk4_interval(f, v, 0.0f, t_scale));
-    FC_TRY(ode_ll_logp_launch(ig.y, a_out_dev, logp_out_dev, B, m, f.s));
-    return f.finish(x_dev);
+    return log_likelihood_rk4("fc_unet_log_likelihood", u, x_dev, B, H, W, ts_host, n_points, t_scale, ids, mask, mask_is_ones, probe_dev, 1,
+                              a_out_dev, logp_out_dev, nullptr, nullptr, stream);
+}
+
+int fc_unet_log_likelihood_probes(fc_unet* u, float* x_dev, int B, int H, int W, const float* ts_host, int n_points, float t_scale,
+                                  const int64_t* ids, const float* mask, int mask_is_ones, const float* probes_dev, int n_probes,
+                                  double* a_out_dev, double* logp_out_dev, double* a_probes_out_dev, double* stderr_out_dev, void* stream) {
+    if (!a_probes_out_dev || !stderr_out_dev) return fail(FC_E_ARG, "fc_unet_log_likelihood_probes: null argument");
+    return log_likelihood_rk4("fc_unet_log_likelihood_probes", u, x_dev, B, H, W, ts_host, n_points, t_scale, ids, mask, mask_is_ones,
+                              probes_dev, n_probes, a_out_dev, logp_out_dev, a_probes_out_dev, stderr_out_dev, stream);
 }
 
 int fc_debug_probe_dot(const float* probe_dev, const float* g_dev, double* out_dev, int batch, int64_t per_sample, void* stream) {
     if (!probe_dev || !g_dev || !out_dev) return fail(FC_E_ARG, "fc_debug_probe_dot: null argument");
     FC_TRY(check_aligned16({probe_dev, g_dev}, "fc_debug_probe_dot: inputs must be 16-byte aligned (read as float4)"));
     if (per_sample < 1 || per_sample > 0x7fffffff) return fail(FC_E_SHAPE, "fc_debug_probe_dot: bad element count");
-    return ode_ll_dot_launch(probe_dev, g_dev, out_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
+    return ode_ll_dot_launch(probe_dev, g_dev, out_dev, nullptr, batch, (int)per_sample, 1, static_cast<hipStream_t>(stream));
 }
 
 // ---- measurement guidance on the RK4 grid ------------------------------------------------------------------------------------------
@@ -617,12 +672,12 @@ static int alloc_rk45(fc_unet* u) {
 
 // What the adaptive likelihood adds to the controller state (plan lifetime, first use): the divergence track a | a_new and the seven
 // rows of its K values; g of the running evaluation is the RK4 likelihood's buffer.
-static int alloc_rk45_ll(fc_unet* u) {
+static int alloc_rk45_ll(fc_unet* u, int n_probes, bool per_probe, hipStream_t s) {
     IntegratorState& ig = u->ig;
-    const int m = u->cfg.channels * u->H * u->W;
-    if (!ig.ll_g) {
-        FC_TRY(ig.get(&ig.ll_d, (size_t)u->maxB * 3, "integrator.likelihood"));
-        FC_TRY(ig.get(&ig.ll_g, (size_t)u->maxB * m, "integrator.likelihood"));
+    FC_TRY(ll_reserve(u, n_probes, s));
+    if (per_probe && !ig.rk_dk) {   // (ll_reserve drops them when the probe count grows)
+        FC_TRY(ig.get(&ig.rk_dk, (size_t)7 * ig.ll_k * u->maxB, "integrator.rk45_likelihood"));
+        FC_TRY(ig.get(&ig.rk_ak, (size_t)ig.ll_k * u->maxB, "integrator.rk45_likelihood"));
     }
     if (ig.rk_a) return FC_OK;
     FC_TRY(ig.get(&ig.rk_d, (size_t)u->maxB * 7, "integrator.rk45_likelihood"));
@@ -631,7 +686,8 @@ static int alloc_rk45_ll(fc_unet* u) {
 
 // The likelihood side of an adaptive solve (fc_unet_log_likelihood_rk45): every evaluation is the forward, the data-gradient chain with
 // the probe as output cotangent and the per-row reduction d = sum eps g into row `slot` of the divergence track's K values.
-struct Rk45Likelihood { const float* probe; double *a_out, *logp_out; };
+// n_probes probes ([K][B][m]): d is their mean; with a_probes_out / stderr_out every probe's own integral is carried beside it.
+struct Rk45Likelihood { const float* probe; double *a_out, *logp_out; int n_probes; double *a_probes_out, *stderr_out; };
 
 // one attempt of RungeKutta._step_impl for every group that still steps: five stages, y_new and f(t + h, y_new), the error norms,
 // the controllers, with a dense-output request (`ev`) the frames an accepted step serves, the commit, the status summary
@@ -718,7 +774,7 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
         return FC_OK;
     }
     if (!ig.rk_st) FC_TRY(alloc_rk45(u));
-    if (lk) FC_TRY(alloc_rk45_ll(u));
+    if (lk) FC_TRY(alloc_rk45_ll(u, lk->n_probes, lk->a_probes_out != nullptr, s));
     if (!ig.rk_host) { void* hp = nullptr; FC_HIP(hipHostMalloc(&hp, sizeof(Rk45Status), hipHostMallocDefault)); ig.rk_host = static_cast<Rk45Status*>(hp); }
     if (!ig.ev_rk) FC_HIP(hipEventCreateWithFlags(&ig.ev_rk, hipEventDisableTiming));
 
@@ -729,18 +785,20 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     // f(t0, y0) and select_initial_step of every group (two forwards, no graph)
     FwdCtx c = integrator_ctx(f);
     c.x = ig.xs;   // every forward of the solve reads the stage input the RK45 kernels write
-    const Rk45LL track{ig.rk_a, ig.rk_d, B};
+    const int K = lk ? lk->n_probes : 1;
+    const bool per_probe = lk && lk->a_probes_out;
+    const Rk45LL track{ig.rk_a, ig.rk_d, B, K, per_probe ? ig.rk_dk : nullptr, per_probe ? ig.rk_ak : nullptr};
     const Rk45LL* ll = lk ? &track : nullptr;
     const int m1 = n / B;
-    if (lk) {      // v2 = v(xs, tvec), ll_g = (dv/dx)^T probe; a = 0 at t0
-        c.d_out = lk->probe; c.dx_out = ig.ll_g;
+    if (lk) {      // v2 = v(xs, tvec), ll_g[k] = (dv/dx)^T probe k; a = 0 (and every a_k = 0) at t0
         FC_HIP(hipMemsetAsync(ig.rk_a, 0, (size_t)2 * B * sizeof(double), s));
+        if (per_probe) FC_HIP(hipMemsetAsync(ig.rk_ak, 0, (size_t)K * B * sizeof(double), s));
     }
     const std::function<int(int)> eval = [&](int slot) {
         FC_TRY(run_plan(u->plan, c, s));
         if (!lk) return (int)FC_OK;
-        FC_TRY(vjp_run(u, c, s));
-        return ode_ll_dot_launch(lk->probe, ig.ll_g, ig.rk_d + (size_t)slot * B, B, m1, s);
+        FC_TRY(probe_chains(u, c, lk->probe, K, n, s));
+        return ode_ll_dot_launch(lk->probe, ig.ll_g, ig.rk_d + (size_t)slot * B, per_probe ? ig.rk_dk + (size_t)slot * K * B : nullptr, B, m1, K, s);
     };
     FC_TRY(rk45_setup_launch(g, x_dev, ig.rk_y, ig.xs, ig.rk_st, t0, t1, rtol, atol, kRk45MaxAttempts, t_scale, ig.tvec, cf, s));
     FC_TRY(eval(0));                                                                                          // f0
@@ -782,6 +840,10 @@ static int integrate_rk45(fc_unet* u, bool per_sample, const char* fn, float* x_
     if (!failed && lk) {
         FC_HIP(hipMemcpyAsync(lk->a_out, ig.rk_a, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s));
         FC_TRY(ode_ll_logp_launch(x_dev, lk->a_out, lk->logp_out, B, m1, s));
+        if (per_probe) {      // the by-products; a_out stays the solve's own a (the mean's integral), not the mean of these
+            FC_HIP(hipMemcpyAsync(lk->a_probes_out, ig.rk_ak, (size_t)K * B * sizeof(double), hipMemcpyDeviceToDevice, s));
+            FC_TRY(ode_ll_mean_launch(ig.rk_ak, K, B, lk->a_out, lk->stderr_out, 1, s));
+        }
     }
     FC_TRY(f.leave());
     if (!failed) return FC_OK;
@@ -824,16 +886,50 @@ int fc_unet_integrate_rk45_dense(fc_unet* u, int per_sample, float* x_dev, int B
 // x from t0 back to t1 < t0 with the adaptive solve above over [x, a]: the integration error of a and z is the controller's, not a
 // grid's.  The host waits on the status summary behind every attempt, as the sampler; x_inout, a_out and logp_out are written only when
 // every group finished.
+static int log_likelihood_rk45(const char* fn, fc_unet* u, float* x_inout, int batch, int H, int W, double t0, double t1, double rtol,
+                               double atol, float t_scale, const int64_t* class_ids, const float* mask, int mask_is_ones, const float* probes,
+                               int n_probes, int per_sample, double* a_out, double* logp_out, double* a_probes_out, double* stderr_out,
+                               int* counters, void* stream) {
+    if (!u || !x_inout || !probes || !a_out || !logp_out || !counters || batch < 1) return fail(FC_E_ARG, std::string(fn) + ": null argument");
+    if (!(t1 < t0) || !(t1 >= 0.0) || !(t0 <= 1.0)) return fail(FC_E_ARG, std::string(fn) + ": needs 0 <= t1 < t0 <= 1 (data at t0 towards noise)");
+    FC_TRY(check_probes(fn, n_probes, a_probes_out, stderr_out));
+    FC_TRY(check_aligned16({x_inout, probes}, (std::string(fn) + ": x and the probe must be 16-byte aligned (the kernels read them as float4)").c_str()));
+    const Rk45Likelihood lk{probes, a_out, logp_out, n_probes, a_probes_out, stderr_out};
+    return integrate_rk45(u, per_sample != 0, fn, x_inout, batch, H, W, t0, t1, rtol, atol, t_scale, class_ids, 0.0f, mask, mask_is_ones,
+                          nullptr, 0, nullptr, counters, stream, &lk);
+}
+
 int fc_unet_log_likelihood_rk45(fc_unet* u, float* x_inout, int batch, int H, int W, double t0, double t1, double rtol, double atol,
                                 float t_scale, const int64_t* class_ids, const float* mask, int mask_is_ones, const float* probe,
                                 int per_sample, double* a_out, double* logp_out, int* counters, void* stream) {
-    const char* fn = "fc_unet_log_likelihood_rk45";
-    if (!u || !x_inout || !probe || !a_out || !logp_out || !counters || batch < 1) return fail(FC_E_ARG, std::string(fn) + ": null argument");
-    if (!(t1 < t0) || !(t1 >= 0.0) || !(t0 <= 1.0)) return fail(FC_E_ARG, std::string(fn) + ": needs 0 <= t1 < t0 <= 1 (data at t0 towards noise)");
-    FC_TRY(check_aligned16({x_inout, probe}, "fc_unet_log_likelihood_rk45: x and the probe must be 16-byte aligned (the kernels read them as float4)"));
-    const Rk45Likelihood lk{probe, a_out, logp_out};
-    return integrate_rk45(u, per_sample != 0, fn, x_inout, batch, H, W, t0, t1, rtol, atol, t_scale, class_ids, 0.0f, mask, mask_is_ones,
-                          nullptr, 0, nullptr, counters, stream, &lk);
+    return log_likelihood_rk45("fc_unet_log_likelihood_rk45", u, x_inout, batch, H, W, t0, t1, rtol, atol, t_scale, class_ids, mask,
+                               mask_is_ones, probe, 1, per_sample, a_out, logp_out, nullptr, nullptr, counters, stream);
+}
+
+int fc_unet_log_likelihood_rk45_probes(fc_unet* u, float* x_inout, int batch, int H, int W, double t0, double t1, double rtol, double atol,
+                                       float t_scale, const int64_t* class_ids, const float* mask, int mask_is_ones, const float* probes,
+                                       int n_probes, int per_sample, double* a_out, double* logp_out, double* a_probes_out,
+                                       double* stderr_out, int* counters, void* stream) {
+    if (!a_probes_out || !stderr_out) return fail(FC_E_ARG, "fc_unet_log_likelihood_rk45_probes: null argument");
+    return log_likelihood_rk45("fc_unet_log_likelihood_rk45_probes", u, x_inout, batch, H, W, t0, t1, rtol, atol, t_scale, class_ids, mask,
+                               mask_is_ones, probes, n_probes, per_sample, a_out, logp_out, a_probes_out, stderr_out, counters, stream);
+}
+
+// The likelihood's counter-based probe field.  The key is the caller's seed moved by a constant, so that a likelihood seed does not
+// replay the SDE sampler's noise of the same seed; the probe index takes the counter word the sampler's draw index has.
+int fc_ode_probe_field(float* out_dev, int kind, uint64_t seed, int64_t probe_index, const int64_t* sample_ids_dev, int batch,
+                       int64_t per_sample, void* stream) {
+    if (!out_dev) return fail(FC_E_ARG, "fc_ode_probe_field: null argument");
+    if (kind != FC_PROBE_RADEMACHER && kind != FC_PROBE_GAUSSIAN) return fail(FC_E_ARG, "fc_ode_probe_field: unknown kind");
+    FC_TRY(check_aligned16({out_dev}, "fc_ode_probe_field: out must be 16-byte aligned (written as float4)"));
+    if (probe_index < 0 || probe_index > 0xffffffffLL) return fail(FC_E_ARG, "fc_ode_probe_field: the probe index is a 32-bit counter word");
+    if (batch < 1 || per_sample < 4 || (per_sample & 3) || (long long)batch * per_sample > 0x7fffffffLL)
+        return fail(FC_E_SHAPE, "fc_ode_probe_field: elements per sample must be a positive multiple of 4, batch * per_sample < 2^31");
+    const uint64_t key = seed + FC_PROBE_KEY_OFFSET;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return kind == FC_PROBE_RADEMACHER
+               ? ode_rademacher_field_launch(out_dev, key, (unsigned)probe_index, sample_ids_dev, batch * (int)per_sample, (int)per_sample, s)
+               : ode_probe_normal_field_launch(out_dev, key, (unsigned)probe_index, sample_ids_dev, batch * (int)per_sample, (int)per_sample, s);
 }
 
 }  // extern "C"

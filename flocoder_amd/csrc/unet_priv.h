@@ -1,6 +1,7 @@
 // The velocity U-Net object behind the fc_unet_* entry points (unet.hip: parameters, forward plan, handle lifecycle;
 // unet_integrate.hip: the integrators; unet_backward.hip: backward plan of the training step).
 #pragma once
+#include <algorithm>
 #include <map>
 #include <tuple>
 
@@ -44,11 +45,15 @@ struct IntegratorPlanState {
     Rk45Status* rk_sum = nullptr;
     // adaptive likelihood (fc_unet_log_likelihood_rk45): the divergence track a | a_new ([2][maxB]) and its K values ([7][maxB]),
     // allocated by the first call (g is ll_g below)
-    double *rk_a = nullptr, *rk_d = nullptr;
+    // ... and with per-probe results its per-probe rows: every probe's K values ([7][ll_k][maxB]) and own integral ([ll_k][maxB])
+    double *rk_a = nullptr, *rk_d = nullptr, *rk_dk = nullptr, *rk_ak = nullptr;
     // likelihood (fc_unet_log_likelihood): g = (dv/dx)^T eps of the running stage and the per-sample stage sums d1..d3 of the running
     // interval, allocated by the first call
+    // With K probes per call g is [K][B][m] and the stage sums [K][B][3] (the call's B is the stride): the buffers hold ll_k probes of
+    // maxB rows and grow when a call brings more (ll_reserve)
     float* ll_g = nullptr;
     double* ll_d = nullptr;
+    int ll_k = 0;
     // measurement guidance (fc_unet_integrate_guided): the call's measurement and keep weights in the library's own buffers (made like
     // mask_own), {sigma_y^2, gamma} of the call, and for the exact form w and q = (dv/dx)^T w of the running stage; allocated by the
     // first call
@@ -63,6 +68,13 @@ struct IntegratorPlanState {
         allocs.push_back(p);
         *out = static_cast<T*>(p);
         return FC_OK;
+    }
+    // free one buffer ahead of the plan (a buffer that grows); the caller has waited for its last user
+    template <class T> void drop(T** buf) {
+        if (!*buf) return;
+        allocs.erase(std::remove(allocs.begin(), allocs.end(), static_cast<void*>(*buf)), allocs.end());
+        dev_free(*buf);
+        *buf = nullptr;
     }
 };
 // ... and this part as long as the HANDLE (fc_unet_create makes the stream and its two events, release_handle() frees all of it).

@@ -8,7 +8,8 @@
   ``$FLOCODER_FID_INCEPTION``) mapping uint8 images [B,3,H,W] to features [B,F] -- torchmetrics downloads its weights, this build
   never touches the network and raises FileNotFoundError without one;
 * ``compute_sample_metrics`` (metrics.py:493-555) -- the same dictionary of numbers;
-* ``bits_per_dim`` -- the flow's log-likelihood (``sampling.log_likelihood``) as bits per latent dimension (no upstream counterpart).
+* ``bits_per_dim`` -- the flow's log-likelihood (``sampling.log_likelihood``) as bits per latent dimension (no upstream counterpart);
+  ``bits_per_dim_stderr`` -- its standard error from a K-probe call's ``logp_stderr``.
 """
 import ctypes as C
 import os
@@ -65,6 +66,13 @@ def bits_per_dim(logp, numel):
     volume is not in it, so the figure compares flows over the same latent space, not models of the pixels."""
     import math
     return -logp / (float(numel) * math.log(2.0))
+
+
+def bits_per_dim_stderr(stderr, numel):
+    """``sampling.log_likelihood(..., return_info=True)``'s ``logp_stderr`` (nats) as bits per dimension: ``stderr / (numel ln 2)``, the
+    standard error of ``bits_per_dim`` of the same sample from the divergence estimator's variance."""
+    import math
+    return stderr / (float(numel) * math.log(2.0))
 
 
 def sample_stats(pred_latents, target_latents, decoded_pred, decoded_target):

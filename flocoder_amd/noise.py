@@ -75,6 +75,28 @@ def normal_field(seed: int, draw_index: int, sample_ids, per_sample: int) -> np.
     return z.reshape(z.shape[0], int(per_sample))
 
 
+# ---- the likelihood's probe field (csrc/ode.hip, fc_ode_probe_field) ----------------------------------------------------------------------
+PROBE_KEY_OFFSET = 0x50524F4245464C44      # "PROBEFLD": added to the seed (mod 2^64), so a likelihood seed does not replay the SDE noise
+PROBE_KINDS = {"rademacher": 0, "gaussian": 1}
+
+
+def probe_field(seed: int, probe_index: int, sample_ids, per_sample: int, kind="rademacher") -> np.ndarray:
+    """fp32 ``[B, per_sample]``: row b holds Hutchinson probe ``probe_index`` of ``(seed, sample_ids[b])``, what ``fc_ode_probe_field``
+    writes.  The Philox key is ``seed + PROBE_KEY_OFFSET`` (mod 2^64), the counter ``(j, probe_index, sample id lo, sample id hi)`` with
+    ``j`` the group of four inside the sample: an entry depends on (seed, probe index, sample id, position) and on nothing else.
+    ``"rademacher"`` (or 0): +1 where the top bit of the entry's Philox word is clear, -1 where it is set -- the device's bits exactly.
+    ``"gaussian"`` (or 1): ``normal_field``'s uniforms and transform under that key (tail cut at 5.77), evaluated in fp64 and rounded once
+    to fp32 -- the device does the same (fp64 transform, one rounding), so the two agree in bits."""
+    kind = PROBE_KINDS.get(kind, kind)
+    if kind not in (0, 1):
+        raise ValueError(f"kind={kind!r}: 'rademacher' (0) or 'gaussian' (1)")
+    key = (int(seed) + PROBE_KEY_OFFSET) & 0xffffffffffffffff
+    if kind == 1:
+        return normal_field(key, probe_index, sample_ids, per_sample).astype(np.float32)
+    w = field_words(key, probe_index, sample_ids, per_sample)
+    return (1.0 - 2.0 * (w >> np.uint32(31)).astype(np.float32)).reshape(w.shape[0], int(per_sample))
+
+
 # ---- the plan sampler's uniforms (csrc/ot_plan.hip, fc_ot_sample_plan) ------------------------------------------------------------------
 PLAN_TAG = 0x4F54504C            # "OTPL": counter word 2 of the plan sampler; word 3 is 0xFFFFFFFF, a sample id no non-negative int64 has
 

@@ -224,6 +224,28 @@ def normal_field(seed, draw_index, sample_ids, shape, device=None, dtype=torch.f
     return out.to(dtype)
 
 
+def probe_field(seed, probe_index, sample_ids, shape, kind="rademacher", device=None, dtype=torch.float32):
+    """The likelihood's counter-based probe field as a tensor ``[B, *shape[1:]]``: row b holds probe ``probe_index`` of
+    ``(seed, sample_ids[b])`` (``flocoder_amd.noise.probe_field``): it depends on those and the position in the sample, never on the
+    row or the batch size.  On a GPU device the library generates it (``fc_ode_probe_field``); on the CPU the NumPy form does."""
+    from . import _binding as B
+    from . import noise as N
+    device = torch.device("cpu" if device is None else device)
+    bsz, per = int(shape[0]), 1
+    for d in shape[1:]:
+        per *= int(d)
+    if kind not in N.PROBE_KINDS:
+        raise ValueError(f"kind={kind!r}: 'rademacher' or 'gaussian'")
+    if device.type != "cuda":
+        ids = sample_ids.detach().cpu().numpy() if torch.is_tensor(sample_ids) else sample_ids
+        return torch.from_numpy(N.probe_field(seed, probe_index, ids, per, kind)).reshape(tuple(shape)).to(device=device, dtype=dtype)
+    ids = torch.as_tensor(sample_ids, dtype=torch.int64).to(device).contiguous()
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    B.check(B.lib().fc_ode_probe_field(B.ptr(out), N.PROBE_KINDS[kind], int(seed) & 0xffffffffffffffff, int(probe_index), B.ptr(ids), bsz, per,
+                                       B.current_stream(device)))
+    return out.to(dtype)
+
+
 _SDE_EVALS = {"euler_maruyama": 1, "heun": 2}
 
 
@@ -440,8 +462,61 @@ def _make_probe(probe, latents, generator):
     return e.to(latents.device).contiguous()
 
 
+def _make_probes(probe, latents, generator, n_probes, probe_seed, sample_ids):
+    """The probes of a ``log_likelihood`` call -> (eps, K): eps of the latents' shape for a plain single-probe call (K is None: today's
+    call), else ``[K, *latents.shape]``."""
+    from . import _binding as B
+    n_probes = int(n_probes)
+    if torch.is_tensor(probe) and probe.dim() == latents.dim() + 1:
+        if probe.shape[1:] != latents.shape:
+            raise ValueError(f"probe must have the shape of latents {tuple(latents.shape)} or [K, ...] of it, got {tuple(probe.shape)}")
+        if n_probes not in (1, probe.shape[0]):
+            raise ValueError(f"n_probes={n_probes} does not agree with the probe tensor's {probe.shape[0]} probes")
+        if probe_seed is not None:
+            raise ValueError("probe_seed draws the probes: pass a kind ('rademacher', 'gaussian'), not a tensor")
+        k = int(probe.shape[0])
+        if not 1 <= k <= B.FC_LL_MAX_PROBES:
+            raise ValueError(f"n_probes={k} must lie in [1, {B.FC_LL_MAX_PROBES}] (the cap on probes per call)")
+        return probe.to(device=latents.device, dtype=latents.dtype).contiguous(), k
+    if not 1 <= n_probes <= B.FC_LL_MAX_PROBES:
+        raise ValueError(f"n_probes={n_probes} must lie in [1, {B.FC_LL_MAX_PROBES}] (the cap on probes per call)")
+    if probe_seed is not None:
+        if generator is not None:
+            raise ValueError("probe_seed and generator are two sources of the probes: pass one")
+        if torch.is_tensor(probe):
+            raise ValueError("probe_seed draws the probes: pass a kind ('rademacher', 'gaussian'), not a tensor")
+        ids = torch.arange(latents.shape[0]) if sample_ids is None else torch.as_tensor(sample_ids, dtype=torch.int64).reshape(-1)
+        if ids.numel() != latents.shape[0]:
+            raise ValueError(f"sample_ids must name the {latents.shape[0]} samples, got {ids.numel()}")
+        eps = torch.stack([probe_field(probe_seed, k, ids, latents.shape, probe, latents.device, latents.dtype) for k in range(n_probes)])
+        return eps.contiguous(), n_probes
+    if sample_ids is not None:
+        raise ValueError("sample_ids index the counter-based probes: pass probe_seed")
+    if n_probes == 1:
+        return _make_probe(probe, latents, generator), None
+    if torch.is_tensor(probe):
+        raise ValueError(f"n_probes={n_probes} needs a [K, ...] probe tensor or a kind to draw from")
+    return torch.stack([_make_probe(probe, latents, generator) for _ in range(n_probes)]).contiguous(), n_probes
+
+
+def _ll_info(a, a_probes, stderr, k):
+    return {"logp_stderr": stderr, "a": a, "a_probes": a_probes, "n_probes": k}
+
+
+def _probe_stats(a_probes, a=None):
+    """(mean in probe order with one division, standard error of the mean around ``a`` or that mean) of ``a_probes`` [K, B] fp64"""
+    k = a_probes.shape[0]
+    mean = a_probes[0].clone()
+    for i in range(1, k):
+        mean = mean + a_probes[i]
+    mean = mean / k
+    centre = mean if a is None else a
+    se = torch.sqrt(((a_probes - centre) ** 2).sum(dim=0) / (k * (k - 1))) if k > 1 else torch.full_like(mean, float("nan"))
+    return mean, se
+
+
 def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", generator=None, cfg_strength=None, method="rk4", rtol=1e-5,
-                   atol=1e-5, per_sample=True, t_end=0.0):
+                   atol=1e-5, per_sample=True, t_end=0.0, n_probes=1, probe_seed=None, sample_ids=None, return_info=False):
     """log p_1(latents) under the flow: the change of variables along the probability-flow ODE walked from t = 1 to t = 0 on
     ``rk4_time_grid(n_steps)`` reversed, with Hutchinson's estimate of the divergence.  Interval by interval (dt < 0), every RK4 stage j
     gives ``v_j = model(x_j, 999 t_j, cond)`` and ``d_j[b] = sum_i eps[b,i] ((dv_j/dx_j)^T eps)[b,i]`` (one VJP of the same forward);
@@ -476,7 +551,19 @@ def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", ge
     batch, as the literature's code does.  ``logp`` is then ``-|z|^2/2 - (D/2) ln 2pi + a`` with ``z = x(t_end)``; nfe is scipy's
     ``nfev`` (per sample: the largest).  A ``flocoder_amd.Unet`` runs the solve in the library (``Unet.log_likelihood_rk45``:
     controller on the device, x in fp64 with fp32 evaluations, a entirely fp64); any other callable goes through ``solve_ivp`` on the
-    host with ``torch.autograd.grad`` per evaluation, in the dtype of ``latents``.  A failed solve raises RuntimeError."""
+    host with ``torch.autograd.grad`` per evaluation, in the dtype of ``latents``.  A failed solve raises RuntimeError.
+
+    Several probes in ONE solve: ``n_probes=K`` (1 <= K <= 64), or ``probe`` a ``[K, *latents.shape]`` tensor (``n_probes`` must then
+    agree or stay 1).  The trajectory does not depend on the probe, so every evaluation is one forward and K VJPs, and ``nfe`` -- the
+    number of VELOCITY evaluations -- does not grow with K.  RK4 grid: every probe carries its own accumulator ``a_k`` (bit-equal to a
+    single-probe call with that probe on the device) and ``a = (a_1 + ... + a_K) / K``.  RK45: the state stays ``[x, a]`` with
+    ``da/dt`` the mean of the K estimates, so K copies of one probe reproduce the single-probe solve; the ``a_k`` are by-products summed
+    over the accepted steps.  Drawn probes come from ``generator`` as before (K draws, the first the one a K = 1 call makes) or, with
+    ``probe_seed`` set (``generator`` must then be None), from the counter-based field ``probe_field(probe_seed, k, sample_ids, ...)``
+    (``sample_ids`` default ``arange(B)``): a sample's probes, hence its ``logp``, then depend on its id and not on its row or batch.
+    ``return_info=True`` appends a dict ``{"logp_stderr", "a", "a_probes", "n_probes"}``: ``logp_stderr`` fp64 ``[B]`` =
+    ``sqrt(sum_k (a_k - a)^2 / (K (K - 1)))`` (NaN for K = 1), the standard error of ``logp`` from the estimator's variance;
+    ``metrics.bits_per_dim_stderr`` converts it."""
     _check_ode_method(method)
     if cfg_strength:
         raise ValueError("log_likelihood takes no classifier-free guidance: the guided field is not the flow of a density the model defines")
@@ -488,45 +575,54 @@ def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", ge
             raise ValueError(f"t_end={t_end} must lie in [0, 1)")
         if unet and not latents.is_cuda:
             raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
-        eps = _make_probe(probe, latents.float() if unet else latents, generator)
+        eps, k = _make_probes(probe, latents.float() if unet else latents, generator, n_probes, probe_seed, sample_ids)
         cond, cls, mask, ones = _conditioning(model, cond)
         if unet:
             x = _start(latents, None, latents.device)
-            (nfev, _, _), _, logp = model.log_likelihood_rk45(x, eps, 1.0, t_end, rtol=rtol, atol=atol, per_sample=per_sample, class_ids=cls,
-                                                              mask=mask, mask_is_ones=ones)
-            return logp, x, (int(nfev.max()) if per_sample else nfev)
-        logp, z, _, nfe = _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end)
-        return logp, z, nfe
+            (nfev, _, _), a, logp, *extra = model.log_likelihood_rk45(x, eps, 1.0, t_end, rtol=rtol, atol=atol, per_sample=per_sample,
+                                                                      class_ids=cls, mask=mask, mask_is_ones=ones)
+            out = (logp, x, (int(nfev.max()) if per_sample else nfev))
+            if not return_info:
+                return out
+            return out + (_ll_info(a, *extra, k) if k else _ll_info(a, a[None].clone(), torch.full_like(a, float("nan")), 1),)
+        logp, z, a, nfe, a_probes = _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end, probes=True)
+        return (logp, z, nfe) + ((_ll_info(a, a_probes, _probe_stats(a_probes, a)[1], k or 1),) if return_info else ())
     ts = _reverse_grid(n_steps, torch.float32 if unet else latents.dtype)
     nfe = 4 * (len(ts) - 1)
     if unet and not latents.is_cuda:
         raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
-    eps = _make_probe(probe, latents.float() if unet else latents, generator)
+    eps, k = _make_probes(probe, latents.float() if unet else latents, generator, n_probes, probe_seed, sample_ids)
     cond, cls, mask, ones = _conditioning(model, cond)
     if unet:
         x = _start(latents, None, latents.device)
-        _, logp = model.log_likelihood(x, ts, eps, class_ids=cls, mask=mask, mask_is_ones=ones)
-        return logp, x, nfe
-    logp, z, _ = _log_likelihood_torch(model, latents, ts.to(latents.device), cond, eps)
-    return logp, z, nfe
+        a, logp, *extra = model.log_likelihood(x, ts, eps, class_ids=cls, mask=mask, mask_is_ones=ones)
+        if not return_info:
+            return logp, x, nfe
+        return logp, x, nfe, (_ll_info(a, *extra, k) if k else _ll_info(a, a[None].clone(), torch.full_like(a, float("nan")), 1))
+    logp, z, a, a_probes = _log_likelihood_torch(model, latents, ts.to(latents.device), cond, eps, probes=True)
+    return (logp, z, nfe) + ((_ll_info(a, a_probes, _probe_stats(a_probes)[1], k or 1),) if return_info else ())
 
 
-def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999):
-    """The loop of ``log_likelihood`` with torch ops: ``torch.autograd.grad(v, x, eps)`` per stage.  Returns (logp, z, a)."""
+def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999, probes=False):
+    """The loop of ``log_likelihood`` with torch ops: one forward per stage and ``torch.autograd.grad(v, x, eps_k)`` per probe (``eps`` of
+    the latents' shape, or ``[K, ...]``: the graph is retained for all but the last).  Every probe carries its own accumulator; ``a`` is
+    their mean in probe order (one probe: its accumulator).  Returns (logp, z, a), with ``probes`` (logp, z, a, a_probes [K, B])."""
     import math
     bsz = latents.shape[0]
-    e64 = eps.double()
+    eps_k = eps if eps.dim() == latents.dim() + 1 else eps[None]
+    n_k = eps_k.shape[0]
+    e64 = eps_k.double()
 
     def stage(x, t):
         with torch.enable_grad():
             xr = x.detach().requires_grad_(True)
             t_vec = torch.full((bsz,), float(t), device=x.device, dtype=x.dtype)
             v = model(xr, t_vec * t_scale, cond=cond)
-            g, = torch.autograd.grad(v, xr, eps)
-        return v.detach(), (e64 * g.double()).flatten(1).sum(dim=1)
+            gs = [torch.autograd.grad(v, xr, eps_k[k], retain_graph=k + 1 < n_k)[0] for k in range(n_k)]
+        return v.detach(), torch.stack([(e64[k] * gs[k].double()).flatten(1).sum(dim=1) for k in range(n_k)])
 
     x = latents.detach()
-    a = torch.zeros(bsz, dtype=torch.float64, device=x.device)
+    a = torch.zeros(n_k, bsz, dtype=torch.float64, device=x.device)
     for i in range(len(ts) - 1):
         t, dt = ts[i], ts[i + 1] - ts[i]
         tpdto2 = t + dt / 2
@@ -538,44 +634,74 @@ def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999):
         a = a + (dt.double() / 6) * (d1 + 2 * d2 + 2 * d3 + d4)
     z = x
     D = z[0].numel()
+    a_probes = a
+    a = _probe_stats(a_probes)[0] if n_k > 1 else a_probes[0]
     logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
-    return logp, z, a
+    return (logp, z, a, a_probes) if probes else (logp, z, a)
 
 
-def _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end=0.0, t_scale=999):
+def _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end=0.0, t_scale=999, probes=False):
     """``log_likelihood(method="rk45")`` for any callable: ``solve_ivp(method="RK45")`` from 1 to ``t_end`` on the concatenated vector
-    ``[x, a]`` of every controller group (the batch, or each sample), ``torch.autograd.grad(v, x, eps)`` per evaluation.  Returns
-    (logp, z, a, nfe)."""
+    ``[x, a]`` of every controller group (the batch, or each sample), ``torch.autograd.grad(v, x, eps_k)`` per evaluation and probe
+    (``eps`` of the latents' shape, or ``[K, ...]``); ``da/dt`` is the probes' mean, summed in probe order with one division.
+
+    ``solve_ivp`` is ``RK45(...)`` stepped until it finishes; the solver object is driven directly here -- same steps, same bits -- so
+    that the per-probe integrals can be recovered: after a successful ``step()`` the accepted attempt is the six evaluations made last
+    plus the first-same-as-last one carried over, and ``a_k += h sum_s B_s d_{s,k}`` over them.  Returns (logp, z, a, nfe), with
+    ``probes`` (logp, z, a, nfe, a_probes [K, B])."""
     import math
     import numpy as np
-    from scipy import integrate
+    from scipy.integrate import RK45
+    eps_k = eps if eps.dim() == latents.dim() + 1 else eps[None]
+    n_k = eps_k.shape[0]
     z, a = latents.detach().clone(), torch.zeros(latents.shape[0], dtype=torch.float64, device=latents.device)
+    a_probes = torch.zeros(n_k, latents.shape[0], dtype=torch.float64, device=latents.device)
     nfevs, failed = [], []
     for rows, cond_g in _host_rk45_groups(latents, cond, per_sample):
-        xg, eg = latents[rows].detach(), eps[rows]
-        shape, n, e64 = tuple(xg.shape), xg.numel(), eps[rows].double()
+        xg, eg = latents[rows].detach(), eps_k[:, rows]
+        shape, n, e64 = tuple(xg.shape), xg.numel(), eps_k[:, rows].double()
+        evals = []                                        # d_{.,k} of every evaluation, in the order made: [K, rows] each
 
         def ode_func(t, y):
             with torch.enable_grad():
                 xr = torch.from_numpy(np.ascontiguousarray(y[:n]).reshape(shape)).to(device=xg.device, dtype=xg.dtype).requires_grad_(True)
                 t_vec = torch.full((shape[0],), float(t), device=xg.device, dtype=xg.dtype)
                 v = model(xr, t_vec * t_scale, cond=cond_g)
-                g, = torch.autograd.grad(v, xr, eg)
-            d = (e64 * g.double()).flatten(1).sum(dim=1)
+                gs = [torch.autograd.grad(v, xr, eg[k], retain_graph=k + 1 < n_k)[0] for k in range(n_k)]
+            dk = torch.stack([(e64[k] * gs[k].double()).flatten(1).sum(dim=1) for k in range(n_k)])
+            evals.append(dk.cpu().numpy())
+            d = dk[0]
+            if n_k > 1:
+                for k in range(1, n_k):
+                    d = d + dk[k]
+                d = d / n_k
             return np.concatenate([v.detach().double().cpu().numpy().reshape(-1), d.cpu().numpy()])
 
         y0 = np.concatenate([xg.double().cpu().numpy().reshape(-1), np.zeros(shape[0])])
-        sol = integrate.solve_ivp(ode_func, (1.0, t_end), y0, rtol=rtol, atol=atol, method="RK45")
-        if not sol.success:
-            failed.append(f"sample {rows.start}: {sol.message}" if per_sample else str(sol.message))
+        solver = RK45(ode_func, 1.0, y0, t_end, rtol=rtol, atol=atol)      # f(t0, y0) and select_initial_step's second evaluation
+        carried, ak, message = evals[0], np.zeros((n_k, shape[0])), None
+        while solver.status == "running":
+            message = solver.step()
+            if solver.status == "failed":
+                break
+            ks = [carried] + evals[-6:-1]                 # K0..K5 of the accepted attempt; evals[-1] is f(t + h, y_new), the next K0
+            acc = ks[0] * solver.B[0]
+            for s_ in range(1, 6):
+                acc = acc + ks[s_] * solver.B[s_]
+            ak = ak + (solver.t - solver.t_old) * acc
+            carried = evals[-1]
+            del evals[:-1]
+        if solver.status == "failed":
+            failed.append(f"sample {rows.start}: {message}" if per_sample else str(message))
             continue
-        z[rows] = torch.from_numpy(sol.y[:n, -1].reshape(shape).copy()).to(device=xg.device, dtype=xg.dtype)
-        a[rows] = torch.from_numpy(sol.y[n:, -1].copy()).to(a.device)
-        nfevs.append(int(sol.nfev))
+        z[rows] = torch.from_numpy(solver.y[:n].reshape(shape).copy()).to(device=xg.device, dtype=xg.dtype)
+        a[rows] = torch.from_numpy(solver.y[n:].copy()).to(a.device)
+        a_probes[:, rows] = torch.from_numpy(ak).to(a.device)
+        nfevs.append(int(solver.nfev))
     _raise_failed("log_likelihood", failed, latents.shape[0])
     D = z[0].numel()
     logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
-    return logp, z, a, max(nfevs)
+    return (logp, z, a, max(nfevs), a_probes) if probes else (logp, z, a, max(nfevs))
 
 
 def _solve_ivp_rk45(ode_func, eps, y0, rtol, atol, t_eval):

@@ -489,6 +489,20 @@ class Unet(NativeModule):
         self._integrator_check(hnd, dev, check)
         return x
 
+    @staticmethod
+    def _probes_arg(x: torch.Tensor, probe: torch.Tensor):
+        """A likelihood call's probe argument: x's shape (one probe: today's call) or ``[K, *x.shape]`` (K probes in one solve).  Returns
+        (probe, K or None), the probe 16-byte aligned."""
+        several = probe.dim() == x.dim() + 1
+        if (probe.shape[1:] if several else probe.shape) != x.shape or probe.device != x.device or probe.dtype != torch.float32 \
+                or not probe.is_contiguous():
+            raise ValueError("probe must be a contiguous fp32 tensor of x's shape, or [K, *x.shape] for K probes, on x's device")
+        if several and not 1 <= probe.shape[0] <= B.FC_LL_MAX_PROBES:
+            raise ValueError(f"n_probes={probe.shape[0]} must lie in [1, {B.FC_LL_MAX_PROBES}] (the cap on probes per call)")
+        if probe.data_ptr() % 16:
+            probe = probe.clone()                       # a view at an odd storage offset: the kernels read the probe as float4
+        return probe, (int(probe.shape[0]) if several else None)
+
     def log_likelihood(self, x: torch.Tensor, ts: torch.Tensor, probe: torch.Tensor, *, t_scale: float = 999.0,
                        class_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, mask_is_ones: bool = False,
                        check: bool = True, restore_plan: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -500,21 +514,31 @@ class Unet(NativeModule):
         The loop needs the backward plan, hence the training form of the plans (``_training_form``).  A model that was NOT in that form
         gets its inference form back before the call returns (``restore_plan``, default): later sampler calls run the plan, and give the
         bits, of a model that never computed a likelihood, at the cost of a device synchronisation and two plan builds per call.  For many
-        likelihood calls in a row pass ``restore_plan=False`` and call ``release_training_plan()`` once at the end."""
+        likelihood calls in a row pass ``restore_plan=False`` and call ``release_training_plan()`` once at the end.
+
+        ``probe`` of shape ``[K, *x.shape]`` (``fc_unet_log_likelihood_probes``, 1 <= K <= 64): K probes in one solve -- one forward per
+        evaluation and K data-gradient chains behind it.  Returns ``(a, logp, a_probes, logp_stderr)``: ``a_probes`` fp64 ``[K, B]``, row k
+        with the bits of a single-probe call with probe k; ``a`` their mean (summed in probe order, one division), ``logp`` formed from
+        it; ``logp_stderr`` fp64 ``[B]`` = ``sqrt(sum_k (a_k - a)^2 / (K (K - 1)))``, NaN for K = 1."""
         class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask, cpu_error=_GPU_ONLY + "; there is no CPU path")
         dev = x.device
         bsz, _, h, w = x.shape
-        if probe.shape != x.shape or probe.device != dev or probe.dtype != torch.float32 or not probe.is_contiguous():
-            raise ValueError("probe must be a contiguous fp32 tensor of x's shape on x's device")
-        if probe.data_ptr() % 16:
-            probe = probe.clone()                       # a view at an odd storage offset: the kernels read the probe as float4
+        probe, k = self._probes_arg(x, probe)
         _, ts_ptr, n_points = self._host_grid(ts, 2)
         a, logp = (torch.empty(bsz, dtype=torch.float64, device=dev) for _ in range(2))
+        if k is not None:
+            a_probes, stderr = torch.empty(k, bsz, dtype=torch.float64, device=dev), torch.empty(bsz, dtype=torch.float64, device=dev)
         with self._training_form(hnd, bsz, h, w, restore_plan):
-            B.check(B.lib().fc_unet_log_likelihood(hnd, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids), B.ptr(mask),
-                                                   int(mask_is_ones), B.ptr(probe), B.ptr(a), B.ptr(logp), B.current_stream(dev)))
+            if k is None:
+                B.check(B.lib().fc_unet_log_likelihood(hnd, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids),
+                                                       B.ptr(mask), int(mask_is_ones), B.ptr(probe), B.ptr(a), B.ptr(logp),
+                                                       B.current_stream(dev)))
+            else:
+                B.check(B.lib().fc_unet_log_likelihood_probes(hnd, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids),
+                                                              B.ptr(mask), int(mask_is_ones), B.ptr(probe), k, B.ptr(a), B.ptr(logp),
+                                                              B.ptr(a_probes), B.ptr(stderr), B.current_stream(dev)))
             self._integrator_check(hnd, dev, check)
-        return a, logp
+        return (a, logp) if k is None else (a, logp, a_probes, stderr)
 
     def log_likelihood_rk45(self, x: torch.Tensor, eps: torch.Tensor, t0: float = 1.0, t1: float = 0.0, rtol: float = 1e-5,
                             atol: float = 1e-5, per_sample: bool = True, *, t_scale: float = 999.0, class_ids: Optional[torch.Tensor] = None,
@@ -527,7 +551,13 @@ class Unet(NativeModule):
         code.  Returns ``(counters, a, logp)``: ``counters = (nfev, accepted, rejected)`` as ``integrate_rk45`` returns them (ints, or int64
         CPU tensors ``[B]`` per sample); ``a`` and ``logp = -|z|^2/2 - (CHW/2) ln 2pi + a`` fp64 ``[B]`` on x's device, ``z`` = the ``x`` left
         behind.  Synchronous.  A failed solve raises RuntimeError with scipy's message (per sample naming the samples) and leaves ``x``
-        untouched.  The form of the plans is handled as in ``log_likelihood`` (``restore_plan``)."""
+        untouched.  The form of the plans is handled as in ``log_likelihood`` (``restore_plan``).
+
+        ``eps`` of shape ``[K, *x.shape]`` (``fc_unet_log_likelihood_rk45_probes``): the state stays ``[x, a]`` with ``da/dt`` the MEAN of
+        the K probes' estimates (summed in probe order, one division), so K copies of one probe give the single-probe solve bit for bit;
+        every evaluation is one forward and K chains.  Returns ``(counters, a, logp, a_probes, logp_stderr)``: ``a_probes`` fp64 ``[K, B]``,
+        every probe's own integral over the accepted steps (by-products outside the error norm; their mean equals ``a`` up to fp64
+        rounding), ``logp_stderr`` as in ``log_likelihood`` around ``a``."""
         rtol, atol = validate_tol(rtol, atol)
         t0, t1 = float(t0), float(t1)
         if not (0.0 <= t1 < t0 <= 1.0):
@@ -535,22 +565,28 @@ class Unet(NativeModule):
         class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask, cpu_error=_GPU_ONLY + "; there is no CPU path")
         dev = x.device
         bsz, _, h, w = x.shape
-        if eps.shape != x.shape or eps.device != dev or eps.dtype != torch.float32 or not eps.is_contiguous():
-            raise ValueError("probe must be a contiguous fp32 tensor of x's shape on x's device")
-        if eps.data_ptr() % 16:
-            eps = eps.clone()                           # a view at an odd storage offset: the kernels read the probe as float4
+        eps, k = self._probes_arg(x, eps)
         self._check_aligned(x)
         a, logp = (torch.empty(bsz, dtype=torch.float64, device=dev) for _ in range(2))
+        extra = ()
+        if k is not None:
+            extra = (torch.empty(k, bsz, dtype=torch.float64, device=dev), torch.empty(bsz, dtype=torch.float64, device=dev))
         counters = (C.c_int * (3 * bsz if per_sample else 3))()
         with self._training_form(hnd, bsz, h, w, restore_plan):
-            B.check(B.lib().fc_unet_log_likelihood_rk45(hnd, B.ptr(x), bsz, h, w, t0, t1, float(rtol), float(atol), float(t_scale),
-                                                        B.ptr(class_ids), B.ptr(mask), int(mask_is_ones), B.ptr(eps), int(per_sample), B.ptr(a),
-                                                        B.ptr(logp), counters, B.current_stream(dev)))
+            if k is None:
+                B.check(B.lib().fc_unet_log_likelihood_rk45(hnd, B.ptr(x), bsz, h, w, t0, t1, float(rtol), float(atol), float(t_scale),
+                                                            B.ptr(class_ids), B.ptr(mask), int(mask_is_ones), B.ptr(eps), int(per_sample),
+                                                            B.ptr(a), B.ptr(logp), counters, B.current_stream(dev)))
+            else:
+                B.check(B.lib().fc_unet_log_likelihood_rk45_probes(hnd, B.ptr(x), bsz, h, w, t0, t1, float(rtol), float(atol), float(t_scale),
+                                                                   B.ptr(class_ids), B.ptr(mask), int(mask_is_ones), B.ptr(eps), k,
+                                                                   int(per_sample), B.ptr(a), B.ptr(logp), B.ptr(extra[0]), B.ptr(extra[1]),
+                                                                   counters, B.current_stream(dev)))
             self._integrator_check(hnd, dev, check)
         if per_sample:
             c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
-            return (c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone()), a, logp
-        return (int(counters[0]), int(counters[1]), int(counters[2])), a, logp
+            return ((c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone()), a, logp) + extra
+        return ((int(counters[0]), int(counters[1]), int(counters[2])), a, logp) + extra
 
     def integrate_guided(self, x: torch.Tensor, ts: torch.Tensor, measurement: torch.Tensor, keep: torch.Tensor, *, sigma_y: float = 0.05,
                          gamma: float = 1.0, jacobian: str = "identity", t_scale: float = 999.0, class_ids: Optional[torch.Tensor] = None,

@@ -233,6 +233,42 @@ int fc_unet_log_likelihood_rk45(fc_unet* u, float* x_inout_dev, int batch, int h
                                 const float* probe_dev, int per_sample, double* a_out_dev, double* logp_out_dev, int* counters,
                                 void* stream);
 
+/* Both likelihoods with K = n_probes Hutchinson probes in one solve.  probes_dev [K][B][C*H*W] fp32, 16-byte aligned;
+ * 1 <= K <= FC_LL_MAX_PROBES (else FC_E_ARG, the message names the cap): the library's input-gradient buffer grows to K * maxB * C*H*W
+ * floats on first use and is released with the plan.  The trajectory does not depend on the probe, so every evaluation is ONE
+ * training-form forward followed by K data-gradient chains, probe k as the cotangent of chain k, and
+ *     d_{s,k}[b] = sum_i probe_k[b,i] ((dv/dx)^T probe_k)[b,i]             the single-probe reduction, per probe
+ * RK4 grid: every probe has its own accumulator, a_k <- a_k + (double(dt)/6)(((d1 + 2 d2) + 2 d3) + d4) on its own d's, so
+ * a_probes_out_dev[k] has the bits of fc_unet_log_likelihood's a_out_dev with probe k; a_out_dev = (a_1 + ... + a_K) / K summed in probe
+ * order with one division.  RK45: the augmented state stays [x, a] with da/dt = (d_{s,1} + ... + d_{s,K}) / K (same order, one
+ * division), which is what every norm reads, n = m + rows as before; a_out_dev is that a.  The per-probe integrals are by-products
+ * outside the norm: the controller thread that commits an accepted step also sets a_k <- a_k + h sum_s B_s d_{s,k}, formed as a_new is.
+ * Both: logp_out_dev from a_out_dev as before; a_probes_out_dev [K][B] fp64; stderr_out_dev [B] fp64 =
+ * sqrt(sum_k (a_k - a)^2 / (K (K - 1))), NaN for K = 1.  K = 1 runs the arithmetic of the single-probe entry points, which are this
+ * routine with K = 1 and no per-probe outputs.  Everything else (arguments, alignment, asynchrony / synchrony, counters, failure: nothing
+ * written) as the entry point each extends. */
+#define FC_LL_MAX_PROBES 64
+int fc_unet_log_likelihood_probes(fc_unet* u, float* x_inout_dev, int batch, int height, int width, const float* ts_host, int n_points,
+                                  float t_scale, const int64_t* class_ids_dev, const float* mask_dev, int mask_is_ones,
+                                  const float* probes_dev, int n_probes, double* a_out_dev, double* logp_out_dev,
+                                  double* a_probes_out_dev, double* stderr_out_dev, void* stream);
+int fc_unet_log_likelihood_rk45_probes(fc_unet* u, float* x_inout_dev, int batch, int height, int width, double t0, double t1, double rtol,
+                                       double atol, float t_scale, const int64_t* class_ids_dev, const float* mask_dev, int mask_is_ones,
+                                       const float* probes_dev, int n_probes, int per_sample, double* a_out_dev, double* logp_out_dev,
+                                       double* a_probes_out_dev, double* stderr_out_dev, int* counters, void* stream);
+/* The likelihood's counter-based probe field: out_dev [batch, per_sample] (fp32, 16-byte aligned, per_sample a multiple of 4) for probe
+ * index probe_index (a 32-bit counter word) and the given sample ids (NULL: 0 .. batch-1).  Philox4x32-10 with key = seed +
+ * FC_PROBE_KEY_OFFSET (mod 2^64; so a likelihood seed does not replay fc_unet_integrate_sde's noise of the same seed) and counter
+ * (float4 group inside the sample, probe_index, sample id): a value depends on (seed, probe index, sample id, position) and on nothing
+ * else.  FC_PROBE_RADEMACHER: +1 where the top bit of the element's Philox word is clear, -1 where it is set.  FC_PROBE_GAUSSIAN:
+ * fc_ode_normal_field's uniforms and Box-Muller transform under that key, evaluated in fp64 and rounded once to fp32 (a probe field is
+ * drawn once per call, so it can afford the host form's arithmetic and have its bits), |value| <= sqrt(48 ln 2) = 5.77. */
+#define FC_PROBE_RADEMACHER 0
+#define FC_PROBE_GAUSSIAN 1
+#define FC_PROBE_KEY_OFFSET 0x50524F4245464C44ULL /* "PROBEFLD" */
+int fc_ode_probe_field(float* out_dev, int kind, uint64_t seed, int64_t probe_index, const int64_t* sample_ids_dev, int batch,
+                       int64_t per_sample, void* stream);
+
 /* Measurement-guided RK4 sampling: the training-free inverse-problem method of the reference (flocoder/inpainting.py:92-130 algorithm3)
  * for a diagonal measurement operator on the conditional-OT path.  fc_unet_integrate(FC_METHOD_RK4) along ts_host (n_points >= 2, every
  * point > 0) in which every stage velocity v -- after classifier-free guidance -- produced at stage state x and stage time t becomes
