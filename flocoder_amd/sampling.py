@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from .unet import Unet, validate_t_eval, validate_tol
+from .unet import Unet, is_ones_mask, require_gpu, validate_t_eval, validate_tol
 
 
 def warp_time(t, dt=None, s=.5):
@@ -69,18 +69,21 @@ def v_func_cfg(model, cond, cfg_strength, t_vec_template, x, t, t_scale=999, deb
 
 def _mask_flags(cond):
     mask = cond.get('mask_cond') if isinstance(cond, dict) else None
-    ones = bool(torch.allclose(mask, torch.ones_like(mask))) if mask is not None else False   # once per call
-    return mask, ones
+    return mask, is_ones_mask(mask)                   # once per call
 
 
-def _conditioning(model, cond):
-    """``cond`` as the samplers take it (a cond dict, a class-id tensor as the legacy samplers, or None) -> ``(cond dict, class ids,
-    mask, mask_is_ones)``.  The last three are what the integrators of a ``flocoder_amd.Unet`` take and are made for one only: the mask
-    test is a host sync, so call this where the native path is taken."""
+def _conditioning(model, cond, x=None, no_cpu_path=True):
+    """The native / host fork of every entry.  ``cond`` as the samplers take it (a cond dict, a class-id tensor as the legacy samplers,
+    or None) -> ``(cond dict, class ids, mask, mask_is_ones)``.  The last three are what the integrators of a ``flocoder_amd.Unet`` take
+    and are made for one only: the mask test is a host sync, so call this once per public call, where the native path is taken.  With
+    ``x``, the tensor the native path would integrate, a ``flocoder_amd.Unet`` on the CPU raises here (``no_cpu_path``: which of the two
+    wordings the entry has always used)."""
     if cond is not None and not isinstance(cond, dict):
         cond = {'class_cond': cond}
     if not isinstance(model, Unet):
         return cond, None, None, False
+    if x is not None:
+        require_gpu(x, no_cpu_path)
     return (cond, cond.get('class_cond') if cond else None) + _mask_flags(cond)
 
 
@@ -88,6 +91,31 @@ def _start(source, shape, device):
     """The fp32 contiguous tensor an integrator updates in place: a copy of ``source`` on ``device``, or noise of ``shape``."""
     x = source if source is not None else torch.randn(shape, device=device)
     return x.to(device=device, dtype=torch.float32).contiguous().clone()
+
+
+def _start_and_grid(model, shape, source, init_latents, init_strength, n_steps, fallback=None):
+    """Start and grid of the fixed-grid generators (sampling.py:95-111) -> ``(current_points, ts, effective n_steps, device, dtype)``:
+    ``source`` or randn on the device and in the dtype of the model's parameters; with ``init_latents`` the blend
+    ``(1 - s) source + s init_latents`` on ``rk4_time_grid(n_steps, s)`` and the reference's ``max(1, int(n_steps (1 - s)))`` bookkeeping.
+    ``fallback`` is the tensor whose device and dtype serve for a model without parameters; without one such a model raises."""
+    has_params = hasattr(model, "parameters") and any(True for _ in model.parameters())
+    p0 = next(model.parameters()) if has_params or fallback is None else fallback
+    device, dtype = p0.device, p0.dtype
+    current_points = source if source is not None else torch.randn(shape, device=device, dtype=dtype)
+    if init_latents is None:
+        return current_points, rk4_time_grid(n_steps, dtype=dtype), n_steps, device, dtype
+    current_points = (1 - init_strength) * current_points + init_strength * init_latents
+    return current_points, rk4_time_grid(n_steps, init_strength, dtype=dtype), max(1, int(n_steps * (1.0 - init_strength))), device, dtype
+
+
+def _velocity(model, cond, cfg_strength, bsz, device, dtype=None):
+    """``v(x, t)`` of a model that is not integrated in the library: ``v_func_cfg`` over a time vector of its own."""
+    return partial(v_func_cfg, model, cond, cfg_strength, torch.zeros(bsz, device=device, dtype=dtype))
+
+
+def _nfe(nfev, per_sample):
+    """``Unet.integrate_rk45``'s nfev -> the samplers' nfe: per sample the largest, the number of batch forwards made."""
+    return int(nfev.max()) if per_sample else nfev
 
 
 def _rk4_loop(v_func, x, ts, jitter_strength=None):
@@ -104,16 +132,9 @@ def _rk4_loop(v_func, x, ts, jitter_strength=None):
 def generate_latents_rk4(model, shape, n_steps=50, cond=None, cfg_strength=3.0, source=None, init_latents=None,
                          init_strength=0.0, jitter_strength=0, debug=False):
     """sampling.py:78-122.  Returns (latents, n_steps*4) -- the reference's nfe bookkeeping."""
-    p0 = next(model.parameters())
-    device, dtype = p0.device, p0.dtype
-    current_points = source if source is not None else torch.randn(shape, device=device, dtype=dtype)
+    current_points, ts, n_steps, device, dtype = _start_and_grid(model, shape, source, init_latents, init_strength, n_steps)
     if init_latents is None:
-        ts = rk4_time_grid(n_steps, dtype=dtype)
         jitter_strength = 0
-    else:
-        current_points = (1 - init_strength) * current_points + init_strength * init_latents
-        ts = rk4_time_grid(n_steps, init_strength, dtype=dtype)
-        n_steps = max(1, int(n_steps * (1.0 - init_strength)))
 
     if isinstance(model, Unet) and not jitter_strength:
         x = _start(current_points, None, device)
@@ -122,10 +143,8 @@ def generate_latents_rk4(model, shape, n_steps=50, cond=None, cfg_strength=3.0, 
             model.integrate("rk4", x, ts, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask, mask_is_ones=ones)
         return x, n_steps * 4
 
-    ts = ts.to(device)
-    t_vec_template = torch.zeros(shape[0], device=device, dtype=dtype)
-    v_func = partial(v_func_cfg, model, cond, cfg_strength, t_vec_template)
-    return _rk4_loop(v_func, current_points, ts, jitter_strength), n_steps * 4
+    v_func = _velocity(model, cond, cfg_strength, shape[0], device, dtype)
+    return _rk4_loop(v_func, current_points, ts.to(device), jitter_strength), n_steps * 4
 
 
 @torch.no_grad()
@@ -164,18 +183,12 @@ def generate_latents_guided(model, shape, measurement, keep, n_steps=50, init_st
     if jacobian == "exact" and cfg_strength and cond and cond.get('class_cond') is not None:
         raise ValueError("jacobian='exact' takes no classifier-free guidance (pass cfg_strength=0): the exact term differentiates one "
                          "forward, not the guided pair")
-    p0 = next(model.parameters()) if hasattr(model, "parameters") else measurement
-    device, dtype = p0.device, p0.dtype
-    current_points = source if source is not None else torch.randn(shape, device=device, dtype=dtype)
-    if init_latents is None:
-        init_latents = measurement
-    current_points = (1 - init_strength) * current_points + init_strength * init_latents
-    ts = rk4_time_grid(n_steps, init_strength, dtype=dtype)
-    nfe = max(1, int(n_steps * (1.0 - init_strength))) * 4
+    current_points, ts, n_steps, device, dtype = _start_and_grid(model, shape, source, measurement if init_latents is None else init_latents,
+                                                                 init_strength, n_steps, fallback=measurement)
+    nfe = n_steps * 4
 
     if unet:
-        if not current_points.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+        require_gpu(current_points)                  # on its own here: the refusal above needs the cond dict before the start exists
         x = _start(current_points, None, device)
         if len(ts) > 1:
             model.integrate_guided(x, ts, measurement, keep, sigma_y=sigma_y, gamma=gamma, jacobian=jacobian, class_ids=cls,
@@ -184,12 +197,12 @@ def generate_latents_guided(model, shape, measurement, keep, n_steps=50, init_st
 
     ts = ts.to(device)
     y, a = measurement.to(device=device, dtype=dtype), keep.to(device=device, dtype=dtype)
-    t_vec_template = torch.zeros(shape[0], device=device, dtype=dtype)
+    v_cfg, t_vec_template = _velocity(model, cond, cfg_strength, shape[0], device, dtype), torch.zeros(shape[0], device=device, dtype=dtype)
 
     def v_func(x, t):
         om = 1 - t
         if jacobian == "identity":
-            v = v_func_cfg(model, cond, cfg_strength, t_vec_template, x, t)
+            v = v_cfg(x, t)
             g = guidance_weight(v, x, t, y, a, sigma_y)
         else:
             with torch.enable_grad():
@@ -204,46 +217,40 @@ def generate_latents_guided(model, shape, measurement, keep, n_steps=50, init_st
     return _rk4_loop(v_func, current_points, ts), nfe
 
 
-def normal_field(seed, draw_index, sample_ids, shape, device=None, dtype=torch.float32):
-    """The counter-based normal field of the stochastic samplers as a tensor ``[B, *shape[1:]]``: row b holds the normals of
-    ``(seed, draw_index, sample_ids[b])`` (``flocoder_amd.noise``).  On a GPU device the library generates it (``fc_ode_normal_field``, fp32
-    arithmetic); on the CPU ``noise.normal_field`` does (fp64 arithmetic, then rounded to ``dtype``)."""
+def _counter_field(host_field, native_field, seed, index, sample_ids, shape, device, dtype):
+    """A counter-based field of ``flocoder_amd.noise`` as a tensor ``[B, *shape[1:]]``, row b that of ``(seed, index, sample_ids[b])``:
+    ``native_field(lib, out, seed, index, ids, B, per-sample size, stream)`` on a GPU device, the NumPy ``host_field`` on the CPU."""
     from . import _binding as B
-    from . import noise as N
     device = torch.device("cpu" if device is None else device)
     bsz, per = int(shape[0]), 1
     for d in shape[1:]:
         per *= int(d)
     if device.type != "cuda":
         ids = sample_ids.detach().cpu().numpy() if torch.is_tensor(sample_ids) else sample_ids
-        return torch.from_numpy(N.normal_field(seed, draw_index, ids, per)).reshape(tuple(shape)).to(device=device, dtype=dtype)
+        return torch.from_numpy(host_field(seed, index, ids, per)).reshape(tuple(shape)).to(device=device, dtype=dtype)
     ids = torch.as_tensor(sample_ids, dtype=torch.int64).to(device).contiguous()
     out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-    B.check(B.lib().fc_ode_normal_field(B.ptr(out), int(seed) & 0xffffffffffffffff, int(draw_index), B.ptr(ids), bsz, per,
-                                        B.current_stream(device)))
+    B.check(native_field(B.lib(), B.ptr(out), int(seed) & 0xffffffffffffffff, int(index), B.ptr(ids), bsz, per, B.current_stream(device)))
     return out.to(dtype)
+
+
+def normal_field(seed, draw_index, sample_ids, shape, device=None, dtype=torch.float32):
+    """The counter-based normal field of the stochastic samplers as a tensor ``[B, *shape[1:]]``: row b holds the normals of
+    ``(seed, draw_index, sample_ids[b])`` (``flocoder_amd.noise``).  On a GPU device the library generates it (``fc_ode_normal_field``, fp32
+    arithmetic); on the CPU ``noise.normal_field`` does (fp64 arithmetic, then rounded to ``dtype``)."""
+    from . import noise as N
+    return _counter_field(N.normal_field, lambda lib, *args: lib.fc_ode_normal_field(*args), seed, draw_index, sample_ids, shape, device, dtype)
 
 
 def probe_field(seed, probe_index, sample_ids, shape, kind="rademacher", device=None, dtype=torch.float32):
     """The likelihood's counter-based probe field as a tensor ``[B, *shape[1:]]``: row b holds probe ``probe_index`` of
     ``(seed, sample_ids[b])`` (``flocoder_amd.noise.probe_field``): it depends on those and the position in the sample, never on the
     row or the batch size.  On a GPU device the library generates it (``fc_ode_probe_field``); on the CPU the NumPy form does."""
-    from . import _binding as B
     from . import noise as N
-    device = torch.device("cpu" if device is None else device)
-    bsz, per = int(shape[0]), 1
-    for d in shape[1:]:
-        per *= int(d)
     if kind not in N.PROBE_KINDS:
         raise ValueError(f"kind={kind!r}: 'rademacher' or 'gaussian'")
-    if device.type != "cuda":
-        ids = sample_ids.detach().cpu().numpy() if torch.is_tensor(sample_ids) else sample_ids
-        return torch.from_numpy(N.probe_field(seed, probe_index, ids, per, kind)).reshape(tuple(shape)).to(device=device, dtype=dtype)
-    ids = torch.as_tensor(sample_ids, dtype=torch.int64).to(device).contiguous()
-    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-    B.check(B.lib().fc_ode_probe_field(B.ptr(out), N.PROBE_KINDS[kind], int(seed) & 0xffffffffffffffff, int(probe_index), B.ptr(ids), bsz, per,
-                                       B.current_stream(device)))
-    return out.to(dtype)
+    return _counter_field(lambda *args: N.probe_field(*args, kind), lambda lib, out, *args: lib.fc_ode_probe_field(out, N.PROBE_KINDS[kind], *args),
+                          seed, probe_index, sample_ids, shape, device, dtype)
 
 
 _SDE_EVALS = {"euler_maruyama": 1, "heun": 2}
@@ -279,18 +286,8 @@ def generate_latents_sde(model, shape, n_steps=50, cond=None, cfg_strength=3.0, 
     sigma = float(sigma)
     if not sigma >= 0:
         raise ValueError("sigma must be >= 0")
-    unet = isinstance(model, Unet)
-    if hasattr(model, "parameters") and any(True for _ in model.parameters()):
-        p0 = next(model.parameters())
-    else:
-        p0 = source if source is not None else torch.zeros(())
-    device, dtype = p0.device, p0.dtype
-    current_points = source if source is not None else torch.randn(shape, device=device, dtype=dtype)
-    if init_latents is None:
-        ts = rk4_time_grid(n_steps, dtype=dtype)
-    else:
-        current_points = (1 - init_strength) * current_points + init_strength * init_latents
-        ts = rk4_time_grid(n_steps, init_strength, dtype=dtype)
+    current_points, ts, _, device, dtype = _start_and_grid(model, shape, source, init_latents, init_strength, n_steps,
+                                                           fallback=source if source is not None else torch.zeros(()))
     n_int = len(ts) - 1
     if n_int < 1:
         raise ValueError(f"n_steps={n_steps}, init_strength={init_strength}: the grid needs at least two points (one interval)")
@@ -303,22 +300,18 @@ def generate_latents_sde(model, shape, n_steps=50, cond=None, cfg_strength=3.0, 
     if noise is not None and tuple(noise.shape) != (n_int,) + tuple(shape):
         raise ValueError(f"noise must have shape {(n_int,) + tuple(shape)}, got {tuple(noise.shape)}")
 
-    if unet:
-        if not current_points.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+    cond, cls, mask, ones = _conditioning(model, cond, current_points)
+    if isinstance(model, Unet):
         x = _start(current_points, None, device)
-        _, cls, mask, ones = _conditioning(model, cond)
         model.integrate_sde(x, ts, sigma=sigma, method=method, seed=seed, sample_ids=sample_ids,
                             noise=None if noise is None else noise.to(device), class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
                             mask_is_ones=ones)
         return x, nfe
 
-    cond = _conditioning(model, cond)[0]
     x = current_points.to(device)
     ts = ts.to(device)
     ids = torch.arange(bsz, dtype=torch.int64) if sample_ids is None else sample_ids
-    t_vec_template = torch.zeros(bsz, device=device, dtype=dtype)
-    v_func = partial(v_func_cfg, model, cond, cfg_strength, t_vec_template)
+    v_func = _velocity(model, cond, cfg_strength, bsz, device, dtype)
     s2 = 0.5 * sigma * sigma
     drift = lambda xx, t: (1 + s2 * t) * v_func(xx, t) - s2 * xx
     for i in range(n_int):
@@ -375,45 +368,64 @@ def _host_rk45_groups(x, cond, per_sample):
             for b in range(x.shape[0])]
 
 
-def _raise_failed(who, failed, bsz):
+def _host_rk45(who, x, cond, per_sample, solve):
+    """The host-side adaptive solves of ``who`` for models that are not a ``flocoder_amd.Unet``: every controller group of ``x`` on its
+    own.  ``solve(rows, x[rows], cond of those rows)`` builds the group's state, integrates it and scatters the result into the caller's
+    outputs; it returns ``(nfev, None)``, or ``(None, the solver's message)`` where scipy would return ``success=False``.  Returns the
+    largest nfev; failed solves raise RuntimeError with the message, per sample naming the samples."""
+    nfevs, failed = [], []
+    for rows, cond_g in _host_rk45_groups(x, cond, per_sample):
+        nfev, message = solve(rows, x[rows], cond_g)
+        if message is None:
+            nfevs.append(int(nfev))
+        else:
+            failed.append(f"sample {rows.start}: {message}" if per_sample else str(message))
     if failed:
-        raise RuntimeError(f"{who}: {len(failed)} of {bsz} samples failed; " + " ".join(failed) if failed[0].startswith("sample")
-                           else f"{who}: {failed[0]}")
+        raise RuntimeError(f"{who}: {len(failed)} of {x.shape[0]} samples failed; " + " ".join(failed) if per_sample else f"{who}: {failed[0]}")
+    return max(nfevs)
 
 
-@torch.no_grad()
-def _invert_rk45(model, latents, cond, rtol, atol, per_sample):
-    """``invert_latents(method="rk45")``: the legacy adaptive solve from t = 1 to t = 0, no guidance."""
-    rtol, atol = validate_tol(rtol, atol)
-    if isinstance(model, Unet):
-        if not latents.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only")
-        x = _start(latents, None, latents.device)
-        _, cls, mask, ones = _conditioning(model, cond)
-        nfev, _, _ = model.integrate_rk45(x, 1.0, 0.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=0.0, mask=mask, mask_is_ones=ones,
-                                          per_sample=per_sample)
-        return x, (int(nfev.max()) if per_sample else nfev)
+def _solve_ivp_rk45(ode_func, span, y0, rtol, atol, t_eval=None):
+    """The legacy ``solve_ivp(method="RK45")`` call over ``span`` -> ``(solution, y at the end of the span)``.  With ``t_eval`` scipy
+    returns the requested times only (``solution.y`` are the frames), so the solver's own final state is taken from an event function
+    that never fires: solve_ivp hands it every accepted ``(t, y)`` and changes nothing else, the steps and the final state are those of
+    the call without ``t_eval``."""
     import numpy as np
     from scipy import integrate
-    cond = _conditioning(model, cond)[0]
-    out, nfevs, failed = latents.detach().clone(), [], []
-    for rows, cond_g in _host_rk45_groups(latents, cond, per_sample):
-        xg = latents[rows]
+    if t_eval is None:
+        solution = integrate.solve_ivp(ode_func, span, y0, rtol=rtol, atol=atol, method="RK45")
+        return solution, solution.y[:, -1]
+    last = [np.asarray(y0)]
+
+    def watch(t, y):
+        last[0] = np.array(y)
+        return 1.0
+
+    solution = integrate.solve_ivp(ode_func, span, y0, rtol=rtol, atol=atol, method="RK45", t_eval=t_eval, events=watch)
+    return solution, last[0]
+
+
+def _invert_rk45_host(model, latents, cond, rtol, atol, per_sample):
+    """``invert_latents(method="rk45")`` for any callable: the legacy adaptive solve from t = 1 to t = 0 in the latents' dtype, no
+    guidance."""
+    import numpy as np
+    out = latents.detach().clone()
+
+    def solve(rows, xg, cond_g):
         shape = tuple(xg.shape)
-        t_vec_template = torch.zeros(shape[0], device=xg.device, dtype=xg.dtype)
+        v_func = _velocity(model, cond_g, 0.0, shape[0], xg.device, xg.dtype)
 
         def ode_func(t, y):
             xt = torch.from_numpy(np.asarray(y).reshape(shape)).to(device=xg.device, dtype=xg.dtype)
-            return v_func_cfg(model, cond_g, 0.0, t_vec_template, xt, t).detach().double().cpu().numpy().reshape((-1,))
+            return v_func(xt, t).detach().double().cpu().numpy().reshape((-1,))
 
-        sol = integrate.solve_ivp(ode_func, (1.0, 0.0), xg.detach().double().cpu().numpy().reshape((-1,)), rtol=rtol, atol=atol, method="RK45")
+        sol, y_end = _solve_ivp_rk45(ode_func, (1.0, 0.0), xg.detach().double().cpu().numpy().reshape((-1,)), rtol, atol)
         if not sol.success:
-            failed.append(f"sample {rows.start}: {sol.message}" if per_sample else str(sol.message))
-            continue
-        out[rows] = torch.from_numpy(sol.y[:, -1].reshape(shape).copy()).to(device=xg.device, dtype=xg.dtype)
-        nfevs.append(int(sol.nfev))
-    _raise_failed("invert_latents", failed, latents.shape[0])
-    return out, max(nfevs)
+            return None, sol.message
+        out[rows] = torch.from_numpy(y_end.reshape(shape).copy()).to(device=xg.device, dtype=xg.dtype)
+        return sol.nfev, None
+
+    return out, _host_rk45("invert_latents", latents, cond, per_sample, solve)
 
 
 @torch.no_grad()
@@ -430,21 +442,24 @@ def invert_latents(model, latents, n_steps=50, cond=None, method="rk4", rtol=1e-
     ``nfev`` (per sample: the largest).  A ``flocoder_amd.Unet`` runs it in the library (``Unet.integrate_rk45``), any other callable
     through scipy on the host in the latents' dtype."""
     _check_ode_method(method)
-    if method == "rk45":
-        return _invert_rk45(model, latents, cond, rtol, atol, per_sample)
-    ts = _reverse_grid(n_steps, torch.float32 if isinstance(model, Unet) else latents.dtype)
-    nfe = 4 * (len(ts) - 1)
+    rk45 = method == "rk45"
+    if rk45:
+        rtol, atol = validate_tol(rtol, atol)
+    else:
+        ts = _reverse_grid(n_steps, torch.float32 if isinstance(model, Unet) else latents.dtype)
+        nfe = 4 * (len(ts) - 1)
+    cond, cls, mask, ones = _conditioning(model, cond, latents, no_cpu_path=False)
     if isinstance(model, Unet):
-        if not latents.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only")
         x = _start(latents, None, latents.device)
-        _, cls, mask, ones = _conditioning(model, cond)
-        model.integrate("rk4", x, ts, class_ids=cls, cfg_strength=0.0, mask=mask, mask_is_ones=ones)
-        return x, nfe
-    cond = _conditioning(model, cond)[0]
-    t_vec_template = torch.zeros(latents.shape[0], device=latents.device, dtype=latents.dtype)
-    v_func = partial(v_func_cfg, model, cond, 0.0, t_vec_template)
-    return _rk4_loop(v_func, latents, ts.to(latents.device)), nfe
+        if not rk45:
+            model.integrate("rk4", x, ts, class_ids=cls, cfg_strength=0.0, mask=mask, mask_is_ones=ones)
+            return x, nfe
+        nfev, _, _ = model.integrate_rk45(x, 1.0, 0.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=0.0, mask=mask, mask_is_ones=ones,
+                                          per_sample=per_sample)
+        return x, _nfe(nfev, per_sample)
+    if rk45:
+        return _invert_rk45_host(model, latents, cond, rtol, atol, per_sample)
+    return _rk4_loop(_velocity(model, cond, 0.0, latents.shape[0], latents.device, latents.dtype), latents, ts.to(latents.device)), nfe
 
 
 def _make_probe(probe, latents, generator):
@@ -497,10 +512,6 @@ def _make_probes(probe, latents, generator, n_probes, probe_seed, sample_ids):
     if torch.is_tensor(probe):
         raise ValueError(f"n_probes={n_probes} needs a [K, ...] probe tensor or a kind to draw from")
     return torch.stack([_make_probe(probe, latents, generator) for _ in range(n_probes)]).contiguous(), n_probes
-
-
-def _ll_info(a, a_probes, stderr, k):
-    return {"logp_stderr": stderr, "a": a, "a_probes": a_probes, "n_probes": k}
 
 
 def _probe_stats(a_probes, a=None):
@@ -567,62 +578,72 @@ def log_likelihood(model, latents, n_steps=50, cond=None, probe="rademacher", ge
     _check_ode_method(method)
     if cfg_strength:
         raise ValueError("log_likelihood takes no classifier-free guidance: the guided field is not the flow of a density the model defines")
-    unet = isinstance(model, Unet)
-    if method == "rk45":
+    unet, rk45 = isinstance(model, Unet), method == "rk45"
+    if rk45:
         rtol, atol = validate_tol(rtol, atol)
         t_end = float(t_end)
         if not 0.0 <= t_end < 1.0:
             raise ValueError(f"t_end={t_end} must lie in [0, 1)")
-        if unet and not latents.is_cuda:
-            raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
-        eps, k = _make_probes(probe, latents.float() if unet else latents, generator, n_probes, probe_seed, sample_ids)
-        cond, cls, mask, ones = _conditioning(model, cond)
-        if unet:
-            x = _start(latents, None, latents.device)
-            (nfev, _, _), a, logp, *extra = model.log_likelihood_rk45(x, eps, 1.0, t_end, rtol=rtol, atol=atol, per_sample=per_sample,
-                                                                      class_ids=cls, mask=mask, mask_is_ones=ones)
-            out = (logp, x, (int(nfev.max()) if per_sample else nfev))
-            if not return_info:
-                return out
-            return out + (_ll_info(a, *extra, k) if k else _ll_info(a, a[None].clone(), torch.full_like(a, float("nan")), 1),)
-        logp, z, a, nfe, a_probes = _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end, probes=True)
-        return (logp, z, nfe) + ((_ll_info(a, a_probes, _probe_stats(a_probes, a)[1], k or 1),) if return_info else ())
-    ts = _reverse_grid(n_steps, torch.float32 if unet else latents.dtype)
-    nfe = 4 * (len(ts) - 1)
-    if unet and not latents.is_cuda:
-        raise RuntimeError("flocoder_amd integrators run on MI355X (gfx950) only; there is no CPU path")
+    else:
+        ts = _reverse_grid(n_steps, torch.float32 if unet else latents.dtype)
+        nfe = 4 * (len(ts) - 1)
+    cond, cls, mask, ones = _conditioning(model, cond, latents)
     eps, k = _make_probes(probe, latents.float() if unet else latents, generator, n_probes, probe_seed, sample_ids)
-    cond, cls, mask, ones = _conditioning(model, cond)
+    a_probes = stderr = None                          # of the paths that do not compute them; the tail does, and only for return_info
     if unet:
-        x = _start(latents, None, latents.device)
-        a, logp, *extra = model.log_likelihood(x, ts, eps, class_ids=cls, mask=mask, mask_is_ones=ones)
-        if not return_info:
-            return logp, x, nfe
-        return logp, x, nfe, (_ll_info(a, *extra, k) if k else _ll_info(a, a[None].clone(), torch.full_like(a, float("nan")), 1))
-    logp, z, a, a_probes = _log_likelihood_torch(model, latents, ts.to(latents.device), cond, eps, probes=True)
-    return (logp, z, nfe) + ((_ll_info(a, a_probes, _probe_stats(a_probes)[1], k or 1),) if return_info else ())
+        z = _start(latents, None, latents.device)
+        if rk45:
+            (nfev, _, _), a, logp, *extra = model.log_likelihood_rk45(z, eps, 1.0, t_end, rtol=rtol, atol=atol, per_sample=per_sample,
+                                                                      class_ids=cls, mask=mask, mask_is_ones=ones)
+            nfe = _nfe(nfev, per_sample)
+        else:
+            a, logp, *extra = model.log_likelihood(z, ts, eps, class_ids=cls, mask=mask, mask_is_ones=ones)
+        if k:
+            a_probes, stderr = extra
+    elif rk45:
+        logp, z, a, nfe, a_probes = _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end)
+    else:
+        logp, z, a, a_probes = _log_likelihood_torch(model, latents, ts.to(latents.device), cond, eps)
+    if not return_info:
+        return logp, z, nfe
+    if a_probes is None:                              # the library's single-probe entries: the one probe's integral is ``a``
+        a_probes, stderr = a[None].clone(), torch.full_like(a, float("nan"))
+    elif stderr is None:                              # the host paths (on the RK4 grid ``a`` is the probes' mean itself)
+        stderr = _probe_stats(a_probes, a)[1]
+    return logp, z, nfe, {"logp_stderr": stderr, "a": a, "a_probes": a_probes, "n_probes": k or 1}
 
 
-def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999, probes=False):
-    """The loop of ``log_likelihood`` with torch ops: one forward per stage and ``torch.autograd.grad(v, x, eps_k)`` per probe (``eps`` of
-    the latents' shape, or ``[K, ...]``: the graph is retained for all but the last).  Every probe carries its own accumulator; ``a`` is
-    their mean in probe order (one probe: its accumulator).  Returns (logp, z, a), with ``probes`` (logp, z, a, a_probes [K, B])."""
-    import math
-    bsz = latents.shape[0]
-    eps_k = eps if eps.dim() == latents.dim() + 1 else eps[None]
+def _hutchinson(model, x, t, cond, eps_k, e64, t_scale):
+    """One evaluation of the host likelihoods: ``v = model(x, t_scale t, cond)`` and ``torch.autograd.grad(v, x, eps_k)`` per probe (the
+    graph is retained for all but the last) -> ``(v, d)``, ``d[k, b] = sum_i eps_k[b,i] ((dv/dx)^T eps_k)[b,i]`` in fp64 (``e64``: the
+    probes as fp64)."""
     n_k = eps_k.shape[0]
-    e64 = eps_k.double()
+    with torch.enable_grad():
+        xr = x.detach().requires_grad_(True)
+        t_vec = torch.full((x.shape[0],), float(t), device=x.device, dtype=x.dtype)
+        v = model(xr, t_vec * t_scale, cond=cond)
+        gs = [torch.autograd.grad(v, xr, eps_k[k], retain_graph=k + 1 < n_k)[0] for k in range(n_k)]
+    return v.detach(), torch.stack([(e64[k] * gs[k].double()).flatten(1).sum(dim=1) for k in range(n_k)])
+
+
+def _logp(z, a):
+    """``-|z_b|^2 / 2 - (D/2) ln 2pi + a[b]`` in fp64"""
+    import math
+    return -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * z[0].numel() * math.log(2 * math.pi) + a
+
+
+def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999):
+    """The loop of ``log_likelihood`` with torch ops: one forward per stage and one VJP per probe (``_hutchinson``; ``eps`` of the
+    latents' shape, or ``[K, ...]``).  Every probe carries its own accumulator; ``a`` is their mean in probe order (one probe: its
+    accumulator).  Returns (logp, z, a, a_probes [K, B])."""
+    eps_k = eps if eps.dim() == latents.dim() + 1 else eps[None]
+    n_k, e64 = eps_k.shape[0], eps_k.double()
 
     def stage(x, t):
-        with torch.enable_grad():
-            xr = x.detach().requires_grad_(True)
-            t_vec = torch.full((bsz,), float(t), device=x.device, dtype=x.dtype)
-            v = model(xr, t_vec * t_scale, cond=cond)
-            gs = [torch.autograd.grad(v, xr, eps_k[k], retain_graph=k + 1 < n_k)[0] for k in range(n_k)]
-        return v.detach(), torch.stack([(e64[k] * gs[k].double()).flatten(1).sum(dim=1) for k in range(n_k)])
+        return _hutchinson(model, x, t, cond, eps_k, e64, t_scale)
 
     x = latents.detach()
-    a = torch.zeros(n_k, bsz, dtype=torch.float64, device=x.device)
+    a_probes = torch.zeros(n_k, latents.shape[0], dtype=torch.float64, device=x.device)
     for i in range(len(ts) - 1):
         t, dt = ts[i], ts[i + 1] - ts[i]
         tpdto2 = t + dt / 2
@@ -631,59 +652,50 @@ def _log_likelihood_torch(model, latents, ts, cond, eps, t_scale=999, probes=Fal
         k3, d3 = stage(x + dt * k2 / 2, tpdto2)
         k4, d4 = stage(x + dt * k3, t + dt)
         x = x + (dt / 6) * (k1 + 2 * k2 + 2 * k3 + k4)
-        a = a + (dt.double() / 6) * (d1 + 2 * d2 + 2 * d3 + d4)
-    z = x
-    D = z[0].numel()
-    a_probes = a
+        a_probes = a_probes + (dt.double() / 6) * (d1 + 2 * d2 + 2 * d3 + d4)
     a = _probe_stats(a_probes)[0] if n_k > 1 else a_probes[0]
-    logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
-    return (logp, z, a, a_probes) if probes else (logp, z, a)
+    return _logp(x, a), x, a, a_probes
 
 
-def _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end=0.0, t_scale=999, probes=False):
+def _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample, t_end=0.0, t_scale=999):
     """``log_likelihood(method="rk45")`` for any callable: ``solve_ivp(method="RK45")`` from 1 to ``t_end`` on the concatenated vector
-    ``[x, a]`` of every controller group (the batch, or each sample), ``torch.autograd.grad(v, x, eps_k)`` per evaluation and probe
-    (``eps`` of the latents' shape, or ``[K, ...]``); ``da/dt`` is the probes' mean, summed in probe order with one division.
+    ``[x, a]`` of every controller group (the batch, or each sample), one forward and one VJP per probe and evaluation (``_hutchinson``;
+    ``eps`` of the latents' shape, or ``[K, ...]``); ``da/dt`` is the probes' mean, summed in probe order with one division.
 
     ``solve_ivp`` is ``RK45(...)`` stepped until it finishes; the solver object is driven directly here -- same steps, same bits -- so
     that the per-probe integrals can be recovered: after a successful ``step()`` the accepted attempt is the six evaluations made last
-    plus the first-same-as-last one carried over, and ``a_k += h sum_s B_s d_{s,k}`` over them.  Returns (logp, z, a, nfe), with
-    ``probes`` (logp, z, a, nfe, a_probes [K, B])."""
-    import math
+    plus the first-same-as-last one carried over, and ``a_k += h sum_s B_s d_{s,k}`` over them.  Returns (logp, z, a, nfe,
+    a_probes [K, B])."""
     import numpy as np
     from scipy.integrate import RK45
     eps_k = eps if eps.dim() == latents.dim() + 1 else eps[None]
     n_k = eps_k.shape[0]
     z, a = latents.detach().clone(), torch.zeros(latents.shape[0], dtype=torch.float64, device=latents.device)
     a_probes = torch.zeros(n_k, latents.shape[0], dtype=torch.float64, device=latents.device)
-    nfevs, failed = [], []
-    for rows, cond_g in _host_rk45_groups(latents, cond, per_sample):
-        xg, eg = latents[rows].detach(), eps_k[:, rows]
-        shape, n, e64 = tuple(xg.shape), xg.numel(), eps_k[:, rows].double()
+
+    def solve(rows, xg, cond_g):
+        eg, e64 = eps_k[:, rows], eps_k[:, rows].double()
+        shape, n = tuple(xg.shape), xg.numel()
         evals = []                                        # d_{.,k} of every evaluation, in the order made: [K, rows] each
 
         def ode_func(t, y):
-            with torch.enable_grad():
-                xr = torch.from_numpy(np.ascontiguousarray(y[:n]).reshape(shape)).to(device=xg.device, dtype=xg.dtype).requires_grad_(True)
-                t_vec = torch.full((shape[0],), float(t), device=xg.device, dtype=xg.dtype)
-                v = model(xr, t_vec * t_scale, cond=cond_g)
-                gs = [torch.autograd.grad(v, xr, eg[k], retain_graph=k + 1 < n_k)[0] for k in range(n_k)]
-            dk = torch.stack([(e64[k] * gs[k].double()).flatten(1).sum(dim=1) for k in range(n_k)])
+            xt = torch.from_numpy(np.ascontiguousarray(y[:n]).reshape(shape)).to(device=xg.device, dtype=xg.dtype)
+            v, dk = _hutchinson(model, xt, t, cond_g, eg, e64, t_scale)
             evals.append(dk.cpu().numpy())
             d = dk[0]
             if n_k > 1:
                 for k in range(1, n_k):
                     d = d + dk[k]
                 d = d / n_k
-            return np.concatenate([v.detach().double().cpu().numpy().reshape(-1), d.cpu().numpy()])
+            return np.concatenate([v.double().cpu().numpy().reshape(-1), d.cpu().numpy()])
 
-        y0 = np.concatenate([xg.double().cpu().numpy().reshape(-1), np.zeros(shape[0])])
+        y0 = np.concatenate([xg.detach().double().cpu().numpy().reshape(-1), np.zeros(shape[0])])
         solver = RK45(ode_func, 1.0, y0, t_end, rtol=rtol, atol=atol)      # f(t0, y0) and select_initial_step's second evaluation
         carried, ak, message = evals[0], np.zeros((n_k, shape[0])), None
         while solver.status == "running":
             message = solver.step()
             if solver.status == "failed":
-                break
+                return None, message
             ks = [carried] + evals[-6:-1]                 # K0..K5 of the accepted attempt; evals[-1] is f(t + h, y_new), the next K0
             acc = ks[0] * solver.B[0]
             for s_ in range(1, 6):
@@ -691,36 +703,13 @@ def _log_likelihood_rk45_host(model, latents, cond, eps, rtol, atol, per_sample,
             ak = ak + (solver.t - solver.t_old) * acc
             carried = evals[-1]
             del evals[:-1]
-        if solver.status == "failed":
-            failed.append(f"sample {rows.start}: {message}" if per_sample else str(message))
-            continue
         z[rows] = torch.from_numpy(solver.y[:n].reshape(shape).copy()).to(device=xg.device, dtype=xg.dtype)
         a[rows] = torch.from_numpy(solver.y[n:].copy()).to(a.device)
         a_probes[:, rows] = torch.from_numpy(ak).to(a.device)
-        nfevs.append(int(solver.nfev))
-    _raise_failed("log_likelihood", failed, latents.shape[0])
-    D = z[0].numel()
-    logp = -0.5 * z.double().flatten(1).pow(2).sum(dim=1) - 0.5 * D * math.log(2 * math.pi) + a
-    return (logp, z, a, max(nfevs), a_probes) if probes else (logp, z, a, max(nfevs))
+        return solver.nfev, None
 
-
-def _solve_ivp_rk45(ode_func, eps, y0, rtol, atol, t_eval):
-    """The legacy ``solve_ivp(method="RK45")`` call -> ``(solution, y(1))``.  With ``t_eval`` scipy returns the requested times only
-    (``solution.y`` are the frames), so the solver's own final state is taken from an event function that never fires: solve_ivp hands
-    it every accepted ``(t, y)`` and changes nothing else, the steps and ``y(1)`` are those of the call without ``t_eval``."""
-    import numpy as np
-    from scipy import integrate
-    if t_eval is None:
-        solution = integrate.solve_ivp(ode_func, (eps, 1), y0, rtol=rtol, atol=atol, method="RK45")
-        return solution, solution.y[:, -1]
-    last = [np.asarray(y0)]
-
-    def watch(t, y):
-        last[0] = np.array(y)
-        return 1.0
-
-    solution = integrate.solve_ivp(ode_func, (eps, 1), y0, rtol=rtol, atol=atol, method="RK45", t_eval=t_eval, events=watch)
-    return solution, last[0]
+    nfe = _host_rk45("log_likelihood", latents, cond, per_sample, solve)
+    return _logp(z, a), z, a, nfe, a_probes
 
 
 def _host_frames(solution, n_eval, shape, device):
@@ -764,55 +753,32 @@ def rk45_sampler(model, shape, device=None, cond=None, source=None, eps=1e-3, rt
     if isinstance(model, Unet):
         nfev, *rest = model.integrate_rk45(x, eps, 1.0, rtol=rtol, atol=atol, class_ids=cls, cfg_strength=cfg_strength or 0.0, mask=mask,
                                            mask_is_ones=ones, per_sample=per_sample, t_eval=te)
-        nfe = int(nfev.max()) if per_sample else nfev
-        return (x, nfe) if te is None else (x, nfe, rest[2])
+        return (x, _nfe(nfev, per_sample)) if te is None else (x, _nfe(nfev, per_sample), rest[2])
 
-    if per_sample:
-        return _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength, te)
-
+    # any other model: the legacy host path through numpy in fp32, the batch as one solve_ivp problem or (per_sample) the model called on
+    # every sample alone (its class id and mask row)
     import numpy as np
-    shape = tuple(x.shape)
-    t_vec_template = torch.zeros(shape[0], device=device)
+    out = x.clone()
+    frames = None if te is None else torch.empty((len(te),) + tuple(x.shape), dtype=torch.float32, device=device)
 
-    def ode_func(t, y):
-        xt = torch.from_numpy(np.asarray(y).reshape(shape)).to(device).type(torch.float32)
-        drift = v_func_cfg(model, cond, cfg_strength, t_vec_template, xt, t)
-        return drift.detach().cpu().numpy().reshape((-1,))
-
-    solution, y1 = _solve_ivp_rk45(ode_func, eps, x.detach().cpu().numpy().reshape((-1,)), rtol, atol, te)
-    if not solution.success:
-        raise RuntimeError(f"rk45_sampler: {solution.message}")
-    lat = torch.tensor(y1).reshape(shape).type(torch.float32).to(device)
-    return (lat, solution.nfev) if te is None else (lat, solution.nfev, _host_frames(solution, len(te), shape, device))
-
-
-def _rk45_host_per_sample(model, x, cond, eps, rtol, atol, cfg_strength, te=None):
-    """rk45_sampler(per_sample=True) for models that are not a flocoder_amd.Unet: one legacy solve_ivp per sample, the model called on
-    that sample alone (its class id and mask row); with ``te`` (validated times) also the frames [F, B, C, H, W]."""
-    import numpy as np
-    out, nfevs, failed = x.clone(), [], []
-    frames = None if te is None else torch.empty((len(te),) + tuple(x.shape), dtype=torch.float32, device=x.device)
-    for b in range(x.shape[0]):
-        shape = (1,) + tuple(x.shape[1:])
-        cond_b = {k: (v[b:b + 1] if torch.is_tensor(v) else v) for k, v in cond.items()} if cond else cond
-        t_vec_template = torch.zeros(1, device=x.device)
+    def solve(rows, xg, cond_g):
+        shape = tuple(xg.shape)
+        v_func = _velocity(model, cond_g, cfg_strength, shape[0], device)
 
         def ode_func(t, y):
-            xt = torch.from_numpy(np.asarray(y).reshape(shape)).to(x.device).type(torch.float32)
-            drift = v_func_cfg(model, cond_b, cfg_strength, t_vec_template, xt, t)
-            return drift.detach().cpu().numpy().reshape((-1,))
+            xt = torch.from_numpy(np.asarray(y).reshape(shape)).to(device).type(torch.float32)
+            return v_func(xt, t).detach().cpu().numpy().reshape((-1,))
 
-        solution, y1 = _solve_ivp_rk45(ode_func, eps, x[b].detach().cpu().numpy().reshape((-1,)), rtol, atol, te)
+        solution, y1 = _solve_ivp_rk45(ode_func, (eps, 1), xg.detach().cpu().numpy().reshape((-1,)), rtol, atol, te)
         if not solution.success:
-            failed.append(f"sample {b}: {solution.message}")
-            continue
-        out[b] = torch.tensor(y1).reshape(shape[1:]).type(torch.float32).to(x.device)
+            return None, solution.message
+        out[rows] = torch.tensor(y1).reshape(shape).type(torch.float32).to(device)
         if te is not None:
-            frames[:, b] = _host_frames(solution, len(te), shape[1:], x.device)
-        nfevs.append(int(solution.nfev))
-    if failed:
-        raise RuntimeError(f"rk45_sampler: {len(failed)} of {x.shape[0]} samples failed; " + " ".join(failed))
-    return (out, max(nfevs)) if te is None else (out, max(nfevs), frames)
+            frames[:, rows] = _host_frames(solution, len(te), shape, device)
+        return solution.nfev, None
+
+    nfe = _host_rk45("rk45_sampler", x, cond, per_sample, solve)
+    return (out, nfe) if te is None else (out, nfe, frames)
 
 
 @torch.no_grad()

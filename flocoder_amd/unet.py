@@ -73,6 +73,17 @@ def validate_tol(rtol, atol):
 
 
 _GPU_ONLY = "flocoder_amd integrators run on MI355X (gfx950) only"
+
+
+def require_gpu(x: torch.Tensor, no_cpu_path: bool = True) -> None:
+    """The integrators' error for a tensor on the CPU, with or without the trailing clause: every entry keeps the wording it had."""
+    if not x.is_cuda:
+        raise RuntimeError(_GPU_ONLY + ("; there is no CPU path" if no_cpu_path else ""))
+
+
+def is_ones_mask(mask: Optional[torch.Tensor]) -> bool:
+    """unet.py:301: whether a mask (None counts as not) is all ones.  One host sync: once per call."""
+    return mask is not None and bool(torch.allclose(mask, torch.ones_like(mask)))
 _SDE_METHODS = {"euler_maruyama": B.FC_SDE_EULER_MARUYAMA, "heun": B.FC_SDE_HEUN}
 
 
@@ -312,9 +323,7 @@ class Unet(NativeModule):
     def _forward_native(self, x, time, cls, mask, train: bool) -> torch.Tensor:
         dev = x.device
         bsz, _, h, w = x.shape
-        ones = 0
-        if mask is not None:
-            ones = int(torch.allclose(mask, torch.ones_like(mask)))   # unet.py:301 (one host sync, as upstream)
+        ones = int(is_ones_mask(mask))                            # one host sync, as upstream
         hnd = self._native(dev)
         B.check((B.lib().fc_unet_train_reserve if train else B.lib().fc_unet_reserve)(hnd, bsz, h, w))
         out = torch.empty_like(x)
@@ -349,7 +358,7 @@ class Unet(NativeModule):
             if accumulate:
                 raise ValueError("backward_native(accumulate=True) needs the gradient vector to add to")
             grads = torch.empty(self._flat_numel, dtype=torch.float32, device=dev)
-        ones = int(torch.allclose(mask, torch.ones_like(mask))) if mask is not None else 0
+        ones = int(is_ones_mask(mask))
         if dx is None:
             dx = torch.empty_like(x) if want_dx else None
         if dm is None:
@@ -365,7 +374,7 @@ class Unet(NativeModule):
         are those of ``backward_native(..., want_dx=True)[1]``; no flat gradient vector is touched."""
         dev = x.device
         bsz, _, h, w = x.shape
-        ones = int(torch.allclose(mask, torch.ones_like(mask))) if mask is not None else 0
+        ones = int(is_ones_mask(mask))
         dx = torch.empty_like(x)
         B.check(B.lib().fc_unet_vjp_x(self._native(dev), B.ptr(x), B.ptr(time), B.ptr(cls), B.ptr(mask), ones, B.ptr(d_out.contiguous()),
                                       B.ptr(dx), bsz, h, w, B.current_stream(dev)))
@@ -409,12 +418,11 @@ class Unet(NativeModule):
         self._synced = self._weights_version()
 
     # ------------------------------------------------------------------ integrators (used by flocoder_amd.sampling)
-    def _integrator_args(self, x, class_ids, mask, cfg_strength=0.0, cpu_error=_GPU_ONLY):
+    def _integrator_args(self, x, class_ids, mask, cfg_strength=0.0):
         """What every integrator method checks of ``x`` and does to its conditioning -> ``(class ids, mask, U-Net rows per evaluation,
         native handle)``: ids as int64 ``[batch]`` in range, or None for a model without classes; the mask as fp32 of x's shape, or None
         for a model without mask conditioning; a guided call evaluates two rows per sample."""
-        if not x.is_cuda:
-            raise RuntimeError(cpu_error)
+        require_gpu(x)
         dev = x.device
         bsz = x.shape[0]
         if not x.is_contiguous() or x.dtype != torch.float32:
@@ -478,6 +486,7 @@ class Unet(NativeModule):
         the call waits for the trajectory when the plan contains cross-workgroup waits and raises if one timed out -- a caller never
         receives samples from a plan whose residency assumption broke.  ``check=False`` keeps the call asynchronous; the error then
         surfaces at the next call on the model or at ``check_errors()``."""
+        require_gpu(x, no_cpu_path=False)                         # this entry's wording has no trailing clause
         class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength)
         code = {"euler": B.FC_METHOD_EULER, "rk4": B.FC_METHOD_RK4}[method]
         dev = x.device
@@ -503,6 +512,30 @@ class Unet(NativeModule):
             probe = probe.clone()                       # a view at an odd storage offset: the kernels read the probe as float4
         return probe, (int(probe.shape[0]) if several else None)
 
+    def _likelihood_call(self, name: str, hnd, x, probe, k, head, mid=(), tail=(), *, check: bool, restore_plan: bool):
+        """Allocate a likelihood call's outputs ``(a, logp)``, for K probes ``(a, logp, a_probes, stderr)``, and run its native entry in the
+        training form of the plans: ``name`` for one probe (``k`` None), ``name_probes`` for K, which takes K behind the probe.  ``head``:
+        the arguments between x's dimensions and the probe, ``mid``: between the probe and the outputs, ``tail``: behind them."""
+        dev = x.device
+        bsz, _, h, w = x.shape
+        out = tuple(torch.empty(bsz, dtype=torch.float64, device=dev) for _ in range(2))
+        if k is not None:
+            out += (torch.empty(k, bsz, dtype=torch.float64, device=dev), torch.empty(bsz, dtype=torch.float64, device=dev))
+        entry = getattr(B.lib(), name if k is None else name + "_probes")
+        with self._training_form(hnd, bsz, h, w, restore_plan):
+            B.check(entry(hnd, B.ptr(x), bsz, h, w, *head, B.ptr(probe), *(() if k is None else (k,)), *mid, *(B.ptr(t) for t in out), *tail,
+                          B.current_stream(dev)))
+            self._integrator_check(hnd, dev, check)
+        return out
+
+    @staticmethod
+    def _public_counters(counters, bsz: int, per_sample: bool):
+        """The native RK45 counters -> ``(nfev, accepted, rejected)``: ints, or per sample int64 CPU tensors ``[B]``."""
+        if per_sample:
+            c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
+            return (c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone())
+        return (int(counters[0]), int(counters[1]), int(counters[2]))
+
     def log_likelihood(self, x: torch.Tensor, ts: torch.Tensor, probe: torch.Tensor, *, t_scale: float = 999.0,
                        class_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, mask_is_ones: bool = False,
                        check: bool = True, restore_plan: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -520,25 +553,12 @@ class Unet(NativeModule):
         evaluation and K data-gradient chains behind it.  Returns ``(a, logp, a_probes, logp_stderr)``: ``a_probes`` fp64 ``[K, B]``, row k
         with the bits of a single-probe call with probe k; ``a`` their mean (summed in probe order, one division), ``logp`` formed from
         it; ``logp_stderr`` fp64 ``[B]`` = ``sqrt(sum_k (a_k - a)^2 / (K (K - 1)))``, NaN for K = 1."""
-        class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask, cpu_error=_GPU_ONLY + "; there is no CPU path")
-        dev = x.device
-        bsz, _, h, w = x.shape
+        class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask)
         probe, k = self._probes_arg(x, probe)
         _, ts_ptr, n_points = self._host_grid(ts, 2)
-        a, logp = (torch.empty(bsz, dtype=torch.float64, device=dev) for _ in range(2))
-        if k is not None:
-            a_probes, stderr = torch.empty(k, bsz, dtype=torch.float64, device=dev), torch.empty(bsz, dtype=torch.float64, device=dev)
-        with self._training_form(hnd, bsz, h, w, restore_plan):
-            if k is None:
-                B.check(B.lib().fc_unet_log_likelihood(hnd, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids),
-                                                       B.ptr(mask), int(mask_is_ones), B.ptr(probe), B.ptr(a), B.ptr(logp),
-                                                       B.current_stream(dev)))
-            else:
-                B.check(B.lib().fc_unet_log_likelihood_probes(hnd, B.ptr(x), bsz, h, w, ts_ptr, n_points, float(t_scale), B.ptr(class_ids),
-                                                              B.ptr(mask), int(mask_is_ones), B.ptr(probe), k, B.ptr(a), B.ptr(logp),
-                                                              B.ptr(a_probes), B.ptr(stderr), B.current_stream(dev)))
-            self._integrator_check(hnd, dev, check)
-        return (a, logp) if k is None else (a, logp, a_probes, stderr)
+        return self._likelihood_call("fc_unet_log_likelihood", hnd, x, probe, k,
+                                     (ts_ptr, n_points, float(t_scale), B.ptr(class_ids), B.ptr(mask), int(mask_is_ones)),
+                                     check=check, restore_plan=restore_plan)
 
     def log_likelihood_rk45(self, x: torch.Tensor, eps: torch.Tensor, t0: float = 1.0, t1: float = 0.0, rtol: float = 1e-5,
                             atol: float = 1e-5, per_sample: bool = True, *, t_scale: float = 999.0, class_ids: Optional[torch.Tensor] = None,
@@ -562,31 +582,15 @@ class Unet(NativeModule):
         t0, t1 = float(t0), float(t1)
         if not (0.0 <= t1 < t0 <= 1.0):
             raise ValueError(f"t0={t0}, t1={t1}: the likelihood is integrated from the data end back towards noise, 0 <= t1 < t0 <= 1")
-        class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask, cpu_error=_GPU_ONLY + "; there is no CPU path")
-        dev = x.device
-        bsz, _, h, w = x.shape
+        class_ids, mask, _, hnd = self._integrator_args(x, class_ids, mask)
+        bsz = x.shape[0]
         eps, k = self._probes_arg(x, eps)
         self._check_aligned(x)
-        a, logp = (torch.empty(bsz, dtype=torch.float64, device=dev) for _ in range(2))
-        extra = ()
-        if k is not None:
-            extra = (torch.empty(k, bsz, dtype=torch.float64, device=dev), torch.empty(bsz, dtype=torch.float64, device=dev))
         counters = (C.c_int * (3 * bsz if per_sample else 3))()
-        with self._training_form(hnd, bsz, h, w, restore_plan):
-            if k is None:
-                B.check(B.lib().fc_unet_log_likelihood_rk45(hnd, B.ptr(x), bsz, h, w, t0, t1, float(rtol), float(atol), float(t_scale),
-                                                            B.ptr(class_ids), B.ptr(mask), int(mask_is_ones), B.ptr(eps), int(per_sample),
-                                                            B.ptr(a), B.ptr(logp), counters, B.current_stream(dev)))
-            else:
-                B.check(B.lib().fc_unet_log_likelihood_rk45_probes(hnd, B.ptr(x), bsz, h, w, t0, t1, float(rtol), float(atol), float(t_scale),
-                                                                   B.ptr(class_ids), B.ptr(mask), int(mask_is_ones), B.ptr(eps), k,
-                                                                   int(per_sample), B.ptr(a), B.ptr(logp), B.ptr(extra[0]), B.ptr(extra[1]),
-                                                                   counters, B.current_stream(dev)))
-            self._integrator_check(hnd, dev, check)
-        if per_sample:
-            c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
-            return ((c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone()), a, logp) + extra
-        return ((int(counters[0]), int(counters[1]), int(counters[2])), a, logp) + extra
+        out = self._likelihood_call("fc_unet_log_likelihood_rk45", hnd, x, eps, k,
+                                    (t0, t1, float(rtol), float(atol), float(t_scale), B.ptr(class_ids), B.ptr(mask), int(mask_is_ones)),
+                                    mid=(int(per_sample),), tail=(counters,), check=check, restore_plan=restore_plan)
+        return (self._public_counters(counters, bsz, per_sample),) + out
 
     def integrate_guided(self, x: torch.Tensor, ts: torch.Tensor, measurement: torch.Tensor, keep: torch.Tensor, *, sigma_y: float = 0.05,
                          gamma: float = 1.0, jacobian: str = "identity", t_scale: float = 999.0, class_ids: Optional[torch.Tensor] = None,
@@ -604,7 +608,7 @@ class Unet(NativeModule):
         exact = jacobian == "exact"
         if exact and class_ids is not None and self.class_condition and cfg_strength:
             raise ValueError("jacobian='exact' takes no classifier-free guidance: the chain differentiates one forward, not the guided pair")
-        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength, cpu_error=_GPU_ONLY + "; there is no CPU path")
+        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength)
         dev = x.device
         bsz, _, h, w = x.shape
         if measurement.shape != x.shape:
@@ -644,7 +648,7 @@ class Unet(NativeModule):
         sigma = float(sigma)
         if not (sigma >= 0 and math.isfinite(sigma)):
             raise ValueError("sigma must be finite and >= 0")
-        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength, cpu_error=_GPU_ONLY + "; there is no CPU path")
+        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength)
         dev = x.device
         bsz, _, h, w = x.shape
         self._check_aligned(x)
@@ -701,7 +705,7 @@ class Unet(NativeModule):
         fails the frames are discarded with it."""
         te = None if t_eval is None else validate_t_eval(t_eval, t0, t1)
         rtol, atol = validate_tol(rtol, atol)
-        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength, cpu_error=_GPU_ONLY + "; there is no CPU path")
+        class_ids, mask, rows, hnd = self._integrator_args(x, class_ids, mask, cfg_strength)
         dev = x.device
         bsz, _, h, w = x.shape
         B.check(B.lib().fc_unet_reserve(hnd, rows, h, w))
@@ -717,11 +721,7 @@ class Unet(NativeModule):
             B.check(B.lib().fc_unet_integrate_rk45_dense(hnd, int(per_sample), *head, te.ctypes.data_as(C.POINTER(C.c_double)), len(te),
                                                          B.ptr(frames), counters, B.current_stream(dev)))
         self._integrator_check(hnd, dev, check)
-        if per_sample:
-            c = torch.tensor(list(counters), dtype=torch.int64).view(bsz, 3)
-            out = (c[:, 0].clone(), c[:, 1].clone(), c[:, 2].clone())
-        else:
-            out = (int(counters[0]), int(counters[1]), int(counters[2]))
+        out = self._public_counters(counters, bsz, per_sample)
         return out if te is None else out + (frames,)
 
     def profile_ops(self, batch: int, repeats: int = 20):

@@ -91,11 +91,11 @@ def test_generic_path_on_the_oracle_unet_equals_the_restatement():
     assert float(((logp - ref.logp).abs() / ref.logp.abs()).max()) <= 1e-12
     assert float(((a - ref.a).abs() / ref.a.abs()).max()) <= 1e-9      # a is recovered from logp here: |a| << |logp|
     assert float(_rel(z, ref.z).max()) <= 1e-12
-    logp_b, _, a_b = S._log_likelihood_torch(lr.oracle_model(sd64), x.double(), lr.reversed_grid(9, torch.float64), cond, eps.double())
+    logp_b, _, a_b, _ = S._log_likelihood_torch(lr.oracle_model(sd64), x.double(), lr.reversed_grid(9, torch.float64), cond, eps.double())
     assert float(((a_b - ref.a).abs() / ref.a.abs()).max()) <= 1e-12 and torch.equal(logp_b, logp)
 
     # fp32: the gate of the GPU test
-    logp32, z32, a32 = S._log_likelihood_torch(lr.oracle_model(sd), x, lr.reversed_grid(9, torch.float32), cond, eps)
+    logp32, z32, a32, _ = S._log_likelihood_torch(lr.oracle_model(sd), x, lr.reversed_grid(9, torch.float32), cond, eps)
     assert z32.dtype == torch.float32 and a32.dtype == torch.float64
     bound = lr.a_bound(ref, eps, G_TOL)
     ratio = (a32 - ref.a).abs() / bound

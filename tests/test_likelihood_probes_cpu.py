@@ -124,14 +124,13 @@ def test_host_rk45_one_probe_identical_probes_and_by_products(per_sample):
     probes = torch.where(torch.randn(3, *x.shape, generator=_gen(9), dtype=torch.float64) >= 0, 1.0, -1.0)
     zp, ap, nfep = _parent_rk45_host(_nonlinear_model, x, None, probes[0], 1e-5, 1e-5, per_sample)
     # K = 1: the bits of the function as it stood
-    logp, z, a, nfe = S._log_likelihood_rk45_host(_nonlinear_model, x, None, probes[0], 1e-5, 1e-5, per_sample)
+    logp, z, a, nfe, _ = S._log_likelihood_rk45_host(_nonlinear_model, x, None, probes[0], 1e-5, 1e-5, per_sample)
     assert torch.equal(z, zp) and torch.equal(a, ap) and nfe == nfep
     lp_pub, z_pub, nfe_pub = S.log_likelihood(_nonlinear_model, x, probe=probes[0], method="rk45", per_sample=per_sample)
     assert torch.equal(lp_pub, logp) and torch.equal(z_pub, zp) and nfe_pub == nfep
     # K copies of one probe: the single-probe result and counters (sums of 2 or 4 equal doubles and the division are exact)
     for k in (2, 4):
-        lk, zk, ak, nk, apk = S._log_likelihood_rk45_host(_nonlinear_model, x, None, probes[:1].expand(k, *x.shape), 1e-5, 1e-5, per_sample,
-                                                          probes=True)
+        lk, zk, ak, nk, apk = S._log_likelihood_rk45_host(_nonlinear_model, x, None, probes[:1].expand(k, *x.shape), 1e-5, 1e-5, per_sample)
         assert torch.equal(zk, zp) and torch.equal(ak, ap) and nk == nfep and torch.equal(lk, logp)
         assert float((apk - ak).abs().max()) <= 1e-11 * (1 + float(apk.abs().max()))
     # distinct probes: the by-products average to the state's a

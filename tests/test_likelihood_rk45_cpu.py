@@ -107,7 +107,7 @@ def test_refusals_and_the_untouched_rk4_default():
         S.invert_latents(m, torch.zeros(1, 4, 8, 8), method="rk45")
     # method="rk4" (the default) is today's loop, bit for bit
     eps = S._make_probe("rademacher", x, _gen())
-    ref, zr, _ = S._log_likelihood_torch(_gauss_model, x, S._reverse_grid(7, x.dtype), None, eps)
+    ref, zr, _, _ = S._log_likelihood_torch(_gauss_model, x, S._reverse_grid(7, x.dtype), None, eps)
     for kw in ({}, {"method": "rk4"}, {"method": "rk4", "rtol": 1e-3, "per_sample": False}):
         logp, z, nfe = S.log_likelihood(_gauss_model, x, n_steps=7, generator=_gen(), **kw)
         assert torch.equal(logp, ref) and torch.equal(z, zr) and nfe == 24
