@@ -99,6 +99,7 @@ SIGNATURES = {
     "fc_ode_guided_correct": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _vp]),
     "fc_unet_integrate_sde": (_i, [_vp, _i, _vp, _i, _i, _i, _pf, _i, _f, _vp, _f, _vp, _i, _f, C.c_uint64, _vp, _vp, _vp]),
     "fc_ode_normal_field": (_i, [_vp, C.c_uint64, _i64, _vp, _i, _i64, _vp]),
+    "fc_inpaint_masks": (_i, [_vp, _vp, C.c_uint64, _vp, _i, _i, _i, _pi, C.POINTER(C.c_double), _i, _i, _vp]),
     "fc_debug_unet_guided_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "fc_unet_arena_serial": (C.c_uint64, [_vp]),
     "fc_unet_class_param_range": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -3,6 +3,9 @@
 //   ode.hip   the SDE samplers' normal field    counter (j, draw, sample id lo, sample id hi)
 //   ode.hip   the likelihood's probe field      counter (j, probe, sample id lo, sample id hi), key = seed + FC_PROBE_KEY_OFFSET (mod 2^64)
 //   ot_plan.hip   the plan sampler's uniforms   counter (k, draw, 0x4F54504C, 0xFFFFFFFF): a sample id with the top word all ones is negative
+//   masks.hip   the inpainting masks            counter (j, region, sample id lo, sample id hi), key = seed + FC_MASK_KEY_OFFSET (mod 2^64);
+//               region 0 the type and the stroke / rectangle counts, 1 the 'noise' pixels, 2 the rectangles, 3 + s brush stroke s
+//               (j = 0, 1 its start, j = 2 + t its step t): the list is at the head of masks.hip
 #pragma once
 #include <hip/hip_runtime.h>
 

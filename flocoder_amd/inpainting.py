@@ -1,16 +1,29 @@
-"""Inpainting conditioning: host-side mirror of ``flocoder/inpainting.py``'s ``MaskEncoder`` / ``mask_blending``
-(inpainting.py:161-253) over the gfx950 library, and ``algorithm3`` (inpainting.py:92-130), the training-free measurement guidance the
-guided sampler applies (``sampling.generate_latents_guided``; on a ``flocoder_amd.Unet`` the correction runs inside the library's RK4
-stage kernels).  The mask *generators*, ``InpaintingDataset`` and the diagnostics of that file are data preparation and stay out of
-scope."""
+"""Inpainting conditioning and its data: host-side mirror of ``flocoder/inpainting.py`` over the gfx950 library.
+
+``MaskEncoder`` / ``mask_blending`` (inpainting.py:161-253) and ``algorithm3`` (inpainting.py:92-130), the training-free measurement
+guidance the guided sampler applies (``sampling.generate_latents_guided``; on a ``flocoder_amd.Unet`` the correction runs inside the
+library's RK4 stage kernels).
+
+The mask generators and what feeds the mask-conditioned training path (inpainting.py:277-441): ``generate_mask``,
+``generate_mask_batch``, ``create_inpainting_triplet``, ``InpaintingDataset`` under upstream's names, and ``InpaintingBatches``, the
+batched producer of the dict batches ``preencode.process_dataset(inpainting=True)`` consumes.  The masks are counter-based
+(``flocoder_amd.noise.mask_field`` is the definition and the NumPy form, ``fc_inpaint_masks`` in csrc/masks.hip the device form, equal in
+every bit): a mask is a function of ``(seed, sample_id, size, type probabilities | forced type)``, so it is reproducible per sample
+whatever the batch, the loader's workers or the rank -- upstream draws from the global ``np.random`` state.  Tensors come from the
+device kernel; ``to_tensor=False`` returns the NumPy form and needs no GPU.  Upstream's cv2 brush variant, its plots and ``approx_AL``
+stay out of scope."""
 from __future__ import annotations
 
+import ctypes
 import math
 
+import numpy as np
 import torch
 from torch import nn
+from torch.utils.data import IterableDataset
 
 from . import _binding as B
+from . import noise as N
 from ._native import NativeModule
 
 
@@ -142,3 +155,135 @@ def algorithm3(v, x, t, tp, y, A, sigma_y=0.05, gamma_t=1.0):
     else:
         g = guidance_weight(v, x, tp, y, A, sigma_y)
     return v + coef * g
+
+
+# ---- mask generation and the training path's data (inpainting.py:277-441) ---------------------------------------------------------------
+MASK_CHOICES = list(N.MASK_TYPES)
+MASK_P = list(N.MASK_DEFAULT_P)
+_NO_CPU = "flocoder_amd.{} runs on MI355X (gfx950) only; there is no CPU path (flocoder_amd.noise.mask_field is the NumPy form)"
+
+
+def _device_masks(size, sample_ids, seed, device, choices, p, mask_type):
+    """``fc_inpaint_masks``: (fp32 ``[B, 1, H, W]``, int32 ``[B]`` type codes) on ``device`` for the int64 ``sample_ids``."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(_NO_CPU.format("generate_mask"))
+    h, w = (int(v) for v in size)
+    ids = torch.as_tensor(sample_ids, dtype=torch.int64).reshape(-1).to(device).contiguous()     # ids made on the device are not copied
+    if mask_type != "":
+        if mask_type not in N.MASK_TYPES:
+            raise ValueError(f"Unsupported mask_type: {mask_type}")
+        forced, n, codes, probs = N.MASK_TYPES.index(mask_type), 0, None, None
+    else:
+        code_arr, _ = N.mask_type_thresholds(choices, p)             # validates as the host form does
+        forced, n = -1, len(code_arr)
+        codes = (ctypes.c_int * n)(*[int(c) for c in code_arr])
+        probs = (ctypes.c_double * n)(*[float(v) for v in p])
+    out = torch.empty(ids.numel(), 1, h, w, dtype=torch.float32, device=device)
+    types = torch.empty(ids.numel(), dtype=torch.int32, device=device)
+    B.check(B.lib().fc_inpaint_masks(B.ptr(out), B.ptr(types), int(seed) & 0xffffffffffffffff, B.ptr(ids), ids.numel(), h, w, codes, probs, n,
+                                     forced, B.current_stream(device)))
+    return out, types
+
+
+def generate_mask(size=(128, 128), mask_type='', choices=MASK_CHOICES, p=MASK_P, to_tensor=True, device='cuda', *, seed=0, sample_id=0,
+                  return_type=False):
+    """inpainting.py:319-351, counter-based: the mask of ``(seed, sample_id)`` -- type drawn from ``choices`` with probabilities ``p`` unless
+    ``mask_type`` names one -- as a ``[1, 1, H, W]`` fp32 tensor on ``device`` (made by the device kernel), or with ``to_tensor=False``
+    as an ``[H, W]`` float64 array like upstream's (the NumPy form, bit-equal to the device's).  ``return_type`` adds the type's name."""
+    if not to_tensor:
+        m, t = N.mask_field(seed, [sample_id], size, choices, p, mask_type, return_types=True)
+        m = m[0, 0].astype(np.float64)
+        return (m, N.MASK_TYPES[int(t[0])]) if return_type else m
+    m, t = _device_masks(size, [sample_id], seed, device, choices, p, mask_type)
+    return (m, N.MASK_TYPES[int(t[0])]) if return_type else m
+
+
+def generate_mask_batch(size=(128, 128), batch_size=1, unique_masks=False, to_tensor=True, *, seed=0, sample_ids=None, device='cuda', **kwargs):
+    """inpainting.py:355-374: ``[batch_size, 1, H, W]`` masks (``[batch_size, H, W]`` array with ``to_tensor=False``).  With
+    ``unique_masks`` row b is the mask of ``(seed, sample_ids[b])`` (ids ``0 .. batch_size-1`` by default); without, as upstream, ONE mask
+    -- that of the first id -- tiled.  ``kwargs``: ``mask_type``, ``choices``, ``p``."""
+    choices, p, mask_type = kwargs.pop("choices", MASK_CHOICES), kwargs.pop("p", MASK_P), kwargs.pop("mask_type", "")
+    if kwargs:
+        raise TypeError(f"generate_mask_batch: unexpected arguments {sorted(kwargs)}")
+    if sample_ids is None:                                       # made where they are used: an upload from the host would wait for the stream
+        sample_ids = torch.arange(int(batch_size), dtype=torch.int64, device=device if to_tensor else "cpu")
+    ids = torch.as_tensor(sample_ids, dtype=torch.int64).reshape(-1)
+    if not unique_masks:
+        ids = ids[:1]
+    elif ids.numel() != int(batch_size):
+        raise ValueError(f"{ids.numel()} sample ids for batch_size={batch_size}")
+    if not to_tensor:
+        m = N.mask_field(seed, ids.cpu().numpy(), size, choices, p, mask_type)[:, 0].astype(np.float64)
+        return m if unique_masks else np.tile(m, (int(batch_size), 1, 1))
+    m, _ = _device_masks(size, ids, seed, device, choices, p, mask_type)
+    return m if unique_masks else m.expand(int(batch_size), -1, -1, -1).contiguous()
+
+
+def create_inpainting_triplet(full_image, codec, quantize=False, *, seed=0, sample_ids=None, **mask_kwargs):
+    """inpainting.py:378-389, batched: ``(source_latents, mask_pixels, target_latents)`` for ``full_image`` ``[B, C, H, W]`` on the GPU --
+    ``target = codec.encode(full_image)``, one mask per row (``sample_ids``, default ``0 .. B-1``), ``source = codec.encode(full_image *
+    (1 - mask))``; ``quantize`` passes both through ``codec.quantize`` as upstream does."""
+    if not full_image.is_cuda:
+        raise RuntimeError(_NO_CPU.format("create_inpainting_triplet"))
+    bsz = full_image.shape[0]
+    target_latents = codec.encode(full_image)
+    mask_pixels = generate_mask_batch(tuple(full_image.shape[-2:]), bsz, unique_masks=True, seed=seed, sample_ids=sample_ids,
+                                      device=full_image.device, **mask_kwargs)
+    source_latents = codec.encode(full_image * (1 - mask_pixels))
+    if quantize:
+        source_latents, target_latents = codec.quantize(source_latents), codec.quantize(target_latents)
+    return source_latents, mask_pixels, target_latents
+
+
+def _split_item(item):
+    if isinstance(item, (tuple, list)):
+        return item[0], (item[1] if len(item) > 1 else 0)
+    return item, 0
+
+
+class InpaintingDataset(IterableDataset):
+    """inpainting.py:411-441: wraps a dataset of GPU images (or ``(image, label)`` items) and yields upstream's per-item dict
+    ``{'source_image', 'mask_pixels' [H, W], 'target_image', 'label'}``.  The mask of an item is that of ``(seed, running item index)``;
+    ``mask_kwargs``: ``mask_type``, ``choices``, ``p``."""
+
+    def __init__(self, base_dataset, mask_kwargs=None, *, seed=0):
+        self.base_dataset, self.mask_kwargs, self.seed = base_dataset, dict(mask_kwargs or {}), seed
+        if hasattr(base_dataset, 'actual_len'):
+            self.actual_len = base_dataset.actual_len
+
+    def __iter__(self):
+        for index, item in enumerate(self.base_dataset):
+            full_image, label = _split_item(item)
+            if not full_image.is_cuda:
+                raise RuntimeError(_NO_CPU.format("InpaintingDataset"))
+            mask_pixels = generate_mask(size=tuple(full_image.shape[-2:]), device=full_image.device, seed=self.seed, sample_id=index,
+                                        **self.mask_kwargs).squeeze()
+            yield {'source_image': full_image * (1 - mask_pixels), 'mask_pixels': mask_pixels, 'target_image': full_image, 'label': label}
+
+
+class InpaintingBatches:
+    """Wraps any loader of ``(images, classes)`` batches and yields the dict batches ``preencode.process_dataset(inpainting=True)``
+    consumes: ``{'source_image' [B,C,H,W], 'mask_pixels' [B,1,H,W], 'target_image' [B,C,H,W], 'label'}``, images moved to ``device``,
+    masks and masked images made there.  The sample id of an item is its global index in the loader's order (``first_id`` + items before
+    it), so every rank that walks the same loader sees the same mask on the same item whichever batches it goes on to encode."""
+
+    def __init__(self, loader, seed=0, device='cuda', first_id=0, **mask_kwargs):
+        self.loader, self.seed, self.device, self.first_id, self.mask_kwargs = loader, seed, torch.device(device), int(first_id), mask_kwargs
+        if self.device.type != "cuda":
+            raise RuntimeError(_NO_CPU.format("InpaintingBatches"))
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        next_id = self.first_id
+        for batch in self.loader:
+            images, classes = _split_item(batch)
+            images = images.to(self.device, non_blocking=True)
+            bsz = images.shape[0]
+            ids = torch.arange(next_id, next_id + bsz, dtype=torch.int64, device=self.device)
+            next_id += bsz
+            mask_pixels = generate_mask_batch(tuple(images.shape[-2:]), bsz, unique_masks=True, seed=self.seed, sample_ids=ids,
+                                              device=self.device, **self.mask_kwargs)
+            yield {'source_image': images * (1 - mask_pixels), 'mask_pixels': mask_pixels, 'target_image': images, 'label': classes}

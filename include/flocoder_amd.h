@@ -316,6 +316,27 @@ int fc_unet_integrate_sde(fc_unet* u, int scheme, float* x_dev, int batch, int h
 int fc_ode_normal_field(float* out_dev, uint64_t seed, int64_t draw_index, const int64_t* sample_ids_dev, int batch, int64_t per_sample,
                         void* stream);
 
+/* Inpainting masks (replace flocoder/inpainting.py:277-351 generate_mask, restated counter-based): masks_out_dev [batch, 1, height, width]
+ * fp32 0/1 and types_out_dev [batch] int32 (the FC_MASK_* code chosen) for the given sample ids (int64; NULL: 0 .. batch-1; negative and
+ * > 2^32 are legal).  A mask depends on (seed, sample id, height, width, the type probabilities or the forced type) and on nothing else --
+ * not on its row, the batch or the stream.  Philox4x32-10 with key = seed + FC_MASK_KEY_OFFSET (mod 2^64) and counter (j, region, sample
+ * id); csrc/masks.hip has the regions, flocoder_amd/noise.py mask_field is the host form and agrees in every bit (all draws and the brush
+ * walk are integer arithmetic; the walk's sine / cosine come from the committed table csrc/mask_trig.h).
+ * Type: forced_type >= 0 gives every sample that type (the choices are not read); otherwise word 0 of the sample's first block against the
+ * cumulative probs_host [n_choices] (fp64, each in [0, 1], sum 1 to 1e-8; 1 <= n_choices <= 16) of choice_types_host [n_choices]: the
+ * thresholds are floor(cum_k 2^32) with cum summed left to right in fp64, the last one 2^32.  Both arrays are host memory, read during the
+ * call.  16 <= height, width <= 1024, else FC_E_SHAPE.  One launch on `stream`, one workgroup per sample; no allocation, no host wait. */
+#define FC_MASK_TOTAL 0
+#define FC_MASK_BRUSH 1
+#define FC_MASK_RECTANGLES 2
+#define FC_MASK_NOISE 3
+#define FC_MASK_NOTHING 4
+#define FC_MASK_MIN_SIZE 16
+#define FC_MASK_MAX_SIZE 1024
+#define FC_MASK_KEY_OFFSET 0x4D41534B464C4431ULL /* "MASKFLD1" */
+int fc_inpaint_masks(float* masks_out_dev, int* types_out_dev, uint64_t seed, const int64_t* sample_ids_dev, int batch, int height, int width,
+                     const int* choice_types_host, const double* probs_host, int n_choices, int forced_type, void* stream);
+
 /* ---- debug / test hooks: not part of the drop-in surface --------------------------------------- */
 /* After an exact-form fc_unet_integrate_guided call: device pointers to the last stage's input state [B,C,H,W], its scaled time rows [B],
  * its w and q = (dv/dx)^T w, while the plan that ran it stands. */
