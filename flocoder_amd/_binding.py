@@ -140,6 +140,10 @@ SIGNATURES = {
     "fc_vae_op_info": (_i, [_vp, _i, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_double)]),
     "fc_vae_set_precision": (_i, [_vp, _i]),
     "fc_vqvae_set_precision": (_i, [_vp, _i]),
+    "fc_vae_debug_taps": (_i, [_vp, _i]),
+    "fc_vae_debug_tensor": (_i, [_vp, _i, C.c_char_p, C.POINTER(_vp), _pi, _pi, _pi]),
+    "fc_vqvae_debug_taps": (_i, [_vp, _i]),
+    "fc_vqvae_debug_tensor": (_i, [_vp, _i, C.c_char_p, C.POINTER(_vp), _pi, _pi, _pi]),
     "fc_debug_set_conv_precision": (_i, [_i]),
     "fc_vae_op_bytes": (_i, [_vp, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fc_unet_op_bytes": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -51,9 +51,10 @@ def conv_debug(x0: torch.Tensor, w: torch.Tensor, bias=None, x1=None, add=None, 
     return res, (mean, var)
 
 
-def fetch_tap(model, name: str, batch: int) -> torch.Tensor:
-    """Copy an internal NHWC activation of the model's last forward into a fresh NCHW tensor."""
-    p, c, h, w = model.debug_tensor(name)
+def fetch_tap(model, name: str, batch: int, decode: Optional[bool] = None) -> torch.Tensor:
+    """Copy an internal NHWC activation of the model's last forward into a fresh NCHW tensor.  ``decode``: for a codec (``debug_taps``
+    on), which of its two plans holds the tap."""
+    p, c, h, w = model.debug_tensor(name) if decode is None else model.debug_tensor(name, decode)
     dev = next(model.parameters()).device
     t = torch.empty(batch, h, w, c, device=dev, dtype=torch.float32)
     B.check(B.lib().fc_debug_copy(t.data_ptr(), p, t.numel() * 4, B.current_stream(dev)))

@@ -81,8 +81,20 @@ class _NativeCodec(NativeModule):
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
         self._precision = mode
 
+    def debug_taps(self, on: bool = True) -> None:
+        """Tests only: plans built from now on recycle no activation buffer and record every module's tensors by name (``debug_tensor``).
+        Switching drops the plans in place; off (the default) is the ordinary recycled plan."""
+        self._taps = bool(on)
+
+    def debug_tensor(self, name: str, decode: bool = True):
+        """(device pointer, C, H, W) of the NHWC tensor the last encode / decode left under ``name`` (``_ops.fetch_tap`` copies it)."""
+        p, c, h, w = C.c_void_p(), C.c_int(), C.c_int(), C.c_int()
+        B.check(self._fn("debug_tensor")(self._handle, int(decode), name.encode(), C.byref(p), C.byref(c), C.byref(h), C.byref(w)))
+        return p.value, c.value, h.value, w.value
+
     def _on_use(self, handle, device):
         B.check(self._fn("set_precision")(handle, _PRECISIONS[getattr(self, "_precision", "fp32")]))
+        B.check(self._fn("debug_taps")(handle, int(getattr(self, "_taps", False))))
 
     def _need_gpu(self, t):
         if not t.is_cuda:

@@ -12,6 +12,7 @@ struct Codec : ParamStore {
     int device = 0;             // < 0: description only (parameter table, no device memory)
     Plan enc, dec;
     int prec = 0;               // set_precision: arithmetic of the plans built from now on (0 exact fp32, 1 split-bf16)
+    int taps = 0;               // debug_taps: the plans built from now on recycle no buffer and name their tensors (PlanBuilder::keep_all)
     const Plan& plan(int decode) const { return decode ? dec : enc; }
 };
 
@@ -55,16 +56,38 @@ inline int codec_load(Codec* v, const char* fn, const float* flat, int64_t numel
     return v->load(flat, numel, on_device, static_cast<hipStream_t>(stream));
 }
 
-// Plans in place were built for the other arithmetic: they are dropped, the next reserve rebuilds.
+// A switch the builders read has changed: the plans in place were built the other way and are dropped, the next reserve rebuilds.
+inline int codec_drop_plans(Codec* v) {
+    if (v->device < 0) return FC_OK;
+    FC_HIP(hipSetDevice(v->device));
+    FC_HIP(hipDeviceSynchronize());
+    v->enc.release(); v->dec.release();
+    return FC_OK;
+}
+
 inline int codec_set_precision(Codec* v, const char* fn, int mode) {
     if (!v || (mode != 0 && mode != 1)) return codec_fail(FC_E_ARG, fn, "mode is 0 (fp32) or 1 (split-bf16)");
     if (v->prec == mode) return FC_OK;
     v->prec = mode;
-    if (v->device >= 0) {
-        FC_HIP(hipSetDevice(v->device));
-        FC_HIP(hipDeviceSynchronize());
-        v->enc.release(); v->dec.release();
-    }
+    return codec_drop_plans(v);
+}
+
+// Debug taps (tests only): plans that recycle no buffer and name their tensors (PlanBuilder::keep_all).
+inline int codec_debug_taps(Codec* v, const char* fn, int on) {
+    if (!v) return codec_fail(FC_E_ARG, fn, "null handle");
+    on = on ? 1 : 0;
+    if (v->taps == on) return FC_OK;
+    v->taps = on;
+    return codec_drop_plans(v);
+}
+
+// A tensor the encode / decode plan recorded under `name` (NHWC, plan.maxB rows); only plans built with taps on have any.
+inline int codec_debug_tensor(const Codec* v, const char* fn, int decode, const char* name, const float** ptr, int* C, int* H, int* W) {
+    if (!v || !name || !ptr || !C || !H || !W) return codec_fail(FC_E_ARG, fn, "null argument");
+    const Plan& pl = v->plan(decode);
+    auto it = pl.named.find(name);
+    if (it == pl.named.end()) return codec_fail(FC_E_ARG, fn, (std::string("no tap named ") + name + (v->taps ? "" : " (debug taps are off)")).c_str());
+    *ptr = it->second.p; *C = it->second.C; *H = it->second.H; *W = it->second.W;
     return FC_OK;
 }
 

@@ -264,7 +264,11 @@ struct PlanBuilder {
         return a;
     }
     // The plan is a fixed sequence on one stream, so a buffer whose last reader has been emitted can serve a later tensor.
-    void release(const Act& a) { if (a.p) pool.emplace((size_t)B * a.H * a.W * a.C, a.p); }
+    // keep_all (debug taps, tests only): nothing goes back to the pool, so every tensor keeps its own memory after a run and tap()
+    // records it in Plan::named.
+    bool keep_all = false;
+    void release(const Act& a) { if (a.p && !keep_all) pool.emplace((size_t)B * a.H * a.W * a.C, a.p); }
+    void tap(const std::string& name, const Act& a) { if (keep_all && !err) pl->named[name] = a; }
     Stat stat(int G, int T, float n_t) { Stat s; s.G = G; s.T = T; s.n_t = n_t; s.p = dmalloc((size_t)B * G * T * 2); return s; }
 
     static SrcXform xf_of(const Stat& st, int mode, const float* gamma, const float* beta, const float* ss = nullptr, int ss_stride = 0,
@@ -442,6 +446,7 @@ struct PlanBuilder {
             a.add = x.p; a.stats_post = 1;
             conv(a, out, want_G, so);
         }
+        tap(scope + ".q", q); tap(scope + ".k", k); tap(scope + ".v", vv); tap(scope + ".p", sc); tap(scope + ".o", o);   // .p: after the softmax
         release(q); release(k); release(vv); release(sc); release(o);
         return out;
     }

@@ -139,6 +139,7 @@ struct VBuilder : PlanBuilder {
         b.add = sc.p; b.stats_post = 1;
         conv(b, out, want_stats ? G : 0, so);
         if (t2.p) release(t2);
+        tap(n, out); tap(n + ".h1", h1);
         release(h1);
         if (proj) release(sc);
         return out;
@@ -149,7 +150,9 @@ struct VBuilder : PlanBuilder {
         scope = n;
         AttnWeights w{v->P(n + ".to_q.weight"), v->R(n + ".to_q.bias"), v->P(n + ".to_k.weight"), v->R(n + ".to_k.bias"),
                       v->P(n + ".to_v.weight"), v->R(n + ".to_v.bias"), v->P(n + ".to_out.0.weight"), v->R(n + ".to_out.0.bias")};
-        return attention_block(x, gn(sx, n + ".group_norm", 1), w, v->groups, so);
+        Act out = attention_block(x, gn(sx, n + ".group_norm", 1), w, v->groups, so);
+        tap(n, out);
+        return out;
     }
 
     Act mid(const std::string& n, Act x, Stat sx, Stat* so) {
@@ -169,7 +172,7 @@ static int build_encoder(fc_vae* v, int maxB, int H, int W) {
     const int L = (int)v->bo.size();
     if (!is_pow2(H) || !is_pow2(W) || (H >> (L - 1)) < 1 || (W >> (L - 1)) < 1) return fail(FC_E_SHAPE, "vae: image height/width must be powers of two >= 8");
     VBuilder b(v, &v->enc, maxB);
-    b.conv_prec = v->prec;
+    b.conv_prec = v->prec; b.keep_all = v->taps != 0;
     const int G = v->groups, ic = v->in_ch;
     Act xin = b.act(4, H, W);
     float* xp = xin.p;
@@ -183,6 +186,7 @@ static int build_encoder(fc_vae* v, int maxB, int H, int W) {
         a.s0.p = xin.p; a.s0.C = 4; a.Hs = H; a.Ws = W; a.KS = 3; a.pad = 1;
         a.w = v->P("encoder.conv_in.weight"); a.bias = v->R("encoder.conv_in.bias");
         b.conv(a, x, G, &st);
+        b.tap(b.scope, x);
     }
     for (int i = 0; i < L && !b.err; ++i) {
         const std::string blk = "encoder.down_blocks." + std::to_string(i);
@@ -200,6 +204,7 @@ static int build_encoder(fc_vae* v, int maxB, int H, int W) {
             a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 0; a.stride = 2;
             a.w = v->P(blk + ".downsamplers.0.conv.weight"); a.bias = v->R(blk + ".downsamplers.0.conv.bias");
             b.conv(a, y, G, &st);
+            b.tap(b.scope, y);
             b.release(x);
             x = y;
         }
@@ -216,11 +221,13 @@ static int build_encoder(fc_vae* v, int maxB, int H, int W) {
         a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
         a.w = v->P("encoder.conv_out.weight"); a.bias = v->R("encoder.conv_out.bias");
         b.conv(a, mo, 0, nullptr);
+        b.tap(b.scope, mo);
         b.scope = "quant_conv";
         ConvArgs q;
         q.s0.p = mo.p; q.s0.C = mo.C; q.Hs = x.H; q.Ws = x.W; q.KS = 1;
         q.w = v->P("quant_conv.weight"); q.bias = v->R("quant_conv.bias");
         b.conv(q, qo, 0, nullptr);
+        b.tap(b.scope, qo);
     }
     if (b.err) return b.err;
     const float* qp = qo.p;
@@ -236,7 +243,7 @@ static int build_decoder(fc_vae* v, int maxB, int h, int w) {
     const int L = (int)v->bo.size();
     if (!is_pow2(h) || !is_pow2(w)) return fail(FC_E_SHAPE, "vae: latent height/width must be powers of two");
     VBuilder b(v, &v->dec, maxB);
-    b.conv_prec = v->prec;
+    b.conv_prec = v->prec; b.keep_all = v->taps != 0;
     const int G = v->groups, lat = v->latent, top = v->bo[L - 1];
     Act zin = b.act(lat, h, w), z1 = b.act(lat, h, w);
     float* zp = zin.p;
@@ -250,11 +257,13 @@ static int build_decoder(fc_vae* v, int maxB, int h, int w) {
         q.s0.p = zin.p; q.s0.C = lat; q.Hs = h; q.Ws = w; q.KS = 1;
         q.w = v->P("post_quant_conv.weight"); q.bias = v->R("post_quant_conv.bias");
         b.conv(q, z1, 0, nullptr);
+        b.tap(b.scope, z1);
         b.scope = "decoder.conv_in";
         ConvArgs a;
         a.s0.p = z1.p; a.s0.C = lat; a.Hs = h; a.Ws = w; a.KS = 3; a.pad = 1;
         a.w = v->P("decoder.conv_in.weight"); a.bias = v->R("decoder.conv_in.bias");
         b.conv(a, x, G, &st);
+        b.tap(b.scope, x);
     }
     if (b.err) return b.err;
     Stat sm;
@@ -282,6 +291,7 @@ static int build_decoder(fc_vae* v, int maxB, int h, int w) {
                 a.w = v->P(blk + ".upsamplers.0.conv.weight"); a.bias = v->R(blk + ".upsamplers.0.conv.bias");
                 b.conv(a, y, G, &st);
             }
+            b.tap(b.scope, y);
             b.release(x);
             x = y;
         }
@@ -295,6 +305,7 @@ static int build_decoder(fc_vae* v, int maxB, int h, int w) {
         a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
         a.w = v->P("decoder.conv_out.weight"); a.bias = v->P("decoder.conv_out.bias");
         b.conv(a, yo, 0, nullptr);
+        b.tap(b.scope, yo);
     }
     if (b.err) return b.err;
     const float* yp = yo.p;
@@ -325,6 +336,10 @@ int fc_vae_load_params(fc_vae* v, const float* flat, int64_t numel, int on_devic
     return codec_load(v, "fc_vae_load_params", flat, numel, on_device, stream);
 }
 int fc_vae_set_precision(fc_vae* v, int mode) { return codec_set_precision(v, "fc_vae_set_precision", mode); }
+int fc_vae_debug_taps(fc_vae* v, int on) { return codec_debug_taps(v, "fc_vae_debug_taps", on); }
+int fc_vae_debug_tensor(const fc_vae* v, int decode, const char* name, const float** ptr, int* C, int* H, int* W) {
+    return codec_debug_tensor(v, "fc_vae_debug_tensor", decode, name, ptr, C, H, W);
+}
 int fc_vae_reserve_encode(fc_vae* v, int max_batch, int height, int width) {
     return codec_reserve(v, "fc_vae_reserve_encode", 0, build_encoder, max_batch, height, width);
 }

@@ -143,6 +143,7 @@ struct QBuilder : PlanBuilder {
             AttnWeights w{v->P(n + ".attn.q.weight"), v->R(n + ".attn.q.bias"), v->P(n + ".attn.k.weight"), v->R(n + ".attn.k.bias"),
                           v->P(n + ".attn.v.weight"), v->R(n + ".attn.v.bias"), v->P(n + ".attn.proj_out.weight"), v->R(n + ".attn.proj_out.bias")};
             Act a2 = attention_block(a1, gn(sa, n + ".attn.norm.norm", 1, 1e-6f), w, 0, nullptr);
+            tap(n + ".act", a1);
             release(a1);
             mid_in = a2; mid_raw = true;
         }
@@ -170,6 +171,7 @@ struct QBuilder : PlanBuilder {
             pj.s0.p = att.p; pj.s0.C = co; pj.Hs = Ho; pj.Ws = Wo; pj.KS = 1;
             pj.w = v->P(n + ".attn.proj.weight"); pj.add = a1.p;
             conv(pj, a2, 0, nullptr);
+            tap(n + ".act", a1); tap(n + ".qkv", qkv); tap(n + ".att", att);    // .att carries gamma
             release(qkv); release(att); release(a1);
             mid_in = a2; mid_raw = true;
         }
@@ -189,6 +191,7 @@ struct QBuilder : PlanBuilder {
         b.Hs = Ho; b.Ws = Wo; b.KS = 3; b.pad = 1;
         b.w = v->P(n + ".conv2.weight"); b.bias = v->R(n + ".conv2.bias");
         conv(b, h2, G, &s2);
+        tap(n + ".h1", h1); tap(n + ".mid", mid_in); tap(n + ".h2", h2);
         if (mid_raw) release(mid_in);
         Act out = act(co, Ho, Wo);
         FinalizeArgs f;
@@ -205,6 +208,8 @@ struct QBuilder : PlanBuilder {
             f.res = x.p;
         }
         if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
+        tap(n, out);
+        if (d.p) tap(n + ".res", d);
         release(h1); release(h2);
         if (d.p) release(d);
         return out;
@@ -217,7 +222,7 @@ static int build_encoder(fc_vqvae* v, int maxB, int H, int W) {
     const int nd = c.num_downsamples, emb = c.vq_embedding_dim;
     if (!is_pow2(H) || !is_pow2(W) || (H >> nd) < 4 || (W >> nd) < 4) return fail(FC_E_SHAPE, "vqvae: image size must be a power of two, >= 4 latent pixels per side");
     QBuilder b(v, &v->enc, maxB);
-    b.conv_prec = v->prec;
+    b.conv_prec = v->prec; b.keep_all = v->taps != 0;
     const int ic = c.in_channels, icp = pad4(ic);
     Act x = b.act(icp, H, W);
     float* xp = x.p;
@@ -251,6 +256,8 @@ static int build_encoder(fc_vqvae* v, int maxB, int H, int W) {
         r.Hs = y.H; r.Ws = y.W; r.KS = 3; r.pad = 1;
         r.w = v->P("encoder." + std::to_string(2 * nd + 5) + ".weight"); r.bias = v->R("encoder." + std::to_string(2 * nd + 5) + ".bias");
         b.conv(r, t3, 0, nullptr);
+        b.tap("encoder." + std::to_string(2 * nd + 1), t1); b.tap("encoder." + std::to_string(2 * nd + 2), t2);
+        b.tap("encoder." + std::to_string(2 * nd + 5), t3);
     }
     if (b.err) return b.err;
     const float* zp = t3.p;
@@ -268,7 +275,7 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
     if (!is_pow2(h) || !is_pow2(w) || h < 4 || w < 4) return fail(FC_E_SHAPE, "vqvae: latent size must be a power of two >= 4");
     if (emb & 3) return fail(FC_E_SHAPE, "vqvae: vq_embedding_dim must be a multiple of 4");
     QBuilder b(v, &v->dec, maxB);
-    b.conv_prec = v->prec;
+    b.conv_prec = v->prec; b.keep_all = v->taps != 0;
     const std::string L = "decoder.layers.";
     Act z = b.act(emb, h, w);
     float* zp = z.p;
@@ -283,6 +290,7 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
         const int n = h * w, cr = emb / 2 > 1 ? emb / 2 : 1;
         b.scope = L + "0";
         b.push([=](const FwdCtx& cx, hipStream_t s) { return rope_attn_launch(ip, wq, bq, wk, bk, wv, bv, wo, bo, op, cx.B, n, emb, cr, s); }, "rope_attn");
+        b.tap(b.scope, z2);
         z = z2;
         i = 1;
     }
@@ -300,6 +308,7 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
         q.Hs = h; q.Ws = w; q.KS = 1;
         q.w = v->P(L + std::to_string(i + 3) + ".weight"); q.bias = v->R(L + std::to_string(i + 3) + ".bias");
         b.conv(q, x, 0, nullptr);
+        b.tap(L + std::to_string(i), t1); b.tap(L + std::to_string(i + 3), x);
     }
     if (b.err) return b.err;
     {
@@ -320,6 +329,7 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
         const float* up = u.p; float* pp = ps.p;
         const int Hs = x.H, Ws = x.W, cc = cur;
         b.push([=](const FwdCtx& cx, hipStream_t s) { return pixel_shuffle2_nhwc_launch(up, pp, cx.B, Hs, Ws, cc, s); }, "pixel_shuffle");
+        b.tap(L + std::to_string(i), u); b.tap(L + std::to_string(i + 2), ps);   // conv with its SiLU epilogue; nn.PixelShuffle is layer i + 2
         b.release(x); b.release(u);
         Act y1 = b.block(L + std::to_string(i + 4), ps, co, 1);
         b.release(ps);
@@ -341,6 +351,7 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
         q.s0.p = f1.p; q.s0.C = 64; q.Hs = x.H; q.Ws = x.W; q.KS = 3; q.pad = 1;
         q.w = v->P(L + std::to_string(i + 4) + ".weight"); q.bias = bias_of(v, L + std::to_string(i + 4));
         b.conv(q, f2, 0, nullptr);
+        b.tap(L + std::to_string(i + 1), f1); b.tap(L + std::to_string(i + 4), f2);   // f1 with its SiLU epilogue
     }
     if (b.err) return b.err;
     const float* yp = f2.p;
@@ -382,6 +393,10 @@ int fc_vqvae_load_params(fc_vqvae* v, const float* flat, int64_t numel, int on_d
     return codec_load(v, "fc_vqvae_load_params", flat, numel, on_device, stream);
 }
 int fc_vqvae_set_precision(fc_vqvae* v, int mode) { return codec_set_precision(v, "fc_vqvae_set_precision", mode); }
+int fc_vqvae_debug_taps(fc_vqvae* v, int on) { return codec_debug_taps(v, "fc_vqvae_debug_taps", on); }
+int fc_vqvae_debug_tensor(const fc_vqvae* v, int decode, const char* name, const float** ptr, int* C, int* H, int* W) {
+    return codec_debug_tensor(v, "fc_vqvae_debug_tensor", decode, name, ptr, C, H, W);
+}
 int fc_vqvae_reserve_encode(fc_vqvae* v, int max_batch, int height, int width) {
     return codec_reserve(v, "fc_vqvae_reserve_encode", 0, build_encoder, max_batch, height, width);
 }

@@ -284,7 +284,16 @@ class Unet(NativeModule):
         row as unconditional, so the host mirror raises like the reference.  One small host sync per call."""
         if cls is None or cls.numel() == 0:
             return
-        lo, hi = (int(v) for v in torch.stack((cls.min(), cls.max())).tolist())
+        mm = torch.stack((cls.min(), cls.max()))
+        if mm.is_cuda:
+            # The reductions are finished before the copy to the host is issued.  Seen once in tools/inflight_diag.py under
+            # FLOCODER_AMD_POISON=1 and AMD_DIRECT_DISPATCH=0 (sample_many, two streams): valid ids read back as 0x00ffffffffffffff /
+            # 0x778a00000000 -- what fresh allocator memory holds there, i.e. `mm` before its kernels ran.  Under that switch ROCm 7.2
+            # lets work submitted from this thread pass launches still queued in its submission thread, and a stream wait on the host
+            # is what orders them (csrc/unet_integrate.hip, the wait before a call's first replay).  Without the poison the leftovers
+            # are usually small numbers and the check passes unnoticed, having checked nothing.
+            torch.cuda.current_stream(mm.device).synchronize()
+        lo, hi = (int(v) for v in mm.tolist())
         if lo < 0 or hi >= self._cfg.n_classes:
             raise IndexError(f"class_cond ids must lie in [0, {self._cfg.n_classes}); got min {lo}, max {hi}")
 

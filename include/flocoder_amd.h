@@ -516,6 +516,13 @@ int fc_vae_op_info(const fc_vae* v, int decode, int i, const char** kernel, cons
 int fc_vae_profile_ops(fc_vae* v, int decode, const float* in_dev, float* out_dev, int batch, int repeats, float* ms_out, int n_out,
                        void* stream);
 int fc_vae_op_bytes(const fc_vae* v, int decode, int i, double* bytes_per_sample, double* bytes_per_launch);   /* as fc_unet_op_bytes */
+/* Tests only.  on != 0: the plans built from now on recycle no activation buffer and record their tensors by reference module name
+ * ("decoder.mid_block.resnets.0", its conv1 output ".h1", an attention's ".q .k .v .p .o", ...); the arena grows to the sum of all tensors
+ * (~1 GB for one 256x256 decode).  Changing the switch drops the current plans; with it off nothing differs from a handle that never had it.
+ * fc_*_debug_tensor: the NHWC tensor [max_batch][H][W][C] the encode (decode = 0) / decode plan recorded under `name`, as the last run left it
+ * (copy it with fc_debug_copy). */
+int fc_vae_debug_taps(fc_vae* v, int on);
+int fc_vae_debug_tensor(const fc_vae* v, int decode, const char* name, const float** ptr, int* channels, int* height, int* width);
 
 /* ------------------------------------------------------------------------------------------------
  * VQVAE codec, encode / decode  (replaces flocoder/codecs.py:386-525 VQVAE.encode / VQVAE.decode with
@@ -552,6 +559,8 @@ int fc_vqvae_encode(fc_vqvae* v, const float* x_dev, float* z_out_dev, int batch
 /* x = vqvae.decode(z_q)  (codecs.py:523-525, noise_strength 0): z_dev [B,vq_embedding_dim,h,w] -> x_out_dev [B,in_channels,H,W]. */
 int fc_vqvae_decode(fc_vqvae* v, const float* z_dev, float* x_out_dev, int batch, int lat_height, int lat_width, void* stream);
 int fc_vqvae_set_precision(fc_vqvae* v, int mode);     /* as fc_vae_set_precision */
+int fc_vqvae_debug_taps(fc_vqvae* v, int on);          /* as fc_vae_debug_taps: block outputs by state_dict prefix, ".h1 .mid .h2 .res" ... */
+int fc_vqvae_debug_tensor(const fc_vqvae* v, int decode, const char* name, const float** ptr, int* channels, int* height, int* width);
 double fc_vqvae_flops_per_sample(const fc_vqvae* v, int decode);
 /* Measurement only (bench.py's config-5 leg): launches of the encode / decode plan, launch i's kernel family, module, algorithmic FLOPs
  * per sample and HBM bytes (per sample / per launch; 0 where not stated), and every launch timed alone as in fc_unet_profile_ops. */

@@ -18,7 +18,7 @@ The wrapper semantics that ARE the reference's own (and are restated exactly): `
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 import torch.nn.functional as F
@@ -88,61 +88,119 @@ def _gn_silu(sd, n, x):
     return F.silu(F.group_norm(x, GROUPS, sd[n + ".weight"], sd[n + ".bias"], eps=EPS))
 
 
-def resnet(sd: SD, n: str, x: Tensor) -> Tensor:
-    h = _conv(sd, n + ".conv1", _gn_silu(sd, n + ".norm1", x), padding=1)
-    h = _conv(sd, n + ".conv2", _gn_silu(sd, n + ".norm2", h), padding=1)
+def resnet_h1(sd: SD, n: str, x: Tensor) -> Tensor:
+    """conv1 output of a resnet (the module's ``.h1`` tap)."""
+    return _conv(sd, n + ".conv1", _gn_silu(sd, n + ".norm1", x), padding=1)
+
+
+def resnet_close(sd: SD, n: str, x: Tensor, h1: Tensor) -> Tensor:
+    h = _conv(sd, n + ".conv2", _gn_silu(sd, n + ".norm2", h1), padding=1)
     if (n + ".conv_shortcut.weight") in sd:
         x = _conv(sd, n + ".conv_shortcut", x)
     return x + h                                            # output_scale_factor = 1
 
 
-def attention(sd: SD, n: str, x: Tensor) -> Tensor:
-    """Single head over all h*w tokens, d = C: softmax(q k^T / sqrt(C)) v, projected, plus the residual."""
+def resnet(sd: SD, n: str, x: Tensor, taps: Optional[dict] = None) -> Tensor:
+    h1 = resnet_h1(sd, n, x)
+    out = resnet_close(sd, n, x, h1)
+    if taps is not None:
+        taps[n + ".h1"], taps[n] = h1, out
+    return out
+
+
+# The mid-block attention in four steps, every tensor NCHW as the library's taps are read back: q / k / v [b, c, h, w]; the scores after
+# the softmax p [b, n_keys, h, w] (channel j of pixel i: the weight query i gives key j); o = p v [b, c, h, w].
+def attn_qkv(sd: SD, n: str, x: Tensor):
     b, c, h, w = x.shape
     t = F.group_norm(x, GROUPS, sd[n + ".group_norm.weight"], sd[n + ".group_norm.bias"], eps=EPS)
     t = t.reshape(b, c, h * w).transpose(1, 2)             # b n c
-    q = F.linear(t, sd[n + ".to_q.weight"], sd[n + ".to_q.bias"])
-    k = F.linear(t, sd[n + ".to_k.weight"], sd[n + ".to_k.bias"])
-    v = F.linear(t, sd[n + ".to_v.weight"], sd[n + ".to_v.bias"])
-    a = torch.softmax(q @ k.transpose(1, 2) * c ** -0.5, dim=-1)
-    o = F.linear(a @ v, sd[n + ".to_out.0.weight"], sd[n + ".to_out.0.bias"])
-    return o.transpose(1, 2).reshape(b, c, h, w) + x
+    return tuple(F.linear(t, sd[n + f".to_{u}.weight"], sd[n + f".to_{u}.bias"]).transpose(1, 2).reshape(b, c, h, w) for u in "qkv")
 
 
-def _mid(sd, n, x):
-    x = resnet(sd, n + ".resnets.0", x)
-    x = attention(sd, n + ".attentions.0", x)
-    return resnet(sd, n + ".resnets.1", x)
+def attn_probs(q: Tensor, k: Tensor) -> Tensor:
+    """softmax over the keys of q k^T / sqrt(C)."""
+    b, c, h, w = q.shape
+    a = torch.softmax(torch.bmm(q.reshape(b, c, h * w).permute(0, 2, 1), k.reshape(b, c, h * w)) * int(c) ** -0.5, dim=2)
+    return a.permute(0, 2, 1).reshape(b, h * w, h, w)
 
 
-def encode_mean(sd: SD, x: Tensor) -> Tensor:
-    """vae.encode(x).latent_dist.mean (codecs.py:642): no sampling, no scaling factor."""
+def attn_apply(p: Tensor, v: Tensor) -> Tensor:
+    b, c, h, w = v.shape
+    return torch.bmm(v.reshape(b, c, h * w), p.reshape(b, h * w, h * w)).reshape(b, c, h, w)
+
+
+def attn_close(sd: SD, n: str, o: Tensor, x: Tensor) -> Tensor:
+    b, c, h, w = x.shape
+    y = F.linear(o.reshape(b, c, h * w).transpose(1, 2), sd[n + ".to_out.0.weight"], sd[n + ".to_out.0.bias"])
+    return y.transpose(1, 2).reshape(b, c, h, w) + x
+
+
+def attention(sd: SD, n: str, x: Tensor, taps: Optional[dict] = None) -> Tensor:
+    """Single head over all h*w tokens, d = C: softmax(q k^T / sqrt(C)) v, projected, plus the residual."""
+    q, k, v = attn_qkv(sd, n, x)
+    p = attn_probs(q, k)
+    o = attn_apply(p, v)
+    out = attn_close(sd, n, o, x)
+    if taps is not None:
+        taps.update({n + ".q": q, n + ".k": k, n + ".v": v, n + ".p": p, n + ".o": o, n: out})
+    return out
+
+
+def _mid(sd, n, x, taps=None):
+    x = resnet(sd, n + ".resnets.0", x, taps)
+    x = attention(sd, n + ".attentions.0", x, taps)
+    return resnet(sd, n + ".resnets.1", x, taps)
+
+
+def downsample(sd: SD, n: str, x: Tensor) -> Tensor:
+    """Downsample2D ``n`` = ...downsamplers.0: pad (0,1,0,1) + conv3x3 stride 2."""
+    return _conv(sd, n + ".conv", F.pad(x, (0, 1, 0, 1)), stride=2)
+
+
+def upsample(sd: SD, n: str, x: Tensor) -> Tensor:
+    """Upsample2D ``n`` = ...upsamplers.0: nearest x2 + conv3x3."""
+    return _conv(sd, n + ".conv", F.interpolate(x, scale_factor=2.0, mode="nearest"), padding=1)
+
+
+def conv_out(sd: SD, side: str, x: Tensor) -> Tensor:
+    return _conv(sd, side + ".conv_out", _gn_silu(sd, side + ".conv_norm_out", x), padding=1)
+
+
+def _tap(taps, name, value):
+    if taps is not None:
+        taps[name] = value
+    return value
+
+
+def encode_mean(sd: SD, x: Tensor, taps: Optional[dict] = None) -> Tensor:
+    """vae.encode(x).latent_dist.mean (codecs.py:642): no sampling, no scaling factor.  ``taps``: filled with every module's output by
+    module name (a resnet's conv1 output as ``.h1``, an attention's ``.q .k .v .p .o``)."""
     n_blocks = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("encoder.down_blocks."))
-    h = _conv(sd, "encoder.conv_in", x, padding=1)
+    h = _tap(taps, "encoder.conv_in", _conv(sd, "encoder.conv_in", x, padding=1))
     for i in range(n_blocks):
         j = 0
         while f"encoder.down_blocks.{i}.resnets.{j}.norm1.weight" in sd:
-            h = resnet(sd, f"encoder.down_blocks.{i}.resnets.{j}", h); j += 1
-        d = f"encoder.down_blocks.{i}.downsamplers.0.conv"
-        if d + ".weight" in sd:
-            h = _conv(sd, d, F.pad(h, (0, 1, 0, 1)), stride=2)
-    h = _mid(sd, "encoder.mid_block", h)
-    h = _conv(sd, "encoder.conv_out", _gn_silu(sd, "encoder.conv_norm_out", h), padding=1)
-    moments = _conv(sd, "quant_conv", h)
+            h = resnet(sd, f"encoder.down_blocks.{i}.resnets.{j}", h, taps); j += 1
+        d = f"encoder.down_blocks.{i}.downsamplers.0"
+        if d + ".conv.weight" in sd:
+            h = _tap(taps, d, downsample(sd, d, h))
+    h = _mid(sd, "encoder.mid_block", h, taps)
+    h = _tap(taps, "encoder.conv_out", conv_out(sd, "encoder", h))
+    moments = _tap(taps, "quant_conv", _conv(sd, "quant_conv", h))
     return moments[:, : moments.shape[1] // 2]
 
 
-def decode(sd: SD, z: Tensor) -> Tensor:
+def decode(sd: SD, z: Tensor, taps: Optional[dict] = None) -> Tensor:
     """vae.decode(z).sample (codecs.py:651)."""
     n_blocks = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("decoder.up_blocks."))
-    h = _conv(sd, "post_quant_conv", z)
-    h = _conv(sd, "decoder.conv_in", h, padding=1)
-    h = _mid(sd, "decoder.mid_block", h)
+    h = _tap(taps, "post_quant_conv", _conv(sd, "post_quant_conv", z))
+    h = _tap(taps, "decoder.conv_in", _conv(sd, "decoder.conv_in", h, padding=1))
+    h = _mid(sd, "decoder.mid_block", h, taps)
     for i in range(n_blocks):
         j = 0
         while f"decoder.up_blocks.{i}.resnets.{j}.norm1.weight" in sd:
-            h = resnet(sd, f"decoder.up_blocks.{i}.resnets.{j}", h); j += 1
-        u = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-        if u + ".weight" in sd:
-            h = _conv(sd, u, F.interpolate(h, scale_factor=2.0, mode="nearest"), padding=1)
-    return _conv(sd, "decoder.conv_out", _gn_silu(sd, "decoder.conv_norm_out", h), padding=1)
+            h = resnet(sd, f"decoder.up_blocks.{i}.resnets.{j}", h, taps); j += 1
+        u = f"decoder.up_blocks.{i}.upsamplers.0"
+        if u + ".conv.weight" in sd:
+            h = _tap(taps, u, upsample(sd, u, h))
+    return _tap(taps, "decoder.conv_out", conv_out(sd, "decoder", h))

@@ -13,7 +13,7 @@ eval mode: dropout is the identity and NoiseInjection is a no-op at noise_streng
 from __future__ import annotations
 
 import math
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 import torch.nn.functional as F
@@ -41,15 +41,32 @@ def _gn(sd, n, x, proposed, eps=1e-5):
     return F.group_norm(x, gn_groups(proposed, c), sd[n + ".weight"], sd[n + ".bias"], eps=eps)
 
 
-def attn_block(sd: SD, n: str, x: Tensor) -> Tensor:
-    """AttnBlock, codecs.py:53-89: GroupNorm(32, eps 1e-6), 1x1 q/k/v, softmax(q^T k c^-1/2) over keys, proj_out, residual."""
-    b, c, h, w = x.shape
-    t = F.group_norm(x, gn_groups(32, c), sd[n + ".norm.norm.weight"], sd[n + ".norm.norm.bias"], eps=1e-6)
-    q, k, v = _conv(sd, n + ".q", t), _conv(sd, n + ".k", t), _conv(sd, n + ".v", t)
-    q = q.reshape(b, c, h * w).permute(0, 2, 1)
-    k = k.reshape(b, c, h * w)
-    a = torch.softmax(torch.bmm(q, k) * int(c) ** -0.5, dim=2)
-    o = torch.bmm(v.reshape(b, c, h * w), a.permute(0, 2, 1)).reshape(b, c, h, w)
+# AttnBlock in four steps, every tensor NCHW as the library's taps are read back: q / k / v [b, c, h, w]; the scores after the softmax
+# p [b, n_keys, h, w] (channel j of pixel i: the weight query i gives key j); o = p v [b, c, h, w].
+def attn_qkv(sd: SD, n: str, x: Tensor):
+    t = F.group_norm(x, gn_groups(32, x.shape[1]), sd[n + ".norm.norm.weight"], sd[n + ".norm.norm.bias"], eps=1e-6)
+    return _conv(sd, n + ".q", t), _conv(sd, n + ".k", t), _conv(sd, n + ".v", t)
+
+
+def attn_probs(q: Tensor, k: Tensor) -> Tensor:
+    b, c, h, w = q.shape
+    a = torch.softmax(torch.bmm(q.reshape(b, c, h * w).permute(0, 2, 1), k.reshape(b, c, h * w)) * int(c) ** -0.5, dim=2)
+    return a.permute(0, 2, 1).reshape(b, h * w, h, w)
+
+
+def attn_apply(p: Tensor, v: Tensor) -> Tensor:
+    b, c, h, w = v.shape
+    return torch.bmm(v.reshape(b, c, h * w), p.reshape(b, h * w, h * w)).reshape(b, c, h, w)
+
+
+def attn_block(sd: SD, n: str, x: Tensor, taps: Optional[dict] = None, tap: str = "") -> Tensor:
+    """AttnBlock, codecs.py:53-89: GroupNorm(32, eps 1e-6), 1x1 q/k/v, softmax(q^T k c^-1/2) over keys, proj_out, residual.
+    ``taps[tap + ".q"]`` ... ``".o"``: the four steps' tensors."""
+    q, k, v = attn_qkv(sd, n, x)
+    p = attn_probs(q, k)
+    o = attn_apply(p, v)
+    if taps is not None:
+        taps.update({tap + ".q": q, tap + ".k": k, tap + ".v": v, tap + ".p": p, tap + ".o": o})
     return x + _conv(sd, n + ".proj_out", o)
 
 
@@ -75,37 +92,75 @@ def na2d(q: Tensor, k: Tensor, v: Tensor, kernel_size: int = 7, scale: float | N
     return torch.einsum("bxyhw,bxyhwd->bxyhd", a, vw)
 
 
-def natten_block(sd: SD, n: str, x: Tensor, layout: int = 1, heads: int = 8, kernel_size: int = 7) -> Tensor:
-    """NATTENBlock._forward, codecs.py:116-140: GroupNorm(gn_groups(8, C)) -> qkv Linear (no bias) -> neighbourhood attention ->
-    proj Linear (no bias) -> identity + gamma * (.).  The reference builds q / k / v as [B, heads, H, W, d] (codecs.py:122-124).
-    ``layout`` 1 reads that as intended (7x7 windows over image rows x columns, per head); ``layout`` 2 is what a natten >= 0.20
-    ``na2d`` -- which documents [B, X, Y, heads, d] -- computes from the very same tensors: windows over (head index, image row), the
-    image column playing the part of the head.  Which one a trained checkpoint needs can only be settled against the package."""
-    B, C, H, W = x.shape
+def natten_qkv(sd: SD, n: str, x: Tensor) -> Tensor:
+    """GroupNorm(gn_groups(8, C)) -> qkv Linear (no bias), as [B, 3C, H, W] (channel = which * C + head * d + i)."""
+    t = F.group_norm(x, gn_groups(8, x.shape[1]), sd[n + ".norm.weight"], sd[n + ".norm.bias"]).permute(0, 2, 3, 1)      # B H W C
+    return F.linear(t, sd[n + ".qkv.weight"]).permute(0, 3, 1, 2)
+
+
+def natten_att(qkv: Tensor, layout: int = 1, heads: int = 8, kernel_size: int = 7) -> Tensor:
+    """The neighbourhood attention of NATTENBlock on its qkv tensor [B, 3C, H, W] -> [B, C, H, W] (before proj and gamma)."""
+    B, C3, H, W = qkv.shape
+    C = C3 // 3
     d = C // heads
-    t = F.group_norm(x, gn_groups(8, C), sd[n + ".norm.weight"], sd[n + ".norm.bias"]).permute(0, 2, 3, 1)      # B H W C
-    qkv = F.linear(t, sd[n + ".qkv.weight"]).reshape(B, H, W, 3, heads, d).permute(3, 0, 4, 1, 2, 5)            # 3 B heads H W d
+    qkv = qkv.permute(0, 2, 3, 1).reshape(B, H, W, 3, heads, d).permute(3, 0, 4, 1, 2, 5)                       # 3 B heads H W d
     q, k, v = qkv[0], qkv[1], qkv[2]
     if layout == 1:
         o = na2d(q.permute(0, 2, 3, 1, 4), k.permute(0, 2, 3, 1, 4), v.permute(0, 2, 3, 1, 4), kernel_size).permute(0, 3, 1, 2, 4)
     else:
         o = na2d(q, k, v, kernel_size)                                                                          # dims taken as [B, X, Y, heads, d]
-    o = o.permute(0, 2, 3, 1, 4).reshape(B, H, W, C)                                                            # codecs.py:137
-    o = F.linear(o, sd[n + ".proj.weight"]).permute(0, 3, 1, 2)
+    return o.permute(0, 2, 3, 1, 4).reshape(B, H, W, C).permute(0, 3, 1, 2)                                    # codecs.py:137
+
+
+def natten_block(sd: SD, n: str, x: Tensor, layout: int = 1, heads: int = 8, kernel_size: int = 7, taps: Optional[dict] = None,
+                 tap: str = "") -> Tensor:
+    """NATTENBlock._forward, codecs.py:116-140: GroupNorm(gn_groups(8, C)) -> qkv Linear (no bias) -> neighbourhood attention ->
+    proj Linear (no bias) -> identity + gamma * (.).  The reference builds q / k / v as [B, heads, H, W, d] (codecs.py:122-124).
+    ``layout`` 1 reads that as intended (7x7 windows over image rows x columns, per head); ``layout`` 2 is what a natten >= 0.20
+    ``na2d`` -- which documents [B, X, Y, heads, d] -- computes from the very same tensors: windows over (head index, image row), the
+    image column playing the part of the head.  Which one a trained checkpoint needs can only be settled against the package.
+    ``taps[tap + ".qkv"]``; ``taps[tap + ".att"]`` = gamma * attention, as the library keeps it (proj is linear and has no bias)."""
+    qkv = natten_qkv(sd, n, x)
+    o = natten_att(qkv, layout, heads, kernel_size)
+    if taps is not None:
+        taps[tap + ".qkv"], taps[tap + ".att"] = qkv, o * sd[n + ".gamma"]
+    o = F.linear(o.permute(0, 2, 3, 1), sd[n + ".proj.weight"]).permute(0, 3, 1, 2)
     return x + o * sd[n + ".gamma"]
 
 
-def res_block(sd: SD, n: str, x: Tensor, stride: int = 1, natten_layout: int = 1) -> Tensor:
-    """EncDecResidualBlock._forward, codecs.py:178-209 (eval): silu(norm1(conv1 x)) [-> attn] -> norm2(conv2 .) + identity -> silu."""
-    out = F.silu(_gn(sd, n + ".norm1", _conv(sd, n + ".conv1", x, padding=1, stride=stride), 8))
+def block_act(sd: SD, n: str, h1: Tensor) -> Tensor:
+    return F.silu(_gn(sd, n + ".norm1", h1, 8))
+
+
+def block_close(sd: SD, n: str, h2: Tensor, x: Tensor, res: Optional[Tensor] = None) -> Tensor:
+    """silu(norm2(h2) + identity): identity = x, or downsample.1 of ``res`` (the downsample.0 convolution of x)."""
+    if res is not None:
+        x = _gn(sd, n + ".downsample.1", res, 8)
+    return F.silu(_gn(sd, n + ".norm2", h2, 8) + x)
+
+
+def res_block(sd: SD, n: str, x: Tensor, stride: int = 1, natten_layout: int = 1, taps: Optional[dict] = None) -> Tensor:
+    """EncDecResidualBlock._forward, codecs.py:178-209 (eval): silu(norm1(conv1 x)) [-> attn] -> norm2(conv2 .) + identity -> silu.
+    ``taps``: ``n.h1`` conv1, ``n.act`` its activation where an attention reads it, ``n.mid`` what conv2 reads, ``n.h2`` conv2,
+    ``n.res`` the downsample.0 convolution, ``n`` the output."""
+    h1 = _conv(sd, n + ".conv1", x, padding=1, stride=stride)
+    out = block_act(sd, n, h1)
+    if taps is not None:
+        taps[n + ".h1"] = h1
+        if (n + ".attn.q.weight") in sd or (n + ".attn.qkv.weight") in sd:
+            taps[n + ".act"] = out
     if (n + ".attn.q.weight") in sd:                       # attention='full'
-        out = attn_block(sd, n + ".attn", out)
+        out = attn_block(sd, n + ".attn", out, taps, n)
     elif (n + ".attn.qkv.weight") in sd:                   # attention='natten' with the package present (else: no attention at all)
-        out = natten_block(sd, n + ".attn", out, natten_layout)
-    out = _gn(sd, n + ".norm2", _conv(sd, n + ".conv2", out, padding=1), 8)
-    if (n + ".downsample.0.weight") in sd:
-        x = _gn(sd, n + ".downsample.1", _conv(sd, n + ".downsample.0", x, stride=stride), 8)
-    return F.silu(out + x)
+        out = natten_block(sd, n + ".attn", out, natten_layout, taps=taps, tap=n)
+    h2 = _conv(sd, n + ".conv2", out, padding=1)
+    res = _conv(sd, n + ".downsample.0", x, stride=stride) if (n + ".downsample.0.weight") in sd else None
+    y = block_close(sd, n, h2, x, res)
+    if taps is not None:
+        taps[n + ".mid"], taps[n + ".h2"], taps[n] = out, h2, y
+        if res is not None:
+            taps[n + ".res"] = res
+    return y
 
 
 def rope(x: Tensor, scale: float = math.log(10000.0)) -> Tensor:
@@ -140,42 +195,57 @@ def n_downsamples(sd: SD) -> int:
     return (len(blocks) - 1) // 2
 
 
-def encode(sd: SD, x: Tensor, natten_layout: int = 1) -> Tensor:
+def _tap(taps, name, value):
+    if taps is not None:
+        taps[name] = value
+    return value
+
+
+def encode(sd: SD, x: Tensor, natten_layout: int = 1, taps: Optional[dict] = None) -> Tensor:
     """VQVAE.encode = self.encoder(x), codecs.py:414-443,492-502: 2 residual blocks per downsample (the first with stride 2), one
-    more to internal_dim, a 1x1 conv, then the compress stack conv1x1 -> GroupNorm -> SiLU -> conv3x3."""
+    more to internal_dim, a 1x1 conv, then the compress stack conv1x1 -> GroupNorm -> SiLU -> conv3x3.  ``taps``: every block's
+    tensors (res_block) and the three convolutions of the tail, by state_dict prefix."""
     nd = n_downsamples(sd)
     h = x
     for i in range(nd):
-        h = res_block(sd, f"encoder.{2 * i}", h, stride=2, natten_layout=natten_layout)
-        h = res_block(sd, f"encoder.{2 * i + 1}", h, natten_layout=natten_layout)
-    h = res_block(sd, f"encoder.{2 * nd}", h, natten_layout=natten_layout)
-    h = _conv(sd, f"encoder.{2 * nd + 1}", h)
-    h = _conv(sd, f"encoder.{2 * nd + 2}", h)
-    h = F.silu(_gn(sd, f"encoder.{2 * nd + 3}", h, 2))
-    return _conv(sd, f"encoder.{2 * nd + 5}", h, padding=1)
+        h = res_block(sd, f"encoder.{2 * i}", h, stride=2, natten_layout=natten_layout, taps=taps)
+        h = res_block(sd, f"encoder.{2 * i + 1}", h, natten_layout=natten_layout, taps=taps)
+    h = res_block(sd, f"encoder.{2 * nd}", h, natten_layout=natten_layout, taps=taps)
+    h = _tap(taps, f"encoder.{2 * nd + 1}", _conv(sd, f"encoder.{2 * nd + 1}", h))
+    h = _tap(taps, f"encoder.{2 * nd + 2}", _conv(sd, f"encoder.{2 * nd + 2}", h))
+    return _tap(taps, f"encoder.{2 * nd + 5}", compress_out(sd, nd, h))
 
 
-def decode(sd: SD, z: Tensor, natten_layout: int = 1) -> Tensor:
-    """VQVAE.decode -> Decoder.forward at noise_strength 0, codecs.py:245-316,523-525."""
+def compress_out(sd: SD, nd: int, h: Tensor) -> Tensor:
+    return _conv(sd, f"encoder.{2 * nd + 5}", F.silu(_gn(sd, f"encoder.{2 * nd + 3}", h, 2)), padding=1)
+
+
+def expand_out(sd: SD, i: int, h: Tensor, emb: int) -> Tensor:
+    """decoder.layers.{i+1 .. i+3}: GroupNorm(gn_groups(emb, C)) -> SiLU -> conv1x1."""
+    return _conv(sd, f"decoder.layers.{i + 3}", F.silu(_gn(sd, f"decoder.layers.{i + 1}", h, emb)))
+
+
+def decode(sd: SD, z: Tensor, natten_layout: int = 1, taps: Optional[dict] = None) -> Tensor:
+    """VQVAE.decode -> Decoder.forward at noise_strength 0, codecs.py:245-316,523-525.  ``taps``: by ``decoder.layers.<index>``; a
+    convolution followed by SiLU is recorded after the SiLU, the PixelShuffle under its own index."""
     nd = n_downsamples(sd)
     L = "decoder.layers."
     i = 0
     h = z
     if (L + "0.q_proj.weight") in sd:
-        h = spatial_nonlocal_attention(sd, L + "0", h); i = 1
-    h = _conv(sd, L + str(i), h)
-    emb = z.shape[1]
-    h = F.silu(_gn(sd, L + str(i + 1), h, emb))
-    h = _conv(sd, L + str(i + 3), h)
-    h = res_block(sd, L + str(i + 5), h, natten_layout=natten_layout)   # i+4 is a NoiseInjection
+        h = _tap(taps, L + "0", spatial_nonlocal_attention(sd, L + "0", h)); i = 1
+    h = _tap(taps, L + str(i), _conv(sd, L + str(i), h))
+    h = _tap(taps, L + str(i + 3), expand_out(sd, i, h, z.shape[1]))
+    h = res_block(sd, L + str(i + 5), h, natten_layout=natten_layout, taps=taps)   # i+4 is a NoiseInjection
     i += 6
     for _ in range(nd):
-        h = F.pixel_shuffle(F.silu(_conv(sd, L + str(i), h, padding=1)), 2)      # conv, SiLU, PixelShuffle(2), NoiseInjection
-        h = res_block(sd, L + str(i + 4), h, natten_layout=natten_layout)
-        h = res_block(sd, L + str(i + 6), h)                                       # i+5 is a NoiseInjection
+        h = _tap(taps, L + str(i), F.silu(_conv(sd, L + str(i), h, padding=1)))     # conv, SiLU, PixelShuffle(2), NoiseInjection
+        h = _tap(taps, L + str(i + 2), F.pixel_shuffle(h, 2))
+        h = res_block(sd, L + str(i + 4), h, natten_layout=natten_layout, taps=taps)
+        h = res_block(sd, L + str(i + 6), h, taps=taps)                              # i+5 is a NoiseInjection
         i += 7
-    h = F.silu(_conv(sd, L + str(i + 1), h, padding=1))   # i is a NoiseInjection
-    return _conv(sd, L + str(i + 4), h, padding=1)        # i+2 SiLU, i+3 NoiseInjection
+    h = _tap(taps, L + str(i + 1), F.silu(_conv(sd, L + str(i + 1), h, padding=1)))   # i is a NoiseInjection
+    return _tap(taps, L + str(i + 4), _conv(sd, L + str(i + 4), h, padding=1))        # i+2 SiLU, i+3 NoiseInjection
 
 
 def residual_vq(codebooks: Tensor, x: Tensor):

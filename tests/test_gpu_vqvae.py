@@ -149,3 +149,78 @@ def test_full_midi_inpainting_shape_vs_oracle_and_batch_independence():
     for k in (0, 33, 63):
         assert rel_l2(y[k:k + 1].cpu(), m.decode(zq[k:k + 1].to(DEV)).cpu()) < 1e-5
     assert torch.equal(m.decode(zq.to(DEV)), y)                                    # bit-reproducible
+
+
+# ---- fc_rvq_quantize by itself -------------------------------------------------------------------------------------------------------
+RVQ_N = 1031                # vectors: more than one 256-thread workgroup, and a ragged last one
+
+
+def _rvq_gpu(z, cbs):
+    """z [N, D], codebooks [L, K, D] -> (z_q [N, D], indices [N, L]) through the C ABI (the kernel's boundary layout is [B, D, hw])."""
+    from flocoder_amd import _binding as B
+    n, d = z.shape
+    zt = z.t().contiguous().to(DEV)
+    cb = cbs.contiguous().to(DEV)
+    zq = torch.full_like(zt, float("nan"))
+    idx = torch.full((n, cbs.shape[0]), -1, dtype=torch.int64, device=DEV)
+    B.check(B.lib().fc_rvq_quantize(B.ptr(zt), B.ptr(cb), B.ptr(zq), B.ptr(idx), 1, d, n, cbs.shape[1], cbs.shape[0], B.current_stream(zt.device)))
+    torch.cuda.synchronize()
+    return zq.t().cpu(), idx.cpu()
+
+
+def _rvq_fp64(z, cbs):
+    """The same in fp64, first index on ties (torch.argmin); also, per vector, the smallest relative gap over the levels between the
+    best squared distance and the next larger one (copies of the best codeword tie exactly, in fp32 as in fp64, and are no gap)."""
+    r, out, idx = z.double().clone(), torch.zeros_like(z, dtype=torch.float64), []
+    gap = torch.full((z.shape[0],), float("inf"), dtype=torch.float64)
+    for cb in cbs.double():
+        d = ((r[:, None, :] - cb[None, :, :]) ** 2).sum(-1)
+        i = d.argmin(dim=1)
+        best = d.min(dim=1, keepdim=True).values
+        nxt = d.masked_fill(d <= best, float("inf")).min(dim=1).values
+        gap = torch.minimum(gap, (nxt - best[:, 0]) / nxt)
+        r, out = r - cb[i], out + cb[i]
+        idx.append(i)
+    return out, torch.stack(idx, dim=-1), gap
+
+
+@pytest.mark.parametrize("D,K,L", [(4, 96, 4), (1, 32, 2), (3, 64, 3), (8, 512, 4), (16, 256, 4)])
+def test_rvq_quantize_alone_vs_fp64(D, K, L):
+    """(4,96,4): the configured size; (8,512,4) and (16,256,4): exactly 64 KB of codebooks in LDS.  Indices are compared on every vector
+    whose best and second-best fp64 distances differ by at least 1e-5 relative at every level (fp32 distances cannot be asked to order
+    closer pairs); at most 1 % may be left out."""
+    g = torch.Generator().manual_seed(100 * D + L)
+    z = torch.randn(RVQ_N, D, generator=g)
+    cbs = torch.stack([torch.randn(K, D, generator=g) * 0.5 ** l for l in range(L)])
+    zq, idx = _rvq_gpu(z, cbs)
+    ref_q, ref_idx, gap = _rvq_fp64(z, cbs)
+    sure = gap >= 1e-5
+    print(f"\n[rvq D={D} K={K} L={L}] {int((~sure).sum())} of {RVQ_N} vectors left out; index mismatches among the rest "
+          f"{int((idx[sure] != ref_idx[sure]).any(dim=1).sum())}; z_q rel-L2 {rel_l2(zq[sure], ref_q[sure]):.2e}")
+    assert int((~sure).sum()) <= RVQ_N // 100
+    assert idx.min() >= 0 and idx.max() < K
+    assert torch.equal(idx[sure], ref_idx[sure])
+    assert rel_l2(zq[sure], ref_q[sure]) < 1e-6                                   # L fp32 additions of fp32 codewords
+    assert torch.isfinite(zq).all()
+
+
+def test_rvq_quantize_takes_the_lower_index_of_a_duplicated_codeword():
+    g = torch.Generator().manual_seed(5)
+    D, K, L = 4, 96, 4
+    cbs = torch.stack([torch.randn(K, D, generator=g) * 0.5 ** l for l in range(L)])
+    cbs[0, 40] = cbs[0, 7]
+    cbs[2, 90] = cbs[2, 0]
+    z = torch.randn(RVQ_N, D, generator=g)
+    z[::5] = cbs[0, 7] + 0.01 * torch.randn(len(z[::5]), D, generator=g)          # many vectors whose nearest codeword is the duplicated one
+    _, idx = _rvq_gpu(z, cbs)
+    _, ref_idx, gap = _rvq_fp64(z, cbs)
+    assert int((idx[:, 0] == 7).sum()) >= RVQ_N // 5 and not (idx[:, 0] == 40).any() and not (idx[:, 2] == 90).any()
+    assert (ref_idx[:, 2] == 0).any()
+    sure = gap >= 1e-5
+    assert int((~sure).sum()) <= RVQ_N // 100 and torch.equal(idx[sure], ref_idx[sure])
+
+
+def test_rvq_quantize_refuses_codebooks_beyond_64_kb():
+    z = torch.zeros(8, 16)
+    with pytest.raises(ValueError, match="codebooks exceed 64 KB"):
+        _rvq_gpu(z, torch.zeros(4, 257, 16))
