@@ -36,3 +36,6 @@ def apply_runtime_defaults(workload: str = "sampling") -> bool:
 
 from .unet import Unet  # noqa: F401,E402
 from .ot import OTPlanSampler, compute_ot_pairing, compute_ot_plan, sample_plan  # noqa: F401,E402
+from .codebook_analysis import CodebookUsageTracker, calc_usage_stats  # noqa: F401,E402
+from .metrics import calc_note_metrics  # noqa: F401,E402
+from .sampling import evaluate_model  # noqa: F401,E402

@@ -19,6 +19,7 @@ FC_JACOBIAN_IDENTITY, FC_JACOBIAN_EXACT = 0, 1
 FC_SDE_EULER_MARUYAMA, FC_SDE_HEUN = 0, 1
 FC_LL_MAX_PROBES = 64
 FC_PROBE_RADEMACHER, FC_PROBE_GAUSSIAN = 0, 1
+FC_HIST_LDS_BINS = 8192
 TILE_AUTO = -1
 TILES = {"M128N32": 0, "M128N64": 1, "M64N32K2": 2, "M32N32K4": 3, "M64N64K2": 4, "M256N64": 5}
 
@@ -100,6 +101,8 @@ SIGNATURES = {
     "fc_unet_integrate_sde": (_i, [_vp, _i, _vp, _i, _i, _i, _pf, _i, _f, _vp, _f, _vp, _i, _f, C.c_uint64, _vp, _vp, _vp]),
     "fc_ode_normal_field": (_i, [_vp, C.c_uint64, _i64, _vp, _i, _i64, _vp]),
     "fc_inpaint_masks": (_i, [_vp, _vp, C.c_uint64, _vp, _i, _i, _i, _pi, C.POINTER(C.c_double), _i, _i, _vp]),
+    "fc_note_confusion": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _f, C.c_double, _i, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fc_index_histogram": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "fc_debug_unet_guided_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "fc_unet_arena_serial": (C.c_uint64, [_vp]),
     "fc_unet_class_param_range": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -8,6 +8,9 @@
   ``$FLOCODER_FID_INCEPTION``) mapping uint8 images [B,3,H,W] to features [B,F] -- torchmetrics downloads its weights, this build
   never touches the network and raises FileNotFoundError without one;
 * ``compute_sample_metrics`` (metrics.py:493-555) -- the same dictionary of numbers;
+* ``calc_note_metrics`` (metrics.py:362-455, with ``targ_pred_mask_to_rgb`` / ``mask_to_rgb``, 330-340) -- onset / sustain sensitivity,
+  specificity, precision and F1 of a piano roll against its target, and their images, from one streaming pass on the device
+  (``fc_note_confusion``): exact int64 counts, ratios in fp64 on the host; ``region=`` restricts it to the pixels that were inpainted;
 * ``bits_per_dim`` -- the flow's log-likelihood (``sampling.log_likelihood``) as bits per latent dimension (no upstream counterpart);
   ``bits_per_dim_stderr`` -- its standard error from a K-probe call's ``logp_stderr``.
 """
@@ -34,6 +37,96 @@ def g2rgb(gf_img, keep_gray=False):
     if keep_gray:
         return (gf > 0.5).float().unsqueeze(-3).repeat(1, 3, 1, 1)
     return torch.stack([(gf >= 0.75).float(), (torch.abs(gf - 0.5) < 0.25).float(), torch.zeros_like(gf)], dim=-3)
+
+
+def targ_pred_mask_to_rgb(t_mask, p_mask):
+    """metrics.py:330-334 -- target mask on red, prediction mask on green, blue zero: [H,W] x 2 -> [3,H,W]."""
+    return torch.cat([t_mask.unsqueeze(0), p_mask.unsqueeze(0), torch.zeros_like(t_mask).unsqueeze(0)], dim=0)
+
+
+def mask_to_rgb(mask, color=(1, 1, 1)):
+    """metrics.py:336-340 -- [B,H,W] mask -> [B,3,H,W] in `color` (white by default)."""
+    rgb = torch.zeros((mask.shape[0], 3, mask.shape[1], mask.shape[2]), device=mask.device)
+    for i in range(3):
+        rgb[:, i, :, :] = mask * color[i]
+    return rgb
+
+
+NOTE_NAMES = ('onset', 'sustain')
+
+
+def note_ratios(tp, tn, fp, fn):
+    """metrics.py:433-438 on exact totals, in fp64: Python ints give Python floats, int64 tensors give float64 tensors."""
+    tp, tn, fp, fn = (v.double() if torch.is_tensor(v) else v for v in (tp, tn, fp, fn))
+    return {'sensitivity': tp / (tp + fn + 1e-8), 'specificity': tn / (tn + fp + 1e-8), 'precision': tp / (tp + fp + 1e-8),
+            'f1': 2 * tp / (2 * tp + fp + fn + 1e-8)}
+
+
+def note_confusion(pred, target, threshold=0.4, minval=None, maxval=None, keep_gray=False, region=None, images=False):
+    """The device half of ``calc_note_metrics`` (``fc_note_confusion``): counts int64 [2, B, 4] (onset | sustain; tp, tn, fp, fn per
+    sample), still on the device and not waited for, plus with ``images`` the planes ``masks`` [2, 4, B, H, W] and ``overlay``
+    [2, B, 3, H, W] (else None, None)."""
+    if not (pred.is_cuda and target.is_cuda):
+        raise RuntimeError("flocoder_amd.metrics.calc_note_metrics runs on MI355X (gfx950) only; there is no CPU path")
+    if pred.dim() != 4 or target.dim() != 4 or pred.shape[0] != target.shape[0] or pred.shape[2:] != target.shape[2:]:
+        raise ValueError(f"calc_note_metrics: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be [B,C,H,W] of one B, H, W")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError("calc_note_metrics: pred and target must be float32")
+    bsz, _, h, w = pred.shape
+    pred = pred if pred.is_contiguous() else pred.contiguous()
+    target = target if target.is_contiguous() else target.contiguous()
+    if region is not None:
+        if not region.is_cuda or tuple(region.shape) != (bsz, 1, h, w):
+            raise ValueError(f"calc_note_metrics: region must be a device tensor [B,1,H,W] = {(bsz, 1, h, w)}")
+        region = region.float().contiguous()
+    dev = pred.device
+    counts = torch.empty(2, bsz, 4, dtype=torch.int64, device=dev)
+    ws = torch.empty(4, dtype=torch.int32, device=dev)
+    masks = torch.empty(2, 4, bsz, h, w, dtype=torch.float32, device=dev) if images else None
+    overlay = torch.empty(2, bsz, 3, h, w, dtype=torch.float32, device=dev) if images else None
+    with torch.cuda.device(dev):
+        B.check(B.lib().fc_note_confusion(B.ptr(pred), pred.shape[1], B.ptr(target), target.shape[1], B.ptr(region), bsz, h, w,
+                                          float(threshold), 0.0 if minval is None else float(minval), int(minval is None),
+                                          0.0 if maxval is None else float(maxval), int(maxval is None), int(bool(keep_gray)),
+                                          B.ptr(ws), B.ptr(counts), B.ptr(masks), B.ptr(overlay), B.current_stream(dev)))
+    return counts, masks, overlay
+
+
+def calc_note_metrics(pred, target, threshold=0.4, minval=None, maxval=None, keep_gray=False, debug=False, *, region=None,
+                      per_sample=False, images=True):
+    """metrics.py:362-455 -- onset / sustain sensitivity, specificity, precision and F1 of a piano roll against its target, and the
+    images that go with them, from one streaming pass on the device (``fc_note_confusion``: upstream's g2rgb, min / max of the whole
+    converted target, clamp, rescale and ``> threshold`` in fp32 and in its order of operations) instead of a Python loop over the batch.
+    Returns ``(metrics, metric_images)`` with upstream's keys: ``{onset,sustain}_{sensitivity,specificity,precision,f1}`` as Python
+    floats and ``{onset,sustain}_{tp,tn,fp,fn,targpred}`` as [B,3,H,W] tensors (the four masks are broadcast views of the [B,H,W] planes
+    the kernel wrote, where upstream repeats them).
+
+    Differences, all deliberate: the counts are exact int64 totals and the ratios are formed from them on the host in fp64, where
+    upstream sums in fp32 (not exact above 2^24 pixels) and divides in fp32 -- the two agree to fp32 rounding; ``minval`` / ``maxval``
+    given as tensors are read as numbers; the rescaling is an IEEE division by the range, as torch does it on the CPU and, with a
+    derived range, on the GPU (given two Python numbers, torch's GPU kernel multiplies by the reciprocal instead, one rounding away).  Keyword-only extensions: ``region`` [B,1,H,W] restricts every count (and image) to the
+    pixels where region > 0.5, e.g. the part of a roll that was inpainted; ``per_sample=True`` adds ``metrics['per_sample']`` (the
+    eight ratios as [B] float64 device tensors) and ``metrics['counts']`` (int64 [2,B,4]: onset | sustain; tp, tn, fp, fn);
+    ``images=False`` skips the image writes and returns ``{}``.  One device-to-host copy (the 2 x 4 totals) ends the call."""
+    if debug:
+        print(f"calc_note_metrics: pred.shape = {tuple(pred.shape)}, target.shape = {tuple(target.shape)}")
+    counts, masks, overlay = note_confusion(pred, target, threshold, minval, maxval, keep_gray, region, images)
+    totals = counts.sum(dim=1).tolist()
+    metrics, metric_images = {}, {}
+    for i, name in enumerate(NOTE_NAMES):
+        tp, tn, fp, fn = totals[i]
+        if debug:
+            print(f" {name}: tp, tn, fp, fn =", [tp, tn, fp, fn])
+        metrics.update({f'{name}_{k}': v for k, v in note_ratios(tp, tn, fp, fn).items()})
+        if images:
+            bsz, h, w = masks.shape[2:]
+            metric_images.update({f'{name}_{k}': masks[i, q].unsqueeze(1).expand(bsz, 3, h, w) for q, k in enumerate(('tp', 'tn', 'fp', 'fn'))})
+            metric_images[f'{name}_targpred'] = overlay[i]
+    if per_sample:
+        metrics['counts'] = counts
+        metrics['per_sample'] = {f'{name}_{k}': v for i, name in enumerate(NOTE_NAMES)
+                                 for k, v in note_ratios(*counts[i].unbind(dim=1)).items()}
+    return metrics, metric_images
 
 
 def to_uint8(x):

@@ -880,6 +880,73 @@ def sampler(model, codec, method='rk4', batch_size=256, n_steps=100, cond=None, 
 
 
 @torch.no_grad()
+def evaluate_model(model, codec, epoch, target_latents, cond=None, batch_size=256, n_classes=0, latent_shape=(4, 16, 16), method='rk4',
+                   n_steps=None, is_midi=False, keep_gray=False, tag="", cb_tracker=None, cfg_strength=3.0, output_dir="./",
+                   use_wandb=False, pre_encoded=True, source=None, mask_pixels=None, debug=False, *, return_images=False,
+                   inception=None, init_image=None, init_strength=0.0):
+    """sampling.py:233-322: one epoch's evaluation -- sample, decode, score -- in upstream's order of work: ``model.eval()`` /
+    ``codec.eval()``; ``sampler`` with ``n_classes=0`` and the latent shape of ``target_latents``; decode ``target_latents[:batch_size]``;
+    ``compute_sample_metrics``; when the codec has a ``vq`` and ``cb_tracker`` is given, the indices of all of ``target_latents`` go to
+    the tracker as "val" and those of the generated latents as "gen" (``cb_tracker.analyze(codec, epoch)`` then gives the statistics
+    upstream sends to wandb); ``model.train()``; the metrics dictionary is returned.  Everything stays on the device until the
+    dictionary's numbers are read.  It composes ``sampler``, ``decode_latents``, ``metrics.compute_sample_metrics`` and
+    ``metrics.calc_note_metrics`` and adds no sampler logic of its own.
+
+    Differences from upstream:
+    * ``n_steps=None`` means 100, which is what upstream effectively runs: it never forwards its own ``n_steps`` to ``sampler``, whose
+      default is 100.  A value given here IS forwarded.
+    * ``use_wandb`` defaults to False and True raises: wandb logging and the plots of the codebook analysis are out of scope.
+    * No image grids are written (``tag`` and ``output_dir`` are accepted and unused).  ``return_images=True`` returns
+      ``(metrics, images)`` with upstream's image dictionary instead: pred / target latents and decodes, the source and its decode when
+      ``source`` is given, ``mask_latents`` / ``mask_pixels`` when they are.
+    * With ``is_midi=True`` the note metrics of ``decoded_pred`` against ``decoded_target`` (as ``compute_sample_metrics`` leaves them:
+      it rescales ``decoded_pred`` to the target's range in place, as upstream) are added under ``note/<key>``; if ``mask_pixels``
+      [B,1,H,W] is given as well, the same metrics restricted to the pixels that were masked (mask > 0.5) under ``note_masked/<key>``.
+    * Keyword-only ``inception`` goes to ``compute_sample_metrics`` (FID needs a local feature extractor), ``init_image`` /
+      ``init_strength`` to ``sampler``.
+    * ``gc.collect()`` / ``torch.cuda.empty_cache()`` are not called: nothing here bounces through the host that they would free."""
+    if use_wandb:
+        raise NotImplementedError("evaluate_model: wandb logging and image grids are out of scope; log the returned dictionary")
+    from . import metrics as M
+    model.eval(), codec.eval()
+    latent_shape = target_latents.shape[-3:]
+    pred_latents, decoded_pred, nfe = sampler(model, codec, method=method, batch_size=batch_size, n_steps=100 if n_steps is None else n_steps,
+                                              cond=cond, n_classes=0, latent_shape=latent_shape, cfg_strength=cfg_strength, is_midi=is_midi,
+                                              keep_gray=keep_gray, source=source, init_image=init_image, init_strength=init_strength)
+    decoded_target = decode_latents(codec, target_latents[:batch_size], is_midi, keep_gray)
+    metrics = M.compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_target, inception=inception)
+
+    if hasattr(codec, 'vq') and cb_tracker is not None:
+        for name, lat in (("val", target_latents), ("gen", pred_latents)):
+            if hasattr(codec.vq, "quantize_nchw"):                      # same vectors in the same order, without the two transposes
+                _, indices, _ = codec.vq.quantize_nchw(lat)
+            else:
+                _, indices, _ = codec.vq(lat.permute(0, 2, 3, 1).reshape(-1, lat.shape[1]))
+            cb_tracker.update_counts(name, indices.reshape(-1, indices.shape[-1]))
+
+    if mask_pixels is not None:
+        mask_pixels = mask_pixels[:batch_size].float()
+    if is_midi:
+        metrics.update({f'note/{k}': v for k, v in M.calc_note_metrics(decoded_pred, decoded_target, keep_gray=keep_gray, images=False)[0].items()})
+        if mask_pixels is not None:
+            region = mask_pixels if mask_pixels.dim() == 4 else mask_pixels.unsqueeze(1)
+            masked = M.calc_note_metrics(decoded_pred, decoded_target, keep_gray=keep_gray, region=region, images=False)[0]
+            metrics.update({f'note_masked/{k}': v for k, v in masked.items()})
+
+    images = None
+    if return_images:
+        images = {'pred_latents': pred_latents, 'target_latents': target_latents, 'decoded_pred': decoded_pred, 'decoded_target': decoded_target}
+        if source is not None:
+            images.update({'source_latents': source[:batch_size], 'decoded_source': decode_latents(codec, source[:batch_size], is_midi, keep_gray)})
+        if cond and isinstance(cond, dict) and cond.get('mask_cond') is not None:
+            images['mask_latents'] = cond['mask_cond'][:batch_size]
+        if mask_pixels is not None:
+            images['mask_pixels'] = mask_pixels
+    model.train()
+    return (metrics, images) if return_images else metrics
+
+
+@torch.no_grad()
 def sample_many(model, shape, batches, method="euler", n_steps=64, cfg_strength=0.0, in_flight=2):
     """Throughput mode for callers that generate MANY batches (the 50 k samples of an FID run, evaluate_model / generate_samples loops around
     sampling.py:186-229): ``batches`` is a sequence of ``(cond, source)`` pairs, one per call of ``generate_latents`` the reference would

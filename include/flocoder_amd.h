@@ -337,6 +337,35 @@ int fc_ode_normal_field(float* out_dev, uint64_t seed, int64_t draw_index, const
 int fc_inpaint_masks(float* masks_out_dev, int* types_out_dev, uint64_t seed, const int64_t* sample_ids_dev, int batch, int height, int width,
                      const int* choice_types_host, const double* probs_host, int n_choices, int forced_type, void* stream);
 
+/* Confusion counts of a piano roll against its target (replace flocoder/metrics.py:362-455 calc_note_metrics up to the ratios, which
+ * the caller forms from these exact totals).  pred_dev [batch, pred_channels, height, width] and target_dev [batch, target_channels,
+ * height, width] fp32, channels 1 or 3 each on its own: 3 is taken as it is, 1 goes through g2rgb (red = gf >= 0.75, green =
+ * |gf - 0.5| < 0.25, blue = 0; keep_gray != 0: gf > 0.5 on all three).  Per pixel, for channel 0 (onset) and 1 (sustain), in fp32 and
+ * upstream's operation order:  t = ((target - lo) / range) > threshold,  p = ((clamp(pred, lo, hi) - lo) / range) > threshold  with
+ * torch's clamp (NaN stays NaN and compares false).  lo = minval and hi = maxval rounded to fp32, or with derive_min / derive_max != 0 the
+ * min / max of the WHOLE converted target (NaN if it holds one, as torch), found by a first launch; range = float(maxval - minval) when
+ * both are given, hi - lo in fp32 otherwise.  An all-black target makes range 0: every comparison is false, every pixel a true negative.
+ * region_dev: NULL or [batch, 1, height, width] fp32; a pixel with region <= 0.5 is counted nowhere and is 0 in every image.
+ * ws_dev: 16 bytes of caller-owned scratch.  counts_out_dev [2][batch][4] int64 (onset | sustain; tp, tn, fp, fn per sample) is
+ * zeroed and written by the call.  masks_out_dev [2][4][batch][height*width] fp32 (tp, tn, fp, fn as 0 / 1) and overlay_out_dev
+ * [2][batch][3][height*width] (target bit, pred bit, 0) are both given or both NULL.  16-byte loads and stores when height*width is a
+ * multiple of 4 and every tensor pointer is 16-byte aligned, otherwise one pixel per lane: a misaligned base is handled.  Channels other
+ * than 1 / 3 -> FC_E_SHAPE.  Two memsets and one or two launches on `stream`; no allocation, no host wait. */
+int fc_note_confusion(const float* pred_dev, int pred_channels, const float* target_dev, int target_channels, const float* region_dev, int batch,
+                      int height, int width, float threshold, double minval, int derive_min, double maxval, int derive_max, int keep_gray,
+                      void* ws_dev, int64_t* counts_out_dev, float* masks_out_dev, float* overlay_out_dev, void* stream);
+
+/* Codebook usage (replace the counting of flocoder/codebook_analysis.py:28-44): indices_dev [n][levels] int64, the layout
+ * fc_rvq_quantize writes; counts_inout_dev [levels][codebook_size] int64 is ADDED to, so a caller accumulates over calls;
+ * keys_out_dev NULL or [n] int64, key = sum_l index_l codebook_size^l (FC_E_SHAPE when codebook_size^levels overflows int64).
+ * A row with an index outside [0, codebook_size) is counted at no level, gets key -1 and adds one to *bad_rows_inout_dev (device int64,
+ * required): the caller reads that word when it next reads the counts.  levels * codebook_size <= FC_HIST_LDS_BINS: 32-bit bins in LDS
+ * per workgroup, one 64-bit global atomic per non-zero bin at the end; above: one 64-bit global atomic per index.  One launch on
+ * `stream` (none for n == 0); no allocation, no host wait. */
+#define FC_HIST_LDS_BINS 8192
+int fc_index_histogram(const int64_t* indices_dev, int64_t n, int levels, int codebook_size, int64_t* counts_inout_dev, int64_t* keys_out_dev,
+                       int64_t* bad_rows_inout_dev, void* stream);
+
 /* ---- debug / test hooks: not part of the drop-in surface --------------------------------------- */
 /* After an exact-form fc_unet_integrate_guided call: device pointers to the last stage's input state [B,C,H,W], its scaled time rows [B],
  * its w and q = (dv/dx)^T w, while the plan that ran it stands. */
