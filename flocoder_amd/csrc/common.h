@@ -246,6 +246,8 @@ bool linattn_fused_supported(int n, int C, int heads);
 int linattn_fused_tiles(int n);
 float linattn_fused_nt(int n, int C);
 int linattn_fused_launch(const LaArgs& a, hipStream_t s);
+void linattn_route_log_set(bool on);                // diagnostics: the instantiations every fused fast-path launch takes (linattn_fused.hip)
+std::string linattn_route_log_get();
 bool linattn_fused_meeting_ok(int B, int n, int C);   // may LaArgs::gran be set: the apply launch's whole grid is resident at this shape
 // The whole Residual(PreNorm(LinearAttention)) module in two launches, a workgroup per (sample, head) then per sample (n <= 64 positions)
 int linattn_sample_init();

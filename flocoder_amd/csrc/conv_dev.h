@@ -141,6 +141,9 @@ constexpr int geo_TB(int k) { return 1 + ((k >> 2) & 1); }
 constexpr int geo_TWl(int k) { return (k >> 3) & 7; }
 constexpr int geo_cpg(int k) { return 1 << ((k >> 6) & 15); }
 constexpr int geo_Tst(int k) { return (k >> 10) & 63; }
+// The masks of the first convolution of a ResnetBlock (statistics of the raw output; in the up path also the concatenated source and the
+// fused res_conv output) that may carry a key as well: no tail, so the key is the OUTPUT geometry, which is that of the Block's closing launch
+constexpr bool geo_conv1_mask(int FL) { return (FL & ~(FL_W4 | FL_STAMP)) == FL_STATS || (FL & ~(FL_W4 | FL_STAMP)) == (FL_STATS | FL_CAT | FL_RES); }
 
 template <int WM, int WN, int WK, int MT, int NT, int FL = FL_ALL, int GEO = 0>
 __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT][NT], f32x16 (&accr)[MT][NT], float* smem, int tid, int lane,
@@ -156,8 +159,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
     const int wk = wave % WK, wn = (wave / WK) % WN, wm = wave / (WK * WN);
     // the tile geometry: constants of the flavour (GEO != 0), else the launch's values
     constexpr bool GEOC = GEO != 0;
-    static_assert(!GEOC || (FL != FL_ALL && (FL & FL_FIN) && (FL & FL_STATS) && !(FL & (FL_MULTI | FL_POST | FL_RES))), "a geometry key belongs to a lean Block-closing flavour");
-    static_assert(!GEOC || (geo_Tst(GEO) >= 1 && geo_TB(GEO) * (geo_cpg(GEO) >= BN ? 1 : BN / geo_cpg(GEO)) * geo_Tst(GEO) * 2 <= 512), "one granule per thread");
+    // GEO1: the key on a Block-OPENING (conv1) flavour -- no tail, so all it fixes is the statistics pass and the store decode; the launch path
+    // (conv_pipe.hip conv1_geo_key) has also checked a plain stride-1 output: out_sh = out_oy = out_ox = 0
+    constexpr bool GEO1 = GEOC && !(FL & FL_FIN);
+    static_assert(!GEOC || (FL != FL_ALL && (FL & FL_STATS) && !(FL & (FL_MULTI | FL_POST)) && ((FL & FL_FIN) ? !(FL & FL_RES) : geo_conv1_mask(FL))),
+                  "a geometry key belongs to a lean Block-closing flavour or to a lean conv1 flavour");
+    static_assert(!GEOC || geo_Tst(GEO) >= 1, "statistics slots of the key");
+    static_assert(!GEOC || GEO1 || geo_TB(GEO) * (geo_cpg(GEO) >= BN ? 1 : BN / geo_cpg(GEO)) * geo_Tst(GEO) * 2 <= 512, "one granule per thread");
     const int g_TB = GEOC ? geo_TB(GEO) : p.TB;
     const int g_TWl = GEOC ? geo_TWl(GEO) : p.TWl;
     const int g_tbsh = GEOC ? geo_log2(BM / geo_TB(GEO)) : p.TWl + p.THl;            // log2 of a sample's pixels in the tile
@@ -220,6 +228,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
         const int m = (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
         const int tw = m & (TW - 1), th = (m >> g_TWl) & (TH - 1), tb = m >> g_tbsh;
         const int b = b0 + tb;
+        if (GEO1) return b < a.B ? (b * a.H + y0 + th) * a.W + x0 + tw : -1;
         return b < a.B ? (b * (a.H << a.out_sh) + ((y0 + th) << a.out_sh) + a.out_oy) * (a.W << a.out_sh) + ((x0 + tw) << a.out_sh) + a.out_ox : -1;
     };
     if (FL & FL_STAMP) conv_stamp(p, 6);
@@ -617,7 +626,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
                 const int m = i / Q4, c4 = (i - m * Q4) * 4, n = n0 + c4;
                 const int tw = m & (TW - 1), th = (m >> g_TWl) & (TH - 1), tb = m >> g_tbsh;
                 const int b = b0 + tb;
-                if (b < a.B && n < Cout) {
+                if (GEO1) {       // whole column tiles, plain output
+                    if (b < a.B) *reinterpret_cast<float4*>(gout + (size_t)((b * a.H + y0 + th) * a.W + x0 + tw) * Cout + n) = *reinterpret_cast<const float4*>(ot + m * OS + c4);
+                } else if (b < a.B && n < Cout) {
                     const float4 v = *reinterpret_cast<const float4*>(ot + m * OS + c4);
                     *reinterpret_cast<float4*>(gout + (size_t)((b * (a.H << a.out_sh) + ((y0 + th) << a.out_sh) + a.out_oy) * (a.W << a.out_sh) + ((x0 + tw) << a.out_sh) + a.out_ox) * Cout + n) = v;
                 }

@@ -110,8 +110,12 @@ __device__ __forceinline__ void split_bf16x4(const f32x4& x, uint2& hi, uint2& l
 // path checks it), and window elements a thread of the run-time-geometry form may hold
 constexpr int kFinGeomGroups = 4, kWWSlots = 8;
 
-template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEO = 0>
+template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEOF = 0, int GEOK1 = 0>
 __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev p_kernarg) {
+    // the geometry key: GEOF on a Block-closing flavour, GEOK1 on a conv1 flavour (two template arguments, so that the route record and
+    // the symbol names say which kind of key a launch carries); below it is one key, and FL_FIN tells the kinds apart
+    static_assert(!(GEOF && GEOK1) && (!GEOF || (FL & FL_FIN)) && (!GEOK1 || !(FL & FL_FIN)), "one key per flavour, of its own kind");
+    constexpr int GEO = GEOF != 0 ? GEOF : GEOK1;
     ConvDev p;
     conv_params_from_lanes(p);       // p_kernarg itself is never touched: see conv_dev.h
     constexpr int NTHR = 256 + 64 * NL, LT = 64 * NL;
@@ -166,24 +170,30 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
     const int half = lane >> 5, l31 = lane & 31;
     const int wk = wave % WK, wn = (wave / WK) % WN, wm = wave / (WK * WN);
 
-    const int bid = conv_parity_select(p, xcd_remap(blockIdx.x, p.nblocks));
+    // GEO1: the key on a conv1 flavour (conv_dev.h).  Such a layer has the dim-32 plan's kFinGeomGroups GroupNorm groups of cpg channels, a
+    // 3x3 stride-1 window without upsampling or parity form -- conv1_geo_key() below tests all of it -- so the column tiles of the grid and
+    // the window's extent are constants too: the tile decode and the staging threads' pixel decode divide by constants
+    constexpr bool GEOC = GEO != 0, GEO1 = GEOC && !(FL & FL_FIN);
+    constexpr int G1_NT = GEO1 ? geo_cpg(GEO) * kFinGeomGroups / BN : 1;
+    static_assert(!GEO1 || (KS == 3 && geo_conv1_mask(FL) && geo_cpg(GEO) * kFinGeomGroups % BN == 0), "conv1 geometry flavours: 3x3, whole column tiles");
+    const int bid = GEO1 ? xcd_remap(blockIdx.x, p.nblocks) : conv_parity_select(p, xcd_remap(blockIdx.x, p.nblocks));
     // tile decode without integer division: tiles_x / tiles_y are powers of two, ntiles goes through a host-made reciprocal
-    const int mt_i = p.ntiles == 1 ? bid : (p.magic_nt ? (int)__umulhi((unsigned)bid, p.magic_nt) : bid / p.ntiles);
-    const int nt_i = bid - mt_i * p.ntiles;
+    const int mt_i = GEO1 ? bid / G1_NT : (p.ntiles == 1 ? bid : (p.magic_nt ? (int)__umulhi((unsigned)bid, p.magic_nt) : bid / p.ntiles));
+    const int nt_i = bid - mt_i * (GEO1 ? G1_NT : p.ntiles);
     const int tx = mt_i & (p.tiles_x - 1), ty = (mt_i >> p.txl) & (p.tiles_y - 1), bg = mt_i >> (p.txl + p.tyl);
     // the tile geometry of a Block-closing flavour is a constant of the instantiation (GEO, conv_dev.h); a launch reaches it only when
     // every condition of fin_geo_key() below holds: one source without concat whose GroupNorm groups and statistics slots are those of
     // the output (Cin = Cout, same cpg, T = Tst), whole column tiles, tables of at most one entry per staging thread
-    constexpr bool GEOC = GEO != 0;
     constexpr int BM = 32 * MT * WM;
-    static_assert(!GEOC || (!(FL & FL_CAT) && (FL & FL_XF) && geo_Tst(GEO) <= kPartPre), "geometry flavours: transform loader, one source");
+    static_assert(!GEOC || GEO1 || (!(FL & FL_CAT) && (FL & FL_XF) && geo_Tst(GEO) <= kPartPre), "Block-closing geometry flavours: transform loader, one source");
     const int g_TB = GEOC ? geo_TB(GEO) : p.TB;
     const int g_TWl = GEOC ? geo_TWl(GEO) : p.TWl;
     const int g_tbsh = GEOC ? geo_log2(BM / geo_TB(GEO)) : p.TWl + p.THl;
     const int g_THl = GEOC ? geo_log2(BM / geo_TB(GEO)) - geo_TWl(GEO) : p.THl;
     const int TW = 1 << g_TWl, TH = 1 << g_THl;
     const int b0 = bg * g_TB, y0 = ty * TH, x0 = tx * TW, n0 = nt_i * BN;
-    const int PW = p.PW, PHW = p.PH * p.PW;
+    constexpr int G1_PW = GEO1 ? (1 << geo_TWl(GEO)) + 2 : 1, G1_PHW = GEO1 ? (BM / geo_TB(GEO) / (1 << geo_TWl(GEO)) + 2) * G1_PW : 1;
+    const int PW = GEO1 ? G1_PW : p.PW, PHW = GEO1 ? G1_PHW : p.PH * p.PW;
     const int C0 = a.s0.C, C1 = a.s1.C, Cin = a.Cin, Cout = a.Cout;
     constexpr bool LEAN = FL != FL_ALL;        // launched for an exact match of the mask only: a set bit means "on"
     const bool has_res = LEAN ? bool(FL & FL_RES) : a.res_out != nullptr;
@@ -393,7 +403,15 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
             for (int k = 0; k < NPL; ++k) {
                 const int pix = ltid / Q + k * PIXSTEP;
                 e_po[k] = -1; e_lds[k] = -1; e_tb[k] = 0;
-                if (pix < p.P) {
+                if (GEO1) {           // the window's extent is a constant of the key: divisions by constants, stride 1, pad 1, no upsampling
+                    if (pix < geo_TB(GEO) * G1_PHW) {
+                        const int tb = pix / G1_PHW, r = pix - tb * G1_PHW, py = r / G1_PW, px = r - py * G1_PW;
+                        const int iy = y0 - 1 + py, ix = x0 - 1 + px, b = b0 + tb;
+                        if (b < a.B && iy >= 0 && iy < a.Hs && ix >= 0 && ix < a.Ws) e_po[k] = (b * a.Hs + iy) * a.Ws + ix;
+                        e_lds[k] = pix * CS + (DB4 ? 8 * ((ltid % Q) >> 1) + 2 * ((ltid % Q) & 1) : q4);
+                        e_tb[k] = tb;
+                    }
+                } else if (pix < p.P) {
                     const int tb = fastdiv(pix, p.magic_phw), r = pix - tb * PHW, py = fastdiv(r, p.magic_pw), px = r - py * PW;
                     const int iy = y0 * a.stride - (a.pad_y >= 0 ? a.pad_y : a.pad) + py, ix = x0 * a.stride - (a.pad_x >= 0 ? a.pad_x : a.pad) + px, b = b0 + tb;
                     if (b < a.B && iy >= 0 && iy < Hin && ix >= 0 && ix < Win) e_po[k] = (b * a.Hs + (iy >> a.ups)) * a.Ws + (ix >> a.ups);
@@ -443,7 +461,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
             }
         };
         f32x4 pv[NPL];
-        const int nk = __builtin_amdgcn_readfirstlane((p.P * Q + LT - 1) / LT);   // element slots in use (scalar: cheap loop exits)
+        const int nk = GEO1 ? (geo_TB(GEO) * G1_PHW * Q + LT - 1) / LT : __builtin_amdgcn_readfirstlane((p.P * Q + LT - 1) / LT);   // element slots in use (scalar: cheap loop exits)
         auto issue_patch = [&](int i, f32x4 (&pv)[NPL]) {   // input window of chunk i -> registers, every load issued back to back
             const int c = i * CC + q4;
             const bool live = c < Cin, first = !(FL & FL_CAT) || c < C0;
@@ -548,7 +566,8 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         for (int mt = 0; mt < MT; ++mt) {
             const int m = (wm * MT + mt) * 32 + l31;
             const int tw = m & (TW - 1), th = (m >> g_TWl) & (TH - 1), tb = m >> g_tbsh;
-            abase[mt] = (tb * PHW + th * a.stride * PW + tw * a.stride) * CS + half;
+            const int st = GEO1 ? 1 : a.stride;
+            abase[mt] = (tb * PHW + th * st * PW + tw * st) * CS + half;
         }
         const int bbase = half * BN + wn * NT * 32 + l31;
         const int kk0 = wk * KPW;
@@ -732,7 +751,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
                 }
             }
             if (has_res) {   // fused res_conv: the centre tap against its own weight slab
-                const int tapoff = (a.pad * PW + a.pad) * CS;
+                const int tapoff = GEO1 ? (PW + 1) * CS : (a.pad * PW + a.pad) * CS;
 #pragma unroll
                 for (int kk = 0; kk < KPW; ++kk) {
                     const int k = 2 * (kk0 + kk);
@@ -857,7 +876,7 @@ static int launch_or_query(K kernel, int nthr, const ConvDev& d, int grid, size_
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
-// Diagnostics (fc_debug_conv_routes, tools/flavour_sizes.py): the template arguments of the instantiation every launch went to, one line
+// Diagnostics (fc_debug_conv_routes, tools/flavour_sizes.py): the thirteen template arguments of the instantiation every launch went to, one line
 // per launch -- they are the instantiation's name in the code object's symbol table.
 static std::mutex g_route_mu;
 static bool g_route_on = false;
@@ -865,14 +884,14 @@ static std::string g_route_log;
 void conv_route_log_set(bool on) { std::lock_guard<std::mutex> lk(g_route_mu); g_route_on = on; if (on) g_route_log.clear(); }
 std::string conv_route_log_get() { std::lock_guard<std::mutex> lk(g_route_mu); return g_route_log; }
 
-template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEO = 0>
+template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEOF = 0, int GEOK1 = 0>
 static int launch_pipe(const ConvDev& d, int grid, size_t lds, hipStream_t s, int* occ) {
     if (!occ && g_route_on) {
         std::lock_guard<std::mutex> lk(g_route_mu);
-        const int v[12] = {WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEO};
-        for (int i = 0; i < 12; ++i) g_route_log += std::to_string(v[i]) + (i < 11 ? " " : "\n");
+        const int v[13] = {WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1};
+        for (int i = 0; i < 13; ++i) g_route_log += std::to_string(v[i]) + (i < 12 ? " " : "\n");
     }
-    return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEO>), 256 + 64 * NL, d, grid, lds, s, occ);
+    return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1>), 256 + 64 * NL, d, grid, lds, s, occ);
 }
 
 template <int FL>
@@ -1009,6 +1028,66 @@ static int fin_geom_launch(const ConvDev& d, int tile, bool w4, int need, int gr
     return -1;
 }
 
+// Block-OPENING (conv1) GEOMETRY flavours: the first convolution of every ResnetBlock of the same plan -- statistics of the raw output, in the
+// up path also the concatenated skip and the fused res_conv output.  A Block's conv1 has the output geometry of its closing launch, so the
+// keys are those of FC_FIN_GEOMS; only the (tile, mask, key) triples the plan's 19 conv1 launches use exist.
+// X(tile, WM, WN, WK, MT, NT, CC, NL, weights, mask, key)
+constexpr int kConv1Up = FL_STATS | FL_CAT | FL_RES;
+#define FC_CONV1_GEOMS(X)                                                                                    \
+    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, FL_STATS, geo_key(GEO_FAST, 1, 16, 8, 8))      /* downs.0.* */      \
+    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, kConv1Up, geo_key(GEO_FAST, 1, 16, 8, 8))      /* ups.3.*, final_res_block */ \
+    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, kConv1Up, geo_key(GEO_FAST, 1, 16, 16, 2))     /* ups.2.* */        \
+    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, FL_STATS, geo_key(GEO_FAST, 1, 16, 8, 4))     /* downs.1.* */      \
+    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, kConv1Up, geo_key(GEO_FAST, 1, 8, 32, 1))     /* ups.1.* */        \
+    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_STATS, geo_key(GEO_FAST, 1, 8, 16, 2)) /* downs.2.* */      \
+    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_STATS, geo_key(GEO_PAIR, 2, 4, 32, 1)) /* downs.3.* */      \
+    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_STATS, geo_key(GEO_PAIR, 2, 4, 64, 2)) /* mid_block1, mid_block2 */ \
+    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, kConv1Up, geo_key(GEO_PAIR, 2, 4, 64, 2)) /* ups.0.* */
+
+// The geometry key of a conv1 launch on a tile of BM x BN, or 0 when it is not one a conv1 geometry flavour may take: the flavours assume
+// (and compile in) everything tested here -- the statistics geometry as fin_geo_key() does, and besides it a plain 3x3 stride-1 window
+// (no upsampling, no parity form, no activation or addend), kFinGeomGroups groups over whole column tiles and the wide store form.
+static int conv1_geo_key(const ConvDev& d, int BM, int BN, bool pair_tile) {
+    const ConvArgs& a = d.a;
+    if (a.fin.gamma || !a.stats_out || a.stats_post || a.par4 || a.stats_tmul != 1 || a.stats_toff != 0 || d.any_xf || a.out_act || a.add || d.o_out < 0) return 0;
+    if (a.KS != 3 || a.stride != 1 || a.ups || a.pad != 1 || a.pad_y >= 0 || a.pad_x >= 0 || a.out_sh || a.out_oy || a.out_ox || a.Hs != a.H || a.Ws != a.W) return 0;
+    if (d.TB != 1 && d.TB != 2) return 0;
+    if (d.rps != BM / d.TB || (1 << (d.TWl + d.THl)) * d.TB != BM) return 0;
+    const int form = (pair_tile && d.TB == 2 && d.rps == 16) ? GEO_PAIR : (d.TB == 1 ? GEO_FAST : 0);
+    if (!form) return 0;
+    const int cpg = d.cpg, NPG = cpg >= BN ? cpg / BN : 1;
+    if (cpg < 1 || (cpg & (cpg - 1)) || cpg > (1 << 15) || d.cpgt != (cpg < BN ? cpg : BN) || d.NPG != NPG) return 0;
+    const int Tst = (d.TB > 1 ? 1 : d.tiles_x * d.tiles_y) * NPG;
+    if (Tst < 1 || Tst > 63) return 0;
+    if (a.Gout != kFinGeomGroups || a.Cout != kFinGeomGroups * cpg || a.Cout % BN || d.ntiles != a.Cout / BN) return 0;
+    const int TW = 1 << d.TWl, TH = 1 << d.THl;
+    if (d.PW != TW + 2 || d.PH != TH + 2 || d.P != d.TB * d.PH * d.PW) return 0;
+    return geo_key(form, d.TB, TW, cpg, Tst);
+}
+
+static int conv1_geom_attr() {
+#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MASK, GEO)                                                                                            \
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4), 0, 0, GEO>),    \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                                           \
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4) | FL_STAMP, 0, 0, GEO>), \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    FC_CONV1_GEOMS(X)
+#undef X
+    return FC_OK;
+}
+
+// -1: no conv1 flavour of this (tile, weights form, mask, geometry)
+static int conv1_geom_launch(const ConvDev& d, int tile, bool w4, int need, int grid, size_t lds, hipStream_t s, int* occ) {
+#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MASK, GEO)                                                                                        \
+    if (tile == T && (w4 ? FL_W4 : 0) == (W4) && (need & ~FL_STAMP) == (MASK) && d.P * (CC / 4) <= 64 * NL * kLeanNPL &&                       \
+        conv1_geo_key(d, 32 * MT * WM, 32 * NT * WN, WM * MT == 1 && WN * NT == 1) == (GEO))                                                   \
+        return (need & FL_STAMP) ? launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4) | FL_STAMP, 0, 0, GEO>(d, grid, lds, s, occ) \
+                                 : launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4), 0, 0, GEO>(d, grid, lds, s, occ);
+    FC_CONV1_GEOMS(X)
+#undef X
+    return -1;
+}
+
 // (four staging waves as in the fp32 form: eight measured 364 against 380 images/s on the SD-VAE decode)
 #define FC_BF3_TILES(X, KS)                \
     X(TILE_M128N32, 4, 1, 1, 1, 1, 16, KS, 4)  \
@@ -1061,6 +1140,7 @@ int conv_pipe_init() {
 #undef X
     FC_TRY((lean_attr<2, 0>()));
     FC_TRY(fin_geom_attr());
+    FC_TRY(conv1_geom_attr());
     done = true;
     return FC_OK;
 }
@@ -1095,6 +1175,7 @@ static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, 
                             (!d.a.res_out || d.a.res_w4);
             const size_t lds_ww = (w4 && (need & FL_FIN)) ? ww_lds(d, tile, lds) : 0;        // whole-window staging, where the launch may take it
             if (need & FL_FIN) r = fin_geom_launch(d, tile, w4, need, grid, lds, lds_ww, s, occ);    // Block-closing: the flavour of exactly this geometry, if there is one
+            else if (need & FL_STATS) r = conv1_geom_launch(d, tile, w4, need, grid, lds, s, occ);   // Block-opening: likewise
             if (lds_ww) {
 #define X(F) if (r == -1 && need == (F)) r = lean_launch_ww<(F)>(d, tile, grid, lds_ww, s, occ);
                 FC_LEAN_FLAVOURS_3(X)
@@ -1130,7 +1211,13 @@ int conv_pipe_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream
 
 // Workgroups of the instantiation this launch would go to that ONE CU holds at once (registers, waves and LDS as the runtime counts
 // them), cached per (tile, kernel size, flavour mask, LDS bytes, statistics geometry: a Block-closing launch's flavour depends on it).  0 = the query failed.
+// A launch without a fused tail is asked for afresh: a conv1 launch's flavour also depends on what conv1_geo_key() tests (groups, window,
+// stride, source extent), which the cache key does not hold.
 int conv_pipe_blocks_per_cu(const ConvDev& d, int tile, size_t lds) {
+    if (!d.a.fin.gamma) {
+        int occ = 0;
+        return conv_pipe_dispatch(d, tile, 1, lds, nullptr, &occ) == FC_OK ? occ : 0;
+    }
     static std::map<std::tuple<int, int, int, size_t, int, int>, int> cache;
     static std::mutex mu;
     const int mask = (d.a.fin.gamma ? FL_FIN : 0) | (d.a.res_out ? FL_RES : 0) | (d.a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |

@@ -11,6 +11,7 @@
 // At the 32x32 level this replaces a 100 MB qkv round trip (to_qkv 32->384 over 65536 pixels) and two 33 MB passes by one
 // read of x per kernel.  fp32 MFMA throughout (exact products), so results match the unfused kernels to summation order.
 #include <cstdlib>
+#include <mutex>
 #include <string>
 
 #include "common.h"
@@ -280,20 +281,22 @@ __global__ void __launch_bounds__(256) la_apply_kernel(const LaArgs a, int T, fl
 // memory (16-byte loads, normalised in registers) -- no x tile in LDS either.
 //
 // a lane's half row of x[b][r0 + l31]: channels [half * C/2, half * C/2 + C/2), NQ = C / 8 float4 loads; rows >= n are zero
-template <int NQ>
+// (NFIX != 0: n = NFIX is a constant of the instantiation and every row exists -- the plan-shape instantiations below)
+template <int NQ, int NFIX = 0>
 __device__ __forceinline__ void fetch_xh(const LaArgs& a, int b, int r0, int lane, float4 (&pre)[NQ]) {
-    const int nn = r0 + (lane & 31);
-    const float* p = a.x + ((size_t)b * a.n + nn) * (NQ * 8) + (lane >> 5) * (NQ * 4);
+    const int nn = r0 + (lane & 31), n = NFIX ? NFIX : a.n;
+    const float* p = a.x + ((size_t)b * n + nn) * (NQ * 8) + (lane >> 5) * (NQ * 4);
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
+        if (NFIX) { pre[j] = *reinterpret_cast<const float4*>(p + 4 * j); continue; }
         pre[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (nn < a.n) pre[j] = *reinterpret_cast<const float4*>(p + 4 * j);
     }
 }
 // GroupNorm of the half row: xn[s] = channel c_s of the lane's position (Ab / Bb: the norm's scale and shift per channel, LDS)
-template <int NQ>
+template <int NQ, int NFIX = 0>
 __device__ __forceinline__ void norm_xh(const LaArgs& a, const float* Ab, const float* Bb, int r0, int lane, const float4 (&pre)[NQ], float (&xn)[NQ * 4]) {
-    const bool in = r0 + (lane & 31) < a.n;
+    const bool in = NFIX ? true : r0 + (lane & 31) < a.n;
     const float* ap = Ab + (lane >> 5) * (NQ * 4);
     const float* bp = Bb + (lane >> 5) * (NQ * 4);
 #pragma unroll
@@ -314,20 +317,32 @@ __device__ __forceinline__ void norm_xh(const LaArgs& a, const float* Ab, const 
 // life of the kernel), E = exp(K - m) in K's registers, then the context TRANSPOSED, ctxT[e][d] += sum_pos V[pos][e] E[pos][d], with
 // A = V's and B = E's accumulator as they sit.  Transposed, the softmax channel d is the LANE of the context accumulator, so the online
 // rescale by exp(m_old - m_new) is one multiply by a value the lane already holds.  Nothing in the loop touches LDS but Ab / Bb.
-template <int NQ, int NW>
+// NB != 0: a PLAN-SHAPE instantiation -- n = 32 NB is a constant (the dim-32 plan's n = 1024 and n = 256 levels).  The tile loop then has
+// NB / NW trips, known when the kernel is compiled: every x tile of the wave is requested before the first wait (no global load inside a
+// loop with a run-time trip count, section 7 of DESIGN.md), and no accumulator row is masked (n is a multiple of 32).  Same values, same
+// order of every sum as the run-time form (NB = 0), which serves every other shape.
+template <int NQ, int NW, int NB = 0>
 __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     constexpr int C = NQ * 8, H2 = C / 2, NT = 64 * NW;
+    constexpr bool FIX = NB != 0;
+    constexpr int NFIX = NB * 32, ITER = FIX ? NB / NW : 1;
+    static_assert(!FIX || (NB % NW == 0 && NB >= NW), "plan-shape instantiation: whole rounds of the workgroup's waves");
     float* Ab = sm;
     float* Bb = Ab + C;
     float* Et = Bb + C;                 // [NW][32][PS]
     float* sct = Et + NW * 32 * PS;     // [NW][32]
     float* mz = sct + NW * 32;          // [NW][2][32]
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const int nblk = (a.n + 31) >> 5;
-    // every cold operand is requested before anything is waited for: first x tile, statistics, norm parameters, weights
-    float4 pre[NQ];
-    if (wave < nblk) fetch_xh<NQ>(a, b, wave * 32, lane, pre);
+    const int nblk = FIX ? NB : (a.n + 31) >> 5;
+    // every cold operand is requested before anything is waited for: first x tile (plan shape: every x tile), statistics, norm parameters, weights
+    float4 pre[ITER][NQ];
+    if constexpr (FIX) {
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) fetch_xh<NQ, NFIX>(a, b, (wave + it * NW) * 32, lane, pre[it]);
+    } else {
+        if (wave < nblk) fetch_xh<NQ>(a, b, wave * 32, lane, pre[0]);
+    }
     PartPre pp;
     partials_request(a.xf, b, 0, pp);
     const float pg = tid < C ? a.xf.gamma[tid] : 0.f, pbt = tid < C ? a.xf.beta[tid] : 0.f;   // C <= 64 < 256 threads
@@ -350,11 +365,8 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) cacc[r] = 0.f;
     float m_run = -INFINITY, z_run = 0.f;
-    for (int rb = wave; rb < nblk; rb += NW) {
-        const int r0 = rb * 32;
-        float xn[H2];
-        norm_xh<NQ>(a, Ab, Bb, r0, lane, pre, xn);
-        if (rb + NW < nblk) fetch_xh<NQ>(a, b, r0 + 32 * NW, lane, pre);
+    // one 32-position tile: k, v, online softmax over the positions, context
+    auto tile = [&](const int r0, const float (&xn)[H2]) {
         f32x16 ak, av;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { ak[r] = 0.f; av[r] = 0.f; }
@@ -365,14 +377,14 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
         }
         float bm = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) if (r0 + acc_row(r, half) < a.n) bm = fmaxf(bm, ak[r]);
+        for (int r = 0; r < 16; ++r) if (FIX || r0 + acc_row(r, half) < a.n) bm = fmaxf(bm, ak[r]);
         bm = fmaxf(bm, __shfl_xor(bm, 32));
         const float m_new = fmaxf(m_run, bm);
         const float sc = __expf(m_run - m_new);
         float zs = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float e = (r0 + acc_row(r, half) < a.n) ? __expf(ak[r] - m_new) : 0.f;
+            const float e = (FIX || r0 + acc_row(r, half) < a.n) ? __expf(ak[r] - m_new) : 0.f;
             zs += e;
             ak[r] = e;
         }
@@ -383,6 +395,23 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
         for (int r = 0; r < 16; ++r) cacc[r] *= sc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) cacc = FC_MFMA(av[r], ak[r], cacc);
+    };
+    if constexpr (FIX) {
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int r0 = (wave + it * NW) * 32;
+            float xn[H2];
+            norm_xh<NQ, NFIX>(a, Ab, Bb, r0, lane, pre[it], xn);
+            tile(r0, xn);
+        }
+    } else {
+        for (int rb = wave; rb < nblk; rb += NW) {
+            const int r0 = rb * 32;
+            float xn[H2];
+            norm_xh<NQ>(a, Ab, Bb, r0, lane, pre[0], xn);
+            if (rb + NW < nblk) fetch_xh<NQ>(a, b, r0 + 32 * NW, lane, pre[0]);
+            tile(r0, xn);
+        }
     }
     if (half == 0) { mz[(wave * 2) * 32 + l31] = m_run; mz[(wave * 2 + 1) * 32 + l31] = z_run; }
     __syncthreads();
@@ -418,27 +447,34 @@ __global__ void __launch_bounds__(64 * NW) la_ctx_fast_kernel(const LaArgs a) {
 // close and the stores work on 16-byte channel quads.
 constexpr int AS = 20;                  // row stride of a 16-step A operand image
 __device__ __forceinline__ int acc_reg(int row) { return (row & 3) + 4 * (row >> 3); }   // acc_row(acc_reg(row), (row >> 2) & 1) == row
-template <int NQ, int CT>
-__global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int T, float n_t) {
+// TT != 0: a PLAN-SHAPE instantiation -- the sample has exactly TT tiles (n = 128 TT), a constant.  No row is masked, the epoch is a shift
+// of the arrival count, a thread polls at most one granule under a constant bound, the close is a straight line of TT terms in the run-time
+// form's order, and the two block sums share one pair of barriers (each quantity's additions in block_sum's order).
+template <int NQ, int CT, int TT = 0>
+__global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int T_rt, float n_t) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     constexpr int C = NQ * 8, H2 = C / 2, SQ = H2 + 4, WO = CT * 32;
+    constexpr bool FIX = TT != 0;
+    constexpr int NFIX = TT * 128;
+    static_assert(TT <= kPartPre, "one granule pair per tile, polled by 2 TT threads");
+    const int T = FIX ? TT : T_rt, n = FIX ? NFIX : a.n;
     float* Ab = sm;
     float* Bb = Ab + C;
     float* WqL = Bb + C;                          // [4 heads][half][32 d][SQ]: Wq[c_s][h * 32 + d] at s
     float* ctxL = WqL + LHEADS * 64 * SQ;         // [4][half][32 e][AS]: ctx[h][acc_row(r, half)][e] at r
     float* WoL = ctxL + LHEADS * 64 * AS;         // [4][CT][half][32 c][AS]: Wout[h * 32 + acc_row(r, half)][ct * 32 + c] at r
-    __shared__ float red[4];
+    __shared__ float red[4], red2[4];
     __shared__ unsigned epoch_s;
     __shared__ float gv[2 * kPartPre];
     const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
     const int r0 = tile * 128 + wave * 32, nn = r0 + l31;
-    const bool in = nn < a.n;
+    const bool in = FIX ? true : nn < a.n;
     // the fused close (a.gran; T <= kPartPre): this launch's epoch from the sample's arrival counter
     unsigned arrival = 0;
     if (a.gran && tid == 0) arrival = __hip_atomic_fetch_add(a.sync + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // every cold operand is requested before anything is waited for: x, statistics, norm parameters, weights, context
     float4 pre[NQ];
-    fetch_xh<NQ>(a, b, r0, lane, pre);
+    fetch_xh<NQ, NFIX>(a, b, r0, lane, pre);
     PartPre pp;
     partials_request(a.xf, b, 0, pp);
     const float pg = tid < C ? a.xf.gamma[tid] : 0.f, pbt = tid < C ? a.xf.beta[tid] : 0.f;   // C <= 64 < 256 threads
@@ -496,11 +532,11 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
             pbias[ct][g] = z; rs[ct][g] = z;
             if (c < C && a.bout) pbias[ct][g] = *reinterpret_cast<const float4*>(a.bout + c);
-            if (a.gran && c < C && in) rs[ct][g] = *reinterpret_cast<const float4*>(a.x + ((size_t)b * a.n + nn) * C + c);
+            if (a.gran && c < C && in) rs[ct][g] = *reinterpret_cast<const float4*>(a.x + ((size_t)b * n + nn) * C + c);
         }
     __syncthreads();
     float xn[H2];
-    norm_xh<NQ>(a, Ab, Bb, r0, lane, pre, xn);
+    norm_xh<NQ, NFIX>(a, Ab, Bb, r0, lane, pre, xn);
     const float scale = 0.17677669529663687f;
     f32x16 y[CT];
 #pragma unroll
@@ -572,8 +608,19 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
                 S += v0; Q += v0 * v0; S += v1; Q += v1 * v1; S += v2; Q += v2 * v2; S += v3; Q += v3 * v3;
             }
         }
-    const float St = block_sum(S, red);
-    const float Qt = block_sum(Q, red);
+    float St, Qt;
+    if constexpr (FIX) {                // both sums over one pair of barriers; each one's additions in block_sum's order
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { S += __shfl_xor(S, o); Q += __shfl_xor(Q, o); }
+        __syncthreads();
+        if (lane == 0) { red[wave] = S; red2[wave] = Q; }
+        __syncthreads();
+        St = red[0] + red[1] + red[2] + red[3];
+        Qt = red2[0] + red2[1] + red2[2] + red2[3];
+    } else {
+        St = block_sum(S, red);
+        Qt = block_sum(Q, red);
+    }
     if (a.gran) {
         // ---- the module closed here: out = GroupNorm(1)(y) * g2 + b2 + x, the statistics completed by the sample's other tiles ----
         // The partials travel as ONE 8-byte write-through store each, {epoch, bits}: the data is its own flag (the convolution tails'
@@ -610,7 +657,7 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
         }
         __syncthreads();
         float sm2 = 0.f;
-        for (int t = 0; t < T; ++t) sm2 += gv[2 * t];
+        for (int t = 0; t < T; ++t) sm2 += gv[2 * t];        // (plan shape: T is a constant, a straight line)
         const float mean = sm2 / (float)T;
         float m2 = 0.f, dv = 0.f;
         for (int t = 0; t < T; ++t) {
@@ -630,7 +677,7 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
                 { const float A = rstd * gg.y, Bc = bb.y - mean * A; ov.y = (A * y[ct][4 * g + 1] + Bc) + rr.y; }
                 { const float A = rstd * gg.z, Bc = bb.z - mean * A; ov.z = (A * y[ct][4 * g + 2] + Bc) + rr.z; }
                 { const float A = rstd * gg.w, Bc = bb.w - mean * A; ov.w = (A * y[ct][4 * g + 3] + Bc) + rr.w; }
-                if (in && c < C) *reinterpret_cast<float4*>(a.out + ((size_t)b * a.n + nn) * C + c) = ov;
+                if (in && c < C) *reinterpret_cast<float4*>(a.out + ((size_t)b * n + nn) * C + c) = ov;
             }
         return;
     }
@@ -645,25 +692,72 @@ __global__ void __launch_bounds__(256) la_apply_fast_kernel(const LaArgs a, int 
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int c = ct * 32 + 8 * g + 4 * half;
-            if (in && c < C) *reinterpret_cast<float4*>(a.y + ((size_t)b * a.n + nn) * C + c) = make_float4(y[ct][4 * g], y[ct][4 * g + 1], y[ct][4 * g + 2], y[ct][4 * g + 3]);
+            if (in && c < C) *reinterpret_cast<float4*>(a.y + ((size_t)b * n + nn) * C + c) = make_float4(y[ct][4 * g], y[ct][4 * g + 1], y[ct][4 * g + 2], y[ct][4 * g + 3]);
         }
 }
 
 static size_t la_ctx_fast_lds(int C, int NW) { return (size_t)(2 * C + NW * 32 * PS + 32 * NW + 64 * NW) * sizeof(float); }
 static int la_ctx_waves(int n) { return n >= 256 ? 8 : 4; }      // eight waves once every one of them has a 32-position block of its own
 static size_t la_apply_fast_lds(int C, int CT) { return (size_t)(2 * C + LHEADS * 64 * (C / 2 + 4) + LHEADS * 64 * AS + LHEADS * CT * 64 * AS) * sizeof(float); }
+// The plan-shape instantiations (the dim-32 inference plan at 4x32x32): (C, n) -> n / 32, or 0: the run-time form.  Exact match only.
+static int la_plan_nb(int C, int n) {
+    if (C == 32 && n == 1024) return 32;     // downs.0.2, ups.3.2
+    if (C == 32 && n == 256) return 8;       // downs.1.2
+    if (C == 64 && n == 256) return 8;       // ups.2.2
+    return 0;
+}
+// Diagnostics (fc_debug_conv_routes switches the record on and off, fc_debug_linattn_routes_read copies it): what launch_fast really
+// launched, one line "C n NB TT" per module -- NB / TT are the template constants of the context / apply kernel it took (0 0: the pair
+// that reads the shape at run time).
+static std::mutex g_la_route_mu;
+static bool g_la_route_on = false;
+static std::string g_la_route_log;
+void linattn_route_log_set(bool on) { std::lock_guard<std::mutex> lk(g_la_route_mu); g_la_route_on = on; if (on) g_la_route_log.clear(); }
+std::string linattn_route_log_get() { std::lock_guard<std::mutex> lk(g_la_route_mu); return g_la_route_log; }
+struct LaCtxSel { void (*fn)(const LaArgs); int NB; };
+struct LaApplySel { void (*fn)(const LaArgs, int, float); int TT; };
+// the instantiation a launch of (C = 8 NQ, n) runs: the exclusive plan, the plan on a shared device and the residency query all ask here
+template <int NQ>
+static LaCtxSel la_ctx_fast_for(int n) {
+    if constexpr (NQ == 4) {
+        if (la_plan_nb(NQ * 8, n) == 32) return {la_ctx_fast_kernel<NQ, 8, 32>, 32};
+        if (la_plan_nb(NQ * 8, n) == 8) return {la_ctx_fast_kernel<NQ, 8, 8>, 8};
+    }
+    if constexpr (NQ == 8) {
+        if (la_plan_nb(NQ * 8, n) == 8) return {la_ctx_fast_kernel<NQ, 8, 8>, 8};
+    }
+    if (la_ctx_waves(n) == 8) return {la_ctx_fast_kernel<NQ, 8>, 0};
+    return {la_ctx_fast_kernel<NQ, 4>, 0};
+}
+template <int NQ>
+static LaApplySel la_apply_fast_for(int n) {
+    if constexpr (NQ == 4) {
+        if (la_plan_nb(NQ * 8, n) == 32) return {la_apply_fast_kernel<NQ, 1, 8>, 8};
+        if (la_plan_nb(NQ * 8, n) == 8) return {la_apply_fast_kernel<NQ, 1, 2>, 2};
+    }
+    if constexpr (NQ == 8) {
+        if (la_plan_nb(NQ * 8, n) == 8) return {la_apply_fast_kernel<NQ, 2, 2>, 2};
+    }
+    if constexpr (NQ * 8 <= 32) return {la_apply_fast_kernel<NQ, 1>, 0};
+    else return {la_apply_fast_kernel<NQ, 2>, 0};
+}
 template <int NQ>
 static int launch_fast(const LaArgs& a, hipStream_t s) {
-    if (la_ctx_waves(a.n) == 8) hipLaunchKernelGGL((la_ctx_fast_kernel<NQ, 8>), dim3(LHEADS, a.B), dim3(512), la_ctx_fast_lds(a.C, 8), s, a);
-    else hipLaunchKernelGGL((la_ctx_fast_kernel<NQ, 4>), dim3(LHEADS, a.B), dim3(256), la_ctx_fast_lds(a.C, 4), s, a);
+    const int NW = la_ctx_waves(a.n);
+    const LaCtxSel cs = la_ctx_fast_for<NQ>(a.n);
+    const LaApplySel as = la_apply_fast_for<NQ>(a.n);
+    if (g_la_route_on) {
+        std::lock_guard<std::mutex> lk(g_la_route_mu);
+        g_la_route_log += std::to_string(a.C) + " " + std::to_string(a.n) + " " + std::to_string(cs.NB) + " " + std::to_string(as.TT) + "\n";
+    }
+    hipLaunchKernelGGL(cs.fn, dim3(LHEADS, a.B), dim3(64 * NW), la_ctx_fast_lds(a.C, NW), s, a);
     FC_HIP(hipGetLastError());
     const int T = linattn_fused_tiles(a.n);
     const float n_t = linattn_fused_nt(a.n, a.C);
     // One 128-position tile per workgroup: the A operand images of a workgroup are 61 KB of LDS at C = 32, so two workgroups share a CU
     // and two waves a SIMD -- one wave's softmax arithmetic runs under the other's matrix phases.
     const dim3 grid(cdiv(a.n, 128), a.B);
-    if (a.C <= 32) hipLaunchKernelGGL((la_apply_fast_kernel<NQ, 1>), grid, dim3(256), la_apply_fast_lds(a.C, 1), s, a, T, n_t);
-    else hipLaunchKernelGGL((la_apply_fast_kernel<NQ, 2>), grid, dim3(256), la_apply_fast_lds(a.C, 2), s, a, T, n_t);
+    hipLaunchKernelGGL(as.fn, grid, dim3(256), la_apply_fast_lds(a.C, a.C <= 32 ? 1 : 2), s, a, T, n_t);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -673,6 +767,10 @@ static int init_fast() {
     FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(la_ctx_fast_kernel<NQ, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(la_apply_fast_kernel<NQ, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(la_apply_fast_kernel<NQ, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    for (int n : {256, 1024}) {          // the plan-shape instantiations (the run-time ones again where there is none)
+        FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(la_ctx_fast_for<NQ>(n).fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(la_apply_fast_for<NQ>(n).fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    }
     return FC_OK;
 }
 
@@ -708,10 +806,9 @@ bool linattn_fused_supported(int n, int C, int heads) {
 // May the apply launch close the module itself (LaArgs::gran)?  Its workgroups wait for the other tiles of their sample, so every
 // workgroup of the grid must be resident at once: occupancy of the kernel at this C times the CU count >= tiles * B.  Fast path only.
 template <int NQ>
-static int apply_blocks_per_cu(int C) {
+static int apply_blocks_per_cu(int C, int n) {      // of the instantiation launch_fast runs at this shape
     int nb = 0;
-    const hipError_t e = C <= 32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, la_apply_fast_kernel<NQ, 1>, 256, la_apply_fast_lds(C, 1))
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, la_apply_fast_kernel<NQ, 2>, 256, la_apply_fast_lds(C, 2));
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, la_apply_fast_for<NQ>(n).fn, 256, la_apply_fast_lds(C, C <= 32 ? 1 : 2));
     return e == hipSuccess ? nb : 0;
 }
 bool linattn_fused_meeting_ok(int B, int n, int C) {
@@ -721,7 +818,7 @@ bool linattn_fused_meeting_ok(int B, int n, int C) {
     if (linattn_fused_init() != FC_OK) return false;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    const int per = C == 8 ? apply_blocks_per_cu<1>(C) : C == 16 ? apply_blocks_per_cu<2>(C) : C == 32 ? apply_blocks_per_cu<4>(C) : apply_blocks_per_cu<8>(C);
+    const int per = C == 8 ? apply_blocks_per_cu<1>(C, n) : C == 16 ? apply_blocks_per_cu<2>(C, n) : C == 32 ? apply_blocks_per_cu<4>(C, n) : apply_blocks_per_cu<8>(C, n);
     return (long long)per * cus >= (long long)T * B;
 }
 

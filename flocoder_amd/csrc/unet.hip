@@ -1126,10 +1126,16 @@ int fc_debug_set_fused_tail(int on) {   // plans built from now on use (1) / do 
 }
 
 // Diagnostics: record which instantiation of the pipelined convolution every launch goes to (on != 0 starts an empty record, 0 stops);
-// fc_debug_conv_routes_read copies the record -- one line of the twelve template arguments per launch -- and returns its length.
-int fc_debug_conv_routes(int on) { conv_route_log_set(on != 0); return FC_OK; }
+// fc_debug_conv_routes_read copies the record -- one line of the thirteen template arguments per launch -- and returns its length.
+int fc_debug_conv_routes(int on) { conv_route_log_set(on != 0); linattn_route_log_set(on != 0); return FC_OK; }
 int fc_debug_conv_routes_read(char* buf, int cap) {
     const std::string r = conv_route_log_get();
+    if (buf && cap > 0) { const size_t n = r.size() < (size_t)cap - 1 ? r.size() : (size_t)cap - 1; memcpy(buf, r.data(), n); buf[n] = 0; }
+    return (int)r.size();
+}
+
+int fc_debug_linattn_routes_read(char* buf, int cap) {
+    const std::string r = linattn_route_log_get();
     if (buf && cap > 0) { const size_t n = r.size() < (size_t)cap - 1 ? r.size() : (size_t)cap - 1; memcpy(buf, r.data(), n); buf[n] = 0; }
     return (int)r.size();
 }

@@ -386,11 +386,16 @@ int fc_debug_poison_check(int* corrupted, int* live);
 /* Diagnostics: subsequent pipelined-conv launches write shader-clock phase stamps to buf_dev
  * ([block][wave][16] uint64); NULL switches them off again. */
 int fc_debug_set_conv_stamps(void* buf_dev);
-/* Diagnostics: fc_debug_conv_routes(1) starts an empty record of the instantiation every pipelined-conv launch goes to (one line of its twelve
- * template arguments per launch, in launch order), 0 stops; fc_debug_conv_routes_read copies it (NUL-terminated, truncated to cap) and
+/* Diagnostics: fc_debug_conv_routes(1) starts an empty record of the instantiation every pipelined-conv launch goes to (one line of its thirteen
+ * template arguments per launch, in launch order; the twelfth is the geometry key of a Block-closing flavour, the thirteenth that of a
+ * conv1 flavour), 0 stops; fc_debug_conv_routes_read copies it (NUL-terminated, truncated to cap) and
  * returns its full length. */
 int fc_debug_conv_routes(int on);
 int fc_debug_conv_routes_read(char* buf, int cap);
+/* Diagnostics: while the record of fc_debug_conv_routes is on, every launch of the fused linear attention's fast path (n >= 256) adds one
+ * line "C n NB TT" to a record of its own: NB = n / 32 and TT = n / 128 when it launched the kernel pair compiled for exactly this shape, 0 0
+ * when it launched the pair that reads the shape at run time.  Copies it like fc_debug_conv_routes_read and returns its full length. */
+int fc_debug_linattn_routes_read(char* buf, int cap);
 /* Diagnostics: fc_unet_profile_ops runs plan entry `op_index` once more with the stamps of fc_debug_set_conv_stamps going to buf_dev
  * (the phase timeline of ONE launch of a real plan, fused tail included: tools/fin_stamps.py); NULL switches it off. */
 int fc_debug_set_stamp_op(int op_index, void* buf_dev);

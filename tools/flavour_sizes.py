@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 READELF = os.environ.get("LLVM_READELF", "/opt/rocm/lib/llvm/bin/llvm-readelf")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-ARGS = ("WM", "WN", "WK", "MT", "NT", "CC", "NPL", "KS", "NL", "FL", "PREC", "GEO")
+ARGS = ("WM", "WN", "WK", "MT", "NT", "CC", "NPL", "KS", "NL", "FL", "PREC", "GEO", "GEO1")    # GEO: key of a Block-closing flavour, GEO1: of a conv1 flavour
 FL_NAMES = {1: "fin", 2: "res", 4: "post", 8: "xf", 16: "cat", 32: "stamp", 64: "stats", 128: "gn1", 256: "postop", 512: "narrow", 1024: "multi",
             2048: "meet", 4096: "w4", 8192: "ww"}
 
@@ -43,7 +43,7 @@ def code_objects(path):
 
 
 def kernel_sizes(path):
-    """{(twelve template arguments): .text bytes} of every conv_pipe_kernel instantiation."""
+    """{(thirteen template arguments): .text bytes} of every conv_pipe_kernel instantiation."""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         for i, img in enumerate(code_objects(path)):
@@ -54,7 +54,7 @@ def kernel_sizes(path):
                 m = re.match(r"\s*\d+:\s+[0-9a-f]+\s+(\d+)\s+FUNC\s+.*\bconv_pipe_kernel<([^>]*)>", line)
                 if m:
                     a = [int(x) for x in m.group(2).split(",")]
-                    a += [0] * (len(ARGS) - len(a))                              # (a build from before the geometry key has eleven)
+                    a += [0] * (len(ARGS) - len(a))                              # (a build from before the geometry keys has eleven or twelve)
                     out[tuple(a)] = int(m.group(1))
     return out
 
@@ -64,8 +64,8 @@ def describe(key):
     tile = f"M{32 * d['MT'] * d['WM']}N{32 * d['NT'] * d['WN']}" + (f"K{d['WK']}" if d["WK"] > 1 else "")
     fl = "all-in-one" if d["FL"] == 4095 else ("+".join(n for b, n in FL_NAMES.items() if d["FL"] & b) or "plain")
     geo = ""
-    if d["GEO"]:
-        g = d["GEO"]
+    if d["GEO"] or d["GEO1"]:
+        g = d["GEO"] or d["GEO1"]
         geo = f" geo[{('?', 'pair', 'fast', 'general')[g & 3]} TB{1 + ((g >> 2) & 1)} TW{1 << ((g >> 3) & 7)} cpg{1 << ((g >> 6) & 15)} Tst{(g >> 10) & 63}]"
     return f"{tile} {d['KS']}x{d['KS']}{' bf16x3' if d['PREC'] else ''} {fl}{geo}"
 
@@ -111,8 +111,9 @@ def main():
     os.environ["FLOCODER_AMD_LIB"] = a.lib
     users = {}
     for module, kernel, key in plan_routes():
-        if key not in sizes and key[:11] + (0,) in sizes:
-            key = key[:11] + (0,)
+        key = tuple(key) + (0,) * (len(ARGS) - len(key))
+        if key not in sizes and key[:11] + (0, 0) in sizes:
+            key = key[:11] + (0, 0)
         users.setdefault(key, []).append(module + ("+fin" if kernel.endswith("+fin") else ""))
     for k, mods in sorted(users.items(), key=lambda kv: describe(kv[0])):
         print(f"{describe(k):70s} {sizes.get(k, -1):7d}   {' '.join(mods)}")
