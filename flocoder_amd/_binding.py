@@ -102,6 +102,8 @@ SIGNATURES = {
     "fc_unet_integrate_sde": (_i, [_vp, _i, _vp, _i, _i, _i, _pf, _i, _f, _vp, _f, _vp, _i, _f, C.c_uint64, _vp, _vp, _vp]),
     "fc_ode_normal_field": (_i, [_vp, C.c_uint64, _i64, _vp, _i, _i64, _vp]),
     "fc_inpaint_masks": (_i, [_vp, _vp, C.c_uint64, _vp, _i, _i, _i, _pi, C.POINTER(C.c_double), _i, _i, _vp]),
+    "fc_augment_images": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _pf, _pf, _pf, _vp]),
+    "fc_augment_midi": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp]),
     "fc_note_confusion": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _f, C.c_double, _i, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "fc_index_histogram": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "fc_debug_unet_guided_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),

@@ -337,3 +337,281 @@ def mask_field(seed: int, sample_ids, size=(128, 128), choices=MASK_TYPES, p=MAS
             sel = rows[lo:lo + 256]
             out[sel, 0] = fn(seed, sid[sel], h, w)
     return (out, types) if return_types else out
+
+
+# ---- pre-encoding augmentation (csrc/augment.hip, fc_augment_images / fc_augment_midi) -------------------------------------------------
+# A counter-based restatement of upstream's two pipelines (flocoder/data.py:49-111).  Key = seed + AUG_KEY_OFFSET (mod 2^64); counter =
+# (j, region, sample id lo, sample id hi):
+#
+#   region 0, j = 0          image_transforms: words 0, 1: the angle (a 53-bit uniform on [-15, 15] degrees); word 2: flip where its top bit
+#                            is clear
+#   region 0, j = 1 + t      try t < 10 of RandomResizedCrop: word 0: the area fraction, word 1: the log-ratio (uniforms (w + 1/2) 2^-32),
+#                            words 2, 3: the box's top and left, mulhi(w, positions that fit)
+#   region 1, j = 0          midi_transforms: word 0: RandomRoll fires where its top bit is clear; words 1, 2: the horizontal and vertical shift
+#   region 1, j = 1          RandomCrop: words 0, 1: top and left
+#
+# The draws are made HERE, on the host, for the device too: the kernels receive one row of integers per sample (``augment_image_table`` /
+# ``augment_midi_table``), so which source pixel a tap reads is the same integer decision on both sides.
+AUG_KEY_OFFSET = 0x415547464C443031        # "AUGFLD01"
+AUG_MIN_SIZE, AUG_MAX_SIZE, AUG_MAX_SIDE = 16, 1024, 8192
+AUG_IMAGE_WORDS, AUG_MIDI_WORDS = 16, 8
+AUG_TILE, AUG_LDS_PIXELS = 16, 6144          # fc_augment_images: the output tile of a workgroup; the largest window of the crop it stages in LDS
+AUG_TRIES = 10
+AUG_DEGREES, AUG_SCALE, AUG_RATIO, AUG_CENTER = 15.0, (0.8, 1.0), (3.0 / 4.0, 4.0 / 3.0), 0.9
+AUG_MAX_V_SHIFT = 24
+
+
+def aug_words(seed: int, sample_ids, region, j) -> np.ndarray:
+    """uint64 ``[B, *j.shape, 4]`` (32-bit values): the Philox blocks with counter ``(j, region, sample id)`` under the augmentation key."""
+    key = (int(seed) + AUG_KEY_OFFSET) & 0xffffffffffffffff
+    sid = np.asarray(sample_ids, dtype=np.int64).reshape(-1).astype(np.uint64)
+    j, region = np.broadcast_arrays(np.asarray(j, dtype=np.uint64), np.asarray(region, dtype=np.uint64))
+    ex = (slice(None),) + (None,) * j.ndim
+    ctr = np.empty((sid.size, *j.shape, 4), dtype=np.uint64)
+    ctr[..., 0] = j[None]
+    ctr[..., 1] = region[None]
+    ctr[..., 2] = (sid & _MASK)[ex]
+    ctr[..., 3] = (sid >> _S32)[ex]
+    return philox4x32(ctr, np.array([key & 0xffffffff, key >> 32], dtype=np.uint64)).astype(np.uint64)
+
+
+def _u32(w) -> np.ndarray:
+    return (w.astype(np.float64) + 0.5) * 2.0 ** -32
+
+
+def _check_aug_size(image_size) -> int:
+    s = int(image_size)
+    if not AUG_MIN_SIZE <= s <= AUG_MAX_SIZE:
+        raise ValueError(f"image_size={s} must lie in [{AUG_MIN_SIZE}, {AUG_MAX_SIZE}]")
+    return s
+
+
+def _src_hw(src_hw, n) -> np.ndarray:
+    hw = np.broadcast_to(np.asarray(src_hw, dtype=np.int64).reshape(-1, 2), (n, 2))
+    if hw.size and (hw.min() < 2 or hw.max() > AUG_MAX_SIDE):
+        raise ValueError(f"source sides must lie in [2, {AUG_MAX_SIDE}]")
+    return hw
+
+
+def augment_image_params(seed: int, sample_ids, src_hw, image_size) -> dict:
+    """The draws of upstream's ``image_transforms`` for every ``(seed, sample_ids[b])`` on a source of ``src_hw`` (one ``(H, W)`` or one
+    per sample), as a dict of ``[B]`` arrays.  ``angle`` (fp64 degrees, uniform on [-15, 15], counter-clockwise as PIL's).  The centre crop
+    is deterministic: ``crop_side = int(0.9 min(H, W))`` at ``crop_top = round((H - side) / 2)``, ``crop_left`` likewise (round half to
+    even, CenterCrop's).  ``RandomResizedCrop(scale=(0.8, 1), ratio=(3/4, 4/3))`` on that square: ten tries from fixed counters, try t
+    draws ``area = side^2 (0.8 + 0.2 u)``, ``ratio = exp(uniform(log 3/4, log 4/3))``, ``w = round(sqrt(area ratio))``, ``h =
+    round(sqrt(area / ratio))`` and is accepted where ``0 < w <= side`` and ``0 < h <= side``; its ``box_top`` / ``box_left`` are
+    uniform integers over the positions that fit.  The first accepted try is taken (``tries`` is its index, ``area_frac`` and ``ratio``
+    its draws); after ten failures (``tries = 10``, NaN draws) the box is upstream's fallback, the central box with the ratio clamped to
+    [3/4, 4/3] -- the whole crop, a square's ratio being 1.  ``flip`` with p = 0.5.  The box is in the centre crop's coordinates."""
+    _check_aug_size(image_size)
+    sid = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+    hw = _src_hw(src_hw, sid.size)
+    h_src, w_src = hw[:, 0], hw[:, 1]
+    head = aug_words(seed, sid, 0, 0)
+    angle = -AUG_DEGREES + 2.0 * AUG_DEGREES * uniforms53(head[:, 0].astype(np.uint32), head[:, 1].astype(np.uint32))
+    flip = (head[:, 2] >> np.uint64(31)) == 0
+    side = (np.minimum(h_src, w_src) * AUG_CENTER).astype(np.int64)
+    top = np.rint((h_src - side) / 2.0).astype(np.int64)
+    left = np.rint((w_src - side) / 2.0).astype(np.int64)
+    tr = aug_words(seed, sid, 0, 1 + np.arange(AUG_TRIES))                                          # [B, 10, 4]
+    frac = AUG_SCALE[0] + (AUG_SCALE[1] - AUG_SCALE[0]) * _u32(tr[..., 0])
+    lo, hi = np.log(AUG_RATIO[0]), np.log(AUG_RATIO[1])
+    ratio = np.exp(lo + (hi - lo) * _u32(tr[..., 1]))
+    area = (side * side)[:, None] * frac
+    bw = np.rint(np.sqrt(area * ratio)).astype(np.int64)
+    bh = np.rint(np.sqrt(area / ratio)).astype(np.int64)
+    ok = (bw > 0) & (bw <= side[:, None]) & (bh > 0) & (bh <= side[:, None])
+    by = _mulhi(tr[..., 2], np.maximum(side[:, None] - bh, 0).astype(np.uint64) + np.uint64(1))
+    bx = _mulhi(tr[..., 3], np.maximum(side[:, None] - bw, 0).astype(np.uint64) + np.uint64(1))
+    first = np.where(ok.any(axis=1), ok.argmax(axis=1), AUG_TRIES)
+    rows, pick = np.arange(sid.size), np.minimum(first, AUG_TRIES - 1)
+    hit = first < AUG_TRIES
+    # the fallback of a side x side image: in_ratio = 1 lies inside [3/4, 4/3], so w = h = side, centred
+    sel = lambda v, fb: np.where(hit, v[rows, pick], fb)
+    return {"angle": angle, "flip": flip, "crop_side": side, "crop_top": top, "crop_left": left,
+            "box_w": sel(bw, side), "box_h": sel(bh, side), "box_top": sel(by, 0), "box_left": sel(bx, 0), "tries": first,
+            "area_frac": sel(frac, np.nan), "ratio": sel(ratio, np.nan)}
+
+
+def _rotation_q16(angle, h_src, w_src):
+    """int64 ``[B, 6]``: the Q16 coefficients with which PIL's ``rotate(angle, NEAREST)`` reads its source -- output pixel (X, Y) is source
+    pixel ``((a0 X + a1 Y + a2) >> 16, (a3 X + a4 Y + a5) >> 16)``.  PIL forms the inverse matrix about the centre (w/2, h/2) in doubles,
+    then ``FIX(v) = floor(65536 v + 1/2)`` of its entries, the offsets with the half-pixel terms folded in."""
+    a = -np.radians(np.mod(np.asarray(angle, dtype=np.float64), 360.0))
+    c, s = np.round(np.cos(a), 15), np.round(np.sin(a), 15)
+    cx, cy = w_src / 2.0, h_src / 2.0
+    m2 = (c * (-cx) + s * (-cy) + 0.0) + cx
+    m5 = ((-s) * (-cx) + c * (-cy) + 0.0) + cy
+    fix = lambda v: np.floor(v * 65536.0 + 0.5).astype(np.int64)
+    return np.stack([fix(c), fix(s), fix(m2 + c * 0.5 + s * 0.5), fix(-s), fix(c), fix(m5 + (-s) * 0.5 + c * 0.5)], axis=1)
+
+
+def augment_image_table(params: dict, src_index, src_hw) -> np.ndarray:
+    """int32 ``[B, AUG_IMAGE_WORDS]``: the quantised row per sample that ``fc_augment_images`` reads, and the only thing
+    ``augment_image_field`` reads of the draws: (source, a0 .. a5 of ``_rotation_q16``, crop left, crop top, crop side, box x0, box y0,
+    box w, box h, flip, 0)."""
+    src = np.asarray(src_index, dtype=np.int64).reshape(-1)
+    hw = _src_hw(src_hw, src.size)
+    rot = _rotation_q16(params["angle"], hw[:, 0], hw[:, 1])
+    cols = [src, *rot.T, params["crop_left"], params["crop_top"], params["crop_side"], params["box_left"], params["box_top"],
+            params["box_w"], params["box_h"], np.asarray(params["flip"]).astype(np.int64), np.zeros_like(src)]
+    tab = np.stack([np.broadcast_to(np.asarray(c, dtype=np.int64), src.shape) for c in cols], axis=1)
+    if tab.size and np.abs(tab).max() > 0x7fffffff:
+        raise ValueError("augmentation table overflows 32 bits")
+    return np.ascontiguousarray(tab.astype(np.int32))
+
+
+def resize_taps(origin: int, extent: int, size: int, limit: int):
+    """PIL's antialiased bilinear coefficients for resizing ``[origin, origin + extent)`` of an axis of ``limit`` pixels to ``size``,
+    in integers: with ``D = 2 max(size, extent)`` and ``c = 2 size origin + (2 j + 1) extent`` (the centre of output j, times 2 size)
+    the taps of output j are ``lo_j <= x < hi_j``, ``lo = max(0, floor((c - D + size) / (2 size)))``, ``hi = min(limit, floor((c + D +
+    size) / (2 size)))``, with numerators ``n = max(0, D - |(2 x + 1) size - c|)`` -- a tent of half-width ``max(1, extent / size)``
+    about the centre -- and the weight is ``n`` over the sum of the output's numerators.  Returns int64 ``(lo [size], hi [size],
+    numerators [size, limit])`` (zero outside the taps)."""
+    j = np.arange(size, dtype=np.int64)
+    d = 2 * max(size, extent)
+    c = 2 * size * origin + (2 * j + 1) * extent
+    lo = np.maximum(0, (c - d + size) // (2 * size))
+    hi = np.minimum(limit, (c + d + size) // (2 * size))
+    x = np.arange(limit, dtype=np.int64)[None, :]
+    n = np.maximum(0, d - np.abs((2 * x + 1) * size - c[:, None]))
+    n = np.where((x >= lo[:, None]) & (x < hi[:, None]), n, 0)
+    return lo, hi, n
+
+
+def _source_bytes(src) -> np.ndarray:
+    a = np.asarray(src)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (1, 3):
+        raise ValueError(f"a source is a uint8 [H, W], [H, W, 1] or [H, W, 3] array, not {a.dtype} {a.shape}")
+    return a
+
+
+def augment_image_field(seed: int, sample_ids, sources, src_index, image_size, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), fill=-1.0,
+                        params=None) -> np.ndarray:
+    """fp64 ``[B, 3, S, S]``: the definition of what ``fc_augment_images`` writes for ``(seed, sample_ids[b])`` on
+    ``sources[src_index[b]]`` (uint8 HWC arrays; one channel is replicated to three) -- upstream's ``image_transforms`` with the rotated
+    image kept virtual:
+
+    - ``R[Y, X]`` = the source at ``((a3 X + a4 Y + a5) >> 16, (a0 X + a1 Y + a2) >> 16)`` (row, column; ``augment_image_table``'s Q16
+      coefficients, which are PIL's own for ``rotate(angle, NEAREST)``, 64-bit integer arithmetic), or ``fill`` outside the source;
+    - the centre crop ``R[top : top + side, left : left + side]``;
+    - PIL's antialiased bilinear resize of the box to ``S x S``: ``out = Wy R Wx^T`` with the rows of ``resize_taps`` -- a separable
+      tent of half-width ``max(1, box / S)`` per axis, taps clamped to the centre crop (as ``Image.resize(..., box=)`` does; upstream
+      crops first, so a tap that here reads the crop beyond the box's edge reads nothing there), weights normalised per output row
+      and column;
+    - the horizontal flip, then ``(v / 255 - mean) / std``.
+
+    Only the weights are floating point, and they are continuous in the position, so no pixel of a comparison hangs on a rounding tie.
+    ``fill`` (a scalar or three values) is in OUTPUT units: a tap outside the source contributes the byte value ``255 (fill std +
+    mean)``; the default -1.0 is black under the default mean and std.  Upstream passes ``fill=means = [0.5, 0.5, 0.5]`` to a rotation
+    of 8-bit PIL images, which is believed to truncate to byte 0, black; that belief cannot be checked without torchvision, which is why
+    it is a parameter.  ``params``: the dict of ``augment_image_params`` with entries replaced (forced angles, flips, boxes)."""
+    s = _check_aug_size(image_size)
+    sid = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+    src_index = np.asarray(src_index, dtype=np.int64).reshape(-1)
+    if src_index.size != sid.size:
+        raise ValueError(f"{src_index.size} source indices for {sid.size} sample ids")
+    if src_index.size and (src_index.min() < 0 or src_index.max() >= len(sources)):
+        raise ValueError(f"source index outside [0, {len(sources)})")
+    srcs = [_source_bytes(a) for a in sources]
+    hw = np.array([srcs[i].shape[:2] for i in src_index], dtype=np.int64).reshape(-1, 2)
+    if params is None:
+        params = augment_image_params(seed, sid, hw, s)
+    tab = augment_image_table(params, src_index, hw).astype(np.int64)
+    mean, std = np.broadcast_to(np.asarray(mean, np.float64), (3,)), np.broadcast_to(np.asarray(std, np.float64), (3,))
+    fill_byte = 255.0 * (np.broadcast_to(np.asarray(fill, np.float64), (3,)) * std + mean)
+    out = np.empty((sid.size, 3, s, s), dtype=np.float64)
+    for b, row in enumerate(tab):
+        a = srcs[row[0]]
+        h_src, w_src = a.shape[:2]
+        a0, a1, a2, a3, a4, a5, left, top, side, bx, by, bw, bh, flip = (int(v) for v in row[1:15])
+        xs, ys = left + np.arange(side, dtype=np.int64)[None, :], top + np.arange(side, dtype=np.int64)[:, None]
+        sx, sy = (a0 * xs + a1 * ys + a2) >> 16, (a3 * xs + a4 * ys + a5) >> 16
+        inside = (sx >= 0) & (sx < w_src) & (sy >= 0) & (sy < h_src)
+        px = a[np.clip(sy, 0, h_src - 1), np.clip(sx, 0, w_src - 1)].astype(np.float64)             # [side, side, C]
+        px = np.broadcast_to(px, (side, side, 3))
+        r = np.where(inside[:, :, None], px, fill_byte[None, None, :])
+        _, _, nx = resize_taps(bx, bw, s, side)
+        _, _, ny = resize_taps(by, bh, s, side)
+        wx, wy = nx / nx.sum(axis=1, keepdims=True), ny / ny.sum(axis=1, keepdims=True)
+        v = np.stack([wy @ r[:, :, c] @ wx.T for c in range(3)])
+        if flip:
+            v = v[:, :, ::-1]
+        out[b] = (v / 255.0 - mean[:, None, None]) / std[:, None, None]
+    return out
+
+
+def augment_midi_params(seed: int, sample_ids, src_hw, image_size, random_roll=True) -> dict:
+    """The draws of upstream's ``midi_transforms`` as ``[B]`` int64 arrays.  ``RandomRoll`` fires (``roll``) with p = 0.5 and then shifts
+    by ``shift_x`` in [-(W // 2), W // 2] and ``shift_y`` in [-24, 24] (two octaves); despite its name it is
+    ``PIL.Image.rotate(0, translate=(shift_x, shift_y))``, a translation with zero fill and nothing circular: the image moves right and
+    down for positive shifts, ``out[y, x] = in[y - shift_y, x - shift_x]``.  ``RandomCrop(image_size)`` follows with ``crop_top`` uniform
+    in [0, H - S] and ``crop_left`` in [0, W - S]."""
+    s = _check_aug_size(image_size)
+    sid = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+    hw = _src_hw(src_hw, sid.size)
+    h_src, w_src = hw[:, 0], hw[:, 1]
+    if hw.size and hw.min() < s:
+        raise ValueError(f"RandomCrop({s}) of a source smaller than that")
+    head, crop = aug_words(seed, sid, 1, 0), aug_words(seed, sid, 1, 1)
+    roll = ((head[:, 0] >> np.uint64(31)) == 0) & bool(random_roll)
+    max_h = w_src // 2
+    sx = _mulhi(head[:, 1], (2 * max_h + 1).astype(np.uint64)) - max_h
+    sy = _mulhi(head[:, 2], 2 * AUG_MAX_V_SHIFT + 1) - AUG_MAX_V_SHIFT
+    return {"roll": roll, "shift_x": np.where(roll, sx, 0), "shift_y": np.where(roll, sy, 0),
+            "crop_top": _mulhi(crop[:, 0], (h_src - s + 1).astype(np.uint64)), "crop_left": _mulhi(crop[:, 1], (w_src - s + 1).astype(np.uint64))}
+
+
+def augment_midi_table(params: dict, src_index) -> np.ndarray:
+    """int32 ``[B, AUG_MIDI_WORDS]``: (source, shift x, shift y, crop left, crop top, 0, 0, 0), the row ``fc_augment_midi`` reads."""
+    src = np.asarray(src_index, dtype=np.int64).reshape(-1)
+    z = np.zeros_like(src)
+    cols = [src, params["shift_x"], params["shift_y"], params["crop_left"], params["crop_top"], z, z, z]
+    tab = np.stack([np.broadcast_to(np.asarray(c, dtype=np.int64), src.shape) for c in cols], axis=1)
+    if tab.size and np.abs(tab).max() > 0x7fffffff:
+        raise ValueError("augmentation table overflows 32 bits")
+    return np.ascontiguousarray(tab.astype(np.int32))
+
+
+def augment_midi_field(seed: int, sample_ids, sources, src_index, image_size, random_roll=True, grayscale=False, binary_thresh=0.3,
+                       out_channels=None, params=None) -> np.ndarray:
+    """fp32 ``[B, out_channels, S, S]``: what ``fc_augment_midi`` writes, bit for bit -- upstream's ``midi_transforms``: the translation
+    and the crop of ``augment_midi_params`` (integers), ``ToTensor``'s ``byte / 255`` in fp32, optionally ``MyRGBToGrayscale`` -- the
+    channel sum ``(u0 + u1) + u2`` in fp32, clamped to [0, 1] -- and, for ``binary_thresh > 0``, ``BinaryGate``: 1 where the fp32 value
+    ``>=`` the threshold rounded to fp32, else 0, as torch compares.  ``out_channels`` (1 or 3; default 1 with ``grayscale``, else 3):
+    the gray value goes to every output channel; otherwise output channel k is source channel k, channel 0 of a one-channel source."""
+    s = _check_aug_size(image_size)
+    sid = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+    src_index = np.asarray(src_index, dtype=np.int64).reshape(-1)
+    if src_index.size != sid.size:
+        raise ValueError(f"{src_index.size} source indices for {sid.size} sample ids")
+    if src_index.size and (src_index.min() < 0 or src_index.max() >= len(sources)):
+        raise ValueError(f"source index outside [0, {len(sources)})")
+    oc = int(out_channels) if out_channels is not None else (1 if grayscale else 3)
+    if oc not in (1, 3):
+        raise ValueError("out_channels is 1 or 3")
+    srcs = [_source_bytes(a) for a in sources]
+    hw = np.array([srcs[i].shape[:2] for i in src_index], dtype=np.int64).reshape(-1, 2)
+    if params is None:
+        params = augment_midi_params(seed, sid, hw, s, random_roll)
+    tab = augment_midi_table(params, src_index).astype(np.int64)
+    out = np.empty((sid.size, oc, s, s), dtype=np.float32)
+    for b, row in enumerate(tab):
+        a = srcs[row[0]]
+        h_src, w_src, ch = a.shape
+        ys = np.arange(s, dtype=np.int64)[:, None] + (row[4] - row[2])
+        xs = np.arange(s, dtype=np.int64)[None, :] + (row[3] - row[1])
+        inside = (ys >= 0) & (ys < h_src) & (xs >= 0) & (xs < w_src)
+        px = np.where(inside[:, :, None], a[np.clip(ys, 0, h_src - 1), np.clip(xs, 0, w_src - 1)], 0)
+        u = px.astype(np.float32) / np.float32(255.0)                                                # [S, S, C] fp32, one rounding
+        if grayscale:
+            g = u[:, :, 0] if ch == 1 else (u[:, :, 0] + u[:, :, 1]) + u[:, :, 2]
+            v = np.broadcast_to(np.minimum(np.maximum(g, np.float32(0)), np.float32(1))[None], (oc, s, s))
+        else:
+            v = np.stack([u[:, :, k if ch == 3 else 0] for k in range(oc)])
+        if binary_thresh > 0:
+            v = (v >= np.float32(binary_thresh)).astype(np.float32)
+        out[b] = v
+    return out

@@ -5,8 +5,9 @@
 batches), ``codec.encode`` on the device, one sample per output item, numeric class directories, the storage / batch budget -- and
 adds two things: ``packed=True`` writes the run as ONE memory-mappable file (``flocoder_amd.data`` format) instead of one pickle
 per latent, and ``rank / world`` give every GPU of a node its own share of the batches and its own shard
-(``<out>/shard_<rank>.fcl``); ``merge_shards`` concatenates them.  The image datasets themselves (torchvision / MIDI
-rendering, preencode_data.py:45-62) are the caller's business.
+(``<out>/shard_<rank>.fcl``); ``merge_shards`` concatenates them.  The augmented batches in front of it (upstream's ``image_transforms`` / ``midi_transforms`` over a
+DataLoader, preencode_data.py:45-62) come from ``flocoder_amd.augment.AugmentedBatches``, made on the device from a resident pool of
+decoded sources; any other loader of ``(images, classes)`` batches serves as well.  MIDI rendering and file discovery stay the caller's.
 """
 from __future__ import annotations
 

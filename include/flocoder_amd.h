@@ -366,6 +366,40 @@ int fc_note_confusion(const float* pred_dev, int pred_channels, const float* tar
 int fc_index_histogram(const int64_t* indices_dev, int64_t n, int levels, int codebook_size, int64_t* counts_inout_dev, int64_t* keys_out_dev,
                        int64_t* bad_rows_inout_dev, void* stream);
 
+/* Pre-encoding augmentation from a resident image pool (replace flocoder/data.py:49-111 image_transforms / midi_transforms; the
+ * definitions are flocoder_amd/noise.py augment_image_field / augment_midi_field).  pool_dev: one uint8 buffer of HWC images;
+ * table_dev [n_sources][4] int64 (16-byte aligned) = (byte offset, H, W, C) per source, C = 1 or 3, H, W <= FC_AUG_MAX_SIDE (the caller vouches that
+ * offset + H W C lies inside the pool; the kernels check every coordinate against H and W).  The random draws are made on the host
+ * (noise.py, Philox key = seed + FC_AUG_KEY_OFFSET) and reach the device as an integer table per sample, so a source pixel is the same
+ * integer decision on both sides; a sample whose source index lies outside [0, n_sources) reads nothing and comes out as `fill`
+ * (images) or zero (MIDI).  One launch on `stream` each; no allocation, no host wait.
+ *
+ * fc_augment_images: out_dev [batch, 3, size, size] fp32; sample_table_dev [batch][FC_AUG_IMAGE_WORDS] int32 =
+ *   (source, a0, a1, a2, a3, a4, a5, crop left, crop top, crop side, box x0, box y0, box w, box h, flip, 0):
+ *   the rotated image R (the source's size) is R[Y][X] = source[(a3 X + a4 Y + a5) >> 16][(a0 X + a1 Y + a2) >> 16] or `fill` outside
+ *   (Q16 coefficients, 64-bit products); the centre crop is R[top .. top + side)[left .. left + side); the box lies in the crop's
+ *   coordinates and is resized to size x size with a tent of half-width max(1, box / size) per axis, taps clamped to the crop, weights
+ *   integer numerators over their integer sum; flip != 0 mirrors the columns; value = (v / 255 - mean[c]) / std[c].  mean, std, fill:
+ *   three host floats each, fill in output units.  16 <= size <= 1024, std finite and > 0, else FC_E_SHAPE / FC_E_ARG.
+ *   A workgroup per 16 x 16 output tile: the tile's window of R goes to LDS as bytes when it has at most FC_AUG_LDS_PIXELS pixels and is
+ *   read through L2 otherwise.
+ * fc_augment_midi: out_dev [batch, out_channels, size, size] fp32; sample_table_dev [batch][FC_AUG_MIDI_WORDS] int32 =
+ *   (source, shift x, shift y, crop left, crop top, 0, 0, 0): u_c[y][x] = source[y + top - shift y][x + left - shift x][c] / 255 in fp32,
+ *   0 outside (a translation with zero fill); gray != 0: g = min(max((u_0 + u_1) + u_2, 0), 1) on every output channel, otherwise
+ *   output channel k is source channel k (channel 0 of a one-channel source); threshold > 0: 1 where the value >= threshold else 0.
+ *   out_channels 1 or 3. */
+#define FC_AUG_KEY_OFFSET 0x415547464C443031ULL /* "AUGFLD01" */
+#define FC_AUG_MIN_SIZE 16
+#define FC_AUG_MAX_SIZE 1024
+#define FC_AUG_MAX_SIDE 8192
+#define FC_AUG_IMAGE_WORDS 16
+#define FC_AUG_MIDI_WORDS 8
+#define FC_AUG_LDS_PIXELS 6144
+int fc_augment_images(float* out_dev, const uint8_t* pool_dev, const int64_t* table_dev, int n_sources, const int* sample_table_dev, int batch,
+                      int size, const float* mean_host, const float* std_host, const float* fill_host, void* stream);
+int fc_augment_midi(float* out_dev, const uint8_t* pool_dev, const int64_t* table_dev, int n_sources, const int* sample_table_dev, int batch,
+                    int size, int out_channels, int gray, float threshold, void* stream);
+
 /* ---- debug / test hooks: not part of the drop-in surface --------------------------------------- */
 /* After an exact-form fc_unet_integrate_guided call: device pointers to the last stage's input state [B,C,H,W], its scaled time rows [B],
  * its w and q = (dv/dx)^T w, while the plan that ran it stands. */
