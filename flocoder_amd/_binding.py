@@ -118,6 +118,7 @@ SIGNATURES = {
     "fc_adam_ema_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.c_float, _i, _vp]),
     "fc_adam_ema_step_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.c_float, _i, _vp, _vp]),
     "fc_debug_conv_wgrad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "fc_debug_conv_wgrad_ex": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _pi, _pi, _pi, _vp]),
     "fc_vae_create": (_i, [_i, C.POINTER(_vp)]),
     "fc_vae_destroy": (None, [_vp]),
     "fc_vae_param_count": (_i, [_vp]),

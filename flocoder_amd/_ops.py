@@ -62,6 +62,23 @@ def fetch_tap(model, name: str, batch: int, decode: Optional[bool] = None) -> to
     return t.permute(0, 3, 1, 2).contiguous()
 
 
+def fetch_tap_rows(model, name: str, batch: int, rows: torch.Tensor, rest_any: bool = False):
+    """``fetch_tap`` for a large batch: the tap is copied to a device tensor, the samples ``rows`` (an int64 device tensor) are gathered
+    there and only they are returned (NCHW, on the device).  With ``rest_any`` also whether any OTHER sample holds a non-zero element
+    (``Tensor.any`` on the device): (rows' tensor, bool)."""
+    p, c, h, w = model.debug_tensor(name)
+    dev = rows.device
+    t = torch.empty(batch, h, w, c, device=dev, dtype=torch.float32)
+    B.check(B.lib().fc_debug_copy(t.data_ptr(), p, t.numel() * 4, B.current_stream(dev)))
+    torch.cuda.synchronize(dev)
+    sel = t[rows].permute(0, 3, 1, 2).contiguous()
+    if not rest_any:
+        return sel
+    keep = torch.ones(batch, dtype=torch.bool, device=dev)
+    keep[rows] = False
+    return sel, bool(t[keep].any())
+
+
 def ot_pairing(source: torch.Tensor, target: torch.Tensor):
     """Greedy OT pairing on the GPU; returns (perm int64 [B], dist [B,B])."""
     bsz = source.shape[0]
@@ -147,15 +164,31 @@ def ot_plan_pairing(plan: torch.Tensor):
     return perm
 
 
-def conv_wgrad_debug(x0: torch.Tensor, dy: torch.Tensor, ks: int, x1=None, *, pad=0, stride=1, upsample=False):
-    """Weight / bias gradient of one convolution from its NCHW input(s) and NCHW output gradient: (dW [O,I,KH,KW], db [O])."""
+def conv_wgrad_debug(x0: torch.Tensor, dy: torch.Tensor, ks: int, x1=None, *, pad=0, stride=1, upsample=False, split_target=0, into=None,
+                     geometry=False):
+    """Weight / bias gradient of one convolution from its NCHW input(s) and NCHW output gradient: (dW [O,I,KH,KW], db [O]).
+    ``split_target``: workgroups wanted per launch (0: the stand-alone default; the backward plan's table entries get 256).  ``into``:
+    a (dW, db) pair the gradient is added to (copies of it; the accumulating instantiations).  ``geometry``: also return
+    {"nsplit", "mtiles", "TB"} as the launch computed them."""
     dev = x0.device
     bsz, c0, hs, ws = x0.shape
     c1 = 0 if x1 is None else x1.shape[1]
     cout = dy.shape[1]
     x0n, x1n, dyn = _nhwc(x0.float()), _nhwc(None if x1 is None else x1.float()), _nhwc(dy.float())
-    dw = torch.full((cout, c0 + c1, ks, ks), float("nan"), device=dev, dtype=torch.float32)
-    db = torch.full((cout,), float("nan"), device=dev, dtype=torch.float32)
-    B.check(B.lib().fc_debug_conv_wgrad(B.ptr(x0n), c0, B.ptr(x1n), c1, B.ptr(dyn), cout, bsz, hs, ws, ks, pad, stride, int(upsample),
-                                        B.ptr(dw), B.ptr(db), B.current_stream(dev)))
-    return dw, db
+    if into is None:
+        dw = torch.full((cout, c0 + c1, ks, ks), float("nan"), device=dev, dtype=torch.float32)
+        db = torch.full((cout,), float("nan"), device=dev, dtype=torch.float32)
+    else:
+        dw, db = (t.to(dev, torch.float32).clone().contiguous() for t in into)
+        assert dw.shape == (cout, c0 + c1, ks, ks) and db.shape == (cout,)
+    if not split_target and into is None and not geometry:
+        B.check(B.lib().fc_debug_conv_wgrad(B.ptr(x0n), c0, B.ptr(x1n), c1, B.ptr(dyn), cout, bsz, hs, ws, ks, pad, stride, int(upsample),
+                                            B.ptr(dw), B.ptr(db), B.current_stream(dev)))
+        return dw, db
+    ns, mt, tb = C.c_int(0), C.c_int(0), C.c_int(0)
+    B.check(B.lib().fc_debug_conv_wgrad_ex(B.ptr(x0n), c0, B.ptr(x1n), c1, B.ptr(dyn), cout, bsz, hs, ws, ks, pad, stride, int(upsample),
+                                           B.ptr(dw), B.ptr(db), int(split_target), int(into is not None), C.byref(ns), C.byref(mt),
+                                           C.byref(tb), B.current_stream(dev)))
+    if not geometry:
+        return dw, db
+    return dw, db, {"nsplit": ns.value, "mtiles": mt.value, "TB": tb.value}

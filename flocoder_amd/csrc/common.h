@@ -112,6 +112,7 @@ struct ConvArgs {
     int stats_tmul = 1, stats_toff = 0;
     int par4 = 0;              // 1: ONE launch carries the four parity classes (quarter q of the grid = class q): w points at [4][4 taps][Cin][Cout]
                                // (w_b3 likewise) and pad_y / pad_x / out_oy / out_ox / stats_toff are derived per workgroup (out_sh = 1, stats_tmul = 4)
+    int split_long_k = 0;      // 1: a reduction of 2048 terms or more at <= 16 pixels per sample goes to the tile whose four waves split it (auto_tile)
     int prec = 0;              // 1: split-bf16 arithmetic where the tile has that form (codec decoders on request; 0 = exact fp32, always for the U-Net)
     ConvFin fin;
 };
@@ -436,6 +437,7 @@ int conv_wgrad_launch(const WgradArgs& a, hipStream_t s, bool acc = false);
 struct WredJob { const float* ws; int nsplit; int nb; size_t stride, nw; int64_t dw, db; int cin, kk; };   // dw / db: offsets into the flat gradient vector (db < 0: none)
 int conv_wgrad_split(const WgradArgs& a, int* nsplit, size_t* part_stride);                   // geometry of the launch conv_wgrad_launch would make
 int conv_wgrad_launch_noreduce(const WgradArgs& a, hipStream_t s);                           // partials into a.ws (nsplit > 1), nothing else
+int conv_wgrad_tiling(const WgradArgs& a, int* nsplit, int* mtiles, int* tb);                // what that launch walks: splits, pixel tiles, samples per tile (tests)
 // Every weight gradient of one kernel size in one launch (full-batch training steps): the entries' inputs must all still be alive
 int conv_wgrad_table_entry(const WgradArgs& a, int64_t dw_off, int64_t db_off, WgradDev* out, int* nblocks, size_t* lds_bytes);
 int conv_wgrad_table_launch(int KS, const WgradDev* jobs_dev, const int2* blocks_dev, int nblocks, size_t lds_bytes, float* grads, hipStream_t s,

@@ -410,6 +410,11 @@ static int auto_tile(const ConvArgs& a) {
     const int hw = a.H * a.W;
     auto blocks = [&](int t) { return (M / kTiles[t].BM) * cdiv(a.Cout, kTiles[t].BN) * (a.par4 ? 4 : 1); };   // (par4: four classes per launch)
     auto ok = [&](int t) { return !(a.w_batch_stride && hw < kTiles[t].BM) && M >= kTiles[t].BM; };
+    // Data gradients of the 256-channel 3x3 layers at 4x4 (unet_backward.hip dgrad_to): at 256 rows the thresholds below give them M128N32,
+    // ONE accumulation chain over K = 2304, whose rounding (7.4e-7 of the result on random data, against 2.7e-7 for four chains of 576)
+    // is past what the backward's pass-through gate allows; the four-chain tile is also the faster one there (256 -> 256: 52.6 against
+    // 62 us, 256 -> 128: 27.4 against 60.6 us, back to back at B = 256)
+    if (a.split_long_k && hw <= 16 && (long)a.Cin * a.KS * a.KS >= 2048 && ok(TILE_M32N32K4)) return TILE_M32N32K4;
     // measured on the SD-VAE shapes (tools/conv_microbench.py --vae, B=16): M256N64 113 / 109 / 101 TFLOP/s at 512@64^2 / 256@128^2 /
     // 128@256^2 against 101 / 97 / 90 for M128N64 and 98 / 105 / 98 for M128N32; the 64-wide column tile only pays for 1x1 layers
     if (a.Cout >= 64 && ok(TILE_M256N64) && blocks(TILE_M256N64) >= 512) {

@@ -367,6 +367,15 @@ int conv_wgrad_split(const WgradArgs& a, int* nsplit, size_t* part_stride) {
     return FC_OK;
 }
 
+int conv_wgrad_tiling(const WgradArgs& a, int* nsplit, int* mtiles, int* tb) {
+    WgradDev d;
+    FC_TRY(wgrad_geometry(a, &d));          // with the caller's workspace, as the launch itself would see it
+    if (nsplit) *nsplit = d.nsplit;
+    if (mtiles) *mtiles = d.mtiles;
+    if (tb) *tb = d.TB;
+    return FC_OK;
+}
+
 static int wgrad_launch_impl(const WgradArgs& a, bool reduce, bool acc, hipStream_t s);
 int conv_wgrad_launch(const WgradArgs& a, hipStream_t s, bool acc) { return wgrad_launch_impl(a, true, acc, s); }
 int conv_wgrad_launch_noreduce(const WgradArgs& a, hipStream_t s) { return wgrad_launch_impl(a, false, false, s); }

@@ -1208,6 +1208,14 @@ int fc_debug_conv(const float* src0, int c0, const float* src1, int c1, const fl
 
 int fc_debug_conv_wgrad(const float* src0, int c0, const float* src1, int c1, const float* dy, int cout, int batch, int hs, int ws, int ksize,
                         int pad, int stride, int upsample, float* dw_out, float* db_out, void* stream) {
+    return fc_debug_conv_wgrad_ex(src0, c0, src1, c1, dy, cout, batch, hs, ws, ksize, pad, stride, upsample, dw_out, db_out, 0, 0, nullptr, nullptr,
+                                  nullptr, stream);
+}
+
+int fc_debug_conv_wgrad_ex(const float* src0, int c0, const float* src1, int c1, const float* dy, int cout, int batch, int hs, int ws, int ksize,
+                           int pad, int stride, int upsample, float* dw_out, float* db_out, int split_target, int accumulate, int* nsplit_out,
+                           int* mtiles_out, int* tb_out, void* stream) {
+    if (split_target < 0) return fail(FC_E_ARG, "fc_debug_conv_wgrad_ex: split_target must not be negative");
     hipStream_t s = static_cast<hipStream_t>(stream);
     FC_TRY(conv_wgrad_init());
     WgradArgs a;
@@ -1216,11 +1224,13 @@ int fc_debug_conv_wgrad(const float* src0, int c0, const float* src1, int c1, co
     a.H = upsample ? hs * 2 : (hs + 2 * pad - ksize) / stride + 1;
     a.W = upsample ? ws * 2 : (ws + 2 * pad - ksize) / stride + 1;
     a.dw = dw_out; a.db = db_out;
+    if (split_target > 0) a.split_target = split_target;
     const size_t need = conv_wgrad_workspace(a);
     float* wsp = nullptr;
     if (need) FC_HIP(hipMalloc(reinterpret_cast<void**>(&wsp), need * sizeof(float)));
     a.ws = wsp; a.ws_floats = need;
-    const int r = conv_wgrad_launch(a, s);
+    int r = conv_wgrad_tiling(a, nsplit_out, mtiles_out, tb_out);
+    if (r == FC_OK) r = conv_wgrad_launch(a, s, accumulate != 0);
     (void)hipStreamSynchronize(s);
     if (wsp) (void)hipFree(wsp);
     return r;

@@ -147,6 +147,7 @@ struct BwdBuilder : PlanBuilder {
         ConvArgs a;
         a.s0.p = dy.p; a.s0.C = O; a.Hs = dy.H; a.Ws = dy.W; a.KS = KS; a.pad = KS - 1 - pad;
         a.w = wp; a.add = add;
+        a.split_long_k = 1;
         conv(a, out, 0, nullptr);
     }
     void accumulate(const Act& target, const Act& src) {   // d(target) (+)= src

@@ -552,6 +552,13 @@ int fc_adam_ema_step_guarded(float* params_dev, const float* grads_dev, float* e
 /* test hook: weight / bias gradient of one convolution (NHWC operands, dw in [O][I][KH][KW]) */
 int fc_debug_conv_wgrad(const float* src0, int c0, const float* src1, int c1, const float* dy, int cout, int batch, int hs, int ws, int ksize,
                         int pad, int stride, int upsample, float* dw_out, float* db_out, void* stream);
+/* The same hook in the forms a training plan uses.  split_target: workgroups wanted per launch (0: the stand-alone default of 1024; the
+ * backward plan gives its table entries 256).  accumulate != 0: the gradient is added to what dw_out / db_out hold (the launches of
+ * fc_unet_backward_accumulate).  nsplit_out / mtiles_out / tb_out (each may be NULL, host integers): the launch's geometry -- how many
+ * workgroups share a 32 x 32 block of dW, how many pixel tiles they walk between them, and how many samples one tile holds. */
+int fc_debug_conv_wgrad_ex(const float* src0, int c0, const float* src1, int c1, const float* dy, int cout, int batch, int hs, int ws, int ksize,
+                           int pad, int stride, int upsample, float* dw_out, float* db_out, int split_target, int accumulate, int* nsplit_out,
+                           int* mtiles_out, int* tb_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * SD-VAE codec  (replaces flocoder/codecs.py:631-663 SD_VAE_Wrapper -> diffusers AutoencoderKL, sd-vae-ft-mse config)

@@ -3,7 +3,15 @@ produced (fixture g10: three consecutive steps of the reference Unet under torch
 
 Tolerances (fp32 throughout; the backward re-associates every reduction, so these are rounding-level bounds, measured values are
 printed with -s): per-parameter gradients rel-L2 <= 2e-5 against the oracle's autograd (measured worst 3.4e-6; <= 5e-3 for tensors whose
-gradient is itself cancellation noise, flagged by a tiny norm); loss 2e-6 relative; parameters / EMA after a step 2e-6 of their magnitude."""
+gradient is itself cancellation noise, flagged by a tiny norm); loss 2e-6 relative; parameters / EMA after a step 2e-6 of their magnitude.
+
+Stand-alone weight gradients (fc_debug_conv_wgrad / _ex against fp64 autograd): rel-L2 < 2e-6 for dW and db up to the reduction length of
+WG_CASES (K = B * Ho * Wo <= 2048), every output channel's slice of dW at 10x that.  Measured worst on the MI355X: the cases whose tile
+loop loops (WG_LOOP_CASES, store and accumulate) dW 5.6e-7, db 1.9e-7, one channel 6.3e-7; the training plans' layers at B = 256 with
+K <= 2048 (WG_PLAN_GEOMETRIES, the dim-16 model's 2x2 level) dW 2.1e-7, db 1.1e-7.  For the longer reductions of those plans (K up to
+262144) the gate is max(2e-6, 4 x the error of torch's fp32 CPU autograd against the same fp64 reference), per case and per tensor:
+fp32 CPU worst dW 2.3e-6 (32->32 3x3 at 32x32), db 6.6e-6 (32->384 1x1 at 32x32), so gates up to 9.0e-6 / 2.7e-5; the kernel's worst
+there dW 1.0e-6, db 7.3e-7, one channel 1.6e-6 (all three 32->384 1x1 at 32x32, 93 tiles per split), at most 0.42 of its gate."""
 import numpy as np
 import pytest
 import torch
@@ -54,6 +62,333 @@ def test_conv_wgrad_matches_autograd(case):
     dw, db = conv_wgrad_debug(x0.to(dev()), dy.to(dev()), ks, None if x1 is None else x1.to(dev()), pad=pad, stride=stride, upsample=bool(ups))
     assert torch.isfinite(dw).all() and torch.isfinite(db).all()
     assert rel_l2(dw.cpu(), w.grad) < 2e-6 and rel_l2(db.cpu(), b.grad) < 2e-6
+
+
+def _wg_out_hw(case):
+    _, _, _, _, H, W, ks, pad, stride, ups = case
+    return (2 * H, 2 * W) if ups else ((H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1)
+
+
+# the longest reduction (output pixels B * Ho * Wo summed per weight element) the 2e-6 gate above has been measured at
+WG_KMAX = max(c[0] * _wg_out_hw(c)[0] * _wg_out_hw(c)[1] for c in WG_CASES)
+_WG_REFS = {}
+
+
+def _wgrad_autograd(x, dy, case, dtype):
+    _, c0, c1, co, _, _, ks, pad, stride, ups = case
+    xin = F.interpolate(x, scale_factor=2, mode="nearest") if ups else x
+    w = torch.zeros(co, c0 + c1, ks, ks, dtype=dtype, requires_grad=True)
+    b = torch.zeros(co, dtype=dtype, requires_grad=True)
+    F.conv2d(xin.to(dtype), w, b, stride=stride, padding=pad).backward(dy.to(dtype))
+    return w.grad, b.grad
+
+
+def _wgrad_problem(case):
+    """Dense random operands of one case, its fp64 autograd gradients and its gates (dW, db), computed once per case.  Up to the
+    reduction length of WG_CASES the gate is theirs, 2e-6.  Beyond it nobody has measured one, so the gate is taken from an
+    independent implementation at the same precision: torch's fp32 CPU autograd against the same fp64 reference, times 4 because the
+    two sum in different blockings (and never below 2e-6)."""
+    if case not in _WG_REFS:
+        B, c0, c1, co, H, W, ks, pad, stride, ups = case
+        g = torch.Generator().manual_seed(hash(case) % 1000)
+        x0 = torch.randn(B, c0, H, W, generator=g)
+        x1 = torch.randn(B, c1, H, W, generator=g) if c1 else None
+        ho, wo = _wg_out_hw(case)
+        dy = torch.randn(B, co, ho, wo, generator=g)
+        x = x0 if x1 is None else torch.cat([x0, x1], 1)
+        dw64, db64 = _wgrad_autograd(x, dy, case, torch.float64)
+        cpu = None
+        if B * ho * wo > WG_KMAX:
+            dw32, db32 = _wgrad_autograd(x, dy, case, torch.float32)
+            cpu = (rel_l2(dw32, dw64), rel_l2(db32, db64))
+        tol = (2e-6, 2e-6) if cpu is None else (max(2e-6, 4 * cpu[0]), max(2e-6, 4 * cpu[1]))
+        _WG_REFS.clear()                                   # one case's operands at a time: the B = 256 ones are 100 MB each
+        _WG_REFS[case] = dict(x0=x0.to(dev()), x1=None if x1 is None else x1.to(dev()), dy=dy.to(dev()), dw=dw64, db=db64, cpu=cpu, tol=tol)
+    return _WG_REFS[case]
+
+
+def _wgrad_gate(tag, case, pr, dw, db, dw_ref=None, db_ref=None):
+    """Whole-tensor rel-L2 of dW and db at the case's gates, every element finite, and every output channel's slice of dW at 10x the
+    tensor gate: one dropped 32 x 32 block of a wide layer is a small part of the whole tensor's norm and all of its own channels'."""
+    dw_ref, db_ref = pr["dw"] if dw_ref is None else dw_ref, pr["db"] if db_ref is None else db_ref
+    dw, db = dw.cpu(), db.cpu()
+    assert torch.isfinite(dw).all() and torch.isfinite(db).all(), tag
+    ew, eb = rel_l2(dw, dw_ref), rel_l2(db, db_ref)
+    d = (dw.double() - dw_ref).flatten(1).norm(dim=1) / dw_ref.flatten(1).norm(dim=1)
+    print(f"[{tag}] K={case[0] * _wg_out_hw(case)[0] * _wg_out_hw(case)[1]} dW {ew:.2e} db {eb:.2e} worst channel {float(d.max()):.2e}; fp32 CPU "
+          + ("not needed" if pr["cpu"] is None else f"dW {pr['cpu'][0]:.2e} db {pr['cpu'][1]:.2e}") + f"; gates {pr['tol'][0]:.1e} {pr['tol'][1]:.1e}")
+    assert ew < pr["tol"][0] and eb < pr["tol"][1], (tag, ew, eb, pr["tol"])
+    assert float(d.max()) < 10 * pr["tol"][0], (tag, int(d.argmax()), float(d.max()))
+    return ew, eb
+
+
+# Small shapes whose pixel-tile loop (conv_wgrad.hip, `for (tile = split; tile < mtiles; tile += nsplit)`) runs more than once per
+# workgroup -- WG_CASES above all have mtiles <= nsplit.  (B, C0, C1, Cout, H, W, KS, pad, stride, ups), the split target that forces
+# the loop, and the geometry the case exists for (nsplit, mtiles, TB), read back from the launch and asserted.
+WG_LOOP_CASES = {
+    "3x3-uneven-4-3-3": ((5, 32, 0, 32, 16, 16, 3, 1, 1, 0), 3, (3, 10, 1)),            # 10 tiles over 3 splits: 4, 3, 3
+    "3x3-4x4-ragged-tile": ((19, 64, 0, 64, 4, 4, 3, 1, 1, 0), 8, (2, 3, 8)),           # 8-sample tiles, the third holds 3 of 8
+    "3x3-4x4-ragged-direct": ((19, 64, 0, 64, 4, 4, 3, 1, 1, 0), 1, (1, 3, 8)),         # ... written to dW without a workspace
+    "3x3-2x2-TB32": ((70, 32, 0, 32, 2, 2, 3, 1, 1, 0), 2, (2, 3, 32)),                 # 32-sample tiles, the third holds 6
+    "1x1-1x1-TB128": ((300, 64, 0, 96, 1, 1, 1, 0, 1, 0), 12, (2, 3, 128)),             # direct1, 128 pixels a tile, the third holds 44
+    "2x2s2-2x2-TB128": ((300, 16, 0, 32, 2, 2, 2, 0, 2, 0), 2, (2, 3, 128)),            # 128-sample tiles in the staged body
+    "2x2s2": ((6, 16, 0, 32, 16, 16, 2, 0, 2, 0), 2, (2, 3, 2)),
+    "5x5-concat": ((3, 8, 4, 12, 16, 16, 5, 2, 1, 0), 4, (4, 6, 1)),
+    "3x3-concat-C0-48": ((7, 48, 16, 40, 16, 16, 3, 1, 1, 0), 12, (3, 14, 1)),          # C0 not a multiple of 32: 5, 5, 4 tiles
+    "3x3-upsample": ((6, 32, 0, 16, 8, 8, 3, 1, 1, 1), 5, (5, 12, 1)),                  # nearest x2 in the loader: 3, 3, 2, 2, 2
+    "3x3-upsample-TB8-direct": ((11, 64, 0, 32, 2, 2, 3, 1, 1, 1), 1, (1, 2, 8)),       # ... with a ragged second tile (3 of 8)
+    "3x3-8x32": ((3, 32, 0, 32, 8, 32, 3, 1, 1, 0), 4, (4, 6, 1)),
+    "3x3-32x8": ((3, 32, 0, 32, 32, 8, 3, 1, 1, 0), 4, (4, 6, 1)),
+    "3x3-direct-8-tiles": ((4, 32, 0, 32, 16, 16, 3, 1, 1, 0), 1, (1, 8, 1)),           # nsplit = 1: acc[] over 8 tiles straight to dW
+    "1x1-direct-6-tiles": ((3, 32, 0, 96, 16, 16, 1, 0, 1, 0), 1, (1, 6, 1)),
+    "1x1-uneven-4-3-3": ((5, 32, 0, 96, 16, 16, 1, 0, 1, 0), 9, (3, 10, 1)),
+    "1x1-concat-8x32": ((3, 20, 12, 24, 8, 32, 1, 0, 1, 0), 2, (2, 6, 1)),
+}
+
+
+@pytest.mark.parametrize("accumulate", [False, True], ids=["store", "accumulate"])
+@pytest.mark.parametrize("cid", list(WG_LOOP_CASES))
+def test_conv_wgrad_tile_loop_matches_autograd(cid, accumulate):
+    """Every workgroup (or at least one) walks several pixel tiles: accumulation in acc[] / bsum across tiles, re-staging of the LDS
+    patch, uneven shares, ragged multi-sample tiles that are not the first.  ``accumulate``: the ACC instantiations on top of a known
+    random dW / db, on the direct (nsplit = 1) and the workspace (nsplit > 1) write paths."""
+    from flocoder_amd._ops import conv_wgrad_debug
+    case, split_target, want = WG_LOOP_CASES[cid]
+    pr = _wgrad_problem(case)
+    into, dw_ref, db_ref = None, pr["dw"], pr["db"]
+    if accumulate:                          # prefill of the gradient's own size, so that neither term hides the other
+        g = torch.Generator().manual_seed(77)
+        into = (torch.randn(dw_ref.shape, generator=g) * float(dw_ref.std()), torch.randn(db_ref.shape, generator=g) * float(db_ref.std()))
+        dw_ref, db_ref = dw_ref + into[0].double(), db_ref + into[1].double()
+    dw, db, geo = conv_wgrad_debug(pr["x0"], pr["dy"], case[6], pr["x1"], pad=case[7], stride=case[8], upsample=bool(case[9]),
+                                   split_target=split_target, into=into, geometry=True)
+    assert (geo["nsplit"], geo["mtiles"], geo["TB"]) == want, (cid, geo)
+    assert geo["mtiles"] > geo["nsplit"], (cid, geo)
+    assert case[0] * _wg_out_hw(case)[0] * _wg_out_hw(case)[1] <= WG_KMAX
+    _wgrad_gate(cid + ("+acc" if accumulate else ""), case, pr, dw, db, dw_ref, db_ref)
+
+
+def test_conv_wgrad_hook_defaults_are_the_plain_hook():
+    """fc_debug_conv_wgrad_ex with split_target 0 and no accumulation is fc_debug_conv_wgrad, bit for bit, and reports its geometry."""
+    from flocoder_amd._ops import conv_wgrad_debug
+    case = WG_CASES[1]
+    pr = _wgrad_problem(case)
+    dw0, db0 = conv_wgrad_debug(pr["x0"], pr["dy"], case[6], pr["x1"], pad=case[7], stride=case[8])
+    dw1, db1, geo = conv_wgrad_debug(pr["x0"], pr["dy"], case[6], pr["x1"], pad=case[7], stride=case[8], geometry=True)
+    assert torch.equal(dw0, dw1) and torch.equal(db0, db1)
+    assert (geo["nsplit"], geo["mtiles"], geo["TB"]) == (2, 2, 2), geo       # 3 samples at 8x8: two 2-sample tiles, one each
+    dw2, _, geo2 = conv_wgrad_debug(pr["x0"], pr["dy"], case[6], pr["x1"], pad=case[7], stride=case[8], split_target=1024, geometry=True)
+    assert torch.equal(dw0, dw2) and geo2 == geo
+
+
+# Every distinct convolution geometry of the two shipped training plans at their batch of 256 (configs/common/flow.yaml): the dim-32 /
+# 102-class model at 4x32x32 and the dim-16 model at 4x16x16.  (C0, C1, Cout, H, W, KS, pad, stride, ups) of the layer's source, then
+# what the launch walks at that batch: TB, mtiles, and nsplit at the split target of a table entry (256) and stand-alone (1024).
+WG_PLAN_BATCH = 256
+WG_PLAN_GEOMETRIES = {
+    "d32c102": (32, [
+        (4, 0, 32, 32, 32, 1, 0, 1, 0, 1, 2048, 256, 256),      # init_conv
+        (32, 0, 4, 32, 32, 1, 0, 1, 0, 1, 2048, 256, 256),      # final_conv
+        (32, 0, 384, 32, 32, 1, 0, 1, 0, 1, 2048, 22, 86),      # downs.0.2.fn.fn.to_qkv (+1)
+        (32, 32, 32, 32, 32, 1, 0, 1, 0, 1, 2048, 128, 256),    # ups.3.0.res_conv (+2)
+        (128, 0, 32, 32, 32, 1, 0, 1, 0, 1, 2048, 64, 256),     # downs.0.2.fn.fn.to_out.0 (+1)
+        (32, 0, 32, 32, 32, 2, 0, 2, 0, 1, 512, 256, 256),      # downs.0.3.1
+        (32, 0, 32, 32, 32, 3, 1, 1, 0, 1, 2048, 256, 256),     # downs.0.0.block1.proj (+7)
+        (32, 32, 32, 32, 32, 3, 1, 1, 0, 1, 2048, 128, 256),    # ups.3.0.block1.proj (+2)
+        (32, 0, 384, 16, 16, 1, 0, 1, 0, 1, 512, 22, 86),       # downs.1.2.fn.fn.to_qkv
+        (64, 0, 384, 16, 16, 1, 0, 1, 0, 1, 512, 11, 43),       # ups.2.2.fn.fn.to_qkv
+        (64, 32, 64, 16, 16, 1, 0, 1, 0, 1, 512, 43, 171),      # ups.2.0.res_conv (+1)
+        (128, 0, 32, 16, 16, 1, 0, 1, 0, 1, 512, 64, 256),      # downs.1.2.fn.fn.to_out.0
+        (128, 0, 64, 16, 16, 1, 0, 1, 0, 1, 512, 32, 128),      # ups.2.2.fn.fn.to_out.0
+        (32, 0, 64, 16, 16, 2, 0, 2, 0, 2, 128, 128, 128),      # downs.1.3.1
+        (32, 0, 32, 16, 16, 3, 1, 1, 0, 1, 512, 256, 256),      # downs.1.0.block1.proj (+3)
+        (64, 0, 32, 16, 16, 3, 1, 1, 1, 1, 2048, 128, 256),     # ups.2.3.1
+        (64, 0, 64, 16, 16, 3, 1, 1, 0, 1, 512, 64, 256),       # ups.2.0.block2.proj (+1)
+        (64, 32, 64, 16, 16, 3, 1, 1, 0, 1, 512, 43, 171),      # ups.2.0.block1.proj (+1)
+        (64, 0, 384, 8, 8, 1, 0, 1, 0, 2, 128, 11, 43),         # downs.2.2.fn.fn.to_qkv
+        (128, 0, 64, 8, 8, 1, 0, 1, 0, 2, 128, 32, 128),        # downs.2.2.fn.fn.to_out.0
+        (128, 0, 128, 8, 8, 1, 0, 1, 0, 2, 128, 16, 64),        # ups.1.2.fn.fn.to_out.0
+        (128, 0, 384, 8, 8, 1, 0, 1, 0, 2, 128, 6, 22),         # ups.1.2.fn.fn.to_qkv
+        (128, 64, 128, 8, 8, 1, 0, 1, 0, 2, 128, 11, 43),       # ups.1.0.res_conv (+1)
+        (64, 0, 128, 8, 8, 2, 0, 2, 0, 8, 32, 32, 32),          # downs.2.3.1
+        (64, 0, 64, 8, 8, 3, 1, 1, 0, 2, 128, 64, 128),         # downs.2.0.block1.proj (+3)
+        (128, 0, 64, 8, 8, 3, 1, 1, 1, 1, 512, 32, 128),        # ups.1.3.1
+        (128, 0, 128, 8, 8, 3, 1, 1, 0, 2, 128, 16, 64),        # ups.1.0.block2.proj (+1)
+        (128, 64, 128, 8, 8, 3, 1, 1, 0, 2, 128, 11, 43),       # ups.1.0.block1.proj (+1)
+        (128, 0, 128, 4, 4, 1, 0, 1, 0, 8, 32, 16, 32),         # downs.3.2.fn.fn.to_out.0
+        (128, 0, 256, 4, 4, 1, 0, 1, 0, 8, 32, 8, 32),          # mid_attn.fn.fn.to_out (+1)
+        (128, 0, 384, 4, 4, 1, 0, 1, 0, 8, 32, 6, 22),          # downs.3.2.fn.fn.to_qkv
+        (256, 0, 384, 4, 4, 1, 0, 1, 0, 8, 32, 3, 11),          # mid_attn.fn.fn.to_qkv (+1)
+        (256, 128, 256, 4, 4, 1, 0, 1, 0, 8, 32, 3, 11),        # ups.0.0.res_conv (+1)
+        (128, 0, 128, 4, 4, 3, 1, 1, 0, 8, 32, 16, 32),         # downs.3.0.block1.proj (+3)
+        (128, 0, 256, 4, 4, 3, 1, 1, 0, 8, 32, 8, 32),          # downs.3.3
+        (256, 0, 128, 4, 4, 3, 1, 1, 1, 2, 128, 8, 32),         # ups.0.3.1
+        (256, 0, 256, 4, 4, 3, 1, 1, 0, 8, 32, 4, 16),          # mid_block1.block1.proj (+5)
+        (256, 128, 256, 4, 4, 3, 1, 1, 0, 8, 32, 3, 11),        # ups.0.0.block1.proj (+1)
+    ]),
+    "d16c10": (16, [
+        (4, 0, 16, 16, 16, 1, 0, 1, 0, 1, 512, 256, 256),       # init_conv
+        (16, 0, 4, 16, 16, 1, 0, 1, 0, 1, 512, 256, 256),       # final_conv
+        (16, 0, 384, 16, 16, 1, 0, 1, 0, 1, 512, 22, 86),       # downs.0.2.fn.fn.to_qkv (+1)
+        (16, 16, 16, 16, 16, 1, 0, 1, 0, 1, 512, 256, 256),     # ups.3.0.res_conv (+2)
+        (128, 0, 16, 16, 16, 1, 0, 1, 0, 1, 512, 64, 256),      # downs.0.2.fn.fn.to_out.0 (+1)
+        (16, 0, 16, 16, 16, 2, 0, 2, 0, 2, 128, 128, 128),      # downs.0.3.1
+        (16, 0, 16, 16, 16, 3, 1, 1, 0, 1, 512, 256, 256),      # downs.0.0.block1.proj (+7)
+        (16, 16, 16, 16, 16, 3, 1, 1, 0, 1, 512, 256, 256),     # ups.3.0.block1.proj (+2)
+        (16, 0, 384, 8, 8, 1, 0, 1, 0, 2, 128, 22, 86),         # downs.1.2.fn.fn.to_qkv
+        (32, 0, 384, 8, 8, 1, 0, 1, 0, 2, 128, 22, 86),         # ups.2.2.fn.fn.to_qkv
+        (32, 16, 32, 8, 8, 1, 0, 1, 0, 2, 128, 128, 128),       # ups.2.0.res_conv (+1)
+        (128, 0, 16, 8, 8, 1, 0, 1, 0, 2, 128, 64, 128),        # downs.1.2.fn.fn.to_out.0
+        (128, 0, 32, 8, 8, 1, 0, 1, 0, 2, 128, 64, 128),        # ups.2.2.fn.fn.to_out.0
+        (16, 0, 32, 8, 8, 2, 0, 2, 0, 8, 32, 32, 32),           # downs.1.3.1
+        (16, 0, 16, 8, 8, 3, 1, 1, 0, 2, 128, 128, 128),        # downs.1.0.block1.proj (+3)
+        (32, 0, 16, 8, 8, 3, 1, 1, 1, 1, 512, 256, 256),        # ups.2.3.1
+        (32, 0, 32, 8, 8, 3, 1, 1, 0, 2, 128, 128, 128),        # ups.2.0.block2.proj (+1)
+        (32, 16, 32, 8, 8, 3, 1, 1, 0, 2, 128, 128, 128),       # ups.2.0.block1.proj (+1)
+        (32, 0, 384, 4, 4, 1, 0, 1, 0, 8, 32, 22, 32),          # downs.2.2.fn.fn.to_qkv
+        (64, 0, 384, 4, 4, 1, 0, 1, 0, 8, 32, 11, 32),          # ups.1.2.fn.fn.to_qkv
+        (64, 32, 64, 4, 4, 1, 0, 1, 0, 8, 32, 32, 32),          # ups.1.0.res_conv (+1)
+        (128, 0, 32, 4, 4, 1, 0, 1, 0, 8, 32, 32, 32),          # downs.2.2.fn.fn.to_out.0
+        (128, 0, 64, 4, 4, 1, 0, 1, 0, 8, 32, 32, 32),          # ups.1.2.fn.fn.to_out.0
+        (32, 0, 64, 4, 4, 2, 0, 2, 0, 32, 8, 8, 8),             # downs.2.3.1
+        (32, 0, 32, 4, 4, 3, 1, 1, 0, 8, 32, 32, 32),           # downs.2.0.block1.proj (+3)
+        (64, 0, 32, 4, 4, 3, 1, 1, 1, 2, 128, 128, 128),        # ups.1.3.1
+        (64, 0, 64, 4, 4, 3, 1, 1, 0, 8, 32, 32, 32),           # ups.1.0.block2.proj (+1)
+        (64, 32, 64, 4, 4, 3, 1, 1, 0, 8, 32, 32, 32),          # ups.1.0.block1.proj (+1)
+        (64, 0, 384, 2, 2, 1, 0, 1, 0, 32, 8, 8, 8),            # downs.3.2.fn.fn.to_qkv
+        (128, 0, 64, 2, 2, 1, 0, 1, 0, 32, 8, 8, 8),            # downs.3.2.fn.fn.to_out.0
+        (128, 0, 128, 2, 2, 1, 0, 1, 0, 32, 8, 8, 8),           # mid_attn.fn.fn.to_out (+1)
+        (128, 0, 384, 2, 2, 1, 0, 1, 0, 32, 8, 6, 8),           # mid_attn.fn.fn.to_qkv (+1)
+        (128, 64, 128, 2, 2, 1, 0, 1, 0, 32, 8, 8, 8),          # ups.0.0.res_conv (+1)
+        (64, 0, 64, 2, 2, 3, 1, 1, 0, 32, 8, 8, 8),             # downs.3.0.block1.proj (+3)
+        (64, 0, 128, 2, 2, 3, 1, 1, 0, 32, 8, 8, 8),            # downs.3.3
+        (128, 0, 64, 2, 2, 3, 1, 1, 1, 8, 32, 32, 32),          # ups.0.3.1
+        (128, 0, 128, 2, 2, 3, 1, 1, 0, 32, 8, 8, 8),           # mid_block1.block1.proj (+5)
+        (128, 64, 128, 2, 2, 3, 1, 1, 0, 32, 8, 8, 8),          # ups.0.0.block1.proj (+1)
+    ]),
+}
+
+
+def plan_conv_geometries(sd, H, W):
+    """{(C0, C1, Cout, H, W, KS, pad, stride, ups): [weight names]} of every convolution the backward plan takes a weight gradient of
+    (unet_backward.hip wgrad(...) calls), walked from the state dict's shapes in the order of the forward (unet.py:289-372): Downsample
+    is the 2x2 stride-2 form of its [O][4I][1][1] weight, Upsample reads its source through the nearest x2 loader, a block behind a
+    concat reads two sources."""
+    from oracle import flow_oracle as fo
+    L = fo.unet_meta(sd)["n_levels"]
+    geo = {}
+
+    def add(name, c1, h, w, pad=0, stride=1, ups=0):
+        co, ci, ks, _ = sd[name + ".weight"].shape
+        if stride == 2:
+            ci, ks = ci // 4, 2
+        geo.setdefault((ci - c1, c1, co, h, w, ks, pad, stride, ups), []).append(name)
+
+    def resblock(p, c1, h, w):
+        add(p + ".block1.proj", c1, h, w, 1)
+        add(p + ".block2.proj", 0, h, w, 1)
+        if p + ".res_conv.weight" in sd:
+            add(p + ".res_conv", c1, h, w)
+
+    def attn(p, to_out, h, w):
+        add(p + ".fn.fn.to_qkv", 0, h, w)
+        add(p + ".fn.fn." + to_out, 0, h, w)
+
+    add("init_conv", 0, H, W)
+    h, w, skips = H, W, []
+    for i in range(L):
+        p = f"downs.{i}"
+        resblock(p + ".0", 0, h, w)
+        resblock(p + ".1", 0, h, w)
+        attn(p + ".2", "to_out.0", h, w)
+        skips += [sd[p + ".0.block1.proj.weight"].shape[0]] * 2
+        if i == L - 1:
+            add(p + ".3", 0, h, w, 1)
+        else:
+            add(p + ".3.1", 0, h, w, 0, 2)
+            h, w = h // 2, w // 2
+    resblock("mid_block1", 0, h, w)
+    attn("mid_attn", "to_out", h, w)
+    resblock("mid_block2", 0, h, w)
+    for i in range(L):
+        p = f"ups.{i}"
+        resblock(p + ".0", skips.pop(), h, w)
+        resblock(p + ".1", skips.pop(), h, w)
+        attn(p + ".2", "to_out.0", h, w)
+        if i == L - 1:
+            add(p + ".3", 0, h, w, 1)
+        else:
+            add(p + ".3.1", 0, h, w, 1, 1, 1)
+            h, w = 2 * h, 2 * w
+    resblock("final_res_block", sd["init_conv.weight"].shape[0], h, w)
+    add("final_conv", 0, h, w)
+    return geo
+
+
+def _backward_plan_wgrads(sd, B, hw):
+    """Modules of the conv_wgrad entries of the B-row backward plan (fc_unet_backward_op_info)."""
+    import ctypes as C
+    from flocoder_amd import _binding as Bn
+    from flocoder_amd.unet import Unet
+    from oracle import flow_oracle as fo
+    meta = fo.unet_meta(sd)
+    m = Unet(dim=meta["dim"], dim_mults=(1, 2, 4, 8), channels=4, n_classes=meta["n_classes"])
+    m.load_state_dict(sd, strict=True)
+    m = m.to(dev()).train()
+    lib = Bn.lib()
+    hnd = m._native(dev())
+    Bn.check(lib.fc_unet_train_reserve(hnd, B, hw, hw))
+    mods = []
+    for i in range(lib.fc_unet_backward_launches(hnd)):
+        k, mod = C.c_char_p(), C.c_char_p()
+        Bn.check(lib.fc_unet_backward_op_info(hnd, i, C.byref(k), C.byref(mod)))
+        if k.value.decode().split("<")[0] == "conv_wgrad":
+            mods.append(mod.value.decode())
+    return mods
+
+
+@pytest.mark.parametrize("tag", list(WG_PLAN_GEOMETRIES))
+def test_the_geometry_table_is_the_training_plans(tag):
+    """WG_PLAN_GEOMETRIES is a literal; this holds it to the model: the table equals the set of geometries walked from the state
+    dict's shapes, and the B = 256 backward plan has exactly one conv_wgrad entry per convolution weight that walk visited."""
+    hw, table = WG_PLAN_GEOMETRIES[tag]
+    sd = synth_state_dict(load_golden("g3_unet_" + tag)["shapes"], 1)
+    geo = plan_conv_geometries(sd, hw, hw)
+    assert sorted(geo) == sorted(r[:9] for r in table) and len(table) == len({r[:9] for r in table})
+    visited = sorted(n for names in geo.values() for n in names)
+    assert visited == sorted(k[:-len(".weight")] for k, v in sd.items() if v.dim() == 4)
+    mods = _backward_plan_wgrads(sd, WG_PLAN_BATCH, hw)
+    assert len(mods) == len(visited), (len(mods), len(visited), sorted(set(mods)))
+
+
+def _plan_params():
+    return [pytest.param(tag, row, id=f"{tag}-" + "x".join(str(v) for v in row[:9])) for tag, (_, rows) in WG_PLAN_GEOMETRIES.items() for row in rows]
+
+
+@pytest.mark.parametrize("tag,row", _plan_params())
+def test_conv_wgrad_at_the_training_plans_geometry(tag, row):
+    """Each layer geometry of the shipped training plans at B = 256, dense random operands, at the split target of a table entry (256)
+    and stand-alone (1024): the tile walk is the production one (2048 tiles over 256 splits at level 0, 32 eight-sample tiles over 3
+    to 16 splits at 4x4), asserted from the launch's own geometry."""
+    from flocoder_amd._ops import conv_wgrad_debug
+    case = (WG_PLAN_BATCH,) + tuple(row[:9])
+    tb, mtiles, ns256, ns1024 = row[9:]
+    pr = _wgrad_problem(case)
+    for st, ns in ((256, ns256), (0, ns1024)):
+        dw, db, geo = conv_wgrad_debug(pr["x0"], pr["dy"], case[6], pr["x1"], pad=case[7], stride=case[8], upsample=bool(case[9]),
+                                       split_target=st, geometry=True)
+        assert (geo["nsplit"], geo["mtiles"], geo["TB"]) == (ns, mtiles, tb), (tag, row, st, geo)
+        _wgrad_gate(f"{tag} {row[:9]} split_target={st or 1024} tiles/split={mtiles / ns:.1f}", case, pr, dw, db)
+
+
+def test_the_training_plan_cases_loop():
+    """What the table above is for: most layers of both plans give a workgroup several tiles at the table's split target, some an uneven
+    share, and the multi-sample tiles are among them.  A change of the split constants that turns them back into one-tile launches fails
+    here (and in the per-case geometry assertions)."""
+    rows = [r for _, rs in WG_PLAN_GEOMETRIES.values() for r in rs]
+    loop256 = [r for r in rows if r[10] > r[11]]
+    assert len(rows) == 76 and len(loop256) == 51 and len([r for r in rows if r[10] > r[12]]) == 40
+    assert len([r for r in loop256 if r[10] % r[11]]) == 19 and {r[9] for r in loop256} == {1, 2, 8, 32}
 
 
 def _model(tag_shapes, seed, **kw):
