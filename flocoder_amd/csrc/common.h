@@ -68,6 +68,30 @@ struct ConvSrc {
 // Fused tail of a Block (unet.py:66-72,96): instead of storing the raw convolution output, the workgroups of one sample (or
 // sample group) exchange their GroupNorm partials through `stats_out` and a per-group arrival counter, then finish
 // out = SiLU(GN(acc)) + res straight from the accumulators.  Needs every workgroup of the launch resident at once.
+// The step boundary of the legacy Euler sampler inside a Block-closing tail (conv_dev.h FL_STEP): what final_res_block's closing launch needs
+// to run final_conv, the update y += v dt and the next evaluation's init_conv per pixel, to publish the next interval's time and to fetch
+// the next conditioning slice.  Device resident, one per plan, written once per call (step_close_setup_launch) -- the kernel's parameter
+// block carries one pointer to it (ConvFin::step).
+struct StepCloseHdr {
+    float* y = nullptr;             // NCHW state of the integrator, updated in place
+    const float* ts = nullptr;      // the call's time grid
+    float *sc = nullptr, *tvec = nullptr;
+    int *step = nullptr, *evalc = nullptr;
+    const float* ss_all = nullptr;  // conditioning rows of every evaluation [evaluation][rows][S] ...
+    float* ss_dst = nullptr;        // ... and the plan's table [rows][S] the next evaluation's slice goes to
+    float dt = 0.f, t_scale = 1.f;
+    int rows = 0, S = 0, n_slices = 0;
+};
+constexpr int kStepDim = 32, kStepCh = 4;      // the one shape the step-closing flavour exists for: dim 32, 4 latent channels
+constexpr int kStepWeights = kStepDim * kStepCh + kStepCh + kStepCh * kStepDim + kStepDim;
+struct StepClose {
+    StepCloseHdr h;
+    float w[kStepWeights];          // final_conv weight transposed to [ch][dim] | bias [ch] | init_conv weight [ch][dim] | bias [dim]
+    unsigned base[4];               // [rows]: sample b's epoch of this launch's arrival counter at the call's first evaluation (allocated behind the struct)
+};
+int step_close_setup_launch(StepClose* blk, const StepCloseHdr& h, const float* fw, const float* fb, const float* iw, const float* ib,
+                            const unsigned* sync, int gsz, hipStream_t s);
+
 struct ConvFin {
     const float* gamma = nullptr;   // != nullptr switches the tail on
     const float* beta = nullptr;
@@ -77,6 +101,7 @@ struct ConvFin {
     unsigned* sync = nullptr;       // one arrival counter per sample group, never reset: arrival number / group size + 1 = this launch's epoch
     unsigned long long* gran = nullptr;   // [B][G][T][2] tagged granules {epoch << 32 | float bits}: the partials AS the hand-off (no flag, no fence)
     int* err = nullptr;             // set to 1 if a wait ever times out
+    const StepClose* step = nullptr;   // != nullptr: the step-closing flavour (above); `out` is then the plan's init_conv output
 };
 
 struct ConvArgs {
@@ -128,9 +153,11 @@ struct ConvGeom {  // filled by conv_plan(): what a consumer must know about `st
     int T1 = 0;        // fused tail: slots / count of the GroupNorm(1) partials of the final value
     float n_t1 = 0.f;
     int groups = 0;    // fused tail: arrival counters needed (sample groups)
+    int gsz = 0;       // fused tail: workgroups that arrive at one counter per launch
     int fin_local = 0; // fused tail: every GroupNorm group of the output lies inside one workgroup's tile (no meeting, no residency condition)
 };
 bool conv_fin_possible(const ConvArgs& a, int tile);   // the fused tail's residency / shape conditions hold for this launch
+bool conv_step_close_possible(const ConvArgs& a, int tile);   // ... and the launch is the one the step-closing flavour is compiled for
 int conv_init();
 unsigned long long* conv_stamp_buffer();
 void conv_set_stamp_buffer(unsigned long long* p);  // diagnostics: phase stamps of the pipelined kernel
@@ -249,6 +276,9 @@ float linattn_fused_nt(int n, int C);
 int linattn_fused_launch(const LaArgs& a, hipStream_t s);
 void linattn_route_log_set(bool on);                // diagnostics: the instantiations every fused fast-path launch takes (linattn_fused.hip)
 std::string linattn_route_log_get();
+void step_route_log_set(bool on);                   // diagnostics: the launches at the step boundary, as enqueued (elementwise.hip): one line per
+std::string step_route_log_get();                   // init_conv / final_conv launch and per step-closing convolution ("step_close")
+void step_route_log_add(const char* what);
 bool linattn_fused_meeting_ok(int B, int n, int C);   // may LaArgs::gran be set: the apply launch's whole grid is resident at this shape
 // The whole Residual(PreNorm(LinearAttention)) module in two launches, a workgroup per (sample, head) then per sample (n <= 64 positions)
 int linattn_sample_init();

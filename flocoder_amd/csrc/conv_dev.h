@@ -104,6 +104,7 @@ __device__ __forceinline__ void conv_params_from_lanes(ConvDev& p) {
     a.stats_out = as_global(a.stats_out); a.res_w = as_global(a.res_w); a.res_b = as_global(a.res_b); a.res_out = as_global(a.res_out);
     a.fin.gamma = as_global(a.fin.gamma); a.fin.beta = as_global(a.fin.beta); a.fin.res = as_global(a.fin.res);
     a.fin.gn1_out = as_global(a.fin.gn1_out); a.fin.sync = as_global(a.fin.sync); a.fin.gran = as_global(a.fin.gran); a.fin.err = as_global(a.fin.err);
+    a.fin.step = as_global(a.fin.step);
     p.zeros16 = as_global(p.zeros16); p.stamps = as_global(p.stamps);
 }
 
@@ -115,6 +116,10 @@ __device__ __forceinline__ void conv_params_from_lanes(ConvDev& p) {
 constexpr int FL_FIN = 1, FL_RES = 2, FL_POST = 4, FL_XF = 8, FL_CAT = 16, FL_STAMP = 32, FL_STATS = 64, FL_GN1 = 128, FL_POSTOP = 256,
               FL_NARROW = 512, FL_MULTI = 1024, FL_MEET = 2048, FL_ALL = 4095, FL_W4 = 4096;
 constexpr int FL_WW = 8192;
+constexpr int FL_STEP = 16384;
+// (16384, outside FL_ALL, one flavour: final_res_block's closing launch inside a replayed Euler step.  Its tail also closes the STEP -- per
+// pixel final_conv, y += v dt, the next evaluation's init_conv, stored to the plan's init_conv output instead of the Block output -- and
+// the launch publishes the next interval's time and fetches the next conditioning slice.  conv_epilogue "STEP")
 // (4096, outside FL_ALL: the 32-row tile at 3x3 reads its weights from the k-step-quad copy -- ConvArgs::w4 -- 16 bytes per lane)
 // (8192, FL_W4 Block-closing flavours only: the WHOLE input window -- every Cin chunk, transformed -- is staged into LDS once, in the
 // prologue, by all twelve waves; the K loop then holds neither staging nor chunk barriers.  conv_pipe.hip "WW")
@@ -148,9 +153,12 @@ constexpr bool geo_conv1_mask(int FL) { return (FL & ~(FL_W4 | FL_STAMP)) == FL_
 template <int WM, int WN, int WK, int MT, int NT, int FL = FL_ALL, int GEO = 0>
 __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT][NT], f32x16 (&accr)[MT][NT], float* smem, int tid, int lane,
                                               int wave, int b0, int y0, int x0, int n0, int tx, int ty, bool active = true,
-                                              int nthr = 256, const float* pre = nullptr, bool staged_dead = false) {
+                                              int nthr = 256, const float* pre = nullptr, bool staged_dead = false,
+                                              const StepCloseHdr* shdr = nullptr) {
     // `pre` (optional, 4*NT floats in the caller's registers): bias | res_conv bias | tail gamma | tail beta of this lane's columns,
     // requested before the main loop -- loaded here they are a cold miss on the epilogue's critical path (~2 k cycles per launch).
+    // `shdr` (FL_STEP only): the header of the launch's StepClose block in the caller's registers, read in the kernel's prologue -- read here it
+    // is a cold round trip in front of every address the step's loads need.
     // `active` = this wave holds accumulators (false for the loader waves of the producer/consumer kernel, which only
     // take part in the barriers and the statistics reduction); `nthr` = threads in the workgroup.
     constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
@@ -421,6 +429,19 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
     }
     if (do_stats && !fast_stats && !pair_stats) block_sums();
 
+    // ---- STEP (FL_STEP): this launch also closes the Euler step.  Thread t of the workgroup's 512 is output channel t & 3 of final_conv
+    // at pixel t >> 2 of the tile (a pixel's four threads are neighbouring lanes); the staging waves, idle in a tail, also move the boundary
+    // weights and the conditioning slice.  Nothing is requested here: the statistics' barrier below waits for every outstanding load.
+    constexpr bool STEP = (FL & FL_STEP) != 0;
+    static_assert(!STEP || (GEOC && !GEO1 && (FL & FL_MEET) && !(FL & (FL_GN1 | FL_RES | FL_NARROW)) && WK == 1 && BM == 128 && BN == kStepDim &&
+                            kStepCh == 4 && geo_TB(GEO) == 1 && 2 * (BM / 16) * BN >= kStepWeights),
+                  "the step-closing flavour: final_res_block's closing launch of the dim-32 plan, 512 threads, weights in the dead statistics scratch");
+    const StepClose* sp = STEP ? a.fin.step : nullptr;
+    const StepCloseHdr sh = STEP ? *shdr : StepCloseHdr();
+    const int s_lt = tid - 256, s_m = tid >> 2, s_j = tid & 3;
+    const int s_pix = STEP ? (y0 + ((s_m >> g_TWl) & (TH - 1))) * a.W + x0 + (s_m & (TW - 1)) : 0;
+    float s_y = 0.f, s_w0 = 0.f, s_w1 = 0.f, s_dt = 0.f;
+
     if (FL & FL_STAMP) conv_stamp(p, 7);
     if (do_stats) {
         if (pair_stats) stats_pair(a.stats_out, a.Gout, g_cpg, g_cpgt, g_NPG, meeting, fin && !meeting);
@@ -459,6 +480,34 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
                         rs[mt][nt][r] = (a.fin.res && nok && px >= 0) ? a.fin.res[(size_t)px * Cout + n] : 0.f;
                     }
                 }
+        }
+        // STEP: the evaluation this launch closes is number epoch - base of its call, so the next conditioning slice, the next entry of the
+        // time grid and the counters' next values all follow from the epoch this workgroup drew in its prologue -- nothing is read from a
+        // word that a workgroup of this launch writes.  Race-free because every workgroup of sample b draws the same epoch (the quotient of
+        // b's arrival counter by the group size: launches of one op never overlap) and `base` was written by the call's prologue, which the
+        // stream orders in front of the first step.  The kernel's prologue has parked the index beside the epoch (conv_pipe.hip), clamped to
+        // the call's last evaluation, so whatever the counter holds the reads below stay inside the table and the grid.
+        // Requested now, beside the residual, and not waited for before the meeting is over: this thread's state value, dt, the boundary
+        // weights, and the slice's SOURCE (the call's table, read-only here; it is stored behind the meeting).
+        float4 s_cond = make_float4(0.f, 0.f, 0.f, 0.f);
+        float s_t = 0.f;
+        int s_next = 0, s_ci = -1;
+        if constexpr (STEP) {
+            s_next = __float_as_int(smem[p.o_epoch + 1]);
+            s_y = as_global(sh.y)[((size_t)b0 * kStepCh + s_j) * (size_t)(a.H * a.W) + s_pix];
+            s_dt = sh.dt;
+            if (!active) {
+                const float* wq = as_global(sp->w);
+                s_w0 = wq[s_lt];
+                if (s_lt < kStepWeights - 256) s_w1 = wq[256 + s_lt];
+                const int S = sh.S, n4 = S >> 2, per = (n4 + geo_Tst(GEO) - 1) / geo_Tst(GEO);    // float4 of row b per workgroup of b (host: per <= 256)
+                const int i = (ty * p.tiles_x + tx) * per + s_lt;
+                if (s_lt < per && i < n4 && __float_as_int(smem[p.o_epoch + 2])) {               // (behind the last evaluation there is no slice)
+                    s_ci = i;
+                    s_cond = *reinterpret_cast<const float4*>(as_global(sh.ss_all) + ((size_t)s_next * sh.rows + b0) * (size_t)S + 4 * i);
+                }
+                if (blockIdx.x == 0 && s_lt >= BM) s_t = as_global(sh.ts)[s_next];
+            }
         }
         if (meeting) {
             // One round trip when the others have already published: every thread polls ONE granule (sc1 loads that bypass this CU's
@@ -514,6 +563,33 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
             }
         }
         lds_only_barrier();
+        if constexpr (STEP) {
+            if (!active) {
+                // The next evaluation's conditioning row of sample b overwrites the row this launch's loaders read (final_res_block's FiLM
+                // slot of plan.ss).  Row b is read by sample b's workgroups alone, in the prologue of their K loop; this workgroup is past
+                // its meeting, so every one of them has published the statistics of its finished K loop: no reader of row b is left.
+                // (Other samples' workgroups may still be in their prologue -- they read other rows.)
+                // first the boundary weights into the statistics scratch (its last reader was in front of the meeting's barriers): the next
+                // barrier waits for them
+                float* swl = smem + p.o_part;
+                swl[s_lt] = s_w0;
+                if (s_lt < kStepWeights - 256) swl[256 + s_lt] = s_w1;
+                if (s_ci >= 0) *reinterpret_cast<float4*>(as_global(sh.ss_dst) + (size_t)b0 * (size_t)sh.S + 4 * s_ci) = s_cond;
+                // what block 0 of final_conv does in the three-launch form: the next interval's time and the two counters
+                if (blockIdx.x == 0 && s_lt >= BM) {
+                    if (s_lt == BM) {
+                        float* scq = as_global(sh.sc);
+                        scq[0] = s_t;
+                        scq[1] = 0.f;
+                        *as_global(sh.step) = s_next + 1;
+                        *as_global(sh.evalc) = s_next;
+                    }
+                    const float tv = __fmul_rn(s_t, sh.t_scale);
+                    float* tvq = as_global(sh.tvec);
+                    for (int r = s_lt - BM; r < sh.rows; r += 256 - BM) tvq[r] = tv;
+                }
+            }
+        }
         if ((FL & FL_STAMP) && active) conv_stamp(p, 12);  // (accumulator rows) the statistics of the whole group are in LDS: meeting over, or the local table
         if (owner) {
 #pragma unroll
@@ -621,6 +697,50 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
             if (active && !pass) conv_stamp(p, 9);
             lds_only_barrier();
             if (active && !pass) conv_stamp(p, 10);
+            if constexpr (STEP) {
+                // The image holds the Block's output, a pixel per row.  Four threads per pixel, one per latent channel: v = final_conv(row) --
+                // bias first, channels ascending, final_conv_small_kernel's expression --, y = y + v dt rounded as there; the pixel's four
+                // new values meet by lane shuffles, and init_conv of them (its kernel's expression, ci ascending), two channel quads per
+                // thread, goes back into the row.  The wide stores below then write the NEXT evaluation's
+                // init_conv output (ConvArgs::out is the plan's x0 in this flavour); the Block output itself is never stored.
+                {
+                    float* row = ot + s_m * OS;
+                    const float* swl = smem + p.o_part;          // final_conv weight [ch][dim] | bias [ch] | init_conv weight [ch][dim] | bias [dim]
+                    float4 xv[kStepDim / 4];
+#pragma unroll
+                    for (int k = 0; k < kStepDim / 4; ++k) xv[k] = *reinterpret_cast<const float4*>(row + 4 * k);
+                    const float* fw = swl + s_j * kStepDim;
+                    float acc1 = swl[kStepCh * kStepDim + s_j];
+#pragma unroll
+                    for (int k = 0; k < kStepDim / 4; ++k) {
+                        const float4 wv = *reinterpret_cast<const float4*>(fw + 4 * k);
+                        acc1 += xv[k].x * wv.x; acc1 += xv[k].y * wv.y; acc1 += xv[k].z * wv.z; acc1 += xv[k].w * wv.w;
+                    }
+                    const float yn = __fadd_rn(s_y, __fmul_rn(acc1, s_dt));    // x + pred * dt
+                    as_global(sh.y)[((size_t)b0 * kStepCh + s_j) * (size_t)(a.H * a.W) + s_pix] = yn;
+                    float y4[kStepCh];
+#pragma unroll
+                    for (int ci = 0; ci < kStepCh; ++ci) y4[ci] = __shfl(yn, (lane & ~3) | ci);
+                    const float* iw = swl + kStepCh * kStepDim + kStepCh;
+                    const float* ib = iw + kStepCh * kStepDim;
+                    float4 o[2];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {              // this thread's two channel quads of the pixel's init_conv output
+                        const int c = 2 * s_j + h;
+                        o[h] = *reinterpret_cast<const float4*>(ib + 4 * c);
+#pragma unroll
+                        for (int ci = 0; ci < kStepCh; ++ci) {
+                            const float xq = y4[ci];
+                            const float4 wv = *reinterpret_cast<const float4*>(iw + ci * kStepDim + 4 * c);
+                            o[h].x += xq * wv.x; o[h].y += xq * wv.y; o[h].z += xq * wv.z; o[h].w += xq * wv.w;
+                        }
+                    }
+                    // (a pixel's four threads are lanes of one wave: every read of the row above has completed before these writes issue)
+                    *reinterpret_cast<float4*>(row + 8 * s_j) = o[0];
+                    *reinterpret_cast<float4*>(row + 8 * s_j + 4) = o[1];
+                }
+                lds_only_barrier();
+            }
             float* gout = pass ? a.res_out : a.out;
             for (int i = tid; i < BM * Q4; i += nthr) {
                 const int m = i / Q4, c4 = (i - m * Q4) * 4, n = n0 + c4;
@@ -640,6 +760,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[MT
 
 int conv_pipe_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s);
 int conv_pipe_blocks_per_cu(const ConvDev& d, int tile, size_t lds);   // occupancy of the instantiation that launch would use (0: unknown)
+bool conv_pipe_step_ok(const ConvDev& d, int tile);                    // the launch is the one the step-closing flavour (FL_STEP) is compiled for
 int conv_pipe_init();
 bool conv_pipe_supports_ks(int ks);
 const float* conv_zeros16();

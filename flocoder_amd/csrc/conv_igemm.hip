@@ -357,7 +357,8 @@ static int conv_geometry(const ConvArgs& a, int tile, bool pipe, ConvDev* d, Con
             g->n_t1 = (float)(p.rps * cpgt1);
             p.fin_local = g->fin_local = (g->T == 1) ? 1 : 0;   // whole groups per tile: nothing to meet for
             if (p.fin_local) p.gsz = 1;
-            else {
+            g->gsz = p.gsz;
+            if (!p.fin_local) {
                 // Workgroups that wait for each other must all be resident.  How many of THIS instantiation one CU holds (registers,
                 // waves, LDS) is asked of the runtime per flavour -- round 2 assumed "two when the LDS fits and NT = 1", an unverified
                 // register-count claim -- and never counted above two.  This proves residency on a device the launch has to itself;
@@ -403,6 +404,20 @@ bool conv_fin_possible(const ConvArgs& a, int tile) {
     if (!b.fin.gamma) b.fin.gamma = reinterpret_cast<const float*>(16);   // geometry only
     if (!b.stats_out) b.stats_out = reinterpret_cast<float*>(16);
     return conv_geometry(b, tile, true, &d, &g) == FC_OK;   // a refusal leaves its reason in fc_last_error, harmlessly
+}
+
+// The launch (a Block-closing one the plan has accepted: every pointer real) is the one the step-closing flavour is compiled for, and
+// that flavour -- its own registers and LDS, asked of the runtime like every meeting launch's -- keeps the whole grid resident too.
+bool conv_step_close_possible(const ConvArgs& a, int tile) {
+    static StepClose dummy;
+    ConvDev d;
+    ConvGeom g;
+    if (!a.fin.gamma || conv_geometry(a, tile, true, &d, &g) != FC_OK || !conv_pipe_step_ok(d, tile)) return false;
+    d.a.fin.step = &dummy;      // (never dereferenced: the occupancy query launches nothing)
+    d.stamps = nullptr;
+    int per_cu = conv_pipe_blocks_per_cu(d, tile, g.lds);
+    if (per_cu > 2) per_cu = 2;
+    return per_cu > 0 && d.nblocks <= conv_cu_count() * per_cu;
 }
 
 static int auto_tile(const ConvArgs& a) {

@@ -210,6 +210,17 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         const gu32* cnt = (const gu32*)(a.fin.sync + b0 / g_TB);
         asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(arrival) : "v"(cnt), "v"(1u) : "memory");
     }
+    // FL_STEP: with the epoch, the number of the evaluation this launch closes in its call (conv_dev.h "STEP") -- the sample's base epoch
+    // and the call's number of evaluations are requested beside the arrival, so the tail finds the index in LDS
+    // The block's header (pointers and constants of the call) is read here as well, into registers that live across the K loop: in the tail
+    // it would be a cold round trip in front of every load the step needs.
+    unsigned step_base = 0, step_n = 0;
+    StepCloseHdr step_h;
+    if constexpr ((FL & FL_STEP) != 0) {
+        step_h = a.fin.step->h;
+        step_n = (unsigned)step_h.n_slices;
+        if (tid == 0) step_base = as_global(a.fin.step->base)[b0];
+    }
 
     // ---- GroupNorm tables: moments per (sample, group), then the folded affine per (sample, channel).  The staging waves build them
     // AFTER they have put the first weight slabs in flight (two dependent global round trips that the slab transfer overlaps).
@@ -613,6 +624,11 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
         if (meet && tid == 0) {
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(arrival) :: "memory");
             smem[p.o_epoch] = __uint_as_float(arrival / (unsigned)p.gsz + 1u);
+            if constexpr ((FL & FL_STEP) != 0) {     // the NEXT evaluation's number, never past the call's last; whether it has a conditioning slice
+                const unsigned nxt = min(arrival / (unsigned)p.gsz + 1u - step_base + 1u, step_n);
+                smem[p.o_epoch + 1] = __uint_as_float(nxt);
+                smem[p.o_epoch + 2] = __uint_as_float(nxt < step_n ? 1u : 0u);
+            }
         }
         __syncthreads();        // stage 0 ready
         if (FL & FL_STAMP) conv_stamp(p, 4);
@@ -786,7 +802,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
     // WW: the one barrier the K loop no longer has -- every accumulator wave has read its last operands, the window (which the tail's
     // scratch aliases) is dead.  lgkmcnt only: a wave's outstanding global requests are not waited for here
     if constexpr (WW) loader_handover();
-    conv_epilogue<WM, WN, WK, MT, NT, FL, GEO>(p, acc, accr, smem, tid, lane, wave, b0, y0, x0, n0, tx, ty, consumer, NTHR, pre, true);
+    conv_epilogue<WM, WN, WK, MT, NT, FL, GEO>(p, acc, accr, smem, tid, lane, wave, b0, y0, x0, n0, tx, ty, consumer, NTHR, pre, true, &step_h);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1028,6 +1044,35 @@ static int fin_geom_launch(const ConvDev& d, int tile, bool w4, int need, int gr
     return -1;
 }
 
+// The step-closing flavour (conv_dev.h FL_STEP): final_res_block's closing launch of the dim-32 plan at 4x32x32 -- the first row of
+// FC_FIN_GEOMS with the meeting, no GroupNorm(1) partials -- and its stamped twin.  Nothing else is instantiated with the bit, and a launch
+// that asks for it (ConvFin::step) without matching the key is an error, never another kernel: the plan has dropped its final_conv and
+// init_conv launches by then.
+constexpr int kStepGeo = geo_key(GEO_FAST, 1, 16, 8, 8), kStepMask = kFinBase | FL_MEET;
+static bool lean_kernels_on() {
+    static const bool lean = [] { const char* e = std::getenv("FLOCODER_AMD_LEAN_KERNELS"); return !(e && std::string(e) == "0"); }();
+    return lean;
+}
+bool conv_pipe_step_ok(const ConvDev& d, int tile) {
+    const ConvArgs& a = d.a;
+    return lean_kernels_on() && tile == TILE_M128N32 && a.KS == 3 && !d.bf3 && d.o_out >= 0 && !a.fin.gn1_out && !a.res_out && !a.stats_post && !a.out_act && !a.add &&
+           !d.fin_local && d.any_xf && !a.out_sh && !a.out_oy && !a.out_ox && a.Cout == kStepDim && d.ntiles == 1 && d.P * (16 / 4) <= 64 * 4 * kLeanNPL &&
+           d.gsz == geo_Tst(kStepGeo) && fin_geo_key(d, 128, 32, 512, false) == kStepGeo;
+}
+static int fin_step_attr() {
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP, 0, kStepGeo>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP | FL_STAMP, 0, kStepGeo>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    return FC_OK;
+}
+static int fin_step_launch(const ConvDev& d, int tile, int need, int grid, size_t lds, hipStream_t s, int* occ) {
+    if (!conv_pipe_step_ok(d, tile) || (need & ~FL_STAMP) != kStepMask) return fail(FC_E_STATE, "conv: the launch is not the one the step-closing flavour is compiled for");
+    if (!occ) step_route_log_add("step_close");
+    return (need & FL_STAMP) ? launch_pipe<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP | FL_STAMP, 0, kStepGeo>(d, grid, lds, s, occ)
+                             : launch_pipe<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP, 0, kStepGeo>(d, grid, lds, s, occ);
+}
+
 // Block-OPENING (conv1) GEOMETRY flavours: the first convolution of every ResnetBlock of the same plan -- statistics of the raw output, in the
 // up path also the concatenated skip and the fused res_conv output.  A Block's conv1 has the output geometry of its closing launch, so the
 // keys are those of FC_FIN_GEOMS; only the (tile, mask, key) triples the plan's 19 conv1 launches use exist.
@@ -1140,6 +1185,7 @@ int conv_pipe_init() {
 #undef X
     FC_TRY((lean_attr<2, 0>()));
     FC_TRY(fin_geom_attr());
+    FC_TRY(fin_step_attr());
     FC_TRY(conv1_geom_attr());
     done = true;
     return FC_OK;
@@ -1160,7 +1206,8 @@ static int pipe_launch_ks(const ConvDev& d, int tile, int grid, size_t lds, hipS
 
 static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
     if (d.bf3) return d.a.KS == 1 ? bf3_launch_ks<1>(d, tile, grid, lds, s, occ) : d.a.KS == 2 ? bf3_launch_ks<2>(d, tile, grid, lds, s, occ) : bf3_launch_ks<3>(d, tile, grid, lds, s, occ);
-    static const bool lean = [] { const char* e = std::getenv("FLOCODER_AMD_LEAN_KERNELS"); return !(e && std::string(e) == "0"); }();
+    const bool lean = lean_kernels_on();
+    if (d.a.fin.step && !(lean && d.a.KS == 3)) return fail(FC_E_STATE, "conv: the step-closing flavour is a lean 3x3 kernel");
     if (lean) {                  // the smallest flavour that covers this launch
         const bool small_tile = tile == TILE_M32N32K4;
         const int need = (d.a.fin.gamma ? FL_FIN : 0) | (d.a.res_out ? FL_RES : 0) | (d.a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |
@@ -1174,7 +1221,8 @@ static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, 
             const bool w4 = small_tile && d.a.w4 && d.a.Cin % 32 == 0 && d.a.Cout % 32 == 0 && d.a.pad == 1 && !d.a.w_batch_stride &&
                             (!d.a.res_out || d.a.res_w4);
             const size_t lds_ww = (w4 && (need & FL_FIN)) ? ww_lds(d, tile, lds) : 0;        // whole-window staging, where the launch may take it
-            if (need & FL_FIN) r = fin_geom_launch(d, tile, w4, need, grid, lds, lds_ww, s, occ);    // Block-closing: the flavour of exactly this geometry, if there is one
+            if ((need & FL_FIN) && d.a.fin.step) r = fin_step_launch(d, tile, need, grid, lds, s, occ);   // ... that also closes the step: that flavour or an error
+            else if (need & FL_FIN) r = fin_geom_launch(d, tile, w4, need, grid, lds, lds_ww, s, occ);    // Block-closing: the flavour of exactly this geometry, if there is one
             else if (need & FL_STATS) r = conv1_geom_launch(d, tile, w4, need, grid, lds, s, occ);   // Block-opening: likewise
             if (lds_ww) {
 #define X(F) if (r == -1 && need == (F)) r = lean_launch_ww<(F)>(d, tile, grid, lds_ww, s, occ);
@@ -1226,7 +1274,7 @@ int conv_pipe_blocks_per_cu(const ConvDev& d, int tile, size_t lds) {
                      ((d.a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
     // (whether a launch takes the whole-window form depends on its grid and Cin as well: part of the key)
     const int ww = (d.a.KS == 3 && d.a.w4 && ww_lds(d, tile, lds)) ? d.a.Cin : 0;
-    const auto key = std::make_tuple(tile, d.a.KS, mask | (d.a.w4 ? FL_W4 : 0), lds, d.cpg, d.TB * 4096 + (d.TWl << 8) + d.tiles_x * d.tiles_y * d.NPG + (ww << 13));
+    const auto key = std::make_tuple(tile, d.a.KS, mask | (d.a.w4 ? FL_W4 : 0) | (d.a.fin.step ? FL_STEP : 0), lds, d.cpg, d.TB * 4096 + (d.TWl << 8) + d.tiles_x * d.tiles_y * d.NPG + (ww << 13));
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;

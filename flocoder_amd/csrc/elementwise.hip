@@ -1,5 +1,8 @@
 // HBM-bound helper kernels: GroupNorm finalisation with residual, the boundary 1x1 convolutions that
 // change layout (NCHW <-> NHWC), layout converters, bilinear resize, standalone GroupNorm statistics.
+#include <mutex>
+#include <string>
+
 #include "common.h"
 #include "stats_dev.h"
 
@@ -227,9 +230,44 @@ __global__ void __launch_bounds__(256) init_conv_kernel(const float* x, int bmod
     }
 }
 
+// Diagnostics (fc_debug_conv_routes switches the record on and off, fc_debug_step_routes_read copies it): the launches at the step
+// boundary in the order they were enqueued -- "init_conv", "final_conv", or "step_close" for a Block-closing convolution on the
+// step-closing flavour (conv_pipe.hip), which stands for both.
+static std::mutex g_step_route_mu;
+static bool g_step_route_on = false;
+static std::string g_step_route_log;
+void step_route_log_set(bool on) { std::lock_guard<std::mutex> lk(g_step_route_mu); g_step_route_on = on; if (on) g_step_route_log.clear(); }
+std::string step_route_log_get() { std::lock_guard<std::mutex> lk(g_step_route_mu); return g_step_route_log; }
+void step_route_log_add(const char* what) {
+    std::lock_guard<std::mutex> lk(g_step_route_mu);
+    if (g_step_route_on) g_step_route_log += std::string(what) + "\n";
+}
+
+// The step-closing flavour's device block (common.h StepClose), once per integrator call: the call's pointers and constants, the two
+// boundary convolutions' weights in the order their kernels read them, and per sample the epoch its arrival counter will hand the
+// call's first evaluation.  Runs behind every earlier launch of the plan on the stream, so a counter is a whole multiple of `gsz` here.
+__global__ void __launch_bounds__(256) step_close_setup_kernel(StepClose* blk, const StepCloseHdr h, const float* fw, const float* fb,
+                                                               const float* iw, const float* ib, const unsigned* sync, int gsz) {
+    const int t = threadIdx.x;
+    if (t == 0) blk->h = h;
+    constexpr int NF = kStepDim * kStepCh, NI = kStepCh * kStepDim;
+    for (int i = t; i < kStepWeights; i += 256)
+        blk->w[i] = i < NF ? fw[(i % kStepDim) * kStepCh + i / kStepDim] : i < NF + kStepCh ? (fb ? fb[i - NF] : 0.f)
+                  : i < NF + kStepCh + NI ? iw[i - NF - kStepCh] : (ib ? ib[i - NF - kStepCh - NI] : 0.f);
+    for (int b = t; b < h.rows; b += 256) blk->base[b] = sync[b] / (unsigned)gsz + 1u;
+}
+
+int step_close_setup_launch(StepClose* blk, const StepCloseHdr& h, const float* fw, const float* fb, const float* iw, const float* ib,
+                            const unsigned* sync, int gsz, hipStream_t s) {
+    hipLaunchKernelGGL(step_close_setup_kernel, dim3(1), dim3(256), 0, s, blk, h, fw, fb, iw, ib, sync, gsz);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
 int init_conv_launch(const CondFetch& fetch, const float* x, int bmod, const float* w, const float* bias, float* out, int B, int Cin, int HW,
                      int Cout, hipStream_t s) {
     if (Cout & 3) return fail(FC_E_SHAPE, "init_conv: Cout must be a multiple of 4");
+    step_route_log_add("init_conv");
     const size_t total = (size_t)B * HW * (Cout / 4);
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     const int extra = fetch.all ? (fetch.n4 + 255) / 256 < 512 ? (fetch.n4 + 255) / 256 : 512 : 0;
@@ -347,6 +385,7 @@ __global__ void __launch_bounds__(256) final_conv_small_kernel(const float* x, c
 int final_conv_launch(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int HW, int Cout, const EulerTail& tail,
                       hipStream_t s) {
     if (Cin & 3) return fail(FC_E_SHAPE, "final_conv: Cin must be a multiple of 4");
+    step_route_log_add("final_conv");
     const size_t total = (size_t)B * HW;
     if (Cout <= 4 && total < (1ull << 31) && (Cin == 8 || Cin == 16 || Cin == 32 || Cin == 64)) {
         const dim3 g((unsigned)((total + 255) / 256));

@@ -38,6 +38,8 @@ struct FwdCtx {             // per-call inputs of one forward
     float* dmask_out = nullptr;        // backward only, optional: NCHW gradient of the mask
     EulerTail euler;                   // integrator only: the Euler update rides in final_conv
     CondFetch fetch;                   // integrator only: conditioning rows of every evaluation were computed up front
+    const StepClose* step = nullptr;   // integrator only: final_res_block's closing launch closes the Euler step as well (conv_dev.h FL_STEP) --
+                                       // the init_conv and final_conv entries launch nothing, `euler` / `fetch` travel in the device block
 };
 using Op = std::function<int(const FwdCtx&, hipStream_t)>;
 
@@ -69,6 +71,11 @@ struct Plan {                 // one launch plan + activation arena for up to ma
     int n_meet = 0;                                 // launches whose workgroups wait for each other (fused Block tails across workgroups)
     std::vector<unsigned*> fin_sync;                // their arrival counters (fc_debug_unet_break_meeting)
     std::vector<int> fin_kind;                      // ... and what waits on them: 0 a convolution's Block tail, 1 the linear attention's close
+    // the step-closing flavour of final_res_block's closing launch (conv_dev.h FL_STEP): its device block, or null when the plan's launch
+    // is not the one that flavour is compiled for; the launch's arrival counters and workgroups per sample (the block's base epochs)
+    StepClose* step_blk = nullptr;
+    const unsigned* step_sync = nullptr;
+    int step_gsz = 0;
     void release() {
         for (void* p : allocs) dev_free(p);
         *this = Plan();
@@ -222,6 +229,7 @@ struct PlanBuilder {
     int* fin_err_word = nullptr;   // device word a timed-out fused tail sets (owned by the handle the plan belongs to)
     int conv_prec = 0;             // ConvArgs::prec of every convolution this builder emits (codec plans: 1 = split-bf16 on request)
     const ParamStore* store = nullptr;   // where conv() finds the split-bf16 copy of a weight (codec builders set it)
+    Act step_out;                  // set around the Block whose closing launch may close the sampler's step too: the tensor that flavour writes (conv_fin)
 
     // guard: 0 always | 1 only when the call has a mask | 2 only when it runs mask_fusion_conv | 3 only when it has NO mask | 4 mask but no fusion
     int guard = 0;
@@ -394,9 +402,20 @@ struct PlanBuilder {
         a.fin.err = fin_err_word ? fin_err_word : reinterpret_cast<int*>(sync + g.groups);   // the handle's error word (one per object)
         if (!g.fin_local) { ++pl->n_meet; pl->fin_sync.push_back(sync); pl->fin_kind.push_back(0); }
         const int tile = g.tile;
+        // the launch that may close the sampler's step as well (`step_out`): only when it is exactly the one that flavour is compiled for
+        float* sout = nullptr;
+        if (step_out.p && step_out.C == out.C && step_out.H == out.H && step_out.W == out.W && conv_step_close_possible(a, tile)) {
+            pl->step_blk = reinterpret_cast<StepClose*>(dmalloc(sizeof(StepClose) / sizeof(float) + (size_t)B));
+            if (err) return false;
+            pl->step_sync = sync; pl->step_gsz = g.gsz;
+            sout = step_out.p;
+        }
         const double fl = 2.0 * out.H * out.W * a.KS * a.KS * (double)a.Cin * a.Cout;
-        push([a, tile](const FwdCtx& c, hipStream_t s) { ConvArgs b = a; b.B = c.B; return conv_launch(b, tile, s); }, std::string(kTileNames[tile]) + "+fin", fl,
-             conv_bytes_ps(a), conv_bytes_fixed(a));
+        push([a, tile, sout](const FwdCtx& c, hipStream_t s) {
+            ConvArgs b = a; b.B = c.B;
+            if (c.step && sout) { b.fin.step = c.step; b.out = sout; }
+            return conv_launch(b, tile, s);
+        }, std::string(kTileNames[tile]) + "+fin", fl, conv_bytes_ps(a), conv_bytes_fixed(a));
         return true;
     }
 

@@ -652,7 +652,8 @@ static int build_plan(fc_unet* u, Plan* pl, int maxB, int H, int W) {
         float* x0p = x0.p;
         b.scope = "init_conv";
         if (!c.mask_cond) {
-            b.push([=](const FwdCtx& cx, hipStream_t s) { return init_conv_launch(cx.fetch, cx.x, cx.x_mod, w, bias, x0p, cx.B, ch, HW, dim, s); }, "init_conv", 2.0 * HW * ch * dim);
+            // (cx.step: the evaluation before this one has written x0 and fetched the conditioning slice -- conv_dev.h FL_STEP)
+            b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.step ? (int)FC_OK : init_conv_launch(cx.fetch, cx.x, cx.x_mod, w, bias, x0p, cx.B, ch, HW, dim, s); }, "init_conv", 2.0 * HW * ch * dim);
         } else {
             Act xi = b.act(dim, H, W), f1 = b.act(2 * dim, H, W), f2 = b.act(2 * dim, H, W);
             const bool keep = u->keep_all;         // training keeps the pre-activations z1, z2 of the two SiLU layers
@@ -776,13 +777,17 @@ static int build_plan(fc_unet* u, Plan* pl, int maxB, int H, int W) {
     }
     if (b.err) return b.err;
     // -- head (unet.py:369-372) --
+    // final_res_block's closing launch may close the Euler sampler's step as well: final_conv, the update and the next evaluation's
+    // init_conv are pointwise per pixel (init_conv is a 1x1 convolution here), and the launch's tile holds every channel of its pixels
+    if (!c.mask_cond && dim == kStepDim && ch == kStepCh) b.step_out = x0;
     x = b.resblock("final_res_block", x, &x0, dim, false, nullptr);
+    b.step_out = Act();
     if (b.err) return b.err;
     pl->head = x;
     {
         const float *xp = x.p, *w = u->P("final_conv.weight"), *bias = u->R("final_conv.bias");
         b.scope = "final_conv";
-        b.push([=](const FwdCtx& cx, hipStream_t s) { return final_conv_launch(xp, w, bias, cx.out, cx.B, dim, HW, ch, cx.euler, s); }, "final_conv", 2.0 * HW * dim * ch);
+        b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.step ? (int)FC_OK : final_conv_launch(xp, w, bias, cx.out, cx.B, dim, HW, ch, cx.euler, s); }, "final_conv", 2.0 * HW * dim * ch);
     }
     if (b.err) return b.err;
     pl->maxB = maxB; pl->H = H; pl->W = W;
@@ -1127,7 +1132,12 @@ int fc_debug_set_fused_tail(int on) {   // plans built from now on use (1) / do 
 
 // Diagnostics: record which instantiation of the pipelined convolution every launch goes to (on != 0 starts an empty record, 0 stops);
 // fc_debug_conv_routes_read copies the record -- one line of the thirteen template arguments per launch -- and returns its length.
-int fc_debug_conv_routes(int on) { conv_route_log_set(on != 0); linattn_route_log_set(on != 0); return FC_OK; }
+int fc_debug_conv_routes(int on) { conv_route_log_set(on != 0); linattn_route_log_set(on != 0); step_route_log_set(on != 0); return FC_OK; }
+int fc_debug_step_routes_read(char* buf, int cap) {
+    const std::string r = step_route_log_get();
+    if (buf && cap > 0) { const size_t n = r.size() < (size_t)cap - 1 ? r.size() : (size_t)cap - 1; memcpy(buf, r.data(), n); buf[n] = 0; }
+    return (int)r.size();
+}
 int fc_debug_conv_routes_read(char* buf, int cap) {
     const std::string r = conv_route_log_get();
     if (buf && cap > 0) { const size_t n = r.size() < (size_t)cap - 1 ? r.size() : (size_t)cap - 1; memcpy(buf, r.data(), n); buf[n] = 0; }

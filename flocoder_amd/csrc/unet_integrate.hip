@@ -262,7 +262,37 @@ static int enqueue_rk4_interval(const CallFrame& f, const Rk4Variant& v, float c
 // Legacy Euler without CFG: the step needs nothing outside the plan (fc_unet_integrate publishes the first time)
 static bool euler_tail_ok(int method, bool cfg_on) { return method == FC_METHOD_EULER && !cfg_on; }
 
-static int enqueue_step(const CallFrame& f, int method, float cfg, float dt_euler, float t_scale, bool pre_on) {
+// Step closing (conv_dev.h FL_STEP): inside a replayed Euler step final_res_block's closing launch also runs final_conv, the update and the
+// next evaluation's init_conv and fetches the next conditioning slice -- 68 launches per step instead of 70.  Only where that launch is
+// the one the flavour is compiled for (Plan::step_blk: the exclusive dim-32 plan at 4x32x32, no mask conditioning) and the call is the
+// legacy Euler sampler without CFG or mask on the conditioning table; everything else keeps the three launches.
+// FLOCODER_AMD_STEP_CLOSE=0 does too (read per call: the two forms have different graph keys).
+static bool step_close_ok(const CallFrame& f, int method, bool pre_on) {
+    const fc_unet* u = f.u;
+    const char* e = std::getenv("FLOCODER_AMD_STEP_CLOSE");
+    if (e && std::strcmp(e, "0") == 0) return false;
+    return euler_tail_ok(method, f.cfg_on) && pre_on && f.mask_mode == 0 && u->plan.step_blk != nullptr && u->S % 4 == 0 &&
+           u->S / 4 <= 256 * u->plan.step_gsz;         // (a sample's workgroups copy its conditioning row, one float4 per staging thread)
+}
+
+// What such a call puts behind integrator_prologue and cond_table, in front of its first replay: the device block of the step-closing
+// launch (the call's pointers and constants, the boundary weights, every sample's base epoch) and the FIRST evaluation's init_conv --
+// the existing launch, outside the graph; it also fetches conditioning slice 0.
+static int step_close_prologue(const CallFrame& f, float dt_euler, float t_scale, int n_steps) {
+    fc_unet* u = f.u;
+    const IntegratorState& ig = u->ig;
+    StepCloseHdr h;
+    h.y = ig.y; h.ts = ig.ts_dev; h.sc = ig.sc; h.tvec = ig.tvec; h.step = ig.step; h.evalc = ig.step + 1;
+    h.ss_all = ig.pre_ss; h.ss_dst = u->plan.ss; h.dt = dt_euler; h.t_scale = t_scale;
+    h.rows = f.rows; h.S = u->S; h.n_slices = n_steps;
+    const float *iw = u->P("init_conv.weight"), *ib = u->R("init_conv.bias");
+    FC_TRY(step_close_setup_launch(u->plan.step_blk, h, u->P("final_conv.weight"), u->R("final_conv.bias"), iw, ib, u->plan.step_sync,
+                                   u->plan.step_gsz, f.s));
+    const FwdCtx c = step_ctx(f, true);
+    return init_conv_launch(c.fetch, ig.y, f.B, iw, ib, u->plan.x0.p, f.rows, u->cfg.channels, u->H * u->W, u->cfg.dim, f.s);
+}
+
+static int enqueue_step(const CallFrame& f, int method, float cfg, float dt_euler, float t_scale, bool pre_on, bool step_close = false) {
     fc_unet* u = f.u;
     const IntegratorState& ig = u->ig;
     const bool cfg_on = f.cfg_on;
@@ -274,6 +304,7 @@ static int enqueue_step(const CallFrame& f, int method, float cfg, float dt_eule
         c.x = ig.y;
         c.euler.y = ig.y; c.euler.dt = dt_euler; c.euler.step = ig.step; c.euler.ts = ig.ts_dev; c.euler.t_scale = t_scale;
         c.euler.sc = ig.sc; c.euler.tvec = ig.tvec; c.euler.rows = rows;
+        if (step_close) c.step = u->plan.step_blk;
         return run_plan(u->plan, c, s);
     }
     FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 0, ig.sc, ig.tvec, rows, s));
@@ -413,8 +444,10 @@ int fc_unet_integrate(fc_unet* u, int method, float* x_dev, int B, int H, int W,
         FC_TRY(ode_time_launch(ig.step, ig.ts_dev, t_scale, 0, ig.sc, ig.tvec, rows, s));
     GraphKey key = graph_key(f, method == FC_METHOD_RK4 ? GraphKey::Rk4 : GraphKey::Euler, cfg_strength, t_scale);
     key.pre_on = pre_on; key.dt_euler = fbits(dt_euler);
+    const bool step_close = key.step_close = step_close_ok(f, method, pre_on);
+    if (step_close) FC_TRY(step_close_prologue(f, dt_euler, t_scale, n_steps));
     FC_TRY(replay_steps(f, key, n_steps, method == FC_METHOD_RK4 ? 4 : 1,
-                        [&] { return enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on); }));
+                        [&] { return enqueue_step(f, method, cfg_strength, dt_euler, t_scale, pre_on, step_close); }));
     return f.finish(x_dev);
 }
 

@@ -16,13 +16,14 @@ struct GraphKey {
     int B = 0, mask_mode = 0;
     bool cfg_on = false, has_ids = false;
     bool pre_on = false;                                    // fixed grids: the conditioning table is in use
+    bool step_close = false;                                // Euler: final_res_block's closing launch closes the step (no final_conv / init_conv launch)
     int steps = 0;                                          // fixed grids: consecutive intervals in the graph
     bool dense = false;                                     // RK45: an attempt with t_eval has one more launch
     uint32_t cfg_strength = 0, dt_euler = 0, t_scale = 0;   // the floats' bits (dt_euler: 0 for RK45)
     int sde_scheme = 0, sde_noise = 0;                      // SDE: the scheme and the noise source (0 generated, 1 supplied)
     uint32_t sde_sigma = 0;                                 // SDE: sigma's bits
     auto tie() const {
-        return std::tie(kind, B, mask_mode, cfg_on, has_ids, pre_on, steps, dense, cfg_strength, dt_euler, t_scale, sde_scheme, sde_noise,
+        return std::tie(kind, B, mask_mode, cfg_on, has_ids, pre_on, step_close, steps, dense, cfg_strength, dt_euler, t_scale, sde_scheme, sde_noise,
                         sde_sigma);
     }
     bool operator<(const GraphKey& o) const { return tie() < o.tie(); }

@@ -430,6 +430,11 @@ int fc_debug_conv_routes_read(char* buf, int cap);
  * line "C n NB TT" to a record of its own: NB = n / 32 and TT = n / 128 when it launched the kernel pair compiled for exactly this shape, 0 0
  * when it launched the pair that reads the shape at run time.  Copies it like fc_debug_conv_routes_read and returns its full length. */
 int fc_debug_linattn_routes_read(char* buf, int cap);
+/* Diagnostics: while the record of fc_debug_conv_routes is on, every launch at the sampler's step boundary adds one line to a record of its
+ * own, in the order the launches were enqueued (a captured graph: when it was captured): "init_conv", "final_conv", or "step_close" for
+ * final_res_block's closing convolution on the flavour that stands for both inside a replayed Euler step.  Copies it like
+ * fc_debug_conv_routes_read and returns its full length. */
+int fc_debug_step_routes_read(char* buf, int cap);
 /* Diagnostics: fc_unet_profile_ops runs plan entry `op_index` once more with the stamps of fc_debug_set_conv_stamps going to buf_dev
  * (the phase timeline of ONE launch of a real plan, fused tail included: tools/fin_stamps.py); NULL switches it off. */
 int fc_debug_set_stamp_op(int op_index, void* buf_dev);

@@ -23,7 +23,7 @@ READELF = os.environ.get("LLVM_READELF", "/opt/rocm/lib/llvm/bin/llvm-readelf")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 ARGS = ("WM", "WN", "WK", "MT", "NT", "CC", "NPL", "KS", "NL", "FL", "PREC", "GEO", "GEO1")    # GEO: key of a Block-closing flavour, GEO1: of a conv1 flavour
 FL_NAMES = {1: "fin", 2: "res", 4: "post", 8: "xf", 16: "cat", 32: "stamp", 64: "stats", 128: "gn1", 256: "postop", 512: "narrow", 1024: "multi",
-            2048: "meet", 4096: "w4", 8192: "ww"}
+            2048: "meet", 4096: "w4", 8192: "ww", 16384: "step"}
 
 
 def code_objects(path):
