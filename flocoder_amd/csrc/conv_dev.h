@@ -44,7 +44,31 @@ __device__ __forceinline__ void conv_stamp(const ConvDev& p, int slot) {
     }
 }
 
+// The tiles, indexed by ConvTile: waves WM x WN x WK, MFMA tiles MT x NT per wave, the pipelined kernel's chunk depth CC (chosen so that
+// two stages fit), the synchronous kernel's CCs (0: the tile exists in the pipelined kernel only) and the pipelined kernel's staging
+// waves NLk at kernel sizes above 1x1.  Every instantiation of either kernel takes its template arguments from here.
+struct ConvTileDef { int WM, WN, WK, MT, NT, CC, CCs, NLk; };
+constexpr ConvTileDef kConvTiles[TILE_COUNT] = {
+    {4, 1, 1, 1, 1, 16, 32, 4},   // TILE_M128N32
+    {4, 1, 1, 1, 2, 16, 16, 4},   // TILE_M128N64
+    {2, 1, 2, 1, 1, 32, 32, 8},   // TILE_M64N32K2
+    {1, 1, 4, 1, 1, 32, 32, 8},   // TILE_M32N32K4
+    {2, 1, 2, 1, 2, 16, 16, 4},   // TILE_M64N64K2
+    {4, 1, 1, 2, 2, 16, 0, 4},    // TILE_M256N64: 64 x 64 per wave (2 x 2 MFMA tiles): one LDS read per MFMA, weights reused by 256 rows
+};
 struct TileInfo { int BM, BN, CC, WK, MTNT, WMWN; };
+constexpr TileInfo conv_tile_info(int tile, bool pipe) {
+    const ConvTileDef& t = kConvTiles[tile];
+    return {32 * t.MT * t.WM, 32 * t.NT * t.WN, pipe ? t.CC : t.CCs, t.WK, t.MT * t.NT, t.WM * t.WN};
+}
+// The pipelined kernel's staging waves (four at 1x1 everywhere) and its staging limit: a staging thread keeps at most `npl` float4
+// window elements of a chunk -- eight in the all-in-one kernels; four in the lean ones, whose staging code is unrolled per element
+// (every U-Net layer needs at most four).
+constexpr int kPipeNPL = 8, kLeanNPL = 4;
+constexpr int conv_tile_nl(int tile, int ks) { return ks == 1 ? 4 : kConvTiles[tile].NLk; }
+constexpr bool conv_staging_fits(int P, int tile, int ks, int npl) { return P * (kConvTiles[tile].CC / 4) <= 64 * conv_tile_nl(tile, ks) * npl; }
+// The (tile, kernel size) pairs with a split-bf16 instantiation (ConvArgs::prec): the three codec tiles at 1x1 / 2x2 / 3x3
+constexpr bool conv_bf3_form(int tile, int ks) { return (tile == TILE_M128N32 || tile == TILE_M128N64 || tile == TILE_M256N64) && ks >= 1 && ks <= 3; }
 
 // x / d for 0 <= x < 2^16 and 1 < d < 2^16 with magic = floor(2^32 / d) + 1 (exact in that range); magic == 0 encodes d == 1
 __device__ __forceinline__ int fastdiv(int x, unsigned magic) { return magic ? (int)__umulhi((unsigned)x, magic) : x; }

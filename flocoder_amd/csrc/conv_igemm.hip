@@ -229,26 +229,16 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(const ConvDev p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-static const TileInfo kTiles[TILE_COUNT] = {
-    {128, 32, 32, 1, 1, 4},  // TILE_M128N32
-    {128, 64, 16, 1, 2, 4},  // TILE_M128N64
-    {64, 32, 32, 2, 1, 2},   // TILE_M64N32K2
-    {32, 32, 32, 4, 1, 1},   // TILE_M32N32K4
-    {64, 64, 16, 2, 2, 2},   // TILE_M64N64K2
-    {256, 64, 16, 1, 4, 4},  // TILE_M256N64: pipelined kernel only
-};
-
-// the pipelined kernel's instantiations (conv_pipe.hip): same wave layouts, chunk depth chosen so that two stages fit
-static const TileInfo kTilesPipe[TILE_COUNT] = {
-    {128, 32, 16, 1, 1, 4},  // TILE_M128N32
-    {128, 64, 16, 1, 2, 4},  // TILE_M128N64
-    {64, 32, 32, 2, 1, 2},   // TILE_M64N32K2
-    {32, 32, 32, 4, 1, 1},   // TILE_M32N32K4
-    {64, 64, 16, 2, 2, 2},   // TILE_M64N64K2
-    {256, 64, 16, 1, 4, 4},  // TILE_M256N64: 64 x 64 per wave (2 x 2 MFMA tiles): one LDS read per MFMA, weights reused by 256 rows
-};
-constexpr int kPipeNPL = 8;   // patch float4 elements a thread may own per stage
-static const int kPipeLoaderThreads[TILE_COUNT] = {256, 256, 512, 512, 256, 256};   // 64 x loader waves of each pipelined instantiation (1x1 kernels: 256 everywhere)
+// The synchronous kernel's instantiation of every tile that has one (conv_dev.h kConvTiles): conv_init() and conv_launch() both ask here.
+typedef void (*SyncKernel)(const ConvDev);
+template <int TILE>
+static constexpr SyncKernel sync_kernel() {
+    constexpr ConvTileDef t = kConvTiles[TILE];
+    if constexpr (t.CCs != 0) return &conv_igemm_kernel<t.WM, t.WN, t.WK, t.MT, t.NT, t.CCs>;
+    else return nullptr;
+}
+static const SyncKernel kSyncKernels[TILE_COUNT] = {sync_kernel<TILE_M128N32>(), sync_kernel<TILE_M128N64>(), sync_kernel<TILE_M64N32K2>(),
+                                                    sync_kernel<TILE_M32N32K4>(), sync_kernel<TILE_M64N64K2>(), sync_kernel<TILE_M256N64>()};
 
 static int align4(int v) { return (v + 3) & ~3; }
 
@@ -257,7 +247,7 @@ static int conv_cu_count() { return g_cu_count > 0 ? g_cu_count : 256; }
 
 static int conv_geometry(const ConvArgs& a, int tile, bool pipe, ConvDev* d, ConvGeom* g) {
     if (tile < 0 || tile >= TILE_COUNT) return fail(FC_E_ARG, "conv: bad tile id");
-    const TileInfo& t = pipe ? kTilesPipe[tile] : kTiles[tile];
+    const TileInfo t = conv_tile_info(tile, pipe);
     if (!is_pow2(a.H) || !is_pow2(a.W)) return fail(FC_E_SHAPE, "conv: H and W must be powers of two");
     if ((a.s0.C & 3) || (a.s1.C & 3) || (a.Cout & 3)) return fail(FC_E_SHAPE, "conv: channel counts must be multiples of 4");
     if (a.s0.C + a.s1.C != a.Cin) return fail(FC_E_ARG, "conv: Cin != C0 + C1");
@@ -307,7 +297,7 @@ static int conv_geometry(const ConvArgs& a, int tile, bool pipe, ConvDev* d, Con
     g->pipe = pipe ? 1 : 0;
     if (pipe) {
         if (!conv_pipe_supports_ks(a.KS)) return fail(FC_E_SHAPE, "conv: kernel size not instantiated in the pipelined kernel");
-        if (p.P * (t.CC / 4) > (a.KS == 1 ? 256 : kPipeLoaderThreads[tile]) * kPipeNPL) return fail(FC_E_SHAPE, "conv: patch too large for the pipelined kernel");
+        if (!conv_staging_fits(p.P, tile, a.KS, kPipeNPL)) return fail(FC_E_SHAPE, "conv: patch too large for the pipelined kernel");
         const int G0 = a.s0.xf.mode ? a.s0.xf.G : 0, G1 = a.s1.xf.mode ? a.s1.xf.G : 0;
         int o = 0;
         p.o_pixoff = p.o_pixtb = 0;
@@ -317,10 +307,9 @@ static int conv_geometry(const ConvArgs& a, int tile, bool pipe, ConvDev* d, Con
         p.o_patch = o;
         // M32N32K4 at 3x3 loads its weights global -> registers (conv_pipe.hip "DB"): no slab stages in LDS
         const bool direct_b = (t.WMWN == 1 && t.MTNT == 1 && a.KS == 3);
-        // split-bf16 form (ConvArgs::prec): the three codec tiles at 1x1 / 3x3, plain launches only (no fused res_conv / tail, shared weights)
-        // whose weights exist pre-split (ConvArgs::w_b3, pack kind 8)
-        p.bf3 = (a.prec == 1 && a.w_b3 && (tile == TILE_M128N32 || tile == TILE_M128N64 || tile == TILE_M256N64) && (a.KS == 1 || a.KS == 2 || a.KS == 3) && !a.res_out &&
-                 !a.fin.gamma && !a.w_batch_stride) ? 1 : 0;
+        // split-bf16 form (ConvArgs::prec): where an instantiation exists (conv_bf3_form), plain launches only (no fused res_conv / tail,
+        // shared weights) whose weights exist pre-split (ConvArgs::w_b3, pack kind 8)
+        p.bf3 = (a.prec == 1 && a.w_b3 && conv_bf3_form(tile, a.KS) && !a.res_out && !a.fin.gamma && !a.w_batch_stride) ? 1 : 0;
         p.patch_stride = align4(p.P * (t.CC + ((direct_b || p.bf3) ? 4 : 1)));    // (its k-step-quad form strides pixels by CC + 4 floats, and so does split-bf16)
         p.o_wl = o + 2 * p.patch_stride;
         p.wl_stride = direct_b ? 0 : a.KS * a.KS * t.CC * t.BN + (a.res_out ? t.CC * t.BN : 0);
@@ -373,6 +362,7 @@ static int conv_geometry(const ConvArgs& a, int tile, bool pipe, ConvDev* d, Con
         return FC_OK;
     }
     if (a.fin.gamma) return fail(FC_E_SHAPE, "conv: fused tail is implemented in the pipelined kernel only");
+    static_assert(kConvTiles[TILE_M256N64].CCs == 0, "the one tile without a synchronous form");
     if (tile == TILE_M256N64) return fail(FC_E_SHAPE, "conv: M256N64 exists in the pipelined kernel only");
     // LDS carve (in floats)
     int o = 0;
@@ -423,8 +413,9 @@ bool conv_step_close_possible(const ConvArgs& a, int tile) {
 static int auto_tile(const ConvArgs& a) {
     const long M = (long)a.B * a.H * a.W;
     const int hw = a.H * a.W;
-    auto blocks = [&](int t) { return (M / kTiles[t].BM) * cdiv(a.Cout, kTiles[t].BN) * (a.par4 ? 4 : 1); };   // (par4: four classes per launch)
-    auto ok = [&](int t) { return !(a.w_batch_stride && hw < kTiles[t].BM) && M >= kTiles[t].BM; };
+    auto T = [](int t) { return conv_tile_info(t, true); };      // (BM and BN are those of both kernels)
+    auto blocks = [&](int t) { return (M / T(t).BM) * cdiv(a.Cout, T(t).BN) * (a.par4 ? 4 : 1); };   // (par4: four classes per launch)
+    auto ok = [&](int t) { return !(a.w_batch_stride && hw < T(t).BM) && M >= T(t).BM; };
     // Data gradients of the 256-channel 3x3 layers at 4x4 (unet_backward.hip dgrad_to): at 256 rows the thresholds below give them M128N32,
     // ONE accumulation chain over K = 2304, whose rounding (7.4e-7 of the result on random data, against 2.7e-7 for four chains of 576)
     // is past what the backward's pass-through gate allows; the four-chain tile is also the faster one there (256 -> 256: 52.6 against
@@ -466,29 +457,12 @@ int conv_plan(const ConvArgs& a, int tile, ConvGeom* g) {
     return geometry_best(a, tile, &d, g);
 }
 
-template <int WM, int WN, int WK, int MT, int NT, int CC>
-static int launch_t(const ConvDev& d, const ConvGeom& g, hipStream_t s) {
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, WK, MT, NT, CC>), dim3(g.grid), dim3(256), g.lds, s, d);
-    FC_HIP(hipGetLastError());
-    return FC_OK;
-}
-
-template <int WM, int WN, int WK, int MT, int NT, int CC>
-static int allow_big_lds() {
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<WM, WN, WK, MT, NT, CC>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return FC_OK;
-}
-
 // Once per process, before any launch or graph capture: let every instantiation use the full 160 KiB of LDS.
 int conv_init() {
     static bool done = false;
     if (done) return FC_OK;
-    FC_TRY((allow_big_lds<4, 1, 1, 1, 1, 32>()));
-    FC_TRY((allow_big_lds<4, 1, 1, 1, 2, 16>()));
-    FC_TRY((allow_big_lds<2, 1, 2, 1, 1, 32>()));
-    FC_TRY((allow_big_lds<1, 1, 4, 1, 1, 32>()));
-    FC_TRY((allow_big_lds<2, 1, 2, 1, 2, 16>()));
+    for (SyncKernel k : kSyncKernels)
+        if (k) FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     FC_TRY(conv_pipe_init());
     {
         int dev = 0;
@@ -507,14 +481,10 @@ int conv_launch(const ConvArgs& a, int tile, hipStream_t s) {
     if (tile == TILE_AUTO) tile = auto_tile(a);
     FC_TRY(geometry_best(a, tile, &d, &g));
     if (g.pipe) return conv_pipe_launch(d, tile, g.grid, g.lds, s);
-    switch (tile) {
-        case TILE_M128N32: return launch_t<4, 1, 1, 1, 1, 32>(d, g, s);
-        case TILE_M128N64: return launch_t<4, 1, 1, 1, 2, 16>(d, g, s);
-        case TILE_M64N32K2: return launch_t<2, 1, 2, 1, 1, 32>(d, g, s);
-        case TILE_M32N32K4: return launch_t<1, 1, 4, 1, 1, 32>(d, g, s);
-        case TILE_M64N64K2: return launch_t<2, 1, 2, 1, 2, 16>(d, g, s);
-    }
-    return fail(FC_E_ARG, "conv: bad tile id");
+    if (!kSyncKernels[tile]) return fail(FC_E_ARG, "conv: bad tile id");
+    hipLaunchKernelGGL(kSyncKernels[tile], dim3(g.grid), dim3(256), g.lds, s, d);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
 }
 
 }  // namespace fc

@@ -16,11 +16,14 @@
 // VALU/VMEM work of staging overlap inside a workgroup instead of relying on a lucky phase shift between workgroups.
 // A loader thread's patch elements are the same pixels for every chunk (only the channel base moves): their source
 // offsets live in registers and the per-(sample, channel) affine table is built once for all Cin.
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <utility>
+#include <vector>
 #include "conv_dev.h"
 #include "stats_dev.h"
 
@@ -809,130 +812,209 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
 static float* g_zeros16 = nullptr;
 const float* conv_zeros16() { return g_zeros16; }
 
-#define FC_PIPE_TILES(X, KS)               \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, KS, 4)  \
-    X(TILE_M128N64, 4, 1, 1, 1, 2, 16, KS, 4)  \
-    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, KS, (KS == 1 ? 4 : 8)) \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, KS, (KS == 1 ? 4 : 8)) \
-    X(TILE_M64N64K2, 2, 1, 2, 1, 2, 16, KS, 4) \
-    X(TILE_M256N64, 4, 1, 1, 2, 2, 16, KS, 4)
+// Every instantiation of conv_pipe_kernel is one row of a table built once, in conv_pipe_init(): what a launch is matched on -- tile,
+// kernel size, flavour mask (conv_dev.h FL_*, the form bits FL_W4 / FL_WW / FL_STEP included), precision and the two geometry keys --
+// and what it then runs.  conv_pipe_select() picks the row of a launch; the launch, the occupancy query, the route record and the LDS
+// attribute are each written once, against the row.
+struct PipeRow {
+    int tile;
+    int targ[13];                   // the template arguments: the instantiation's name in the code object's symbol table, and its route record
+    void (*fn)(const ConvDev);
+    int nthr;
+    unsigned long long key;         // pipe_key() of the match fields
+};
+enum { A_NPL = 6, A_FL = 9 };       // positions in PipeRow::targ (WM WN WK MT NT CC NPL KS NL FL PREC GEOF GEOK1)
+// The selection runs in front of every eager launch (a training step has some two hundred), so the table is sorted by key and indexed by
+// (tile, kernel size), the key's leading bits: the rows of bucket b are g_begin[b] .. g_begin[b + 1], and g_keys holds their keys
+// side by side, so that a search reads a few consecutive cache lines.  (Before conv_pipe_init() every bucket is empty.)
+static std::vector<PipeRow> g_rows;
+static std::vector<unsigned long long> g_keys;
+constexpr int kBuckets = TILE_COUNT * 16;
+static int g_begin[kBuckets + 1];
 
-template <int KS>
-static int pipe_attr_ks() {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                               \
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, 8, K, NL>),        \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_PIPE_TILES(X, KS)
-#undef X
-    return FC_OK;
+static unsigned long long pipe_key(int tile, int ks, int fl, int prec, int geof, int geok1) {     // add_row() asserts the field widths
+    typedef unsigned long long u64;
+    return (u64)(tile * 16 + ks) << 49 | (u64)prec << 48 | (u64)fl << 32 | (u64)geof << 16 | (u64)geok1;
 }
 
-// Lean flavours (conv_dev.h FL_*) of the tiles the U-Net runs on: 3x3 as plain / + fused res_conv / + fused tail, 1x1 and 2x2 plain.
-// Everything else goes to the FL_ALL instantiation above.
-#define FC_LEAN_TILES(X, KS)               \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, KS, 4)  \
-    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, KS, (KS == 1 ? 4 : 8)) \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, KS, (KS == 1 ? 4 : 8))
+// The one place that names an instantiation: everything about the tile comes from kConvTiles, the staging elements per thread from the
+// mask (conv_dev.h kPipeNPL / kLeanNPL).  A split-bf16 row exists where conv_geometry() may set ConvDev::bf3, and nowhere else.
+template <int TILE, int KS, int FL, int PREC = 0, int GEOF = 0, int GEOK1 = 0>
+static void add_row() {
+    static_assert(KS < 16 && PREC < 2 && FL < (1 << 16) && GEOF < (1 << 16) && GEOK1 < (1 << 16), "the fields of pipe_key()");
+    if constexpr (PREC == 0 || conv_bf3_form(TILE, KS)) {
+        constexpr ConvTileDef t = kConvTiles[TILE];
+        constexpr int NPL = FL == FL_ALL ? kPipeNPL : kLeanNPL, NL = conv_tile_nl(TILE, KS);
+        g_rows.push_back({TILE, {t.WM, t.WN, t.WK, t.MT, t.NT, t.CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1},
+                          &conv_pipe_kernel<t.WM, t.WN, t.WK, t.MT, t.NT, t.CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1>, 256 + 64 * NL,
+                          pipe_key(TILE, KS, FL, PREC, GEOF, GEOK1)});
+    }
+}
+template <int KS, int FL, int PREC = 0, int... TILES>
+static void add_tiles(std::integer_sequence<int, TILES...>) { (add_row<TILES, KS, FL, PREC>(), ...); }
+
+// The all-in-one kernel (FL_ALL) exists for every tile; lean flavours for the tiles the U-Net runs on: 3x3 as plain / + fused res_conv /
+// + fused tail, 1x1 and 2x2 plain.  Everything else goes to the all-in-one instantiation.
+// (The order of the tiles in a list, like that of the rows, carries no meaning.)
+using AllTiles = std::integer_sequence<int, TILE_M256N64, TILE_M64N64K2, TILE_M32N32K4, TILE_M64N32K2, TILE_M128N64, TILE_M128N32>;
+using LeanTiles = std::integer_sequence<int, TILE_M32N32K4, TILE_M64N32K2, TILE_M128N32>;
+// the 64-column tiles the 1x1 projections of the larger models run on (to_qkv and its data gradient): lean flavours for 1x1 only
+using Wide1Tiles = std::integer_sequence<int, TILE_M256N64, TILE_M128N64>;
 
 #define FC_LEAN_FLAVOURS_3(X) X(0) X(FL_POSTOP) X(FL_STATS) X(FL_STATS | FL_STAMP) X(FL_STATS | FL_CAT | FL_STAMP) X(FL_STATS | FL_RES) X(FL_STATS | FL_CAT) X(FL_STATS | FL_RES | FL_CAT) X(FL_STATS | FL_XF) \
     X(FL_STATS | FL_XF | FL_FIN) X(FL_STATS | FL_XF | FL_FIN | FL_GN1) X(FL_STATS | FL_XF | FL_FIN | FL_MEET) X(FL_STATS | FL_XF | FL_FIN | FL_GN1 | FL_MEET) \
     X(FL_STATS | FL_XF | FL_FIN | FL_STAMP) X(FL_STATS | FL_XF | FL_FIN | FL_GN1 | FL_STAMP) X(FL_STATS | FL_XF | FL_FIN | FL_MEET | FL_STAMP) X(FL_STATS | FL_XF | FL_FIN | FL_GN1 | FL_MEET | FL_STAMP)   /* diagnostics: tools/fin_stamps.py */
 #define FC_LEAN_FLAVOURS_1(X) X(0) X(FL_POSTOP) X(FL_XF) X(FL_STATS) X(FL_STATS | FL_XF)
 
-// the 64-column tiles the 1x1 projections of the larger models run on (to_qkv and its data gradient): lean flavours for 1x1 only
-#define FC_LEAN_TILES_WIDE1(X)             \
-    X(TILE_M128N64, 4, 1, 1, 1, 2, 16, 1, 4)   \
-    X(TILE_M256N64, 4, 1, 1, 2, 2, 16, 1, 4)
-
-// the lean kernels keep four window elements per staging thread (the all-in-one ones eight): every U-Net layer needs at most four, and
-// the staging code is unrolled per element
-constexpr int kLeanNPL = 4;
-template <int KS, int FL>
-static int lean_attr() {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                               \
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>),  \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_LEAN_TILES(X, KS)
-#undef X
-    return FC_OK;
-}
-
 // the k-step-quad (FL_W4) flavours exist for the one tile that feeds its weights from registers: M32N32K4 at 3x3; the Block-closing
 // ones among them also in the whole-window form (FL_WW)
 constexpr bool ww_flavour(int FL) { return (FL & FL_FIN) && (FL & FL_XF) && !(FL & (FL_CAT | FL_RES)); }
 template <int FL>
-static int lean_attr_db4() {
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if constexpr (ww_flavour(FL))
-        FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4 | FL_WW>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return FC_OK;
+static void add_lean3() {
+    add_tiles<3, FL>(LeanTiles{});
+    add_row<TILE_M32N32K4, 3, FL | FL_W4>();
+    if constexpr (ww_flavour(FL)) add_row<TILE_M32N32K4, 3, FL | FL_W4 | FL_WW>();
 }
 
-template <int FL>
-static int lean_attr_wide1() {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                               \
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>),  \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_LEAN_TILES_WIDE1(X)
+// Block-closing (fused tail) GEOMETRY flavours: one per tile geometry of the dim-32 inference plan at 4x32x32 (DESIGN.md section 4 lists the launches
+// behind each row), each as plain / + GroupNorm(1) partials / either with stamps, the register-fed rows also in the whole-window form.
+// X(tile, weights, meeting, key); key = geo_key(statistics form, TB, TW, cpg, Tst), conv_dev.h.  A Block-closing launch of any other
+// geometry runs on the lean flavour of its mask that reads the geometry at run time (FC_LEAN_FLAVOURS_3 above) -- not on the all-in-one
+// kernel, which has no register-fed (FL_W4) form of the 32-row tile: it would sum those layers' products in another order, and be slower.
+#define FC_FIN_GEOMS(X)                                                                   \
+    X(TILE_M128N32, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 8, 8))        /* 32 ch @ 32x32 */  \
+    X(TILE_M128N32, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 16, 2))       /* 64 ch @ 16x16 */  \
+    X(TILE_M64N32K2, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 8, 4))       /* 32 ch @ 16x16 */  \
+    X(TILE_M64N32K2, 0, 0, geo_key(GEO_FAST, 1, 8, 32, 1))             /* 128 ch @ 8x8, a whole group per tile */ \
+    X(TILE_M32N32K4, FL_W4, FL_MEET, geo_key(GEO_FAST, 1, 8, 16, 2))   /* 64 ch @ 8x8 */    \
+    X(TILE_M32N32K4, FL_W4, 0, geo_key(GEO_PAIR, 2, 4, 32, 1))         /* 128 ch @ 4x4, two samples per tile */ \
+    X(TILE_M32N32K4, FL_W4, FL_MEET, geo_key(GEO_PAIR, 2, 4, 64, 2))   /* 256 ch @ 4x4: a group spans two column tiles */
+#define FC_FIN_VARIANTS(Y) Y(0) Y(FL_GN1) Y(FL_STAMP) Y(FL_GN1 | FL_STAMP)
+constexpr int kFinBase = FL_STATS | FL_XF | FL_FIN;
+template <int TILE, int W4, int MEET, int GEO>
+static void add_fin_geom() {
+#define Y(V) add_row<TILE, 3, kFinBase | W4 | MEET | (V), 0, GEO>();
+    FC_FIN_VARIANTS(Y)
+#undef Y
+    if constexpr (W4 != 0) {
+#define Y(V) add_row<TILE, 3, kFinBase | W4 | FL_WW | MEET | (V), 0, GEO>();
+        FC_FIN_VARIANTS(Y)
+#undef Y
+    }
+}
+
+// The step-closing flavour (conv_dev.h FL_STEP): final_res_block's closing launch of the dim-32 plan at 4x32x32 -- the first row of
+// FC_FIN_GEOMS with the meeting, no GroupNorm(1) partials -- and its stamped twin.  Nothing else is instantiated with the bit, and a launch
+// that asks for it (ConvFin::step) without matching the key is an error, never another kernel: the plan has dropped its final_conv and
+// init_conv launches by then.
+constexpr int kStepGeo = geo_key(GEO_FAST, 1, 16, 8, 8), kStepMask = kFinBase | FL_MEET;
+
+// Block-OPENING (conv1) GEOMETRY flavours: the first convolution of every ResnetBlock of the same plan -- statistics of the raw output, in the
+// up path also the concatenated skip and the fused res_conv output -- each also with stamps.  A Block's conv1 has the output geometry of its
+// closing launch, so the keys are those of FC_FIN_GEOMS; only the (tile, mask, key) triples the plan's 19 conv1 launches use exist.
+// X(tile, weights, mask, key)
+constexpr int kConv1Up = FL_STATS | FL_CAT | FL_RES;
+#define FC_CONV1_GEOMS(X)                                                                   \
+    X(TILE_M128N32, 0, FL_STATS, geo_key(GEO_FAST, 1, 16, 8, 8))       /* downs.0.* */      \
+    X(TILE_M128N32, 0, kConv1Up, geo_key(GEO_FAST, 1, 16, 8, 8))       /* ups.3.*, final_res_block */ \
+    X(TILE_M128N32, 0, kConv1Up, geo_key(GEO_FAST, 1, 16, 16, 2))      /* ups.2.* */        \
+    X(TILE_M64N32K2, 0, FL_STATS, geo_key(GEO_FAST, 1, 16, 8, 4))      /* downs.1.* */      \
+    X(TILE_M64N32K2, 0, kConv1Up, geo_key(GEO_FAST, 1, 8, 32, 1))      /* ups.1.* */        \
+    X(TILE_M32N32K4, FL_W4, FL_STATS, geo_key(GEO_FAST, 1, 8, 16, 2))  /* downs.2.* */      \
+    X(TILE_M32N32K4, FL_W4, FL_STATS, geo_key(GEO_PAIR, 2, 4, 32, 1))  /* downs.3.* */      \
+    X(TILE_M32N32K4, FL_W4, FL_STATS, geo_key(GEO_PAIR, 2, 4, 64, 2))  /* mid_block1, mid_block2 */ \
+    X(TILE_M32N32K4, FL_W4, kConv1Up, geo_key(GEO_PAIR, 2, 4, 64, 2))  /* ups.0.* */
+
+static void build_rows() {
+    g_rows.clear();
+#define X(T, W4, MEET, GEO) add_fin_geom<T, W4, MEET, GEO>();
+    FC_FIN_GEOMS(X)
 #undef X
-    return FC_OK;
-}
-
-// Either launches `kernel` or, when `occ` is given, asks the runtime how many workgroups of it one CU holds at this LDS size (the
-// fused tail's residency condition is derived from that, per instantiation -- conv_igemm.hip).
-template <class K>
-static int launch_or_query(K kernel, int nthr, const ConvDev& d, int grid, size_t lds, hipStream_t s, int* occ) {
-    if (occ) {
-        FC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kernel, nthr, lds));
-        return FC_OK;
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(nthr), lds, s, d);
-    FC_HIP(hipGetLastError());
-    return FC_OK;
-}
-// Diagnostics (fc_debug_conv_routes, tools/flavour_sizes.py): the thirteen template arguments of the instantiation every launch went to, one line
-// per launch -- they are the instantiation's name in the code object's symbol table.
-static std::mutex g_route_mu;
-static bool g_route_on = false;
-static std::string g_route_log;
-void conv_route_log_set(bool on) { std::lock_guard<std::mutex> lk(g_route_mu); g_route_on = on; if (on) g_route_log.clear(); }
-std::string conv_route_log_get() { std::lock_guard<std::mutex> lk(g_route_mu); return g_route_log; }
-
-template <int WM, int WN, int WK, int MT, int NT, int CC, int NPL, int KS, int NL, int FL = FL_ALL, int PREC = 0, int GEOF = 0, int GEOK1 = 0>
-static int launch_pipe(const ConvDev& d, int grid, size_t lds, hipStream_t s, int* occ) {
-    if (!occ && g_route_on) {
-        std::lock_guard<std::mutex> lk(g_route_mu);
-        const int v[13] = {WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1};
-        for (int i = 0; i < 13; ++i) g_route_log += std::to_string(v[i]) + (i < 12 ? " " : "\n");
-    }
-    return launch_or_query((conv_pipe_kernel<WM, WN, WK, MT, NT, CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1>), 256 + 64 * NL, d, grid, lds, s, occ);
-}
-
-template <int FL>
-static int lean_launch_wide1(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
-    switch (tile) {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                                       \
-    case T:                                                                                                                       \
-        if (d.P * (CC / 4) > 64 * NL * kLeanNPL) return -1;                                                                       \
-        return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>(d, grid, lds, s, occ);
-        FC_LEAN_TILES_WIDE1(X)
+    add_row<TILE_M128N32, 3, kStepMask | FL_STEP, 0, kStepGeo>();
+    add_row<TILE_M128N32, 3, kStepMask | FL_STEP | FL_STAMP, 0, kStepGeo>();
+#define X(T, W4, MASK, GEO) add_row<T, 3, (MASK) | (W4), 0, 0, GEO>(); add_row<T, 3, (MASK) | (W4) | FL_STAMP, 0, 0, GEO>();
+    FC_CONV1_GEOMS(X)
 #undef X
-        default: return -1;
-    }
+    // (split-bf16: four staging waves as in the fp32 form: eight measured 364 against 380 images/s on the SD-VAE decode)
+    add_tiles<1, FL_ALL, 1>(AllTiles{}); add_tiles<2, FL_ALL, 1>(AllTiles{}); add_tiles<3, FL_ALL, 1>(AllTiles{});
+    add_tiles<1, FL_ALL>(AllTiles{}); add_tiles<2, FL_ALL>(AllTiles{}); add_tiles<3, FL_ALL>(AllTiles{}); add_tiles<5, FL_ALL>(AllTiles{});
+#define X(F) add_lean3<(F)>();
+    FC_LEAN_FLAVOURS_3(X)
+#undef X
+#define X(F) add_tiles<1, (F)>(LeanTiles{}); add_tiles<1, (F)>(Wide1Tiles{});
+    FC_LEAN_FLAVOURS_1(X)
+#undef X
+    add_tiles<2, 0>(LeanTiles{});
 }
 
-template <int FL>
-static int lean_launch_db4(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
-    if (tile != TILE_M32N32K4 || d.P * (32 / 4) > 64 * 8 * kLeanNPL) return -1;
-    return launch_pipe<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4>(d, grid, lds, s, occ);
+static const PipeRow* find_row(int tile, int ks, int fl, int prec = 0, int geof = 0, int geok1 = 0) {
+    if (ks < 0 || ks >= 16) return nullptr;
+    const unsigned long long key = pipe_key(tile, ks, fl, prec, geof, geok1);
+    for (int i = g_begin[tile * 16 + ks]; i < g_begin[tile * 16 + ks + 1]; ++i)
+        if (g_keys[i] == key) return &g_rows[i];
+    return nullptr;
+}
+
+// The statistics geometry of a launch on `tile`, shared by the two kinds of geometry key: form, channels per group, column tiles and
+// groups per tile, statistics slots per group (at most max_Tst).  False when the launch is not one a geometry flavour may take.
+struct StatGeo { int BM, BN, nthr, form, cpg, ngt, Tst; };
+static bool stat_geometry(const ConvDev& d, int tile, int max_Tst, StatGeo* g) {
+    const ConvArgs& a = d.a;
+    const TileInfo t = conv_tile_info(tile, true);
+    if (!a.stats_out || a.par4 || a.stats_tmul != 1 || a.stats_toff != 0) return false;
+    if (d.TB != 1 && d.TB != 2) return false;
+    if (d.rps != t.BM / d.TB || (1 << (d.TWl + d.THl)) * d.TB != t.BM) return false;
+    const bool pair_tile = t.BM == 32 && t.BN == 32;
+    const int form = (pair_tile && d.TB == 2 && d.rps == 16) ? GEO_PAIR : (d.TB == 1 ? GEO_FAST : 0);
+    if (!form) return false;
+    const int cpg = d.cpg, NPG = cpg >= t.BN ? cpg / t.BN : 1;
+    if (cpg < 1 || (cpg & (cpg - 1)) || cpg > (1 << 15) || d.cpgt != (cpg < t.BN ? cpg : t.BN) || d.NPG != NPG) return false;
+    const int Tst = (d.TB > 1 ? 1 : d.tiles_x * d.tiles_y) * NPG;
+    if (Tst < 1 || Tst > max_Tst) return false;
+    *g = {t.BM, t.BN, 256 + 64 * conv_tile_nl(tile, 3), form, cpg, cpg >= t.BN ? 1 : t.BN / cpg, Tst};
+    return true;
+}
+
+// The geometry key of a Block-closing launch, or 0 when the launch is not one a geometry flavour may take: the flavours assume (and
+// compile in) everything tested here.
+static int fin_geo_key(const ConvDev& d, int tile) {
+    const ConvArgs& a = d.a;
+    StatGeo g;
+    if (!a.fin.gamma || a.s1.C || !a.s0.xf.mode || !stat_geometry(d, tile, kPartPre, &g)) return 0;
+    if (a.Cout % g.BN || a.Cin != a.Cout || a.s0.xf.G <= 0 || a.s0.C != a.s0.xf.G * g.cpg || a.s0.xf.T != g.Tst) return 0;   // the input is this Block's own h
+    if (d.TB * a.Cin > g.nthr - 256 || d.TB * a.s0.xf.G > g.nthr - 256 || d.TB * g.ngt * g.Tst * 2 > g.nthr) return 0;        // one table entry / granule per thread
+    return geo_key(g.form, d.TB, 1 << d.TWl, g.cpg, g.Tst);
+}
+
+// The geometry key of a conv1 launch, or 0 when it is not one a conv1 geometry flavour may take: the statistics geometry as above, and
+// besides it a plain 3x3 stride-1 window (no upsampling, no parity form, no activation or addend), kFinGeomGroups groups over whole
+// column tiles and the wide store form.
+static int conv1_geo_key(const ConvDev& d, int tile) {
+    const ConvArgs& a = d.a;
+    StatGeo g;
+    if (a.fin.gamma || a.stats_post || d.any_xf || a.out_act || a.add || d.o_out < 0 || !stat_geometry(d, tile, 63, &g)) return 0;
+    if (a.KS != 3 || a.stride != 1 || a.ups || a.pad != 1 || a.pad_y >= 0 || a.pad_x >= 0 || a.out_sh || a.out_oy || a.out_ox || a.Hs != a.H || a.Ws != a.W) return 0;
+    if (a.Gout != kFinGeomGroups || a.Cout != kFinGeomGroups * g.cpg || a.Cout % g.BN || d.ntiles != a.Cout / g.BN) return 0;
+    const int TW = 1 << d.TWl, TH = 1 << d.THl;
+    if (d.PW != TW + 2 || d.PH != TH + 2 || d.P != d.TB * d.PH * d.PW) return 0;
+    return geo_key(g.form, d.TB, TW, g.cpg, g.Tst);
+}
+
+static bool lean_kernels_on() {
+    static const bool lean = [] { const char* e = std::getenv("FLOCODER_AMD_LEAN_KERNELS"); return !(e && std::string(e) == "0"); }();
+    return lean;
+}
+bool conv_pipe_step_ok(const ConvDev& d, int tile) {
+    const ConvArgs& a = d.a;
+    return lean_kernels_on() && tile == TILE_M128N32 && a.KS == 3 && !d.bf3 && d.o_out >= 0 && !a.fin.gn1_out && !a.res_out && !a.stats_post && !a.out_act && !a.add &&
+           !d.fin_local && d.any_xf && !a.out_sh && !a.out_oy && !a.out_ox && a.Cout == kStepDim && d.ntiles == 1 && conv_staging_fits(d.P, tile, 3, kLeanNPL) &&
+           d.gsz == geo_Tst(kStepGeo) && fin_geo_key(d, tile) == kStepGeo;
 }
 
 // Whole-window staging (FL_WW): the LDS bytes of the launch in that form, or 0 when it keeps the per-chunk loader -- the window of all Cin
 // chunks (chunk i at o_patch + i patch_stride; the tail's scratch aliases it as before) does not fit, a thread would hold more than
 // kWWSlots elements, or the grid needs two workgroups per CU, which the larger LDS may not allow.  The caller has checked the
-// register-fed form's own conditions (`w4`: whole 32-channel chunks, pad 1).
+// register-fed form's own conditions (pipe_w4: whole 32-channel chunks, pad 1).
 static int g_pipe_cus = 0;
 static size_t ww_lds(const ConvDev& d, int tile, size_t lds) {
     const ConvArgs& a = d.a;
@@ -942,346 +1024,138 @@ static size_t ww_lds(const ConvDev& d, int tile, size_t lds) {
     return tot <= 160 * 1024 ? tot : 0;
 }
 
-template <int FL>
-static int lean_launch_ww(const ConvDev& d, int tile, int grid, size_t lds_ww, hipStream_t s, int* occ) {
-    if constexpr (ww_flavour(FL)) return launch_pipe<1, 1, 4, 1, 1, 32, kLeanNPL, 3, 8, FL | FL_W4 | FL_WW>(d, grid, lds_ww, s, occ);
-    else return -1;
-}
-
-template <int KS, int FL>
-static int lean_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
-    switch (tile) {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                                       \
-    case T:                                                                                                                       \
-        if (d.P * (CC / 4) > 64 * NL * kLeanNPL) return -1;    /* more window elements per staging thread than a lean kernel keeps */ \
-        return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, K, NL, FL>(d, grid, lds, s, occ);
-        FC_LEAN_TILES(X, KS)
-#undef X
-        default: return -1;      // no lean flavour of this tile
-    }
-}
-
-// Block-closing (fused tail) GEOMETRY flavours: one per tile geometry of the dim-32 inference plan at 4x32x32 (DESIGN.md section 4 lists the launches
-// behind each row), each as plain / + GroupNorm(1) partials / either with stamps.  X(tile, WM, WN, WK, MT, NT, CC, NL, weights, meeting, key);
-// key = geo_key(statistics form, TB, TW, cpg, Tst), conv_dev.h.  A Block-closing launch of any other geometry runs on the lean flavour of its
-// mask that reads the geometry at run time (FC_LEAN_FLAVOURS_3 above, as before) -- not on the all-in-one kernel, which has no register-fed
-// (FL_W4) form of the 32-row tile: it would sum those layers' products in another order, and be slower.
-#define FC_FIN_GEOMS(X)                                                                                      \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 8, 8))       /* 32 ch @ 32x32 */  \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 16, 2))      /* 64 ch @ 16x16 */  \
-    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, FL_MEET, geo_key(GEO_FAST, 1, 16, 8, 4))      /* 32 ch @ 16x16 */  \
-    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, 0, geo_key(GEO_FAST, 1, 8, 32, 1))            /* 128 ch @ 8x8, a whole group per tile */ \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_MEET, geo_key(GEO_FAST, 1, 8, 16, 2))  /* 64 ch @ 8x8 */    \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, 0, geo_key(GEO_PAIR, 2, 4, 32, 1))        /* 128 ch @ 4x4, two samples per tile */ \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_MEET, geo_key(GEO_PAIR, 2, 4, 64, 2))  /* 256 ch @ 4x4: a group spans two column tiles */
-#define FC_FIN_VARIANTS(Y) Y(0) Y(FL_GN1) Y(FL_STAMP) Y(FL_GN1 | FL_STAMP)
-constexpr int kFinBase = FL_STATS | FL_XF | FL_FIN;
-
-// The geometry key of a Block-closing launch on a tile of BM x BN with `nthr` threads, or 0 when the launch is not one a geometry flavour
-// may take: the flavours assume (and compile in) everything tested here.
-static int fin_geo_key(const ConvDev& d, int BM, int BN, int nthr, bool pair_tile) {
+// The flavour mask of a launch: what the instantiation it runs on has to be able to do.  The selection and the occupancy cache both ask here.
+static int pipe_need(const ConvDev& d, int tile) {
     const ConvArgs& a = d.a;
-    if (!a.fin.gamma || !a.stats_out || a.par4 || a.stats_tmul != 1 || a.stats_toff != 0 || a.s1.C || !a.s0.xf.mode) return 0;
-    if (d.TB != 1 && d.TB != 2) return 0;
-    if (d.rps != BM / d.TB || (1 << (d.TWl + d.THl)) * d.TB != BM) return 0;
-    const int form = (pair_tile && d.TB == 2 && d.rps == 16) ? GEO_PAIR : (d.TB == 1 ? GEO_FAST : 0);
-    if (!form) return 0;
-    const int cpg = d.cpg, NPG = cpg >= BN ? cpg / BN : 1, ngt = cpg >= BN ? 1 : BN / cpg;
-    if (cpg < 1 || (cpg & (cpg - 1)) || cpg > (1 << 15) || d.cpgt != (cpg < BN ? cpg : BN) || d.NPG != NPG) return 0;
-    const int Tst = (d.TB > 1 ? 1 : d.tiles_x * d.tiles_y) * NPG;
-    if (Tst < 1 || Tst > kPartPre) return 0;
-    if (a.Cout % BN || a.Cin != a.Cout || a.s0.xf.G <= 0 || a.s0.C != a.s0.xf.G * cpg || a.s0.xf.T != Tst) return 0;   // the input is this Block's own h
-    if (d.TB * a.Cin > nthr - 256 || d.TB * a.s0.xf.G > nthr - 256 || d.TB * ngt * Tst * 2 > nthr) return 0;           // one table entry / granule per thread
-    return geo_key(form, d.TB, 1 << d.TWl, cpg, Tst);
+    return (a.fin.gamma ? FL_FIN : 0) | (a.res_out ? FL_RES : 0) | (a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |
+           (a.s1.C ? FL_CAT : 0) | (d.stamps ? FL_STAMP : 0) | (a.stats_out ? FL_STATS : 0) | (a.fin.gn1_out ? FL_GN1 : 0) |
+           ((a.out_act || a.add) ? FL_POSTOP : 0) | (d.o_out < 0 ? FL_NARROW : 0) |
+           ((d.TB > 1 && tile != TILE_M32N32K4) ? FL_MULTI : 0) |        // (the 32-row tile always handles several samples)
+           ((a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
+}
+// register-fed weights in the k-step-quad layout: whole 32-channel chunks, whole 32-column tiles, the centre tap at (1, 1)
+static bool pipe_w4(const ConvDev& d, int tile) {
+    const ConvArgs& a = d.a;
+    return tile == TILE_M32N32K4 && a.KS == 3 && a.w4 && a.Cin % 32 == 0 && a.Cout % 32 == 0 && a.pad == 1 && !a.w_batch_stride && (!a.res_out || a.res_w4);
 }
 
-template <int WM, int WN, int WK, int MT, int NT, int CC, int NL, int W4, int MEET, int GEO>
-static int fin_geom_row_attr() {
-#define Y(V) FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | MEET | (V), 0, GEO>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_FIN_VARIANTS(Y)
-#undef Y
-    if constexpr (W4 != 0) {         // the register-fed rows also in the whole-window form
-#define Y(V) FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | FL_WW | MEET | (V), 0, GEO>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        FC_FIN_VARIANTS(Y)
-#undef Y
+// The row a launch runs on and the LDS bytes to launch it with (the whole-window form has its own).  With lean kernels on, the smallest
+// flavour that covers the launch, in this order: the step-closing flavour (or its error), the flavour of exactly this geometry, the
+// whole-window, k-step-quad and plain lean flavours of the mask; else the all-in-one kernel.
+struct PipePick { const PipeRow* row; size_t lds; };
+static int conv_pipe_select(const ConvDev& d, int tile, size_t lds, PipePick* out) {
+    const ConvArgs& a = d.a;
+    if (tile < 0 || tile >= TILE_COUNT) return fail(FC_E_ARG, "conv: bad tile id");
+    if (d.bf3) {
+        *out = {find_row(tile, a.KS, FL_ALL, 1), lds};
+        return out->row ? FC_OK : fail(FC_E_ARG, "conv: no split-bf16 form of this tile");
     }
-    return FC_OK;
-}
-static int fin_geom_attr() {
-#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO) FC_TRY((fin_geom_row_attr<WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO>()));
-    FC_FIN_GEOMS(X)
-#undef X
-    return FC_OK;
-}
-
-// one row of FC_FIN_GEOMS, its geometry matched already: the whole-window form when the launch may take it (lds_ww != 0, and the layer
-// has the groups the flavour's trip counts assume), else the per-chunk form.  -1: no variant of this mask
-template <int WM, int WN, int WK, int MT, int NT, int CC, int NL, int W4, int MEET, int GEO>
-static int fin_geom_row_launch(const ConvDev& d, int need, int grid, size_t lds, size_t lds_ww, hipStream_t s, int* occ) {
-    if constexpr (W4 != 0) {
-        if (lds_ww && d.a.Cin == kFinGeomGroups * geo_cpg(GEO)) {
-#define Y(V) if (need == (kFinBase | MEET | (V))) return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | FL_WW | MEET | (V), 0, GEO>(d, grid, lds_ww, s, occ);
-            FC_FIN_VARIANTS(Y)
-#undef Y
+    // a lean row is taken if it exists and its loader can stage the window (the whole-window form has no per-chunk loader)
+    auto take = [&](int fl, int geof, int geok1, size_t row_lds) {
+        const PipeRow* r = find_row(tile, a.KS, fl, 0, geof, geok1);
+        if (!r || (!(fl & FL_WW) && !conv_staging_fits(d.P, tile, a.KS, r->targ[A_NPL]))) return false;
+        *out = {r, row_lds};
+        return true;
+    };
+    const bool lean = lean_kernels_on();
+    if (a.fin.step && !(lean && a.KS == 3)) return fail(FC_E_STATE, "conv: the step-closing flavour is a lean 3x3 kernel");
+    if (lean) {
+        const int need = pipe_need(d, tile), w4 = pipe_w4(d, tile) ? FL_W4 : 0;
+        const size_t lds_ww = (w4 && (need & FL_FIN)) ? ww_lds(d, tile, lds) : 0;
+        if ((need & FL_FIN) && a.fin.step) {
+            if (conv_pipe_step_ok(d, tile) && (need & ~FL_STAMP) == kStepMask && take(need | FL_STEP, kStepGeo, 0, lds)) return FC_OK;
+            return fail(FC_E_STATE, "conv: the launch is not the one the step-closing flavour is compiled for");
         }
+        if (a.KS == 3 && (need & FL_FIN)) {             // Block-closing: whole-window where the launch may take it and the layer has the groups the flavour's trip counts assume
+            const int geo = fin_geo_key(d, tile);
+            if (geo && lds_ww && a.Cin == kFinGeomGroups * geo_cpg(geo) && take(need | w4 | FL_WW, geo, 0, lds_ww)) return FC_OK;
+            if (geo && take(need | w4, geo, 0, lds)) return FC_OK;
+        } else if (a.KS == 3 && (need & FL_STATS)) {    // Block-opening
+            const int geo = conv1_geo_key(d, tile);
+            if (geo && take(need | w4, 0, geo, lds)) return FC_OK;
+        }
+        if (lds_ww && take(need | FL_W4 | FL_WW, 0, 0, lds_ww)) return FC_OK;
+        if (w4 && take(need | FL_W4, 0, 0, lds)) return FC_OK;
+        if (take(need, 0, 0, lds)) return FC_OK;
     }
-#define Y(V) if (need == (kFinBase | MEET | (V))) return launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, kFinBase | W4 | MEET | (V), 0, GEO>(d, grid, lds, s, occ);
-    FC_FIN_VARIANTS(Y)
-#undef Y
-    return -1;
-}
-
-// -1: no flavour of this (tile, weights form, mask, geometry)
-static int fin_geom_launch(const ConvDev& d, int tile, bool w4, int need, int grid, size_t lds, size_t lds_ww, hipStream_t s, int* occ) {
-#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO)                                                         \
-    if (tile == T && (w4 ? FL_W4 : 0) == (W4) && d.P * (CC / 4) <= 64 * NL * kLeanNPL &&                        \
-        fin_geo_key(d, 32 * MT * WM, 32 * NT * WN, 256 + 64 * NL, WM * MT == 1 && WN * NT == 1) == (GEO))       \
-        return fin_geom_row_launch<WM, WN, WK, MT, NT, CC, NL, W4, MEET, GEO>(d, need, grid, lds, lds_ww, s, occ);
-    FC_FIN_GEOMS(X)
-#undef X
-    return -1;
-}
-
-// The step-closing flavour (conv_dev.h FL_STEP): final_res_block's closing launch of the dim-32 plan at 4x32x32 -- the first row of
-// FC_FIN_GEOMS with the meeting, no GroupNorm(1) partials -- and its stamped twin.  Nothing else is instantiated with the bit, and a launch
-// that asks for it (ConvFin::step) without matching the key is an error, never another kernel: the plan has dropped its final_conv and
-// init_conv launches by then.
-constexpr int kStepGeo = geo_key(GEO_FAST, 1, 16, 8, 8), kStepMask = kFinBase | FL_MEET;
-static bool lean_kernels_on() {
-    static const bool lean = [] { const char* e = std::getenv("FLOCODER_AMD_LEAN_KERNELS"); return !(e && std::string(e) == "0"); }();
-    return lean;
-}
-bool conv_pipe_step_ok(const ConvDev& d, int tile) {
-    const ConvArgs& a = d.a;
-    return lean_kernels_on() && tile == TILE_M128N32 && a.KS == 3 && !d.bf3 && d.o_out >= 0 && !a.fin.gn1_out && !a.res_out && !a.stats_post && !a.out_act && !a.add &&
-           !d.fin_local && d.any_xf && !a.out_sh && !a.out_oy && !a.out_ox && a.Cout == kStepDim && d.ntiles == 1 && d.P * (16 / 4) <= 64 * 4 * kLeanNPL &&
-           d.gsz == geo_Tst(kStepGeo) && fin_geo_key(d, 128, 32, 512, false) == kStepGeo;
-}
-static int fin_step_attr() {
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP, 0, kStepGeo>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP | FL_STAMP, 0, kStepGeo>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return FC_OK;
-}
-static int fin_step_launch(const ConvDev& d, int tile, int need, int grid, size_t lds, hipStream_t s, int* occ) {
-    if (!conv_pipe_step_ok(d, tile) || (need & ~FL_STAMP) != kStepMask) return fail(FC_E_STATE, "conv: the launch is not the one the step-closing flavour is compiled for");
-    if (!occ) step_route_log_add("step_close");
-    return (need & FL_STAMP) ? launch_pipe<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP | FL_STAMP, 0, kStepGeo>(d, grid, lds, s, occ)
-                             : launch_pipe<4, 1, 1, 1, 1, 16, kLeanNPL, 3, 4, kStepMask | FL_STEP, 0, kStepGeo>(d, grid, lds, s, occ);
-}
-
-// Block-OPENING (conv1) GEOMETRY flavours: the first convolution of every ResnetBlock of the same plan -- statistics of the raw output, in the
-// up path also the concatenated skip and the fused res_conv output.  A Block's conv1 has the output geometry of its closing launch, so the
-// keys are those of FC_FIN_GEOMS; only the (tile, mask, key) triples the plan's 19 conv1 launches use exist.
-// X(tile, WM, WN, WK, MT, NT, CC, NL, weights, mask, key)
-constexpr int kConv1Up = FL_STATS | FL_CAT | FL_RES;
-#define FC_CONV1_GEOMS(X)                                                                                    \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, FL_STATS, geo_key(GEO_FAST, 1, 16, 8, 8))      /* downs.0.* */      \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, kConv1Up, geo_key(GEO_FAST, 1, 16, 8, 8))      /* ups.3.*, final_res_block */ \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, 4, 0, kConv1Up, geo_key(GEO_FAST, 1, 16, 16, 2))     /* ups.2.* */        \
-    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, FL_STATS, geo_key(GEO_FAST, 1, 16, 8, 4))     /* downs.1.* */      \
-    X(TILE_M64N32K2, 2, 1, 2, 1, 1, 32, 8, 0, kConv1Up, geo_key(GEO_FAST, 1, 8, 32, 1))     /* ups.1.* */        \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_STATS, geo_key(GEO_FAST, 1, 8, 16, 2)) /* downs.2.* */      \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_STATS, geo_key(GEO_PAIR, 2, 4, 32, 1)) /* downs.3.* */      \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, FL_STATS, geo_key(GEO_PAIR, 2, 4, 64, 2)) /* mid_block1, mid_block2 */ \
-    X(TILE_M32N32K4, 1, 1, 4, 1, 1, 32, 8, FL_W4, kConv1Up, geo_key(GEO_PAIR, 2, 4, 64, 2)) /* ups.0.* */
-
-// The geometry key of a conv1 launch on a tile of BM x BN, or 0 when it is not one a conv1 geometry flavour may take: the flavours assume
-// (and compile in) everything tested here -- the statistics geometry as fin_geo_key() does, and besides it a plain 3x3 stride-1 window
-// (no upsampling, no parity form, no activation or addend), kFinGeomGroups groups over whole column tiles and the wide store form.
-static int conv1_geo_key(const ConvDev& d, int BM, int BN, bool pair_tile) {
-    const ConvArgs& a = d.a;
-    if (a.fin.gamma || !a.stats_out || a.stats_post || a.par4 || a.stats_tmul != 1 || a.stats_toff != 0 || d.any_xf || a.out_act || a.add || d.o_out < 0) return 0;
-    if (a.KS != 3 || a.stride != 1 || a.ups || a.pad != 1 || a.pad_y >= 0 || a.pad_x >= 0 || a.out_sh || a.out_oy || a.out_ox || a.Hs != a.H || a.Ws != a.W) return 0;
-    if (d.TB != 1 && d.TB != 2) return 0;
-    if (d.rps != BM / d.TB || (1 << (d.TWl + d.THl)) * d.TB != BM) return 0;
-    const int form = (pair_tile && d.TB == 2 && d.rps == 16) ? GEO_PAIR : (d.TB == 1 ? GEO_FAST : 0);
-    if (!form) return 0;
-    const int cpg = d.cpg, NPG = cpg >= BN ? cpg / BN : 1;
-    if (cpg < 1 || (cpg & (cpg - 1)) || cpg > (1 << 15) || d.cpgt != (cpg < BN ? cpg : BN) || d.NPG != NPG) return 0;
-    const int Tst = (d.TB > 1 ? 1 : d.tiles_x * d.tiles_y) * NPG;
-    if (Tst < 1 || Tst > 63) return 0;
-    if (a.Gout != kFinGeomGroups || a.Cout != kFinGeomGroups * cpg || a.Cout % BN || d.ntiles != a.Cout / BN) return 0;
-    const int TW = 1 << d.TWl, TH = 1 << d.THl;
-    if (d.PW != TW + 2 || d.PH != TH + 2 || d.P != d.TB * d.PH * d.PW) return 0;
-    return geo_key(form, d.TB, TW, cpg, Tst);
-}
-
-static int conv1_geom_attr() {
-#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MASK, GEO)                                                                                            \
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4), 0, 0, GEO>),    \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                                           \
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4) | FL_STAMP, 0, 0, GEO>), \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_CONV1_GEOMS(X)
-#undef X
-    return FC_OK;
-}
-
-// -1: no conv1 flavour of this (tile, weights form, mask, geometry)
-static int conv1_geom_launch(const ConvDev& d, int tile, bool w4, int need, int grid, size_t lds, hipStream_t s, int* occ) {
-#define X(T, WM, WN, WK, MT, NT, CC, NL, W4, MASK, GEO)                                                                                        \
-    if (tile == T && (w4 ? FL_W4 : 0) == (W4) && (need & ~FL_STAMP) == (MASK) && d.P * (CC / 4) <= 64 * NL * kLeanNPL &&                       \
-        conv1_geo_key(d, 32 * MT * WM, 32 * NT * WN, WM * MT == 1 && WN * NT == 1) == (GEO))                                                   \
-        return (need & FL_STAMP) ? launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4) | FL_STAMP, 0, 0, GEO>(d, grid, lds, s, occ) \
-                                 : launch_pipe<WM, WN, WK, MT, NT, CC, kLeanNPL, 3, NL, (MASK) | (W4), 0, 0, GEO>(d, grid, lds, s, occ);
-    FC_CONV1_GEOMS(X)
-#undef X
-    return -1;
-}
-
-// (four staging waves as in the fp32 form: eight measured 364 against 380 images/s on the SD-VAE decode)
-#define FC_BF3_TILES(X, KS)                \
-    X(TILE_M128N32, 4, 1, 1, 1, 1, 16, KS, 4)  \
-    X(TILE_M128N64, 4, 1, 1, 1, 2, 16, KS, 4)  \
-    X(TILE_M256N64, 4, 1, 1, 2, 2, 16, KS, 4)
-template <int KS>
-static int bf3_attr_ks() {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL)                                                                                  \
-    FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pipe_kernel<WM, WN, WK, MT, NT, CC, 8, K, NL, FL_ALL, 1>), \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    FC_BF3_TILES(X, KS)
-#undef X
-    return FC_OK;
-}
-template <int KS>
-static int bf3_launch_ks(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
-    switch (tile) {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL) \
-    case T: return launch_pipe<WM, WN, WK, MT, NT, CC, 8, K, NL, FL_ALL, 1>(d, grid, lds, s, occ);
-        FC_BF3_TILES(X, KS)
-#undef X
-        default: return fail(FC_E_ARG, "conv: no split-bf16 form of this tile");
-    }
-}
-
-int conv_pipe_init() {
-    static bool done = false;
-    if (done) return FC_OK;
-    FC_TRY(bf3_attr_ks<1>());
-    FC_TRY(bf3_attr_ks<2>());
-    FC_TRY(bf3_attr_ks<3>());
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        FC_HIP(hipGetDevice(&dev));
-        FC_HIP(hipGetDeviceProperties(&prop, dev));
-        g_pipe_cus = prop.multiProcessorCount;
-    }
-    FC_HIP(hipMalloc(reinterpret_cast<void**>(&g_zeros16), 256));
-    FC_HIP(hipMemset(g_zeros16, 0, 256));
-    FC_TRY(pipe_attr_ks<1>());
-    FC_TRY(pipe_attr_ks<2>());
-    FC_TRY(pipe_attr_ks<3>());
-    FC_TRY(pipe_attr_ks<5>());
-#define X(F) FC_TRY((lean_attr<3, (F)>())); FC_TRY((lean_attr_db4<(F)>()));
-    FC_LEAN_FLAVOURS_3(X)
-#undef X
-#define X(F) FC_TRY((lean_attr<1, (F)>())); FC_TRY((lean_attr_wide1<(F)>()));
-    FC_LEAN_FLAVOURS_1(X)
-#undef X
-    FC_TRY((lean_attr<2, 0>()));
-    FC_TRY(fin_geom_attr());
-    FC_TRY(fin_step_attr());
-    FC_TRY(conv1_geom_attr());
-    done = true;
-    return FC_OK;
+    *out = {find_row(tile, a.KS, FL_ALL), lds};
+    return out->row ? FC_OK : fail(FC_E_SHAPE, "conv: kernel size not instantiated in the pipelined kernel");
 }
 
 bool conv_pipe_supports_ks(int ks) { return ks == 1 || ks == 2 || ks == 3 || ks == 5; }
 
-template <int KS>
-static int pipe_launch_ks(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
-    switch (tile) {
-#define X(T, WM, WN, WK, MT, NT, CC, K, NL) \
-    case T: return launch_pipe<WM, WN, WK, MT, NT, CC, 8, K, NL>(d, grid, lds, s, occ);
-        FC_PIPE_TILES(X, KS)
-#undef X
-        default: return fail(FC_E_ARG, "conv: bad tile id");
+// Once per process, before any launch or graph capture: the table, and the full 160 KiB of LDS for every row of it.
+int conv_pipe_init() {
+    static bool done = false;
+    if (done) return FC_OK;
+    build_rows();
+    std::sort(g_rows.begin(), g_rows.end(), [](const PipeRow& x, const PipeRow& y) { return x.key < y.key; });
+    g_keys.clear();
+    for (const PipeRow& r : g_rows) {
+        if (!g_keys.empty() && g_keys.back() == r.key)      // two rows with one match key: the second could never be selected
+            return fail(FC_E_STATE, "conv: two instantiations of the pipelined kernel share a match key");
+        g_keys.push_back(r.key);
+        FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(r.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
+    for (int b = 0, i = 0; b <= kBuckets; ++b) {            // the key's bits above 48 are its bucket
+        while (i < (int)g_keys.size() && (int)(g_keys[i] >> 49) < b) ++i;
+        g_begin[b] = i;
+    }
+    int dev = 0;
+    hipDeviceProp_t prop;
+    FC_HIP(hipGetDevice(&dev));
+    FC_HIP(hipGetDeviceProperties(&prop, dev));
+    g_pipe_cus = prop.multiProcessorCount;
+    FC_HIP(hipMalloc(reinterpret_cast<void**>(&g_zeros16), 256));
+    FC_HIP(hipMemset(g_zeros16, 0, 256));
+    done = true;
+    return FC_OK;
 }
 
-static int conv_pipe_dispatch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s, int* occ) {
-    if (d.bf3) return d.a.KS == 1 ? bf3_launch_ks<1>(d, tile, grid, lds, s, occ) : d.a.KS == 2 ? bf3_launch_ks<2>(d, tile, grid, lds, s, occ) : bf3_launch_ks<3>(d, tile, grid, lds, s, occ);
-    const bool lean = lean_kernels_on();
-    if (d.a.fin.step && !(lean && d.a.KS == 3)) return fail(FC_E_STATE, "conv: the step-closing flavour is a lean 3x3 kernel");
-    if (lean) {                  // the smallest flavour that covers this launch
-        const bool small_tile = tile == TILE_M32N32K4;
-        const int need = (d.a.fin.gamma ? FL_FIN : 0) | (d.a.res_out ? FL_RES : 0) | (d.a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |
-                         (d.a.s1.C ? FL_CAT : 0) | (d.stamps ? FL_STAMP : 0) | (d.a.stats_out ? FL_STATS : 0) | (d.a.fin.gn1_out ? FL_GN1 : 0) |
-                         ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | (d.o_out < 0 ? FL_NARROW : 0) |
-                         ((d.TB > 1 && !small_tile) ? FL_MULTI : 0) |
-                         ((d.a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
-        int r = -1;
-        if (d.a.KS == 3) {
-            // register-fed weights in the k-step-quad layout: whole 32-channel chunks, whole 32-column tiles, the centre tap at (1, 1)
-            const bool w4 = small_tile && d.a.w4 && d.a.Cin % 32 == 0 && d.a.Cout % 32 == 0 && d.a.pad == 1 && !d.a.w_batch_stride &&
-                            (!d.a.res_out || d.a.res_w4);
-            const size_t lds_ww = (w4 && (need & FL_FIN)) ? ww_lds(d, tile, lds) : 0;        // whole-window staging, where the launch may take it
-            if ((need & FL_FIN) && d.a.fin.step) r = fin_step_launch(d, tile, need, grid, lds, s, occ);   // ... that also closes the step: that flavour or an error
-            else if (need & FL_FIN) r = fin_geom_launch(d, tile, w4, need, grid, lds, lds_ww, s, occ);    // Block-closing: the flavour of exactly this geometry, if there is one
-            else if (need & FL_STATS) r = conv1_geom_launch(d, tile, w4, need, grid, lds, s, occ);   // Block-opening: likewise
-            if (lds_ww) {
-#define X(F) if (r == -1 && need == (F)) r = lean_launch_ww<(F)>(d, tile, grid, lds_ww, s, occ);
-                FC_LEAN_FLAVOURS_3(X)
-#undef X
-            }
-            if (w4) {
-#define X(F) if (r == -1 && need == (F)) r = lean_launch_db4<(F)>(d, tile, grid, lds, s, occ);
-                FC_LEAN_FLAVOURS_3(X)
-#undef X
-            }
-#define X(F) if (r == -1 && need == (F)) r = lean_launch<3, (F)>(d, tile, grid, lds, s, occ);
-            FC_LEAN_FLAVOURS_3(X)
-#undef X
-        } else if (d.a.KS == 1) {
-#define X(F) if (r == -1 && need == (F)) { r = lean_launch<1, (F)>(d, tile, grid, lds, s, occ); if (r == -1) r = lean_launch_wide1<(F)>(d, tile, grid, lds, s, occ); }
-            FC_LEAN_FLAVOURS_1(X)
-#undef X
-        } else if (d.a.KS == 2 && need == 0) {
-            r = lean_launch<2, 0>(d, tile, grid, lds, s, occ);
-        }
-        if (r != -1) return r;
-    }
-    switch (d.a.KS) {
-        case 1: return pipe_launch_ks<1>(d, tile, grid, lds, s, occ);
-        case 2: return pipe_launch_ks<2>(d, tile, grid, lds, s, occ);
-        case 3: return pipe_launch_ks<3>(d, tile, grid, lds, s, occ);
-        case 5: return pipe_launch_ks<5>(d, tile, grid, lds, s, occ);
-    }
-    return fail(FC_E_SHAPE, "conv: kernel size not instantiated in the pipelined kernel");
-}
+// Diagnostics (fc_debug_conv_routes, tools/flavour_sizes.py): the thirteen template arguments of the instantiation every launch went to, one line
+// per launch -- they are the instantiation's name in the code object's symbol table.
+static std::mutex g_route_mu;
+static bool g_route_on = false;
+static std::string g_route_log;
+void conv_route_log_set(bool on) { std::lock_guard<std::mutex> lk(g_route_mu); g_route_on = on; if (on) g_route_log.clear(); }
+std::string conv_route_log_get() { std::lock_guard<std::mutex> lk(g_route_mu); return g_route_log; }
 
-int conv_pipe_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s) { return conv_pipe_dispatch(d, tile, grid, lds, s, nullptr); }
+int conv_pipe_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s) {
+    PipePick k;
+    FC_TRY(conv_pipe_select(d, tile, lds, &k));
+    if (k.row->targ[A_FL] & FL_STEP) step_route_log_add("step_close");
+    if (g_route_on) {
+        std::lock_guard<std::mutex> lk(g_route_mu);
+        for (int i = 0; i < 13; ++i) g_route_log += std::to_string(k.row->targ[i]) + (i < 12 ? " " : "\n");
+    }
+    hipLaunchKernelGGL(k.row->fn, dim3(grid), dim3(k.row->nthr), k.lds, s, d);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
 
 // Workgroups of the instantiation this launch would go to that ONE CU holds at once (registers, waves and LDS as the runtime counts
-// them), cached per (tile, kernel size, flavour mask, LDS bytes, statistics geometry: a Block-closing launch's flavour depends on it).  0 = the query failed.
+// them; the fused tail's residency condition is derived from that, per instantiation -- conv_igemm.hip), cached per (tile, kernel size,
+// flavour mask, LDS bytes, statistics geometry: a Block-closing launch's flavour depends on it).  0 = the query failed.
 // A launch without a fused tail is asked for afresh: a conv1 launch's flavour also depends on what conv1_geo_key() tests (groups, window,
 // stride, source extent), which the cache key does not hold.
+static int pipe_query_blocks_per_cu(const ConvDev& d, int tile, size_t lds) {
+    PipePick k;
+    int occ = 0;
+    if (conv_pipe_select(d, tile, lds, &k) != FC_OK) return 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.row->fn, k.row->nthr, k.lds) == hipSuccess ? occ : 0;
+}
 int conv_pipe_blocks_per_cu(const ConvDev& d, int tile, size_t lds) {
-    if (!d.a.fin.gamma) {
-        int occ = 0;
-        return conv_pipe_dispatch(d, tile, 1, lds, nullptr, &occ) == FC_OK ? occ : 0;
-    }
+    if (!d.a.fin.gamma) return pipe_query_blocks_per_cu(d, tile, lds);
     static std::map<std::tuple<int, int, int, size_t, int, int>, int> cache;
     static std::mutex mu;
-    const int mask = (d.a.fin.gamma ? FL_FIN : 0) | (d.a.res_out ? FL_RES : 0) | (d.a.stats_post ? FL_POST : 0) | (d.any_xf ? FL_XF : 0) |
-                     (d.a.s1.C ? FL_CAT : 0) | (d.stamps ? FL_STAMP : 0) | (d.a.stats_out ? FL_STATS : 0) | (d.a.fin.gn1_out ? FL_GN1 : 0) |
-                     ((d.a.out_act || d.a.add) ? FL_POSTOP : 0) | (d.o_out < 0 ? FL_NARROW : 0) | (d.TB > 1 ? FL_MULTI : 0) |
-                     ((d.a.fin.gamma && !d.fin_local) ? FL_MEET : 0);
     // (whether a launch takes the whole-window form depends on its grid and Cin as well: part of the key)
     const int ww = (d.a.KS == 3 && d.a.w4 && ww_lds(d, tile, lds)) ? d.a.Cin : 0;
-    const auto key = std::make_tuple(tile, d.a.KS, mask | (d.a.w4 ? FL_W4 : 0) | (d.a.fin.step ? FL_STEP : 0), lds, d.cpg, d.TB * 4096 + (d.TWl << 8) + d.tiles_x * d.tiles_y * d.NPG + (ww << 13));
+    const auto key = std::make_tuple(tile, d.a.KS, pipe_need(d, tile) | (d.a.w4 ? FL_W4 : 0) | (d.a.fin.step ? FL_STEP : 0), lds, d.cpg,
+                                     d.TB * 4096 + (d.TWl << 8) + d.tiles_x * d.tiles_y * d.NPG + (ww << 13));
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
-    int occ = 0;
-    if (conv_pipe_dispatch(d, tile, 1, lds, nullptr, &occ) != FC_OK) occ = 0;
-    cache[key] = occ;
-    return occ;
+    return cache[key] = pipe_query_blocks_per_cu(d, tile, lds);
 }
 
 }  // namespace fc
