@@ -66,6 +66,7 @@ SIGNATURES = {
     "fc_debug_set_stamp_op": (_i, [_i, _vp]),
     "fc_debug_conv_routes": (_i, [_i]),
     "fc_debug_conv_routes_read": (_i, [C.c_char_p, _i]),
+    "fc_debug_conv_table_read": (_i, [C.c_char_p, _i]),
     "fc_debug_linattn_routes_read": (_i, [C.c_char_p, _i]),
     "fc_debug_step_routes_read": (_i, [C.c_char_p, _i]),
     "fc_debug_conv": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _pi, _pf, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _pf, _vp]),

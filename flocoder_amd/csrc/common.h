@@ -163,6 +163,7 @@ unsigned long long* conv_stamp_buffer();
 void conv_set_stamp_buffer(unsigned long long* p);  // diagnostics: phase stamps of the pipelined kernel
 void conv_route_log_set(bool on);                   // diagnostics: the instantiation each pipelined launch goes to (conv_pipe.hip)
 std::string conv_route_log_get();
+std::string conv_table_list();                      // diagnostics: every instantiation of the pipelined kernel, in the record's format; no device needed
 int conv_plan(const ConvArgs& a, int tile, ConvGeom* g);
 int conv_launch(const ConvArgs& a, int tile, hipStream_t s);
 

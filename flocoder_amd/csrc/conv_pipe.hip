@@ -828,6 +828,7 @@ enum { A_NPL = 6, A_FL = 9 };       // positions in PipeRow::targ (WM WN WK MT N
 // (tile, kernel size), the key's leading bits: the rows of bucket b are g_begin[b] .. g_begin[b + 1], and g_keys holds their keys
 // side by side, so that a search reads a few consecutive cache lines.  (Before conv_pipe_init() every bucket is empty.)
 static std::vector<PipeRow> g_rows;
+static std::vector<PipeRow>* g_fill = &g_rows;    // where build_rows() puts its rows: the table, or the listing of conv_table_list()
 static std::vector<unsigned long long> g_keys;
 constexpr int kBuckets = TILE_COUNT * 16;
 static int g_begin[kBuckets + 1];
@@ -845,7 +846,7 @@ static void add_row() {
     if constexpr (PREC == 0 || conv_bf3_form(TILE, KS)) {
         constexpr ConvTileDef t = kConvTiles[TILE];
         constexpr int NPL = FL == FL_ALL ? kPipeNPL : kLeanNPL, NL = conv_tile_nl(TILE, KS);
-        g_rows.push_back({TILE, {t.WM, t.WN, t.WK, t.MT, t.NT, t.CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1},
+        g_fill->push_back({TILE, {t.WM, t.WN, t.WK, t.MT, t.NT, t.CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1},
                           &conv_pipe_kernel<t.WM, t.WN, t.WK, t.MT, t.NT, t.CC, NPL, KS, NL, FL, PREC, GEOF, GEOK1>, 256 + 64 * NL,
                           pipe_key(TILE, KS, FL, PREC, GEOF, GEOK1)});
     }
@@ -925,8 +926,10 @@ constexpr int kConv1Up = FL_STATS | FL_CAT | FL_RES;
     X(TILE_M32N32K4, FL_W4, FL_STATS, geo_key(GEO_PAIR, 2, 4, 64, 2))  /* mid_block1, mid_block2 */ \
     X(TILE_M32N32K4, FL_W4, kConv1Up, geo_key(GEO_PAIR, 2, 4, 64, 2))  /* ups.0.* */
 
-static void build_rows() {
-    g_rows.clear();
+static std::mutex g_build_mu;     // build_rows() fills through g_fill: one caller at a time
+static void build_rows(std::vector<PipeRow>& rows) {
+    rows.clear();
+    g_fill = &rows;
 #define X(T, W4, MEET, GEO) add_fin_geom<T, W4, MEET, GEO>();
     FC_FIN_GEOMS(X)
 #undef X
@@ -945,6 +948,7 @@ static void build_rows() {
     FC_LEAN_FLAVOURS_1(X)
 #undef X
     add_tiles<2, 0>(LeanTiles{});
+    g_fill = &g_rows;
 }
 
 static const PipeRow* find_row(int tile, int ks, int fl, int prec = 0, int geof = 0, int geok1 = 0) {
@@ -1088,7 +1092,8 @@ bool conv_pipe_supports_ks(int ks) { return ks == 1 || ks == 2 || ks == 3 || ks 
 int conv_pipe_init() {
     static bool done = false;
     if (done) return FC_OK;
-    build_rows();
+    std::lock_guard<std::mutex> lk(g_build_mu);
+    build_rows(g_rows);
     std::sort(g_rows.begin(), g_rows.end(), [](const PipeRow& x, const PipeRow& y) { return x.key < y.key; });
     g_keys.clear();
     for (const PipeRow& r : g_rows) {
@@ -1119,6 +1124,21 @@ static bool g_route_on = false;
 static std::string g_route_log;
 void conv_route_log_set(bool on) { std::lock_guard<std::mutex> lk(g_route_mu); g_route_on = on; if (on) g_route_log.clear(); }
 std::string conv_route_log_get() { std::lock_guard<std::mutex> lk(g_route_mu); return g_route_log; }
+
+// Diagnostics (fc_debug_conv_table_read): every row of the table in the route record's format, one line of the thirteen template arguments per
+// instantiation, in the order build_rows() names them.  Host code only -- build_rows() takes the addresses of the kernels' host stubs and
+// nothing else -- so the listing needs neither conv_pipe_init() nor a device; it is built into a vector of its own, never into the table.
+std::string conv_table_list() {
+    std::vector<PipeRow> rows;
+    {
+        std::lock_guard<std::mutex> lk(g_build_mu);
+        build_rows(rows);
+    }
+    std::string out;
+    for (const PipeRow& r : rows)
+        for (int i = 0; i < 13; ++i) out += std::to_string(r.targ[i]) + (i < 12 ? " " : "\n");
+    return out;
+}
 
 int conv_pipe_launch(const ConvDev& d, int tile, int grid, size_t lds, hipStream_t s) {
     PipePick k;

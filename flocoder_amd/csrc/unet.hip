@@ -1144,6 +1144,14 @@ int fc_debug_conv_routes_read(char* buf, int cap) {
     return (int)r.size();
 }
 
+// Diagnostics: the table of conv_pipe_kernel instantiations (conv_pipe.hip build_rows), one line of the thirteen template arguments per row.
+// Host code only: works before conv_init() and without a device.
+int fc_debug_conv_table_read(char* buf, int cap) {
+    const std::string r = conv_table_list();
+    if (buf && cap > 0) { const size_t n = r.size() < (size_t)cap - 1 ? r.size() : (size_t)cap - 1; memcpy(buf, r.data(), n); buf[n] = 0; }
+    return (int)r.size();
+}
+
 int fc_debug_linattn_routes_read(char* buf, int cap) {
     const std::string r = linattn_route_log_get();
     if (buf && cap > 0) { const size_t n = r.size() < (size_t)cap - 1 ? r.size() : (size_t)cap - 1; memcpy(buf, r.data(), n); buf[n] = 0; }
@@ -1188,7 +1196,7 @@ int fc_debug_conv(const float* src0, int c0, const float* src1, int c1, const fl
         a.w4 = wp8;
     }
     float* wp3 = nullptr;       // ... and the split-bf16 copy when that arithmetic is asked for, as a codec plan would (pack kind 8)
-    if (r == FC_OK && a.prec == 1 && (ksize == 3 || ksize == 1)) {
+    if (r == FC_OK && a.prec == 1 && ksize >= 1 && ksize <= 3) {        // (the kernel sizes of conv_bf3_form)
         const int ipad = (a.Cin + 15) / 16 * 16;
         FC_HIP(hipMalloc(reinterpret_cast<void**>(&wp3), (size_t)cout * ipad * ksize * ksize * sizeof(float)));
         r = pack_conv_b3_launch(w_oihw, wp3, cout, a.Cin, ksize * ksize, ipad, s);

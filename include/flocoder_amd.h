@@ -426,6 +426,9 @@ int fc_debug_set_conv_stamps(void* buf_dev);
  * returns its full length. */
 int fc_debug_conv_routes(int on);
 int fc_debug_conv_routes_read(char* buf, int cap);
+/* Diagnostics: the table of pipelined-conv instantiations itself, one line per row in the format of fc_debug_conv_routes_read (the thirteen
+ * template arguments), copied and counted like that record.  Host code only: it needs no device and no earlier call. */
+int fc_debug_conv_table_read(char* buf, int cap);
 /* Diagnostics: while the record of fc_debug_conv_routes is on, every launch of the fused linear attention's fast path (n >= 256) adds one
  * line "C n NB TT" to a record of its own: NB = n / 32 and TT = n / 128 when it launched the kernel pair compiled for exactly this shape, 0 0
  * when it launched the pair that reads the shape at run time.  Copies it like fc_debug_conv_routes_read and returns its full length. */
