@@ -161,6 +161,12 @@ SIGNATURES = {
     "fc_vqvae_profile_ops": (_i, [_vp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float), _i, _vp]),
     "fc_vae_profile_ops": (_i, [_vp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float), _i, _vp]),
     "fc_rvq_quantize": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fc_rvq_train_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "fc_codebook_draws": (_i, [_vp, C.c_uint64, _i, _i64, _i64, _i64, _vp]),
+    "fc_rvq_seed_codes": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint64, _i64, _vp]),
+    "fc_rvq_kmeans": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fc_rvq_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, _f, C.c_uint64, _i64, _vp,
+                               C.c_size_t, _vp]),
     "fc_mask_encoder_create": (_i, [_i, C.POINTER(_vp)]),
     "fc_mask_encoder_destroy": (None, [_vp]),
     "fc_mask_encoder_param_count": (_i, [_vp]),

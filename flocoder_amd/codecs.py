@@ -262,15 +262,30 @@ class _VQLayer(nn.Module):
 
 
 class ResidualVQ(nn.Module):
-    """Inference form of ``vector_quantize_pytorch.ResidualVQ`` as VQVAE builds it (codecs.py:456-467), holding the buffers under the
-    package's state_dict names (``layers.{i}._codebook.{initted,cluster_size,embed_avg,embed}``) so trained checkpoints load.
-    THIRD-PARTY ALGORITHM, PARITY UNPINNED (the package is absent offline): per level the nearest codeword of the running
-    residual, output = their sum; k-means initialisation, EMA updates and the training losses are not built -- calling it with
-    codebooks that were never initialised (``initted`` false) or in training mode raises."""
+    """``vector_quantize_pytorch.ResidualVQ`` as VQVAE builds it (codecs.py:456-467), holding the buffers under the package's state_dict
+    names (``layers.{i}._codebook.{initted,cluster_size,embed_avg,embed}``) so trained checkpoints load.  THIRD-PARTY ALGORITHM, PARITY
+    UNPINNED (the package is absent offline): per level the nearest codeword of the running residual, output = their sum.
 
-    def __init__(self, dim, codebook_size, num_quantizers, **unused):
+    Eval mode is the inference form (``fc_rvq_quantize``): codebooks that were never initialised (``initted`` false) raise, the losses
+    are zero.  Training mode FITS the codebooks on the device, without gradients (``fc_rvq_train_step``; the definition is
+    ``flocoder_amd/noise.py``, "codebook fitting"): a level whose ``initted`` is false is first initialised from the batch -- ``codebook_size``
+    drawn residual vectors, then ``kmeans_iters`` Lloyd iterations (none with ``kmeans_init=False``) --, then every level assigns against
+    its current codebook and updates ``cluster_size`` / ``embed_avg`` / ``embed`` by the EMA rule with ``decay`` and replaces codes whose
+    cluster size fell below ``threshold_ema_dead_code``.  A training call returns ``(quantized, indices, losses [1, levels])`` from the
+    PRE-update codebooks, the losses ``commitment_weight`` * mean squared distance per level.  THE OUTPUTS CARRY NO GRADIENT: neither the
+    straight-through / rotation-trick path to the encoder nor the orthogonality term (which acts only through the gradients of a
+    learnable codebook; EMA codebooks have none) is built.  ``seed`` and ``draw_index`` (advanced once per training call) select the
+    counter-based draws; they are plain attributes, not buffers: a caller that wants a resumed run to replay the draws carries them.
+    ``last_expired`` holds the last training call's expired codes per level (int32, on the device)."""
+
+    def __init__(self, dim, codebook_size, num_quantizers, decay=0.95, commitment_weight=0.25, kmeans_init=True, kmeans_iters=15,
+                 threshold_ema_dead_code=2, seed=0, **unused):
         super().__init__()
         self.dim, self.codebook_size, self.num_quantizers = dim, codebook_size, num_quantizers
+        self.decay, self.commitment_weight = float(decay), float(commitment_weight)
+        self.kmeans_init, self.kmeans_iters = bool(kmeans_init), int(kmeans_iters)
+        self.threshold_ema_dead_code = float(threshold_ema_dead_code)
+        self.seed, self.draw_index, self.last_expired = int(seed), 0, None
         self.layers = nn.ModuleList([_VQLayer(codebook_size, dim) for _ in range(num_quantizers)])
 
     @property
@@ -278,14 +293,56 @@ class ResidualVQ(nn.Module):
         return torch.stack([l._codebook.embed[0] for l in self.layers])
 
     def _check(self, t):
-        if self.training:
-            raise NotImplementedError("ResidualVQ: only the inference form is built (codec training is out of scope)")
         if not all(bool(l._codebook.initted) for l in self.layers):
             raise NotImplementedError("ResidualVQ: codebooks are uninitialised (k-means init is not built); load a trained checkpoint")
+        self._need_gpu(t)
+
+    @staticmethod
+    def _need_gpu(t):
         if not t.is_cuda:
             raise RuntimeError("flocoder_amd.ResidualVQ runs on MI355X (gfx950) only; there is no CPU path")
 
+    @torch.no_grad()
+    def _fit_nchw(self, z):
+        """One training call on z [B, dim, h, w]: initialise what is not, then the step.  One host read (``initted``), no other wait."""
+        self._need_gpu(z)
+        bsz, d, h, w = z.shape
+        z = z.detach().contiguous().float()
+        lib, dev, nl, k = B.lib(), z.device, self.num_quantizers, self.codebook_size
+        nbytes = lib.fc_rvq_train_workspace_bytes(bsz, h * w, d, k, nl)
+        if not nbytes:
+            raise ValueError(f"flocoder_amd: {lib.fc_last_error().decode(errors='replace')}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        books = [l._codebook for l in self.layers]
+        cb = torch.stack([c.embed[0] for c in books]).to(dev).contiguous()
+        cs = torch.stack([c.cluster_size[0] for c in books]).to(dev).contiguous()
+        ea = torch.stack([c.embed_avg[0] for c in books]).to(dev).contiguous()
+        initted = torch.stack([c.initted for c in books]).tolist()
+        shape, stream, draw = (bsz, d, h * w, k, nl), B.current_stream(dev), self.draw_index & 0xffffffff
+        for lvl, done in enumerate(initted):               # in sequence: level l's residuals need the finished level l - 1
+            if done:
+                continue
+            B.check(lib.fc_rvq_seed_codes(B.ptr(z), B.ptr(cb), *shape, lvl, self.seed, draw, stream))
+            B.check(lib.fc_rvq_kmeans(B.ptr(z), B.ptr(cb), *shape, lvl, self.kmeans_iters if self.kmeans_init else 0, B.ptr(cs[lvl]),
+                                      B.ptr(ea[lvl]), None, B.ptr(ws), nbytes, stream))
+        zq = torch.empty_like(z)
+        idx = torch.empty(bsz * h * w, nl, dtype=torch.int64, device=dev)
+        losses = torch.empty(nl, dtype=torch.float32, device=dev)
+        expired = torch.empty(nl, dtype=torch.int32, device=dev)
+        B.check(lib.fc_rvq_train_step(B.ptr(z), B.ptr(cb), B.ptr(cs), B.ptr(ea), B.ptr(zq), B.ptr(idx), B.ptr(losses), B.ptr(expired), *shape,
+                                      self.decay, self.commitment_weight, self.threshold_ema_dead_code, self.seed, draw, B.ptr(ws), nbytes, stream))
+        for lvl, c in enumerate(books):
+            c.embed[0].copy_(cb[lvl])
+            c.cluster_size[0].copy_(cs[lvl])
+            c.embed_avg[0].copy_(ea[lvl])
+            c.initted.fill_(True)
+        self.draw_index += 1
+        self.last_expired = expired
+        return zq, idx, losses.view(1, nl)
+
     def quantize_nchw(self, z):
+        if self.training:
+            return self._fit_nchw(z)
         self._check(z)
         bsz, d, h, w = z.shape
         z = z.contiguous().float()
@@ -308,8 +365,9 @@ class VQVAE(_NativeCodec):
 
     Parameters carry the reference's state_dict names (``encoder.0.conv1.weight`` ... ``decoder.layers.0.q_proj.weight`` ...), so
     ``load_state_dict(ckpt['model_state_dict'], strict=False)`` takes a reference checkpoint as is.  ``quantize`` / ``forward`` run the
-    inference form of ResidualVQ (third party, parity unpinned -- see ``ResidualVQ`` above); ``decode`` with a non-zero
-    ``noise_strength`` (training-time NoiseInjection) raises NotImplementedError."""
+    inference form of ResidualVQ (third party, parity unpinned -- see ``ResidualVQ`` above); ``fit_codebooks`` fits the codebooks to the
+    encoder's latents without gradients; ``forward`` in training mode (codec training through the encoder) and ``decode`` with a non-zero
+    ``noise_strength`` (training-time NoiseInjection) raise NotImplementedError."""
 
     _fc, _create = "fc_vqvae", "create_ex"
 
@@ -359,7 +417,8 @@ class VQVAE(_NativeCodec):
             cur, i = co, i + 7
         self.decoder.layers.add_module(str(i), _NoiseInjectionParams(cur))
         self.decoder.layers.add_module(str(i + 3), _NoiseInjectionParams(64))
-        self.vq = ResidualVQ(dim=vq_embedding_dim, codebook_size=vq_num_embeddings, num_quantizers=codebook_levels)
+        self.vq = ResidualVQ(dim=vq_embedding_dim, codebook_size=vq_num_embeddings, num_quantizers=codebook_levels, decay=0.95,
+                             commitment_weight=commitment_weight, kmeans_init=True, kmeans_iters=15, threshold_ema_dead_code=2)
         self.register_buffer('codebook_usage', torch.zeros(codebook_levels, vq_num_embeddings))
         self.usage_count = 0
 
@@ -392,6 +451,32 @@ class VQVAE(_NativeCodec):
         """codecs.py:504-521: z [B,C,h,w] -> (z_q [B,C,h,w], commit_loss); the indices of the last call stay in ``self.indices``."""
         z_q, self.indices, commit_loss = self.vq.quantize_nchw(z)
         return z_q, commit_loss
+
+    @torch.no_grad()
+    def fit_codebooks(self, batches, epochs=1, reset=False):
+        """Fit the quantiser's codebooks to this encoder's latents: per batch (a tensor, or a tuple whose first entry is one) a
+        ``no_grad`` encode and then the quantiser's training call (``ResidualVQ`` above: k-means initialisation of levels that are not
+        initialised, EMA update, dead-code expiry); nothing else of the model changes.  ``reset=True`` clears ``initted`` first, so a loaded
+        checkpoint's codebooks are refitted from scratch.  ``batches`` is walked ``epochs`` times (pass a list or a loader, not a
+        generator, for more than one).  Returns (losses [calls, levels], expired codes [calls, levels]) as device tensors and leaves the
+        model in eval mode.  Each data-parallel rank fits its own shard: the statistics are not reduced across ranks."""
+        if reset:
+            for layer in self.vq.layers:
+                layer._codebook.initted.fill_(False)
+        losses, expired = [], []
+        self.eval()
+        self.vq.train()
+        try:
+            for _ in range(int(epochs)):
+                for x in batches:
+                    z = self.encode(x[0] if isinstance(x, (tuple, list)) else x)
+                    losses.append(self.vq.quantize_nchw(z)[2][0])
+                    expired.append(self.vq.last_expired)
+        finally:
+            self.eval()
+        if not losses:
+            raise ValueError("VQVAE.fit_codebooks: no batches")
+        return torch.stack(losses), torch.stack(expired)
 
     @torch.no_grad()
     def calc_distance_stats(self, z, z_q):

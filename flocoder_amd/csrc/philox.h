@@ -6,6 +6,8 @@
 //   masks.hip   the inpainting masks            counter (j, region, sample id lo, sample id hi), key = seed + FC_MASK_KEY_OFFSET (mod 2^64);
 //               region 0 the type and the stroke / rectangle counts, 1 the 'noise' pixels, 2 the rectangles, 3 + s brush stroke s
 //               (j = 0, 1 its start, j = 2 + t its step t): the list is at the head of masks.hip
+//   rvq_train.hip   the codebook draws          counter (0 | 1, draw index, level, N), key = seed + FC_CODEBOOK_KEY_OFFSET (mod 2^64): the
+//               four multipliers / addends of the bijection that is cycle-walked into [0, N) (codebook_draw)
 // The augmentation draws (key = seed + FC_AUG_KEY_OFFSET, counter (j, region, sample id)) are made on the host alone (noise.py): augment.hip
 // reads their integer table and includes nothing of this file.
 #pragma once

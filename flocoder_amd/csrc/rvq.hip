@@ -6,10 +6,9 @@
 // One thread per latent vector, reading / writing the NCHW boundary tensors directly (the reference permutes to [N, D] and back,
 // codecs.py:506-520); all levels' codebooks sit in LDS.   grid (ceil(N/256)), LDS L*K*D floats
 #include "common.h"
+#include "rvq_dev.h"
 
 namespace fc {
-
-constexpr int RVQ_MAXD = 16;
 
 __global__ void __launch_bounds__(256) rvq_kernel(const float* z, const float* cb, float* zq, int64_t* idx, int B, int D, int HW, int K, int L) {
     extern __shared__ __attribute__((aligned(16))) float cs[];   // [L][K][D]
@@ -24,15 +23,7 @@ __global__ void __launch_bounds__(256) rvq_kernel(const float* z, const float* c
     for (int d = 0; d < RVQ_MAXD; ++d) { r[d] = d < D ? zp[(size_t)d * HW] : 0.f; q[d] = 0.f; }
     for (int l = 0; l < L; ++l) {
         const float* cl = cs + (size_t)l * K * D;
-        float best = INFINITY;
-        int bi = 0;
-        for (int k = 0; k < K; ++k) {
-            float dist = 0.f;
-#pragma unroll
-            for (int d = 0; d < RVQ_MAXD; ++d)
-                if (d < D) { const float t = r[d] - cl[k * D + d]; dist += t * t; }
-            if (dist < best) { best = dist; bi = k; }
-        }
+        const int bi = rvq_nearest(r, cl, K, D);
 #pragma unroll
         for (int d = 0; d < RVQ_MAXD; ++d)
             if (d < D) { const float e = cl[bi * D + d]; r[d] -= e; q[d] += e; }

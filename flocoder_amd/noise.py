@@ -615,3 +615,112 @@ def augment_midi_field(seed: int, sample_ids, sources, src_index, image_size, ra
             v = (v >= np.float32(binary_thresh)).astype(np.float32)
         out[b] = v
     return out
+
+
+# ---- codebook fitting (csrc/rvq_train.hip: fc_codebook_draws, fc_rvq_seed_codes, fc_rvq_kmeans, fc_rvq_train_step) ------------------------
+# How the residual quantiser's codebooks learn without gradients (the EMA / k-means / dead-code configuration the reference builds its
+# ResidualVQ with, flocoder/codecs.py:456-467; third-party algorithm, parity unpinned, stated here).  Per level l, with r the residuals
+# entering the level ([N, D] fp32; r_0 = z, r_{l+1} = r_l - E_l[i_l] formed in fp32) and E [K, D] its codebook:
+#   assign      i_n = argmin_k |r_n - E_k|^2, first index on ties; counts n_k, sums S_k = sum_{i_n = k} r_n, commitment sum_n |r_n - E_{i_n}|^2
+#   k-means     means <- r_{pi(0 .. K-1)}; ``iters`` times: assign, mean_k <- S_k / n_k (an empty cluster keeps its mean); then
+#               E = means, cluster_size = the last counts, embed_avg = E * cluster_size              (codebook_lloyd)
+#   EMA step    cs <- cs + (1 - decay)(n - cs); A <- A + (1 - decay)(S - A); E_k <- A_k / ((cs_k + 1e-5) / (sum cs + K 1e-5) * sum cs),
+#               evaluated in fp64 and rounded once to the buffers' fp32, sum cs in index order        (codebook_ema)
+#   expiry      threshold > 0: the j-th code in index order with cs_k < threshold takes r_{pi(j)}; its cs_k = threshold and
+#               A_k = E_k * threshold                                                                (codebook_expire)
+#   loss        commitment_weight * commitment sum / (N D)
+# pi is the permutation of [0, N) of (seed, level, draw_index)                                        (codebook_draws)
+CODEBOOK_KEY_OFFSET = 0x43424F4F4B464954       # "CBOOKFIT"
+CODEBOOK_MAX_N = 1 << 24
+CODEBOOK_EPS = 1e-5
+
+
+def codebook_draws(seed: int, level: int, draw_index: int, n: int, count=None) -> np.ndarray:
+    """int64 ``[count]`` (default ``n``): slot j holds ``pi(j mod n)``, the bits of ``fc_codebook_draws``.  Two Philox4x32-10 blocks under
+    key ``seed + CODEBOOK_KEY_OFFSET`` (mod 2^64) with counters ``(0, draw_index, level, n)`` and ``(1, draw_index, level, n)`` give the
+    multipliers ``m_0..3`` and addends ``a_0..3`` of a bijection of the b-bit words (b >= 1 the smallest with 2^b >= n): four rounds of
+    ``x <- (x (m_r | 1) + a_r) mod 2^b; x <- x xor (x >> ceil(b / 2))``.  A slot applies it until the value falls below n (cycle walking:
+    expected under two applications), so slots 0 .. n-1 are a permutation of ``range(n)``: the draws are distinct, with no sort."""
+    n = int(n)
+    if not 1 <= n <= CODEBOOK_MAX_N:
+        raise ValueError(f"n={n}: 1 .. 2^24 vectors")
+    if not 0 <= int(draw_index) <= 0xffffffff:
+        raise ValueError("draw_index is a 32-bit counter word")
+    count = n if count is None else int(count)
+    key = (int(seed) + CODEBOOK_KEY_OFFSET) & 0xffffffffffffffff
+    ctr = np.array([[0, int(draw_index), int(level), n], [1, int(draw_index), int(level), n]], dtype=np.uint64)
+    w = philox4x32(ctr, np.array([key & 0xffffffff, key >> 32], dtype=np.uint64)).astype(np.uint64)
+    b = max(1, (n - 1).bit_length())
+    mask, sh = np.uint64((1 << b) - 1), np.uint64((b + 1) // 2)
+    x = np.arange(count, dtype=np.uint64) % np.uint64(n)
+    todo = np.ones(count, dtype=bool)
+    while todo.any():
+        v = x[todo]
+        for r in range(4):
+            v = (v * (w[0, r] | np.uint64(1)) + w[1, r]) & mask
+            v ^= v >> sh
+        x[todo] = v
+        todo[todo] = v >= np.uint64(n)
+    return x.astype(np.int64)
+
+
+def codebook_assign(r, means):
+    """fp64: (index of the nearest mean, first on ties; squared distance to it; squared distance to the nearest other VALUE) per row."""
+    r, means = np.asarray(r, dtype=np.float64), np.asarray(means, dtype=np.float64)
+    d = np.zeros((len(r), len(means)))
+    for c in range(r.shape[1]):                                       # one [N, K] plane at a time: no [N, K, D] temporary
+        d += (r[:, c, None] - means[None, :, c]) ** 2
+    i = d.argmin(axis=1)
+    best = d[np.arange(len(r)), i]
+    nxt = np.where(d <= best[:, None], np.inf, d).min(axis=1)
+    return i, best, nxt
+
+
+def codebook_sums(r, idx, k: int):
+    """(counts int64 [K], sums fp64 [K, D]) of the rows of r by their index."""
+    r = np.asarray(r, dtype=np.float64)
+    counts = np.bincount(idx, minlength=k).astype(np.int64)
+    sums = np.zeros((k, r.shape[1]), dtype=np.float64)
+    np.add.at(sums, idx, r)
+    return counts, sums
+
+
+def codebook_lloyd(data, init, iters: int):
+    """``iters`` Lloyd iterations in fp64 from the means ``init``: (means, the last iteration's counts, the objective of every iteration =
+    the sum of squared distances to the means the rows were assigned to, before the update).  An empty cluster keeps its mean."""
+    data, means = np.asarray(data, dtype=np.float64), np.array(init, dtype=np.float64)
+    counts, obj = np.zeros(len(means), dtype=np.int64), []
+    for _ in range(int(iters)):
+        i, best, _ = codebook_assign(data, means)
+        counts, sums = codebook_sums(data, i, len(means))
+        obj.append(best.sum())
+        full = counts > 0
+        means[full] = sums[full] / counts[full, None]
+    return means, counts, np.array(obj)
+
+
+def codebook_ema(cs, avg, counts, sums, decay: float, dtype=np.float32):
+    """The EMA step of one level: (cluster_size, embed_avg, embed).  Evaluated in fp64; ``dtype`` = fp32 rounds where the device stores
+    (cluster_size and embed_avg once each, and the codebook from the ROUNDED buffers), fp64 is the published lines as they stand."""
+    om = 1.0 - float(decay)
+    cs, avg = np.asarray(cs, dtype=np.float64), np.asarray(avg, dtype=np.float64)
+    cs = (cs + om * (np.asarray(counts, dtype=np.float64) - cs)).astype(dtype)
+    avg = (avg + om * (np.asarray(sums, dtype=np.float64) - avg)).astype(dtype)
+    c64 = cs.astype(np.float64)
+    tot = float(np.cumsum(c64)[-1])                                   # in index order
+    smoothed = (c64 + CODEBOOK_EPS) / (tot + len(c64) * CODEBOOK_EPS) * tot
+    return cs, avg, (avg.astype(np.float64) / smoothed[:, None]).astype(dtype)
+
+
+def codebook_expire(cs, avg, embed, residuals, threshold: float, seed: int, level: int, draw_index: int):
+    """Dead-code expiry on fp32 buffers (copies returned, with the indices of the replaced codes): code k with ``cs_k < threshold`` is
+    dead; the j-th dead code in index order takes row ``pi(j)`` of ``residuals`` (this level's fp32 input)."""
+    cs, avg, embed = (np.array(a, dtype=np.float32) for a in (cs, avg, embed))
+    thr = np.float32(threshold)
+    dead = np.flatnonzero(cs < thr) if thr > 0 else np.zeros(0, dtype=np.int64)
+    if dead.size:
+        pick = codebook_draws(seed, level, draw_index, len(residuals), dead.size)
+        embed[dead] = np.asarray(residuals, dtype=np.float32)[pick]
+        cs[dead] = thr
+        avg[dead] = embed[dead] * thr
+    return cs, avg, embed, dead

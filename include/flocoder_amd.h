@@ -17,6 +17,7 @@
 #ifndef FLOCODER_AMD_H
 #define FLOCODER_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -658,6 +659,41 @@ int fc_vqvae_profile_ops(fc_vqvae* v, int decode, const float* in_dev, float* ou
  * int64 or NULL. */
 int fc_rvq_quantize(const float* z_dev, const float* codebooks_dev, float* zq_out_dev, int64_t* indices_out_dev, int batch, int dim, int hw,
                     int codebook_size, int levels, void* stream);
+
+/* Fitting the quantiser's codebooks on the device without gradients (the EMA / k-means / dead-code form of
+ * vector_quantize_pytorch's codebook as the reference configures it, codecs.py:456-467; third party, parity unpinned; the definition is
+ * DESIGN.md section 4 "Codebook fitting", its host form flocoder_amd/noise.py codebook_*).  Tensors as fc_rvq_quantize: z_dev [B,dim,hw],
+ * codebooks_dev [levels][codebook_size][dim], indices [B*hw][levels] int64; cluster_size_dev [levels][codebook_size] and embed_avg_dev
+ * [levels][codebook_size][dim] fp32.  Supported: dim <= 16, codebooks <= 64 KB, B*hw <= 2^24; anything else FC_E_SHAPE.  Every call
+ * assigns with the search of fc_rvq_quantize, accumulates counts as integers and sums as 64-bit fixed point (integer atomics: the same
+ * bits run to run; error bound at the head of csrc/rvq_train.hip), enqueues on `stream`, allocates nothing and reads nothing back;
+ * ws_dev is caller-owned scratch of fc_rvq_train_workspace_bytes(...) bytes (0 for an unsupported shape), 64-byte aligned.
+ *
+ * fc_codebook_draws: out_dev [count] int64, slot j = pi(j mod n), pi the permutation of [0, n) of (seed, level, draw_index): Philox4x32-10
+ * under key seed + FC_CODEBOOK_KEY_OFFSET (mod 2^64), counter (0 | 1, draw_index, level, n), keys a bijection of [0, 2^b) (four rounds of
+ * an odd multiply-add and a xor-shift) that is cycle-walked into [0, n).
+ * fc_rvq_seed_codes: code slot j of `level` <- the residual entering that level of vector pi(j), j = 0 .. codebook_size-1 (levels below
+ * it are read, nothing else is written).
+ * fc_rvq_kmeans: `iters` Lloyd iterations of `level` on the residuals entering it, means in place in the codebook; an empty cluster keeps
+ * its mean.  cluster_size_out_dev [codebook_size] / embed_avg_out_dev [codebook_size][dim] (both or neither): the last iteration's counts
+ * and mean * count (zeros for iters = 0).  objective_out_dev NULL or [iters] fp64: iteration i's sum of squared distances of the
+ * residuals to the means they were assigned to (before that iteration's update).  1 + 2 iters launches, iters memsets.
+ * fc_rvq_train_step: all levels assign against the codebooks as passed (zq_out_dev / indices_out_dev are fc_rvq_quantize's of them, bit
+ * for bit), then in place cluster_size <- cs + (1-decay)(n - cs), embed_avg likewise with the sums, codebook <- embed_avg / Laplace-smoothed
+ * cluster size, and with threshold_ema_dead_code > 0 the j-th code in index order below it <- residual of vector pi(j), its cluster
+ * size the threshold, its embed_avg codeword * threshold.  losses_out_dev [levels] fp32: commitment_weight * mean squared distance;
+ * expired_out_dev [levels] int32.  Three launches and one memset. */
+#define FC_CODEBOOK_KEY_OFFSET 0x43424F4F4B464954ULL /* "CBOOKFIT" */
+size_t fc_rvq_train_workspace_bytes(int batch, int hw, int dim, int codebook_size, int levels);
+int fc_codebook_draws(int64_t* out_dev, uint64_t seed, int level, int64_t draw_index, int64_t n, int64_t count, void* stream);
+int fc_rvq_seed_codes(const float* z_dev, float* codebooks_dev, int batch, int dim, int hw, int codebook_size, int levels, int level, uint64_t seed,
+                      int64_t draw_index, void* stream);
+int fc_rvq_kmeans(const float* z_dev, float* codebooks_dev, int batch, int dim, int hw, int codebook_size, int levels, int level, int iters,
+                  float* cluster_size_out_dev, float* embed_avg_out_dev, double* objective_out_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int fc_rvq_train_step(const float* z_dev, float* codebooks_dev, float* cluster_size_dev, float* embed_avg_dev, float* zq_out_dev,
+                      int64_t* indices_out_dev, float* losses_out_dev, int* expired_out_dev, int batch, int dim, int hw, int codebook_size,
+                      int levels, double decay, double commitment_weight, float threshold_ema_dead_code, uint64_t seed, int64_t draw_index,
+                      void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Inpainting conditioning  (replaces flocoder/inpainting.py:161-253 MaskEncoder / mask_blending)
