@@ -50,7 +50,8 @@ struct MidRec { Act x, qkv, ao, out; Stat gn1; };
 struct ConvRec { std::string name; Act x, out; int KS = 1, pad = 0, stride = 1, ups = 0; };
 struct InjRec { std::string name; Act x, mr, z, out; };                      // x + SiLU(conv3x3(cat[x, bilinear(mask)])), unet.py:336-340
 struct FuseRec { bool present = false; Act xi, mask, z1, f1, z2, f2, x0; };  // mask_fusion_conv, unet.py:298-305
-struct TapeItem { int kind, idx; };   // 0 ResRec, 1 LinRec, 2 MidRec, 3 ConvRec, 4 InjRec -- in forward order
+enum TapeKind { TAPE_RES, TAPE_LIN, TAPE_MID, TAPE_CONV, TAPE_INJ };          // which of Plan's record vectors `idx` points into
+struct TapeItem { TapeKind kind; int idx; };   // in forward order
 
 struct Plan {                 // one launch plan + activation arena for up to maxB rows
     int maxB = 0, H = 0, W = 0;
@@ -261,6 +262,15 @@ struct PlanBuilder {
         if (dev_alloc(&p, (floats ? floats : 1) * sizeof(float), scope.c_str()) != FC_OK) { err = fail(FC_E_HIP, "hipMalloc failed while reserving the arena"); return nullptr; }
         pl->allocs.push_back(p);
         return static_cast<float*>(p);
+    }
+    // a host table copied into a buffer of the arena (before returning: the vector may die); null with `err` set on failure
+    template <class T> T* upload(const std::vector<T>& v) {
+        T* d = reinterpret_cast<T*>(dmalloc((v.size() * sizeof(T) + 3) / 4 + 4));
+        if (d && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+            err = fail(FC_E_HIP, "hipMemcpy failed while uploading a plan table");
+            return nullptr;
+        }
+        return d;
     }
     std::multimap<size_t, float*> pool;   // buffers handed back by release(): later tensors of the same size reuse them
     Act act(int C, int H, int W) {

@@ -19,6 +19,7 @@
 #include "plan.h"
 #include "unet_priv.h"
 #include "unet_sample.h"
+#include "unet_walk.h"
 
 namespace fc {
 
@@ -58,6 +59,7 @@ static void decl_linattn(fc_unet* u, const std::string& p, int C) {
     decl_norm(u, p + ".fn.norm", C);
 }
 
+// PyTorch's registration order (ups before mid_*), not walk_unet's execution order: every parameter's offset in the flat table pins it
 static int declare_all(fc_unet* u) {
     const fc_unet_config& c = u->cfg;
     const int dim = c.dim, ch = c.channels, L = c.n_levels;
@@ -128,14 +130,30 @@ static int g_fused_tail = -1;
 static bool fused_tail_enabled() { return g_fused_tail != 0; }
 
 // ------------------------------------------------------------------------------------------- plan builder
+// Arithmetic of one attention module per sample: to_qkv, the two products of the core (linear: 32x32 contexts per head; full: n x n scores), to_out
+static double attn_flops(int n, int C, int heads, bool full) {
+    const int hid = heads * 32;
+    return 2.0 * n * (double)C * 3 * hid + (full ? 2.0 * 2.0 * n * n * 32 * heads : 2.0 * 2 * n * 32 * 32 * heads) + 2.0 * n * (double)hid * C;
+}
+
+// The ordinary plan: walk_unet's emitter of one launch (or a few) per module over arena tensors.  Every activation keeps a buffer of its
+// own (retire does nothing): debug taps and the backward read them after the forward.
 struct Builder : PlanBuilder {
+    using T = Act;
     fc_unet* u = nullptr;
-    Builder(fc_unet* u_, Plan* pl_, int B_) : u(u_) { pl = pl_; B = B_; fin_err_word = u_->dev_err; }
+    const int H, W;           // the latent's extent
+    Act mask_nhwc;            // stem: the call's mask as the injections read it
+    Stat gn1;                 // GroupNorm(1) statistics a resblock(..., feeds_attention) leaves of its output: the following attention's PreNorm
+    Builder(fc_unet* u_, Plan* pl_, int B_, int H_, int W_) : u(u_), H(H_), W(W_) { pl = pl_; B = B_; fin_err_word = u_->dev_err; }
     // launches that wait for other workgroups: only on a device this handle has to itself
     bool meeting_ok() const { return fused_tail_enabled() && !u->shared; }
+    void retire(const Act&) {}
+    void push_finalize(const FinalizeArgs& f) {
+        if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
+    }
 
     // ResnetBlock (unet.py:76-96): conv1 [+res_conv] | conv2 with GN+FiLM+SiLU folded into its loader | finalize.
-    Act resblock(const std::string& p, const Act& x, const Act* skip, int cout, bool want_gn1, Stat* gn1) {
+    Act resblock(const std::string& p, const Act& x, const Act* skip, int cout, bool feeds_attention) {
         scope = p;
         const int G = u->cfg.groups, cin = x.C + (skip ? skip->C : 0);
         Act h1 = act(cout, x.H, x.W), h2 = act(cout, x.H, x.W), out = act(cout, x.H, x.W), rb;
@@ -165,37 +183,38 @@ struct Builder : PlanBuilder {
         // the backward: conv + finalize (a fused training tail measured no faster, r02: stl_sd step 3.515 against 3.446 ms).
         const float* resp = (cin != cout) ? rb.p : x.p;
         const bool fused = !u->keep_all &&
-                           conv_fin(b, out, G, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias"), resp, want_gn1, gn1, !meeting_ok());
+                           conv_fin(b, out, G, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias"), resp, feeds_attention, &gn1, !meeting_ok());
         if (!fused) {
             conv(b, h2, G, &st2);
             FinalizeArgs f;
             f.h = h2.p; f.xf = xf_of(st2, 2, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias"));
             f.res = resp; f.y = out.p; f.HW = x.H * x.W; f.C = cout;
-            if (want_gn1) {
+            if (feeds_attention) {
                 const int bps = finalize_blocks_per_sample(f.HW, f.C);
-                *gn1 = stat(1, bps, (float)(f.HW * f.C / bps));
-                f.stats_out = gn1->p;
+                gn1 = stat(1, bps, (float)(f.HW * f.C / bps));
+                f.stats_out = gn1.p;
             }
-            if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
+            push_finalize(f);
         }
         pl->named[p] = out; pl->named[p + ".h1"] = h1; pl->named[p + ".h2"] = h2;
         ResRec rec;
         rec.p = p; rec.x = x; if (skip) rec.skip = *skip; rec.h1 = h1; rec.h2 = h2; rec.rb = rb; rec.out = out; rec.st1 = st1; rec.st2 = st2; rec.cout = cout;
-        pl->tape.push_back({0, (int)pl->res.size()});
+        pl->tape.push_back({TAPE_RES, (int)pl->res.size()});
         pl->res.push_back(rec);
         return out;
     }
 
     // Residual(PreNorm(LinearAttention)) (unet.py:125-161,250): qkv conv with GroupNorm(1) in its loader | context |
     // apply | to_out conv | GroupNorm(1) + residual.
-    Act linattn(const std::string& p, const Act& x, const Stat& gn1) {
+    Act attention(const std::string& p, const Act& x, bool full) {
         scope = p;
+        if (full) return midattn(p, x);
         const int hid = u->heads * 32, n = x.H * x.W, heads = u->heads;
         // measured (tools/op_table.py, B=64): fused 110 vs 201 us at n=1024, 43 vs 65 us at n=256; at n <= 64 the per-workgroup weight
         // loads dominate and the unfused chain wins (37 vs 67 us at n=16, C=256)
-        if (!u->keep_all && n >= 256 && linattn_fused_supported(n, x.C, heads)) return linattn_fused(p, x, gn1);
+        if (!u->keep_all && n >= 256 && linattn_fused_supported(n, x.C, heads)) return linattn_fused(p, x);
         // n <= 64: a workgroup per (sample, head), then one per sample (linattn_sample.hip): 2 launches instead of 5
-        if (!u->keep_all && linattn_sample_supported(n, x.C, heads)) return linattn_sample(p, x, gn1);
+        if (!u->keep_all && linattn_sample_supported(n, x.C, heads)) return attn_sample(p, x, false);
         Act qkv = act(3 * hid, x.H, x.W), lao = act(hid, x.H, x.W), yb = act(x.C, x.H, x.W), out = act(x.C, x.H, x.W);
         float* ctx = dmalloc((size_t)B * heads * 32 * 32);
         ConvArgs a;
@@ -216,25 +235,33 @@ struct Builder : PlanBuilder {
         FinalizeArgs f;
         f.h = yb.p; f.xf = xf_of(sty, 1, u->R(p + ".fn.fn.to_out.1.weight"), u->R(p + ".fn.fn.to_out.1.bias"));
         f.res = x.p; f.y = out.p; f.HW = n; f.C = x.C;
-        if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
+        push_finalize(f);
         pl->named[p] = out; pl->named[p + ".qkv"] = qkv; pl->named[p + ".lao"] = lao; pl->named[p + ".y"] = yb;
         LinRec rec;
         rec.p = p; rec.x = x; rec.qkv = qkv; rec.lao = lao; rec.yb = yb; rec.out = out; rec.ctx = ctx; rec.gn1 = gn1; rec.sty = sty;
-        pl->tape.push_back({1, (int)pl->lin.size()});
+        pl->tape.push_back({TAPE_LIN, (int)pl->lin.size()});
         pl->lin.push_back(rec);
         return out;
     }
 
-    // the same module on the fused kernels (linattn_fused.hip): x -> context -> y in two launches, q/k/v never stored
-    Act linattn_fused(const std::string& p, const Act& x, const Stat& gn1) {
-        const int n = x.H * x.W, heads = u->heads, hid = heads * 32;
-        Act yb = act(x.C, x.H, x.W), out = act(x.C, x.H, x.W);
-        Stat sty = stat(1, linattn_fused_tiles(n), linattn_fused_nt(n, x.C));
+    // what the three one- and two-launch attention forms fill alike; `full`: mid_attn's to_out is a bare convolution (unet.py:112), no Sequential
+    LaArgs la_args(const std::string& p, const Act& x, bool full) const {
+        const std::string to_out = p + (full ? ".fn.fn.to_out" : ".fn.fn.to_out.0");
         LaArgs a;
         a.x = x.p; a.xf = xf_of(gn1, 1, u->R(p + ".fn.norm.weight"), u->R(p + ".fn.norm.bias"));
-        a.wqkv = u->P(p + ".fn.fn.to_qkv.weight"); a.wout = u->P(p + ".fn.fn.to_out.0.weight"); a.bout = u->R(p + ".fn.fn.to_out.0.bias");
-        a.ctx = dmalloc((size_t)B * heads * 32 * 32); a.y = yb.p; a.stats_out = sty.p; a.n = n; a.C = x.C; a.heads = heads;
-        const double fl = 2.0 * n * (double)x.C * 3 * hid + 2.0 * 2 * n * 32 * 32 * heads + 2.0 * n * (double)hid * x.C;
+        a.wqkv = u->P(p + ".fn.fn.to_qkv.weight"); a.wout = u->P(to_out + ".weight"); a.bout = u->R(to_out + ".bias");
+        a.n = x.H * x.W; a.C = x.C; a.heads = u->heads;
+        return a;
+    }
+
+    // the same module on the fused kernels (linattn_fused.hip): x -> context -> y in two launches, q/k/v never stored
+    Act linattn_fused(const std::string& p, const Act& x) {
+        const int n = x.H * x.W, heads = u->heads;
+        Act yb = act(x.C, x.H, x.W), out = act(x.C, x.H, x.W);
+        Stat sty = stat(1, linattn_fused_tiles(n), linattn_fused_nt(n, x.C));
+        LaArgs a = la_args(p, x, false);
+        a.ctx = dmalloc((size_t)B * heads * 32 * 32); a.y = yb.p; a.stats_out = sty.p;
+        const double fl = attn_flops(n, x.C, heads, false);
         // The module closed by its own apply launch (to_out.1's GroupNorm(1) + the residual on the tile still in registers: no y round trip,
         // no finalize launch) where the workgroups of a sample may wait for each other: the exclusive plan, the whole grid resident.
         if (!err && meeting_ok() && linattn_fused_meeting_ok(B, n, x.C)) {
@@ -257,50 +284,35 @@ struct Builder : PlanBuilder {
         FinalizeArgs f;
         f.h = yb.p; f.xf = xf_of(sty, 1, u->R(p + ".fn.fn.to_out.1.weight"), u->R(p + ".fn.fn.to_out.1.bias"));
         f.res = x.p; f.y = out.p; f.HW = n; f.C = x.C;
-        if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
+        push_finalize(f);
         pl->named[p] = out; pl->named[p + ".y"] = yb;
         return out;
     }
 
-    // the whole module in two launches (linattn_sample.hip)
-    Act linattn_sample(const std::string& p, const Act& x, const Stat& gn1) {
-        const int n = x.H * x.W, heads = u->heads, hid = heads * 32;
+    // the whole module, linear or full, in two launches (linattn_sample.hip)
+    Act attn_sample(const std::string& p, const Act& x, bool full) {
+        const int n = x.H * x.W, heads = u->heads;
         Act out = act(x.C, x.H, x.W);
-        LaArgs a;
-        a.x = x.p; a.xf = xf_of(gn1, 1, u->R(p + ".fn.norm.weight"), u->R(p + ".fn.norm.bias"));
-        a.wqkv = u->P(p + ".fn.fn.to_qkv.weight"); a.wout = u->P(p + ".fn.fn.to_out.0.weight"); a.bout = u->R(p + ".fn.fn.to_out.0.bias");
+        LaArgs a = la_args(p, x, full);
         a.wqkv4 = u->P8(p + ".fn.fn.to_qkv.weight");
-        a.g2 = u->R(p + ".fn.fn.to_out.1.weight"); a.b2 = u->R(p + ".fn.fn.to_out.1.bias"); a.out = out.p;
-        a.n = n; a.C = x.C; a.heads = heads;
+        if (!full) { a.g2 = u->R(p + ".fn.fn.to_out.1.weight"); a.b2 = u->R(p + ".fn.fn.to_out.1.bias"); }
+        a.out = out.p;
         a.part = dmalloc((size_t)B * heads * n * x.C);
-        const double fl = 2.0 * n * (double)x.C * 3 * hid + 2.0 * 2 * n * 32 * 32 * heads + 2.0 * n * (double)hid * x.C;
-        if (!err) push([a](const FwdCtx& c, hipStream_t s) { LaArgs b = a; b.B = c.B; return linattn_sample_launch(b, s); }, "linattn_sample", fl);
+        if (!err) push([a, full](const FwdCtx& c, hipStream_t s) { LaArgs b = a; b.B = c.B; return full ? attn_sample_launch(b, s) : linattn_sample_launch(b, s); },
+                       full ? "attn_sample" : "linattn_sample", attn_flops(n, x.C, heads, full));
         pl->named[p] = out;
         return out;
     }
 
     // Residual(PreNorm(Attention)) (unet.py:99-122,262)
-    Act midattn(const Act& x, const Stat& gn1) {
-        scope = "mid_attn";
+    Act midattn(const std::string& p, const Act& x) {
         const int hid = u->heads * 32, n = x.H * x.W, heads = u->heads;
-        if (!u->keep_all && attn_sample_supported(n, x.C, heads)) {    // two launches instead of three (linattn_sample.hip)
-            Act out = act(x.C, x.H, x.W);
-            LaArgs a;
-            a.x = x.p; a.xf = xf_of(gn1, 1, u->R("mid_attn.fn.norm.weight"), u->R("mid_attn.fn.norm.bias"));
-            a.wqkv = u->P("mid_attn.fn.fn.to_qkv.weight"); a.wout = u->P("mid_attn.fn.fn.to_out.weight"); a.bout = u->R("mid_attn.fn.fn.to_out.bias");
-            a.wqkv4 = u->P8("mid_attn.fn.fn.to_qkv.weight");
-            a.out = out.p; a.n = n; a.C = x.C; a.heads = heads;
-            a.part = dmalloc((size_t)B * heads * n * x.C);
-            const double fl = 2.0 * n * (double)x.C * 3 * hid + 2.0 * 2.0 * n * n * 32 * heads + 2.0 * n * (double)hid * x.C;
-            if (!err) push([a](const FwdCtx& c, hipStream_t s) { LaArgs b = a; b.B = c.B; return attn_sample_launch(b, s); }, "attn_sample", fl);
-            pl->named["mid_attn"] = out;
-            return out;
-        }
+        if (!u->keep_all && attn_sample_supported(n, x.C, heads)) return attn_sample(p, x, true);    // two launches instead of three
         Act qkv = act(3 * hid, x.H, x.W), ao = act(hid, x.H, x.W), out = act(x.C, x.H, x.W);
         ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.s0.xf = xf_of(gn1, 1, u->R("mid_attn.fn.norm.weight"), u->R("mid_attn.fn.norm.bias"));
+        a.s0.p = x.p; a.s0.C = x.C; a.s0.xf = xf_of(gn1, 1, u->R(p + ".fn.norm.weight"), u->R(p + ".fn.norm.bias"));
         a.Hs = x.H; a.Ws = x.W; a.KS = 1;
-        a.w = u->P("mid_attn.fn.fn.to_qkv.weight");
+        a.w = u->P(p + ".fn.fn.to_qkv.weight");
         conv(a, qkv, 0, nullptr);
         const float* qp = qkv.p; float* ap = ao.p;
         if (!err) {
@@ -308,21 +320,22 @@ struct Builder : PlanBuilder {
         }
         ConvArgs o;
         o.s0.p = ao.p; o.s0.C = hid; o.Hs = x.H; o.Ws = x.W; o.KS = 1;
-        o.w = u->P("mid_attn.fn.fn.to_out.weight"); o.bias = u->R("mid_attn.fn.fn.to_out.bias");
+        o.w = u->P(p + ".fn.fn.to_out.weight"); o.bias = u->R(p + ".fn.fn.to_out.bias");
         o.add = x.p;
         conv(o, out, 0, nullptr);
-        pl->named["mid_attn"] = out;
+        pl->named[p] = out;
         MidRec rec;
         rec.x = x; rec.qkv = qkv; rec.ao = ao; rec.out = out; rec.gn1 = gn1;
-        pl->tape.push_back({2, (int)pl->mid.size()});
+        pl->tape.push_back({TAPE_MID, (int)pl->mid.size()});
         pl->mid.push_back(rec);
         return out;
     }
 
     // x + SiLU(conv3x3(cat[x, bilinear(mask)]))  (unet.py:336-340,360-364); a plain copy when no mask is given
-    Act mask_inject(const std::string& name, const Act& x, const Act& mask_nhwc) {
+    Act inject(const std::string& name, const Act& x) {
         scope = name;
         Act mr = act(mask_nhwc.C, x.H, x.W), out = act(x.C, x.H, x.W);
+        if (err) return out;
         const float* mp = mask_nhwc.p; float* rp = mr.p;
         const int C = mask_nhwc.C, Hs = mask_nhwc.H, Ws = mask_nhwc.W, Hd = x.H, Wd = x.W;
         const bool keep = u->keep_all;             // training: the pre-activation z stays (SiLU' needs it), SiLU + residual as a pass of its own
@@ -346,10 +359,108 @@ struct Builder : PlanBuilder {
             return keep ? silu_fwd_launch(zp, xp, op, per * c.B, s) : FC_OK;
         }, std::string("bilinear+") + kTileNames[tile], 2.0 * x.H * x.W * 9 * (double)a.Cin * a.Cout);
         InjRec rec;
-        rec.name = name.substr(0, name.size() - 0); rec.x = x; rec.mr = mr; rec.z = z; rec.out = out;
-        pl->tape.push_back({4, (int)pl->inj.size()});
+        rec.name = name; rec.x = x; rec.mr = mr; rec.z = z; rec.out = out;
+        pl->tape.push_back({TAPE_INJ, (int)pl->inj.size()});
         pl->inj.push_back(rec);
         return out;
+    }
+
+    // init_conv (unet.py:295) and mask fusion (unet.py:298-305)
+    Act stem() {
+        const fc_unet_config& c = u->cfg;
+        const int dim = c.dim, ch = c.channels, HW = H * W, maxB = B;
+        Act x0 = act(dim, H, W);
+        pl->named["init"] = x0;
+        pl->x0 = x0;
+        const float *w = u->P("init_conv.weight"), *bias = u->R("init_conv.bias");
+        float* x0p = x0.p;
+        scope = "init_conv";
+        if (!c.mask_cond) {
+            // (cx.step: the evaluation before this one has written x0 and fetched the conditioning slice -- conv_dev.h FL_STEP)
+            push([=](const FwdCtx& cx, hipStream_t s) { return cx.step ? (int)FC_OK : init_conv_launch(cx.fetch, cx.x, cx.x_mod, w, bias, x0p, cx.B, ch, HW, dim, s); }, "init_conv", 2.0 * HW * ch * dim);
+            return x0;
+        }
+        Act xi = act(dim, H, W), f1 = act(2 * dim, H, W), f2 = act(2 * dim, H, W);
+        const bool keep = u->keep_all;         // training keeps the pre-activations z1, z2 of the two SiLU layers
+        Act z1 = keep ? act(2 * dim, H, W) : Act(), z2 = keep ? act(2 * dim, H, W) : Act();
+        mask_nhwc = act(ch, H, W);
+        float *xip = xi.p, *mp = mask_nhwc.p;
+        push([=](const FwdCtx& cx, hipStream_t s) -> int {
+            if (cx.mask) FC_TRY(nchw_to_nhwc_launch(cx.mask, mp, cx.B, ch, HW, ch, cx.x_mod, s));
+            return init_conv_launch(cx.fetch, cx.x, cx.x_mod, w, bias, cx.mask_fuse ? xip : x0p, cx.B, ch, HW, dim, s);
+        }, "init_conv", 2.0 * HW * ch * dim);
+        ConvArgs a[3];
+        const char* names[3] = {"mask_fusion_conv.0", "mask_fusion_conv.2", "mask_fusion_conv.4"};
+        const Act* srcs[3] = {&xi, &f1, &f2};
+        const Act* dsts[3] = {keep ? &z1 : &f1, keep ? &z2 : &f2, &x0};
+        int tiles[3];
+        for (int i = 0; i < 3 && !err; ++i) {
+            a[i].s0.p = srcs[i]->p; a[i].s0.C = srcs[i]->C;
+            if (i == 0) { a[i].s1.p = mask_nhwc.p; a[i].s1.C = ch; }
+            a[i].Hs = H; a[i].Ws = W; a[i].KS = i == 0 ? 5 : 3; a[i].pad = i == 0 ? 2 : 1; a[i].out_act = (i < 2 && !keep);
+            a[i].w = u->P(std::string(names[i]) + ".weight"); a[i].bias = u->R(std::string(names[i]) + ".bias");
+            a[i].B = maxB; a[i].H = H; a[i].W = W; a[i].Cout = dsts[i]->C; a[i].out = dsts[i]->p; a[i].Cin = a[i].s0.C + a[i].s1.C;
+            ConvGeom g;
+            err = conv_plan(a[i], TILE_AUTO, &g);
+            tiles[i] = g.tile;
+        }
+        if (err) return x0;
+        const ConvArgs a0 = a[0], a1 = a[1], a2 = a[2];
+        const int t0 = tiles[0], t1 = tiles[1], t2 = tiles[2];
+        const float *z1p = z1.p, *z2p = z2.p;
+        float *f1p = f1.p, *f2p = f2.p;
+        const size_t nf = (size_t)HW * 2 * dim;
+        scope = "mask_fusion_conv";
+        push([=](const FwdCtx& cx, hipStream_t s) -> int {
+            if (!cx.mask_fuse) return FC_OK;
+            ConvArgs q = a0; q.B = cx.B; FC_TRY(conv_launch(q, t0, s));
+            if (keep) FC_TRY(silu_fwd_launch(z1p, nullptr, f1p, nf * cx.B, s));
+            q = a1; q.B = cx.B; FC_TRY(conv_launch(q, t1, s));
+            if (keep) FC_TRY(silu_fwd_launch(z2p, nullptr, f2p, nf * cx.B, s));
+            q = a2; q.B = cx.B; return conv_launch(q, t2, s);
+        }, "mask_fusion(3 x conv_igemm)", 2.0 * HW * (25.0 * (dim + ch) * 2 * dim + 9.0 * 2 * dim * 2 * dim + 9.0 * 2 * dim * dim));
+        pl->fuse.present = true;
+        pl->fuse.xi = xi; pl->fuse.mask = mask_nhwc; pl->fuse.z1 = z1; pl->fuse.f1 = f1; pl->fuse.z2 = z2; pl->fuse.f2 = f2; pl->fuse.x0 = x0;
+        return x0;
+    }
+
+    // downs.i.3 / ups.i.3: Downsample, a 2x2 / stride-2 convolution (unet.py:253); Upsample, nearest x2 + 3x3 (unet.py:42-46); on the last
+    // level a 3x3 convolution that keeps the resolution
+    Act resample(const std::string& p, const Act& x, int cout, bool last, bool up) {
+        scope = p;
+        const std::string name = last ? p : p + ".1";
+        const bool down = !last && !up;
+        ConvArgs a;
+        a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W;
+        a.KS = down ? 2 : 3; a.pad = down ? 0 : 1; a.stride = down ? 2 : 1; a.ups = !last && up;
+        a.w = u->P(name + ".weight"); a.bias = u->R(name + ".bias"); a.w4 = u->P8(name + ".weight");    // (no k-step-quad copy of a Downsample's weight)
+        Act o = down ? act(cout, x.H / 2, x.W / 2) : act(cout, x.H << a.ups, x.W << a.ups);
+        // (round 3) the upsampling folded into the WEIGHTS -- four 2x2 parity convolutions on x in one launch, 4/9 of the multiply-adds
+        // (plan.h conv_up2; FLOCODER_AMD_UPS_FOLD=0: off).  Training plans too: it is the same function of (x, w) up to fp32 rounding, and
+        // the backward differentiates it in its 3x3 form from the same saved x (flowers-sized step 6.49 -> 6.45 ms).  Where the shape is
+        // not covered, nn.Upsample folded into the convolution's loader.
+        if (!a.ups || !conv_up2(a.s0, x, u->PUP(name + ".weight"), a.bias, o, 0, nullptr)) conv(a, o, 0, nullptr);
+        pl->tape.push_back({TAPE_CONV, (int)pl->convs.size()});
+        pl->convs.push_back({name, x, o, a.KS, a.pad, a.stride, a.ups});
+        pl->named[p] = o;
+        return o;
+    }
+    Act downsample(const std::string& p, const Act& x, int cout, bool last) { return resample(p, x, cout, last, false); }
+    Act upsample(const std::string& p, const Act& x, int cout, bool last) { return resample(p, x, cout, last, true); }
+
+    // final_res_block on cat[x, x0] and final_conv (unet.py:369-372)
+    Act head(const Act& x, const Act& x0) {
+        const fc_unet_config& c = u->cfg;
+        const int dim = c.dim, ch = c.channels, HW = H * W;
+        // final_res_block's closing launch may close the Euler sampler's step as well: final_conv, the update and the next evaluation's
+        // init_conv are pointwise per pixel (init_conv is a 1x1 convolution here), and the launch's tile holds every channel of its pixels
+        if (!c.mask_cond && dim == kStepDim && ch == kStepCh) step_out = x0;
+        pl->head = resblock("final_res_block", x, &x0, dim, false);
+        step_out = Act();
+        const float *xp = pl->head.p, *w = u->P("final_conv.weight"), *bias = u->R("final_conv.bias");
+        scope = "final_conv";
+        if (!err) push([=](const FwdCtx& cx, hipStream_t s) { return cx.step ? (int)FC_OK : final_conv_launch(xp, w, bias, cx.out, cx.B, dim, HW, ch, cx.euler, s); }, "final_conv", 2.0 * HW * dim * ch);
+        return Act();             // final_conv writes the caller's tensor (FwdCtx::out), not the arena
     }
 };
 
@@ -368,38 +479,35 @@ static void free_plan(fc_unet* u) {
 
 // ---- one workgroup per sample (unet_sample.hip): the forward as a program over LDS-resident activations -------------------------------
 // Used for inference plans of models whose whole per-sample state fits a CU's LDS (the dim-8 inpainting flow at 4x8x8: BASELINE config 5).
-// Returns FC_OK and leaves ONE launch in the plan, or 1 when the model does not qualify (the caller then builds the ordinary plan).
-static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, int W) {
-    // ON for the models that qualify unless FLOCODER_AMD_SAMPLE_KERNEL=0 (round 4, config 5's dim-8 / 4x8x8 flow: 538 us per evaluation
-    // against 842 us for the 115 launches of the ordinary plan; profiles/r04_sample_kernel_stamps.txt, DESIGN.md section 7).  A sample
-    // is ONE workgroup, so the kernel's time is that of one sample as long as every sample has a CU of its own: beyond that the ordinary
-    // plan (whose launches grow wider, not longer) wins again -- batches larger than the CU count keep it.
-    static const bool off = [] { const char* e = std::getenv("FLOCODER_AMD_SAMPLE_KERNEL"); return e && std::string(e) == "0"; }();
-    static const int cus = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; return n; }();
-    if (maxB > cus) return 1;
-    const fc_unet_config& c = u->cfg;
-    const int L = c.n_levels, dim = c.dim, ch = c.channels, G = c.groups, heads = u->heads;
-    if (off || u->keep_all || G > 8 || heads != 4) return 1;
-    const std::vector<int>& cs = u->chans;
+// SampleProgram is walk_unet's emitter of that program: tensors are offsets into the workgroup's LDS, a step is one SStep.
+struct SampleProgram {
     struct T { int off = -1, C = 0, H = 0, W = 0; };
+    const fc_unet* u;
+    const int H, W, dim, ch, G, heads;
     std::vector<SStep> prog;
     int top = 0, peak = 0;
     double flops = 0.0;
-    auto alloc = [&](int floats) { const int o = top; top += (floats + 3) & ~3; if (top > peak) peak = top; return o; };
+    T xin, mask;              // stem: where the launch puts the call's x and mask
+    SampleProgram(const fc_unet* u_, int H_, int W_) : u(u_), H(H_), W(W_), dim(u_->cfg.dim), ch(u_->cfg.channels), G(u_->cfg.groups), heads(u_->heads) {}
+
+    int alloc(int floats) { const int o = top; top += (floats + 3) & ~3; if (top > peak) peak = top; return o; }
     // block outputs whose last reader has been emitted serve later tensors of the same size (every tensor a step reads or writes is alive
-    // for the whole step, so a buffer may be handed out again only AFTER the step that last read it has been pushed)
+    // for the whole step, so a buffer may be handed out again only AFTER the step that last read it has been pushed: walk_unet's order)
     std::multimap<int, int> pool;
-    auto tensor = [&](int C, int h, int w) {
+    T tensor(int C, int h, int w) {
         T t; t.C = C; t.H = h; t.W = w;
         auto it = pool.find(C * h * w);
         if (it != pool.end()) { t.off = it->second; pool.erase(it); }
         else t.off = alloc(C * h * w);
         return t;
-    };
-    auto release = [&](const T& t) { if (t.off >= 0) pool.emplace(t.C * t.H * t.W, t.off); };
+    }
+    void retire(const T& t) { if (t.off >= 0) pool.emplace(t.C * t.H * t.W, t.off); }
+    // a temporary of the running module: stack-allocated above the module's `mark`, never pooled
+    T temp(int C, int h, int w) { T t; t.C = C; t.H = h; t.W = w; t.off = alloc(C * h * w); return t; }
     struct NormSpec { std::string name; int groups = 0, ss_off = -1; };       // a GroupNorm folded into the convolution's epilogue (groups > 0)
-    auto conv = [&](const T& x, const T* x1, const T& out, const std::string& name, int KS, int pad, int stride, int ups, int act, int res, int guard, bool bias = true,
-                    const NormSpec* nm = nullptr) {
+    // emits the step; returns its FLOPs per sample
+    double conv(const T& x, const T* x1, const T& out, const std::string& name, int KS, int pad, int stride, int ups, int act, int res, int guard, bool bias = true,
+                const NormSpec* nm = nullptr) {
         SStep s;
         if (nm && nm->groups > 0) {
             s.fnorm = 1; s.G = nm->groups; s.ss_off = nm->ss_off; s.lcpg = ilog2(out.C / nm->groups);
@@ -443,32 +551,32 @@ static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, 
         }
         prog.push_back(s);
         return 2.0 * out.H * out.W * KS * KS * (double)(s.C0 + s.C1) * out.C;
-    };
-    auto copy = [&](const T& x, const T& out, int guard) {
+    }
+    void copy(const T& x, const T& out, int guard) {
         SStep s;
         s.op = S_COPY; s.guard = guard; s.in0 = x.off; s.out = out.off; s.Cout = x.C * x.H * x.W;
         prog.push_back(s);
-    };
-    auto resblock = [&](const std::string& p, const T& x, const T* skip, int cout) {
+    }
+    T resblock(const std::string& p, const T& x, const T* skip, int cout, bool /*feeds_attention: the attention step takes its own statistics*/) {
         T out = tensor(cout, x.H, x.W);
         const int mark = top, cin = x.C + (skip ? skip->C : 0);
         // Block = convolution with GroupNorm (+ FiLM) + SiLU in its epilogue (unet.py:57-73); block2 adds the residual there too
-        T a1; a1.C = cout; a1.H = x.H; a1.W = x.W; a1.off = alloc(cout * x.H * x.W);      // (temporaries: stack-allocated above `mark`, never pooled)
+        T a1 = temp(cout, x.H, x.W);
         NormSpec n1{p + ".block1.norm", G, u->ss_off.at(p)}, n2{p + ".block2.norm", G, -1};
         flops += conv(x, skip, a1, p + ".block1.proj", 3, 1, 1, 0, 1, -1, 0, true, &n1);
         int res = x.off;
         if (cin != cout) {
-            T rb; rb.C = cout; rb.H = x.H; rb.W = x.W; rb.off = alloc(cout * x.H * x.W);
+            T rb = temp(cout, x.H, x.W);
             flops += conv(x, skip, rb, p + ".res_conv", 1, 0, 1, 0, 0, -1, 0);
             res = rb.off;
         }
         flops += conv(a1, nullptr, out, p + ".block2.proj", 3, 1, 1, 0, 1, res, 0, true, &n2);
         top = mark;
         return out;
-    };
-    auto attention = [&](const std::string& p, const T& x, bool full) {
+    }
+    T attention(const std::string& p, const T& x, bool full) {
         T out = tensor(x.C, x.H, x.W);
-        const int mark = top, n = x.H * x.W, hid = heads * 32;
+        const int mark = top, n = x.H * x.W;
         SStep s;
         s.op = full ? S_ATTN : S_LINATTN; s.in0 = x.off; s.out = out.off; s.C0 = x.C; s.Hi = x.H; s.Wi = x.W;
         if (n == 1) { s.op = S_ATTN1; s.full = full ? 1 : 0; }       // one position: the closed form (unet_sample.hip op_attention1)
@@ -486,31 +594,32 @@ static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, 
             s.g2 = u->R(p + ".fn.fn.to_out.1.weight"); s.be2 = u->R(p + ".fn.fn.to_out.1.bias");
         }
         prog.push_back(s);
-        flops += 2.0 * n * (double)x.C * 3 * hid + (full ? 2.0 * 2.0 * n * n * 32 * heads : 2.0 * 2 * n * 32 * 32 * heads) + 2.0 * n * (double)hid * x.C;
+        flops += attn_flops(n, x.C, heads, full);
         top = mark;
         return out;
-    };
-    T xin = tensor(ch, H, W), mask;
-    if (c.mask_cond) mask = tensor(ch, H, W);
-    T xi = tensor(dim, H, W), x0 = xi;
-    flops += conv(xin, nullptr, xi, "init_conv", 1, 0, 1, 0, 0, -1, 0);
-    if (c.mask_cond) {                                   // unet.py:298-305: replaces x when a mask is given that is not all ones
-        x0 = tensor(dim, H, W);
+    }
+    T stem() {
+        xin = tensor(ch, H, W);
+        if (u->cfg.mask_cond) mask = tensor(ch, H, W);
+        T xi = tensor(dim, H, W);
+        flops += conv(xin, nullptr, xi, "init_conv", 1, 0, 1, 0, 0, -1, 0);
+        if (!u->cfg.mask_cond) return xi;
+        T x0 = tensor(dim, H, W);                        // unet.py:298-305: replaces x when a mask is given that is not all ones
         const int mark = top;
-        T f1, f2;
-        f1.C = f2.C = 2 * dim; f1.H = f2.H = H; f1.W = f2.W = W; f1.off = alloc(2 * dim * H * W); f2.off = alloc(2 * dim * H * W);
+        T f1 = temp(2 * dim, H, W), f2 = temp(2 * dim, H, W);
         conv(xi, &mask, f1, "mask_fusion_conv.0", 5, 2, 1, 0, 1, -1, 2);
         conv(f1, nullptr, f2, "mask_fusion_conv.2", 3, 1, 1, 0, 1, -1, 2);
         conv(f2, nullptr, x0, "mask_fusion_conv.4", 3, 1, 1, 0, 0, -1, 2);
         copy(xi, x0, 5);
         flops += 2.0 * H * W * (25.0 * (dim + ch) * 2 * dim + 9.0 * 2 * dim * 2 * dim + 9.0 * 2 * dim * dim);
         top = mark;
-        release(xi);
+        retire(xi);
+        return x0;
     }
-    auto inject = [&](const std::string& name, const T& x) {       // x + SiLU(conv3x3(cat[x, bilinear(mask)])), unet.py:336-340,360-364
+    T inject(const std::string& name, const T& x) {       // x + SiLU(conv3x3(cat[x, bilinear(mask)])), unet.py:336-340,360-364
         T out = tensor(x.C, x.H, x.W);
         const int mark = top;
-        T mr; mr.C = ch; mr.H = x.H; mr.W = x.W; mr.off = alloc(ch * x.H * x.W);
+        T mr = temp(ch, x.H, x.W);
         SStep s;
         s.op = S_BILINEAR; s.guard = 1; s.in0 = mask.off; s.out = mr.off; s.C0 = ch; s.Hi = H; s.Wi = W; s.Ho = x.H; s.Wo = x.W;
         prog.push_back(s);
@@ -518,43 +627,39 @@ static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, 
         copy(x, out, 3);
         top = mark;
         return out;
-    };
-    std::vector<T> skips;
-    T x = x0;
-    // `step(y = f(x))`: the new tensor is taken BEFORE the old one is released (they are alive together in the step), the old one after
-    auto next = [&](T& cur, const T& nw, bool keep_old) { if (!keep_old) release(cur); cur = nw; };
-    for (int i = 0; i < L; ++i) {
-        const std::string p = "downs." + std::to_string(i);
-        next(x, resblock(p + ".0", x, nullptr, cs[i]), i == 0);                 // (level 0's input is x0: final_res_block reads it)
-        skips.push_back(x);
-        next(x, resblock(p + ".1", x, nullptr, cs[i]), true);                   // the input is a skip
-        next(x, attention(p + ".2", x, false), false);
-        skips.push_back(x);
-        if (c.mask_cond && i < 2) next(x, inject("down_mask_fusions." + std::to_string(i) + ".0", x), true);     // the input is a skip
-        const bool x_is_skip = !(c.mask_cond && i < 2);
-        if (i == L - 1) { T o = tensor(cs[i + 1], x.H, x.W); flops += conv(x, nullptr, o, p + ".3", 3, 1, 1, 0, 0, -1, 0); next(x, o, x_is_skip); }
-        else { T o = tensor(cs[i + 1], x.H / 2, x.W / 2); flops += conv(x, nullptr, o, p + ".3.1", 2, 0, 2, 0, 0, -1, 0); next(x, o, x_is_skip); }
     }
-    next(x, resblock("mid_block1", x, nullptr, cs[L]), false);
-    next(x, attention("mid_attn", x, true), false);
-    next(x, resblock("mid_block2", x, nullptr, cs[L]), false);
-    for (int i = 0; i < L; ++i) {
-        const std::string p = "ups." + std::to_string(i);
-        const int din = cs[L - 1 - i], dout = cs[L - i];
-        T s1 = skips.back(); skips.pop_back();
-        next(x, resblock(p + ".0", x, &s1, dout), false);
-        release(s1);
-        T s2 = skips.back(); skips.pop_back();
-        next(x, resblock(p + ".1", x, &s2, dout), false);
-        release(s2);
-        next(x, attention(p + ".2", x, false), false);
-        if (c.mask_cond && i < 2) next(x, inject("up_mask_fusions." + std::to_string(i) + ".0", x), false);
-        if (i == L - 1) { T o = tensor(din, x.H, x.W); flops += conv(x, nullptr, o, p + ".3", 3, 1, 1, 0, 0, -1, 0); next(x, o, false); }
-        else { T o = tensor(din, x.H * 2, x.W * 2); flops += conv(x, nullptr, o, p + ".3.1", 3, 1, 1, 1, 0, -1, 0); next(x, o, false); }
+    T downsample(const std::string& p, const T& x, int cout, bool last) {
+        T o = last ? tensor(cout, x.H, x.W) : tensor(cout, x.H / 2, x.W / 2);
+        flops += last ? conv(x, nullptr, o, p, 3, 1, 1, 0, 0, -1, 0) : conv(x, nullptr, o, p + ".1", 2, 0, 2, 0, 0, -1, 0);
+        return o;
     }
-    next(x, resblock("final_res_block", x, &x0, dim), false);
-    T v = tensor(ch, H, W);
-    flops += conv(x, nullptr, v, "final_conv", 1, 0, 1, 0, 0, -1, 0);
+    T upsample(const std::string& p, const T& x, int cout, bool last) {
+        T o = last ? tensor(cout, x.H, x.W) : tensor(cout, x.H * 2, x.W * 2);
+        flops += last ? conv(x, nullptr, o, p, 3, 1, 1, 0, 0, -1, 0) : conv(x, nullptr, o, p + ".1", 3, 1, 1, 1, 0, -1, 0);
+        return o;
+    }
+    T head(const T& x, const T& x0) {
+        T h = resblock("final_res_block", x, &x0, dim, false);
+        T v = tensor(ch, H, W);
+        flops += conv(h, nullptr, v, "final_conv", 1, 0, 1, 0, 0, -1, 0);
+        return v;
+    }
+};
+
+// Returns FC_OK and leaves ONE launch in the plan, or 1 when the model does not qualify (the caller then builds the ordinary plan).
+static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, const WalkCfg& walk, int maxB, int H, int W) {
+    // ON for the models that qualify unless FLOCODER_AMD_SAMPLE_KERNEL=0 (round 4, config 5's dim-8 / 4x8x8 flow: 538 us per evaluation
+    // against 842 us for the 115 launches of the ordinary plan; profiles/r04_sample_kernel_stamps.txt, DESIGN.md section 7).  A sample
+    // is ONE workgroup, so the kernel's time is that of one sample as long as every sample has a CU of its own: beyond that the ordinary
+    // plan (whose launches grow wider, not longer) wins again -- batches larger than the CU count keep it.
+    static const bool off = [] { const char* e = std::getenv("FLOCODER_AMD_SAMPLE_KERNEL"); return e && std::string(e) == "0"; }();
+    static const int cus = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; return n; }();
+    if (maxB > cus) return 1;
+    const fc_unet_config& c = u->cfg;
+    if (off || u->keep_all || c.groups > 8 || u->heads != 4) return 1;
+    SampleProgram e(u, H, W);
+    const SampleProgram::T v = walk_unet(walk, e);
+    const std::vector<SStep>& prog = e.prog;
     // every tensor at most four elements per thread, attention at most 64 channels / 64 keys (unet_sample.hip's register and staging budgets)
     // (powers of two throughout: the kernel indexes by shifts and masks)
     const int cap = 4 * SAMPLE_THREADS;
@@ -568,20 +673,19 @@ static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, 
         if ((s.op == S_ATTN || s.op == S_LINATTN) && (s.C0 > 64 || s.C0 < 4 || !is_pow2(s.C0) || !is_pow2(s.Hi * s.Wi) || s.Hi * s.Wi * s.C0 > cap)) return 1;
         if (s.op == S_ATTN && s.Hi * s.Wi > 64) return 1;
     }
-    top = peak;                                           // behind every temporary (they were released, not forgotten)
-    const int zero_off = alloc(128);
-    const int wbuf_off = alloc(2 * 4096), prog_off = alloc((int)(prog.size() * sizeof(SStep) / 4) + 4);
-    const size_t lds = (size_t)peak * sizeof(float);
+    e.top = e.peak;                                       // behind every temporary (they were released, not forgotten)
+    const int zero_off = e.alloc(128);
+    const int wbuf_off = e.alloc(2 * 4096), prog_off = e.alloc((int)(prog.size() * sizeof(SStep) / 4) + 4);
+    const size_t lds = (size_t)e.peak * sizeof(float);
     if (lds > 158 * 1024) return 1;                       // the sample does not fit a CU: ordinary plan
     FC_TRY(unet_sample_init());
-    SStep* dev = reinterpret_cast<SStep*>(b.dmalloc((prog.size() * sizeof(SStep) + 3) / 4 + 4));
+    SStep* dev = b.upload(prog);
     unsigned* done = reinterpret_cast<unsigned*>(b.dmalloc(4));
     if (b.err) return b.err;
-    FC_HIP(hipMemcpy(dev, prog.data(), prog.size() * sizeof(SStep), hipMemcpyHostToDevice));
     FC_HIP(hipMemset(done, 0, 4 * sizeof(unsigned)));
     SampleArgs a;
-    a.prog = dev; a.nsteps = (int)prog.size(); a.S = u->S; a.ss = pl->ss; a.ch = ch; a.HW = H * W;
-    a.x_off = xin.off; a.mask_off = mask.off; a.v_off = v.off; a.done = done; a.wbuf_off = wbuf_off; a.prog_off = prog_off; a.zero_off = zero_off;
+    a.prog = dev; a.nsteps = (int)prog.size(); a.S = u->S; a.ss = pl->ss; a.ch = c.channels; a.HW = H * W;
+    a.x_off = e.xin.off; a.mask_off = e.mask.off; a.v_off = v.off; a.done = done; a.wbuf_off = wbuf_off; a.prog_off = prog_off; a.zero_off = zero_off;
     const bool mask_cond = c.mask_cond != 0;
     b.scope = "unet (one workgroup per sample)";
     b.push([a, lds, mask_cond](const FwdCtx& cx, hipStream_t s) {
@@ -590,21 +694,20 @@ static int build_sample_plan(fc_unet* u, Plan* pl, Builder& b, int maxB, int H, 
         q.ss_all = cx.fetch.all; q.evalc = cx.fetch.all ? cx.fetch.evalc : nullptr; q.rows = cx.B; q.out = cx.out; q.euler = cx.euler;
         q.stamps = 5 * q.nsteps + 16 <= 4096 ? conv_stamp_buffer() : nullptr;   // (2 words per step + the phase split of the convolutions; fc_debug_set_conv_stamps: >= 4096 words)
         return unet_sample_launch(q, cx.B, lds, s);
-    }, "unet_sample", flops);
+    }, "unet_sample", e.flops);
     return FC_OK;
 }
 
 static int build_plan(fc_unet* u, Plan* pl, int maxB, int H, int W) {
     const fc_unet_config& c = u->cfg;
-    const int L = c.n_levels, dim = c.dim, ch = c.channels, HW = H * W;
+    const int L = c.n_levels, dim = c.dim, ch = c.channels;
     if (!is_pow2(H) || !is_pow2(W) || (H >> (L - 1)) < 1 || (W >> (L - 1)) < 1)
         return fail(FC_E_SHAPE, "unet: latent height/width must be powers of two >= 2^(levels-1)");
     if ((ch & 3) || (dim & 3)) return fail(FC_E_SHAPE, "unet: channels and dim must be multiples of 4");
-    Builder b(u, pl, maxB);
+    Builder b(u, pl, maxB, H, W);
     pl->flops = 0.0;
     pl->t_emb = b.dmalloc((size_t)maxB * u->td);
     pl->ss = b.dmalloc((size_t)maxB * u->S);
-    const std::vector<int>& cs = u->chans;
     const int td = u->td, S = u->S, ncls = c.n_classes;
 
     // -- conditioning (unet.py:310-316 and every ResnetBlock.mlp) --
@@ -634,161 +737,12 @@ static int build_plan(fc_unet* u, Plan* pl, int maxB, int H, int W) {
         b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.fetch.all ? (int)FC_OK : ss_launch(te, wt, sb, ss, cx.B, td, S, s); }, "ss", 2.0 * (double)td * S);
     }
 
-    {   // small models: the whole forward of a sample in one workgroup (unet_sample.hip); 1 = does not qualify
-        const int r = build_sample_plan(u, pl, b, maxB, H, W);
-        if (r != 1) {
-            if (r != FC_OK) return r;
-            pl->maxB = maxB; pl->H = H; pl->W = W;
-            return FC_OK;
-        }
-    }
-    // -- init_conv (unet.py:295) and mask fusion (unet.py:298-305) --
-    Act x0 = b.act(dim, H, W);
-    pl->named["init"] = x0;
-    pl->x0 = x0;
-    Act mask_nhwc;
-    {
-        const float *w = u->P("init_conv.weight"), *bias = u->R("init_conv.bias");
-        float* x0p = x0.p;
-        b.scope = "init_conv";
-        if (!c.mask_cond) {
-            // (cx.step: the evaluation before this one has written x0 and fetched the conditioning slice -- conv_dev.h FL_STEP)
-            b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.step ? (int)FC_OK : init_conv_launch(cx.fetch, cx.x, cx.x_mod, w, bias, x0p, cx.B, ch, HW, dim, s); }, "init_conv", 2.0 * HW * ch * dim);
-        } else {
-            Act xi = b.act(dim, H, W), f1 = b.act(2 * dim, H, W), f2 = b.act(2 * dim, H, W);
-            const bool keep = u->keep_all;         // training keeps the pre-activations z1, z2 of the two SiLU layers
-            Act z1 = keep ? b.act(2 * dim, H, W) : Act(), z2 = keep ? b.act(2 * dim, H, W) : Act();
-            mask_nhwc = b.act(ch, H, W);
-            float *xip = xi.p, *mp = mask_nhwc.p;
-            b.push([=](const FwdCtx& cx, hipStream_t s) -> int {
-                if (cx.mask) FC_TRY(nchw_to_nhwc_launch(cx.mask, mp, cx.B, ch, HW, ch, cx.x_mod, s));
-                return init_conv_launch(cx.fetch, cx.x, cx.x_mod, w, bias, cx.mask_fuse ? xip : x0p, cx.B, ch, HW, dim, s);
-            }, "init_conv", 2.0 * HW * ch * dim);
-            ConvArgs a[3];
-            const char* names[3] = {"mask_fusion_conv.0", "mask_fusion_conv.2", "mask_fusion_conv.4"};
-            const Act* srcs[3] = {&xi, &f1, &f2};
-            const Act* dsts[3] = {keep ? &z1 : &f1, keep ? &z2 : &f2, &x0};
-            int tiles[3];
-            for (int i = 0; i < 3 && !b.err; ++i) {
-                a[i].s0.p = srcs[i]->p; a[i].s0.C = srcs[i]->C;
-                if (i == 0) { a[i].s1.p = mask_nhwc.p; a[i].s1.C = ch; }
-                a[i].Hs = H; a[i].Ws = W; a[i].KS = i == 0 ? 5 : 3; a[i].pad = i == 0 ? 2 : 1; a[i].out_act = (i < 2 && !keep);
-                a[i].w = u->P(std::string(names[i]) + ".weight"); a[i].bias = u->R(std::string(names[i]) + ".bias");
-                a[i].B = maxB; a[i].H = H; a[i].W = W; a[i].Cout = dsts[i]->C; a[i].out = dsts[i]->p; a[i].Cin = a[i].s0.C + a[i].s1.C;
-                ConvGeom g;
-                b.err = conv_plan(a[i], TILE_AUTO, &g);
-                tiles[i] = g.tile;
-            }
-            if (b.err) return b.err;
-            const ConvArgs a0 = a[0], a1 = a[1], a2 = a[2];
-            const int t0 = tiles[0], t1 = tiles[1], t2 = tiles[2];
-            const float *z1p = z1.p, *z2p = z2.p;
-            float *f1p = f1.p, *f2p = f2.p;
-            const size_t nf = (size_t)HW * 2 * dim;
-            b.scope = "mask_fusion_conv";
-            b.push([=](const FwdCtx& cx, hipStream_t s) -> int {
-                if (!cx.mask_fuse) return FC_OK;
-                ConvArgs q = a0; q.B = cx.B; FC_TRY(conv_launch(q, t0, s));
-                if (keep) FC_TRY(silu_fwd_launch(z1p, nullptr, f1p, nf * cx.B, s));
-                q = a1; q.B = cx.B; FC_TRY(conv_launch(q, t1, s));
-                if (keep) FC_TRY(silu_fwd_launch(z2p, nullptr, f2p, nf * cx.B, s));
-                q = a2; q.B = cx.B; return conv_launch(q, t2, s);
-            }, "mask_fusion(3 x conv_igemm)", 2.0 * HW * (25.0 * (dim + ch) * 2 * dim + 9.0 * 2 * dim * 2 * dim + 9.0 * 2 * dim * dim));
-            pl->fuse.present = true;
-            pl->fuse.xi = xi; pl->fuse.mask = mask_nhwc; pl->fuse.z1 = z1; pl->fuse.f1 = f1; pl->fuse.z2 = z2; pl->fuse.f2 = f2; pl->fuse.x0 = x0;
-        }
-    }
-
-    // -- down path (unet.py:326-343) --
-    std::vector<Act> skips;
-    Act x = x0;
-    for (int i = 0; i < L && !b.err; ++i) {
-        const std::string p = "downs." + std::to_string(i);
-        Stat gn1;
-        x = b.resblock(p + ".0", x, nullptr, cs[i], false, nullptr);
-        skips.push_back(x);
-        x = b.resblock(p + ".1", x, nullptr, cs[i], true, &gn1);
-        x = b.linattn(p + ".2", x, gn1);
-        skips.push_back(x);
-        if (c.mask_cond && i < 2) x = b.mask_inject("down_mask_fusions." + std::to_string(i) + ".0", x, mask_nhwc);
-        b.scope = p + ".3";
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W;
-        if (i == L - 1) {
-            a.KS = 3; a.pad = 1; a.w = u->P(p + ".3.weight"); a.bias = u->R(p + ".3.bias"); a.w4 = u->P8(p + ".3.weight");
-            Act o = b.act(cs[i + 1], x.H, x.W);
-            b.conv(a, o, 0, nullptr);
-            pl->tape.push_back({3, (int)pl->convs.size()});
-            pl->convs.push_back({p + ".3", x, o, 3, 1, 1, 0});
-            x = o;
-            pl->named[p + ".3"] = o;
-        } else {
-            a.KS = 2; a.pad = 0; a.stride = 2; a.w = u->P(p + ".3.1.weight"); a.bias = u->R(p + ".3.1.bias");
-            Act o = b.act(cs[i + 1], x.H / 2, x.W / 2);
-            b.conv(a, o, 0, nullptr);
-            pl->tape.push_back({3, (int)pl->convs.size()});
-            pl->convs.push_back({p + ".3.1", x, o, 2, 0, 2, 0});
-            x = o;
-            pl->named[p + ".3"] = o;
-        }
-    }
-    // -- bottleneck (unet.py:345-347) --
-    {
-        Stat gn1;
-        x = b.resblock("mid_block1", x, nullptr, cs[L], true, &gn1);
-        if (!b.err) x = b.midattn(x, gn1);
-        if (!b.err) x = b.resblock("mid_block2", x, nullptr, cs[L], false, nullptr);
-    }
-    // -- up path (unet.py:350-367) --
-    for (int i = 0; i < L && !b.err; ++i) {
-        const std::string p = "ups." + std::to_string(i);
-        const int din = cs[L - 1 - i], dout = cs[L - i];
-        Stat gn1;
-        Act s1 = skips.back(); skips.pop_back();
-        x = b.resblock(p + ".0", x, &s1, dout, false, nullptr);
-        Act s2 = skips.back(); skips.pop_back();
-        x = b.resblock(p + ".1", x, &s2, dout, true, &gn1);
-        x = b.linattn(p + ".2", x, gn1);
-        if (c.mask_cond && i < 2) x = b.mask_inject("up_mask_fusions." + std::to_string(i) + ".0", x, mask_nhwc);
-        b.scope = p + ".3";
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
-        if (i == L - 1) {
-            a.w = u->P(p + ".3.weight"); a.bias = u->R(p + ".3.bias"); a.w4 = u->P8(p + ".3.weight");
-            Act o = b.act(din, x.H, x.W);
-            b.conv(a, o, 0, nullptr);
-            pl->tape.push_back({3, (int)pl->convs.size()});
-            pl->convs.push_back({p + ".3", x, o, 3, 1, 1, 0});
-            x = o;
-        } else {  // nn.Upsample(nearest x2) folded into the conv's loader (unet.py:42-46)
-            Act o = b.act(din, x.H * 2, x.W * 2);
-            // (round 3) the upsampling folded into the WEIGHTS -- four 2x2 parity convolutions on x in one launch, 4/9 of the multiply-adds
-            // (plan.h conv_up2; FLOCODER_AMD_UPS_FOLD=0: off).  Training plans too: it is the same function of (x, w) up to fp32 rounding, and
-            // the backward differentiates it in its 3x3 form from the same saved x (flowers-sized step 6.49 -> 6.45 ms).
-            if (!b.conv_up2(a.s0, x, u->PUP(p + ".3.1.weight"), u->R(p + ".3.1.bias"), o, 0, nullptr)) {
-                a.ups = 1; a.w = u->P(p + ".3.1.weight"); a.bias = u->R(p + ".3.1.bias"); a.w4 = u->P8(p + ".3.1.weight");
-                b.conv(a, o, 0, nullptr);
-            }
-            pl->tape.push_back({3, (int)pl->convs.size()});
-            pl->convs.push_back({p + ".3.1", x, o, 3, 1, 1, 1});
-            x = o;
-        }
-        pl->named[p + ".3"] = x;
-    }
-    if (b.err) return b.err;
-    // -- head (unet.py:369-372) --
-    // final_res_block's closing launch may close the Euler sampler's step as well: final_conv, the update and the next evaluation's
-    // init_conv are pointwise per pixel (init_conv is a 1x1 convolution here), and the launch's tile holds every channel of its pixels
-    if (!c.mask_cond && dim == kStepDim && ch == kStepCh) b.step_out = x0;
-    x = b.resblock("final_res_block", x, &x0, dim, false, nullptr);
-    b.step_out = Act();
-    if (b.err) return b.err;
-    pl->head = x;
-    {
-        const float *xp = x.p, *w = u->P("final_conv.weight"), *bias = u->R("final_conv.bias");
-        b.scope = "final_conv";
-        b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.step ? (int)FC_OK : final_conv_launch(xp, w, bias, cx.out, cx.B, dim, HW, ch, cx.euler, s); }, "final_conv", 2.0 * HW * dim * ch);
-    }
+    WalkCfg walk;
+    walk.n_levels = L; walk.mask_cond = c.mask_cond != 0; walk.cs = u->chans;
+    // small models: the whole forward of a sample in one workgroup (unet_sample.hip); 1 = does not qualify
+    const int r = build_sample_plan(u, pl, b, walk, maxB, H, W);
+    if (r != FC_OK && r != 1) return r;
+    if (r == 1) walk_unet(walk, b);
     if (b.err) return b.err;
     pl->maxB = maxB; pl->H = H; pl->W = W;
     return FC_OK;

@@ -416,8 +416,6 @@ int build_backward(fc_unet* u) {
         b.s12p = b.dmalloc((size_t)B * m * 2);
     }
     b.dss = b.dmalloc((size_t)B * S);
-    float* redws = b.dmalloc(256);
-    (void)redws;
     if (b.err) return b.err;
     if (ncls > 0) {
         u->class_lo = b.off("class_cond_mlp.0.weight");
@@ -461,13 +459,10 @@ int build_backward(fc_unet* u) {
             for (int k = 0; k < bps.back() * B; ++k) blocks.push_back(make_int2((int)j, k));
             if (finalize_lds_bytes(f) > lds) lds = finalize_lds_bytes(f);
         }
-        FinalizeArgs* jd = reinterpret_cast<FinalizeArgs*>(b.dmalloc((b.fin_jobs.size() * sizeof(FinalizeArgs) + 3) / 4 + 4));
-        int* pd = reinterpret_cast<int*>(b.dmalloc(bps.size() + 4));
-        int2* bd = reinterpret_cast<int2*>(b.dmalloc(blocks.size() * 2 + 4));
+        const FinalizeArgs* jd = b.upload(b.fin_jobs);
+        const int* pd = b.upload(bps);
+        const int2* bd = b.upload(blocks);
         if (b.err) return b.err;
-        FC_HIP(hipMemcpy(jd, b.fin_jobs.data(), b.fin_jobs.size() * sizeof(FinalizeArgs), hipMemcpyHostToDevice));
-        FC_HIP(hipMemcpy(pd, bps.data(), bps.size() * sizeof(int), hipMemcpyHostToDevice));
-        FC_HIP(hipMemcpy(bd, blocks.data(), blocks.size() * sizeof(int2), hipMemcpyHostToDevice));
         const int nblk = (int)blocks.size();
         b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.B == B ? finalize_table_launch(jd, pd, bd, nblk, lds, s) : (int)FC_OK; }, "finalize_table");
     }
@@ -476,11 +471,9 @@ int build_backward(fc_unet* u) {
         BwdBuilder::WgradClass& wc = kv.second;
         if (wc.jobs.empty()) continue;
         b.scope = "wgrad";
-        WgradDev* jd = reinterpret_cast<WgradDev*>(b.dmalloc((wc.jobs.size() * sizeof(WgradDev) + 3) / 4 + 4));
-        int2* bd = reinterpret_cast<int2*>(b.dmalloc(wc.blocks.size() * 2 + 4));
+        const WgradDev* jd = b.upload(wc.jobs);
+        const int2* bd = b.upload(wc.blocks);
         if (b.err) return b.err;
-        FC_HIP(hipMemcpy(jd, wc.jobs.data(), wc.jobs.size() * sizeof(WgradDev), hipMemcpyHostToDevice));
-        FC_HIP(hipMemcpy(bd, wc.blocks.data(), wc.blocks.size() * sizeof(int2), hipMemcpyHostToDevice));
         const int nblk = (int)wc.blocks.size(), ks = kv.first;
         const size_t lds = wc.lds;
         double fl = 0;
@@ -497,51 +490,45 @@ int build_backward(fc_unet* u) {
             const size_t total = w.nw + (w.db >= 0 ? (size_t)w.nb : 0);
             for (size_t k = 0; k < (total + 63) / 64; ++k) blocks.push_back(make_int2((int)j, (int)k));
         }
-        WredJob* jd = reinterpret_cast<WredJob*>(b.dmalloc((b.wred_jobs.size() * sizeof(WredJob) + 3) / 4 + 4));
-        int2* bd = reinterpret_cast<int2*>(b.dmalloc(blocks.size() * 2 + 4));
+        const WredJob* jd = b.upload(b.wred_jobs);
+        const int2* bd = b.upload(blocks);
         if (b.err) return b.err;
-        FC_HIP(hipMemcpy(jd, b.wred_jobs.data(), b.wred_jobs.size() * sizeof(WredJob), hipMemcpyHostToDevice));
-        FC_HIP(hipMemcpy(bd, blocks.data(), blocks.size() * sizeof(int2), hipMemcpyHostToDevice));
         const int nblk = (int)blocks.size();
         b.push([=](const FwdCtx& cx, hipStream_t s) { return cx.B == B ? wgrad_reduce_table_launch(jd, bd, nblk, cx.grads, s, cx.grads_acc) : (int)FC_OK; }, "wgrad_reduce");
     }
     // -- parameter gradients of every norm layer and the FiLM gradients, one launch --
     if (!b.norm_jobs.empty()) {
         b.scope = "norms";
-        NormJob* jd = reinterpret_cast<NormJob*>(b.dmalloc((b.norm_jobs.size() * sizeof(NormJob) + 3) / 4 + 4));
+        const NormJob* jd = b.upload(b.norm_jobs);
         if (b.err) return b.err;
-        FC_HIP(hipMemcpy(jd, b.norm_jobs.data(), b.norm_jobs.size() * sizeof(NormJob), hipMemcpyHostToDevice));
         const int nj = (int)b.norm_jobs.size();
         int mc = 0;
         for (const NormJob& j : b.norm_jobs) if (j.C > mc) mc = j.C;
         float* dssp = b.dss;
         b.push([=](const FwdCtx& cx, hipStream_t s) { return norm_param_grads_table_launch(jd, nj, mc, cx.grads, dssp, S, cx.B, s, cx.grads_acc); }, "norm_param_grads");
     }
-        if (!b.film_blocks.empty()) {
-            b.scope = "resblock.mlp";
-            const float* te = te_film;
-            float* dss = b.dss;
-        {   // every block's mlp.1 weight / bias gradient: one table-driven launch
-            std::vector<DenseWJob> jobs;
-            std::vector<int2> blocks;
-            for (const std::string& p : b.film_blocks) {
-                const int rows = (int)u->params[u->pidx.at(p + ".mlp.1.bias")].numel;
-                jobs.push_back({u->ss_off.at(p), rows, b.off(p + ".mlp.1.weight"), b.off(p + ".mlp.1.bias")});
-                const int nb = cdiv(rows * td, 256);
-                for (int k = 0; k < nb; ++k) blocks.push_back(make_int2((int)jobs.size() - 1, k));
-            }
-            DenseWJob* jd = reinterpret_cast<DenseWJob*>(b.dmalloc((jobs.size() * sizeof(DenseWJob) + 3) / 4 + 4));
-            int2* bd = reinterpret_cast<int2*>(b.dmalloc(blocks.size() * 2 + 4));
-            if (b.err) return b.err;
-            FC_HIP(hipMemcpy(jd, jobs.data(), jobs.size() * sizeof(DenseWJob), hipMemcpyHostToDevice));
-            FC_HIP(hipMemcpy(bd, blocks.data(), blocks.size() * sizeof(int2), hipMemcpyHostToDevice));
-            const int nblk = (int)blocks.size();
-            b.push([=](const FwdCtx& cx, hipStream_t s) { return dense_bwd_w_table_launch(jd, bd, nblk, dss, S, te, 2, cx.grads, cx.B, td, s, cx.grads_acc); }, "dense_bwd_w");
+    // -- every block's mlp.1 weight / bias gradient: one table-driven launch --
+    if (!b.film_blocks.empty()) {
+        b.scope = "resblock.mlp";
+        const float* te = te_film;
+        float* dss = b.dss;
+        std::vector<DenseWJob> jobs;
+        std::vector<int2> blocks;
+        for (const std::string& p : b.film_blocks) {
+            const int rows = (int)u->params[u->pidx.at(p + ".mlp.1.bias")].numel;
+            jobs.push_back({u->ss_off.at(p), rows, b.off(p + ".mlp.1.weight"), b.off(p + ".mlp.1.bias")});
+            const int nb = cdiv(rows * td, 256);
+            for (int k = 0; k < nb; ++k) blocks.push_back(make_int2((int)jobs.size() - 1, k));
         }
-        }
-        b.fin_jobs.clear(); b.wclasses.clear(); b.wred_jobs.clear(); b.norm_jobs.clear(); b.film_blocks.clear();
-        b.pinned.clear();          // what the tables read may be recycled by later plan entries
-        return b.err;
+        const DenseWJob* jd = b.upload(jobs);
+        const int2* bd = b.upload(blocks);
+        if (b.err) return b.err;
+        const int nblk = (int)blocks.size();
+        b.push([=](const FwdCtx& cx, hipStream_t s) { return dense_bwd_w_table_launch(jd, bd, nblk, dss, S, te, 2, cx.grads, cx.B, td, s, cx.grads_acc); }, "dense_bwd_w");
+    }
+    b.fin_jobs.clear(); b.wclasses.clear(); b.wred_jobs.clear(); b.norm_jobs.clear(); b.film_blocks.clear();
+    b.pinned.clear();          // what the tables read may be recycled by later plan entries
+    return b.err;
     };
     // -- the tape in reverse --
     u->bwd_split_op = -1; u->grad_split = 0;
@@ -550,7 +537,7 @@ int build_backward(fc_unet* u) {
     const bool no_buckets = !u->want_buckets;
     for (int i = (int)fw.tape.size() - 1; i >= 0 && !b.err; --i) {
         const TapeItem& t = fw.tape[i];
-        if (t.kind == 0) {
+        if (t.kind == TAPE_RES) {
             b.resblock(fw.res[t.idx]);
             if (!no_buckets && fw.res[t.idx].p == "mid_block1" && u->has("ups.0.0.mlp.1.weight")) {
                 if (emit_deferred() != FC_OK) return b.err;
@@ -559,10 +546,9 @@ int build_backward(fc_unet* u) {
             }
             continue;
         }
-        if (false) b.resblock(fw.res[t.idx]);
-        else if (t.kind == 1) b.linattn(fw.lin[t.idx]);
-        else if (t.kind == 2) b.midattn(fw.mid[t.idx]);
-        else if (t.kind == 3) b.resample(fw.convs[t.idx]);
+        if (t.kind == TAPE_LIN) b.linattn(fw.lin[t.idx]);
+        else if (t.kind == TAPE_MID) b.midattn(fw.mid[t.idx]);
+        else if (t.kind == TAPE_CONV) b.resample(fw.convs[t.idx]);
         else b.inject(fw.inj[t.idx]);
     }
     if (b.err) return b.err;
