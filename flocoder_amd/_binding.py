@@ -186,6 +186,9 @@ SIGNATURES = {
     "fc_ot_plan_sinkhorn": (_i, [_vp, _vp, _i, _i64, C.c_double, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "fc_ot_sample_plan": (_i, [_vp, _i, _i, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fc_ot_plan_pairing": (_i, [_vp, _i, _vp, _vp]),
+    "fc_knn_workspace_bytes": (_i64, [_i, _i64, _i]),
+    "fc_knn_update": (_i, [_vp, _i, _vp, _i64, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "fc_knn_ball_counts": (_i, [_vp, _i, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

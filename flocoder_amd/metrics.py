@@ -11,6 +11,8 @@
 * ``calc_note_metrics`` (metrics.py:362-455, with ``targ_pred_mask_to_rgb`` / ``mask_to_rgb``, 330-340) -- onset / sustain sensitivity,
   specificity, precision and F1 of a piano roll against its target, and their images, from one streaming pass on the device
   (``fc_note_confusion``): exact int64 counts, ratios in fp64 on the host; ``region=`` restricts it to the pixels that were inpainted;
+* ``prdc`` -- improved precision / recall and density / coverage of a generated set against a real one from exact k-NN radii on the
+  device (``flocoder_amd.neighbors``; no upstream counterpart), optional in ``compute_sample_metrics`` (``prdc_k=``);
 * ``bits_per_dim`` -- the flow's log-likelihood (``sampling.log_likelihood``) as bits per latent dimension (no upstream counterpart);
   ``bits_per_dim_stderr`` -- its standard error from a K-probe call's ``logp_stderr``.
 """
@@ -279,10 +281,42 @@ def fid_score(real, fake, device='cuda', chunk=False, inception=None, chunk_size
     return frechet_distance(*stats[0].moments(), *stats[1].moments())
 
 
+# ------------------------------------------------------------------------------------------------ precision / recall / density / coverage
 @torch.no_grad()
-def compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_target, debug=False, inception=None):
+def prdc(real, fake, k=5):
+    """Improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) between the sample sets
+    ``real`` [N,...] and ``fake`` [M,...] (flattened per sample), on squared distances -- every comparison is monotone, so squared and
+    plain distances agree.  With r_real[i] the d2 of real i's k-th neighbour among the OTHER real rows, r_fake[j] likewise:
+
+        precision = mean_j [exists i: d2(fake_j, real_i) <= r_real[i]]      recall   = mean_i [exists j: d2(real_i, fake_j) <= r_fake[j]]
+        density   = sum_j #{i: d2(fake_j, real_i) <= r_real[i]} / (k M)     coverage = mean_i [min_j d2(real_i, fake_j) <= r_real[i]]
+
+    Five calls into ``flocoder_amd.neighbors`` (two self-``knn``, two ``ball_counts``, one cross ``knn`` with k = 1), exact and
+    deterministic; a set with fewer than k + 1 rows has radius +inf.  Nothing is read on the host until the four numbers are.  Returns
+    a dict of Python floats."""
+    from . import neighbors as NB
+    if not (real.is_cuda and fake.is_cuda):
+        raise RuntimeError("flocoder_amd.metrics.prdc runs on MI355X (gfx950) only; there is no CPU path")
+    n, m = real.shape[0], fake.shape[0]
+    if n < 1 or m < 1:
+        raise ValueError(f"prdc: both sets need at least one sample, got {n} and {m}")
+    dev = real.device
+    r_real = NB.knn(real, real, k, query_ids=torch.arange(n, device=dev))[0][:, k - 1].contiguous()
+    r_fake = NB.knn(fake, fake, k, query_ids=torch.arange(m, device=dev))[0][:, k - 1].contiguous()
+    in_real = NB.ball_counts(fake, real, r_real)                     # per fake sample: the real balls it lies in
+    in_fake = NB.ball_counts(real, fake, r_fake)
+    nearest_fake = NB.knn(real, fake, 1)[0][:, 0]
+    # exact integer counts, one fp64 division each: the numbers are count / size to the last bit
+    counts = torch.stack([(in_real > 0).sum(), (in_fake > 0).sum(), in_real.sum(dtype=torch.int64), (nearest_fake <= r_real).sum()]).double()
+    out = (counts / torch.tensor([m, n, k * m, n], dtype=torch.float64, device=dev)).tolist()
+    return dict(zip(('precision', 'recall', 'density', 'coverage'), out))
+
+
+@torch.no_grad()
+def compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_target, debug=False, inception=None, *, prdc_k=None):
     """metrics.py:493-555: the dictionary evaluate_model logs.  'FID_px' is present only when a local feature extractor is (it is
-    the one entry that needs third-party weights); everything else is computed unconditionally."""
+    the one entry that needs third-party weights); everything else is computed unconditionally.  Keyword-only ``prdc_k`` (an integer)
+    adds ``prdc/{precision,recall,density,coverage}`` of ``prdc(target_latents, pred_latents, prdc_k)``: the target latents are the real set."""
     n = min(pred_latents.shape[0], target_latents.shape[0])
     decoded_pred = normalize_recon(decoded_target, decoded_pred)
     out = {}
@@ -291,4 +325,6 @@ def compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_t
     out['sinkhorn'] = sinkhorn_loss(target_latents[:n], pred_latents[:n], device=pred_latents.device)
     out['sinkhorn_px'] = sinkhorn_loss(decoded_target, decoded_pred, device=decoded_pred.device)
     out.update(sample_stats(pred_latents, target_latents, decoded_pred, decoded_target))
+    if prdc_k is not None:
+        out.update({f'prdc/{key}': v for key, v in prdc(target_latents, pred_latents, prdc_k).items()})
     return out

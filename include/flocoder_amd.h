@@ -767,6 +767,29 @@ int fc_sinkhorn_divergence(const float* x_dev, const float* y_dev, int n, int m,
                            double diameter, double* value_out_host, double* diameter_out_host, int* iterations_out_host,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Nearest neighbours  (no upstream counterpart: exact k-NN over latent sets, the primitive under metrics.prdc)
+ * ---------------------------------------------------------------------------------------------- */
+/* d2(a, b) = sum_f (a_f - b_f)^2 in fp32 by direct differences, one accumulator per pair over the features in ascending order,
+ * acc = fma(a_f - b_f, a_f - b_f, acc): a function of the two vectors alone (the same bits whichever is the query and whichever tile,
+ * chunk, batch or call the pair falls in); a non-finite d2 is stored as FLT_MAX.  Neighbours are ordered by (d2, global reference
+ * index), ties to the lower index.  1 <= k <= 64, dim >= 1, 1 <= n_query <= 2^30, n_ref >= 0, first_index >= 0, else FC_E_SHAPE; null
+ * or misaligned pointers FC_E_ARG.  A dim that is not a multiple of 4, or q_dev / ref_dev not 16-byte aligned, takes scalar loads.
+ * Everything runs on `stream`, allocates nothing, reads nothing back and never waits for another workgroup.
+ *
+ * fc_knn_update merges the references ref_dev [n_ref][dim] of global indices first_index .. first_index + n_ref - 1 into the running
+ * lists best_d2_inout_dev / best_idx_inout_dev [n_query][k], ascending, empty slots (+inf, -1) -- which is how the caller initialises
+ * them.  query_ids_dev (may be NULL) [n_query]: the reference whose global index equals query_ids[q] is skipped for query q.  Any split
+ * of the references into calls, in any order, gives the same bits as one call.  ws_dev: 16-byte aligned, the workspace-bytes function's
+ * size for the same (n_query, n_ref, k).
+ * fc_knn_ball_counts: counts_inout_dev[q] += #{r : d2(q, r) <= radius2_dev[r]} over the same references (radius2_dev [n_ref], one per
+ * reference row of this call; integer atomics, so the result does not depend on their order). */
+int64_t fc_knn_workspace_bytes(int n_query, int64_t n_ref, int k);
+int fc_knn_update(const float* q_dev, int n_query, const float* ref_dev, int64_t n_ref, int64_t dim, int k, int64_t first_index,
+                  const int64_t* query_ids_dev, float* best_d2_inout_dev, int64_t* best_idx_inout_dev, void* ws_dev, void* stream);
+int fc_knn_ball_counts(const float* q_dev, int n_query, const float* ref_dev, int64_t n_ref, int64_t dim, const float* radius2_dev,
+                       int64_t first_index, const int64_t* query_ids_dev, int32_t* counts_inout_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
