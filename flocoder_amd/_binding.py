@@ -70,6 +70,7 @@ SIGNATURES = {
     "fc_debug_linattn_routes_read": (_i, [C.c_char_p, _i]),
     "fc_debug_step_routes_read": (_i, [C.c_char_p, _i]),
     "fc_debug_conv": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _pi, _pf, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _pf, _vp]),
+    "fc_debug_pack": (_i, [_i, _pi, _pi, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _vp]),
     "fc_debug_set_fused_tail": (_i, [_i]),
     "fc_unet_fused_tail_errors": (_i, [_vp, C.POINTER(_i)]),
     "fc_unet_set_shared": (_i, [_vp, _i]),

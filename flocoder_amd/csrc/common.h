@@ -123,12 +123,12 @@ struct ConvArgs {
     int Cin = 0, Cout = 0;
     int KS = 1, pad = 0, stride = 1, ups = 0;
     int w_batch_stride = 0;    // != 0: per-sample weights (w + b*stride), tiles then hold one sample
-    // the same weights in the k-step-quad layout [tap][Cin/8][half][Cout][4] (pack kind 6), or null: the 32-row tile at 3x3 loads its MFMA B
+    // the same weights in the k-step-quad layout [tap][Cin/8][half][Cout][4] (PACK_CONV_K8), or null: the 32-row tile at 3x3 loads its MFMA B
     // operands straight from it, 16 bytes per lane (conv_pipe.hip)
     const float* w4 = nullptr;
     const float* res_w4 = nullptr;
-    const float* w_b3 = nullptr;   // the weights as split bf16 (pack kind 8) or null: needed by prec == 1
-    // One parity class of "nearest x2 upsampling + 3x3" as a 2x2 convolution on the low-resolution input (pack kinds 9 / 10): the window
+    const float* w_b3 = nullptr;   // the weights as split bf16 (PACK_CONV_B3) or null: needed by prec == 1
+    // One parity class of "nearest x2 upsampling + 3x3" as a 2x2 convolution on the low-resolution input (PACK_UP4 / PACK_UP4_B3): the window
     // starts pad_y / pad_x above / left of the output pixel (-1: `pad` for both) and output pixel (y, x) of this launch's H x W grid is
     // pixel (2y + out_oy, 2x + out_ox) of a 2H x 2W image when out_sh = 1; its GroupNorm partials go to slot stats_toff of stats_tmul
     // launches that share one statistics tensor.
@@ -251,7 +251,7 @@ struct LaArgs {
     SrcXform xf;                   // mode 1, G = 1: statistics / gamma / beta of fn.norm
     const float* wqkv = nullptr;   // packed [C][3*128]
     const float* wout = nullptr;   // packed [128][C]
-    const float* wqkv4 = nullptr;  // wqkv in the k-step-quad layout [C/8][half][384][4] (pack kind 6) or null: the eight-wave la_head reads it
+    const float* wqkv4 = nullptr;  // wqkv in the k-step-quad layout [C/8][half][384][4] (PACK_CONV_K8) or null: the eight-wave la_head reads it
     const float* bout = nullptr;   // [C]
     float* ctx = nullptr;          // [B][4][32][32] scratch
     float* y = nullptr;            // NHWC [B][n][C]: to_out.0 output (before to_out.1's GroupNorm)
@@ -411,7 +411,61 @@ int rk45_status_launch(const Rk45Groups& g, const Rk45State* st, Rk45Status* out
 int rk45_out_launch(const double* y, float* x, int n, hipStream_t s);
 
 // ---- weight packing (pack.hip) ----------------------------------------------------------------
-struct PackJob { const float* src; float* dst; int kind, a, b, c, d, e; size_t total; };
+// The layouts the kernels read their weights in, each made from a state_dict tensor by one job of the table kernel.  `w` is a convolution
+// weight [O][I][KH][KW] with tap = ky * KW + kx and KK = KH * KW; w(o, ci, tap) = src[(o * I + ci) * KK + tap].  A job moves `total`
+// elements, element t to the place given below; the dimensions are the arguments of the layout's constructor.
+enum PackKind : int {
+    // dst[tap][ci][o] = w(o, ci, tap): the implicit GEMM's B operand, [KK][I][O].                                         (O, I, KK)
+    PACK_CONV,
+    // Downsample (unet.py:52-53): Rearrange 'b c (h p1) (w p2) -> b (c p1 p2) h w' and a 1x1 convolution over 4C channels, src [O][4C], as
+    // a 2x2 stride-2 convolution over C channels: dst[tap = 2 p1 + p2][c][o] = src[o][4 c + tap].                          (O, C)
+    PACK_S2D,
+    // a Linear [R = out][Cc = in] transposed into columns col0 .. col0 + R of a matrix of leading dimension ld:
+    // dst[c * ld + col0 + r] = src[r][c].                                                                                 (R, Cc, ld, col0)
+    PACK_TRANSPOSE,
+    // dst[t] = src[t] for n floats (a bias into a slice of a concatenated or zero-padded vector).                         (n)
+    PACK_COPY,
+    // PACK_CONV over [KK][Ipad][Opad], exact zeros where o >= O or ci >= I (RGB ends of the codecs).                      (O, I, KK, Opad, Ipad)
+    PACK_CONV_PAD,
+    // data-gradient operand of a stride-1 KS x KS convolution, for input channels ci0 .. ci0 + nci: the forward kernel run on dY with
+    // dst[(KS-1-ky) * KS + (KS-1-kx)][o][i - ci0] = w[o][i][ky][kx] ([taps][Cin' = O][Cout' = nci]) and padding KS-1-pad yields that
+    // slice of dX (a slice, so that the two sources of a channel concatenation get their gradients from two launches).   (O, I, KS, ci0, nci)
+    PACK_DGRAD,
+    // k-step quads, I % 8 == 0: dst[tap][c8][half][o][jj] = w(o, 8 c8 + 2 jj + half, tap), [KK][I/8][2][O][4] -- the MFMA B operands of
+    // four consecutive k-steps of one lane as ONE 16-byte load (conv_pipe.hip, register-fed weights; ConvArgs::w4).       (O, I, KK)
+    PACK_CONV_K8,
+    // split bf16, Ipad % 8 == 0: two arrays of 16-bit values, the hi parts and then the lo parts, each [KK][Ipad/8][O][8] with
+    // [tap][c8][o][jj] = part of w(o, 8 c8 + jj, tap), zero where the channel is >= I; x = hi + lo, hi = bf16(x) to nearest even,
+    // lo = bf16(x - hi).  The B operand of v_mfma_f32_32x32x16_bf16 for one column and eight channels is 16 contiguous bytes and a 64-column
+    // row of one (tap, c8) one 1 KiB LDS-DMA piece (ConvArgs::w_b3).  `total` counts the elements of ONE part.            (O, I, KK, Ipad)
+    PACK_CONV_B3,
+    // nearest x2 upsampling folded into a 3x3 convolution (unet.py:42-46, SD-VAE Upsample2D): output pixel (2y + a, 2x + b) reads a 2x2
+    // window of the low-resolution tensor, each pixel through the SUM of the 3x3 taps that land on it -- rows {ky} for window row ty:
+    // a = 0: {0}, {1, 2}; a = 1: {0, 1}, {2}; columns likewise -- added in fp32, ky outer, kx inner, from 0.  Four 2x2 kernels:
+    // dst[parity = 2 a + b][tap = 2 ty + tx][ci][o], 16 taps instead of 36 per 2x2 output block.                          (O, I)
+    PACK_UP4,
+    // the same sums in the form of PACK_CONV_B3 with KK = 4, per parity: [parity][hi | lo][tap][c8][o][jj].               (O, I, Ipad)
+    PACK_UP4_B3,
+    PACK_KINDS
+};
+// One constructor per layout, taking its dimensions in the order listed above and filling `total`; at() gives the job its pointers.
+struct PackJob {
+    const float* src; float* dst; PackKind kind; int a, b, c, d, e; size_t total;
+    PackJob at(const float* s, float* d_) const { PackJob j = *this; j.src = s; j.dst = d_; return j; }
+};
+inline PackJob pack_spec(PackKind k, size_t total, int a, int b = 0, int c = 0, int d = 0, int e = 0) {
+    return PackJob{nullptr, nullptr, k, a, b, c, d, e, total};
+}
+inline PackJob pack_job_conv(int O, int I, int KK) { return pack_spec(PACK_CONV, (size_t)O * I * KK, O, I, KK); }
+inline PackJob pack_job_s2d(int O, int C) { return pack_spec(PACK_S2D, (size_t)O * C * 4, O, C); }
+inline PackJob pack_job_transpose(int R, int Cc, int ld, int col0) { return pack_spec(PACK_TRANSPOSE, (size_t)R * Cc, R, Cc, ld, col0); }
+inline PackJob pack_job_copy(int n) { return pack_spec(PACK_COPY, (size_t)n, n); }
+inline PackJob pack_job_conv_pad(int O, int I, int KK, int Opad, int Ipad) { return pack_spec(PACK_CONV_PAD, (size_t)Opad * Ipad * KK, O, I, KK, Opad, Ipad); }
+inline PackJob pack_job_dgrad(int O, int I, int KS, int ci0, int nci) { return pack_spec(PACK_DGRAD, (size_t)O * nci * KS * KS, O, I, KS, ci0, nci); }
+inline PackJob pack_job_conv_k8(int O, int I, int KK) { return pack_spec(PACK_CONV_K8, (size_t)O * I * KK, O, I, KK); }
+inline PackJob pack_job_conv_b3(int O, int I, int KK, int Ipad) { return pack_spec(PACK_CONV_B3, (size_t)O * Ipad * KK, O, I, KK, Ipad); }
+inline PackJob pack_job_up4(int O, int I) { return pack_spec(PACK_UP4, (size_t)16 * O * I, O, I); }
+inline PackJob pack_job_up4_b3(int O, int I, int Ipad) { return pack_spec(PACK_UP4_B3, (size_t)16 * O * Ipad, O, I, Ipad); }
 constexpr int kPackPerBlock = 4096;          // elements a workgroup of the table kernel moves
 struct PackTable {                            // device-resident job list + (job, block) map of one batched launch
     PackJob* jobs = nullptr;
@@ -419,24 +473,12 @@ struct PackTable {                            // device-resident job list + (job
     int nblocks = 0;
     void release();
 };
-int pack_conv_launch(const float* oihw, float* dst /*[KK][I][O]*/, int O, int I, int KH, int KW, hipStream_t s);
-// k-step-quad layout [KK][I/8][half][O][4] (I % 8 == 0): ConvArgs::w4
-int pack_conv_k8_launch(const float* oihw, float* dst, int O, int I, int KK, hipStream_t s);
-// split-bf16 copy: hi parts then lo parts, each [KK][Ipad/8][O][8] 16-bit values (Ipad a multiple of 16; KK * Ipad * O floats in all): ConvArgs::w_b3
-int pack_conv_b3_launch(const float* oihw, float* dst, int O, int I, int KK, int Ipad, hipStream_t s);
-// same with zero padding of either channel count: dst [KK][Ipad][Opad]
-int pack_conv_pad_launch(const float* oihw, float* dst, int O, int I, int KK, int Opad, int Ipad, hipStream_t s);
-// operand of the data-gradient pass (forward kernel on dY): [taps flipped][O][nci] for input channels ci0..ci0+nci
-int pack_conv_dgrad_launch(const float* oihw, float* dst, int O, int I, int KS, int ci0, int nci, hipStream_t s);
-int pack_table_build(std::vector<PackJob> jobs, PackTable* out);   // uploads; the table keeps raw device pointers of src / dst
+int pack_table_build(const std::vector<PackJob>& jobs, PackTable* out);   // uploads; the table keeps raw device pointers of src / dst
 int pack_table_launch(const PackTable& t, hipStream_t s);
 // [B][rows][cols] -> [B][cols][rows]
 int transpose_batched_launch(const float* src, float* dst, int B, int rows, int cols, hipStream_t s);
 // in place: x[r][:] = softmax(scale * x[r][:]) for `rows` rows of `cols` floats
 int softmax_rows_launch(float* x, long rows, int cols, float scale, hipStream_t s);
-int pack_s2d_conv_launch(const float* oi, float* dst /*[4][C][O]*/, int O, int C, hipStream_t s);  // Downsample: (c p1 p2) -> 2x2 s2
-int pack_transpose_launch(const float* src /*[R][Cc]*/, float* dst /*[Cc][R]*/, int R, int Cc, int dst_ld, int dst_col0,
-                          hipStream_t s);
 
 // ---- training step (conv_wgrad.hip, backward.hip) ----------------------------------------------
 struct WgradArgs {          // dW[co][ci][ky][kx] (+ db[co]) of a convolution from its input and its output gradient

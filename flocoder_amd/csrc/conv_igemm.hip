@@ -308,7 +308,7 @@ static int conv_geometry(const ConvArgs& a, int tile, bool pipe, ConvDev* d, Con
         // M32N32K4 at 3x3 loads its weights global -> registers (conv_pipe.hip "DB"): no slab stages in LDS
         const bool direct_b = (t.WMWN == 1 && t.MTNT == 1 && a.KS == 3);
         // split-bf16 form (ConvArgs::prec): where an instantiation exists (conv_bf3_form), plain launches only (no fused res_conv / tail,
-        // shared weights) whose weights exist pre-split (ConvArgs::w_b3, pack kind 8)
+        // shared weights) whose weights exist pre-split (ConvArgs::w_b3, PACK_CONV_B3)
         p.bf3 = (a.prec == 1 && a.w_b3 && conv_bf3_form(tile, a.KS) && !a.res_out && !a.fin.gamma && !a.w_batch_stride) ? 1 : 0;
         p.patch_stride = align4(p.P * (t.CC + ((direct_b || p.bf3) ? 4 : 1)));    // (its k-step-quad form strides pixels by CC + 4 floats, and so does split-bf16)
         p.o_wl = o + 2 * p.patch_stride;

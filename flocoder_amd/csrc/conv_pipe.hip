@@ -88,7 +88,7 @@ __device__ __forceinline__ void loader_handover() {   // LDS stores of this wave
 // PREC = 1: split-bf16 arithmetic (round 3, codec decoders on request -- never the U-Net, never a default): every fp32 operand x is taken as
 // hi + lo with hi = bf16(x), lo = bf16(x - hi), and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 (fp32 accumulation; the
 // dropped lo*lo term is 2^-16 relative).  Three MFMAs of 32 cycles cover sixteen channels where the exact-fp32 pipe needs eight of 64: 5.3x
-// the matrix rate.  Nobody splits inside the accumulator waves' loop: the weights are split once, when the parameters are packed (pack kind 8,
+// the matrix rate.  Nobody splits inside the accumulator waves' loop: the weights are split once, when the parameters are packed (PACK_CONV_B3,
 // ConvArgs::w_b3) and reach LDS by the same LDS-DMA pieces as the fp32 slab; the window is split by the staging waves on its way into LDS
 // (a pixel is read by up to nine taps).  The accumulator waves read 16-byte hi / lo operands and issue MFMAs.  The epilogue is the fp32 kernel's.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
     // straight into the MFMA B register layout (two 128-byte row segments per wave load), one chunk ahead, and the loaders keep
     // only the input window.
     constexpr bool DB = (WM * WN == 1 && MT == 1 && NT == 1 && KS == 3);
-    // DB4 (round 3): the same with the weights in the k-step-quad layout (pack kind 6): a lane's B operands of the four k-steps its wave
+    // DB4 (round 3): the same with the weights in the k-step-quad layout (PACK_CONV_K8): a lane's B operands of the four k-steps its wave
     // owns in a chunk are ONE 16-byte load per tap (nine loads per chunk instead of 36, uniform base + 32-bit lane offset), and the two
     // register sets swap roles from chunk to chunk instead of being copied.  The copy was the round-2 kernel's hidden stall: the compiler
     // moved `wcur = wnxt` up to the last use of each wcur register, and every such move waits for a load issued moments earlier --
@@ -450,7 +450,7 @@ __global__ void __launch_bounds__(256 + 64 * NL) conv_pipe_kernel(const ConvDev 
             const int j = lw + NL * m, f = j * 256 + lane * 4, row = f / BN, n = n0 + (f % BN);
             if constexpr (BF3) {
                 // split-bf16 slab [part hi/lo][tap][channel block of 8 (two per chunk)][BN] x 16 bytes, read from the pre-split copy of the
-                // weights (pack kind 8: per part [tap][Ipad/8][Cout] x 16 bytes, Ipad = 16 nchunks, zero beyond Cin): one lane, one column's
+                // weights (PACK_CONV_B3: per part [tap][Ipad/8][Cout] x 16 bytes, Ipad = 16 nchunks, zero beyond Cin): one lane, one column's
                 // eight channels.  Same byte count per chunk as the fp32 slab, so the piece bookkeeping is shared
                 const int e = j * 64 + lane, r = e / BN, nn = n0 + e % BN, part = r / (2 * KK), tap = (r >> 1) % KK, c8l = r & 1;
                 d_row[m] = 0;

@@ -313,7 +313,7 @@ __global__ void __launch_bounds__(256) la_head_kernel(const LaArgs a) {
 // ---- eight-wave form (round 4) ------------------------------------------------------------------------------------------------
 // The same module with 512 threads: the q / k / v projections are K-split over two waves each (waves 0-2: channels [0, C/2), waves 3-5:
 // [C/2, C)), the halves meet in LDS; waves 6-7 bring the head's rows of to_out.0 into LDS.  The weights come from the k-step-quad copy
-// (pack kind 6: a lane's B operands of four k-steps are ONE 16-byte load, four loads per round of 16 k-steps instead of sixteen), two
+// (PACK_CONV_K8: a lane's B operands of four k-steps are ONE 16-byte load, four loads per round of 16 k-steps instead of sixteen), two
 // register sets swapping roles.  Why: with four waves a (sample, head) workgroup -- the only one on its CU -- ran the projections on
 // three waves of one SIMD each, 4 KB of weights in flight per wave, and the phase took 9.3 of the kernel's ~15 us for 3.4 us of matrix
 // work (round-3 knock-outs): it waits for weights.  Twice the waves stream twice the bytes at a time and halve the dependent MFMA chain.

@@ -83,8 +83,7 @@ struct Plan {                 // one launch plan + activation arena for up to ma
     }
 };
 
-struct PackOp { int kind; int64_t src, dst; int a, b, c, d, e = 0; };
-// kind 0 conv OIHW(O=a,I=b,KH=c,KW=d), 1 s2d, 2 transpose(R=a,Cc=b,ld=c,col0=d), 3 copy(a floats), 4 conv with channel padding(O=a,I=b,KK=c,Opad=d,Ipad=e)
+struct PackOp { int64_t src, dst; PackJob job; };   // a job whose pointers are still offsets into `raw` / `packed` (until alloc_device)
 
 static const char* const kTileNames[] = {"conv_igemm<M128,N32>", "conv_igemm<M128,N64>", "conv_igemm<M64,N32,K2>", "conv_igemm<M32,N32,K4>",
                                          "conv_igemm<M64,N64,K2>", "conv_igemm<M256,N64>"};
@@ -101,13 +100,13 @@ struct ParamStore {
     PackTable pack_table;                          // all of `packops` as one launch
     bool loaded = false;
 
-    bool want_b3 = false;   // also keep 3x3 / 1x1 conv weights as split bf16 (pack kind 8): the codecs, for their opt-in split-bf16 arithmetic
+    bool want_b3 = false;   // also keep 3x3 / 1x1 conv weights as split bf16 (PACK_CONV_B3): the codecs, for their opt-in split-bf16 arithmetic
     std::unordered_map<int64_t, int64_t> b3_of;   // packed offset of a weight -> packed offset of its split-bf16 copy
     const float* B3(const float* w) const {         // the split-bf16 copy of packed weight pointer `w`, or null
         auto it = b3_of.find(w - packed);
         return it == b3_of.end() ? nullptr : packed + it->second;
     }
-    bool want_k8 = false;   // also keep 3x3 / 1x1 conv weights in the k-step-quad layout (pack kind 6) where the shapes allow: the U-Net's low-resolution layers
+    bool want_k8 = false;   // also keep 3x3 / 1x1 conv weights in the k-step-quad layout (PACK_CONV_K8) where the shapes allow: the U-Net's low-resolution layers
     // the k-step-quad copy of a convolution weight, or null when there is none
     const float* P8(const std::string& n) const { auto it = pk.find(n + "#k8"); return it == pk.end() ? nullptr : packed + it->second; }
     const float* R(const std::string& n) const { return raw + params[pidx.at(n)].offset; }
@@ -131,31 +130,46 @@ struct ParamStore {
         packed_numel += (numel + 3) & ~3ll;
         return off;
     }
+    int64_t off(const std::string& n) const { return params[pidx.at(n)].offset; }
+    // parameter `n` goes, laid out as `job` says, to offset `dst` of `packed`
+    void pack(const std::string& n, int64_t dst, const PackJob& job) { packops.push_back(PackOp{off(n), dst, job}); }
     void decl_conv(const std::string& n, int O, int I, int K, bool bias = true) {
         declare(n + ".weight", {O, I, K, K});
         if (bias) declare(n + ".bias", {O});
         const int64_t dst = pk_alloc(n + ".weight", (int64_t)O * I * K * K);
-        packops.push_back({0, params[pidx[n + ".weight"]].offset, dst, O, I, K, K});
+        pack(n + ".weight", dst, pack_job_conv(O, I, K * K));
         if (want_b3 && (K == 3 || K == 1)) {
             const int Ipad = (I + 15) / 16 * 16;
             const int64_t d3 = pk_alloc(n + ".weight#b3", (int64_t)O * Ipad * K * K);
-            packops.push_back({8, params[pidx[n + ".weight"]].offset, d3, O, I, K * K, Ipad});
+            pack(n + ".weight", d3, pack_job_conv_b3(O, I, K * K, Ipad));
             b3_of[dst] = d3;
         }
-        if (want_k8 && (K == 3 || K == 1) && I % 32 == 0 && O % 32 == 0) {
-            const int64_t d8 = pk_alloc(n + ".weight#k8", (int64_t)O * I * K * K);
-            packops.push_back({6, params[pidx[n + ".weight"]].offset, d8, O, I, K * K, 0});
-        }
+        if (want_k8 && (K == 3 || K == 1) && I % 32 == 0 && O % 32 == 0)
+            pack(n + ".weight", pk_alloc(n + ".weight#k8", (int64_t)O * I * K * K), pack_job_conv_k8(O, I, K * K));
     }
-    // a 3x3 convolution behind nn.Upsample(nearest, x2): besides the plain packed copy, the four parity kernels of the folded form (pack kinds 9 / 10)
+    // Conv2d whose channel counts need not be multiples of 4 (the pixel-space ends of the codecs): operands zero-padded to Opad / Ipad;
+    // `packed_bias`: the bias too, copied into a zero-initialised packed slot of Opad floats (P(n + ".bias"))
+    void decl_conv_pad(const std::string& n, int O, int I, int K, int Opad, int Ipad, bool packed_bias) {
+        declare(n + ".weight", {O, I, K, K});
+        declare(n + ".bias", {O});
+        pack(n + ".weight", pk_alloc(n + ".weight", (int64_t)Opad * Ipad * K * K), pack_job_conv_pad(O, I, K * K, Opad, Ipad));
+        if (packed_bias) pack(n + ".bias", pk_alloc(n + ".bias", Opad), pack_job_copy(O));
+    }
+    // Downsample's 1x1 convolution over the space-to-depth rearrangement, [O][4C][1][1], as a 2x2 stride-2 convolution (PACK_S2D)
+    void decl_conv_s2d(const std::string& n, int O, int C) {
+        declare(n + ".weight", {O, 4 * C, 1, 1});
+        declare(n + ".bias", {O});
+        pack(n + ".weight", pk_alloc(n + ".weight", (int64_t)O * 4 * C), pack_job_s2d(O, C));
+    }
+    // a 3x3 convolution behind nn.Upsample(nearest, x2): besides the plain packed copy, the four parity kernels of the folded form (PACK_UP4 / PACK_UP4_B3)
     void decl_conv_up2(const std::string& n, int O, int I) {
         decl_conv(n, O, I, 3);
         const int64_t d4 = pk_alloc(n + ".weight#up4", (int64_t)16 * O * I);
-        packops.push_back({9, params[pidx[n + ".weight"]].offset, d4, O, I, 9, 0});
+        pack(n + ".weight", d4, pack_job_up4(O, I));
         if (want_b3) {
             const int Ipad = (I + 15) / 16 * 16;
             const int64_t d3 = pk_alloc(n + ".weight#up4b3", (int64_t)16 * O * Ipad);
-            packops.push_back({10, params[pidx[n + ".weight"]].offset, d3, O, I, 9, Ipad});
+            pack(n + ".weight", d3, pack_job_up4_b3(O, I, Ipad));
             for (int par = 0; par < 4; ++par) b3_of[d4 + (int64_t)par * 4 * O * I] = d3 + (int64_t)par * 4 * O * Ipad;
         }
     }
@@ -163,12 +177,15 @@ struct ParamStore {
         auto it = pk.find(n + "#up4");
         return it == pk.end() ? nullptr : packed + it->second;
     }
-    void decl_linear_t(const std::string& n, int O, int I) {  // stored transposed [I][O]
+    void decl_linear_t(const std::string& n, int O, int I, bool bias = true) {  // stored transposed [I][O]
         declare(n + ".weight", {O, I});
-        declare(n + ".bias", {O});
-        const int64_t dst = pk_alloc(n + ".weight", (int64_t)O * I);
-        packops.push_back({2, params[pidx[n + ".weight"]].offset, dst, O, I, O, 0});
+        if (bias) declare(n + ".bias", {O});
+        pack(n + ".weight", pk_alloc(n + ".weight", (int64_t)O * I), pack_job_transpose(O, I, O, 0));
     }
+    // parameter `n` into a slice of the named packed buffer `buf`: a Linear [R][Cc] transposed into columns col0 .. col0 + R of its rows of
+    // ld floats; a vector of R floats copied to elements col0 .. col0 + R
+    void pack_transpose_into(const std::string& buf, const std::string& n, int R, int Cc, int ld, int col0) { pack(n, pk.at(buf), pack_job_transpose(R, Cc, ld, col0)); }
+    void pack_copy_into(const std::string& buf, const std::string& n, int R, int col0) { pack(n, pk.at(buf) + col0, pack_job_copy(R)); }
     void decl_norm(const std::string& n, int C) {
         declare(n + ".weight", {C});
         declare(n + ".bias", {C});
@@ -178,7 +195,7 @@ struct ParamStore {
         FC_TRY(dev_alloc(reinterpret_cast<void**>(&packed), (size_t)(packed_numel ? packed_numel : 4) * sizeof(float), "params.packed"));
         FC_HIP(hipMemset(raw, 0, (size_t)(raw_numel ? raw_numel : 4) * sizeof(float)));
         std::vector<PackJob> jobs;
-        for (const PackOp& o : packops) jobs.push_back({raw + o.src, packed + o.dst, o.kind, o.a, o.b, o.kind == 0 ? o.c * o.d : o.c, o.d, o.e, 0});
+        for (const PackOp& o : packops) jobs.push_back(o.job.at(raw + o.src, packed + o.dst));
         return pack_table_build(jobs, &pack_table);
     }
     void free_device() {
@@ -187,22 +204,7 @@ struct ParamStore {
         if (packed) dev_free(packed);
         raw = packed = nullptr;
     }
-    int run_pack(hipStream_t s) const {
-        if (pack_table.nblocks) return pack_table_launch(pack_table, s);
-        for (const PackOp& o : packops) {
-            const float* src = raw + o.src;
-            float* dst = packed + o.dst;
-            switch (o.kind) {
-                case 0: FC_TRY(pack_conv_launch(src, dst, o.a, o.b, o.c, o.d, s)); break;
-                case 1: FC_TRY(pack_s2d_conv_launch(src, dst, o.a, o.b, s)); break;
-                case 2: FC_TRY(pack_transpose_launch(src, dst, o.a, o.b, o.c, o.d, s)); break;
-                case 3: FC_HIP(hipMemcpyAsync(dst, src, (size_t)o.a * sizeof(float), hipMemcpyDeviceToDevice, s)); break;
-                case 4: FC_TRY(pack_conv_pad_launch(src, dst, o.a, o.b, o.c, o.d, o.e, s)); break;
-                case 6: return fail(FC_E_STATE, "pack: the k-step-quad layout exists in the table launch only");
-            }
-        }
-        return FC_OK;
-    }
+    int run_pack(hipStream_t s) const { return pack_table_launch(pack_table, s); }
     // flat fp32 vector in table order (padded layout) -> raw -> packed
     int load(const float* flat, int64_t numel, int on_device, hipStream_t s) {
         if (numel != raw_numel) return fail(FC_E_ARG, "load_params: expected " + std::to_string(raw_numel) + " floats (padded table layout)");

@@ -88,12 +88,7 @@ static int declare_all(fc_unet* u) {
         decl_resblock(u, p + ".1", cs[i], cs[i]);
         decl_linattn(u, p + ".2", cs[i]);
         if (i == L - 1) decl_conv(u, p + ".3", cs[i + 1], cs[i], 3);
-        else {
-            declare(u, p + ".3.1.weight", {cs[i + 1], 4 * cs[i], 1, 1});
-            declare(u, p + ".3.1.bias", {cs[i + 1]});
-            const int64_t dst = pk_alloc(u, p + ".3.1.weight", (int64_t)cs[i + 1] * 4 * cs[i]);
-            u->packops.push_back({1, u->params[u->pidx[p + ".3.1.weight"]].offset, dst, cs[i + 1], cs[i], 0, 0});
-        }
+        else u->decl_conv_s2d(p + ".3.1", cs[i + 1], cs[i]);
     }
     for (int i = 0; i < L; ++i) {  // unet.py:265-281, (dim_in, dim_out) = reversed(in_out)[i]
         const std::string p = "ups." + std::to_string(i);
@@ -116,10 +111,9 @@ static int declare_all(fc_unet* u) {
     pk_alloc(u, "__ss_wt", (int64_t)u->td * u->S);
     pk_alloc(u, "__ss_bias", u->S);
     for (auto& kv : u->ss_off) {
-        const Param& w = u->params[u->pidx[kv.first + ".mlp.1.weight"]];
-        const Param& b = u->params[u->pidx[kv.first + ".mlp.1.bias"]];
-        u->packops.push_back({2, w.offset, u->pk["__ss_wt"], (int)w.shape[0], u->td, u->S, kv.second});
-        u->packops.push_back({3, b.offset, u->pk["__ss_bias"] + kv.second, (int)b.numel, 0, 0, 0});
+        const int n = (int)u->params[u->pidx[kv.first + ".mlp.1.bias"]].numel;     // 2 * cout
+        u->pack_transpose_into("__ss_wt", kv.first + ".mlp.1.weight", n, u->td, u->S, kv.second);
+        u->pack_copy_into("__ss_bias", kv.first + ".mlp.1.bias", n, kv.second);
     }
     return FC_OK;
 }
@@ -1139,23 +1133,22 @@ int fc_debug_conv(const float* src0, int c0, const float* src1, int c1, const fl
     a.bias = bias; a.add = add; a.out = out; a.out_act = out_act;
     a.stats_out = stats_out; a.Gout = groups_out;
     a.prec = g_debug_conv_prec;
+    // the weights as a plan would carry them, packed by the plans' own packer: one buffer, one transient table of one to three jobs
+    const int KK = ksize * ksize, ipad = (a.Cin + 15) / 16 * 16;
+    const bool k8 = ksize == 3 && a.Cin % 32 == 0 && cout % 32 == 0;    // the k-step-quad copy where the shapes allow it (conv_pipe.hip FL_W4)
+    const bool b3 = a.prec == 1 && ksize >= 1 && ksize <= 3;            // the split-bf16 copy when that arithmetic is asked for (the kernel sizes of conv_bf3_form)
+    const size_t n = ((size_t)cout * a.Cin * KK + 63) & ~(size_t)63, n3 = (size_t)cout * ipad * KK;    // each copy 256-byte aligned
     float* wp = nullptr;
-    FC_HIP(hipMalloc(reinterpret_cast<void**>(&wp), (size_t)cout * a.Cin * ksize * ksize * sizeof(float)));
-    int r = pack_conv_launch(w_oihw, wp, cout, a.Cin, ksize, ksize, s);
+    FC_HIP(hipMalloc(reinterpret_cast<void**>(&wp), (n + (k8 ? n : 0) + (b3 ? n3 : 0)) * sizeof(float)));
+    float* const wp8 = wp + n;
+    float* const wp3 = wp8 + (k8 ? n : 0);
+    std::vector<PackJob> jobs{pack_job_conv(cout, a.Cin, KK).at(w_oihw, wp)};
     a.w = wp;
-    float* wp8 = nullptr;       // the k-step-quad copy where the shapes allow it, as a U-Net plan would carry it (conv_pipe.hip FL_W4)
-    if (r == FC_OK && ksize == 3 && a.Cin % 32 == 0 && cout % 32 == 0) {
-        FC_HIP(hipMalloc(reinterpret_cast<void**>(&wp8), (size_t)cout * a.Cin * 9 * sizeof(float)));
-        r = pack_conv_k8_launch(w_oihw, wp8, cout, a.Cin, 9, s);
-        a.w4 = wp8;
-    }
-    float* wp3 = nullptr;       // ... and the split-bf16 copy when that arithmetic is asked for, as a codec plan would (pack kind 8)
-    if (r == FC_OK && a.prec == 1 && ksize >= 1 && ksize <= 3) {        // (the kernel sizes of conv_bf3_form)
-        const int ipad = (a.Cin + 15) / 16 * 16;
-        FC_HIP(hipMalloc(reinterpret_cast<void**>(&wp3), (size_t)cout * ipad * ksize * ksize * sizeof(float)));
-        r = pack_conv_b3_launch(w_oihw, wp3, cout, a.Cin, ksize * ksize, ipad, s);
-        a.w_b3 = wp3;
-    }
+    if (k8) { a.w4 = wp8; jobs.push_back(pack_job_conv_k8(cout, a.Cin, KK).at(w_oihw, wp8)); }
+    if (b3) { a.w_b3 = wp3; jobs.push_back(pack_job_conv_b3(cout, a.Cin, KK, ipad).at(w_oihw, wp3)); }
+    PackTable table;
+    int r = pack_table_build(jobs, &table);
+    if (r == FC_OK) r = pack_table_launch(table, s);
     ConvGeom g;
     if (r == FC_OK) r = conv_plan(a, tile_cfg, &g);
     if (r == FC_OK) { if (stats_T) *stats_T = g.T; if (stats_nt) *stats_nt = g.n_t; r = conv_launch(a, g.tile, s); }
@@ -1172,9 +1165,40 @@ int fc_debug_conv(const float* src0, int c0, const float* src1, int c1, const fl
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
     (void)hipStreamSynchronize(s);
+    table.release();
     (void)hipFree(wp);
-    if (wp8) (void)hipFree(wp8);
-    if (wp3) (void)hipFree(wp3);
+    return r;
+}
+
+// Tests: `n` weight re-layout jobs as ONE table launch on `stream`.  kinds[i] is a PackKind, dims + 5 * i the arguments of its constructor
+// in order (the rest zero); dst_floats[i] (when not null) receives the size of job i's destination in floats; with src or dst null nothing runs.
+int fc_debug_pack(int n, const int* kinds, const int* dims, const float* const* src, float* const* dst, int64_t* dst_floats, void* stream) {
+    if (n < 0 || !kinds || !dims) return fail(FC_E_ARG, "fc_debug_pack: null argument");
+    std::vector<PackJob> jobs;
+    for (int i = 0; i < n; ++i) {
+        const int* d = dims + 5 * i;
+        PackJob j;
+        switch (kinds[i]) {
+            case PACK_CONV: j = pack_job_conv(d[0], d[1], d[2]); break;
+            case PACK_S2D: j = pack_job_s2d(d[0], d[1]); break;
+            case PACK_TRANSPOSE: j = pack_job_transpose(d[0], d[1], d[2], d[3]); break;
+            case PACK_COPY: j = pack_job_copy(d[0]); break;
+            case PACK_CONV_PAD: j = pack_job_conv_pad(d[0], d[1], d[2], d[3], d[4]); break;
+            case PACK_DGRAD: j = pack_job_dgrad(d[0], d[1], d[2], d[3], d[4]); break;
+            case PACK_CONV_K8: j = pack_job_conv_k8(d[0], d[1], d[2]); break;
+            case PACK_CONV_B3: j = pack_job_conv_b3(d[0], d[1], d[2], d[3]); break;
+            case PACK_UP4: j = pack_job_up4(d[0], d[1]); break;
+            case PACK_UP4_B3: j = pack_job_up4_b3(d[0], d[1], d[2]); break;
+            default: j = pack_spec((PackKind)kinds[i], 0, d[0], d[1], d[2], d[3], d[4]); break;      // for pack_table_build to refuse
+        }
+        if (dst_floats) dst_floats[i] = j.kind == PACK_TRANSPOSE ? (int64_t)j.b * j.c : (int64_t)j.total;   // the split layouts: two 16-bit parts of `total`
+        jobs.push_back(j.at(src ? src[i] : nullptr, dst ? dst[i] : nullptr));
+    }
+    PackTable table;
+    int r = pack_table_build(jobs, &table);
+    if (r == FC_OK && src && dst) r = pack_table_launch(table, static_cast<hipStream_t>(stream));
+    (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));     // the table's device memory goes with this call
+    table.release();
     return r;
 }
 

@@ -143,7 +143,7 @@ struct BwdBuilder : PlanBuilder {
         if (err) return;
         const int nci = out.C;
         float* wp = dmalloc((size_t)O * nci * KS * KS);
-        u->dgrad_packs.push_back({off(wname), wp, O, I, KS, ci0, nci});
+        u->dgrad_packs.push_back(pack_job_dgrad(O, I, KS, ci0, nci).at(u->raw + off(wname), wp));
         ConvArgs a;
         a.s0.p = dy.p; a.s0.C = O; a.Hs = dy.H; a.Ws = dy.W; a.KS = KS; a.pad = KS - 1 - pad;
         a.w = wp; a.add = add;
@@ -583,7 +583,7 @@ int build_backward(fc_unet* u) {
         // d(x) = init_conv^T d(.) as an NHWC tensor, converted to the NCHW boundary layout on request (fc_unet_backward_ex)
         Act dxn = b.act(ch, H, W);
         float* wp = b.dmalloc((size_t)dim * ch);
-        u->dgrad_packs.push_back({b.off("init_conv.weight"), wp, dim, ch, 1, 0, ch});
+        u->dgrad_packs.push_back(pack_job_dgrad(dim, ch, 1, 0, ch).at(u->raw + b.off("init_conv.weight"), wp));
         ConvArgs q;
         q.s0.C = dim; q.Hs = H; q.Ws = W; q.KS = 1; q.w = wp;
         q.B = B; q.H = H; q.W = W; q.Cout = ch; q.out = dxn.p; q.Cin = dim;
@@ -657,9 +657,7 @@ int build_backward(fc_unet* u) {
         if (it != b.gmap.end()) u->bwd.named["grad:" + kv.first] = it->second.g;
     }
     u->bwd.maxB = B; u->bwd.H = H; u->bwd.W = W;
-    std::vector<PackJob> jobs;
-    for (const auto& k : u->dgrad_packs) jobs.push_back({u->raw + k.src, k.dst, 5, k.O, k.I, k.KS, k.ci0, k.nci, 0});
-    return pack_table_build(jobs, &u->dgrad_table);
+    return pack_table_build(u->dgrad_packs, &u->dgrad_table);
 }
 
 // The data-gradient chain of the backward plan alone: the entries that are not parameter-only, in plan order, for the activations the

@@ -43,22 +43,10 @@ static void decl_mid(fc_vae* v, const std::string& n, int c) {
     v->decl_linear_t(a + ".to_out.0", c, c);
     decl_resnet(v, n + ".resnets.1", c, c);
 }
-// Conv2d whose channel counts are not multiples of 4 (RGB in / out): packed with zero padding to 4
-static void decl_conv_padded(fc_vae* v, const std::string& n, int O, int I, int K, int Opad, int Ipad) {
-    v->declare(n + ".weight", {O, I, K, K});
-    v->declare(n + ".bias", {O});
-    const int64_t dst = v->pk_alloc(n + ".weight", (int64_t)Opad * Ipad * K * K);
-    v->packops.push_back({4, v->params[v->pidx[n + ".weight"]].offset, dst, O, I, K * K, Opad, Ipad});
-    if (Opad != O) {   // bias padded with zeros: copy O floats into a zero-initialised packed slot
-        const int64_t bd = v->pk_alloc(n + ".bias", Opad);
-        v->packops.push_back({3, v->params[v->pidx[n + ".bias"]].offset, bd, O, 0, 0, 0});
-    }
-}
-
 static int declare_all(fc_vae* v) {
     const std::vector<int>& bo = v->bo;
     const int L = (int)bo.size();
-    decl_conv_padded(v, "encoder.conv_in", bo[0], v->in_ch, 3, bo[0], 4);
+    v->decl_conv_pad("encoder.conv_in", bo[0], v->in_ch, 3, bo[0], 4, false);      // RGB in / out: channels zero-padded to 4
     int ci = bo[0];
     for (int i = 0; i < L; ++i) {
         for (int j = 0; j < v->lpb; ++j) decl_resnet(v, "encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), j == 0 ? ci : bo[i], bo[i]);
@@ -80,7 +68,7 @@ static int declare_all(fc_vae* v) {
         ci = co;
     }
     v->decl_norm("decoder.conv_norm_out", bo[0]);
-    decl_conv_padded(v, "decoder.conv_out", v->in_ch, bo[0], 3, 4, bo[0]);
+    v->decl_conv_pad("decoder.conv_out", v->in_ch, bo[0], 3, 4, bo[0], true);
     return FC_OK;
 }
 

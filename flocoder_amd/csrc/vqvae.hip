@@ -29,14 +29,8 @@ static int pad4(int c) { return (c + 3) & ~3; }
 
 // Conv2d with channel counts that are not multiples of 4 (pixel-space ends): zero-padded operands
 static void decl_conv_any(fc_vqvae* v, const std::string& n, int O, int I, int K) {
-    const int Op = pad4(O), Ip = pad4(I);
-    if (Op == O && Ip == I) { v->decl_conv(n, O, I, K); return; }
-    v->declare(n + ".weight", {O, I, K, K});
-    v->declare(n + ".bias", {O});
-    const int64_t dst = v->pk_alloc(n + ".weight", (int64_t)Op * Ip * K * K);
-    v->packops.push_back({4, v->params[v->pidx[n + ".weight"]].offset, dst, O, I, K * K, Op, Ip});
-    const int64_t bd = v->pk_alloc(n + ".bias", Op);
-    v->packops.push_back({3, v->params[v->pidx[n + ".bias"]].offset, bd, O, 0, 0, 0});
+    if (pad4(O) == O && pad4(I) == I) v->decl_conv(n, O, I, K);
+    else v->decl_conv_pad(n, O, I, K, pad4(O), pad4(I), true);
 }
 static const float* bias_of(const fc_vqvae* v, const std::string& n) { return v->pk.count(n + ".bias") ? v->P(n + ".bias") : v->R(n + ".bias"); }
 
@@ -55,11 +49,8 @@ static void decl_block(fc_vqvae* v, const std::string& n, int ci, int co, int st
     if (attn == 2) {   // state_dict order of NATTENBlock: its own parameter (gamma) first, then the sub-modules norm, qkv, proj
         v->declare(n + ".attn.gamma", {1});
         v->decl_norm(n + ".attn.norm", co);
-        for (auto pr : {std::make_pair(".attn.qkv", 3 * co), std::make_pair(".attn.proj", co)}) {   // nn.Linear [out][in] -> operand [in][out]
-            v->declare(n + pr.first + ".weight", {pr.second, co});
-            const int64_t dst = v->pk_alloc(n + pr.first + ".weight", (int64_t)pr.second * co);
-            v->packops.push_back({2, v->params[v->pidx[n + pr.first + ".weight"]].offset, dst, pr.second, co, pr.second, 0});
-        }
+        v->decl_linear_t(n + ".attn.qkv", 3 * co, co, false);   // nn.Linear [out][in] -> operand [in][out]
+        v->decl_linear_t(n + ".attn.proj", co, co, false);
     }
 }
 

@@ -451,6 +451,13 @@ int fc_debug_conv(const float* src0_nhwc, int c0, const float* src1_nhwc, int c1
                   const float* add_nhwc, float* out_nhwc, float* stats_out, int groups_out, int* stats_T, float* stats_nt, int batch,
                   int hs, int ws, int cout, int ksize, int pad, int stride, int upsample, int out_act, int tile_cfg, int repeats,
                   float* ms_out, void* stream);
+/* Tests: `n` weight re-layout jobs as ONE launch of the kernel every plan packs its weights with.  kinds[i]: 0 conv (O, I, KK), 1 space-to-depth
+ * conv (O, C), 2 transpose into a slice (R, Cc, ld, col0), 3 copy (n), 4 channel-padded conv (O, I, KK, Opad, Ipad), 5 data-gradient operand
+ * (O, I, KS, ci0, nci), 6 k-step-quad conv (O, I, KK), 7 split-bf16 conv (O, I, KK, Ipad), 8 folded upsample (O, I), 9 folded upsample
+ * split-bf16 (O, I, Ipad); dims + 5 * i holds job i's dimensions in that order, the rest zero; src[i] / dst[i] are device pointers.
+ * dst_floats[i] (or null) receives the size of job i's destination in floats; with src or dst null that is all the call does.  Any other
+ * kind: FC_E_ARG, nothing is launched.  Synchronises. */
+int fc_debug_pack(int n, const int* kinds, const int* dims, const float* const* src_dev, float* const* dst_dev, int64_t* dst_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Flow training step  (replaces train_flow.py:346-397: interpolation, loss.backward() through flocoder/unet.py,

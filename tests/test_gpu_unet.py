@@ -244,7 +244,7 @@ torch.save((v.cpu(), img.cpu(), m.flops_per_sample, executed), sys.argv[1])
 def test_folded_upsampling_equals_the_conv_over_the_upsampled_window(tmp_path):
     """Upsample = nn.Upsample(scale_factor=2, nearest) + Conv2d(3x3, padding 1) (unet.py:42-46; AutoencoderKL's Upsample2D behind
     codecs.py:631-652).  Output pixel (2y + a, 2x + b) only ever sees a 2x2 block of source pixels, each through the sum of the taps that land
-    on it, so inference plans run four 2x2 convolutions on the low-resolution tensor (plan.h conv_up2, pack kinds 9 / 10) -- 4/9 of the
+    on it, so inference plans run four 2x2 convolutions on the low-resolution tensor (plan.h conv_up2, PACK_UP4 / PACK_UP4_B3) -- 4/9 of the
     multiply-adds, exact in real arithmetic.  FLOCODER_AMD_UPS_FOLD=0 keeps the 3x3 form: same result to fp32 rounding for the U-Net's three
     Upsample layers and the SD-VAE decoder's three; the FLOPs per sample stay the reference's figure, the executed ones drop."""
     import os

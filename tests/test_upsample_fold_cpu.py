@@ -1,4 +1,4 @@
-"""The algebra behind the folded upsampling (flocoder_amd/csrc/pack.hip kinds 9 / 10, plan.h conv_up2), checked on the CPU in float64.
+"""The algebra behind the folded upsampling (flocoder_amd/csrc/common.h PACK_UP4 / PACK_UP4_B3, plan.h conv_up2), checked on the CPU in float64.
 
 Reference modules: unet.py:42-46 ``Upsample`` = nn.Upsample(scale_factor=2, mode="nearest") + nn.Conv2d(dim, dim_out, 3, padding=1); the
 SD-VAE decoder's Upsample2D behind codecs.py:631-652 is the same pair.  Output pixel (2y + a, 2x + b) reads, through its nine taps, only a
