@@ -112,6 +112,13 @@ struct ParamStore {
     const float* R(const std::string& n) const { return raw + params[pidx.at(n)].offset; }
     const float* P(const std::string& n) const { return packed + pk.at(n); }
     bool has(const std::string& n) const { return pidx.count(n) != 0; }
+    // the bias of layer `n` as its convolution reads it: the packed copy where one was declared (decl_conv_pad's zero-padded slot), else
+    // the raw tensor, or null for a layer declared without a bias (to_qkv, NATTEN's qkv / proj)
+    const float* bias(const std::string& n) const {
+        auto it = pk.find(n + ".bias");
+        if (it != pk.end()) return packed + it->second;
+        return has(n + ".bias") ? R(n + ".bias") : nullptr;
+    }
 
     void declare(const std::string& name, std::initializer_list<int64_t> shape) {
         Param p;
@@ -231,7 +238,7 @@ struct PlanBuilder {
     std::string scope;  // reference module the ops being emitted belong to
     int* fin_err_word = nullptr;   // device word a timed-out fused tail sets (owned by the handle the plan belongs to)
     int conv_prec = 0;             // ConvArgs::prec of every convolution this builder emits (codec plans: 1 = split-bf16 on request)
-    const ParamStore* store = nullptr;   // where conv() finds the split-bf16 copy of a weight (codec builders set it)
+    const ParamStore* store = nullptr;   // the model: where layer() finds a layer's operands and bind_out() the split-bf16 copy of a weight
     Act step_out;                  // set around the Block whose closing launch may close the sampler's step too: the tensor that flavour writes (conv_fin)
 
     // guard: 0 always | 1 only when the call has a mask | 2 only when it runs mask_fusion_conv | 3 only when it has NO mask | 4 mask but no fusion
@@ -315,14 +322,57 @@ struct PlanBuilder {
         return 4.0 * e;
     }
 
-    // Emits one implicit-GEMM launch (plus a standalone statistics pass when the output has < 16 pixels per sample).
-    // `want_G` > 0 asks for GroupNorm partials of the output; returns them in *st.
-    void conv(ConvArgs a, const Act& out, int want_G, Stat* st) {
-        if (err) return;
+    // ---- The vocabulary of a launch site.  A site states only what is special about its layer: it takes the ordinary arguments from one of
+    // these and sets on the result the fields that differ (stride, ups, out_act, add, stats_post, s1, s0.xf, w_batch_stride, w4, res_*, ...).
+
+    // a tensor as a convolution source, read through `xf`
+    static ConvSrc src(const Act& x, const SrcXform& xf = SrcXform()) { ConvSrc s; s.p = x.p; s.C = x.C; s.xf = xf; return s; }
+    // the "same" stride-1 KS x KS convolution of x with weights w (packed) and `bias` (or null)
+    static ConvArgs conv_on(const Act& x, int KS, const float* w, const float* bias) {
+        ConvArgs a;
+        a.s0 = src(x); a.Hs = x.H; a.Ws = x.W; a.KS = KS; a.pad = KS / 2; a.w = w; a.bias = bias;
+        return a;
+    }
+    // ... of the layer `name` of the model in `store`.  The k-step-quad operands (w4 / res_w4) stay with the sites that want them:
+    // attaching a layer's `#k8` copy changes the route its launch takes.
+    ConvArgs layer(const std::string& name, const Act& x, int KS) const { return conv_on(x, KS, store->P(name + ".weight"), store->bias(name)); }
+    // What follows from the output tensor and the builder.  Precision and the split-bf16 copy are set for every launch alike: the paths
+    // that left them out before (conv_fin, the U-Net's stem and injections) belong to the U-Net's builders, whose conv_prec is 0.
+    void bind_out(ConvArgs& a, const Act& out) const {
         a.B = B; a.H = out.H; a.W = out.W; a.Cout = out.C; a.out = out.p;
         a.Cin = a.s0.C + a.s1.C;
         a.prec = conv_prec;
         if (conv_prec && store && !a.w_batch_stride) a.w_b3 = store->B3(a.w);
+    }
+    // y = act(gn(h)) as finalize's arguments; a site adds res / xf_res / act_after_add / stats_out
+    static FinalizeArgs fin_of(const Act& h, const SrcXform& xf, const Act& y) {
+        FinalizeArgs f;
+        f.h = h.p; f.xf = xf; f.y = y.p; f.HW = h.H * h.W; f.C = h.C;
+        return f;
+    }
+    void finalize(const FinalizeArgs& f) {
+        if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
+    }
+    // a new tensor holding act(gn(h)), for the consumers that read it raw
+    Act activated(const Act& h, const SrcXform& xf) {
+        if (err) return Act();      // a builder in error allocates nothing more
+        Act y = act(h.C, h.H, h.W);
+        finalize(fin_of(h, xf, y));
+        return y;
+    }
+    // GroupNorm(G) statistics of a stored tensor in a launch of their own
+    Stat gn_stats(const Act& a, int G) {
+        Stat st = stat(G, 1, (float)(a.H * a.W * (a.C / G)));
+        float* sp = st.p; const float* xp = a.p; const int HW = a.H * a.W, C = a.C;
+        push([=](const FwdCtx& c, hipStream_t s) { return gn_stats_launch(xp, sp, c.B, HW, C, G, s); }, "gn_stats");
+        return st;
+    }
+
+    // Emits one implicit-GEMM launch (plus a standalone statistics pass when the output has < 16 pixels per sample).
+    // `want_G` > 0 asks for GroupNorm partials of the output; returns them in *st.
+    void conv(ConvArgs a, const Act& out, int want_G, Stat* st) {
+        if (err) return;
+        bind_out(a, out);
         const bool fused = want_G > 0 && (out.H * out.W) % 16 == 0;
         ConvGeom g;
         if (fused) { a.Gout = want_G; a.stats_out = reinterpret_cast<float*>(1); }  // placeholder: geometry only
@@ -333,36 +383,35 @@ struct PlanBuilder {
         if (a.res_out) fl += 2.0 * out.H * out.W * (double)a.Cin * a.Cout;
         push([a, tile](const FwdCtx& c, hipStream_t s) { ConvArgs b = a; b.B = c.B; return conv_launch(b, tile, s); }, kTileNames[tile], fl,
              conv_bytes_ps(a), conv_bytes_fixed(a));
-        if (fused && st->T > 16) {   // many tiles per sample (large images): fold the partials once instead of in every consumer workgroup
-            const Stat raw = *st;
-            *st = stat(want_G, 1, raw.n_t * (float)raw.T);
-            const float* ip = raw.p; float* op = st->p;
-            const int G = want_G, T = raw.T; const float nt = raw.n_t;
-            push([=](const FwdCtx& c, hipStream_t s) { return gn_fold_launch(ip, op, c.B, G, T, nt, s); }, "gn_fold");
-        }
-        if (want_G > 0 && !fused) {
-            *st = stat(want_G, 1, (float)(out.H * out.W * (out.C / want_G)));
-            float* sp = st->p; const float* xp = out.p; const int HW = out.H * out.W, C = out.C, G = want_G;
-            push([=](const FwdCtx& c, hipStream_t s) { return gn_stats_launch(xp, sp, c.B, HW, C, G, s); }, "gn_stats");
-        }
+        if (fused) fold_partials(st);
+        if (want_G > 0 && !fused) *st = gn_stats(out, want_G);
     }
 
+private:
+    // many tiles per sample (large images): fold the partials once instead of in every consumer workgroup
+    void fold_partials(Stat* st) {
+        if (st->T <= 16) return;
+        const Stat raw = *st;
+        *st = stat(raw.G, 1, raw.n_t * (float)raw.T);
+        const float* ip = raw.p; float* op = st->p;
+        const int G = raw.G, T = raw.T; const float nt = raw.n_t;
+        push([=](const FwdCtx& c, hipStream_t s) { return gn_fold_launch(ip, op, c.B, G, T, nt, s); }, "gn_fold");
+    }
+
+public:
     // nn.Upsample(nearest, x2) + 3x3 convolution as four 2x2 convolutions on the low-resolution input, one per output parity, with the taps
     // that fall on the same source pixel summed at pack time (ParamStore::decl_conv_up2): 16 instead of 36 multiply-adds per 2x2 output
     // block and channel pair -- exact in real arithmetic, a different summation order in fp32.  One launch carries the four classes
     // (ConvArgs::par4).  `w4` = PUP(name); x low resolution, out 2x.  Returns false, emitting nothing, when the shape is not covered
     // (the caller then emits the 3x3 convolution over the upsampled window).
-    bool conv_up2(const ConvSrc& src, const Act& x, const float* w4, const float* bias, const Act& out, int want_G, Stat* st) {
+    bool conv_up2(const Act& x, const float* w4, const float* bias, const Act& out, int want_G, Stat* st) {
         if (err || !w4) return false;
         static const bool no_fold = [] { const char* e = std::getenv("FLOCODER_AMD_UPS_FOLD"); return e && std::string(e) == "0"; }();
         if (no_fold || (want_G > 0 && (x.H * x.W) % 16 != 0)) return false;
-        ConvArgs a;
-        a.s0 = src; a.Hs = x.H; a.Ws = x.W; a.KS = 2; a.pad = 0; a.stride = 1;
-        a.B = B; a.H = x.H; a.W = x.W; a.Cout = out.C; a.out = out.p; a.bias = bias;
-        a.Cin = a.s0.C;
-        a.prec = conv_prec;
-        a.w = w4;
-        if (conv_prec && store) a.w_b3 = store->B3(w4);
+        ConvArgs a = conv_on(x, 2, w4, bias);
+        a.pad = 0;
+        bind_out(a, out);
+        a.H = x.H; a.W = x.W;      // the launch's grid is the low-resolution one: each of its pixels writes a 2x2 block of `out` (out_sh)
         a.par4 = 1; a.out_sh = 1; a.stats_tmul = 4; a.pad_y = 1; a.pad_x = 1;
         const bool fused = want_G > 0;
         ConvGeom g;
@@ -374,13 +423,7 @@ struct PlanBuilder {
         push([a, tile](const FwdCtx& c, hipStream_t s) { ConvArgs b = a; b.B = c.B; return conv_launch(b, tile, s); }, kTileNames[tile], fl,
              4.0 * ((double)x.H * x.W * a.Cin + (double)out.H * out.W * a.Cout), 4.0 * 16.0 * a.Cin * a.Cout,
              2.0 * out.H * out.W * 9.0 * (double)a.Cin * a.Cout);
-        if (fused && st->T > 16) {
-            const Stat raw = *st;
-            *st = stat(want_G, 1, raw.n_t * (float)raw.T);
-            const float* ip = raw.p; float* op = st->p;
-            const int G = want_G, T = raw.T; const float nt = raw.n_t;
-            push([=](const FwdCtx& c, hipStream_t s) { return gn_fold_launch(ip, op, c.B, G, T, nt, s); }, "gn_fold");
-        }
+        if (fused) fold_partials(st);
         return true;
     }
 
@@ -390,8 +433,7 @@ struct PlanBuilder {
     bool conv_fin(ConvArgs a, const Act& out, int G, const float* gamma, const float* beta, const float* res, bool want_gn1, Stat* gn1,
                   bool only_local = false) {
         if (err) return false;
-        a.B = B; a.H = out.H; a.W = out.W; a.Cout = out.C; a.out = out.p;
-        a.Cin = a.s0.C + a.s1.C;
+        bind_out(a, out);
         if ((out.H * out.W) % 16) return false;
         a.Gout = G; a.stats_out = reinterpret_cast<float*>(16);
         a.fin.gamma = gamma; a.fin.beta = beta; a.fin.res = res;
@@ -434,19 +476,17 @@ struct PlanBuilder {
     // Single-head softmax attention over the h*w tokens of x with d = C (diffusers' VAE mid-block attention, VQGAN's AttnBlock):
     //   out = proj(softmax(q k^T / sqrt(C)) v) + x,   q/k/v = 1x1 conv of GroupNorm(x)
     // as three 1x1 convs with the norm in their loader, a batched transpose, two per-sample-weight GEMMs on the conv kernel and a
-    // one-pass row softmax.  w* are packed [Cin][Cout]; want_G > 0 also returns GroupNorm partials of the sum.
-    struct AttnWeights { const float *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo; };
-    Act attention_block(const Act& x, const SrcXform& norm_x, const AttnWeights& w, int want_G, Stat* so) {
+    // one-pass row softmax.  `names`: the model's q, k, v and output projections (1x1 convolutions or transposed Linears, packed [Cin][Cout]);
+    // want_G > 0 also returns GroupNorm partials of the sum.
+    struct AttnNames { std::string q, k, v, out; };
+    Act attention_block(const Act& x, const SrcXform& norm_x, const AttnNames& names, int want_G, Stat* so) {
         const int C = x.C, hw = x.H * x.W;
         Act q = act(C, x.H, x.W), k = act(C, x.H, x.W), vv = act(C, x.H, x.W);
-        const float* ws[3] = {w.wq, w.wk, w.wv};
-        const float* bs[3] = {w.bq, w.bk, w.bv};
+        const std::string* proj[3] = {&names.q, &names.k, &names.v};
         const Act* outs[3] = {&q, &k, &vv};
         for (int i = 0; i < 3; ++i) {
-            ConvArgs a;
-            a.s0.p = x.p; a.s0.C = C; a.s0.xf = norm_x;
-            a.Hs = x.H; a.Ws = x.W; a.KS = 1;
-            a.w = ws[i]; a.bias = bs[i];
+            ConvArgs a = layer(*proj[i], x, 1);
+            a.s0.xf = norm_x;
             conv(a, *outs[i], 0, nullptr);
         }
         float* kt = dmalloc((size_t)B * C * hw);                    // k^T per sample: [C][n]
@@ -454,9 +494,8 @@ struct PlanBuilder {
         push([=](const FwdCtx& c, hipStream_t s) { return transpose_batched_launch(kp, kt, c.B, hw, C, s); }, "transpose");
         Act sc = act(hw, x.H, x.W);                                 // scores [B][n][n]
         {
-            ConvArgs a;
-            a.s0.p = q.p; a.s0.C = C; a.Hs = x.H; a.Ws = x.W; a.KS = 1;
-            a.w = kt; a.w_batch_stride = C * hw;
+            ConvArgs a = conv_on(q, 1, kt, nullptr);
+            a.w_batch_stride = C * hw;
             conv(a, sc, 0, nullptr);
         }
         float* sp = sc.p;
@@ -464,16 +503,13 @@ struct PlanBuilder {
         push([=](const FwdCtx& c, hipStream_t s) { return softmax_rows_launch(sp, (long)c.B * hw, hw, scale, s); }, "softmax_rows");
         Act o = act(C, x.H, x.W);
         {
-            ConvArgs a;
-            a.s0.p = sc.p; a.s0.C = hw; a.Hs = x.H; a.Ws = x.W; a.KS = 1;
-            a.w = vv.p; a.w_batch_stride = hw * C;
+            ConvArgs a = conv_on(sc, 1, vv.p, nullptr);
+            a.w_batch_stride = hw * C;
             conv(a, o, 0, nullptr);
         }
         Act out = act(C, x.H, x.W);
         {
-            ConvArgs a;
-            a.s0.p = o.p; a.s0.C = C; a.Hs = x.H; a.Ws = x.W; a.KS = 1;
-            a.w = w.wo; a.bias = w.bo;
+            ConvArgs a = layer(names.out, o, 1);
             a.add = x.p; a.stats_post = 1;
             conv(a, out, want_G, so);
         }

@@ -138,13 +138,10 @@ struct Builder : PlanBuilder {
     const int H, W;           // the latent's extent
     Act mask_nhwc;            // stem: the call's mask as the injections read it
     Stat gn1;                 // GroupNorm(1) statistics a resblock(..., feeds_attention) leaves of its output: the following attention's PreNorm
-    Builder(fc_unet* u_, Plan* pl_, int B_, int H_, int W_) : u(u_), H(H_), W(W_) { pl = pl_; B = B_; fin_err_word = u_->dev_err; }
+    Builder(fc_unet* u_, Plan* pl_, int B_, int H_, int W_) : u(u_), H(H_), W(W_) { pl = pl_; B = B_; fin_err_word = u_->dev_err; store = u_; }
     // launches that wait for other workgroups: only on a device this handle has to itself
     bool meeting_ok() const { return fused_tail_enabled() && !u->shared; }
     void retire(const Act&) {}
-    void push_finalize(const FinalizeArgs& f) {
-        if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
-    }
 
     // ResnetBlock (unet.py:76-96): conv1 [+res_conv] | conv2 with GN+FiLM+SiLU folded into its loader | finalize.
     Act resblock(const std::string& p, const Act& x, const Act* skip, int cout, bool feeds_attention) {
@@ -152,11 +149,8 @@ struct Builder : PlanBuilder {
         const int G = u->cfg.groups, cin = x.C + (skip ? skip->C : 0);
         Act h1 = act(cout, x.H, x.W), h2 = act(cout, x.H, x.W), out = act(cout, x.H, x.W), rb;
         Stat st1, st2;
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C;
-        if (skip) { a.s1.p = skip->p; a.s1.C = skip->C; }
-        a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
-        a.w = u->P(p + ".block1.proj.weight"); a.bias = u->R(p + ".block1.proj.bias");
+        ConvArgs a = layer(p + ".block1.proj", x, 3);
+        if (skip) a.s1 = src(*skip);
         a.w4 = u->P8(p + ".block1.proj.weight");
         if (cin != cout) {
             rb = act(cout, x.H, x.W);
@@ -165,11 +159,8 @@ struct Builder : PlanBuilder {
             if (!a.res_w4) a.w4 = nullptr;      // both operands or neither
         }
         conv(a, h1, G, &st1);
-        ConvArgs b;
-        b.s0.p = h1.p; b.s0.C = cout;
+        ConvArgs b = layer(p + ".block2.proj", h1, 3);
         b.s0.xf = xf_of(st1, 2, u->R(p + ".block1.norm.weight"), u->R(p + ".block1.norm.bias"), pl->ss + u->ss_off.at(p), u->S);
-        b.Hs = x.H; b.Ws = x.W; b.KS = 3; b.pad = 1;
-        b.w = u->P(p + ".block2.proj.weight"); b.bias = u->R(p + ".block2.proj.bias");
         b.w4 = u->P8(p + ".block2.proj.weight");
         // Inference plans close the Block inside conv2 (ConvFin) when the launch keeps its whole grid resident: across workgroups where
         // meeting launches are allowed (meeting_ok), and always where a tile holds whole GroupNorm groups (dim 32: the 128-channel blocks
@@ -180,15 +171,14 @@ struct Builder : PlanBuilder {
                            conv_fin(b, out, G, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias"), resp, feeds_attention, &gn1, !meeting_ok());
         if (!fused) {
             conv(b, h2, G, &st2);
-            FinalizeArgs f;
-            f.h = h2.p; f.xf = xf_of(st2, 2, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias"));
-            f.res = resp; f.y = out.p; f.HW = x.H * x.W; f.C = cout;
+            FinalizeArgs f = fin_of(h2, xf_of(st2, 2, u->R(p + ".block2.norm.weight"), u->R(p + ".block2.norm.bias")), out);
+            f.res = resp;
             if (feeds_attention) {
                 const int bps = finalize_blocks_per_sample(f.HW, f.C);
                 gn1 = stat(1, bps, (float)(f.HW * f.C / bps));
                 f.stats_out = gn1.p;
             }
-            push_finalize(f);
+            finalize(f);
         }
         pl->named[p] = out; pl->named[p + ".h1"] = h1; pl->named[p + ".h2"] = h2;
         ResRec rec;
@@ -211,25 +201,19 @@ struct Builder : PlanBuilder {
         if (!u->keep_all && linattn_sample_supported(n, x.C, heads)) return attn_sample(p, x, false);
         Act qkv = act(3 * hid, x.H, x.W), lao = act(hid, x.H, x.W), yb = act(x.C, x.H, x.W), out = act(x.C, x.H, x.W);
         float* ctx = dmalloc((size_t)B * heads * 32 * 32);
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.s0.xf = xf_of(gn1, 1, u->R(p + ".fn.norm.weight"), u->R(p + ".fn.norm.bias"));
-        a.Hs = x.H; a.Ws = x.W; a.KS = 1; a.pad = 0;
-        a.w = u->P(p + ".fn.fn.to_qkv.weight");
+        ConvArgs a = layer(p + ".fn.fn.to_qkv", x, 1);
+        a.s0.xf = xf_of(gn1, 1, u->R(p + ".fn.norm.weight"), u->R(p + ".fn.norm.bias"));
         conv(a, qkv, 0, nullptr);
         const float* qp = qkv.p; float* lp = lao.p;
         if (!err) {
             push([=](const FwdCtx& c, hipStream_t s) { return linattn_ctx_launch(qp, ctx, c.B, n, heads, s); }, "linattn_ctx", 2.0 * n * 32 * 32 * heads);
             push([=](const FwdCtx& c, hipStream_t s) { return linattn_apply_launch(qp, ctx, lp, c.B, n, heads, s); }, "linattn_apply", 2.0 * n * 32 * 32 * heads);
         }
-        ConvArgs o;
-        o.s0.p = lao.p; o.s0.C = hid; o.Hs = x.H; o.Ws = x.W; o.KS = 1; o.pad = 0;
-        o.w = u->P(p + ".fn.fn.to_out.0.weight"); o.bias = u->R(p + ".fn.fn.to_out.0.bias");
         Stat sty;
-        conv(o, yb, 1, &sty);
-        FinalizeArgs f;
-        f.h = yb.p; f.xf = xf_of(sty, 1, u->R(p + ".fn.fn.to_out.1.weight"), u->R(p + ".fn.fn.to_out.1.bias"));
-        f.res = x.p; f.y = out.p; f.HW = n; f.C = x.C;
-        push_finalize(f);
+        conv(layer(p + ".fn.fn.to_out.0", lao, 1), yb, 1, &sty);
+        FinalizeArgs f = fin_of(yb, xf_of(sty, 1, u->R(p + ".fn.fn.to_out.1.weight"), u->R(p + ".fn.fn.to_out.1.bias")), out);
+        f.res = x.p;
+        finalize(f);
         pl->named[p] = out; pl->named[p + ".qkv"] = qkv; pl->named[p + ".lao"] = lao; pl->named[p + ".y"] = yb;
         LinRec rec;
         rec.p = p; rec.x = x; rec.qkv = qkv; rec.lao = lao; rec.yb = yb; rec.out = out; rec.ctx = ctx; rec.gn1 = gn1; rec.sty = sty;
@@ -275,10 +259,9 @@ struct Builder : PlanBuilder {
             return out;
         }
         if (!err) push([a](const FwdCtx& c, hipStream_t s) { LaArgs b = a; b.B = c.B; return linattn_fused_launch(b, s); }, "linattn_fused", fl);
-        FinalizeArgs f;
-        f.h = yb.p; f.xf = xf_of(sty, 1, u->R(p + ".fn.fn.to_out.1.weight"), u->R(p + ".fn.fn.to_out.1.bias"));
-        f.res = x.p; f.y = out.p; f.HW = n; f.C = x.C;
-        push_finalize(f);
+        FinalizeArgs f = fin_of(yb, xf_of(sty, 1, u->R(p + ".fn.fn.to_out.1.weight"), u->R(p + ".fn.fn.to_out.1.bias")), out);
+        f.res = x.p;
+        finalize(f);
         pl->named[p] = out; pl->named[p + ".y"] = yb;
         return out;
     }
@@ -303,18 +286,14 @@ struct Builder : PlanBuilder {
         const int hid = u->heads * 32, n = x.H * x.W, heads = u->heads;
         if (!u->keep_all && attn_sample_supported(n, x.C, heads)) return attn_sample(p, x, true);    // two launches instead of three
         Act qkv = act(3 * hid, x.H, x.W), ao = act(hid, x.H, x.W), out = act(x.C, x.H, x.W);
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.s0.xf = xf_of(gn1, 1, u->R(p + ".fn.norm.weight"), u->R(p + ".fn.norm.bias"));
-        a.Hs = x.H; a.Ws = x.W; a.KS = 1;
-        a.w = u->P(p + ".fn.fn.to_qkv.weight");
+        ConvArgs a = layer(p + ".fn.fn.to_qkv", x, 1);
+        a.s0.xf = xf_of(gn1, 1, u->R(p + ".fn.norm.weight"), u->R(p + ".fn.norm.bias"));
         conv(a, qkv, 0, nullptr);
         const float* qp = qkv.p; float* ap = ao.p;
         if (!err) {
             push([=](const FwdCtx& c, hipStream_t s) { return attn_small_launch(qp, ap, c.B, n, heads, s); }, "attn_small", 2.0 * 2.0 * n * n * 32 * heads);
         }
-        ConvArgs o;
-        o.s0.p = ao.p; o.s0.C = hid; o.Hs = x.H; o.Ws = x.W; o.KS = 1;
-        o.w = u->P(p + ".fn.fn.to_out.weight"); o.bias = u->R(p + ".fn.fn.to_out.bias");
+        ConvArgs o = layer(p + ".fn.fn.to_out", ao, 1);
         o.add = x.p;
         conv(o, out, 0, nullptr);
         pl->named[p] = out;
@@ -334,12 +313,10 @@ struct Builder : PlanBuilder {
         const int C = mask_nhwc.C, Hs = mask_nhwc.H, Ws = mask_nhwc.W, Hd = x.H, Wd = x.W;
         const bool keep = u->keep_all;             // training: the pre-activation z stays (SiLU' needs it), SiLU + residual as a pass of its own
         Act z = keep ? act(x.C, x.H, x.W) : Act();
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.s1.p = mr.p; a.s1.C = C;
-        a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
+        ConvArgs a = layer(name, x, 3);
+        a.s1 = src(mr);
         if (!keep) { a.out_act = 1; a.add = x.p; }
-        a.w = u->P(name + ".weight"); a.bias = u->R(name + ".bias");
-        a.B = B; a.H = x.H; a.W = x.W; a.Cout = x.C; a.out = keep ? z.p : out.p; a.Cin = x.C + C;
+        bind_out(a, keep ? z : out);
         ConvGeom g;
         if ((err = conv_plan(a, TILE_AUTO, &g)) != FC_OK) return out;
         const int tile = g.tile;
@@ -362,7 +339,7 @@ struct Builder : PlanBuilder {
     // init_conv (unet.py:295) and mask fusion (unet.py:298-305)
     Act stem() {
         const fc_unet_config& c = u->cfg;
-        const int dim = c.dim, ch = c.channels, HW = H * W, maxB = B;
+        const int dim = c.dim, ch = c.channels, HW = H * W;
         Act x0 = act(dim, H, W);
         pl->named["init"] = x0;
         pl->x0 = x0;
@@ -389,11 +366,10 @@ struct Builder : PlanBuilder {
         const Act* dsts[3] = {keep ? &z1 : &f1, keep ? &z2 : &f2, &x0};
         int tiles[3];
         for (int i = 0; i < 3 && !err; ++i) {
-            a[i].s0.p = srcs[i]->p; a[i].s0.C = srcs[i]->C;
-            if (i == 0) { a[i].s1.p = mask_nhwc.p; a[i].s1.C = ch; }
-            a[i].Hs = H; a[i].Ws = W; a[i].KS = i == 0 ? 5 : 3; a[i].pad = i == 0 ? 2 : 1; a[i].out_act = (i < 2 && !keep);
-            a[i].w = u->P(std::string(names[i]) + ".weight"); a[i].bias = u->R(std::string(names[i]) + ".bias");
-            a[i].B = maxB; a[i].H = H; a[i].W = W; a[i].Cout = dsts[i]->C; a[i].out = dsts[i]->p; a[i].Cin = a[i].s0.C + a[i].s1.C;
+            a[i] = layer(names[i], *srcs[i], i == 0 ? 5 : 3);
+            if (i == 0) a[i].s1 = src(mask_nhwc);
+            a[i].out_act = (i < 2 && !keep);
+            bind_out(a[i], *dsts[i]);
             ConvGeom g;
             err = conv_plan(a[i], TILE_AUTO, &g);
             tiles[i] = g.tile;
@@ -424,16 +400,16 @@ struct Builder : PlanBuilder {
         scope = p;
         const std::string name = last ? p : p + ".1";
         const bool down = !last && !up;
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W;
-        a.KS = down ? 2 : 3; a.pad = down ? 0 : 1; a.stride = down ? 2 : 1; a.ups = !last && up;
-        a.w = u->P(name + ".weight"); a.bias = u->R(name + ".bias"); a.w4 = u->P8(name + ".weight");    // (no k-step-quad copy of a Downsample's weight)
+        ConvArgs a = layer(name, x, down ? 2 : 3);
+        if (down) { a.pad = 0; a.stride = 2; }
+        a.ups = !last && up;
+        a.w4 = u->P8(name + ".weight");    // (no k-step-quad copy of a Downsample's weight)
         Act o = down ? act(cout, x.H / 2, x.W / 2) : act(cout, x.H << a.ups, x.W << a.ups);
         // (round 3) the upsampling folded into the WEIGHTS -- four 2x2 parity convolutions on x in one launch, 4/9 of the multiply-adds
         // (plan.h conv_up2; FLOCODER_AMD_UPS_FOLD=0: off).  Training plans too: it is the same function of (x, w) up to fp32 rounding, and
         // the backward differentiates it in its 3x3 form from the same saved x (flowers-sized step 6.49 -> 6.45 ms).  Where the shape is
         // not covered, nn.Upsample folded into the convolution's loader.
-        if (!a.ups || !conv_up2(a.s0, x, u->PUP(name + ".weight"), a.bias, o, 0, nullptr)) conv(a, o, 0, nullptr);
+        if (!a.ups || !conv_up2(x, u->PUP(name + ".weight"), a.bias, o, 0, nullptr)) conv(a, o, 0, nullptr);
         pl->tape.push_back({TAPE_CONV, (int)pl->convs.size()});
         pl->convs.push_back({name, x, o, a.KS, a.pad, a.stride, a.ups});
         pl->named[p] = o;

@@ -45,7 +45,7 @@ struct BwdBuilder : PlanBuilder {
     std::map<const float*, Slot> gmap;
     float *ws = nullptr, *s12 = nullptr, *s12p = nullptr, *dss = nullptr;
     size_t ws_floats = 0;
-    BwdBuilder(fc_unet* u_, const Plan* fw_, Plan* pl_, int B_) : u(u_), fw(fw_) { pl = pl_; B = B_; }
+    BwdBuilder(fc_unet* u_, const Plan* fw_, Plan* pl_, int B_) : u(u_), fw(fw_) { pl = pl_; B = B_; store = u_; }
 
     int64_t off(const std::string& n) const { return u->params[u->pidx.at(n)].offset; }
     Slot& slot(const Act& a) {
@@ -144,9 +144,9 @@ struct BwdBuilder : PlanBuilder {
         const int nci = out.C;
         float* wp = dmalloc((size_t)O * nci * KS * KS);
         u->dgrad_packs.push_back(pack_job_dgrad(O, I, KS, ci0, nci).at(u->raw + off(wname), wp));
-        ConvArgs a;
-        a.s0.p = dy.p; a.s0.C = O; a.Hs = dy.H; a.Ws = dy.W; a.KS = KS; a.pad = KS - 1 - pad;
-        a.w = wp; a.add = add;
+        ConvArgs a = conv_on(dy, KS, wp, nullptr);      // dy has the layer's O channels
+        a.pad = KS - 1 - pad;                           // the transposed convolution's padding
+        a.add = add;
         a.split_long_k = 1;
         conv(a, out, 0, nullptr);
     }
@@ -179,8 +179,7 @@ struct BwdBuilder : PlanBuilder {
     void materialize(const Act& h, const SrcXform& xf, const Act& y, bool for_wgrad = false) {
         if (err) return;
         if (pending_mat.flag) { err = fail(FC_E_STATE, "backward: an activation materialised for a weight gradient was never read by one (" + scope + ")"); return; }
-        FinalizeArgs f;
-        f.h = h.p; f.xf = xf; f.y = y.p; f.HW = h.H * h.W; f.C = h.C;
+        const FinalizeArgs f = fin_of(h, xf, y);
         auto deferred = std::make_shared<bool>(false);      // set by the wgrad() that reads y, if and only if that entry joins the table launch
         if (for_wgrad) { pending_mat.f = f; pending_mat.f.B = B; pending_mat.flag = deferred; pending_mat.y = y.p; }
         const int maxB = B;
@@ -584,10 +583,8 @@ int build_backward(fc_unet* u) {
         Act dxn = b.act(ch, H, W);
         float* wp = b.dmalloc((size_t)dim * ch);
         u->dgrad_packs.push_back(pack_job_dgrad(dim, ch, 1, 0, ch).at(u->raw + b.off("init_conv.weight"), wp));
-        ConvArgs q;
-        q.s0.C = dim; q.Hs = H; q.Ws = W; q.KS = 1; q.w = wp;
-        q.B = B; q.H = H; q.W = W; q.Cout = ch; q.out = dxn.p; q.Cin = dim;
-        q.s0.p = gx0;
+        ConvArgs q = b.conv_on(g0, 1, wp, nullptr);     // (the launch picks its source: d(xi) or d(x0))
+        b.bind_out(q, dxn);
         ConvGeom g;
         if ((b.err = conv_plan(q, TILE_AUTO, &g)) != FC_OK) return b.err;
         const int tile = g.tile;

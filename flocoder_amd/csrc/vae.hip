@@ -78,55 +78,33 @@ struct VBuilder : PlanBuilder {
 
     SrcXform gn(const Stat& st, const std::string& norm, int mode) { return xf_of(st, mode, v->R(norm + ".weight"), v->R(norm + ".bias"), nullptr, 0, kEps); }
 
-    // Pre-norm input of a resnet convolution.  Round 3: one elementwise launch writes act(GN(x)) and the convolution reads that.  Rounds 1-2
-    // normalised in the convolution's staging waves and never materialised the tensor, which saves one round trip through HBM but
-    // transforms every window element once per output-channel tile and halo copy -- ~10x at 512 channels -- and VALU work of the staging
-    // waves does not overlap the MFMAs of the waves they share a SIMD with: measured per resnet, fp32: 1.40 -> 1.29 + 0.03 ms
-    // at 512 channels, 6.32 -> 5.79 + 0.43 ms at 128; split-bf16: 0.55 -> 0.45 + 0.03, 2.89 -> 2.38 + 0.43.
-    // Fills `src` for a convolution that reads x through `xf`; *tmp is the tensor to release after the convolution (or empty).
-    void prenorm_src(ConvSrc& src, const Act& x, const SrcXform& xf, Act* tmp) {
-        src.p = x.p; src.C = x.C; src.xf = xf;
-        *tmp = Act();
-        if (err) return;
-        Act y = act(x.C, x.H, x.W);
-        FinalizeArgs f;
-        f.h = x.p; f.xf = xf; f.y = y.p; f.HW = x.H * x.W; f.C = x.C;
-        push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
-        src.p = y.p; src.xf = SrcXform();
-        *tmp = y;
-    }
-
     // x (+ its GroupNorm(32) partials) -> resnet output (+ partials when the consumer starts with a norm)
+    // The pre-norm input of each convolution is a tensor of its own (PlanBuilder::activated).  Round 3: one elementwise launch writes
+    // act(GN(x)) and the convolution reads that.  Rounds 1-2 normalised in the convolution's staging waves and never materialised the
+    // tensor, which saves one round trip through HBM but transforms every window element once per output-channel tile and halo copy --
+    // ~10x at 512 channels -- and VALU work of the staging waves does not overlap the MFMAs of the waves they share a SIMD with
+    // (DESIGN.md 5): measured per resnet, fp32: 1.40 -> 1.29 + 0.03 ms at 512 channels, 6.32 -> 5.79 + 0.43 ms at 128; split-bf16:
+    // 0.55 -> 0.45 + 0.03, 2.89 -> 2.38 + 0.43.
     Act resnet(const std::string& n, const Act& x, const Stat& sx, int co, bool want_stats, Stat* so) {
         scope = n;
         const int G = v->groups;
         Act h1 = act(co, x.H, x.W);
         Stat s1;
-        ConvArgs a;
-        Act t1;
-        prenorm_src(a.s0, x, gn(sx, n + ".norm1", 2), &t1);
-        a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
-        a.w = v->P(n + ".conv1.weight"); a.bias = v->R(n + ".conv1.bias");
-        conv(a, h1, G, &s1);
-        if (t1.p) release(t1);
+        Act t1 = activated(x, gn(sx, n + ".norm1", 2));
+        conv(layer(n + ".conv1", t1, 3), h1, G, &s1);
+        release(t1);
         Act sc = x;
         const bool proj = x.C != co;
         if (proj) {
             sc = act(co, x.H, x.W);
-            ConvArgs c;
-            c.s0.p = x.p; c.s0.C = x.C; c.Hs = x.H; c.Ws = x.W; c.KS = 1;
-            c.w = v->P(n + ".conv_shortcut.weight"); c.bias = v->R(n + ".conv_shortcut.bias");
-            conv(c, sc, 0, nullptr);
+            conv(layer(n + ".conv_shortcut", x, 1), sc, 0, nullptr);
         }
         Act out = act(co, x.H, x.W);
-        ConvArgs b;
-        Act t2;
-        prenorm_src(b.s0, h1, gn(s1, n + ".norm2", 2), &t2);
-        b.Hs = x.H; b.Ws = x.W; b.KS = 3; b.pad = 1;
-        b.w = v->P(n + ".conv2.weight"); b.bias = v->R(n + ".conv2.bias");
+        Act t2 = activated(h1, gn(s1, n + ".norm2", 2));
+        ConvArgs b = layer(n + ".conv2", t2, 3);
         b.add = sc.p; b.stats_post = 1;
         conv(b, out, want_stats ? G : 0, so);
-        if (t2.p) release(t2);
+        release(t2);
         tap(n, out); tap(n + ".h1", h1);
         release(h1);
         if (proj) release(sc);
@@ -136,9 +114,7 @@ struct VBuilder : PlanBuilder {
     // mid-block attention: out = to_out(softmax(q k^T / sqrt(C)) v) + x, q/k/v = Linear(GroupNorm(x))
     Act attention(const std::string& n, const Act& x, const Stat& sx, Stat* so) {
         scope = n;
-        AttnWeights w{v->P(n + ".to_q.weight"), v->R(n + ".to_q.bias"), v->P(n + ".to_k.weight"), v->R(n + ".to_k.bias"),
-                      v->P(n + ".to_v.weight"), v->R(n + ".to_v.bias"), v->P(n + ".to_out.0.weight"), v->R(n + ".to_out.0.bias")};
-        Act out = attention_block(x, gn(sx, n + ".group_norm", 1), w, v->groups, so);
+        Act out = attention_block(x, gn(sx, n + ".group_norm", 1), {n + ".to_q", n + ".to_k", n + ".to_v", n + ".to_out.0"}, v->groups, so);
         tap(n, out);
         return out;
     }
@@ -170,10 +146,7 @@ static int build_encoder(fc_vae* v, int maxB, int H, int W) {
     Act x = b.act(v->bo[0], H, W);
     {
         b.scope = "encoder.conv_in";
-        ConvArgs a;
-        a.s0.p = xin.p; a.s0.C = 4; a.Hs = H; a.Ws = W; a.KS = 3; a.pad = 1;
-        a.w = v->P("encoder.conv_in.weight"); a.bias = v->R("encoder.conv_in.bias");
-        b.conv(a, x, G, &st);
+        b.conv(b.layer(b.scope, xin, 3), x, G, &st);
         b.tap(b.scope, x);
     }
     for (int i = 0; i < L && !b.err; ++i) {
@@ -188,9 +161,8 @@ static int build_encoder(fc_vae* v, int maxB, int H, int W) {
         if (i < L - 1 && !b.err) {   // Downsample2D: pad (0,1,0,1) + conv3x3 stride 2
             b.scope = blk + ".downsamplers.0";
             Act y = b.act(v->bo[i], x.H / 2, x.W / 2);
-            ConvArgs a;
-            a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 0; a.stride = 2;
-            a.w = v->P(blk + ".downsamplers.0.conv.weight"); a.bias = v->R(blk + ".downsamplers.0.conv.bias");
+            ConvArgs a = b.layer(blk + ".downsamplers.0.conv", x, 3);
+            a.pad = 0; a.stride = 2;
             b.conv(a, y, G, &st);
             b.tap(b.scope, y);
             b.release(x);
@@ -204,17 +176,12 @@ static int build_encoder(fc_vae* v, int maxB, int H, int W) {
     Act mo = b.act(2 * v->latent, x.H, x.W), qo = b.act(2 * v->latent, x.H, x.W);
     {
         b.scope = "encoder.conv_out";
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.s0.xf = b.gn(sm, "encoder.conv_norm_out", 2);
-        a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
-        a.w = v->P("encoder.conv_out.weight"); a.bias = v->R("encoder.conv_out.bias");
+        ConvArgs a = b.layer(b.scope, x, 3);
+        a.s0.xf = b.gn(sm, "encoder.conv_norm_out", 2);
         b.conv(a, mo, 0, nullptr);
         b.tap(b.scope, mo);
         b.scope = "quant_conv";
-        ConvArgs q;
-        q.s0.p = mo.p; q.s0.C = mo.C; q.Hs = x.H; q.Ws = x.W; q.KS = 1;
-        q.w = v->P("quant_conv.weight"); q.bias = v->R("quant_conv.bias");
-        b.conv(q, qo, 0, nullptr);
+        b.conv(b.layer(b.scope, mo, 1), qo, 0, nullptr);
         b.tap(b.scope, qo);
     }
     if (b.err) return b.err;
@@ -241,16 +208,10 @@ static int build_decoder(fc_vae* v, int maxB, int h, int w) {
     Act x = b.act(top, h, w);
     {
         b.scope = "post_quant_conv";
-        ConvArgs q;
-        q.s0.p = zin.p; q.s0.C = lat; q.Hs = h; q.Ws = w; q.KS = 1;
-        q.w = v->P("post_quant_conv.weight"); q.bias = v->R("post_quant_conv.bias");
-        b.conv(q, z1, 0, nullptr);
+        b.conv(b.layer(b.scope, zin, 1), z1, 0, nullptr);
         b.tap(b.scope, z1);
         b.scope = "decoder.conv_in";
-        ConvArgs a;
-        a.s0.p = z1.p; a.s0.C = lat; a.Hs = h; a.Ws = w; a.KS = 3; a.pad = 1;
-        a.w = v->P("decoder.conv_in.weight"); a.bias = v->R("decoder.conv_in.bias");
-        b.conv(a, x, G, &st);
+        b.conv(b.layer(b.scope, z1, 3), x, G, &st);
         b.tap(b.scope, x);
     }
     if (b.err) return b.err;
@@ -272,13 +233,9 @@ static int build_decoder(fc_vae* v, int maxB, int h, int w) {
             Act y = b.act(co, x.H * 2, x.W * 2);
             // (round 3) the upsampling is folded into the weights: four 2x2 convolutions on x, 4/9 of the multiply-adds (plan.h conv_up2);
             // FLOCODER_AMD_UPS_FOLD=0: the 3x3 convolution over the upsampled window as in rounds 1-2
-            ConvSrc src; src.p = x.p; src.C = x.C;
-            if (!b.conv_up2(src, x, v->PUP(blk + ".upsamplers.0.conv.weight"), v->R(blk + ".upsamplers.0.conv.bias"), y, G, &st)) {
-                ConvArgs a;
-                a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1; a.ups = 1;
-                a.w = v->P(blk + ".upsamplers.0.conv.weight"); a.bias = v->R(blk + ".upsamplers.0.conv.bias");
-                b.conv(a, y, G, &st);
-            }
+            ConvArgs a = b.layer(blk + ".upsamplers.0.conv", x, 3);
+            a.ups = 1;
+            if (!b.conv_up2(x, v->PUP(blk + ".upsamplers.0.conv.weight"), a.bias, y, G, &st)) b.conv(a, y, G, &st);
             b.tap(b.scope, y);
             b.release(x);
             x = y;
@@ -288,10 +245,8 @@ static int build_decoder(fc_vae* v, int maxB, int h, int w) {
     Act yo = b.act(4, x.H, x.W);
     {
         b.scope = "decoder.conv_out";
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.s0.xf = b.gn(st, "decoder.conv_norm_out", 2);
-        a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1;
-        a.w = v->P("decoder.conv_out.weight"); a.bias = v->P("decoder.conv_out.bias");
+        ConvArgs a = b.layer(b.scope, x, 3);            // (its bias is the packed, zero-padded one: ParamStore::bias)
+        a.s0.xf = b.gn(st, "decoder.conv_norm_out", 2);
         b.conv(a, yo, 0, nullptr);
         b.tap(b.scope, yo);
     }

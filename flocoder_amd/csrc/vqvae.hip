@@ -3,8 +3,8 @@
 // noise_strength 0).  quantize() (ResidualVQ, third-party) is not built.
 //
 // EncDecResidualBlock is post-norm:  out = SiLU(GN(conv2(SiLU(GN(conv1 x)))) + identity),  identity = x or GN(conv1x1/s x).
-// On the implicit-GEMM kernel that is: conv1 (+ partials) | conv2 with GN+SiLU in its loader (+ partials) | optional 1x1
-// projection (+ partials) | one finalize pass that normalises both branches, adds and applies SiLU.  Upsampling is
+// On the implicit-GEMM kernel that is: conv1 (+ partials) | one finalize pass that writes SiLU(GN(.)) | conv2 (+ partials) | optional
+// 1x1 projection (+ partials) | one finalize pass that normalises both branches, adds and applies SiLU.  Upsampling is
 // conv3x3 -> SiLU (epilogue) -> PixelShuffle(2) (one re-layout pass).
 #include <memory>
 
@@ -32,7 +32,6 @@ static void decl_conv_any(fc_vqvae* v, const std::string& n, int O, int I, int K
     if (pad4(O) == O && pad4(I) == I) v->decl_conv(n, O, I, K);
     else v->decl_conv_pad(n, O, I, K, pad4(O), pad4(I), true);
 }
-static const float* bias_of(const fc_vqvae* v, const std::string& n) { return v->pk.count(n + ".bias") ? v->P(n + ".bias") : v->R(n + ".bias"); }
 
 // attn: 0 none | 1 AttnBlock ('full', codecs.py:52-90) | 2 NATTENBlock ('natten', codecs.py:93-145: GroupNorm, bias-free qkv / proj Linears, scalar gate)
 static void decl_block(fc_vqvae* v, const std::string& n, int ci, int co, int stride, int attn) {
@@ -115,90 +114,56 @@ struct QBuilder : PlanBuilder {
         const int G = gn_groups(8, co), Ho = x.H / stride, Wo = x.W / stride;
         Act h1 = act(co, Ho, Wo);
         Stat s1, s2, sd;
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = x.C; a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1; a.stride = stride;
-        a.w = v->P(n + ".conv1.weight"); a.bias = bias_of(v, n + ".conv1");
+        ConvArgs a = layer(n + ".conv1", x, 3);
+        a.stride = stride;
         conv(a, h1, G, &s1);
-        Act mid_in = h1;
-        SrcXform mid_xf = gn(s1, n + ".norm1", 2);
-        bool mid_raw = false;
+        // (round 3) conv2, or the attention in front of it, reads the activated tensor from memory instead of normalising it in its staging
+        // waves once per output-channel tile and halo copy (vae.hip VBuilder::resnet has the measurements)
+        const Act a1 = activated(h1, gn(s1, n + ".norm1", 2));
+        Act mid_in = a1;
         if (v->has(n + ".attn.q.weight")) {                       // attention='full': AttnBlock on the activated tensor (codecs.py:190-192)
-            Act a1 = act(co, Ho, Wo);
-            FinalizeArgs f;
-            f.h = h1.p; f.xf = mid_xf; f.y = a1.p; f.HW = Ho * Wo; f.C = co;
-            push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
-            const int G32 = gn_groups(32, co);
-            Stat sa = stat(G32, 1, (float)(Ho * Wo * (co / G32)));
-            float* sp = sa.p; const float* ap = a1.p; const int HW = Ho * Wo;
-            push([=](const FwdCtx& c, hipStream_t s) { return gn_stats_launch(ap, sp, c.B, HW, co, G32, s); }, "gn_stats");
-            AttnWeights w{v->P(n + ".attn.q.weight"), v->R(n + ".attn.q.bias"), v->P(n + ".attn.k.weight"), v->R(n + ".attn.k.bias"),
-                          v->P(n + ".attn.v.weight"), v->R(n + ".attn.v.bias"), v->P(n + ".attn.proj_out.weight"), v->R(n + ".attn.proj_out.bias")};
-            Act a2 = attention_block(a1, gn(sa, n + ".attn.norm.norm", 1, 1e-6f), w, 0, nullptr);
+            const Stat sa = gn_stats(a1, gn_groups(32, co));
+            mid_in = attention_block(a1, gn(sa, n + ".attn.norm.norm", 1, 1e-6f),
+                                     {n + ".attn.q", n + ".attn.k", n + ".attn.v", n + ".attn.proj_out"}, 0, nullptr);
             tap(n + ".act", a1);
             release(a1);
-            mid_in = a2; mid_raw = true;
         }
         if (v->has(n + ".attn.qkv.weight")) {                     // attention='natten': NATTENBlock on the activated tensor (codecs.py:93-145)
-            Act a1 = act(co, Ho, Wo);
-            FinalizeArgs f;
-            f.h = h1.p; f.xf = mid_xf; f.y = a1.p; f.HW = Ho * Wo; f.C = co;
-            push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
-            const int G8 = gn_groups(8, co);
-            Stat sa = stat(G8, 1, (float)(Ho * Wo * (co / G8)));
-            float* sp = sa.p; const float* ap = a1.p; const int HW = Ho * Wo;
-            push([=](const FwdCtx& c, hipStream_t s) { return gn_stats_launch(ap, sp, c.B, HW, co, G8, s); }, "gn_stats");
+            const Stat sa = gn_stats(a1, gn_groups(8, co));
             Act qkv = act(3 * co, Ho, Wo), att = act(co, Ho, Wo), a2 = act(co, Ho, Wo);
-            ConvArgs q;
-            q.s0.p = a1.p; q.s0.C = co; q.s0.xf = gn(sa, n + ".attn.norm", 1);
-            q.Hs = Ho; q.Ws = Wo; q.KS = 1;
-            q.w = v->P(n + ".attn.qkv.weight");
+            ConvArgs q = layer(n + ".attn.qkv", a1, 1);
+            q.s0.xf = gn(sa, n + ".attn.norm", 1);
             conv(q, qkv, 0, nullptr);
             const float *qp = qkv.p, *gam = v->R(n + ".attn.gamma");
             float* tp = att.p;
             const int mode = v->c.natten;
             push([=](const FwdCtx& c, hipStream_t s) { return na2d_launch(qp, tp, gam, c.B, Ho, Wo, co, 8, 7, mode, s); }, "na2d",
                  2.0 * 2 * 49 * (double)co * Ho * Wo);
-            ConvArgs pj;                                            // identity + gamma * proj(att): gamma rides in na2d's output (proj is linear, no bias)
-            pj.s0.p = att.p; pj.s0.C = co; pj.Hs = Ho; pj.Ws = Wo; pj.KS = 1;
-            pj.w = v->P(n + ".attn.proj.weight"); pj.add = a1.p;
+            ConvArgs pj = layer(n + ".attn.proj", att, 1);          // identity + gamma * proj(att): gamma rides in na2d's output (proj is linear, no bias)
+            pj.add = a1.p;
             conv(pj, a2, 0, nullptr);
             tap(n + ".act", a1); tap(n + ".qkv", qkv); tap(n + ".att", att);    // .att carries gamma
             release(qkv); release(att); release(a1);
-            mid_in = a2; mid_raw = true;
-        }
-        // (round 3) without an attention in between, the activated tensor is materialised as well instead of being normalised in conv2's staging
-        // waves once per output-channel tile and halo copy (vae.hip prenorm_src has the measurements)
-        if (!mid_raw && !err) {
-            Act a1 = act(co, Ho, Wo);
-            FinalizeArgs f;
-            f.h = h1.p; f.xf = mid_xf; f.y = a1.p; f.HW = Ho * Wo; f.C = co;
-            push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
-            mid_in = a1; mid_raw = true;
+            mid_in = a2;
         }
         Act h2 = act(co, Ho, Wo);
-        ConvArgs b;
-        b.s0.p = mid_in.p; b.s0.C = co;
-        if (!mid_raw) b.s0.xf = mid_xf;
-        b.Hs = Ho; b.Ws = Wo; b.KS = 3; b.pad = 1;
-        b.w = v->P(n + ".conv2.weight"); b.bias = v->R(n + ".conv2.bias");
-        conv(b, h2, G, &s2);
+        conv(layer(n + ".conv2", mid_in, 3), h2, G, &s2);
         tap(n + ".h1", h1); tap(n + ".mid", mid_in); tap(n + ".h2", h2);
-        if (mid_raw) release(mid_in);
+        release(mid_in);
         Act out = act(co, Ho, Wo);
-        FinalizeArgs f;
-        f.h = h2.p; f.xf = gn(s2, n + ".norm2", 1); f.y = out.p; f.HW = Ho * Wo; f.C = co; f.act_after_add = 1;
+        FinalizeArgs f = fin_of(h2, gn(s2, n + ".norm2", 1), out);
+        f.act_after_add = 1;
         Act d;
         if (v->has(n + ".downsample.0.weight")) {
             d = act(co, Ho, Wo);
-            ConvArgs c;
-            c.s0.p = x.p; c.s0.C = x.C; c.Hs = x.H; c.Ws = x.W; c.KS = 1; c.stride = stride;
-            c.w = v->P(n + ".downsample.0.weight"); c.bias = bias_of(v, n + ".downsample.0");
+            ConvArgs c = layer(n + ".downsample.0", x, 1);
+            c.stride = stride;
             conv(c, d, G, &sd);
             f.res = d.p; f.xf_res = gn(sd, n + ".downsample.1", 1);
         } else {
             f.res = x.p;
         }
-        if (!err) push([f](const FwdCtx& c, hipStream_t s) { FinalizeArgs g = f; g.B = c.B; return finalize_launch(g, s); }, "finalize");
+        finalize(f);
         tap(n, out);
         if (d.p) tap(n + ".res", d);
         release(h1); release(h2);
@@ -234,18 +199,10 @@ static int build_encoder(fc_vqvae* v, int maxB, int H, int W) {
     Stat st;
     {
         b.scope = "encoder.compress";
-        ConvArgs a;
-        a.s0.p = y.p; a.s0.C = y.C; a.Hs = y.H; a.Ws = y.W; a.KS = 1;
-        a.w = v->P("encoder." + std::to_string(2 * nd + 1) + ".weight"); a.bias = v->R("encoder." + std::to_string(2 * nd + 1) + ".bias");
-        b.conv(a, t1, 0, nullptr);
-        ConvArgs q;
-        q.s0.p = t1.p; q.s0.C = t1.C; q.Hs = y.H; q.Ws = y.W; q.KS = 1;
-        q.w = v->P("encoder." + std::to_string(2 * nd + 2) + ".weight"); q.bias = v->R("encoder." + std::to_string(2 * nd + 2) + ".bias");
-        b.conv(q, t2, gn_groups(2, emb), &st);
-        ConvArgs r;
-        r.s0.p = t2.p; r.s0.C = emb; r.s0.xf = b.gn(st, "encoder." + std::to_string(2 * nd + 3), 2);
-        r.Hs = y.H; r.Ws = y.W; r.KS = 3; r.pad = 1;
-        r.w = v->P("encoder." + std::to_string(2 * nd + 5) + ".weight"); r.bias = v->R("encoder." + std::to_string(2 * nd + 5) + ".bias");
+        b.conv(b.layer("encoder." + std::to_string(2 * nd + 1), y, 1), t1, 0, nullptr);
+        b.conv(b.layer("encoder." + std::to_string(2 * nd + 2), t1, 1), t2, gn_groups(2, emb), &st);
+        ConvArgs r = b.layer("encoder." + std::to_string(2 * nd + 5), t2, 3);
+        r.s0.xf = b.gn(st, "encoder." + std::to_string(2 * nd + 3), 2);
         b.conv(r, t3, 0, nullptr);
         b.tap("encoder." + std::to_string(2 * nd + 1), t1); b.tap("encoder." + std::to_string(2 * nd + 2), t2);
         b.tap("encoder." + std::to_string(2 * nd + 5), t3);
@@ -290,14 +247,9 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
     Stat st;
     {
         b.scope = L + std::to_string(i);
-        ConvArgs a;
-        a.s0.p = z.p; a.s0.C = emb; a.Hs = h; a.Ws = w; a.KS = 1;
-        a.w = v->P(L + std::to_string(i) + ".weight"); a.bias = v->R(L + std::to_string(i) + ".bias");
-        b.conv(a, t1, gn_groups(emb, c.internal_dim), &st);
-        ConvArgs q;
-        q.s0.p = t1.p; q.s0.C = t1.C; q.s0.xf = b.gn(st, L + std::to_string(i + 1), 2);
-        q.Hs = h; q.Ws = w; q.KS = 1;
-        q.w = v->P(L + std::to_string(i + 3) + ".weight"); q.bias = v->R(L + std::to_string(i + 3) + ".bias");
+        b.conv(b.layer(L + std::to_string(i), z, 1), t1, gn_groups(emb, c.internal_dim), &st);
+        ConvArgs q = b.layer(L + std::to_string(i + 3), t1, 1);
+        q.s0.xf = b.gn(st, L + std::to_string(i + 1), 2);
         b.conv(q, x, 0, nullptr);
         b.tap(L + std::to_string(i), t1); b.tap(L + std::to_string(i + 3), x);
     }
@@ -313,9 +265,8 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
         if (lvl == 0) co = hid;
         b.scope = L + std::to_string(i);
         Act u = b.act(4 * cur, x.H, x.W), ps = b.act(cur, 2 * x.H, 2 * x.W);
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = cur; a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1; a.out_act = 1;     // conv, SiLU
-        a.w = v->P(L + std::to_string(i) + ".weight"); a.bias = v->R(L + std::to_string(i) + ".bias");
+        ConvArgs a = b.layer(L + std::to_string(i), x, 3);
+        a.out_act = 1;                                                                              // conv, SiLU
         b.conv(a, u, 0, nullptr);
         const float* up = u.p; float* pp = ps.p;
         const int Hs = x.H, Ws = x.W, cc = cur;
@@ -334,14 +285,10 @@ static int build_decoder(fc_vqvae* v, int maxB, int h, int w) {
     Act f1 = b.act(64, x.H, x.W), f2 = b.act(icp, x.H, x.W);
     {
         b.scope = "decoder.final";
-        ConvArgs a;
-        a.s0.p = x.p; a.s0.C = cur; a.Hs = x.H; a.Ws = x.W; a.KS = 3; a.pad = 1; a.out_act = 1;
-        a.w = v->P(L + std::to_string(i + 1) + ".weight"); a.bias = v->R(L + std::to_string(i + 1) + ".bias");
+        ConvArgs a = b.layer(L + std::to_string(i + 1), x, 3);
+        a.out_act = 1;
         b.conv(a, f1, 0, nullptr);
-        ConvArgs q;
-        q.s0.p = f1.p; q.s0.C = 64; q.Hs = x.H; q.Ws = x.W; q.KS = 3; q.pad = 1;
-        q.w = v->P(L + std::to_string(i + 4) + ".weight"); q.bias = bias_of(v, L + std::to_string(i + 4));
-        b.conv(q, f2, 0, nullptr);
+        b.conv(b.layer(L + std::to_string(i + 4), f1, 3), f2, 0, nullptr);
         b.tap(L + std::to_string(i + 1), f1); b.tap(L + std::to_string(i + 4), f2);   // f1 with its SiLU epilogue
     }
     if (b.err) return b.err;
