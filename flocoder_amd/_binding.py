@@ -118,8 +118,8 @@ SIGNATURES = {
     "fc_mse_loss_grad_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp]),
     "fc_mse_loss_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fc_grad_clip_coef": (_i, [_vp, _i64, _vp, _i64, C.c_float, _vp, _vp, _vp]),
-    "fc_adam_ema_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.c_float, _i, _vp]),
-    "fc_adam_ema_step_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.c_float, _i, _vp, _vp]),
+    "fc_adam_ema_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _i, C.c_double, _i, _vp]),
+    "fc_adam_ema_step_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _i, C.c_double, _i, _vp, _vp]),
     "fc_debug_conv_wgrad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "fc_debug_conv_wgrad_ex": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _pi, _pi, _pi, _vp]),
     "fc_vae_create": (_i, [_i, C.POINTER(_vp)]),

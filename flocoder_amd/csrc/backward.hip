@@ -1066,8 +1066,8 @@ int grad_clip_coef_launch(const float* g, size_t n0, const float* g2, size_t n1,
 
 // Adam as torch.optim.Adam computes it (no weight decay, no amsgrad), on g*coef, followed by the EMA recurrence of train_flow.py:46-54.
 __global__ void __launch_bounds__(256) adam_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, size_t n, const float* coef_ptr,
-                                                       float lr_over_bc1, float b1, float b2, float inv_sqrt_bc2, float eps, float decay,
-                                                       float one_minus_decay, int do_adam, const int* skip) {
+                                                       float lr_over_bc1, float one_minus_b1, float b2, float one_minus_b2, float inv_sqrt_bc2,
+                                                       float eps, float decay, float one_minus_decay, int do_adam, const int* skip) {
     if (skip && *skip) return;   // a step whose inputs were flagged invalid (class id / pairing out of range) updates nothing
     const float coef = coef_ptr ? *coef_ptr : 1.0f;
     for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
@@ -1075,8 +1075,8 @@ __global__ void __launch_bounds__(256) adam_ema_kernel(float* p, const float* g,
         if (do_adam) {
             const float gv = g[i] * coef;
             float mv = m[i], vv = v[i];
-            mv = mv + (gv - mv) * (1.0f - b1);                 // lerp_
-            vv = vv * b2 + (1.0f - b2) * gv * gv;              // mul_ + addcmul_
+            mv = mv + (gv - mv) * one_minus_b1;                // lerp_
+            vv = vv * b2 + one_minus_b2 * gv * gv;             // mul_ + addcmul_
             const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
             pv = pv - lr_over_bc1 * (mv / denom);
             m[i] = mv; v[i] = vv; p[i] = pv;
@@ -1084,14 +1084,17 @@ __global__ void __launch_bounds__(256) adam_ema_kernel(float* p, const float* g,
         if (ema) ema[i] = decay * ema[i] + one_minus_decay * pv;
     }
 }
-int adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, const float* coef_dev, float lr, float b1, float b2,
-                    float eps, int step, float ema_decay, int do_adam, hipStream_t s, const int* skip_flag_dev) {
+// The hyper-parameters arrive as the doubles torch holds them in; every constant the kernel uses is formed in double and rounded to
+// float once, as torch rounds a Python scalar where it meets a float tensor: 1 - beta2 is (float)(1.0 - 0.999) = 0.001f, where
+// 1.0f - 0.999f is 1.3e-5 (relative) below it, a bias of one sign that every step's exp_avg_sq would carry.
+int adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, const float* coef_dev, double lr, double b1, double b2,
+                    double eps, int step, double ema_decay, int do_adam, hipStream_t s, const int* skip_flag_dev) {
     if (!n) return FC_OK;
-    const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
-    const float lr_over_bc1 = do_adam ? (float)((double)lr / bc1) : 0.f;
+    const double bc1 = 1.0 - std::pow(b1, step), bc2 = 1.0 - std::pow(b2, step);
+    const float lr_over_bc1 = do_adam ? (float)(lr / bc1) : 0.f;
     const float inv_sqrt_bc2 = do_adam ? (float)(1.0 / std::sqrt(bc2)) : 0.f;
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(grid_1d(n, 2048)), dim3(256), 0, s, p, g, m, v, ema, n, coef_dev, lr_over_bc1, b1, b2, inv_sqrt_bc2,
-                       eps, ema_decay, (float)(1.0 - (double)ema_decay), do_adam, skip_flag_dev);
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(grid_1d(n, 2048)), dim3(256), 0, s, p, g, m, v, ema, n, coef_dev, lr_over_bc1, (float)(1.0 - b1),
+                       (float)b2, (float)(1.0 - b2), inv_sqrt_bc2, (float)eps, (float)ema_decay, (float)(1.0 - ema_decay), do_adam, skip_flag_dev);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }

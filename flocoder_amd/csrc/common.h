@@ -566,8 +566,8 @@ int mse_loss_grad_launch(const float* v, const float* tgt, float* dv, float* los
 int mse_loss_grad_scaled_launch(const float* v, const float* tgt, float* dv, float* loss_acc, float* ws /*256*/, size_t n, float scale, hipStream_t s);
 int grad_clip_coef_launch(const float* g, size_t n0, const float* g2, size_t n1, float max_norm, float* out2 /*{norm, coef}*/, float* ws /*256*/,
                           hipStream_t s);
-int adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, const float* coef_dev, float lr, float b1, float b2,
-                    float eps, int step, float ema_decay, int do_adam, hipStream_t s, const int* skip_flag_dev = nullptr);
+int adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, const float* coef_dev, double lr, double b1, double b2,
+                    double eps, int step, double ema_decay, int do_adam, hipStream_t s, const int* skip_flag_dev = nullptr);
 
 // ---- OT (ot.hip) ------------------------------------------------------------------------------
 // what the OT solvers may compare: NaN and +-inf become the one finite sentinel

@@ -18,6 +18,7 @@
 // Every entry carries a flag (Plan::op_param_only, set through PlanBuilder::param_only while it is pushed): its products are parameter
 // gradients, or something only parameter gradients read.  fc_unet_vjp_x / fc_unet_log_likelihood run the unflagged entries alone -- the
 // data-gradient chain towards d(x), the same kernels in the same order as the full backward runs them.
+#include <climits>
 #include <cstdlib>
 #include <memory>
 #include <set>
@@ -824,6 +825,7 @@ int fc_unet_class_param_range(const fc_unet* u, int64_t* lo, int64_t* hi) {
 int fc_flow_interp(const float* source_dev, const float* target_dev, const float* t_dev, float* x_out_dev, float* v_out_dev, int batch,
                    int64_t per_sample, void* stream) {
     if (!source_dev || !target_dev || !t_dev || !x_out_dev || !v_out_dev || batch < 1) return fail(FC_E_ARG, "fc_flow_interp: null argument");
+    if (per_sample < 1 || per_sample > INT_MAX) return fail(FC_E_ARG, "fc_flow_interp: per_sample must lie in [1, INT_MAX]");
     return flow_interp_launch(source_dev, target_dev, t_dev, x_out_dev, v_out_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
 }
 
@@ -832,6 +834,7 @@ int fc_flow_prepare(const float* source_dev, const float* target_dev, const int6
                     float* v_out_dev, int* id_flag_dev, int batch, int64_t per_sample, void* stream) {
     if (!source_dev || !target_dev || !u_dev || !t_out_dev || !time_out_dev || !x_out_dev || !v_out_dev || batch < 1 || per_sample < 1)
         return fail(FC_E_ARG, "fc_flow_prepare: null argument");
+    if (per_sample > INT_MAX) return fail(FC_E_ARG, "fc_flow_prepare: per_sample must lie in [1, INT_MAX]");
     if (warp_s < 0.f || warp_s > 1.5f) return fail(FC_E_ARG, "fc_flow_prepare: warp parameter s out of bounds (sampling.py:27)");
     return flow_prepare_launch(source_dev, target_dev, pairing_dev, u_dev, t_eps, warp_s, t_scale, class_ids_dev, n_classes, t_out_dev, time_out_dev,
                                x_out_dev, v_out_dev, id_flag_dev, batch, (int)per_sample, static_cast<hipStream_t>(stream));
@@ -842,6 +845,7 @@ int fc_flow_prepare_rows(const float* source_dev, const float* target_dev, const
                          float* v_out_dev, int* id_flag_dev, int batch, int first_row, int target_rows, int64_t per_sample, void* stream) {
     if (!source_dev || !target_dev || !u_dev || !t_out_dev || !time_out_dev || !x_out_dev || !v_out_dev || batch < 1 || per_sample < 1)
         return fail(FC_E_ARG, "fc_flow_prepare_rows: null argument");
+    if (per_sample > INT_MAX) return fail(FC_E_ARG, "fc_flow_prepare_rows: per_sample must lie in [1, INT_MAX]");
     if (first_row < 0 || target_rows < 1 || (int64_t)first_row + batch > target_rows)
         return fail(FC_E_ARG, "fc_flow_prepare_rows: rows [first_row, first_row + batch) must lie inside [0, target_rows)");
     if (warp_s < 0.f || warp_s > 1.5f) return fail(FC_E_ARG, "fc_flow_prepare_rows: warp parameter s out of bounds (sampling.py:27)");
@@ -864,12 +868,13 @@ int fc_mse_loss_grad(const float* v_dev, const float* target_dev, float* dv_out_
 int fc_grad_clip_coef(const float* grads_dev, int64_t numel, const float* grads2_dev, int64_t numel2, float max_norm, float* norm_coef_out_dev,
                       float* ws256_dev, void* stream) {
     if (!grads_dev || !norm_coef_out_dev || !ws256_dev) return fail(FC_E_ARG, "fc_grad_clip_coef: null argument");
+    if (numel < 0 || (grads2_dev && numel2 < 0)) return fail(FC_E_ARG, "fc_grad_clip_coef: negative element count");
     return grad_clip_coef_launch(grads_dev, (size_t)numel, grads2_dev, grads2_dev ? (size_t)numel2 : 0, max_norm, norm_coef_out_dev, ws256_dev,
                                  static_cast<hipStream_t>(stream));
 }
 
 int fc_adam_ema_step(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, int64_t numel,
-                     const float* clip_coef_dev, float lr, float beta1, float beta2, float eps, int step, float ema_decay, int apply_adam,
+                     const float* clip_coef_dev, double lr, double beta1, double beta2, double eps, int step, double ema_decay, int apply_adam,
                      void* stream) {
     if (!params_dev || numel < 0 || (apply_adam && (!grads_dev || !exp_avg_dev || !exp_avg_sq_dev || step < 1)))
         return fail(FC_E_ARG, "fc_adam_ema_step: bad argument");
@@ -878,7 +883,7 @@ int fc_adam_ema_step(float* params_dev, const float* grads_dev, float* exp_avg_d
 }
 
 int fc_adam_ema_step_guarded(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, int64_t numel,
-                             const float* clip_coef_dev, float lr, float beta1, float beta2, float eps, int step, float ema_decay, int apply_adam,
+                             const float* clip_coef_dev, double lr, double beta1, double beta2, double eps, int step, double ema_decay, int apply_adam,
                              const int* skip_flag_dev, void* stream) {
     if (!params_dev || numel < 0 || (apply_adam && (!grads_dev || !exp_avg_dev || !exp_avg_sq_dev || step < 1)))
         return fail(FC_E_ARG, "fc_adam_ema_step_guarded: bad argument");

@@ -525,7 +525,8 @@ int fc_unet_vjp_op_info(const fc_unet* u, int i, const char** kernel, const char
 uint64_t fc_unet_arena_serial(const fc_unet* u);
 /* [lo, hi) of class_cond_mlp.* inside the flat table (0,0 without classes). */
 int fc_unet_class_param_range(const fc_unet* u, int64_t* lo, int64_t* hi);
-/* x = (1-t) source + t target ; v* = target - source   (train_flow.py:350-353), t per sample. */
+/* x = (1-t) source + t target ; v* = target - source   (train_flow.py:350-353), t per sample.  per_sample (here and in the two
+ * calls below) lies in [1, INT_MAX]; anything else is FC_E_ARG. */
 int fc_flow_interp(const float* source_dev, const float* target_dev, const float* t_dev, float* x_out_dev, float* v_out_dev, int batch,
                    int64_t per_sample, void* stream);
 /* The per-step prologue of train_flow.py:346-357 in one launch: t = warp_time(u (1 - t_eps) + t_eps, s = warp_s) (sampling.py:23-33,
@@ -552,18 +553,22 @@ int fc_mse_loss_grad_scaled(const float* v_dev, const float* target_dev, float* 
 /* loss = mean((v - v*)^2) (train_flow.py:359) and, when dv_out_dev != NULL, its gradient 2 (v - v*) / numel.  ws: 256 floats. */
 int fc_mse_loss_grad(const float* v_dev, const float* target_dev, float* dv_out_dev, float* loss_out_dev, float* ws256_dev, int64_t numel,
                      void* stream);
-/* clip_grad_norm_ (train_flow.py:392): out[0] = 2-norm over both ranges, out[1] = min(1, max_norm / (norm + 1e-6)). */
+/* clip_grad_norm_ (train_flow.py:392): out[0] = 2-norm over both ranges, out[1] = min(1, max_norm / (norm + 1e-6)).  grads2_dev NULL:
+ * one range, numel2 is not looked at.  A negative numel (or numel2 of a second range) is FC_E_ARG. */
 int fc_grad_clip_coef(const float* grads_dev, int64_t numel, const float* grads2_dev, int64_t numel2, float max_norm, float* norm_coef_out_dev,
                       float* ws256_dev, void* stream);
 /* One torch.optim.Adam step (no weight decay / amsgrad) on grads * (*clip_coef_dev), bias corrections for step count `step`
- * (1-based), followed by ema = decay ema + (1 - decay) p.  apply_adam == 0: EMA only (parameters without a gradient). */
+ * (1-based), followed by ema = decay ema + (1 - decay) p.  apply_adam == 0: EMA only (parameters without a gradient).  The
+ * hyper-parameters are doubles, as torch holds them: 1 - beta1, 1 - beta2, lr / bc1, 1 / sqrt(bc2) and 1 - decay are formed in double
+ * and rounded to float once each, which is what torch does where a Python scalar meets a float tensor ((float)(1.0 - 0.999) is 0.001f;
+ * 1.0f - 0.999f is 1.3e-5 below it).  clip_coef_dev NULL: coefficient 1.  ema_dev NULL: Adam only. */
 int fc_adam_ema_step(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, int64_t numel,
-                     const float* clip_coef_dev, float lr, float beta1, float beta2, float eps, int step, float ema_decay, int apply_adam,
+                     const float* clip_coef_dev, double lr, double beta1, double beta2, double eps, int step, double ema_decay, int apply_adam,
                      void* stream);
 /* The same, skipped entirely (no Adam, no EMA) when *skip_flag_dev != 0 (NULL: never): FlowTrainer passes fc_flow_prepare's flag, so a
  * step whose class ids / pairing were out of range changes nothing before the host has seen the flag and raised. */
 int fc_adam_ema_step_guarded(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, int64_t numel,
-                             const float* clip_coef_dev, float lr, float beta1, float beta2, float eps, int step, float ema_decay, int apply_adam,
+                             const float* clip_coef_dev, double lr, double beta1, double beta2, double eps, int step, double ema_decay, int apply_adam,
                              const int* skip_flag_dev, void* stream);
 /* test hook: weight / bias gradient of one convolution (NHWC operands, dw in [O][I][KH][KW]) */
 int fc_debug_conv_wgrad(const float* src0, int c0, const float* src1, int c1, const float* dy, int cout, int batch, int hs, int ws, int ksize,
