@@ -20,6 +20,8 @@ FC_SDE_EULER_MARUYAMA, FC_SDE_HEUN = 0, 1
 FC_LL_MAX_PROBES = 64
 FC_PROBE_RADEMACHER, FC_PROBE_GAUSSIAN = 0, 1
 FC_HIST_LDS_BINS = 8192
+FC_JACOBI_LDS_R, FC_JACOBI_MAX_SWEEPS, FC_FRECHET_MAX_SMALL, FC_FRECHET_MAX_LARGE, FC_GRAM_MAX_ROWS = 4088, 30, 4096, 16384, 65536
+FC_WS_GRAM, FC_WS_MOMENTS, FC_WS_JACOBI, FC_WS_FRECHET, FC_WS_KID = 0, 1, 2, 3, 4
 TILE_AUTO = -1
 TILES = {"M128N32": 0, "M128N64": 1, "M64N32K2": 2, "M32N32K4": 3, "M64N64K2": 4, "M256N64": 5}
 
@@ -190,6 +192,12 @@ SIGNATURES = {
     "fc_knn_workspace_bytes": (_i64, [_i, _i64, _i]),
     "fc_knn_update": (_i, [_vp, _i, _vp, _i64, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "fc_knn_ball_counts": (_i, [_vp, _i, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "fc_frechet_workspace_bytes": (_i64, [_i, _i, _i, _i64]),
+    "fc_gram_f64": (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "fc_col_moments": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp]),
+    "fc_jacobi_svals": (_i, [_vp, _i, _i, _vp, _vp, _vp, _pi, _pi, _vp]),
+    "fc_frechet_sets": (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _pi, _pi, C.POINTER(_i64), _vp]),
+    "fc_kid_sets": (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

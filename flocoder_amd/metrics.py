@@ -13,6 +13,8 @@
   (``fc_note_confusion``): exact int64 counts, ratios in fp64 on the host; ``region=`` restricts it to the pixels that were inpainted;
 * ``prdc`` -- improved precision / recall and density / coverage of a generated set against a real one from exact k-NN radii on the
   device (``flocoder_amd.neighbors``; no upstream counterpart), optional in ``compute_sample_metrics`` (``prdc_k=``);
+* ``frechet`` / ``frechet_px`` / ``kid`` / ``kid_px`` in ``compute_sample_metrics`` (``frechet=``, ``kid=``) and ``fid_score(solver="jacobi")``
+  -- Frechet and kernel distances between the sample sets themselves on the device (``flocoder_amd.distances``; no upstream counterpart);
 * ``bits_per_dim`` -- the flow's log-likelihood (``sampling.log_likelihood``) as bits per latent dimension (no upstream counterpart);
   ``bits_per_dim_stderr`` -- its standard error from a K-probe call's ``logp_stderr``.
 """
@@ -267,9 +269,26 @@ def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
 
 
 @torch.no_grad()
-def fid_score(real, fake, device='cuda', chunk=False, inception=None, chunk_size=256):
-    """metrics.py:266-308.  ``inception``: a callable uint8 [B,3,H,W] -> features, or a TorchScript path (see load_feature_extractor)."""
+def fid_score(real, fake, device='cuda', chunk=False, inception=None, chunk_size=256, solver="eig"):
+    """metrics.py:266-308.  ``inception``: a callable uint8 [B,3,H,W] -> features, or a TorchScript path (see load_feature_extractor).
+    ``solver="jacobi"`` keeps the extractor's features on the device and returns ``distances.frechet_distance_sets`` of them (no F x F
+    covariance, no host eigenvalues; sample counts within that function's limits); ``"eig"`` is the moment form above."""
+    if solver not in ("eig", "jacobi"):
+        raise ValueError(f"fid_score: solver must be 'eig' or 'jacobi', got {solver!r}")
     net = inception if callable(inception) else load_feature_extractor(inception, device)
+    if solver == "jacobi":
+        from . import distances as D
+        step = chunk_size if chunk else max(real.shape[0], fake.shape[0])
+        feats = []
+        for imgs in (real, fake):
+            parts = []
+            for i in range(0, imgs.shape[0], step):
+                u8 = to_uint8(imgs[i:i + step].to(device))
+                if u8.shape[1] == 1:
+                    u8 = u8.repeat(1, 3, 1, 1)
+                parts.append(net(u8).reshape(u8.shape[0], -1).float())
+            feats.append(torch.cat(parts))
+        return D.frechet_distance_sets(feats[0], feats[1])
     stats = (FrechetStatistics(), FrechetStatistics())
     step = chunk_size if chunk else max(real.shape[0], fake.shape[0])
     for side, imgs in enumerate((real, fake)):
@@ -313,10 +332,14 @@ def prdc(real, fake, k=5):
 
 
 @torch.no_grad()
-def compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_target, debug=False, inception=None, *, prdc_k=None):
+def compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_target, debug=False, inception=None, *, prdc_k=None,
+                           frechet=False, kid=False):
     """metrics.py:493-555: the dictionary evaluate_model logs.  'FID_px' is present only when a local feature extractor is (it is
     the one entry that needs third-party weights); everything else is computed unconditionally.  Keyword-only ``prdc_k`` (an integer)
-    adds ``prdc/{precision,recall,density,coverage}`` of ``prdc(target_latents, pred_latents, prdc_k)``: the target latents are the real set."""
+    adds ``prdc/{precision,recall,density,coverage}`` of ``prdc(target_latents, pred_latents, prdc_k)``: the target latents are the real set.
+    Keyword-only ``frechet`` / ``kid`` add ``frechet`` and ``frechet_px`` / ``kid`` and ``kid_px``: ``distances.frechet_distance_sets`` /
+    ``distances.kernel_distance`` of the target latents against the generated ones and of the decoded images, on the sets that
+    ``sinkhorn`` / ``sinkhorn_px`` compare -- raw latents and pixels, no feature network."""
     n = min(pred_latents.shape[0], target_latents.shape[0])
     decoded_pred = normalize_recon(decoded_target, decoded_pred)
     out = {}
@@ -327,4 +350,10 @@ def compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_t
     out.update(sample_stats(pred_latents, target_latents, decoded_pred, decoded_target))
     if prdc_k is not None:
         out.update({f'prdc/{key}': v for key, v in prdc(target_latents, pred_latents, prdc_k).items()})
+    if frechet or kid:
+        from . import distances as D
+        for on, name, fn in ((frechet, 'frechet', D.frechet_distance_sets), (kid, 'kid', D.kernel_distance)):
+            if on:
+                out[name] = fn(target_latents[:n], pred_latents[:n])
+                out[f'{name}_px'] = fn(decoded_target, decoded_pred)
     return out

@@ -883,7 +883,7 @@ def sampler(model, codec, method='rk4', batch_size=256, n_steps=100, cond=None, 
 def evaluate_model(model, codec, epoch, target_latents, cond=None, batch_size=256, n_classes=0, latent_shape=(4, 16, 16), method='rk4',
                    n_steps=None, is_midi=False, keep_gray=False, tag="", cb_tracker=None, cfg_strength=3.0, output_dir="./",
                    use_wandb=False, pre_encoded=True, source=None, mask_pixels=None, debug=False, *, return_images=False,
-                   inception=None, init_image=None, init_strength=0.0, prdc_k=None):
+                   inception=None, init_image=None, init_strength=0.0, prdc_k=None, frechet=False, kid=False):
     """sampling.py:233-322: one epoch's evaluation -- sample, decode, score -- in upstream's order of work: ``model.eval()`` /
     ``codec.eval()``; ``sampler`` with ``n_classes=0`` and the latent shape of ``target_latents``; decode ``target_latents[:batch_size]``;
     ``compute_sample_metrics``; when the codec has a ``vq`` and ``cb_tracker`` is given, the indices of all of ``target_latents`` go to
@@ -905,6 +905,8 @@ def evaluate_model(model, codec, epoch, target_latents, cond=None, batch_size=25
     * Keyword-only ``inception`` goes to ``compute_sample_metrics`` (FID needs a local feature extractor), ``init_image`` /
       ``init_strength`` to ``sampler``, ``prdc_k`` (an integer) to ``compute_sample_metrics``: it adds ``prdc/precision``, ``prdc/recall``,
       ``prdc/density`` and ``prdc/coverage`` of the generated latents against ``target_latents``; with None the dictionary is unchanged.
+      ``frechet`` / ``kid`` go there too and add ``frechet``, ``frechet_px`` / ``kid``, ``kid_px`` (``flocoder_amd.distances``) on the sets
+      that ``sinkhorn`` / ``sinkhorn_px`` compare; with False the dictionary is unchanged.
     * ``gc.collect()`` / ``torch.cuda.empty_cache()`` are not called: nothing here bounces through the host that they would free."""
     if use_wandb:
         raise NotImplementedError("evaluate_model: wandb logging and image grids are out of scope; log the returned dictionary")
@@ -915,7 +917,8 @@ def evaluate_model(model, codec, epoch, target_latents, cond=None, batch_size=25
                                               cond=cond, n_classes=0, latent_shape=latent_shape, cfg_strength=cfg_strength, is_midi=is_midi,
                                               keep_gray=keep_gray, source=source, init_image=init_image, init_strength=init_strength)
     decoded_target = decode_latents(codec, target_latents[:batch_size], is_midi, keep_gray)
-    metrics = M.compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_target, inception=inception, prdc_k=prdc_k)
+    metrics = M.compute_sample_metrics(pred_latents, target_latents, decoded_pred, decoded_target, inception=inception, prdc_k=prdc_k,
+                                       frechet=frechet, kid=kid)
 
     if hasattr(codec, 'vq') and cb_tracker is not None:
         for name, lat in (("val", target_latents), ("gen", pred_latents)):

@@ -802,6 +802,53 @@ int fc_knn_update(const float* q_dev, int n_query, const float* ref_dev, int64_t
 int fc_knn_ball_counts(const float* q_dev, int n_query, const float* ref_dev, int64_t n_ref, int64_t dim, const float* radius2_dev,
                        int64_t first_index, const int64_t* query_ids_dev, int32_t* counts_inout_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Set distances  (no upstream counterpart: Frechet and kernel (KID) distances between sample sets)
+ * ---------------------------------------------------------------------------------------------- */
+#define FC_JACOBI_LDS_R 4088        /* longest vector a pair of which stays in LDS between the products and the rotation */
+#define FC_JACOBI_MAX_SWEEPS 30
+#define FC_FRECHET_MAX_SMALL 4096   /* min(n1, n2), and the number of vectors of a Jacobi solve */
+#define FC_FRECHET_MAX_LARGE 16384  /* max(n1, n2) */
+#define FC_GRAM_MAX_ROWS 65536
+#define FC_WS_GRAM 0
+#define FC_WS_MOMENTS 1
+#define FC_WS_JACOBI 2
+#define FC_WS_FRECHET 3
+#define FC_WS_KID 4
+/* Sets are fp32 [rows][dim] row-major on the device; every result is fp64.  All sums run in a fixed order (per-workgroup partials added by a
+ * second launch, no floating-point atomics): the same bits run to run.  Everything runs on `stream` and allocates nothing; workspaces
+ * are the caller's, 16-byte aligned, of the workspace-bytes function's size for the kind (FC_WS_*) and the call's own n1, n2, dim
+ * (FC_WS_MOMENTS: n1 = n2 = n; FC_WS_JACOBI: n1 = n, n2 = r).  Limits -> FC_E_SHAPE, null or misaligned pointers -> FC_E_ARG, both before any launch.
+ *
+ * fc_gram_f64: c_out_dev [n1][n2] = scale * sum_f (a[i][f] - mean_a[f]) (b[j][f] - mean_b[f]); the means are [dim] fp64 or NULL (no
+ *   centring), subtracted in fp64 on load; products and sums on the fp64 matrix pipe.  fro2_out_dev (NULL, or one fp64; then ws_dev of
+ *   FC_WS_GRAM): the squared Frobenius norm of the stored matrix.  1 <= n1, n2 <= 65536, dim >= 1.
+ * fc_col_moments: mean_out_dev [dim] = the mean of every feature, *ssq_out_dev = sum_i |x_i - mean|^2.  ws_dev: FC_WS_MOMENTS.
+ * fc_jacobi_svals: the singular values of the fp64 matrix given as n vectors of r contiguous elements (z_inout_dev [n][r], destroyed), by
+ *   one-sided Jacobi: sweeps of n' - 1 rounds of the round-robin schedule (n' = n rounded up to even; the padding vector is zero and its
+ *   pairs do nothing), one launch per round, one workgroup per pair.  A pair with alpha = |a|^2, beta = |b|^2, gamma = a.b (recomputed
+ *   every time) is left alone when |gamma| <= r 2^-53 sqrt(alpha beta) or alpha beta <= (2^-53 ||Z||_F^2)^2, else rotated by the
+ *   smaller-angle tangent.  The host reads one 8-byte word per sweep (rotations, non-finite pairs) and stops after the first sweep
+ *   without a rotation (*converged_out_host = 1), after a sweep that met a non-finite product, or after FC_JACOBI_MAX_SWEEPS (0).
+ *   svals_out_dev [n]: the vector norms, descending; nuclear_out_dev (may be NULL): their sum.  1 <= n <= 4096, r >= 1.
+ * fc_frechet_sets: out_dev [6] = {FD, |mx - my|^2, tr S1, tr S2, ||C||_*, ||C||_F^2} with
+ *   FD = |mx - my|^2 + sum |x - mx|^2 / (n1 - 1) + sum |y - my|^2 / (n2 - 1) - 2 ||C||_*, C = the centred cross-Gram of the smaller set
+ *   against the larger, scaled by 1 / sqrt((n1 - 1)(n2 - 1)) -- tr sqrt(S1 S2) = ||C||_* exactly, and no dim x dim matrix is formed.
+ *   svals_out_dev: NULL or [min(n1, n2)].  launches_out_host: NULL or the number of kernel launches of the call.
+ *   2 <= n1, n2; min(n1, n2) <= 4096; max(n1, n2) <= 16384; dim >= 1.
+ * fc_kid_sets: out_dev [4] = {MMD^2, sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)}, k(x, y) = (x.y / dim + 1)^3,
+ *   MMD^2 = sum_xx / (n1 (n1 - 1)) + sum_yy / (n2 (n2 - 1)) - 2 sum_xy / (n1 n2): three Gram launches whose epilogue reduces.
+ *   2 <= n1, n2 <= 16384. */
+int64_t fc_frechet_workspace_bytes(int what, int n1, int n2, int64_t dim);
+int fc_gram_f64(const float* a_dev, int n1, const float* b_dev, int n2, int64_t dim, const double* mean_a_dev, const double* mean_b_dev,
+                double scale, double* c_out_dev, double* fro2_out_dev, void* ws_dev, void* stream);
+int fc_col_moments(const float* x_dev, int n, int64_t dim, double* mean_out_dev, double* ssq_out_dev, void* ws_dev, void* stream);
+int fc_jacobi_svals(double* z_inout_dev, int n, int r, double* svals_out_dev, double* nuclear_out_dev, void* ws_dev, int* sweeps_out_host,
+                    int* converged_out_host, void* stream);
+int fc_frechet_sets(const float* x_dev, int n1, const float* y_dev, int n2, int64_t dim, void* ws_dev, double* out_dev, double* svals_out_dev,
+                    int* sweeps_out_host, int* converged_out_host, int64_t* launches_out_host, void* stream);
+int fc_kid_sets(const float* x_dev, int n1, const float* y_dev, int n2, int64_t dim, void* ws_dev, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
