@@ -39,3 +39,4 @@ from .ot import OTPlanSampler, compute_ot_pairing, compute_ot_plan, sample_plan 
 from .codebook_analysis import CodebookUsageTracker, calc_usage_stats  # noqa: F401,E402
 from .metrics import calc_note_metrics  # noqa: F401,E402
 from .sampling import evaluate_model  # noqa: F401,E402
+from .pianoroll import images_to_midi_files, images_to_notes, notes_to_images  # noqa: F401,E402

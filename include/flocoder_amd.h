@@ -849,6 +849,35 @@ int fc_frechet_sets(const float* x_dev, int n1, const float* y_dev, int n2, int6
                     int* sweeps_out_host, int* converged_out_host, int64_t* launches_out_host, void* stream);
 int fc_kid_sets(const float* x_dev, int n1, const float* y_dev, int n2, int64_t dim, void* ws_dev, double* out_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Piano rolls and MIDI  (flocoder/pianoroll.py: img2midi_multi, and the painting of get_piano_rolls + piano_roll_to_img; DESIGN.md
+ * section 4 "Piano rolls and MIDI"; the definitions are flocoder_amd/pianoroll.py's NumPy functions)
+ * ---------------------------------------------------------------------------------------------- */
+#define FC_ROLL_STRIPS 0            /* [B,3,128 S,W]: column t = s W + x reads pixel (128 s + y, x) */
+#define FC_ROLL_SQUARE 1            /* 256 x 256: t < 256 reads (y, t), t >= 256 reads (128 + y, 511 - t) */
+#define FC_ROLL_GRID 2              /* 2048 x 2048: 64 squares, row-major, 512 columns each */
+#define FC_ROLL_MAX_COLUMNS 32768
+#define FC_ROLL_MAX_WIDTH 2048
+/* Integer work only, on `stream`, nothing allocated, nothing waited for, no atomic decides a note's place: the same bits run to run.
+ * fc_pianoroll_scan: images_dev uint8 (is_float = 0) or fp32 (1; read through metrics.to_uint8's per-image stretch, NaN as 0)
+ *   [batch][3][height][width]; classifies, runs the onset scan (require_onsets), zeroes rows 0 / 127 of every strip, draws the separators
+ *   (every `separators` columns, 0 = none) and leaves in ws_dev (16-byte aligned, fc_pianoroll_workspace_bytes(batch, columns)) the velocity
+ *   plane and the note masks; counts_out_dev [batch] = the number of notes of every roll.  split_on_onsets: a red pixel behind a sounding
+ *   column also ends the running note and starts another.
+ * fc_pianoroll_emit: from the workspace of a scan of the same batch and columns, notes_out_dev int32 [batch][max_notes][4] = (pitch,
+ *   start, end, velocity) ascending in (end, pitch), the first max_notes of every roll, the rest -1.  16-byte aligned.
+ * fc_pianoroll_render: notes_dev [batch][max_notes][4] + counts_dev [batch] (entries at or past min(count, max_notes) are not read) ->
+ *   images_out_dev uint8 [batch][3][128][width], columns col0_dev[b] (NULL: 0) .. + width of the roll in which every entry in list order
+ *   sets [start, end) of its pitch to its velocity (clamped to 0..255) and then column start - 1 to 0; green = min(2 v, 255), a pixel is
+ *   red (g, 0, 0) iff v >= 11 and (t = 0 or v[t - 1] <= 9), else (0, g, 0); image row 127 - pitch.  Entries with a pitch outside 0..127
+ *   paint nothing. */
+int64_t fc_pianoroll_workspace_bytes(int batch, int columns);   /* -1: outside the limits */
+int fc_pianoroll_scan(const void* images_dev, int is_float, int batch, int height, int width, int layout, int require_onsets, int separators,
+                      int split_on_onsets, void* ws_dev, int64_t* counts_out_dev, void* stream);
+int fc_pianoroll_emit(const void* ws_dev, int batch, int columns, int32_t* notes_out_dev, int max_notes, void* stream);
+int fc_pianoroll_render(const int32_t* notes_dev, const int64_t* counts_dev, int batch, int max_notes, int width, const int32_t* col0_dev,
+                        uint8_t* images_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
