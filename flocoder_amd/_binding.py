@@ -22,6 +22,7 @@ FC_PROBE_RADEMACHER, FC_PROBE_GAUSSIAN = 0, 1
 FC_HIST_LDS_BINS = 8192
 FC_JACOBI_LDS_R, FC_JACOBI_MAX_SWEEPS, FC_FRECHET_MAX_SMALL, FC_FRECHET_MAX_LARGE, FC_GRAM_MAX_ROWS = 4088, 30, 4096, 16384, 65536
 FC_WS_GRAM, FC_WS_MOMENTS, FC_WS_JACOBI, FC_WS_FRECHET, FC_WS_KID = 0, 1, 2, 3, 4
+FC_WS_MOMENTS_UPDATE, FC_WS_MOMENTS_MERGE, FC_WS_MOMENTS_FACTOR, FC_WS_MOMENTS_DISTANCE = 5, 6, 7, 8
 FC_ROLL_STRIPS, FC_ROLL_SQUARE, FC_ROLL_GRID, FC_ROLL_MAX_COLUMNS, FC_ROLL_MAX_WIDTH = 0, 1, 2, 32768, 2048
 TILE_AUTO = -1
 TILES = {"M128N32": 0, "M128N64": 1, "M64N32K2": 2, "M32N32K4": 3, "M64N64K2": 4, "M256N64": 5}
@@ -199,6 +200,10 @@ SIGNATURES = {
     "fc_jacobi_svals": (_i, [_vp, _i, _i, _vp, _vp, _vp, _pi, _pi, _vp]),
     "fc_frechet_sets": (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _pi, _pi, C.POINTER(_i64), _vp]),
     "fc_kid_sets": (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp, _vp]),
+    "fc_frechet_moments_update": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp]),
+    "fc_frechet_moments_merge": (_i, [_i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "fc_frechet_moments_factor": (_i, [_i, _i64, _vp, _vp, _vp, _vp, _vp, _pi, _pi, C.POINTER(_i64), _vp]),
+    "fc_frechet_moments_distance": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi, _pi, C.POINTER(_i64), _vp]),
     "fc_pianoroll_workspace_bytes": (_i64, [_i, _i]),
     "fc_pianoroll_scan": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "fc_pianoroll_emit": (_i, [_vp, _i, _i, _vp, _i, _vp]),

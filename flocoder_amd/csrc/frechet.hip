@@ -3,6 +3,9 @@
 //   Frechet:  FD = |mx - my|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2),   tr sqrt(S1 S2) = ||A B^T||_*  (nuclear norm),
 //             A = (X - mx) / sqrt(N1 - 1), B = (Y - my) / sqrt(N2 - 1): no D x D matrix exists, D is the inner extent of one fp64 Gram.
 //   KID:      the unbiased MMD^2 with k(x, y) = (x.y / D + 1)^3 from three Gram launches whose epilogue reduces instead of storing.
+//   Moments:  for N >> D a set is (n, mean, M = sum (x - mean)(x - mean)^T), fed batch by batch (scatter_kernel: the batch's centred
+//             scatter on the same MFMA, joined by Chan's pairwise rule), S = M / (n - 1) = F^T F with F from the Jacobi iteration run on the
+//             rows of S, and tr sqrt(S1 S2) = ||F1 F2^T||_*: one fp64 Gram of two factors (gram_kernel on fp64 rows) and a third solve.
 //
 // Kernels: gram_kernel (fp32 rows, centred in fp64 on load, v_mfma_f64_16x16x4_f64, 32 x 32 tile per workgroup of four waves, LDS tiled
 // over the features, every edge predicated), col_moments_kernel (fp64 mean per feature and sum |x - mean|^2), jacobi_pair_kernel (one
@@ -34,8 +37,9 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
 }
 
 // ------------------------------------------------------------------------------------------------ Gram
-struct GramArgs {
-    const float *a, *b;          // [n1][dim], [n2][dim]
+template <typename T>
+struct GramArgsT {
+    const T *a, *b;              // [n1][dim], [n2][dim]: fp32 sample rows, or the fp64 rows of two covariance factors
     const double *ma, *mb;       // [dim] or null
     int n1, n2;
     long long dim;
@@ -44,11 +48,12 @@ struct GramArgs {
     double* part;                // one fp64 per workgroup or null: sum of the stored values squared (store), sum of k (reduce)
     int skip_diag;
 };
+using GramArgs = GramArgsT<float>;
 
 // C = scale (a - ma)(b - mb)^T.  The f64 MFMA's lane maps: lane l feeds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15], one
 // f64 each, and holds C[row = (l >> 4) + 4 reg][col = l & 15] in reg 0..3 (not the fp32 shapes' row map).
-template <bool REDUCE>
-__global__ void __launch_bounds__(GR_THREADS) gram_kernel(const GramArgs g) {
+template <bool REDUCE, typename T>
+__global__ void __launch_bounds__(GR_THREADS) gram_kernel(const GramArgsT<T> g) {
     __shared__ double As[GR_T * GR_LD], Bs[GR_T * GR_LD];
     __shared__ double red[4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -258,6 +263,126 @@ __global__ void kid_final_kernel(const double* sums, int n1, int n2, double* out
     out[1] = sums[0]; out[2] = sums[1]; out[3] = sums[2];
 }
 
+// ------------------------------------------------------------------------------------------------ moment form
+// State of a set: n (host), mean [dim], M [dim][dim] = sum (x - mean)(x - mean)^T, full and bit-symmetric.  A batch enters through its
+// own centred scatter and Chan's pairwise update: M += Mb + w d d^T, d = mean_b - mean, w = n nb / (n + nb).
+struct ScatterArgs {
+    const float* x;              // [nb][dim]
+    const double *mb, *delta;    // [dim]: the batch's mean; mean_b - mean (zeros for the first batch)
+    int nb, dim;                 // workgroup b of cdiv(dim, 32) (cdiv(dim, 32) + 1) / 2 owns tile (ti, tj), tj <= ti, b = ti (ti + 1) / 2 + tj
+    double w;
+    double* m;                   // [dim][dim] in/out
+    int first;                   // store, do not read M
+};
+
+// C[f][g] = sum_rows (x[r][f] - mb[f]) (x[r][g] - mb[g]): gram_kernel with the roles turned -- the inner extent is the row index and both
+// operands are column blocks of one matrix.  A wave's 32 lanes load 32 neighbouring features of one row (coalesced) and store them
+// down a column of the [feature][row] LDS tile: stride GR_LD = 33 doubles, 32 different banks.  The MFMA side reads the tile as
+// gram_kernel does.  A diagonal tile stages one operand.  Each tile has one owner, who also writes the mirror: no atomics, M == M^T.
+__global__ void __launch_bounds__(GR_THREADS) scatter_kernel(const ScatterArgs g) {
+    __shared__ double As[GR_T * GR_LD], Bs[GR_T * GR_LD];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int ti = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
+    while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
+    while (ti * (ti + 1) / 2 > (int)blockIdx.x) --ti;
+    const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
+    const bool diag = ti == tj;
+    const int i0 = ti * GR_T, j0 = tj * GR_T;
+    const int lr = tid >> 5, lc = tid & 31;                   // this thread stages rows lr + 8 q of a chunk, feature lc of both blocks
+    const int fa = i0 + lc, fb = j0 + lc;
+    const bool aok = fa < g.dim, bok = fb < g.dim && !diag;
+    const double ca = aok ? g.mb[fa] : 0.0, cb = bok ? g.mb[fb] : 0.0;
+    double ra[4], rb[4];
+    auto load = [&](int r0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = r0 + lr + 8 * q;
+            const bool rok = r < g.nb;
+            ra[q] = (rok && aok) ? (double)g.x[(size_t)r * g.dim + fa] - ca : 0.0;
+            rb[q] = (rok && bok) ? (double)g.x[(size_t)r * g.dim + fb] - cb : 0.0;
+        }
+    };
+    const int wi = (w >> 1) * 16, wj = (w & 1) * 16;
+    const int ar = (wi + (lane & 15)) * GR_LD + (lane >> 4), br = (wj + (lane & 15)) * GR_LD + (lane >> 4);
+    const double* Bp = diag ? As : Bs;
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+    load(0);
+    for (int r0 = 0; r0 < g.nb; r0 += GR_BK) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            As[lc * GR_LD + lr + 8 * q] = ra[q];
+            if (!diag) Bs[lc * GR_LD + lr + 8 * q] = rb[q];
+        }
+        __syncthreads();
+        if (r0 + GR_BK < g.nb) load(r0 + GR_BK);
+#pragma unroll
+        for (int kk = 0; kk < GR_BK / 4; ++kk)
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(As[ar + 4 * kk], Bp[br + 4 * kk], acc, 0, 0, 0);
+        __syncthreads();
+    }
+    const int col = j0 + wj + (lane & 15);
+    if (col >= g.dim) return;
+    const double dc = g.delta[col];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int row = i0 + wi + (lane >> 4) + 4 * reg;
+        if (row >= g.dim || (diag && row < col)) continue;     // a diagonal tile: the lower triangle's lanes own both elements
+        double v = acc[reg] + g.w * (g.delta[row] * dc);
+        if (!g.first) v = g.m[(size_t)row * g.dim + col] + v;
+        g.m[(size_t)row * g.dim + col] = v;
+        if (row != col) g.m[(size_t)col * g.dim + row] = v;
+    }
+}
+
+// delta[f] = mean_b[f] - mean[f], mean[f] += frac delta[f]; the first batch: delta = 0, mean = mean_b
+__global__ void __launch_bounds__(256) mean_merge_kernel(const double* mean_b, int dim, double frac, int first, double* mean, double* delta) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= dim) return;
+    const double d = first ? 0.0 : mean_b[f] - mean[f];
+    delta[f] = d;
+    mean[f] = first ? mean_b[f] : mean[f] + frac * d;
+}
+
+// M_a[f][g] += M_b[f][g] + w delta[f] delta[g] (symmetric in, symmetric out: the product of the deltas commutes); first: M_a = M_b
+__global__ void __launch_bounds__(256) scatter_merge_kernel(const double* mb, const double* delta, int dim, double w, int first, double* ma) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)dim * dim) return;
+    const int f = (int)(i / dim), gg = (int)(i % dim);
+    const double v = mb[i] + w * (delta[f] * delta[gg]);
+    ma[i] = first ? mb[i] : ma[i] + v;
+}
+
+// z = scale M
+__global__ void __launch_bounds__(256) scale_copy_kernel(const double* m, long long count, double scale, double* z) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < count) z[i] = scale * m[i];
+}
+
+// out[0] = scale * sum_f M[f][f], thread t adds f = t, t + 256, ... in order
+__global__ void __launch_bounds__(256) trace_kernel(const double* m, int dim, double scale, double* out) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int f = threadIdx.x; f < dim; f += 256) s += m[(size_t)f * dim + f];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) out[0] = scale * s;
+}
+
+// f_i = z_i / sqrt(|z_i|) with alpha[i] = |z_i|^2, one workgroup per vector; a zero (or non-finite-norm) row is left as it is
+__global__ void __launch_bounds__(256) factor_scale_kernel(double* z, int r, const double* alpha) {
+    const double a = alpha[blockIdx.x];
+    if (!(a > 0.0) || !isfinite(a)) return;
+    const double s = 1.0 / sqrt(sqrt(a));
+    double* v = z + (size_t)blockIdx.x * r;
+    for (int f = threadIdx.x; f < r; f += 256) v[f] = s * v[f];
+}
+
+// out: {FD, |m1 - m2|^2, tr S1, tr S2, ||F1 F2^T||_*, ||F1 F2^T||_F^2}; sc: {dm2, nuclear, fro2}
+__global__ void moments_final_kernel(const double* sc, const double* tr1, const double* tr2, double* out) {
+    if (threadIdx.x || blockIdx.x) return;
+    out[0] = ((sc[0] + tr1[0]) + tr2[0]) - 2.0 * sc[1];
+    out[1] = sc[0]; out[2] = tr1[0]; out[3] = tr2[0]; out[4] = sc[1]; out[5] = sc[2];
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static inline long long fr_align(long long b) { return (b + 15) / 16 * 16; }
 static inline long long fr_tiles(int n1, int n2) { return (long long)cdiv(n1, GR_T) * cdiv(n2, GR_T); }
@@ -290,12 +415,36 @@ static FrechetWs frechet_ws_layout(int ns, int nl, long long dim) {
     return w;
 }
 
+struct MomentsUpdateWs { long long mean_b, delta, part, scalars, total; };
+static MomentsUpdateWs moments_update_ws_layout(long long dim) {
+    MomentsUpdateWs w = {};
+    long long o = 0;
+    w.mean_b = o; o += fr_align(dim * 8);
+    w.delta = o; o += fr_align(dim * 8);
+    w.part = o; o += fr_align(fr_cm_blocks(dim) * 8);
+    w.scalars = o; o += FR_SCALAR_BYTES;
+    w.total = o;
+    return w;
+}
+struct MomentsDistanceWs { long long g, part, scalars, jacobi, total; };     // scalars: {dm2, nuclear, fro2}
+static MomentsDistanceWs moments_distance_ws_layout(int dim) {
+    MomentsDistanceWs w = {};
+    long long o = 0;
+    w.g = o; o += fr_align((long long)dim * dim * 8);
+    w.part = o; o += fr_align(fr_tiles(dim, dim) * 8);
+    w.scalars = o; o += FR_SCALAR_BYTES;
+    w.jacobi = o; o += jacobi_ws_layout(dim).total;
+    w.total = o;
+    return w;
+}
+
 static bool fr_misaligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) != 0; }
 
-static int gram_launch(const GramArgs& g, bool reduce, hipStream_t s) {
+template <typename T>
+static int gram_launch(const GramArgsT<T>& g, bool reduce, hipStream_t s) {
     const dim3 grid(cdiv(g.n2, GR_T), cdiv(g.n1, GR_T));
-    if (reduce) hipLaunchKernelGGL(gram_kernel<true>, grid, dim3(GR_THREADS), 0, s, g);
-    else hipLaunchKernelGGL(gram_kernel<false>, grid, dim3(GR_THREADS), 0, s, g);
+    if (reduce) hipLaunchKernelGGL((gram_kernel<true, T>), grid, dim3(GR_THREADS), 0, s, g);
+    else hipLaunchKernelGGL((gram_kernel<false, T>), grid, dim3(GR_THREADS), 0, s, g);
     FC_HIP(hipGetLastError());
     return FC_OK;
 }
@@ -379,6 +528,15 @@ int64_t fc_frechet_workspace_bytes(int what, int n1, int n2, int64_t dim) {
     case FC_WS_KID:
         if (nl > FC_FRECHET_MAX_LARGE) return fail(FC_E_SHAPE, "fc_frechet_workspace_bytes: max(n1, n2) <= 16384");
         return fr_align((fr_tiles(n1, n1) + fr_tiles(n2, n2) + fr_tiles(n1, n2)) * 8) + FR_SCALAR_BYTES;
+    case FC_WS_MOMENTS_UPDATE:
+    case FC_WS_MOMENTS_MERGE:
+    case FC_WS_MOMENTS_FACTOR:
+    case FC_WS_MOMENTS_DISTANCE:
+        if (dim > FC_FRECHET_MAX_SMALL) return fail(FC_E_SHAPE, "fc_frechet_workspace_bytes: the moment form takes dim <= 4096");
+        if (what == FC_WS_MOMENTS_UPDATE) return moments_update_ws_layout(dim).total;
+        if (what == FC_WS_MOMENTS_MERGE) return fr_align(dim * 8);
+        if (what == FC_WS_MOMENTS_FACTOR) return jacobi_ws_layout((int)dim).total;
+        return moments_distance_ws_layout((int)dim).total;
     }
     return fail(FC_E_ARG, "fc_frechet_workspace_bytes: unknown workspace kind");
 }
@@ -490,6 +648,122 @@ int fc_kid_sets(const float* x_dev, int n1, const float* y_dev, int n2, int64_t 
     }
     hipLaunchKernelGGL(kid_final_kernel, dim3(1), dim3(64), 0, s, sums, n1, n2, out_dev);
     FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
+static int moments_dim_check(const char* who, int64_t dim) {
+    if (dim < 1 || dim > FC_FRECHET_MAX_SMALL) return fail(FC_E_SHAPE, std::string(who) + ": 1 <= dim <= 4096");
+    return FC_OK;
+}
+
+int fc_frechet_moments_update(const float* x_dev, int nb, int dim, int64_t n_before, double* mean_inout_dev, double* m_inout_dev, void* ws_dev,
+                              void* stream) {
+    if (!x_dev || !mean_inout_dev || !m_inout_dev || !ws_dev) return fail(FC_E_ARG, "fc_frechet_moments_update: null argument");
+    FC_TRY(moments_dim_check("fc_frechet_moments_update", dim));
+    if (nb < 1 || nb > FC_GRAM_MAX_ROWS || n_before < 0) return fail(FC_E_SHAPE, "fc_frechet_moments_update: 1 <= nb <= 65536 and n_before >= 0");
+    if (fr_misaligned(x_dev, 4) || fr_misaligned(mean_inout_dev, 8) || fr_misaligned(m_inout_dev, 8) || fr_misaligned(ws_dev, 16))
+        return fail(FC_E_ARG, "fc_frechet_moments_update: a pointer that is not naturally aligned (the workspace: 16 bytes)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(ws_dev);
+    const MomentsUpdateWs w = moments_update_ws_layout(dim);
+    double* mean_b = reinterpret_cast<double*>(ws + w.mean_b);
+    double* delta = reinterpret_cast<double*>(ws + w.delta);
+    FC_TRY(moments_launch(x_dev, nb, dim, mean_b, reinterpret_cast<double*>(ws + w.part), reinterpret_cast<double*>(ws + w.scalars), s));
+    const int first = n_before == 0;
+    const double total = (double)n_before + (double)nb;
+    hipLaunchKernelGGL(mean_merge_kernel, dim3(cdiv(dim, 256)), dim3(256), 0, s, mean_b, dim, (double)nb / total, first, mean_inout_dev, delta);
+    FC_HIP(hipGetLastError());
+    ScatterArgs g = {};
+    g.x = x_dev; g.mb = mean_b; g.delta = delta; g.nb = nb; g.dim = dim;
+    g.w = (double)n_before * (double)nb / total; g.m = m_inout_dev; g.first = first;
+    const int tiles = cdiv(dim, GR_T);
+    hipLaunchKernelGGL(scatter_kernel, dim3(tiles * (tiles + 1) / 2), dim3(GR_THREADS), 0, s, g);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
+int fc_frechet_moments_merge(int dim, int64_t n_a, double* mean_a_inout_dev, double* m_a_inout_dev, int64_t n_b, const double* mean_b_dev,
+                             const double* m_b_dev, void* ws_dev, void* stream) {
+    if (!mean_a_inout_dev || !m_a_inout_dev || !mean_b_dev || !m_b_dev || !ws_dev) return fail(FC_E_ARG, "fc_frechet_moments_merge: null argument");
+    FC_TRY(moments_dim_check("fc_frechet_moments_merge", dim));
+    if (n_a < 0 || n_b < 1) return fail(FC_E_SHAPE, "fc_frechet_moments_merge: n_a >= 0 and n_b >= 1");
+    if (fr_misaligned(mean_a_inout_dev, 8) || fr_misaligned(m_a_inout_dev, 8) || fr_misaligned(mean_b_dev, 8) || fr_misaligned(m_b_dev, 8) ||
+        fr_misaligned(ws_dev, 16))
+        return fail(FC_E_ARG, "fc_frechet_moments_merge: a pointer that is not naturally aligned (the workspace: 16 bytes)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* delta = static_cast<double*>(ws_dev);
+    const int first = n_a == 0;
+    const double total = (double)n_a + (double)n_b;
+    hipLaunchKernelGGL(mean_merge_kernel, dim3(cdiv(dim, 256)), dim3(256), 0, s, mean_b_dev, dim, (double)n_b / total, first, mean_a_inout_dev, delta);
+    FC_HIP(hipGetLastError());
+    const long long count = (long long)dim * dim;
+    hipLaunchKernelGGL(scatter_merge_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, m_b_dev, delta, dim,
+                       (double)n_a * (double)n_b / total, first, m_a_inout_dev);
+    FC_HIP(hipGetLastError());
+    return FC_OK;
+}
+
+int fc_frechet_moments_factor(int dim, int64_t n, const double* m_dev, double* factor_out_dev, double* evals_out_dev, double* trace_out_dev,
+                              void* ws_dev, int* sweeps_out_host, int* converged_out_host, int64_t* launches_out_host, void* stream) {
+    if (!m_dev || !factor_out_dev || !evals_out_dev || !trace_out_dev || !ws_dev || !sweeps_out_host || !converged_out_host)
+        return fail(FC_E_ARG, "fc_frechet_moments_factor: null argument");
+    FC_TRY(moments_dim_check("fc_frechet_moments_factor", dim));
+    if (n < 2) return fail(FC_E_SHAPE, "fc_frechet_moments_factor: a covariance needs n >= 2 samples");
+    if (fr_misaligned(m_dev, 8) || fr_misaligned(factor_out_dev, 8) || fr_misaligned(evals_out_dev, 8) || fr_misaligned(trace_out_dev, 8) ||
+        fr_misaligned(ws_dev, 16))
+        return fail(FC_E_ARG, "fc_frechet_moments_factor: a pointer that is not naturally aligned (the workspace: 16 bytes)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(ws_dev);
+    const JacobiWs w = jacobi_ws_layout(dim);
+    double* alpha = reinterpret_cast<double*>(ws + w.alpha);
+    double* fro2 = reinterpret_cast<double*>(ws + w.scalars);
+    const double scale = 1.0 / (double)(n - 1);
+    const long long count = (long long)dim * dim;
+    hipLaunchKernelGGL(scale_copy_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, m_dev, count, scale, factor_out_dev);
+    FC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(256), 0, s, m_dev, dim, scale, trace_out_dev);
+    FC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sq_norms_kernel, dim3(dim), dim3(256), 0, s, factor_out_dev, dim, alpha);
+    FC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, alpha, (long long)dim, fro2);
+    FC_HIP(hipGetLastError());
+    long long launches = 0;
+    FC_TRY(jacobi_run(factor_out_dev, dim, dim, fro2, ws, evals_out_dev, nullptr, sweeps_out_host, converged_out_host, &launches, s));
+    hipLaunchKernelGGL(factor_scale_kernel, dim3(dim), dim3(256), 0, s, factor_out_dev, dim, alpha);   // alpha: the final norms, jacobi_run's
+    FC_HIP(hipGetLastError());
+    if (launches_out_host) *launches_out_host = launches + 5;
+    return FC_OK;
+}
+
+int fc_frechet_moments_distance(int dim, const double* mean1_dev, const double* factor1_dev, const double* trace1_dev, const double* mean2_dev,
+                                const double* factor2_dev, const double* trace2_dev, void* ws_dev, double* out_dev, double* svals_out_dev,
+                                int* sweeps_out_host, int* converged_out_host, int64_t* launches_out_host, void* stream) {
+    if (!mean1_dev || !factor1_dev || !trace1_dev || !mean2_dev || !factor2_dev || !trace2_dev || !ws_dev || !out_dev || !sweeps_out_host ||
+        !converged_out_host)
+        return fail(FC_E_ARG, "fc_frechet_moments_distance: null argument");
+    FC_TRY(moments_dim_check("fc_frechet_moments_distance", dim));
+    if (fr_misaligned(mean1_dev, 8) || fr_misaligned(factor1_dev, 8) || fr_misaligned(trace1_dev, 8) || fr_misaligned(mean2_dev, 8) ||
+        fr_misaligned(factor2_dev, 8) || fr_misaligned(trace2_dev, 8) || fr_misaligned(out_dev, 8) || fr_misaligned(svals_out_dev, 8) ||
+        fr_misaligned(ws_dev, 16))
+        return fail(FC_E_ARG, "fc_frechet_moments_distance: a pointer that is not naturally aligned (the workspace: 16 bytes)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(ws_dev);
+    const MomentsDistanceWs w = moments_distance_ws_layout(dim);
+    double* z = reinterpret_cast<double*>(ws + w.g);
+    double* part = reinterpret_cast<double*>(ws + w.part);
+    double* sc = reinterpret_cast<double*>(ws + w.scalars);         // {dm2, nuclear, fro2}
+    hipLaunchKernelGGL(mean_diff2_kernel, dim3(1), dim3(256), 0, s, mean1_dev, mean2_dev, (long long)dim, sc);
+    FC_HIP(hipGetLastError());
+    GramArgsT<double> g = {};
+    g.a = factor1_dev; g.b = factor2_dev; g.n1 = dim; g.n2 = dim; g.dim = dim; g.scale = 1.0; g.c = z; g.part = part;
+    FC_TRY(gram_launch(g, false, s));
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, part, fr_tiles(dim, dim), sc + 2);
+    FC_HIP(hipGetLastError());
+    long long launches = 0;
+    FC_TRY(jacobi_run(z, dim, dim, sc + 2, ws + w.jacobi, svals_out_dev, sc + 1, sweeps_out_host, converged_out_host, &launches, s));
+    hipLaunchKernelGGL(moments_final_kernel, dim3(1), dim3(64), 0, s, sc, trace1_dev, trace2_dev, out_dev);
+    FC_HIP(hipGetLastError());
+    if (launches_out_host) *launches_out_host = launches + 4;
     return FC_OK;
 }
 

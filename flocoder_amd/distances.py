@@ -15,13 +15,26 @@ relative accuracy on the rank-deficient matrices that N < D gives.  DESIGN.md se
 - ``frechet_distance_sets(real, fake, return_info=False)`` -- FD as a Python float; with ``return_info`` also a dict (``sweeps``,
   ``converged``, ``launches``, ``mean_term``, ``trace_real``, ``trace_fake``, ``nuclear``, ``svals``);
 - ``kernel_distance(real, fake)`` -- the unbiased MMD^2 with k(x, y) = (x.y / D + 1)^3 over ALL pairs (no random subsets).
+- ``FrechetMoments`` and ``frechet_distance_moments(a, b, return_info=False)`` -- the moment form for N >> D, below.
 
 Samples of any shape are flattened per row.  2 <= N; min(N1, N2) <= 4096 and max(N1, N2) <= 16384 for the Frechet distance, N <= 16384
 for the kernel distance.  A solve that does not converge (a non-finite input, or 30 sweeps) raises RuntimeError.  Sums run in a fixed
 order: a call repeated gives the same bits.  CPU tensors raise.
 
-Not built: the moment form for N >> D, random-subset KID, distances across ranks, a one-launch solve for matrices that fit LDS
-(DESIGN.md section 7)."""
+The moment form, for sets too large to hold (a standard FID: tens of thousands of samples, statistics of the real set kept).  A
+``FrechetMoments`` keeps ``n``, the fp64 ``mean`` [D] and ``M`` = sum (x - mean)(x - mean)^T [D, D] of everything it has been fed,
+batch by batch (each batch's centred scatter on the fp64 matrix pipe, joined by Chan's pairwise rule -- no raw second moments, so a
+mean far from zero costs nothing), can be merged with another and saved.  ``factor()`` is F with F^T F = S = M / (n - 1), from the
+same Jacobi iteration run on S itself; then tr sqrt(S1 S2) = ||F1 F2^T||_* and
+
+    FD = |m1 - m2|^2 + tr S1 + tr S2 - 2 ||F1 F2^T||_*        (one D x D fp64 Gram and a third Jacobi solve)
+
+D <= 4096, any N >= 2.  No D x D matrix leaves the device and nothing calls LAPACK.  Use it when N > D on both sides.  For N <= D the
+covariance is singular, its zero eigenvalues come back as rounding noise of size u ||S|| and their square roots, of size sqrt(u), enter
+the factor: the sample form above keeps its relative accuracy there and is the right tool (DESIGN.md section 4 has both bounds).
+
+Not built: random-subset KID, distances across ranks (``merge`` makes that an all-gather), a two-solve variant through F1 S2 F1^T, a
+one-launch solve for matrices that fit LDS, D > 4096."""
 import ctypes as C
 
 import torch
@@ -137,3 +150,141 @@ def kernel_distance(real, fake):
         ws = _workspace(B.FC_WS_KID, x.shape[0], y.shape[0], x.shape[1], dev)
         B.check(B.lib().fc_kid_sets(B.ptr(x), x.shape[0], B.ptr(y), y.shape[0], x.shape[1], B.ptr(ws), B.ptr(out), B.current_stream(dev)))
     return out[0].item()
+
+
+class FrechetMoments:
+    """Running fp64 statistics of a sample set on the device: ``n``, ``mean`` [D] and ``M`` = sum (x - mean)(x - mean)^T [D, D].
+
+    ``update(feats)`` takes a batch of rows (any shape, flattened per row, cast to fp32; the first call fixes ``dim`` and the device),
+    ``merge(other)`` another state's samples.  ``covariance()`` is M / (n - 1), ``trace()`` its trace as a Python float, ``factor()``
+    ``(F, eigenvalues, info)`` with F^T F = covariance, cached until the next ``update`` / ``merge`` / ``load_state_dict``."""
+
+    def __init__(self):
+        self.n, self.dim, self.mean, self.M = 0, None, None, None
+        self._factor = None
+
+    def _like(self, *shape):
+        return torch.empty(*shape, dtype=torch.float64, device=self.mean.device)
+
+    def update(self, feats):
+        x = _rows(feats, "feats")
+        nb, dim = x.shape
+        if nb < 1 or not 1 <= dim <= MAX_SMALL:
+            raise ValueError(f"flocoder_amd.distances.FrechetMoments: a batch is [rows >= 1, 1 <= features <= {MAX_SMALL}], got {tuple(x.shape)}")
+        if self.dim is None:
+            self.dim = dim
+            self.mean = torch.empty(dim, dtype=torch.float64, device=x.device)
+            self.M = torch.empty(dim, dim, dtype=torch.float64, device=x.device)
+        elif dim != self.dim:
+            raise ValueError(f"flocoder_amd.distances.FrechetMoments: the state has {self.dim} features, the batch {dim}")
+        elif x.device != self.mean.device:
+            raise ValueError("flocoder_amd.distances.FrechetMoments: the batch is on another device than the state")
+        self._factor = None
+        with torch.cuda.device(x.device):
+            for r0 in range(0, nb, B.FC_GRAM_MAX_ROWS):
+                part = x[r0:r0 + B.FC_GRAM_MAX_ROWS]
+                ws = _workspace(B.FC_WS_MOMENTS_UPDATE, part.shape[0], 1, dim, x.device)
+                B.check(B.lib().fc_frechet_moments_update(B.ptr(part), part.shape[0], dim, self.n, B.ptr(self.mean), B.ptr(self.M), B.ptr(ws),
+                                                          B.current_stream(x.device)))
+                self.n += part.shape[0]
+        return self
+
+    def merge(self, other):
+        if not isinstance(other, FrechetMoments):
+            raise TypeError("flocoder_amd.distances.FrechetMoments.merge: other must be a FrechetMoments")
+        if other.n == 0:
+            return self
+        if self.dim is None:
+            self.dim, self.mean, self.M = other.dim, torch.empty_like(other.mean), torch.empty_like(other.M)
+        elif other.dim != self.dim:
+            raise ValueError(f"flocoder_amd.distances.FrechetMoments.merge: {self.dim} features against {other.dim}")
+        elif other.mean.device != self.mean.device:
+            raise ValueError("flocoder_amd.distances.FrechetMoments.merge: the states are on different devices")
+        self._factor = None
+        dev = self.mean.device
+        with torch.cuda.device(dev):
+            ws = _workspace(B.FC_WS_MOMENTS_MERGE, 1, 1, self.dim, dev)
+            B.check(B.lib().fc_frechet_moments_merge(self.dim, self.n, B.ptr(self.mean), B.ptr(self.M), other.n, B.ptr(other.mean), B.ptr(other.M),
+                                                     B.ptr(ws), B.current_stream(dev)))
+        self.n += other.n
+        return self
+
+    def _need(self, rows, what):
+        if self.n < rows:
+            raise ValueError(f"flocoder_amd.distances.FrechetMoments: {what} needs at least {rows} sample(s), the state has {self.n}")
+
+    def covariance(self):
+        self._need(2, "a covariance")
+        return self.M * (1.0 / (self.n - 1))                             # the factor's own scaling: factor() reproduces exactly this matrix
+
+    def trace(self):
+        self._need(2, "a covariance")
+        return float(self.M.diagonal().sum() / (self.n - 1)) if self._factor is None else float(self._factor[3])
+
+    def factor(self):
+        """``(F [D, D], eigenvalues [D] descending, info)``: F^T F = covariance(); ``info`` has ``sweeps``, ``converged``, ``launches`` and
+        ``trace`` (a 1-element device tensor).  Raises RuntimeError when the solve did not converge."""
+        self._need(2, "a factor")
+        if self._factor is None:
+            dev = self.mean.device
+            f, ev, tr = self._like(self.dim, self.dim), self._like(self.dim), self._like(1)
+            sweeps, converged, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
+            with torch.cuda.device(dev):
+                ws = _workspace(B.FC_WS_MOMENTS_FACTOR, 1, 1, self.dim, dev)
+                B.check(B.lib().fc_frechet_moments_factor(self.dim, self.n, B.ptr(self.M), B.ptr(f), B.ptr(ev), B.ptr(tr), B.ptr(ws),
+                                                          C.byref(sweeps), C.byref(converged), C.byref(launches), B.current_stream(dev)))
+            if not converged.value:
+                raise RuntimeError(f"flocoder_amd.distances.FrechetMoments.factor: the eigenvalues did not converge in {sweeps.value} sweep(s) "
+                                   f"(a non-finite sample, or the cap of {MAX_SWEEPS} sweeps)")
+            self._factor = (f, ev, {"sweeps": sweeps.value, "converged": True, "launches": launches.value, "trace": tr}, tr)
+        return self._factor[:3]
+
+    def state_dict(self):
+        if self.dim is None:
+            raise ValueError("flocoder_amd.distances.FrechetMoments.state_dict: the state is empty")
+        return {"n": torch.tensor(self.n, dtype=torch.int64), "mean": self.mean.clone(), "M": self.M.clone()}
+
+    def load_state_dict(self, sd, device=None):
+        n, mean, m = int(sd["n"]), sd["mean"], sd["M"]
+        if mean.dim() != 1 or m.shape != (mean.shape[0], mean.shape[0]) or not 1 <= mean.shape[0] <= MAX_SMALL or n < 1:
+            raise ValueError("flocoder_amd.distances.FrechetMoments.load_state_dict: n >= 1, mean [D], M [D, D], D <= 4096")
+        device = device or (mean.device if mean.is_cuda else "cuda")
+        self.n, self.dim = n, mean.shape[0]
+        self.mean = mean.to(device=device, dtype=torch.float64).contiguous().clone()
+        self.M = m.to(device=device, dtype=torch.float64).contiguous().clone()
+        self._factor = None
+        return self
+
+
+def frechet_distance_moments(a, b, return_info=False):
+    """The Frechet distance between the sets two ``FrechetMoments`` have seen (unbiased covariances), a Python float; ``(value, info)``
+    with ``return_info``: ``sweeps`` (of a's factor, b's factor and the product), ``converged``, ``launches``, ``mean_term``,
+    ``trace_real``, ``trace_fake``, ``nuclear``, ``svals``.  A factor already cached is not computed again."""
+    for s, name in ((a, "a"), (b, "b")):
+        if not isinstance(s, FrechetMoments):
+            raise TypeError(f"flocoder_amd.distances.frechet_distance_moments: {name} must be a FrechetMoments")
+        s._need(2, f"the distance ({name})")
+    if a.dim != b.dim:
+        raise ValueError(f"flocoder_amd.distances.frechet_distance_moments: a has {a.dim} features, b {b.dim}")
+    if a.mean.device != b.mean.device:
+        raise ValueError("flocoder_amd.distances.frechet_distance_moments: a and b are on different devices")
+    cached = (a._factor is not None, b._factor is not None)
+    (fa, _, ia), (fb, _, ib) = a.factor(), b.factor()
+    dev, dim = a.mean.device, a.dim
+    out = torch.empty(6, dtype=torch.float64, device=dev)
+    svals = torch.empty(dim, dtype=torch.float64, device=dev) if return_info else None
+    sweeps, converged, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
+    with torch.cuda.device(dev):
+        ws = _workspace(B.FC_WS_MOMENTS_DISTANCE, 1, 1, dim, dev)
+        B.check(B.lib().fc_frechet_moments_distance(dim, B.ptr(a.mean), B.ptr(fa), B.ptr(ia["trace"]), B.ptr(b.mean), B.ptr(fb), B.ptr(ib["trace"]),
+                                                    B.ptr(ws), B.ptr(out), B.ptr(svals), C.byref(sweeps), C.byref(converged), C.byref(launches),
+                                                    B.current_stream(dev)))
+    if not converged.value:
+        raise RuntimeError(f"flocoder_amd.distances.frechet_distance_moments: the singular values did not converge in {sweeps.value} sweep(s) "
+                           f"(the cap of {MAX_SWEEPS} sweeps)")
+    fd, dm2, t1, t2, nuc, _ = out.tolist()
+    if not return_info:
+        return fd
+    spent = launches.value + (0 if cached[0] else ia["launches"]) + (0 if cached[1] else ib["launches"])
+    return fd, {"sweeps": (ia["sweeps"], ib["sweeps"], sweeps.value), "converged": True, "launches": spent, "mean_term": dm2, "trace_real": t1,
+                "trace_fake": t2, "nuclear": nuc, "svals": svals}

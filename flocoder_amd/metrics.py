@@ -272,10 +272,23 @@ def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
 def fid_score(real, fake, device='cuda', chunk=False, inception=None, chunk_size=256, solver="eig"):
     """metrics.py:266-308.  ``inception``: a callable uint8 [B,3,H,W] -> features, or a TorchScript path (see load_feature_extractor).
     ``solver="jacobi"`` keeps the extractor's features on the device and returns ``distances.frechet_distance_sets`` of them (no F x F
-    covariance, no host eigenvalues; sample counts within that function's limits); ``"eig"`` is the moment form above."""
-    if solver not in ("eig", "jacobi"):
-        raise ValueError(f"fid_score: solver must be 'eig' or 'jacobi', got {solver!r}")
+    covariance, no host eigenvalues; sample counts within that function's limits); ``"eig"`` is the moment form above.
+    ``solver="moments"`` feeds every chunk's features straight into two ``distances.FrechetMoments`` and returns
+    ``distances.frechet_distance_moments`` of them: the features are never held, any number of samples, at most 4096 features."""
+    if solver not in ("eig", "jacobi", "moments"):
+        raise ValueError(f"fid_score: solver must be 'eig', 'jacobi' or 'moments', got {solver!r}")
     net = inception if callable(inception) else load_feature_extractor(inception, device)
+    if solver == "moments":
+        from . import distances as D
+        states = (D.FrechetMoments(), D.FrechetMoments())
+        step = chunk_size if chunk else max(real.shape[0], fake.shape[0])
+        for side, imgs in enumerate((real, fake)):
+            for i in range(0, imgs.shape[0], step):
+                u8 = to_uint8(imgs[i:i + step].to(device))
+                if u8.shape[1] == 1:
+                    u8 = u8.repeat(1, 3, 1, 1)
+                states[side].update(net(u8))
+        return D.frechet_distance_moments(states[0], states[1])
     if solver == "jacobi":
         from . import distances as D
         step = chunk_size if chunk else max(real.shape[0], fake.shape[0])

@@ -815,6 +815,10 @@ int fc_knn_ball_counts(const float* q_dev, int n_query, const float* ref_dev, in
 #define FC_WS_JACOBI 2
 #define FC_WS_FRECHET 3
 #define FC_WS_KID 4
+#define FC_WS_MOMENTS_UPDATE 5      /* the moment form's workspaces: dim as given, n1 and n2 are not looked at beyond 1 .. 65536 */
+#define FC_WS_MOMENTS_MERGE 6
+#define FC_WS_MOMENTS_FACTOR 7
+#define FC_WS_MOMENTS_DISTANCE 8
 /* Sets are fp32 [rows][dim] row-major on the device; every result is fp64.  All sums run in a fixed order (per-workgroup partials added by a
  * second launch, no floating-point atomics): the same bits run to run.  Everything runs on `stream` and allocates nothing; workspaces
  * are the caller's, 16-byte aligned, of the workspace-bytes function's size for the kind (FC_WS_*) and the call's own n1, n2, dim
@@ -838,7 +842,24 @@ int fc_knn_ball_counts(const float* q_dev, int n_query, const float* ref_dev, in
  *   2 <= n1, n2; min(n1, n2) <= 4096; max(n1, n2) <= 16384; dim >= 1.
  * fc_kid_sets: out_dev [4] = {MMD^2, sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)}, k(x, y) = (x.y / dim + 1)^3,
  *   MMD^2 = sum_xx / (n1 (n1 - 1)) + sum_yy / (n2 (n2 - 1)) - 2 sum_xy / (n1 n2): three Gram launches whose epilogue reduces.
- *   2 <= n1, n2 <= 16384. */
+ *   2 <= n1, n2 <= 16384.
+ *
+ * The moment form of the Frechet distance, for sets with far more samples than features (1 <= dim <= 4096).  The state of a set is its
+ * sample count (the caller's, on the host), mean [dim] and M [dim][dim] = sum_i (x_i - mean)(x_i - mean)^T, fp64, full and bit-symmetric.
+ * fc_frechet_moments_update: takes the batch x_dev [nb][dim] into a state of n_before samples by Chan's pairwise rule: with mean_b and
+ *   M_b the batch's own mean and centred scatter (fp32 rows centred in fp64 on load, fp64 matrix pipe, lower-triangle tiles, each tile
+ *   and its mirror written by one workgroup), d = mean_b - mean and N = n_before + nb: M += M_b + (n_before nb / N) d d^T,
+ *   mean += (nb / N) d.  n_before = 0 stores instead (mean and M need no initialisation).  1 <= nb <= 65536.  ws_dev: FC_WS_MOMENTS_UPDATE.
+ * fc_frechet_moments_merge: the same rule with the second state (n_b >= 1, mean_b, m_b) in the batch's place; n_a = 0 copies.
+ *   ws_dev: FC_WS_MOMENTS_MERGE.
+ * fc_frechet_moments_factor: from a state of n >= 2 samples, S = M / (n - 1): factor_out_dev [dim][dim] = F with F^T F = S (the rows
+ *   of S rotated by fc_jacobi_svals' iteration until orthogonal, z_i = lambda_i v_i^T, each divided by the square root of its norm;
+ *   zero rows stay zero; row order is the iteration's), evals_out_dev [dim] = the row norms = the eigenvalues of S, descending,
+ *   *trace_out_dev = tr S (the diagonal's sum).  sweeps / converged as fc_jacobi_svals.  ws_dev: FC_WS_MOMENTS_FACTOR.
+ * fc_frechet_moments_distance: out_dev [6] = {FD, |m1 - m2|^2, tr S1, tr S2, ||F1 F2^T||_*, ||F1 F2^T||_F^2},
+ *   FD = |m1 - m2|^2 + tr S1 + tr S2 - 2 ||F1 F2^T||_* (tr sqrt(S1 S2) = ||F1 F2^T||_*): one dim x dim fp64 Gram of the two factors' rows
+ *   and one Jacobi solve.  trace1_dev / trace2_dev: one fp64 each, as fc_frechet_moments_factor left them.  svals_out_dev: NULL or
+ *   [dim].  ws_dev: FC_WS_MOMENTS_DISTANCE. */
 int64_t fc_frechet_workspace_bytes(int what, int n1, int n2, int64_t dim);
 int fc_gram_f64(const float* a_dev, int n1, const float* b_dev, int n2, int64_t dim, const double* mean_a_dev, const double* mean_b_dev,
                 double scale, double* c_out_dev, double* fro2_out_dev, void* ws_dev, void* stream);
@@ -848,6 +869,15 @@ int fc_jacobi_svals(double* z_inout_dev, int n, int r, double* svals_out_dev, do
 int fc_frechet_sets(const float* x_dev, int n1, const float* y_dev, int n2, int64_t dim, void* ws_dev, double* out_dev, double* svals_out_dev,
                     int* sweeps_out_host, int* converged_out_host, int64_t* launches_out_host, void* stream);
 int fc_kid_sets(const float* x_dev, int n1, const float* y_dev, int n2, int64_t dim, void* ws_dev, double* out_dev, void* stream);
+int fc_frechet_moments_update(const float* x_dev, int nb, int dim, int64_t n_before, double* mean_inout_dev, double* m_inout_dev, void* ws_dev,
+                              void* stream);
+int fc_frechet_moments_merge(int dim, int64_t n_a, double* mean_a_inout_dev, double* m_a_inout_dev, int64_t n_b, const double* mean_b_dev,
+                             const double* m_b_dev, void* ws_dev, void* stream);
+int fc_frechet_moments_factor(int dim, int64_t n, const double* m_dev, double* factor_out_dev, double* evals_out_dev, double* trace_out_dev,
+                              void* ws_dev, int* sweeps_out_host, int* converged_out_host, int64_t* launches_out_host, void* stream);
+int fc_frechet_moments_distance(int dim, const double* mean1_dev, const double* factor1_dev, const double* trace1_dev, const double* mean2_dev,
+                                const double* factor2_dev, const double* trace2_dev, void* ws_dev, double* out_dev, double* svals_out_dev,
+                                int* sweeps_out_host, int* converged_out_host, int64_t* launches_out_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Piano rolls and MIDI  (flocoder/pianoroll.py: img2midi_multi, and the painting of get_piano_rolls + piano_roll_to_img; DESIGN.md
